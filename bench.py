@@ -6,7 +6,7 @@ One "step" = one hb_step_dev call = one physics step of every env of this rank's
 state and controls already resident in HBM.  Before anything is timed every env is rolled through
 PREROLL (600) untimed steps of the same workload, so that a short timed window (the driver runs
 --steps 20) samples the steady regime — the humanoids on the floor, about ten constraint rows per
-env — and not the contact-free fall that follows the reset.  The CPU leg times the same window.
+env — and not the contact-free fall that follows the reset.  The CPU leg (--full) times the same window.
 The timed loop runs with hb_batch_pipeline on.  Its K hb_step_dev calls are enqueued back to back, nothing else in between - the
 reference's own loop, mj_step after mj_step (simulation/mujoco/sample/testspeed.cc:93-96) - and for this workload the library runs such
 calls as launches of up to 256 steps of the two-envs-per-wave kernel, step t on the controls of call t (include/hb.h: hb_step_dev;
@@ -15,8 +15,15 @@ those launches themselves: they run one after the other on the batch's stream, s
 their number (hb_batch_step_launches) is the launch duration the rocprofv3 kernel trace shows.  Where the library does not fold (fewer
 envs, other models, --duo 0, --no-pipeline) each call enqueues the batch as three env segments on three streams, so that the slow tail
 of one step overlaps the next (tests/test_gpu_parity.py::test_pipelined_stepping_is_bit_identical), and the roofline object is measured
-on a second, unpipelined leg (one launch per step, HIP events on the launch stream) - which is always run and reported as
+on a second, unpipelined leg (one launch per step, HIP events on the launch stream) - which --full runs and reports as
 roofline.single_step.
+
+A plain run sets up, pre-rolls, warms up, times the K steps, writes the outputs of the last timed step if --dump-outputs DIR is
+given, and prints the result line.  Everything else it can measure - the single-step roofline leg, the rollout, Newton and team-robot
+legs, the CPU baseline and the libmujoco probe - runs only with --full (the --no-* options then drop single legs of it).
+--dump-outputs DIR writes the state every env holds after the last timed step, as a caller of hb_step_dev reads it back (float32:
+time, qpos, qvel, qacc_warmstart; envs in global order), to DIR/<name>.npy; the inputs are fixed (Halton-perturbed reset, Halton
+controls), so two builds run with the same arguments can be compared output for output.
 
 Launching.  `python3 bench.py --gpus N`: with WORLD_SIZE unset the parent process — before it makes
 any HIP or torch call — starts N children of itself, one per GPU (RANK / LOCAL_RANK / WORLD_SIZE /
@@ -43,6 +50,7 @@ ENVS_PER_GPU = 4096
 PREROLL = 600                  # untimed steps from the reset before any measurement (the fall takes ~300)
 ALGO_BYTES_PER_ENV_STEP = 748  # fp32 x [read qpos 28 + qvel 27 + warmstart 27 + ctrl 21 + time 1; write 28+27+27+1]
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: beyond this, a fixed seeded sample of envs is written
 
 
 def shard_range(n_total, world, rank):
@@ -199,6 +207,22 @@ def load_traffic(kernel=None):
     return None
 
 
+def dump_outputs(path, parts):
+    """--dump-outputs: every rank's {name: array over its envs} (rank order) -> path/<name>.npy, envs in global order.  Above
+    DUMP_MAX_BYTES a fixed, seeded sample of envs is written, with their indices as env_index.npy."""
+    import numpy as np
+    out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+    n = len(out["qpos"])
+    per_env = sum(v[0].nbytes for v in out.values())
+    if n * per_env > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // (per_env + 8), replace=False))
+        out = {k: v[keep] for k, v in out.items()}
+        out["env_index"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -206,6 +230,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
     ap.add_argument("--preroll", type=int, default=PREROLL, help="untimed steps from the reset before any measurement")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure: the single-step roofline leg, the rollout, Newton and "
+                    "team-robot measurements, the CPU baseline and the libmujoco probe (the --no-* options below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the state of every env after the last one to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rollout", action="store_true", help="skip the second (single-launch rollout) measurement, e.g. under rocprofv3")
     ap.add_argument("--no-newton", action="store_true", help="skip the third measurement (same workload with the reference's default solver, Newton)")
@@ -338,30 +365,37 @@ def main():
                     "kernel": timed_kernel, "launches": timed_launches})
     status = batch.status()
     nc, ne, ni = batch.counts()
+    if args.dump_outputs:
+        parts = gather({"time": batch.get_state(hb.STATE_TIME)[:, 0], "qpos": batch.get_state(hb.STATE_QPOS), "qvel": batch.get_state(hb.STATE_QVEL),
+                        "qacc_warmstart": batch.get_state(hb.STATE_WARMSTART)})
+        if rank == 0:
+            dump_outputs(args.dump_outputs, parts)
 
-    # Roofline leg: the dominant kernel as ONE launch per step (all 4096 envs), unpipelined, continuing from
+    # Roofline leg (--full): the dominant kernel as ONE launch per step (all 4096 envs), unpipelined, continuing from
     # the state the timed loop left; HIP events around KR back-to-back launches on the launch stream.
     # (When the timed loop's calls were folded into multi-step launches, those launches ARE the roofline object's - they run back to back
     # on the batch's stream, inside the HIP events of the timed region - and this leg is reported beside them as `single_step`.)
-    batch.pipeline(False)
-    # (the library picks the kernel of a step call by the launch's shape: hold it to the one the timed loop ran)
-    batch.tune(duo=2 if "duo" in timed_kernel else 0)
-    KR = min(K, 200)
-    for t in range(5):
-        batch.step_dev(ctrl + (W + min(t, K - 1)) * stride)
-    batch.sync()
-    batch.timer_start()
-    for t in range(KR):
-        batch.step_dev(ctrl + (W + t) * stride)
-    launch_us = 1e3 * batch.timer_stop() / KR
-    roofline_kernel = batch.last_kernel()
-    batch.tune(duo=duo_default)
+    roofline_kernel = launch_us = KR = None
+    if args.full:
+        batch.pipeline(False)
+        # (the library picks the kernel of a step call by the launch's shape: hold it to the one the timed loop ran)
+        batch.tune(duo=2 if "duo" in timed_kernel else 0)
+        KR = min(K, 200)
+        for t in range(5):
+            batch.step_dev(ctrl + (W + min(t, K - 1)) * stride)
+        batch.sync()
+        batch.timer_start()
+        for t in range(KR):
+            batch.step_dev(ctrl + (W + t) * stride)
+        launch_us = 1e3 * batch.timer_stop() / KR
+        roofline_kernel = batch.last_kernel()
+        batch.tune(duo=duo_default)
 
     # Second measurement, reported beside `value`: the same K steps as ONE hb_rollout_dev launch (state
     # resident on chip, each env advancing through its own K steps without a per-step batch barrier) —
     # the shape of the reference's C++ harness simulation/mujoco/sample/testspeed.cc:84-103,203-210.
     elapsed_rollout = None
-    if not args.no_rollout:
+    if args.full and not args.no_rollout:
         preroll(batch)
         batch.rollout_dev(ctrl, W)
         barrier()
@@ -378,7 +412,7 @@ def main():
     # reference's own model file selects (none given = mjOption's default, Newton / 100 iterations) instead of the
     # benchmark configuration's PGS / 50.
     newton = None
-    if world == 1 and not args.no_newton:
+    if world == 1 and args.full and not args.no_newton:
         nm = hb.Model.load(os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "humanoid27.hbm"))
         nm.set_opt(solver=2, iterations=100)
         nb = hb.Batch(nm, n_env, device)
@@ -401,7 +435,7 @@ def main():
     # Fourth measurement (N = 1 only): the reference's OWN robot (simulation/assets/world.xml: mesh hulls, condim 6, height-field floor,
     # Newton, dt 0.002), same step API, from its standing reset after 200 settling steps, small random motor commands.
     team = None
-    if world == 1 and not args.no_team:
+    if world == 1 and args.full and not args.no_team:
         import numpy as np
         tm = hb.Model.load(os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "team_robot.hbm"))
         tb = hb.Batch(tm, n_env, device)
@@ -476,7 +510,7 @@ def main():
         single_step = {"kernel": roofline_kernel, "avg_launch_us": launch_us, "launches": KR,
                        "achieved": ALGO_BYTES_PER_ENV_STEP * n_env / (launch_us * 1e-6) / 1e9,
                        "launch_shape": ("%d blocks x 64 lanes, two envs per block, one step per launch, unpipelined" % ((n_env + 1) // 2)) if "duo" in roofline_kernel
-                                       else "%d blocks x 64 lanes, one env per block, one step per launch, unpipelined" % n_env}
+                                       else "%d blocks x 64 lanes, one env per block, one step per launch, unpipelined" % n_env} if args.full else None
         if folded:
             steps_per_launch = K / timed_launches
             roofline_kernel = timed_kernel
@@ -485,12 +519,31 @@ def main():
             KR = timed_launches
             launch_shape = "%d blocks x 64 lanes, two envs per block, %s steps per launch (the timed loop's hb_step_dev calls, folded), one launch after the other on the batch's stream" % (
                 (n_env + 1) // 2, ("%d" % steps_per_launch) if steps_per_launch == int(steps_per_launch) else ("%.1f" % steps_per_launch))
-        else:
+        elif single_step is not None:
             steps_per_launch = 1
             algo_per_launch = ALGO_BYTES_PER_ENV_STEP * n_env
             launch_shape = single_step["launch_shape"] + " leg"
-        achieved = algo_per_launch / (launch_us * 1e-6) / 1e9
-        traffic = load_traffic(roofline_kernel)
+        # (a plain run whose step calls were not folded has no launches of its own to put on the roofline: that takes --full's leg)
+        traffic = roofline = None
+        if folded or single_step is not None:
+            achieved = algo_per_launch / (launch_us * 1e-6) / 1e9
+            traffic = load_traffic(roofline_kernel)
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                        "traffic": ((traffic or {}).get("hbm_bytes_per_step") * steps_per_launch) if (traffic or {}).get("hbm_bytes_per_step") else (traffic or {}).get("hbm_bytes_per_launch"),
+                        "kernel": roofline_kernel, "avg_launch_us": launch_us, "launches": KR, "steps_per_launch": steps_per_launch,
+                        "launch_shape": launch_shape,
+                        # the launches the TIMED loop makes
+                        "timed_shape": ({"kernel": timed_kernel, "launches": timed_launches, "steps_per_launch": steps_per_launch, "segments": 1, "ms_per_step": 1e3 * elapsed / K,
+                                         "what": "the roofline object's own launches: HIP events around the timed region / launches"} if folded else
+                                        {"kernel": timed_kernel, "launches": timed_launches, "segments": nseg, "envs_per_segment": [n_env * (c + 1) // nseg - n_env * c // nseg for c in range(nseg)],
+                                         "ms_per_step": 1e3 * elapsed / K,
+                                         "segment_launch_us_from_profile": (traffic or {}).get("segment_launch_us")}),
+                        "single_step": single_step,
+                        "timed_region_ms_per_step": region_ms / K,
+                        "algorithmic_bytes_per_launch": algo_per_launch,
+                        "note": "path is latency/VALU bound, not HBM bound (SURVEY.md §8d); see DESIGN.md"}
+            if single_step is None:
+                del roofline["single_step"]
         out = {
             "metric": "env-steps/sec (whole node), 27-DoF humanoid, 4096 envs/GPU",
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -504,23 +557,12 @@ def main():
                                       else (" (pipelined: %d env segments on %d streams)" % (nseg, nseg)) if pipelined else "", PRE, W, K),
                        "model": "27-DoF humanoid (assets/humanoid27.hbm)", "envs_per_gpu": n_env, "global_envs": n_env * world, "preroll_steps": PRE,
                        "sharding": "env blocks by rank, no collective"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": ((traffic or {}).get("hbm_bytes_per_step") * steps_per_launch) if (traffic or {}).get("hbm_bytes_per_step") else (traffic or {}).get("hbm_bytes_per_launch"),
-                         "kernel": roofline_kernel, "avg_launch_us": launch_us, "launches": KR, "steps_per_launch": steps_per_launch,
-                         "launch_shape": launch_shape,
-                         # the launches the TIMED loop makes
-                         "timed_shape": ({"kernel": timed_kernel, "launches": timed_launches, "steps_per_launch": steps_per_launch, "segments": 1, "ms_per_step": 1e3 * elapsed / K,
-                                          "what": "the roofline object's own launches: HIP events around the timed region / launches"} if folded else
-                                         {"kernel": timed_kernel, "launches": timed_launches, "segments": nseg, "envs_per_segment": [n_env * (c + 1) // nseg - n_env * c // nseg for c in range(nseg)],
-                                          "ms_per_step": 1e3 * elapsed / K,
-                                          "segment_launch_us_from_profile": (traffic or {}).get("segment_launch_us")}),
-                         "single_step": single_step,
-                         "timed_region_ms_per_step": region_ms / K,
-                         "algorithmic_bytes_per_launch": algo_per_launch,
-                         "note": "path is latency/VALU bound, not HBM bound (SURVEY.md §8d); see DESIGN.md"},
+            "roofline": roofline,
             "state_check": {"envs_with_warnings": int((status != 0).sum()), "mean_ncon": float(nc.mean()), "mean_nefc": float(ne.mean()),
                             "mean_pgs_iters": float(ni.mean())},
         }
+        if roofline is None:
+            del out["roofline"]
         if traffic:
             out["roofline"]["traffic_source"] = "committed profile, not this run: " + str(traffic.get("source"))
             # what actually bounds the kernel (from the same PMC passes; informational): share of the chip's fp32 VALU
@@ -545,7 +587,7 @@ def main():
             out["newton"] = newton
         if team is not None:
             out["team_robot"] = team
-        if not args.no_cpu_baseline:  # (one number per box: rank 0, whatever N)
+        if args.full and not args.no_cpu_baseline:  # (one number per box: rank 0, whatever N)
             out["cpu_baseline"] = cpu_baseline()
             out["cpu_baseline"].update(probe_libmujoco())
         print(json.dumps(out), flush=True)

@@ -31,9 +31,11 @@ def test_fixture_is_what_the_generator_lifts(expect):
     import subprocess
     import sys
     before = open(GOLD, "rb").read()
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_mjpc_expectations.py")], stdout=subprocess.DEVNULL)
-    assert json.loads(str(np.load(GOLD)["manifest"])) == expect
-    open(GOLD, "wb").write(before)
+    try:
+        subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_mjpc_expectations.py")], stdout=subprocess.DEVNULL)
+        assert json.loads(str(np.load(GOLD)["manifest"])) == expect
+    finally:  # (the committed file stays as it was, whatever the generator wrote)
+        open(GOLD, "wb").write(before)
     assert len(expect["spline"]) == 27 and sum(len(c["samples"]) for c in expect["spline"]) == 59
 
 

@@ -119,24 +119,18 @@ def test_one_step_parity_in_both_contact_orders(hbmod, gpu, tmp_path, order):
     contact order.  The device mirrors whichever the model carries: one step from oracle states of the benchmark's steady regime (fallen
     humanoids: self collisions, several bodies on the floor) against the oracle on the same ordering - contacts in the same ORDER (geom
     ids row by row), same counts, qacc / forces to the one-step tolerances.  (profiles/r04_contact_order_modes.txt: how rarely the two
-    orders differ on this model, and by how much.)"""
+    orders differ on this model, and by how much.)  The states: tests/golden/contact_order_states.npz, every 8th step from 300 to 699 of an
+    oracle rollout of envs 1, 4 and 6 on the model in that order (tools/make_contact_order_states.py)."""
     m = hbmod.Model.load(HUMANOID_HBM)
     assert m.pair_order() == 1 and m.pair_order(order) == order
     p = str(tmp_path / ("order%d.hbm" % order))
     m.save(p)
     o = Oracle(p)
-    states, ctrls = [], []
-    for e in (1, 4, 6):
-        o.init_env(e)
-        for t in range(700):
-            c = o.ctrl_env(t, e)
-            o.ctrl[:] = c
-            if t >= 300 and t % 8 == 0:
-                states.append(np.concatenate([[o.time], o.qpos, o.qvel, o.qacc_warmstart])); ctrls.append(c.copy())
-            o.step()
-    n = len(states)
-    st = np.array(states).astype(np.float32).astype(np.float64)
-    ct = np.array(ctrls, dtype=np.float32)
+    g = np.load(os.path.join(GOLDEN, "contact_order_states.npz"))
+    st = g["state%d" % order].astype(np.float64)
+    ct = g["ctrl%d" % order]
+    n = len(st)
+    assert n == 150 and st.shape[1] == 1 + m.nq + 2 * m.nv and ct.dtype == np.float32
     b = hbmod.Batch(m, n, gpu)
     b.diag_enable(True)
     b.set_state(hbmod.STATE_INTEGRATION, st)
