@@ -613,6 +613,8 @@ struct hb_batch {
   EnvConfig env_cfg = {};
   bool env_ready = false;
   float *d_prev = nullptr, *d_latest = nullptr, *d_qfrc = nullptr, *d_action = nullptr;
+  float* d_inv = nullptr;  // hb_inverse's device copies: qacc [n_env][nv] | qfrc_inverse [n_env][nv] | warnings [n_env] (allocated by its first call)
+  int* d_inv_scratch = nullptr;  // hb_inverse_dev: the counts [n_env][kCountStride] | status [n_env] its launches write instead of the batch's
   int* d_episode = nullptr;
   int env_offset = 0;
   // realism layer (hb_env_randomize)
@@ -1127,7 +1129,7 @@ void hb_batch_free(hb_batch* b) {
   if (b->d_rmask) HB_IGN(hipFree(b->d_rmask));
   if (b->d_pending) HB_IGN(hipFree(b->d_pending));
   void* ptrs[] = {b->stage.geom, b->stage.item, b->stage.nsearch, b->stage.nwork, b->stage.result, b->stage.defer, b->d_term_obs, b->d_seen, b->d_state, b->d_ctrl, b->d_xfrc, b->d_diag_qacc, b->d_diag_force, b->d_diag_contact, b->d_obs, b->d_mask,
-                  b->d_status, b->d_counts, b->d_qpos_out, b->d_qvel_out, b->d_task_out, b->d_knots, b->d_order, b->d_order2, b->d_prev, b->d_latest, b->d_qfrc, b->d_action, b->d_episode};
+                  b->d_status, b->d_counts, b->d_qpos_out, b->d_qvel_out, b->d_task_out, b->d_knots, b->d_order, b->d_order2, b->d_prev, b->d_latest, b->d_qfrc, b->d_action, b->d_episode, b->d_inv, b->d_inv_scratch};
   for (void* p : ptrs) if (p) HB_IGN(hipFree(p));
   delete b;
 }
@@ -1269,6 +1271,47 @@ int hb_forward(hb_batch* b, const float* ctrl) {
   BatchPtrs P = make_ptrs(b);
   P.ctrl = b->d_ctrl; P.ctrl_mode = 0; P.integrate = 0;
   HB_HIP(launch_step(b->D.d_dm, b->D.dm.variant, b->D.dm.solver, b->D.dm.nv, b->D.dm.lds_floats, P, 1, main_stream(b))); b->last_kernel = last_step_kernel();
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  return HB_OK;
+}
+
+int hb_inverse_dev(hb_batch* b, const float* qacc_dev, int flags, float* qfrc_inverse_dev, int* warnings_dev) {
+  if (!b || !qacc_dev || !qfrc_inverse_dev || (flags & ~HB_INV_DISCRETE)) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined: the inverse sees the state they leave)
+  // a launch of its own, not make_ptrs: nothing of the batch's state, status, counts, orders or noise process is written
+  // (the pose and narrowphase kernels of a general variant write per-env counts and status bits: here into scratch, which the inverse
+  // kernel reads back into the warnings)
+  const size_t ncount = (size_t)b->n_env * kCountStride;
+  if (!b->d_inv_scratch && hipMalloc((void**)&b->d_inv_scratch, (ncount + (size_t)b->n_env) * sizeof(int)) != hipSuccess) { b->d_inv_scratch = nullptr; return HB_ENOMEM; }
+  HB_HIP(hipMemsetAsync(b->d_inv_scratch + ncount, 0, (size_t)b->n_env * sizeof(int), stream));
+  BatchPtrs P;
+  memset(&P, 0, sizeof P);
+  P.state = b->d_state; P.counts = b->d_inv_scratch; P.status = b->d_inv_scratch + ncount;
+  P.ctrl = b->d_ctrl;  // (never applied: mj_inverse leaves the actuators out)
+  P.n_env = b->n_env; P.blk0 = 0; P.nblk = b->n_env;
+  P.dr = b->d_dr; P.dr_stride = b->dr_stride;
+  P.stage = b->stage;  // general variants: the narrowphase of a staged step into the batch's stage buffers, which every step rewrites
+  P.stage.defer = nullptr; P.stage.defer_list = nullptr; P.stage.defer_count = nullptr; P.stage.dm_fast = nullptr; P.stage.fast_lds = 0;
+  P.inv_qacc = qacc_dev; P.inv_out = qfrc_inverse_dev; P.inv_warn = warnings_dev; P.inv_flags = flags;
+  HB_HIP(launch_inverse(b->D.d_dm, b->D.dm.variant, b->D.dm.nv, b->D.dm.lds_floats, P, stream));
+  b->last_kernel = last_step_kernel();
+  return HB_OK;
+}
+
+int hb_inverse(hb_batch* b, const float* qacc, int flags, float* qfrc_inverse, int* warnings) {
+  if (!b || !qacc || !qfrc_inverse || (flags & ~HB_INV_DISCRETE)) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  const size_t n = (size_t)b->n_env * b->D.dm.nv;
+  if (!b->d_inv && hipMalloc((void**)&b->d_inv, (2 * n + (size_t)b->n_env) * sizeof(float)) != hipSuccess) { b->d_inv = nullptr; return HB_ENOMEM; }
+  float* d_qacc = b->d_inv;
+  float* d_out = b->d_inv + n;
+  int* d_warn = reinterpret_cast<int*>(b->d_inv + 2 * n);
+  if (n) HB_HIP(hipMemcpyAsync(d_qacc, qacc, n * sizeof(float), hipMemcpyHostToDevice, main_stream(b)));
+  const int rc = hb_inverse_dev(b, d_qacc, flags, d_out, warnings ? d_warn : nullptr);
+  if (rc != HB_OK) return rc;
+  if (n) HB_HIP(hipMemcpyAsync(qfrc_inverse, d_out, n * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  if (warnings) HB_HIP(hipMemcpyAsync(warnings, d_warn, (size_t)b->n_env * sizeof(int), hipMemcpyDeviceToHost, main_stream(b)));
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   return HB_OK;
 }

@@ -357,6 +357,12 @@ struct BatchPtrs {
   const float* ctrl_tab[kFoldMax];  // ctrl_mode 3: step t of this launch is the step call whose [n_env][nu] controls these are (hb_api.cpp: fold_steps)
   int duo;                    // host side only (launch_step): two envs per wave 0 never, 1 where it pays, 2 always (hb_batch_duo)
   StageBufs stage;
+  // inverse dynamics (launch_inverse, the INV instantiations only): qacc [n_env][nv] in, qfrc_inverse [n_env][nv] out, the per-env
+  // HB_WARN_CONTACTFULL / HB_WARN_CNSTRFULL bits out (nullable), HB_INV_* flags; counts and status point at scratch in such a launch
+  const float* inv_qacc;
+  float* inv_out;
+  int* inv_warn;
+  int inv_flags;
 };
 
 }  // namespace hb

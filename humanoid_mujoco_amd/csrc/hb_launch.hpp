@@ -4,6 +4,8 @@
 #include "hb_device.hpp"
 namespace hb {
 hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int nv, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream);
+// inverse dynamics of the launch's envs (hb_inverse_dev; hb_step.hip)
+hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int lds_floats, const BatchPtrs& P, hipStream_t stream);
 // two envs per wave: a lean single-step launch of the 27-dof humanoid's PGS kernel (hb_step_duo.hip; chosen by launch_step)
 hipError_t launch_step_duo(const DevModel* M_dev, const BatchPtrs& P, int nsteps, hipStream_t stream);
 // name of the step kernel the last launch_step of this thread launched last (hb_last_kernel)

@@ -46,26 +46,28 @@ __device__ __forceinline__ void defer_env(const BatchPtrs& P, int env) {
     const int n_ = rr_ ? P.stage.defer_count[P.blk0] : (int)gridDim.x;                                      \
     for (int i_ = (int)blockIdx.x; i_ < n_; i_ += (int)gridDim.x) step_body<__VA_ARGS__>(Mp, P, nsteps, rr_ ? P.stage.defer_list[P.blk0 + i_] : -1); \
   } while (0)
-template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0>
+// INV: inverse dynamics (hb_inverse, mj_inverse): the forward stages up to the per-row quantities without the actuators and xfrc_applied,
+// then qfrc_inverse in place of the solver, the integrator and every write of the batch's state, status or counts (nsteps is 1)
+template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0, int INV = 0>
 __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P, int nsteps_in, int env_in = -1) {
   const int nsteps = LEAN == 1 ? 1 : nsteps_in;  // (LEAN == 1 is launched for single steps only: the step API; rollouts take LEAN == 2)
   // LEAN (1 = a single step without the constraint-force read-out; 2 = any number of steps, read-out optional): a launch without the optional inputs and outputs (applied forces and their noise, constraint-force / sensor / trajectory
   // read-outs, diagnostics, per-env model parameters, an env mask; mj_step, not mj_forward) - known at compile time, so their tests,
   // pointers and code are not in the kernel at all
-  float* const P_xfrc = LEAN ? nullptr : P.xfrc;
+  float* const P_xfrc = (LEAN || INV) ? nullptr : P.xfrc;
   const float P_xfrc_scale = LEAN ? 0.f : P.xfrc_scale, P_xfrc_rate = LEAN ? 0.f : P.xfrc_rate;
   const auto P_xfrc_seed = P.xfrc_seed; const auto P_xfrc_call = P.xfrc_call;
-  float* const P_qfrc_out = LEAN == 1 ? nullptr : P.qfrc_out;  // (LEAN == 2: the lean kernel of the env adapter, whose reward reads the constraint forces)
-  float* const P_sensor_out = LEAN ? nullptr : P.sensor_out;
-  float* const P_qpos_out = LEAN ? nullptr : P.qpos_out;
-  float* const P_qvel_out = LEAN ? nullptr : P.qvel_out;
-  float* const P_diag_qacc = LEAN ? nullptr : P.diag_qacc;
-  float* const P_diag_force = LEAN ? nullptr : P.diag_force;
-  float* const P_diag_contact = LEAN ? nullptr : P.diag_contact;
+  float* const P_qfrc_out = (LEAN == 1 || INV) ? nullptr : P.qfrc_out;  // (LEAN == 2: the lean kernel of the env adapter, whose reward reads the constraint forces)
+  float* const P_sensor_out = (LEAN || INV) ? nullptr : P.sensor_out;
+  float* const P_qpos_out = (LEAN || INV) ? nullptr : P.qpos_out;
+  float* const P_qvel_out = (LEAN || INV) ? nullptr : P.qvel_out;
+  float* const P_diag_qacc = (LEAN || INV) ? nullptr : P.diag_qacc;
+  float* const P_diag_force = (LEAN || INV) ? nullptr : P.diag_force;
+  float* const P_diag_contact = (LEAN || INV) ? nullptr : P.diag_contact;
   const float* const P_dr = LEAN ? nullptr : P.dr;
   const int P_dr_stride = LEAN ? 0 : P.dr_stride;
-  const unsigned char* const P_env_mask = LEAN ? nullptr : P.env_mask;
-  const int P_integrate = LEAN ? 1 : P.integrate;
+  const unsigned char* const P_env_mask = (LEAN || INV) ? nullptr : P.env_mask;
+  const int P_integrate = INV ? 0 : LEAN ? 1 : P.integrate;
   static_assert(SIZED == 0 || (NG == 1 && ((NDENSE == 28 && (COLL == 0 || SOLVER == 0)) || (NDENSE == 20 && COLL == 1 && SOLVER == 2))), "the size-specialised instantiations: the humanoid (classic or variant-1 layout) and the robot (Newton, variant-1 layout)");
   static_assert(NG == 1 || SOLVER == 2 || (COLL == 1 && NG == kPgsGroups && DEFER == 0), "PGS on more than one row group: the general variant's kPgsGroups instantiation");
   constexpr int kNR = NG == 1 ? kNefcMax : 64 * NG;  // row capacity of this instantiation
@@ -604,7 +606,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       s_smooth[d] = passive - bias;
     }
     gsync();
-    if (!(M_disableflags & (1 << 10))) {
+    if (!INV && !(M_disableflags & (1 << 10))) {  // (mj_inverse: the actuator forces are not part of qfrc_inverse)
       for (int a = lane; a < HB_SZ(nu); a += kGroup) {
         if (a != lane) { const float4 HB_CONST* AR4 = M.arec + (size_t)a * 4; pf_a0 = AR4[0]; pf_a1 = AR4[1]; pf_a2 = AR4[2]; pf_a3 = AR4[3]; }  // (more than 64 actuators)
         const int qa = __float_as_int(pf_a0.z), da = __float_as_int(pf_a0.w);
@@ -1073,6 +1075,57 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     float R = Rg[0], Dd = Ddg[0], aref = arefg[0], jw = jwg[0], force = 0.f, bvec = 0.f;
     (void)R; (void)bvec; (void)jw;
     gsync();
+    if constexpr (INV) {
+      // ---------------------------------------------------------------- mj_inverse (mj_invConstraint, mj_rne with acceleration)
+      //   qfrc_inverse = M qacc - qfrc_smooth - J' f,   f_i = -D_i jar_i where jar_i = J_i qacc - aref_i < 0, else 0
+      // with qfrc_smooth = qfrc_passive - qfrc_bias (no actuators, no xfrc_applied in this instantiation).  Discrete (HB_INV_DISCRETE):
+      // the caller's qacc is (qvel' - qvel) / h of the damped Euler step, H qacc = M qacc_c with H = M + h B, so the continuous
+      // acceleration is qacc_c = qacc + M^-1 (h B qacc).  Dof vectors mirrored in both halves (lane l and l + 32: dof l & 31).
+      const int li = lane & 31;
+      const float qd = li < nv ? P.inv_qacc[(size_t)env * nv + li] : 0.f;
+      float qc = qd;
+      if ((P.inv_flags & 1) && eulerdamp) {
+        const float rhs = li < nv ? M.timestep * M.dof_damping[li] * qd : 0.f;
+        float x;
+        if constexpr (NDENSE <= 28) {
+          x = sym_solve_mfma<NDENSE / 2>(load_sym_pairs<0>(M, s_qLD, lane0), rhs, lane);
+        } else {
+          f32x2 Mr[16];
+#pragma unroll
+          for (int j = 0; j < 32; j++) Mr[j >> 1][j & 1] = s_qLD[M.mdense[j * 32 + li]].x;
+          const float dv = chol_rows<NDENSE>(Mr, s_v1, li, lane);  // (its pivot line: s_v1 and s_v2)
+          x = rdlane_mirror(chol_solve_rows<NDENSE>(Mr, dv, rhs), lane);
+        }
+        qc = li < nv ? qd + x : 0.f;
+      }
+      if (lane < nv) s_v0[lane] = qc;
+      gsync();
+      // the row forces (lane = row, rows l + 64 g)
+#pragma unroll
+      for (int g = 0; g < NG; g++) {
+        const int row = lane + 64 * g;
+        if (64 * g < nefc && actg[g]) {
+          const float* Jr = s_C + row * cs;
+          float jq = 0.f, jq2 = 0.f;
+          int k = 0;
+          for (; k + 2 <= nv; k += 2) { jq = __builtin_fmaf(Jr[k], s_v0[k], jq); jq2 = __builtin_fmaf(Jr[k + 1], s_v0[k + 1], jq2); }
+          if (k < nv) jq = __builtin_fmaf(Jr[k], s_v0[k], jq);
+          const float jar = jq + jq2 - arefg[g];
+          s_force[row] = jar < 0.f ? -Ddg[g] * jar : 0.f;
+        }
+      }
+      gsync();
+      if (lane < nv) {
+        float Ma = 0.f, qfc = 0.f;
+#pragma unroll 8
+        for (int j = 0; j < 32; j++) Ma = __builtin_fmaf(s_qLD[M.mdense[j * 32 + lane]].x, j < nv ? s_v0[j] : 0.f, Ma);
+        for (int i = 0; i < nefc; i++) qfc = __builtin_fmaf(s_force[i], s_C[i * cs + lane], qfc);
+        P.inv_out[(size_t)env * nv + lane] = Ma - s_smooth[lane] - qfc;
+      }
+      // HB_WARN_CONTACTFULL | HB_WARN_CNSTRFULL, with those of the launch's own narrowphase (general variants: P.status is scratch here)
+      if (P.inv_warn && lane == 0) P.inv_warn[env] = (status | (COLL != 0 ? P.status[env] : 0)) & ((1 << 1) | (1 << 2));
+      return;
+    }
     HB_STAMP(10);
     int niter = 0;
     float newton_grad = 0.f;  // Newton: gradient left at the solution (lane = dof); enters the damped Euler solve
@@ -1884,6 +1937,14 @@ __global__ __launch_bounds__(kGroup, 2) void hb_step_newton_gen20_team_kernel(co
 __global__ __launch_bounds__(kGroup, 2) void hb_step_gen_fast_h27_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28, 1, 1, 2, 1, 1>(Mp, P, nsteps); }
 __global__ __launch_bounds__(kGroup, 2) void hb_step_newton_gen20_lean_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 20, 1, 1, 1, 1>(Mp, P, nsteps); }
 __global__ __launch_bounds__(kGroup, 2) void hb_step_newton32_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 32>(Mp, P, nsteps); }
+// inverse dynamics (step_body's INV; hb_inverse): one per row capacity and dense order, with the stages of the model's variant.  The solver
+// template argument only selects the dense views (no solver runs); the general variants read the contacts of launch_pose_narrow (DEFER 2)
+__global__ __launch_bounds__(kGroup, 2) void hb_inverse_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 28, 0, 1, 0, 0, 0, 1>(Mp, P, 1); }
+__global__ __launch_bounds__(kGroup, 2) void hb_inverse32_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 32, 0, 1, 0, 0, 0, 1>(Mp, P, 1); }
+__global__ __launch_bounds__(kGroup, 2) void hb_inverse_gen_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 28, 1, 1, 2, 0, 0, 1>(Mp, P, 1); }
+__global__ __launch_bounds__(kGroup, 1) void hb_inverse_pgs_big_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 28, 1, kPgsGroups, 2, 0, 0, 1>(Mp, P, 1); }
+__global__ __launch_bounds__(kGroup, 1) void hb_inverse_big20_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 20, 1, kBigGroups, 2, 0, 0, 1>(Mp, P, 1); }
+__global__ __launch_bounds__(kGroup, 1) void hb_inverse_big28_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 28, 1, kBigGroups, 2, 0, 0, 1>(Mp, P, 1); }
 
 // every step-kernel launch leaves its kernel's name behind (hb_last_kernel: tests and bench.py name the kernel they measured by what the
 // library says it launched, not by a literal)
@@ -2013,6 +2074,25 @@ hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int nv, i
   if (fast_name) g_last_step_kernel = fast_name;
   return hipSuccess;
 }
+
+// Inverse dynamics of every env in the launch (hb_inverse_dev): a general variant's poses and narrowphase first, as in a staged step,
+// then the inverse instantiation of the variant's row capacity
+hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int lds_floats, const BatchPtrs& P, hipStream_t stream) {
+  const size_t shmem = (size_t)lds_floats * sizeof(float);
+  if (variant != 0) {
+    const hipError_t e = launch_pose_narrow(M_dev, P, stream);
+    if (e != hipSuccess) return e;
+  }
+  (void)hipGetLastError();
+  const dim3 grid(P.nblk), block(kGroup);
+  if (variant == 1) HB_STEP_LAUNCH(hb_inverse_gen_kernel, grid, block, shmem, stream, M_dev, P);
+  else if (variant == 2 && nv <= 20) HB_STEP_LAUNCH(hb_inverse_big20_kernel, grid, block, shmem, stream, M_dev, P);
+  else if (variant == 2) HB_STEP_LAUNCH(hb_inverse_big28_kernel, grid, block, shmem, stream, M_dev, P);
+  else if (variant == 3) HB_STEP_LAUNCH(hb_inverse_pgs_big_kernel, grid, block, shmem, stream, M_dev, P);
+  else if (nv <= 28) HB_STEP_LAUNCH(hb_inverse_kernel, grid, block, shmem, stream, M_dev, P);
+  else HB_STEP_LAUNCH(hb_inverse32_kernel, grid, block, shmem, stream, M_dev, P);
+  return hipGetLastError();
+}
 hipError_t set_step_lds_limit(int bytes) {
   hipError_t e = hipFuncSetAttribute((const void*)hb_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e != hipSuccess) return e;
@@ -2036,6 +2116,11 @@ hipError_t set_step_lds_limit(int bytes) {
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)hb_step_newton_big28_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e != hipSuccess) return e;
+  for (const void* k : {(const void*)hb_inverse_kernel, (const void*)hb_inverse32_kernel, (const void*)hb_inverse_gen_kernel, (const void*)hb_inverse_pgs_big_kernel,
+                        (const void*)hb_inverse_big20_kernel, (const void*)hb_inverse_big28_kernel}) {
+    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return e;
+  }
   return hipFuncSetAttribute((const void*)hb_step_newton32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 

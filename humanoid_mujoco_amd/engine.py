@@ -20,6 +20,7 @@ WARN_CONTACTFULL, WARN_CNSTRFULL, WARN_BADQPOS, WARN_BADQVEL, WARN_BADQACC = 1 <
 STATE_TIME, STATE_QPOS, STATE_QVEL, STATE_WARMSTART, STATE_XFRC_APPLIED = 1 << 0, 1 << 1, 1 << 2, 1 << 4, 1 << 7
 STATE_PHYSICS = STATE_QPOS | STATE_QVEL
 STATE_INTEGRATION = STATE_TIME | STATE_QPOS | STATE_QVEL | STATE_WARMSTART
+HB_INV_DISCRETE = 1  # hb_inverse flags: mjENBL_INVDISCRETE
 
 # mjtDisableBit (simulation/mujoco/include/mujoco/mjmodel.h:50-68)
 DSBL_CONSTRAINT, DSBL_LIMIT, DSBL_CONTACT, DSBL_PASSIVE, DSBL_GRAVITY = 1 << 0, 1 << 3, 1 << 4, 1 << 5, 1 << 6
@@ -140,6 +141,8 @@ def lib():
     L.hb_rollout_dev.argtypes = [vp, vp, ci, vp]
     L.hb_rollout_halton.argtypes = [vp, ci, ci, ci, vp]
     L.hb_forward.argtypes = [vp, vp]
+    L.hb_inverse.argtypes = [vp, vp, ci, vp, vp]
+    L.hb_inverse_dev.argtypes = [vp, vp, ci, vp, vp]
     L.hb_state_size.argtypes = [vp, cu]
     L.hb_get_state.argtypes = [vp, cu, vp]; L.hb_set_state.argtypes = [vp, cu, vp]
     L.hb_get_state_f64.argtypes = [vp, cu, vp]; L.hb_set_state_f64.argtypes = [vp, cu, vp]
@@ -370,6 +373,23 @@ class Batch:
     def forward(self, ctrl=None):
         c = None if ctrl is None else np.ascontiguousarray(ctrl, dtype=np.float32)
         _check(lib().hb_forward(self._h, _ptr(c)), "hb_forward")
+
+    def inverse(self, qacc, discrete=False, want_warnings=False):
+        """mj_inverse of every env at its current state (include/hb.h: hb_inverse): qacc float32 [n_env, nv] -> qfrc_inverse float32
+        [n_env, nv]; with want_warnings also the per-env HB_WARN_CONTACTFULL / HB_WARN_CNSTRFULL bits of rows this call dropped.
+        discrete: qacc is (qvel' - qvel) / h of one step (mjENBL_INVDISCRETE).  The batch's state is left as it is."""
+        a = np.ascontiguousarray(qacc, dtype=np.float32)
+        assert a.shape == (self.n_env, self.model.nv), a.shape
+        out = np.empty((self.n_env, self.model.nv), dtype=np.float32)
+        warn = np.zeros(self.n_env, dtype=np.int32) if want_warnings else None
+        _check(lib().hb_inverse(self._h, _ptr(a), HB_INV_DISCRETE if discrete else 0, _ptr(out), _ptr(warn)), "hb_inverse")
+        return (out, warn) if want_warnings else out
+
+    def inverse_dev(self, qacc_ptr, out_ptr, discrete=False, warnings_ptr=None):
+        """qacc_ptr / out_ptr: device addresses (int) of float32 [n_env, nv] arrays, warnings_ptr (nullable) of int32 [n_env];
+        asynchronous (hb_inverse_dev)."""
+        _check(lib().hb_inverse_dev(self._h, ctypes.c_void_p(qacc_ptr), HB_INV_DISCRETE if discrete else 0, ctypes.c_void_p(out_ptr),
+                                    ctypes.c_void_p(warnings_ptr) if warnings_ptr else None), "hb_inverse_dev")
 
     def rollout(self, ctrl, want_qpos=False):
         c = np.ascontiguousarray(ctrl, dtype=np.float32)

@@ -166,6 +166,21 @@ int hb_rollout_halton(hb_batch* b, int T, int t0, int env_offset, float* qpos_ou
 /* Replaces mj_forward (mujoco.h:129): recompute everything up to qacc without integrating. */
 int hb_forward(hb_batch* b, const float* ctrl);
 
+/* Replaces mj_inverse (mujoco.h, declared beside mj_forward) [recall]: the generalized forces that produce the given accelerations in every env,
+ *   qfrc_inverse = M qacc + qfrc_bias - qfrc_passive - J' f,   f_i = -D_i (J_i qacc - aref_i) where that is negative, else 0,
+ * with M (armature included), the bias and passive forces, the collisions, the constraint rows and their aref computed from the
+ * batch's qpos / qvel exactly as hb_forward computes them (per-env model parameters included).  ctrl and xfrc_applied do not enter:
+ * for the qacc of hb_forward, qfrc_inverse is qfrc_actuator + J' xfrc_applied.  qacc and qfrc_inverse are env-major [n_env][nv].
+ * flags HB_INV_DISCRETE (mjENBL_INVDISCRETE): qacc is (qvel' - qvel) / h of this engine's Euler step with implicit damping, and is
+ * turned into the continuous acceleration M^-1 (M + h diag(damping)) qacc first.  warnings (nullable) receives per env the
+ * HB_WARN_CONTACTFULL / HB_WARN_CNSTRFULL bits of rows this call dropped.  The call is a pure function of the batch: state, controls,
+ * xfrc_applied, status and warning words, env adapter and heavy-first orders are left as they are.  Step calls held back (hb_step_dev)
+ * are launched first and the pipes joined, as for every other call.  hb_last_kernel names the inverse kernel.
+ * hb_inverse is synchronous with host arrays; hb_inverse_dev takes device arrays and is asynchronous like hb_step_dev. */
+#define HB_INV_DISCRETE 1 /* mjENBL_INVDISCRETE */
+int hb_inverse(hb_batch* b, const float* qacc, int flags, float* qfrc_inverse, int* warnings);
+int hb_inverse_dev(hb_batch* b, const float* qacc_dev, int flags, float* qfrc_inverse_dev, int* warnings_dev);
+
 /* ---- wire format of a state ------------------------------------------------------------ */
 
 /* One env's state as the `State` message of the reference's gRPC agent service (mujoco_mpc/mjpc/grpc/agent.proto:75-83:
