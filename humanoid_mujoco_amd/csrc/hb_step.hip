@@ -2093,35 +2093,21 @@ hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int lds_fl
   else HB_STEP_LAUNCH(hb_inverse32_kernel, grid, block, shmem, stream, M_dev, P);
   return hipGetLastError();
 }
+// every step and inverse instantiation: a layout over 64 KB must launch whichever of them the dispatch picks (launch_step_kernel, launch_step)
 hipError_t set_step_lds_limit(int bytes) {
-  hipError_t e = hipFuncSetAttribute((const void*)hb_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step_newton28_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step_gen_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step_gen_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step_gen_fast1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step_gen_fast_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step_newton_gen20_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step_newton_gen28_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step_newton_big20_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute((const void*)hb_step_newton_big28_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e != hipSuccess) return e;
-  for (const void* k : {(const void*)hb_inverse_kernel, (const void*)hb_inverse32_kernel, (const void*)hb_inverse_gen_kernel, (const void*)hb_inverse_pgs_big_kernel,
+  for (const void* k : {(const void*)hb_step_kernel, (const void*)hb_step_lean_kernel, (const void*)hb_step_h27_kernel, (const void*)hb_step_h27_q_kernel,
+                        (const void*)hb_step_lean_q_kernel, (const void*)hb_step32_kernel, (const void*)hb_step_gen_kernel, (const void*)hb_step_gen_big_kernel,
+                        (const void*)hb_step_gen_fast1_kernel, (const void*)hb_step_gen_fast_kernel, (const void*)hb_step_gen_fast_lean_kernel,
+                        (const void*)hb_step_gen_fast_h27_kernel, (const void*)hb_step_newton_big20_kernel, (const void*)hb_step_newton_big28_kernel,
+                        (const void*)hb_step_newton_gen20_kernel, (const void*)hb_step_newton_gen20_lean_kernel, (const void*)hb_step_newton_gen20_team_kernel,
+                        (const void*)hb_step_newton_gen28_kernel, (const void*)hb_step_newton28_kernel, (const void*)hb_step_newton28_lean_kernel,
+                        (const void*)hb_step_newton28_h27_kernel, (const void*)hb_step_newton28_lean_q_kernel, (const void*)hb_step_newton32_kernel,
+                        (const void*)hb_inverse_kernel, (const void*)hb_inverse32_kernel, (const void*)hb_inverse_gen_kernel, (const void*)hb_inverse_pgs_big_kernel,
                         (const void*)hb_inverse_big20_kernel, (const void*)hb_inverse_big28_kernel}) {
-    e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) return e;
   }
-  return hipFuncSetAttribute((const void*)hb_step_newton32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return hipSuccess;
 }
 
 }  // namespace hb

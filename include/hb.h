@@ -369,9 +369,12 @@ long long hb_batch_step_launches(hb_batch* b);
 /* "<device name> (<gfx arch>, <n> CUs) #<index>" of the GPU the batch lives on: what every rank of a multi-GPU bench.py run reports about
  * itself (the reference's testspeed.cc prints its thread count: sample/testspeed.cc:203-210). */
 int hb_batch_device_name(const hb_batch* b, char* out, int cap);
-/* Run-time choices between kernels and schedules that give the SAME results (every one of them is held bit-identical to its alternative
- * by a test): for the tests that compare them and for measurements.  Takes effect from the next launch on.  Nothing of the reference
- * corresponds: mj_step (mujoco.h:120) has one code path.
+/* Run-time choices between kernels and schedules: for the tests that compare them and for measurements.  Takes effect from the next
+ * launch on.  Nothing of the reference corresponds: mj_step (mujoco.h:120) has one code path.  DUO, LEAN, SIZED, NARROW_PRIM, SCHEDULE
+ * and FOLD give the SAME results: a test holds each bit-identical to its alternative (tests/test_gpu_kernel_matrix.py, test_gpu_duo.py,
+ * test_gpu_fold.py).  STAGED, FASTPASS and POLICY_LEAN choose kernels that sum in other orders (one register group against two or four,
+ * the policy kernel's own arithmetic): their results differ by rounding, and tests hold them to the fp64 oracle or to each other within
+ * bounds instead (tests/test_gpu_kernel_matrix.py, test_gpu_staged.py, test_gpu_policy.py).
  *   HB_TUNE_DUO            two envs per wavefront for the lean launches of the 27-dof humanoid's PGS kernel (csrc/hb_step_duo.hip; DESIGN.md
  *                          3.8): 1 (default) where it pays - pipelined step calls of batches from 2.5 x the chip's wave slots on (5120 envs on
  *                          MI355X), unpipelined ones from 1.5 x (3072), launches of several steps from more than 1 x (2049); 0 never; 2 always
