@@ -772,6 +772,11 @@ int fork_pipes(hb_batch* b, int nseg) {
   b->forked = true;
   return HB_OK;
 }
+// the batch's model through launch_step; the launched kernel's name stays with the batch (hb_last_kernel)
+hipError_t launch_batch_step(hb_batch* b, const BatchPtrs& P, int nsteps, hipStream_t stream) {
+  const DevModel& dm = b->D.dm;
+  return launch_step(b->D.d_dm, dm.variant, dm.solver, dm.nv, dm.lds_floats, P, nsteps, stream, &b->last_kernel);
+}
 // one segment's launch of the step kernel, then (heavy-first scheduling, every 4th call) the tiny kernel that
 // orders the segment's next launch by the cost of this one; costs change slowly, and the sort sits on the
 // critical path of its stream
@@ -780,7 +785,7 @@ int launch_segment(hb_batch* b, BatchPtrs P, int nsteps, const Segment& sg, int 
   // a whole-batch permutation would mix segments: a segment only uses the order of its own envs
   P.order = (b->schedule && (nseg == 1 ? b->order_mode != 0 : b->order_mode == 2)) ? b->d_order : nullptr;
   P.order2 = (P.order && staged_on(b)) ? b->d_order2 : nullptr;
-  HB_HIP(launch_step(b->D.d_dm, b->D.dm.variant, b->D.dm.solver, b->D.dm.nv, b->D.dm.lds_floats, P, nsteps, sg.st)); b->last_kernel = last_step_kernel();
+  HB_HIP(launch_batch_step(b, P, nsteps, sg.st));
   // (the key of the counting sort is 8 bits of the cost: of a single step's rows x sweeps - up to ~ 1600 - the bits above the lowest three; of the
   // AVERAGE over a launch of several steps, which the two-envs-per-wave kernel leaves behind and pairs its envs by - 180 .. 700 -, one bit more)
   if (reorder) HB_HIP(launch_order(b->d_counts, b->d_order, b->n_env, sg.lo, sg.hi - sg.lo, sg.st, /*slot=*/3, /*shift=*/(nsteps >= 8 && b->D.dm.variant == 0) ? 2 : 3));
@@ -1270,7 +1275,7 @@ int hb_forward(hb_batch* b, const float* ctrl) {
   else if (n) HB_HIP(hipMemsetAsync(ctrl_for_write(b), 0, n * sizeof(float), main_stream(b)));
   BatchPtrs P = make_ptrs(b);
   P.ctrl = b->d_ctrl; P.ctrl_mode = 0; P.integrate = 0;
-  HB_HIP(launch_step(b->D.d_dm, b->D.dm.variant, b->D.dm.solver, b->D.dm.nv, b->D.dm.lds_floats, P, 1, main_stream(b))); b->last_kernel = last_step_kernel();
+  HB_HIP(launch_batch_step(b, P, 1, main_stream(b)));
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   return HB_OK;
 }
@@ -1294,8 +1299,7 @@ int hb_inverse_dev(hb_batch* b, const float* qacc_dev, int flags, float* qfrc_in
   P.stage = b->stage;  // general variants: the narrowphase of a staged step into the batch's stage buffers, which every step rewrites
   P.stage.defer = nullptr; P.stage.defer_list = nullptr; P.stage.defer_count = nullptr; P.stage.dm_fast = nullptr; P.stage.fast_lds = 0;
   P.inv_qacc = qacc_dev; P.inv_out = qfrc_inverse_dev; P.inv_warn = warnings_dev; P.inv_flags = flags;
-  HB_HIP(launch_inverse(b->D.d_dm, b->D.dm.variant, b->D.dm.nv, b->D.dm.lds_floats, P, stream));
-  b->last_kernel = last_step_kernel();
+  HB_HIP(launch_inverse(b->D.d_dm, b->D.dm.variant, b->D.dm.nv, b->D.dm.lds_floats, P, stream, &b->last_kernel));
   return HB_OK;
 }
 
@@ -1795,7 +1799,7 @@ static int rollout_rows(hb_batch* b, const float* ctrl, int H, const hb_sensor_s
   F.ctrl = b->d_ctrl + (H > 1 ? (size_t)(H - 2) * N * nu : 0); F.ctrl_mode = 0; F.integrate = 0;
   F.sensor_out = b->d_sensor_out + (size_t)(H - 1) * N * *stride;
   F.blk0 = 0; F.nblk = N;
-  HB_HIP(launch_step(b->D.d_dm, dm.variant, dm.solver, dm.nv, dm.lds_floats, F, 1, main_stream(b))); b->last_kernel = last_step_kernel();
+  HB_HIP(launch_batch_step(b, F, 1, main_stream(b)));
   return HB_OK;
 }
 
@@ -1939,7 +1943,7 @@ int hb_sensors(hb_batch* b, const float* ctrl, const hb_sensor_spec* spec, float
   P.ctrl = b->d_ctrl; P.ctrl_mode = 0; P.integrate = 0;
   int rc = sensor_setup(b, spec, 1, P);
   if (rc != HB_OK) return rc;
-  HB_HIP(launch_step(b->D.d_dm, b->D.dm.variant, b->D.dm.solver, b->D.dm.nv, b->D.dm.lds_floats, P, 1, main_stream(b))); b->last_kernel = last_step_kernel();
+  HB_HIP(launch_batch_step(b, P, 1, main_stream(b)));
   HB_HIP(hipMemcpyAsync(sensor_out, b->d_sensor_out, (size_t)b->n_env * P.sensor_stride * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   return HB_OK;

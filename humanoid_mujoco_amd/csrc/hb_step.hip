@@ -1904,53 +1904,78 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
 }
 
 #undef HB_SZ
-// PGS instantiations: dense order 28 (nv <= 28: the 27-dof humanoid; M^-1 by elimination on the matrix cores) and 32 (sparse L'DL)
-// (224 registers instead of the 229 the allocator would take - two values spilled - so that beside two of its waves a SIMD has 64
-// registers left: what the closed loop's policy kernel runs in, hb_policy_lean_kernel; amdgpu_num_vgpr counts per half of the file)
-__attribute__((amdgpu_num_vgpr(112))) __global__ __launch_bounds__(kGroup, 2) void hb_step_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28>(Mp, P, nsteps); }
-__attribute__((amdgpu_num_vgpr(112))) __global__ __launch_bounds__(kGroup, 2) void hb_step_lean_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28, 0, 1, 0, 1>(Mp, P, nsteps); }
-// (the single-step lean kernel with the sizes and the LDS layout of the reference's 27-dof humanoid as constants)
-__attribute__((amdgpu_num_vgpr(112))) __global__ __launch_bounds__(kGroup, 2) void hb_step_h27_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28, 0, 1, 0, 1, 1>(Mp, P, nsteps); }
-__attribute__((amdgpu_num_vgpr(112))) __global__ __launch_bounds__(kGroup, 2) void hb_step_h27_q_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28, 0, 1, 0, 2, 1>(Mp, P, nsteps); }
-__attribute__((amdgpu_num_vgpr(112))) __global__ __launch_bounds__(kGroup, 2) void hb_step_lean_q_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28, 0, 1, 0, 2>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step32_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 32>(Mp, P, nsteps); }
-// General instantiations (mesh hulls, height-field prisms, condim 4 / 6): PGS on 63 rows (configs[4]: the 27-dof humanoid on terrain),
-// Newton on 256 rows (the reference's own robot, simulation/assets/world.xml: 18 dofs -> dense order 20; up to 28 dofs)
-__global__ __launch_bounds__(kGroup, 2) void hb_step_gen_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_OR_RERUN(0, 28, 1, 1); }
-// PGS on kPgsNefcMax rows (AR in LDS: one env per CU) for condim 4 / 6 models, and the one-group fast pass that defers to it (variant 3)
-__global__ __launch_bounds__(kGroup, 1) void hb_step_gen_big_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_OR_RERUN(0, 28, 1, kPgsGroups); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_gen_fast1_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28, 1, 1, 1>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_gen_fast_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28, 1, 1, 2>(Mp, P, nsteps); }  // staged step, fast pass
-__global__ __launch_bounds__(kGroup, 1) void hb_step_newton_big20_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_OR_RERUN(2, 20, 1, kBigGroups); }
-__global__ __launch_bounds__(kGroup, 1) void hb_step_newton_big28_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_OR_RERUN(2, 28, 1, kBigGroups); }
-// fast pass of a variant-2 model's staged step: Newton on one row group, general collision results, deferring what does not fit
-__global__ __launch_bounds__(kGroup, 2) void hb_step_newton_gen20_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 20, 1, 1, 1>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_newton_gen28_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 28, 1, 1, 1>(Mp, P, nsteps); }
-// Newton instantiations: dense order 28 (nv <= 28: the 27-dof humanoid) and 32
-__global__ __launch_bounds__(kGroup, 2) void hb_step_newton28_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 28>(Mp, P, nsteps); }
-// lean instantiations (step_body's LEAN: no optional inputs / outputs in the launch) of the kernels the plain step API spends its time in
-__global__ __launch_bounds__(kGroup, 2) void hb_step_newton28_lean_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 28, 0, 1, 0, 1>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_newton28_h27_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 28, 0, 1, 0, 1, 1>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_newton28_lean_q_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 28, 0, 1, 0, 2>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_gen_fast_lean_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28, 1, 1, 2, 1>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_newton_gen20_team_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 20, 1, 1, 1, 1, 1>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_gen_fast_h27_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<0, 28, 1, 1, 2, 1, 1>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_newton_gen20_lean_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 20, 1, 1, 1, 1>(Mp, P, nsteps); }
-__global__ __launch_bounds__(kGroup, 2) void hb_step_newton32_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<2, 32>(Mp, P, nsteps); }
+// ---- The kernel table: one row per step_body instantiation.  The __global__ definitions, the host array the dispatch looks kernels up in
+// (select_step) and the kernels' names (hb_last_kernel) are all generated from these two lists.  RERUN: the second pass of a staged step,
+// a few waves that walk the list of deferred envs (HB_STEP_OR_RERUN).  VGPRS: amdgpu_num_vgpr, counted per half of the file (0: no cap).
+//  K(name,                             SOLVER, NDENSE, COLL, NG,         DEFER, LEAN, SIZED, INV, WAVES, VGPRS, RERUN)
+#define HB_STEP_KERNELS(K) /* (Mp, P, nsteps) */                                                                                           \
+  /* PGS: dense order 28 (nv <= 28: the 27-dof humanoid; M^-1 by elimination on the matrix cores) and 32 (sparse L'DL)                   */ \
+  /* (224 registers instead of the 229 the allocator would take - two values spilled - so that beside two of its waves a SIMD has 64     */ \
+  /* registers left: what the closed loop's policy kernel runs in, hb_policy_lean_kernel)                                                */ \
+  K(hb_step_kernel,                     0,      28,     0,    1,          0,     0,    0,     0,   2,     112,   0)                         \
+  K(hb_step_lean_kernel,                0,      28,     0,    1,          0,     1,    0,     0,   2,     112,   0)                         \
+  /* (the lean kernels with the sizes and the LDS layout of the reference's 27-dof humanoid as constants)                                */ \
+  K(hb_step_h27_kernel,                 0,      28,     0,    1,          0,     1,    1,     0,   2,     112,   0)                         \
+  K(hb_step_h27_q_kernel,               0,      28,     0,    1,          0,     2,    1,     0,   2,     112,   0)                         \
+  K(hb_step_lean_q_kernel,              0,      28,     0,    1,          0,     2,    0,     0,   2,     112,   0)                         \
+  K(hb_step32_kernel,                   0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
+  /* General (mesh hulls, height-field prisms, condim 4 / 6): PGS on 63 rows (configs[4]: the 27-dof humanoid on terrain), Newton on     */ \
+  /* 256 rows (the reference's own robot, simulation/assets/world.xml: 18 dofs -> dense order 20; up to 28 dofs)                         */ \
+  K(hb_step_gen_kernel,                 0,      28,     1,    1,          0,     0,    0,     0,   2,     0,     1)                         \
+  /* PGS on kPgsNefcMax rows (AR in LDS: one env per CU) for condim 4 / 6 models, and the one-group fast pass that defers to it          */ \
+  /* (variant 3); hb_step_gen_fast_kernel: the fast pass of a variant-1 staged step                                                      */ \
+  K(hb_step_gen_big_kernel,             0,      28,     1,    kPgsGroups, 0,     0,    0,     0,   1,     0,     1)                         \
+  K(hb_step_gen_fast1_kernel,           0,      28,     1,    1,          1,     0,    0,     0,   2,     0,     0)                         \
+  K(hb_step_gen_fast_kernel,            0,      28,     1,    1,          2,     0,    0,     0,   2,     0,     0)                         \
+  K(hb_step_newton_big20_kernel,        2,      20,     1,    kBigGroups, 0,     0,    0,     0,   1,     0,     1)                         \
+  K(hb_step_newton_big28_kernel,        2,      28,     1,    kBigGroups, 0,     0,    0,     0,   1,     0,     1)                         \
+  /* fast pass of a variant-2 model's staged step: Newton on one row group, general collision results, deferring what does not fit       */ \
+  K(hb_step_newton_gen20_kernel,        2,      20,     1,    1,          1,     0,    0,     0,   2,     0,     0)                         \
+  K(hb_step_newton_gen28_kernel,        2,      28,     1,    1,          1,     0,    0,     0,   2,     0,     0)                         \
+  /* Newton: dense order 28 (nv <= 28: the 27-dof humanoid) and 32                                                                       */ \
+  K(hb_step_newton28_kernel,            2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
+  /* lean instantiations (step_body's LEAN: no optional inputs / outputs in the launch) of the kernels the plain step API spends its     */ \
+  /* time in                                                                                                                             */ \
+  K(hb_step_newton28_lean_kernel,       2,      28,     0,    1,          0,     1,    0,     0,   2,     0,     0)                         \
+  K(hb_step_newton28_h27_kernel,        2,      28,     0,    1,          0,     1,    1,     0,   2,     0,     0)                         \
+  K(hb_step_newton28_lean_q_kernel,     2,      28,     0,    1,          0,     2,    0,     0,   2,     0,     0)                         \
+  K(hb_step_gen_fast_lean_kernel,       0,      28,     1,    1,          2,     1,    0,     0,   2,     0,     0)                         \
+  K(hb_step_newton_gen20_team_kernel,   2,      20,     1,    1,          1,     1,    1,     0,   2,     0,     0)                         \
+  K(hb_step_gen_fast_h27_kernel,        0,      28,     1,    1,          2,     1,    1,     0,   2,     0,     0)                         \
+  K(hb_step_newton_gen20_lean_kernel,   2,      20,     1,    1,          1,     1,    0,     0,   2,     0,     0)                         \
+  K(hb_step_newton32_kernel,            2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
 // inverse dynamics (step_body's INV; hb_inverse): one per row capacity and dense order, with the stages of the model's variant.  The solver
 // template argument only selects the dense views (no solver runs); the general variants read the contacts of launch_pose_narrow (DEFER 2)
-__global__ __launch_bounds__(kGroup, 2) void hb_inverse_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 28, 0, 1, 0, 0, 0, 1>(Mp, P, 1); }
-__global__ __launch_bounds__(kGroup, 2) void hb_inverse32_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 32, 0, 1, 0, 0, 0, 1>(Mp, P, 1); }
-__global__ __launch_bounds__(kGroup, 2) void hb_inverse_gen_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 28, 1, 1, 2, 0, 0, 1>(Mp, P, 1); }
-__global__ __launch_bounds__(kGroup, 1) void hb_inverse_pgs_big_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 28, 1, kPgsGroups, 2, 0, 0, 1>(Mp, P, 1); }
-__global__ __launch_bounds__(kGroup, 1) void hb_inverse_big20_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 20, 1, kBigGroups, 2, 0, 0, 1>(Mp, P, 1); }
-__global__ __launch_bounds__(kGroup, 1) void hb_inverse_big28_kernel(const DevModel* Mp, const BatchPtrs P) { step_body<2, 28, 1, kBigGroups, 2, 0, 0, 1>(Mp, P, 1); }
+#define HB_INVERSE_KERNELS(K) /* (Mp, P): a single step */                                                                                 \
+  K(hb_inverse_kernel,                  2,      28,     0,    1,          0,     0,    0,     1,   2,     0,     0)                         \
+  K(hb_inverse32_kernel,                2,      32,     0,    1,          0,     0,    0,     1,   2,     0,     0)                         \
+  K(hb_inverse_gen_kernel,              2,      28,     1,    1,          2,     0,    0,     1,   2,     0,     0)                         \
+  K(hb_inverse_pgs_big_kernel,          2,      28,     1,    kPgsGroups, 2,     0,    0,     1,   1,     0,     0)                         \
+  K(hb_inverse_big20_kernel,            2,      20,     1,    kBigGroups, 2,     0,    0,     1,   1,     0,     0)                         \
+  K(hb_inverse_big28_kernel,            2,      28,     1,    kBigGroups, 2,     0,    0,     1,   1,     0,     0)
 
-// every step-kernel launch leaves its kernel's name behind (hb_last_kernel: tests and bench.py name the kernel they measured by what the
-// library says it launched, not by a literal)
-static thread_local const char* g_last_step_kernel = "";
-const char* last_step_kernel() { return g_last_step_kernel; }
-#define HB_STEP_LAUNCH(kernel, ...) do { g_last_step_kernel = #kernel; hipLaunchKernelGGL(kernel, __VA_ARGS__); } while (0)
+// (the entry calls step_body directly: a forwarding function template in between changes register allocation and scheduling)
+#define HB_STEP_BODY_0(...) step_body<__VA_ARGS__>(Mp, P, nsteps)
+#define HB_STEP_BODY_1(...) HB_STEP_OR_RERUN(__VA_ARGS__)
+#define HB_DEFINE_STEP(name, S, ND, C, G, D, L, Z, I, W, V, R) \
+  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_BODY_##R(S, ND, C, G, D, L, Z, I); }
+#define HB_DEFINE_INVERSE(name, S, ND, C, G, D, L, Z, I, W, V, R) \
+  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P) { step_body<S, ND, C, G, D, L, Z, I>(Mp, P, 1); }
+HB_STEP_KERNELS(HB_DEFINE_STEP)
+HB_INVERSE_KERNELS(HB_DEFINE_INVERSE)
+
+struct StepConfig {
+  int solver, ndense, coll, ng, defer, lean, sized, inv;
+  bool operator==(const StepConfig& o) const { return solver == o.solver && ndense == o.ndense && coll == o.coll && ng == o.ng && defer == o.defer && lean == o.lean && sized == o.sized && inv == o.inv; }
+};
+struct StepKernel { const char* name; const void* fn; StepConfig cfg; bool rerun; };
+#define HB_STEP_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I}, R != 0},
+static const StepKernel kStepKernels[] = {HB_STEP_KERNELS(HB_STEP_ROW) HB_INVERSE_KERNELS(HB_STEP_ROW)};
+static const StepKernel* find_step_kernel(const StepConfig& c) {
+  for (const StepKernel& k : kStepKernels) if (k.cfg == c) return &k;
+  return nullptr;
+}
+
 // Two envs per wave (hb_step_duo.hip) for the lean launches of the 27-dof humanoid's PGS kernel - where it pays.  A duo wave takes ~ 1.6 x as
 // long as a one-env wave and holds two envs: 25 % more env-steps per wave-cycle.  But a single-step launch lasts as long as its slowest
 // wave, and the batch-wide barrier between step calls is hidden only while the launches in flight hold more waves than the chip has
@@ -1978,6 +2003,53 @@ static bool lean_launch(const BatchPtrs& P, bool with_qfrc = false) {
   return (P.lean_ok & 1) && !P.xfrc && (with_qfrc || !P.qfrc_out) && !P.sensor_out && !P.qpos_out && !P.qvel_out && !P.diag_qacc && !P.diag_force && !P.diag_contact && !P.dr && !P.env_mask &&
          P.integrate;
 }
+
+// Which kernel a launch gets: the main step kernel of the model's variant, the fast pass of a staged step (which for variants 2 and 3
+// runs on the one-group model StageBufs::dm_fast with its own LDS size: kernel, model and LDS size are chosen together), or the inverse.
+enum class StepPass { Main, Fast, Inverse };
+struct StepChoice { const StepKernel* kernel; bool duo; const DevModel* M_dev; size_t shmem; };  // (duo: launch_step_duo, no table row)
+static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant, int solver, int nv, size_t shmem, const BatchPtrs& P, int nsteps) {
+  StepConfig c = variant == 1   ? StepConfig{0, 28, 1, 1}
+                 : variant == 3 ? StepConfig{0, 28, 1, kPgsGroups}
+                 : variant == 2 ? StepConfig{2, nv <= 20 ? 20 : 28, 1, kBigGroups}
+                                : StepConfig{solver == 2 ? 2 : 0, nv <= 28 ? 28 : 32, 0, 1};
+  if (pass == StepPass::Inverse) {
+    c.solver = 2; c.defer = c.coll ? 2 : 0; c.inv = 1;
+    return {find_step_kernel(c), false, M_dev, shmem};
+  }
+  if (pass == StepPass::Fast) {
+    c.ng = 1; c.defer = variant == 1 ? 2 : 1;
+    if (variant != 1) { M_dev = P.stage.dm_fast; shmem = (size_t)P.stage.fast_lds; }
+  }
+  const bool sized_ok = P.lean_ok & (c.ndense == 20 ? 4 : 2);  // (the layout HB_SZ would take)
+  // (the two-envs-per-wave kernels write the joint torques when asked: the env adapter's launches take them as well)
+  if (!c.coll && c.solver == 0 && c.ndense == 28 && lean_launch(P, true) && sized_ok && duo_pays(P, nsteps)) return {nullptr, true, M_dev, shmem};
+  // LEAN 1: a single step without the constraint-force read-out; 2: any number of steps, read-out optional.  An instantiation that does
+  // not exist: the same without the sizes as constants, then the full kernel.
+  c.lean = (nsteps == 1 && lean_launch(P)) ? 1 : lean_launch(P, true) ? 2 : 0;
+  c.sized = c.lean && sized_ok;
+  const StepKernel* k = find_step_kernel(c);
+  if (!k && c.sized) { c.sized = 0; k = find_step_kernel(c); }
+  if (!k && c.lean) { c.lean = 0; k = find_step_kernel(c); }
+  return {k, false, M_dev, shmem};
+}
+// The one launch site.  Every launch hands back its kernel's name (hb_last_kernel: tests and bench.py name the kernel they measured by
+// what the library says it launched, not by a literal).
+static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, int variant, int solver, int nv, size_t shmem, const BatchPtrs& P, int nsteps, hipStream_t stream,
+                              const char** kernel) {
+  const StepChoice s = select_step(pass, M_dev, variant, solver, nv, shmem, P, nsteps);
+  if (s.duo) return launch_step_duo(s.M_dev, P, nsteps, stream, kernel);
+  if (!s.kernel) return hipErrorInvalidDeviceFunction;
+  (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
+  // (the second pass of a staged step: kRerunWaves waves that walk the list of deferred envs - HB_STEP_OR_RERUN)
+  constexpr int kRerunWaves = 1024;  // (one per SIMD: the four-group kernels hold one wave per SIMD)
+  const int grid = (s.kernel->rerun && P.stage.rerun && P.stage.defer_list && P.nblk > kRerunWaves) ? kRerunWaves : P.nblk;
+  void* args[] = {(void*)&s.M_dev, (void*)&P, &nsteps};  // (passed by value, as ever; the inverse kernels take the first two)
+  *kernel = s.kernel->name;
+  (void)hipLaunchKernel(s.kernel->fn, dim3(grid), dim3(kGroup), args, s.shmem, stream);
+  return hipGetLastError();
+}
+
 // Does it pay to run step calls the host has enqueued back to back as ONE launch of several steps (hb_api.cpp: fold_steps)?  When all the
 // launch's waves are on the chip at once: then no wave waits for a slot while others run through their steps, and no env waits for the
 // batch's slowest one between steps.  One-env waves: up to 8 per CU (2048 envs on MI355X: 42 us per step against 64 for pipelined single
@@ -1987,45 +2059,17 @@ static bool lean_launch(const BatchPtrs& P, bool with_qfrc = false) {
 bool fold_pays(int variant, int solver, int nv, const BatchPtrs& P) {
   if (variant != 0) return false;
   if (P.n_env <= wave_slots()) return true;
-  const bool duo_kernel = solver != 2 && nv <= 28 && lean_launch(P) && (P.lean_ok & 2) && duo_pays(P, 2);
+  // (would the folded launch be a duo launch?  Step calls that read the constraint forces out are not folded onto it)
+  const bool duo_kernel = !P.qfrc_out && select_step(StepPass::Main, nullptr, variant, solver, nv, 0, P, 2).duo;
   return duo_kernel && (P.n_env + 1) / 2 <= wave_slots();
-}
-static hipError_t launch_step_kernel(const DevModel* M_dev, int variant, int solver, int nv, size_t shmem, const BatchPtrs& P, int nsteps, hipStream_t stream) {
-  (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
-  // (the second pass of a staged step: kRerunWaves waves that walk the list of deferred envs - HB_STEP_OR_RERUN)
-  constexpr int kRerunWaves = 1024;  // (one per SIMD: the four-group kernels hold one wave per SIMD)
-  const int grid = (P.stage.rerun && P.stage.defer_list) ? (P.nblk < kRerunWaves ? P.nblk : kRerunWaves) : P.nblk;
-  if (variant == 2 && nv <= 20) HB_STEP_LAUNCH(hb_step_newton_big20_kernel, dim3(grid), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-  else if (variant == 2) HB_STEP_LAUNCH(hb_step_newton_big28_kernel, dim3(grid), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-  else if (variant == 1) HB_STEP_LAUNCH(hb_step_gen_kernel, dim3(grid), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-  else if (variant == 3) HB_STEP_LAUNCH(hb_step_gen_big_kernel, dim3(grid), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-  else if (solver == 2 && nv <= 28) {
-    if (nsteps == 1 && lean_launch(P) && (P.lean_ok & 2)) HB_STEP_LAUNCH(hb_step_newton28_h27_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-    else if (nsteps == 1 && lean_launch(P)) HB_STEP_LAUNCH(hb_step_newton28_lean_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-    else if (lean_launch(P, true)) HB_STEP_LAUNCH(hb_step_newton28_lean_q_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-    else HB_STEP_LAUNCH(hb_step_newton28_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-  }
-  else if (solver == 2) HB_STEP_LAUNCH(hb_step_newton32_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-  else if (nv <= 28) {
-    // (the two-envs-per-wave kernels write the joint torques when asked: the env adapter's launches take them as well)
-    if (lean_launch(P, true) && (P.lean_ok & 2) && duo_pays(P, nsteps)) { g_last_step_kernel = nsteps == 1 ? "hb_step_duo_kernel" : "hb_step_duo_q_kernel"; return launch_step_duo(M_dev, P, nsteps, stream); }
-    else if (nsteps == 1 && lean_launch(P) && (P.lean_ok & 2)) HB_STEP_LAUNCH(hb_step_h27_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-    else if (nsteps == 1 && lean_launch(P)) HB_STEP_LAUNCH(hb_step_lean_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-    else if (lean_launch(P, true) && (P.lean_ok & 2)) HB_STEP_LAUNCH(hb_step_h27_q_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-    else if (lean_launch(P, true)) HB_STEP_LAUNCH(hb_step_lean_q_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-    else HB_STEP_LAUNCH(hb_step_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-  }
-  else HB_STEP_LAUNCH(hb_step32_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, P, nsteps);
-  return hipGetLastError();
 }
 
 // One step launch of the classic variant covers all nsteps.  A general variant with stage buffers runs every step as three launches
 // on the same stream: poses + work items, narrowphase (a small kernel at 2-4x the step kernel's occupancy: its time is chains of
 // dependent loads along the hulls' edge graphs), then the step kernel, which appends the results instead of colliding.
-hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int nv, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream) {
+hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int nv, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel) {
   const size_t shmem = (size_t)lds_floats * sizeof(float);
-  if (variant == 0 || !P.stage.result) return launch_step_kernel(M_dev, variant, solver, nv, shmem, P, nsteps, stream);
-  const char* fast_name = nullptr;  // (a staged step is named after its fast-pass kernel: the one that steps almost every env)
+  if (variant == 0 || !P.stage.result) return launch_pass(StepPass::Main, M_dev, variant, solver, nv, shmem, P, nsteps, stream, kernel);
   for (int t = 0; t < nsteps; t++) {
     BatchPtrs Q = P;
     Q.t0 = P.t0 + t;
@@ -2035,34 +2079,18 @@ hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int nv, i
     if (P.sensor_out) Q.sensor_out = P.sensor_out + (size_t)t * P.n_env * P.sensor_stride;
     hipError_t e = launch_pose_narrow(M_dev, Q, stream);  // (hb_narrow.hip)
     if (e != hipSuccess) return e;
-    if (variant == 1 && Q.stage.defer) {
-      // the step kernel without the portal-search code; the full one then takes the (rare) env-steps whose qacc came out bad
-      if (lean_launch(Q) && (Q.lean_ok & 2)) HB_STEP_LAUNCH(hb_step_gen_fast_h27_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, Q, 1);
-      else if (lean_launch(Q)) HB_STEP_LAUNCH(hb_step_gen_fast_lean_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, Q, 1);
-      else HB_STEP_LAUNCH(hb_step_gen_fast_kernel, dim3(P.nblk), dim3(kGroup), shmem, stream, M_dev, Q, 1);
-      e = hipGetLastError();
+    // The fast pass, then the variant's own kernel for what it deferred.  Variant 1: the step kernel without the portal-search code; the
+    // full one then takes the (rare) env-steps whose qacc came out bad.  Variant 3 (PGS): the one-group kernel (63 rows, 24 contacts, two
+    // waves per SIMD) first; the kPgsNefcMax-row kernel then steps what it defers.  Variant 2: most env-steps fit the one-group Newton
+    // instantiation (two waves per SIMD); the four-group kernel then steps the rest.
+    const bool fast = variant == 1 ? Q.stage.defer != nullptr : Q.stage.dm_fast != nullptr;
+    const char* second = nullptr;  // (a staged step is named after its fast-pass kernel: the one that steps almost every env)
+    if (fast) {
+      e = launch_pass(StepPass::Fast, M_dev, variant, solver, nv, shmem, Q, 1, stream, kernel);
       if (e != hipSuccess) return e;
-      fast_name = g_last_step_kernel;
-      Q.stage.rerun = 1;
-    } else if (variant == 3 && Q.stage.dm_fast) {
-      // PGS: the one-group kernel (63 rows, 24 contacts, two waves per SIMD) first; the kPgsNefcMax-row kernel then steps what it defers
-      HB_STEP_LAUNCH(hb_step_gen_fast1_kernel, dim3(P.nblk), dim3(kGroup), (size_t)Q.stage.fast_lds, stream, Q.stage.dm_fast, Q, 1);
-      e = hipGetLastError();
-      if (e != hipSuccess) return e;
-      fast_name = g_last_step_kernel;
-      Q.stage.rerun = 1;
-    } else if (variant == 2 && Q.stage.dm_fast) {
-      // most env-steps fit the one-group Newton instantiation (two waves per SIMD); the four-group kernel then steps the rest
-      if (nv <= 20 && lean_launch(Q) && (Q.lean_ok & 4)) HB_STEP_LAUNCH(hb_step_newton_gen20_team_kernel, dim3(P.nblk), dim3(kGroup), (size_t)Q.stage.fast_lds, stream, Q.stage.dm_fast, Q, 1);
-      else if (nv <= 20 && lean_launch(Q)) HB_STEP_LAUNCH(hb_step_newton_gen20_lean_kernel, dim3(P.nblk), dim3(kGroup), (size_t)Q.stage.fast_lds, stream, Q.stage.dm_fast, Q, 1);
-      else if (nv <= 20) HB_STEP_LAUNCH(hb_step_newton_gen20_kernel, dim3(P.nblk), dim3(kGroup), (size_t)Q.stage.fast_lds, stream, Q.stage.dm_fast, Q, 1);
-      else HB_STEP_LAUNCH(hb_step_newton_gen28_kernel, dim3(P.nblk), dim3(kGroup), (size_t)Q.stage.fast_lds, stream, Q.stage.dm_fast, Q, 1);
-      e = hipGetLastError();
-      if (e != hipSuccess) return e;
-      fast_name = g_last_step_kernel;
       Q.stage.rerun = 1;
     }
-    e = launch_step_kernel(M_dev, variant, solver, nv, shmem, Q, 1, stream);
+    e = launch_pass(StepPass::Main, M_dev, variant, solver, nv, shmem, Q, 1, stream, fast ? &second : kernel);
     if (e != hipSuccess) return e;
     // a long rollout is one call: refresh the heavy-first orders of its launches along the way (the caller does it between calls)
     if (P.order && P.order2 && (t & 7) == 7 && t + 1 < nsteps) {
@@ -2071,40 +2099,22 @@ hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int nv, i
       if (e != hipSuccess) return e;
     }
   }
-  if (fast_name) g_last_step_kernel = fast_name;
   return hipSuccess;
 }
 
 // Inverse dynamics of every env in the launch (hb_inverse_dev): a general variant's poses and narrowphase first, as in a staged step,
 // then the inverse instantiation of the variant's row capacity
-hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int lds_floats, const BatchPtrs& P, hipStream_t stream) {
-  const size_t shmem = (size_t)lds_floats * sizeof(float);
+hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int lds_floats, const BatchPtrs& P, hipStream_t stream, const char** kernel) {
   if (variant != 0) {
     const hipError_t e = launch_pose_narrow(M_dev, P, stream);
     if (e != hipSuccess) return e;
   }
-  (void)hipGetLastError();
-  const dim3 grid(P.nblk), block(kGroup);
-  if (variant == 1) HB_STEP_LAUNCH(hb_inverse_gen_kernel, grid, block, shmem, stream, M_dev, P);
-  else if (variant == 2 && nv <= 20) HB_STEP_LAUNCH(hb_inverse_big20_kernel, grid, block, shmem, stream, M_dev, P);
-  else if (variant == 2) HB_STEP_LAUNCH(hb_inverse_big28_kernel, grid, block, shmem, stream, M_dev, P);
-  else if (variant == 3) HB_STEP_LAUNCH(hb_inverse_pgs_big_kernel, grid, block, shmem, stream, M_dev, P);
-  else if (nv <= 28) HB_STEP_LAUNCH(hb_inverse_kernel, grid, block, shmem, stream, M_dev, P);
-  else HB_STEP_LAUNCH(hb_inverse32_kernel, grid, block, shmem, stream, M_dev, P);
-  return hipGetLastError();
+  return launch_pass(StepPass::Inverse, M_dev, variant, /*solver=*/2, nv, (size_t)lds_floats * sizeof(float), P, 1, stream, kernel);
 }
-// every step and inverse instantiation: a layout over 64 KB must launch whichever of them the dispatch picks (launch_step_kernel, launch_step)
+// every step and inverse instantiation: a layout over 64 KB must launch whichever of them the dispatch picks
 hipError_t set_step_lds_limit(int bytes) {
-  for (const void* k : {(const void*)hb_step_kernel, (const void*)hb_step_lean_kernel, (const void*)hb_step_h27_kernel, (const void*)hb_step_h27_q_kernel,
-                        (const void*)hb_step_lean_q_kernel, (const void*)hb_step32_kernel, (const void*)hb_step_gen_kernel, (const void*)hb_step_gen_big_kernel,
-                        (const void*)hb_step_gen_fast1_kernel, (const void*)hb_step_gen_fast_kernel, (const void*)hb_step_gen_fast_lean_kernel,
-                        (const void*)hb_step_gen_fast_h27_kernel, (const void*)hb_step_newton_big20_kernel, (const void*)hb_step_newton_big28_kernel,
-                        (const void*)hb_step_newton_gen20_kernel, (const void*)hb_step_newton_gen20_lean_kernel, (const void*)hb_step_newton_gen20_team_kernel,
-                        (const void*)hb_step_newton_gen28_kernel, (const void*)hb_step_newton28_kernel, (const void*)hb_step_newton28_lean_kernel,
-                        (const void*)hb_step_newton28_h27_kernel, (const void*)hb_step_newton28_lean_q_kernel, (const void*)hb_step_newton32_kernel,
-                        (const void*)hb_inverse_kernel, (const void*)hb_inverse32_kernel, (const void*)hb_inverse_gen_kernel, (const void*)hb_inverse_pgs_big_kernel,
-                        (const void*)hb_inverse_big20_kernel, (const void*)hb_inverse_big28_kernel}) {
-    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  for (const StepKernel& k : kStepKernels) {
+    const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

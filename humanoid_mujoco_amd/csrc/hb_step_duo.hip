@@ -1396,11 +1396,12 @@ __global__ __launch_bounds__(kGroup, 2) void hb_step_duo_kernel(const DevModel* 
 // the rollouts' kernel: the step loop inside (hb_rollout_dev / hb_rollout_halton without optional outputs)
 __global__ __launch_bounds__(kGroup, 2) void hb_step_duo_q_kernel(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_duo<1>(Mp, P, nsteps); }
 
-// lean single-step launches of the 27-dof humanoid's PGS kernel, two envs per wave (launch_step_kernel, hb_step.hip)
-hipError_t launch_step_duo(const DevModel* M_dev, const BatchPtrs& P, int nsteps, hipStream_t stream) {
+// lean launches of the 27-dof humanoid's PGS kernel, two envs per wave (chosen by select_step, hb_step.hip); *kernel: the launched kernel's name
+#define HB_DUO_LAUNCH(k, ...) do { *kernel = #k; hipLaunchKernelGGL(k, dim3((P.nblk + 1) / 2), dim3(kGroup), (size_t)duo::kLdsF * sizeof(float), stream, __VA_ARGS__); } while (0)
+hipError_t launch_step_duo(const DevModel* M_dev, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel) {
   (void)hipGetLastError();
-  if (nsteps == 1) hipLaunchKernelGGL(hb_step_duo_kernel, dim3((P.nblk + 1) / 2), dim3(kGroup), (size_t)duo::kLdsF * sizeof(float), stream, M_dev, P);
-  else hipLaunchKernelGGL(hb_step_duo_q_kernel, dim3((P.nblk + 1) / 2), dim3(kGroup), (size_t)duo::kLdsF * sizeof(float), stream, M_dev, P, nsteps);
+  if (nsteps == 1) HB_DUO_LAUNCH(hb_step_duo_kernel, M_dev, P);
+  else HB_DUO_LAUNCH(hb_step_duo_q_kernel, M_dev, P, nsteps);
   return hipGetLastError();
 }
 

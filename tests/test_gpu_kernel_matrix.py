@@ -1,4 +1,4 @@
-"""Every step kernel, named and held to the fp64 oracle at the sizes where the dispatch (hb_step.hip: launch_step_kernel, launch_step) and
+"""Every step kernel, named and held to the fp64 oracle at the sizes where the dispatch (hb_step.hip: select_step, launch_step) and
 the dense, padded code change: nv 20 / 21 (the general Newton kernels' order 20, C stride 21), 28 / 29 (the classic kernels' order 28
 and 32; a dense block with no padding row, then an odd order), 31 and 32, on capsule chains (tests/kernel_models.py) and on same-size
 variants of the two assets the size-specialised kernels were written for.
@@ -132,7 +132,8 @@ def _kernel_names_in_source():
     names = set()
     for f in ("hb_step.hip", "hb_step_duo.hip"):
         src = open(os.path.join(CSRC, f)).read()
-        names |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(hb_step\w*_kernel)\s*\(", src))
+        names |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(hb_step\w*_kernel)\s*\(", src))  # defined by hand (the duo kernels)
+        names |= set(re.findall(r"^\s*K\((hb_step\w*_kernel),", src, re.M))  # rows of hb_step.hip's kernel table
     return names
 
 
