@@ -27,6 +27,56 @@ void set_err(char* err, int err_sz, const std::string& s) {
   if (err && err_sz > 0) { snprintf(err, err_sz, "%s", s.c_str()); }
 }
 
+// HB_DEBUG=1 in the environment names the failing HIP call on stderr
+static bool hb_debug() { static const bool on = getenv("HB_DEBUG") != nullptr; return on; }
+// a call whose failure is not fatal (teardown paths): still named under HB_DEBUG, and never left behind as the
+// thread's sticky last error for an unrelated launch to trip over
+#define HB_IGN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+    if (hb_debug()) fprintf(stderr, "[hb] %s:%d: %s -> %s (ignored)\n", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
+    (void)hipGetLastError(); } } while (0)
+#define HB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+    if (hb_debug()) fprintf(stderr, "[hb] %s:%d: %s -> %s\n", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
+    return HB_ENODEVICE; } } while (0)
+
+// The owner of one device allocation of T (or of none: a null pointer, which call sites read as "this feature is off").  All device
+// memory of a DeviceModel and of an hb_batch is held through these, so whatever is allocated is released with its owner.
+template <class T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  size_t capacity() const { return cap_; }
+  void reset() {
+    if (p_) HB_IGN(hipFree(p_));
+    p_ = nullptr; cap_ = 0;
+  }
+  // first use allocates exactly n elements (zero: and fills them with zero bytes); nothing when the buffer is there already
+  int alloc(size_t n, bool zero = false) {
+    if (p_) return HB_OK;
+    if (hipMalloc((void**)&p_, n * sizeof(T)) != hipSuccess) { p_ = nullptr; return HB_ENOMEM; }
+    cap_ = n;
+    if (zero) HB_HIP(hipMemset(p_, 0, n * sizeof(T)));
+    return HB_OK;
+  }
+  // grow only: room for n elements; a buffer that has to grow loses its contents, and is empty when that fails
+  int reserve(size_t n) {
+    if (n <= cap_) return HB_OK;
+    reset();
+    return alloc(n);
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t cap_ = 0;  // elements
+};
+// buffers that are allocated together are all there or all released
+template <class... B>
+void reset_all(B&... bufs) { (bufs.reset(), ...); }
+
 // flat table builder: ints and floats pushed into two arrays; offsets resolved after upload
 struct TableBuilder {
   std::vector<int> iv;
@@ -40,26 +90,18 @@ struct TableBuilder {
 
 struct DeviceModel {
   DevModel dm;
-  int* d_int = nullptr;
-  float* d_flt = nullptr;
-  unsigned long long* d_u64 = nullptr;
-  float* d_qpos_src = nullptr;  // qpos0 followed by keyframes, fp32
-  DevModel* d_dm = nullptr;     // device copy of dm (the step kernel reads the tables through it)
-  DevModel* d_dm_fast = nullptr;  // variant 2 only: the same model with the variant-1 LDS layout (fast step kernel of the staged step)
+  DevBuf<int> d_int;
+  DevBuf<float> d_flt;
+  DevBuf<unsigned long long> d_u64;
+  DevBuf<float> d_qpos_src;  // qpos0 followed by keyframes, fp32
+  DevBuf<DevModel> d_dm;     // device copy of dm (the step kernel reads the tables through it)
+  DevBuf<DevModel> d_dm_fast;  // variant 2 only: the same model with the variant-1 LDS layout (fast step kernel of the staged step)
   int fast_lds_floats = 0;
   bool sized_h27 = false;  // sizes and LDS layout equal kSizedHumanoid27's: the size-specialised step kernel applies
   bool sized_team = false; // the fast layout equals kSizedTeamV1's
   // observation order tables (device pointers): joint order and, when it exists, actuator order (hb_env_config.obs_actuator_order)
   const int *obs_jnt_joint = nullptr, *obs_src_joint = nullptr, *obs_jnt_act = nullptr, *obs_src_act = nullptr;
   bool has_act_order = false;
-  ~DeviceModel() {
-    if (d_int) (void)hipFree(d_int);
-    if (d_flt) (void)hipFree(d_flt);
-    if (d_u64) (void)hipFree(d_u64);
-    if (d_qpos_src) (void)hipFree(d_qpos_src);
-    if (d_dm) (void)hipFree(d_dm);
-    if (d_dm_fast) (void)hipFree(d_dm_fast);
-  }
 };
 
 // contact parameter mixing per candidate pair (mj_contactParam restatement; static per pair)
@@ -516,8 +558,7 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
          o_lrec = T.addraw(lrec);
 
   // ---- upload
-  if (hipMalloc((void**)&D.d_int, T.iv.size() * sizeof(int)) != hipSuccess || hipMalloc((void**)&D.d_flt, T.fv.size() * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&D.d_u64, T.uv.size() * sizeof(unsigned long long)) != hipSuccess) { err = "hipMalloc failed for model tables"; return false; }
+  if (D.d_int.alloc(T.iv.size()) != HB_OK || D.d_flt.alloc(T.fv.size()) != HB_OK || D.d_u64.alloc(T.uv.size()) != HB_OK) { err = "hipMalloc failed for model tables"; return false; }
   if (hipMemcpy(D.d_int, T.iv.data(), T.iv.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(D.d_flt, T.fv.data(), T.fv.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(D.d_u64, T.uv.data(), T.uv.size() * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMemcpy failed for model tables"; return false; }
@@ -540,9 +581,9 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
   std::vector<float> qsrc;
   for (double v : m.qpos0) qsrc.push_back((float)v);
   for (double v : m.key_qpos) qsrc.push_back((float)v);
-  if (hipMalloc((void**)&D.d_qpos_src, qsrc.size() * sizeof(float)) != hipSuccess ||
+  if (D.d_qpos_src.alloc(qsrc.size()) != HB_OK ||
       hipMemcpy(D.d_qpos_src, qsrc.data(), qsrc.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMalloc failed for qpos sources"; return false; }
-  if (hipMalloc((void**)&D.d_dm, sizeof(DevModel)) != hipSuccess || hipMemcpy(D.d_dm, &dm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMalloc failed for the device model"; return false; }
+  if (D.d_dm.alloc(1) != HB_OK || hipMemcpy(D.d_dm, &dm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMalloc failed for the device model"; return false; }
   // A variant-2 model (Newton on 256 rows in four register groups: one wave per SIMD) almost always has at most 63 rows and 24
   // contacts in a step: its staged step first runs the one-group Newton instantiation (two waves per SIMD) on the variant-1 LDS
   // layout and falls back to the four-group kernel for the envs that overflow (launch_step).  Same tables, other offsets.
@@ -562,7 +603,7 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
     DevModel fm = dm;
     fm.variant = 1; fm.ncon_max = kNconMax; fm.nefc_max = kNefcMax;
     if (!lay(fm)) return false;
-    if (hipMalloc((void**)&D.d_dm_fast, sizeof(DevModel)) != hipSuccess || hipMemcpy(D.d_dm_fast, &fm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMalloc failed for the device model"; return false; }
+    if (D.d_dm_fast.alloc(1) != HB_OK || hipMemcpy(D.d_dm_fast, &fm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMalloc failed for the device model"; return false; }
     D.fast_lds_floats = fm.lds_floats;
     {
       const SizedModel z = kSizedTeamV1;  // the robot's fast layout against its compile-time mirror (hb_step_newton_gen20_team_kernel)
@@ -585,56 +626,59 @@ struct hb_batch {
   DeviceModel D;
   int n_env = 0, device = 0;
   hipStream_t stream = nullptr;
-  float *d_state = nullptr, *d_ctrl = nullptr, *d_xfrc = nullptr, *d_diag_qacc = nullptr, *d_diag_force = nullptr, *d_diag_contact = nullptr;
-  float *d_obs = nullptr, *d_reward = nullptr;
-  int* d_seen = nullptr;        // [n_env] warning bits of episodes that ended since the last hb_env_warnings
-  float* d_term_obs = nullptr;  // [n_env][nobs] observations of the states episodes ended in (hb_env_terminal_obs), null until asked for
-  uint8_t *d_term = nullptr, *d_trunc = nullptr, *d_mask = nullptr;
-  int *d_status = nullptr, *d_counts = nullptr;
-  size_t ctrl_cap = 0;  // floats
-  float* d_qpos_out = nullptr;
-  size_t qpos_out_cap = 0;
-  float* d_qvel_out = nullptr;
-  size_t qvel_out_cap = 0;
-  float* d_task_out = nullptr;  // task returns and stage costs
+  // device memory: every buffer is a DevBuf member (null until the feature that needs it allocates it), released when the batch is deleted
+  DevBuf<float> d_state, d_ctrl, d_xfrc, d_diag_qacc, d_diag_force, d_diag_contact;
+  DevBuf<uint8_t> d_record;  // the env adapter's outputs as one block: obs [n_env][nobs] | reward [n_env] | terminated [n_env] | truncated [n_env]
+  float *d_obs = nullptr, *d_reward = nullptr;  // (its parts)
+  uint8_t *d_term = nullptr, *d_trunc = nullptr;
+  DevBuf<int> d_seen;        // [n_env] warning bits of episodes that ended since the last hb_env_warnings
+  DevBuf<float> d_term_obs;  // [n_env][nobs] observations of the states episodes ended in (hb_env_terminal_obs), null until asked for
+  DevBuf<uint8_t> d_mask;
+  DevBuf<int> d_status, d_counts;
+  DevBuf<float> d_qpos_out, d_qvel_out;
+  DevBuf<float> d_task_out;  // task returns and stage costs
   float xfrc_std = 0.f, xfrc_rate = 0.f;  // rollout noise (hb_rollout_noise)
   int tape_steps = 0;                      // steps of the action tape hb_ctrl_tape_splines left in d_ctrl (0: none)
-  float* d_knots = nullptr;               // spline nodes and node times staged for it
-  size_t knots_cap = 0;
+  DevBuf<float> d_knots;                   // spline nodes and node times staged for it
   unsigned xfrc_seed = 0, xfrc_calls = 0;
-  size_t task_out_cap = 0;
-  float* d_sensor_out = nullptr;
-  size_t sensor_out_cap = 0;
+  DevBuf<float> d_sensor_out;
   bool diag = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  unsigned long long* d_stamps = nullptr;
-  StageBufs stage = {};  // staged step of the general variants (null: fused)
+  DevBuf<unsigned long long> d_stamps;
+  // staged step of the general variants: the buffers, and the kernel argument that points into them (all null: fused)
+  DevBuf<float> d_stage_geom;
+  DevBuf<int4> d_stage_item;
+  DevBuf<int> d_stage_nsearch, d_stage_nwork, d_stage_defer;  // defer: flags | list | counters
+  DevBuf<float4> d_stage_result;
+  StageBufs stage = {};
   // env adapter (hb_env_*)
   EnvConfig env_cfg = {};
   bool env_ready = false;
-  float *d_prev = nullptr, *d_latest = nullptr, *d_qfrc = nullptr, *d_action = nullptr;
-  float* d_inv = nullptr;  // hb_inverse's device copies: qacc [n_env][nv] | qfrc_inverse [n_env][nv] | warnings [n_env] (allocated by its first call)
-  int* d_inv_scratch = nullptr;  // hb_inverse_dev: the counts [n_env][kCountStride] | status [n_env] its launches write instead of the batch's
-  int* d_episode = nullptr;
+  DevBuf<float> d_prev, d_latest, d_qfrc, d_action;
+  DevBuf<float> d_inv;  // hb_inverse's device copies: qacc [n_env][nv] | qfrc_inverse [n_env][nv] | warnings [n_env] (allocated by its first call)
+  DevBuf<int> d_inv_scratch;  // hb_inverse_dev: the counts [n_env][kCountStride] | status [n_env] its launches write instead of the batch's
+  DevBuf<int> d_episode;
   int env_offset = 0;
   // realism layer (hb_env_randomize)
   EnvRand env_rand = {};
-  EnvRandState rs = {};     // device arrays; all null while off
+  DevBuf<int> d_rs_k_act, d_rs_k_obs, d_rs_delay;
+  DevBuf<float> d_rs_fifo_act, d_rs_fifo_joint, d_rs_fifo_gyro, d_rs_fifo_grav, d_rs_push;
+  EnvRandState rs = {};     // the kernel argument that points into them; all null while off
   bool rand_on = false;
   DomainRand dom_rand = {};    // hb_env_domain_randomize
-  float* d_dr = nullptr;       // [n_env][dr_stride] per-env model parameters, null while off
+  DevBuf<float> d_dr;          // [n_env][dr_stride] per-env model parameters, null while off
   int dr_stride = 0;
-  uint8_t* d_rmask = nullptr;  // hb_env_reset's pending-envs mask
-  int* d_pending = nullptr;
+  DevBuf<uint8_t> d_rmask;     // hb_env_reset's pending-envs mask
+  DevBuf<int> d_pending;
   // policy MLP (hb_policy_*)
   int mlp_layers = 0;
   int mlp_sizes[5] = {0, 0, 0, 0, 0};
-  float* d_mlp_w[4] = {nullptr, nullptr, nullptr, nullptr};
-  float* d_mlp_wp[4] = {nullptr, nullptr, nullptr, nullptr};  // packed for hb_policy_kernel (all widths <= 256), else null
+  DevBuf<float> d_mlp_w[4];
+  DevBuf<float> d_mlp_wp[4];  // packed for hb_policy_kernel (all widths <= 256), else null
   bool mlp_fused = false;
-  float* d_mlp_b[4] = {nullptr, nullptr, nullptr, nullptr};
-  float* d_mlp_h[2] = {nullptr, nullptr};  // hidden activations, ping-pong
-  float* d_mlp_act = nullptr;              // activation scratch of the LDS-free policy kernel: [n_env / 16 + kPipes][2][16][widest + 4]
+  DevBuf<float> d_mlp_b[4];
+  DevBuf<float> d_mlp_h[2];  // hidden activations, ping-pong
+  DevBuf<float> d_mlp_act;   // activation scratch of the LDS-free policy kernel: [n_env / 16 + kPipes][2][16][widest + 4]
   // optional per-kernel timing of the step kernel (hb_step_timing)
   bool time_steps = false;
   std::vector<hipEvent_t> tev;  // pairs
@@ -647,8 +691,8 @@ struct hb_batch {
   BatchPtrs fold_P;
   const float* fold_ctrl[kFoldMax] = {};
   int fold_n = 0;
-  int* d_order = nullptr;   // heavy-first dispatch order (hb_order_kernel), valid once a step has run
-  int* d_order2 = nullptr;  // the same for the narrowphase launch of a staged step
+  DevBuf<int> d_order;      // heavy-first dispatch order (hb_order_kernel), valid once a step has run
+  DevBuf<int> d_order2;     // the same for the narrowphase launch of a staged step
   int order_mode = 0;       // 0: none yet, 1: one permutation of the whole batch, 2: one permutation per pipe segment
   bool schedule = true;  // heavy-first dispatch order (HB_TUNE_SCHEDULE)
   // Pipelined stepping (hb_batch_pipeline): the batch is cut into npipe fixed env segments, each stepped by
@@ -668,28 +712,13 @@ struct hb_batch {
 
 namespace {
 
-// HB_DEBUG=1 in the environment names the failing HIP call on stderr
-static bool hb_debug() { static const bool on = getenv("HB_DEBUG") != nullptr; return on; }
-// a call whose failure is not fatal (teardown paths): still named under HB_DEBUG, and never left behind as the
-// thread's sticky last error for an unrelated launch to trip over
-#define HB_IGN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-    if (hb_debug()) fprintf(stderr, "[hb] %s:%d: %s -> %s (ignored)\n", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-    (void)hipGetLastError(); } } while (0)
-#define HB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-    if (hb_debug()) fprintf(stderr, "[hb] %s:%d: %s -> %s\n", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-    return HB_ENODEVICE; } } while (0)
-
 // the batch's control buffer for WRITING: whatever hb_ctrl_tape_splines left there is gone afterwards, so a later
 // HB_CTRL_TAPE rollout must fail (HB_EINVAL) instead of rolling out stale controls
 float* ctrl_for_write(hb_batch* b) { b->tape_steps = 0; return b->d_ctrl; }
 
 int ensure_ctrl(hb_batch* b, size_t floats) {
-  if (floats <= b->ctrl_cap) return HB_OK;
-  if (b->d_ctrl) HB_IGN(hipFree(b->d_ctrl));
-  b->d_ctrl = nullptr; b->ctrl_cap = 0; b->tape_steps = 0;
-  if (hipMalloc((void**)&b->d_ctrl, floats * sizeof(float)) != hipSuccess) return HB_ENOMEM;
-  b->ctrl_cap = floats;
-  return HB_OK;
+  if (floats > b->d_ctrl.capacity()) b->tape_steps = 0;  // a regrown control buffer no longer holds a spline tape
+  return b->d_ctrl.reserve(floats);
 }
 
 // the staged step's buffers as this launch sees them (HB_TUNE_STAGED / FASTPASS / NARROW_PRIM switch parts of it off: all null = the fused step)
@@ -709,7 +738,7 @@ BatchPtrs make_ptrs(hb_batch* b) {
   if (b->diag) { P.diag_qacc = b->d_diag_qacc; P.diag_force = b->d_diag_force; P.diag_contact = b->d_diag_contact; }
   P.n_env = b->n_env;
   P.integrate = 1;
-  if (b->schedule && b->order_mode) { P.order = b->d_order; P.order2 = staged_on(b) ? b->d_order2 : nullptr; }
+  if (b->schedule && b->order_mode) { P.order = b->d_order; P.order2 = staged_on(b) ? b->d_order2.get() : nullptr; }
   P.blk0 = 0; P.nblk = b->n_env;
   P.dr = b->d_dr; P.dr_stride = b->dr_stride;
   P.stamps = b->d_stamps;
@@ -783,8 +812,8 @@ hipError_t launch_batch_step(hb_batch* b, const BatchPtrs& P, int nsteps, hipStr
 int launch_segment(hb_batch* b, BatchPtrs P, int nsteps, const Segment& sg, int nseg, bool reorder) {
   P.blk0 = sg.lo; P.nblk = sg.hi - sg.lo;
   // a whole-batch permutation would mix segments: a segment only uses the order of its own envs
-  P.order = (b->schedule && (nseg == 1 ? b->order_mode != 0 : b->order_mode == 2)) ? b->d_order : nullptr;
-  P.order2 = (P.order && staged_on(b)) ? b->d_order2 : nullptr;
+  P.order = (b->schedule && (nseg == 1 ? b->order_mode != 0 : b->order_mode == 2)) ? b->d_order.get() : nullptr;
+  P.order2 = (P.order && staged_on(b)) ? b->d_order2.get() : nullptr;
   HB_HIP(launch_batch_step(b, P, nsteps, sg.st));
   // (the key of the counting sort is 8 bits of the cost: of a single step's rows x sweeps - up to ~ 1600 - the bits above the lowest three; of the
   // AVERAGE over a launch of several steps, which the two-envs-per-wave kernel leaves behind and pairs its envs by - 180 .. 700 -, one bit more)
@@ -866,6 +895,17 @@ int launch_steps(hb_batch* b, BatchPtrs& P, int nsteps, bool foldable = false) {
   return b->fold_n >= cap ? flush_steps(b) : HB_OK;
 }
 
+// hb_rollout*'s shared opening: the control tape of T steps on the device, and room for the qpos trace when the caller wants one
+int rollout_open(hb_batch* b, const float* ctrl, int T, bool want_qpos) {
+  const size_t n = (size_t)T * b->n_env * b->D.dm.nu;
+  const int rc = ensure_ctrl(b, std::max<size_t>(n, 1));
+  if (rc != HB_OK) return rc;
+  if (n) HB_HIP(hipMemcpyAsync(ctrl_for_write(b), ctrl, n * sizeof(float), hipMemcpyHostToDevice, main_stream(b)));
+  return want_qpos ? b->d_qpos_out.reserve((size_t)T * b->n_env * b->D.dm.nq) : HB_OK;
+}
+// the batch's xfrc_applied exists, and was zeroed when it was created
+int ensure_xfrc(hb_batch* b) { return b->d_xfrc.alloc((size_t)b->n_env * 6 * b->D.dm.nbody, /*zero=*/true); }
+
 // field offsets of the per-env state record for a state spec
 struct SpecLayout { int total; };
 int spec_size(const Model& m, unsigned spec) {
@@ -926,7 +966,8 @@ int set_state_impl(hb_batch* b, unsigned spec, const T* in) {
   }
   HB_HIP(hipMemcpy(b->d_state, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
   if (spec & HB_STATE_XFRC_APPLIED) {
-    if (!b->d_xfrc) { if (hipMalloc((void**)&b->d_xfrc, xf.size() * sizeof(float)) != hipSuccess) return HB_ENOMEM; }
+    const int rc = ensure_xfrc(b);
+    if (rc != HB_OK) return rc;
     HB_HIP(hipMemcpy(b->d_xfrc, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   return HB_OK;
@@ -1074,30 +1115,27 @@ hb_batch* hb_batch_create(const hb_model* m, int n_env, int device, char* err, i
   ok = ok && hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming) == hipSuccess;
   // (the pipes' streams are created when hb_batch_pipeline asks for them: the runtime maps streams
   // onto four hardware queues, and streams that share one serialise - a batch should not own more streams than it uses)
-  ok = ok && hipMalloc((void**)&b->d_state, (size_t)n_env * dm.nstate * sizeof(float)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&b->d_status, (size_t)n_env * sizeof(int)) == hipSuccess;
-  ok = ok && hipMalloc((void**)&b->d_counts, (size_t)n_env * kCountStride * sizeof(int)) == hipSuccess;
-  ok = ok && hipMemset(b->d_counts, 0, (size_t)n_env * kCountStride * sizeof(int)) == hipSuccess;
+  ok = ok && b->d_state.alloc((size_t)n_env * dm.nstate) == HB_OK;
+  ok = ok && b->d_status.alloc((size_t)n_env) == HB_OK;
+  ok = ok && b->d_counts.alloc((size_t)n_env * kCountStride, /*zero=*/true) == HB_OK;
   ok = ok && ensure_ctrl(b, (size_t)n_env * std::max(1, dm.nu)) == HB_OK;
-  ok = ok && hipMalloc((void**)&b->d_order, (size_t)2 * n_env * sizeof(int)) == hipSuccess;  // the permutation | the sort keys of a pass
-  ok = ok && hipMalloc((void**)&b->d_order2, (size_t)2 * n_env * sizeof(int)) == hipSuccess;
+  ok = ok && b->d_order.alloc((size_t)2 * n_env) == HB_OK;  // the permutation | the sort keys of a pass
+  ok = ok && b->d_order2.alloc((size_t)2 * n_env) == HB_OK;
   // general variants: the staged step (pose -> narrowphase -> step kernels); hb_batch_tune(HB_TUNE_STAGED, 0) keeps everything in the step kernel
   if (dm.variant != 0) {
     StageBufs& sb = b->stage;
-    ok = ok && hipMalloc((void**)&sb.geom, (size_t)n_env * std::max(1, dm.ngeom) * 10 * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&sb.item, (size_t)n_env * kWorkMax * sizeof(int4)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&sb.nwork, (size_t)n_env * sizeof(int)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&sb.nsearch, (size_t)n_env * 2 * sizeof(int)) == hipSuccess;
-    ok = ok && hipMemset(sb.nsearch, 0, (size_t)n_env * 2 * sizeof(int)) == hipSuccess;
-    ok = ok && hipMalloc((void**)&sb.result, (size_t)n_env * kWorkMax * 4 * sizeof(float4)) == hipSuccess;
-    ok = ok && hipMemset(sb.nwork, 0, (size_t)n_env * sizeof(int)) == hipSuccess;
+    ok = ok && b->d_stage_geom.alloc((size_t)n_env * std::max(1, dm.ngeom) * 10) == HB_OK;
+    ok = ok && b->d_stage_item.alloc((size_t)n_env * kWorkMax) == HB_OK;
+    ok = ok && b->d_stage_nwork.alloc((size_t)n_env, /*zero=*/true) == HB_OK;
+    ok = ok && b->d_stage_nsearch.alloc((size_t)n_env * 2, /*zero=*/true) == HB_OK;
+    ok = ok && b->d_stage_result.alloc((size_t)n_env * kWorkMax * 4) == HB_OK;
+    sb.geom = b->d_stage_geom; sb.item = b->d_stage_item; sb.nwork = b->d_stage_nwork; sb.nsearch = b->d_stage_nsearch; sb.result = b->d_stage_result;
     sb.nq = dm.nq; sb.nv = dm.nv; sb.nu = dm.nu;
     sb.no_mesh = b->model->m.nmesh == 0 ? 1 : 0;
     sb.pose_lds = pose_lds_floats(dm.nq, dm.nbody, dm.ngeom) * (int)sizeof(float);
     if (dm.variant == 1 || b->D.d_dm_fast) {
-      ok = ok && hipMalloc((void**)&sb.defer, (size_t)n_env * 3 * sizeof(int)) == hipSuccess;  // flags | list | counters (StageBufs)
-      ok = ok && hipMemset(sb.defer, 0, (size_t)n_env * 3 * sizeof(int)) == hipSuccess;
-      if (ok) { sb.defer_list = sb.defer + n_env; sb.defer_count = sb.defer + 2 * (size_t)n_env; }
+      ok = ok && b->d_stage_defer.alloc((size_t)n_env * 3, /*zero=*/true) == HB_OK;  // flags | list | counters (StageBufs)
+      if (ok) { sb.defer = b->d_stage_defer; sb.defer_list = sb.defer + n_env; sb.defer_count = sb.defer + 2 * (size_t)n_env; }
       if (dm.variant == 2 || dm.variant == 3) { sb.dm_fast = b->D.d_dm_fast; sb.fast_lds = b->D.fast_lds_floats * (int)sizeof(float); }
       if (ok && sb.fast_lds > 64 * 1024) ok = set_step_lds_limit(sb.fast_lds) == hipSuccess;
     }
@@ -1111,7 +1149,6 @@ hb_batch* hb_batch_create(const hb_model* m, int n_env, int device, char* err, i
   return b;
 }
 
-static void envrand_free_fwd(hb_batch* b);
 void hb_batch_free(hb_batch* b) {
   if (!b) return;
   b->fold_n = 0;  // (step calls nobody will read the results of)
@@ -1123,20 +1160,9 @@ void hb_batch_free(hb_batch* b) {
   if (b->ev_fork) HB_IGN(hipEventDestroy(b->ev_fork));
   if (b->stream) { HB_IGN(hipStreamSynchronize(b->stream)); HB_IGN(hipStreamDestroy(b->stream)); }
   for (auto e : b->tev) HB_IGN(hipEventDestroy(e));
-  for (int i = 0; i < 4; i++) { if (b->d_mlp_w[i]) HB_IGN(hipFree(b->d_mlp_w[i])); if (b->d_mlp_b[i]) HB_IGN(hipFree(b->d_mlp_b[i])); if (b->d_mlp_wp[i]) HB_IGN(hipFree(b->d_mlp_wp[i])); }
-  for (int i = 0; i < 2; i++) if (b->d_mlp_h[i]) HB_IGN(hipFree(b->d_mlp_h[i]));
-  if (b->d_mlp_act) HB_IGN(hipFree(b->d_mlp_act));
   if (b->ev0) HB_IGN(hipEventDestroy(b->ev0));
   if (b->ev1) HB_IGN(hipEventDestroy(b->ev1));
-  envrand_free_fwd(b);
-  if (b->d_sensor_out) HB_IGN(hipFree(b->d_sensor_out));
-  if (b->d_dr) HB_IGN(hipFree(b->d_dr));
-  if (b->d_rmask) HB_IGN(hipFree(b->d_rmask));
-  if (b->d_pending) HB_IGN(hipFree(b->d_pending));
-  void* ptrs[] = {b->stage.geom, b->stage.item, b->stage.nsearch, b->stage.nwork, b->stage.result, b->stage.defer, b->d_term_obs, b->d_seen, b->d_state, b->d_ctrl, b->d_xfrc, b->d_diag_qacc, b->d_diag_force, b->d_diag_contact, b->d_obs, b->d_mask,
-                  b->d_status, b->d_counts, b->d_qpos_out, b->d_qvel_out, b->d_task_out, b->d_knots, b->d_order, b->d_order2, b->d_prev, b->d_latest, b->d_qfrc, b->d_action, b->d_episode, b->d_inv, b->d_inv_scratch};
-  for (void* p : ptrs) if (p) HB_IGN(hipFree(p));
-  delete b;
+  delete b;  // (the device buffers: every stream was waited for above, and the device is still set)
 }
 
 int hb_batch_n_env(const hb_batch* b) { return b ? b->n_env : HB_EINVAL; }
@@ -1169,14 +1195,13 @@ static int make_pipes(hb_batch* b, int n) {
 // one idling wave per stream (60 us each), all n overlapping pairwise in the GPU's own clock or not.
 // returns -1 when all n run side by side, else the higher stream index of the first pair that does not (-2: the probe itself failed)
 static int pipes_conflict(hb_batch* b, int n) {
-  unsigned long long* d = nullptr;
+  DevBuf<unsigned long long> d;
   unsigned long long h[2 * hb_batch::kPipes] = {};
-  if (hipStreamSynchronize(b->stream) != hipSuccess || hipMalloc((void**)&d, sizeof h) != hipSuccess) return -2;
-  bool ok = hipMemset(d, 0, sizeof h) == hipSuccess;
+  if (hipStreamSynchronize(b->stream) != hipSuccess || d.alloc(2 * hb_batch::kPipes, /*zero=*/true) != HB_OK) return -2;
+  bool ok = true;
   for (int c = 0; c < n && ok; c++) ok = launch_probe_spin(d + 2 * c, 6000, b->pipe[c]) == hipSuccess;
   for (int c = 0; c < n; c++) ok = hipStreamSynchronize(b->pipe[c]) == hipSuccess && ok;
   ok = ok && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) == hipSuccess;
-  HB_IGN(hipFree(d));
   if (!ok) return -2;
   for (int i = 0; i < n; i++)
     for (int j = i + 1; j < n; j++)
@@ -1233,7 +1258,7 @@ static int reset_impl(hb_batch* b, const uint8_t* mask, int keyframe, float pert
   HB_HIP(hipSetDevice(b->device));
   const uint8_t* dmask = nullptr;
   if (mask) {
-    if (!b->d_mask && hipMalloc((void**)&b->d_mask, b->n_env) != hipSuccess) return HB_ENOMEM;
+    if (b->d_mask.alloc(b->n_env) != HB_OK) return HB_ENOMEM;
     HB_HIP(hipMemcpyAsync(b->d_mask, mask, b->n_env, hipMemcpyHostToDevice, main_stream(b)));
     dmask = b->d_mask;
   }
@@ -1288,7 +1313,7 @@ int hb_inverse_dev(hb_batch* b, const float* qacc_dev, int flags, float* qfrc_in
   // (the pose and narrowphase kernels of a general variant write per-env counts and status bits: here into scratch, which the inverse
   // kernel reads back into the warnings)
   const size_t ncount = (size_t)b->n_env * kCountStride;
-  if (!b->d_inv_scratch && hipMalloc((void**)&b->d_inv_scratch, (ncount + (size_t)b->n_env) * sizeof(int)) != hipSuccess) { b->d_inv_scratch = nullptr; return HB_ENOMEM; }
+  if (b->d_inv_scratch.alloc(ncount + (size_t)b->n_env) != HB_OK) return HB_ENOMEM;
   HB_HIP(hipMemsetAsync(b->d_inv_scratch + ncount, 0, (size_t)b->n_env * sizeof(int), stream));
   BatchPtrs P;
   memset(&P, 0, sizeof P);
@@ -1307,7 +1332,7 @@ int hb_inverse(hb_batch* b, const float* qacc, int flags, float* qfrc_inverse, i
   if (!b || !qacc || !qfrc_inverse || (flags & ~HB_INV_DISCRETE)) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
   const size_t n = (size_t)b->n_env * b->D.dm.nv;
-  if (!b->d_inv && hipMalloc((void**)&b->d_inv, (2 * n + (size_t)b->n_env) * sizeof(float)) != hipSuccess) { b->d_inv = nullptr; return HB_ENOMEM; }
+  if (b->d_inv.alloc(2 * n + (size_t)b->n_env) != HB_OK) return HB_ENOMEM;
   float* d_qacc = b->d_inv;
   float* d_out = b->d_inv + n;
   int* d_warn = reinterpret_cast<int*>(b->d_inv + 2 * n);
@@ -1331,31 +1356,13 @@ int hb_rollout_dev(hb_batch* b, const float* ctrl_dev, int T, float* qpos_out_de
 int hb_rollout(hb_batch* b, const float* ctrl, int T, float* qpos_out) {
   if (!b || T < 1 || (!ctrl && b->D.dm.nu > 0)) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
-  size_t n = (size_t)T * b->n_env * b->D.dm.nu;
-  int rc = ensure_ctrl(b, std::max<size_t>(n, 1));
+  int rc = rollout_open(b, ctrl, T, qpos_out != nullptr);
   if (rc != HB_OK) return rc;
-  if (n) HB_HIP(hipMemcpyAsync(ctrl_for_write(b), ctrl, n * sizeof(float), hipMemcpyHostToDevice, main_stream(b)));
-  size_t nq_out = (size_t)T * b->n_env * b->D.dm.nq;
-  if (qpos_out && nq_out > b->qpos_out_cap) {
-    if (b->d_qpos_out) HB_IGN(hipFree(b->d_qpos_out));
-    b->d_qpos_out = nullptr; b->qpos_out_cap = 0;
-    if (hipMalloc((void**)&b->d_qpos_out, nq_out * sizeof(float)) != hipSuccess) return HB_ENOMEM;
-    b->qpos_out_cap = nq_out;
-  }
-  rc = hb_rollout_dev(b, b->d_ctrl, T, qpos_out ? b->d_qpos_out : nullptr);
+  const size_t nq_out = (size_t)T * b->n_env * b->D.dm.nq;
+  rc = hb_rollout_dev(b, b->d_ctrl, T, qpos_out ? b->d_qpos_out.get() : nullptr);
   if (rc != HB_OK) return rc;
   if (qpos_out) HB_HIP(hipMemcpyAsync(qpos_out, b->d_qpos_out, nq_out * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
   HB_HIP(hipStreamSynchronize(main_stream(b)));
-  return HB_OK;
-}
-
-// grows a device trace buffer to `need` floats
-static int ensure_trace(float** buf, size_t* cap, size_t need) {
-  if (need <= *cap) return HB_OK;
-  if (*buf) HB_IGN(hipFree(*buf));
-  *buf = nullptr; *cap = 0;
-  if (hipMalloc((void**)buf, need * sizeof(float)) != hipSuccess) return HB_ENOMEM;
-  *cap = need;
   return HB_OK;
 }
 
@@ -1506,7 +1513,7 @@ int hb_ctrl_tape_splines(hb_batch* b, const float* knots, const float* times, in
   HB_HIP(hipSetDevice(b->device));
   const int N = b->n_env, nu = b->D.dm.nu;
   const size_t nk = (size_t)N * n_points * nu;
-  int rc = ensure_trace(&b->d_knots, &b->knots_cap, nk + 64);
+  int rc = b->d_knots.reserve(nk + 64);
   if (rc != HB_OK) return rc;
   rc = ensure_ctrl(b, (size_t)T * N * nu);
   if (rc != HB_OK) return rc;
@@ -1541,9 +1548,9 @@ int hb_task_cost(hb_batch* b, const float* residual, int n, int n_residual, cons
   K.nterm = spec->n_term; K.risk = spec->risk;
   HB_HIP(hipSetDevice(b->device));
   const size_t nr = (size_t)n * n_residual, nt = (size_t)n * spec->n_term;
-  int rc = ensure_trace(&b->d_sensor_out, &b->sensor_out_cap, nr);
+  int rc = b->d_sensor_out.reserve(nr);
   if (rc != HB_OK) return rc;
-  if ((rc = ensure_trace(&b->d_task_out, &b->task_out_cap, nt + n)) != HB_OK) return rc;
+  if ((rc = b->d_task_out.reserve(nt + n)) != HB_OK) return rc;
   HB_HIP(hipMemcpyAsync(b->d_sensor_out, residual, nr * sizeof(float), hipMemcpyHostToDevice, main_stream(b)));
   HB_HIP(launch_cost_terms(b->d_sensor_out, n, n_residual, K, terms ? b->d_task_out + n : nullptr, b->d_task_out, main_stream(b)));
   HB_HIP(hipMemcpyAsync(cost, b->d_task_out, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
@@ -1555,10 +1562,9 @@ int hb_task_cost(hb_batch* b, const float* residual, int n, int n_residual, cons
 int hb_rollout_noise(hb_batch* b, float xfrc_std, float xfrc_rate, unsigned seed) {
   if (!b || !(xfrc_std >= 0.f) || !(xfrc_rate >= 0.f)) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
-  if (xfrc_std > 0.f && !b->d_xfrc) {
-    const size_t nx = (size_t)b->n_env * b->D.dm.nbody * 6;
-    if (hipMalloc((void**)&b->d_xfrc, nx * sizeof(float)) != hipSuccess) return HB_ENOMEM;
-    HB_HIP(hipMemset(b->d_xfrc, 0, nx * sizeof(float)));
+  if (xfrc_std > 0.f) {
+    const int rc = ensure_xfrc(b);
+    if (rc != HB_OK) return rc;
   }
   b->xfrc_std = xfrc_std; b->xfrc_rate = xfrc_rate; b->xfrc_seed = seed; b->xfrc_calls = 0;
   return HB_OK;
@@ -1567,17 +1573,14 @@ int hb_rollout_noise(hb_batch* b, float xfrc_std, float xfrc_rate, unsigned seed
 int hb_rollout_trajectory(hb_batch* b, const float* ctrl, int T, float* qpos_out, float* qvel_out, int* failed) {
   if (!b || T < 1 || (!ctrl && b->D.dm.nu > 0)) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
-  const size_t n = (size_t)T * b->n_env * b->D.dm.nu;
-  int rc = ensure_ctrl(b, std::max<size_t>(n, 1));
+  int rc = rollout_open(b, ctrl, T, qpos_out != nullptr);
   if (rc != HB_OK) return rc;
-  if (n) HB_HIP(hipMemcpyAsync(ctrl_for_write(b), ctrl, n * sizeof(float), hipMemcpyHostToDevice, main_stream(b)));
   const size_t nq_out = (size_t)T * b->n_env * b->D.dm.nq, nv_out = (size_t)T * b->n_env * b->D.dm.nv;
-  if (qpos_out && (rc = ensure_trace(&b->d_qpos_out, &b->qpos_out_cap, nq_out)) != HB_OK) return rc;
-  if (qvel_out && (rc = ensure_trace(&b->d_qvel_out, &b->qvel_out_cap, nv_out)) != HB_OK) return rc;
+  if (qvel_out && (rc = b->d_qvel_out.reserve(nv_out)) != HB_OK) return rc;
   BatchPtrs P = make_ptrs(b);
   P.ctrl = b->d_ctrl; P.ctrl_mode = 1;
-  P.qpos_out = qpos_out ? b->d_qpos_out : nullptr;
-  P.qvel_out = qvel_out ? b->d_qvel_out : nullptr;
+  P.qpos_out = qpos_out ? b->d_qpos_out.get() : nullptr;
+  P.qvel_out = qvel_out ? b->d_qvel_out.get() : nullptr;
   rc = launch_steps(b, P, T);
   if (rc != HB_OK) return rc;
   if (qpos_out) HB_HIP(hipMemcpyAsync(qpos_out, b->d_qpos_out, nq_out * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
@@ -1701,13 +1704,8 @@ static int sensor_setup(hb_batch* b, const hb_sensor_spec* spec, int T, BatchPtr
       if (m.body_parentid[bd] == 0) { if (bd == spec->subtree_body) tree = t; t++; }
     if (tree < 0) return HB_EINVAL;
   }
-  const size_t need = (size_t)T * b->n_env * ns;
-  if (need > b->sensor_out_cap) {
-    if (b->d_sensor_out) HB_IGN(hipFree(b->d_sensor_out));
-    b->d_sensor_out = nullptr; b->sensor_out_cap = 0;
-    if (hipMalloc((void**)&b->d_sensor_out, need * sizeof(float)) != hipSuccess) return HB_ENOMEM;
-    b->sensor_out_cap = need;
-  }
+  const int rc = b->d_sensor_out.reserve((size_t)T * b->n_env * ns);
+  if (rc != HB_OK) return rc;
   P.sensor_out = b->d_sensor_out; P.sensor_stride = ns; P.sensor_nframe = spec->n_framepos; P.sensor_tree = tree;
   for (int k = 0; k < spec->n_framepos; k++) {
     P.sensor_body[k] = spec->framepos_body[k];
@@ -1739,19 +1737,11 @@ static int sensor_setup(hb_batch* b, const hb_sensor_spec* spec, int T, BatchPtr
 int hb_rollout_sensors(hb_batch* b, const float* ctrl, int T, const hb_sensor_spec* spec, float* sensor_out, float* qpos_out) {
   if (!b || T < 1 || !spec || !sensor_out || (!ctrl && b->D.dm.nu > 0)) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
-  const size_t n = (size_t)T * b->n_env * b->D.dm.nu;
-  int rc = ensure_ctrl(b, std::max<size_t>(n, 1));
+  int rc = rollout_open(b, ctrl, T, qpos_out != nullptr);
   if (rc != HB_OK) return rc;
-  if (n) HB_HIP(hipMemcpyAsync(ctrl_for_write(b), ctrl, n * sizeof(float), hipMemcpyHostToDevice, main_stream(b)));
   const size_t nq_out = (size_t)T * b->n_env * b->D.dm.nq;
-  if (qpos_out && nq_out > b->qpos_out_cap) {
-    if (b->d_qpos_out) HB_IGN(hipFree(b->d_qpos_out));
-    b->d_qpos_out = nullptr; b->qpos_out_cap = 0;
-    if (hipMalloc((void**)&b->d_qpos_out, nq_out * sizeof(float)) != hipSuccess) return HB_ENOMEM;
-    b->qpos_out_cap = nq_out;
-  }
   BatchPtrs P = make_ptrs(b);
-  P.ctrl = b->d_ctrl; P.ctrl_mode = 1; P.qpos_out = qpos_out ? b->d_qpos_out : nullptr;
+  P.ctrl = b->d_ctrl; P.ctrl_mode = 1; P.qpos_out = qpos_out ? b->d_qpos_out.get() : nullptr;
   rc = sensor_setup(b, spec, T, P);
   if (rc != HB_OK) return rc;
   rc = launch_steps(b, P, T);
@@ -1786,8 +1776,8 @@ static int rollout_rows(hb_batch* b, const float* ctrl, int H, const hb_sensor_s
   rc = sensor_setup(b, spec, H, P);
   if (rc != HB_OK) return rc;
   *stride = P.sensor_stride + ((flags & 4) ? dm.nq : 0) + ((flags & 1) ? dm.nv : 0) + ((flags & 2) ? nu : 0);
-  if ((rc = ensure_trace(&b->d_sensor_out, &b->sensor_out_cap, (size_t)H * N * *stride)) != HB_OK) return rc;
-  if ((rc = ensure_trace(&b->d_task_out, &b->task_out_cap, (size_t)(H + 1) * N)) != HB_OK) return rc;
+  if ((rc = b->d_sensor_out.reserve((size_t)H * N * *stride)) != HB_OK) return rc;
+  if ((rc = b->d_task_out.reserve((size_t)(H + 1) * N)) != HB_OK) return rc;
   P.sensor_out = b->d_sensor_out; P.sensor_stride = *stride; P.sensor_flags = flags;
   if (H > 1) {
     P.ctrl = b->d_ctrl; P.ctrl_mode = 1;
@@ -1974,23 +1964,21 @@ static int env_alloc(hb_batch* b) {
   const DevModel& dm = b->D.dm;
   size_t n = b->n_env;
   HB_HIP(hipSetDevice(b->device));
-  if (!b->d_obs) {
-    // one record [obs n x nobs | reward n | terminated n | truncated n]: a host that keeps its four buffers in the same order and
-    // back to back (engine.py does) gets them in one transfer instead of four
-    if (hipMalloc((void**)&b->d_obs, n * dm.nobs * sizeof(float) + n * sizeof(float) + 2 * n) != hipSuccess) return HB_ENOMEM;
-    b->d_reward = b->d_obs + n * dm.nobs;
-    b->d_term = reinterpret_cast<uint8_t*>(b->d_reward + n);
-    b->d_trunc = b->d_term + n;
-  }
-  size_t nu = std::max(1, dm.nu);
-  if (hipMalloc((void**)&b->d_prev, n * nu * sizeof(float)) != hipSuccess || hipMalloc((void**)&b->d_latest, n * nu * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&b->d_action, n * nu * sizeof(float)) != hipSuccess || hipMalloc((void**)&b->d_qfrc, n * dm.nv * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&b->d_episode, n * sizeof(int)) != hipSuccess || hipMalloc((void**)&b->d_seen, n * sizeof(int)) != hipSuccess) return HB_ENOMEM;
-  HB_HIP(hipMemset(b->d_seen, 0, n * sizeof(int)));
-  HB_HIP(hipMemset(b->d_prev, 0, n * nu * sizeof(float)));
-  HB_HIP(hipMemset(b->d_latest, 0, n * nu * sizeof(float)));
-  HB_HIP(hipMemset(b->d_qfrc, 0, n * dm.nv * sizeof(float)));
-  HB_HIP(hipMemset(b->d_episode, 0, n * sizeof(int)));
+  const size_t nu = std::max(1, dm.nu);
+  // one record [obs n x nobs | reward n | terminated n | truncated n]: a host that keeps its four buffers in the same order and
+  // back to back (engine.py does) gets them in one transfer instead of four
+  int rc = b->d_record.alloc(n * dm.nobs * sizeof(float) + n * sizeof(float) + 2 * n);
+  if (rc == HB_OK) rc = b->d_prev.alloc(n * nu, /*zero=*/true);
+  if (rc == HB_OK) rc = b->d_latest.alloc(n * nu, /*zero=*/true);
+  if (rc == HB_OK) rc = b->d_action.alloc(n * nu);
+  if (rc == HB_OK) rc = b->d_qfrc.alloc(n * dm.nv, /*zero=*/true);
+  if (rc == HB_OK) rc = b->d_episode.alloc(n, /*zero=*/true);
+  if (rc == HB_OK) rc = b->d_seen.alloc(n, /*zero=*/true);
+  if (rc != HB_OK) { reset_all(b->d_record, b->d_prev, b->d_latest, b->d_action, b->d_qfrc, b->d_episode, b->d_seen); return rc; }
+  b->d_obs = reinterpret_cast<float*>(b->d_record.get());
+  b->d_reward = b->d_obs + n * dm.nobs;
+  b->d_term = reinterpret_cast<uint8_t*>(b->d_reward + n);
+  b->d_trunc = b->d_term + n;
   hb_env_config def;
   hb_env_default_config(b->model, &def);
   static_assert(sizeof(hb_env_config) == sizeof(EnvConfig), "hb_env_config and EnvConfig must have the same layout");
@@ -2009,7 +1997,7 @@ static int env_eval(hb_batch* b, bool allow_reset, bool observe, const uint8_t* 
   EnvRandState S = b->rs;
   if (!b->rand_on) memset(&S, 0, sizeof S);
   HB_HIP(launch_env(b->D.dm, cfg, b->env_rand, S, b->d_state, b->d_qfrc, b->d_counts, b->d_prev, b->d_latest, src, b->d_episode, b->d_status, d_obs, d_reward,
-                    d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs : nullptr, b->d_seen));
+                    d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen));
   return HB_OK;
 }
 
@@ -2129,9 +2117,12 @@ int hb_env_default_randomization(const hb_model* h, hb_env_randomization* r) {
   return HB_OK;
 }
 
-// releases the realism layer's device arrays
-static void envrand_free_fwd(hb_batch* b) { void* ptrs[] = {b->rs.k_act, b->rs.k_obs, b->rs.delay, b->rs.fifo_act, b->rs.fifo_joint, b->rs.fifo_gyro, b->rs.fifo_grav, b->rs.push}; for (void* p : ptrs) if (p) HB_IGN(hipFree(p)); memset(&b->rs, 0, sizeof b->rs); b->rand_on = false; }
-static void envrand_free(hb_batch* b) { envrand_free_fwd(b); }
+// releases the realism layer's device arrays: the layer is off
+static void envrand_free(hb_batch* b) {
+  reset_all(b->d_rs_k_act, b->d_rs_k_obs, b->d_rs_delay, b->d_rs_fifo_act, b->d_rs_fifo_joint, b->d_rs_fifo_gyro, b->d_rs_fifo_grav, b->d_rs_push);
+  memset(&b->rs, 0, sizeof b->rs);
+  b->rand_on = false;
+}
 int hb_env_randomize(hb_batch* b, const hb_env_randomization* cfg) {
   if (!b) return HB_EINVAL;
   int rc = env_alloc(b);
@@ -2147,21 +2138,21 @@ int hb_env_randomize(hb_batch* b, const hb_env_randomization* cfg) {
   static_assert(sizeof(hb_env_randomization) == sizeof(EnvRand), "hb_env_randomization and EnvRand must have the same layout");
   const size_t n = b->n_env, nu = std::max(1, dm.nu), nj2 = std::max(2, dm.nobs - 6);
   if (!b->rs.k_act) {
-    bool ok = hipMalloc((void**)&b->rs.k_act, n * sizeof(int)) == hipSuccess && hipMalloc((void**)&b->rs.k_obs, n * sizeof(int)) == hipSuccess &&
-              hipMalloc((void**)&b->rs.delay, n * 4 * sizeof(int)) == hipSuccess && hipMalloc((void**)&b->rs.fifo_act, n * kDelaySlots * nu * sizeof(float)) == hipSuccess &&
-              hipMalloc((void**)&b->rs.fifo_joint, n * kDelaySlots * nj2 * sizeof(float)) == hipSuccess &&
-              hipMalloc((void**)&b->rs.fifo_gyro, n * kDelaySlots * 3 * sizeof(float)) == hipSuccess &&
-              hipMalloc((void**)&b->rs.fifo_grav, n * kDelaySlots * 3 * sizeof(float)) == hipSuccess && hipMalloc((void**)&b->rs.push, n * 8 * sizeof(float)) == hipSuccess;
-    if (!ok) { envrand_free(b); return HB_ENOMEM; }
-    HB_HIP(hipMemset(b->rs.push, 0, n * 8 * sizeof(float)));
+    rc = b->d_rs_k_act.alloc(n);
+    if (rc == HB_OK) rc = b->d_rs_k_obs.alloc(n);
+    if (rc == HB_OK) rc = b->d_rs_delay.alloc(n * 4);
+    if (rc == HB_OK) rc = b->d_rs_fifo_act.alloc(n * kDelaySlots * nu);
+    if (rc == HB_OK) rc = b->d_rs_fifo_joint.alloc(n * kDelaySlots * nj2);
+    if (rc == HB_OK) rc = b->d_rs_fifo_gyro.alloc(n * kDelaySlots * 3);
+    if (rc == HB_OK) rc = b->d_rs_fifo_grav.alloc(n * kDelaySlots * 3);
+    if (rc == HB_OK) rc = b->d_rs_push.alloc(n * 8, /*zero=*/true);
+    if (rc != HB_OK) { envrand_free(b); return rc; }
+    b->rs.k_act = b->d_rs_k_act; b->rs.k_obs = b->d_rs_k_obs; b->rs.delay = b->d_rs_delay; b->rs.fifo_act = b->d_rs_fifo_act;
+    b->rs.fifo_joint = b->d_rs_fifo_joint; b->rs.fifo_gyro = b->d_rs_fifo_gyro; b->rs.fifo_grav = b->d_rs_fifo_grav; b->rs.push = b->d_rs_push;
   }
-  if (cfg->push_enabled && !b->d_xfrc) {
-    const size_t nx = n * 6 * dm.nbody;
-    if (hipMalloc((void**)&b->d_xfrc, nx * sizeof(float)) != hipSuccess) return HB_ENOMEM;
-    HB_HIP(hipMemset(b->d_xfrc, 0, nx * sizeof(float)));
-  }
+  if (cfg->push_enabled && (rc = ensure_xfrc(b)) != HB_OK) return rc;
   memcpy(&b->env_rand, cfg, sizeof *cfg);
-  b->rs.xfrc = cfg->push_enabled ? b->d_xfrc : nullptr;
+  b->rs.xfrc = cfg->push_enabled ? b->d_xfrc.get() : nullptr;
   b->rand_on = true;
   // a consistent episode state until the caller resets: delays drawn, rings empty
   HB_HIP(launch_envrand_reset(dm, b->env_rand, b->rs, b->d_episode, nullptr, b->n_env, b->env_offset, main_stream(b)));
@@ -2189,8 +2180,8 @@ int hb_env_domain_randomize(hb_batch* b, const hb_domain_randomization* cfg) {
   HB_HIP(hipSetDevice(b->device));
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   if (!cfg || !(cfg->factor > 0.f)) {
-    if (b->d_dr) HB_IGN(hipFree(b->d_dr));
-    b->d_dr = nullptr; b->dr_stride = 0;
+    b->d_dr.reset();
+    b->dr_stride = 0;
     return HB_OK;
   }
   if (!(cfg->friction_max_mult >= cfg->friction_min_mult) || cfg->friction_min_mult < 0.f || cfg->max_mass_change < 0.f || cfg->max_external_mass < 0.f ||
@@ -2199,7 +2190,7 @@ int hb_env_domain_randomize(hb_batch* b, const hb_domain_randomization* cfg) {
   static_assert(sizeof(hb_domain_randomization) == sizeof(DomainRand), "hb_domain_randomization and DomainRand must have the same layout");
   const DevModel& dm = b->D.dm;
   const DomainLayout L = domain_layout(dm.nbody, dm.nv, dm.nlimcand, dm.nu, dm.nhfielddata);
-  if (!b->d_dr && hipMalloc((void**)&b->d_dr, (size_t)b->n_env * L.stride * sizeof(float)) != hipSuccess) return HB_ENOMEM;
+  if (b->d_dr.alloc((size_t)b->n_env * L.stride) != HB_OK) return HB_ENOMEM;
   b->dr_stride = L.stride;
   memcpy(&b->dom_rand, cfg, sizeof *cfg);
   // valid parameters at once (the draw of episode 0); hb_env_reset draws again for the episode numbers it assigns
@@ -2256,7 +2247,7 @@ int hb_env_reset(hb_batch* b, float* obs) {
     // The reference's protocol (cpu_env.py:374-416): randomise, take one step with the current (zero) controls, and
     // start over with a new draw while that step ends in a collision or in a terminal state.  Pending envs carry
     // a mask; everything (reset, realism layer, physics, evaluation) runs masked, at most eight draws.
-    if (!b->d_rmask && (hipMalloc((void**)&b->d_rmask, n) != hipSuccess || hipMalloc((void**)&b->d_pending, sizeof(int)) != hipSuccess)) return HB_ENOMEM;
+    if (b->d_rmask.alloc(n) != HB_OK || b->d_pending.alloc(1) != HB_OK) return HB_ENOMEM;
     HB_HIP(hipMemsetAsync(b->d_rmask, 1, n, main_stream(b)));
     const float* src = b->D.d_qpos_src + (c.reset_keyframe < 0 ? 0 : (size_t)(1 + c.reset_keyframe) * m.nq);
     const float dtc = b->rand_on && b->env_rand.control_timestep > 0.f ? b->env_rand.control_timestep : (float)m.timestep;
@@ -2317,7 +2308,7 @@ int hb_env_terminal_obs(hb_batch* b, float* terminal_obs) {
   HB_HIP(hipSetDevice(b->device));
   const size_t bytes = (size_t)b->n_env * b->D.dm.nobs * sizeof(float);
   if (!b->d_term_obs) {  // first call: from the next hb_env_step on the env kernel records them
-    if (hipMalloc((void**)&b->d_term_obs, bytes) != hipSuccess) return HB_ENOMEM;
+    if (b->d_term_obs.alloc((size_t)b->n_env * b->D.dm.nobs) != HB_OK) return HB_ENOMEM;
     HB_HIP(hipMemsetAsync(b->d_term_obs, 0, bytes, main_stream(b)));
   }
   if (terminal_obs) {
@@ -2346,7 +2337,7 @@ int hb_policy_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* 
   for (int l = 0; l <= n_layers; l++) fused = fused && sizes[l] <= 256;
   for (int l = 0; l < n_layers; l++) {
     if (!weights[l] || !biases[l]) return HB_EINVAL;
-    if (b->d_mlp_wp[l]) { HB_IGN(hipFree(b->d_mlp_wp[l])); b->d_mlp_wp[l] = nullptr; }
+    b->d_mlp_wp[l].reset();
     if (fused) {
       // B-operand order of v_mfma_f32_16x16x4_f32: wp[tile][k/4][lane] = W[4(k/4) + lane/16][16 tile + lane%16], zero padded
       const int K = sizes[l], N = sizes[l + 1], KK = (K + 3) / 4, ntile = (N + 15) / 16;
@@ -2357,28 +2348,26 @@ int hb_policy_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* 
             const int k = 4 * kk + (ln >> 4), n = 16 * nt + (ln & 15);
             if (k < K && n < N) wp[((size_t)nt * KK + kk) * 64 + ln] = weights[l][(size_t)k * N + n];
           }
-      if (hipMalloc((void**)&b->d_mlp_wp[l], wp.size() * sizeof(float)) != hipSuccess) return HB_ENOMEM;
+      if (b->d_mlp_wp[l].alloc(wp.size()) != HB_OK) return HB_ENOMEM;
       HB_HIP(hipMemcpy(b->d_mlp_wp[l], wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    if (b->d_mlp_w[l]) { HB_IGN(hipFree(b->d_mlp_w[l])); b->d_mlp_w[l] = nullptr; }
-    if (b->d_mlp_b[l]) { HB_IGN(hipFree(b->d_mlp_b[l])); b->d_mlp_b[l] = nullptr; }
+    reset_all(b->d_mlp_w[l], b->d_mlp_b[l]);
     size_t nw = (size_t)sizes[l] * sizes[l + 1];
-    if (hipMalloc((void**)&b->d_mlp_w[l], nw * sizeof(float)) != hipSuccess || hipMalloc((void**)&b->d_mlp_b[l], sizes[l + 1] * sizeof(float)) != hipSuccess) return HB_ENOMEM;
+    if (b->d_mlp_w[l].alloc(nw) != HB_OK || b->d_mlp_b[l].alloc(sizes[l + 1]) != HB_OK) return HB_ENOMEM;
     HB_HIP(hipMemcpy(b->d_mlp_w[l], weights[l], nw * sizeof(float), hipMemcpyHostToDevice));
     HB_HIP(hipMemcpy(b->d_mlp_b[l], biases[l], sizes[l + 1] * sizeof(float), hipMemcpyHostToDevice));
     if (l + 1 < n_layers) maxh = std::max(maxh, sizes[l + 1]);
   }
   for (int i = 0; i < 2; i++) {
-    if (b->d_mlp_h[i]) { HB_IGN(hipFree(b->d_mlp_h[i])); b->d_mlp_h[i] = nullptr; }
-    if (hipMalloc((void**)&b->d_mlp_h[i], (size_t)b->n_env * maxh * sizeof(float)) != hipSuccess) return HB_ENOMEM;
+    b->d_mlp_h[i].reset();
+    if (b->d_mlp_h[i].alloc((size_t)b->n_env * maxh) != HB_OK) return HB_ENOMEM;
   }
-  if (b->d_mlp_act) { HB_IGN(hipFree(b->d_mlp_act)); b->d_mlp_act = nullptr; }
+  b->d_mlp_act.reset();
   if (fused) {
     int widest = 1;
     for (int l = 0; l <= n_layers; l++) widest = std::max(widest, sizes[l]);
     const size_t floats = ((size_t)(b->n_env + 15) / 16 + hb_batch::kPipes) * 32 * (widest + 4);
-    if (hipMalloc((void**)&b->d_mlp_act, floats * sizeof(float)) != hipSuccess) return HB_ENOMEM;
-    HB_HIP(hipMemset(b->d_mlp_act, 0, floats * sizeof(float)));
+    if ((rc = b->d_mlp_act.alloc(floats, /*zero=*/true)) != HB_OK) return rc;
   }
   b->mlp_layers = n_layers;
   b->mlp_fused = fused;
@@ -2537,10 +2526,11 @@ int hb_batch_tune(hb_batch* b, int knob, int value) {
 int hb_diag_enable(hb_batch* b, int on) {
   if (!b) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
-  if (on && !b->d_diag_qacc) {
-    size_t n = b->n_env;
-    if (hipMalloc((void**)&b->d_diag_qacc, n * b->D.dm.nv * sizeof(float)) != hipSuccess || hipMalloc((void**)&b->d_diag_force, n * b->D.dm.nefc_max * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&b->d_diag_contact, n * b->D.dm.ncon_max * kDiagConStride * sizeof(float)) != hipSuccess) return HB_ENOMEM;
+  const size_t n = b->n_env;
+  if (on && (b->d_diag_qacc.alloc(n * b->D.dm.nv) != HB_OK || b->d_diag_force.alloc(n * b->D.dm.nefc_max) != HB_OK ||
+             b->d_diag_contact.alloc(n * b->D.dm.ncon_max * kDiagConStride) != HB_OK)) {
+    reset_all(b->d_diag_qacc, b->d_diag_force, b->d_diag_contact);
+    return HB_ENOMEM;
   }
   b->diag = on != 0;
   return HB_OK;
@@ -2554,9 +2544,9 @@ static int copy_out(hb_batch* b, float* out, const float* dev, size_t n) {
   HB_HIP(hipMemcpy(out, dev, n * sizeof(float), hipMemcpyDeviceToHost));
   return HB_OK;
 }
-int hb_get_qacc(hb_batch* b, float* qacc) { return copy_out(b, qacc, b ? b->d_diag_qacc : nullptr, b ? (size_t)b->n_env * b->D.dm.nv : 0); }
-int hb_get_efc_force(hb_batch* b, float* f) { return copy_out(b, f, b ? b->d_diag_force : nullptr, b ? (size_t)b->n_env * b->D.dm.nefc_max : 0); }
-int hb_get_contacts(hb_batch* b, float* c) { return copy_out(b, c, b ? b->d_diag_contact : nullptr, b ? (size_t)b->n_env * b->D.dm.ncon_max * kDiagConStride : 0); }
+int hb_get_qacc(hb_batch* b, float* qacc) { return copy_out(b, qacc, b ? b->d_diag_qacc.get() : nullptr, b ? (size_t)b->n_env * b->D.dm.nv : 0); }
+int hb_get_efc_force(hb_batch* b, float* f) { return copy_out(b, f, b ? b->d_diag_force.get() : nullptr, b ? (size_t)b->n_env * b->D.dm.nefc_max : 0); }
+int hb_get_contacts(hb_batch* b, float* c) { return copy_out(b, c, b ? b->d_diag_contact.get() : nullptr, b ? (size_t)b->n_env * b->D.dm.ncon_max * kDiagConStride : 0); }
 
 void* hb_dev_alloc(hb_batch* b, uint64_t bytes) {
   if (!b || hipSetDevice(b->device) != hipSuccess) return nullptr;
@@ -2600,11 +2590,7 @@ int hb_get_stamps(hb_batch* b, unsigned long long* out) {
 #ifdef HB_STAMPS
   if (!b || !out) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
-  if (!b->d_stamps) {
-    if (hipMalloc((void**)&b->d_stamps, (size_t)b->n_env * 16 * sizeof(unsigned long long)) != hipSuccess) return HB_ENOMEM;
-    HB_HIP(hipMemset(b->d_stamps, 0, (size_t)b->n_env * 16 * sizeof(unsigned long long)));
-    return HB_OK;  // first call arms the stamps; call again after a step to read them
-  }
+  if (!b->d_stamps) return b->d_stamps.alloc((size_t)b->n_env * 16, /*zero=*/true);  // first call arms the stamps; call again after a step to read them
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   HB_HIP(hipMemcpy(out, b->d_stamps, (size_t)b->n_env * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return HB_OK;
