@@ -176,6 +176,12 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
   dm.disableflags = m.disableflags;
   dm.solver = m.solver; dm.ls_iterations = m.ls_iterations; dm.ls_tolerance = (float)m.ls_tolerance;
   if (!model_variant(m, dm.variant, dm.ncon_max, dm.nefc_max, err)) return false;
+  dm.integrator = m.integrator;
+  if (m.integrator != INT_EULER && m.integrator != INT_RK4) { err = "integrator " + std::to_string(m.integrator) + " is not implemented (Euler = 0, RK4 = 1)"; return false; }
+  if (m.integrator == INT_RK4 && dm.variant != 0) {
+    err = "RK4: only models that step in one kernel (plane / sphere / capsule geoms, condim 1 / 3) are implemented; this model steps in stages (mesh hulls, height fields or condim 4 / 6): use the Euler integrator";
+    return false;
+  }
   dm.mpr_iterations = 50; dm.mpr_tolerance = 1e-6f;  // mjOption.mpr_iterations / mpr_tolerance defaults (mjmodel.h:413,437)
 
   // trees, levels, children, dof masks
@@ -261,6 +267,10 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
   int endB = off;
   // xipos and scom/cdof are read while region B is being written (xfrc, Jacobians): keep xipos out of the alias
   dm.lds_floats = std::max(endA, endB);
+  // RK4: the stage block (start state and the two running sums) behind both regions, so that an RK4 model's layout is the Euler layout
+  // plus a tail and no offset moves
+  dm.o_rk = 0;
+  if (dm.integrator == INT_RK4) { off = dm.lds_floats; dm.o_rk = take(m.nq + 3 * nv); dm.lds_floats = off; }
   if (dm.lds_floats * 4 > 160 * 1024) { err = "model needs more LDS than one CU has"; return false; }
   return true;
   };
@@ -804,7 +814,7 @@ int fork_pipes(hb_batch* b, int nseg) {
 // the batch's model through launch_step; the launched kernel's name stays with the batch (hb_last_kernel)
 hipError_t launch_batch_step(hb_batch* b, const BatchPtrs& P, int nsteps, hipStream_t stream) {
   const DevModel& dm = b->D.dm;
-  return launch_step(b->D.d_dm, dm.variant, dm.solver, dm.nv, dm.lds_floats, P, nsteps, stream, &b->last_kernel);
+  return launch_step(b->D.d_dm, dm.variant, dm.solver, dm.integrator, dm.nv, dm.lds_floats, P, nsteps, stream, &b->last_kernel);
 }
 // one segment's launch of the step kernel, then (heavy-first scheduling, every 4th call) the tiny kernel that
 // orders the segment's next launch by the cost of this one; costs change slowly, and the sort sits on the
@@ -879,7 +889,7 @@ int launch_steps(hb_batch* b, BatchPtrs& P, int nsteps, bool foldable = false) {
   foldable = false;  // (the diagnostic build samples single launches)
 #endif
   foldable = foldable && b->npipe > 1 && cap > 1 && nsteps <= cap && P.ctrl_mode == 0 && !b->time_steps && !b->diag && !P.stamps && P.xfrc_scale == 0.f &&
-             fold_pays(b->D.dm.variant, b->D.dm.solver, b->D.dm.nv, P);
+             fold_pays(b->D.dm.variant, b->D.dm.solver, b->D.dm.integrator, b->D.dm.nv, P);
   if (!foldable) {
     const int rc = flush_steps(b);
     return rc != HB_OK ? rc : launch_steps_now(b, P, nsteps);
@@ -1052,11 +1062,11 @@ int hb_options_get(const hb_model* h, hb_options* o) {
 
 int hb_options_set(hb_model* h, const hb_options* o) {
   if (!h || !o) return HB_EINVAL;
-  if ((o->solver != SOL_PGS && o->solver != SOL_NEWTON) || o->cone != 0 || o->integrator != 0) return HB_EUNSUPPORTED;
+  if ((o->solver != SOL_PGS && o->solver != SOL_NEWTON) || o->cone != 0 || (o->integrator != INT_EULER && o->integrator != INT_RK4)) return HB_EUNSUPPORTED;
   if (!(o->timestep > 0) || !(o->impratio > 0) || o->iterations < 0 || o->ls_iterations < 0 || !(o->ls_tolerance >= 0)) return HB_EINVAL;
   Model& m = h->m;
   m.timestep = o->timestep; memcpy(m.gravity, o->gravity, sizeof o->gravity); m.impratio = o->impratio; m.tolerance = o->tolerance;
-  m.iterations = o->iterations; m.disableflags = o->disableflags; m.solver = o->solver;
+  m.iterations = o->iterations; m.disableflags = o->disableflags; m.solver = o->solver; m.integrator = o->integrator;
   m.ls_iterations = o->ls_iterations; m.ls_tolerance = o->ls_tolerance;
   return HB_OK;
 }
@@ -1307,6 +1317,7 @@ int hb_forward(hb_batch* b, const float* ctrl) {
 
 int hb_inverse_dev(hb_batch* b, const float* qacc_dev, int flags, float* qfrc_inverse_dev, int* warnings_dev) {
   if (!b || !qacc_dev || !qfrc_inverse_dev || (flags & ~HB_INV_DISCRETE)) return HB_EINVAL;
+  if ((flags & HB_INV_DISCRETE) && b->D.dm.integrator != INT_EULER) return HB_EUNSUPPORTED;  // (the discrete inverse is that of the Euler step)
   HB_HIP(hipSetDevice(b->device));
   const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined: the inverse sees the state they leave)
   // a launch of its own, not make_ptrs: nothing of the batch's state, status, counts, orders or noise process is written

@@ -135,6 +135,8 @@ struct DevModel {
   int o_con, o_C, o_efc, o_force;
   int lds_floats;  // total floats per env
   int cstride;     // row stride of C (odd: conflict-free lane-strided access; the last column is zero padding)
+  // mjtIntegrator (0 Euler, 1 RK4) and, RK4 only, the stage block behind both regions: q0[nq] | v0[nv] | sum b V [nv] | sum b F [nv]
+  int integrator, o_rk;
 };
 
 typedef const DevModel HB_CONST& DevModelRef;

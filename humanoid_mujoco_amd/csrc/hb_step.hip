@@ -48,7 +48,10 @@ __device__ __forceinline__ void defer_env(const BatchPtrs& P, int env) {
   } while (0)
 // INV: inverse dynamics (hb_inverse, mj_inverse): the forward stages up to the per-row quantities without the actuators and xfrc_applied,
 // then qfrc_inverse in place of the solver, the integrator and every write of the batch's state, status or counts (nsteps is 1)
-template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0, int INV = 0>
+// INTEG: mjtIntegrator of the instantiation (0 = Euler, 1 = RK4: mj_RungeKutta(4)).  An RK4 step is four passes of the step loop, the
+// forward dynamics at the four stage states, and advances at the end of the fourth (the stage machine sits where mj_Euler does); what
+// belongs to the step and not to a forward pass - controls, noise, the mj_check*s, the sensor read-out - is done in the first pass only.
+template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0, int INV = 0, int INTEG = 0>
 __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P, int nsteps_in, int env_in = -1) {
   const int nsteps = LEAN == 1 ? 1 : nsteps_in;  // (LEAN == 1 is launched for single steps only: the step API; rollouts take LEAN == 2)
   // LEAN (1 = a single step without the constraint-force read-out; 2 = any number of steps, read-out optional): a launch without the optional inputs and outputs (applied forces and their noise, constraint-force / sensor / trajectory
@@ -69,6 +72,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   const unsigned char* const P_env_mask = (LEAN || INV) ? nullptr : P.env_mask;
   const int P_integrate = INV ? 0 : LEAN ? 1 : P.integrate;
   static_assert(SIZED == 0 || (NG == 1 && ((NDENSE == 28 && (COLL == 0 || SOLVER == 0)) || (NDENSE == 20 && COLL == 1 && SOLVER == 2))), "the size-specialised instantiations: the humanoid (classic or variant-1 layout) and the robot (Newton, variant-1 layout)");
+  static_assert(INTEG == 0 || (COLL == 0 && NG == 1 && DEFER == 0 && LEAN == 0 && SIZED == 0 && INV == 0), "RK4: the full kernels of the classic variant");
   static_assert(NG == 1 || SOLVER == 2 || (COLL == 1 && NG == kPgsGroups && DEFER == 0), "PGS on more than one row group: the general variant's kPgsGroups instantiation");
   constexpr int kNR = NG == 1 ? kNefcMax : 64 * NG;  // row capacity of this instantiation
   constexpr int kNC = NG == 1 ? kNconMax : kBigNconMax;  // contact capacity
@@ -131,6 +135,9 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   float* s_AR = lds + M.o_AR;              // PGS on several row groups only: the matrix AR, [kNR][kNR]
   (void)s_AR;
   (void)s_gquat; (void)s_meta;
+  // RK4 only, behind both regions: q0[nq] | v0[nv] | sum b_i V_i [nv] | sum b_i F_i [nv] (the tableau is sub-diagonal: no F_i is kept)
+  float* s_rk = lds + M.o_rk;
+  (void)s_rk;
   constexpr int kCs = 33;            // row stride of C (odd: conflict-free lane-strided access; column 32 is zero padding)
   static_assert(kNefcMax == kGroup - 1, "C holds kNefcMax constraint rows plus the qfrc_smooth row");
   // per-row meta slots
@@ -151,7 +158,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   for (int i = lane; i < nv; i += kGroup) { s_qvel[i] = ld_state(1 + nq + i); s_warm[i] = ld_state(1 + nq + nv + i); }
   int status = 0;
   bool eulerdamp = false;
-  if (!(M_disableflags & (1 << 14))) {
+  if (INTEG == 0 && !(M_disableflags & (1 << 14))) {  // (implicit joint damping is mj_Euler's: mj_RungeKutta has none)
     bool d = false;
     for (int i = lane; i < nv; i += kGroup) d |= M.dof_damping[i] > 0.f;
     eulerdamp = __any(d);
@@ -168,6 +175,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   // mj_resetData inside a step (mj_check*, mujoco.h:301-307) also zeroes ctrl and xfrc_applied: the rest of that step runs without controls
   bool ctrl_zeroed = false;  // this pass of the step runs on reset data
   bool redo = false;         // this pass is the second mj_forward of a step whose first one gave a bad qacc (mj_checkAcc)
+  int stage = 0;             // RK4: which of the step's four forward passes this one is (Euler: always 0)
   for (int step = 0; step < nsteps; step++) {
     if constexpr (LEAN != 1) {
       // a launch of several steps whose waves are all resident (hb_api.cpp folds step calls into such launches): the two waves of a SIMD are
@@ -203,7 +211,9 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     if (lane < nv) { pf_dA = M.drec[3 * lane]; pf_dB = M.drec[3 * lane + 1]; }
     HB_STAMP(0);
     // ---------------------------------------------------------------- controls
-    if (ctrl_mode == 2) {
+    if (INTEG != 0 && stage != 0) {
+      // (a later stage of an RK4 step: the step's controls are in place and its state has been checked)
+    } else if (ctrl_mode == 2) {
       int idx = 1 + ctrl_t0 + step + 1000 * (P.env_offset + env);
       for (int i = lane; i < HB_SZ(nu); i += kGroup) s_ctrl[i] = 2.f * halton(idx, i + 2) - 1.f;
     } else {
@@ -214,7 +224,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       if (LEAN != 1 && ctrl_mode == 3 && step + 1 < nsteps && lane < HB_SZ(nu)) ctrl_pf = P.ctrl_tab[step + 1][(size_t)env * HB_SZ(nu) + lane];
     }
     // ---------------------------------------------------------------- mj_checkPos / mj_checkVel
-    {
+    if (INTEG == 0 || stage == 0) {
       bool badp = false, badv = false;
       for (int i = lane; i < nq; i += kGroup) { float v = s_qpos[i]; badp |= !(fabsf(v) <= HB_MAXVAL); }
       for (int i = lane; i < nv; i += kGroup) { float v = s_qvel[i]; badv |= !(fabsf(v) <= HB_MAXVAL); }
@@ -470,7 +480,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     }
     if (!(M_disableflags & (1 << 6))) for (int i = 0; i < 3; i++) mycacc[3 + i] -= M.gravity[i];  // the world's cacc
     // sensor read-out for planner residuals (mj_sensorPos/Vel of framepos, subtreecom, subtreelinvel)
-    if (P_sensor_out) {
+    if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // (RK4: the sensors of mj_step are those of the first stage)
       float* so = P_sensor_out + ((size_t)step * P.n_env + env) * P.sensor_stride;
       for (int k = 0; k < P.sensor_nframe; k++) {
         const int sb = P.sensor_body[k];
@@ -622,7 +632,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     gsync();
     // xfrc_applied: Cartesian wrench at each body com (mj_xfrcAccumulate)
     if (P_xfrc) {
-      if (P_xfrc_scale > 0.f && P_integrate && !P.stage.rerun) {  // (a plain mj_forward - hb_forward, the terminal read-out - leaves the process where it is;
+      if (P_xfrc_scale > 0.f && P_integrate && !P.stage.rerun && (INTEG == 0 || stage == 0)) {  // (a plain mj_forward - hb_forward, the terminal read-out - leaves the process where it is;
         // the rerun of a deferred env-step finds the process already advanced by the fast pass)
         // Trajectory::NoisyRollout's perturbation (trajectory.cc:147-156): Ornstein-Uhlenbeck noise on every xfrc_applied entry
         float* xw = P_xfrc + (size_t)env * nb * 6;
@@ -1748,7 +1758,8 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       gsync();
     }
     // mj_checkAcc (mujoco.h:307): a bad qacc resets the data and runs mj_forward again; the step then integrates that result
-    {
+    // (RK4: after the first stage only; the step then runs all four stages from the reset state)
+    if (INTEG == 0 || stage == 0) {
       bool bad = false;
       for (int i = lane; i < nv; i += kGroup) bad |= !(fabsf(s_v0[i]) <= HB_MAXVAL);
       if (__any(bad)) {
@@ -1773,8 +1784,11 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       }
     }
     redo = false;
-    ctrl_zeroed = false;
+    // RK4: what a caller reads after the step is the last forward pass, as mjData after mj_step
+    const bool last_pass = INTEG == 0 || !P_integrate || stage == 3;
+    if (last_pass) ctrl_zeroed = false;
     // diagnostics of this step (parity tests)
+    if (last_pass) {
     if (P_diag_qacc) for (int i = lane; i < nv; i += kGroup) P_diag_qacc[(size_t)env * nv + i] = s_v0[i];
     if (P_diag_force && lane < kNR) P_diag_force[(size_t)env * kNR + lane] = rowact ? force : 0.f;
     if (P_diag_contact) {
@@ -1793,8 +1807,61 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       }
     }
     if (lane == 0) { int* c = P.counts + kCountStride * (size_t)env; c[0] = ncon; c[1] = nefc; c[2] = niter; c[3] = nefc * (niter + 4); c[4] = selfcol; }
+    }
 
     HB_STAMP(14);
+    if constexpr (INTEG == 1) {
+      if (P_integrate) {
+        // ---------------------------------------------------------------- mj_RungeKutta(4): tableau A = diag(1/2, 1/2, 1) below the
+        // diagonal, b = (1/6, 1/3, 1/3, 1/6).  Stage i has run at (Q_i, V_i) and left F_i = qacc in s_v0:
+        //   Q_{i+1} = integratePos(q0, V_i, a h),  V_{i+1} = v0 + a h F_i;   after stage 3: qpos' = integratePos(q0, sum b_i V_i, h),
+        //   qvel' = v0 + h sum b_i F_i, qacc_warmstart' = F_3 (every stage has warm-started from the step's incoming one)
+        float* r_q0 = s_rk; float* r_v0 = s_rk + nq; float* r_sv = r_v0 + nv; float* r_sf = r_sv + nv;
+        const float bw = (stage == 0 || stage == 3) ? 1.f / 6.f : 1.f / 3.f;
+        const float hh = M.timestep * (stage < 2 ? 0.5f : 1.f);
+        if (stage == 0) {
+          for (int i = lane; i < nq; i += kGroup) r_q0[i] = s_qpos[i];
+          for (int i = lane; i < nv; i += kGroup) { r_v0[i] = s_qvel[i]; r_sv[i] = 0.f; r_sf[i] = 0.f; }
+        }
+        for (int i = lane; i < nv; i += kGroup) {
+          const float sv = r_sv[i] + bw * s_qvel[i], sf = r_sf[i] + bw * s_v0[i];
+          r_sv[i] = sv; r_sf[i] = sf;
+          s_v2[i] = stage < 3 ? s_qvel[i] : sv;                             // the velocity the positions advance along
+          s_qvel[i] = r_v0[i] + hh * (stage < 3 ? s_v0[i] : sf);
+          if (stage == 3) s_warm[i] = s_v0[i];
+        }
+        for (int i = lane; i < nq; i += kGroup) s_qpos[i] = r_q0[i];
+        gsync();
+        // mj_integratePos (quaternions through the tangent space), the loop of mj_advance below on another velocity and time: kept apart,
+        // because sharing it through a function moves the Euler kernels' register allocation (tools/kernel_resources.sh)
+        for (int j = lane; j < HB_SZ(njnt); j += kGroup) {
+          int qa = M.jnt_qposadr[j], da = M.jnt_dofadr[j];
+          if (M.jnt_type[j] == 0) {
+            for (int i = 0; i < 3; i++) s_qpos[qa + i] += hh * s_v2[da + i];
+            float n;
+            V3 w = normalized(ld3(s_v2 + da + 3), &n);
+            Q4 q = qnormalize(ldq(s_qpos + qa + 3));
+            stq(s_qpos + qa + 3, qmul(q, axisangle(w, hh * n)));
+          } else s_qpos[qa] += hh * s_v2[da];
+        }
+        gsync();
+        if (stage < 3) {  // the next stage: another pass of this step (the loop increment undoes the decrement)
+          stage++;
+          step--;
+          continue;
+        }
+        stage = 0;
+        time += M.timestep;
+        if (P_qpos_out) {
+          float* o = P_qpos_out + ((size_t)step * P.n_env + env) * nq;
+          for (int i = lane; i < nq; i += kGroup) o[i] = s_qpos[i];
+        }
+        if (P_qvel_out) {
+          float* o = P_qvel_out + ((size_t)step * P.n_env + env) * nv;
+          for (int i = lane; i < nv; i += kGroup) o[i] = s_qvel[i];
+        }
+      }
+    } else
     if (P_integrate) {
       // ---------------------------------------------------------------- mj_Euler: (M + h diag(damping)) qacc' = qfrc_smooth + qfrc_constraint
       // With H = M + h B and M qacc = qfrc_smooth + qfrc_constraint the solve is the same as
@@ -1905,7 +1972,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
 
 #undef HB_SZ
 // ---- The kernel table: one row per step_body instantiation.  The __global__ definitions, the host array the dispatch looks kernels up in
-// (select_step) and the kernels' names (hb_last_kernel) are all generated from these two lists.  RERUN: the second pass of a staged step,
+// (select_step) and the kernels' names (hb_last_kernel) are all generated from these lists.  RERUN: the second pass of a staged step,
 // a few waves that walk the list of deferred envs (HB_STEP_OR_RERUN).  VGPRS: amdgpu_num_vgpr, counted per half of the file (0: no cap).
 //  K(name,                             SOLVER, NDENSE, COLL, NG,         DEFER, LEAN, SIZED, INV, WAVES, VGPRS, RERUN)
 #define HB_STEP_KERNELS(K) /* (Mp, P, nsteps) */                                                                                           \
@@ -1953,6 +2020,12 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   K(hb_inverse_pgs_big_kernel,          2,      28,     1,    kPgsGroups, 2,     0,    0,     1,   1,     0,     0)                         \
   K(hb_inverse_big20_kernel,            2,      20,     1,    kBigGroups, 2,     0,    0,     1,   1,     0,     0)                         \
   K(hb_inverse_big28_kernel,            2,      28,     1,    kBigGroups, 2,     0,    0,     1,   1,     0,     0)
+// the RK4 integrator (step_body's INTEG; mjINT_RK4): the full kernels of the classic variant, one per solver and dense order
+#define HB_RK4_KERNELS(K) /* (Mp, P, nsteps) */                                                                                            \
+  K(hb_rk4_kernel,                      0,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
+  K(hb_rk4_32_kernel,                   0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
+  K(hb_rk4_newton28_kernel,             2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
+  K(hb_rk4_newton32_kernel,             2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
 
 // (the entry calls step_body directly: a forwarding function template in between changes register allocation and scheduling)
 #define HB_STEP_BODY_0(...) step_body<__VA_ARGS__>(Mp, P, nsteps)
@@ -1961,16 +2034,20 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_BODY_##R(S, ND, C, G, D, L, Z, I); }
 #define HB_DEFINE_INVERSE(name, S, ND, C, G, D, L, Z, I, W, V, R) \
   __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P) { step_body<S, ND, C, G, D, L, Z, I>(Mp, P, 1); }
+#define HB_DEFINE_RK4(name, S, ND, C, G, D, L, Z, I, W, V, R) \
+  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<S, ND, C, G, D, L, Z, I, 1>(Mp, P, nsteps); }
 HB_STEP_KERNELS(HB_DEFINE_STEP)
 HB_INVERSE_KERNELS(HB_DEFINE_INVERSE)
+HB_RK4_KERNELS(HB_DEFINE_RK4)
 
 struct StepConfig {
-  int solver, ndense, coll, ng, defer, lean, sized, inv;
-  bool operator==(const StepConfig& o) const { return solver == o.solver && ndense == o.ndense && coll == o.coll && ng == o.ng && defer == o.defer && lean == o.lean && sized == o.sized && inv == o.inv; }
+  int solver, ndense, coll, ng, defer, lean, sized, inv, integ;
+  bool operator==(const StepConfig& o) const { return solver == o.solver && ndense == o.ndense && coll == o.coll && ng == o.ng && defer == o.defer && lean == o.lean && sized == o.sized && inv == o.inv && integ == o.integ; }
 };
 struct StepKernel { const char* name; const void* fn; StepConfig cfg; bool rerun; };
-#define HB_STEP_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I}, R != 0},
-static const StepKernel kStepKernels[] = {HB_STEP_KERNELS(HB_STEP_ROW) HB_INVERSE_KERNELS(HB_STEP_ROW)};
+#define HB_STEP_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 0}, R != 0},
+#define HB_RK4_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 1}, R != 0},
+static const StepKernel kStepKernels[] = {HB_STEP_KERNELS(HB_STEP_ROW) HB_INVERSE_KERNELS(HB_STEP_ROW) HB_RK4_KERNELS(HB_RK4_ROW)};
 static const StepKernel* find_step_kernel(const StepConfig& c) {
   for (const StepKernel& k : kStepKernels) if (k.cfg == c) return &k;
   return nullptr;
@@ -2008,7 +2085,7 @@ static bool lean_launch(const BatchPtrs& P, bool with_qfrc = false) {
 // runs on the one-group model StageBufs::dm_fast with its own LDS size: kernel, model and LDS size are chosen together), or the inverse.
 enum class StepPass { Main, Fast, Inverse };
 struct StepChoice { const StepKernel* kernel; bool duo; const DevModel* M_dev; size_t shmem; };  // (duo: launch_step_duo, no table row)
-static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant, int solver, int nv, size_t shmem, const BatchPtrs& P, int nsteps) {
+static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant, int solver, int integrator, int nv, size_t shmem, const BatchPtrs& P, int nsteps) {
   StepConfig c = variant == 1   ? StepConfig{0, 28, 1, 1}
                  : variant == 3 ? StepConfig{0, 28, 1, kPgsGroups}
                  : variant == 2 ? StepConfig{2, nv <= 20 ? 20 : 28, 1, kBigGroups}
@@ -2016,6 +2093,12 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant,
   if (pass == StepPass::Inverse) {
     c.solver = 2; c.defer = c.coll ? 2 : 0; c.inv = 1;
     return {find_step_kernel(c), false, M_dev, shmem};
+  }
+  // RK4: the full kernel of the solver and dense order, whatever the launch looks like (no staged, lean, size-specialised or
+  // two-envs-per-wave instantiation has it; a staged model is refused when its batch is created)
+  if (integrator != 0) {
+    c.integ = integrator;
+    return {variant == 0 && pass == StepPass::Main ? find_step_kernel(c) : nullptr, false, M_dev, shmem};
   }
   if (pass == StepPass::Fast) {
     c.ng = 1; c.defer = variant == 1 ? 2 : 1;
@@ -2035,9 +2118,9 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant,
 }
 // The one launch site.  Every launch hands back its kernel's name (hb_last_kernel: tests and bench.py name the kernel they measured by
 // what the library says it launched, not by a literal).
-static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, int variant, int solver, int nv, size_t shmem, const BatchPtrs& P, int nsteps, hipStream_t stream,
+static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, int variant, int solver, int integrator, int nv, size_t shmem, const BatchPtrs& P, int nsteps, hipStream_t stream,
                               const char** kernel) {
-  const StepChoice s = select_step(pass, M_dev, variant, solver, nv, shmem, P, nsteps);
+  const StepChoice s = select_step(pass, M_dev, variant, solver, integrator, nv, shmem, P, nsteps);
   if (s.duo) return launch_step_duo(s.M_dev, P, nsteps, stream, kernel);
   if (!s.kernel) return hipErrorInvalidDeviceFunction;
   (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
@@ -2056,20 +2139,20 @@ static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, int variant,
 // steps); two-envs-per-wave waves, for the models that have that kernel: up to twice as many envs (4096: 67 against 78).  Beyond one
 // round a multi-step launch is no faster than pipelined single steps, and slower when its last round is part empty (4608 envs: 104
 // against 85) - profiles/r04_fold_sizes_by_batch.txt.
-bool fold_pays(int variant, int solver, int nv, const BatchPtrs& P) {
+bool fold_pays(int variant, int solver, int integrator, int nv, const BatchPtrs& P) {
   if (variant != 0) return false;
   if (P.n_env <= wave_slots()) return true;
   // (would the folded launch be a duo launch?  Step calls that read the constraint forces out are not folded onto it)
-  const bool duo_kernel = !P.qfrc_out && select_step(StepPass::Main, nullptr, variant, solver, nv, 0, P, 2).duo;
+  const bool duo_kernel = !P.qfrc_out && select_step(StepPass::Main, nullptr, variant, solver, integrator, nv, 0, P, 2).duo;
   return duo_kernel && (P.n_env + 1) / 2 <= wave_slots();
 }
 
 // One step launch of the classic variant covers all nsteps.  A general variant with stage buffers runs every step as three launches
 // on the same stream: poses + work items, narrowphase (a small kernel at 2-4x the step kernel's occupancy: its time is chains of
 // dependent loads along the hulls' edge graphs), then the step kernel, which appends the results instead of colliding.
-hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int nv, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel) {
+hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integrator, int nv, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel) {
   const size_t shmem = (size_t)lds_floats * sizeof(float);
-  if (variant == 0 || !P.stage.result) return launch_pass(StepPass::Main, M_dev, variant, solver, nv, shmem, P, nsteps, stream, kernel);
+  if (variant == 0 || !P.stage.result) return launch_pass(StepPass::Main, M_dev, variant, solver, integrator, nv, shmem, P, nsteps, stream, kernel);
   for (int t = 0; t < nsteps; t++) {
     BatchPtrs Q = P;
     Q.t0 = P.t0 + t;
@@ -2086,11 +2169,11 @@ hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int nv, i
     const bool fast = variant == 1 ? Q.stage.defer != nullptr : Q.stage.dm_fast != nullptr;
     const char* second = nullptr;  // (a staged step is named after its fast-pass kernel: the one that steps almost every env)
     if (fast) {
-      e = launch_pass(StepPass::Fast, M_dev, variant, solver, nv, shmem, Q, 1, stream, kernel);
+      e = launch_pass(StepPass::Fast, M_dev, variant, solver, integrator, nv, shmem, Q, 1, stream, kernel);
       if (e != hipSuccess) return e;
       Q.stage.rerun = 1;
     }
-    e = launch_pass(StepPass::Main, M_dev, variant, solver, nv, shmem, Q, 1, stream, fast ? &second : kernel);
+    e = launch_pass(StepPass::Main, M_dev, variant, solver, integrator, nv, shmem, Q, 1, stream, fast ? &second : kernel);
     if (e != hipSuccess) return e;
     // a long rollout is one call: refresh the heavy-first orders of its launches along the way (the caller does it between calls)
     if (P.order && P.order2 && (t & 7) == 7 && t + 1 < nsteps) {
@@ -2109,7 +2192,7 @@ hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int lds_fl
     const hipError_t e = launch_pose_narrow(M_dev, P, stream);
     if (e != hipSuccess) return e;
   }
-  return launch_pass(StepPass::Inverse, M_dev, variant, /*solver=*/2, nv, (size_t)lds_floats * sizeof(float), P, 1, stream, kernel);
+  return launch_pass(StepPass::Inverse, M_dev, variant, /*solver=*/2, /*integrator=*/0, nv, (size_t)lds_floats * sizeof(float), P, 1, stream, kernel);
 }
 // every step and inverse instantiation: a layout over 64 KB must launch whichever of them the dispatch picks
 hipError_t set_step_lds_limit(int bytes) {

@@ -571,7 +571,9 @@ bool read_option(Ctx& c, const XmlNode& n) {
   s = a.str("cone", "pyramidal");
   if (s != "pyramidal") return c.fail("mjcf: only the pyramidal friction cone is implemented");
   s = a.str("integrator", "Euler");
-  if (s != "Euler") return c.fail("mjcf: only the Euler integrator is implemented");
+  if (s == "Euler") m.integrator = INT_EULER;
+  else if (s == "RK4") m.integrator = INT_RK4;
+  else return c.fail("mjcf: integrator '" + s + "' is not implemented; this engine has Euler and RK4");
   if (const XmlNode* f = n.child("flag")) {
     struct { const char* name; int bit; } flags[] = {
         {"constraint", DSBL_CONSTRAINT}, {"limit", DSBL_LIMIT}, {"contact", DSBL_CONTACT}, {"passive", DSBL_PASSIVE},

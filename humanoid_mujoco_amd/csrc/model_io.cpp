@@ -141,6 +141,9 @@ bool validate_model(const Model& m, std::string& err) {
   if (m.nq < 0 || m.nv < 0 || m.nu < 0 || m.njnt < 0 || m.ngeom < 0 || m.ntendon < 0 || m.nwrap < 0 || m.nkey < 0 || m.nexclude < 0 || m.npair < 0 ||
       m.nhfield < 0 || m.nhfielddata < 0 || m.nM < 0 || m.nmesh < 0 || m.nmeshvert < 0 || m.nmeshnbr < 0)
     return bad("negative size");
+  // (unsupported options are errors, never silently dropped: an integrator or cone this engine does not have would otherwise be stepped as Euler / pyramidal)
+  if (m.integrator != INT_EULER && m.integrator != INT_RK4) return bad("integrator " + std::to_string(m.integrator) + " is not implemented (Euler = 0, RK4 = 1)");
+  if (m.cone != 0) return bad("cone " + std::to_string(m.cone) + " is not implemented (pyramidal = 0)");
   if (m.nq > 4096 || m.nv > 4096 || m.nu > 4096 || m.njnt > 4096 || m.ngeom > 4096 || m.nwrap > 65536 || m.npair > (1 << 20)) return bad("size out of range");
   struct { const char* name; size_t have, want; } lens[] = {
 #define HB_LEN(x, n) {#x, m.x.size(), (size_t)(n)}

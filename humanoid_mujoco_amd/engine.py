@@ -21,6 +21,7 @@ STATE_TIME, STATE_QPOS, STATE_QVEL, STATE_WARMSTART, STATE_XFRC_APPLIED = 1 << 0
 STATE_PHYSICS = STATE_QPOS | STATE_QVEL
 STATE_INTEGRATION = STATE_TIME | STATE_QPOS | STATE_QVEL | STATE_WARMSTART
 HB_INV_DISCRETE = 1  # hb_inverse flags: mjENBL_INVDISCRETE
+INT_EULER, INT_RK4 = 0, 1  # hb_options.integrator (mjtIntegrator): Model.set_opt(integrator=...)
 
 # mjtDisableBit (simulation/mujoco/include/mujoco/mjmodel.h:50-68)
 DSBL_CONSTRAINT, DSBL_LIMIT, DSBL_CONTACT, DSBL_PASSIVE, DSBL_GRAVITY = 1 << 0, 1 << 3, 1 << 4, 1 << 5, 1 << 6

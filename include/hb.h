@@ -29,6 +29,10 @@ extern "C" {
 #define HB_ENODEVICE (-2) /* no usable HIP device / HIP call failed */
 #define HB_ENOMEM (-3)
 #define HB_EUNSUPPORTED (-4)
+
+/* hb_options.integrator (mjtIntegrator, mjmodel.h:138-143) */
+#define HB_INT_EULER 0 /* mjINT_EULER */
+#define HB_INT_RK4 1   /* mjINT_RK4 */
 #define HB_EIO (-5)
 
 /* per-env status bits, the batched counterpart of mjData.warning[] (mjdata.h:54-65,185) */
@@ -61,7 +65,8 @@ typedef struct hb_options {
   int iterations;    /* PGS sweep cap / Newton iteration cap */
   int solver;        /* 0 = PGS (mjSOL_PGS), 2 = Newton (mjSOL_NEWTON, the reference's default); CG is not implemented */
   int cone;          /* 0 = pyramidal; the only cone implemented */
-  int integrator;    /* 0 = Euler (semi-implicit, implicit joint damping) */
+  int integrator;    /* HB_INT_EULER (semi-implicit, implicit joint damping) or HB_INT_RK4 (models that step in one kernel: see hb_step);
+                      * implicit (2) and implicitfast (3) are not implemented */
   int disableflags;  /* mjtDisableBit (mjmodel.h:50-68) */
   int ls_iterations;   /* Newton: cap on line-search evaluations per iteration (mjOption.ls_iterations, mjmodel.h:434) */
   double ls_tolerance; /* Newton: line-search slope tolerance relative to `tolerance` (mjmodel.h:411) */
@@ -141,7 +146,16 @@ int hb_reset(hb_batch* b, const uint8_t* mask, int keyframe, int perturb, int en
 
 /* Replaces `for e: mju_copy(d->ctrl, ...); mj_step(m, d)` (mujoco.h:120; call sites
  * simulation/cpu_env.py:683-684, simulation/mujoco/sample/testspeed.cc:93-96).
- * ctrl: env-major [n_env][nu] float32, applied for n_substeps consecutive steps. */
+ * ctrl: env-major [n_env][nu] float32, applied for n_substeps consecutive steps.
+ * With integrator HB_INT_RK4 a step is mj_RungeKutta(4): four forward passes (collision, constraint rows and solver in each) at the
+ * stage states, combined by the classic tableau, so it costs about four Euler steps; no implicit joint damping (mjDSBL_EULERDAMP has
+ * no effect).  ctrl, xfrc_applied (rollout noise: one draw per step) and qacc_warmstart are held for all four stages; the warm start is
+ * replaced once, by the last stage's qacc.  The position / velocity checks run at the start of the step and the acceleration check
+ * after the first stage only.  What is read after the step is what mjData holds after mj_step: sensors (hb_rollout_sensors, the task
+ * residuals, hb_sensors) are those of the FIRST stage; everything else - hb_get_qacc, hb_get_efc_force, hb_get_contacts, hb_get_counts,
+ * the env adapter's joint torques - is that of the LAST stage.  HB_WARN_CONTACTFULL / HB_WARN_CNSTRFULL accumulate over all stages.
+ * RK4 exists for models that step in one kernel (plane / sphere / capsule geoms, condim 1 / 3): for a model that steps in stages (mesh
+ * hulls, height fields, condim 4 / 6) hb_batch_create fails and says so. */
 int hb_step(hb_batch* b, const float* ctrl, int n_substeps);
 /* The same with the controls already in device memory, asynchronous: the call returns at once, its results are there after hb_batch_sync
  * or behind anything enqueued on hb_batch_stream later, and ctrl_dev must stay allocated and untouched until then.  On a PIPELINED batch
@@ -172,7 +186,8 @@ int hb_forward(hb_batch* b, const float* ctrl);
  * batch's qpos / qvel exactly as hb_forward computes them (per-env model parameters included).  ctrl and xfrc_applied do not enter:
  * for the qacc of hb_forward, qfrc_inverse is qfrc_actuator + J' xfrc_applied.  qacc and qfrc_inverse are env-major [n_env][nv].
  * flags HB_INV_DISCRETE (mjENBL_INVDISCRETE): qacc is (qvel' - qvel) / h of this engine's Euler step with implicit damping, and is
- * turned into the continuous acceleration M^-1 (M + h diag(damping)) qacc first.  warnings (nullable) receives per env the
+ * turned into the continuous acceleration M^-1 (M + h diag(damping)) qacc first (defined for the Euler step only: HB_EUNSUPPORTED on a
+ * model whose integrator is HB_INT_RK4).  warnings (nullable) receives per env the
  * HB_WARN_CONTACTFULL / HB_WARN_CNSTRFULL bits of rows this call dropped.  The call is a pure function of the batch: state, controls,
  * xfrc_applied, status and warning words, env adapter and heavy-first orders are left as they are.  Step calls held back (hb_step_dev)
  * are launched first and the pipes joined, as for every other call.  hb_last_kernel names the inverse kernel.
