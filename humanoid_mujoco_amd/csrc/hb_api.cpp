@@ -653,6 +653,10 @@ struct hb_batch {
   unsigned xfrc_seed = 0, xfrc_calls = 0;
   DevBuf<float> d_sensor_out;
   bool diag = false;
+  // contact-force read-out (hb_contact_readout): [n_env][ncon_max][6] and [n_env][nbody][6]; a sensor spec with touch / contact-force
+  // entries allocates them as well and hands them to its own launches only
+  DevBuf<float> d_contact_force, d_body_contact;
+  bool contact_readout = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   DevBuf<unsigned long long> d_stamps;
   // staged step of the general variants: the buffers, and the kernel argument that points into them (all null: fused)
@@ -746,6 +750,8 @@ BatchPtrs make_ptrs(hb_batch* b) {
   memset(&P, 0, sizeof P);
   P.state = b->d_state; P.status = b->d_status; P.counts = b->d_counts; P.xfrc = b->d_xfrc; P.qfrc_out = b->d_qfrc;
   if (b->diag) { P.diag_qacc = b->d_diag_qacc; P.diag_force = b->d_diag_force; P.diag_contact = b->d_diag_contact; }
+  if (b->contact_readout) { P.contact_force = b->d_contact_force; P.body_contact = b->d_body_contact; }
+  P.cfrc_ncon = b->D.dm.ncon_max;
   P.n_env = b->n_env;
   P.integrate = 1;
   if (b->schedule && b->order_mode) { P.order = b->d_order; P.order2 = staged_on(b) ? b->d_order2.get() : nullptr; }
@@ -1699,7 +1705,19 @@ int hb_state_from_proto(hb_batch* b, int env, const unsigned char* buf, int len)
 int hb_sensor_size(const hb_sensor_spec* spec) {
   if (!spec || spec->n_framepos < 0 || spec->n_framepos > HB_MAX_FRAMEPOS) return HB_EINVAL;
   if (spec->n_frameaxis < 0 || spec->n_frameaxis > 8 || spec->n_framelinvel < 0 || spec->n_framelinvel > 8 || spec->n_subtreelinvel < 0 || spec->n_subtreelinvel > 4) return HB_EINVAL;
-  return 3 * spec->n_framepos + (spec->subtree_body >= 0 ? 6 : 0) + 3 * (spec->n_frameaxis + spec->n_framelinvel + spec->n_subtreelinvel);
+  if (spec->n_touch < 0 || spec->n_touch > 8 || spec->n_contactforce < 0 || spec->n_contactforce > 4) return HB_EINVAL;
+  return 3 * spec->n_framepos + (spec->subtree_body >= 0 ? 6 : 0) + 3 * (spec->n_frameaxis + spec->n_framelinvel + spec->n_subtreelinvel) + spec->n_touch +
+         3 * spec->n_contactforce;
+}
+
+// the two buffers of the contact-force read-out: both there or neither
+static int alloc_contact_readout(hb_batch* b) {
+  const size_t n = b->n_env;
+  if (b->d_contact_force.alloc(n * b->D.dm.ncon_max * 6, true) != HB_OK || b->d_body_contact.alloc(n * b->D.dm.nbody * 6, true) != HB_OK) {
+    reset_all(b->d_contact_force, b->d_body_contact);
+    return HB_ENOMEM;
+  }
+  return HB_OK;
 }
 
 // fills the sensor fields of P and sizes the device read-out buffer for T steps
@@ -1741,6 +1759,20 @@ static int sensor_setup(hb_batch* b, const hb_sensor_spec* spec, int T, BatchPtr
         if (a == root) { mask |= 1ull << bd; mass += m.body_mass[bd]; break; }
     P.sensor_submask[k] = mask;
     P.sensor_subinv[k] = mass > 1e-15 ? (float)(1.0 / mass) : 0.f;
+  }
+  // touch / contact-force entries: written by the step kernel's contact-force epilogue, so the launch carries the read-out buffers
+  P.sensor_ntouch = spec->n_touch; P.sensor_ncfrc = spec->n_contactforce;
+  for (int k = 0; k < spec->n_touch; k++) {
+    if (spec->touch_body[k] < 0 || spec->touch_body[k] >= m.nbody) return HB_EINVAL;
+    P.sensor_touch_body[k] = spec->touch_body[k];
+  }
+  for (int k = 0; k < spec->n_contactforce; k++) {
+    if (spec->contactforce_body[k] < 0 || spec->contactforce_body[k] >= m.nbody) return HB_EINVAL;
+    P.sensor_cfrc_body[k] = spec->contactforce_body[k];
+  }
+  if (spec->n_touch + spec->n_contactforce > 0) {
+    if (alloc_contact_readout(b) != HB_OK) return HB_ENOMEM;
+    P.contact_force = b->d_contact_force; P.body_contact = b->d_body_contact;
   }
   return HB_OK;
 }
@@ -2544,6 +2576,32 @@ int hb_diag_enable(hb_batch* b, int on) {
     return HB_ENOMEM;
   }
   b->diag = on != 0;
+  return HB_OK;
+}
+
+int hb_contact_readout(hb_batch* b, int on) {
+  if (!b) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  (void)main_stream(b);  // from the next launch on: step calls held back are launched as they were made
+  if (on && alloc_contact_readout(b) != HB_OK) return HB_ENOMEM;
+  b->contact_readout = on != 0;
+  return HB_OK;
+}
+static int contact_out(hb_batch* b, float* out, const float* dev, size_t n) {
+  if (!b || !out || !b->contact_readout || !dev) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  HB_HIP(hipMemcpy(out, dev, n * sizeof(float), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+int hb_get_contact_force(hb_batch* b, float* out) { return contact_out(b, out, b ? b->d_contact_force.get() : nullptr, b ? (size_t)b->n_env * b->D.dm.ncon_max * 6 : 0); }
+int hb_get_body_contact(hb_batch* b, float* out) { return contact_out(b, out, b ? b->d_body_contact.get() : nullptr, b ? (size_t)b->n_env * b->D.dm.nbody * 6 : 0); }
+int hb_contact_readout_dev(hb_batch* b, const float** contact_force_dev, const float** body_contact_dev) {
+  if (!b || !b->contact_readout) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  (void)main_stream(b);  // (joins like hb_batch_stream: work enqueued on the batch's stream from here on follows every step call made so far)
+  if (contact_force_dev) *contact_force_dev = b->d_contact_force;
+  if (body_contact_dev) *body_contact_dev = b->d_body_contact;
   return HB_OK;
 }
 

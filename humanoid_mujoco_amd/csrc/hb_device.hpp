@@ -365,6 +365,16 @@ struct BatchPtrs {
   float* inv_out;
   int* inv_warn;
   int inv_flags;
+  // contact-force read-out (hb_contact_readout), both null or both set: mj_contactForce of every contact, [n_env][cfrc_ncon][6] in the
+  // contact frame (cfrc_ncon: the MODEL's contact capacity, whichever kernel of a staged step writes the env), and the bodies' contact
+  // wrenches, [n_env][nbody][6] = force | torque about the body's xipos, world axes.  A launch that carries them takes a full kernel.
+  float* contact_force;
+  float* body_contact;
+  int cfrc_ncon;
+  // ... and their sensor entries, behind every other read-out of a sensor row: the normal-force sum of a body's contacts (one float
+  // each), then the force part of a body's contact wrench (three floats each)
+  int sensor_ntouch, sensor_touch_body[8];
+  int sensor_ncfrc, sensor_cfrc_body[4];
 };
 
 }  // namespace hb

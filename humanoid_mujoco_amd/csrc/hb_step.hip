@@ -67,6 +67,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   float* const P_diag_qacc = (LEAN || INV) ? nullptr : P.diag_qacc;
   float* const P_diag_force = (LEAN || INV) ? nullptr : P.diag_force;
   float* const P_diag_contact = (LEAN || INV) ? nullptr : P.diag_contact;
+  float* const P_cfrc = (LEAN || INV) ? nullptr : P.contact_force;  // contact-force read-out (hb_contact_readout); P.body_contact comes with it
   const float* const P_dr = LEAN ? nullptr : P.dr;
   const int P_dr_stride = LEAN ? 0 : P.dr_stride;
   const unsigned char* const P_env_mask = (LEAN || INV) ? nullptr : P.env_mask;
@@ -479,6 +480,14 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       gsync();
     }
     if (!(M_disableflags & (1 << 6))) for (int i = 0; i < 3; i++) mycacc[3 + i] -= M.gravity[i];  // the world's cacc
+    // contact-force read-out: the wrench of body b is taken about xipos[b], which the constraint region overwrites before the solver
+    // ends.  Lane b parks it in the torque half of its own output row and reads it back in the epilogue behind the solver (the same
+    // lane, the same addresses: program order; no LDS and no register is held across the solver for it)
+    if (P_cfrc && lane < nb) {
+      float* w = P.body_contact + ((size_t)env * nb + lane) * 6;
+      const V3 x = ld3(s_xipos + 3 * lane);
+      w[3] = x.x; w[4] = x.y; w[5] = x.z;
+    }
     // sensor read-out for planner residuals (mj_sensorPos/Vel of framepos, subtreecom, subtreelinvel)
     if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // (RK4: the sensors of mj_step are those of the first stage)
       float* so = P_sensor_out + ((size_t)step * P.n_env + env) * P.sensor_stride;
@@ -510,6 +519,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
           const float vx = wave_sum(mom.x) * im, vy = wave_sum(mom.y) * im, vz = wave_sum(mom.z) * im;
           if (lane < 3) so[o + lane] = lane == 0 ? vx : (lane == 1 ? vy : vz);
         }
+        o += P.sensor_ntouch + 3 * P.sensor_ncfrc;  // (touch / contact-force entries: written behind the solver, by the contact-force epilogue)
         if (P.sensor_flags & 4) { for (int i = lane; i < nq; i += kGroup) so[o + i] = s_qpos[i]; o += nq; }
         if (P.sensor_flags & 1) { for (int i = lane; i < nv; i += kGroup) so[o + i] = s_qvel[i]; o += nv; }
         if (P.sensor_flags & 2) for (int i = lane; i < HB_SZ(nu); i += kGroup) so[o + i] = s_ctrl[i];
@@ -1751,6 +1761,10 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
 #pragma unroll
         for (int g = 1; g < NG; g++) P_diag_force[(size_t)env * kNR + lane + 64 * g] = actg[g] ? forceg[g] : 0.f;
       }
+      if (NG > 1 && P_cfrc) {  // (the contact-force epilogue reads the rows from s_force; it stages group 0 itself)
+#pragma unroll
+        for (int g = 1; g < NG; g++) s_force[lane + 64 * g] = actg[g] ? forceg[g] : 0.f;
+      }
       if (dofl) {
         s_v0[lane] = qacc;
         if (P_qfrc_out) P_qfrc_out[(size_t)env * nv + lane] = smooth + qfc;  // qfrc_smooth + qfrc_constraint
@@ -1787,6 +1801,73 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     // RK4: what a caller reads after the step is the last forward pass, as mjData after mj_step
     const bool last_pass = INTEG == 0 || !P_integrate || stage == 3;
     if (last_pass) ctrl_zeroed = false;
+    // ---------------------------------------------------------------- contact-force read-out (hb_contact_readout, include/hb.h)
+    // mj_contactForce of every contact and the bodies' contact wrenches (cfrc_ext without xfrc_applied), from the row forces the solver
+    // ended with.  Every forward pass writes them - what stays is the last one's - and the sensor rows are the first pass's.
+    if (P_cfrc) {
+      constexpr int kCw = 9;   // staged per contact: world force[3], world torque[3], normal force, body1, body2
+      float* s_cw = s_C;       // (the Jacobian rows are dead once the solver has ended)
+      const int cn = P.cfrc_ncon;
+      const bool rows_on = constraints_on && contacts_on;  // (otherwise no contact has rows, and C_ROW is not written)
+      s_force[lane] = (lane < kNR && rowact) ? force : 0.f;  // (row group 0; further groups: staged where the solvers end)
+      gsync();
+      for (int ci = lane; ci < cn; ci += kGroup) {  // lane = contact: decode the pyramid
+        float f[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (ci < ncon) {
+          const float* c = s_con + ci * kConStride;
+          const int a = rows_on ? __float_as_int(c[C_ROW]) : -1, d = __float_as_int(c[C_DIM]), pid = __float_as_int(c[C_PAIR]);
+          if (a >= 0) {
+            if (d == 1) f[0] = s_force[a];
+            else {
+              const float mu = c[C_FRIC];
+              const float mu_t = COLL != 0 ? fmaxf(1e-5f, M.pair_friction[3 * pid + 1]) : 0.f, mu_r = COLL != 0 ? fmaxf(1e-5f, M.pair_friction[3 * pid + 2]) : 0.f;
+#pragma unroll
+              for (int i = 0; i < (COLL != 0 ? 5 : 2); i++)
+                if (i < d - 1) {
+                  const float r0 = s_force[a + 2 * i], r1 = s_force[a + 2 * i + 1];
+                  f[0] += r0 + r1;
+                  f[i + 1] = (i < 2 ? mu : i == 2 ? mu_t : mu_r) * (r0 - r1);
+                }
+            }
+          }
+          const V3 fn = ld3(c + C_FRAME), ft1 = ld3(c + C_FRAME + 3), ft2 = ld3(c + C_FRAME + 6);
+          const float4 p0 = M.prec[(size_t)pid * 5];
+          float* w = s_cw + kCw * ci;
+          st3(w, fn * f[0] + ft1 * f[1] + ft2 * f[2]);
+          st3(w + 3, fn * f[3] + ft1 * f[4] + ft2 * f[5]);
+          w[6] = f[0]; w[7] = p0.x; w[8] = p0.y;
+        }
+        float* o = P_cfrc + ((size_t)env * cn + ci) * 6;
+#pragma unroll
+        for (int i = 0; i < 6; i++) o[i] = f[i];
+      }
+      gsync();
+      if (lane < nb) {  // lane = body: its contacts in contact order (no atomics: the same bits whatever the launch looks like)
+        float* w = P.body_contact + ((size_t)env * nb + lane) * 6;
+        const V3 xi = {w[3], w[4], w[5]};  // xipos of this body, parked here by this lane behind the kinematics
+        V3 Fs = {0.f, 0.f, 0.f}, Ts = {0.f, 0.f, 0.f};
+        float touch = 0.f;
+        for (int ci = 0; ci < ncon; ci++) {
+          const float* cw = s_cw + kCw * ci;
+          const bool on1 = __float_as_int(cw[7]) == lane, on2 = __float_as_int(cw[8]) == lane;
+          if (on1 || on2) {  // + on the body of geom2, - on the body of geom1
+            const float sg = (on2 ? 1.f : 0.f) - (on1 ? 1.f : 0.f);
+            const V3 F = ld3(cw) * sg, T = ld3(cw + 3) * sg;
+            Fs = Fs + F;
+            Ts = Ts + cross(ld3(s_con + ci * kConStride + C_POS) - xi, F) + T;
+            touch += cw[6];
+          }
+        }
+        w[0] = Fs.x; w[1] = Fs.y; w[2] = Fs.z; w[3] = Ts.x; w[4] = Ts.y; w[5] = Ts.z;
+        if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // touch / contact-force entries, behind every other read-out of the row
+          float* so = P_sensor_out + ((size_t)step * P.n_env + env) * P.sensor_stride + 3 * (P.sensor_nframe + P.sensor_naxis + P.sensor_nlinvel + P.sensor_nsub) + (P.sensor_tree >= 0 ? 6 : 0);
+          for (int k = 0; k < P.sensor_ntouch; k++) if (P.sensor_touch_body[k] == lane) so[k] = touch;
+          so += P.sensor_ntouch;
+          for (int k = 0; k < P.sensor_ncfrc; k++) if (P.sensor_cfrc_body[k] == lane) { so[3 * k] = Fs.x; so[3 * k + 1] = Fs.y; so[3 * k + 2] = Fs.z; }
+        }
+      }
+      gsync();
+    }
     // diagnostics of this step (parity tests)
     if (last_pass) {
     if (P_diag_qacc) for (int i = lane; i < nv; i += kGroup) P_diag_qacc[(size_t)env * nv + i] = s_v0[i];
@@ -2077,7 +2158,7 @@ static bool duo_pays(const BatchPtrs& P, int nsteps) {
 
 // the lean instantiations apply when the launch has none of the optional inputs / outputs (BatchPtrs::lean_ok bit 0, HB_TUNE_LEAN)
 static bool lean_launch(const BatchPtrs& P, bool with_qfrc = false) {
-  return (P.lean_ok & 1) && !P.xfrc && (with_qfrc || !P.qfrc_out) && !P.sensor_out && !P.qpos_out && !P.qvel_out && !P.diag_qacc && !P.diag_force && !P.diag_contact && !P.dr && !P.env_mask &&
+  return (P.lean_ok & 1) && !P.xfrc && (with_qfrc || !P.qfrc_out) && !P.sensor_out && !P.qpos_out && !P.qvel_out && !P.diag_qacc && !P.diag_force && !P.diag_contact && !P.contact_force && !P.dr && !P.env_mask &&
          P.integrate;
 }
 

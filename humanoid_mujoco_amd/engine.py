@@ -89,7 +89,9 @@ class HbSensorSpec(ctypes.Structure):
                 ("framepos_offset", (ctypes.c_float * 3) * 16),
                 ("n_frameaxis", ctypes.c_int), ("frameaxis_body", ctypes.c_int * 8), ("frameaxis_which", ctypes.c_int * 8),
                 ("n_framelinvel", ctypes.c_int), ("framelinvel_body", ctypes.c_int * 8),
-                ("n_subtreelinvel", ctypes.c_int), ("subtreelinvel_body", ctypes.c_int * 4)]
+                ("n_subtreelinvel", ctypes.c_int), ("subtreelinvel_body", ctypes.c_int * 4),
+                ("n_touch", ctypes.c_int), ("touch_body", ctypes.c_int * 8),
+                ("n_contactforce", ctypes.c_int), ("contactforce_body", ctypes.c_int * 4)]
 
 
 class HbDomainRandomization(ctypes.Structure):
@@ -161,6 +163,9 @@ def lib():
     L.hb_batch_segments.argtypes = [vp]
     L.hb_diag_enable.argtypes = [vp, ci]
     L.hb_get_qacc.argtypes = [vp, vp]; L.hb_get_efc_force.argtypes = [vp, vp]; L.hb_get_contacts.argtypes = [vp, vp]
+    L.hb_contact_readout.argtypes = [vp, ci]
+    L.hb_get_contact_force.argtypes = [vp, vp]; L.hb_get_body_contact.argtypes = [vp, vp]
+    L.hb_contact_readout_dev.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
     L.hb_env_default_config.argtypes = [vp, ctypes.POINTER(HbEnvConfig)]
     L.hb_env_team_config.argtypes = [vp, ctypes.POINTER(HbEnvConfig)]
     L.hb_env_configure.argtypes = [vp, ctypes.POINTER(HbEnvConfig)]
@@ -503,6 +508,29 @@ class Batch:
         _check(lib().hb_get_contacts(self._h, _ptr(out)), "hb_get_contacts")
         return out
 
+    # ---- contact forces (mj_contactForce, cfrc_ext without xfrc_applied; include/hb.h)
+    def contact_readout(self, on=True):
+        """From the next launch on, steps write every contact's force and every body's contact wrench (full step kernels only)."""
+        _check(lib().hb_contact_readout(self._h, int(on)), "hb_contact_readout")
+
+    def contact_force(self):
+        """[n_env, ncon_max, 6]: contact-frame force and torque of contact k of contacts(); zeros beyond the env's ncon."""
+        out = np.zeros((self.n_env, self.model.ncon_max, 6), dtype=np.float32)
+        _check(lib().hb_get_contact_force(self._h, _ptr(out)), "hb_get_contact_force")
+        return out
+
+    def body_contact(self):
+        """[n_env, nbody, 6]: force | torque about the body's xipos, world axes, of the contacts on every body (row 0: the world)."""
+        out = np.zeros((self.n_env, self.model.nbody, 6), dtype=np.float32)
+        _check(lib().hb_get_body_contact(self._h, _ptr(out)), "hb_get_body_contact")
+        return out
+
+    def contact_readout_dev(self):
+        """Device addresses (contact_force, body_contact) of the read-out buffers, ordered behind the step calls made so far."""
+        a, b = ctypes.c_void_p(), ctypes.c_void_p()
+        _check(lib().hb_contact_readout_dev(self._h, ctypes.byref(a), ctypes.byref(b)), "hb_contact_readout_dev")
+        return a.value, b.value
+
     # ---- wire format: agent.proto State of one env
     def state_to_proto(self, env):
         n = lib().hb_state_to_proto(self._h, int(env), None, 0)
@@ -517,10 +545,12 @@ class Batch:
 
     # ---- planner rollouts (MJPC Trajectory::Rollout analogue)
     @staticmethod
-    def sensor_spec(framepos_bodies=(), subtree_body=-1, offsets=None, axes=(), linvel_bodies=(), subtreelinvel_bodies=()):
+    def sensor_spec(framepos_bodies=(), subtree_body=-1, offsets=None, axes=(), linvel_bodies=(), subtreelinvel_bodies=(), touch_bodies=(),
+                    contactforce_bodies=()):
         """offsets: per frame, the site's position in its body frame (None / missing: the body frame itself);
         axes: (body, which) pairs, which = 0 (framexaxis) or 2 (framezaxis); linvel_bodies: framelinvel (objtype body);
-        subtreelinvel_bodies: subtreelinvel of further bodies."""
+        subtreelinvel_bodies: subtreelinvel of further bodies; touch_bodies: summed normal contact force of a body (one float);
+        contactforce_bodies: contact force on a body, world axes (three floats)."""
         sp = HbSensorSpec()
         sp.n_framepos = len(framepos_bodies)
         for k, bd in enumerate(framepos_bodies):
@@ -538,6 +568,12 @@ class Batch:
         sp.n_subtreelinvel = len(subtreelinvel_bodies)
         for k, bd in enumerate(subtreelinvel_bodies):
             sp.subtreelinvel_body[k] = int(bd)
+        sp.n_touch = len(touch_bodies)
+        for k, bd in enumerate(touch_bodies):
+            sp.touch_body[k] = int(bd)
+        sp.n_contactforce = len(contactforce_bodies)
+        for k, bd in enumerate(contactforce_bodies):
+            sp.contactforce_body[k] = int(bd)
         return sp
 
     def set_state_broadcast(self, spec, state):

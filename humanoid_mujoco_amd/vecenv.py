@@ -49,11 +49,14 @@ _NO_INFO = {}  # (shared by the envs that did not finish an episode this step: S
 
 
 class VecEnv:
-    def __init__(self, model, n_envs, device=0, n_substeps=1, randomization_factor=1.0, realism=False, domain_randomization=False, seed=0, team=False, **reward_overrides):
+    def __init__(self, model, n_envs, device=0, n_substeps=1, randomization_factor=1.0, realism=False, domain_randomization=False, seed=0, team=False,
+                 contact_forces=False, **reward_overrides):
         """realism=True adds CPUEnv's sensor/action noise, delay FIFOs and pushes (hb_env_randomization), scaled by
         randomization_factor exactly like the reset perturbation; domain_randomization=True draws per-env masses, floor
         friction, joint and actuator parameters at every reset (hb_domain_randomization).  team=True: the reference's own
-        constants for its own robot (hb_env_team_config: obs[30] in JOINT_NAMES order, action[12], standup reset, kp = 2)."""
+        constants for its own robot (hb_env_team_config: obs[30] in JOINT_NAMES order, action[12], standup reset, kp = 2).
+        contact_forces=True: the physics steps also write every body's contact wrench (hb_contact_readout), read with
+        body_contact_forces(); such steps run the full step kernel."""
         self.model = model if isinstance(model, Model) else Model.load(model)
         self.batch = Batch(self.model, n_envs, device)
         self.num_envs = int(n_envs)
@@ -67,6 +70,9 @@ class VecEnv:
                 raise AttributeError("unknown env parameter %r" % k)
             setattr(self.cfg, k, v)
         self.batch.env_configure(self.cfg)
+        self.contact_forces = bool(contact_forces)
+        if self.contact_forces:
+            self.batch.contact_readout(True)
         self.realism = None
         if realism:
             self.realism = self.batch.env_default_randomization()
@@ -197,6 +203,13 @@ class VecEnv:
         infos = {"is_success": trunc.copy(), "done": done, "warnings": w,  # cpu_env.py:688-689
                  "overflow": (w & (WARN_CONTACTFULL | WARN_CNSTRFULL)) != 0}
         return obs, rew, term, trunc, infos
+
+    def body_contact_forces(self):
+        """[n_envs, nbody, 6]: force | torque about the body's xipos (world axes) of the contacts on every body, from the last physics
+        substep of the last step (an env that finished there and was reset in place: from its reset's settle step, if it has one)."""
+        if not self.contact_forces:
+            raise RuntimeError("body_contact_forces: create the VecEnv with contact_forces=True")
+        return self.batch.body_contact()
 
     def warning_counts(self):
         """Number of envs currently carrying each warning bit."""

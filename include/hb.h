@@ -153,7 +153,7 @@ int hb_reset(hb_batch* b, const uint8_t* mask, int keyframe, int perturb, int en
  * replaced once, by the last stage's qacc.  The position / velocity checks run at the start of the step and the acceleration check
  * after the first stage only.  What is read after the step is what mjData holds after mj_step: sensors (hb_rollout_sensors, the task
  * residuals, hb_sensors) are those of the FIRST stage; everything else - hb_get_qacc, hb_get_efc_force, hb_get_contacts, hb_get_counts,
- * the env adapter's joint torques - is that of the LAST stage.  HB_WARN_CONTACTFULL / HB_WARN_CNSTRFULL accumulate over all stages.
+ * hb_get_contact_force, hb_get_body_contact, the env adapter's joint torques - is that of the LAST stage.  HB_WARN_CONTACTFULL / HB_WARN_CNSTRFULL accumulate over all stages.
  * RK4 exists for models that step in one kernel (plane / sphere / capsule geoms, condim 1 / 3): for a model that steps in stages (mesh
  * hulls, height fields, condim 4 / 6) hb_batch_create fails and says so. */
 int hb_step(hb_batch* b, const float* ctrl, int n_substeps);
@@ -214,7 +214,7 @@ int hb_state_from_proto(hb_batch* b, int env, const unsigned char* buf, int len)
 /* The sensors MJPC's humanoid tasks build their residuals from (tasks/humanoid_cap/stand/task.xml:22-40): framepos of
  * up to 16 bodies or sites (a site is a body plus an offset in the body frame), and subtreecom / subtreelinvel (mj_subtreeVel, mujoco.h:346) of one kinematic tree, named by its root
  * body (a direct child of the world; < 0: none).  Per env and step the read-out is
- * [framepos 0 (3) | ... | subtreecom (3) | subtreelinvel (3)], hb_sensor_size() floats. */
+ * [framepos 0 (3) | ... | subtreecom (3) | subtreelinvel (3) | further read-outs, in the order of the fields below], hb_sensor_size() floats. */
 #define HB_MAX_FRAMEPOS 16
 typedef struct hb_sensor_spec {
   int n_framepos;
@@ -230,6 +230,13 @@ typedef struct hb_sensor_spec {
   int framelinvel_body[8];
   int n_subtreelinvel;        /* subtreelinvel of further bodies (any body of the model, not only a tree root) */
   int subtreelinvel_body[4];
+  /* contact sensors, appended behind all of the above.  They belong to the acceleration stage of the step's forward pass: row t of
+   * hb_rollout_sensors holds the forces of step t's constraint solve (RK4: of its first stage, like every sensor).  A spec that has
+   * any of them makes its launches carry the contact-force read-out (see hb_contact_readout; the getters there stay off). */
+  int n_touch;                /* one float each: the sum of the normal forces f[0] of the contacts that involve the body - MuJoCo's touch */
+  int touch_body[8];          /*   sensor taken over the WHOLE BODY instead of a site volume */
+  int n_contactforce;         /* three floats each: the force part of the body's contact wrench (hb_get_body_contact), world axes */
+  int contactforce_body[4];
 } hb_sensor_spec;
 int hb_sensor_size(const hb_sensor_spec* spec);
 /* mj_setState of ONE state on every env: the N candidate action sequences of a sampling planner all start from the
@@ -427,6 +434,34 @@ int hb_diag_enable(hb_batch* b, int on);
 int hb_get_qacc(hb_batch* b, float* qacc);
 int hb_get_efc_force(hb_batch* b, float* efc_force);
 int hb_get_contacts(hb_batch* b, float* contact);
+
+/* ---- contact forces (mj_contactForce, mjData.cfrc_ext; mujoco.h, mjdata.h) ---------------------------------------------------
+ * What each contact pushed with in the last constraint solve, decoded on the device from the solver's own rows.
+ * For contact c with first row a, dimension d, friction coefficients mu[0..d-2] (sliding, sliding, torsional, rolling, rolling) and
+ * frame rows n, t1, t2 (hb_get_contacts):
+ *   contact-frame force f[6]:  d == 1: f[0] = efc_force[a];  otherwise, with r = efc_force[a .. a + 2 (d - 1)) the pyramid rows:
+ *                              f[0] = sum r, f[i + 1] = mu[i] (r[2 i] - r[2 i + 1]);  entries at and beyond d are 0.
+ *                              A contact without rows - in the gap (dist >= margin - gap), or dropped with HB_WARN_CNSTRFULL - has f = 0.
+ *   world force  F = frame' f[0:3], world torque T = frame' f[3:6]: acting with + on the body of geom2, with - on the body of geom1,
+ *                              at the contact position.
+ *   body contact wrench        w[b] = (sum +-F, sum +-((pos - xipos[b]) x F + T)) over the contacts of body b, for every body, the
+ *                              world (row 0) included: mjData.cfrc_ext WITHOUT xfrc_applied, and with the torque taken about the
+ *                              body's OWN inertial-frame origin xipos[b], world axes (the reference's cfrc_ext refers to the subtree
+ *                              centre of mass of the body's tree).  The sums run in contact order in one lane per body, without
+ *                              atomics: the same bits for the same state, however the batch is launched.
+ * hb_contact_readout(b, 1) allocates the two buffers; from the next launch on every step, forward and env-step launch writes them (such
+ * a launch runs the full step kernel: the lean and two-envs-per-wave kernels have no read-out).  off: launches stop writing them.
+ * hb_get_contact_force: [n_env][ncon_max][6], zeros beyond the env's ncon; row k belongs to contact k of hb_get_contacts.
+ * hb_get_body_contact:  [n_env][nbody][6] = force[3] | torque[3].
+ * Both launch step calls held back and join the pipes like every other read, and return HB_EINVAL while the read-out is off.  They
+ * hold the LAST forward pass (RK4: the last stage; the sensor entries of hb_sensor_spec hold the first - the rule at hb_step).  Envs a
+ * launch skips (an env mask) keep their rows.
+ * hb_contact_readout_dev hands out the device buffers (same layouts; either pointer may be NULL) for a policy or reward on the same
+ * GPU: it joins like hb_batch_stream, so work enqueued on the batch's stream afterwards sees the step calls made so far. */
+int hb_contact_readout(hb_batch* b, int on);
+int hb_get_contact_force(hb_batch* b, float* out);
+int hb_get_body_contact(hb_batch* b, float* out);
+int hb_contact_readout_dev(hb_batch* b, const float** contact_force_dev, const float** body_contact_dev);
 
 /* ---- env adapter: the 27-DoF analogue of CPUEnv.step/reset (simulation/cpu_env.py:374-416,656-693) --------- */
 
