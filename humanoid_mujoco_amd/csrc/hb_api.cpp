@@ -657,6 +657,10 @@ struct hb_batch {
   // entries allocates them as well and hands them to its own launches only
   DevBuf<float> d_contact_force, d_body_contact;
   bool contact_readout = false;
+  // body-acceleration read-out (hb_body_acc_readout): [n_env][nbody][6], and the scratch the step kernel parks a body's kinematics in
+  // across the solver, [n_env][nbody][kAccPark]; a sensor spec with accelerometer / frame-acceleration entries allocates them as well
+  DevBuf<float> d_body_acc, d_body_acc_park;
+  bool body_acc_readout = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   DevBuf<unsigned long long> d_stamps;
   // staged step of the general variants: the buffers, and the kernel argument that points into them (all null: fused)
@@ -752,6 +756,7 @@ BatchPtrs make_ptrs(hb_batch* b) {
   if (b->diag) { P.diag_qacc = b->d_diag_qacc; P.diag_force = b->d_diag_force; P.diag_contact = b->d_diag_contact; }
   if (b->contact_readout) { P.contact_force = b->d_contact_force; P.body_contact = b->d_body_contact; }
   P.cfrc_ncon = b->D.dm.ncon_max;
+  if (b->body_acc_readout) { P.body_acc = b->d_body_acc; P.body_acc_park = b->d_body_acc_park; }
   P.n_env = b->n_env;
   P.integrate = 1;
   if (b->schedule && b->order_mode) { P.order = b->d_order; P.order2 = staged_on(b) ? b->d_order2.get() : nullptr; }
@@ -1706,8 +1711,9 @@ int hb_sensor_size(const hb_sensor_spec* spec) {
   if (!spec || spec->n_framepos < 0 || spec->n_framepos > HB_MAX_FRAMEPOS) return HB_EINVAL;
   if (spec->n_frameaxis < 0 || spec->n_frameaxis > 8 || spec->n_framelinvel < 0 || spec->n_framelinvel > 8 || spec->n_subtreelinvel < 0 || spec->n_subtreelinvel > 4) return HB_EINVAL;
   if (spec->n_touch < 0 || spec->n_touch > 8 || spec->n_contactforce < 0 || spec->n_contactforce > 4) return HB_EINVAL;
+  if (spec->n_imu < 0 || spec->n_imu > 4 || spec->n_frameacc < 0 || spec->n_frameacc > 4) return HB_EINVAL;
   return 3 * spec->n_framepos + (spec->subtree_body >= 0 ? 6 : 0) + 3 * (spec->n_frameaxis + spec->n_framelinvel + spec->n_subtreelinvel) + spec->n_touch +
-         3 * spec->n_contactforce;
+         3 * spec->n_contactforce + 6 * (spec->n_imu + spec->n_frameacc);
 }
 
 // the two buffers of the contact-force read-out: both there or neither
@@ -1715,6 +1721,16 @@ static int alloc_contact_readout(hb_batch* b) {
   const size_t n = b->n_env;
   if (b->d_contact_force.alloc(n * b->D.dm.ncon_max * 6, true) != HB_OK || b->d_body_contact.alloc(n * b->D.dm.nbody * 6, true) != HB_OK) {
     reset_all(b->d_contact_force, b->d_body_contact);
+    return HB_ENOMEM;
+  }
+  return HB_OK;
+}
+
+// the read-out and the scratch of the body-acceleration read-out: both there or neither
+static int alloc_body_acc_readout(hb_batch* b) {
+  const size_t n = (size_t)b->n_env * b->D.dm.nbody;
+  if (b->d_body_acc.alloc(n * 6, true) != HB_OK || b->d_body_acc_park.alloc(n * kAccPark, true) != HB_OK) {
+    reset_all(b->d_body_acc, b->d_body_acc_park);
     return HB_ENOMEM;
   }
   return HB_OK;
@@ -1773,6 +1789,23 @@ static int sensor_setup(hb_batch* b, const hb_sensor_spec* spec, int T, BatchPtr
   if (spec->n_touch + spec->n_contactforce > 0) {
     if (alloc_contact_readout(b) != HB_OK) return HB_ENOMEM;
     P.contact_force = b->d_contact_force; P.body_contact = b->d_body_contact;
+  }
+  // accelerometer / gyro and frame-acceleration entries: written by the body-acceleration epilogue, likewise
+  P.sensor_nimu = spec->n_imu; P.sensor_nfacc = spec->n_frameacc;
+  P.sensor_acc_off = ns - 6 * (spec->n_imu + spec->n_frameacc);  // (they are the last entries hb_sensor_size counts)
+  P.sensor_behind = spec->n_touch + 3 * spec->n_contactforce + 6 * (spec->n_imu + spec->n_frameacc);
+  for (int k = 0; k < spec->n_imu; k++) {
+    if (spec->imu_body[k] < 0 || spec->imu_body[k] >= m.nbody) return HB_EINVAL;
+    P.sensor_imu_body[k] = spec->imu_body[k];
+    for (int i = 0; i < 3; i++) P.sensor_imu_off[k][i] = spec->imu_offset[k][i];
+  }
+  for (int k = 0; k < spec->n_frameacc; k++) {
+    if (spec->frameacc_body[k] < 0 || spec->frameacc_body[k] >= m.nbody) return HB_EINVAL;
+    P.sensor_facc_body[k] = spec->frameacc_body[k];
+  }
+  if (spec->n_imu + spec->n_frameacc > 0) {
+    if (alloc_body_acc_readout(b) != HB_OK) return HB_ENOMEM;
+    P.body_acc = b->d_body_acc; P.body_acc_park = b->d_body_acc_park;
   }
   return HB_OK;
 }
@@ -2602,6 +2635,29 @@ int hb_contact_readout_dev(hb_batch* b, const float** contact_force_dev, const f
   (void)main_stream(b);  // (joins like hb_batch_stream: work enqueued on the batch's stream from here on follows every step call made so far)
   if (contact_force_dev) *contact_force_dev = b->d_contact_force;
   if (body_contact_dev) *body_contact_dev = b->d_body_contact;
+  return HB_OK;
+}
+
+int hb_body_acc_readout(hb_batch* b, int on) {
+  if (!b) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  (void)main_stream(b);  // from the next launch on: step calls held back are launched as they were made
+  if (on && alloc_body_acc_readout(b) != HB_OK) return HB_ENOMEM;
+  b->body_acc_readout = on != 0;
+  return HB_OK;
+}
+int hb_get_body_acc(hb_batch* b, float* out) {
+  if (!b || !out || !b->body_acc_readout || !b->d_body_acc.get()) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  HB_HIP(hipMemcpy(out, b->d_body_acc.get(), (size_t)b->n_env * b->D.dm.nbody * 6 * sizeof(float), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+int hb_body_acc_readout_dev(hb_batch* b, const float** body_acc_dev) {
+  if (!b || !b->body_acc_readout) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  (void)main_stream(b);  // (joins like hb_batch_stream)
+  if (body_acc_dev) *body_acc_dev = b->d_body_acc;
   return HB_OK;
 }
 

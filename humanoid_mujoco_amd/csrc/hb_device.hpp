@@ -375,6 +375,20 @@ struct BatchPtrs {
   // each), then the force part of a body's contact wrench (three floats each)
   int sensor_ntouch, sensor_touch_body[8];
   int sensor_ncfrc, sensor_cfrc_body[4];
+  // body-acceleration read-out (hb_body_acc_readout), both null or both set: [n_env][nbody][6] = angular | linear acceleration of the
+  // body's xipos, world axes, gravity pseudo-acceleration included; and the scratch the step kernel parks what the read-out needs of the
+  // kinematics in, [n_env][nbody][kAccPark]: bias cacc[6] | cvel[6] | xipos - subtree_com[3] | xpos - subtree_com[3] | xquat[4] | -.
+  // A launch that carries them takes the full kernel's instantiation with the read-out (step_body's ACC, hb_step.hip: HB_ACC_KERNELS).
+  float* body_acc;
+  float* body_acc_park;
+  // ... and their sensor entries, behind the contact-force entries: accelerometer[3] | gyro[3] at body frame + offset in the body's
+  // axes (six floats each), then frameangacc[3] | framelinacc[3] of a body (six floats each: its row of body_acc)
+  int sensor_nimu, sensor_imu_body[4];
+  float sensor_imu_off[4][3];
+  int sensor_nfacc, sensor_facc_body[4];
+  int sensor_acc_off;  // where these entries begin in a sensor row (floats)
+  int sensor_behind;   // floats of a sensor row written behind the solver: the contact-force read-out's entries and these
 };
+constexpr int kAccPark = 24;  // floats per body in BatchPtrs::body_acc_park (six 16-byte moves)
 
 }  // namespace hb

@@ -51,7 +51,9 @@ __device__ __forceinline__ void defer_env(const BatchPtrs& P, int env) {
 // INTEG: mjtIntegrator of the instantiation (0 = Euler, 1 = RK4: mj_RungeKutta(4)).  An RK4 step is four passes of the step loop, the
 // forward dynamics at the four stage states, and advances at the end of the fourth (the stage machine sits where mj_Euler does); what
 // belongs to the step and not to a forward pass - controls, noise, the mj_check*s, the sensor read-out - is done in the first pass only.
-template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0, int INV = 0, int INTEG = 0>
+// ACC: the body-acceleration read-out (hb_body_acc_readout).  Its parking and its epilogue exist in instantiations of their own, which a
+// launch takes when it carries the read-out (select_step); every other instantiation compiles without them, as before the read-out existed.
+template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0, int INV = 0, int INTEG = 0, int ACC = 0>
 __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P, int nsteps_in, int env_in = -1) {
   const int nsteps = LEAN == 1 ? 1 : nsteps_in;  // (LEAN == 1 is launched for single steps only: the step API; rollouts take LEAN == 2)
   // LEAN (1 = a single step without the constraint-force read-out; 2 = any number of steps, read-out optional): a launch without the optional inputs and outputs (applied forces and their noise, constraint-force / sensor / trajectory
@@ -68,11 +70,13 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   float* const P_diag_force = (LEAN || INV) ? nullptr : P.diag_force;
   float* const P_diag_contact = (LEAN || INV) ? nullptr : P.diag_contact;
   float* const P_cfrc = (LEAN || INV) ? nullptr : P.contact_force;  // contact-force read-out (hb_contact_readout); P.body_contact comes with it
+  float* const P_bacc = ACC ? P.body_acc : nullptr;  // body-acceleration read-out (hb_body_acc_readout); P.body_acc_park comes with it
   const float* const P_dr = LEAN ? nullptr : P.dr;
   const int P_dr_stride = LEAN ? 0 : P.dr_stride;
   const unsigned char* const P_env_mask = (LEAN || INV) ? nullptr : P.env_mask;
   const int P_integrate = INV ? 0 : LEAN ? 1 : P.integrate;
   static_assert(SIZED == 0 || (NG == 1 && ((NDENSE == 28 && (COLL == 0 || SOLVER == 0)) || (NDENSE == 20 && COLL == 1 && SOLVER == 2))), "the size-specialised instantiations: the humanoid (classic or variant-1 layout) and the robot (Newton, variant-1 layout)");
+  static_assert(ACC == 0 || (LEAN == 0 && SIZED == 0 && INV == 0), "the body-acceleration read-out: full kernels only");
   static_assert(INTEG == 0 || (COLL == 0 && NG == 1 && DEFER == 0 && LEAN == 0 && SIZED == 0 && INV == 0), "RK4: the full kernels of the classic variant");
   static_assert(NG == 1 || SOLVER == 2 || (COLL == 1 && NG == kPgsGroups && DEFER == 0), "PGS on more than one row group: the general variant's kPgsGroups instantiation");
   constexpr int kNR = NG == 1 ? kNefcMax : 64 * NG;  // row capacity of this instantiation
@@ -488,6 +492,31 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       const V3 x = ld3(s_xipos + 3 * lane);
       w[3] = x.x; w[4] = x.y; w[5] = x.z;
     }
+    // body-acceleration read-out: a body's acceleration is its bias acceleration - what the RNE forward pass has just formed with
+    // qacc = 0 and left in s_va - plus sum cdof qacc over the dofs above it, which exists behind the solver only, where region A is gone.
+    // Lane b parks what the epilogue there needs of body b in the batch's scratch and reads it back itself (the same lane, the same
+    // addresses: program order; no LDS and no register is held across the solver for it):
+    // bias cacc | cvel | xipos - subtree_com | xpos - subtree_com | xquat
+    if (P_bacc && lane < nb) {
+      float4* w = reinterpret_cast<float4*>(P.body_acc_park + ((size_t)env * nb + lane) * kAccPark);
+      const V3 g = (M_disableflags & (1 << 6)) ? V3{0.f, 0.f, 0.f} : V3{M.gravity[0], M.gravity[1], M.gravity[2]};
+      float4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0, v2 = v0, xq = {1.f, 0.f, 0.f, 0.f};  // (the world: at rest at the origin; s_va has no row for it)
+      V3 ri = {0.f, 0.f, 0.f}, rx = ri;
+      if (lane > 0) {
+        const float4* Pp = reinterpret_cast<const float4*>(s_va + 12 * lane);
+        v0 = Pp[0]; v1 = Pp[1]; v2 = Pp[2];
+        const V3 com = ld3(s_scom + 3 * M.body_treeid[lane]);
+        ri = ld3(s_xipos + 3 * lane) - com;
+        rx = ld3(s_xpq + kXpqStride * lane) - com;
+        xq = reinterpret_cast<const float4*>(s_xpq + kXpqStride * lane)[1];
+      }
+      w[0] = {v1.z, v1.w, v2.x, v2.y - g.x};  // cacc: angular[3], linear[3] with the world's (0, -gravity)
+      w[1] = {v2.z - g.y, v2.w - g.z, v0.x, v0.y};
+      w[2] = {v0.z, v0.w, v1.x, v1.y};        // cvel
+      w[3] = {ri.x, ri.y, ri.z, rx.x};
+      w[4] = {rx.y, rx.z, xq.x, xq.y};
+      w[5] = {xq.z, xq.w, 0.f, 0.f};
+    }
     // sensor read-out for planner residuals (mj_sensorPos/Vel of framepos, subtreecom, subtreelinvel)
     if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // (RK4: the sensors of mj_step are those of the first stage)
       float* so = P_sensor_out + ((size_t)step * P.n_env + env) * P.sensor_stride;
@@ -519,7 +548,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
           const float vx = wave_sum(mom.x) * im, vy = wave_sum(mom.y) * im, vz = wave_sum(mom.z) * im;
           if (lane < 3) so[o + lane] = lane == 0 ? vx : (lane == 1 ? vy : vz);
         }
-        o += P.sensor_ntouch + 3 * P.sensor_ncfrc;  // (touch / contact-force entries: written behind the solver, by the contact-force epilogue)
+        o += P.sensor_behind;  // (touch / contact-force and accelerometer / gyro / frame-acceleration entries: written behind the solver, by the two epilogues)
         if (P.sensor_flags & 4) { for (int i = lane; i < nq; i += kGroup) so[o + i] = s_qpos[i]; o += nq; }
         if (P.sensor_flags & 1) { for (int i = lane; i < nv; i += kGroup) so[o + i] = s_qvel[i]; o += nv; }
         if (P.sensor_flags & 2) for (int i = lane; i < HB_SZ(nu); i += kGroup) so[o + i] = s_ctrl[i];
@@ -1868,6 +1897,49 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       }
       gsync();
     }
+    // ---------------------------------------------------------------- body-acceleration read-out (hb_body_acc_readout, include/hb.h)
+    // mj_rnePostConstraint's cacc, taken to the body's own xipos (mj_objectAcceleration): cacc = bias cacc + sum over the dofs above the
+    // body of cdof qacc, with the qacc the solver ended with (s_v0: what hb_get_qacc reports).  Lane = body, its dofs in ascending order:
+    // no atomics and no cross-lane sums.  Every forward pass writes the rows - what stays is the last one's - and the sensor rows are
+    // the first pass's.
+    if (P_bacc) {
+      if (lane < nb) {
+        const float4* pk = reinterpret_cast<const float4*>(P.body_acc_park + ((size_t)env * nb + lane) * kAccPark);
+        const float4 k0 = pk[0], k1 = pk[1], k2 = pk[2], k3 = pk[3], k4 = pk[4], k5 = pk[5];
+        float a[6] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y};
+        const V3 om = {k1.z, k1.w, k2.x}, vc = {k2.y, k2.z, k2.w}, ri = {k3.x, k3.y, k3.z}, rx = {k3.w, k4.x, k4.y};
+        unsigned long long mask = M.body_dofmask[lane];
+        while (mask) {
+          const int d = __builtin_ctzll(mask);
+          mask &= mask - 1;
+          float cd[6];
+          ld_cdof(s_cdof, d, cd);
+          const float qa = s_v0[d];
+#pragma unroll
+          for (int i = 0; i < 6; i++) a[i] = __builtin_fmaf(cd[i], qa, a[i]);
+        }
+        const V3 al = {a[0], a[1], a[2]}, ac = {a[3], a[4], a[5]};
+        // at a point r away from the subtree centre of mass: v = vc + om x r, acc = ac + al x r + om x v
+        const V3 li = ac + cross(al, ri) + cross(om, vc + cross(om, ri));
+        float* w = P_bacc + ((size_t)env * nb + lane) * 6;
+        w[0] = al.x; w[1] = al.y; w[2] = al.z; w[3] = li.x; w[4] = li.y; w[5] = li.z;
+        if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // behind the contact-force entries of the row
+          float* so = P_sensor_out + ((size_t)step * P.n_env + env) * P.sensor_stride + P.sensor_acc_off;
+          const int nimu = P.sensor_nimu, nfacc = P.sensor_nfacc;
+          for (int k = 0; k < nimu; k++)
+            if (P.sensor_imu_body[k] == lane) {  // a site with the body's orientation: the point's acceleration and the angular velocity in its axes
+              const Q4 q = {k4.z, k4.w, k5.x, k5.y};
+              const Q4 qc = {q.w, -q.x, -q.y, -q.z};
+              const V3 r = rx + qrot(q, {P.sensor_imu_off[k][0], P.sensor_imu_off[k][1], P.sensor_imu_off[k][2]});
+              const V3 acc = qrot(qc, ac + cross(al, r) + cross(om, vc + cross(om, r))), gy = qrot(qc, om);
+              so[6 * k] = acc.x; so[6 * k + 1] = acc.y; so[6 * k + 2] = acc.z; so[6 * k + 3] = gy.x; so[6 * k + 4] = gy.y; so[6 * k + 5] = gy.z;
+            }
+          so += 6 * nimu;
+          for (int k = 0; k < nfacc; k++)
+            if (P.sensor_facc_body[k] == lane) { so[6 * k] = al.x; so[6 * k + 1] = al.y; so[6 * k + 2] = al.z; so[6 * k + 3] = li.x; so[6 * k + 4] = li.y; so[6 * k + 5] = li.z; }
+        }
+      }
+    }
     // diagnostics of this step (parity tests)
     if (last_pass) {
     if (P_diag_qacc) for (int i = lane; i < nv; i += kGroup) P_diag_qacc[(size_t)env * nv + i] = s_v0[i];
@@ -2108,6 +2180,27 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   K(hb_rk4_newton28_kernel,             2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
   K(hb_rk4_newton32_kernel,             2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
 
+// the body-acceleration read-out (step_body's ACC; hb_body_acc_readout): every full kernel above once more, row for row, with the read-out's
+// parking and epilogue - what a launch that carries the read-out runs in place of the kernel of the same row
+#define HB_ACC_KERNELS(K) /* (Mp, P, nsteps) */ \
+  K(hb_acc_kernel,                      0,      28,     0,    1,          0,     0,    0,     0,   2,     112,   0) \
+  K(hb_acc32_kernel,                    0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
+  K(hb_acc_gen_kernel,                  0,      28,     1,    1,          0,     0,    0,     0,   2,     0,     1) \
+  K(hb_acc_gen_big_kernel,              0,      28,     1,    kPgsGroups, 0,     0,    0,     0,   1,     0,     1) \
+  K(hb_acc_gen_fast1_kernel,            0,      28,     1,    1,          1,     0,    0,     0,   2,     0,     0) \
+  K(hb_acc_gen_fast_kernel,             0,      28,     1,    1,          2,     0,    0,     0,   2,     0,     0) \
+  K(hb_acc_newton_big20_kernel,         2,      20,     1,    kBigGroups, 0,     0,    0,     0,   1,     0,     1) \
+  K(hb_acc_newton_big28_kernel,         2,      28,     1,    kBigGroups, 0,     0,    0,     0,   1,     0,     1) \
+  K(hb_acc_newton_gen20_kernel,         2,      20,     1,    1,          1,     0,    0,     0,   2,     0,     0) \
+  K(hb_acc_newton_gen28_kernel,         2,      28,     1,    1,          1,     0,    0,     0,   2,     0,     0) \
+  K(hb_acc_newton28_kernel,             2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
+  K(hb_acc_newton32_kernel,             2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
+#define HB_ACC_RK4_KERNELS(K) /* (Mp, P, nsteps) */ \
+  K(hb_acc_rk4_kernel,                  0,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
+  K(hb_acc_rk4_32_kernel,               0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
+  K(hb_acc_rk4_newton28_kernel,         2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
+  K(hb_acc_rk4_newton32_kernel,         2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
+
 // (the entry calls step_body directly: a forwarding function template in between changes register allocation and scheduling)
 #define HB_STEP_BODY_0(...) step_body<__VA_ARGS__>(Mp, P, nsteps)
 #define HB_STEP_BODY_1(...) HB_STEP_OR_RERUN(__VA_ARGS__)
@@ -2119,16 +2212,24 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<S, ND, C, G, D, L, Z, I, 1>(Mp, P, nsteps); }
 HB_STEP_KERNELS(HB_DEFINE_STEP)
 HB_INVERSE_KERNELS(HB_DEFINE_INVERSE)
+#define HB_DEFINE_ACC(name, S, ND, C, G, D, L, Z, I, W, V, R) \
+  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_BODY_##R(S, ND, C, G, D, L, Z, I, 0, 1); }
+#define HB_DEFINE_ACC_RK4(name, S, ND, C, G, D, L, Z, I, W, V, R) \
+  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<S, ND, C, G, D, L, Z, I, 1, 1>(Mp, P, nsteps); }
 HB_RK4_KERNELS(HB_DEFINE_RK4)
+HB_ACC_KERNELS(HB_DEFINE_ACC)
+HB_ACC_RK4_KERNELS(HB_DEFINE_ACC_RK4)
 
 struct StepConfig {
-  int solver, ndense, coll, ng, defer, lean, sized, inv, integ;
-  bool operator==(const StepConfig& o) const { return solver == o.solver && ndense == o.ndense && coll == o.coll && ng == o.ng && defer == o.defer && lean == o.lean && sized == o.sized && inv == o.inv && integ == o.integ; }
+  int solver, ndense, coll, ng, defer, lean, sized, inv, integ, acc;
+  bool operator==(const StepConfig& o) const { return solver == o.solver && ndense == o.ndense && coll == o.coll && ng == o.ng && defer == o.defer && lean == o.lean && sized == o.sized && inv == o.inv && integ == o.integ && acc == o.acc; }
 };
 struct StepKernel { const char* name; const void* fn; StepConfig cfg; bool rerun; };
 #define HB_STEP_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 0}, R != 0},
 #define HB_RK4_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 1}, R != 0},
-static const StepKernel kStepKernels[] = {HB_STEP_KERNELS(HB_STEP_ROW) HB_INVERSE_KERNELS(HB_STEP_ROW) HB_RK4_KERNELS(HB_RK4_ROW)};
+#define HB_ACC_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 0, 1}, R != 0},
+#define HB_ACC_RK4_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 1, 1}, R != 0},
+static const StepKernel kStepKernels[] = {HB_STEP_KERNELS(HB_STEP_ROW) HB_INVERSE_KERNELS(HB_STEP_ROW) HB_RK4_KERNELS(HB_RK4_ROW) HB_ACC_KERNELS(HB_ACC_ROW) HB_ACC_RK4_KERNELS(HB_ACC_RK4_ROW)};
 static const StepKernel* find_step_kernel(const StepConfig& c) {
   for (const StepKernel& k : kStepKernels) if (k.cfg == c) return &k;
   return nullptr;
@@ -2158,7 +2259,7 @@ static bool duo_pays(const BatchPtrs& P, int nsteps) {
 
 // the lean instantiations apply when the launch has none of the optional inputs / outputs (BatchPtrs::lean_ok bit 0, HB_TUNE_LEAN)
 static bool lean_launch(const BatchPtrs& P, bool with_qfrc = false) {
-  return (P.lean_ok & 1) && !P.xfrc && (with_qfrc || !P.qfrc_out) && !P.sensor_out && !P.qpos_out && !P.qvel_out && !P.diag_qacc && !P.diag_force && !P.diag_contact && !P.contact_force && !P.dr && !P.env_mask &&
+  return (P.lean_ok & 1) && !P.xfrc && (with_qfrc || !P.qfrc_out) && !P.sensor_out && !P.qpos_out && !P.qvel_out && !P.diag_qacc && !P.diag_force && !P.diag_contact && !P.contact_force && !P.body_acc && !P.dr && !P.env_mask &&
          P.integrate;
 }
 
@@ -2179,6 +2280,7 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant,
   // two-envs-per-wave instantiation has it; a staged model is refused when its batch is created)
   if (integrator != 0) {
     c.integ = integrator;
+    c.acc = P.body_acc ? 1 : 0;
     return {variant == 0 && pass == StepPass::Main ? find_step_kernel(c) : nullptr, false, M_dev, shmem};
   }
   if (pass == StepPass::Fast) {
@@ -2192,6 +2294,7 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant,
   // not exist: the same without the sizes as constants, then the full kernel.
   c.lean = (nsteps == 1 && lean_launch(P)) ? 1 : lean_launch(P, true) ? 2 : 0;
   c.sized = c.lean && sized_ok;
+  c.acc = P.body_acc ? 1 : 0;  // (never lean: lean_launch; the full kernel of the same row with the body-acceleration read-out)
   const StepKernel* k = find_step_kernel(c);
   if (!k && c.sized) { c.sized = 0; k = find_step_kernel(c); }
   if (!k && c.lean) { c.lean = 0; k = find_step_kernel(c); }

@@ -91,7 +91,9 @@ class HbSensorSpec(ctypes.Structure):
                 ("n_framelinvel", ctypes.c_int), ("framelinvel_body", ctypes.c_int * 8),
                 ("n_subtreelinvel", ctypes.c_int), ("subtreelinvel_body", ctypes.c_int * 4),
                 ("n_touch", ctypes.c_int), ("touch_body", ctypes.c_int * 8),
-                ("n_contactforce", ctypes.c_int), ("contactforce_body", ctypes.c_int * 4)]
+                ("n_contactforce", ctypes.c_int), ("contactforce_body", ctypes.c_int * 4),
+                ("n_imu", ctypes.c_int), ("imu_body", ctypes.c_int * 4), ("imu_offset", (ctypes.c_float * 3) * 4),
+                ("n_frameacc", ctypes.c_int), ("frameacc_body", ctypes.c_int * 4)]
 
 
 class HbDomainRandomization(ctypes.Structure):
@@ -166,6 +168,9 @@ def lib():
     L.hb_contact_readout.argtypes = [vp, ci]
     L.hb_get_contact_force.argtypes = [vp, vp]; L.hb_get_body_contact.argtypes = [vp, vp]
     L.hb_contact_readout_dev.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]
+    L.hb_body_acc_readout.argtypes = [vp, ci]
+    L.hb_get_body_acc.argtypes = [vp, vp]
+    L.hb_body_acc_readout_dev.argtypes = [vp, ctypes.POINTER(vp)]
     L.hb_env_default_config.argtypes = [vp, ctypes.POINTER(HbEnvConfig)]
     L.hb_env_team_config.argtypes = [vp, ctypes.POINTER(HbEnvConfig)]
     L.hb_env_configure.argtypes = [vp, ctypes.POINTER(HbEnvConfig)]
@@ -531,6 +536,23 @@ class Batch:
         _check(lib().hb_contact_readout_dev(self._h, ctypes.byref(a), ctypes.byref(b)), "hb_contact_readout_dev")
         return a.value, b.value
 
+    # ---- body accelerations (mj_objectAcceleration of every body, gravity pseudo-acceleration included; include/hb.h)
+    def body_acc_readout(self, on=True):
+        """From the next launch on, steps write every body's acceleration (full step kernels only)."""
+        _check(lib().hb_body_acc_readout(self._h, int(on)), "hb_body_acc_readout")
+
+    def body_acc(self):
+        """[n_env, nbody, 6]: angular | linear acceleration of the body's xipos, world axes (row 0, the world: (0, -gravity))."""
+        out = np.zeros((self.n_env, self.model.nbody, 6), dtype=np.float32)
+        _check(lib().hb_get_body_acc(self._h, _ptr(out)), "hb_get_body_acc")
+        return out
+
+    def body_acc_readout_dev(self):
+        """Device address of the read-out buffer, ordered behind the step calls made so far."""
+        a = ctypes.c_void_p()
+        _check(lib().hb_body_acc_readout_dev(self._h, ctypes.byref(a)), "hb_body_acc_readout_dev")
+        return a.value
+
     # ---- wire format: agent.proto State of one env
     def state_to_proto(self, env):
         n = lib().hb_state_to_proto(self._h, int(env), None, 0)
@@ -546,11 +568,13 @@ class Batch:
     # ---- planner rollouts (MJPC Trajectory::Rollout analogue)
     @staticmethod
     def sensor_spec(framepos_bodies=(), subtree_body=-1, offsets=None, axes=(), linvel_bodies=(), subtreelinvel_bodies=(), touch_bodies=(),
-                    contactforce_bodies=()):
+                    contactforce_bodies=(), imu=(), frameacc_bodies=()):
         """offsets: per frame, the site's position in its body frame (None / missing: the body frame itself);
         axes: (body, which) pairs, which = 0 (framexaxis) or 2 (framezaxis); linvel_bodies: framelinvel (objtype body);
         subtreelinvel_bodies: subtreelinvel of further bodies; touch_bodies: summed normal contact force of a body (one float);
-        contactforce_bodies: contact force on a body, world axes (three floats)."""
+        contactforce_bodies: contact force on a body, world axes (three floats); imu: (body, (x, y, z)) pairs, accelerometer | gyro
+        of a site at that offset in the body frame, in the body's axes (six floats); frameacc_bodies: frameangacc | framelinacc of a
+        body, world axes (six floats: its row of body_acc())."""
         sp = HbSensorSpec()
         sp.n_framepos = len(framepos_bodies)
         for k, bd in enumerate(framepos_bodies):
@@ -574,6 +598,14 @@ class Batch:
         sp.n_contactforce = len(contactforce_bodies)
         for k, bd in enumerate(contactforce_bodies):
             sp.contactforce_body[k] = int(bd)
+        sp.n_imu = len(imu)
+        for k, (bd, off) in enumerate(imu):
+            sp.imu_body[k] = int(bd)
+            for i in range(3):
+                sp.imu_offset[k][i] = float(off[i])
+        sp.n_frameacc = len(frameacc_bodies)
+        for k, bd in enumerate(frameacc_bodies):
+            sp.frameacc_body[k] = int(bd)
         return sp
 
     def set_state_broadcast(self, spec, state):

@@ -50,13 +50,14 @@ _NO_INFO = {}  # (shared by the envs that did not finish an episode this step: S
 
 class VecEnv:
     def __init__(self, model, n_envs, device=0, n_substeps=1, randomization_factor=1.0, realism=False, domain_randomization=False, seed=0, team=False,
-                 contact_forces=False, **reward_overrides):
+                 contact_forces=False, body_accelerations=False, **reward_overrides):
         """realism=True adds CPUEnv's sensor/action noise, delay FIFOs and pushes (hb_env_randomization), scaled by
         randomization_factor exactly like the reset perturbation; domain_randomization=True draws per-env masses, floor
         friction, joint and actuator parameters at every reset (hb_domain_randomization).  team=True: the reference's own
         constants for its own robot (hb_env_team_config: obs[30] in JOINT_NAMES order, action[12], standup reset, kp = 2).
         contact_forces=True: the physics steps also write every body's contact wrench (hb_contact_readout), read with
-        body_contact_forces(); such steps run the full step kernel."""
+        body_contact_forces(); such steps run the full step kernel.  body_accelerations=True: likewise every body's acceleration
+        (hb_body_acc_readout), read with body_accelerations()."""
         self.model = model if isinstance(model, Model) else Model.load(model)
         self.batch = Batch(self.model, n_envs, device)
         self.num_envs = int(n_envs)
@@ -73,6 +74,9 @@ class VecEnv:
         self.contact_forces = bool(contact_forces)
         if self.contact_forces:
             self.batch.contact_readout(True)
+        self._body_accelerations = bool(body_accelerations)
+        if self._body_accelerations:
+            self.batch.body_acc_readout(True)
         self.realism = None
         if realism:
             self.realism = self.batch.env_default_randomization()
@@ -210,6 +214,13 @@ class VecEnv:
         if not self.contact_forces:
             raise RuntimeError("body_contact_forces: create the VecEnv with contact_forces=True")
         return self.batch.body_contact()
+
+    def body_accelerations(self):
+        """[n_envs, nbody, 6]: angular | linear acceleration of every body's xipos (world axes, gravity pseudo-acceleration included:
+        +|g| upward at rest), from the last physics substep of the last step (as body_contact_forces)."""
+        if not self._body_accelerations:
+            raise RuntimeError("body_accelerations: create the VecEnv with body_accelerations=True")
+        return self.batch.body_acc()
 
     def warning_counts(self):
         """Number of envs currently carrying each warning bit."""

@@ -153,7 +153,7 @@ int hb_reset(hb_batch* b, const uint8_t* mask, int keyframe, int perturb, int en
  * replaced once, by the last stage's qacc.  The position / velocity checks run at the start of the step and the acceleration check
  * after the first stage only.  What is read after the step is what mjData holds after mj_step: sensors (hb_rollout_sensors, the task
  * residuals, hb_sensors) are those of the FIRST stage; everything else - hb_get_qacc, hb_get_efc_force, hb_get_contacts, hb_get_counts,
- * hb_get_contact_force, hb_get_body_contact, the env adapter's joint torques - is that of the LAST stage.  HB_WARN_CONTACTFULL / HB_WARN_CNSTRFULL accumulate over all stages.
+ * hb_get_contact_force, hb_get_body_contact, hb_get_body_acc, the env adapter's joint torques - is that of the LAST stage.  HB_WARN_CONTACTFULL / HB_WARN_CNSTRFULL accumulate over all stages.
  * RK4 exists for models that step in one kernel (plane / sphere / capsule geoms, condim 1 / 3): for a model that steps in stages (mesh
  * hulls, height fields, condim 4 / 6) hb_batch_create fails and says so. */
 int hb_step(hb_batch* b, const float* ctrl, int n_substeps);
@@ -237,6 +237,15 @@ typedef struct hb_sensor_spec {
   int touch_body[8];          /*   sensor taken over the WHOLE BODY instead of a site volume */
   int n_contactforce;         /* three floats each: the force part of the body's contact wrench (hb_get_body_contact), world axes */
   int contactforce_body[4];
+  /* acceleration sensors, appended behind the contact sensors.  They too belong to the acceleration stage: row t holds step t's forward
+   * pass (RK4: its first stage).  A spec that has any of them makes its launches carry the body-acceleration read-out (see
+   * hb_body_acc_readout; the getter there stays off).  Both include the gravity pseudo-acceleration, as MuJoCo's do: at rest on the
+   * floor they read +|g| upward, in free fall 0. */
+  int n_imu;                  /* six floats each: accelerometer[3] | gyro[3] of a site at body frame + offset with the body's orientation: */
+  int imu_body[4];            /*   R' (linear acceleration of that point, omega x v included) | R' omega, R = the body's xmat */
+  float imu_offset[4][3];
+  int n_frameacc;             /* six floats each: frameangacc[3] | framelinacc[3], objtype body: row b of hb_get_body_acc */
+  int frameacc_body[4];
 } hb_sensor_spec;
 int hb_sensor_size(const hb_sensor_spec* spec);
 /* mj_setState of ONE state on every env: the N candidate action sequences of a sampling planner all start from the
@@ -462,6 +471,29 @@ int hb_contact_readout(hb_batch* b, int on);
 int hb_get_contact_force(hb_batch* b, float* out);
 int hb_get_body_contact(hb_batch* b, float* out);
 int hb_contact_readout_dev(hb_batch* b, const float** contact_force_dev, const float** body_contact_dev);
+
+/* ---- body accelerations (mj_rnePostConstraint's cacc, mj_objectAcceleration; mujoco.h) -------------------------------------------
+ * What every body does in the last forward pass, from the qacc the solver ended with (exactly the vector hb_get_qacc reports):
+ *   cacc[0] = (0, -gravity)   (the world; zero with mjDSBL_GRAVITY)
+ *   cacc[b] = cacc[parent(b)] + sum over the dofs i of b: cdof_dot[i] qvel[i] + cdof[i] qacc[i]
+ * The convention INCLUDES the gravity pseudo-acceleration: a body at rest on the floor reads +|g| upward, a body in free fall reads 0 -
+ * what MuJoCo's accelerometer, framelinacc and cacc all do, and what a real IMU's specific force is.
+ * hb_get_body_acc: [n_env][nbody][6] = angular acceleration[3] | linear acceleration[3] of the body's OWN inertial-frame origin
+ * xipos[b], world axes: mj_objectAcceleration(objtype body, flg_local = 0).  The reference's raw cacc refers to the subtree centre of
+ * mass of the body's tree and lacks the omega x v term; here it is transported to xipos and omega x v(xipos) is added - the same "own
+ * origin, world axes" choice as hb_get_body_contact.  Row 0 (the world) is (0, -gravity).  One lane per body sums its dofs in
+ * ascending order, without atomics: the same bits for the same state, however the batch is launched.
+ * hb_body_acc_readout(b, 1) allocates the buffer (and a scratch of 24 floats per body); from the next launch on every step, forward
+ * and env-step launch writes it (such a launch runs the full step kernel's instantiation with the read-out, hb_acc_* in hb_last_kernel:
+ * the lean and two-envs-per-wave kernels have none, and the full kernels themselves are compiled without it).
+ * off: launches stop writing it.  hb_get_body_acc launches step calls held back and joins the pipes like every other read, and returns
+ * HB_EINVAL while the read-out is off.  It holds the LAST forward pass (RK4: the last stage; the sensor entries of hb_sensor_spec hold
+ * the first - the rule at hb_step).  Envs a launch skips (an env mask) keep their rows.
+ * hb_body_acc_readout_dev hands out the device buffer (same layout) for a policy or reward on the same GPU: it joins like
+ * hb_batch_stream, so work enqueued on the batch's stream afterwards sees the step calls made so far. */
+int hb_body_acc_readout(hb_batch* b, int on);
+int hb_get_body_acc(hb_batch* b, float* out);
+int hb_body_acc_readout_dev(hb_batch* b, const float** body_acc_dev);
 
 /* ---- env adapter: the 27-DoF analogue of CPUEnv.step/reset (simulation/cpu_env.py:374-416,656-693) --------- */
 
