@@ -66,6 +66,15 @@ __device__ __forceinline__ void half_sums(float v, float& lo, float& hi) {
   lo = rdlane(v, 0) + rdlane(v, 16);
   hi = rdlane(v, 32) + rdlane(v, 48);
 }
+// the half that starts at lane BASE (0 or 32) alone
+template <int BASE>
+__device__ __forceinline__ float half_sum(float v) {
+  v += dpp_mov<0xB1>(v);
+  v += dpp_mov<0x4E>(v);
+  v += dpp_mov<0x141>(v);
+  v += dpp_mov<0x140>(v);
+  return rdlane(v, BASE) + rdlane(v, BASE + 16);
+}
 
 // the sparse M (WHICH = 0) or H = M + h B (WHICH = 1: the diagonal from s_Hd) of one env in the accumulator layout (load_sym_pairs of hb_kcommon.hpp)
 template <int WHICH>
@@ -1098,8 +1107,39 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       bool liveLo = nLo > 0 && max_sweeps > 0, liveHi = nHi > 0 && max_sweeps > 0;
       const bool sweptLo = liveLo, sweptHi = liveHi;
       float force_out = force;
-      // while BOTH envs sweep: one row step = row i of both (7 VALU: mul, max, two v_readlane, the half's pick, fma, and ONE v_cndmask under the
-      // mask {i, 32 + i} that keeps the two turn-holders' steps - they are the d_ of those very lanes)
+      // The row step writes its proposal max(res * nAinv, nforce) straight into the sweep's step register dl, under an EXEC that holds only the
+      // lanes whose turn has not passed (todo: the rows this sweep runs; bit i leaves after row i).  Lane i so keeps the step of its own turn,
+      // a lane without a turn keeps the 0 that dl starts with, and nothing is spent on carrying the steps along (v_readlane ignores EXEC, and
+      // only pending lanes' proposals are ever read).  Every value comes from the instruction, and the operands, of the one-env kernel's row step.
+      // A chunk of four rows is ONE asm statement: EXEC is narrowed inside it only and restored before it ends.  Wait states inside the string
+      // (the compiler's hazard recogniser does not look there): the scalar mask update sits between the v_max that writes dl and the v_readlane
+      // that reads it (one state), and no VALU instruction reads a scalar register within two instructions of the v_readlane that wrote it.
+      // while BOTH envs sweep: one row step = row i of both, 6 VALU: mul, max, two v_readlane, and each half's fma under its half of EXEC (a
+      // v_cndmask between the two scalars would cost two more VALU moves: one scalar operand per instruction)
+#define HB_PGS_MASK2 "s_mov_b32 exec_lo, %[m]\n\ts_mov_b32 exec_hi, %[m]\n\t"
+#define HB_PGS_ROW2(k)                                                               \
+  "v_mul_f32_e32 %[d], %[na], %[r]\n\t"                                              \
+  "v_max_f32_e32 %[dl], %[d], %[nf]\n\t"                                             \
+  "s_bitset0_b32 %[m], %[i0]+" #k "\n\t"                                             \
+  "v_readlane_b32 %[a], %[dl], %[i0]+" #k "\n\t"                                     \
+  "v_readlane_b32 %[b], %[dl], %[i0]+32+" #k "\n\t"                                  \
+  "s_mov_b64 exec, %[lo]\n\t"                                                        \
+  "v_fmac_f32_e32 %[r], %[a], %[ar" #k "]\n\t"                                       \
+  "s_mov_b64 exec, %[hi]\n\t"                                                        \
+  "v_fmac_f32_e32 %[r], %[b], %[ar" #k "]\n\t"
+#define HB_PGS_ROWS2_4 HB_PGS_MASK2 HB_PGS_ROW2(0) HB_PGS_MASK2 HB_PGS_ROW2(1) HB_PGS_MASK2 HB_PGS_ROW2(2) HB_PGS_MASK2 HB_PGS_ROW2(3)
+#define HB_PGS_ROWS2_3 HB_PGS_MASK2 HB_PGS_ROW2(0) HB_PGS_MASK2 HB_PGS_ROW2(1) HB_PGS_MASK2 HB_PGS_ROW2(2)
+#define HB_PGS_CHUNK2(c, rows)                                                       \
+  if ((c) * 4 >= ne) break;                                                          \
+  {                                                                                  \
+    float d_;                                                                        \
+    int da_, db_;                                                                    \
+    unsigned long long ex_;                                                          \
+    asm volatile("s_mov_b64 %[t], exec\n\t" rows "s_mov_b64 exec, %[t]"              \
+                 : [r] "+v"(res), [dl] "+v"(dl), [m] "+s"(todo), [d] "=&v"(d_), [a] "=&s"(da_), [b] "=&s"(db_), [t] "=&s"(ex_) \
+                 : [na] "v"(nAinv), [nf] "v"(nforce), [ar0] "v"(arS[(c) * 4]), [ar1] "v"(arS[(c) * 4 + 1]), [ar2] "v"(arS[(c) * 4 + 2]), \
+                   [ar3] "v"(arS[(c) * 4 + 3 < 31 ? (c) * 4 + 3 : 30]), [i0] "n"((c) * 4), [lo] "s"(0x00000000ffffffffull), [hi] "s"(0xffffffff00000000ull)); \
+  }
       while (liveLo && liveHi) {
         int ne;
         {
@@ -1108,37 +1148,11 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
         }
         const float nforce = -force, res0 = res;
         float dl = 0.f;
-        unsigned long long turn_ = 0x0000000100000001ull;  // the lanes whose turn it is: row 0 of both envs
-#define HB_PGS_ROW2(i)                                                               \
-  if ((i) < 31) {                                                                    \
-    const float d_ = fmaxf(res * nAinv, nforce);                                     \
-    int da_, db_;                                                                    \
-    unsigned long long ex_;                                                          \
-    /* res += arS[i] * (the step of row i of the lane's own env): the two steps stay in scalar registers and each half takes its own */ \
-    /* under its half of EXEC (a v_cndmask between two scalars would cost two more VALU moves: one scalar operand per instruction). */ \
-    /* The turn-holders' mask {i, 32 + i} walks up one bit per row (thirty-one 64-bit constants would live in scalar registers, and */ \
-    /* spill).  One asm statement, ordered so that no VALU instruction reads a scalar register within two instructions of the */      \
-    /* statement's start or of the v_readlane that wrote it: the compiler's hazard recogniser does not look inside. */                 \
-    asm volatile("s_mov_b64 %[t], exec\n\t"                                          \
-                 "v_readlane_b32 %[a], %[d], %[ia]\n\t"                              \
-                 "v_readlane_b32 %[b], %[d], %[ib]\n\t"                              \
-                 "v_cndmask_b32_e64 %[dl], %[dl], %[d], %[turn]\n\t"                 \
-                 "s_lshl_b64 %[turn], %[turn], 1\n\t"                                \
-                 "s_mov_b64 exec, %[lo]\n\t"                                         \
-                 "v_fmac_f32_e32 %[r], %[a], %[ar]\n\t"                              \
-                 "s_mov_b64 exec, %[hi]\n\t"                                         \
-                 "v_fmac_f32_e32 %[r], %[b], %[ar]\n\t"                              \
-                 "s_mov_b64 exec, %[t]"                                               \
-                 : [r] "+v"(res), [dl] "+v"(dl), [turn] "+s"(turn_), [a] "=&s"(da_), [b] "=&s"(db_), [t] "=&s"(ex_) \
-                 : [d] "v"(d_), [ar] "v"(arS[(i) < 31 ? (i) : 0]), [ia] "n"(i), [ib] "n"(32 + (i)), [lo] "s"(0x00000000ffffffffull), [hi] "s"(0xffffffff00000000ull) \
-                 : "scc");                                                           \
-  }
-#define HB_PGS_CHUNK2(c) if ((c) * 4 >= ne) break; HB_PGS_ROW2((c) * 4) HB_PGS_ROW2((c) * 4 + 1) HB_PGS_ROW2((c) * 4 + 2) HB_PGS_ROW2((c) * 4 + 3)
+        unsigned todo = (1u << min((ne + 3) & ~3, 31)) - 1u;  // the rows the chunks below run, in both halves
         do {
-          HB_PGS_CHUNK2(0) HB_PGS_CHUNK2(1) HB_PGS_CHUNK2(2) HB_PGS_CHUNK2(3) HB_PGS_CHUNK2(4) HB_PGS_CHUNK2(5) HB_PGS_CHUNK2(6) HB_PGS_CHUNK2(7)
+          HB_PGS_CHUNK2(0, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(1, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(2, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(3, HB_PGS_ROWS2_4)
+          HB_PGS_CHUNK2(4, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(5, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(6, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(7, HB_PGS_ROWS2_3)
         } while (0);
-#undef HB_PGS_CHUNK2
-#undef HB_PGS_ROW2
         const float delta = dl;
         force += delta;
         float iLo, iHi;
@@ -1153,8 +1167,16 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
           if (h) { force_out = force; res = 0.f; force = 0.f; }
         }
       }
-      // ONE env still sweeps (the wave sweeps max(sA, sB) times: 29 against a mean of 20 per env): the one-env kernel's row step (5 VALU) on that
-      // env's lanes.  The other half's lanes ride along: their res takes garbage, their step stays 0 and their forces are in force_out.
+#undef HB_PGS_CHUNK2
+#undef HB_PGS_ROWS2_3
+#undef HB_PGS_ROWS2_4
+#undef HB_PGS_ROW2
+#undef HB_PGS_MASK2
+      // ONE env still sweeps (the wave sweeps max(sA, sB) times, each env its own count): the one-env kernel's row step (5 VALU, the compiler's
+      // code, EXEC untouched) on that env's lanes, and the sum of the convergence test over that env's half alone.  The pending-lane form of
+      // the paired loop was measured here too (4 VALU, two EXEC writes per row): 5 % SLOWER per step - a scalar write of EXEC ahead of a
+      // vector instruction costs this loop more than the v_writelane it saves (profiles/pgs_sweeps_bench.txt).  The other half's lanes ride
+      // along: their res takes garbage, their step stays 0 and their forces are in force_out.
 #define HB_PGS_ROW1(base, i)                                                         \
   if ((i) < 31) {                                                                    \
     const float d_ = fmaxf(res * nAinv, nforce);                                     \
@@ -1174,10 +1196,9 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
         } while (0);                                                                 \
         const float delta = __int_as_float(dl);                                      \
         force += delta;                                                              \
-        float iLo, iHi;                                                              \
-        env_sums((mine) ? delta * (res0 + res) : 0.f, iLo, iHi);                     \
+        const float improvement = half_sum<base>(delta * (res0 + res));              \
         niter_++;                                                                    \
-        if (-0.5f * ((base) ? iHi : iLo) * pgs_scale < pgs_tol || niter_ >= max_sweeps) { \
+        if (-0.5f * improvement * pgs_scale < pgs_tol || niter_ >= max_sweeps) {     \
           live = false;                                                              \
           if (mine) force_out = force;                                               \
         }                                                                            \
