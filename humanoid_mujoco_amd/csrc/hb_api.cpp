@@ -183,6 +183,39 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
     return false;
   }
   dm.mpr_iterations = 50; dm.mpr_tolerance = 1e-6f;  // mjOption.mpr_iterations / mpr_tolerance defaults (mjmodel.h:413,437)
+  // Friction loss (mj_instantiateFriction): one always-active row per dof with dof_frictionloss > 0, in front of the limit rows, unless the
+  // options disable it - then the model is an ordinary one.  What a row needs besides its dof and its bound does not depend on the state
+  // (pos = margin = 0), so it is worked out here, in fp64, with the options as they are now: one record per row, (dof, frictionloss, R, B).
+  std::vector<float> frec;
+  if (!(m.disableflags & (DSBL_CONSTRAINT | DSBL_FRICTIONLOSS))) {
+    for (int d = 0; d < nv; d++) {
+      const double fl = m.dof_frictionloss[d];
+      if (!(fl > 0)) continue;
+      static const double def_ref[2] = {0.02, 1}, def_imp[5] = {0.9, 0.95, 0.001, 0.5, 2};
+      const double* sr = m.dof_solref_friction.size() == (size_t)2 * nv ? &m.dof_solref_friction[2 * d] : def_ref;
+      const double* si = m.dof_solimp_friction.size() == (size_t)5 * nv ? &m.dof_solimp_friction[5 * d] : def_imp;
+      const double MINVAL = 1e-15, MINIMP = 0.0001, MAXIMP = 0.9999;
+      auto clip = [](double x, double lo, double hi) { return std::min(std::max(x, lo), hi); };
+      // impedance(solimp, 0, 0): solimp[0] clipped - or the mean of the two ends in the degenerate cases of getimpedance
+      const double d0 = clip(si[0], MINIMP, MAXIMP), d1 = clip(si[1], MINIMP, MAXIMP);
+      const double imp = (d0 == d1 || std::max(0.0, si[2]) <= MINVAL) ? 0.5 * (d0 + d1) : d0;
+      const double R = std::max(MINVAL, (1 - imp) / imp * m.dof_invweight0[d]);
+      double B;  // (kb_from_solref; K multiplies pos - margin = 0)
+      if (sr[0] > 0) {
+        const double tc = (m.disableflags & DSBL_REFSAFE) ? sr[0] : std::max(sr[0], 2 * m.timestep);
+        B = 2 / std::max(MINVAL, d1 * tc);
+      } else B = -sr[1] / std::max(MINVAL, d1);
+      float dbits; memcpy(&dbits, &d, 4);  // (the dof index as bits, as every record keeps its integers)
+      frec.push_back(dbits); frec.push_back((float)fl); frec.push_back((float)R); frec.push_back((float)B);
+    }
+  }
+  dm.nfric = (int)frec.size() / 4;
+  if (dm.nfric && dm.variant != 0) {
+    err = "friction loss: only models that step in one kernel (plane / sphere / capsule geoms, condim 1 / 3) are implemented; this model steps in stages (mesh hulls, height fields or condim 4 / 6): remove the joints' frictionloss or set <flag frictionloss=\"disable\"/>";
+    return false;
+  }
+  if (dm.nfric && m.integrator == INT_RK4) { err = "friction loss: the RK4 integrator is not implemented for a model with joint frictionloss: use the Euler integrator"; return false; }
+  if (frec.empty()) frec.assign(4, 0.f);
 
   // trees, levels, children, dof masks
   std::vector<int> treeid(nb, 0), roots;
@@ -565,7 +598,7 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
   const size_t o_meshv = T.addraw(meshv), o_meshn = T.addraw(meshn), o_meshs = T.addraw(meshs);
   const size_t o_arec = T.addraw(arec);
   size_t o_brec = T.addraw(brec), o_drec = T.addraw(drec), o_mdiag = T.addraw(mdiag), o_prec = T.addraw(prec), o_crec = T.addraw(crec), o_trec = T.addraw(trec),
-         o_lrec = T.addraw(lrec);
+         o_lrec = T.addraw(lrec), o_frec = T.addraw(frec);
 
   // ---- upload
   if (D.d_int.alloc(T.iv.size()) != HB_OK || D.d_flt.alloc(T.fv.size()) != HB_OK || D.d_u64.alloc(T.uv.size()) != HB_OK) { err = "hipMalloc failed for model tables"; return false; }
@@ -581,6 +614,7 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
   dm.crec = reinterpret_cast<const float4*>(D.d_flt + o_crec);
   dm.trec = reinterpret_cast<const float4*>(D.d_flt + o_trec);
   dm.lrec = reinterpret_cast<const float4*>(D.d_flt + o_lrec);
+  dm.frec = reinterpret_cast<const float4*>(D.d_flt + o_frec);
   D.obs_jnt_joint = dm.obs_jnt; D.obs_src_joint = dm.obs_src;
   D.obs_jnt_act = D.d_int + o_obs_jnt_act; D.obs_src_act = D.d_int + o_obs_src_act;
   dm.arec = reinterpret_cast<const float4*>(D.d_flt + o_arec);
@@ -825,7 +859,7 @@ int fork_pipes(hb_batch* b, int nseg) {
 // the batch's model through launch_step; the launched kernel's name stays with the batch (hb_last_kernel)
 hipError_t launch_batch_step(hb_batch* b, const BatchPtrs& P, int nsteps, hipStream_t stream) {
   const DevModel& dm = b->D.dm;
-  return launch_step(b->D.d_dm, dm.variant, dm.solver, dm.integrator, dm.nv, dm.lds_floats, P, nsteps, stream, &b->last_kernel);
+  return launch_step(b->D.d_dm, dm.variant, dm.solver, dm.integrator, dm.nv, dm.nfric, dm.lds_floats, P, nsteps, stream, &b->last_kernel);
 }
 // one segment's launch of the step kernel, then (heavy-first scheduling, every 4th call) the tiny kernel that
 // orders the segment's next launch by the cost of this one; costs change slowly, and the sort sits on the
@@ -900,7 +934,7 @@ int launch_steps(hb_batch* b, BatchPtrs& P, int nsteps, bool foldable = false) {
   foldable = false;  // (the diagnostic build samples single launches)
 #endif
   foldable = foldable && b->npipe > 1 && cap > 1 && nsteps <= cap && P.ctrl_mode == 0 && !b->time_steps && !b->diag && !P.stamps && P.xfrc_scale == 0.f &&
-             fold_pays(b->D.dm.variant, b->D.dm.solver, b->D.dm.integrator, b->D.dm.nv, P);
+             fold_pays(b->D.dm.variant, b->D.dm.solver, b->D.dm.integrator, b->D.dm.nv, b->D.dm.nfric, P);
   if (!foldable) {
     const int rc = flush_steps(b);
     return rc != HB_OK ? rc : launch_steps_now(b, P, nsteps);
@@ -1105,6 +1139,7 @@ int hb_model_get_array(const hb_model* h, const char* field, double* out, int ca
   if (!h || !field) return HB_EINVAL;
   struct Finder {
     const char* want; const vecd* found = nullptr; const veci* foundi = nullptr;
+    bool optional(bool) { return true; }
     void operator()(const char* n, vecd& v) { if (!strcmp(n, want)) found = &v; }
     void operator()(const char* n, veci& v) { if (!strcmp(n, want)) foundi = &v; }
     void operator()(const char*, int&) {}
@@ -1346,7 +1381,7 @@ int hb_inverse_dev(hb_batch* b, const float* qacc_dev, int flags, float* qfrc_in
   P.stage = b->stage;  // general variants: the narrowphase of a staged step into the batch's stage buffers, which every step rewrites
   P.stage.defer = nullptr; P.stage.defer_list = nullptr; P.stage.defer_count = nullptr; P.stage.dm_fast = nullptr; P.stage.fast_lds = 0;
   P.inv_qacc = qacc_dev; P.inv_out = qfrc_inverse_dev; P.inv_warn = warnings_dev; P.inv_flags = flags;
-  HB_HIP(launch_inverse(b->D.d_dm, b->D.dm.variant, b->D.dm.nv, b->D.dm.lds_floats, P, stream, &b->last_kernel));
+  HB_HIP(launch_inverse(b->D.d_dm, b->D.dm.variant, b->D.dm.nv, b->D.dm.nfric, b->D.dm.lds_floats, P, stream, &b->last_kernel));
   return HB_OK;
 }
 
@@ -1741,6 +1776,7 @@ static int sensor_setup(hb_batch* b, const hb_sensor_spec* spec, int T, BatchPtr
   const Model& m = b->model->m;
   const int ns = hb_sensor_size(spec);
   if (ns <= 0) return HB_EINVAL;
+  if (spec->n_imu + spec->n_frameacc > 0 && b->D.dm.nfric) return HB_EUNSUPPORTED;  // (friction loss: no kernel with the body-acceleration read-out)
   for (int k = 0; k < spec->n_framepos; k++) if (spec->framepos_body[k] < 0 || spec->framepos_body[k] >= m.nbody) return HB_EINVAL;
   int tree = -1;
   if (spec->subtree_body >= 0) {
@@ -2641,6 +2677,7 @@ int hb_contact_readout_dev(hb_batch* b, const float** contact_force_dev, const f
 int hb_body_acc_readout(hb_batch* b, int on) {
   if (!b) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
+  if (on && b->D.dm.nfric) return HB_EUNSUPPORTED;  // (a model with friction loss: no step kernel has both the friction rows and this read-out)
   (void)main_stream(b);  // from the next launch on: step calls held back are launched as they were made
   if (on && alloc_body_acc_readout(b) != HB_OK) return HB_ENOMEM;
   b->body_acc_readout = on != 0;

@@ -137,6 +137,10 @@ struct DevModel {
   int cstride;     // row stride of C (odd: conflict-free lane-strided access; the last column is zero padding)
   // mjtIntegrator (0 Euler, 1 RK4) and, RK4 only, the stage block behind both regions: q0[nq] | v0[nv] | sum b V [nv] | sum b F [nv]
   int integrator, o_rk;
+  // friction loss: the rows in front of the limit rows, one per dof with dof_frictionloss > 0 (0: an ordinary model, or disabled by the
+  // options), and per row (dof, frictionloss, R, B) as build_device_model works them out.  Read by step_body's FRIC instantiations only.
+  int nfric;
+  const float4 HB_CONST* frec;
 };
 
 typedef const DevModel HB_CONST& DevModelRef;

@@ -49,6 +49,15 @@ struct Model {
   // ---- dofs (mjmodel.h:715-728)
   veci dof_bodyid, dof_jntid, dof_parentid, dof_Madr;
   vecd dof_armature, dof_damping, dof_frictionloss, dof_invweight0, dof_M0;
+  // solver parameters of the friction-loss rows (mjModel.dof_solref / dof_solimp), 2 / 5 per dof.  Optional records of the .hbm format:
+  // written only by a model with a non-zero dof_frictionloss, MuJoCo's defaults when absent (fill_friction_defaults)
+  vecd dof_solref_friction, dof_solimp_friction;
+  bool has_frictionloss() const { for (double v : dof_frictionloss) if (v != 0) return true; return false; }
+  void fill_friction_defaults() {
+    static const double si[5] = {0.9, 0.95, 0.001, 0.5, 2};
+    if (dof_solref_friction.empty()) for (int d = 0; d < nv; d++) { dof_solref_friction.push_back(0.02); dof_solref_friction.push_back(1); }
+    if (dof_solimp_friction.empty()) for (int d = 0; d < nv; d++) for (double v : si) dof_solimp_friction.push_back(v);
+  }
   // ---- geoms (mjmodel.h:729-760)
   veci geom_type, geom_bodyid, geom_contype, geom_conaffinity, geom_condim, geom_priority,
       geom_dataid;
@@ -107,6 +116,7 @@ struct Model {
     HB_F(jnt_solref); HB_F(jnt_solimp);
     HB_F(dof_bodyid); HB_F(dof_jntid); HB_F(dof_parentid); HB_F(dof_Madr);
     HB_F(dof_armature); HB_F(dof_damping); HB_F(dof_frictionloss); HB_F(dof_invweight0); HB_F(dof_M0);
+    if (f.optional(has_frictionloss())) { HB_F(dof_solref_friction); HB_F(dof_solimp_friction); }  // (a writer: only when present)
     HB_F(geom_type); HB_F(geom_bodyid); HB_F(geom_contype); HB_F(geom_conaffinity); HB_F(geom_condim);
     HB_F(geom_priority); HB_F(geom_dataid);
     HB_F(geom_size); HB_F(geom_pos); HB_F(geom_quat); HB_F(geom_rbound); HB_F(geom_friction);

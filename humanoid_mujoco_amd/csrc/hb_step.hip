@@ -53,7 +53,11 @@ __device__ __forceinline__ void defer_env(const BatchPtrs& P, int env) {
 // belongs to the step and not to a forward pass - controls, noise, the mj_check*s, the sensor read-out - is done in the first pass only.
 // ACC: the body-acceleration read-out (hb_body_acc_readout).  Its parking and its epilogue exist in instantiations of their own, which a
 // launch takes when it carries the read-out (select_step); every other instantiation compiles without them, as before the read-out existed.
-template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0, int INV = 0, int INTEG = 0, int ACC = 0>
+// FRIC: joint friction loss (mj_instantiateFriction): one always-active row per dof with dof_frictionloss > 0, in front of the limit rows,
+// whose force is bounded on both sides, -frictionloss <= f <= frictionloss.  In the dual (PGS) the row's max becomes a clamp; in the primal
+// (Newton, mj_inverse) the row's cost has three zones: quadratic inside |jar| < R frictionloss, linear with the force at its bound outside.
+// Every line of it sits behind FRIC: the instantiations a model without friction loss runs are the code they were (HB_FRIC_KERNELS).
+template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0, int INV = 0, int INTEG = 0, int ACC = 0, int FRIC = 0>
 __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P, int nsteps_in, int env_in = -1) {
   const int nsteps = LEAN == 1 ? 1 : nsteps_in;  // (LEAN == 1 is launched for single steps only: the step API; rollouts take LEAN == 2)
   // LEAN (1 = a single step without the constraint-force read-out; 2 = any number of steps, read-out optional): a launch without the optional inputs and outputs (applied forces and their noise, constraint-force / sensor / trajectory
@@ -77,6 +81,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   const int P_integrate = INV ? 0 : LEAN ? 1 : P.integrate;
   static_assert(SIZED == 0 || (NG == 1 && ((NDENSE == 28 && (COLL == 0 || SOLVER == 0)) || (NDENSE == 20 && COLL == 1 && SOLVER == 2))), "the size-specialised instantiations: the humanoid (classic or variant-1 layout) and the robot (Newton, variant-1 layout)");
   static_assert(ACC == 0 || (LEAN == 0 && SIZED == 0 && INV == 0), "the body-acceleration read-out: full kernels only");
+  static_assert(FRIC == 0 || (COLL == 0 && NG == 1 && DEFER == 0 && LEAN == 0 && SIZED == 0 && INTEG == 0 && ACC == 0), "friction loss: the full Euler kernels of the classic variant");
   static_assert(INTEG == 0 || (COLL == 0 && NG == 1 && DEFER == 0 && LEAN == 0 && SIZED == 0 && INV == 0), "RK4: the full kernels of the classic variant");
   static_assert(NG == 1 || SOLVER == 2 || (COLL == 1 && NG == kPgsGroups && DEFER == 0), "PGS on more than one row group: the general variant's kPgsGroups instantiation");
   constexpr int kNR = NG == 1 ? kNefcMax : 64 * NG;  // row capacity of this instantiation
@@ -820,6 +825,11 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     int nefc = 0;
     const bool constraints_on = !(M_disableflags & (1 << 0));
     const int selfcol = __any(selfc) ? 1 : 0;
+    // friction loss (FRIC only): the number of friction rows - rows 0 .. nf - 1, lane = row - and what this lane's row needs: its bound, R
+    // and the damper B of its reference (aref = -B qvel[dof]: pos - margin = 0).  M.nfric is zero when the options disable the rows.
+    int nf = 0;
+    float fr_fl = 0.f, fr_R = 1.f, fr_B = 0.f;
+    (void)nf; (void)fr_fl; (void)fr_R; (void)fr_B;
     if constexpr (COLL != 0) {
       // ---- general form: limits, then contacts of dimension 1 / 3 / 4 / 6 (one row, or 2 (dim - 1) pyramid rows); what the solver
       // needs of a row besides its Jacobian is written once, here: s_meta[row] = (R, K imp (pos - margin), B, -)
@@ -944,6 +954,18 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
         nefc = nefc_after;
       }
     } else {
+    if constexpr (FRIC) {
+      // (0) friction loss: a unit Jacobian row per dof that has it, in dof order (nf <= nv <= 32: these rows always fit)
+      nf = M.nfric;
+      if (lane < nf) {
+        const float4 fr = M.frec[lane];
+        float* Jr = s_C + lane * cs;
+        for (int k = 0; k < cs; k++) Jr[k] = 0.f;
+        Jr[__float_as_int(fr.x)] = 1.f;
+        fr_fl = fr.y; fr_R = fr.z; fr_B = fr.w;
+      }
+      nefc = nf;
+    }
     // (a) limits: 2 candidates (lower, upper) per limited joint / tendon, in constraint order
     if (constraints_on && !(M_disableflags & (1 << 3))) {
       for (int c0 = 0; c0 < HB_SZ(nlimcand); c0 += kGroup) {
@@ -1103,6 +1125,10 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
           Rg[g] = e[0];
           Ddg[g] = 1.f / Rg[g];
           arefg[g] = -e[2] * vel - e[1];
+        } else if (FRIC && row < nf) {  // (a friction row: R and B from the host, no row meta)
+          Rg[g] = fr_R;
+          Ddg[g] = 1.f / fr_R;
+          arefg[g] = -fr_B * vel;
         } else {
           const float* e = s_efc + row;
           float pos = e[E_POS * kNR], margin = e[E_MARGIN * kNR];
@@ -1123,6 +1149,10 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     const bool rowact = actg[0];
     float R = Rg[0], Dd = Ddg[0], aref = arefg[0], jw = jwg[0], force = 0.f, bvec = 0.f;
     (void)R; (void)bvec; (void)jw;
+    // FRIC: the force bounds of this lane's row: [-frictionloss, frictionloss] on a friction row, [0, inf) on every other
+    const bool fricrow = FRIC && lane < nf;
+    const float f_lo = fricrow ? -fr_fl : 0.f, f_hi = fricrow ? fr_fl : __builtin_inff();
+    (void)fricrow; (void)f_lo; (void)f_hi;
     gsync();
     if constexpr (INV) {
       // ---------------------------------------------------------------- mj_inverse (mj_invConstraint, mj_rne with acceleration)
@@ -1160,7 +1190,8 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
           for (; k + 2 <= nv; k += 2) { jq = __builtin_fmaf(Jr[k], s_v0[k], jq); jq2 = __builtin_fmaf(Jr[k + 1], s_v0[k + 1], jq2); }
           if (k < nv) jq = __builtin_fmaf(Jr[k], s_v0[k], jq);
           const float jar = jq + jq2 - arefg[g];
-          s_force[row] = jar < 0.f ? -Ddg[g] * jar : 0.f;
+          if constexpr (FRIC) s_force[row] = __builtin_amdgcn_fmed3f(-Ddg[g] * jar, f_lo, f_hi);  // (the three zones of a friction row are this clamp)
+          else s_force[row] = jar < 0.f ? -Ddg[g] * jar : 0.f;
         }
       }
       gsync();
@@ -1299,7 +1330,8 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       float arf = 0.f;  // (AR force)_lane
       if (!(M_disableflags & (1 << 8))) {
         const float jar = jw - aref;
-        force = (rowact && jar < 0.f) ? -Dd * jar : 0.f;
+        if constexpr (FRIC) force = rowact ? __builtin_amdgcn_fmed3f(-Dd * jar, f_lo, f_hi) : 0.f;
+        else force = (rowact && jar < 0.f) ? -Dd * jar : 0.f;
 #pragma unroll
         for (int c = 0; c < (kNR + 3) / 4; c++) {
           if (c * 4 < nefc) {
@@ -1332,11 +1364,15 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
         int ne;
         asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(nefc));
         const float nforce = -force, res0 = res;
+        // FRIC: the step of a row is clamped on both sides, med3(-res / AR_ii, lo - force, hi - force): one v_med3_f32 where the
+        // unilateral rows have one v_max_f32 (for them lo - force = -force and hi - force = inf: the same step)
+        const float dlo = f_lo - force, dhi = f_hi - force;
+        (void)nforce; (void)dlo; (void)dhi;
         int dl = 0;
         // hand-unrolled (ar[i] needs a compile-time register index) with one scalar exit test per 4 rows
 #define HB_PGS_ROW(i)                                                              \
   if ((i) < kNR) {                                                            \
-    const float d_ = fmaxf(res * nAinv, nforce);                                   \
+    const float d_ = FRIC ? __builtin_amdgcn_fmed3f(res * nAinv, dlo, dhi) : fmaxf(res * nAinv, nforce); \
     const int di_ = __builtin_amdgcn_readlane(__float_as_int(d_), (i));            \
     res = __builtin_fmaf(ar[(i) < kNR ? (i) : 0], __int_as_float(di_), res);  \
     dl = hb_writelane(di_, (i), dl);                                               \
@@ -1353,6 +1389,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
         static_assert(kNefcMax <= 64, "PGS sweep is unrolled for at most 64 rows");
         const float delta = __int_as_float(dl);
         force += delta;  // a clamped row lands on exactly 0
+        if constexpr (FRIC) force = __builtin_amdgcn_fmed3f(force, f_lo, f_hi);  // (... and on its bound to the last bit: f + (hi - f) may round past hi)
         const float improvement = -0.5f * wave_sum(delta * (res0 + res));
         niter++;
         if (improvement * pgs_scale < pgs_tol) break;
@@ -1570,6 +1607,18 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
 #pragma unroll
       for (int g = 0; g < NG; g++) forceg[g] = 0.f;
       HB_STAMP(11);
+      // FRIC: the three cost zones of a friction row (PrimalUpdateConstraint's mjCNSTRSTATE_LINEARNEG / LINEARPOS / QUADRATIC) in terms of
+      // jar = J qacc - aref:  jar <= -R fl: force +fl, cost fl (-R fl / 2 - jar);  jar >= R fl: force -fl, cost fl (-R fl / 2 + jar);
+      // between: force -D jar, cost D jar^2 / 2 - the only zone in which the row is part of the Hessian.  (one row group: lane = row)
+      const float f_Rfl = fr_R * fr_fl;
+      (void)f_Rfl;
+      // zone of this lane's row at jar = x: +1 / -1 the linear zone whose force is +fl / -fl, 0 quadratic (a friction row) or active (any other), 2 inactive
+      auto fzone = [&](float x) -> int { return fricrow ? (x <= -f_Rfl ? 1 : x >= f_Rfl ? -1 : 0) : (x < 0.f ? 0 : 2); };
+      auto fcost = [&](float x) -> float {
+        const int z = fzone(x);
+        return z == 0 ? 0.5f * Ddg[0] * x * x : z == 2 ? 0.f : fr_fl * (-0.5f * f_Rfl - (float)z * x);
+      };
+      (void)fcost;
       if (nefc > 0) {
         // J x for every row group (and M x through the shared broadcasts): rows beyond nefc give 0
 #define HB_JDOT(x, Mout, Jout)                                                        \
@@ -1595,8 +1644,11 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
 #pragma unroll
           for (int g = 0; g < NG; g++) {
             jarw[g] = actg[g] ? jwg[g] - arefg[g] : 1.f;
+            if constexpr (FRIC) { cw += fcost(jarw[g]); cq += fcost(jar[g]); }
+            else {
             cw += jarw[g] < 0.f ? 0.5f * Ddg[g] * jarw[g] * jarw[g] : 0.f;
             cq += jar[g] < 0.f ? 0.5f * Ddg[g] * jar[g] * jar[g] : 0.f;
+            }
           }
           if (wave_sum(cw - cq) <= 0.f) {
             qacc = warm; Ma = Mw;
@@ -1622,11 +1674,23 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
           float rowcost = 0.f;
 #pragma unroll
           for (int g = 0; g < NG; g++) {
+            if constexpr (FRIC) {  // (a friction row in a linear zone carries a force but is no part of the active set: the Hessian and its cached factor)
+              const int z = fzone(jar[g]);
+              act[g] = z == 0;
+              forceg[g] = z == 0 ? -Ddg[g] * jar[g] : z == 2 ? 0.f : (float)z * fr_fl;
+              actmask[g] = __ballot(act[g]);
+              rowcost += fcost(jar[g]);
+            } else {
             act[g] = jar[g] < 0.f;
             forceg[g] = act[g] ? -Ddg[g] * jar[g] : 0.f;
             actmask[g] = __ballot(act[g]);
             rowcost += act[g] ? 0.5f * Ddg[g] * jar[g] * jar[g] : 0.f;
+            }
           }
+          // rows that carry a force (FRIC: the active rows and the friction rows at a bound)
+          unsigned long long frcmask[NG];
+#pragma unroll
+          for (int g = 0; g < NG; g++) frcmask[g] = FRIC ? __ballot(forceg[g] != 0.f) : actmask[g];
           qfc = 0.f;
           {
             // eight rows in flight; rows beyond nefc are read from the last row with a zero force
@@ -1636,7 +1700,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
             for (int g = 0; g < NG; g++) {
               if (64 * g >= nefc) break;
               for (int i0 = 0; i0 < 64 && 64 * g + i0 < nefc; i0 += 8) {
-                if (!((actmask[g] >> i0) & 0xffull)) continue;  // eight inactive rows: zero force
+                if (!((frcmask[g] >> i0) & 0xffull)) continue;  // eight inactive rows: zero force
                 float c[8];
 #pragma unroll
                 for (int u = 0; u < 8; u++) c[u] = s_C[min(64 * g + i0 + u, last) * cs + lic];
@@ -1739,8 +1803,14 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
 #pragma unroll
           for (int g = 0; g < NG; g++) {
             DJv[g] = Ddg[g] * Jv[g]; DJv2[g] = DJv[g] * Jv[g];
+            if constexpr (FRIC) {  // (a linear zone: slope -force Jv = -/+ fl Jv, no curvature)
+              const float sl = act[g] ? DJv[g] * jar[g] : -forceg[g] * Jv[g];
+              magr += fabsf(sl);
+              s0 += sl;
+            } else {
             magr += act[g] ? fabsf(DJv[g] * jar[g]) : 0.f;
             s0 += act[g] ? DJv[g] * jar[g] : 0.f;
+            }
             s1 += act[g] ? DJv2[g] : 0.f;
           }
           const float mag = wave_sum(fabsf(search * gq) + magr);
@@ -1755,9 +1825,15 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
 #pragma unroll
                 for (int g = 0; g < NG; g++) {
                   const float x = jar[g] + a * Jv[g];
+                  if constexpr (FRIC) {
+                    const int z = fzone(x);
+                    t0 += z == 0 ? DJv[g] * x : z == 2 ? 0.f : -(float)z * fr_fl * Jv[g];
+                    t1 += z == 0 ? DJv2[g] : 0.f;
+                  } else {
                   const bool on = x < 0.f;
                   t0 += on ? DJv[g] * x : 0.f;
                   t1 += on ? DJv2[g] : 0.f;
+                  }
                 }
                 const float e0 = qg1 + 2.f * a * qg2 + wave_sum(t0), e1 = 2.f * qg2 + wave_sum(t1);
                 alpha = a;
@@ -2201,6 +2277,16 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   K(hb_acc_rk4_newton28_kernel,         2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
   K(hb_acc_rk4_newton32_kernel,         2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
 
+// joint friction loss (step_body's FRIC): the full kernels of the classic variant and its inverse dynamics, one per solver and dense order -
+// what a model with friction rows runs whatever the launch looks like (select_step).
+#define HB_FRIC_KERNELS(K) /* (Mp, P, nsteps) */ \
+  K(hb_fric_kernel,                     0,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
+  K(hb_fric32_kernel,                   0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
+  K(hb_fric_newton28_kernel,            2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
+  K(hb_fric_newton32_kernel,            2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
+  K(hb_fric_inverse_kernel,             2,      28,     0,    1,          0,     0,    0,     1,   2,     0,     0) \
+  K(hb_fric_inverse32_kernel,           2,      32,     0,    1,          0,     0,    0,     1,   2,     0,     0)
+
 // (the entry calls step_body directly: a forwarding function template in between changes register allocation and scheduling)
 #define HB_STEP_BODY_0(...) step_body<__VA_ARGS__>(Mp, P, nsteps)
 #define HB_STEP_BODY_1(...) HB_STEP_OR_RERUN(__VA_ARGS__)
@@ -2219,17 +2305,22 @@ HB_INVERSE_KERNELS(HB_DEFINE_INVERSE)
 HB_RK4_KERNELS(HB_DEFINE_RK4)
 HB_ACC_KERNELS(HB_DEFINE_ACC)
 HB_ACC_RK4_KERNELS(HB_DEFINE_ACC_RK4)
+// (one signature for the whole list: an inverse row runs a single step whatever the count says - launch_pass hands every kernel all three arguments)
+#define HB_DEFINE_FRIC(name, S, ND, C, G, D, L, Z, I, W, V, R) \
+  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<S, ND, C, G, D, L, Z, I, 0, 0, 1>(Mp, P, I ? 1 : nsteps); }
+HB_FRIC_KERNELS(HB_DEFINE_FRIC)
 
 struct StepConfig {
-  int solver, ndense, coll, ng, defer, lean, sized, inv, integ, acc;
-  bool operator==(const StepConfig& o) const { return solver == o.solver && ndense == o.ndense && coll == o.coll && ng == o.ng && defer == o.defer && lean == o.lean && sized == o.sized && inv == o.inv && integ == o.integ && acc == o.acc; }
+  int solver, ndense, coll, ng, defer, lean, sized, inv, integ, acc, fric;
+  bool operator==(const StepConfig& o) const { return solver == o.solver && ndense == o.ndense && coll == o.coll && ng == o.ng && defer == o.defer && lean == o.lean && sized == o.sized && inv == o.inv && integ == o.integ && acc == o.acc && fric == o.fric; }
 };
 struct StepKernel { const char* name; const void* fn; StepConfig cfg; bool rerun; };
 #define HB_STEP_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 0}, R != 0},
 #define HB_RK4_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 1}, R != 0},
 #define HB_ACC_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 0, 1}, R != 0},
 #define HB_ACC_RK4_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 1, 1}, R != 0},
-static const StepKernel kStepKernels[] = {HB_STEP_KERNELS(HB_STEP_ROW) HB_INVERSE_KERNELS(HB_STEP_ROW) HB_RK4_KERNELS(HB_RK4_ROW) HB_ACC_KERNELS(HB_ACC_ROW) HB_ACC_RK4_KERNELS(HB_ACC_RK4_ROW)};
+#define HB_FRIC_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 0, 0, 1}, R != 0},
+static const StepKernel kStepKernels[] = {HB_STEP_KERNELS(HB_STEP_ROW) HB_INVERSE_KERNELS(HB_STEP_ROW) HB_RK4_KERNELS(HB_RK4_ROW) HB_ACC_KERNELS(HB_ACC_ROW) HB_ACC_RK4_KERNELS(HB_ACC_RK4_ROW) HB_FRIC_KERNELS(HB_FRIC_ROW)};
 static const StepKernel* find_step_kernel(const StepConfig& c) {
   for (const StepKernel& k : kStepKernels) if (k.cfg == c) return &k;
   return nullptr;
@@ -2267,11 +2358,14 @@ static bool lean_launch(const BatchPtrs& P, bool with_qfrc = false) {
 // runs on the one-group model StageBufs::dm_fast with its own LDS size: kernel, model and LDS size are chosen together), or the inverse.
 enum class StepPass { Main, Fast, Inverse };
 struct StepChoice { const StepKernel* kernel; bool duo; const DevModel* M_dev; size_t shmem; };  // (duo: launch_step_duo, no table row)
-static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant, int solver, int integrator, int nv, size_t shmem, const BatchPtrs& P, int nsteps) {
+static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant, int solver, int integrator, int nv, int fric, size_t shmem, const BatchPtrs& P, int nsteps) {
   StepConfig c = variant == 1   ? StepConfig{0, 28, 1, 1}
                  : variant == 3 ? StepConfig{0, 28, 1, kPgsGroups}
                  : variant == 2 ? StepConfig{2, nv <= 20 ? 20 : 28, 1, kBigGroups}
                                 : StepConfig{solver == 2 ? 2 : 0, nv <= 28 ? 28 : 32, 0, 1};
+  // a model with friction rows: the FRIC instantiation of the full kernel - there is no lean, size-specialised, two-envs-per-wave, staged,
+  // RK4 or body-acceleration one (the latter three are refused before a launch: hb_batch_create, hb_body_acc_readout)
+  c.fric = fric ? 1 : 0;
   if (pass == StepPass::Inverse) {
     c.solver = 2; c.defer = c.coll ? 2 : 0; c.inv = 1;
     return {find_step_kernel(c), false, M_dev, shmem};
@@ -2289,7 +2383,7 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant,
   }
   const bool sized_ok = P.lean_ok & (c.ndense == 20 ? 4 : 2);  // (the layout HB_SZ would take)
   // (the two-envs-per-wave kernels write the joint torques when asked: the env adapter's launches take them as well)
-  if (!c.coll && c.solver == 0 && c.ndense == 28 && lean_launch(P, true) && sized_ok && duo_pays(P, nsteps)) return {nullptr, true, M_dev, shmem};
+  if (!c.fric && !c.coll && c.solver == 0 && c.ndense == 28 && lean_launch(P, true) && sized_ok && duo_pays(P, nsteps)) return {nullptr, true, M_dev, shmem};
   // LEAN 1: a single step without the constraint-force read-out; 2: any number of steps, read-out optional.  An instantiation that does
   // not exist: the same without the sizes as constants, then the full kernel.
   c.lean = (nsteps == 1 && lean_launch(P)) ? 1 : lean_launch(P, true) ? 2 : 0;
@@ -2302,9 +2396,9 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant,
 }
 // The one launch site.  Every launch hands back its kernel's name (hb_last_kernel: tests and bench.py name the kernel they measured by
 // what the library says it launched, not by a literal).
-static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, int variant, int solver, int integrator, int nv, size_t shmem, const BatchPtrs& P, int nsteps, hipStream_t stream,
+static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, int variant, int solver, int integrator, int nv, int fric, size_t shmem, const BatchPtrs& P, int nsteps, hipStream_t stream,
                               const char** kernel) {
-  const StepChoice s = select_step(pass, M_dev, variant, solver, integrator, nv, shmem, P, nsteps);
+  const StepChoice s = select_step(pass, M_dev, variant, solver, integrator, nv, fric, shmem, P, nsteps);
   if (s.duo) return launch_step_duo(s.M_dev, P, nsteps, stream, kernel);
   if (!s.kernel) return hipErrorInvalidDeviceFunction;
   (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
@@ -2323,20 +2417,20 @@ static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, int variant,
 // steps); two-envs-per-wave waves, for the models that have that kernel: up to twice as many envs (4096: 67 against 78).  Beyond one
 // round a multi-step launch is no faster than pipelined single steps, and slower when its last round is part empty (4608 envs: 104
 // against 85) - profiles/r04_fold_sizes_by_batch.txt.
-bool fold_pays(int variant, int solver, int integrator, int nv, const BatchPtrs& P) {
-  if (variant != 0) return false;
+bool fold_pays(int variant, int solver, int integrator, int nv, int fric, const BatchPtrs& P) {
+  if (variant != 0 || fric) return false;  // (a model with friction rows: single-step launches of its full kernel, as they are tested)
   if (P.n_env <= wave_slots()) return true;
   // (would the folded launch be a duo launch?  Step calls that read the constraint forces out are not folded onto it)
-  const bool duo_kernel = !P.qfrc_out && select_step(StepPass::Main, nullptr, variant, solver, integrator, nv, 0, P, 2).duo;
+  const bool duo_kernel = !P.qfrc_out && select_step(StepPass::Main, nullptr, variant, solver, integrator, nv, fric, 0, P, 2).duo;
   return duo_kernel && (P.n_env + 1) / 2 <= wave_slots();
 }
 
 // One step launch of the classic variant covers all nsteps.  A general variant with stage buffers runs every step as three launches
 // on the same stream: poses + work items, narrowphase (a small kernel at 2-4x the step kernel's occupancy: its time is chains of
 // dependent loads along the hulls' edge graphs), then the step kernel, which appends the results instead of colliding.
-hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integrator, int nv, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel) {
+hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integrator, int nv, int fric, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel) {
   const size_t shmem = (size_t)lds_floats * sizeof(float);
-  if (variant == 0 || !P.stage.result) return launch_pass(StepPass::Main, M_dev, variant, solver, integrator, nv, shmem, P, nsteps, stream, kernel);
+  if (variant == 0 || !P.stage.result) return launch_pass(StepPass::Main, M_dev, variant, solver, integrator, nv, fric, shmem, P, nsteps, stream, kernel);
   for (int t = 0; t < nsteps; t++) {
     BatchPtrs Q = P;
     Q.t0 = P.t0 + t;
@@ -2353,11 +2447,11 @@ hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integ
     const bool fast = variant == 1 ? Q.stage.defer != nullptr : Q.stage.dm_fast != nullptr;
     const char* second = nullptr;  // (a staged step is named after its fast-pass kernel: the one that steps almost every env)
     if (fast) {
-      e = launch_pass(StepPass::Fast, M_dev, variant, solver, integrator, nv, shmem, Q, 1, stream, kernel);
+      e = launch_pass(StepPass::Fast, M_dev, variant, solver, integrator, nv, fric, shmem, Q, 1, stream, kernel);
       if (e != hipSuccess) return e;
       Q.stage.rerun = 1;
     }
-    e = launch_pass(StepPass::Main, M_dev, variant, solver, integrator, nv, shmem, Q, 1, stream, fast ? &second : kernel);
+    e = launch_pass(StepPass::Main, M_dev, variant, solver, integrator, nv, fric, shmem, Q, 1, stream, fast ? &second : kernel);
     if (e != hipSuccess) return e;
     // a long rollout is one call: refresh the heavy-first orders of its launches along the way (the caller does it between calls)
     if (P.order && P.order2 && (t & 7) == 7 && t + 1 < nsteps) {
@@ -2371,12 +2465,12 @@ hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integ
 
 // Inverse dynamics of every env in the launch (hb_inverse_dev): a general variant's poses and narrowphase first, as in a staged step,
 // then the inverse instantiation of the variant's row capacity
-hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int lds_floats, const BatchPtrs& P, hipStream_t stream, const char** kernel) {
+hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int fric, int lds_floats, const BatchPtrs& P, hipStream_t stream, const char** kernel) {
   if (variant != 0) {
     const hipError_t e = launch_pose_narrow(M_dev, P, stream);
     if (e != hipSuccess) return e;
   }
-  return launch_pass(StepPass::Inverse, M_dev, variant, /*solver=*/2, /*integrator=*/0, nv, (size_t)lds_floats * sizeof(float), P, 1, stream, kernel);
+  return launch_pass(StepPass::Inverse, M_dev, variant, /*solver=*/2, /*integrator=*/0, nv, fric, (size_t)lds_floats * sizeof(float), P, 1, stream, kernel);
 }
 // every step and inverse instantiation: a layout over 64 KB must launch whichever of them the dispatch picks
 hipError_t set_step_lds_limit(int bytes) {

@@ -369,6 +369,7 @@ bool add_joint(Ctx& c, const XmlNode& n, int body, const std::string& childclass
   double stiffness = 0, damping = 0, armature = 0, frictionloss = 0, margin = 0, ref = 0, springref = 0;
   int limited = 0;
   double solref[2] = {0.02, 1}, solimp[5] = {0.9, 0.95, 0.001, 0.5, 2};
+  double solref_fric[2] = {0.02, 1}, solimp_fric[5] = {0.9, 0.95, 0.001, 0.5, 2};
   if (type != JNT_FREE) {
     nr = a.vec("range", range, 2, 2);
     if (nr < 0) return false;
@@ -385,11 +386,13 @@ bool add_joint(Ctx& c, const XmlNode& n, int body, const std::string& childclass
     springref = a.num("springref", 0);
     if (ang) { ref *= PI / 180; springref *= PI / 180; }
     if (a.vec("solreflimit", solref, 2) < 0 || a.vec("solimplimit", solimp, 5) < 0) return false;
+    if (a.vec("solreffriction", solref_fric, 2) < 0 || a.vec("solimpfriction", solimp_fric, 5) < 0) return false;
   } else {
     // <joint type="free"> may still carry damping/armature; <freejoint> has none
-    if (!freejoint) { damping = a.num("damping", 0); armature = a.num("armature", 0); }
+    if (!freejoint) { damping = a.num("damping", 0); armature = a.num("armature", 0); frictionloss = a.num("frictionloss", 0); }
+    if (frictionloss != 0) return c.fail("mjcf: frictionloss on a free joint is not supported (hinge and slide joints only) in " + a.where);
   }
-  if (frictionloss != 0) return c.fail("mjcf: joint frictionloss is not supported in " + a.where);
+  if (frictionloss < 0) return c.fail("mjcf: negative joint frictionloss in " + a.where);
   m.jnt_limited.push_back(limited);
   m.jnt_range.push_back(range[0]); m.jnt_range.push_back(range[1]);
   m.jnt_stiffness.push_back(stiffness);
@@ -420,7 +423,9 @@ bool add_joint(Ctx& c, const XmlNode& n, int body, const std::string& childclass
     m.dof_parentid.push_back(parent_dof);
     m.dof_armature.push_back(armature);
     m.dof_damping.push_back(damping);
-    m.dof_frictionloss.push_back(0);
+    m.dof_frictionloss.push_back(frictionloss);
+    m.dof_solref_friction.push_back(solref_fric[0]); m.dof_solref_friction.push_back(solref_fric[1]);
+    for (int i = 0; i < 5; i++) m.dof_solimp_friction.push_back(solimp_fric[i]);
   }
   m.nq += nq;
   m.nv += nv;
@@ -750,8 +755,9 @@ bool read_tendons(Ctx& c, const XmlNode& n) {
     if (a.vec("solreflimit", sr, 2) < 0 || a.vec("solimplimit", si, 5) < 0) return false;
     m.tendon_solref_lim.push_back(sr[0]); m.tendon_solref_lim.push_back(sr[1]);
     for (int i = 0; i < 5; i++) m.tendon_solimp_lim.push_back(si[i]);
-    if (a.num("stiffness", 0) != 0 || a.num("damping", 0) != 0 || a.num("frictionloss", 0) != 0)
-      return c.fail("mjcf: tendon stiffness/damping/frictionloss are not supported");
+    if (a.num("frictionloss", 0) != 0) return c.fail("mjcf: tendon frictionloss is not supported (joint frictionloss is)");
+    if (a.num("stiffness", 0) != 0 || a.num("damping", 0) != 0)
+      return c.fail("mjcf: tendon stiffness/damping are not supported");
     m.tendon_invweight0.push_back(0);
     m.tendon_length0.push_back(0);
     m.ntendon++;

@@ -18,6 +18,7 @@ namespace {
 struct Writer {
   std::ostringstream os;
   char buf[64];
+  bool optional(bool present) { return present; }  // (an optional record is written only by a model that uses it)
   void operator()(const char* n, int& v) { os << "i " << n << " " << v << "\n"; }
   void operator()(const char* n, double& v) {
     snprintf(buf, sizeof buf, "%.17g", v);
@@ -57,6 +58,7 @@ struct Record {
 struct Reader {
   std::map<std::string, Record>* recs;
   std::string err;
+  bool optional(bool) { return true; }
   Record* find(const char* n, char kind) {
     auto it = recs->find(n);
     if (it == recs->end()) return nullptr;  // missing field keeps its default
@@ -129,6 +131,7 @@ bool load_hbm_string(const std::string& text, Model& m, std::string& err) {
   rd.recs = &recs;
   m.visit(rd);
   if (!rd.err.empty()) { err = rd.err; return false; }
+  m.fill_friction_defaults();
   return validate_model(m, err);
 }
 
@@ -176,6 +179,10 @@ bool validate_model(const Model& m, std::string& err) {
   };
   for (auto& l : lens)
     if (l.have != l.want) return bad(std::string("array ") + l.name + " has " + std::to_string(l.have) + " entries, its size field says " + std::to_string(l.want));
+  // (the optional friction-loss records: absent, or one solref / solimp per dof)
+  if (!m.dof_solref_friction.empty() && m.dof_solref_friction.size() != (size_t)2 * m.nv) return bad("array dof_solref_friction has " + std::to_string(m.dof_solref_friction.size()) + " entries, its size field says " + std::to_string(2 * m.nv));
+  if (!m.dof_solimp_friction.empty() && m.dof_solimp_friction.size() != (size_t)5 * m.nv) return bad("array dof_solimp_friction has " + std::to_string(m.dof_solimp_friction.size()) + " entries, its size field says " + std::to_string(5 * m.nv));
+  for (double v : m.dof_frictionloss) if (!(v >= 0)) return bad("negative dof_frictionloss");
   auto in = [](int v, int lo, int hi) { return v >= lo && v < hi; };  // lo <= v < hi
   int nq = 0, nv = 0;
   for (int j = 0; j < m.njnt; j++) {

@@ -216,9 +216,9 @@ def lib():
     return L
 
 
-def _check(rc, what):
+def _check(rc, what, why=None):
     if rc != HB_OK:
-        raise HbError("%s failed with code %d" % (what, rc))
+        raise HbError("%s failed with code %d%s" % (what, rc, ": " + why if why else ""))
 
 
 def _ptr(a):
@@ -537,9 +537,16 @@ class Batch:
         return a.value, b.value
 
     # ---- body accelerations (mj_objectAcceleration of every body, gravity pseudo-acceleration included; include/hb.h)
+    def _friction_loss_why(self, rc):
+        """HB_EUNSUPPORTED (-4) from a body-acceleration read-out on a model with joint frictionloss: say so (include/hb.h)"""
+        if rc == -4 and self.model.array("dof_frictionloss").any():
+            return "a model with joint friction loss has no body-acceleration read-out (accelerometer, gyro and frame-acceleration sensors included)"
+        return None
+
     def body_acc_readout(self, on=True):
         """From the next launch on, steps write every body's acceleration (full step kernels only)."""
-        _check(lib().hb_body_acc_readout(self._h, int(on)), "hb_body_acc_readout")
+        rc = lib().hb_body_acc_readout(self._h, int(on))
+        _check(rc, "hb_body_acc_readout", self._friction_loss_why(rc))
 
     def body_acc(self):
         """[n_env, nbody, 6]: angular | linear acceleration of the body's xipos, world axes (row 0, the world: (0, -gravity))."""
@@ -734,7 +741,8 @@ class Batch:
             raise HbError("hb_sensor_size: invalid sensor spec")
         out = np.zeros((self.n_env, ns), dtype=np.float32)
         c = None if ctrl is None else np.ascontiguousarray(ctrl, dtype=np.float32)
-        _check(lib().hb_sensors(self._h, _ptr(c), ctypes.byref(spec), _ptr(out)), "hb_sensors")
+        rc = lib().hb_sensors(self._h, _ptr(c), ctypes.byref(spec), _ptr(out))
+        _check(rc, "hb_sensors", self._friction_loss_why(rc) if spec.n_imu + spec.n_frameacc else None)
         return out
 
     # ---- env adapter (CPUEnv.step/reset analogue)
