@@ -1,5 +1,5 @@
 // hb_api.cpp — the C-ABI of libhb.so (include/hb.h): model handles, device model tables,
-// batches of environments on one GPU, and the launch plumbing around the kernel translation units (hb_step.hip, hb_narrow.hip, hb_env.hip).
+// batches of environments on one GPU, and the launch plumbing around the kernel translation units (hb_step.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip).
 //
 // Host C++ only; no PyTorch.  One hb_batch owns one HIP stream and all device memory of its
 // envs; the model is immutable and shareable (reference ownership rules: SURVEY.md §8b).
@@ -709,6 +709,7 @@ struct hb_batch {
   DevBuf<float> d_prev, d_latest, d_qfrc, d_action;
   DevBuf<float> d_inv;  // hb_inverse's device copies: qacc [n_env][nv] | qfrc_inverse [n_env][nv] | warnings [n_env] (allocated by its first call)
   DevBuf<int> d_inv_scratch;  // hb_inverse_dev: the counts [n_env][kCountStride] | status [n_env] its launches write instead of the batch's
+  DevBuf<float> d_kin;     // hb_kinematics / hb_kinematics_states: device copies of their host arrays (outputs | qpos | qvel), grown on demand
   DevBuf<int> d_episode;
   int env_offset = 0;
   // realism layer (hb_env_randomize)
@@ -738,7 +739,7 @@ struct hb_batch {
   long long launch_count = 0;
   const char* last_kernel = "";  // hb_last_kernel
   // run-time choices between kernels / schedules that give the same results (hb_batch_tune, include/hb.h: HB_TUNE_*), indexed by knob
-  int tune[HB_TUNE_COUNT] = {getenv("HB_DUO") ? atoi(getenv("HB_DUO")) : 1, 1, 1, 1, 1, 1, 1, 4, 1, kFoldMax};
+  int tune[HB_TUNE_COUNT] = {getenv("HB_DUO") ? atoi(getenv("HB_DUO")) : 1, 1, 1, 1, 1, 1, 1, 4, 1, kFoldMax, 1};
   // hb_step_dev calls not launched yet (fold_steps): the launch parameters they share, and the controls of each
   BatchPtrs fold_P;
   const float* fold_ctrl[kFoldMax] = {};
@@ -1400,6 +1401,66 @@ int hb_inverse(hb_batch* b, const float* qacc, int flags, float* qfrc_inverse, i
   if (warnings) HB_HIP(hipMemcpyAsync(warnings, d_warn, (size_t)b->n_env * sizeof(int), hipMemcpyDeviceToHost, main_stream(b)));
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   return HB_OK;
+}
+
+// ---- whole-body kinematics read-out (hb_kin.hip) -----------------------------------------------------------------
+namespace {
+int kinematics_launch(hb_batch* b, const float* qpos, const float* qvel, int qpos_stride, int qvel_stride, long long n, float* body_pose, float* body_vel,
+                      float* geom_pose, hipStream_t stream) {
+  KinArgs A;
+  A.qpos = qpos; A.qvel = qvel; A.qpos_stride = qpos_stride; A.qvel_stride = qvel_stride; A.n = n;
+  A.body_pose = body_pose; A.body_vel = body_vel; A.geom_pose = geom_pose;
+  HB_HIP(launch_kinematics(b->D.d_dm, b->D.dm, A, b->tune[HB_TUNE_KIN_PACK], stream, &b->last_kernel));
+  return HB_OK;
+}
+// host form: the outputs asked for (and qpos / qvel when given) staged in d_kin, one launch, copied back
+int kinematics_host(hb_batch* b, const float* qpos, const float* qvel, long long n, float* body_pose, float* body_vel, float* geom_pose) {
+  const DevModel& dm = b->D.dm;
+  const size_t np = body_pose ? (size_t)n * dm.nbody * 10 : 0, nvel = body_vel ? (size_t)n * dm.nbody * 6 : 0, ng = geom_pose ? (size_t)n * dm.ngeom * 7 : 0;
+  const size_t nqp = qpos ? (size_t)n * dm.nq : 0, nqv = qpos && qvel ? (size_t)n * dm.nv : 0;
+  const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined; d_kin is idle: the host form before this one ended synchronised)
+  if (b->d_kin.reserve(np + nvel + ng + nqp + nqv + 1) != HB_OK) return HB_ENOMEM;
+  float* d_pose = b->d_kin;
+  float* d_vel = d_pose + np;
+  float* d_geom = d_vel + nvel;
+  float* d_qpos = d_geom + ng;
+  float* d_qvel = d_qpos + nqp;
+  if (nqp) HB_HIP(hipMemcpyAsync(d_qpos, qpos, nqp * sizeof(float), hipMemcpyHostToDevice, stream));
+  if (nqv) HB_HIP(hipMemcpyAsync(d_qvel, qvel, nqv * sizeof(float), hipMemcpyHostToDevice, stream));
+  int rc;
+  if (qpos) rc = kinematics_launch(b, d_qpos, nqv ? d_qvel : nullptr, dm.nq, dm.nv, n, np ? d_pose : nullptr, nvel ? d_vel : nullptr, ng ? d_geom : nullptr, stream);
+  else rc = kinematics_launch(b, b->d_state + 1, b->d_state + 1 + dm.nq, dm.nstate, dm.nstate, n, np ? d_pose : nullptr, nvel ? d_vel : nullptr, ng ? d_geom : nullptr, stream);
+  if (rc != HB_OK) return rc;
+  if (np) HB_HIP(hipMemcpyAsync(body_pose, d_pose, np * sizeof(float), hipMemcpyDeviceToHost, stream));
+  if (nvel) HB_HIP(hipMemcpyAsync(body_vel, d_vel, nvel * sizeof(float), hipMemcpyDeviceToHost, stream));
+  if (ng) HB_HIP(hipMemcpyAsync(geom_pose, d_geom, ng * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HB_HIP(hipStreamSynchronize(stream));
+  return HB_OK;
+}
+}  // namespace
+
+int hb_kinematics_dev(hb_batch* b, float* body_pose_dev, float* body_vel_dev, float* geom_pose_dev) {
+  if (!b || (!body_pose_dev && !body_vel_dev && !geom_pose_dev)) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined: the read-out sees the state they leave)
+  const DevModel& dm = b->D.dm;
+  return kinematics_launch(b, b->d_state + 1, b->d_state + 1 + dm.nq, dm.nstate, dm.nstate, b->n_env, body_pose_dev, body_vel_dev, geom_pose_dev, stream);
+}
+int hb_kinematics(hb_batch* b, float* body_pose, float* body_vel, float* geom_pose) {
+  if (!b || (!body_pose && !body_vel && !geom_pose)) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  return kinematics_host(b, nullptr, nullptr, b->n_env, body_pose, body_vel, geom_pose);
+}
+int hb_kinematics_states_dev(hb_batch* b, const float* qpos_dev, const float* qvel_dev, int n, float* body_pose_dev, float* body_vel_dev, float* geom_pose_dev) {
+  if (!b || !qpos_dev || n <= 0 || (!body_pose_dev && !body_vel_dev && !geom_pose_dev) || (body_vel_dev && !qvel_dev)) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  const hipStream_t stream = main_stream(b);
+  return kinematics_launch(b, qpos_dev, qvel_dev, b->D.dm.nq, b->D.dm.nv, n, body_pose_dev, body_vel_dev, geom_pose_dev, stream);
+}
+int hb_kinematics_states(hb_batch* b, const float* qpos, const float* qvel, int n, float* body_pose, float* body_vel, float* geom_pose) {
+  if (!b || !qpos || n <= 0 || (!body_pose && !body_vel && !geom_pose) || (body_vel && !qvel)) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  return kinematics_host(b, qpos, body_vel ? qvel : nullptr, n, body_pose, body_vel, geom_pose);
 }
 
 int hb_rollout_dev(hb_batch* b, const float* ctrl_dev, int T, float* qpos_out_dev) {
@@ -2627,6 +2688,7 @@ int hb_batch_tune(hb_batch* b, int knob, int value) {
   if (!b || knob < 0 || knob >= HB_TUNE_COUNT || value < 0) return HB_EINVAL;
   if (knob == HB_TUNE_DUO && value > 2) return HB_EINVAL;
   if (knob == HB_TUNE_FOLD && (value < 1 || value > kFoldMax)) return HB_EINVAL;
+  if (knob == HB_TUNE_KIN_PACK && value > 1) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
   (void)main_stream(b);  // the choice holds from the next launch on: whatever is in flight on the segments' streams is joined first
   b->tune[knob] = value;

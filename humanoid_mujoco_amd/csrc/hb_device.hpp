@@ -1,5 +1,5 @@
 // hb_device.hpp — device-side model tables and batch buffers (fp32), shared by the host
-// runtime (hb_api.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip).
+// runtime (hb_api.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip).
 //
 // The model is replicated read-only per device as two flat arrays (int, float); DevModel holds
 // typed pointers into them plus the per-env LDS layout.  All tables are small (a few KB) and
@@ -392,6 +392,17 @@ struct BatchPtrs {
   int sensor_nfacc, sensor_facc_body[4];
   int sensor_acc_off;  // where these entries begin in a sensor row (floats)
   int sensor_behind;   // floats of a sensor row written behind the solver: the contact-force read-out's entries and these
+};
+// arguments of the kinematics read-out (hb_kin.hip; hb_kinematics*): n states, state k's qpos at qpos + k qpos_stride (the batch's state
+// records, or packed rows), qvel likewise (read only when body_vel is asked for); the outputs are nullable, layouts in include/hb.h
+struct KinArgs {
+  const float* qpos;
+  const float* qvel;
+  int qpos_stride, qvel_stride;
+  long long n;
+  float* body_pose;  // [n][nbody][10]
+  float* body_vel;   // [n][nbody][6]
+  float* geom_pose;  // [n][ngeom][7]
 };
 constexpr int kAccPark = 24;  // floats per body in BatchPtrs::body_acc_park (six 16-byte moves)
 

@@ -1,4 +1,4 @@
-// hb_launch.hpp — host-callable launchers implemented in the kernel translation units (hb_step.hip, hb_narrow.hip, hb_env.hip)
+// hb_launch.hpp — host-callable launchers implemented in the kernel translation units (hb_step.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "hb_device.hpp"
@@ -8,6 +8,8 @@ namespace hb {
 hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integrator, int nv, int fric, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel);
 // inverse dynamics of the launch's envs (hb_inverse_dev; hb_step.hip)
 hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int fric, int lds_floats, const BatchPtrs& P, hipStream_t stream, const char** kernel);
+// whole-body kinematics of A.n states (hb_kin.hip): pack = 0 one state per wave, 1 as many as fit (HB_TUNE_KIN_PACK); M: the host's copy of *M_dev
+hipError_t launch_kinematics(const DevModel* M_dev, const DevModel& M, const KinArgs& A, int pack, hipStream_t stream, const char** kernel);
 // two envs per wave: a lean launch of the 27-dof humanoid's PGS kernel (hb_step_duo.hip; chosen by launch_step)
 hipError_t launch_step_duo(const DevModel* M_dev, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel);
 bool fold_pays(int variant, int solver, int integrator, int nv, int fric, const BatchPtrs& P);

@@ -148,6 +148,8 @@ def lib():
     L.hb_forward.argtypes = [vp, vp]
     L.hb_inverse.argtypes = [vp, vp, ci, vp, vp]
     L.hb_inverse_dev.argtypes = [vp, vp, ci, vp, vp]
+    L.hb_kinematics.argtypes = [vp, vp, vp, vp]; L.hb_kinematics_dev.argtypes = [vp, vp, vp, vp]
+    L.hb_kinematics_states.argtypes = [vp, vp, vp, ci, vp, vp, vp]; L.hb_kinematics_states_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp]
     L.hb_state_size.argtypes = [vp, cu]
     L.hb_get_state.argtypes = [vp, cu, vp]; L.hb_set_state.argtypes = [vp, cu, vp]
     L.hb_get_state_f64.argtypes = [vp, cu, vp]; L.hb_set_state_f64.argtypes = [vp, cu, vp]
@@ -214,6 +216,18 @@ def lib():
     L.hb_step_timing.argtypes = [vp, ci]; L.hb_step_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
     _lib = L
     return L
+
+
+def quat_to_mat(q):
+    """rotation matrices [..., 3, 3] of unit quaternions [..., 4] (w x y z): xmat / geom_xmat of the quaternions Batch.kinematics returns
+    (mju_quat2Mat)"""
+    q = np.asarray(q)
+    w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    m = np.empty(q.shape[:-1] + (3, 3), dtype=q.dtype)
+    m[..., 0, 0] = w * w + x * x - y * y - z * z; m[..., 0, 1] = 2 * (x * y - w * z); m[..., 0, 2] = 2 * (x * z + w * y)
+    m[..., 1, 0] = 2 * (x * y + w * z); m[..., 1, 1] = w * w - x * x + y * y - z * z; m[..., 1, 2] = 2 * (y * z - w * x)
+    m[..., 2, 0] = 2 * (x * z - w * y); m[..., 2, 1] = 2 * (y * z + w * x); m[..., 2, 2] = w * w - x * x - y * y + z * z
+    return m
 
 
 def _check(rc, what, why=None):
@@ -402,6 +416,45 @@ class Batch:
         _check(lib().hb_inverse_dev(self._h, ctypes.c_void_p(qacc_ptr), HB_INV_DISCRETE if discrete else 0, ctypes.c_void_p(out_ptr),
                                     ctypes.c_void_p(warnings_ptr) if warnings_ptr else None), "hb_inverse_dev")
 
+    def _kin_out(self, lead, pose, vel, geoms):
+        m = self.model
+        return (np.empty(lead + (m.nbody, 10), dtype=np.float32) if pose else None, np.empty(lead + (m.nbody, 6), dtype=np.float32) if vel else None,
+                np.empty(lead + (m.ngeom, 7), dtype=np.float32) if geoms else None)
+
+    def kinematics(self, pose=True, vel=True, geoms=False):
+        """mj_kinematics + mj_objectVelocity of every env at its state as it is now (include/hb.h: hb_kinematics): a dict of float32
+        arrays, "pose" [n_env, nbody, 10] = xpos | xquat (w x y z) | xipos, "vel" [n_env, nbody, 6] = omega | velocity of the body's
+        xipos (world axes), "geoms" [n_env, ngeom, 7] = geom_xpos | quaternion - those asked for.  The batch is left as it is."""
+        p, v, g = self._kin_out((self.n_env,), pose, vel, geoms)
+        _check(lib().hb_kinematics(self._h, _ptr(p), _ptr(v), _ptr(g)), "hb_kinematics")
+        return {k: a for k, a in (("pose", p), ("vel", v), ("geoms", g)) if a is not None}
+
+    def kinematics_dev(self, pose_ptr=None, vel_ptr=None, geom_ptr=None):
+        """the same into device arrays (addresses as int, None: not wanted); asynchronous (hb_kinematics_dev)"""
+        _check(lib().hb_kinematics_dev(self._h, ctypes.c_void_p(pose_ptr or 0), ctypes.c_void_p(vel_ptr or 0), ctypes.c_void_p(geom_ptr or 0)), "hb_kinematics_dev")
+
+    def kinematics_states(self, qpos, qvel=None, pose=True, vel=True, geoms=False):
+        """the same of given states (hb_kinematics_states): qpos [n, nq] or [T, n_env, nq] (e.g. rollout_trajectory's), qvel likewise
+        (may be None with vel=False); any n.  The arrays of the returned dict have qpos' leading shape."""
+        q = np.ascontiguousarray(qpos, dtype=np.float32)
+        assert q.ndim >= 2 and q.shape[-1] == self.model.nq, q.shape
+        lead = q.shape[:-1]
+        n = int(np.prod(lead))
+        assert n < 2 ** 31, "hb_kinematics_states takes the number of states as an int: %d states, split the call" % n
+        qv = None
+        if qvel is not None:
+            qv = np.ascontiguousarray(qvel, dtype=np.float32)
+            assert qv.shape == lead + (self.model.nv,), qv.shape
+        p, v, g = self._kin_out(lead, pose, vel, geoms)
+        _check(lib().hb_kinematics_states(self._h, _ptr(q), _ptr(qv), n, _ptr(p), _ptr(v), _ptr(g)), "hb_kinematics_states")
+        return {k: a for k, a in (("pose", p), ("vel", v), ("geoms", g)) if a is not None}
+
+    def kinematics_states_dev(self, qpos_ptr, qvel_ptr, n, pose_ptr=None, vel_ptr=None, geom_ptr=None):
+        """device arrays: qpos [n, nq], qvel [n, nv] (None without vel_ptr) in, the outputs asked for out; asynchronous"""
+        assert int(n) < 2 ** 31, n
+        _check(lib().hb_kinematics_states_dev(self._h, ctypes.c_void_p(qpos_ptr or 0), ctypes.c_void_p(qvel_ptr or 0), int(n), ctypes.c_void_p(pose_ptr or 0),
+                                              ctypes.c_void_p(vel_ptr or 0), ctypes.c_void_p(geom_ptr or 0)), "hb_kinematics_states_dev")
+
     def rollout(self, ctrl, want_qpos=False):
         c = np.ascontiguousarray(ctrl, dtype=np.float32)
         T = c.shape[0]
@@ -463,7 +516,8 @@ class Batch:
         _check(lib().hb_get_counts(self._h, _ptr(a), _ptr(b), _ptr(c)), "hb_get_counts")
         return a, b, c
 
-    TUNE = {"duo": 0, "lean": 1, "sized": 2, "staged": 3, "fastpass": 4, "narrow_prim": 5, "schedule": 6, "reorder_period": 7, "policy_lean": 8, "fold": 9}
+    TUNE = {"duo": 0, "lean": 1, "sized": 2, "staged": 3, "fastpass": 4, "narrow_prim": 5, "schedule": 6, "reorder_period": 7, "policy_lean": 8, "fold": 9,
+            "kin_pack": 10}
 
     def tune(self, **knobs):
         """run-time choices between kernels / schedules that give the same results (include/hb.h: hb_batch_tune, HB_TUNE_*), e.g.

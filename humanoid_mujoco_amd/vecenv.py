@@ -222,6 +222,19 @@ class VecEnv:
             raise RuntimeError("body_accelerations: create the VecEnv with body_accelerations=True")
         return self.batch.body_acc()
 
+    def body_poses(self):
+        """[n_envs, nbody, 10]: xpos | xquat (w x y z) | xipos of every body at the envs' current states - the states the last returned
+        observations describe (Batch.kinematics; computed on demand from qpos)"""
+        return self.batch.kinematics(pose=True, vel=False)["pose"]
+
+    def body_velocities(self):
+        """[n_envs, nbody, 6]: angular velocity | velocity of every body's xipos, world axes, at the envs' current states"""
+        return self.batch.kinematics(pose=False, vel=True)["vel"]
+
+    def geom_poses(self):
+        """[n_envs, ngeom, 7]: geom_xpos | orientation quaternion (w x y z) of every geom at the envs' current states"""
+        return self.batch.kinematics(pose=False, vel=False, geoms=True)["geoms"]
+
     def warning_counts(self):
         """Number of envs currently carrying each warning bit."""
         w = self.batch.status()

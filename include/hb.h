@@ -206,6 +206,33 @@ int hb_forward(hb_batch* b, const float* ctrl);
 int hb_inverse(hb_batch* b, const float* qacc, int flags, float* qfrc_inverse, int* warnings);
 int hb_inverse_dev(hb_batch* b, const float* qacc_dev, int flags, float* qfrc_inverse_dev, int* warnings_dev);
 
+/* ---- whole-body kinematics read-out ---------------------------------------------------------------------------- */
+
+/* Replaces a direct mj_kinematics + mj_comVel call and the mjData fields it fills (mjData.xpos, xquat, xipos, geom_xpos, geom_xmat),
+ * and mj_objectVelocity(objtype body, flg_local = 0) of every body: the poses and velocities of all bodies and the poses of all geoms,
+ * as a pure function of (qpos, qvel) and the model.
+ *   body_pose [n][nbody][10] = xpos[3] | xquat[4] (w x y z) | xipos[3]
+ *   body_vel  [n][nbody][6]  = omega[3] | v[3]: angular velocity and the velocity of the body's own xipos, world axes - the point and
+ *                              axes hb_get_body_acc, hb_get_body_contact and the framelinvel sensor entries refer to
+ *   geom_pose [n][ngeom][7]  = geom_xpos[3] | quaternion[4] (w x y z) of the geom's world orientation (geom_xmat is its matrix)
+ * Row 0 of the body arrays is the world: zero position and velocity, identity quaternion.  Each output may be NULL, not all three.
+ * hb_kinematics / hb_kinematics_dev evaluate the batch's qpos / qvel AS THEY ARE NOW (n = n_env): what mj_kinematics + mj_comVel would
+ * give if called now.  After a step that is the NEW state, the one the returned observation describes - the mjData.xpos that mj_step
+ * leaves behind belongs to the state before the step and is one step stale.  Step calls held back (hb_step_dev) are launched first and
+ * the pipes joined, as for hb_inverse.  hb_kinematics_states / _states_dev evaluate n >= 1 given states, qpos [n][nq] and qvel [n][nv]
+ * row-major (e.g. the [T][n_env] tapes of hb_rollout_trajectory with n = T * n_env): n is not tied to n_env, qvel may be NULL when
+ * body_vel is NULL, and the batch is used for its model, device and stream only.
+ * The calls read and compute: state, status and warning words, counts, warm start and orders of the batch stay as they are, and a free
+ * joint's quaternion is normalised for the computation only, not written back.  A non-finite or huge input makes the rows of that state
+ * unspecified and nothing else.  No model is refused, whatever kernels it steps in: the read-out is a kernel of its own
+ * (csrc/hb_kin.hip), hb_last_kernel names it ("hb_kin16_kernel" / "hb_kin32_kernel" / "hb_kin64_kernel": HB_TUNE_KIN_PACK), and
+ * hb_batch_step_launches does not count it.  HB_EINVAL: NULL batch, all outputs NULL, n <= 0, NULL qpos, body_vel without qvel.
+ * The host forms are synchronous; the _dev forms take device arrays and are asynchronous like hb_inverse_dev. */
+int hb_kinematics(hb_batch* b, float* body_pose, float* body_vel, float* geom_pose);
+int hb_kinematics_dev(hb_batch* b, float* body_pose_dev, float* body_vel_dev, float* geom_pose_dev);
+int hb_kinematics_states(hb_batch* b, const float* qpos, const float* qvel, int n, float* body_pose, float* body_vel, float* geom_pose);
+int hb_kinematics_states_dev(hb_batch* b, const float* qpos_dev, const float* qvel_dev, int n, float* body_pose_dev, float* body_vel_dev, float* geom_pose_dev);
+
 /* ---- wire format of a state ------------------------------------------------------------ */
 
 /* One env's state as the `State` message of the reference's gRPC agent service (mujoco_mpc/mjpc/grpc/agent.proto:75-83:
@@ -412,8 +439,8 @@ long long hb_batch_step_launches(hb_batch* b);
  * itself (the reference's testspeed.cc prints its thread count: sample/testspeed.cc:203-210). */
 int hb_batch_device_name(const hb_batch* b, char* out, int cap);
 /* Run-time choices between kernels and schedules: for the tests that compare them and for measurements.  Takes effect from the next
- * launch on.  Nothing of the reference corresponds: mj_step (mujoco.h:120) has one code path.  DUO, LEAN, SIZED, NARROW_PRIM, SCHEDULE
- * and FOLD give the SAME results: a test holds each bit-identical to its alternative (tests/test_gpu_kernel_matrix.py, test_gpu_duo.py,
+ * launch on.  Nothing of the reference corresponds: mj_step (mujoco.h:120) has one code path.  DUO, LEAN, SIZED, NARROW_PRIM, SCHEDULE,
+ * FOLD and KIN_PACK give the SAME results: a test holds each bit-identical to its alternative (tests/test_gpu_kernel_matrix.py, test_gpu_duo.py,
  * test_gpu_fold.py).  STAGED, FASTPASS and POLICY_LEAN choose kernels that sum in other orders (one register group against two or four,
  * the policy kernel's own arithmetic): their results differ by rounding, and tests hold them to the fp64 oracle or to each other within
  * bounds instead (tests/test_gpu_kernel_matrix.py, test_gpu_staged.py, test_gpu_policy.py).
@@ -434,11 +461,13 @@ int hb_batch_device_name(const hb_batch* b, char* out, int cap);
  *                          pipelined; 0 never; 2 always
  *   HB_TUNE_FOLD           hb_step_dev calls enqueued back to back run as ONE launch of up to this many steps (default and maximum 256; 1:
  *                          every call its own launch).  See hb_step_dev.
+ *   HB_TUNE_KIN_PACK       hb_kinematics*: 1 (default) as many states per wavefront as fit (16 or 32 lanes per state for models of up to 16 /
+ *                          32 moving bodies); 0: one state per wavefront.  The same bits (tests/test_gpu_kinematics.py)
  * Environment variables the library reads (all others of earlier rounds are gone): HB_DEBUG (name failing HIP calls on stderr), HB_DUO
  * (HB_TUNE_DUO's value for new batches), HB_BOX_CULL=0 (model tables without the oriented-box cull of portal-search pairs: a test),
  * and in the diagnostic build (-DHB_STAMPS) HB_STOP_PHASE and HB_MPR_LIMIT (tools/gpu_narrow_limits.sh). */
 enum { HB_TUNE_DUO = 0, HB_TUNE_LEAN, HB_TUNE_SIZED, HB_TUNE_STAGED, HB_TUNE_FASTPASS, HB_TUNE_NARROW_PRIM, HB_TUNE_SCHEDULE, HB_TUNE_REORDER_PERIOD,
-       HB_TUNE_POLICY_LEAN, HB_TUNE_FOLD, HB_TUNE_COUNT };
+       HB_TUNE_POLICY_LEAN, HB_TUNE_FOLD, HB_TUNE_KIN_PACK, HB_TUNE_COUNT };
 int hb_batch_tune(hb_batch* b, int knob, int value);
 /* Narrowphase work of the last step of each env, for models that collide through mesh hulls or height fields (the staged step:
  * DESIGN.md 3.6): nwork = work items (a candidate pair that passed the broadphase, or one prism of a height-field pair's sub-grid),
