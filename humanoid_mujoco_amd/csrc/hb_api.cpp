@@ -13,6 +13,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace hb;
@@ -250,64 +251,28 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
     for (int j = i; j >= 0; j = m.dof_parentid[j]) { Mi[adr] = i; Mj[adr] = j; adr++; }
   }
   if (m.nM > 1023) { err = "sparse mass matrix too large for the packed index tables"; return false; }
-  // ---- LDS layout (a function of the variant: a variant-2 model also gets the variant-1 layout for its fast step kernel)
-  auto lay = [&](DevModel& dm) -> bool {
-  int off = 0;
-  auto take = [&](int n) { int o = off; off += (n + 3) & ~3; return o; };
-  // row stride of C: 33 (K = 32 for the matrix cores plus a pad column); the big Newton layout stores J rows only as wide as its dense
-  // order (NDENSE + 1: 21 for the reference's 18-dof robot, else 29): 256 rows of 33 floats would be 34 KB per env
-  // (variant 1 with the Newton solver is the fast layout of a variant-2 model: its one-group Newton kernel reads J rows like the big one)
-  dm.cstride = (dm.variant == 2 || (dm.variant == 1 && dm.solver == 2)) ? (nv <= 20 ? 21 : 29) : 33;
-  dm.o_gquat = dm.variant ? take(4 * m.ngeom) : 0;
-  dm.o_qpos = take(m.nq); dm.o_qvel = take(nv); dm.o_warm = take(nv); dm.o_ctrl = take(std::max(1, m.nu));
-  dm.o_gpos = take(3 * m.ngeom); dm.o_gaxis = take(3 * m.ngeom); dm.o_scom = take(3 * std::max(1, dm.ntree)); dm.o_cdof = take(12 * nv);  /* angular[3], -, linear[3], -, pad[4] per dof (kCdofStride: conflict-free b128 reads) */
-  dm.o_qLD = take(2 * m.nM + 4); dm.o_smooth = take(nv);  // qLD: {M, H} pairs + the zero and one pad pairs of the dense views
-  dm.o_vec0 = take(32); dm.o_vec1 = take(32); dm.o_vec2 = take(32);  /* read 32 wide */ dm.o_tenlen = take(std::max(1, m.ntendon));
-  int region = off;
-  dm.o_xpos = take(12 * nb);  /* xpos[3], -, xquat[4], pad[4] records (kXpqStride) */ dm.o_xmat = take(9 * nb); dm.o_xipos = take(3 * nb);
-  dm.o_xanchor = take(3 * m.njnt); dm.o_xaxis = take(3 * m.njnt); dm.o_cinert = take(10 * nb); dm.o_crb = take(20 * nb);  // crb: inertia[10] | cfrc[6] | pad[4] records (kIfStride)
-  dm.o_cvel = take(12 * nb);  // cvel[6] | cacc[6] records
-  int endA = off;
-  off = region;
-  dm.o_meta = 0;
-  dm.o_AR = 0;
-  if (dm.variant == 2) {
-    // Newton on kBigNefcMax rows: contacts, J rows, the dense M ([32][33], where the classic layout keeps the row meta), the
-    // compact row meta, one D / force word per row
-    dm.o_con = take(dm.ncon_max * kConStride);
-    dm.o_C = take(std::max(dm.nefc_max * dm.cstride + 64, kListMax * 5 + kWorkMax));  // (the collision pass borrows the head of C for its lists)
-    dm.o_efc = take(32 * 36);
-    dm.o_meta = take(dm.nefc_max * kMetaStride);
-  } else if (dm.variant == 3) {
-    // PGS on kPgsNefcMax rows: contacts, J / C rows (+ the qfrc_smooth row), W, the compact row meta, the matrix AR
-    dm.o_con = take(dm.ncon_max * kConStride);
-    dm.o_C = take(std::max((dm.nefc_max + 1) * dm.cstride + 64, kListMax * 5 + kWorkMax));
-    dm.o_efc = take(32 * 36);
-    dm.o_meta = take(dm.nefc_max * kMetaStride);
-    dm.o_AR = take(dm.nefc_max * dm.nefc_max);
-  } else {
-  dm.o_con = take(kNconMax * kConStride); dm.o_C = take((kNefcMax + 1) * dm.cstride);
-  // per-row meta (13 slots x kNefcMax) is dead once the row quantities are in registers; W = L^-1 D^-1/2
-  // ([32][33]) is built over it before the J W product and lives until the dual finish
-  dm.o_efc = take(std::max(13 * kNefcMax, 32 * 36));
-  // mj_Euler builds W_H and its transpose (2 x [32][36]) from the start of C, running on into the row-meta area
-  if (dm.o_efc != dm.o_C + (((kNefcMax + 1) * dm.cstride + 3) & ~3) || dm.o_efc + std::max(13 * kNefcMax, 32 * 36) - dm.o_C < 2 * 32 * 36) {
-    err = "internal: LDS layout leaves no room for the Euler solve's W_H pair"; return false;
-  }
-  if (dm.variant == 1) dm.o_meta = take(64 * kMetaStride);
-  }
-  dm.o_force = take(std::max(kGroup, dm.nefc_max));
-  int endB = off;
-  // xipos and scom/cdof are read while region B is being written (xfrc, Jacobians): keep xipos out of the alias
-  dm.lds_floats = std::max(endA, endB);
-  // RK4: the stage block (start state and the two running sums) behind both regions, so that an RK4 model's layout is the Euler layout
-  // plus a tail and no offset moves
-  dm.o_rk = 0;
-  if (dm.integrator == INT_RK4) { off = dm.lds_floats; dm.o_rk = take(m.nq + 3 * nv); dm.lds_floats = off; }
-  if (dm.lds_floats * 4 > 160 * 1024) { err = "model needs more LDS than one CU has"; return false; }
-  return true;
+  // ---- LDS layout (hb_device.hpp: lds_layout - a function of the variant: a variant-2 / -3 model also gets the variant-1 layout for its fast
+  // step kernel).  The one place a layout goes into a DevModel; hands the layout back for the comparison with the size-specialised kernels'
+  auto lay = [&](DevModel& dm, LdsLayout& L) -> bool {
+    L = lds_layout(m.nq, nv, m.nu, nb, m.njnt, m.ngeom, m.ntendon, m.nM, dm.ntree, dm.variant, dm.solver, dm.integrator, dm.ncon_max, dm.nefc_max);
+    if (L.fail == kLdsNoEulerRoom) { err = "internal: LDS layout leaves no room for the Euler solve's W_H pair"; return false; }
+    if (L.fail == kLdsTooLarge) { err = "model needs more LDS than one CU has"; return false; }
+    dm.o_gquat = L.o_gquat; dm.o_meta = L.o_meta; dm.o_AR = L.o_AR;
+    dm.o_qpos = L.o_qpos; dm.o_qvel = L.o_qvel; dm.o_warm = L.o_warm; dm.o_ctrl = L.o_ctrl; dm.o_gpos = L.o_gpos; dm.o_gaxis = L.o_gaxis; dm.o_scom = L.o_scom;
+    dm.o_cdof = L.o_cdof; dm.o_qLD = L.o_qLD; dm.o_smooth = L.o_smooth; dm.o_vec0 = L.o_vec0; dm.o_vec1 = L.o_vec1; dm.o_vec2 = L.o_vec2; dm.o_tenlen = L.o_tenlen;
+    dm.o_xpos = L.o_xpos; dm.o_xmat = L.o_xmat; dm.o_xipos = L.o_xipos; dm.o_xanchor = L.o_xanchor; dm.o_xaxis = L.o_xaxis; dm.o_cinert = L.o_cinert; dm.o_crb = L.o_crb;
+    dm.o_cvel = L.o_cvel; dm.o_con = L.o_con; dm.o_C = L.o_C; dm.o_efc = L.o_efc; dm.o_force = L.o_force;
+    dm.lds_floats = L.lds_floats; dm.cstride = L.cstride; dm.o_rk = L.o_rk;
+    return true;
   };
-  if (!lay(dm)) return false;
+  // a model takes a size-specialised kernel when its sizes are the constant's and its layout is, every field, the constant's layout
+  static_assert(std::has_unique_object_representations_v<LdsLayout>, "layouts are compared as bytes");
+  auto sized_as = [&](const SizedModel& z, const LdsLayout& L) {
+    return m.nq == z.nq && nv == z.nv && m.nu == z.nu && nb == z.nbody && m.njnt == z.njnt && m.ngeom == z.ngeom && m.ntendon == z.ntendon && m.nM == z.nM && dm.ntree == z.ntree &&
+           m.npair == z.npair && dm.nlevel == z.nlevel && dm.nlimcand == z.nlimcand && dm.nstate == z.nstate && memcmp(&L, static_cast<const LdsLayout*>(&z), sizeof(LdsLayout)) == 0;
+  };
+  LdsLayout dm_lay;
+  if (!lay(dm, dm_lay)) return false;
 
   std::vector<int> mdense((size_t)32 * 32, m.nM);
   for (int i = 0; i < 32; i++) mdense[(size_t)i * 32 + i] = m.nM + 1;
@@ -628,37 +593,20 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
   if (D.d_qpos_src.alloc(qsrc.size()) != HB_OK ||
       hipMemcpy(D.d_qpos_src, qsrc.data(), qsrc.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMalloc failed for qpos sources"; return false; }
   if (D.d_dm.alloc(1) != HB_OK || hipMemcpy(D.d_dm, &dm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMalloc failed for the device model"; return false; }
+  // the size-specialised kernels (hb_step_h27_kernel and its kin): the model's sizes and the layout computed above against the constant's
+  D.sized_h27 = (dm.variant == 0 || (dm.variant == 1 && dm.solver == 0)) && sized_as(dm.variant == 1 ? kSizedHumanoid27V1 : kSizedHumanoid27, dm_lay);
   // A variant-2 model (Newton on 256 rows in four register groups: one wave per SIMD) almost always has at most 63 rows and 24
   // contacts in a step: its staged step first runs the one-group Newton instantiation (two waves per SIMD) on the variant-1 LDS
   // layout and falls back to the four-group kernel for the envs that overflow (launch_step).  Same tables, other offsets.
-  {
-    // the size-specialised kernel (hb_step_h27_kernel): the model's sizes and the layout just computed against the compile-time mirror
-    const SizedModel z = dm.variant == 1 ? kSizedHumanoid27V1 : kSizedHumanoid27;
-    D.sized_h27 = (dm.variant == 0 || (dm.variant == 1 && dm.solver == 0)) && dm.o_gquat == z.o_gquat && dm.o_meta == z.o_meta && m.nq == z.nq && nv == z.nv && m.nu == z.nu && nb == z.nbody && m.njnt == z.njnt && m.ngeom == z.ngeom &&
-                  m.ntendon == z.ntendon && m.nM == z.nM && dm.ntree == z.ntree && m.npair == z.npair && dm.nlevel == z.nlevel && dm.nlimcand == z.nlimcand && dm.nstate == z.nstate && dm.cstride == z.cstride &&
-                  dm.o_qpos == z.o_qpos && dm.o_qvel == z.o_qvel && dm.o_warm == z.o_warm && dm.o_ctrl == z.o_ctrl && dm.o_gpos == z.o_gpos && dm.o_gaxis == z.o_gaxis &&
-                  dm.o_scom == z.o_scom && dm.o_cdof == z.o_cdof && dm.o_qLD == z.o_qLD && dm.o_smooth == z.o_smooth && dm.o_vec0 == z.o_vec0 && dm.o_vec1 == z.o_vec1 &&
-                  dm.o_vec2 == z.o_vec2 && dm.o_tenlen == z.o_tenlen && dm.o_xpos == z.o_xpos && dm.o_xmat == z.o_xmat && dm.o_xipos == z.o_xipos &&
-                  dm.o_xanchor == z.o_xanchor && dm.o_xaxis == z.o_xaxis && dm.o_cinert == z.o_cinert && dm.o_crb == z.o_crb && dm.o_cvel == z.o_cvel &&
-                  dm.o_con == z.o_con && dm.o_C == z.o_C && dm.o_efc == z.o_efc && dm.o_force == z.o_force && dm.lds_floats == z.lds_floats;
-  }
   D.fast_lds_floats = 0;
   if (dm.variant == 2 || dm.variant == 3) {
     DevModel fm = dm;
     fm.variant = 1; fm.ncon_max = kNconMax; fm.nefc_max = kNefcMax;
-    if (!lay(fm)) return false;
+    LdsLayout fm_lay;
+    if (!lay(fm, fm_lay)) return false;
     if (D.d_dm_fast.alloc(1) != HB_OK || hipMemcpy(D.d_dm_fast, &fm, sizeof(DevModel), hipMemcpyHostToDevice) != hipSuccess) { err = "hipMalloc failed for the device model"; return false; }
     D.fast_lds_floats = fm.lds_floats;
-    {
-      const SizedModel z = kSizedTeamV1;  // the robot's fast layout against its compile-time mirror (hb_step_newton_gen20_team_kernel)
-      D.sized_team = dm.variant == 2 && fm.o_gquat == z.o_gquat && fm.o_meta == z.o_meta && m.nq == z.nq && nv == z.nv && m.nu == z.nu && nb == z.nbody && m.njnt == z.njnt &&
-                     m.ngeom == z.ngeom && m.ntendon == z.ntendon && m.nM == z.nM && fm.ntree == z.ntree && m.npair == z.npair && fm.nlevel == z.nlevel && fm.nlimcand == z.nlimcand &&
-                     fm.nstate == z.nstate && fm.cstride == z.cstride && fm.o_qpos == z.o_qpos && fm.o_qvel == z.o_qvel && fm.o_warm == z.o_warm && fm.o_ctrl == z.o_ctrl &&
-                     fm.o_gpos == z.o_gpos && fm.o_gaxis == z.o_gaxis && fm.o_scom == z.o_scom && fm.o_cdof == z.o_cdof && fm.o_qLD == z.o_qLD && fm.o_smooth == z.o_smooth &&
-                     fm.o_vec0 == z.o_vec0 && fm.o_vec1 == z.o_vec1 && fm.o_vec2 == z.o_vec2 && fm.o_tenlen == z.o_tenlen && fm.o_xpos == z.o_xpos && fm.o_xmat == z.o_xmat &&
-                     fm.o_xipos == z.o_xipos && fm.o_xanchor == z.o_xanchor && fm.o_xaxis == z.o_xaxis && fm.o_cinert == z.o_cinert && fm.o_crb == z.o_crb && fm.o_cvel == z.o_cvel &&
-                     fm.o_con == z.o_con && fm.o_C == z.o_C && fm.o_efc == z.o_efc && fm.o_force == z.o_force && fm.lds_floats == z.lds_floats;
-    }
+    D.sized_team = dm.variant == 2 && sized_as(kSizedTeamV1, fm_lay);  // (the robot's fast layout: hb_step_newton_gen20_team_kernel)
   }
   return true;
 }
@@ -859,8 +807,7 @@ int fork_pipes(hb_batch* b, int nseg) {
 }
 // the batch's model through launch_step; the launched kernel's name stays with the batch (hb_last_kernel)
 hipError_t launch_batch_step(hb_batch* b, const BatchPtrs& P, int nsteps, hipStream_t stream) {
-  const DevModel& dm = b->D.dm;
-  return launch_step(b->D.d_dm, dm.variant, dm.solver, dm.integrator, dm.nv, dm.nfric, dm.lds_floats, P, nsteps, stream, &b->last_kernel);
+  return launch_step(b->D.d_dm, b->D.dm, P, nsteps, stream, &b->last_kernel);
 }
 // one segment's launch of the step kernel, then (heavy-first scheduling, every 4th call) the tiny kernel that
 // orders the segment's next launch by the cost of this one; costs change slowly, and the sort sits on the
@@ -935,7 +882,7 @@ int launch_steps(hb_batch* b, BatchPtrs& P, int nsteps, bool foldable = false) {
   foldable = false;  // (the diagnostic build samples single launches)
 #endif
   foldable = foldable && b->npipe > 1 && cap > 1 && nsteps <= cap && P.ctrl_mode == 0 && !b->time_steps && !b->diag && !P.stamps && P.xfrc_scale == 0.f &&
-             fold_pays(b->D.dm.variant, b->D.dm.solver, b->D.dm.integrator, b->D.dm.nv, b->D.dm.nfric, P);
+             fold_pays(b->D.dm, P);
   if (!foldable) {
     const int rc = flush_steps(b);
     return rc != HB_OK ? rc : launch_steps_now(b, P, nsteps);
@@ -1382,7 +1329,7 @@ int hb_inverse_dev(hb_batch* b, const float* qacc_dev, int flags, float* qfrc_in
   P.stage = b->stage;  // general variants: the narrowphase of a staged step into the batch's stage buffers, which every step rewrites
   P.stage.defer = nullptr; P.stage.defer_list = nullptr; P.stage.defer_count = nullptr; P.stage.dm_fast = nullptr; P.stage.fast_lds = 0;
   P.inv_qacc = qacc_dev; P.inv_out = qfrc_inverse_dev; P.inv_warn = warnings_dev; P.inv_flags = flags;
-  HB_HIP(launch_inverse(b->D.d_dm, b->D.dm.variant, b->D.dm.nv, b->D.dm.nfric, b->D.dm.lds_floats, P, stream, &b->last_kernel));
+  HB_HIP(launch_inverse(b->D.d_dm, b->D.dm, P, stream, &b->last_kernel));
   return HB_OK;
 }
 

@@ -267,49 +267,97 @@ struct StageBufs {
   int no_mesh;              // the model has no mesh geoms: the narrowphase launch is hb_narrow_prim_kernel
 };
 
+// ---- The per-env LDS layout of the step kernels: every o_* offset of DevModel, the row stride of C, the RK4 stage block and the total,
+// as a function of the model's shape.  This is the one place that computes it: build_device_model copies the result into the DevModel
+// (and, for variants 2 and 3, into the one-group fast model), and the size-specialised kernels below take it as compile-time constants.
+enum { kLdsOk = 0, kLdsNoEulerRoom, kLdsTooLarge };  // LdsLayout::fail
+struct LdsLayout {
+  int o_gquat, o_meta, o_AR;
+  int o_qpos, o_qvel, o_warm, o_ctrl, o_gpos, o_gaxis, o_scom, o_cdof, o_qLD, o_smooth, o_vec0, o_vec1, o_vec2, o_tenlen;
+  int o_xpos, o_xmat, o_xipos, o_xanchor, o_xaxis, o_cinert, o_crb, o_cvel;
+  int o_con, o_C, o_efc, o_force;
+  int lds_floats, cstride, o_rk;
+  int fail;  // kLdsOk, or why no kernel can run the model: no room for the Euler solve's W_H pair, more LDS than a CU has
+};
+// variant, solver, integrator, ncon_max, nefc_max: DevModel's (mjtSolver 0 PGS / 2 Newton, mjtIntegrator 0 Euler / 1 RK4)
+constexpr LdsLayout lds_layout(int nq, int nv, int nu, int nbody, int njnt, int ngeom, int ntendon, int nM, int ntree, int variant, int solver, int integrator, int ncon_max,
+                               int nefc_max) {
+  LdsLayout L{};
+  int off = 0;
+  auto take = [&off](int n) { int o = off; off += (n + 3) & ~3; return o; };
+  auto imax = [](int a, int b) { return a > b ? a : b; };
+  // row stride of C: 33 (K = 32 for the matrix cores plus a pad column); the big Newton layout stores J rows only as wide as its dense
+  // order (NDENSE + 1: 21 for the reference's 18-dof robot, else 29): 256 rows of 33 floats would be 34 KB per env
+  // (variant 1 with the Newton solver is the fast layout of a variant-2 model: its one-group Newton kernel reads J rows like the big one)
+  L.cstride = (variant == 2 || (variant == 1 && solver == 2)) ? (nv <= 20 ? 21 : 29) : 33;
+  // persistent region
+  L.o_gquat = variant ? take(4 * ngeom) : 0;
+  L.o_qpos = take(nq); L.o_qvel = take(nv); L.o_warm = take(nv); L.o_ctrl = take(imax(1, nu));
+  L.o_gpos = take(3 * ngeom); L.o_gaxis = take(3 * ngeom); L.o_scom = take(3 * imax(1, ntree)); L.o_cdof = take(12 * nv);  // angular[3], -, linear[3], -, pad[4] per dof (kCdofStride: conflict-free b128 reads)
+  L.o_qLD = take(2 * nM + 4); L.o_smooth = take(nv);  // qLD: {M, H} pairs + the zero and one pad pairs of the dense views
+  L.o_vec0 = take(32); L.o_vec1 = take(32); L.o_vec2 = take(32);  /* read 32 wide */ L.o_tenlen = take(imax(1, ntendon));
+  const int region = off;
+  // region A (dynamics scratch)
+  L.o_xpos = take(12 * nbody);  /* xpos[3], -, xquat[4], pad[4] records (kXpqStride) */ L.o_xmat = take(9 * nbody); L.o_xipos = take(3 * nbody);
+  L.o_xanchor = take(3 * njnt); L.o_xaxis = take(3 * njnt); L.o_cinert = take(10 * nbody); L.o_crb = take(20 * nbody);  // crb: inertia[10] | cfrc[6] | pad[4] records (kIfStride)
+  L.o_cvel = take(12 * nbody);  // cvel[6] | cacc[6] records
+  const int endA = off;
+  // region B (constraints) aliases region A
+  off = region;
+  if (variant == 2) {
+    // Newton on kBigNefcMax rows: contacts, J rows, the dense M ([32][33], where the classic layout keeps the row meta), the
+    // compact row meta, one D / force word per row
+    L.o_con = take(ncon_max * kConStride);
+    L.o_C = take(imax(nefc_max * L.cstride + 64, kListMax * 5 + kWorkMax));  // (the collision pass borrows the head of C for its lists)
+    L.o_efc = take(32 * 36);
+    L.o_meta = take(nefc_max * kMetaStride);
+  } else if (variant == 3) {
+    // PGS on kPgsNefcMax rows: contacts, J / C rows (+ the qfrc_smooth row), W, the compact row meta, the matrix AR
+    L.o_con = take(ncon_max * kConStride);
+    L.o_C = take(imax((nefc_max + 1) * L.cstride + 64, kListMax * 5 + kWorkMax));
+    L.o_efc = take(32 * 36);
+    L.o_meta = take(nefc_max * kMetaStride);
+    L.o_AR = take(nefc_max * nefc_max);
+  } else {
+    L.o_con = take(kNconMax * kConStride); L.o_C = take((kNefcMax + 1) * L.cstride);
+    // per-row meta (13 slots x kNefcMax) is dead once the row quantities are in registers; W = L^-1 D^-1/2
+    // ([32][33]) is built over it before the J W product and lives until the dual finish
+    L.o_efc = take(imax(13 * kNefcMax, 32 * 36));
+    // mj_Euler builds W_H and its transpose (2 x [32][36]) from the start of C, running on into the row-meta area
+    if (L.o_efc != L.o_C + (((kNefcMax + 1) * L.cstride + 3) & ~3) || L.o_efc + imax(13 * kNefcMax, 32 * 36) - L.o_C < 2 * 32 * 36) { L.fail = kLdsNoEulerRoom; return L; }
+    if (variant == 1) L.o_meta = take(64 * kMetaStride);
+  }
+  L.o_force = take(imax(kGroup, nefc_max));
+  // xipos and scom/cdof are read while region B is being written (xfrc, Jacobians): keep xipos out of the alias
+  L.lds_floats = imax(endA, off);
+  // RK4: the stage block (start state and the two running sums) behind both regions, so that an RK4 model's layout is the Euler layout
+  // plus a tail and no offset moves
+  if (integrator == 1) { off = L.lds_floats; L.o_rk = take(nq + 3 * nv); L.lds_floats = off; }
+  if (L.lds_floats * 4 > 160 * 1024) L.fail = kLdsTooLarge;
+  return L;
+}
+
 // ---- Size-specialised instantiation of the classic PGS step kernel (step_body's SIZED) ---------------------------------------------
 // Every loop bound and every LDS offset of the step kernel is a function of the model's sizes.  For the size signature of the
 // reference's 27-dof humanoid (simulation/mujoco/model/humanoid/humanoid.xml) they are compile-time constants in one
 // more instantiation: addresses fold into the instructions' offset fields and 40 SGPRs spill instead of 84.  Any model with this
-// signature takes it (the host compares sizes AND the layout it computed itself, field by field: build_device_model); every other
-// model takes the generic kernels.
-struct SizedModel {
-  int nq, nv, nu, nbody, njnt, ngeom, ntendon, nM, ntree, npair, nlevel, nlimcand, nstate, cstride;
-  int o_qpos, o_qvel, o_warm, o_ctrl, o_gpos, o_gaxis, o_scom, o_cdof, o_qLD, o_smooth, o_vec0, o_vec1, o_vec2, o_tenlen;
-  int o_xpos, o_xmat, o_xipos, o_xanchor, o_xaxis, o_cinert, o_crb, o_cvel;
-  int o_con, o_C, o_efc, o_force, o_gquat, o_meta, lds_floats;
+// signature takes it (the host compares its sizes, and the layout lds_layout gave it against the constant's: build_device_model);
+// every other model takes the generic kernels.
+struct SizedModel : LdsLayout {
+  int nq, nv, nu, nbody, njnt, ngeom, ntendon, nM, ntree, npair, nlevel, nlimcand, nstate;
 };
-// the classic layout (variant 0, full capacity) as build_device_model's lay() computes it
-constexpr SizedModel sized_model(int nq, int nv, int nu, int nbody, int njnt, int ngeom, int ntendon, int nM, int ntree, int npair, int nlevel, int nlimcand, int variant = 0, int cstride = 33) {
-  SizedModel z{};
-  z.nq = nq; z.nv = nv; z.nu = nu; z.nbody = nbody; z.njnt = njnt; z.ngeom = ngeom; z.ntendon = ntendon; z.nM = nM; z.ntree = ntree; z.npair = npair; z.nlevel = nlevel; z.nlimcand = nlimcand;
-  z.nstate = 1 + nq + 2 * nv; z.cstride = cstride;
-  int off = 0;
-  auto up = [](int n) { return (n + 3) & ~3; };
-  z.o_gquat = 0; z.o_meta = 0;
-  if (variant) { z.o_gquat = off; off += up(4 * ngeom); }  // (general collision: world orientation of every geom)
-  z.o_qpos = off; off += up(nq); z.o_qvel = off; off += up(nv); z.o_warm = off; off += up(nv); z.o_ctrl = off; off += up(nu > 1 ? nu : 1);
-  z.o_gpos = off; off += up(3 * ngeom); z.o_gaxis = off; off += up(3 * ngeom); z.o_scom = off; off += up(3 * (ntree > 1 ? ntree : 1)); z.o_cdof = off; off += up(12 * nv);
-  z.o_qLD = off; off += up(2 * nM + 4); z.o_smooth = off; off += up(nv);
-  z.o_vec0 = off; off += 32; z.o_vec1 = off; off += 32; z.o_vec2 = off; off += 32; z.o_tenlen = off; off += up(ntendon > 1 ? ntendon : 1);
-  const int region = off;
-  z.o_xpos = off; off += up(12 * nbody); z.o_xmat = off; off += up(9 * nbody); z.o_xipos = off; off += up(3 * nbody);
-  z.o_xanchor = off; off += up(3 * njnt); z.o_xaxis = off; off += up(3 * njnt); z.o_cinert = off; off += up(10 * nbody); z.o_crb = off; off += up(20 * nbody);
-  z.o_cvel = off; off += up(12 * nbody);
-  const int endA = off;
-  off = region;
-  z.o_con = off; off += up(kNconMax * kConStride); z.o_C = off; off += up((kNefcMax + 1) * cstride);
-  z.o_efc = off; off += up(13 * kNefcMax > 32 * 36 ? 13 * kNefcMax : 32 * 36);
-  if (variant == 1) { z.o_meta = off; off += up(64 * kMetaStride); }
-  z.o_force = off; off += up(kGroup > kNefcMax ? kGroup : kNefcMax);
-  z.lds_floats = endA > off ? endA : off;
-  return z;
+// (full capacity, Euler: the layout of variant 0 or 1 as lds_layout computes it for these sizes)
+constexpr SizedModel sized_for(int nq, int nv, int nu, int nbody, int njnt, int ngeom, int ntendon, int nM, int ntree, int npair, int nlevel, int nlimcand, int variant, int solver) {
+  return {lds_layout(nq, nv, nu, nbody, njnt, ngeom, ntendon, nM, ntree, variant, solver, /*integrator*/ 0, kNconMax, kNefcMax),
+          nq, nv, nu, nbody, njnt, ngeom, ntendon, nM, ntree, npair, nlevel, nlimcand, 1 + nq + 2 * nv};
 }
-constexpr SizedModel kSizedHumanoid27 = sized_model(28, 27, 21, 17, 22, 20, 2, 243, 1, 159, /*tree levels*/ 7, /*limit candidates*/ 46);
+constexpr SizedModel kSizedHumanoid27 = sized_for(28, 27, 21, 17, 22, 20, 2, 243, 1, 159, /*tree levels*/ 7, /*limit candidates*/ 46, /*variant*/ 0, /*PGS or Newton: the same layout*/ 0);
 // the same humanoid on a height field (configs[4]; general collision, PGS: the variant-1 layout of the staged step's fast kernel)
+constexpr SizedModel kSizedHumanoid27V1 = sized_for(28, 27, 21, 17, 22, 20, 2, 243, 1, 159, 7, 46, /*variant*/ 1, /*PGS*/ 0);
 // the reference's own robot (simulation/assets/world.xml + humanoid.xml: 18 dofs, 13 geoms) on the variant-1 layout of its fast Newton kernel
-constexpr SizedModel kSizedTeamV1 = sized_model(19, 18, 12, 15, 13, 13, 0, 117, 1, 37, /*tree levels*/ 5, /*limit candidates*/ 24, /*variant*/ 1, /*J row stride of a Newton kernel of dense order 20*/ 21);
-constexpr SizedModel kSizedHumanoid27V1 = sized_model(28, 27, 21, 17, 22, 20, 2, 243, 1, 159, 7, 46, /*variant*/ 1);
+// (J row stride 21: a Newton kernel of dense order 20)
+constexpr SizedModel kSizedTeamV1 = sized_for(19, 18, 12, 15, 13, 13, 0, 117, 1, 37, /*tree levels*/ 5, /*limit candidates*/ 24, /*variant*/ 1, /*Newton*/ 2);
+static_assert(!kSizedHumanoid27.fail && !kSizedHumanoid27V1.fail && !kSizedTeamV1.fail, "the size-specialised kernels' layouts must be valid");
 
 // LDS of hb_pose_kernel in floats: qpos | body poses (12 floats each, kXpqStride) | geom position, z axis, quaternion | the work lists
 __host__ __device__ inline int pose_lds_floats(int nq, int nb, int ngeom) {
@@ -382,7 +430,7 @@ struct BatchPtrs {
   // body-acceleration read-out (hb_body_acc_readout), both null or both set: [n_env][nbody][6] = angular | linear acceleration of the
   // body's xipos, world axes, gravity pseudo-acceleration included; and the scratch the step kernel parks what the read-out needs of the
   // kinematics in, [n_env][nbody][kAccPark]: bias cacc[6] | cvel[6] | xipos - subtree_com[3] | xpos - subtree_com[3] | xquat[4] | -.
-  // A launch that carries them takes the full kernel's instantiation with the read-out (step_body's ACC, hb_step.hip: HB_ACC_KERNELS).
+  // A launch that carries them takes the full kernel's instantiation with the read-out (step_body's ACC, hb_step.hip: the ACC rows of HB_KERNELS).
   float* body_acc;
   float* body_acc_park;
   // ... and their sensor entries, behind the contact-force entries: accelerometer[3] | gyro[3] at body frame + offset in the body's

@@ -3,16 +3,16 @@
 #include <hip/hip_runtime.h>
 #include "hb_device.hpp"
 namespace hb {
-// (fric: the model has friction rows, DevModel::nfric - the launch takes a FRIC instantiation)
+// M: the host's copy of *M_dev, from which every launcher reads the sizes, the variant and the LDS layout it needs
 // the step launchers leave the name of the kernel they launched in *kernel (hb_last_kernel; a staged step: its fast-pass kernel)
-hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integrator, int nv, int fric, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel);
+hipError_t launch_step(const DevModel* M_dev, const DevModel& M, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel);
 // inverse dynamics of the launch's envs (hb_inverse_dev; hb_step.hip)
-hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int fric, int lds_floats, const BatchPtrs& P, hipStream_t stream, const char** kernel);
-// whole-body kinematics of A.n states (hb_kin.hip): pack = 0 one state per wave, 1 as many as fit (HB_TUNE_KIN_PACK); M: the host's copy of *M_dev
+hipError_t launch_inverse(const DevModel* M_dev, const DevModel& M, const BatchPtrs& P, hipStream_t stream, const char** kernel);
+// whole-body kinematics of A.n states (hb_kin.hip): pack = 0 one state per wave, 1 as many as fit (HB_TUNE_KIN_PACK)
 hipError_t launch_kinematics(const DevModel* M_dev, const DevModel& M, const KinArgs& A, int pack, hipStream_t stream, const char** kernel);
 // two envs per wave: a lean launch of the 27-dof humanoid's PGS kernel (hb_step_duo.hip; chosen by launch_step)
 hipError_t launch_step_duo(const DevModel* M_dev, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel);
-bool fold_pays(int variant, int solver, int integrator, int nv, int fric, const BatchPtrs& P);
+bool fold_pays(const DevModel& M, const BatchPtrs& P);
 // the pose + narrowphase launches of one staged step (hb_narrow.hip)
 hipError_t launch_pose_narrow(const DevModel* M_dev, const BatchPtrs& Q, hipStream_t stream);
 hipError_t launch_reset(const DevModel& M, float* state, int* status, const uint8_t* mask, const float* qpos_src, const int* episode, int n_env, float perturb,

@@ -56,7 +56,7 @@ __device__ __forceinline__ void defer_env(const BatchPtrs& P, int env) {
 // FRIC: joint friction loss (mj_instantiateFriction): one always-active row per dof with dof_frictionloss > 0, in front of the limit rows,
 // whose force is bounded on both sides, -frictionloss <= f <= frictionloss.  In the dual (PGS) the row's max becomes a clamp; in the primal
 // (Newton, mj_inverse) the row's cost has three zones: quadratic inside |jar| < R frictionloss, linear with the force at its bound outside.
-// Every line of it sits behind FRIC: the instantiations a model without friction loss runs are the code they were (HB_FRIC_KERNELS).
+// Every line of it sits behind FRIC: the instantiations a model without friction loss runs are the code they were (HB_KERNELS: the FRIC rows).
 template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0, int INV = 0, int INTEG = 0, int ACC = 0, int FRIC = 0>
 __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P, int nsteps_in, int env_in = -1) {
   const int nsteps = LEAN == 1 ? 1 : nsteps_in;  // (LEAN == 1 is launched for single steps only: the step API; rollouts take LEAN == 2)
@@ -2200,127 +2200,103 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
 }
 
 #undef HB_SZ
-// ---- The kernel table: one row per step_body instantiation.  The __global__ definitions, the host array the dispatch looks kernels up in
-// (select_step) and the kernels' names (hb_last_kernel) are all generated from these lists.  RERUN: the second pass of a staged step,
-// a few waves that walk the list of deferred envs (HB_STEP_OR_RERUN).  VGPRS: amdgpu_num_vgpr, counted per half of the file (0: no cap).
-//  K(name,                             SOLVER, NDENSE, COLL, NG,         DEFER, LEAN, SIZED, INV, WAVES, VGPRS, RERUN)
-#define HB_STEP_KERNELS(K) /* (Mp, P, nsteps) */                                                                                           \
-  /* PGS: dense order 28 (nv <= 28: the 27-dof humanoid; M^-1 by elimination on the matrix cores) and 32 (sparse L'DL)                   */ \
-  /* (224 registers instead of the 229 the allocator would take - two values spilled - so that beside two of its waves a SIMD has 64     */ \
-  /* registers left: what the closed loop's policy kernel runs in, hb_policy_lean_kernel)                                                */ \
-  K(hb_step_kernel,                     0,      28,     0,    1,          0,     0,    0,     0,   2,     112,   0)                         \
-  K(hb_step_lean_kernel,                0,      28,     0,    1,          0,     1,    0,     0,   2,     112,   0)                         \
-  /* (the lean kernels with the sizes and the LDS layout of the reference's 27-dof humanoid as constants)                                */ \
-  K(hb_step_h27_kernel,                 0,      28,     0,    1,          0,     1,    1,     0,   2,     112,   0)                         \
-  K(hb_step_h27_q_kernel,               0,      28,     0,    1,          0,     2,    1,     0,   2,     112,   0)                         \
-  K(hb_step_lean_q_kernel,              0,      28,     0,    1,          0,     2,    0,     0,   2,     112,   0)                         \
-  K(hb_step32_kernel,                   0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
-  /* General (mesh hulls, height-field prisms, condim 4 / 6): PGS on 63 rows (configs[4]: the 27-dof humanoid on terrain), Newton on     */ \
-  /* 256 rows (the reference's own robot, simulation/assets/world.xml: 18 dofs -> dense order 20; up to 28 dofs)                         */ \
-  K(hb_step_gen_kernel,                 0,      28,     1,    1,          0,     0,    0,     0,   2,     0,     1)                         \
-  /* PGS on kPgsNefcMax rows (AR in LDS: one env per CU) for condim 4 / 6 models, and the one-group fast pass that defers to it          */ \
-  /* (variant 3); hb_step_gen_fast_kernel: the fast pass of a variant-1 staged step                                                      */ \
-  K(hb_step_gen_big_kernel,             0,      28,     1,    kPgsGroups, 0,     0,    0,     0,   1,     0,     1)                         \
-  K(hb_step_gen_fast1_kernel,           0,      28,     1,    1,          1,     0,    0,     0,   2,     0,     0)                         \
-  K(hb_step_gen_fast_kernel,            0,      28,     1,    1,          2,     0,    0,     0,   2,     0,     0)                         \
-  K(hb_step_newton_big20_kernel,        2,      20,     1,    kBigGroups, 0,     0,    0,     0,   1,     0,     1)                         \
-  K(hb_step_newton_big28_kernel,        2,      28,     1,    kBigGroups, 0,     0,    0,     0,   1,     0,     1)                         \
-  /* fast pass of a variant-2 model's staged step: Newton on one row group, general collision results, deferring what does not fit       */ \
-  K(hb_step_newton_gen20_kernel,        2,      20,     1,    1,          1,     0,    0,     0,   2,     0,     0)                         \
-  K(hb_step_newton_gen28_kernel,        2,      28,     1,    1,          1,     0,    0,     0,   2,     0,     0)                         \
-  /* Newton: dense order 28 (nv <= 28: the 27-dof humanoid) and 32                                                                       */ \
-  K(hb_step_newton28_kernel,            2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
-  /* lean instantiations (step_body's LEAN: no optional inputs / outputs in the launch) of the kernels the plain step API spends its     */ \
-  /* time in                                                                                                                             */ \
-  K(hb_step_newton28_lean_kernel,       2,      28,     0,    1,          0,     1,    0,     0,   2,     0,     0)                         \
-  K(hb_step_newton28_h27_kernel,        2,      28,     0,    1,          0,     1,    1,     0,   2,     0,     0)                         \
-  K(hb_step_newton28_lean_q_kernel,     2,      28,     0,    1,          0,     2,    0,     0,   2,     0,     0)                         \
-  K(hb_step_gen_fast_lean_kernel,       0,      28,     1,    1,          2,     1,    0,     0,   2,     0,     0)                         \
-  K(hb_step_newton_gen20_team_kernel,   2,      20,     1,    1,          1,     1,    1,     0,   2,     0,     0)                         \
-  K(hb_step_gen_fast_h27_kernel,        0,      28,     1,    1,          2,     1,    1,     0,   2,     0,     0)                         \
-  K(hb_step_newton_gen20_lean_kernel,   2,      20,     1,    1,          1,     1,    0,     0,   2,     0,     0)                         \
-  K(hb_step_newton32_kernel,            2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
-// inverse dynamics (step_body's INV; hb_inverse): one per row capacity and dense order, with the stages of the model's variant.  The solver
-// template argument only selects the dense views (no solver runs); the general variants read the contacts of launch_pose_narrow (DEFER 2)
-#define HB_INVERSE_KERNELS(K) /* (Mp, P): a single step */                                                                                 \
-  K(hb_inverse_kernel,                  2,      28,     0,    1,          0,     0,    0,     1,   2,     0,     0)                         \
-  K(hb_inverse32_kernel,                2,      32,     0,    1,          0,     0,    0,     1,   2,     0,     0)                         \
-  K(hb_inverse_gen_kernel,              2,      28,     1,    1,          2,     0,    0,     1,   2,     0,     0)                         \
-  K(hb_inverse_pgs_big_kernel,          2,      28,     1,    kPgsGroups, 2,     0,    0,     1,   1,     0,     0)                         \
-  K(hb_inverse_big20_kernel,            2,      20,     1,    kBigGroups, 2,     0,    0,     1,   1,     0,     0)                         \
-  K(hb_inverse_big28_kernel,            2,      28,     1,    kBigGroups, 2,     0,    0,     1,   1,     0,     0)
-// the RK4 integrator (step_body's INTEG; mjINT_RK4): the full kernels of the classic variant, one per solver and dense order
-#define HB_RK4_KERNELS(K) /* (Mp, P, nsteps) */                                                                                            \
-  K(hb_rk4_kernel,                      0,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
-  K(hb_rk4_32_kernel,                   0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
-  K(hb_rk4_newton28_kernel,             2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0)                         \
-  K(hb_rk4_newton32_kernel,             2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
+// ---- The kernel table: one row per step_body instantiation, one column per template argument of step_body plus the launch attributes.
+// The __global__ definitions, the host array the dispatch looks kernels up in (select_step) and the kernels' names (hb_last_kernel) are
+// all generated from this list.  WAVES: the second argument of __launch_bounds__.  VGPRS: amdgpu_num_vgpr, counted per half of the file
+// (0: no cap).  RERUN: the second pass of a staged step, a few waves that walk the list of deferred envs (HB_STEP_OR_RERUN).
+//  K(name,                             SOLVER, NDENSE, COLL, NG,         DEFER, LEAN, SIZED, INV, INTEG, ACC, FRIC, WAVES, VGPRS, RERUN)
+#define HB_KERNELS(K)                                                                                                                     \
+  /* PGS: dense order 28 (nv <= 28: the 27-dof humanoid; M^-1 by elimination on the matrix cores) and 32 (sparse L'DL)                 */ \
+  /* (224 registers instead of the 229 the allocator would take - two values spilled - so that beside two of its waves a SIMD has 64   */ \
+  /* registers left: what the closed loop's policy kernel runs in, hb_policy_lean_kernel)                                              */ \
+  K(hb_step_kernel,                   0,      28,     0,    1,          0,     0,    0,     0,   0,     0,   0,    2,     112,   0)       \
+  K(hb_step_lean_kernel,              0,      28,     0,    1,          0,     1,    0,     0,   0,     0,   0,    2,     112,   0)       \
+  /* (the lean kernels with the sizes and the LDS layout of the reference's 27-dof humanoid as constants)                              */ \
+  K(hb_step_h27_kernel,               0,      28,     0,    1,          0,     1,    1,     0,   0,     0,   0,    2,     112,   0)       \
+  K(hb_step_h27_q_kernel,             0,      28,     0,    1,          0,     2,    1,     0,   0,     0,   0,    2,     112,   0)       \
+  K(hb_step_lean_q_kernel,            0,      28,     0,    1,          0,     2,    0,     0,   0,     0,   0,    2,     112,   0)       \
+  K(hb_step32_kernel,                 0,      32,     0,    1,          0,     0,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  /* General (mesh hulls, height-field prisms, condim 4 / 6): PGS on 63 rows (configs[4]: the 27-dof humanoid on terrain), Newton on   */ \
+  /* 256 rows (the reference's own robot, simulation/assets/world.xml: 18 dofs -> dense order 20; up to 28 dofs)                       */ \
+  K(hb_step_gen_kernel,               0,      28,     1,    1,          0,     0,    0,     0,   0,     0,   0,    2,     0,     1)       \
+  /* PGS on kPgsNefcMax rows (AR in LDS: one env per CU) for condim 4 / 6 models, and the one-group fast pass that defers to it        */ \
+  /* (variant 3); hb_step_gen_fast_kernel: the fast pass of a variant-1 staged step                                                    */ \
+  K(hb_step_gen_big_kernel,           0,      28,     1,    kPgsGroups, 0,     0,    0,     0,   0,     0,   0,    1,     0,     1)       \
+  K(hb_step_gen_fast1_kernel,         0,      28,     1,    1,          1,     0,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_gen_fast_kernel,          0,      28,     1,    1,          2,     0,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_newton_big20_kernel,      2,      20,     1,    kBigGroups, 0,     0,    0,     0,   0,     0,   0,    1,     0,     1)       \
+  K(hb_step_newton_big28_kernel,      2,      28,     1,    kBigGroups, 0,     0,    0,     0,   0,     0,   0,    1,     0,     1)       \
+  /* fast pass of a variant-2 model's staged step: Newton on one row group, general collision results, deferring what does not fit     */ \
+  K(hb_step_newton_gen20_kernel,      2,      20,     1,    1,          1,     0,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_newton_gen28_kernel,      2,      28,     1,    1,          1,     0,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  /* Newton: dense order 28 (nv <= 28: the 27-dof humanoid) and 32                                                                     */ \
+  K(hb_step_newton28_kernel,          2,      28,     0,    1,          0,     0,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  /* lean instantiations (step_body's LEAN: no optional inputs / outputs in the launch) of the kernels the plain step API spends its   */ \
+  /* time in                                                                                                                           */ \
+  K(hb_step_newton28_lean_kernel,     2,      28,     0,    1,          0,     1,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_newton28_h27_kernel,      2,      28,     0,    1,          0,     1,    1,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_newton28_lean_q_kernel,   2,      28,     0,    1,          0,     2,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_gen_fast_lean_kernel,     0,      28,     1,    1,          2,     1,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_newton_gen20_team_kernel, 2,      20,     1,    1,          1,     1,    1,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_gen_fast_h27_kernel,      0,      28,     1,    1,          2,     1,    1,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_newton_gen20_lean_kernel, 2,      20,     1,    1,          1,     1,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  K(hb_step_newton32_kernel,          2,      32,     0,    1,          0,     0,    0,     0,   0,     0,   0,    2,     0,     0)       \
+  /* inverse dynamics (step_body's INV; hb_inverse): one per row capacity and dense order, with the stages of the model's variant.     */ \
+  /* The solver column only selects the dense views (no solver runs); the general variants read the contacts of launch_pose_narrow     */ \
+  /* (DEFER 2).  An INV row runs a single step whatever the count says.                                                                */ \
+  K(hb_inverse_kernel,                2,      28,     0,    1,          0,     0,    0,     1,   0,     0,   0,    2,     0,     0)       \
+  K(hb_inverse32_kernel,              2,      32,     0,    1,          0,     0,    0,     1,   0,     0,   0,    2,     0,     0)       \
+  K(hb_inverse_gen_kernel,            2,      28,     1,    1,          2,     0,    0,     1,   0,     0,   0,    2,     0,     0)       \
+  K(hb_inverse_pgs_big_kernel,        2,      28,     1,    kPgsGroups, 2,     0,    0,     1,   0,     0,   0,    1,     0,     0)       \
+  K(hb_inverse_big20_kernel,          2,      20,     1,    kBigGroups, 2,     0,    0,     1,   0,     0,   0,    1,     0,     0)       \
+  K(hb_inverse_big28_kernel,          2,      28,     1,    kBigGroups, 2,     0,    0,     1,   0,     0,   0,    1,     0,     0)       \
+  /* the RK4 integrator (step_body's INTEG; mjINT_RK4): the full kernels of the classic variant, one per solver and dense order        */ \
+  K(hb_rk4_kernel,                    0,      28,     0,    1,          0,     0,    0,     0,   1,     0,   0,    2,     0,     0)       \
+  K(hb_rk4_32_kernel,                 0,      32,     0,    1,          0,     0,    0,     0,   1,     0,   0,    2,     0,     0)       \
+  K(hb_rk4_newton28_kernel,           2,      28,     0,    1,          0,     0,    0,     0,   1,     0,   0,    2,     0,     0)       \
+  K(hb_rk4_newton32_kernel,           2,      32,     0,    1,          0,     0,    0,     0,   1,     0,   0,    2,     0,     0)       \
+  /* the body-acceleration read-out (step_body's ACC; hb_body_acc_readout): every full kernel above once more, row for row, with the   */ \
+  /* read-out's parking and epilogue - what a launch that carries the read-out runs in place of the kernel of the same row             */ \
+  K(hb_acc_kernel,                    0,      28,     0,    1,          0,     0,    0,     0,   0,     1,   0,    2,     112,   0)       \
+  K(hb_acc32_kernel,                  0,      32,     0,    1,          0,     0,    0,     0,   0,     1,   0,    2,     0,     0)       \
+  K(hb_acc_gen_kernel,                0,      28,     1,    1,          0,     0,    0,     0,   0,     1,   0,    2,     0,     1)       \
+  K(hb_acc_gen_big_kernel,            0,      28,     1,    kPgsGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)       \
+  K(hb_acc_gen_fast1_kernel,          0,      28,     1,    1,          1,     0,    0,     0,   0,     1,   0,    2,     0,     0)       \
+  K(hb_acc_gen_fast_kernel,           0,      28,     1,    1,          2,     0,    0,     0,   0,     1,   0,    2,     0,     0)       \
+  K(hb_acc_newton_big20_kernel,       2,      20,     1,    kBigGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)       \
+  K(hb_acc_newton_big28_kernel,       2,      28,     1,    kBigGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)       \
+  K(hb_acc_newton_gen20_kernel,       2,      20,     1,    1,          1,     0,    0,     0,   0,     1,   0,    2,     0,     0)       \
+  K(hb_acc_newton_gen28_kernel,       2,      28,     1,    1,          1,     0,    0,     0,   0,     1,   0,    2,     0,     0)       \
+  K(hb_acc_newton28_kernel,           2,      28,     0,    1,          0,     0,    0,     0,   0,     1,   0,    2,     0,     0)       \
+  K(hb_acc_newton32_kernel,           2,      32,     0,    1,          0,     0,    0,     0,   0,     1,   0,    2,     0,     0)       \
+  K(hb_acc_rk4_kernel,                0,      28,     0,    1,          0,     0,    0,     0,   1,     1,   0,    2,     0,     0)       \
+  K(hb_acc_rk4_32_kernel,             0,      32,     0,    1,          0,     0,    0,     0,   1,     1,   0,    2,     0,     0)       \
+  K(hb_acc_rk4_newton28_kernel,       2,      28,     0,    1,          0,     0,    0,     0,   1,     1,   0,    2,     0,     0)       \
+  K(hb_acc_rk4_newton32_kernel,       2,      32,     0,    1,          0,     0,    0,     0,   1,     1,   0,    2,     0,     0)       \
+  /* joint friction loss (step_body's FRIC): the full kernels of the classic variant and its inverse dynamics, one per solver and      */ \
+  /* dense order - what a model with friction rows runs whatever the launch looks like (select_step)                                   */ \
+  K(hb_fric_kernel,                   0,      28,     0,    1,          0,     0,    0,     0,   0,     0,   1,    2,     0,     0)       \
+  K(hb_fric32_kernel,                 0,      32,     0,    1,          0,     0,    0,     0,   0,     0,   1,    2,     0,     0)       \
+  K(hb_fric_newton28_kernel,          2,      28,     0,    1,          0,     0,    0,     0,   0,     0,   1,    2,     0,     0)       \
+  K(hb_fric_newton32_kernel,          2,      32,     0,    1,          0,     0,    0,     0,   0,     0,   1,    2,     0,     0)       \
+  K(hb_fric_inverse_kernel,           2,      28,     0,    1,          0,     0,    0,     1,   0,     0,   1,    2,     0,     0)       \
+  K(hb_fric_inverse32_kernel,         2,      32,     0,    1,          0,     0,    0,     1,   0,     0,   1,    2,     0,     0)
 
-// the body-acceleration read-out (step_body's ACC; hb_body_acc_readout): every full kernel above once more, row for row, with the read-out's
-// parking and epilogue - what a launch that carries the read-out runs in place of the kernel of the same row
-#define HB_ACC_KERNELS(K) /* (Mp, P, nsteps) */ \
-  K(hb_acc_kernel,                      0,      28,     0,    1,          0,     0,    0,     0,   2,     112,   0) \
-  K(hb_acc32_kernel,                    0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
-  K(hb_acc_gen_kernel,                  0,      28,     1,    1,          0,     0,    0,     0,   2,     0,     1) \
-  K(hb_acc_gen_big_kernel,              0,      28,     1,    kPgsGroups, 0,     0,    0,     0,   1,     0,     1) \
-  K(hb_acc_gen_fast1_kernel,            0,      28,     1,    1,          1,     0,    0,     0,   2,     0,     0) \
-  K(hb_acc_gen_fast_kernel,             0,      28,     1,    1,          2,     0,    0,     0,   2,     0,     0) \
-  K(hb_acc_newton_big20_kernel,         2,      20,     1,    kBigGroups, 0,     0,    0,     0,   1,     0,     1) \
-  K(hb_acc_newton_big28_kernel,         2,      28,     1,    kBigGroups, 0,     0,    0,     0,   1,     0,     1) \
-  K(hb_acc_newton_gen20_kernel,         2,      20,     1,    1,          1,     0,    0,     0,   2,     0,     0) \
-  K(hb_acc_newton_gen28_kernel,         2,      28,     1,    1,          1,     0,    0,     0,   2,     0,     0) \
-  K(hb_acc_newton28_kernel,             2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
-  K(hb_acc_newton32_kernel,             2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
-#define HB_ACC_RK4_KERNELS(K) /* (Mp, P, nsteps) */ \
-  K(hb_acc_rk4_kernel,                  0,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
-  K(hb_acc_rk4_32_kernel,               0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
-  K(hb_acc_rk4_newton28_kernel,         2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
-  K(hb_acc_rk4_newton32_kernel,         2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0)
-
-// joint friction loss (step_body's FRIC): the full kernels of the classic variant and its inverse dynamics, one per solver and dense order -
-// what a model with friction rows runs whatever the launch looks like (select_step).
-#define HB_FRIC_KERNELS(K) /* (Mp, P, nsteps) */ \
-  K(hb_fric_kernel,                     0,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
-  K(hb_fric32_kernel,                   0,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
-  K(hb_fric_newton28_kernel,            2,      28,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
-  K(hb_fric_newton32_kernel,            2,      32,     0,    1,          0,     0,    0,     0,   2,     0,     0) \
-  K(hb_fric_inverse_kernel,             2,      28,     0,    1,          0,     0,    0,     1,   2,     0,     0) \
-  K(hb_fric_inverse32_kernel,           2,      32,     0,    1,          0,     0,    0,     1,   2,     0,     0)
-
-// (the entry calls step_body directly: a forwarding function template in between changes register allocation and scheduling)
-#define HB_STEP_BODY_0(...) step_body<__VA_ARGS__>(Mp, P, nsteps)
+// (the entry calls step_body directly: a forwarding function template in between changes register allocation and scheduling; every kernel
+// has the one signature - launch_pass hands all of them three arguments - and an INV row runs a single step whatever the count says)
+#define HB_STEP_BODY_0(S, ND, C, G, D, L, Z, I, N, A, F) step_body<S, ND, C, G, D, L, Z, I, N, A, F>(Mp, P, I ? 1 : nsteps)
 #define HB_STEP_BODY_1(...) HB_STEP_OR_RERUN(__VA_ARGS__)
-#define HB_DEFINE_STEP(name, S, ND, C, G, D, L, Z, I, W, V, R) \
-  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_BODY_##R(S, ND, C, G, D, L, Z, I); }
-#define HB_DEFINE_INVERSE(name, S, ND, C, G, D, L, Z, I, W, V, R) \
-  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P) { step_body<S, ND, C, G, D, L, Z, I>(Mp, P, 1); }
-#define HB_DEFINE_RK4(name, S, ND, C, G, D, L, Z, I, W, V, R) \
-  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<S, ND, C, G, D, L, Z, I, 1>(Mp, P, nsteps); }
-HB_STEP_KERNELS(HB_DEFINE_STEP)
-HB_INVERSE_KERNELS(HB_DEFINE_INVERSE)
-#define HB_DEFINE_ACC(name, S, ND, C, G, D, L, Z, I, W, V, R) \
-  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_BODY_##R(S, ND, C, G, D, L, Z, I, 0, 1); }
-#define HB_DEFINE_ACC_RK4(name, S, ND, C, G, D, L, Z, I, W, V, R) \
-  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<S, ND, C, G, D, L, Z, I, 1, 1>(Mp, P, nsteps); }
-HB_RK4_KERNELS(HB_DEFINE_RK4)
-HB_ACC_KERNELS(HB_DEFINE_ACC)
-HB_ACC_RK4_KERNELS(HB_DEFINE_ACC_RK4)
-// (one signature for the whole list: an inverse row runs a single step whatever the count says - launch_pass hands every kernel all three arguments)
-#define HB_DEFINE_FRIC(name, S, ND, C, G, D, L, Z, I, W, V, R) \
-  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { step_body<S, ND, C, G, D, L, Z, I, 0, 0, 1>(Mp, P, I ? 1 : nsteps); }
-HB_FRIC_KERNELS(HB_DEFINE_FRIC)
+#define HB_DEFINE(name, S, ND, C, G, D, L, Z, I, N, A, F, W, V, R) \
+  __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_BODY_##R(S, ND, C, G, D, L, Z, I, N, A, F); }
+HB_KERNELS(HB_DEFINE)
 
 struct StepConfig {
   int solver, ndense, coll, ng, defer, lean, sized, inv, integ, acc, fric;
   bool operator==(const StepConfig& o) const { return solver == o.solver && ndense == o.ndense && coll == o.coll && ng == o.ng && defer == o.defer && lean == o.lean && sized == o.sized && inv == o.inv && integ == o.integ && acc == o.acc && fric == o.fric; }
 };
 struct StepKernel { const char* name; const void* fn; StepConfig cfg; bool rerun; };
-#define HB_STEP_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 0}, R != 0},
-#define HB_RK4_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 1}, R != 0},
-#define HB_ACC_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 0, 1}, R != 0},
-#define HB_ACC_RK4_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 1, 1}, R != 0},
-#define HB_FRIC_ROW(name, S, ND, C, G, D, L, Z, I, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, 0, 0, 1}, R != 0},
-static const StepKernel kStepKernels[] = {HB_STEP_KERNELS(HB_STEP_ROW) HB_INVERSE_KERNELS(HB_STEP_ROW) HB_RK4_KERNELS(HB_RK4_ROW) HB_ACC_KERNELS(HB_ACC_ROW) HB_ACC_RK4_KERNELS(HB_ACC_RK4_ROW) HB_FRIC_KERNELS(HB_FRIC_ROW)};
+#define HB_ROW(name, S, ND, C, G, D, L, Z, I, N, A, F, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, N, A, F}, R != 0},
+static const StepKernel kStepKernels[] = {HB_KERNELS(HB_ROW)};
 static const StepKernel* find_step_kernel(const StepConfig& c) {
   for (const StepKernel& k : kStepKernels) if (k.cfg == c) return &k;
   return nullptr;
@@ -2358,22 +2334,25 @@ static bool lean_launch(const BatchPtrs& P, bool with_qfrc = false) {
 // runs on the one-group model StageBufs::dm_fast with its own LDS size: kernel, model and LDS size are chosen together), or the inverse.
 enum class StepPass { Main, Fast, Inverse };
 struct StepChoice { const StepKernel* kernel; bool duo; const DevModel* M_dev; size_t shmem; };  // (duo: launch_step_duo, no table row)
-static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant, int solver, int integrator, int nv, int fric, size_t shmem, const BatchPtrs& P, int nsteps) {
+// (M: the host's copy of *M_dev)
+static StepChoice select_step(StepPass pass, const DevModel* M_dev, const DevModel& M, const BatchPtrs& P, int nsteps) {
+  const int variant = M.variant, nv = M.nv;
+  size_t shmem = (size_t)M.lds_floats * sizeof(float);
   StepConfig c = variant == 1   ? StepConfig{0, 28, 1, 1}
                  : variant == 3 ? StepConfig{0, 28, 1, kPgsGroups}
                  : variant == 2 ? StepConfig{2, nv <= 20 ? 20 : 28, 1, kBigGroups}
-                                : StepConfig{solver == 2 ? 2 : 0, nv <= 28 ? 28 : 32, 0, 1};
+                                : StepConfig{M.solver == 2 ? 2 : 0, nv <= 28 ? 28 : 32, 0, 1};
   // a model with friction rows: the FRIC instantiation of the full kernel - there is no lean, size-specialised, two-envs-per-wave, staged,
   // RK4 or body-acceleration one (the latter three are refused before a launch: hb_batch_create, hb_body_acc_readout)
-  c.fric = fric ? 1 : 0;
+  c.fric = M.nfric ? 1 : 0;
   if (pass == StepPass::Inverse) {
     c.solver = 2; c.defer = c.coll ? 2 : 0; c.inv = 1;
     return {find_step_kernel(c), false, M_dev, shmem};
   }
   // RK4: the full kernel of the solver and dense order, whatever the launch looks like (no staged, lean, size-specialised or
   // two-envs-per-wave instantiation has it; a staged model is refused when its batch is created)
-  if (integrator != 0) {
-    c.integ = integrator;
+  if (M.integrator != 0) {
+    c.integ = M.integrator;
     c.acc = P.body_acc ? 1 : 0;
     return {variant == 0 && pass == StepPass::Main ? find_step_kernel(c) : nullptr, false, M_dev, shmem};
   }
@@ -2396,16 +2375,15 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, int variant,
 }
 // The one launch site.  Every launch hands back its kernel's name (hb_last_kernel: tests and bench.py name the kernel they measured by
 // what the library says it launched, not by a literal).
-static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, int variant, int solver, int integrator, int nv, int fric, size_t shmem, const BatchPtrs& P, int nsteps, hipStream_t stream,
-                              const char** kernel) {
-  const StepChoice s = select_step(pass, M_dev, variant, solver, integrator, nv, fric, shmem, P, nsteps);
+static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, const DevModel& M, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel) {
+  const StepChoice s = select_step(pass, M_dev, M, P, nsteps);
   if (s.duo) return launch_step_duo(s.M_dev, P, nsteps, stream, kernel);
   if (!s.kernel) return hipErrorInvalidDeviceFunction;
   (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
   // (the second pass of a staged step: kRerunWaves waves that walk the list of deferred envs - HB_STEP_OR_RERUN)
   constexpr int kRerunWaves = 1024;  // (one per SIMD: the four-group kernels hold one wave per SIMD)
   const int grid = (s.kernel->rerun && P.stage.rerun && P.stage.defer_list && P.nblk > kRerunWaves) ? kRerunWaves : P.nblk;
-  void* args[] = {(void*)&s.M_dev, (void*)&P, &nsteps};  // (passed by value, as ever; the inverse kernels take the first two)
+  void* args[] = {(void*)&s.M_dev, (void*)&P, &nsteps};  // (passed by value, as ever)
   *kernel = s.kernel->name;
   (void)hipLaunchKernel(s.kernel->fn, dim3(grid), dim3(kGroup), args, s.shmem, stream);
   return hipGetLastError();
@@ -2417,20 +2395,20 @@ static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, int variant,
 // steps); two-envs-per-wave waves, for the models that have that kernel: up to twice as many envs (4096: 67 against 78).  Beyond one
 // round a multi-step launch is no faster than pipelined single steps, and slower when its last round is part empty (4608 envs: 104
 // against 85) - profiles/r04_fold_sizes_by_batch.txt.
-bool fold_pays(int variant, int solver, int integrator, int nv, int fric, const BatchPtrs& P) {
-  if (variant != 0 || fric) return false;  // (a model with friction rows: single-step launches of its full kernel, as they are tested)
+bool fold_pays(const DevModel& M, const BatchPtrs& P) {
+  if (M.variant != 0 || M.nfric) return false;  // (a model with friction rows: single-step launches of its full kernel, as they are tested)
   if (P.n_env <= wave_slots()) return true;
   // (would the folded launch be a duo launch?  Step calls that read the constraint forces out are not folded onto it)
-  const bool duo_kernel = !P.qfrc_out && select_step(StepPass::Main, nullptr, variant, solver, integrator, nv, fric, 0, P, 2).duo;
+  const bool duo_kernel = !P.qfrc_out && select_step(StepPass::Main, nullptr, M, P, 2).duo;
   return duo_kernel && (P.n_env + 1) / 2 <= wave_slots();
 }
 
 // One step launch of the classic variant covers all nsteps.  A general variant with stage buffers runs every step as three launches
 // on the same stream: poses + work items, narrowphase (a small kernel at 2-4x the step kernel's occupancy: its time is chains of
 // dependent loads along the hulls' edge graphs), then the step kernel, which appends the results instead of colliding.
-hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integrator, int nv, int fric, int lds_floats, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel) {
-  const size_t shmem = (size_t)lds_floats * sizeof(float);
-  if (variant == 0 || !P.stage.result) return launch_pass(StepPass::Main, M_dev, variant, solver, integrator, nv, fric, shmem, P, nsteps, stream, kernel);
+hipError_t launch_step(const DevModel* M_dev, const DevModel& M, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel) {
+  const int variant = M.variant;
+  if (variant == 0 || !P.stage.result) return launch_pass(StepPass::Main, M_dev, M, P, nsteps, stream, kernel);
   for (int t = 0; t < nsteps; t++) {
     BatchPtrs Q = P;
     Q.t0 = P.t0 + t;
@@ -2447,11 +2425,11 @@ hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integ
     const bool fast = variant == 1 ? Q.stage.defer != nullptr : Q.stage.dm_fast != nullptr;
     const char* second = nullptr;  // (a staged step is named after its fast-pass kernel: the one that steps almost every env)
     if (fast) {
-      e = launch_pass(StepPass::Fast, M_dev, variant, solver, integrator, nv, fric, shmem, Q, 1, stream, kernel);
+      e = launch_pass(StepPass::Fast, M_dev, M, Q, 1, stream, kernel);
       if (e != hipSuccess) return e;
       Q.stage.rerun = 1;
     }
-    e = launch_pass(StepPass::Main, M_dev, variant, solver, integrator, nv, fric, shmem, Q, 1, stream, fast ? &second : kernel);
+    e = launch_pass(StepPass::Main, M_dev, M, Q, 1, stream, fast ? &second : kernel);
     if (e != hipSuccess) return e;
     // a long rollout is one call: refresh the heavy-first orders of its launches along the way (the caller does it between calls)
     if (P.order && P.order2 && (t & 7) == 7 && t + 1 < nsteps) {
@@ -2465,12 +2443,12 @@ hipError_t launch_step(const DevModel* M_dev, int variant, int solver, int integ
 
 // Inverse dynamics of every env in the launch (hb_inverse_dev): a general variant's poses and narrowphase first, as in a staged step,
 // then the inverse instantiation of the variant's row capacity
-hipError_t launch_inverse(const DevModel* M_dev, int variant, int nv, int fric, int lds_floats, const BatchPtrs& P, hipStream_t stream, const char** kernel) {
-  if (variant != 0) {
+hipError_t launch_inverse(const DevModel* M_dev, const DevModel& M, const BatchPtrs& P, hipStream_t stream, const char** kernel) {
+  if (M.variant != 0) {
     const hipError_t e = launch_pose_narrow(M_dev, P, stream);
     if (e != hipSuccess) return e;
   }
-  return launch_pass(StepPass::Inverse, M_dev, variant, /*solver=*/2, /*integrator=*/0, nv, fric, (size_t)lds_floats * sizeof(float), P, 1, stream, kernel);
+  return launch_pass(StepPass::Inverse, M_dev, M, P, 1, stream, kernel);
 }
 // every step and inverse instantiation: a layout over 64 KB must launch whichever of them the dispatch picks
 hipError_t set_step_lds_limit(int bytes) {

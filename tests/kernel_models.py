@@ -6,10 +6,37 @@ the floor, so that a state's contacts and limit rows stay inside the classic ker
 
 perturbed_hbm writes a copy of a compiled .hbm with other masses, inertias, joint axes, ranges, damping, geom sizes and gears but the same
 sizes: a model that still takes the size-specialised kernels (hb_api.cpp: sized_h27 / sized_team).
+
+kernel_table reads the step kernels' table (hb_step.hip: HB_KERNELS) for the CPU tests that hold its rows to what they must be.
 """
+import os
+import re
+
 import numpy as np
 
-from oracle_lib import Oracle, load_state
+from oracle_lib import ROOT, Oracle, load_state
+
+# the columns of a row of HB_KERNELS behind the name: step_body's template arguments (the configuration the dispatch looks a kernel up
+# by), then the launch attributes
+CONFIG_COLUMNS = ("SOLVER", "NDENSE", "COLL", "NG", "DEFER", "LEAN", "SIZED", "INV", "INTEG", "ACC", "FRIC")
+KERNEL_COLUMNS = CONFIG_COLUMNS + ("WAVES", "VGPRS", "RERUN")
+
+
+def kernel_table():
+    """hb_step.hip's kernel table in row order: [(name, {column: the cell's text})]"""
+    lines = open(os.path.join(ROOT, "humanoid_mujoco_amd", "csrc", "hb_step.hip")).read().split("\n")
+    first = lines.index(next(ln for ln in lines if ln.startswith("#define HB_KERNELS(K)")))
+    last = next(k for k in range(first, len(lines)) if not lines[k].rstrip().endswith("\\"))  # the macro's last line has no continuation
+    rows = []
+    for ln in lines[first + 1:last + 1]:
+        m = re.match(r"\s*K\((\w+),([^)]*)\)", ln)
+        if m:
+            cells = [c.strip() for c in m.group(2).split(",")]
+            assert len(cells) == len(KERNEL_COLUMNS), ln
+            rows.append((m.group(1), dict(zip(KERNEL_COLUMNS, cells))))
+        else:
+            assert ln.strip().startswith("/*"), ln  # (only rows and comments)
+    return rows
 
 CNSTR_LIMIT_JOINT, CNSTR_CONTACT_FRICTIONLESS, CNSTR_CONTACT_PYRAMIDAL = 3, 5, 6  # (oracle/mjstep_oracle.c: mjmodel.h:256-265)
 HFIELD_ELEV = np.array([[0.0, 0.3, 0.1, 0.6, 0.2],

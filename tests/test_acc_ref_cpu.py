@@ -14,7 +14,7 @@ import numpy as np
 
 import acc_ref
 import rk4_ref
-from kernel_models import chain_xml, oracle_for, rollout_states
+from kernel_models import KERNEL_COLUMNS, chain_xml, kernel_table, oracle_for, rollout_states
 from oracle_lib import GOLDEN, HUMANOID_HBM, ROOT, Oracle, load_state
 
 MODELS = os.path.join(ROOT, "tests", "models")
@@ -183,20 +183,16 @@ def test_spinning_hinge_reads_the_centripetal_acceleration(hbmod, tmp_path):
 
 
 def test_every_full_kernel_has_a_twin_with_the_readout():
-    """hb_step.hip's kernel lists: the read-out's instantiations (HB_ACC_KERNELS, HB_ACC_RK4_KERNELS) repeat, parameter for parameter,
-    exactly the rows of the step and RK4 lists that are full kernels (LEAN = 0, INV = 0) - so that a launch with the read-out finds its
-    kernel whatever the model - under names the step-kernel matrix does not collect; tests/test_gpu_body_acc.py names the ones it runs"""
+    """hb_step.hip's kernel table (HB_KERNELS): the read-out's instantiations (ACC = 1) repeat, parameter for parameter, exactly the
+    rows that are full kernels (LEAN = 0, INV = 0, FRIC = 0) of the same INTEG - so that a launch with the read-out finds its kernel
+    whatever the model - under names the step-kernel matrix does not collect; tests/test_gpu_body_acc.py names the ones it runs"""
     import test_gpu_body_acc as tg
-    src = open(os.path.join(ROOT, "humanoid_mujoco_amd", "csrc", "hb_step.hip")).read()
 
-    def rows(macro):
-        lines = src[src.index("#define %s(K)" % macro):].split("\n")
-        end = next(k for k, ln in enumerate(lines) if not ln.rstrip().endswith("\\"))  # the macro's last line has no continuation
-        body = "\n".join(lines[:end + 1])
-        return {m.group(1): tuple(x.strip() for x in m.group(2).split(",")) for m in re.finditer(r"^\s*K\((\w+),([^)]*)\)", body, re.M)}
-    full = {n: r for n, r in rows("HB_STEP_KERNELS").items() if r[5] == "0" and r[7] == "0"}
-    rk4 = rows("HB_RK4_KERNELS")
-    acc, acc_rk4 = rows("HB_ACC_KERNELS"), rows("HB_ACC_RK4_KERNELS")
+    def rows(integ, acc):  # (every column but ACC itself)
+        return {n: tuple(c[k] for k in KERNEL_COLUMNS if k != "ACC") for n, c in kernel_table()
+                if c["INTEG"] == integ and c["ACC"] == acc and (acc == "1" or (c["LEAN"] == "0" and c["INV"] == "0" and c["FRIC"] == "0"))}
+    full, rk4 = rows("0", "0"), rows("1", "0")
+    acc, acc_rk4 = rows("0", "1"), rows("1", "1")
     assert len(full) == 12 and len(rk4) == 4
     assert {n.replace("hb_step", "hb_acc", 1): r for n, r in full.items()} == acc
     assert {n.replace("hb_rk4", "hb_acc_rk4", 1): r for n, r in rk4.items()} == acc_rk4

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import fric_ref
-from kernel_models import CNSTR_LIMIT_JOINT, chain_xml, oracle_for, oracle_steps, rollout_states, row_kinds
+from kernel_models import CNSTR_LIMIT_JOINT, chain_xml, kernel_table, oracle_for, oracle_steps, rollout_states, row_kinds
 from oracle_lib import ROOT, Oracle, load_state, parse_hbm
 from test_gpu_fric import MODELS, add_friction, fric_chain_xml, pendulum_xml, reference
 from test_gpu_kernel_matrix import _kernel_names_in_source
@@ -174,11 +174,9 @@ def test_gpu_state_sets_cover_the_zones(hbmod, fric_tmp):
 
 
 def test_kernel_list():
-    src = open(os.path.join(CSRC, "hb_step.hip")).read()
-    block = re.search(r"#define HB_FRIC_KERNELS\(K\).*?\n((?:\s*K\(.*\n?)+)", src).group(1)
-    names = re.findall(r"K\((\w+),", block)
+    names = [n for n, c in kernel_table() if c["FRIC"] == "1"]
     assert names == FRIC_KERNELS, names
     assert not any(re.fullmatch(r"hb_step\w*_kernel", n) for n in names)
     assert not set(names) & _kernel_names_in_source()
-    init = re.search(r"kStepKernels\[\] = \{(.*?)\};", src, re.S).group(1)
-    assert "HB_FRIC_KERNELS(" in init
+    src = open(os.path.join(CSRC, "hb_step.hip")).read()
+    assert re.search(r"kStepKernels\[\] = \{(.*?)\};", src, re.S).group(1) == "HB_KERNELS(HB_ROW)"  # (every row of the table)

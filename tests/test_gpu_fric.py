@@ -1,4 +1,4 @@
-"""Joint friction loss on the GPU (step_body's FRIC instantiations, hb_step.hip: HB_FRIC_KERNELS) against the fp64 reference of
+"""Joint friction loss on the GPU (step_body's FRIC instantiations, hb_step.hip: the FRIC rows of HB_KERNELS) against the fp64 reference of
 tests/fric_ref.py: the oracle's forward pass with the friction rows stacked in front and the two-sided force bound.
 
 Models: the capsule chains of tests/kernel_models.py at the two dense orders (nv 28 and 32), PGS condim 3 and Newton condim 1, with

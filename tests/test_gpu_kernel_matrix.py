@@ -24,7 +24,7 @@ import numpy as np
 import pytest
 
 from inverse_ref import force_scale, forward_at, inverse_terms
-from kernel_models import chain_xml, oracle_for, oracle_steps, perturbed_hbm, rollout_states, row_kinds
+from kernel_models import CONFIG_COLUMNS, chain_xml, kernel_table, oracle_for, oracle_steps, perturbed_hbm, rollout_states, row_kinds
 from oracle_lib import HUMANOID_HBM, ROOT, Oracle, load_state, prove_rounding_fence
 
 ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
@@ -129,11 +129,10 @@ NOT_BIT_IDENTICAL = ("staged", "fastpass")  # knobs that select another algorith
 
 
 def _kernel_names_in_source():
-    names = set()
+    names = {n for n, _ in kernel_table() if re.fullmatch(r"hb_step\w*_kernel", n)}  # rows of hb_step.hip's kernel table
     for f in ("hb_step.hip", "hb_step_duo.hip"):
         src = open(os.path.join(CSRC, f)).read()
         names |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(hb_step\w*_kernel)\s*\(", src))  # defined by hand (the duo kernels)
-        names |= set(re.findall(r"^\s*K\((hb_step\w*_kernel),", src, re.M))  # rows of hb_step.hip's kernel table
     return names
 
 
@@ -144,6 +143,17 @@ def test_table_names_every_step_kernel():
     src = _kernel_names_in_source()
     assert len(src) >= 25
     assert src == table | DUO_KERNELS, (sorted(src - table - DUO_KERNELS), sorted(table - src))
+
+
+def test_kernel_table_rows_are_unique():
+    """(CPU) the dispatch takes the first row whose configuration matches (hb_step.hip: find_step_kernel), so a second row with the same
+    eleven configuration columns would be shadowed silently, and a second row with the same name would not even be a second kernel"""
+    rows = kernel_table()
+    assert len(rows) >= 55
+    names = [n for n, _ in rows]
+    configs = [tuple(c[k] for k in CONFIG_COLUMNS) for _, c in rows]
+    assert len(set(names)) == len(names), sorted(n for n in set(names) if names.count(n) > 1)
+    assert len(set(configs)) == len(configs), sorted(n for (n, _), c in zip(rows, configs) if configs.count(c) > 1)
 
 
 def test_generated_models_stay_inside_the_engine_and_reach_their_rows(hbmod, tmp_path):

@@ -1,4 +1,4 @@
-"""The RK4 integrator (mjINT_RK4; hb_step.hip: step_body's INTEG, the HB_RK4_KERNELS list) on the GPU, against the fp64 reference of
+"""The RK4 integrator (mjINT_RK4; hb_step.hip: step_body's INTEG, the INTEG rows of HB_KERNELS) on the GPU, against the fp64 reference of
 tests/rk4_ref.py (the RK4 recurrence restated over the oracle's mj_forward).
 
 KERNELS names every RK4 kernel and the model that must run it (Batch.last_kernel): the benchmark humanoid under PGS/50 and Newton/100,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-step time of the friction-loss kernels (hb_step.hip: HB_FRIC_KERNELS) against the full kernels of the same chain without the
+"""Per-step time of the friction-loss kernels (hb_step.hip: the FRIC rows of HB_KERNELS) against the full kernels of the same chain without the
 joints' frictionloss, 4096 envs, PGS/50 condim 3 and Newton/100 condim 1 on the nv = 28 capsule chain of tests/kernel_models.py with
 the friction attributes of tests/test_gpu_fric.py.  Both batches start from ONE state - the plain chain pre-rolled 300 untimed steps
 of the Halton workload from the perturbed reset, onto the floor - and run 20 warm-up and 200 timed hb_step_dev calls under the same
