@@ -474,6 +474,53 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
     for (int i = 0; i < 4; i++) r[12 + i] = (float)pair_solimp[5 * p + i];
     r[16] = (float)pair_solimp[5 * p + 4]; r[17] = fi(pair_dim[p]);
   }
+  // Equality rows (mj_instantiateEquality): the rows in front of the friction rows, in the order of the model's equalities - one per active
+  // joint coupling, three (world x, y, z) per active connect - unless the options disable them: then the model is an ordinary one.  Per row
+  // a 7-quad record (kErecQuads):
+  //   joint:    [0] 0, -, qposadr1, qposadr2 (-1: none)   [1] dof1, dof2, qpos0 of joint1, of joint2   [2] polycoef[0..3]   [3] polycoef[4]
+  //   connect:  [0] 1, axis, body1, body2   [1] tree1, tree2   [2] dof mask of body1 (lo, hi), of body2 (lo, hi)   [3] anchor in body1's frame
+  //             [4].xyz anchor in body2's frame
+  //   both:     [4].w diagApprox   [5] solref[2], solimp[0..1]   [6] solimp[2..4]
+  std::vector<float> erec;
+  if (!(m.disableflags & (DSBL_CONSTRAINT | DSBL_EQUALITY))) {
+    for (int e = 0; e < m.neq(); e++) {
+      if (!m.eq_active0[e]) continue;
+      const double* d = &m.eq_data[(size_t)kEqData * e];
+      const int o1 = m.eq_obj1id[e], o2 = m.eq_obj2id[e];
+      const int nrow = m.eq_type[e] == EQ_JOINT ? 1 : 3;
+      for (int a = 0; a < nrow; a++) {
+        float r[4 * kErecQuads] = {0};
+        if (m.eq_type[e] == EQ_JOINT) {
+          const int q1 = m.jnt_qposadr[o1], q2 = o2 >= 0 ? m.jnt_qposadr[o2] : -1;
+          r[0] = fi(0); r[2] = fi(q1); r[3] = fi(q2);
+          r[4] = fi(m.jnt_dofadr[o1]); r[5] = fi(o2 >= 0 ? m.jnt_dofadr[o2] : 0); r[6] = (float)m.qpos0[q1]; r[7] = o2 >= 0 ? (float)m.qpos0[q2] : 0.f;
+          for (int i = 0; i < 5; i++) r[8 + i] = (float)d[i];
+          r[19] = (float)(m.dof_invweight0[m.jnt_dofadr[o1]] + (o2 >= 0 ? m.dof_invweight0[m.jnt_dofadr[o2]] : 0.0));
+        } else {
+          r[0] = fi(1); r[1] = fi(a); r[2] = fi(o1); r[3] = fi(o2);
+          r[4] = fi(treeid[o1]); r[5] = fi(treeid[o2]);
+          r[8] = fi((int)(dofmask[o1] & 0xffffffffull)); r[9] = fi((int)(dofmask[o1] >> 32));
+          r[10] = fi((int)(dofmask[o2] & 0xffffffffull)); r[11] = fi((int)(dofmask[o2] >> 32));
+          for (int i = 0; i < 3; i++) { r[12 + i] = (float)d[i]; r[16 + i] = (float)d[3 + i]; }
+          r[19] = (float)(m.body_invweight0[2 * o1] + m.body_invweight0[2 * o2]);
+        }
+        r[20] = (float)m.eq_solref[2 * e]; r[21] = (float)m.eq_solref[2 * e + 1];
+        for (int i = 0; i < 5; i++) r[22 + i] = (float)m.eq_solimp[5 * e + i];
+        erec.insert(erec.end(), r, r + 4 * kErecQuads);
+      }
+    }
+  }
+  dm.neq_rows = (int)erec.size() / (4 * kErecQuads);
+  if (dm.neq_rows && dm.variant != 0) {
+    err = "equality constraints: only models that step in one kernel (plane / sphere / capsule geoms, condim 1 / 3) are implemented; this model steps in stages (mesh hulls, height fields or condim 4 / 6): remove the <equality> section or set <flag equality=\"disable\"/>";
+    return false;
+  }
+  if (dm.neq_rows && m.integrator == INT_RK4) { err = "equality constraints: the RK4 integrator is not implemented for a model with equality rows: use the Euler integrator"; return false; }
+  if (dm.neq_rows && dm.neq_rows + dm.nfric > 32) {
+    err = "equality constraints: " + std::to_string(dm.neq_rows) + " equality rows and " + std::to_string(dm.nfric) + " friction-loss rows: a model may have at most 32 always-active rows";
+    return false;
+  }
+  if (erec.empty()) erec.assign(4 * kErecQuads, 0.f);
   // per collision pair, what mj_collision needs of it in one 3-quad record (one vector fetch per lane and round):
   // [0] geom1, geom2, type1 | type2 << 8, margin   [1] rbound1, rbound2, size1[0], size1[1]   [2] size2[0], size2[1], -, -
   std::vector<float> crec((size_t)(std::max(1, m.npair) + 64) * 12, 0.f);  // + one round of padding for the prefetch
@@ -563,7 +610,7 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
   const size_t o_meshv = T.addraw(meshv), o_meshn = T.addraw(meshn), o_meshs = T.addraw(meshs);
   const size_t o_arec = T.addraw(arec);
   size_t o_brec = T.addraw(brec), o_drec = T.addraw(drec), o_mdiag = T.addraw(mdiag), o_prec = T.addraw(prec), o_crec = T.addraw(crec), o_trec = T.addraw(trec),
-         o_lrec = T.addraw(lrec), o_frec = T.addraw(frec);
+         o_lrec = T.addraw(lrec), o_frec = T.addraw(frec), o_erec = T.addraw(erec);
 
   // ---- upload
   if (D.d_int.alloc(T.iv.size()) != HB_OK || D.d_flt.alloc(T.fv.size()) != HB_OK || D.d_u64.alloc(T.uv.size()) != HB_OK) { err = "hipMalloc failed for model tables"; return false; }
@@ -580,6 +627,7 @@ bool build_device_model(const Model& m, DeviceModel& D, std::string& err) {
   dm.trec = reinterpret_cast<const float4*>(D.d_flt + o_trec);
   dm.lrec = reinterpret_cast<const float4*>(D.d_flt + o_lrec);
   dm.frec = reinterpret_cast<const float4*>(D.d_flt + o_frec);
+  dm.erec = reinterpret_cast<const float4*>(D.d_flt + o_erec);
   D.obs_jnt_joint = dm.obs_jnt; D.obs_src_joint = dm.obs_src;
   D.obs_jnt_act = D.d_int + o_obs_jnt_act; D.obs_src_act = D.d_int + o_obs_src_act;
   dm.arec = reinterpret_cast<const float4*>(D.d_flt + o_arec);
@@ -1078,9 +1126,23 @@ int hb_model_name2id(const hb_model* h, const char* kind, const char* name) {
   std::string k = kind;
   if (k == "body") v = &m.body_name; else if (k == "joint") v = &m.jnt_name; else if (k == "geom") v = &m.geom_name;
   else if (k == "actuator") v = &m.actuator_name; else if (k == "tendon") v = &m.tendon_name; else if (k == "key") v = &m.key_name;
+  else if (k == "equality") v = &m.eq_name;
   if (!v) return -1;
   for (size_t i = 0; i < v->size(); i++) if ((*v)[i] == name) return (int)i;
   return -1;
+}
+
+int hb_model_id2name(const hb_model* h, const char* kind, int id, char* out, int cap) {
+  if (!h || !kind || !out || cap <= 0) return HB_EINVAL;
+  const Model& m = h->m;
+  const std::vector<std::string>* v = nullptr;
+  const std::string k = kind;
+  if (k == "body") v = &m.body_name; else if (k == "joint") v = &m.jnt_name; else if (k == "geom") v = &m.geom_name;
+  else if (k == "actuator") v = &m.actuator_name; else if (k == "tendon") v = &m.tendon_name; else if (k == "key") v = &m.key_name;
+  else if (k == "equality") v = &m.eq_name;
+  if (!v || id < 0 || (size_t)id >= v->size() || (*v)[id].size() >= (size_t)cap) return HB_EINVAL;
+  memcpy(out, (*v)[id].c_str(), (*v)[id].size() + 1);
+  return (int)(*v)[id].size();
 }
 
 int hb_model_get_array(const hb_model* h, const char* field, double* out, int cap) {
@@ -1784,7 +1846,7 @@ static int sensor_setup(hb_batch* b, const hb_sensor_spec* spec, int T, BatchPtr
   const Model& m = b->model->m;
   const int ns = hb_sensor_size(spec);
   if (ns <= 0) return HB_EINVAL;
-  if (spec->n_imu + spec->n_frameacc > 0 && b->D.dm.nfric) return HB_EUNSUPPORTED;  // (friction loss: no kernel with the body-acceleration read-out)
+  if (spec->n_imu + spec->n_frameacc > 0 && (b->D.dm.nfric || b->D.dm.neq_rows)) return HB_EUNSUPPORTED;  // (friction loss, equality rows: no kernel with the body-acceleration read-out)
   for (int k = 0; k < spec->n_framepos; k++) if (spec->framepos_body[k] < 0 || spec->framepos_body[k] >= m.nbody) return HB_EINVAL;
   int tree = -1;
   if (spec->subtree_body >= 0) {
@@ -2686,7 +2748,7 @@ int hb_contact_readout_dev(hb_batch* b, const float** contact_force_dev, const f
 int hb_body_acc_readout(hb_batch* b, int on) {
   if (!b) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
-  if (on && b->D.dm.nfric) return HB_EUNSUPPORTED;  // (a model with friction loss: no step kernel has both the friction rows and this read-out)
+  if (on && (b->D.dm.nfric || b->D.dm.neq_rows)) return HB_EUNSUPPORTED;  // (a model with friction loss or equality rows: no step kernel has both those rows and this read-out)
   (void)main_stream(b);  // from the next launch on: step calls held back are launched as they were made
   if (on && alloc_body_acc_readout(b) != HB_OK) return HB_ENOMEM;
   b->body_acc_readout = on != 0;

@@ -141,7 +141,12 @@ struct DevModel {
   // options), and per row (dof, frictionloss, R, B) as build_device_model works them out.  Read by step_body's FRIC instantiations only.
   int nfric;
   const float4 HB_CONST* frec;
+  // equality constraints: the rows in front of the friction rows, one per active joint coupling and three per active connect (0: a model
+  // without them, or disabled by the options), and per row a kErecQuads record (hb_api.cpp).  Read by step_body's FRIC == 2 instantiations only.
+  int neq_rows;
+  const float4 HB_CONST* erec;
 };
+constexpr int kErecQuads = 7;
 
 typedef const DevModel HB_CONST& DevModelRef;
 

@@ -15,6 +15,8 @@ enum JointType { JNT_FREE = 0, JNT_BALL = 1, JNT_SLIDE = 2, JNT_HINGE = 3 };    
 enum GeomType { GEOM_PLANE = 0, GEOM_HFIELD = 1, GEOM_SPHERE = 2, GEOM_CAPSULE = 3, GEOM_ELLIPSOID = 4, GEOM_CYLINDER = 5, GEOM_BOX = 6, GEOM_MESH = 7 };   // mjmodel.h:94-103
 enum Solver { SOL_PGS = 0, SOL_CG = 1, SOL_NEWTON = 2 };                                // mjmodel.h:159-163
 enum Integrator { INT_EULER = 0, INT_RK4 = 1, INT_IMPLICIT = 2, INT_IMPLICITFAST = 3 };  // mjmodel.h:138-143
+enum EqType { EQ_CONNECT = 0, EQ_WELD = 1, EQ_JOINT = 2, EQ_TENDON = 3 };                                      // mjmodel.h: mjtEq
+constexpr int kEqData = 11;                                                                                   // mjNEQDATA
 enum DisableBit {                                                                      // mjmodel.h:50-68
   DSBL_CONSTRAINT = 1 << 0, DSBL_EQUALITY = 1 << 1, DSBL_FRICTIONLOSS = 1 << 2, DSBL_LIMIT = 1 << 3,
   DSBL_CONTACT = 1 << 4, DSBL_PASSIVE = 1 << 5, DSBL_GRAVITY = 1 << 6, DSBL_CLAMPCTRL = 1 << 7,
@@ -58,6 +60,12 @@ struct Model {
     if (dof_solref_friction.empty()) for (int d = 0; d < nv; d++) { dof_solref_friction.push_back(0.02); dof_solref_friction.push_back(1); }
     if (dof_solimp_friction.empty()) for (int d = 0; d < nv; d++) for (double v : si) dof_solimp_friction.push_back(v);
   }
+  // ---- equality constraints (mjmodel.h: eq_*): scalar-joint couplings and connect anchors.  Optional records of the .hbm format: written
+  // only by a model that has an <equality> section; neq is the length of eq_type.  eq_data, 11 per element: a joint's polycoef[5], or a
+  // connect's anchor in body1's frame [3] | the same point in body2's frame at qpos0 [3]; the rest zero
+  veci eq_type, eq_obj1id, eq_obj2id, eq_active0;
+  vecd eq_data, eq_solref, eq_solimp;
+  int neq() const { return (int)eq_type.size(); }
   // ---- geoms (mjmodel.h:729-760)
   veci geom_type, geom_bodyid, geom_contype, geom_conaffinity, geom_condim, geom_priority,
       geom_dataid;
@@ -89,7 +97,7 @@ struct Model {
   vecd qpos0, qpos_spring, key_qpos;
 
   // ---- names
-  std::vector<std::string> body_name, jnt_name, geom_name, tendon_name, actuator_name, key_name, mesh_name;
+  std::vector<std::string> body_name, jnt_name, geom_name, tendon_name, actuator_name, key_name, mesh_name, eq_name;
 
   // Order of the candidate collision pairs = order in which mj_collision emits contacts (it changes nothing physical, but PGS cut at a
   // finite sweep count depends on it: DESIGN.md 2).  1 (what the MJCF compiler writes): body pairs ascending, inside a body pair the geoms of
@@ -117,6 +125,9 @@ struct Model {
     HB_F(dof_bodyid); HB_F(dof_jntid); HB_F(dof_parentid); HB_F(dof_Madr);
     HB_F(dof_armature); HB_F(dof_damping); HB_F(dof_frictionloss); HB_F(dof_invweight0); HB_F(dof_M0);
     if (f.optional(has_frictionloss())) { HB_F(dof_solref_friction); HB_F(dof_solimp_friction); }  // (a writer: only when present)
+    if (f.optional(neq() > 0)) {
+      HB_F(eq_type); HB_F(eq_obj1id); HB_F(eq_obj2id); HB_F(eq_active0); HB_F(eq_data); HB_F(eq_solref); HB_F(eq_solimp); HB_F(eq_name);
+    }
     HB_F(geom_type); HB_F(geom_bodyid); HB_F(geom_contype); HB_F(geom_conaffinity); HB_F(geom_condim);
     HB_F(geom_priority); HB_F(geom_dataid);
     HB_F(geom_size); HB_F(geom_pos); HB_F(geom_quat); HB_F(geom_rbound); HB_F(geom_friction);

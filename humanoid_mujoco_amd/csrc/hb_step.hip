@@ -57,6 +57,13 @@ __device__ __forceinline__ void defer_env(const BatchPtrs& P, int env) {
 // whose force is bounded on both sides, -frictionloss <= f <= frictionloss.  In the dual (PGS) the row's max becomes a clamp; in the primal
 // (Newton, mj_inverse) the row's cost has three zones: quadratic inside |jar| < R frictionloss, linear with the force at its bound outside.
 // Every line of it sits behind FRIC: the instantiations a model without friction loss runs are the code they were (HB_KERNELS: the FRIC rows).
+// FRIC == 2: equality rows (mj_instantiateEquality: scalar-joint couplings, one row, and connect anchors, three rows) in front of the friction
+// rows.  Always active like those, but with a general Jacobian, a reference that depends on the violation (the ordinary per-row path, with a
+// pos of either sign) and no bound on the force: the clamp's ends are -inf and +inf, the row is in the quadratic zone wherever jar is.
+// what a lane keeps of its equality row between the kinematics and makeConstraint (FRIC == 2): the number of rows, the head of the row's
+// record, a connect's two anchor points in world coordinates
+template <bool ON> struct EqLane { int ne = 0; float4 r0 = {0.f, 0.f, 0.f, 0.f}; V3 p1 = {0.f, 0.f, 0.f}, p2 = {0.f, 0.f, 0.f}; };
+template <> struct EqLane<false> { static constexpr int ne = 0; };
 template <int SOLVER, int NDENSE, int COLL = 0, int NG = 1, int DEFER = 0, int LEAN = 0, int SIZED = 0, int INV = 0, int INTEG = 0, int ACC = 0, int FRIC = 0>
 __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P, int nsteps_in, int env_in = -1) {
   const int nsteps = LEAN == 1 ? 1 : nsteps_in;  // (LEAN == 1 is launched for single steps only: the step API; rollouts take LEAN == 2)
@@ -343,6 +350,24 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       st3(s_xipos + 3 * myb, mypos + mrot(mat, {ip.x, ip.y, ip.z}));
     }
     gsync();
+    // equality rows (FRIC == 2 only; lane = row): the two anchor points of a connect row in world coordinates, taken here, while the body poses
+    // are still in LDS (region B, which makeConstraint fills, aliases them), and kept in registers until the rows are built
+    // (EqLane: empty, with the constant ne = 0, in every other instantiation - they hold no trace of it)
+    EqLane<FRIC == 2> eq;
+    if constexpr (FRIC == 2) {
+      eq.ne = M.neq_rows;
+      if (lane < eq.ne) {
+        const float4 HB_CONST* ER = M.erec + (size_t)lane * kErecQuads;
+        eq.r0 = ER[0];
+        if (__float_as_int(eq.r0.x) == 1) {
+          const float4 a1 = ER[3], a2 = ER[4];
+          const int b1 = __float_as_int(eq.r0.z), b2 = __float_as_int(eq.r0.w);
+          eq.p1 = ld3(s_xpq + kXpqStride * b1) + mrot(s_xmat + 9 * b1, {a1.x, a1.y, a1.z});
+          eq.p2 = ld3(s_xpq + kXpqStride * b2) + mrot(s_xmat + 9 * b2, {a2.x, a2.y, a2.z});
+        }
+      }
+    }
+    [[maybe_unused]] const int neq = eq.ne;
     HB_STAMP(2);
     // geoms: world position and z axis
     if (lane < HB_SZ(ngeom)) {
@@ -954,17 +979,76 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
         nefc = nefc_after;
       }
     } else {
+    if constexpr (FRIC == 2) {
+      // (-1) equality rows, in the order of the model's equalities (neq + nf <= 32: these rows always fit).  What a row needs besides its
+      // Jacobian goes through the ordinary row meta: pos (of either sign), margin 0, the element's solref / solimp, its diagApprox.
+      if (lane < neq) {
+        const float4 HB_CONST* ER = M.erec + (size_t)lane * kErecQuads;
+        const float4 e1 = ER[1], e4 = ER[4], e5 = ER[5], e6 = ER[6];
+        float pos;
+        if (__float_as_int(eq.r0.x) == 0) {
+          // a joint coupling: pos = dq1 - poly(dq2), J = e_dof1 - poly'(dq2) e_dof2 (without joint2: pos = dq1 - polycoef[0], J = e_dof1)
+          const float4 e2 = ER[2], e3 = ER[3];
+          const int qa2 = __float_as_int(eq.r0.w);
+          float* Jr = s_C + lane * cs;
+          for (int k = 0; k < cs; k++) Jr[k] = 0.f;
+          Jr[__float_as_int(e1.x)] = 1.f;
+          float poly = e2.x;
+          if (qa2 >= 0) {
+            const float dq2 = s_qpos[qa2] - e1.w;
+            poly = e2.x + dq2 * (e2.y + dq2 * (e2.z + dq2 * (e2.w + dq2 * e3.x)));
+            Jr[__float_as_int(e1.y)] -= e2.y + dq2 * (2.f * e2.z + dq2 * (3.f * e2.w + dq2 * 4.f * e3.x));
+          }
+          pos = s_qpos[__float_as_int(eq.r0.z)] - e1.z - poly;
+        } else {
+          const V3 dp = eq.p1 - eq.p2;
+          const int ax = __float_as_int(eq.r0.y);
+          pos = ax == 0 ? dp.x : ax == 1 ? dp.y : dp.z;
+        }
+        float* e = s_efc + lane;
+        e[E_POS * kNR] = pos; e[E_MARGIN * kNR] = 0.f;
+        e[E_SOLREF0 * kNR] = e5.x; e[E_SOLREF1 * kNR] = e5.y;
+        e[(E_IMP0 + 0) * kNR] = e5.z; e[(E_IMP0 + 1) * kNR] = e5.w; e[(E_IMP0 + 2) * kNR] = e6.x; e[(E_IMP0 + 3) * kNR] = e6.y;
+        e[(E_IMP0 + 4) * kNR] = e6.z;
+        e[E_DA * kNR] = e4.w; e[E_DAFIRST * kNR] = e4.w; e[E_MU2 * kNR] = 0.f;
+      }
+      // the Jacobian of a connect row, J = jacp(body1, p1) - jacp(body2, p2) along its world axis: uniform loop over the rows, lanes over
+      // dofs, as for the contacts below (the anchor points come out of the lane that owns the row; the record by scalar loads)
+      for (int i = 0; i < neq; i++) {
+        const float4 HB_CONST* ER = M.erec + (size_t)i * kErecQuads;
+        const float4 r0 = ER[0];
+        if (__float_as_int(r0.x) != 1) continue;
+        const float4 r1 = ER[1], r2 = ER[2];
+        const int ax = __float_as_int(r0.y);
+        const unsigned long long m1 = ((unsigned long long)__float_as_uint(r2.y) << 32) | __float_as_uint(r2.x);
+        const unsigned long long m2 = ((unsigned long long)__float_as_uint(r2.w) << 32) | __float_as_uint(r2.z);
+        auto bcast = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i)); };
+        const V3 p1 = {bcast(eq.p1.x), bcast(eq.p1.y), bcast(eq.p1.z)}, p2 = {bcast(eq.p2.x), bcast(eq.p2.y), bcast(eq.p2.z)};
+        const V3 off1 = p1 - ld3(s_scom + 3 * __float_as_int(r1.x)), off2 = p2 - ld3(s_scom + 3 * __float_as_int(r1.y));
+        for (int d = lane; d < cs; d += kGroup) {
+          V3 jd = {0.f, 0.f, 0.f};
+          if (d < nv) {
+            float cdd[6];
+            ld_cdof(s_cdof, d, cdd);
+            const V3 ang = {cdd[0], cdd[1], cdd[2]}, lin = {cdd[3], cdd[4], cdd[5]};
+            if ((m1 >> d) & 1ull) jd = jd + lin + cross(ang, off1);
+            if ((m2 >> d) & 1ull) jd = jd - (lin + cross(ang, off2));
+          }
+          s_C[i * cs + d] = ax == 0 ? jd.x : ax == 1 ? jd.y : jd.z;
+        }
+      }
+    }
     if constexpr (FRIC) {
-      // (0) friction loss: a unit Jacobian row per dof that has it, in dof order (nf <= nv <= 32: these rows always fit)
+      // (0) friction loss: a unit Jacobian row per dof that has it, in dof order (neq + nf <= 32: these rows always fit)
       nf = M.nfric;
-      if (lane < nf) {
-        const float4 fr = M.frec[lane];
+      if ((FRIC != 2 || lane >= neq) && lane < neq + nf) {  // (FRIC 1: neq is the constant 0, and the test the one it was)
+        const float4 fr = M.frec[lane - neq];
         float* Jr = s_C + lane * cs;
         for (int k = 0; k < cs; k++) Jr[k] = 0.f;
         Jr[__float_as_int(fr.x)] = 1.f;
         fr_fl = fr.y; fr_R = fr.z; fr_B = fr.w;
       }
-      nefc = nf;
+      nefc = neq + nf;
     }
     // (a) limits: 2 candidates (lower, upper) per limited joint / tendon, in constraint order
     if (constraints_on && !(M_disableflags & (1 << 3))) {
@@ -1125,7 +1209,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
           Rg[g] = e[0];
           Ddg[g] = 1.f / Rg[g];
           arefg[g] = -e[2] * vel - e[1];
-        } else if (FRIC && row < nf) {  // (a friction row: R and B from the host, no row meta)
+        } else if (FRIC && (FRIC != 2 || row >= neq) && row < neq + nf) {  // (a friction row: R and B from the host, no row meta)
           Rg[g] = fr_R;
           Ddg[g] = 1.f / fr_R;
           arefg[g] = -fr_B * vel;
@@ -1149,9 +1233,11 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     const bool rowact = actg[0];
     float R = Rg[0], Dd = Ddg[0], aref = arefg[0], jw = jwg[0], force = 0.f, bvec = 0.f;
     (void)R; (void)bvec; (void)jw;
-    // FRIC: the force bounds of this lane's row: [-frictionloss, frictionloss] on a friction row, [0, inf) on every other
-    const bool fricrow = FRIC && lane < nf;
-    const float f_lo = fricrow ? -fr_fl : 0.f, f_hi = fricrow ? fr_fl : __builtin_inff();
+    // FRIC: the force bounds of this lane's row: [-frictionloss, frictionloss] on a friction row, (-inf, inf) on an equality row, [0, inf) on
+    // every other
+    // (the equality test is spelled out where it is used: one more local here changes the register allocation of instantiations without FRIC)
+    const bool fricrow = FRIC && (FRIC != 2 || lane >= neq) && lane < neq + nf;
+    const float f_lo = fricrow ? -fr_fl : (FRIC == 2 && lane < neq) ? -__builtin_inff() : 0.f, f_hi = fricrow ? fr_fl : __builtin_inff();
     (void)fricrow; (void)f_lo; (void)f_hi;
     gsync();
     if constexpr (INV) {
@@ -1613,7 +1699,11 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       const float f_Rfl = fr_R * fr_fl;
       (void)f_Rfl;
       // zone of this lane's row at jar = x: +1 / -1 the linear zone whose force is +fl / -fl, 0 quadratic (a friction row) or active (any other), 2 inactive
-      auto fzone = [&](float x) -> int { return fricrow ? (x <= -f_Rfl ? 1 : x >= f_Rfl ? -1 : 0) : (x < 0.f ? 0 : 2); };
+      // (an equality row: quadratic wherever jar is - its infinite bounds enter no product)
+      auto fzone = [&](float x) -> int {
+        if constexpr (FRIC == 2) { if (lane < neq) return 0; }
+        return fricrow ? (x <= -f_Rfl ? 1 : x >= f_Rfl ? -1 : 0) : (x < 0.f ? 0 : 2);
+      };
       auto fcost = [&](float x) -> float {
         const int z = fzone(x);
         return z == 0 ? 0.5f * Ddg[0] * x * x : z == 2 ? 0.f : fr_fl * (-0.5f * f_Rfl - (float)z * x);
@@ -2280,7 +2370,14 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   K(hb_fric_newton28_kernel,          2,      28,     0,    1,          0,     0,    0,     0,   0,     0,   1,    2,     0,     0)       \
   K(hb_fric_newton32_kernel,          2,      32,     0,    1,          0,     0,    0,     0,   0,     0,   1,    2,     0,     0)       \
   K(hb_fric_inverse_kernel,           2,      28,     0,    1,          0,     0,    0,     1,   0,     0,   1,    2,     0,     0)       \
-  K(hb_fric_inverse32_kernel,         2,      32,     0,    1,          0,     0,    0,     1,   0,     0,   1,    2,     0,     0)
+  K(hb_fric_inverse32_kernel,         2,      32,     0,    1,          0,     0,    0,     1,   0,     0,   1,    2,     0,     0)       \
+  /* equality rows in front of the friction rows (FRIC 2): the same six, for a model with active joint couplings or connect anchors    */ \
+  K(hb_eq_kernel,                     0,      28,     0,    1,          0,     0,    0,     0,   0,     0,   2,    2,     0,     0)       \
+  K(hb_eq32_kernel,                   0,      32,     0,    1,          0,     0,    0,     0,   0,     0,   2,    2,     0,     0)       \
+  K(hb_eq_newton28_kernel,            2,      28,     0,    1,          0,     0,    0,     0,   0,     0,   2,    2,     0,     0)       \
+  K(hb_eq_newton32_kernel,            2,      32,     0,    1,          0,     0,    0,     0,   0,     0,   2,    2,     0,     0)       \
+  K(hb_eq_inverse_kernel,             2,      28,     0,    1,          0,     0,    0,     1,   0,     0,   2,    2,     0,     0)       \
+  K(hb_eq_inverse32_kernel,           2,      32,     0,    1,          0,     0,    0,     1,   0,     0,   2,    2,     0,     0)
 
 // (the entry calls step_body directly: a forwarding function template in between changes register allocation and scheduling; every kernel
 // has the one signature - launch_pass hands all of them three arguments - and an INV row runs a single step whatever the count says)
@@ -2344,7 +2441,8 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, const DevMod
                                 : StepConfig{M.solver == 2 ? 2 : 0, nv <= 28 ? 28 : 32, 0, 1};
   // a model with friction rows: the FRIC instantiation of the full kernel - there is no lean, size-specialised, two-envs-per-wave, staged,
   // RK4 or body-acceleration one (the latter three are refused before a launch: hb_batch_create, hb_body_acc_readout)
-  c.fric = M.nfric ? 1 : 0;
+  // (equality rows: FRIC 2, which has the friction rows as well)
+  c.fric = M.neq_rows ? 2 : M.nfric ? 1 : 0;
   if (pass == StepPass::Inverse) {
     c.solver = 2; c.defer = c.coll ? 2 : 0; c.inv = 1;
     return {find_step_kernel(c), false, M_dev, shmem};
@@ -2396,7 +2494,7 @@ static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, const DevMod
 // round a multi-step launch is no faster than pipelined single steps, and slower when its last round is part empty (4608 envs: 104
 // against 85) - profiles/r04_fold_sizes_by_batch.txt.
 bool fold_pays(const DevModel& M, const BatchPtrs& P) {
-  if (M.variant != 0 || M.nfric) return false;  // (a model with friction rows: single-step launches of its full kernel, as they are tested)
+  if (M.variant != 0 || M.nfric || M.neq_rows) return false;  // (a model with friction or equality rows: single-step launches of its full kernel, as they are tested)
   if (P.n_env <= wave_slots()) return true;
   // (would the folded launch be a duo launch?  Step calls that read the constraint forces out are not folded onto it)
   const bool duo_kernel = !P.qfrc_out && select_step(StepPass::Main, nullptr, M, P, 2).duo;

@@ -765,6 +765,59 @@ bool read_tendons(Ctx& c, const XmlNode& n) {
   return c.err.empty();
 }
 
+// <equality>: scalar-joint couplings and connect anchors (a connect's anchor in body2's frame is set_const's, at qpos0)
+bool read_equalities(Ctx& c, const XmlNode& n) {
+  Model& m = *c.m;
+  for (auto& ch : n.children) {
+    const std::string& k = ch->name;
+    Attrs a = merged(c, *ch, "equality", "");
+    if (!c.err.empty()) return false;
+    if (k == "weld" || k == "tendon" || k == "flex" || k == "distance")
+      return c.fail("mjcf: equality <" + k + "> is not supported (joint and connect equalities are) in " + a.where);
+    if (k != "joint" && k != "connect") return c.fail("mjcf: unknown equality element <" + k + ">");
+    double data[kEqData] = {0};
+    int o1 = -1, o2 = -1;
+    if (k == "joint") {
+      const std::string j1 = a.str("joint1"), j2 = a.str("joint2");
+      o1 = find_name(m.jnt_name, j1);
+      if (j1.empty() || o1 < 0) return c.fail("mjcf: joint equality needs a valid joint1= in " + a.where);
+      if (a.has("joint2")) {
+        o2 = find_name(m.jnt_name, j2);
+        if (j2.empty() || o2 < 0) return c.fail("mjcf: unknown joint2 in " + a.where);
+      }
+      for (int j : {o1, o2})
+        if (j >= 0 && m.jnt_type[j] != JNT_HINGE && m.jnt_type[j] != JNT_SLIDE)
+          return c.fail("mjcf: joint equality on a free joint is not supported (hinge and slide joints only) in " + a.where);
+      data[1] = 1;  // polycoef default: 0 1 0 0 0
+      if (a.vec("polycoef", data, 5) < 0) return false;
+    } else {
+      if (a.has("site1") || a.has("site2")) return c.fail("mjcf: the site1 / site2 form of connect is not supported (use body1, body2 and anchor) in " + a.where);
+      const std::string b1 = a.str("body1");
+      o1 = find_name(m.body_name, b1);
+      if (b1.empty() || o1 < 0) return c.fail("mjcf: connect needs a valid body1= in " + a.where);
+      o2 = 0;
+      if (a.has("body2")) {
+        o2 = find_name(m.body_name, a.str("body2"));
+        if (o2 < 0) return c.fail("mjcf: unknown body2 in " + a.where);
+      }
+      if (a.vec("anchor", data, 3, 3) < 0) return false;
+      if (!a.has("anchor")) return c.fail("mjcf: connect needs anchor= in " + a.where);
+    }
+    double sr[2] = {0.02, 1}, si[5] = {0.9, 0.95, 0.001, 0.5, 2};
+    if (a.vec("solref", sr, 2) < 0 || a.vec("solimp", si, 5) < 0) return false;
+    const int active = a.tri("active", 1);
+    if (!c.err.empty()) return false;
+    m.eq_type.push_back(k == "joint" ? EQ_JOINT : EQ_CONNECT);
+    m.eq_obj1id.push_back(o1); m.eq_obj2id.push_back(o2);
+    m.eq_active0.push_back(active != 0 ? 1 : 0);
+    for (double v : data) m.eq_data.push_back(v);
+    m.eq_solref.push_back(sr[0]); m.eq_solref.push_back(sr[1]);
+    for (double v : si) m.eq_solimp.push_back(v);
+    m.eq_name.push_back(a.str("name"));
+  }
+  return c.err.empty();
+}
+
 bool read_actuators(Ctx& c, const XmlNode& n) {
   Model& m = *c.m;
   for (auto& ch : n.children) {
@@ -950,7 +1003,7 @@ bool compile_root(Ctx& c, XmlNode& root) {
     } else if (ch->name == "actuator") {
       if (!read_actuators(c, *ch)) return false;
     } else if (ch->name == "equality") {
-      if (!ch->children.empty()) return c.fail("mjcf: equality constraints are not supported");
+      if (!read_equalities(c, *ch)) return false;
     }
   }
   // Madr / nM

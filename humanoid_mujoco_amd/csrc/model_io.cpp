@@ -184,6 +184,16 @@ bool validate_model(const Model& m, std::string& err) {
   if (!m.dof_solimp_friction.empty() && m.dof_solimp_friction.size() != (size_t)5 * m.nv) return bad("array dof_solimp_friction has " + std::to_string(m.dof_solimp_friction.size()) + " entries, its size field says " + std::to_string(5 * m.nv));
   for (double v : m.dof_frictionloss) if (!(v >= 0)) return bad("negative dof_frictionloss");
   auto in = [](int v, int lo, int hi) { return v >= lo && v < hi; };  // lo <= v < hi
+  // (the optional equality records: every array as long as eq_type says; ids are checked below, behind the joints and bodies they name)
+  {
+    const size_t neq = m.eq_type.size();
+    struct { const char* name; size_t have, want; } eqlens[] = {{"eq_obj1id", m.eq_obj1id.size(), neq}, {"eq_obj2id", m.eq_obj2id.size(), neq},
+      {"eq_active0", m.eq_active0.size(), neq}, {"eq_data", m.eq_data.size(), (size_t)kEqData * neq}, {"eq_solref", m.eq_solref.size(), 2 * neq},
+      {"eq_solimp", m.eq_solimp.size(), 5 * neq}, {"eq_name", m.eq_name.size(), neq}};
+    for (auto& l : eqlens)
+      if (l.have != l.want) return bad(std::string("array ") + l.name + " has " + std::to_string(l.have) + " entries, eq_type has " + std::to_string(neq) + " elements");
+    if (neq > 4096) return bad("size out of range");
+  }
   int nq = 0, nv = 0;
   for (int j = 0; j < m.njnt; j++) {
     const int t = m.jnt_type[j];
@@ -249,6 +259,16 @@ bool validate_model(const Model& m, std::string& err) {
   for (int a = 0; a < m.nu; a++) {
     if (!in(m.actuator_trnid[a], 0, m.njnt)) return bad("actuator_trnid out of range");
     if (m.jnt_type[m.actuator_trnid[a]] != JNT_SLIDE && m.jnt_type[m.actuator_trnid[a]] != JNT_HINGE) return bad("actuator on a non-scalar joint");
+  }
+  for (int e = 0; e < m.neq(); e++) {
+    const int t = m.eq_type[e], o1 = m.eq_obj1id[e], o2 = m.eq_obj2id[e];
+    if (t == EQ_JOINT) {
+      if (!in(o1, 0, m.njnt) || !in(o2, -1, m.njnt)) return bad("equality: joint id out of range");
+      for (int j : {o1, o2}) if (j >= 0 && m.jnt_type[j] != JNT_SLIDE && m.jnt_type[j] != JNT_HINGE) return bad("equality: a joint equality on a non-scalar joint");
+    } else if (t == EQ_CONNECT) {
+      if (!in(o1, 0, m.nbody) || !in(o2, 0, m.nbody)) return bad("equality: body id out of range");
+    } else return bad("equality type " + std::to_string(t) + " is not implemented (connect = 0, joint = 2)");
+    if (m.eq_active0[e] != 0 && m.eq_active0[e] != 1) return bad("eq_active0 must be 0 or 1");
   }
   for (int e = 0; e < m.nexclude; e++)
     if (!in(m.exclude_body1[e], 0, m.nbody) || !in(m.exclude_body2[e], 0, m.nbody)) return bad("exclude body out of range");

@@ -253,6 +253,17 @@ bool set_const(Model& m, std::string& err) {
     m.tendon_length0[t] = len;
     m.tendon_invweight0[t] = w;
   }
+  // connect equalities: the anchor (given in body1's frame) in body2's frame at qpos0, where the two points coincide
+  for (int e = 0; e < m.neq(); e++) {
+    if (m.eq_type[e] != EQ_CONNECT) continue;
+    double* d = &m.eq_data[(size_t)kEqData * e];
+    const int b1 = m.eq_obj1id[e], b2 = m.eq_obj2id[e];
+    double p[3], q[3];
+    hm::rot_vec_quat(p, d, &k.xquat[4 * b1]);
+    for (int i = 0; i < 3; i++) q[i] = p[i] + k.xpos[3 * b1 + i] - k.xpos[3 * b2 + i];
+    const double* R = &k.xmat[9 * b2];  // (world <- body2, row-major: the transpose takes the offset into the body's frame)
+    for (int i = 0; i < 3; i++) d[3 + i] = R[i] * q[0] + R[3 + i] * q[1] + R[6 + i] * q[2];
+  }
   return true;
 }
 

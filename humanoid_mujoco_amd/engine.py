@@ -26,6 +26,8 @@ INT_EULER, INT_RK4 = 0, 1  # hb_options.integrator (mjtIntegrator): Model.set_op
 # mjtDisableBit (simulation/mujoco/include/mujoco/mjmodel.h:50-68)
 DSBL_CONSTRAINT, DSBL_LIMIT, DSBL_CONTACT, DSBL_PASSIVE, DSBL_GRAVITY = 1 << 0, 1 << 3, 1 << 4, 1 << 5, 1 << 6
 DSBL_CLAMPCTRL, DSBL_WARMSTART, DSBL_FILTERPARENT, DSBL_ACTUATION, DSBL_REFSAFE, DSBL_EULERDAMP = 1 << 7, 1 << 8, 1 << 9, 1 << 10, 1 << 11, 1 << 14
+DSBL_EQUALITY, DSBL_FRICTIONLOSS = 1 << 1, 1 << 2
+EQ_CONNECT, EQ_JOINT = 0, 2  # mjtEq values of Model.array("eq_type")
 
 
 class HbOptions(ctypes.Structure):
@@ -131,6 +133,7 @@ def lib():
     L.hb_options_get.argtypes = [vp, ctypes.POINTER(HbOptions)]
     L.hb_options_set.argtypes = [vp, ctypes.POINTER(HbOptions)]
     L.hb_model_name2id.argtypes = [vp, cp, cp]
+    L.hb_model_id2name.argtypes = [vp, cp, ctypes.c_int, cp, ctypes.c_int]
     L.hb_model_get_array.argtypes = [vp, cp, vp, ci]
     L.hb_batch_create.restype = vp; L.hb_batch_create.argtypes = [vp, ci, ci, cp, ci]
     L.hb_batch_free.argtypes = [vp]; L.hb_batch_free.restype = None
@@ -327,6 +330,11 @@ class Model:
     def name2id(self, kind, name):
         return lib().hb_model_name2id(self._h, kind.encode(), name.encode())
 
+    def id2name(self, kind, i):
+        buf = ctypes.create_string_buffer(256)
+        _check(min(0, lib().hb_model_id2name(self._h, kind.encode(), int(i), buf, len(buf))), "hb_model_id2name")
+        return buf.value.decode()
+
     def array(self, field):
         n = lib().hb_model_get_array(self._h, field.encode(), None, 0)
         if n < 0:
@@ -334,6 +342,27 @@ class Model:
         out = np.zeros(n, dtype=np.float64)
         lib().hb_model_get_array(self._h, field.encode(), _ptr(out), n)
         return out
+
+    # ---- equality constraints (include/hb.h: hb_batch_create)
+    @property
+    def neq(self):
+        """number of elements of the model's <equality> section, active or not"""
+        return len(self.array("eq_type"))
+
+    def equalities(self):
+        """One dict per equality: name, type ("joint" / "connect"), obj1, obj2 (joint ids, -1 for no joint2; body ids, 0 for the world),
+        active, data (a joint's polycoef[5]; a connect's anchor in body1's frame [3] | in body2's frame [3]), solref, solimp."""
+        t, o1, o2, act = (self.array(f).astype(int) for f in ("eq_type", "eq_obj1id", "eq_obj2id", "eq_active0"))
+        data, sr, si = self.array("eq_data").reshape(-1, 11), self.array("eq_solref").reshape(-1, 2), self.array("eq_solimp").reshape(-1, 5)
+        return [dict(name=self.id2name("equality", e), type={EQ_CONNECT: "connect", EQ_JOINT: "joint"}[int(t[e])], obj1=int(o1[e]), obj2=int(o2[e]),
+                     active=bool(act[e]), data=data[e, :5 if t[e] == EQ_JOINT else 6].copy(), solref=sr[e].copy(), solimp=si[e].copy()) for e in range(len(t))]
+
+    def equality_rows(self):
+        """ne: the equality rows a batch of this model has with the options as they are now (one per active joint coupling, three per
+        active connect; none under mjDSBL_EQUALITY or mjDSBL_CONSTRAINT)"""
+        if self.opt.disableflags & (DSBL_CONSTRAINT | DSBL_EQUALITY):
+            return 0
+        return int(sum((1 if e["type"] == "joint" else 3) for e in self.equalities() if e["active"]))
 
 
 class Batch:
@@ -591,8 +620,10 @@ class Batch:
         return a.value, b.value
 
     # ---- body accelerations (mj_objectAcceleration of every body, gravity pseudo-acceleration included; include/hb.h)
-    def _friction_loss_why(self, rc):
-        """HB_EUNSUPPORTED (-4) from a body-acceleration read-out on a model with joint frictionloss: say so (include/hb.h)"""
+    def _no_body_acc_why(self, rc):
+        """HB_EUNSUPPORTED (-4) from a body-acceleration read-out on a model with equality rows or joint frictionloss: say so (include/hb.h)"""
+        if rc == -4 and self.model.equality_rows():
+            return "a model with equality constraints has no body-acceleration read-out (accelerometer, gyro and frame-acceleration sensors included)"
         if rc == -4 and self.model.array("dof_frictionloss").any():
             return "a model with joint friction loss has no body-acceleration read-out (accelerometer, gyro and frame-acceleration sensors included)"
         return None
@@ -600,7 +631,7 @@ class Batch:
     def body_acc_readout(self, on=True):
         """From the next launch on, steps write every body's acceleration (full step kernels only)."""
         rc = lib().hb_body_acc_readout(self._h, int(on))
-        _check(rc, "hb_body_acc_readout", self._friction_loss_why(rc))
+        _check(rc, "hb_body_acc_readout", self._no_body_acc_why(rc))
 
     def body_acc(self):
         """[n_env, nbody, 6]: angular | linear acceleration of the body's xipos, world axes (row 0, the world: (0, -gravity))."""
@@ -796,7 +827,7 @@ class Batch:
         out = np.zeros((self.n_env, ns), dtype=np.float32)
         c = None if ctrl is None else np.ascontiguousarray(ctrl, dtype=np.float32)
         rc = lib().hb_sensors(self._h, _ptr(c), ctypes.byref(spec), _ptr(out))
-        _check(rc, "hb_sensors", self._friction_loss_why(rc) if spec.n_imu + spec.n_frameacc else None)
+        _check(rc, "hb_sensors", self._no_body_acc_why(rc) if spec.n_imu + spec.n_frameacc else None)
         return out
 
     # ---- env adapter (CPUEnv.step/reset analogue)

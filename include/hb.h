@@ -68,7 +68,8 @@ typedef struct hb_options {
   int integrator;    /* HB_INT_EULER (semi-implicit, implicit joint damping) or HB_INT_RK4 (models that step in one kernel: see hb_step);
                       * implicit (2) and implicitfast (3) are not implemented */
   int disableflags;  /* mjtDisableBit (mjmodel.h:50-68).  Bit 2 (mjDSBL_FRICTIONLOSS, <flag frictionloss="disable"/>): the joints'
-                      * frictionloss has no rows, and the model steps in the kernels of a model without friction loss */
+                      * frictionloss has no rows, and the model steps in the kernels of a model without friction loss.  Bit 1
+                      * (mjDSBL_EQUALITY, <flag equality="disable"/>): likewise for the model's equality constraints */
   int ls_iterations;   /* Newton: cap on line-search evaluations per iteration (mjOption.ls_iterations, mjmodel.h:434) */
   double ls_tolerance; /* Newton: line-search slope tolerance relative to `tolerance` (mjmodel.h:411) */
 } hb_options;
@@ -105,8 +106,11 @@ int hb_options_set(hb_model* m, const hb_options* in);
  * ascending (this engine's rounds 1-3, and .hbm files written then).  -1: query.  Returns the order in force.  Call before
  * hb_batch_create. */
 int hb_model_pair_order(hb_model* m, int order);
-/* mj_name2id (mujoco.h:516) for kind in {"body","joint","geom","actuator","tendon","key"}; -1 if absent. */
+/* mj_name2id (mujoco.h:516) for kind in {"body","joint","geom","actuator","tendon","key","equality"}; -1 if absent. */
 int hb_model_name2id(const hb_model* m, const char* kind, const char* name);
+/* mj_id2name for the same kinds: copies the name (empty for an unnamed element) into out[cap], zero-terminated; returns its length,
+ * HB_EINVAL for an unknown kind, an id out of range or a buffer that is too small. */
+int hb_model_id2name(const hb_model* m, const char* kind, int id, char* out, int cap);
 /* Copies a named fp64 model array (mjModel field name, e.g. "body_mass", "qpos0") into out[cap];
  * returns its length, or HB_EINVAL. */
 int hb_model_get_array(const hb_model* m, const char* field, double* out, int cap);
@@ -118,7 +122,13 @@ int hb_model_get_array(const hb_model* m, const char* field, double* out, int ca
  * dof, always active, with the force bounded by -frictionloss <= f <= frictionloss (mj_instantiateFriction).  The rows' constants are
  * worked out here from the options as they are now.  Implemented for models that step in one kernel with the Euler integrator: a model
  * with friction loss that steps in stages (mesh hulls, height fields, condim 4 / 6), or whose integrator is HB_INT_RK4, is refused here
- * with a message that says so. */
+ * with a message that says so.
+ * Equality constraints (the model's <equality> section: scalar-joint couplings, mjEQ_JOINT, and connect anchors, mjEQ_CONNECT; get_array
+ * fields eq_type, eq_obj1id, eq_obj2id, eq_active0, eq_data [neq][11], eq_solref, eq_solimp - neq is the length of eq_type): one row per
+ * active joint coupling and three per active connect, always active, in front of the friction-loss rows, with an unbounded force
+ * (mj_instantiateEquality), unless the options carry mjDSBL_EQUALITY or mjDSBL_CONSTRAINT.  The same rules as for friction loss: a model
+ * with equality rows that steps in stages, or whose integrator is HB_INT_RK4, is refused here, and so is a model whose equality and
+ * friction-loss rows together number more than 32; each message names equality constraints. */
 hb_batch* hb_batch_create(const hb_model* m, int n_env, int device, char* err, int err_sz);
 /* Replaces mj_deleteData (mujoco.h:206). */
 void hb_batch_free(hb_batch* b);
@@ -165,7 +175,10 @@ int hb_reset(hb_batch* b, const uint8_t* mask, int keyframe, int perturb, int en
  * A model with joint friction loss (hb_batch_create) steps in the friction kernels, hb_fric_* in hb_last_kernel, whatever the launch
  * looks like: they are full kernels - no lean, size-specialised, two-envs-per-wave or folded launch applies to such a model - and run
  * every read-out but the body accelerations.  Row overflow still drops limit and contact rows from the end (HB_WARN_CNSTRFULL): the
- * friction rows, at most nv <= 32, always fit. */
+ * friction rows, at most nv <= 32, always fit.
+ * A model with equality rows (hb_batch_create) steps in the equality kernels, hb_eq_* in hb_last_kernel, under the same rules; they hold
+ * the friction rows as well, and the two kinds together, at most 32 rows, always fit.  hb_inverse runs hb_eq_inverse*_kernel: an
+ * equality row's force is -D (J qacc - aref) whatever its sign. */
 int hb_step(hb_batch* b, const float* ctrl, int n_substeps);
 /* The same with the controls already in device memory, asynchronous: the call returns at once, its results are there after hb_batch_sync
  * or behind anything enqueued on hb_batch_stream later, and ctrl_dev must stay allocated and untouched until then.  On a PIPELINED batch
@@ -424,7 +437,8 @@ int hb_get_status(hb_batch* b, int* status);
 int hb_env_warnings(hb_batch* b, int* warnings);
 /* Per-env counters of the last step: ncon, nefc, solver iterations (mjData.ncon/nefc/
  * solver_niter, mjdata.h:196-201) — what testspeed.cc:97-98 accumulates.  nefc counts the friction-loss rows of the model as well
- * (one per dof with dof_frictionloss > 0: they are always active). */
+ * (one per dof with dof_frictionloss > 0: they are always active) and its equality rows (one per active joint coupling, three per
+ * active connect). */
 int hb_get_counts(hb_batch* b, int* ncon, int* nefc, int* niter);
 /* Name of the step kernel the batch's last step / rollout / forward launch ran ("hb_step_duo_kernel", "hb_step_h27_q_kernel", ...; ""
  * before the first).  Which instantiation a launch takes depends on the model's solver and sizes and on the optional inputs / outputs
@@ -479,9 +493,12 @@ int hb_get_collision_counts(hb_batch* b, int* nwork, int* nsearch, int* kcycles)
 /* Diagnostics of the last step for parity tests (mjData.qacc, efc_force, contact[]; mjdata.h:
  * 362,376,427): enable once, then read after a step.  efc_force is [n_env][nefc_max];
  * contact is [n_env][ncon_max][16] = dist, pos[3], frame[9], dim, geom1, geom2.
- * Row order (mj_makeConstraint's, without equality rows): the friction-loss rows in dof order, then joint limits, tendon limits and
+ * Row order (mj_makeConstraint's; a model without equality rows): the friction-loss rows in dof order, then joint limits, tendon limits and
  * contacts.  A friction row's entry is the joint-space friction force on its dof, in [-frictionloss, frictionloss]; every other row's is
- * >= 0.  A model with nf friction rows has its limit rows start at row nf, and every contact's first row moves up by nf as well. */
+ * >= 0.  A model with nf friction rows has its limit rows start at row nf, and every contact's first row moves up by nf as well.
+ * With equality rows the order is mj_makeConstraint's in full: the ne equality rows first, in the order of the <equality> section (a
+ * connect: world x, y, z), then friction loss, limits, contacts.  An equality row's entry is signed and unbounded; limit rows start
+ * at row ne + nf. */
 int hb_diag_enable(hb_batch* b, int on);
 int hb_get_qacc(hb_batch* b, float* qacc);
 int hb_get_efc_force(hb_batch* b, float* efc_force);
@@ -530,7 +547,7 @@ int hb_contact_readout_dev(hb_batch* b, const float** contact_force_dev, const f
  * and env-step launch writes it (such a launch runs the full step kernel's instantiation with the read-out, hb_acc_* in hb_last_kernel:
  * the lean and two-envs-per-wave kernels have none, and the full kernels themselves are compiled without it).
  * off: launches stop writing it.  hb_get_body_acc launches step calls held back and joins the pipes like every other read, and returns
- * HB_EINVAL while the read-out is off.  hb_body_acc_readout(b, 1) on a model with friction-loss rows returns HB_EUNSUPPORTED (no step
+ * HB_EINVAL while the read-out is off.  hb_body_acc_readout(b, 1) on a model with friction-loss or equality rows returns HB_EUNSUPPORTED (no step
  * kernel has both), and so does a sensor spec with n_imu or n_frameacc entries; the batch goes on stepping.  It holds the LAST forward pass (RK4: the last stage; the sensor entries of hb_sensor_spec hold
  * the first - the rule at hb_step).  Envs a launch skips (an env mask) keep their rows.
  * hb_body_acc_readout_dev hands out the device buffer (same layout) for a policy or reward on the same GPU: it joins like
