@@ -56,6 +56,9 @@ constexpr int d_xpq = 0, d_xmat = d_xpq + kXpqStride * NB, d_xipos = d_xmat + 15
 static_assert(2 * kDynF <= kLdsF - o_meta, "the dynamics scratch of both envs fits under the constraint arrays");
 static_assert(kLdsF * 4 <= 20480, "eight blocks per CU");
 static_assert(9 * NB <= 156 && 3 * NB <= 52 && 3 * NJ <= 68 && 10 * NB <= 172, "dynamics scratch map");
+// crb[body(i)] cdof_i per dof (qM stage): over xmat | xipos | xanchor | xaxis, which nothing reads after the cdof / geoms stage
+constexpr int kMbufStride = 8, d_mbuf = d_xmat;
+static_assert(kMbufStride * NV <= d_cinert - d_mbuf && d_mbuf % 4 == 0 && kDynF % 4 == 0 && o_meta % 4 == 0, "the per-dof buffer of the qM stage fits the dead kinematics scratch, 16-byte aligned");
 
 // sum over the 32 lanes of each half (wave_sum's DPP tree inside the rows of 16, then the two rows of the half): lo for lanes 0..31, hi for 32..63
 __device__ __forceinline__ void half_sums(float v, float& lo, float& hi) {
@@ -540,21 +543,36 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     float4 pf_bA = {0.f, 0.f, 0.f, 0.f}, pf_bB = pf_bA, pf_bC = pf_bA, pf_a0 = pf_bA, pf_a1 = pf_bA, pf_a2 = pf_bA, pf_a3 = pf_bA;
     if (dofl) { pf_bA = M.drec[3 * l]; pf_bB = M.drec[3 * l + 1]; pf_bC = M.drec[3 * l + 2]; }
     if (on && l < NU) { const float4 HB_CONST* AR4 = M.arec + (size_t)l * 4; pf_a0 = AR4[0]; pf_a1 = AR4[1]; pf_a2 = AR4[2]; pf_a3 = AR4[3]; }
+    // crb[body(i)] cdof_i is the same for every entry (i, j) of row i: once per dof (lane = dof), kept in the kinematics scratch
+    // (xmat .. xaxis: last read by the cdof / geoms stage) for the entries' rounds below
+    float* const s_mb = Dn + d_mbuf;
+    if (dofl) {
+      float buf[6], cd[6];
+      ld_cdof(s_cdof, l, cd);
+      float in[10];
+      {
+        const float4* Ip = reinterpret_cast<const float4*>(s_if + kIfStride * __float_as_int(pf_dA.y));  // (drec: the dof's body)
+        const float4 i0 = Ip[0], i1 = Ip[1], i2 = Ip[2];
+        in[0] = i0.x; in[1] = i0.y; in[2] = i0.z; in[3] = i0.w; in[4] = i1.x; in[5] = i1.y; in[6] = i1.z; in[7] = i1.w; in[8] = i2.x; in[9] = i2.y;
+      }
+      mul_inert_vec(buf, in, cd);
+      float4* Bp = reinterpret_cast<float4*>(s_mb + kMbufStride * l);
+      Bp[0] = {buf[0], buf[1], buf[2], buf[3]};
+      Bp[1] = {buf[4], buf[5], 0.f, 0.f};
+    }
+    gsync();
     if (on) {
       for (int e = l; e < NM; e += H) {
         const int pk = pf_pk;
         const float2 ad = pf_ad;
         if (e + H < NM) { pf_pk = M.mrec[e + H]; pf_ad = M.mdiag[e + H]; }
-        const int i = pk & 255, j = (pk >> 8) & 255, bi = pk >> 16;
-        float buf[6], cd[6];
-        ld_cdof(s_cdof, i, cd);
-        float in[10];
+        const int i = pk & 255, j = (pk >> 8) & 255;
+        float buf[6];
         {
-          const float4* Ip = reinterpret_cast<const float4*>(s_if + kIfStride * bi);
-          const float4 i0 = Ip[0], i1 = Ip[1], i2 = Ip[2];
-          in[0] = i0.x; in[1] = i0.y; in[2] = i0.z; in[3] = i0.w; in[4] = i1.x; in[5] = i1.y; in[6] = i1.z; in[7] = i1.w; in[8] = i2.x; in[9] = i2.y;
+          const float4* Bp = reinterpret_cast<const float4*>(s_mb + kMbufStride * i);
+          const float4 b0 = Bp[0], b1 = Bp[1];
+          buf[0] = b0.x; buf[1] = b0.y; buf[2] = b0.z; buf[3] = b0.w; buf[4] = b1.x; buf[5] = b1.y;
         }
-        mul_inert_vec(buf, in, cd);
         float sacc = 0.f;
         float cj[6];
         ld_cdof(s_cdof, j, cj);
@@ -969,12 +987,13 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
 #pragma unroll
             for (int kk = 0; kk < 14; kk++) D = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], Wp[(2 * kk + half) * kWsD + col], D, 0, 0, 0);
           }
+          // The tile is stored whole.  A row outside both envs' ranges takes the zeros of its masked A operand, and no reader minds: the
+          // jas / diag loop, the AR operands and the dual finish read rows below an env's count and its y row only, and a row that is live
+          // in a later pass or step has all kCsD columns rewritten by mj_makeConstraint (limit rows, contact rows, the y row) before that.
           if (col < 28) {
+            float* Cp = s_C + (32 * I + 4 * half) * kCsD + col;
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-              const int row = 32 * I + (r & 3) + 8 * (r >> 2) + 4 * half;
-              if ((row >= pLo0 && row <= pLo1) || (both && row >= pHi0 && row <= pHi1)) s_C[row * kCsD + col] = D[r];
-            }
+            for (int r = 0; r < 16; r++) Cp[((r & 3) + 8 * (r >> 2)) * kCsD] = D[r];
           }
         }
       }
@@ -983,8 +1002,10 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     HB_STAMP(11);
     // ---------------------------------------------------------------- efc_b, AR = C C^T + diag(R) (mj_projectConstraint), block diagonal over the envs
     const float* yv = s_C + ysrow * kCsD;
-    float ar[kNefcMax];
+    float ar[kNefcMax];  // the lane's AR column: over the packed rows, or (paired) over the rows of the lane's own env
     float Aii = 1.f;
+    // both envs at most 31 rows, env A's on lanes 0.., env B's on lanes 32..: the paired sweeps below
+    const bool paired = both && split == 32;
     {
       const float* Cr = s_C + lane * kCsD;
       float jas = 0.f, diag = 0.f;
@@ -1005,14 +1026,36 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       const float* A1p = s_C + (32 + col) * kCsD + half;
       const u32x2 rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(R), __float_as_uint(R), false, false);
       const float R0 = __uint_as_float(rr.x), R1 = __uint_as_float(rr.y);
+      // AR tiles (row tile, column tile): X0 = (0, 0), Y0 = (0, 1), X1 = (1, 0), Y1 = (1, 1).  Paired, each env keeps to its own tile, (0, 1) and
+      // (1, 0) are zero and unread, and ONE swap per register of (0, 0) and (1, 1) - lane c takes rows ra and ra + 4 of column c of the first,
+      // lane 32 + c those of column c of the second - gives every lane its column over the rows of its OWN env (ar[0..30]), where the
+      // general layout has its column over packed rows 0..31: no second swap, and the sweeps take ar[i] as it is instead of choosing between
+      // ar[i] and ar[32 + i] (31 selects).
+      // The high env's tile reaches that swap in one of two ways, with the same values: built in Y0 (kHiInY0: X1 and Y1 are then neither
+      // initialised nor read - nLo > 32 and !paired cannot hold when paired), or built in Y1 as ever and chosen at the swap by 16 selects on
+      // the uniform `paired`.  The choice per kernel is made by the register allocator alone and has to be re-made whenever
+      // tools/kernel_resources.sh hb_step_duo reports scratch: with hipcc of ROCm 7.2 for gfx950 the first form leaves 0 B/lane in the
+      // single-step kernel and 80 B/lane in the multi-step one, the second 104 B and 0 B (profiles/duo_once_bench.txt).  Both kernels must
+      // report ScratchSize 0.
+      constexpr bool kHiInY0 = MULTI == 0;
+      const bool hiY0 = kHiInY0 && paired;
       f32x16 X0, Y0, X1, Y1;
+      if (hiY0) {
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
-        X0[r] = (row == col && (lo0 || hi0)) ? R0 : 0.f;
-        Y1[r] = (row == col && (lo1 || hi1)) ? R1 : 0.f;
-        Y0[r] = 0.f;
-        X1[r] = 0.f;
+        for (int r = 0; r < 16; r++) {
+          const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+          X0[r] = (row == col && (lo0 || hi0)) ? R0 : 0.f;
+          Y0[r] = (row == col && (lo1 || hi1)) ? R1 : 0.f;
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+          X0[r] = (row == col && (lo0 || hi0)) ? R0 : 0.f;
+          Y1[r] = (row == col && (lo1 || hi1)) ? R1 : 0.f;
+          Y0[r] = 0.f;
+          X1[r] = 0.f;
+        }
       }
       // low env
       {
@@ -1021,7 +1064,7 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
           const float a0 = lo0 ? A0p[2 * kk] : 0.f;
           X0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, a0, X0, 0, 0, 0);
         }
-        if (nLo > 32) {
+        if (nLo > 32) {  // (never paired)
 #pragma unroll
           for (int kk = 0; kk < 14; kk++) {
             const float a0 = lo0 ? A0p[2 * kk] : 0.f;
@@ -1034,22 +1077,36 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       }
       // high env: always inside tile 1 (split >= 32)
       if (both && nHi > 0) {
+        if (hiY0) {
 #pragma unroll
-        for (int kk = 0; kk < 14; kk++) {
-          const float a1 = hi1 ? A1p[2 * kk] : 0.f;
-          Y1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, a1, Y1, 0, 0, 0);
+          for (int kk = 0; kk < 14; kk++) {
+            const float a1 = hi1 ? A1p[2 * kk] : 0.f;
+            Y0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, a1, Y0, 0, 0, 0);
+          }
+        } else {
+#pragma unroll
+          for (int kk = 0; kk < 14; kk++) {
+            const float a1 = hi1 ? A1p[2 * kk] : 0.f;
+            Y1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, a1, Y1, 0, 0, 0);
+          }
         }
       }
       (void)two; (void)hi0;
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int ra = (r & 3) + 8 * (r >> 2);
-        const u32x2 s0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(X0[r]), __float_as_uint(Y0[r]), false, false);
+        const u32x2 s0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(X0[r]), __float_as_uint((!kHiInY0 && paired) ? Y1[r] : Y0[r]), false, false);
         ar[ra] = __uint_as_float(s0.x);
         ar[ra + 4] = __uint_as_float(s0.y);
-        const u32x2 s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(X1[r]), __float_as_uint(Y1[r]), false, false);
-        ar[32 + ra] = __uint_as_float(s1.x);
-        if (32 + ra + 4 < kNefcMax) ar[32 + ra + 4] = __uint_as_float(s1.y);
+      }
+      if (!paired) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int ra = (r & 3) + 8 * (r >> 2);
+          const u32x2 s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(X1[r]), __float_as_uint(Y1[r]), false, false);
+          ar[32 + ra] = __uint_as_float(s1.x);
+          if (32 + ra + 4 < kNefcMax) ar[32 + ra + 4] = __uint_as_float(s1.y);
+        }
       }
     }
     HB_STAMP(12);
@@ -1074,14 +1131,12 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       }
     };
     int niterLo = 0, niterHi = 0;
-    if (both && split == 32) {
+    if (paired) {
       // Both envs at most 31 rows, env A's on lanes 0.., env B's on lanes 32..: the two Gauss-Seidel sweeps run SIDE BY SIDE - row i of
       // both envs in one row step (every lane proposes; the turn-holders of the two halves are read out by two v_readlane, each half
       // takes its own).  The two dependency chains share their instructions: one row step serves two envs.  Per env the arithmetic,
       // and its order, is the one-env sweep's.
-      float arS[31];  // the lane's AR column over the rows of its own env
-#pragma unroll
-      for (int i = 0; i < 31; i++) arS[i] = h ? ar[32 + i] : ar[i];
+      const float* const arS = ar;  // the lane's AR column over the rows of its own env (0..30)
       const float nAinv = -1.f / Aii;
       float arf = 0.f;
       const int nmax2 = max(nLo, nHi);
@@ -1312,7 +1367,12 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       float acc = 0.f;
 #pragma unroll 8
       for (int j = 0; j < 32; j++) acc = __builtin_fmaf(s_qM[M.mdense[j * 32 + l]], j < NV ? s_v0[j] : 0.f, acc);
-      P.qfrc_out[(size_t)env * NV + l] = acc;
+      // (the env index goes through an opaque move so that the 64-bit address of this store is built here and not hoisted out of the pass
+      // loop: hoisted, that register pair was the one value the single-step kernel spilled - 12 B/lane of scratch against 0,
+      // tools/kernel_resources.sh.  It exists for the register allocator only.)
+      int eq;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(eq) : "v"(env));
+      P.qfrc_out[(size_t)eq * NV + l] = acc;
     }
     // mj_checkAcc (mujoco.h:307): a bad qacc resets the data and runs mj_forward again; the step then integrates that result
     unsigned again = 0u;  // envs of this pass that run a second forward pass

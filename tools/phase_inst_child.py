@@ -5,7 +5,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import humanoid_mujoco_amd.engine as eng
-eng.LIB_PATH = os.path.join(ROOT, "build", "libhb_stamps.so")
+eng.LIB_PATH = os.environ.get("HB_STAMPS_LIB", os.path.join(ROOT, "build", "libhb_stamps.so"))  # (HB_STAMPS_LIB: another commit's diagnostic build)
 import humanoid_mujoco_amd as hb
 m = hb.Model.load(os.path.join(ROOT, "humanoid_mujoco_amd", "assets", sys.argv[2] if len(sys.argv) > 2 else "humanoid27.hbm"))
 N = 4096
