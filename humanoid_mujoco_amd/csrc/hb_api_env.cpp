@@ -1,0 +1,506 @@
+// hb_api_env.cpp — the C-ABI of libhb.so (include/hb.h), the env adapter: observations, rewards and resets, the realism layer and
+// domain randomisation, and the policy MLP.
+#include "hb_batch.hpp"
+
+extern "C" {
+
+static int env_alloc(hb_batch* b) {
+  if (b->env_ready) return HB_OK;
+  const DevModel& dm = b->D.dm;
+  size_t n = b->n_env;
+  HB_HIP(hipSetDevice(b->device));
+  const size_t nu = std::max(1, dm.nu);
+  // one record [obs n x nobs | reward n | terminated n | truncated n]: a host that keeps its four buffers in the same order and
+  // back to back (engine.py does) gets them in one transfer instead of four
+  int rc = b->d_record.alloc(n * dm.nobs * sizeof(float) + n * sizeof(float) + 2 * n);
+  if (rc == HB_OK) rc = b->d_prev.alloc(n * nu, /*zero=*/true);
+  if (rc == HB_OK) rc = b->d_latest.alloc(n * nu, /*zero=*/true);
+  if (rc == HB_OK) rc = b->d_action.alloc(n * nu);
+  if (rc == HB_OK) rc = b->d_qfrc.alloc(n * dm.nv, /*zero=*/true);
+  if (rc == HB_OK) rc = b->d_episode.alloc(n, /*zero=*/true);
+  if (rc == HB_OK) rc = b->d_seen.alloc(n, /*zero=*/true);
+  if (rc != HB_OK) { reset_all(b->d_record, b->d_prev, b->d_latest, b->d_action, b->d_qfrc, b->d_episode, b->d_seen); return rc; }
+  b->d_obs = reinterpret_cast<float*>(b->d_record.get());
+  b->d_reward = b->d_obs + n * dm.nobs;
+  b->d_term = reinterpret_cast<uint8_t*>(b->d_reward + n);
+  b->d_trunc = b->d_term + n;
+  hb_env_config def;
+  hb_env_default_config(b->model, &def);
+  static_assert(sizeof(hb_env_config) == sizeof(EnvConfig), "hb_env_config and EnvConfig must have the same layout");
+  memcpy(&b->env_cfg, &def, sizeof def);
+  b->env_ready = true;
+  return HB_OK;
+}
+
+// reward / termination / observation of every env (or those of `mask`).  observe: push the observation through the
+// realism layer's noise and delay lines (a step of the episode) instead of returning the true one.
+static int env_eval(hb_batch* b, bool allow_reset, bool observe, const uint8_t* mask, float* d_obs, float* d_reward, uint8_t* d_term, uint8_t* d_trunc) {
+  EnvConfig cfg = b->env_cfg;
+  if (!allow_reset) cfg.auto_reset = 0;
+  const Model& m = b->model->m;
+  const float* src = b->D.d_qpos_src + (cfg.reset_keyframe < 0 || cfg.reset_keyframe >= m.nkey ? 0 : (size_t)(1 + cfg.reset_keyframe) * m.nq);
+  EnvRandState S = b->rs;
+  if (!b->rand_on) memset(&S, 0, sizeof S);
+  HB_HIP(launch_env(b->D.dm, cfg, b->env_rand, S, b->d_state, b->d_qfrc, b->d_counts, b->d_prev, b->d_latest, src, b->d_episode, b->d_status, d_obs, d_reward,
+                    d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen));
+  return HB_OK;
+}
+
+int hb_get_obs(hb_batch* b, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated) {
+  if (!b || !obs) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  int n = b->n_env, nobs = b->D.dm.nobs;
+  if (reward || terminated || truncated) {
+    rc = env_eval(b, false, false, nullptr, b->d_obs, b->d_reward, b->d_term, b->d_trunc);  // pure evaluation: no reset, no bookkeeping, true observation
+    if (rc != HB_OK) return rc;
+  } else {
+    HB_HIP(launch_obs(b->D.dm, b->d_state, b->d_obs, n, main_stream(b)));
+  }
+  HB_HIP(hipMemcpyAsync(obs, b->d_obs, (size_t)n * nobs * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  if (reward) HB_HIP(hipMemcpyAsync(reward, b->d_reward, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  if (terminated) HB_HIP(hipMemcpyAsync(terminated, b->d_term, n, hipMemcpyDeviceToHost, main_stream(b)));
+  if (truncated) HB_HIP(hipMemcpyAsync(truncated, b->d_trunc, n, hipMemcpyDeviceToHost, main_stream(b)));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  return HB_OK;
+}
+
+int hb_env_default_config(const hb_model* h, hb_env_config* c) {
+  if (!h || !c) return HB_EINVAL;
+  const Model& m = h->m;
+  memset(c, 0, sizeof *c);
+  double z0 = 1.0;
+  for (int j = 0; j < m.njnt; j++) if (m.jnt_type[j] == JNT_FREE) { z0 = m.qpos0[m.jnt_qposadr[j] + 2]; break; }
+  c->target_z = (float)(0.94 * z0);  // the reference targets its standing height (Z_INITIAL_POS); 6 % slack for the soft stance
+  c->min_z = (float)(0.3 * z0);
+  c->max_time = 10.f;                 // MAX_SIM_TIME_STANDUP
+  double gear = 0;
+  for (int a = 0; a < m.nu; a++) gear += std::fabs(m.actuator_gear[a]);
+  c->safe_torque = (float)(m.nu ? 0.05 * gear / m.nu : 1.0);  // reference: 1.0 N m = 5 % of its 20 N m motors
+  c->control_frequency = (float)(1.0 / m.timestep);
+  c->action_scale = 1.5707963267948966f;
+  c->w_hvel = 5.f; c->w_upright = 10.f; c->w_height = 15.f; c->w_torque = 2.5f; c->w_ctrl_change = 2.f; c->w_ctrl_reg = 0.5f; c->w_symmetry = 1.f;
+  c->self_collision_penalty = -20.f; c->terminal_reward = -100.f; c->upright_tol = 0.7f;
+  // symmetry pairs: actuators named <x>_right / <x>_left (mirrored joint axes in the model => equal controls)
+  for (int a = 0; a < m.nu && c->n_equal < HB_ENV_MAX_PAIRS; a++) {
+    const std::string& n = m.actuator_name[a];
+    const std::string suf = "_right";
+    if (n.size() > suf.size() && n.compare(n.size() - suf.size(), suf.size(), suf) == 0) {
+      std::string other = n.substr(0, n.size() - suf.size()) + "_left";
+      for (int k = 0; k < m.nu; k++) if (m.actuator_name[k] == other) { c->equal_pairs[c->n_equal][0] = k; c->equal_pairs[c->n_equal][1] = a; c->n_equal++; break; }
+    }
+  }
+  c->auto_reset = 1; c->reset_keyframe = -1; c->reset_perturb = 1.f;
+  c->reward_kind = 0; c->w_vvel = 0.f;
+  c->min_z_grounded = (float)(0.25 * z0);  // the reference's MIN_Z_BEFORE_GROUNDED sits a quarter of the way up its robot
+  c->reset_collision_mode = 0;
+  return HB_OK;
+}
+
+int hb_env_team_config(const hb_model* h, hb_env_config* c) {
+  if (!h || !c) return HB_EINVAL;
+  const Model& m = h->m;
+  int rc = hb_env_default_config(h, c);
+  if (rc != HB_OK) return rc;
+  auto act = [&](const char* name) { for (int a = 0; a < m.nu; a++) if (m.actuator_name[a] == name) return a; return -1; };
+  // reward_functions.py:289-339 (standupReward) and simulation_parameters.py:51-77
+  c->target_z = -0.375f;            // TARGET_Z_POS = Z_INITIAL_POS
+  c->min_z = -0.6f;                 // MIN_Z_POS_FOR_REWARD
+  c->max_time = 10.f;               // MAX_SIM_TIME_STANDUP
+  c->safe_torque = 1.0f;            // MAX__SAFE_JOINT_TORQUE
+  c->control_frequency = 500.f;     // CONTROL_FREQUENCY
+  c->n_equal = c->n_opposite = 0;
+  const char* eq[][2] = {{"left_elbow", "right_elbow"}};
+  const char* op[][2] = {{"left_hip_roll", "right_hip_roll"}, {"left_hip_pitch", "right_hip_pitch"}, {"left_knee", "right_knee"},
+                         {"left_shoulder_pitch", "right_shoulder_pitch"}, {"left_shoulder_roll", "right_shoulder_roll"}};
+  for (auto& pr : eq) { const int a = act(pr[0]), b2 = act(pr[1]); if (a < 0 || b2 < 0) return HB_EINVAL; c->equal_pairs[c->n_equal][0] = a; c->equal_pairs[c->n_equal][1] = b2; c->n_equal++; }
+  for (auto& pr : op) { const int a = act(pr[0]), b2 = act(pr[1]); if (a < 0 || b2 < 0) return HB_EINVAL; c->opposite_pairs[c->n_opposite][0] = a; c->opposite_pairs[c->n_opposite][1] = b2; c->n_opposite++; }
+  c->reset_keyframe = -1;
+  for (int k = 0; k < m.nkey; k++) if (m.key_name[k] == "standup_reset") c->reset_keyframe = k;
+  c->reset_perturb = 1.f;
+  c->reset_quat_perturb = 0.1f;     // QUAT_INITIAL_OFFSET_MAX
+  c->obs_actuator_order = 1;        // JOINT_NAMES order = the <motor> order of the reference's humanoid.xml
+  c->min_z_grounded = -0.6f;
+  c->reset_collision_mode = 1;      // CPUEnv.reset starts over while anything is in contact (cpu_env.py:411-414)
+  return HB_OK;
+}
+
+int hb_env_configure(hb_batch* b, const hb_env_config* cfg) {
+  if (!b || !cfg) return HB_EINVAL;
+  if (cfg->n_equal < 0 || cfg->n_equal > HB_ENV_MAX_PAIRS || cfg->n_opposite < 0 || cfg->n_opposite > HB_ENV_MAX_PAIRS || !(cfg->action_scale > 0)) return HB_EINVAL;
+  int nu = b->D.dm.nu;
+  for (int k = 0; k < cfg->n_equal; k++) for (int t = 0; t < 2; t++) if (cfg->equal_pairs[k][t] < 0 || cfg->equal_pairs[k][t] >= nu) return HB_EINVAL;
+  for (int k = 0; k < cfg->n_opposite; k++) for (int t = 0; t < 2; t++) if (cfg->opposite_pairs[k][t] < 0 || cfg->opposite_pairs[k][t] >= nu) return HB_EINVAL;
+  if (cfg->reset_keyframe >= b->model->m.nkey) return HB_EINVAL;
+  if (cfg->reward_kind < 0 || cfg->reward_kind > 1 || cfg->reset_collision_mode < 0 || cfg->reset_collision_mode > 2) return HB_EINVAL;
+  if (!(cfg->reset_quat_perturb >= 0.f) || (cfg->obs_actuator_order != 0 && cfg->obs_actuator_order != 1)) return HB_EINVAL;
+  if (cfg->obs_actuator_order && !b->D.has_act_order) return HB_EINVAL;  // needs exactly one actuator per scalar joint
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  memcpy(&b->env_cfg, cfg, sizeof *cfg);
+  // the env / observation / policy kernels take the DevModel by value from this host copy: point it at the chosen order
+  b->D.dm.obs_jnt = cfg->obs_actuator_order ? b->D.obs_jnt_act : b->D.obs_jnt_joint;
+  b->D.dm.obs_src = cfg->obs_actuator_order ? b->D.obs_src_act : b->D.obs_src_joint;
+  return HB_OK;
+}
+
+int hb_env_default_randomization(const hb_model* h, hb_env_randomization* r) {
+  if (!h || !r) return HB_EINVAL;
+  memset(r, 0, sizeof *r);
+  const float deg = 0.017453292519943295f;
+  r->factor = 1.f; r->seed = 0; r->control_timestep = (float)h->m.timestep;
+  r->joint_angle_noise = 2.f * deg;     // JOINT_ANGLE_NOISE_STDDEV     (simulation_parameters.py:39-45)
+  r->joint_velocity_noise = 5.f * deg;  // JOINT_VELOCITY_NOISE_STDDEV
+  r->gyro_noise = 2.f * deg;            // GYRO_NOISE_STDDEV
+  r->imu_noise = 5.f * deg;             // IMU_NOISE_STDDEV
+  r->action_noise = 0.5f * deg;         // JOINT_ACTION_NOISE_STDDEV
+  r->min_delay = 0.01f; r->max_delay = 0.05f;  // MIN_DELAY, MAX_DELAY
+  r->frozen_noise = 0;
+  r->push_enabled = 1;                  // *_EXTERNAL_FORCE_* (simulation_parameters.py:14-20)
+  r->push_min_interval = 1.f; r->push_max_interval = 3.f; r->push_min_duration = 0.05f; r->push_max_duration = 0.15f;
+  r->push_min_force = 5.f; r->push_max_force = 15.f;
+  return HB_OK;
+}
+
+// releases the realism layer's device arrays: the layer is off
+static void envrand_free(hb_batch* b) {
+  reset_all(b->d_rs_k_act, b->d_rs_k_obs, b->d_rs_delay, b->d_rs_fifo_act, b->d_rs_fifo_joint, b->d_rs_fifo_gyro, b->d_rs_fifo_grav, b->d_rs_push);
+  memset(&b->rs, 0, sizeof b->rs);
+  b->rand_on = false;
+}
+int hb_env_randomize(hb_batch* b, const hb_env_randomization* cfg) {
+  if (!b) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  if (!cfg || !(cfg->factor > 0.f)) { envrand_free(b); return HB_OK; }
+  const DevModel& dm = b->D.dm;
+  const float dt = cfg->control_timestep > 0.f ? cfg->control_timestep : dm.timestep;
+  if (!(cfg->max_delay >= cfg->min_delay) || cfg->min_delay < 0.f || cfg->max_delay * cfg->factor / dt > (float)(kDelaySlots - 1)) return HB_EINVAL;
+  if (cfg->push_enabled && (!(cfg->push_max_interval >= cfg->push_min_interval) || !(cfg->push_max_duration >= cfg->push_min_duration) ||
+                            !(cfg->push_max_force >= cfg->push_min_force) || dm.nbody < 2)) return HB_EINVAL;
+  static_assert(sizeof(hb_env_randomization) == sizeof(EnvRand), "hb_env_randomization and EnvRand must have the same layout");
+  const size_t n = b->n_env, nu = std::max(1, dm.nu), nj2 = std::max(2, dm.nobs - 6);
+  if (!b->rs.k_act) {
+    rc = b->d_rs_k_act.alloc(n);
+    if (rc == HB_OK) rc = b->d_rs_k_obs.alloc(n);
+    if (rc == HB_OK) rc = b->d_rs_delay.alloc(n * 4);
+    if (rc == HB_OK) rc = b->d_rs_fifo_act.alloc(n * kDelaySlots * nu);
+    if (rc == HB_OK) rc = b->d_rs_fifo_joint.alloc(n * kDelaySlots * nj2);
+    if (rc == HB_OK) rc = b->d_rs_fifo_gyro.alloc(n * kDelaySlots * 3);
+    if (rc == HB_OK) rc = b->d_rs_fifo_grav.alloc(n * kDelaySlots * 3);
+    if (rc == HB_OK) rc = b->d_rs_push.alloc(n * 8, /*zero=*/true);
+    if (rc != HB_OK) { envrand_free(b); return rc; }
+    b->rs.k_act = b->d_rs_k_act; b->rs.k_obs = b->d_rs_k_obs; b->rs.delay = b->d_rs_delay; b->rs.fifo_act = b->d_rs_fifo_act;
+    b->rs.fifo_joint = b->d_rs_fifo_joint; b->rs.fifo_gyro = b->d_rs_fifo_gyro; b->rs.fifo_grav = b->d_rs_fifo_grav; b->rs.push = b->d_rs_push;
+  }
+  if (cfg->push_enabled && (rc = ensure_xfrc(b)) != HB_OK) return rc;
+  memcpy(&b->env_rand, cfg, sizeof *cfg);
+  b->rs.xfrc = cfg->push_enabled ? b->d_xfrc.get() : nullptr;
+  b->rand_on = true;
+  // a consistent episode state until the caller resets: delays drawn, rings empty
+  HB_HIP(launch_envrand_reset(dm, b->env_rand, b->rs, b->d_episode, nullptr, b->n_env, b->env_offset, main_stream(b)));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  return HB_OK;
+}
+
+int hb_env_default_domain_randomization(const hb_model* h, hb_domain_randomization* d) {
+  if (!h || !d) return HB_EINVAL;
+  memset(d, 0, sizeof *d);
+  d->factor = 1.f; d->seed = 0;
+  d->friction_min_mult = 0.5f; d->friction_max_mult = 1.f;   // FLOOR_FRICTION_*_MULTIPLIER (simulation_parameters.py:5-7)
+  d->max_mass_change = 0.05f; d->max_external_mass = 0.2f;   // MAX_MASS_CHANGE_PER_LIMB, MAX_EXTERNAL_MASS_ADDED
+  d->armature_max_change = 0.0005f; d->stiffness_max_change = 0.f; d->margin_max_change = 0.05f; d->range_max_change = 0.1f;  // JOINT_*_MAX_CHANGE
+  d->kp_nominal = 0.f; d->kp_max_change = 0.5f;              // JOINT_P_GAIN(_MAX_CHANGE); nominal 0: keep the model's gains
+  d->force_limit_max_change = 0.05f;                         // JOINT_FORCE_LIMIT_MAX_CHANGE
+  d->floor_bump_min = 0.f; d->floor_bump_max = h->m.nhfield > 0 ? 0.1f : 0.f;  // MIN/MAX_FLOOR_BUMP_HEIGHT (simulation_parameters.py:47-48); only with a height field
+  return HB_OK;
+}
+
+int hb_env_domain_randomize(hb_batch* b, const hb_domain_randomization* cfg) {
+  if (!b) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  if (!cfg || !(cfg->factor > 0.f)) {
+    b->d_dr.reset();
+    b->dr_stride = 0;
+    return HB_OK;
+  }
+  if (!(cfg->friction_max_mult >= cfg->friction_min_mult) || cfg->friction_min_mult < 0.f || cfg->max_mass_change < 0.f || cfg->max_external_mass < 0.f ||
+      cfg->armature_max_change < 0.f || cfg->stiffness_max_change < 0.f || cfg->margin_max_change < 0.f || cfg->range_max_change < 0.f || cfg->kp_max_change < 0.f ||
+      cfg->force_limit_max_change < 0.f || cfg->floor_bump_min < 0.f || cfg->floor_bump_max < 0.f) return HB_EINVAL;
+  static_assert(sizeof(hb_domain_randomization) == sizeof(DomainRand), "hb_domain_randomization and DomainRand must have the same layout");
+  const DevModel& dm = b->D.dm;
+  const DomainLayout L = domain_layout(dm.nbody, dm.nv, dm.nlimcand, dm.nu, dm.nhfielddata);
+  if (b->d_dr.alloc((size_t)b->n_env * L.stride) != HB_OK) return HB_ENOMEM;
+  b->dr_stride = L.stride;
+  memcpy(&b->dom_rand, cfg, sizeof *cfg);
+  // valid parameters at once (the draw of episode 0); hb_env_reset draws again for the episode numbers it assigns
+  HB_HIP(launch_domain_rand(dm, b->dom_rand, b->d_dr, b->dr_stride, b->d_episode, nullptr, b->n_env, b->env_offset, main_stream(b)));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  return HB_OK;
+}
+
+int hb_env_get_domain_params(hb_batch* b, float* out) {
+  if (!b) return HB_EINVAL;
+  if (!b->d_dr) return 0;
+  if (out) {
+    HB_HIP(hipSetDevice(b->device));
+    HB_HIP(hipStreamSynchronize(main_stream(b)));
+    HB_HIP(hipMemcpy(out, b->d_dr, (size_t)b->n_env * b->dr_stride * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return b->dr_stride;
+}
+
+// CPUEnv._apply_action (+ pushes) -> n_substeps x mj_step -> reward / termination / observation, for every env or those of `mask`
+static int env_step_impl(hb_batch* b, const float* action_dev, int n_substeps, const uint8_t* mask, bool allow_reset, float* obs_dev, float* reward_dev,
+                         uint8_t* terminated_dev, uint8_t* truncated_dev) {
+  const int n = b->n_env * b->D.dm.nu;
+  if (b->rand_on) {
+    HB_HIP(launch_action_env(b->D.dm, b->env_rand, b->rs, action_dev, b->d_prev, b->d_latest, ctrl_for_write(b), b->d_episode, b->d_state, mask, b->n_env, b->env_offset,
+                             main_stream(b)));
+  } else if (n && action_dev) {
+    HB_HIP(launch_action(action_dev, b->d_prev, b->d_latest, ctrl_for_write(b), n, main_stream(b)));
+  }
+  BatchPtrs P = make_ptrs(b);
+  P.ctrl = b->d_ctrl; P.ctrl_mode = 0; P.env_mask = mask;
+  int rc = launch_steps(b, P, n_substeps);
+  if (rc != HB_OK) return rc;
+  return env_eval(b, allow_reset, true, mask, obs_dev, reward_dev, terminated_dev, truncated_dev);
+}
+
+int hb_env_reset(hb_batch* b, float* obs) {
+  if (!b || !obs) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  const EnvConfig& c = b->env_cfg;
+  const Model& m = b->model->m;
+  const size_t n = b->n_env, nu = std::max(1, b->D.dm.nu);
+  HB_HIP(hipMemsetAsync(b->d_prev, 0, n * nu * sizeof(float), main_stream(b)));
+  HB_HIP(hipMemsetAsync(b->d_latest, 0, n * nu * sizeof(float), main_stream(b)));
+  HB_HIP(hipMemsetAsync(b->d_episode, 0, n * sizeof(int), main_stream(b)));
+  if (b->d_ctrl) HB_HIP(hipMemsetAsync(ctrl_for_write(b), 0, n * nu * sizeof(float), main_stream(b)));
+  if (c.reset_collision_mode == 0) {
+    rc = reset_impl(b, nullptr, c.reset_keyframe, c.reset_perturb, b->env_offset);
+    if (rc != HB_OK) return rc;
+    if (b->rand_on) HB_HIP(launch_envrand_reset(b->D.dm, b->env_rand, b->rs, b->d_episode, nullptr, b->n_env, b->env_offset, main_stream(b)));
+    if (b->d_dr) HB_HIP(launch_domain_rand(b->D.dm, b->dom_rand, b->d_dr, b->dr_stride, b->d_episode, nullptr, b->n_env, b->env_offset, main_stream(b)));
+  } else {
+    // The reference's protocol (cpu_env.py:374-416): randomise, take one step with the current (zero) controls, and
+    // start over with a new draw while that step ends in a collision or in a terminal state.  Pending envs carry
+    // a mask; everything (reset, realism layer, physics, evaluation) runs masked, at most eight draws.
+    if (b->d_rmask.alloc(n) != HB_OK || b->d_pending.alloc(1) != HB_OK) return HB_ENOMEM;
+    HB_HIP(hipMemsetAsync(b->d_rmask, 1, n, main_stream(b)));
+    const float* src = b->D.d_qpos_src + (c.reset_keyframe < 0 ? 0 : (size_t)(1 + c.reset_keyframe) * m.nq);
+    const float dtc = b->rand_on && b->env_rand.control_timestep > 0.f ? b->env_rand.control_timestep : (float)m.timestep;
+    const int substeps = std::max(1, (int)std::lround(dtc / m.timestep));
+    for (int attempt = 0; attempt < 8; attempt++) {
+      HB_HIP(launch_reset(b->D.dm, b->d_state, b->d_status, b->d_rmask, src, b->d_episode, b->n_env, c.reset_perturb, b->env_offset, main_stream(b), c.reset_quat_perturb));
+      if (b->rand_on) HB_HIP(launch_envrand_reset(b->D.dm, b->env_rand, b->rs, b->d_episode, b->d_rmask, b->n_env, b->env_offset, main_stream(b)));
+      if (b->d_dr) HB_HIP(launch_domain_rand(b->D.dm, b->dom_rand, b->d_dr, b->dr_stride, b->d_episode, b->d_rmask, b->n_env, b->env_offset, main_stream(b)));
+      rc = env_step_impl(b, nullptr, substeps, b->d_rmask, false, b->d_obs, b->d_reward, b->d_term, b->d_trunc);
+      if (rc != HB_OK) return rc;
+      HB_HIP(hipMemsetAsync(b->d_pending, 0, sizeof(int), main_stream(b)));
+      HB_HIP(launch_reset_check(b->d_counts, b->d_term, b->d_trunc, b->d_rmask, b->d_episode, b->d_pending, c.reset_collision_mode, b->n_env, main_stream(b)));
+      int pending = 0;
+      HB_HIP(hipMemcpyAsync(&pending, b->d_pending, sizeof(int), hipMemcpyDeviceToHost, main_stream(b)));
+      HB_HIP(hipStreamSynchronize(main_stream(b)));
+      if (pending == 0) break;
+    }
+  }
+  // the observation the reference returns from reset(): one more pass through the noise and delay lines
+  rc = env_eval(b, false, true, nullptr, b->d_obs, b->d_reward, b->d_term, b->d_trunc);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipMemcpyAsync(obs, b->d_obs, n * b->D.dm.nobs * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  return HB_OK;
+}
+
+int hb_env_step_dev(hb_batch* b, const float* action_dev, int n_substeps, float* obs_dev, float* reward_dev, uint8_t* terminated_dev, uint8_t* truncated_dev) {
+  if (!b || !action_dev || n_substeps < 1 || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  return env_step_impl(b, action_dev, n_substeps, nullptr, true, obs_dev, reward_dev, terminated_dev, truncated_dev);
+}
+
+static int env_step_host(hb_batch* b, const float* action, int n_substeps, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated, bool wait) {
+  if (!b || !action || !obs || !reward || !terminated || !truncated) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  int n = b->n_env, nu = b->D.dm.nu, nobs = b->D.dm.nobs;
+  if (nu) HB_HIP(hipMemcpyAsync(b->d_action, action, (size_t)n * nu * sizeof(float), hipMemcpyHostToDevice, main_stream(b)));
+  rc = hb_env_step_dev(b, b->d_action, n_substeps, b->d_obs, b->d_reward, b->d_term, b->d_trunc);
+  if (rc != HB_OK) return rc;
+  const size_t ob = (size_t)n * nobs * sizeof(float), rb = (size_t)n * sizeof(float);
+  if (reinterpret_cast<const uint8_t*>(reward) == reinterpret_cast<const uint8_t*>(obs) + ob && terminated == reinterpret_cast<const uint8_t*>(reward) + rb && truncated == terminated + n) {
+    HB_HIP(hipMemcpyAsync(obs, b->d_obs, ob + rb + 2 * (size_t)n, hipMemcpyDeviceToHost, main_stream(b)));  // the caller's buffers are one record too
+  } else {
+    HB_HIP(hipMemcpyAsync(obs, b->d_obs, ob, hipMemcpyDeviceToHost, main_stream(b)));
+    HB_HIP(hipMemcpyAsync(reward, b->d_reward, rb, hipMemcpyDeviceToHost, main_stream(b)));
+    HB_HIP(hipMemcpyAsync(terminated, b->d_term, n, hipMemcpyDeviceToHost, main_stream(b)));
+    HB_HIP(hipMemcpyAsync(truncated, b->d_trunc, n, hipMemcpyDeviceToHost, main_stream(b)));
+  }
+  if (wait) HB_HIP(hipStreamSynchronize(main_stream(b)));
+  return HB_OK;
+}
+int hb_env_terminal_obs(hb_batch* b, float* terminal_obs) {
+  if (!b) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  const size_t bytes = (size_t)b->n_env * b->D.dm.nobs * sizeof(float);
+  if (!b->d_term_obs) {  // first call: from the next hb_env_step on the env kernel records them
+    if (b->d_term_obs.alloc((size_t)b->n_env * b->D.dm.nobs) != HB_OK) return HB_ENOMEM;
+    HB_HIP(hipMemsetAsync(b->d_term_obs, 0, bytes, main_stream(b)));
+  }
+  if (terminal_obs) {
+    HB_HIP(hipMemcpyAsync(terminal_obs, b->d_term_obs, bytes, hipMemcpyDeviceToHost, main_stream(b)));
+    HB_HIP(hipStreamSynchronize(main_stream(b)));
+  }
+  return HB_OK;
+}
+int hb_env_step(hb_batch* b, const float* action, int n_substeps, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated) {
+  return env_step_host(b, action, n_substeps, obs, reward, terminated, truncated, true);
+}
+int hb_env_step_async(hb_batch* b, const float* action, int n_substeps, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated) {
+  return env_step_host(b, action, n_substeps, obs, reward, terminated, truncated, false);
+}
+
+int hb_policy_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases) {
+  if (!b || !sizes || !weights || !biases || n_layers < 1 || n_layers > 4) return HB_EINVAL;
+  if (sizes[0] != b->D.dm.nobs || sizes[n_layers] != b->D.dm.nu) return HB_EINVAL;
+  for (int l = 0; l <= n_layers; l++) if (sizes[l] < 1 || sizes[l] > 512) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  int maxh = 1;
+  bool fused = true;  // one-launch policy kernel: every width fits its LDS tiles
+  for (int l = 0; l <= n_layers; l++) fused = fused && sizes[l] <= 256;
+  for (int l = 0; l < n_layers; l++) {
+    if (!weights[l] || !biases[l]) return HB_EINVAL;
+    b->d_mlp_wp[l].reset();
+    if (fused) {
+      // B-operand order of v_mfma_f32_16x16x4_f32: wp[tile][k/4][lane] = W[4(k/4) + lane/16][16 tile + lane%16], zero padded
+      const int K = sizes[l], N = sizes[l + 1], KK = (K + 3) / 4, ntile = (N + 15) / 16;
+      std::vector<float> wp((size_t)ntile * KK * 64, 0.f);
+      for (int nt = 0; nt < ntile; nt++)
+        for (int kk = 0; kk < KK; kk++)
+          for (int ln = 0; ln < 64; ln++) {
+            const int k = 4 * kk + (ln >> 4), n = 16 * nt + (ln & 15);
+            if (k < K && n < N) wp[((size_t)nt * KK + kk) * 64 + ln] = weights[l][(size_t)k * N + n];
+          }
+      if (b->d_mlp_wp[l].alloc(wp.size()) != HB_OK) return HB_ENOMEM;
+      HB_HIP(hipMemcpy(b->d_mlp_wp[l], wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    reset_all(b->d_mlp_w[l], b->d_mlp_b[l]);
+    size_t nw = (size_t)sizes[l] * sizes[l + 1];
+    if (b->d_mlp_w[l].alloc(nw) != HB_OK || b->d_mlp_b[l].alloc(sizes[l + 1]) != HB_OK) return HB_ENOMEM;
+    HB_HIP(hipMemcpy(b->d_mlp_w[l], weights[l], nw * sizeof(float), hipMemcpyHostToDevice));
+    HB_HIP(hipMemcpy(b->d_mlp_b[l], biases[l], sizes[l + 1] * sizeof(float), hipMemcpyHostToDevice));
+    if (l + 1 < n_layers) maxh = std::max(maxh, sizes[l + 1]);
+  }
+  for (int i = 0; i < 2; i++) {
+    b->d_mlp_h[i].reset();
+    if (b->d_mlp_h[i].alloc((size_t)b->n_env * maxh) != HB_OK) return HB_ENOMEM;
+  }
+  b->d_mlp_act.reset();
+  if (fused) {
+    int widest = 1;
+    for (int l = 0; l <= n_layers; l++) widest = std::max(widest, sizes[l]);
+    const size_t floats = ((size_t)(b->n_env + 15) / 16 + hb_batch::kPipes) * 32 * (widest + 4);
+    if ((rc = b->d_mlp_act.alloc(floats, /*zero=*/true)) != HB_OK) return rc;
+  }
+  b->mlp_layers = n_layers;
+  b->mlp_fused = fused;
+  for (int l = 0; l <= n_layers; l++) b->mlp_sizes[l] = sizes[l];
+  return HB_OK;
+}
+
+// obs -> MLP -> ctrl for envs [lo, hi) on `st`
+// (seg >= 0: env segment `seg` of a pipelined closed loop: the LDS-free kernel, which the GPU places beside the running step kernels)
+static int policy_forward(hb_batch* b, int lo, int hi, hipStream_t st, int seg = -1) {
+  if (b->mlp_layers < 1) return HB_EINVAL;
+  const DevModel& dm = b->D.dm;
+  if (b->mlp_fused) {
+    PolicyDesc pd;
+    memset(&pd, 0, sizeof pd);
+    pd.nl = b->mlp_layers;
+    int widest = 1;
+    for (int l = 0; l <= b->mlp_layers; l++) { pd.sizes[l] = b->mlp_sizes[l]; widest = std::max(widest, b->mlp_sizes[l]); }
+    for (int l = 0; l < b->mlp_layers; l++) { pd.w[l] = b->d_mlp_wp[l]; pd.b[l] = b->d_mlp_b[l]; }
+    pd.ldx = widest + 4;  // + the K pad columns (K is swept four at a time); 16-row tiles
+    const bool lean_ok = b->tune[HB_TUNE_POLICY_LEAN] != 0;
+    const bool lean_all = b->tune[HB_TUNE_POLICY_LEAN] == 2;
+    if (lean_all && seg < 0) seg = 0;
+    if (seg >= 0 && lean_ok && b->d_mlp_act)
+      HB_HIP(launch_policy_lean(dm, pd, b->d_state + (size_t)lo * dm.nstate, ctrl_for_write(b) + (size_t)lo * dm.nu,
+                                b->d_mlp_act + ((size_t)(lo + 15) / 16 + seg) * 32 * pd.ldx, hi - lo, st));
+    else
+      HB_HIP(launch_policy(dm, pd, b->d_state + (size_t)lo * dm.nstate, ctrl_for_write(b) + (size_t)lo * dm.nu, hi - lo, st));
+    return HB_OK;
+  }
+  // wide layers: one launch per layer, activations through HBM
+  HB_HIP(launch_obs(dm, b->d_state + (size_t)lo * dm.nstate, b->d_obs + (size_t)lo * b->mlp_sizes[0], hi - lo, st));
+  const float* x = b->d_obs + (size_t)lo * b->mlp_sizes[0];
+  for (int l = 0; l < b->mlp_layers; l++) {
+    float* y = ((l + 1 == b->mlp_layers) ? ctrl_for_write(b) : b->d_mlp_h[l & 1]) + (size_t)lo * b->mlp_sizes[l + 1];
+    HB_HIP(launch_mlp_layer(x, b->d_mlp_w[l], b->d_mlp_b[l], y, hi - lo, b->mlp_sizes[l], b->mlp_sizes[l + 1], 1, st));
+    x = y;
+  }
+  return HB_OK;
+}
+
+int hb_policy_eval(hb_batch* b, float* ctrl_out) {
+  if (!b) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  int rc = policy_forward(b, 0, b->n_env, main_stream(b));
+  if (rc != HB_OK) return rc;
+  if (ctrl_out) HB_HIP(hipMemcpyAsync(ctrl_out, b->d_ctrl, (size_t)b->n_env * b->D.dm.nu * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  return HB_OK;
+}
+
+int hb_rollout_policy(hb_batch* b, int T, float* qpos_out_dev) {
+  if (!b || T < 1) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  // every segment is its own obs -> MLP -> mj_step chain: with pipelining on, the chains run side by side
+  const int nseg = segment_count(b);
+  int rc = fork_pipes(b, nseg);
+  if (rc != HB_OK) return rc;
+  for (int t = 0; t < T; t++) {
+    const bool reorder = b->schedule && (b->launch_count % reorder_period(b) == 0);
+    BatchPtrs P = make_ptrs(b);
+    P.qfrc_out = nullptr;  // (the env adapter's read-out: nothing in this loop reads it, and without it the step launches are the lean kernels)
+    P.ctrl = b->d_ctrl; P.ctrl_mode = 0;
+    P.qpos_out = qpos_out_dev ? qpos_out_dev + (size_t)t * b->n_env * b->D.dm.nq : nullptr;
+    for (int c = 0; c < nseg; c++) {
+      const Segment sg = segment(b, c, nseg);
+      rc = policy_forward(b, sg.lo, sg.hi, sg.st, nseg > 1 ? c : -1);
+      if (rc == HB_OK) rc = launch_segment(b, P, 1, sg, nseg, reorder);
+      if (rc != HB_OK) return rc;
+    }
+    steps_enqueued(b, nseg, reorder);
+  }
+  return HB_OK;
+}
+
+int hb_env_warnings(hb_batch* b, int* warnings) {
+  if (!b || !warnings) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  hipStream_t st = main_stream(b);
+  std::vector<int> seen((size_t)b->n_env);
+  HB_HIP(hipMemcpyAsync(warnings, b->d_status, seen.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HB_HIP(hipMemcpyAsync(seen.data(), b->d_seen, seen.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  HB_HIP(hipMemsetAsync(b->d_seen, 0, seen.size() * sizeof(int), st));
+  HB_HIP(hipStreamSynchronize(st));
+  for (size_t e = 0; e < seen.size(); e++) warnings[e] |= seen[e];
+  return HB_OK;
+}
+
+}  // extern "C"

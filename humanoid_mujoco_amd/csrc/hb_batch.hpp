@@ -1,0 +1,222 @@
+// hb_batch.hpp — internal to libhb.so: the model and batch handles behind include/hb.h, the owner of their device memory, and the
+// launch plumbing (hb_batch.cpp) the C-ABI translation units (hb_api.cpp, hb_api_rollout.cpp, hb_api_env.cpp) share.
+#pragma once
+#include "../../include/hb.h"
+#include "hb_device.hpp"
+#include "hb_launch.hpp"
+#include "hb_model.hpp"
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+using namespace hb;
+
+struct hb_model {
+  Model m;
+};
+
+namespace hb {
+
+inline void set_err(char* err, int err_sz, const std::string& s) {
+  if (err && err_sz > 0) { snprintf(err, err_sz, "%s", s.c_str()); }
+}
+
+// HB_DEBUG=1 in the environment names the failing HIP call on stderr
+inline bool hb_debug() { static const bool on = getenv("HB_DEBUG") != nullptr; return on; }
+// a call whose failure is not fatal (teardown paths): still named under HB_DEBUG, and never left behind as the
+// thread's sticky last error for an unrelated launch to trip over
+#define HB_IGN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+    if (hb_debug()) fprintf(stderr, "[hb] %s:%d: %s -> %s (ignored)\n", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
+    (void)hipGetLastError(); } } while (0)
+#define HB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
+    if (hb_debug()) fprintf(stderr, "[hb] %s:%d: %s -> %s\n", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
+    return HB_ENODEVICE; } } while (0)
+
+// The owner of one device allocation of T (or of none: a null pointer, which call sites read as "this feature is off").  All device
+// memory of a DeviceModel and of an hb_batch is held through these, so whatever is allocated is released with its owner.
+template <class T>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+  size_t capacity() const { return cap_; }
+  void reset() {
+    if (p_) HB_IGN(hipFree(p_));
+    p_ = nullptr; cap_ = 0;
+  }
+  // first use allocates exactly n elements (zero: and fills them with zero bytes); nothing when the buffer is there already
+  int alloc(size_t n, bool zero = false) {
+    if (p_) return HB_OK;
+    if (hipMalloc((void**)&p_, n * sizeof(T)) != hipSuccess) { p_ = nullptr; return HB_ENOMEM; }
+    cap_ = n;
+    if (zero) HB_HIP(hipMemset(p_, 0, n * sizeof(T)));
+    return HB_OK;
+  }
+  // grow only: room for n elements; a buffer that has to grow loses its contents, and is empty when that fails
+  int reserve(size_t n) {
+    if (n <= cap_) return HB_OK;
+    reset();
+    return alloc(n);
+  }
+
+ private:
+  T* p_ = nullptr;
+  size_t cap_ = 0;  // elements
+};
+// buffers that are allocated together are all there or all released
+template <class... B>
+void reset_all(B&... bufs) { (bufs.reset(), ...); }
+
+struct DeviceModel {
+  DevModel dm;
+  DevBuf<int> d_int;
+  DevBuf<float> d_flt;
+  DevBuf<unsigned long long> d_u64;
+  DevBuf<float> d_qpos_src;  // qpos0 followed by keyframes, fp32
+  DevBuf<DevModel> d_dm;     // device copy of dm (the step kernel reads the tables through it)
+  DevBuf<DevModel> d_dm_fast;  // variant 2 only: the same model with the variant-1 LDS layout (fast step kernel of the staged step)
+  int fast_lds_floats = 0;
+  bool sized_h27 = false;  // sizes and LDS layout equal kSizedHumanoid27's: the size-specialised step kernel applies
+  bool sized_team = false; // the fast layout equals kSizedTeamV1's
+  // observation order tables (device pointers): joint order and, when it exists, actuator order (hb_env_config.obs_actuator_order)
+  const int *obs_jnt_joint = nullptr, *obs_src_joint = nullptr, *obs_jnt_act = nullptr, *obs_src_act = nullptr;
+  bool has_act_order = false;
+};
+
+}  // namespace hb
+
+struct hb_batch {
+  const hb_model* model = nullptr;
+  DeviceModel D;
+  int n_env = 0, device = 0;
+  hipStream_t stream = nullptr;
+  // device memory: every buffer is a DevBuf member (null until the feature that needs it allocates it), released when the batch is deleted
+  DevBuf<float> d_state, d_ctrl, d_xfrc, d_diag_qacc, d_diag_force, d_diag_contact;
+  DevBuf<uint8_t> d_record;  // the env adapter's outputs as one block: obs [n_env][nobs] | reward [n_env] | terminated [n_env] | truncated [n_env]
+  float *d_obs = nullptr, *d_reward = nullptr;  // (its parts)
+  uint8_t *d_term = nullptr, *d_trunc = nullptr;
+  DevBuf<int> d_seen;        // [n_env] warning bits of episodes that ended since the last hb_env_warnings
+  DevBuf<float> d_term_obs;  // [n_env][nobs] observations of the states episodes ended in (hb_env_terminal_obs), null until asked for
+  DevBuf<uint8_t> d_mask;
+  DevBuf<int> d_status, d_counts;
+  DevBuf<float> d_qpos_out, d_qvel_out;
+  DevBuf<float> d_task_out;  // task returns and stage costs
+  float xfrc_std = 0.f, xfrc_rate = 0.f;  // rollout noise (hb_rollout_noise)
+  int tape_steps = 0;                      // steps of the action tape hb_ctrl_tape_splines left in d_ctrl (0: none)
+  DevBuf<float> d_knots;                   // spline nodes and node times staged for it
+  unsigned xfrc_seed = 0, xfrc_calls = 0;
+  DevBuf<float> d_sensor_out;
+  bool diag = false;
+  // contact-force read-out (hb_contact_readout): [n_env][ncon_max][6] and [n_env][nbody][6]; a sensor spec with touch / contact-force
+  // entries allocates them as well and hands them to its own launches only
+  DevBuf<float> d_contact_force, d_body_contact;
+  bool contact_readout = false;
+  // body-acceleration read-out (hb_body_acc_readout): [n_env][nbody][6], and the scratch the step kernel parks a body's kinematics in
+  // across the solver, [n_env][nbody][kAccPark]; a sensor spec with accelerometer / frame-acceleration entries allocates them as well
+  DevBuf<float> d_body_acc, d_body_acc_park;
+  bool body_acc_readout = false;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBuf<unsigned long long> d_stamps;
+  // staged step of the general variants: the buffers, and the kernel argument that points into them (all null: fused)
+  DevBuf<float> d_stage_geom;
+  DevBuf<int4> d_stage_item;
+  DevBuf<int> d_stage_nsearch, d_stage_nwork, d_stage_defer;  // defer: flags | list | counters
+  DevBuf<float4> d_stage_result;
+  StageBufs stage = {};
+  // env adapter (hb_env_*)
+  EnvConfig env_cfg = {};
+  bool env_ready = false;
+  DevBuf<float> d_prev, d_latest, d_qfrc, d_action;
+  DevBuf<float> d_inv;  // hb_inverse's device copies: qacc [n_env][nv] | qfrc_inverse [n_env][nv] | warnings [n_env] (allocated by its first call)
+  DevBuf<int> d_inv_scratch;  // hb_inverse_dev: the counts [n_env][kCountStride] | status [n_env] its launches write instead of the batch's
+  DevBuf<float> d_kin;     // hb_kinematics / hb_kinematics_states: device copies of their host arrays (outputs | qpos | qvel), grown on demand
+  DevBuf<int> d_episode;
+  int env_offset = 0;
+  // realism layer (hb_env_randomize)
+  EnvRand env_rand = {};
+  DevBuf<int> d_rs_k_act, d_rs_k_obs, d_rs_delay;
+  DevBuf<float> d_rs_fifo_act, d_rs_fifo_joint, d_rs_fifo_gyro, d_rs_fifo_grav, d_rs_push;
+  EnvRandState rs = {};     // the kernel argument that points into them; all null while off
+  bool rand_on = false;
+  DomainRand dom_rand = {};    // hb_env_domain_randomize
+  DevBuf<float> d_dr;          // [n_env][dr_stride] per-env model parameters, null while off
+  int dr_stride = 0;
+  DevBuf<uint8_t> d_rmask;     // hb_env_reset's pending-envs mask
+  DevBuf<int> d_pending;
+  // policy MLP (hb_policy_*)
+  int mlp_layers = 0;
+  int mlp_sizes[5] = {0, 0, 0, 0, 0};
+  DevBuf<float> d_mlp_w[4];
+  DevBuf<float> d_mlp_wp[4];  // packed for hb_policy_kernel (all widths <= 256), else null
+  bool mlp_fused = false;
+  DevBuf<float> d_mlp_b[4];
+  DevBuf<float> d_mlp_h[2];  // hidden activations, ping-pong
+  DevBuf<float> d_mlp_act;   // activation scratch of the LDS-free policy kernel: [n_env / 16 + kPipes][2][16][widest + 4]
+  // optional per-kernel timing of the step kernel (hb_step_timing)
+  bool time_steps = false;
+  std::vector<hipEvent_t> tev;  // pairs
+  int tev_used = 0;
+  long long launch_count = 0;
+  const char* last_kernel = "";  // hb_last_kernel
+  // run-time choices between kernels / schedules that give the same results (hb_batch_tune, include/hb.h: HB_TUNE_*), indexed by knob
+  int tune[HB_TUNE_COUNT] = {getenv("HB_DUO") ? atoi(getenv("HB_DUO")) : 1, 1, 1, 1, 1, 1, 1, 4, 1, kFoldMax, 1};
+  // hb_step_dev calls not launched yet (fold_steps): the launch parameters they share, and the controls of each
+  BatchPtrs fold_P;
+  const float* fold_ctrl[kFoldMax] = {};
+  int fold_n = 0;
+  DevBuf<int> d_order;      // heavy-first dispatch order (hb_order_kernel), valid once a step has run
+  DevBuf<int> d_order2;     // the same for the narrowphase launch of a staged step
+  int order_mode = 0;       // 0: none yet, 1: one permutation of the whole batch, 2: one permutation per pipe segment
+  bool schedule = true;  // heavy-first dispatch order (HB_TUNE_SCHEDULE)
+  // Pipelined stepping (hb_batch_pipeline): the batch is cut into npipe fixed env segments, each stepped by
+  // its own launch on its own stream.  Envs are independent, so segment c of step t+1 only has to follow
+  // segment c of step t: the tail of one step (its slowest envs) overlaps the head of the next.  `stream`
+  // stays the batch's ordering point: pipes fork from it at every step call and are joined back into it
+  // before anything else is enqueued on it.
+  static constexpr int kPipes = 8;  // most segments; npipe of them in use (streams are created when first asked for)
+  int npipe = 0;                    // 0: unpipelined
+  int probed_segments = 0;          // what hb_batch_pipeline(b, 1)'s probe of the segment streams found (0: not probed yet); the streams are kept, so is the answer
+  bool forked = false;
+  hipStream_t pipe[kPipes] = {};
+  hipEvent_t ev_fork = nullptr, ev_pipe[kPipes] = {};
+  int join_error = 0;
+  bool main_dirty = true;  // work was enqueued on `stream` since the pipes last forked from it
+};
+
+// ---- launch plumbing (hb_batch.cpp); internal to the library
+#pragma GCC visibility push(hidden)
+namespace hb {
+bool build_device_model(const Model& m, DeviceModel& D, std::string& err);
+// the batch's control buffer for WRITING: whatever hb_ctrl_tape_splines left there is gone afterwards, so a later
+// HB_CTRL_TAPE rollout must fail (HB_EINVAL) instead of rolling out stale controls
+inline float* ctrl_for_write(hb_batch* b) { b->tape_steps = 0; return b->d_ctrl; }
+int ensure_ctrl(hb_batch* b, size_t floats);
+int ensure_xfrc(hb_batch* b);
+int alloc_contact_readout(hb_batch* b);
+int alloc_body_acc_readout(hb_batch* b);
+int reset_impl(hb_batch* b, const uint8_t* mask, int keyframe, float perturb_scale, int env_offset);
+bool staged_on(const hb_batch* b);
+BatchPtrs make_ptrs(hb_batch* b);
+void join_pipes(hb_batch* b);
+int flush_steps(hb_batch* b);
+hipStream_t main_stream(hb_batch* b);
+int reorder_period(const hb_batch* b);
+int segment_count(const hb_batch* b);
+struct Segment { int lo, hi; hipStream_t st; };
+Segment segment(hb_batch* b, int c, int nseg);
+int fork_pipes(hb_batch* b, int nseg);
+hipError_t launch_batch_step(hb_batch* b, const BatchPtrs& P, int nsteps, hipStream_t stream);
+int launch_segment(hb_batch* b, BatchPtrs P, int nsteps, const Segment& sg, int nseg, bool reorder);
+void steps_enqueued(hb_batch* b, int nseg, bool reorder, bool refreshed = false);
+int launch_steps(hb_batch* b, BatchPtrs& P, int nsteps, bool foldable = false);
+int rollout_open(hb_batch* b, const float* ctrl, int T, bool want_qpos);
+}  // namespace hb
+#pragma GCC visibility pop

@@ -1,5 +1,5 @@
 // hb_device.hpp — device-side model tables and batch buffers (fp32), shared by the host
-// runtime (hb_api.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip).
+// runtime (hb_tables.cpp, hb_batch.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip).
 //
 // The model is replicated read-only per device as two flat arrays (int, float); DevModel holds
 // typed pointers into them plus the per-env LDS layout.  All tables are small (a few KB) and
@@ -39,7 +39,7 @@ constexpr int kMetaStride = 4;  // floats per row in the general variants' row m
 constexpr int kMeshChunk = 8;   // neighbour records per climb round's load batch (DevModel::mesh_nbr)
 constexpr int kMeshStart = 96;  // start records per mesh: cube map, 6 faces x 4 x 4 (DevModel::mesh_start)
 constexpr int kCountStride = 8;  // ints per env in BatchPtrs::counts: ncon, nefc, niter, cost, self-collision flag, spare
-constexpr int kBrecQuads = 18;  // float4s per level-ordered body record (see build_device_model)
+constexpr int kBrecQuads = 18;  // float4s per level-ordered body record (see build_model_tables)
 
 // contact record layout in LDS (floats)
 enum { C_DIST = 0, C_POS = 1, C_FRAME = 4, C_PAIR = 13, C_ROW = 14, C_DIM = 15, C_FRIC = 16 };
@@ -106,8 +106,8 @@ struct DevModel {
   const float4 HB_CONST* prec;
   // per pair, 3 float4 for mj_collision: [0] geom1, geom2, type1 | type2 << 8, margin [1] rbound1, rbound2, size1[0..1] [2] size2[0..1]
   const float4 HB_CONST* crec;
-  const float4 HB_CONST* arec;  // per actuator: 4 quads (hb_api.cpp)
-  const float4 HB_CONST* lrec;  // per limit candidate: 4 quads (hb_api.cpp)
+  const float4 HB_CONST* arec;  // per actuator: 4 quads (hb_tables.cpp)
+  const float4 HB_CONST* lrec;  // per limit candidate: 4 quads (hb_tables.cpp)
   const float HB_CONST* pair_fricab;  // per pair: (sliding friction of the floor geom if it is in the pair, else 0; the other geom's / the mixed one)
   const float HB_CONST *pair_friction, *pair_solref, *pair_solimp, *pair_margin, *pair_gap;
   // limit candidates: 2 per limited joint/tendon in constraint order (lower, upper)
@@ -138,11 +138,11 @@ struct DevModel {
   // mjtIntegrator (0 Euler, 1 RK4) and, RK4 only, the stage block behind both regions: q0[nq] | v0[nv] | sum b V [nv] | sum b F [nv]
   int integrator, o_rk;
   // friction loss: the rows in front of the limit rows, one per dof with dof_frictionloss > 0 (0: an ordinary model, or disabled by the
-  // options), and per row (dof, frictionloss, R, B) as build_device_model works them out.  Read by step_body's FRIC instantiations only.
+  // options), and per row (dof, frictionloss, R, B) as build_model_tables works them out.  Read by step_body's FRIC instantiations only.
   int nfric;
   const float4 HB_CONST* frec;
   // equality constraints: the rows in front of the friction rows, one per active joint coupling and three per active connect (0: a model
-  // without them, or disabled by the options), and per row a kErecQuads record (hb_api.cpp).  Read by step_body's FRIC == 2 instantiations only.
+  // without them, or disabled by the options), and per row a kErecQuads record (hb_tables.cpp).  Read by step_body's FRIC == 2 instantiations only.
   int neq_rows;
   const float4 HB_CONST* erec;
 };
@@ -273,7 +273,7 @@ struct StageBufs {
 };
 
 // ---- The per-env LDS layout of the step kernels: every o_* offset of DevModel, the row stride of C, the RK4 stage block and the total,
-// as a function of the model's shape.  This is the one place that computes it: build_device_model copies the result into the DevModel
+// as a function of the model's shape.  This is the one place that computes it: build_model_tables copies the result into the DevModel
 // (and, for variants 2 and 3, into the one-group fast model), and the size-specialised kernels below take it as compile-time constants.
 enum { kLdsOk = 0, kLdsNoEulerRoom, kLdsTooLarge };  // LdsLayout::fail
 struct LdsLayout {
@@ -346,7 +346,7 @@ constexpr LdsLayout lds_layout(int nq, int nv, int nu, int nbody, int njnt, int 
 // Every loop bound and every LDS offset of the step kernel is a function of the model's sizes.  For the size signature of the
 // reference's 27-dof humanoid (simulation/mujoco/model/humanoid/humanoid.xml) they are compile-time constants in one
 // more instantiation: addresses fold into the instructions' offset fields and 40 SGPRs spill instead of 84.  Any model with this
-// signature takes it (the host compares its sizes, and the layout lds_layout gave it against the constant's: build_device_model);
+// signature takes it (the host compares its sizes, and the layout lds_layout gave it against the constant's: build_model_tables);
 // every other model takes the generic kernels.
 struct SizedModel : LdsLayout {
   int nq, nv, nu, nbody, njnt, ngeom, ntendon, nM, ntree, npair, nlevel, nlimcand, nstate;
@@ -369,7 +369,7 @@ __host__ __device__ inline int pose_lds_floats(int nq, int nb, int ngeom) {
   return ((nq + 3) & ~3) + 12 * nb + 2 * ((3 * ngeom + 3) & ~3) + 4 * ngeom + kListMax * 5 + kWorkMax;
 }
 
-// most step calls one launch executes (the calls the host enqueued back to back, hb_api.cpp fold_steps)
+// most step calls one launch executes (the calls the host enqueued back to back, hb_batch.cpp fold_steps)
 constexpr int kFoldMax = 256;
 struct BatchPtrs {
   float* state;        // [n_env][nstate]
@@ -413,7 +413,7 @@ struct BatchPtrs {
   int lean_ok;                // bit 0: the model's options allow the lean instantiations (mjOption.disableflags == 0); bit 1: its sizes and LDS
                               // layout are kSizedHumanoid27's (the size-specialised instantiations); bit 2: its fast layout is kSizedTeamV1's
   int stop_phase;             // diagnostic builds only: 0 = off (HB_STOP_PHASE in the environment, read at every launch)
-  const float* ctrl_tab[kFoldMax];  // ctrl_mode 3: step t of this launch is the step call whose [n_env][nu] controls these are (hb_api.cpp: fold_steps)
+  const float* ctrl_tab[kFoldMax];  // ctrl_mode 3: step t of this launch is the step call whose [n_env][nu] controls these are (hb_batch.cpp: fold_steps)
   int duo;                    // host side only (launch_step): two envs per wave 0 never, 1 where it pays, 2 always (hb_batch_duo)
   StageBufs stage;
   // inverse dynamics (launch_inverse, the INV instantiations only): qacc [n_env][nv] in, qfrc_inverse [n_env][nv] out, the per-env

@@ -195,7 +195,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   int stage = 0;             // RK4: which of the step's four forward passes this one is (Euler: always 0)
   for (int step = 0; step < nsteps; step++) {
     if constexpr (LEAN != 1) {
-      // a launch of several steps whose waves are all resident (hb_api.cpp folds step calls into such launches): the two waves of a SIMD are
+      // a launch of several steps whose waves are all resident (hb_batch.cpp folds step calls into such launches): the two waves of a SIMD are
       // blocks half a round apart and the SIMD favours the older one, so they take the higher priority in turns (hb_step_duo.hip has the numbers)
       if (nsteps > 1) {
         if (((step & 1) == 0) == ((int)blockIdx.x < ((int)gridDim.x >> 1))) __builtin_amdgcn_s_setprio(1);
@@ -2487,7 +2487,7 @@ static hipError_t launch_pass(StepPass pass, const DevModel* M_dev, const DevMod
   return hipGetLastError();
 }
 
-// Does it pay to run step calls the host has enqueued back to back as ONE launch of several steps (hb_api.cpp: fold_steps)?  When all the
+// Does it pay to run step calls the host has enqueued back to back as ONE launch of several steps (hb_batch.cpp: fold_steps)?  When all the
 // launch's waves are on the chip at once: then no wave waits for a slot while others run through their steps, and no env waits for the
 // batch's slowest one between steps.  One-env waves: up to 8 per CU (2048 envs on MI355X: 42 us per step against 64 for pipelined single
 // steps); two-envs-per-wave waves, for the models that have that kernel: up to twice as many envs (4096: 67 against 78).  Beyond one

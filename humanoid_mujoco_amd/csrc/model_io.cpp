@@ -135,7 +135,7 @@ bool load_hbm_string(const std::string& text, Model& m, std::string& err) {
   return validate_model(m, err);
 }
 
-// Every array length against its size field and every id / address against its range: what build_device_model and the
+// Every array length against its size field and every id / address against its range: what build_model_tables and the
 // kernels index without further checks.  Run on every loaded .hbm (a truncated or edited file must give an error string,
 // not a host out-of-bounds read or a GPU fault) and on every compiled MJCF.
 bool validate_model(const Model& m, std::string& err) {

@@ -5,7 +5,7 @@ on every joint, ranges on every third joint, a plane or a height-field floor.  O
 the floor, so that a state's contacts and limit rows stay inside the classic kernels' capacity (24 contacts, 63 rows).
 
 perturbed_hbm writes a copy of a compiled .hbm with other masses, inertias, joint axes, ranges, damping, geom sizes and gears but the same
-sizes: a model that still takes the size-specialised kernels (hb_api.cpp: sized_h27 / sized_team).
+sizes: a model that still takes the size-specialised kernels (hb_tables.cpp: sized_h27 / sized_team).
 
 kernel_table reads the step kernels' table (hb_step.hip: HB_KERNELS) for the CPU tests that hold its rows to what they must be.
 """

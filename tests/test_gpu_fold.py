@@ -1,4 +1,4 @@
-"""Step calls enqueued back to back run as ONE launch (include/hb.h: hb_step_dev, HB_TUNE_FOLD; csrc/hb_api.cpp: fold_steps).
+"""Step calls enqueued back to back run as ONE launch (include/hb.h: hb_step_dev, HB_TUNE_FOLD; csrc/hb_batch.cpp: fold_steps).
 
 The reference steps a thread's envs in a loop with nothing between the steps (simulation/mujoco/sample/testspeed.cc:93-96: mj_step
 after mj_step); hb_step_dev is asynchronous, so K calls in a row are the same thing to the caller as one launch of K steps - which

@@ -119,7 +119,7 @@ def _chain_rows(spec):
 TABLE = {name: _chain_rows(spec) for name, spec in CHAINS.items()}
 TABLE.update(humanoid27_pgs=H27_PGS, humanoid27_newton=H27_NEWTON, humanoid27_hfield=H27_HFIELD, team_robot=TEAM,
              humanoid27_perturbed_pgs=H27_PGS, humanoid27_perturbed_newton=H27_NEWTON, team_robot_perturbed=TEAM)
-# With the diagnostic outputs on, a variant-2 / -3 model steps in its own variant's kernel (the four- / two-group one: hb_api.cpp, "the
+# With the diagnostic outputs on, a variant-2 / -3 model steps in its own variant's kernel (the four- / two-group one: hb_batch.cpp, "the
 # diagnostic buffers are laid out for the kernel of the model's own variant"), not in the one-group fast kernel of its staged step.  For
 # those models the diag row is held to the oracle in full, and the fast kernels' one-step reference is the full fast instantiation
 # (lean=0), whose state, counts and sweep counts are held to the oracle step.

@@ -297,7 +297,7 @@ def _set_record(lines, name, values):
 @pytest.mark.parametrize("case", ["short_array", "bad_actuator_joint", "bad_pair_geom", "bad_geom_body", "bad_parent", "bad_madr", "huge_count", "bad_tendon_wrap", "bad_key"])
 def test_edited_or_truncated_hbm_is_an_error_not_a_fault(hbmod, tmp_path, case):
     """A damaged compiled model must come back as an error string from hb_model_load: every array length is checked against
-    its size field and every id / address against its range before build_device_model or a kernel indexes with it."""
+    its size field and every id / address against its range before build_model_tables or a kernel indexes with it."""
     from oracle_lib import HUMANOID_HBM, parse_hbm
     info = parse_hbm(HUMANOID_HBM)
 
