@@ -47,10 +47,11 @@ HFIELD_ELEV = np.array([[0.0, 0.3, 0.1, 0.6, 0.2],
 AXES = ("0 1 0", "0 0 1", "1 0 0")
 
 
-def chain_xml(nv, free=True, floor="plane", condim=3, solver="PGS", timestep=0.004):
+def chain_xml(nv, free=True, floor="plane", condim=3, solver="PGS", timestep=0.004, forcerange=None):
     """A capsule chain of nv degrees of freedom (6 of them the free base's).  floor: "plane" or "hfield" (the height field of
     test_oracle_convex._hfield_xml with condim and friction of its own).  PGS runs its 50 sweeps with tolerance 0, as the terrain
-    config does: whenever there are rows the sweep counts of device and oracle are the same number."""
+    config does: whenever there are rows the sweep counts of device and oracle are the same number.  forcerange: None (no force limits, the XML of
+    every caller that does not pass it) or r: every motor forcelimited to [-r, r]."""
     nj = nv - (6 if free else 0)
     assert nj >= 2
     nlink = (nj + 1) // 2
@@ -84,7 +85,8 @@ def chain_xml(nv, free=True, floor="plane", condim=3, solver="PGS", timestep=0.0
         e = HFIELD_ELEV
         asset = '<asset><hfield name="h" nrow="%d" ncol="%d" size="3 3 0.08 0.5" elevation="%s"/></asset>' % (e.shape[0], e.shape[1], " ".join("%.17g" % v for v in e.reshape(-1)))
         ground = '<geom name="floor" type="hfield" hfield="h" condim="%d" friction="1 0.01 0.001" contype="1" conaffinity="1"/>' % condim
-    motors = "".join('<motor name="m_%s" joint="%s" gear="%g" ctrlrange="-1 1" ctrllimited="true"/>' % (n, n, 2.0 if i != 2 else 20.0) for i, n in enumerate(joints))
+    frc = "" if forcerange is None else ' forcelimited="true" forcerange="-%g %g"' % (forcerange, forcerange)
+    motors = "".join('<motor name="m_%s" joint="%s" gear="%g" ctrlrange="-1 1" ctrllimited="true"%s/>' % (n, n, 2.0 if i != 2 else 20.0, frc) for i, n in enumerate(joints))
     return ('<mujoco model="chain%d"><compiler angle="degree"/><option timestep="%g" iterations="%d" tolerance="%s" solver="%s"/>'
             '<default><joint damping="0.05" armature="0.01"/><geom conaffinity="0" condim="%d"/></default>%s'
             '<worldbody>%s%s</worldbody><actuator>%s</actuator></mujoco>'

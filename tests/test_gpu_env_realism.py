@@ -5,6 +5,7 @@ controlInputReward semantics (reward_functions.py:116-245) and the reset-until-c
 import numpy as np
 import pytest
 
+import dr_ref
 from env_ref import RealismRef, control_input_reward, obs_from_state
 from oracle_lib import Oracle
 
@@ -191,18 +192,6 @@ def test_randomize_argument_checks_and_off_switch(hbmod, humanoid_model, gpu):
     assert np.allclose(o2, true, atol=1e-6) and not np.allclose(o1, o2)
 
 
-def _domain_layout(m, nlim):
-    nb, nv, nu = 17, m.nv, m.nu
-    o = dict(mass=0, arm=nb, stiff=nb + nv, lmargin=nb + 2 * nv)
-    o["lrange"] = o["lmargin"] + nlim
-    o["gain"] = o["lrange"] + nlim
-    o["bias1"] = o["gain"] + nu
-    o["frc"] = o["bias1"] + nu
-    o["fric"] = o["frc"] + 2 * nu
-    o["stride"] = o["fric"] + 1
-    return o
-
-
 def test_domain_randomization_draws_and_physics(hbmod, humanoid_model, gpu):
     """hb_domain_randomization: per-env masses, armature, joint limits, actuator force ranges and floor friction are
     drawn inside the reference's bounds, differ between envs and episodes, and the physics uses them — one step from
@@ -224,9 +213,8 @@ def test_domain_randomization_draws_and_physics(hbmod, humanoid_model, gpu):
     base_mass = o.marr("body_mass").copy(); base_arm = o.marr("dof_armature").copy(); base_rng = o.marr("jnt_range").copy()
     base_frc = o.marr("actuator_forcerange").copy(); base_stiff = o.marr("jnt_stiffness").copy(); base_margin = o.marr("jnt_margin").copy()
     base_fric = o.marr("geom_friction").copy()
-    nlim = (P.shape[1] - 1 - 17 - 2 * m.nv - 4 * m.nu) // 2
-    L = _domain_layout(m, nlim)
-    assert P.shape[1] == L["stride"] and nlim == 2 * 21 + 2 * 2  # 21 limited hinges + 2 limited tendons, lower and upper each
+    L = dr_ref.layout(m, P.shape[1])
+    assert P.shape[1] == L["stride"] and L["nlimcand"] == 2 * 21 + 2 * 2  # 21 limited hinges + 2 limited tendons, lower and upper each
     mass = P[:, L["mass"]:L["mass"] + 17]
     assert np.all(np.abs(mass[:, 1:] - base_mass[1:]) <= 0.5 + 0.2 + 1e-5) and np.all(mass[:, 1:] >= 1e-5) and mass[:, 1:].std(axis=0).min() > 0
     arm = P[:, L["arm"]:L["arm"] + m.nv]

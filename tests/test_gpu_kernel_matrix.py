@@ -205,8 +205,9 @@ def _contacts_ok(o, con, nc, ne):
     return w
 
 
-def _vs_oracle(hbmod, b, o, st, ct, fences_ok, label):
-    """one diag step of batch b from the states against the oracle from the same states; returns the worst deviations"""
+def _vs_oracle(hbmod, b, o, st, ct, fences_ok, label, before=None):
+    """one diag step of batch b from the states against the oracle from the same states; returns the worst deviations.  before(k), if
+    given, is called ahead of env k's oracle step (tests/test_gpu_domain_params.py: it writes env k's model parameters into the oracle)"""
     b.diag_enable(True)
     b.set_state(hbmod.STATE_INTEGRATION, st)
     b.step(ct)
@@ -219,6 +220,8 @@ def _vs_oracle(hbmod, b, o, st, ct, fences_ok, label):
     fences = 0
     pgs = o.opt("solver") != 2
     for k in range(len(st)):
+        if before is not None:
+            before(k)
         load_state(o, st[k], ct[k].astype(np.float64))
         o.forward()
         w = _contacts_ok(o, con[k], nc[k], ne[k])
@@ -252,7 +255,7 @@ def _vs_oracle(hbmod, b, o, st, ct, fences_ok, label):
     return worst
 
 
-def _state_vs_oracle(hbmod, b, o, st, ct, fences_ok, label):
+def _state_vs_oracle(hbmod, b, o, st, ct, fences_ok, label, before=None):
     """the state a one-step launch of batch b left (no diagnostic outputs) against the oracle's step from the same states: counts and
     PGS sweep counts identical, qpos and qvel within the golden bounds"""
     q, v = b.qpos.astype(np.float64), b.qvel.astype(np.float64)
@@ -262,6 +265,8 @@ def _state_vs_oracle(hbmod, b, o, st, ct, fences_ok, label):
     fences = 0
     pgs = o.opt("solver") != 2
     for k in range(len(st)):
+        if before is not None:
+            before(k)
         load_state(o, st[k], ct[k].astype(np.float64))
         o.forward()
         on_fence = (o.ncon, o.nefc) != (nc[k], ne[k])
@@ -283,6 +288,7 @@ def _state_vs_oracle(hbmod, b, o, st, ct, fences_ok, label):
     assert fences <= max(1, 0.05 * len(st)), (label, fences)
     for key, x in worst.items():
         assert x <= BOUNDS[key], (label, key, x, BOUNDS[key])
+    return worst
 
 
 def _result(hbmod, b):

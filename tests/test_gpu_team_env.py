@@ -7,8 +7,10 @@ import os
 import numpy as np
 import pytest
 
+import dr_ref
 from env_ref import obs_from_state, standup_reward
-from oracle_lib import ROOT, Oracle
+from oracle_lib import ROOT, Oracle, load_state
+from test_gpu_kernel_matrix import BOUNDS, _state_vs_oracle
 
 pytestmark = pytest.mark.gpu
 TEAM_HBM = os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "team_robot.hbm")
@@ -107,14 +109,33 @@ def test_team_domain_randomisation_sets_the_motor_gains(hbmod, gpu):
     env = hbmod.VecEnv(m, n, gpu, team=True, domain_randomization=True)
     env.reset()
     prm = env.batch.env_domain_params()
-    nb, nv, nu = m.nbody, m.nv, m.nu
-    nlim = 2 * 12
-    o_gain = nb + 2 * nv + 2 * nlim
-    gain = prm[:, o_gain:o_gain + nu]
-    frc = prm[:, o_gain + 2 * nu:o_gain + 4 * nu].reshape(n, nu, 2)
+    nu = m.nu
+    L = dr_ref.layout(m, prm.shape[1])
+    assert L["nlimcand"] == 2 * 12 and L["nhfielddata"] == 64
+    gain = dr_ref.table(prm, L, "gain")
+    frc = dr_ref.table(prm, L, "frc").reshape(n, nu, 2)
     assert gain.min() >= 1.5 - 1e-6 and gain.max() <= 2.5 + 1e-6 and gain.std() > 0.2
     assert np.abs(frc[:, :, 0] + 1).max() <= 0.05 + 1e-6 and np.abs(frc[:, :, 1] - 1).max() <= 0.05 + 1e-6
-    # and the physics uses them: one step with full command from rest, the hinge accelerations scale with the drawn gains
-    obs, rew, term, trunc, info = env.step_arrays(np.ones((n, nu), np.float32))
-    assert np.isfinite(obs).all() and np.isfinite(rew).all()
+    # and the physics uses them: one step from rest of every env against the fp64 oracle carrying that env's block (the
+    # bounds of tests/test_gpu_kernel_matrix.py).  At 0.4 of full command the motor force is 0.4 x gain, inside the force range: the hinge
+    # accelerations scale with the drawn gains, and the oracle with the model's own gain 1 does not reproduce the step.  At full command
+    # the force sits on the drawn force range's upper bound instead.
+    b = env.batch
+    o = Oracle(TEAM_HBM)
+    base = dr_ref.snapshot(o)
+    for level in (0.4, 1.0):
+        st = b.get_state(hbmod.STATE_INTEGRATION, dtype=np.float64)
+        act = np.full((n, nu), level, np.float32)
+        obs, rew, term, trunc, info = env.step_arrays(act)
+        assert np.isfinite(obs).all() and np.isfinite(rew).all() and not (term | trunc).any()
+        v1 = b.qvel.astype(np.float64)
+        # (counts identical - or, for this mesh-on-height-field model, proved to sit on a rounding fence -, qpos and qvel within BOUNDS)
+        _state_vs_oracle(hbmod, b, o, st, act, True, "team domain randomisation, command %.1f" % level, before=lambda k: dr_ref.apply(o, prm[k], L, base))
+        dr_ref.restore(o, base)
+        moved = 0
+        for e in range(0, n, 8):
+            load_state(o, st[e], act[e].astype(np.float64))
+            o.step()
+            moved += np.abs(v1[e] - o.qvel).max() / max(1.0, np.abs(o.qvel).max()) >= 10 * BOUNDS["qvel"]
+        assert moved >= 12, (level, moved)  # (the model's own gain 1 and force range do not reproduce the step)
     env.close()
