@@ -426,6 +426,91 @@ int hb_kinematics_states(hb_batch* b, const float* qpos, const float* qvel, int 
   return kinematics_host(b, qpos, body_vel ? qvel : nullptr, n, body_pose, body_vel, geom_pose);
 }
 
+// ---- ray casting (hb_ray.hip) ----------------------------------------------------------------------------------------
+int hb_ray_configure(hb_batch* b, const hb_ray_spec* spec, const float* pnt, const float* vec, int n_ray) {
+  if (!b) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  if (!spec || n_ray == 0) {  // remove: rays in flight (hb_rays_dev) read the buffers until the stream has run dry
+    HB_HIP(hipStreamSynchronize(main_stream(b)));
+    b->n_ray = 0;
+    reset_all(b->d_ray, b->d_ray_kin, b->d_ray_out, b->d_ray_geoms);
+    return HB_OK;
+  }
+  const Model& m = b->model->m;
+  if (!pnt || !vec || n_ray < 1 || n_ray > kRayMax) return HB_EINVAL;
+  if (spec->frame < HB_RAY_FRAME_WORLD || spec->frame > HB_RAY_FRAME_YAW || spec->frame_body < 0 || spec->frame_body >= m.nbody) return HB_EINVAL;
+  if (spec->bodyexclude < -1 || spec->bodyexclude >= m.nbody) return HB_EINVAL;
+  if (!(spec->flags & (HB_RAY_STATIC | HB_RAY_MOVING)) || (spec->flags & ~(HB_RAY_STATIC | HB_RAY_MOVING)) || !std::isfinite(spec->cutoff)) return HB_EINVAL;
+  std::vector<float> h(6 * (size_t)n_ray);
+  for (int i = 0; i < n_ray; i++) {
+    const double x = vec[3 * i], y = vec[3 * i + 1], z = vec[3 * i + 2], n = std::sqrt(x * x + y * y + z * z);
+    if (!std::isfinite(n) || !(n > 0) || !std::isfinite(pnt[3 * i]) || !std::isfinite(pnt[3 * i + 1]) || !std::isfinite(pnt[3 * i + 2])) return HB_EINVAL;
+    for (int k = 0; k < 3; k++) { h[3 * i + k] = pnt[3 * i + k]; h[3 * (size_t)n_ray + 3 * i + k] = (float)(vec[3 * i + k] / n); }
+  }
+  // the eligible geoms; one whose surface has no intersection routine refuses the whole configuration (Batch.ray_configure names it)
+  std::vector<int> geoms;
+  bool moving = false, hfield = false;
+  for (int g = 0; g < m.ngeom; g++) {
+    const int body = m.geom_bodyid[g], type = m.geom_type[g];
+    if (body == spec->bodyexclude || !(spec->flags & (body == 0 ? HB_RAY_STATIC : HB_RAY_MOVING))) continue;
+    if (type != GEOM_PLANE && type != GEOM_HFIELD && type != GEOM_SPHERE && type != GEOM_CAPSULE) {
+      if (!m.geom_contype[g] && !m.geom_conaffinity[g]) continue;  // (a visual marker: it collides with nothing, and no ray sees it)
+      return HB_EUNSUPPORTED;
+    }
+    geoms.push_back(g);
+    moving |= body != 0; hfield |= type == GEOM_HFIELD;
+  }
+  // from here on the previous configuration is replaced: nothing of it may still be in use
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  b->n_ray = 0;
+  const size_t nkin = spec->frame != HB_RAY_FRAME_WORLD || moving ? (size_t)b->n_env * ((size_t)m.nbody * 10 + (size_t)m.ngeom * 7) : 0;
+  if (b->d_ray.reserve(h.size()) != HB_OK || b->d_ray_geoms.reserve(geoms.size() + 1) != HB_OK || (nkin && b->d_ray_kin.reserve(nkin) != HB_OK)) return HB_ENOMEM;
+  HB_HIP(hipMemcpy(b->d_ray, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (!geoms.empty()) HB_HIP(hipMemcpy(b->d_ray_geoms, geoms.data(), geoms.size() * sizeof(int), hipMemcpyHostToDevice));
+  b->ray_spec = *spec; b->ray_ngeom = (int)geoms.size(); b->ray_moving = moving; b->ray_hfield = hfield;
+  b->n_ray = n_ray;
+  return HB_OK;
+}
+int hb_rays_dev(hb_batch* b, float* dist_dev, int* geomid_dev) {
+  if (!b || (!dist_dev && !geomid_dev) || b->n_ray < 1) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined: the rays see the state they leave)
+  const DevModel& dm = b->D.dm;
+  const bool framed = b->ray_spec.frame != HB_RAY_FRAME_WORLD;
+  float* d_body = b->d_ray_kin;
+  float* d_geom = d_body ? d_body + (size_t)b->n_env * dm.nbody * 10 : nullptr;
+  if (framed || b->ray_moving) {  // the poses the rays need, by the kinematics read-out's own launch; world-frame rays at static geoms need none
+    const int rc = kinematics_launch(b, b->d_state + 1, b->d_state + 1 + dm.nq, dm.nstate, dm.nstate, b->n_env, framed ? d_body : nullptr, nullptr,
+                                     b->ray_moving ? d_geom : nullptr, stream);
+    if (rc != HB_OK) return rc;
+  }
+  RayArgs A;
+  memset(&A, 0, sizeof A);
+  A.pnt = b->d_ray; A.vec = b->d_ray + 3 * (size_t)b->n_ray; A.geoms = b->d_ray_geoms;
+  A.n_ray = b->n_ray; A.n_geom = b->ray_ngeom; A.n_env = b->n_env;
+  A.frame = b->ray_spec.frame; A.frame_body = b->ray_spec.frame_body; A.cutoff = b->ray_spec.cutoff;
+  A.body_pose = framed ? d_body : nullptr; A.geom_pose = b->ray_moving ? d_geom : nullptr;
+  A.dr = b->d_dr; A.dr_stride = b->dr_stride; A.has_hfield = b->ray_hfield ? 1 : 0;
+  A.dist = dist_dev; A.geomid = geomid_dev;
+  HB_HIP(launch_rays(b->D.d_dm, dm, A, stream, &b->last_kernel));
+  return HB_OK;
+}
+int hb_rays(hb_batch* b, float* dist, int* geomid) {
+  if (!b || (!dist && !geomid) || b->n_ray < 1) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  const size_t n = (size_t)b->n_env * b->n_ray;
+  const hipStream_t stream = main_stream(b);  // (d_ray_out is idle: the host form before this one ended synchronised)
+  if (b->d_ray_out.reserve(2 * n) != HB_OK) return HB_ENOMEM;
+  float* d_dist = b->d_ray_out;
+  int* d_id = reinterpret_cast<int*>(d_dist + n);
+  const int rc = hb_rays_dev(b, dist ? d_dist : nullptr, geomid ? d_id : nullptr);
+  if (rc != HB_OK) return rc;
+  if (dist) HB_HIP(hipMemcpyAsync(dist, d_dist, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+  if (geomid) HB_HIP(hipMemcpyAsync(geomid, d_id, n * sizeof(int), hipMemcpyDeviceToHost, stream));
+  HB_HIP(hipStreamSynchronize(stream));
+  return HB_OK;
+}
+
 int hb_get_status(hb_batch* b, int* status) {
   if (!b || !status) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));

@@ -138,6 +138,14 @@ struct hb_batch {
   DevBuf<float> d_inv;  // hb_inverse's device copies: qacc [n_env][nv] | qfrc_inverse [n_env][nv] | warnings [n_env] (allocated by its first call)
   DevBuf<int> d_inv_scratch;  // hb_inverse_dev: the counts [n_env][kCountStride] | status [n_env] its launches write instead of the batch's
   DevBuf<float> d_kin;     // hb_kinematics / hb_kinematics_states: device copies of their host arrays (outputs | qpos | qvel), grown on demand
+  // ray read-out (hb_ray_configure, hb_rays*): the installed rays, pnt [n_ray][3] | vec [n_ray][3], and the eligible geoms in ascending order;
+  // the scratch hb_rays* runs the kinematics read-out into, body poses [n_env][nbody][10] | geom poses [n_env][ngeom][7] (allocated only for
+  // a configuration that needs either); the device copies of hb_rays' host arrays, dist [n_env][n_ray] | geomid [n_env][n_ray]
+  DevBuf<float> d_ray, d_ray_kin, d_ray_out;
+  DevBuf<int> d_ray_geoms;
+  hb_ray_spec ray_spec = {};
+  int n_ray = 0, ray_ngeom = 0;                  // n_ray 0: nothing configured
+  bool ray_moving = false, ray_hfield = false;   // a geom of a moving body / a height field is among the eligible geoms
   DevBuf<int> d_episode;
   int env_offset = 0;
   // realism layer (hb_env_randomize)

@@ -1,5 +1,5 @@
 // hb_device.hpp — device-side model tables and batch buffers (fp32), shared by the host
-// runtime (hb_tables.cpp, hb_batch.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip).
+// runtime (hb_tables.cpp, hb_batch.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip, hb_ray.hip).
 //
 // The model is replicated read-only per device as two flat arrays (int, float); DevModel holds
 // typed pointers into them plus the per-env LDS layout.  All tables are small (a few KB) and
@@ -456,6 +456,27 @@ struct KinArgs {
   float* body_pose;  // [n][nbody][10]
   float* body_vel;   // [n][nbody][6]
   float* geom_pose;  // [n][ngeom][7]
+};
+// arguments of the ray read-out (hb_ray.hip; hb_rays*): n_ray rays of hb_ray_configure against every env's geoms.  geoms: the eligible
+// geoms in ascending order (the host checked the types: plane, height field, sphere, capsule).  A geom of the world body has the model's
+// own pose; every other one is read from geom_pose, and the frame body from body_pose (hb_kin.hip's layouts; either null when unused).
+constexpr int kRayMax = 4096;       // most rays of a configuration
+constexpr int kRayBlock = 256;      // lanes of a block: up to four waves of 64 rays share the env's staged elevations
+constexpr int kRayLdsFloats = 8192; // elevations staged in LDS when the model has no more than this many (32 KB), read from memory otherwise
+struct RayArgs {
+  const float* pnt;        // [n_ray][3]
+  const float* vec;        // [n_ray][3], unit
+  const int* geoms;        // [n_geom]
+  int n_ray, n_geom, n_env;
+  int frame, frame_body;   // HB_RAY_FRAME_*
+  float cutoff;            // <= 0: none
+  const float* body_pose;  // [n_env][nbody][10], null for HB_RAY_FRAME_WORLD
+  const float* geom_pose;  // [n_env][ngeom][7], null when no geom of a moving body is eligible
+  const float* dr;         // nullable [n_env][dr_stride]: per-env model parameters (DomainLayout: the env's own elevations)
+  int dr_stride;
+  int has_hfield;          // a height field is among the geoms
+  float* dist;             // [n_env][n_ray], nullable
+  int* geomid;             // [n_env][n_ray], nullable
 };
 constexpr int kAccPark = 24;  // floats per body in BatchPtrs::body_acc_park (six 16-byte moves)
 

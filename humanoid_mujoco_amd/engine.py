@@ -42,6 +42,27 @@ class HbSizes(ctypes.Structure):
                                             "npair", "nobs", "ncon_max", "nefc_max")]
 
 
+class HbRaySpec(ctypes.Structure):
+    """hb_ray_spec (include/hb.h): frame, eligible geoms and cutoff of the installed rays."""
+    _fields_ = [("frame", ctypes.c_int), ("frame_body", ctypes.c_int), ("bodyexclude", ctypes.c_int), ("flags", ctypes.c_int), ("cutoff", ctypes.c_float)]
+
+
+RAY_STATIC, RAY_MOVING = 1, 2
+RAY_FRAMES = {"world": 0, "body": 1, "yaw": 2}
+RAY_SURFACES = (0, 1, 2, 3)  # geom types a ray intersects: plane, height field, sphere, capsule
+
+
+def height_scan_rays(xs, ys, z0=1.0):
+    """The downward grid of a terrain height scan: (pnt, vec) float32 [len(ys) * len(xs), 3], row-major over (y, x), pnt = (x, y, z0) and
+    vec = (0, 0, -1) - for Batch.ray_configure(..., frame="yaw")."""
+    xs, ys = np.asarray(xs, dtype=np.float32).reshape(-1), np.asarray(ys, dtype=np.float32).reshape(-1)
+    pnt = np.empty((len(ys), len(xs), 3), dtype=np.float32)
+    pnt[..., 0] = xs[None, :]; pnt[..., 1] = ys[:, None]; pnt[..., 2] = z0
+    vec = np.zeros_like(pnt)
+    vec[..., 2] = -1.0
+    return pnt.reshape(-1, 3), vec.reshape(-1, 3)
+
+
 class HbEnvConfig(ctypes.Structure):
     """hb_env_config (include/hb.h): reward / termination parameters of the env adapter."""
     _fields_ = [("target_velocity", ctypes.c_float * 2), ("target_z", ctypes.c_float), ("min_z", ctypes.c_float),
@@ -153,6 +174,8 @@ def lib():
     L.hb_inverse_dev.argtypes = [vp, vp, ci, vp, vp]
     L.hb_kinematics.argtypes = [vp, vp, vp, vp]; L.hb_kinematics_dev.argtypes = [vp, vp, vp, vp]
     L.hb_kinematics_states.argtypes = [vp, vp, vp, ci, vp, vp, vp]; L.hb_kinematics_states_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+    L.hb_ray_configure.argtypes = [vp, ctypes.POINTER(HbRaySpec), vp, vp, ci]
+    L.hb_rays.argtypes = [vp, vp, vp]; L.hb_rays_dev.argtypes = [vp, vp, vp]
     L.hb_state_size.argtypes = [vp, cu]
     L.hb_get_state.argtypes = [vp, cu, vp]; L.hb_set_state.argtypes = [vp, cu, vp]
     L.hb_get_state_f64.argtypes = [vp, cu, vp]; L.hb_set_state_f64.argtypes = [vp, cu, vp]
@@ -483,6 +506,50 @@ class Batch:
         assert int(n) < 2 ** 31, n
         _check(lib().hb_kinematics_states_dev(self._h, ctypes.c_void_p(qpos_ptr or 0), ctypes.c_void_p(qvel_ptr or 0), int(n), ctypes.c_void_p(pose_ptr or 0),
                                               ctypes.c_void_p(vel_ptr or 0), ctypes.c_void_p(geom_ptr or 0)), "hb_kinematics_states_dev")
+
+    # ---- ray casting (mj_ray of a fixed set of rays in every env; include/hb.h)
+    def _no_rays_why(self, rc, flags, bodyexclude):
+        """HB_EUNSUPPORTED (-4) from hb_ray_configure: name the first eligible geom that has no ray surface (include/hb.h)"""
+        if rc != -4:
+            return None
+        m = self.model
+        gtype, gbody = m.array("geom_type").astype(int), m.array("geom_bodyid").astype(int)
+        marker = (m.array("geom_contype") == 0) & (m.array("geom_conaffinity") == 0)
+        names = {5: "cylinder", 7: "mesh", 6: "box", 4: "ellipsoid"}
+        for g in range(m.ngeom):
+            if gbody[g] != bodyexclude and (flags & (RAY_STATIC if gbody[g] == 0 else RAY_MOVING)) and gtype[g] not in RAY_SURFACES and not marker[g]:
+                return ("geom %d (%s, a %s geom of body %r) would be eligible and rays intersect planes, height fields, spheres and capsules only"
+                        % (g, m.id2name("geom", g) or "unnamed", names.get(int(gtype[g]), "type %d" % gtype[g]), m.id2name("body", int(gbody[g]))))
+        return None
+
+    def ray_configure(self, pnt, vec, frame="world", frame_body=0, bodyexclude=-1, static=True, moving=True, cutoff=0.0):
+        """Installs rays (hb_ray_configure): pnt, vec [n_ray, 3] in the world frame, in frame_body's frame ("body": a rangefinder site) or in
+        its heading frame ("yaw": the height-scan frame); static / moving: geoms of the world body / of the other bodies are eligible,
+        less those of body bodyexclude; hits beyond cutoff (> 0) count as none.  pnt=None removes the rays.  A configuration that is
+        refused (HbError) leaves the previous one installed."""
+        if pnt is None:
+            _check(lib().hb_ray_configure(self._h, None, None, None, 0), "hb_ray_configure")
+            self._n_ray = 0
+            return
+        p, v = np.ascontiguousarray(pnt, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(vec, dtype=np.float32).reshape(-1, 3)
+        assert p.shape == v.shape, (p.shape, v.shape)
+        flags = (RAY_STATIC if static else 0) | (RAY_MOVING if moving else 0)
+        spec = HbRaySpec(RAY_FRAMES[frame] if isinstance(frame, str) else int(frame), int(frame_body), int(bodyexclude), flags, float(cutoff))
+        rc = lib().hb_ray_configure(self._h, ctypes.byref(spec), _ptr(p), _ptr(v), len(p))
+        _check(rc, "hb_ray_configure", self._no_rays_why(rc, flags, int(bodyexclude)))
+        self._n_ray = len(p)
+
+    def rays(self):
+        """(dist float32 [n_env, n_ray], geomid int32 [n_env, n_ray]) of the installed rays at the batch's state as it is now (hb_rays):
+        metres to the nearest eligible surface and the geom hit, -1 / -1 where nothing is.  The batch is left as it is."""
+        n = getattr(self, "_n_ray", 0)
+        dist, gid = np.empty((self.n_env, n), dtype=np.float32), np.empty((self.n_env, n), dtype=np.int32)
+        _check(lib().hb_rays(self._h, _ptr(dist) if n else None, _ptr(gid) if n else None), "hb_rays")
+        return dist, gid
+
+    def rays_dev(self, dist_ptr=None, geomid_ptr=None):
+        """the same into device arrays (addresses as int, None: not wanted); asynchronous (hb_rays_dev)"""
+        _check(lib().hb_rays_dev(self._h, ctypes.c_void_p(dist_ptr or 0), ctypes.c_void_p(geomid_ptr or 0)), "hb_rays_dev")
 
     def rollout(self, ctrl, want_qpos=False):
         c = np.ascontiguousarray(ctrl, dtype=np.float32)

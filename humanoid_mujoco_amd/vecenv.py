@@ -17,7 +17,7 @@ arrays) for callers that do not want N dicts per step; ``step_torch`` keeps ever
 """
 import numpy as np
 
-from .engine import WARN_BADQACC, WARN_BADQPOS, WARN_BADQVEL, WARN_CNSTRFULL, WARN_CONTACTFULL, Batch, Model
+from .engine import WARN_BADQACC, WARN_BADQPOS, WARN_BADQVEL, WARN_CNSTRFULL, WARN_CONTACTFULL, Batch, Model, height_scan_rays
 
 
 class Box:
@@ -50,14 +50,16 @@ _NO_INFO = {}  # (shared by the envs that did not finish an episode this step: S
 
 class VecEnv:
     def __init__(self, model, n_envs, device=0, n_substeps=1, randomization_factor=1.0, realism=False, domain_randomization=False, seed=0, team=False,
-                 contact_forces=False, body_accelerations=False, **reward_overrides):
+                 contact_forces=False, body_accelerations=False, height_scan=None, **reward_overrides):
         """realism=True adds CPUEnv's sensor/action noise, delay FIFOs and pushes (hb_env_randomization), scaled by
         randomization_factor exactly like the reset perturbation; domain_randomization=True draws per-env masses, floor
         friction, joint and actuator parameters at every reset (hb_domain_randomization).  team=True: the reference's own
         constants for its own robot (hb_env_team_config: obs[30] in JOINT_NAMES order, action[12], standup reset, kp = 2).
         contact_forces=True: the physics steps also write every body's contact wrench (hb_contact_readout), read with
         body_contact_forces(); such steps run the full step kernel.  body_accelerations=True: likewise every body's acceleration
-        (hb_body_acc_readout), read with body_accelerations()."""
+        (hb_body_acc_readout), read with body_accelerations().  height_scan=dict(body=..., xs=..., ys=..., z0=1.0, cutoff=2 * z0): a grid
+        of downward rays from z0 above `body` (id or name) at the offsets xs (forward) x ys (left) of its heading frame, at the geoms of the
+        world body only (hb_ray_configure: yaw frame, static), read with height_scan() / height_scan_torch(); the observation is unchanged."""
         self.model = model if isinstance(model, Model) else Model.load(model)
         self.batch = Batch(self.model, n_envs, device)
         self.num_envs = int(n_envs)
@@ -77,6 +79,20 @@ class VecEnv:
         self._body_accelerations = bool(body_accelerations)
         if self._body_accelerations:
             self.batch.body_acc_readout(True)
+        self._scan = None
+        self._device = int(device)
+        if height_scan is not None:
+            hs = dict(height_scan)
+            body = hs.pop("body")
+            body = self.model.name2id("body", body) if isinstance(body, str) else int(body)
+            xs, ys = np.asarray(hs.pop("xs"), dtype=np.float32).reshape(-1), np.asarray(hs.pop("ys"), dtype=np.float32).reshape(-1)
+            z0 = float(hs.pop("z0", 1.0))
+            cutoff = float(hs.pop("cutoff", 2.0 * z0))
+            if hs or cutoff <= 0:
+                raise ValueError("height_scan: body, xs, ys, z0 and a cutoff > 0 (got %r)" % sorted(hs))
+            pnt, vec = height_scan_rays(xs, ys, z0)
+            self.batch.ray_configure(pnt, vec, frame="yaw", frame_body=body, static=True, moving=False, cutoff=cutoff)
+            self._scan = (len(ys), len(xs), cutoff)
         self.realism = None
         if realism:
             self.realism = self.batch.env_default_randomization()
@@ -234,6 +250,33 @@ class VecEnv:
     def geom_poses(self):
         """[n_envs, ngeom, 7]: geom_xpos | orientation quaternion (w x y z) of every geom at the envs' current states"""
         return self.batch.kinematics(pose=False, vel=False, geoms=True)["geoms"]
+
+    def height_scan(self):
+        """[n_envs, len(ys), len(xs)] float32: the distance from each point of the scan grid (z0 above the body, in its heading frame)
+        down to the terrain at the envs' current states, `cutoff` where nothing is hit (Batch.rays; computed on demand from qpos)"""
+        if self._scan is None:
+            raise RuntimeError("height_scan: create the VecEnv with height_scan=dict(body=..., xs=..., ys=...)")
+        ny, nx, cutoff = self._scan
+        dist, gid = self.batch.rays()
+        return np.where(gid >= 0, dist, np.float32(cutoff)).astype(np.float32).reshape(self.num_envs, ny, nx)
+
+    def height_scan_torch(self):
+        """The same as a float32 CUDA tensor, without a host transfer or synchronisation (hb_rays_dev): ordered behind the steps made so
+        far on the batch's stream and visible to the caller's current torch stream, like step_torch's outputs."""
+        import torch
+        if self._scan is None:
+            raise RuntimeError("height_scan_torch: create the VecEnv with height_scan=dict(body=..., xs=..., ys=...)")
+        ny, nx, cutoff = self._scan
+        dev = torch.device("cuda", self._device)
+        if getattr(self, "_t_scan", None) is None:
+            self._t_scan = (torch.empty((self.num_envs, ny * nx), dtype=torch.float32, device=dev), torch.empty((self.num_envs, ny * nx), dtype=torch.int32, device=dev))
+        stream = torch.cuda.ExternalStream(self.batch.stream, device=dev)  # (fetching the stream launches held step calls and joins the pipes)
+        cur = torch.cuda.current_stream(dev)
+        stream.wait_stream(cur)  # whoever still reads the previous scan is done before it is rewritten
+        dist, gid = self._t_scan
+        self.batch.rays_dev(dist.data_ptr(), gid.data_ptr())
+        cur.wait_stream(stream)
+        return torch.where(gid >= 0, dist, torch.full_like(dist, cutoff)).reshape(self.num_envs, ny, nx)
 
     def warning_counts(self):
         """Number of envs currently carrying each warning bit."""

@@ -246,6 +246,58 @@ int hb_kinematics_dev(hb_batch* b, float* body_pose_dev, float* body_vel_dev, fl
 int hb_kinematics_states(hb_batch* b, const float* qpos, const float* qvel, int n, float* body_pose, float* body_vel, float* geom_pose);
 int hb_kinematics_states_dev(hb_batch* b, const float* qpos_dev, const float* qvel_dev, int n, float* body_pose_dev, float* body_vel_dev, float* geom_pose_dev);
 
+/* ---- ray casting ------------------------------------------------------------------------------------------------------ */
+
+/* Replaces mj_ray / mj_multiRay (mujoco.h) [recall] for a fixed set of rays cast in every env: what a rangefinder, or the grid of downward
+ * rays of a terrain height scan, sees from the batch's state.
+ * hb_ray_configure installs n_ray rays, 1 <= n_ray <= 4096: pnt / vec are host arrays [n_ray][3], origin and direction in the frame the
+ * spec names.  They are copied to the device, into a buffer the batch owns, and stay installed until replaced or removed (n_ray 0 or a
+ * NULL spec).  vec is normalised here; a zero or non-finite vector (or a non-finite pnt) gives HB_EINVAL.
+ *   HB_RAY_FRAME_WORLD  world coordinates
+ *   HB_RAY_FRAME_BODY   coordinates of frame_body's frame (xpos, xquat): a rangefinder site
+ *   HB_RAY_FRAME_YAW    the heading frame of frame_body, the height-scan frame: origin = xpos[frame_body]; x = the body's x axis projected
+ *                       onto the world xy plane and normalised, or the world x axis when that projection is shorter than 1e-6; z = world
+ *                       z; y = z x x
+ * Eligible geoms: those of the world body with HB_RAY_STATIC, those of every other body with HB_RAY_MOVING, less the geoms of body
+ * bodyexclude (-1: none).  The surfaces are mj_rayGeom's [recall]:
+ *   plane        the z = 0 plane of the geom frame, hit from either side, inside size[0..1] where those are > 0
+ *   sphere       the smallest non-negative root; from inside that is the exit point
+ *   capsule      likewise, on the cylinder wall between the caps and the outer halves of the two end spheres
+ *   height field the elevation surface, triangulated exactly as the collider triangulates it: cell (r, c) is cut along the diagonal
+ *                (r, c) - (r + 1, c + 1).  Both faces are hit.  With per-env elevations installed (hb_env_domain_randomize with
+ *                floor_bump_max > 0) the env's OWN elevations are used.  The field's side walls and base are NOT intersected - a
+ *                departure from MuJoCo, which also tests the field's bounding box: a ray that passes under the surface from the side
+ *                sees the surface from below, or nothing.
+ * Mesh and cylinder geoms (and box and ellipsoid ones) are not intersected: a configuration under which a geom of such a type would be
+ * eligible is refused with HB_EUNSUPPORTED (Batch.ray_configure names the geom), e.g. HB_RAY_MOVING on the reference's robot, whose
+ * HB_RAY_STATIC configurations see its height-field floor.  The one exception: a geom of such a type that collides with nothing (contype
+ * and conaffinity both 0 - a visual marker, like the axis cylinders of the reference's world) is skipped, not refused.  A refused configuration (HB_EUNSUPPORTED or HB_EINVAL) leaves the previous
+ * one installed and the batch stepping.  HB_EINVAL: NULL batch or arrays, n_ray out of range, an unknown frame, frame_body or
+ * bodyexclude out of range, flags without HB_RAY_STATIC or HB_RAY_MOVING.
+ * hb_rays / hb_rays_dev cast the installed rays at the batch's qpos AS IT IS NOW (after a step: the new state, as for hb_kinematics):
+ *   dist   [n_env][n_ray]  metres along the unit direction to the nearest eligible surface; a hit farther than cutoff (> 0) counts as none
+ *   geomid [n_env][n_ray]  the geom that was hit; ties go to the lowest geom id
+ * Both are -1 where nothing is hit: mj_ray's return convention.  Either may be NULL, not both.  Step calls held back (hb_step_dev) are
+ * launched first and the pipes joined.  Nothing of the batch is written: state, warm start, status and warning words, counts and orders
+ * stay as they are.  The arithmetic is fp32, one lane per ray, without atomics: a ray's result has the same bits whatever n_env is and
+ * wherever the ray stands in the array.  A non-finite state makes that env's rows unspecified and nothing else.  The rays are a kernel
+ * of their own (csrc/hb_ray.hip; "hb_ray_kernel" / "hb_ray_lds_kernel" in hb_last_kernel - the latter stages the env's elevations in LDS),
+ * behind the kinematics read-out's launch for the poses it needs (none for world-frame rays at static geoms); hb_batch_step_launches
+ * counts neither.  HB_EINVAL: nothing configured, or both outputs NULL.  hb_rays is synchronous with host arrays; hb_rays_dev takes
+ * device arrays and is asynchronous like hb_kinematics_dev. */
+#define HB_RAY_STATIC 1      /* geoms of the world body are eligible (terrain, floor) */
+#define HB_RAY_MOVING 2      /* geoms of moving bodies are eligible */
+#define HB_RAY_FRAME_WORLD 0 /* pnt / vec are world coordinates */
+#define HB_RAY_FRAME_BODY 1  /* ... coordinates of frame_body's frame (xpos, xquat): a rangefinder site */
+#define HB_RAY_FRAME_YAW 2   /* ... of the heading frame of frame_body: the height-scan frame */
+typedef struct hb_ray_spec {
+  int frame, frame_body, bodyexclude /* -1: none */, flags;
+  float cutoff; /* > 0: hits farther than this count as no hit; <= 0: no limit */
+} hb_ray_spec;
+int hb_ray_configure(hb_batch* b, const hb_ray_spec* spec, const float* pnt, const float* vec, int n_ray);
+int hb_rays(hb_batch* b, float* dist, int* geomid);
+int hb_rays_dev(hb_batch* b, float* dist_dev, int* geomid_dev);
+
 /* ---- wire format of a state ------------------------------------------------------------ */
 
 /* One env's state as the `State` message of the reference's gRPC agent service (mujoco_mpc/mjpc/grpc/agent.proto:75-83:
