@@ -1,5 +1,5 @@
 // hb_batch.hpp — internal to libhb.so: the model and batch handles behind include/hb.h, the owner of their device memory, and the
-// launch plumbing (hb_batch.cpp) the C-ABI translation units (hb_api.cpp, hb_api_rollout.cpp, hb_api_env.cpp) share.
+// launch plumbing (hb_batch.cpp) the C-ABI translation units (hb_api.cpp, hb_api_rollout.cpp, hb_api_env.cpp, hb_api_dyn.cpp) share.
 #pragma once
 #include "../../include/hb.h"
 #include "hb_device.hpp"
@@ -138,6 +138,7 @@ struct hb_batch {
   DevBuf<float> d_inv;  // hb_inverse's device copies: qacc [n_env][nv] | qfrc_inverse [n_env][nv] | warnings [n_env] (allocated by its first call)
   DevBuf<int> d_inv_scratch;  // hb_inverse_dev: the counts [n_env][kCountStride] | status [n_env] its launches write instead of the batch's
   DevBuf<float> d_kin;     // hb_kinematics / hb_kinematics_states: device copies of their host arrays (outputs | qpos | qvel), grown on demand
+  DevBuf<float> d_dyn;     // hb_dynamics / hb_dynamics_states: device copies of their host arrays (outputs | qpos | qvel), grown on demand
   // ray read-out (hb_ray_configure, hb_rays*): the installed rays, pnt [n_ray][3] | vec [n_ray][3], and the eligible geoms in ascending order;
   // the scratch hb_rays* runs the kinematics read-out into, body poses [n_env][nbody][10] | geom poses [n_env][ngeom][7] (allocated only for
   // a configuration that needs either); the device copies of hb_rays' host arrays, dist [n_env][n_ray] | geomid [n_env][n_ray]

@@ -1,5 +1,5 @@
 // hb_device.hpp — device-side model tables and batch buffers (fp32), shared by the host
-// runtime (hb_tables.cpp, hb_batch.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip, hb_ray.hip).
+// runtime (hb_tables.cpp, hb_batch.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip, hb_ray.hip, hb_dyn.hip).
 //
 // The model is replicated read-only per device as two flat arrays (int, float); DevModel holds
 // typed pointers into them plus the per-env LDS layout.  All tables are small (a few KB) and
@@ -456,6 +456,24 @@ struct KinArgs {
   float* body_pose;  // [n][nbody][10]
   float* body_vel;   // [n][nbody][6]
   float* geom_pose;  // [n][ngeom][7]
+};
+// arguments of the dynamics read-out (hb_dyn.hip; hb_dynamics*): n states addressed as in KinArgs (qvel null: zero velocities, for M and
+// Jacobians only); dr nullable [n][dr_stride]: state k's own masses, armature and stiffness (DomainLayout); the outputs are nullable,
+// layouts in include/hb.h; the Jacobian points are hb_jac_spec's (kind 0: a point fixed in the body's frame, 1: the subtree's centre of mass)
+constexpr int kJacMax = 16;
+struct DynArgs {
+  const float* qpos;
+  const float* qvel;
+  int qpos_stride, qvel_stride;
+  long long n;
+  const float* dr;
+  int dr_stride;
+  float* M;        // [n][nv][nv]
+  float* bias;     // [n][nv]
+  float* passive;  // [n][nv]
+  float* jac;      // [n][njac][6][nv]
+  int njac, jkind[kJacMax], jbody[kJacMax];
+  float joff[kJacMax][3];
 };
 // arguments of the ray read-out (hb_ray.hip; hb_rays*): n_ray rays of hb_ray_configure against every env's geoms.  geoms: the eligible
 // geoms in ascending order (the host checked the types: plane, height field, sphere, capsule).  A geom of the world body has the model's

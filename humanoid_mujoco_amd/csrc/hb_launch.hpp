@@ -1,4 +1,4 @@
-// hb_launch.hpp — host-callable launchers implemented in the kernel translation units (hb_step.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip, hb_ray.hip)
+// hb_launch.hpp — host-callable launchers implemented in the kernel translation units (hb_step.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip, hb_ray.hip, hb_dyn.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "hb_device.hpp"
@@ -10,6 +10,8 @@ hipError_t launch_step(const DevModel* M_dev, const DevModel& M, const BatchPtrs
 hipError_t launch_inverse(const DevModel* M_dev, const DevModel& M, const BatchPtrs& P, hipStream_t stream, const char** kernel);
 // whole-body kinematics of A.n states (hb_kin.hip): pack = 0 one state per wave, 1 as many as fit (HB_TUNE_KIN_PACK)
 hipError_t launch_kinematics(const DevModel* M_dev, const DevModel& M, const KinArgs& A, int pack, hipStream_t stream, const char** kernel);
+// mass matrix, bias and passive forces and Jacobians of A.n states (hb_dyn.hip; hb_dynamics*): pack as for launch_kinematics
+hipError_t launch_dynamics(const DevModel* M_dev, const DevModel& M, const DynArgs& A, int pack, hipStream_t stream, const char** kernel);
 // the configured rays against every env's geoms (hb_ray.hip; hb_rays*)
 hipError_t launch_rays(const DevModel* M_dev, const DevModel& M, const RayArgs& A, hipStream_t stream, const char** kernel);
 // two envs per wave: a lean launch of the 27-dof humanoid's PGS kernel (hb_step_duo.hip; chosen by launch_step)

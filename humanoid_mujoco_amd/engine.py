@@ -47,6 +47,12 @@ class HbRaySpec(ctypes.Structure):
     _fields_ = [("frame", ctypes.c_int), ("frame_body", ctypes.c_int), ("bodyexclude", ctypes.c_int), ("flags", ctypes.c_int), ("cutoff", ctypes.c_float)]
 
 
+class HbJacSpec(ctypes.Structure):
+    """hb_jac_spec (include/hb.h): the points whose Jacobians hb_dynamics* returns."""
+    _fields_ = [("n", ctypes.c_int), ("kind", ctypes.c_int * 16), ("body", ctypes.c_int * 16), ("offset", (ctypes.c_float * 3) * 16)]
+
+
+MAX_JAC, JAC_POINT, JAC_SUBTREE_COM = 16, 0, 1
 RAY_STATIC, RAY_MOVING = 1, 2
 RAY_FRAMES = {"world": 0, "body": 1, "yaw": 2}
 RAY_SURFACES = (0, 1, 2, 3)  # geom types a ray intersects: plane, height field, sphere, capsule
@@ -174,6 +180,9 @@ def lib():
     L.hb_inverse_dev.argtypes = [vp, vp, ci, vp, vp]
     L.hb_kinematics.argtypes = [vp, vp, vp, vp]; L.hb_kinematics_dev.argtypes = [vp, vp, vp, vp]
     L.hb_kinematics_states.argtypes = [vp, vp, vp, ci, vp, vp, vp]; L.hb_kinematics_states_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+    jp = ctypes.POINTER(HbJacSpec)
+    L.hb_dynamics.argtypes = [vp, vp, vp, vp, jp, vp]; L.hb_dynamics_dev.argtypes = [vp, vp, vp, vp, jp, vp]
+    L.hb_dynamics_states.argtypes = [vp, vp, vp, ci, vp, vp, vp, jp, vp]; L.hb_dynamics_states_dev.argtypes = [vp, vp, vp, ci, vp, vp, vp, jp, vp]
     L.hb_ray_configure.argtypes = [vp, ctypes.POINTER(HbRaySpec), vp, vp, ci]
     L.hb_rays.argtypes = [vp, vp, vp]; L.hb_rays_dev.argtypes = [vp, vp, vp]
     L.hb_state_size.argtypes = [vp, cu]
@@ -366,6 +375,30 @@ class Model:
         lib().hb_model_get_array(self._h, field.encode(), _ptr(out), n)
         return out
 
+    def jac_spec(self, bodies=(), sites=(), body_coms=(), subtree_coms=()):
+        """The points of a Jacobian read-out (HbJacSpec, at most 16), in this order: the frame origins of `bodies` (mj_jacBody), the
+        `sites` as (body, offset in the body's frame) pairs (mj_jacSite), the centres of mass of `body_coms` (mj_jacBodyCom) and of the
+        subtrees rooted at `subtree_coms` (mj_jacSubtreeCom).  Bodies are names or ids."""
+        m = self
+
+        def bid(b):
+            i = m.name2id("body", b) if isinstance(b, str) else int(b)
+            if not 0 <= i < m.nbody:
+                raise ValueError("jac_spec: no body %r" % (b,))
+            return i
+        ipos = m.array("body_ipos").reshape(-1, 3)
+        pts = [(JAC_POINT, bid(b), (0.0, 0.0, 0.0)) for b in bodies] + [(JAC_POINT, bid(b), tuple(float(x) for x in off)) for b, off in sites]
+        pts += [(JAC_POINT, bid(b), tuple(ipos[bid(b)])) for b in body_coms] + [(JAC_SUBTREE_COM, bid(b), (0.0, 0.0, 0.0)) for b in subtree_coms]
+        if not 1 <= len(pts) <= MAX_JAC:
+            raise ValueError("jac_spec: %d points, 1 to %d are supported" % (len(pts), MAX_JAC))
+        spec = HbJacSpec()
+        spec.n = len(pts)
+        for k, (kind, body, off) in enumerate(pts):
+            spec.kind[k], spec.body[k] = kind, body
+            for i in range(3):
+                spec.offset[k][i] = off[i]
+        return spec
+
     # ---- equality constraints (include/hb.h: hb_batch_create)
     @property
     def neq(self):
@@ -506,6 +539,58 @@ class Batch:
         assert int(n) < 2 ** 31, n
         _check(lib().hb_kinematics_states_dev(self._h, ctypes.c_void_p(qpos_ptr or 0), ctypes.c_void_p(qvel_ptr or 0), int(n), ctypes.c_void_p(pose_ptr or 0),
                                               ctypes.c_void_p(vel_ptr or 0), ctypes.c_void_p(geom_ptr or 0)), "hb_kinematics_states_dev")
+
+    # ---- dynamics read-out (mj_fullM, qfrc_bias, qfrc_passive, mj_jac*; include/hb.h: hb_dynamics)
+    def jac_spec(self, bodies=(), sites=(), body_coms=(), subtree_coms=()):
+        """the points of a Jacobian read-out, for dynamics(jac=...): Model.jac_spec"""
+        return self.model.jac_spec(bodies=bodies, sites=sites, body_coms=body_coms, subtree_coms=subtree_coms)
+
+    def _dyn_out(self, lead, M, bias, passive, jac):
+        nv = self.model.nv
+        return (np.empty(lead + (nv, nv), dtype=np.float32) if M else None, np.empty(lead + (nv,), dtype=np.float32) if bias else None,
+                np.empty(lead + (nv,), dtype=np.float32) if passive else None, np.empty(lead + (jac.n, 6, nv), dtype=np.float32) if jac is not None else None)
+
+    @staticmethod
+    def _dyn_dict(M, b, p, j):
+        return {k: a for k, a in (("M", M), ("bias", b), ("passive", p), ("jac", j)) if a is not None}
+
+    def dynamics(self, M=True, bias=True, passive=True, jac=None):
+        """The terms of the equations of motion of every env at its state as it is now (include/hb.h: hb_dynamics): a dict of float32
+        arrays, "M" [n_env, nv, nv] the dense mass matrix (mj_fullM), "bias" [n_env, nv] qfrc_bias, "passive" [n_env, nv] qfrc_passive,
+        "jac" [n_env, jac.n, 6, nv] = jacp | jacr of the points of `jac` (a jac_spec) - those asked for.  With domain randomisation
+        installed every env's own masses, armature and stiffness enter.  The batch is left as it is."""
+        Mo, b, p, j = self._dyn_out((self.n_env,), M, bias, passive, jac)
+        _check(lib().hb_dynamics(self._h, _ptr(Mo), _ptr(b), _ptr(p), ctypes.byref(jac) if jac is not None else None, _ptr(j)), "hb_dynamics")
+        return self._dyn_dict(Mo, b, p, j)
+
+    def dynamics_dev(self, M_ptr=None, bias_ptr=None, passive_ptr=None, jac=None, jac_ptr=None):
+        """the same into device arrays (addresses as int, None: not wanted); asynchronous (hb_dynamics_dev)"""
+        _check(lib().hb_dynamics_dev(self._h, ctypes.c_void_p(M_ptr or 0), ctypes.c_void_p(bias_ptr or 0), ctypes.c_void_p(passive_ptr or 0),
+                                     ctypes.byref(jac) if jac is not None else None, ctypes.c_void_p(jac_ptr or 0)), "hb_dynamics_dev")
+
+    def dynamics_states(self, qpos, qvel=None, M=True, bias=True, passive=True, jac=None):
+        """the same of given states with the model's nominal parameters (hb_dynamics_states): qpos [n, nq] or [T, n_env, nq], qvel
+        likewise (may be None with bias=False, passive=False); any n.  The arrays of the returned dict have qpos' leading shape."""
+        q = np.ascontiguousarray(qpos, dtype=np.float32)
+        assert q.ndim >= 2 and q.shape[-1] == self.model.nq, q.shape
+        lead = q.shape[:-1]
+        n = int(np.prod(lead))
+        assert n < 2 ** 31, "hb_dynamics_states takes the number of states as an int: %d states, split the call" % n
+        qv = None
+        if qvel is not None:
+            qv = np.ascontiguousarray(qvel, dtype=np.float32)
+            assert qv.shape == lead + (self.model.nv,), qv.shape
+        Mo, b, p, j = self._dyn_out(lead, M, bias, passive, jac)
+        _check(lib().hb_dynamics_states(self._h, _ptr(q), _ptr(qv), n, _ptr(Mo), _ptr(b), _ptr(p), ctypes.byref(jac) if jac is not None else None, _ptr(j)),
+               "hb_dynamics_states")
+        return self._dyn_dict(Mo, b, p, j)
+
+    def dynamics_states_dev(self, qpos_ptr, qvel_ptr, n, M_ptr=None, bias_ptr=None, passive_ptr=None, jac=None, jac_ptr=None):
+        """device arrays: qpos [n, nq], qvel [n, nv] (None without bias_ptr and passive_ptr) in, the outputs asked for out; asynchronous"""
+        assert int(n) < 2 ** 31, n
+        _check(lib().hb_dynamics_states_dev(self._h, ctypes.c_void_p(qpos_ptr or 0), ctypes.c_void_p(qvel_ptr or 0), int(n), ctypes.c_void_p(M_ptr or 0),
+                                            ctypes.c_void_p(bias_ptr or 0), ctypes.c_void_p(passive_ptr or 0), ctypes.byref(jac) if jac is not None else None,
+                                            ctypes.c_void_p(jac_ptr or 0)), "hb_dynamics_states_dev")
 
     # ---- ray casting (mj_ray of a fixed set of rays in every env; include/hb.h)
     def _no_rays_why(self, rc, flags, bodyexclude):

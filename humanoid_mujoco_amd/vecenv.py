@@ -278,6 +278,36 @@ class VecEnv:
         cur.wait_stream(stream)
         return torch.where(gid >= 0, dist, torch.full_like(dist, cutoff)).reshape(self.num_envs, ny, nx)
 
+    def dynamics(self, M=True, bias=True, passive=True, jac=None):
+        """dict of float32 arrays, those asked for: "M" [n_envs, nv, nv], "bias" and "passive" [n_envs, nv], "jac" [n_envs, jac.n, 6, nv]
+        (jac: a Batch.jac_spec) at the envs' current states - the states the last returned observations describe (Batch.dynamics)"""
+        return self.batch.dynamics(M=M, bias=bias, passive=passive, jac=jac)
+
+    def dynamics_torch(self, M=True, bias=True, passive=True, jac=None):
+        """The same as float32 CUDA tensors, without a host transfer or synchronisation (hb_dynamics_dev): ordered behind the steps made
+        so far on the batch's stream and visible to the caller's current torch stream, like step_torch's outputs.  The tensors are
+        rewritten by the next call that asks for the same outputs."""
+        import torch
+        nv, n = self.batch.model.nv, self.num_envs
+        dev = torch.device("cuda", self._device)
+        shapes = {"M": (n, nv, nv) if M else None, "bias": (n, nv) if bias else None, "passive": (n, nv) if passive else None,
+                  "jac": (n, jac.n, 6, nv) if jac is not None else None}
+        if getattr(self, "_t_dyn", None) is None:
+            self._t_dyn = {}
+        out = {}
+        for k, shape in shapes.items():
+            if shape is not None:
+                if k not in self._t_dyn or tuple(self._t_dyn[k].shape) != shape:
+                    self._t_dyn[k] = torch.empty(shape, dtype=torch.float32, device=dev)
+                out[k] = self._t_dyn[k]
+        stream = torch.cuda.ExternalStream(self.batch.stream, device=dev)  # (fetching the stream launches held step calls and joins the pipes)
+        cur = torch.cuda.current_stream(dev)
+        stream.wait_stream(cur)  # whoever still reads the previous tensors is done before they are rewritten
+        ptr = {k: out[k].data_ptr() if k in out else None for k in shapes}
+        self.batch.dynamics_dev(ptr["M"], ptr["bias"], ptr["passive"], jac, ptr["jac"])
+        cur.wait_stream(stream)
+        return out
+
     def warning_counts(self):
         """Number of envs currently carrying each warning bit."""
         w = self.batch.status()

@@ -246,6 +246,51 @@ int hb_kinematics_dev(hb_batch* b, float* body_pose_dev, float* body_vel_dev, fl
 int hb_kinematics_states(hb_batch* b, const float* qpos, const float* qvel, int n, float* body_pose, float* body_vel, float* geom_pose);
 int hb_kinematics_states_dev(hb_batch* b, const float* qpos_dev, const float* qvel_dev, int n, float* body_pose_dev, float* body_vel_dev, float* geom_pose_dev);
 
+/* ---- dynamics read-out ----------------------------------------------------------------------------------------------- */
+
+/* Replaces mj_fullM of mjData.qM, reads of mjData.qfrc_bias and mjData.qfrc_passive, and mj_jacBody / mj_jacSite / mj_jacBodyCom /
+ * mj_jacSubtreeCom: the terms of the equations of motion  M qacc + qfrc_bias = qfrc_passive + qfrc_actuator + J' f  of every state, as a
+ * pure function of (qpos, qvel) and the model.
+ *   M            [n][nv][nv]         the dense symmetric joint-space inertia, armature included; both triangles are written from one
+ *                                    computed value: M[i][j] and M[j][i] have the same bits
+ *   qfrc_bias    [n][nv]             mj_rne with zero acceleration: Coriolis, centrifugal and gravity terms (none of the last under mjDSBL_GRAVITY)
+ *   qfrc_passive [n][nv]             what hb_forward forms: joint springs and dampers (zero under mjDSBL_PASSIVE)
+ *   jac          [n][spec.n][6][nv]  per point of the spec: rows 0..2 jacp, rows 3..5 jacr, world axes
+ * The dofs of a free joint follow MuJoCo's convention: translations along the world axes, rotations about the body's own axes.
+ * A point of the spec is HB_JAC_POINT: fixed in `body`'s frame at `offset` (body coordinates) - offset 0 is mj_jacBody, a site's pos
+ * mj_jacSite, the body's ipos mj_jacBodyCom; or HB_JAC_SUBTREE_COM: the centre of mass of the subtree rooted at `body` (mj_jacSubtreeCom;
+ * translational rows only, the rotational rows are zero, offset is ignored).  The spec is the same for every state.
+ * Any output may be NULL, not all of them; jac and spec go together.
+ * hb_dynamics / hb_dynamics_dev evaluate the batch's state AS IT IS NOW (n = n_env; after a step the NEW state, as hb_kinematics does):
+ * step calls held back (hb_step_dev) are launched first and the pipes joined.  With per-env model parameters installed
+ * (hb_env_domain_randomize) they use each env's own masses, armature and stiffness, as the step kernels do.
+ * hb_dynamics_states / _states_dev evaluate n >= 1 given states, qpos [n][nq] and qvel [n][nv] row-major, with the model's nominal
+ * parameters: n is not tied to n_env, qvel may be NULL when only M and jac are asked for, and the batch is used for its model, device and
+ * stream only.
+ * The calls read and compute: state, warm start, status and warning words, counts and orders of the batch stay as they are, and a free
+ * joint's quaternion is normalised for the computation only.  A non-finite state makes the rows of that state unspecified and nothing
+ * else.  No model is refused, whatever kernels it steps in: the read-out is a kernel of its own (csrc/hb_dyn.hip, no atomics: every sum
+ * runs in a fixed order, so a state's result has the same bits whatever n is and wherever the state stands), hb_last_kernel names it
+ * ("hb_dyn16_kernel" / "hb_dyn32_kernel" / "hb_dyn64_kernel": HB_TUNE_KIN_PACK chooses as for hb_kinematics), and
+ * hb_batch_step_launches does not count it.  HB_EINVAL: NULL batch, all outputs NULL, exactly one of jac and spec, spec.n outside
+ * 1..HB_MAX_JAC, a body or kind out of range, n <= 0, NULL qpos, qfrc_bias or qfrc_passive without qvel.
+ * The host forms are synchronous; the _dev forms take device arrays (the spec stays a host struct) and are asynchronous like
+ * hb_kinematics_dev. */
+#define HB_MAX_JAC 16
+#define HB_JAC_POINT 0       /* a point fixed in body's frame at `offset` (body frame) */
+#define HB_JAC_SUBTREE_COM 1 /* mj_jacSubtreeCom of the subtree rooted at `body`: translational rows only, rotational rows zero */
+typedef struct hb_jac_spec {
+  int n;
+  int kind[HB_MAX_JAC];
+  int body[HB_MAX_JAC];
+  float offset[HB_MAX_JAC][3];
+} hb_jac_spec;
+int hb_dynamics(hb_batch* b, float* M, float* qfrc_bias, float* qfrc_passive, const hb_jac_spec* spec, float* jac);
+int hb_dynamics_dev(hb_batch* b, float* M_dev, float* qfrc_bias_dev, float* qfrc_passive_dev, const hb_jac_spec* spec, float* jac_dev);
+int hb_dynamics_states(hb_batch* b, const float* qpos, const float* qvel, int n, float* M, float* qfrc_bias, float* qfrc_passive, const hb_jac_spec* spec, float* jac);
+int hb_dynamics_states_dev(hb_batch* b, const float* qpos_dev, const float* qvel_dev, int n, float* M_dev, float* qfrc_bias_dev, float* qfrc_passive_dev,
+                           const hb_jac_spec* spec, float* jac_dev);
+
 /* ---- ray casting ------------------------------------------------------------------------------------------------------ */
 
 /* Replaces mj_ray / mj_multiRay (mujoco.h) [recall] for a fixed set of rays cast in every env: what a rangefinder, or the grid of downward
@@ -527,7 +572,7 @@ int hb_batch_device_name(const hb_batch* b, char* out, int cap);
  *                          pipelined; 0 never; 2 always
  *   HB_TUNE_FOLD           hb_step_dev calls enqueued back to back run as ONE launch of up to this many steps (default and maximum 256; 1:
  *                          every call its own launch).  See hb_step_dev.
- *   HB_TUNE_KIN_PACK       hb_kinematics*: 1 (default) as many states per wavefront as fit (16 or 32 lanes per state for models of up to 16 /
+ *   HB_TUNE_KIN_PACK       hb_kinematics* and hb_dynamics*: 1 (default) as many states per wavefront as fit (16 or 32 lanes per state for models of up to 16 /
  *                          32 moving bodies); 0: one state per wavefront.  The same bits (tests/test_gpu_kinematics.py)
  * Environment variables the library reads (all others of earlier rounds are gone): HB_DEBUG (name failing HIP calls on stderr), HB_DUO
  * (HB_TUNE_DUO's value for new batches), HB_BOX_CULL=0 (model tables without the oriented-box cull of portal-search pairs: a test),
