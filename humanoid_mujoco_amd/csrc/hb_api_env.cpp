@@ -503,4 +503,15 @@ int hb_env_warnings(hb_batch* b, int* warnings) {
   return HB_OK;
 }
 
+int hb_env_joint_torques(hb_batch* b, float* qfrc) {
+  if (!b || !qfrc) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  hipStream_t st = main_stream(b);
+  HB_HIP(hipMemcpyAsync(qfrc, b->d_qfrc, (size_t)b->n_env * b->D.dm.nv * sizeof(float), hipMemcpyDeviceToHost, st));
+  HB_HIP(hipStreamSynchronize(st));
+  return HB_OK;
+}
+
 }  // extern "C"

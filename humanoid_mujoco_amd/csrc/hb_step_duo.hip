@@ -1140,6 +1140,7 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       const float nAinv = -1.f / Aii;
       float arf = 0.f;
       const int nmax2 = max(nLo, nHi);
+      const bool short16 = nmax2 <= 16;  // both envs at most 16 rows: the sweeps take the broadcast row step (HB_PGS_ROWB below)
       {
         const float jar = jw - aref;
         force = (rowact && jar < 0.f) ? -Dd * jar : 0.f;
@@ -1195,6 +1196,59 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
                  : [na] "v"(nAinv), [nf] "v"(nforce), [ar0] "v"(arS[(c) * 4]), [ar1] "v"(arS[(c) * 4 + 1]), [ar2] "v"(arS[(c) * 4 + 2]), \
                    [ar3] "v"(arS[(c) * 4 + 3 < 31 ? (c) * 4 + 3 : 30]), [i0] "n"((c) * 4), [lo] "s"(0x00000000ffffffffull), [hi] "s"(0xffffffff00000000ull)); \
   }
+      // Both envs at most 16 rows (short16): every row of an env lies in ONE DPP row of 16 lanes (row 0 for env A, row 2 for env B), and lane k's value
+      // reaches the row lanes of its own env by the DPP control row_newbcast:k inside the vector pipe - no v_readlane, no SGPR, no EXEC
+      // write.  Lanes 16..31 and 48..63 read lane 16 + k of their own row: a lane without a row, whose proposal is -0 and whose AR column is 0.
+#define HB_BCAST_FMAC(k) "v_fmac_f32_dpp %[r], %[d], %[ar" #k "] row_newbcast:%[k" #k "] row_mask:0xf bank_mask:0xf\n\t"
+      // The same row step when both envs have at most 16 rows (short16), 4 VALU and one scalar shift: the proposal d = max(res * nAinv, nforce)
+      // on every lane, lanes k and 32 + k keep it as their step (v_cndmask under a 64-bit mask that walks up one lane per row), and ONE
+      // v_fmac_f32_dpp row_newbcast:k hands lane k's proposal to the row lanes of its own env, each half with its own.  Nothing writes EXEC
+      // and no vector instruction reads an SGPR that a vector instruction wrote.  Lane k keeps what it keeps above: its proposal of row step
+      // k, for every k the chunks run (the padding rows of the last chunk included), and 0 without a turn.  Wait states inside the string:
+      // the v_cndmask and the shift fill the two states between the v_max that writes d and its DPP read; the s_nop of the first chunk
+      // completes the five between a VALU write of EXEC ahead of the statement and the first DPP.  The one-env tail takes the same
+      // statement with one bit in the mask: the live env's lane k.
+#define HB_PGS_ROWB(k)                                                               \
+  "v_mul_f32_e32 %[d], %[na], %[r]\n\t"                                              \
+  "v_max_f32_e32 %[d], %[d], %[nf]\n\t"                                              \
+  "v_cndmask_b32_e64 %[dl], %[dl], %[d], %[m]\n\t"                                   \
+  "s_lshl_b64 %[m], %[m], 1\n\t"                                                     \
+  HB_BCAST_FMAC(k)
+#define HB_PGS_CHUNKB(c, pre)                                                        \
+  if ((c) * 4 >= ne) break;                                                          \
+  {                                                                                  \
+    float d_;                                                                        \
+    asm volatile(pre HB_PGS_ROWB(0) HB_PGS_ROWB(1) HB_PGS_ROWB(2) HB_PGS_ROWB(3)     \
+                 : [r] "+v"(res), [dl] "+v"(dl), [m] "+s"(turn), [d] "=&v"(d_)       \
+                 : [na] "v"(nAinv), [nf] "v"(nforce), [ar0] "v"(arS[(c) * 4]), [ar1] "v"(arS[(c) * 4 + 1]), [ar2] "v"(arS[(c) * 4 + 2]), \
+                   [ar3] "v"(arS[(c) * 4 + 3]), [k0] "n"((c) * 4), [k1] "n"((c) * 4 + 1), [k2] "n"((c) * 4 + 2), [k3] "n"((c) * 4 + 3) \
+                 : "scc");                                                           \
+  }
+#define HB_PGS_SWEEPB do { HB_PGS_CHUNKB(0, "s_nop 0\n\t") HB_PGS_CHUNKB(1, "") HB_PGS_CHUNKB(2, "") HB_PGS_CHUNKB(3, "") } while (0)
+      // the end of a paired sweep, the same behind both forms of the row step: the steps join the forces, then each env's convergence test
+      auto paired_end = [&](float delta, float res0) {
+        force += delta;
+        float iLo, iHi;
+        env_sums(delta * (res0 + res), iLo, iHi);
+        niterLo++; niterHi++;
+        if (-0.5f * iLo * pgs_scale < pgs_tol || niterLo >= max_sweeps) {
+          liveLo = false;
+          if (!h) { force_out = force; res = 0.f; force = 0.f; }  // rows of a finished env are inert from here on
+        }
+        if (-0.5f * iHi * pgs_scale < pgs_tol || niterHi >= max_sweeps) {
+          liveHi = false;
+          if (h) { force_out = force; res = 0.f; force = 0.f; }
+        }
+      };
+      while (short16 && liveLo && liveHi) {
+        int ne;
+        asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(nmax2));
+        const float nforce = -force, res0 = res;
+        float dl = 0.f;
+        unsigned long long turn = 0x0000000100000001ull;  // the lanes whose turn it is: row 0 of both envs
+        HB_PGS_SWEEPB;
+        paired_end(dl, res0);
+      }
       while (liveLo && liveHi) {
         int ne;
         {
@@ -1208,19 +1262,7 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
           HB_PGS_CHUNK2(0, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(1, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(2, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(3, HB_PGS_ROWS2_4)
           HB_PGS_CHUNK2(4, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(5, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(6, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(7, HB_PGS_ROWS2_3)
         } while (0);
-        const float delta = dl;
-        force += delta;
-        float iLo, iHi;
-        env_sums(delta * (res0 + res), iLo, iHi);
-        niterLo++; niterHi++;
-        if (-0.5f * iLo * pgs_scale < pgs_tol || niterLo >= max_sweeps) {
-          liveLo = false;
-          if (!h) { force_out = force; res = 0.f; force = 0.f; }  // rows of a finished env are inert from here on
-        }
-        if (-0.5f * iHi * pgs_scale < pgs_tol || niterHi >= max_sweeps) {
-          liveHi = false;
-          if (h) { force_out = force; res = 0.f; force = 0.f; }
-        }
+        paired_end(dl, res0);
       }
 #undef HB_PGS_CHUNK2
 #undef HB_PGS_ROWS2_3
@@ -1241,6 +1283,26 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
   }
 #define HB_PGS_CHUNK1(base, c) if ((c) * 4 >= ne) break; HB_PGS_ROW1(base, (c) * 4) HB_PGS_ROW1(base, (c) * 4 + 1) HB_PGS_ROW1(base, (c) * 4 + 2) HB_PGS_ROW1(base, (c) * 4 + 3)
 #define HB_PGS_TAIL(base, live, n_, niter_, mine)                                    \
+    {                                                                                \
+      /* the end of a sweep of the one env left, the same behind both forms of the row step */ \
+      auto tail_end_ = [&](float delta, float res0) {                                \
+        force += delta;                                                              \
+        const float improvement = half_sum<base>(delta * (res0 + res));              \
+        niter_++;                                                                    \
+        if (-0.5f * improvement * pgs_scale < pgs_tol || niter_ >= max_sweeps) {     \
+          live = false;                                                              \
+          if (mine) force_out = force;                                               \
+        }                                                                            \
+      };                                                                             \
+      while (n_ <= 16 && live) { /* the broadcast row step above, on this env's DPP row */ \
+        int ne;                                                                      \
+        asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(n_));                       \
+        const float nforce = -force, res0 = res;                                     \
+        float dl = 0.f;                                                              \
+        unsigned long long turn = 1ull << (base);                                    \
+        HB_PGS_SWEEPB;                                                               \
+        tail_end_(dl, res0);                                                         \
+      }                                                                              \
       while (live) {                                                                 \
         int ne;                                                                      \
         asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(n_));                       \
@@ -1249,18 +1311,16 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
         do {                                                                         \
           HB_PGS_CHUNK1(base, 0) HB_PGS_CHUNK1(base, 1) HB_PGS_CHUNK1(base, 2) HB_PGS_CHUNK1(base, 3) HB_PGS_CHUNK1(base, 4) HB_PGS_CHUNK1(base, 5) HB_PGS_CHUNK1(base, 6) HB_PGS_CHUNK1(base, 7) \
         } while (0);                                                                 \
-        const float delta = __int_as_float(dl);                                      \
-        force += delta;                                                              \
-        const float improvement = half_sum<base>(delta * (res0 + res));              \
-        niter_++;                                                                    \
-        if (-0.5f * improvement * pgs_scale < pgs_tol || niter_ >= max_sweeps) {     \
-          live = false;                                                              \
-          if (mine) force_out = force;                                               \
-        }                                                                            \
-      }
+        tail_end_(__int_as_float(dl), res0);                                         \
+      }                                                                              \
+    }
       HB_PGS_TAIL(0, liveLo, nLo, niterLo, !h)
       HB_PGS_TAIL(32, liveHi, nHi, niterHi, h)
 #undef HB_PGS_TAIL
+#undef HB_PGS_SWEEPB
+#undef HB_PGS_CHUNKB
+#undef HB_PGS_ROWB
+#undef HB_BCAST_FMAC
 #undef HB_PGS_CHUNK1
 #undef HB_PGS_ROW1
       force = (h ? sweptHi : sweptLo) ? force_out : force;

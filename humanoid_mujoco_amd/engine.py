@@ -197,6 +197,7 @@ def lib():
     L.hb_model_pair_order.argtypes = [vp, ci]
     L.hb_env_terminal_obs.argtypes = [vp, vp]
     L.hb_env_warnings.argtypes = [vp, vp]
+    L.hb_env_joint_torques.argtypes = [vp, vp]
     L.hb_batch_device_name.argtypes = [vp, cp, ci]
     L.hb_get_collision_counts.argtypes = [vp, vp, vp, vp]
     L.hb_batch_segments.argtypes = [vp]
@@ -1073,6 +1074,12 @@ class Batch:
         w = np.zeros(self.n_env, dtype=np.int32)
         _check(lib().hb_env_warnings(self._h, _ptr(w)), "hb_env_warnings")
         return w
+
+    def env_joint_torques(self):
+        """[n_env, nv] qfrc_smooth + qfrc_constraint of the last physics step of the last env step (include/hb.h: hb_env_joint_torques)"""
+        out = np.zeros((self.n_env, self.model.nv), dtype=np.float32)
+        _check(lib().hb_env_joint_torques(self._h, _ptr(out)), "hb_env_joint_torques")
+        return out
 
     def env_terminal_obs(self, fetch=True):
         """[n_env, nobs] observations of the states episodes ended in (include/hb.h: hb_env_terminal_obs); fetch=False only switches the

@@ -532,6 +532,9 @@ int hb_get_status(hb_batch* b, int* status);
  * so a warning of an episode that ended before the next poll would be lost.  warnings[e] = the bits env e has raised since the previous
  * call of this function, in whatever episodes; the call clears what finished episodes left behind. */
 int hb_env_warnings(hb_batch* b, int* warnings);
+/* The joint torques the env adapter's reward reads: qfrc[n_env][nv] = qfrc_smooth + qfrc_constraint (= M qacc) of the last physics step of
+ * the last hb_env_step; zeros before the first one. */
+int hb_env_joint_torques(hb_batch* b, float* qfrc);
 /* Per-env counters of the last step: ncon, nefc, solver iterations (mjData.ncon/nefc/
  * solver_niter, mjdata.h:196-201) — what testspeed.cc:97-98 accumulates.  nefc counts the friction-loss rows of the model as well
  * (one per dof with dof_frictionloss > 0: they are always active) and its equality rows (one per active joint coupling, three per
