@@ -379,26 +379,14 @@ int kinematics_launch(hb_batch* b, const float* qpos, const float* qvel, int qpo
 // host form: the outputs asked for (and qpos / qvel when given) staged in d_kin, one launch, copied back
 int kinematics_host(hb_batch* b, const float* qpos, const float* qvel, long long n, float* body_pose, float* body_vel, float* geom_pose) {
   const DevModel& dm = b->D.dm;
-  const size_t np = body_pose ? (size_t)n * dm.nbody * 10 : 0, nvel = body_vel ? (size_t)n * dm.nbody * 6 : 0, ng = geom_pose ? (size_t)n * dm.ngeom * 7 : 0;
-  const size_t nqp = qpos ? (size_t)n * dm.nq : 0, nqv = qpos && qvel ? (size_t)n * dm.nv : 0;
-  const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined; d_kin is idle: the host form before this one ended synchronised)
-  if (b->d_kin.reserve(np + nvel + ng + nqp + nqv + 1) != HB_OK) return HB_ENOMEM;
-  float* d_pose = b->d_kin;
-  float* d_vel = d_pose + np;
-  float* d_geom = d_vel + nvel;
-  float* d_qpos = d_geom + ng;
-  float* d_qvel = d_qpos + nqp;
-  if (nqp) HB_HIP(hipMemcpyAsync(d_qpos, qpos, nqp * sizeof(float), hipMemcpyHostToDevice, stream));
-  if (nqv) HB_HIP(hipMemcpyAsync(d_qvel, qvel, nqv * sizeof(float), hipMemcpyHostToDevice, stream));
-  int rc;
-  if (qpos) rc = kinematics_launch(b, d_qpos, nqv ? d_qvel : nullptr, dm.nq, dm.nv, n, np ? d_pose : nullptr, nvel ? d_vel : nullptr, ng ? d_geom : nullptr, stream);
-  else rc = kinematics_launch(b, b->d_state + 1, b->d_state + 1 + dm.nq, dm.nstate, dm.nstate, n, np ? d_pose : nullptr, nvel ? d_vel : nullptr, ng ? d_geom : nullptr, stream);
-  if (rc != HB_OK) return rc;
-  if (np) HB_HIP(hipMemcpyAsync(body_pose, d_pose, np * sizeof(float), hipMemcpyDeviceToHost, stream));
-  if (nvel) HB_HIP(hipMemcpyAsync(body_vel, d_vel, nvel * sizeof(float), hipMemcpyDeviceToHost, stream));
-  if (ng) HB_HIP(hipMemcpyAsync(geom_pose, d_geom, ng * sizeof(float), hipMemcpyDeviceToHost, stream));
-  HB_HIP(hipStreamSynchronize(stream));
-  return HB_OK;
+  const size_t sn = (size_t)n;
+  StageBlock blk[5] = {{body_pose ? sn * dm.nbody * 10 : 0, nullptr, body_pose}, {body_vel ? sn * dm.nbody * 6 : 0, nullptr, body_vel},
+                       {geom_pose ? sn * dm.ngeom * 7 : 0, nullptr, geom_pose}, {qpos ? sn * dm.nq : 0, qpos, nullptr}, {qpos && qvel ? sn * dm.nv : 0, qvel, nullptr}};
+  const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined)
+  return staged_call(b->d_kin, blk, 5, stream, [&] {
+    if (qpos) return kinematics_launch(b, blk[3].dev, blk[4].dev, dm.nq, dm.nv, n, blk[0].dev, blk[1].dev, blk[2].dev, stream);
+    return kinematics_launch(b, b->d_state + 1, b->d_state + 1 + dm.nq, dm.nstate, dm.nstate, n, blk[0].dev, blk[1].dev, blk[2].dev, stream);
+  });
 }
 }  // namespace
 

@@ -41,32 +41,15 @@ int dynamics_launch(hb_batch* b, const float* qpos, const float* qvel, int qpos_
 // host form: the outputs asked for (and qpos / qvel when given) staged in d_dyn, one launch, copied back
 int dynamics_host(hb_batch* b, const float* qpos, const float* qvel, long long n, const DynOut& o, const hb_jac_spec* spec) {
   const DevModel& dm = b->D.dm;
-  auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };  // (every block starts 16-byte aligned)
-  const size_t nM = o.M ? (size_t)n * dm.nv * dm.nv : 0, nb = o.bias ? (size_t)n * dm.nv : 0, np = o.passive ? (size_t)n * dm.nv : 0;
-  const size_t nj = o.jac ? (size_t)n * spec->n * 6 * dm.nv : 0;
-  const size_t nqp = qpos ? (size_t)n * dm.nq : 0, nqv = qpos && qvel ? (size_t)n * dm.nv : 0;
-  const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined; d_dyn is idle: the host form before this one ended synchronised)
-  if (b->d_dyn.reserve(r4(nM) + r4(nb) + r4(np) + r4(nj) + r4(nqp) + r4(nqv) + 4) != HB_OK) return HB_ENOMEM;
-  DynOut d;
-  d.M = b->d_dyn;
-  d.bias = d.M + r4(nM);
-  d.passive = d.bias + r4(nb);
-  d.jac = d.passive + r4(np);
-  float* d_qpos = d.jac + r4(nj);
-  float* d_qvel = d_qpos + r4(nqp);
-  if (nqp) HB_HIP(hipMemcpyAsync(d_qpos, qpos, nqp * sizeof(float), hipMemcpyHostToDevice, stream));
-  if (nqv) HB_HIP(hipMemcpyAsync(d_qvel, qvel, nqv * sizeof(float), hipMemcpyHostToDevice, stream));
-  const DynOut dev = {nM ? d.M : nullptr, nb ? d.bias : nullptr, np ? d.passive : nullptr, nj ? d.jac : nullptr};
-  int rc;
-  if (qpos) rc = dynamics_launch(b, d_qpos, nqv ? d_qvel : nullptr, dm.nq, dm.nv, n, nullptr, dev, spec, stream);
-  else rc = dynamics_launch(b, b->d_state + 1, b->d_state + 1 + dm.nq, dm.nstate, dm.nstate, n, b->d_dr, dev, spec, stream);
-  if (rc != HB_OK) return rc;
-  if (nM) HB_HIP(hipMemcpyAsync(o.M, d.M, nM * sizeof(float), hipMemcpyDeviceToHost, stream));
-  if (nb) HB_HIP(hipMemcpyAsync(o.bias, d.bias, nb * sizeof(float), hipMemcpyDeviceToHost, stream));
-  if (np) HB_HIP(hipMemcpyAsync(o.passive, d.passive, np * sizeof(float), hipMemcpyDeviceToHost, stream));
-  if (nj) HB_HIP(hipMemcpyAsync(o.jac, d.jac, nj * sizeof(float), hipMemcpyDeviceToHost, stream));
-  HB_HIP(hipStreamSynchronize(stream));
-  return HB_OK;
+  const size_t sn = (size_t)n;
+  StageBlock blk[6] = {{o.M ? sn * dm.nv * dm.nv : 0, nullptr, o.M}, {o.bias ? sn * dm.nv : 0, nullptr, o.bias}, {o.passive ? sn * dm.nv : 0, nullptr, o.passive},
+                       {o.jac ? sn * spec->n * 6 * dm.nv : 0, nullptr, o.jac}, {qpos ? sn * dm.nq : 0, qpos, nullptr}, {qpos && qvel ? sn * dm.nv : 0, qvel, nullptr}};
+  const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined)
+  return staged_call(b->d_dyn, blk, 6, stream, [&] {
+    const DynOut dev = {blk[0].dev, blk[1].dev, blk[2].dev, blk[3].dev};
+    if (qpos) return dynamics_launch(b, blk[4].dev, blk[5].dev, dm.nq, dm.nv, n, nullptr, dev, spec, stream);
+    return dynamics_launch(b, b->d_state + 1, b->d_state + 1 + dm.nq, dm.nstate, dm.nstate, n, b->d_dr, dev, spec, stream);
+  });
 }
 
 }  // namespace

@@ -75,6 +75,36 @@ class DevBuf {
 template <class... B>
 void reset_all(B&... bufs) { (bufs.reset(), ...); }
 
+// One block of the device copies of a host call's arrays: count floats (none: the block is not there, and dev stays null), filled from
+// `up` before the launch where that is given and copied to `down` behind it where that is given.
+struct StageBlock {
+  size_t count;
+  const float* up;
+  float* down;
+  float* dev;
+};
+// The host form of a read-out: carves the blocks out of buf, each 16-byte aligned (buf grows on demand; it is idle: the host form before
+// this one ended synchronised), uploads, runs launch() - which takes the blocks' device pointers -, downloads and ends synchronised.
+template <class Launch>
+int staged_call(DevBuf<float>& buf, StageBlock* blk, int nblk, hipStream_t stream, Launch&& launch) {
+  auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+  size_t total = 4;  // (never an empty allocation)
+  for (int i = 0; i < nblk; i++) total += r4(blk[i].count);
+  if (buf.reserve(total) != HB_OK) return HB_ENOMEM;
+  float* p = buf;
+  for (int i = 0; i < nblk; i++) {
+    blk[i].dev = blk[i].count ? p : nullptr;
+    p += r4(blk[i].count);
+    if (blk[i].count && blk[i].up) HB_HIP(hipMemcpyAsync(blk[i].dev, blk[i].up, blk[i].count * sizeof(float), hipMemcpyHostToDevice, stream));
+  }
+  const int rc = launch();
+  if (rc != HB_OK) return rc;
+  for (int i = 0; i < nblk; i++)
+    if (blk[i].count && blk[i].down) HB_HIP(hipMemcpyAsync(blk[i].down, blk[i].dev, blk[i].count * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HB_HIP(hipStreamSynchronize(stream));
+  return HB_OK;
+}
+
 struct DeviceModel {
   DevModel dm;
   DevBuf<int> d_int;

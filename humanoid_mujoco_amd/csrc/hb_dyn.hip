@@ -4,7 +4,7 @@
 // and, for the batch's own state, the env's own masses, armature and stiffness.  A kernel of its own: no solver and no collision enters, so
 // every model takes it whatever kernels it steps in, and no step kernel carries anything for it.
 #include <hip/hip_runtime.h>
-#include "hb_kcommon.hpp"
+#include "hb_kinematics.hpp"
 #include "hb_launch.hpp"
 
 namespace hb {
@@ -39,8 +39,8 @@ __device__ __forceinline__ void dyn_copy_out(float* dst, const float* src, int c
   if (l < cnt - t0) dst[t0 + l] = src[t0 + l];
 }
 
-// Lane = body for the tree passes and lane = dof (in rounds of L) for everything per dof; L lanes per state (the smallest of 16 / 32 / 64
-// that holds the nbody - 1 moving bodies), 64 / L states per wave, as in hb_kin.hip: every sub-group of L lanes has an LDS block of its
+// Lane = body for the tree passes and lane = dof (in rounds of L) for everything per dof; L lanes per state (packed_lanes()), 64 / L states per
+// wave, as in hb_kin.hip: every sub-group of L lanes has an LDS block of its
 // own and executes the same instructions on it as a wave that holds one state, so a state's result depends neither on L nor on its place
 // in the wave, its neighbours or n.  No atomics: every sum runs in a fixed order.  Nothing of the batch is written; a non-finite input
 // makes that state's own rows garbage and nothing else: no index depends on data.
@@ -92,38 +92,15 @@ __device__ __forceinline__ void dyn_body(const DevModel* Mp, const DynArgs& A) {
   const float mymass = (dr && bl) ? dr[DL.o_mass + myb] : q1.z;
   const int mych[8] = {__float_as_int(ch0.x), __float_as_int(ch0.y), __float_as_int(ch0.z), __float_as_int(ch0.w),
                        __float_as_int(ch1.x), __float_as_int(ch1.y), __float_as_int(ch1.z), __float_as_int(ch1.w)};
-  // ---------------------------------------------------------------- mj_kinematics (as hb_kin.hip: the pose in the parent's frame, then pointer jumping)
+  // ---------------------------------------------------------------- mj_kinematics (hb_kinematics.hpp: the pose in the parent's frame, then pointer jumping)
   const bool isfree = bl && myjn == 1 && __float_as_int(JA[0].x) == 0;
-  V3 posl = {bp.x, bp.y, bp.z};
-  Q4 quatl = {bq.x, bq.y, bq.z, bq.w};
-  V3 axl[3], ancl[3];  // joint axes and anchors in the parent's frame
-#pragma unroll
-  for (int jj = 0; jj < 3; jj++) { axl[jj] = {0.f, 0.f, 0.f}; ancl[jj] = {0.f, 0.f, 0.f}; }
-  if (isfree) {
-    const int qa = __float_as_int(JA[0].y);
-    posl = ld3(s_qpos + qa);
-    quatl = qnormalize(ldq(s_qpos + qa + 3));
-  } else if (bl) {
-#pragma unroll
-    for (int jj = 0; jj < 3; jj++) {
-      if (jj < myjn) {
-        const int qa = __float_as_int(JA[jj].y);
-        const V3 laxis = {JB[jj].x, JB[jj].y, JB[jj].z}, lpos = {JC[jj].x, JC[jj].y, JC[jj].z};
-        axl[jj] = qrot(quatl, laxis);
-        ancl[jj] = qrot(quatl, lpos) + posl;
-        const float dq = s_qpos[qa] - JA[jj].w;
-        if (__float_as_int(JA[jj].x) == 2) posl = posl + axl[jj] * dq;
-        else {
-          quatl = qmul(quatl, axisangle(laxis, dq));
-          posl = ancl[jj] - qrot(quatl, lpos);
-        }
-      }
-    }
-  }
+  V3 posl, axl[3], ancl[3];  // the pose, joint axes and anchors in the parent's frame
+  Q4 quatl;
+  local_pose(bl, isfree, myjn, bp, bq, JA, JB, JC, s_qpos, posl, quatl, axl, ancl);
   V3 mypos = posl;
   Q4 myquat = quatl;
   // bit b of a body's mask: body b is the body itself or one of its ancestors (the subtree test of the centre-of-mass Jacobians); it rides
-  // along in the pose records' pad and is composed in the same rounds
+  // along in the pose records' pad and is composed in the same rounds (compose_world()'s, statement for statement, with the masks between)
   unsigned mylo = bl ? (myb < 32 ? 1u << myb : 0u) | 1u : 0u, myhi = bl && myb >= 32 ? 1u << (myb - 32) : 0u;
   if (bl) {
     reinterpret_cast<float4*>(s_xpq + kXpqStride * myb)[0] = {mypos.x, mypos.y, mypos.z, 0.f};
@@ -132,7 +109,7 @@ __device__ __forceinline__ void dyn_body(const DevModel* Mp, const DynArgs& A) {
   }
   gsync();
   for (int r = 0, span = 1; span < M.nlevel - 1 || r == 0; r++, span <<= 1) {
-    const int anc = r == 0 ? myp : (r == 1 ? myanc2 : (r == 2 ? myanc4 : myanc8));
+    const int anc = ancestor_up(r, myp, myanc2, myanc4, myanc8);
     float4 pp4 = {0.f, 0.f, 0.f, 0.f}, pq4 = {1.f, 0.f, 0.f, 0.f}, pm4 = pp4;
     if (bl) { const float4* Pp = reinterpret_cast<const float4*>(s_xpq + kXpqStride * anc); pp4 = Pp[0]; pq4 = Pp[1]; pm4 = Pp[2]; }
     gsync();  // every lane has read its ancestor before anyone overwrites a record
@@ -268,7 +245,7 @@ __device__ __forceinline__ void dyn_body(const DevModel* Mp, const DynArgs& A) {
   }
   gsync();
   for (int r = 0, span = 1; span < M.nlevel - 1 || r == 0; r++, span <<= 1) {
-    const int anc = r == 0 ? myp : (r == 1 ? myanc2 : (r == 2 ? myanc4 : myanc8));
+    const int anc = ancestor_up(r, myp, myanc2, myanc4, myanc8);
     float4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0;
     if (bl && anc != 0) { const float4* Pp = reinterpret_cast<const float4*>(s_va + kDynVaStride * anc); a0 = Pp[0]; a1 = Pp[1]; a2 = Pp[2]; }
     gsync();
@@ -423,17 +400,8 @@ __global__ __launch_bounds__(kGroup) void hb_dyn32_kernel(const DevModel* Mp, co
 __global__ __launch_bounds__(kGroup) void hb_dyn64_kernel(const DevModel* Mp, const DynArgs A) { dyn_body<64>(Mp, A); }
 
 hipError_t launch_dynamics(const DevModel* M_dev, const DevModel& M, const DynArgs& A, int pack, hipStream_t stream, const char** kernel) {
-  (void)hipGetLastError();
-  const int lanes = M.nbody - 1;
-  const int L = !pack || lanes > 32 ? 64 : (lanes > 16 ? 32 : 16);
-  const int per = kGroup / L;
-  const size_t lds = (size_t)per * dyn_lds_floats(M.nq, M.nv, M.nbody, M.ntree) * sizeof(float);
-  const long long blocks = (A.n + per - 1) / per;
-  if (blocks < 1 || blocks > 0x7fffffffLL || lds > 64 * 1024) return hipErrorInvalidValue;
-  if (L == 16) { hipLaunchKernelGGL(hb_dyn16_kernel, dim3((unsigned)blocks), dim3(kGroup), lds, stream, M_dev, A); *kernel = "hb_dyn16_kernel"; }
-  else if (L == 32) { hipLaunchKernelGGL(hb_dyn32_kernel, dim3((unsigned)blocks), dim3(kGroup), lds, stream, M_dev, A); *kernel = "hb_dyn32_kernel"; }
-  else { hipLaunchKernelGGL(hb_dyn64_kernel, dim3((unsigned)blocks), dim3(kGroup), lds, stream, M_dev, A); *kernel = "hb_dyn64_kernel"; }
-  return hipGetLastError();
+  static const PackedKernel<DynArgs> triple[3] = {{hb_dyn16_kernel, "hb_dyn16_kernel"}, {hb_dyn32_kernel, "hb_dyn32_kernel"}, {hb_dyn64_kernel, "hb_dyn64_kernel"}};
+  return launch_packed(triple, M_dev, M, A, pack, dyn_lds_floats(M.nq, M.nv, M.nbody, M.ntree), stream, kernel);
 }
 
 }  // namespace hb

@@ -16,8 +16,10 @@ __host__ __device__ inline int kin_lds_floats(int nq, int nv, int nb) { return (
 // humanoid (16 bodies) and the reference's robot (14) run four states per wave instead of leaving 47 lanes empty.  Every sub-group of L
 // lanes has an LDS block of its own and executes the same instructions on it as a wave that holds one state: a state's result
 // depends neither on L nor on its place in the wave, its neighbours or n (tests/test_gpu_kinematics.py holds that bit for bit).
-// mj_kinematics as hb_pose_kernel and step_body do it (level-ordered records, pointer jumping over the 1 / 2 / 4 / 8-up ancestors);
-// the velocities ride along in the same rounds: a body carries (omega, v of its frame origin) RELATIVE to the ancestor it currently
+// mj_kinematics as local_pose() and compose_world() of hb_kinematics.hpp do it, statement for statement (level-ordered records, pointer
+// jumping over the 1 / 2 / 4 / 8-up ancestors), with the velocities between their statements; the kernel calls none of the header's
+// functions (with ancestor_up and geom_world_pose its time on the 15-body robot left the parent's spread: profiles/kinematics_shared_bench.txt).
+// The velocities ride along in the same rounds: a body carries (omega, v of its frame origin) RELATIVE to the ancestor it currently
 // refers to, in that ancestor's axes, and composing with the ancestor's own record is
 //   omega' = W + Q omega,   v' = V + W x (Q p) + Q v        (P, Q, W, V: the ancestor's record; p: the body's position in it)
 // so that after the last round both are world quantities.  No mass enters (mj_comVel refers its cvel to the subtree's centre of mass;
@@ -158,17 +160,8 @@ __global__ __launch_bounds__(kGroup) void hb_kin32_kernel(const DevModel* Mp, co
 __global__ __launch_bounds__(kGroup) void hb_kin64_kernel(const DevModel* Mp, const KinArgs A) { kin_body<64>(Mp, A); }
 
 hipError_t launch_kinematics(const DevModel* M_dev, const DevModel& M, const KinArgs& A, int pack, hipStream_t stream, const char** kernel) {
-  (void)hipGetLastError();
-  const int lanes = M.nbody - 1;
-  const int L = !pack || lanes > 32 ? 64 : (lanes > 16 ? 32 : 16);
-  const int per = kGroup / L;
-  const size_t lds = (size_t)per * kin_lds_floats(M.nq, M.nv, M.nbody) * sizeof(float);
-  const long long blocks = (A.n + per - 1) / per;
-  if (blocks < 1 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (L == 16) { hipLaunchKernelGGL(hb_kin16_kernel, dim3((unsigned)blocks), dim3(kGroup), lds, stream, M_dev, A); *kernel = "hb_kin16_kernel"; }
-  else if (L == 32) { hipLaunchKernelGGL(hb_kin32_kernel, dim3((unsigned)blocks), dim3(kGroup), lds, stream, M_dev, A); *kernel = "hb_kin32_kernel"; }
-  else { hipLaunchKernelGGL(hb_kin64_kernel, dim3((unsigned)blocks), dim3(kGroup), lds, stream, M_dev, A); *kernel = "hb_kin64_kernel"; }
-  return hipGetLastError();
+  static const PackedKernel<KinArgs> triple[3] = {{hb_kin16_kernel, "hb_kin16_kernel"}, {hb_kin32_kernel, "hb_kin32_kernel"}, {hb_kin64_kernel, "hb_kin64_kernel"}};
+  return launch_packed(triple, M_dev, M, A, pack, kin_lds_floats(M.nq, M.nv, M.nbody), stream, kernel);
 }
 
 }  // namespace hb

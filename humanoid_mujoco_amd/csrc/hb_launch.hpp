@@ -12,6 +12,29 @@ hipError_t launch_inverse(const DevModel* M_dev, const DevModel& M, const BatchP
 hipError_t launch_kinematics(const DevModel* M_dev, const DevModel& M, const KinArgs& A, int pack, hipStream_t stream, const char** kernel);
 // mass matrix, bias and passive forces and Jacobians of A.n states (hb_dyn.hip; hb_dynamics*): pack as for launch_kinematics
 hipError_t launch_dynamics(const DevModel* M_dev, const DevModel& M, const DynArgs& A, int pack, hipStream_t stream, const char** kernel);
+// ---- the packed read-out kernels: lane = body, L lanes per state (the smallest of 16 / 32 / 64 that holds the nbody - 1 moving bodies; 64 without
+// packing), 64 / L states per wave, every state with an LDS block of its own
+inline int packed_lanes(int nbody, int pack) {
+  const int lanes = nbody - 1;
+  return !pack || lanes > 32 ? 64 : (lanes > 16 ? 32 : 16);
+}
+// one launch of the kernel of a 16 / 32 / 64 triple that packed_lanes() names, over A.n states of lds_floats floats each
+template <class Args>
+struct PackedKernel { void (*fn)(const DevModel*, const Args); const char* name; };
+template <class Args>
+inline hipError_t launch_packed(const PackedKernel<Args> (&triple)[3], const DevModel* M_dev, const DevModel& M, const Args& A, int pack, int lds_floats, hipStream_t stream,
+                                const char** kernel) {
+  (void)hipGetLastError();
+  const int L = packed_lanes(M.nbody, pack);
+  const int per = kGroup / L;
+  const size_t lds = (size_t)per * lds_floats * sizeof(float);
+  const long long blocks = (A.n + per - 1) / per;
+  if (blocks < 1 || blocks > 0x7fffffffLL || lds > 64 * 1024) return hipErrorInvalidValue;  // (a block has 64 KB of LDS to ask for)
+  const PackedKernel<Args>& K = triple[L == 16 ? 0 : (L == 32 ? 1 : 2)];
+  hipLaunchKernelGGL(K.fn, dim3((unsigned)blocks), dim3(kGroup), lds, stream, M_dev, A);
+  *kernel = K.name;
+  return hipGetLastError();
+}
 // the configured rays against every env's geoms (hb_ray.hip; hb_rays*)
 hipError_t launch_rays(const DevModel* M_dev, const DevModel& M, const RayArgs& A, hipStream_t stream, const char** kernel);
 // two envs per wave: a lean launch of the 27-dof humanoid's PGS kernel (hb_step_duo.hip; chosen by launch_step)

@@ -9,14 +9,14 @@
 #define HB_NARROW_DIAG 1
 namespace hb { __device__ int g_mpr_limit[2] = {1 << 30, 1 << 30}; }
 #endif
-#include "hb_kcommon.hpp"
+#include "hb_kinematics.hpp"
 #include "hb_collide.hpp"
 #include "hb_launch.hpp"
 
 namespace hb {
 
 // ---- staged step of the general variants: poses + work lists, then the narrowphase, each in a kernel of its own ------------------
-// hb_pose_kernel: one wave per env.  The state checks and mj_kinematics of step_body, statement for statement (the step kernel
+// hb_pose_kernel: one wave per env.  The state checks of step_body and the same mj_kinematics (hb_kinematics.hpp; the step kernel
 // repeats them: a pose costs less to recompute than to hand over), the geoms' world poses, broadphase and work items.
 __global__ __launch_bounds__(kGroup, 4) void hb_pose_kernel(const DevModel* Mp, const BatchPtrs P) {
   DevModelRef M = *(const DevModel HB_CONST*)(uintptr_t)Mp;
@@ -59,58 +59,20 @@ __global__ __launch_bounds__(kGroup, 4) void hb_pose_kernel(const DevModel* Mp, 
   const int myb = __float_as_int(q0.x), myp = __float_as_int(q0.y), myjn = __float_as_int(q0.z);
   const int myanc2 = (__float_as_int(q1.x) >> 8) & 255, myanc4 = (__float_as_int(q1.x) >> 16) & 255, myanc8 = (__float_as_int(q1.x) >> 24) & 255;
   const bool isfree = bl && myjn == 1 && __float_as_int(JA[0].x) == 0;
-  V3 posl = {bp.x, bp.y, bp.z};
-  Q4 quatl = {bq.x, bq.y, bq.z, bq.w};
-  if (isfree) {
-    const int qa = __float_as_int(JA[0].y);
-    posl = ld3(s_qpos + qa);
-    quatl = qnormalize(ldq(s_qpos + qa + 3));
-  } else if (bl) {
-#pragma unroll
-    for (int jj = 0; jj < 3; jj++) {
-      if (jj < myjn) {
-        const int qa = __float_as_int(JA[jj].y);
-        const V3 laxis = {JB[jj].x, JB[jj].y, JB[jj].z}, lpos = {JC[jj].x, JC[jj].y, JC[jj].z};
-        const V3 axl = qrot(quatl, laxis);
-        const V3 ancl = qrot(quatl, lpos) + posl;
-        const float dq = s_qpos[qa] - JA[jj].w;
-        if (__float_as_int(JA[jj].x) == 2) posl = posl + axl * dq;
-        else {
-          quatl = qmul(quatl, axisangle(laxis, dq));
-          posl = ancl - qrot(quatl, lpos);
-        }
-      }
-    }
-  }
+  V3 posl, axl[3], ancl[3];
+  Q4 quatl;
+  local_pose(bl, isfree, myjn, bp, bq, JA, JB, JC, s_qpos, posl, quatl, axl, ancl);
   V3 mypos = posl;
   Q4 myquat = quatl;
-  if (bl) {
-    reinterpret_cast<float4*>(s_xpq + kXpqStride * myb)[0] = {mypos.x, mypos.y, mypos.z, 0.f};
-    reinterpret_cast<float4*>(s_xpq + kXpqStride * myb)[1] = {myquat.w, myquat.x, myquat.y, myquat.z};
-  }
-  gsync();
-  for (int r = 0, span = 1; span < M.nlevel - 1 || r == 0; r++, span <<= 1) {
-    const int anc = r == 0 ? myp : (r == 1 ? myanc2 : (r == 2 ? myanc4 : myanc8));
-    float4 pp4 = {0.f, 0.f, 0.f, 0.f}, pq4 = {1.f, 0.f, 0.f, 0.f};
-    if (bl) { const float4* Pp = reinterpret_cast<const float4*>(s_xpq + kXpqStride * anc); pp4 = Pp[0]; pq4 = Pp[1]; }
-    gsync();
-    if (bl && anc != 0) {
-      const Q4 pq = {pq4.x, pq4.y, pq4.z, pq4.w};
-      mypos = V3{pp4.x, pp4.y, pp4.z} + qrot(pq, mypos);
-      myquat = qnormalize(qmul(pq, myquat));
-      reinterpret_cast<float4*>(s_xpq + kXpqStride * myb)[0] = {mypos.x, mypos.y, mypos.z, 0.f};
-      reinterpret_cast<float4*>(s_xpq + kXpqStride * myb)[1] = {myquat.w, myquat.x, myquat.y, myquat.z};
-    }
-    gsync();
-  }
+  compose_world(bl, myb, myp, myanc2, myanc4, myanc8, M.nlevel, s_xpq, mypos, myquat);
   // geoms: world position, z axis and orientation (the step kernel rotates the offset with the body's matrix: the same q2mat here)
   if (lane < ng) {
     const int g = lane, b = pf_gbody;
     float mat[9];
     q2mat(mat, ldq(s_xpq + kXpqStride * b + 4));
-    const V3 gp = ld3(s_xpq + kXpqStride * b) + mrot(mat, pf_gpos);
-    const Q4 q = qmul(ldq(s_xpq + kXpqStride * b + 4), pf_gquat);
-    const V3 ga = {2.f * (q.x * q.z + q.w * q.y), 2.f * (q.y * q.z - q.w * q.x), q.w * q.w - q.x * q.x - q.y * q.y + q.z * q.z};
+    const GeomPose G = geom_world_pose(s_xpq, b, mat, pf_gpos, pf_gquat);
+    const V3 gp = G.pos, ga = quat_zaxis(G.quat);
+    const Q4 q = G.quat;
     st3(s_gpos + 3 * g, gp); st3(s_gaxis + 3 * g, ga); stq(s_gquat + 4 * g, q);
     float* o = P.stage.geom + (size_t)env * ng * 10;  // per env: positions[3 ng] | z axes[3 ng] | quaternions[4 ng]
     st3(o + 3 * g, gp); st3(o + 3 * ng + 3 * g, ga); stq(o + 6 * ng + 4 * g, q);

@@ -17,7 +17,7 @@
 //   collision                                     lanes = candidate geom pairs
 //   constraint rows, half-solve, AR, PGS          lane  = constraint row
 //   dof vectors                                   lanes = dofs
-#include "hb_kcommon.hpp"
+#include "hb_kinematics.hpp"
 #include "hb_collide.hpp"
 #include "hb_launch.hpp"
 
@@ -278,32 +278,10 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     // body at once; the level loop that follows only composes parent and local pose (mj_kinematics does the
     // same products in world coordinates, body by body).
     const bool isfree = bl && myjn == 1 && __float_as_int(JA[0].x) == 0;
-    V3 posl = {bp.x, bp.y, bp.z};
-    Q4 quatl = {bq.x, bq.y, bq.z, bq.w};
-    V3 axl[3], ancl[3];  // joint axes and anchors in the parent frame
-#pragma unroll
-    for (int jj = 0; jj < 3; jj++) { axl[jj] = {0.f, 0.f, 0.f}; ancl[jj] = {0.f, 0.f, 0.f}; }
-    if (isfree) {
-      const int qa = __float_as_int(JA[0].y);
-      posl = ld3(s_qpos + qa);
-      quatl = qnormalize(ldq(s_qpos + qa + 3));
-    } else if (bl) {
-#pragma unroll
-      for (int jj = 0; jj < 3; jj++) {
-        if (jj < myjn) {
-          const int qa = __float_as_int(JA[jj].y);
-          const V3 laxis = {JB[jj].x, JB[jj].y, JB[jj].z}, lpos = {JC[jj].x, JC[jj].y, JC[jj].z};
-          axl[jj] = qrot(quatl, laxis);
-          ancl[jj] = qrot(quatl, lpos) + posl;
-          const float dq = s_qpos[qa] - JA[jj].w;
-          if (__float_as_int(JA[jj].x) == 2) posl = posl + axl[jj] * dq;
-          else {
-            quatl = qmul(quatl, axisangle(laxis, dq));
-            posl = ancl[jj] - qrot(quatl, lpos);
-          }
-        }
-      }
-    }
+    V3 posl, axl[3], ancl[3];  // the pose, joint axes and anchors in the parent's frame
+    Q4 quatl;
+    local_pose(bl, isfree, myjn, bp, bq, JA, JB, JC, s_qpos, posl, quatl, axl, ancl);
+    // (compose_world() of hb_kinematics.hpp, statement for statement: calling it moves the SGPR spill counts of six of these kernels)
     // World poses by pointer jumping: every body starts with its pose relative to its parent and, in round r, composes
     // it with the (partially composed) pose of its ancestor 2^r links up; after ceil(log2(depth)) rounds it is the world
     // pose.  The world body holds the identity and is every short chain's fixed point.  (mj_kinematics composes the same
@@ -316,7 +294,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     }
     gsync();
     for (int r = 0, span = 1; span < HB_SZ(nlevel) - 1 || r == 0; r++, span <<= 1) {
-      const int anc = r == 0 ? myp : (r == 1 ? myanc2 : (r == 2 ? myanc4 : myanc8));
+      const int anc = ancestor_up(r, myp, myanc2, myanc4, myanc8);
       float4 pp4 = {0.f, 0.f, 0.f, 0.f}, pq4 = {1.f, 0.f, 0.f, 0.f};
       if (bl) { const float4* Pp = reinterpret_cast<const float4*>(s_xpq + kXpqStride * anc); pp4 = Pp[0]; pq4 = Pp[1]; }
       gsync();  // every lane has read its ancestor before anyone overwrites a pose
@@ -329,26 +307,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       }
       gsync();
     }
-    if (bl) {  // everything that hangs off the world poses, all bodies at once
-      if (isfree) {
-        st3(s_xanchor + 3 * myja, mypos);
-        st3(s_xaxis + 3 * myja, {JB[0].x, JB[0].y, JB[0].z});
-      } else {
-        const Q4 pq = ldq(s_xpq + kXpqStride * myp + 4);
-        const V3 pp = ld3(s_xpq + kXpqStride * myp);
-#pragma unroll
-        for (int jj = 0; jj < 3; jj++) {
-          if (jj < myjn) {
-            st3(s_xaxis + 3 * (myja + jj), qrot(pq, axl[jj]));
-            st3(s_xanchor + 3 * (myja + jj), qrot(pq, ancl[jj]) + pp);
-          }
-        }
-      }
-      float mat[9];
-      q2mat(mat, myquat);
-      for (int i = 0; i < 9; i++) s_xmat[9 * myb + i] = mat[i];
-      st3(s_xipos + 3 * myb, mypos + mrot(mat, {ip.x, ip.y, ip.z}));
-    }
+    if (bl) store_world_frames(isfree, myb, myp, myjn, myja, JB[0], axl, ancl, ip, mypos, myquat, s_xpq, s_xaxis, s_xanchor, s_xmat, s_xipos);
     gsync();
     // equality rows (FRIC == 2 only; lane = row): the two anchor points of a connect row in world coordinates, taken here, while the body poses
     // are still in LDS (region B, which makeConstraint fills, aliases them), and kept in registers until the rows are built
@@ -372,9 +331,10 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     // geoms: world position and z axis
     if (lane < HB_SZ(ngeom)) {
       const int g = lane, b = pf_gbody;
-      st3(s_gpos + 3 * g, ld3(s_xpq + kXpqStride * b) + mrot(s_xmat + 9 * b, pf_gpos));
-      Q4 q = qmul(ldq(s_xpq + kXpqStride * b + 4), pf_gquat);
-      st3(s_gaxis + 3 * g, {2.f * (q.x * q.z + q.w * q.y), 2.f * (q.y * q.z - q.w * q.x), q.w * q.w - q.x * q.x - q.y * q.y + q.z * q.z});
+      const GeomPose G = geom_world_pose(s_xpq, b, s_xmat + 9 * b, pf_gpos, pf_gquat);
+      st3(s_gpos + 3 * g, G.pos);
+      const Q4 q = G.quat;
+      st3(s_gaxis + 3 * g, quat_zaxis(q));
       if constexpr (COLL != 0) stq(lds + HB_SZ(o_gquat) + 4 * g, q);
     }
     // ---------------------------------------------------------------- mj_comPos
@@ -496,7 +456,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
     }
     gsync();
     for (int r = 0, span = 1; span < HB_SZ(nlevel) - 1 || r == 0; r++, span <<= 1) {
-      const int anc = r == 0 ? myp : (r == 1 ? myanc2 : (r == 2 ? myanc4 : myanc8));
+      const int anc = ancestor_up(r, myp, myanc2, myanc4, myanc8);
       float4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0;
       if (bl && anc != 0) { const float4* Pp = reinterpret_cast<const float4*>(s_va + 12 * anc); a0 = Pp[0]; a1 = Pp[1]; a2 = Pp[2]; }
       gsync();  // every lane has read its ancestor's segment before anyone overwrites one

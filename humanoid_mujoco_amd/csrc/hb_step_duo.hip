@@ -21,7 +21,7 @@
 //
 // LDS (one block = one wave = two envs): 20 320 bytes -> 8 blocks per CU, two waves per SIMD, i.e. 16 envs resident per CU where the
 // one-env kernel holds 8: all 4096 envs of the benchmark batch are resident at once.
-#include "hb_kcommon.hpp"
+#include "hb_kinematics.hpp"
 #include "hb_launch.hpp"
 
 namespace hb {
@@ -302,81 +302,21 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     const int mych[8] = {__float_as_int(ch0.x), __float_as_int(ch0.y), __float_as_int(ch0.z), __float_as_int(ch0.w),
                          __float_as_int(ch1.x), __float_as_int(ch1.y), __float_as_int(ch1.z), __float_as_int(ch1.w)};
     const bool isfree = bl && myjn == 1 && __float_as_int(JA[0].x) == 0;
-    V3 posl = {bp.x, bp.y, bp.z};
-    Q4 quatl = {bq.x, bq.y, bq.z, bq.w};
-    V3 axl[3], ancl[3];
-#pragma unroll
-    for (int jj = 0; jj < 3; jj++) { axl[jj] = {0.f, 0.f, 0.f}; ancl[jj] = {0.f, 0.f, 0.f}; }
-    if (isfree) {
-      const int qa = __float_as_int(JA[0].y);
-      posl = ld3(s_qpos + qa);
-      quatl = qnormalize(ldq(s_qpos + qa + 3));
-    } else if (bl) {
-#pragma unroll
-      for (int jj = 0; jj < 3; jj++) {
-        if (jj < myjn) {
-          const int qa = __float_as_int(JA[jj].y);
-          const V3 laxis = {JB[jj].x, JB[jj].y, JB[jj].z}, lpos = {JC[jj].x, JC[jj].y, JC[jj].z};
-          axl[jj] = qrot(quatl, laxis);
-          ancl[jj] = qrot(quatl, lpos) + posl;
-          const float dq = s_qpos[qa] - JA[jj].w;
-          if (__float_as_int(JA[jj].x) == 2) posl = posl + axl[jj] * dq;
-          else {
-            quatl = qmul(quatl, axisangle(laxis, dq));
-            posl = ancl[jj] - qrot(quatl, lpos);
-          }
-        }
-      }
-    }
+    V3 posl, axl[3], ancl[3];  // the pose, joint axes and anchors in the parent's frame
+    Q4 quatl;
+    local_pose(bl, isfree, myjn, bp, bq, JA, JB, JC, s_qpos, posl, quatl, axl, ancl);
     V3 mypos = posl;
     Q4 myquat = quatl;
-    if (bl) {
-      reinterpret_cast<float4*>(s_xpq + kXpqStride * myb)[0] = {mypos.x, mypos.y, mypos.z, 0.f};
-      reinterpret_cast<float4*>(s_xpq + kXpqStride * myb)[1] = {myquat.w, myquat.x, myquat.y, myquat.z};
-    }
-    gsync();
-    for (int r = 0, span = 1; span < NLEVEL - 1 || r == 0; r++, span <<= 1) {
-      const int anc = r == 0 ? myp : (r == 1 ? myanc2 : (r == 2 ? myanc4 : myanc8));
-      float4 pp4 = {0.f, 0.f, 0.f, 0.f}, pq4 = {1.f, 0.f, 0.f, 0.f};
-      if (bl) { const float4* Pp = reinterpret_cast<const float4*>(s_xpq + kXpqStride * anc); pp4 = Pp[0]; pq4 = Pp[1]; }
-      gsync();
-      if (bl && anc != 0) {
-        const Q4 pq = {pq4.x, pq4.y, pq4.z, pq4.w};
-        mypos = V3{pp4.x, pp4.y, pp4.z} + qrot(pq, mypos);
-        myquat = qnormalize(qmul(pq, myquat));
-        reinterpret_cast<float4*>(s_xpq + kXpqStride * myb)[0] = {mypos.x, mypos.y, mypos.z, 0.f};
-        reinterpret_cast<float4*>(s_xpq + kXpqStride * myb)[1] = {myquat.w, myquat.x, myquat.y, myquat.z};
-      }
-      gsync();
-    }
-    if (bl) {
-      if (isfree) {
-        st3(s_xanchor + 3 * myja, mypos);
-        st3(s_xaxis + 3 * myja, {JB[0].x, JB[0].y, JB[0].z});
-      } else {
-        const Q4 pq = ldq(s_xpq + kXpqStride * myp + 4);
-        const V3 pp = ld3(s_xpq + kXpqStride * myp);
-#pragma unroll
-        for (int jj = 0; jj < 3; jj++) {
-          if (jj < myjn) {
-            st3(s_xaxis + 3 * (myja + jj), qrot(pq, axl[jj]));
-            st3(s_xanchor + 3 * (myja + jj), qrot(pq, ancl[jj]) + pp);
-          }
-        }
-      }
-      float mat[9];
-      q2mat(mat, myquat);
-      for (int i = 0; i < 9; i++) s_xmat[9 * myb + i] = mat[i];
-      st3(s_xipos + 3 * myb, mypos + mrot(mat, {ip.x, ip.y, ip.z}));
-    }
+    compose_world(bl, myb, myp, myanc2, myanc4, myanc8, NLEVEL, s_xpq, mypos, myquat);
+    if (bl) store_world_frames(isfree, myb, myp, myjn, myja, JB[0], axl, ancl, ip, mypos, myquat, s_xpq, s_xaxis, s_xanchor, s_xmat, s_xipos);
     gsync();
     HB_STAMP(2);
     // geoms: world position and z axis
     if (geoml) {
       const int g = l, b = pf_gbody;
-      st3(s_gpos + 3 * g, ld3(s_xpq + kXpqStride * b) + mrot(s_xmat + 9 * b, pf_gpos));
-      Q4 q = qmul(ldq(s_xpq + kXpqStride * b + 4), pf_gquat);
-      st3(s_gaxis + 3 * g, {2.f * (q.x * q.z + q.w * q.y), 2.f * (q.y * q.z - q.w * q.x), q.w * q.w - q.x * q.x - q.y * q.y + q.z * q.z});
+      const GeomPose G = geom_world_pose(s_xpq, b, s_xmat + 9 * b, pf_gpos, pf_gquat);
+      st3(s_gpos + 3 * g, G.pos);
+      st3(s_gaxis + 3 * g, quat_zaxis(G.quat));
     }
     // ---------------------------------------------------------------- mj_comPos (one kinematic tree)
     {
@@ -485,7 +425,7 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     }
     gsync();
     for (int r = 0, span = 1; span < NLEVEL - 1 || r == 0; r++, span <<= 1) {
-      const int anc = r == 0 ? myp : (r == 1 ? myanc2 : (r == 2 ? myanc4 : myanc8));
+      const int anc = ancestor_up(r, myp, myanc2, myanc4, myanc8);
       float4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0;
       if (bl && anc != 0) { const float4* Pp = reinterpret_cast<const float4*>(s_va + 12 * anc); a0 = Pp[0]; a1 = Pp[1]; a2 = Pp[2]; }
       gsync();
