@@ -1,5 +1,5 @@
 // hb_api_env.cpp — the C-ABI of libhb.so (include/hb.h), the env adapter: observations, rewards and resets, the realism layer and
-// domain randomisation, and the policy MLP.
+// domain randomisation, the policy MLP, and the sampling actor with its rollout collection.
 #include "hb_batch.hpp"
 
 extern "C" {
@@ -369,6 +369,20 @@ int hb_env_step_async(hb_batch* b, const float* action, int n_substeps, float* o
   return env_step_host(b, action, n_substeps, obs, reward, terminated, truncated, false);
 }
 
+// A layer's weights W[K][N] (row-major) in the B-operand order of v_mfma_f32_16x16x4_f32, as the fused policy and actor kernels stream them:
+// wp[tile][k/4][lane] = W[4(k/4) + lane/16][16 tile + lane%16], zero padded
+static std::vector<float> pack_mfma_b(const float* W, int K, int N) {
+  const int KK = (K + 3) / 4, ntile = (N + 15) / 16;
+  std::vector<float> wp((size_t)ntile * KK * 64, 0.f);
+  for (int nt = 0; nt < ntile; nt++)
+    for (int kk = 0; kk < KK; kk++)
+      for (int ln = 0; ln < 64; ln++) {
+        const int k = 4 * kk + (ln >> 4), n = 16 * nt + (ln & 15);
+        if (k < K && n < N) wp[((size_t)nt * KK + kk) * 64 + ln] = W[(size_t)k * N + n];
+      }
+  return wp;
+}
+
 int hb_policy_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases) {
   if (!b || !sizes || !weights || !biases || n_layers < 1 || n_layers > 4) return HB_EINVAL;
   if (sizes[0] != b->D.dm.nobs || sizes[n_layers] != b->D.dm.nu) return HB_EINVAL;
@@ -384,15 +398,7 @@ int hb_policy_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* 
     if (!weights[l] || !biases[l]) return HB_EINVAL;
     b->d_mlp_wp[l].reset();
     if (fused) {
-      // B-operand order of v_mfma_f32_16x16x4_f32: wp[tile][k/4][lane] = W[4(k/4) + lane/16][16 tile + lane%16], zero padded
-      const int K = sizes[l], N = sizes[l + 1], KK = (K + 3) / 4, ntile = (N + 15) / 16;
-      std::vector<float> wp((size_t)ntile * KK * 64, 0.f);
-      for (int nt = 0; nt < ntile; nt++)
-        for (int kk = 0; kk < KK; kk++)
-          for (int ln = 0; ln < 64; ln++) {
-            const int k = 4 * kk + (ln >> 4), n = 16 * nt + (ln & 15);
-            if (k < K && n < N) wp[((size_t)nt * KK + kk) * 64 + ln] = weights[l][(size_t)k * N + n];
-          }
+      const std::vector<float> wp = pack_mfma_b(weights[l], sizes[l], sizes[l + 1]);
       if (b->d_mlp_wp[l].alloc(wp.size()) != HB_OK) return HB_ENOMEM;
       HB_HIP(hipMemcpy(b->d_mlp_wp[l], wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
     }
@@ -484,6 +490,75 @@ int hb_rollout_policy(hb_batch* b, int T, float* qpos_out_dev) {
       if (rc != HB_OK) return rc;
     }
     steps_enqueued(b, nseg, reorder);
+  }
+  return HB_OK;
+}
+
+// ---- actor and rollout collection
+
+int hb_actor_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases, const hb_actor_config* cfg) {
+  if (!b || !sizes || !weights || !biases || !cfg || n_layers < 1 || n_layers > 4) return HB_EINVAL;
+  const int nu = b->D.dm.nu;
+  if (cfg->head != HB_ACTOR_DETERMINISTIC && cfg->head != HB_ACTOR_GAUSSIAN && cfg->head != HB_ACTOR_SQUASHED) return HB_EINVAL;
+  if (nu < 1 || nu > kActorMaxNu) return HB_EINVAL;
+  if (sizes[0] != b->D.dm.nobs || sizes[n_layers] != (cfg->head == HB_ACTOR_SQUASHED ? 2 * nu : nu)) return HB_EINVAL;
+  for (int l = 0; l <= n_layers; l++) if (sizes[l] < 1) return HB_EINVAL;
+  for (int l = 0; l < n_layers; l++) if (!weights[l] || !biases[l]) return HB_EINVAL;
+  if (cfg->head == HB_ACTOR_GAUSSIAN) for (int i = 0; i < nu; i++) if (!std::isfinite(cfg->log_std[i])) return HB_EINVAL;
+  for (int l = 0; l <= n_layers; l++) if (sizes[l] > 256) return HB_EUNSUPPORTED;  // (the fused kernel's LDS tiles; no layer-by-layer fallback)
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a collection still in flight reads the buffers that are replaced below)
+  // (every argument check is behind us: from here on only the device can fail, and then no actor is installed)
+  b->actor_layers = 0;
+  for (int l = 0; l < 4; l++) reset_all(b->d_actor_wp[l], b->d_actor_b[l]);
+  for (int l = 0; l < n_layers; l++) {
+    const std::vector<float> packed = pack_mfma_b(weights[l], sizes[l], sizes[l + 1]);
+    if (b->d_actor_wp[l].alloc(packed.size()) != HB_OK || b->d_actor_b[l].alloc(sizes[l + 1]) != HB_OK) return HB_ENOMEM;
+    HB_HIP(hipMemcpy(b->d_actor_wp[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+    HB_HIP(hipMemcpy(b->d_actor_b[l], biases[l], sizes[l + 1] * sizeof(float), hipMemcpyHostToDevice));
+  }
+  b->actor_layers = n_layers;
+  for (int l = 0; l <= n_layers; l++) b->actor_sizes[l] = sizes[l];
+  b->actor_cfg = *cfg;
+  b->actor_draw0 = 0;
+  return HB_OK;
+}
+
+int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out* out) {
+  if (!b || T < 1 || n_substeps < 1 || !out || !out->obs || !out->action || b->actor_layers < 1) return HB_EINVAL;
+  if (out->log_std && b->actor_cfg.head != HB_ACTOR_SQUASHED) return HB_EINVAL;
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  const DevModel& dm = b->D.dm;
+  const size_t n = b->n_env, nu = dm.nu, nobs = dm.nobs;
+  if (out->terminal_obs && !b->d_term_obs && (rc = hb_env_terminal_obs(b, nullptr)) != HB_OK) return rc;
+  ActorDesc ad;
+  memset(&ad, 0, sizeof ad);
+  ad.net.nl = b->actor_layers;
+  int widest = 1;
+  for (int l = 0; l <= b->actor_layers; l++) { ad.net.sizes[l] = b->actor_sizes[l]; widest = std::max(widest, b->actor_sizes[l]); }
+  for (int l = 0; l < b->actor_layers; l++) { ad.net.w[l] = b->d_actor_wp[l]; ad.net.b[l] = b->d_actor_b[l]; }
+  ad.net.ldx = widest + 4;  // + the K pad columns (K is swept four at a time); 16-row tiles
+  ad.head = b->actor_cfg.head; ad.deterministic = b->actor_cfg.deterministic != 0; ad.nu = dm.nu; ad.seed = b->actor_cfg.seed;
+  memcpy(ad.log_std, b->actor_cfg.log_std, sizeof ad.log_std);
+  for (int t = 0; t < T; t++) {
+    const size_t row = (size_t)t * n;
+    ActorTapes tp;
+    tp.action = out->action + row * nu;
+    tp.mean = out->mean ? out->mean + row * nu : nullptr;
+    tp.log_std = out->log_std ? out->log_std + row * nu : nullptr;
+    tp.eps = out->eps ? out->eps + row * nu : nullptr;
+    HB_HIP(launch_actor(ad, out->obs + row * nobs, tp, b->n_env, (unsigned)b->env_offset, b->actor_draw0, main_stream(b)));
+    b->actor_draw0++;
+    // (outputs of the step that have no tape land in the batch's own record, hb_env_step's device buffers)
+    rc = env_step_impl(b, tp.action, n_substeps, nullptr, true, out->obs + (row + n) * nobs, out->reward ? out->reward + row : b->d_reward,
+                       out->terminated ? out->terminated + row : b->d_term, out->truncated ? out->truncated + row : b->d_trunc);
+    if (rc != HB_OK) return rc;
+    if (out->terminal_obs)
+      HB_HIP(hipMemcpyAsync(out->terminal_obs + row * nobs, b->d_term_obs, n * nobs * sizeof(float), hipMemcpyDeviceToDevice, main_stream(b)));
   }
   return HB_OK;
 }

@@ -199,6 +199,13 @@ struct hb_batch {
   DevBuf<float> d_mlp_b[4];
   DevBuf<float> d_mlp_h[2];  // hidden activations, ping-pong
   DevBuf<float> d_mlp_act;   // activation scratch of the LDS-free policy kernel: [n_env / 16 + kPipes][2][16][widest + 4]
+  // sampling actor (hb_actor_set_mlp, hb_env_collect_dev): packed weights and biases of hb_actor_kernel, the head, and the number of
+  // steps collected since the actor was installed (the step counter of its random draws)
+  int actor_layers = 0;  // 0: none installed
+  int actor_sizes[5] = {0, 0, 0, 0, 0};
+  DevBuf<float> d_actor_wp[4], d_actor_b[4];
+  hb_actor_config actor_cfg = {};
+  unsigned actor_draw0 = 0;
   // optional per-kernel timing of the step kernel (hb_step_timing)
   bool time_steps = false;
   std::vector<hipEvent_t> tev;  // pairs

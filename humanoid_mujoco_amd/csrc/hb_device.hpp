@@ -245,6 +245,21 @@ struct PolicyDesc {
   int ldx;  // LDS row stride of an activation tile: widest layer + 4 (K is swept four columns at a time: zero pad columns)
 };
 
+// fused actor kernel (hb_actor_kernel, hb_actor.hip): the same network description, the sampling head (hb_actor_config, include/hb.h)
+// and the tapes of one step, each [n_env][nu]; action is always there, the others may be null
+constexpr int kActorMaxNu = 32;
+enum { kActorDeterministic = 0, kActorGaussian = 1, kActorSquashed = 2 };  // ActorDesc::head = HB_ACTOR_* (include/hb.h)
+constexpr unsigned RS_ACTOR = 32;  // random-number stream of the actor's draws (hb_kcommon.hpp: RS_*, 1..8; hb_env.hip: RS_DR_*, 16..25)
+struct ActorDesc {
+  PolicyDesc net;
+  int head, deterministic, nu;
+  unsigned seed;
+  float log_std[kActorMaxNu];
+};
+struct ActorTapes {
+  float *action, *mean, *log_std, *eps;
+};
+
 // Buffers of the STAGED step of the general variants (launch_step): hb_pose_kernel writes every geom's world pose and the env's
 // narrowphase work items, hb_narrow_kernel evaluates the items (one per lane, at the occupancy of a small kernel: the MPR climbs are
 // chains of dependent loads), the step kernel appends the results in item order.  All null: the step kernel does all of it itself.

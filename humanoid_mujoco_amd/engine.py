@@ -134,6 +134,21 @@ class HbDomainRandomization(ctypes.Structure):
                 ("floor_bump_min", ctypes.c_float), ("floor_bump_max", ctypes.c_float)]
 
 
+ACTOR_DETERMINISTIC, ACTOR_GAUSSIAN, ACTOR_SQUASHED = 0, 1, 2  # hb_actor_config.head (HB_ACTOR_*)
+ACTOR_HEADS = {"deterministic": ACTOR_DETERMINISTIC, "gaussian": ACTOR_GAUSSIAN, "squashed": ACTOR_SQUASHED}
+RS_ACTOR = 32  # random-number stream of the actor's draws (include/hb.h: hb_env_collect_dev)
+
+
+class HbActorConfig(ctypes.Structure):
+    """hb_actor_config (include/hb.h): the sampling head of the actor."""
+    _fields_ = [("head", ctypes.c_int), ("seed", ctypes.c_uint), ("log_std", ctypes.c_float * 32), ("deterministic", ctypes.c_int)]
+
+
+class HbCollectOut(ctypes.Structure):
+    """hb_collect_out (include/hb.h): device pointers of the tapes hb_env_collect_dev reads (obs row 0) and writes."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("obs", "action", "mean", "log_std", "eps", "reward", "terminated", "truncated", "terminal_obs")]
+
+
 class HbError(RuntimeError):
     pass
 
@@ -242,6 +257,8 @@ def lib():
     L.hb_policy_set_mlp.argtypes = [vp, ci, vp, vp, vp]
     L.hb_policy_eval.argtypes = [vp, vp]
     L.hb_rollout_policy.argtypes = [vp, ci, vp]
+    L.hb_actor_set_mlp.argtypes = [vp, ci, vp, vp, vp, ctypes.POINTER(HbActorConfig)]
+    L.hb_env_collect_dev.argtypes = [vp, ci, ci, ctypes.POINTER(HbCollectOut)]
     L.hb_dev_alloc.restype = vp; L.hb_dev_alloc.argtypes = [vp, ctypes.c_uint64]
     L.hb_dev_free.restype = None; L.hb_dev_free.argtypes = [vp, vp]
     L.hb_host_alloc.restype = vp; L.hb_host_alloc.argtypes = [ctypes.c_uint64]
@@ -1115,6 +1132,43 @@ class Batch:
 
     def rollout_policy(self, T, qpos_out_ptr=None):
         _check(lib().hb_rollout_policy(self._h, int(T), ctypes.c_void_p(qpos_out_ptr or 0)), "hb_rollout_policy")
+
+    # ---- actor and rollout collection (include/hb.h: hb_actor_set_mlp, hb_env_collect_dev)
+    def actor_set(self, sizes, weights, biases, head="gaussian", log_std=None, seed=0, deterministic=False):
+        """Installs the sampling actor.  sizes: [nobs, hidden..., nu] (head "squashed": ..., 2 nu); weights[l]: [sizes[l], sizes[l+1]]
+        float32 - the TRANSPOSE of torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; tanh after every hidden layer.  head: "deterministic"
+        (tanh output, no sampling), "gaussian" (linear mean, state-independent log_std [nu]: SB3 PPO / A2C) or "squashed" (linear
+        mean | log_std, clamped to [-20, 2], tanh of the sample: SB3 SAC), or the ACTOR_* value.  At most four layers of width <= 256."""
+        head = ACTOR_HEADS[head] if isinstance(head, str) else int(head)
+        sizes = [int(s) for s in sizes]
+        ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
+        bs = [np.ascontiguousarray(x, dtype=np.float32) for x in biases]
+        if len(ws) != len(sizes) - 1 or len(bs) != len(ws) or any(w.shape != (a, c) for w, a, c in zip(ws, sizes[:-1], sizes[1:])) or \
+                any(x.shape != (c,) for x, c in zip(bs, sizes[1:])):
+            raise ValueError("actor_set: weights[l] must be [sizes[l], sizes[l+1]] and biases[l] [sizes[l+1]]")
+        cfg = HbActorConfig()
+        cfg.head, cfg.seed, cfg.deterministic = head, int(seed) & 0xFFFFFFFF, int(bool(deterministic))
+        if log_std is not None:
+            ls = np.broadcast_to(np.asarray(log_std, dtype=np.float32), (self.model.nu,))
+            if len(ls) > 32:
+                raise ValueError("actor_set: log_std holds at most 32 actuators")
+            cfg.log_std[:len(ls)] = [float(x) for x in ls]
+        csz = (ctypes.c_int * len(sizes))(*sizes)
+        wp = (ctypes.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+        bp = (ctypes.c_void_p * len(bs))(*[x.ctypes.data for x in bs])
+        rc = lib().hb_actor_set_mlp(self._h, len(ws), csz, wp, bp, ctypes.byref(cfg))
+        _check(rc, "hb_actor_set_mlp", "a layer wider than 256: the actor is one fused kernel, there is no layer-by-layer path" if rc == -4 else
+               "sizes must run from nobs to nu (squashed: 2 nu) over 1..4 layers, nu <= 32, log_std finite" if rc == -1 else None)
+        self.actor_head = head
+
+    def env_collect_dev(self, T, n_substeps=1, obs=None, action=None, mean=None, log_std=None, eps=None, reward=None, terminated=None,
+                        truncated=None, terminal_obs=None):
+        """hb_env_collect_dev: T env steps with the installed actor in the loop, enqueued on the batch's stream.  Device pointers (ints, e.g.
+        torch tensors' data_ptr()) of the tapes; obs [T + 1, n_env, nobs] (row 0 is the input) and action [T, n_env, nu] are required."""
+        out = HbCollectOut(obs, action, mean, log_std, eps, reward, terminated, truncated, terminal_obs)
+        rc = lib().hb_env_collect_dev(self._h, int(T), int(n_substeps), ctypes.byref(out))
+        _check(rc, "hb_env_collect_dev", "needs T >= 1, n_substeps >= 1, obs and action tapes, an installed actor (actor_set), and a log_std "
+               "tape only with the squashed head" if rc == -1 else None)
 
     # ---- device buffers / timing helpers (no HIP headers or torch needed on the caller's side)
     def dev_alloc(self, nbytes):

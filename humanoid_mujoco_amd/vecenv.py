@@ -80,6 +80,7 @@ class VecEnv:
         if self._body_accelerations:
             self.batch.body_acc_readout(True)
         self._scan = None
+        self._last_obs = None  # the observation last returned (host array or CUDA tensor): collect()'s default starting point
         self._device = int(device)
         if height_scan is not None:
             hs = dict(height_scan)
@@ -176,7 +177,8 @@ class VecEnv:
         return [indices] if isinstance(indices, int) else list(indices)
 
     def reset(self):
-        return self.batch.env_reset()
+        self._last_obs = self.batch.env_reset()  # (a reference only: what collect() starts from when it is given no obs0)
+        return self._last_obs
 
     def step_async(self, actions):
         """stable-baselines3's VecEnv.step_async: the step is enqueued (actions up, physics, observations down) and the host returns at once"""
@@ -210,6 +212,7 @@ class VecEnv:
         return obs, rew, done, infos
 
     def _finish(self, obs, rew, term, trunc):
+        self._last_obs = obs
         done = term | trunc
         # "warnings": the per-env HB_WARN_* bits (mjData.warning, mjdata.h:54-65): a contact or constraint-row overflow (rows were dropped for
         # that env-step) or a bad-state reset is visible to the training loop instead of silently changing that env's physics.  Polled every
@@ -332,7 +335,63 @@ class VecEnv:
         self.batch.env_step_dev(a.data_ptr(), o.data_ptr(), r.data_ptr(), te.data_ptr(), tr.data_ptr(), self.n_substeps)
         cur.wait_stream(self._t_stream)   # and the caller's stream sees the results
         a.record_stream(self._t_stream)
+        self._last_obs = o
         return o, r, te.view(torch.bool), tr.view(torch.bool)  # (the kernel writes 0 / 1 bytes: a view, not two conversion kernels)
+
+    def actor_set(self, sizes, weights, biases, head="gaussian", log_std=None, seed=None, deterministic=False):
+        """Installs the sampling actor collect() / collect_torch() run in the env loop (Batch.actor_set: weights[l] is [in, out], the
+        transpose of torch.nn.Linear.weight; heads "deterministic", "gaussian", "squashed").  seed defaults to this VecEnv's seed; its
+        draws are a random stream of their own, independent of the realism layer's."""
+        self.batch.actor_set(sizes, weights, biases, head=head, log_std=log_std, seed=self.seed_value if seed is None else seed, deterministic=deterministic)
+
+    def collect_torch(self, T, obs0=None, terminal_obs=False):
+        """T steps of the installed actor in the env loop on the device (hb_env_collect_dev): no host transfer, no host synchronisation,
+        one Python call.  Returns a dict of CUDA tensors: "obs" [T + 1, n, nobs] (row 0 is obs0; row t + 1 the observation after step t,
+        for an env that finished there the first of its new episode), "action", "mean", "eps" [T, n, nu] (and "log_std" with the squashed
+        head), "reward" [T, n] float32, "terminated", "truncated" [T, n] bool, and with terminal_obs=True "terminal_obs" [T, n, nobs], whose
+        row (t, e) is the observation of the state env e's episode ended in where terminated | truncated is set at (t, e) and an older
+        value elsewhere.  obs0: the observation the envs last returned, [n, nobs] as a CUDA tensor or array; default: what this VecEnv
+        last returned from reset / step* / collect* (uploaded here if it lives on the host).  The tensors are rewritten by the next
+        collection of the same T.  Streams are ordered as in step_torch."""
+        import torch
+        T = int(T)
+        n, nobs, nu = self.num_envs, self.model.nobs, self.model.nu
+        dev = torch.device("cuda", self._device)
+        squashed = getattr(self.batch, "actor_head", None) == 2
+        key = (T, bool(terminal_obs), squashed)
+        cache = getattr(self, "_t_collect", None)
+        if cache is None:
+            cache = self._t_collect = {}
+        if key not in cache:
+            f32 = dict(dtype=torch.float32, device=dev)
+            t = {"obs": torch.empty((T + 1, n, nobs), **f32), "action": torch.empty((T, n, nu), **f32), "mean": torch.empty((T, n, nu), **f32),
+                 "eps": torch.empty((T, n, nu), **f32), "reward": torch.empty((T, n), **f32),
+                 "terminated": torch.empty((T, n), dtype=torch.uint8, device=dev), "truncated": torch.empty((T, n), dtype=torch.uint8, device=dev)}
+            if squashed:
+                t["log_std"] = torch.empty((T, n, nu), **f32)
+            if terminal_obs:
+                t["terminal_obs"] = torch.empty((T, n, nobs), **f32)
+            cache[key] = t
+        t = cache[key]
+        src = self._last_obs if obs0 is None else obs0
+        if src is None:
+            raise RuntimeError("collect: no observation to start from - call reset() first or pass obs0")
+        stream = torch.cuda.ExternalStream(self.batch.stream, device=dev)  # (fetching the stream launches held step calls and joins the pipes)
+        cur = torch.cuda.current_stream(dev)
+        src = torch.as_tensor(src, dtype=torch.float32)
+        assert tuple(src.shape) == (n, nobs), tuple(src.shape)
+        t["obs"][0].copy_(src)  # on the caller's stream, behind whatever produced src (a host array: uploaded here)
+        stream.wait_stream(cur)   # obs[0] is complete, and whoever still reads the previous tapes is done, before they are rewritten
+        self.batch.env_collect_dev(T, self.n_substeps, **{k: v.data_ptr() for k, v in t.items()})
+        cur.wait_stream(stream)   # and the caller's stream sees the results
+        self._last_obs = t["obs"][T]
+        out = dict(t)
+        out["terminated"], out["truncated"] = t["terminated"].view(torch.bool), t["truncated"].view(torch.bool)
+        return out
+
+    def collect(self, T, obs0=None, terminal_obs=False):
+        """collect_torch with numpy arrays: the same dict, copied to the host (one synchronisation at the end)."""
+        return {k: v.cpu().numpy() for k, v in self.collect_torch(T, obs0=obs0, terminal_obs=terminal_obs).items()}
 
     def close(self):
         self.batch.close()

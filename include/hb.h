@@ -803,6 +803,57 @@ int hb_policy_eval(hb_batch* b, float* ctrl_out);
  * qpos_out_dev (nullable, device) receives [T][n_env][nq]. */
 int hb_rollout_policy(hb_batch* b, int T, float* qpos_out_dev);
 
+/* ---- actor and rollout collection: a sampling policy in the env loop, with tapes of what happened ------------------------------ */
+
+#define HB_ACTOR_DETERMINISTIC 0  /* action = tanh(last layer): hb_policy_eval's network, no sampling */
+#define HB_ACTOR_GAUSSIAN 1       /* action = mean + exp(log_std[i]) * eps; the last layer is linear; log_std is state independent (SB3 PPO / A2C) */
+#define HB_ACTOR_SQUASHED 2       /* the last layer is linear and 2 nu wide: mean | log_std; log_std is clamped to [-20, 2];
+                                     action = tanh(mean + exp(log_std) * eps)  (SB3 SAC's actor - what the reference trains) */
+typedef struct hb_actor_config {
+  int head;              /* HB_ACTOR_* */
+  unsigned seed;
+  float log_std[32];     /* HB_ACTOR_GAUSSIAN: one per actuator (nu <= 32) */
+  int deterministic;     /* 1: eps = 0 for every head (evaluation rollouts) */
+} hb_actor_config;
+
+/* Installs the actor of hb_env_collect_dev: an MLP obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] with tanh after every hidden layer; the
+ * last layer has tanh for head 0 and is linear for heads 1 and 2.  sizes[0] == nobs; sizes[n_layers] == nu for heads 0 and 1 and 2 nu for
+ * head 2.  weights[l] is row-major [sizes[l]][sizes[l+1]] float32 (the transpose of torch.nn.Linear.weight), biases[l] is [sizes[l+1]];
+ * host pointers, copied to the device.  The actor is separate from the MLP of hb_policy_set_mlp: either may be installed or replaced
+ * without touching the other.  Installing an actor sets the batch's draw counter (below) back to 0.
+ * Refusals: HB_EINVAL - NULL argument, n_layers outside 1..4, a size < 1, sizes[0] or sizes[n_layers] not as above, a head that is none
+ * of HB_ACTOR_*, nu > 32, a non-finite log_std[i] (i < nu, head 1); HB_EUNSUPPORTED - a width above 256: the actor is one fused kernel
+ * whose activation tiles live in LDS, and there is no layer-by-layer fallback.  A refused call leaves the installed actor as it was. */
+int hb_actor_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases, const hb_actor_config* cfg);
+
+typedef struct hb_collect_out {   /* device pointers; every field but obs and action may be NULL */
+  float* obs;           /* [T + 1][n_env][nobs]  row 0 is INPUT, written by the caller (see below) */
+  float* action;        /* [T][n_env][nu]        what was handed to the env adapter */
+  float* mean;          /* [T][n_env][nu]        the head's mean (head 0: equal to action) */
+  float* log_std;       /* [T][n_env][nu]        HB_ACTOR_SQUASHED: the clamped log_std */
+  float* eps;           /* [T][n_env][nu]        the N(0, 1) draws (zeros when deterministic) */
+  float* reward;        /* [T][n_env] */
+  uint8_t* terminated;  /* [T][n_env] */
+  uint8_t* truncated;   /* [T][n_env] */
+  float* terminal_obs;  /* [T][n_env][nobs]      row (t, e) is meaningful where env e finished at step t */
+} hb_collect_out;
+
+/* T env steps with the actor in the loop, all enqueued on the batch's stream: no host synchronisation, no host transfer.  For
+ * t = 0 .. T-1: the actor kernel reads obs[t] and writes mean[t], log_std[t], eps[t] (those given) and action[t]; then exactly
+ * hb_env_step_dev(b, action[t], n_substeps, obs[t+1], reward[t], terminated[t], truncated[t]) - action noise and delay, pushes, physics,
+ * reward, termination, auto-reset (an env that finishes at step t is reset in place and obs[t+1] holds the first observation of its new
+ * episode), the realism layer on the observation.  With terminal_obs the recording of hb_env_terminal_obs is switched on if it is not
+ * yet, and after step t the batch's terminal-observation table is copied (device to device) into terminal_obs[t]: rows of envs that did
+ * NOT finish at t hold older values (the table's row of an env changes only when that env finishes; zeros before its first end).
+ * obs[0] is supplied by the caller: the observation the env last returned - from hb_env_reset, the last hb_env_step*, or row T of the
+ * previous collection.  The library keeps no hidden current observation, so the call is a pure function of the batch, the actor and
+ * obs[0].  eps[t][e][i] is the existing counter-based normal draw (seed = cfg.seed, env = the batch's env offset + e, episode 0,
+ * step = draw0 + t, stream RS_ACTOR = 32 - the realism layer uses 1..8, domain randomisation 16..25 -, element i), where draw0 counts the
+ * steps collected since hb_actor_set_mlp: reproducible, the same on any split of a batch across GPUs, independent of the env adapter's
+ * noise.  hb_last_kernel names the step kernel; hb_batch_step_launches counts as for hb_env_step_dev.
+ * HB_EINVAL: NULL b or out, T < 1, n_substeps < 1, NULL obs or action, no actor installed, a log_std tape with a head other than 2. */
+int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out* out);
+
 /* ---- host-side helpers so a C/C++/ctypes caller needs no HIP headers ---------------------------- */
 
 /* Device buffer on the batch's GPU (hipMalloc / hipFree). */
