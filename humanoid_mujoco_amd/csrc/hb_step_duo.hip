@@ -69,6 +69,13 @@ __device__ __forceinline__ void half_sums(float v, float& lo, float& hi) {
   lo = rdlane(v, 0) + rdlane(v, 16);
   hi = rdlane(v, 32) + rdlane(v, 48);
 }
+// x of lanes 0..15 of each half in both DPP rows of that half (u), and x of lanes 16..31 likewise (v): v_permlane16_swap_b32 on two copies of x
+// swaps lanes 16..31 of the first with lanes 0..15 of the second, half by half
+__device__ __forceinline__ void uv_copies(float x, float& u, float& v) {
+  const u32x2 s = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  u = __uint_as_float(s.x);
+  v = __uint_as_float(s.y);
+}
 // the half that starts at lane BASE (0 or 32) alone
 template <int BASE>
 __device__ __forceinline__ float half_sum(float v) {
@@ -1073,14 +1080,19 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     int niterLo = 0, niterHi = 0;
     if (paired) {
       // Both envs at most 31 rows, env A's on lanes 0.., env B's on lanes 32..: the two Gauss-Seidel sweeps run SIDE BY SIDE - row i of
-      // both envs in one row step (every lane proposes; the turn-holders of the two halves are read out by two v_readlane, each half
-      // takes its own).  The two dependency chains share their instructions: one row step serves two envs.  Per env the arithmetic,
-      // and its order, is the one-env sweep's.
+      // both envs in one row step (every lane proposes; the turn-holder's proposal reaches the row lanes of its own env by a DPP broadcast
+      // inside its row of 16 lanes, each half with its own).  The two dependency chains share their instructions: one row step serves two
+      // envs.  Per env the arithmetic, and its order, is the one-env sweep's.  Two forms: both envs at most 16 rows - an env's rows lie in
+      // ONE DPP row (HB_PGS_ROWB, 4 VALU and a shift per row step); an env of 17..31 rows - every sweep quantity is held twice, once per
+      // DPP row (HB_PGS_ROWW, 6 VALU and a shift).  Neither writes EXEC, reads a lane through an SGPR or has a VALU read an SGPR that a VALU
+      // wrote; the forms that did are in profiles/pgs_sweeps_bench.txt and profiles/pgs_bcast_bench.txt.  Once one env has stopped, the
+      // other sweeps on alone (the tail below).
       const float* const arS = ar;  // the lane's AR column over the rows of its own env (0..30)
-      const float nAinv = -1.f / Aii;
+      float nAinv = -1.f / Aii;
       float arf = 0.f;
       const int nmax2 = max(nLo, nHi);
       const bool short16 = nmax2 <= 16;  // both envs at most 16 rows: the sweeps take the broadcast row step (HB_PGS_ROWB below)
+      const bool wide = !short16;        // an env of 17..31 rows: every sweep quantity is held twice, once per DPP row (HB_PGS_ROWW below)
       {
         const float jar = jw - aref;
         force = (rowact && jar < 0.f) ? -Dd * jar : 0.f;
@@ -1098,44 +1110,26 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
         if (cost > 0.f) { force = 0.f; arf = 0.f; }
       }
       float res = rowact ? bvec + arf : 0.f;
+      // An env of 17..31 rows spans both DPP rows of its half, so the wide sweeps keep every sweep quantity TWICE, once in each DPP row:
+      // lane c holds U, the residual of row c & 15 (in `res`), and V, that of row 16 + (c & 15) (in `resV`), and likewise nAinv, nforce
+      // and the AR entries - ar[k] = AR[c & 15][k], ar[32 + k] = AR[16 + (c & 15)][k] (AR is bitwise symmetric: lane c ^ 16's column IS the
+      // second column lane c needs; ar[32..62] are free while paired).  Lanes c and c ^ 16 then compute the same, and a row step needs
+      // nothing from outside the lane's own DPP row.  v_permlane16_swap_b32 x, x' on two copies of x leaves {lanes 0..15 of a half twice}
+      // in the one and {lanes 16..31 twice} in the other: the U and the V copy at once.  `rres` is the residual in row layout (lane =
+      // row), where the forces, the steps and the convergence sums stay; while nothing is wide it is `res`.  Only the paired loop has a
+      // wide form: the tail takes everything back in row layout (below).
+      float rres = res, resV = 0.f, nAinvV = nAinv;
+      if (wide) {
+#pragma unroll
+        for (int k = 0; k < 31; k++) uv_copies(ar[k], ar[k], ar[32 + k]);
+        uv_copies(nAinv, nAinv, nAinvV);
+        uv_copies(rres, res, resV);
+      }
       const int max_sweeps = M.iterations;
       const float pgs_tol = M.tolerance, pgs_scale = M.pgs_scale;
       bool liveLo = nLo > 0 && max_sweeps > 0, liveHi = nHi > 0 && max_sweeps > 0;
       const bool sweptLo = liveLo, sweptHi = liveHi;
       float force_out = force;
-      // The row step writes its proposal max(res * nAinv, nforce) straight into the sweep's step register dl, under an EXEC that holds only the
-      // lanes whose turn has not passed (todo: the rows this sweep runs; bit i leaves after row i).  Lane i so keeps the step of its own turn,
-      // a lane without a turn keeps the 0 that dl starts with, and nothing is spent on carrying the steps along (v_readlane ignores EXEC, and
-      // only pending lanes' proposals are ever read).  Every value comes from the instruction, and the operands, of the one-env kernel's row step.
-      // A chunk of four rows is ONE asm statement: EXEC is narrowed inside it only and restored before it ends.  Wait states inside the string
-      // (the compiler's hazard recogniser does not look there): the scalar mask update sits between the v_max that writes dl and the v_readlane
-      // that reads it (one state), and no VALU instruction reads a scalar register within two instructions of the v_readlane that wrote it.
-      // while BOTH envs sweep: one row step = row i of both, 6 VALU: mul, max, two v_readlane, and each half's fma under its half of EXEC (a
-      // v_cndmask between the two scalars would cost two more VALU moves: one scalar operand per instruction)
-#define HB_PGS_MASK2 "s_mov_b32 exec_lo, %[m]\n\ts_mov_b32 exec_hi, %[m]\n\t"
-#define HB_PGS_ROW2(k)                                                               \
-  "v_mul_f32_e32 %[d], %[na], %[r]\n\t"                                              \
-  "v_max_f32_e32 %[dl], %[d], %[nf]\n\t"                                             \
-  "s_bitset0_b32 %[m], %[i0]+" #k "\n\t"                                             \
-  "v_readlane_b32 %[a], %[dl], %[i0]+" #k "\n\t"                                     \
-  "v_readlane_b32 %[b], %[dl], %[i0]+32+" #k "\n\t"                                  \
-  "s_mov_b64 exec, %[lo]\n\t"                                                        \
-  "v_fmac_f32_e32 %[r], %[a], %[ar" #k "]\n\t"                                       \
-  "s_mov_b64 exec, %[hi]\n\t"                                                        \
-  "v_fmac_f32_e32 %[r], %[b], %[ar" #k "]\n\t"
-#define HB_PGS_ROWS2_4 HB_PGS_MASK2 HB_PGS_ROW2(0) HB_PGS_MASK2 HB_PGS_ROW2(1) HB_PGS_MASK2 HB_PGS_ROW2(2) HB_PGS_MASK2 HB_PGS_ROW2(3)
-#define HB_PGS_ROWS2_3 HB_PGS_MASK2 HB_PGS_ROW2(0) HB_PGS_MASK2 HB_PGS_ROW2(1) HB_PGS_MASK2 HB_PGS_ROW2(2)
-#define HB_PGS_CHUNK2(c, rows)                                                       \
-  if ((c) * 4 >= ne) break;                                                          \
-  {                                                                                  \
-    float d_;                                                                        \
-    int da_, db_;                                                                    \
-    unsigned long long ex_;                                                          \
-    asm volatile("s_mov_b64 %[t], exec\n\t" rows "s_mov_b64 exec, %[t]"              \
-                 : [r] "+v"(res), [dl] "+v"(dl), [m] "+s"(todo), [d] "=&v"(d_), [a] "=&s"(da_), [b] "=&s"(db_), [t] "=&s"(ex_) \
-                 : [na] "v"(nAinv), [nf] "v"(nforce), [ar0] "v"(arS[(c) * 4]), [ar1] "v"(arS[(c) * 4 + 1]), [ar2] "v"(arS[(c) * 4 + 2]), \
-                   [ar3] "v"(arS[(c) * 4 + 3 < 31 ? (c) * 4 + 3 : 30]), [i0] "n"((c) * 4), [lo] "s"(0x00000000ffffffffull), [hi] "s"(0xffffffff00000000ull)); \
-  }
       // Both envs at most 16 rows (short16): every row of an env lies in ONE DPP row of 16 lanes (row 0 for env A, row 2 for env B), and lane k's value
       // reaches the row lanes of its own env by the DPP control row_newbcast:k inside the vector pipe - no v_readlane, no SGPR, no EXEC
       // write.  Lanes 16..31 and 48..63 read lane 16 + k of their own row: a lane without a row, whose proposal is -0 and whose AR column is 0.
@@ -1165,55 +1159,99 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
                  : "scc");                                                           \
   }
 #define HB_PGS_SWEEPB do { HB_PGS_CHUNKB(0, "s_nop 0\n\t") HB_PGS_CHUNKB(1, "") HB_PGS_CHUNKB(2, "") HB_PGS_CHUNKB(3, "") } while (0)
-      // the end of a paired sweep, the same behind both forms of the row step: the steps join the forces, then each env's convergence test
+      // The wide row step, for an env of 17..31 rows (the U / V copies above), 6 VALU and the shift: for k < 16 the proposal comes from U, for
+      // k >= 16 from V with row_newbcast:(k - 16) - [rp] is the residual the proposals of the chunk come from, [rq] the other one.  Both DPP rows
+      // of a half compute the same proposals, so lane k's proposal of row k is in lane k & 15 of BOTH rows and each fmac reads it inside the
+      // lane's own DPP row.  The mask {k, 32 + k} keeps walking up: above 15 its bit is lane k, whose V is row k - the steps stay in row
+      // layout.  Only the fmac into [rp] is on the chain to the next proposal.  No EXEC write, no v_readlane, no SGPR that a vector
+      // instruction reads after a vector instruction wrote it; wait states as in HB_PGS_ROWB.  A short env beside a tall one rides along:
+      // its V rows are inert (zero AR, proposals of -0) like the padding rows of the last chunk.
+#define HB_PGS_ROWW(k)                                                               \
+  "v_mul_f32_e32 %[d], %[na], %[rp]\n\t"                                             \
+  "v_max_f32_e32 %[d], %[d], %[nf]\n\t"                                              \
+  "v_cndmask_b32_e64 %[dl], %[dl], %[d], %[m]\n\t"                                   \
+  "s_lshl_b64 %[m], %[m], 1\n\t"                                                     \
+  "v_fmac_f32_dpp %[rp], %[d], %[ap" #k "] row_newbcast:%[k" #k "] row_mask:0xf bank_mask:0xf\n\t" \
+  "v_fmac_f32_dpp %[rq], %[d], %[aq" #k "] row_newbcast:%[k" #k "] row_mask:0xf bank_mask:0xf\n\t"
+#define HB_PGS_ROWSW_4 HB_PGS_ROWW(0) HB_PGS_ROWW(1) HB_PGS_ROWW(2) HB_PGS_ROWW(3)
+#define HB_PGS_ROWSW_3 HB_PGS_ROWW(0) HB_PGS_ROWW(1) HB_PGS_ROWW(2)
+      // one chunk of four rows (the last: three); po / qo: where the columns of [rp] / [rq] start in ar (0: U, 32: V).  A wide sweep has at
+      // least 17 rows: the first five chunks run without a test
+#define HB_PGS_CHUNKW(c, pre, rows, rp_, rq_, na_, nf_, po, qo)                      \
+  if ((c) > 4 && (c) * 4 >= ne) break;                                               \
+  {                                                                                  \
+    float d_;                                                                        \
+    asm volatile(pre rows                                                            \
+                 : [rp] "+v"(rp_), [rq] "+v"(rq_), [dl] "+v"(dl), [m] "+s"(turn), [d] "=&v"(d_) \
+                 : [na] "v"(na_), [nf] "v"(nf_),                                     \
+                   [ap0] "v"(arS[(po) + (c) * 4]), [ap1] "v"(arS[(po) + (c) * 4 + 1]), [ap2] "v"(arS[(po) + (c) * 4 + 2]), [ap3] "v"(arS[(po) + ((c) * 4 + 3 < 31 ? (c) * 4 + 3 : 30)]), \
+                   [aq0] "v"(arS[(qo) + (c) * 4]), [aq1] "v"(arS[(qo) + (c) * 4 + 1]), [aq2] "v"(arS[(qo) + (c) * 4 + 2]), [aq3] "v"(arS[(qo) + ((c) * 4 + 3 < 31 ? (c) * 4 + 3 : 30)]), \
+                   [k0] "n"(((c) * 4) & 15), [k1] "n"(((c) * 4 + 1) & 15), [k2] "n"(((c) * 4 + 2) & 15), [k3] "n"(((c) * 4 + 3) & 15) \
+                 : "scc");                                                           \
+  }
+#define HB_PGS_CHUNKWU(c, pre) HB_PGS_CHUNKW(c, pre, HB_PGS_ROWSW_4, res, resV, nAinv, nforce, 0, 32)
+#define HB_PGS_CHUNKWV(c, rows) HB_PGS_CHUNKW(c, "", rows, resV, res, nAinvV, nforceV, 32, 0)
+#define HB_PGS_SWEEPW do {                                                           \
+    HB_PGS_CHUNKWU(0, "s_nop 0\n\t") HB_PGS_CHUNKWU(1, "") HB_PGS_CHUNKWU(2, "") HB_PGS_CHUNKWU(3, "") \
+    HB_PGS_CHUNKWV(4, HB_PGS_ROWSW_4) HB_PGS_CHUNKWV(5, HB_PGS_ROWSW_4) HB_PGS_CHUNKWV(6, HB_PGS_ROWSW_4) HB_PGS_CHUNKWV(7, HB_PGS_ROWSW_3) \
+  } while (0)
+      // the end of a paired sweep, the same behind every form of the row step: the steps join the forces, then each env's convergence test
+      // (all in row layout: rres is the residual of the lane's own row)
       auto paired_end = [&](float delta, float res0) {
         force += delta;
         float iLo, iHi;
-        env_sums(delta * (res0 + res), iLo, iHi);
+        env_sums(delta * (res0 + rres), iLo, iHi);
         niterLo++; niterHi++;
         if (-0.5f * iLo * pgs_scale < pgs_tol || niterLo >= max_sweeps) {
           liveLo = false;
-          if (!h) { force_out = force; res = 0.f; force = 0.f; }  // rows of a finished env are inert from here on
+          if (!h) { force_out = force; res = 0.f; resV = 0.f; rres = 0.f; force = 0.f; }  // rows of a finished env are inert from here on
         }
         if (-0.5f * iHi * pgs_scale < pgs_tol || niterHi >= max_sweeps) {
           liveHi = false;
-          if (h) { force_out = force; res = 0.f; force = 0.f; }
+          if (h) { force_out = force; res = 0.f; resV = 0.f; rres = 0.f; force = 0.f; }
         }
       };
       while (short16 && liveLo && liveHi) {
         int ne;
         asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(nmax2));
-        const float nforce = -force, res0 = res;
+        const float nforce = -force, res0 = rres;
         float dl = 0.f;
         unsigned long long turn = 0x0000000100000001ull;  // the lanes whose turn it is: row 0 of both envs
         HB_PGS_SWEEPB;
+        rres = res;
         paired_end(dl, res0);
       }
-      while (liveLo && liveHi) {
+      while (wide && liveLo && liveHi) {
         int ne;
-        {
-          const int a = max(nLo, nHi);
-          asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(a));
-        }
-        const float nforce = -force, res0 = res;
+        asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(nmax2));
+        const float res0 = rres;
+        float nforce, nforceV;
+        uv_copies(-force, nforce, nforceV);
         float dl = 0.f;
-        unsigned todo = (1u << min((ne + 3) & ~3, 31)) - 1u;  // the rows the chunks below run, in both halves
-        do {
-          HB_PGS_CHUNK2(0, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(1, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(2, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(3, HB_PGS_ROWS2_4)
-          HB_PGS_CHUNK2(4, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(5, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(6, HB_PGS_ROWS2_4) HB_PGS_CHUNK2(7, HB_PGS_ROWS2_3)
-        } while (0);
+        unsigned long long turn = 0x0000000100000001ull;
+        HB_PGS_SWEEPW;
+        rres = (lane & 16) ? resV : res;  // (the select at the end of a sweep is the next sweep's res0)
         paired_end(dl, res0);
       }
-#undef HB_PGS_CHUNK2
-#undef HB_PGS_ROWS2_3
-#undef HB_PGS_ROWS2_4
-#undef HB_PGS_ROW2
-#undef HB_PGS_MASK2
-      // ONE env still sweeps (the wave sweeps max(sA, sB) times, each env its own count): the one-env kernel's row step (5 VALU, the compiler's
-      // code, EXEC untouched) on that env's lanes, and the sum of the convergence test over that env's half alone.  The pending-lane form of
-      // the paired loop was measured here too (4 VALU, two EXEC writes per row): 5 % SLOWER per step - a scalar write of EXEC ahead of a
-      // vector instruction costs this loop more than the v_writelane it saves (profiles/pgs_sweeps_bench.txt).  The other half's lanes ride
-      // along: their res takes garbage, their step stays 0 and their forces are in force_out.
+      // ONE env still sweeps (the wave sweeps max(sA, sB) times, each env its own count).  The tail works in row layout: behind a wide paired
+      // loop every lane takes its own row's column, nAinv and residual back (33 selects, once).  With at most 16 rows in the env that sweeps
+      // on it is the broadcast row step with ONE bit in the mask; above 16 rows the one-env kernel's row step (5 VALU, the compiler's code,
+      // EXEC untouched) on that env's lanes.  The wide statement with one bit in the mask was measured there too: its median was not faster than
+      // this form's, alone or behind the wide paired loop (profiles/pgs_wide_bench.txt), as little as the pending-lane form before it (4 VALU, two
+      // EXEC writes per row: 5 % SLOWER per step, profiles/pgs_sweeps_bench.txt).  The sum of the convergence test runs over that env's half
+      // alone.  The other half's lanes ride along: their res takes garbage, their step stays 0 and their forces are in force_out.
+      if (wide && (liveLo || liveHi)) {
+        const bool vrow = (lane & 16) != 0;  // the lane's own row is a V row
+#pragma unroll
+        for (int k = 0; k < 31; k++) {
+          // (both read first: a select of values.  As a conditional lvalue it compiles to a select of ADDRESSES, an indexed access that
+          // sends all of ar to scratch: 256 B/lane)
+          const float u = ar[k], v = ar[32 + k];
+          ar[k] = vrow ? v : u;
+        }
+        nAinv = vrow ? nAinvV : nAinv;
+        res = rres;
+      }
 #define HB_PGS_ROW1(base, i)                                                         \
   if ((i) < 31) {                                                                    \
     const float d_ = fmaxf(res * nAinv, nforce);                                     \
@@ -1257,6 +1295,13 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       HB_PGS_TAIL(0, liveLo, nLo, niterLo, !h)
       HB_PGS_TAIL(32, liveHi, nHi, niterHi, h)
 #undef HB_PGS_TAIL
+#undef HB_PGS_SWEEPW
+#undef HB_PGS_CHUNKWV
+#undef HB_PGS_CHUNKWU
+#undef HB_PGS_CHUNKW
+#undef HB_PGS_ROWSW_3
+#undef HB_PGS_ROWSW_4
+#undef HB_PGS_ROWW
 #undef HB_PGS_SWEEPB
 #undef HB_PGS_CHUNKB
 #undef HB_PGS_ROWB
