@@ -1,5 +1,5 @@
 // hb_api_env.cpp — the C-ABI of libhb.so (include/hb.h), the env adapter: observations, rewards and resets, the realism layer and
-// domain randomisation, the policy MLP, and the sampling actor with its rollout collection.
+// domain randomisation, the policy MLP, the sampling actor with its rollout collection, and the critic with the PPO buffer over the tapes.
 #include "hb_batch.hpp"
 
 extern "C" {
@@ -559,6 +559,96 @@ int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out*
     if (rc != HB_OK) return rc;
     if (out->terminal_obs)
       HB_HIP(hipMemcpyAsync(out->terminal_obs + row * nobs, b->d_term_obs, n * nobs * sizeof(float), hipMemcpyDeviceToDevice, main_stream(b)));
+  }
+  return HB_OK;
+}
+
+// ---- critic and the PPO buffer over a collection's tapes
+
+int hb_critic_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases) {
+  if (!b || !sizes || !weights || !biases || n_layers < 1 || n_layers > 4) return HB_EINVAL;
+  if (sizes[0] != b->D.dm.nobs || sizes[n_layers] != 1) return HB_EINVAL;
+  for (int l = 0; l <= n_layers; l++) if (sizes[l] < 1) return HB_EINVAL;
+  for (int l = 0; l < n_layers; l++) if (!weights[l] || !biases[l]) return HB_EINVAL;
+  for (int l = 0; l <= n_layers; l++) if (sizes[l] > 256) return HB_EUNSUPPORTED;  // (the fused kernel's LDS tiles; no layer-by-layer fallback)
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a call still in flight reads the buffers that are replaced below)
+  // (every argument check is behind us: from here on only the device can fail, and then no critic is installed)
+  b->critic_layers = 0;
+  for (int l = 0; l < 4; l++) reset_all(b->d_critic_wp[l], b->d_critic_b[l]);
+  for (int l = 0; l < n_layers; l++) {
+    const std::vector<float> packed = pack_mfma_b(weights[l], sizes[l], sizes[l + 1]);
+    if (b->d_critic_wp[l].alloc(packed.size()) != HB_OK || b->d_critic_b[l].alloc(sizes[l + 1]) != HB_OK) return HB_ENOMEM;
+    HB_HIP(hipMemcpy(b->d_critic_wp[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+    HB_HIP(hipMemcpy(b->d_critic_b[l], biases[l], sizes[l + 1] * sizeof(float), hipMemcpyHostToDevice));
+  }
+  b->critic_layers = n_layers;
+  for (int l = 0; l <= n_layers; l++) b->critic_sizes[l] = sizes[l];
+  return HB_OK;
+}
+
+int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb_gae_config* cfg, const hb_gae_out* out) {
+  if (!b || !tapes || !cfg || !out || T < 1) return HB_EINVAL;
+  if (!out->value && !out->terminal_value && !out->log_prob && !out->advantage && !out->returns) return HB_EINVAL;
+  if (!std::isfinite(cfg->gamma) || !std::isfinite(cfg->lam) || cfg->gamma < 0.f || cfg->gamma > 1.f || cfg->lam < 0.f || cfg->lam > 1.f) return HB_EINVAL;
+  const bool boot = cfg->bootstrap_truncated != 0, scan = out->advantage || out->returns;
+  const bool want_value = out->value || scan, want_tv = out->terminal_value || (scan && boot);
+  if ((want_value || want_tv) && b->critic_layers < 1) return HB_EINVAL;
+  if (want_value && !tapes->obs) return HB_EINVAL;
+  if (scan && (!tapes->reward || !tapes->terminated || !tapes->truncated)) return HB_EINVAL;
+  if (want_tv && (!tapes->terminal_obs || !tapes->terminated || !tapes->truncated)) return HB_EINVAL;
+  const int head = b->actor_cfg.head;
+  if (out->log_prob) {
+    if (b->actor_layers < 1 || head == HB_ACTOR_DETERMINISTIC || !tapes->eps) return HB_EINVAL;
+    if (head == HB_ACTOR_SQUASHED && (!tapes->mean || !tapes->log_std)) return HB_EINVAL;
+  }
+  HB_HIP(hipSetDevice(b->device));
+  const size_t n = b->n_env;
+  const long long rows = (long long)T * b->n_env;
+  // value and terminal-value tapes the caller did not ask for but the scan needs: the batch's scratch
+  float* value = out->value;
+  float* tv = out->terminal_value;
+  const size_t need = (want_value && !value ? (size_t)(T + 1) * n : 0) + (want_tv && !tv ? (size_t)T * n : 0);
+  if (need) {
+    if (need > b->d_gae.capacity()) HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a call still in flight writes the buffer that is replaced)
+    const int rc = b->d_gae.reserve(need);
+    if (rc != HB_OK) return rc;
+    float* p = b->d_gae;
+    if (want_value && !value) { value = p; p += (size_t)(T + 1) * n; }
+    if (want_tv && !tv) tv = p;
+  }
+  hipStream_t st = main_stream(b);
+  PolicyDesc pd;
+  memset(&pd, 0, sizeof pd);
+  if (want_value || want_tv) {
+    pd.nl = b->critic_layers;
+    int widest = 1;
+    for (int l = 0; l <= b->critic_layers; l++) { pd.sizes[l] = b->critic_sizes[l]; widest = std::max(widest, b->critic_sizes[l]); }
+    for (int l = 0; l < b->critic_layers; l++) { pd.w[l] = b->d_critic_wp[l]; pd.b[l] = b->d_critic_b[l]; }
+    pd.ldx = widest + 4;  // + the K pad columns (K is swept four at a time); 16-row tiles
+  }
+  if (want_value) HB_HIP(launch_value(pd, tapes->obs, nullptr, nullptr, rows + b->n_env, value, st));
+  if (want_tv) {
+    if (boot) HB_HIP(launch_value(pd, tapes->terminal_obs, tapes->terminated, tapes->truncated, rows, tv, st));
+    else HB_HIP(hipMemsetAsync(tv, 0, (size_t)rows * sizeof(float), st));  // (only as an output: the scan does not read it then)
+  }
+  if (scan) {
+    GaeScan g;
+    memset(&g, 0, sizeof g);
+    g.reward = tapes->reward; g.value = value; g.term_value = boot ? tv : nullptr;
+    g.terminated = tapes->terminated; g.truncated = tapes->truncated;
+    g.advantage = out->advantage; g.returns = out->returns;
+    g.gamma = cfg->gamma; g.gl = (float)((double)cfg->gamma * (double)cfg->lam);
+    g.T = T; g.n_env = b->n_env;
+    HB_HIP(launch_gae_scan(g, st));
+  }
+  if (out->log_prob) {
+    LogProbDesc d;
+    memset(&d, 0, sizeof d);
+    d.head = head; d.nu = b->D.dm.nu;
+    memcpy(d.log_std, b->actor_cfg.log_std, sizeof d.log_std);
+    d.eps = tapes->eps; d.mean = tapes->mean; d.ls = tapes->log_std; d.out = out->log_prob;
+    HB_HIP(launch_log_prob(d, rows, st));
   }
   return HB_OK;
 }

@@ -206,6 +206,12 @@ struct hb_batch {
   DevBuf<float> d_actor_wp[4], d_actor_b[4];
   hb_actor_config actor_cfg = {};
   unsigned actor_draw0 = 0;
+  // critic (hb_critic_set_mlp, hb_collect_gae_dev): packed weights and biases of hb_value_kernel, and the scratch the value and terminal-value
+  // tapes go to when the caller gives none, [2 T + 1][n_env], grown on demand
+  int critic_layers = 0;  // 0: none installed
+  int critic_sizes[5] = {0, 0, 0, 0, 0};
+  DevBuf<float> d_critic_wp[4], d_critic_b[4];
+  DevBuf<float> d_gae;
   // optional per-kernel timing of the step kernel (hb_step_timing)
   bool time_steps = false;
   std::vector<hipEvent_t> tev;  // pairs

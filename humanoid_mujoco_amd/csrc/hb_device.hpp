@@ -260,6 +260,23 @@ struct ActorTapes {
   float *action, *mean, *log_std, *eps;
 };
 
+// hb_collect_gae_dev (hb_gae.hip): the scan's tapes, each [T][n_env] (value: [T + 1][n_env]); term_value null: no bootstrap of truncated
+// envs; gl = gamma lam rounded to fp32 once; advantage or returns may be null
+struct GaeScan {
+  const float *reward, *value, *term_value;
+  const uint8_t *terminated, *truncated;
+  float *advantage, *returns;
+  float gamma, gl;
+  int T, n_env;
+};
+// the log-probability pass: the actor's head (kActorGaussian: log_std[]; kActorSquashed: the mean and log_std tapes), tapes [rows][nu], out [rows]
+struct LogProbDesc {
+  int head, nu;
+  float log_std[kActorMaxNu];
+  const float *eps, *mean, *ls;
+  float* out;
+};
+
 // Buffers of the STAGED step of the general variants (launch_step): hb_pose_kernel writes every geom's world pose and the env's
 // narrowphase work items, hb_narrow_kernel evaluates the items (one per lane, at the occupancy of a small kernel: the MPR climbs are
 // chains of dependent loads), the step kernel appends the results in item order.  All null: the step kernel does all of it itself.

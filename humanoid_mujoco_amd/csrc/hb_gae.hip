@@ -1,0 +1,187 @@
+// hb_gae.hip - the PPO buffer of hb_collect_gae_dev over the tapes of a collection: the critic over rows of observations (hb_value_kernel),
+// the GAE(gamma, lambda) scan (hb_gae_scan_kernel) and the log-probabilities of the recorded draws (hb_log_prob_kernel).  A translation
+// unit of its own: no other kernel compiles differently for it.
+#include <hip/hip_runtime.h>
+#include "hb_kcommon.hpp"
+#include "hb_launch.hpp"
+
+namespace hb {
+
+// hb_actor_kernel's design (hb_actor.hip) on a row array [n_rows][nobs]: 16 rows per block, activations ping-pong between two LDS tiles,
+// eight waves share the 16-column output tiles of a layer, each sweeping K four columns per v_mfma_f32_16x16x4_f32 (exact f32), B operand
+// from the packed weights; a layer with fewer than eight tiles splits K across the idle waves and the partial tiles are summed in a fixed
+// order.  The layer loop is a COPY of hb_actor_kernel's, statement for statement (the same operations in the same order): moved into a
+// shared __device__ function, the actor compiled to 53 VGPRs instead of 50 (profiles/gae_kernel_resources.txt), so the actor keeps its own.
+// What differs from the actor:
+//  - term / trunc null: every row is evaluated (the obs tape).  Both given: row i is evaluated where trunc[i] && !term[i] - the rows
+//    that are bootstrapped - and every other row is NOT READ (it holds stale or arbitrary data), loads as zeros and gets out[i] = 0; a
+//    block with no selected row writes its zeros and returns;
+//  - the last layer has one output column: one tile, split-K across the eight waves; out[i] is its pre-activation (the critic is linear
+//    at the top).
+// A row's value does not depend on the other rows of its tile nor on where in the tile it stands (every D[i][j] of an MFMA is its own
+// chain over k), so V is the same bits however the rows are cut into batches.
+typedef float f32x4g __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(512) void hb_value_kernel(const PolicyDesc pd, const float* rows, const uint8_t* term, const uint8_t* trunc, long long n_rows, float* out) {
+  extern __shared__ __attribute__((aligned(16))) float sm_value[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long m0 = (long long)blockIdx.x * 16;
+  const int ldx = pd.ldx;
+  const int live = (int)min(16LL, n_rows - m0);  // rows of this block that exist
+  // bit r: row m0 + r is evaluated (every wave forms the same word)
+  unsigned sel = (1u << live) - 1u;
+  if (term) sel = (unsigned)__ballot(lane < live && trunc[m0 + min(lane, live - 1)] && !term[m0 + min(lane, live - 1)]) & 0xffffu;
+  if (!sel) {
+    if (tid < live) out[m0 + tid] = 0.f;
+    return;
+  }
+  float* cur = sm_value;
+  float* nxt = sm_value + 16 * ldx;
+  float* part = sm_value + 32 * ldx;  // [8][16][16] partial tiles
+  {
+    const int nobs = pd.sizes[0];
+    const float* src = rows + (size_t)m0 * nobs;
+    for (int idx = tid; idx < 16 * nobs; idx += 512) {
+      const int row = idx / nobs, c = idx - row * nobs;
+      cur[row * ldx + c] = (sel >> row & 1u) ? src[idx] : 0.f;
+    }
+    if (tid < 48) cur[(tid / 3) * ldx + nobs + tid % 3] = 0.f;
+  }
+  __syncthreads();
+  const int col = lane & 15, quad = lane >> 4;  // A: row = col, k offset = quad;  B: k offset = quad, column = col;  D: rows 4 quad + r, column col
+  for (int l = 0; l < pd.nl; l++) {
+    const int K = pd.sizes[l], N = pd.sizes[l + 1], KK = (K + 3) / 4, ntile = (N + 15) / 16;
+    const bool last = l + 1 == pd.nl;
+    int S = 1;  // K slices per tile
+    while (S * 2 * ntile <= 8) S *= 2;
+    const float* wp = pd.w[l];
+    const float* bias = pd.b[l];
+    if (!last && tid < 48) nxt[(tid / 3) * ldx + N + tid % 3] = 0.f;  // pad columns of the next layer's input
+    for (int it = wave; it < ntile * S; it += 8) {
+      const int nt = it / S, sl = it - nt * S;
+      const int kb = KK * sl / S, ke = KK * (sl + 1) / S;
+      f32x4g D = {0.f, 0.f, 0.f, 0.f};
+      const float* ap = cur + col * ldx + quad;
+      const float* bp = wp + (size_t)nt * KK * 64 + lane;
+      int kk = kb;
+      for (; kk + 8 <= ke; kk += 8) {  // eight operand pairs in flight per batch of MFMAs
+        float a[8], w[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) { a[u] = ap[4 * (kk + u)]; w[u] = bp[(size_t)(kk + u) * 64]; }
+#pragma unroll
+        for (int u = 0; u < 8; u++) D = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u], D, 0, 0, 0);
+      }
+      for (; kk < ke; kk++) D = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[4 * kk], bp[(size_t)kk * 64], D, 0, 0, 0);
+      const int n = nt * 16 + col;
+      if (S == 1) {
+        if (n < N) {
+          const float bn = bias[n];
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const float v = D[r] + bn;
+            nxt[(4 * quad + r) * ldx + n] = last ? v : tanhf(v);
+          }
+        }
+      } else {
+        float* pp = part + it * 256;
+#pragma unroll
+        for (int r = 0; r < 4; r++) pp[(4 * quad + r) * 16 + col] = D[r];
+      }
+    }
+    __syncthreads();
+    if (S > 1) {
+      for (int idx = tid; idx < ntile * 256; idx += 512) {
+        const int nt = idx >> 8, rc = idx & 255, row = rc >> 4, n = nt * 16 + (rc & 15);
+        if (n < N) {
+          float v = bias[n];
+          for (int sl = 0; sl < S; sl++) v += part[(nt * S + sl) * 256 + rc];
+          nxt[row * ldx + n] = last ? v : tanhf(v);
+        }
+      }
+      __syncthreads();
+    }
+    float* t = cur; cur = nxt; nxt = t;
+  }
+  // cur holds the last layer's output, column 0 of every row
+  if (tid < live) out[m0 + tid] = (sel >> tid & 1u) ? cur[tid * ldx] : 0.f;
+}
+
+hipError_t launch_value(const PolicyDesc& pd, const float* rows, const uint8_t* term, const uint8_t* trunc, long long n_rows, float* out, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (n_rows < 1 || !rows || !out || (term == nullptr) != (trunc == nullptr) || pd.nl < 1 || pd.sizes[pd.nl] != 1) return hipErrorInvalidValue;
+  const size_t shmem = ((size_t)32 * pd.ldx + 8 * 256) * sizeof(float);  // two activation tiles + the split-K partial tiles
+  const long long nblk = (n_rows + 15) / 16;
+  if (shmem > 64 * 1024 || nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hb_value_kernel, dim3((unsigned)nblk), dim3(512), shmem, stream, pd, rows, term, trunc, n_rows, out);
+  return hipGetLastError();
+}
+
+// One lane per env, t = T-1 .. 0; every tape is [t][n_env], so the lanes of a wave read consecutive floats.  No cross-lane operation: env
+// e's results are the same bits whatever n_env is and wherever e stands.  The arithmetic, with its fp32 roundings (tests/test_gpu_gae.py
+// derives its bound from this count): r' = fma(gamma, tv, reward) [1]; q = fma(gamma nt, V[t+1], r') [1]; delta = q - V[t] [1];
+// A = fma(gl nt, A, delta) [1], gl = gamma lam rounded once on the host [1]; returns = A + V[t] [1, not fed back].  nt is applied as a
+// select (the coefficient is gamma or 0, gl or 0), not as a product; terminal values are read only where the env is bootstrapped.
+__global__ __launch_bounds__(64) void hb_gae_scan_kernel(const GaeScan g) {
+  const int e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= g.n_env) return;
+  const size_t n = (size_t)g.n_env;
+  float adv = 0.f;
+  float vnext = g.value[(size_t)g.T * n + e];
+  for (int t = g.T - 1; t >= 0; t--) {
+    const size_t o = (size_t)t * n + e;
+    const bool te = g.terminated[o] != 0, tr = g.truncated[o] != 0;
+    const bool done = te || tr;
+    const float v = g.value[o];
+    float rp = g.reward[o];
+    if (g.term_value && tr && !te) rp = __fmaf_rn(g.gamma, g.term_value[o], rp);
+    const float q = __fmaf_rn(done ? 0.f : g.gamma, vnext, rp);
+    const float delta = __fsub_rn(q, v);
+    adv = __fmaf_rn(done ? 0.f : g.gl, adv, delta);
+    if (g.advantage) g.advantage[o] = adv;
+    if (g.returns) g.returns[o] = __fadd_rn(adv, v);
+    vnext = v;
+  }
+}
+
+hipError_t launch_gae_scan(const GaeScan& g, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (g.n_env < 1 || g.T < 1 || !g.reward || !g.value || !g.terminated || !g.truncated || (!g.advantage && !g.returns)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hb_gae_scan_kernel, dim3((g.n_env + 63) / 64), dim3(64), 0, stream, g);
+  return hipGetLastError();
+}
+
+// One lane per tape row (t, e): the sum over the actuators in index order, no cross-lane operation.  Per actuator (roundings in
+// brackets): term = fma(-eps / 2, eps, -ls) [1] - log(2 pi) / 2 [1, the constant 1]; head 2: x = fma(exp(ls), eps, mean) [expf, 1],
+// a = |x|, corr = 2 ((log 2 - a) [1, the constant 1] - log1p(exp(-2 a)) [expf, log1pf, 1]), term -= corr [1]; sum += term [1].
+// log 2 - |x| - log1p(exp(-2 |x|)) is log 2 - x - softplus(-2 x) (even in x) without the overflow of exp(-2 x) at large negative x.
+__global__ __launch_bounds__(256) void hb_log_prob_kernel(const LogProbDesc d, long long n_rows) {
+  const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n_rows) return;
+  const size_t o = (size_t)row * d.nu;
+  const float half_log_2pi = 0.91893853320467274178f, log2f_ = 0.69314718055994530942f;
+  float sum = 0.f;
+  for (int i = 0; i < d.nu; i++) {
+    const float eps = d.eps[o + i];
+    const float ls = d.head == kActorSquashed ? d.ls[o + i] : d.log_std[i];
+    float term = __fsub_rn(__fmaf_rn(-0.5f * eps, eps, -ls), half_log_2pi);
+    if (d.head == kActorSquashed) {
+      const float a = fabsf(__fmaf_rn(expf(ls), eps, d.mean[o + i]));
+      const float corr = 2.f * __fsub_rn(__fsub_rn(log2f_, a), log1pf(expf(-2.f * a)));
+      term = __fsub_rn(term, corr);
+    }
+    sum = __fadd_rn(sum, term);
+  }
+  d.out[row] = sum;
+}
+
+hipError_t launch_log_prob(const LogProbDesc& d, long long n_rows, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (n_rows < 1 || d.nu < 1 || d.nu > kActorMaxNu || !d.eps || !d.out || (d.head != kActorGaussian && d.head != kActorSquashed) ||
+      (d.head == kActorSquashed && (!d.mean || !d.ls)))
+    return hipErrorInvalidValue;
+  const long long nblk = (n_rows + 255) / 256;
+  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hb_log_prob_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, d, n_rows);
+  return hipGetLastError();
+}
+
+}  // namespace hb

@@ -61,6 +61,11 @@ hipError_t launch_policy(const DevModel& M, const PolicyDesc& pd, const float* s
 hipError_t launch_policy_lean(const DevModel& M, const PolicyDesc& pd, const float* state, float* ctrl, float* act, int n_env, hipStream_t stream);
 // the sampling actor on obs [n_env][nobs] (hb_actor.hip; hb_env_collect_dev): env_global0 is the global index of row 0, draw the step counter of the draws
 hipError_t launch_actor(const ActorDesc& ad, const float* obs, const ActorTapes& tp, int n_env, unsigned env_global0, unsigned draw, hipStream_t stream);
+// the critic over rows [n_rows][nobs] (hb_gae.hip; hb_collect_gae_dev): out[i] = V(rows[i]); term / trunc given: only where trunc[i] && !term[i], the
+// other rows are not read and get 0
+hipError_t launch_value(const PolicyDesc& pd, const float* rows, const uint8_t* term, const uint8_t* trunc, long long n_rows, float* out, hipStream_t stream);
+hipError_t launch_gae_scan(const GaeScan& g, hipStream_t stream);
+hipError_t launch_log_prob(const LogProbDesc& d, long long n_rows, hipStream_t stream);
 // order: [2 * n_env] ints - the permutation, then the sort keys of the pass (read once from counts)
 hipError_t launch_order(const int* counts, int* order, int n_env, int e0, int n, hipStream_t stream, int slot = 3, int shift = 3);
 hipError_t launch_mlp_layer(const float* X, const float* W, const float* bias, float* Y, int Mrows, int K, int N, int act, hipStream_t stream);

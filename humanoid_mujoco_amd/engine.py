@@ -149,6 +149,16 @@ class HbCollectOut(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("obs", "action", "mean", "log_std", "eps", "reward", "terminated", "truncated", "terminal_obs")]
 
 
+class HbGaeConfig(ctypes.Structure):
+    """hb_gae_config (include/hb.h): discount, GAE lambda, and whether envs cut by truncation alone are bootstrapped."""
+    _fields_ = [("gamma", ctypes.c_float), ("lam", ctypes.c_float), ("bootstrap_truncated", ctypes.c_int)]
+
+
+class HbGaeOut(ctypes.Structure):
+    """hb_gae_out (include/hb.h): device pointers of what hb_collect_gae_dev writes, each nullable."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("value", "terminal_value", "log_prob", "advantage", "returns")]
+
+
 class HbError(RuntimeError):
     pass
 
@@ -259,6 +269,8 @@ def lib():
     L.hb_rollout_policy.argtypes = [vp, ci, vp]
     L.hb_actor_set_mlp.argtypes = [vp, ci, vp, vp, vp, ctypes.POINTER(HbActorConfig)]
     L.hb_env_collect_dev.argtypes = [vp, ci, ci, ctypes.POINTER(HbCollectOut)]
+    L.hb_critic_set_mlp.argtypes = [vp, ci, vp, vp, vp]
+    L.hb_collect_gae_dev.argtypes = [vp, ci, ctypes.POINTER(HbCollectOut), ctypes.POINTER(HbGaeConfig), ctypes.POINTER(HbGaeOut)]
     L.hb_dev_alloc.restype = vp; L.hb_dev_alloc.argtypes = [vp, ctypes.c_uint64]
     L.hb_dev_free.restype = None; L.hb_dev_free.argtypes = [vp, vp]
     L.hb_host_alloc.restype = vp; L.hb_host_alloc.argtypes = [ctypes.c_uint64]
@@ -1169,6 +1181,36 @@ class Batch:
         rc = lib().hb_env_collect_dev(self._h, int(T), int(n_substeps), ctypes.byref(out))
         _check(rc, "hb_env_collect_dev", "needs T >= 1, n_substeps >= 1, obs and action tapes, an installed actor (actor_set), and a log_std "
                "tape only with the squashed head" if rc == -1 else None)
+
+    # ---- critic and the PPO buffer over a collection's tapes (include/hb.h: hb_critic_set_mlp, hb_collect_gae_dev)
+    def critic_set(self, sizes, weights, biases):
+        """Installs the critic.  sizes: [nobs, hidden..., 1]; weights[l]: [sizes[l], sizes[l+1]] float32 - the TRANSPOSE of
+        torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; tanh after every hidden layer, the last layer linear.  At most four layers of
+        width <= 256.  Independent of the actor and of the policy MLP."""
+        sizes = [int(s) for s in sizes]
+        ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
+        bs = [np.ascontiguousarray(x, dtype=np.float32) for x in biases]
+        if len(ws) != len(sizes) - 1 or len(bs) != len(ws) or any(w.shape != (a, c) for w, a, c in zip(ws, sizes[:-1], sizes[1:])) or \
+                any(x.shape != (c,) for x, c in zip(bs, sizes[1:])):
+            raise ValueError("critic_set: weights[l] must be [sizes[l], sizes[l+1]] and biases[l] [sizes[l+1]]")
+        csz = (ctypes.c_int * len(sizes))(*sizes)
+        wp = (ctypes.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+        bp = (ctypes.c_void_p * len(bs))(*[x.ctypes.data for x in bs])
+        rc = lib().hb_critic_set_mlp(self._h, len(ws), csz, wp, bp)
+        _check(rc, "hb_critic_set_mlp", "a layer wider than 256: the critic is one fused kernel, there is no layer-by-layer path" if rc == -4 else
+               "sizes must run from nobs to 1 over 1..4 layers" if rc == -1 else None)
+
+    def collect_gae_dev(self, T, gamma, lam, bootstrap_truncated=True, *, obs=None, action=None, mean=None, log_std=None, eps=None, reward=None,
+                        terminated=None, truncated=None, terminal_obs=None, value=None, terminal_value=None, log_prob=None, advantage=None, returns=None):
+        """hb_collect_gae_dev: critic values, log-probabilities and GAE(gamma, lam) advantages / returns over the T-step tapes of a collection,
+        enqueued on the batch's stream.  Device pointers (ints, e.g. torch tensors' data_ptr()): the tapes as env_collect_dev takes them, and
+        the outputs value [T + 1, n_env], terminal_value, log_prob, advantage, returns [T, n_env], each optional (at least one)."""
+        tapes = HbCollectOut(obs, action, mean, log_std, eps, reward, terminated, truncated, terminal_obs)
+        cfg = HbGaeConfig(float(gamma), float(lam), int(bool(bootstrap_truncated)))
+        out = HbGaeOut(value, terminal_value, log_prob, advantage, returns)
+        rc = lib().hb_collect_gae_dev(self._h, int(T), ctypes.byref(tapes), ctypes.byref(cfg), ctypes.byref(out))
+        _check(rc, "hb_collect_gae_dev", "needs T >= 1, gamma and lam in [0, 1], at least one output, the tapes each output reads, a critic "
+               "(critic_set) for the value outputs and a sampling actor (actor_set, not the deterministic head) for log_prob" if rc == -1 else None)
 
     # ---- device buffers / timing helpers (no HIP headers or torch needed on the caller's side)
     def dev_alloc(self, nbytes):

@@ -344,7 +344,12 @@ class VecEnv:
         draws are a random stream of their own, independent of the realism layer's."""
         self.batch.actor_set(sizes, weights, biases, head=head, log_std=log_std, seed=self.seed_value if seed is None else seed, deterministic=deterministic)
 
-    def collect_torch(self, T, obs0=None, terminal_obs=False):
+    def critic_set(self, sizes, weights, biases):
+        """Installs the critic collect() / collect_torch() evaluate with gae=... (Batch.critic_set: sizes [nobs, hidden..., 1], weights[l] is
+        [in, out], the transpose of torch.nn.Linear.weight; tanh hidden layers, linear output)."""
+        self.batch.critic_set(sizes, weights, biases)
+
+    def collect_torch(self, T, obs0=None, terminal_obs=False, gae=None):
         """T steps of the installed actor in the env loop on the device (hb_env_collect_dev): no host transfer, no host synchronisation,
         one Python call.  Returns a dict of CUDA tensors: "obs" [T + 1, n, nobs] (row 0 is obs0; row t + 1 the observation after step t,
         for an env that finished there the first of its new episode), "action", "mean", "eps" [T, n, nu] (and "log_std" with the squashed
@@ -352,9 +357,20 @@ class VecEnv:
         row (t, e) is the observation of the state env e's episode ended in where terminated | truncated is set at (t, e) and an older
         value elsewhere.  obs0: the observation the envs last returned, [n, nobs] as a CUDA tensor or array; default: what this VecEnv
         last returned from reset / step* / collect* (uploaded here if it lives on the host).  The tensors are rewritten by the next
-        collection of the same T.  Streams are ordered as in step_torch."""
+        collection of the same T.  Streams are ordered as in step_torch.
+        gae=dict(gamma=..., lam=..., bootstrap_truncated=True): the PPO buffer behind the collection on the same stream (hb_collect_gae_dev,
+        needs critic_set): adds "value" [T + 1, n], "advantage" and "returns" [T, n], and with the gaussian and squashed heads "log_prob"
+        [T, n]; with bootstrap_truncated (the default) the terminal_obs tape is recorded whether asked for or not, and V of it is folded
+        into the reward of envs cut by truncation alone, as stable-baselines3's collect_rollouts does.  gae=None: exactly the call above."""
         import torch
         T = int(T)
+        if gae is not None:
+            gae = dict(gae)
+            g_gamma, g_lam, g_boot = float(gae.pop("gamma")), float(gae.pop("lam")), bool(gae.pop("bootstrap_truncated", True))
+            if gae:
+                raise TypeError("collect: unknown gae option(s) %s" % sorted(gae))
+            gae = True
+            terminal_obs = terminal_obs or g_boot
         n, nobs, nu = self.num_envs, self.model.nobs, self.model.nu
         dev = torch.device("cuda", self._device)
         squashed = getattr(self.batch, "actor_head", None) == 2
@@ -383,15 +399,24 @@ class VecEnv:
         t["obs"][0].copy_(src)  # on the caller's stream, behind whatever produced src (a host array: uploaded here)
         stream.wait_stream(cur)   # obs[0] is complete, and whoever still reads the previous tapes is done, before they are rewritten
         self.batch.env_collect_dev(T, self.n_substeps, **{k: v.data_ptr() for k, v in t.items()})
+        out = dict(t)
+        if gae:
+            gkey = ("gae", T)
+            if gkey not in cache:
+                cache[gkey] = {k: torch.empty((T + 1 if k == "value" else T, n), dtype=torch.float32, device=dev) for k in ("value", "log_prob", "advantage", "returns")}
+            g = dict(cache[gkey])
+            if getattr(self.batch, "actor_head", None) not in (1, 2):
+                del g["log_prob"]  # (the deterministic head has no density)
+            self.batch.collect_gae_dev(T, g_gamma, g_lam, g_boot, **{k: v.data_ptr() for k, v in t.items()}, **{k: v.data_ptr() for k, v in g.items()})
+            out.update(g)
         cur.wait_stream(stream)   # and the caller's stream sees the results
         self._last_obs = t["obs"][T]
-        out = dict(t)
         out["terminated"], out["truncated"] = t["terminated"].view(torch.bool), t["truncated"].view(torch.bool)
         return out
 
-    def collect(self, T, obs0=None, terminal_obs=False):
+    def collect(self, T, obs0=None, terminal_obs=False, gae=None):
         """collect_torch with numpy arrays: the same dict, copied to the host (one synchronisation at the end)."""
-        return {k: v.cpu().numpy() for k, v in self.collect_torch(T, obs0=obs0, terminal_obs=terminal_obs).items()}
+        return {k: v.cpu().numpy() for k, v in self.collect_torch(T, obs0=obs0, terminal_obs=terminal_obs, gae=gae).items()}
 
     def close(self):
         self.batch.close()

@@ -854,6 +854,62 @@ typedef struct hb_collect_out {   /* device pointers; every field but obs and ac
  * HB_EINVAL: NULL b or out, T < 1, n_substeps < 1, NULL obs or action, no actor installed, a log_std tape with a head other than 2. */
 int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out* out);
 
+/* ---- PPO buffer over the tapes of a collection: critic values, log-probabilities, GAE(gamma, lambda) advantages and returns ---- */
+
+/* Installs the critic of hb_collect_gae_dev: an MLP obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] == 1 with tanh after every hidden layer
+ * and a linear last layer.  The weight conventions are hb_actor_set_mlp's: weights[l] is row-major [sizes[l]][sizes[l+1]] float32 (the
+ * transpose of torch.nn.Linear.weight), biases[l] is [sizes[l+1]]; host pointers, copied to the device and packed.  The critic is
+ * independent of the actor and of the MLP of hb_policy_set_mlp: any of them may be installed or replaced without touching the others.
+ * Refusals: HB_EINVAL - NULL argument, n_layers outside 1..4, a size < 1, sizes[0] != nobs, sizes[n_layers] != 1; HB_EUNSUPPORTED - a
+ * width above 256 (the critic is the actor's fused kernel design: activation tiles in LDS, no layer-by-layer fallback).  A refused call
+ * leaves the installed critic as it was. */
+int hb_critic_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases);
+
+typedef struct hb_gae_config {
+  float gamma, lam;          /* discount and GAE lambda, each in [0, 1] */
+  int bootstrap_truncated;   /* 1: an env cut by truncation alone gets gamma V(terminal_obs) added to its reward (VecEnv's TimeLimit.truncated) */
+} hb_gae_config;
+typedef struct hb_gae_out {  /* device pointers, each nullable, not all NULL */
+  float* value;           /* [T + 1][n_env]  V(obs[t]) */
+  float* terminal_value;  /* [T][n_env]      V(terminal_obs[t][e]) where the env is bootstrapped at (t, e), 0 elsewhere */
+  float* log_prob;        /* [T][n_env] */
+  float* advantage;       /* [T][n_env] */
+  float* returns;         /* [T][n_env]      advantage + value[t] */
+} hb_gae_out;
+
+/* What a PPO update needs from the T-step tapes of hb_env_collect_dev (`tapes`: the struct that collection was given, or any tapes of
+ * the same shapes), computed on the device in at most four launches on the batch's stream: no host synchronisation, no host transfer,
+ * no allocation beyond a scratch the batch owns and grows on demand.  A pure function of the tapes, the installed critic and the
+ * installed actor's head (cfg.head, and for HB_ACTOR_GAUSSIAN its log_std[]): nothing of the batch is written - state, draw counter,
+ * status words, counts, hb_last_kernel and hb_batch_step_launches stay as they are (held hb_step_dev calls are launched first and the
+ * pipes joined, as for every other call).  With done = terminated | truncated, boot = bootstrap_truncated && truncated && !terminated:
+ *   value[t][e]          = V(obs[t][e])                                   t = 0..T
+ *   terminal_value[t][e] = boot ? V(terminal_obs[t][e]) : 0
+ *   r'                   = reward[t][e] + gamma * terminal_value[t][e]
+ *   nt                   = done ? 0 : 1
+ *   delta                = r' + gamma * nt * value[t+1][e] - value[t][e]
+ *   advantage[t][e]      = delta + gamma * lam * nt * advantage[t+1][e],      advantage[T] = 0
+ *   returns[t][e]        = advantage[t][e] + value[t][e]
+ * - stable-baselines3's on-policy semantics (collect_rollouts' bootstrap of truncated envs, RolloutBuffer.compute_returns_and_advantage).
+ * obs[t+1] of an env that finished at t is the first observation of its NEW episode (the auto-reset): value[t+1] is masked by nt there.
+ * What terminated and truncated mean depends on hb_env_config.reward_kind; where both are set the env is not bootstrapped.
+ * terminal_obs rows where boot is not set are NOT READ (they hold older values or whatever the caller left there).
+ * log_prob[t][e], with ls_i the actor's log_std[i] (head 1) or the log_std tape (head 2):
+ *   head 1: sum_i (-eps_i^2 / 2 - ls_i - log(2 pi) / 2)          - the normal log-density of action, (action - mean) / sigma being eps;
+ *   head 2: the same sum minus sum_i 2 (log 2 - x_i - softplus(-2 x_i)), x_i = mean_i + exp(ls_i) eps_i - the change of variables of
+ *           tanh, log(1 - tanh(x)^2), written so that it does not cancel near |action| = 1.  SB3 writes log(1 - a^2 + 1e-6) on the
+ *           squashed action instead: the two differ only where 1 - a^2 is of the order of 1e-6 (|x| above about 7);
+ *   head 0 has no density: a non-NULL log_prob is refused.
+ * Each env's column is computed by one lane from that env's rows alone, and a row's value does not depend on its neighbours: env e's
+ * results are the same bits whatever n_env is and wherever e stands in the batch.
+ * Tapes read per output (others may be NULL): value - obs; advantage, returns - obs, reward, terminated, truncated, and terminal_obs
+ * when bootstrap_truncated; terminal_value - terminal_obs, terminated, truncated (all zeros without bootstrap_truncated); log_prob -
+ * eps, and mean and log_std for head 2.
+ * HB_EINVAL: NULL b, tapes, cfg or out; T < 1; all outputs NULL; gamma or lam not finite or outside [0, 1]; a tape missing for a
+ * requested output; value, terminal_value, advantage or returns without a critic; log_prob without an actor or with head 0.  A refused
+ * call writes nothing. */
+int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb_gae_config* cfg, const hb_gae_out* out);
+
 /* ---- host-side helpers so a C/C++/ctypes caller needs no HIP headers ---------------------------- */
 
 /* Device buffer on the batch's GPU (hipMalloc / hipFree). */
