@@ -1,5 +1,6 @@
 // hb_api_env.cpp — the C-ABI of libhb.so (include/hb.h), the env adapter: observations, rewards and resets, the realism layer and
-// domain randomisation, the policy MLP, the sampling actor with its rollout collection, and the critic with the PPO buffer over the tapes.
+// domain randomisation, the policy MLP, the sampling actor with its rollout collection, the critic with the PPO buffer over the tapes, and
+// the running observation / reward normaliser with its episode statistics.
 #include "hb_batch.hpp"
 
 extern "C" {
@@ -526,9 +527,13 @@ int hb_actor_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* c
   return HB_OK;
 }
 
-int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out* out) {
+static int norm_step_impl(hb_batch* b, const hb_norm_io& io);
+
+// the loop of hb_env_collect_dev; norm: one normaliser step behind every env step (hb_env_collect_norm_dev), aux: its tapes or null
+static int collect_impl(hb_batch* b, int T, int n_substeps, const hb_collect_out* out, bool norm, const hb_norm_tapes* aux) {
   if (!b || T < 1 || n_substeps < 1 || !out || !out->obs || !out->action || b->actor_layers < 1) return HB_EINVAL;
   if (out->log_std && b->actor_cfg.head != HB_ACTOR_SQUASHED) return HB_EINVAL;
+  if (norm && !b->norm_on) return HB_EINVAL;
   int rc = env_alloc(b);
   if (rc != HB_OK) return rc;
   HB_HIP(hipSetDevice(b->device));
@@ -553,15 +558,32 @@ int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out*
     tp.eps = out->eps ? out->eps + row * nu : nullptr;
     HB_HIP(launch_actor(ad, out->obs + row * nobs, tp, b->n_env, (unsigned)b->env_offset, b->actor_draw0, main_stream(b)));
     b->actor_draw0++;
-    // (outputs of the step that have no tape land in the batch's own record, hb_env_step's device buffers)
-    rc = env_step_impl(b, tp.action, n_substeps, nullptr, true, out->obs + (row + n) * nobs, out->reward ? out->reward + row : b->d_reward,
-                       out->terminated ? out->terminated + row : b->d_term, out->truncated ? out->truncated + row : b->d_trunc);
+    // (outputs of the step that have no tape land in the batch's own record, hb_env_step's device buffers; with the normaliser the raw
+    // observations and rewards go to their aux tapes where those are given, else to the main tapes, which are then normalised in place)
+    float* obs_next = out->obs + (row + n) * nobs;
+    float* raw_obs = norm && aux && aux->raw_obs ? aux->raw_obs + row * nobs : obs_next;
+    float* reward = out->reward ? out->reward + row : nullptr;
+    float* raw_reward = norm && aux && aux->raw_reward ? aux->raw_reward + row : (reward ? reward : b->d_reward);
+    uint8_t* term = out->terminated ? out->terminated + row : b->d_term;
+    uint8_t* trunc = out->truncated ? out->truncated + row : b->d_trunc;
+    rc = env_step_impl(b, tp.action, n_substeps, nullptr, true, raw_obs, raw_reward, term, trunc);
     if (rc != HB_OK) return rc;
     if (out->terminal_obs)
       HB_HIP(hipMemcpyAsync(out->terminal_obs + row * nobs, b->d_term_obs, n * nobs * sizeof(float), hipMemcpyDeviceToDevice, main_stream(b)));
+    if (norm) {
+      hb_norm_io io;
+      memset(&io, 0, sizeof io);
+      io.obs_in = raw_obs; io.obs_out = obs_next; io.reward_in = raw_reward; io.reward_out = reward; io.terminated = term; io.truncated = trunc;
+      if (out->terminal_obs) io.terminal_obs_in = io.terminal_obs_out = out->terminal_obs + row * nobs;
+      io.ep_return_out = aux && aux->ep_return ? aux->ep_return + row : nullptr;
+      io.ep_length_out = aux && aux->ep_length ? aux->ep_length + row : nullptr;
+      if ((rc = norm_step_impl(b, io)) != HB_OK) return rc;
+    }
   }
   return HB_OK;
 }
+
+int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out* out) { return collect_impl(b, T, n_substeps, out, false, nullptr); }
 
 // ---- critic and the PPO buffer over a collection's tapes
 
@@ -651,6 +673,150 @@ int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb
     HB_HIP(launch_log_prob(d, rows, st));
   }
   return HB_OK;
+}
+
+// ---- running observation / reward normalisation and episode statistics (hb_norm.hip)
+
+int hb_norm_default_config(hb_norm_config* c) {
+  if (!c) return HB_EINVAL;
+  c->norm_obs = c->norm_reward = c->training = 1;
+  c->clip_obs = c->clip_reward = 10.f; c->gamma = 0.99f; c->epsilon = 1e-8f;
+  return HB_OK;
+}
+
+int hb_norm_configure(hb_batch* b, const hb_norm_config* cfg) {
+  if (!b) return HB_EINVAL;
+  if (cfg && (!std::isfinite(cfg->clip_obs) || !(cfg->clip_obs > 0.f) || !std::isfinite(cfg->clip_reward) || !(cfg->clip_reward > 0.f) ||
+              !std::isfinite(cfg->epsilon) || !(cfg->epsilon > 0.f) || !std::isfinite(cfg->gamma) || cfg->gamma < 0.f || cfg->gamma > 1.f))
+    return HB_EINVAL;
+  const int nobs = b->D.dm.nobs;
+  if (cfg && (nobs < 1 || nobs > kNormMaxObs)) return HB_EUNSUPPORTED;
+  HB_HIP(hipSetDevice(b->device));
+  if (!cfg) {
+    HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a step still in flight uses the buffers that are released)
+    reset_all(b->d_norm_rec, b->d_norm_env, b->d_norm_part, b->d_norm_len);
+    b->norm_on = false;
+    return HB_OK;
+  }
+  if (!b->norm_on) {
+    const size_t n = b->n_env, R = norm_rec_doubles(nobs), nchunk = (n + kNormChunk - 1) / kNormChunk;
+    int rc = b->d_norm_rec.alloc(2 * R);
+    if (rc == HB_OK) rc = b->d_norm_env.alloc(2 * n, /*zero=*/true);
+    if (rc == HB_OK) rc = b->d_norm_len.alloc(n, /*zero=*/true);
+    if (rc == HB_OK) rc = b->d_norm_part.reserve(nchunk * norm_part_doubles(nobs));
+    std::vector<double> rec(2 * R, 0.0);
+    for (int c = 0; c < nobs; c++) rec[nobs + c] = 1.0;
+    rec[2 * nobs] = 1e-4; rec[2 * nobs + 2] = 1.0; rec[2 * nobs + 3] = 1e-4;
+    if (rc == HB_OK && hipMemcpy(b->d_norm_rec, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = HB_ENODEVICE;
+    if (rc != HB_OK) { reset_all(b->d_norm_rec, b->d_norm_env, b->d_norm_part, b->d_norm_len); return rc; }
+    b->norm_k = 0;
+    b->norm_on = true;
+  }
+  b->norm_cfg = *cfg;
+  return HB_OK;
+}
+
+int hb_norm_get_stats(hb_batch* b, double* out) {
+  if (!b || !out || !b->norm_on) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  const int nobs = b->D.dm.nobs;
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  HB_HIP(hipMemcpy(out, b->d_norm_rec + (size_t)b->norm_k * norm_rec_doubles(nobs), (size_t)(2 * nobs + 4) * sizeof(double), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+int hb_norm_set_stats(hb_batch* b, const double* in) {
+  if (!b || !in || !b->norm_on) return HB_EINVAL;
+  const int nobs = b->D.dm.nobs;
+  for (int i = 0; i < 2 * nobs + 4; i++) if (!std::isfinite(in[i])) return HB_EINVAL;
+  for (int c = 0; c < nobs; c++) if (in[nobs + c] < 0.0) return HB_EINVAL;
+  if (in[2 * nobs] < 0.0 || in[2 * nobs + 2] < 0.0 || in[2 * nobs + 3] < 0.0) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  HB_HIP(hipMemcpy(b->d_norm_rec + (size_t)b->norm_k * norm_rec_doubles(nobs), in, (size_t)(2 * nobs + 4) * sizeof(double), hipMemcpyHostToDevice));
+  return HB_OK;
+}
+
+int hb_norm_get_env(hb_batch* b, double* disc_return, double* ep_return, int32_t* ep_length) {
+  if (!b || !b->norm_on) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  const size_t n = b->n_env;
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  if (disc_return) HB_HIP(hipMemcpy(disc_return, b->d_norm_env, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (ep_return) HB_HIP(hipMemcpy(ep_return, b->d_norm_env + n, n * sizeof(double), hipMemcpyDeviceToHost));
+  if (ep_length) HB_HIP(hipMemcpy(ep_length, b->d_norm_len, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+int hb_norm_episode_totals(hb_batch* b, double out[4]) {
+  if (!b || !out || !b->norm_on) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  const int nobs = b->D.dm.nobs;
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  HB_HIP(hipMemcpy(out, b->d_norm_rec + (size_t)b->norm_k * norm_rec_doubles(nobs) + 2 * nobs + 4, 4 * sizeof(double), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+// the fields every launch of the normaliser shares
+static NormDesc norm_desc(hb_batch* b) {
+  const hb_norm_config& c = b->norm_cfg;
+  NormDesc d;
+  memset(&d, 0, sizeof d);
+  d.nobs = b->D.dm.nobs;
+  d.norm_obs = c.norm_obs != 0; d.norm_reward = c.norm_reward != 0;
+  d.k = b->norm_k;
+  d.clip_obs = c.clip_obs; d.clip_reward = c.clip_reward; d.gamma = (double)c.gamma; d.epsilon = (double)c.epsilon;
+  d.rec = b->d_norm_rec; d.part = b->d_norm_part;
+  d.ret = b->d_norm_env; d.ep_ret = b->d_norm_env + b->n_env; d.ep_len = b->d_norm_len;
+  return d;
+}
+
+// a step (io.reward_in given) or a reset over the batch's n_env rows: the moments launch, the apply launch, and the slot flips
+static int norm_step_impl(hb_batch* b, const hb_norm_io& io) {
+  const hb_norm_config& c = b->norm_cfg;
+  NormDesc d = norm_desc(b);
+  d.n_rows = b->n_env; d.nchunk = (b->n_env + kNormChunk - 1) / kNormChunk;
+  d.reset = io.reward_in == nullptr;
+  d.upd_obs = c.training && c.norm_obs; d.upd_ret = c.training && !d.reset;
+  d.store = 1;
+  d.obs_in = io.obs_in; d.obs_out = io.obs_out; d.reward_in = io.reward_in; d.reward_out = io.reward_out;
+  d.term = io.terminated; d.trunc = io.truncated; d.tobs_in = io.terminal_obs_in; d.tobs_out = io.terminal_obs_out;
+  d.ep_return_out = io.ep_return_out; d.ep_length_out = io.ep_length_out;
+  hipStream_t st = main_stream(b);
+  HB_HIP(launch_norm_moments(d, st));
+  HB_HIP(launch_norm_apply(d, st));
+  b->norm_k ^= 1;
+  return HB_OK;
+}
+
+int hb_norm_step_dev(hb_batch* b, const hb_norm_io* io) {
+  if (!b || !io || !b->norm_on || !io->obs_in || !io->obs_out || !io->reward_in || !io->terminated || !io->truncated) return HB_EINVAL;
+  if ((io->terminal_obs_in == nullptr) != (io->terminal_obs_out == nullptr)) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  return norm_step_impl(b, *io);
+}
+
+int hb_norm_reset_dev(hb_batch* b, const float* obs_in, float* obs_out) {
+  if (!b || !b->norm_on || !obs_in || !obs_out) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  hb_norm_io io;
+  memset(&io, 0, sizeof io);
+  io.obs_in = obs_in; io.obs_out = obs_out;
+  return norm_step_impl(b, io);
+}
+
+int hb_norm_obs_dev(hb_batch* b, const float* in, float* out, long long n_rows) {
+  if (!b || !b->norm_on || !in || !out || n_rows < 1) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  NormDesc d = norm_desc(b);
+  d.n_rows = n_rows;
+  d.obs_in = in; d.obs_out = out;
+  HB_HIP(launch_norm_apply(d, main_stream(b)));
+  return HB_OK;
+}
+
+int hb_env_collect_norm_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out* out, const hb_norm_tapes* aux) {
+  return collect_impl(b, T, n_substeps, out, true, aux);
 }
 
 int hb_env_warnings(hb_batch* b, int* warnings) {

@@ -212,6 +212,13 @@ struct hb_batch {
   int critic_sizes[5] = {0, 0, 0, 0, 0};
   DevBuf<float> d_critic_wp[4], d_critic_b[4];
   DevBuf<float> d_gae;
+  // normaliser (hb_norm_*): the double-buffered statistics record (slot norm_k is current; hb_device.hpp: NormDesc), the per-env
+  // accumulators ret | ep_ret [2][n_env] and ep_len [n_env], and the chunk partials of a step; all null while none is configured
+  bool norm_on = false;
+  hb_norm_config norm_cfg = {};
+  int norm_k = 0;
+  DevBuf<double> d_norm_rec, d_norm_env, d_norm_part;
+  DevBuf<int> d_norm_len;
   // optional per-kernel timing of the step kernel (hb_step_timing)
   bool time_steps = false;
   std::vector<hipEvent_t> tev;  // pairs

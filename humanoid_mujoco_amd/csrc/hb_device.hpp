@@ -277,6 +277,35 @@ struct LogProbDesc {
   float* out;
 };
 
+// hb_norm_* (hb_norm.hip).  The rows are reduced in chunks of kNormChunk consecutive envs, chunk c = envs [64 c, 64 c + 64).
+// rec: the double-buffered record, slot s at rec + s norm_rec_doubles(nobs): obs_mean[nobs] | obs_var[nobs] | obs_count | ret_mean |
+// ret_var | ret_count (the flat record of hb_norm_get_stats) | the four episode totals.  part: one partial per chunk,
+// norm_part_doubles(nobs) doubles: n | the chunk's four episode-total terms | (mean, biased variance) of every obs column and of
+// the ret column.
+constexpr int kNormChunk = 64;
+constexpr int kNormMaxObs = 240;  // (a chunk of rows in LDS: 64 x 240 floats = 60 KB)
+__host__ __device__ inline int norm_rec_doubles(int nobs) { return 2 * nobs + 8; }
+__host__ __device__ inline int norm_part_doubles(int nobs) { return 5 + 2 * (nobs + 1); }
+struct NormDesc {
+  int nobs;
+  long long n_rows;                // rows of this call (n_env for a step or a reset)
+  int nchunk;                      // partials to merge (0: none - hb_norm_obs_dev)
+  int upd_obs, upd_ret;            // form and merge the partials of obs_rms / ret_rms (training && norm_obs, training)
+  int reset;                       // moments: set ret, ep_ret, ep_len to 0 instead of advancing them
+  int norm_obs, norm_reward;
+  int store;                       // apply: block 0 writes the record to slot k ^ 1 (a step or a reset; not hb_norm_obs_dev)
+  int k;                           // the slot that is read
+  float clip_obs, clip_reward;
+  double gamma, epsilon;
+  double *rec, *part;
+  double *ret, *ep_ret;            // [n_env]
+  int* ep_len;                     // [n_env]
+  const float *obs_in, *reward_in, *tobs_in;
+  const uint8_t *term, *trunc;
+  float *obs_out, *reward_out, *tobs_out, *ep_return_out;
+  int* ep_length_out;
+};
+
 // Buffers of the STAGED step of the general variants (launch_step): hb_pose_kernel writes every geom's world pose and the env's
 // narrowphase work items, hb_narrow_kernel evaluates the items (one per lane, at the occupancy of a small kernel: the MPR climbs are
 // chains of dependent loads), the step kernel appends the results in item order.  All null: the step kernel does all of it itself.

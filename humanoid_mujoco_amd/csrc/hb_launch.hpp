@@ -66,6 +66,9 @@ hipError_t launch_actor(const ActorDesc& ad, const float* obs, const ActorTapes&
 hipError_t launch_value(const PolicyDesc& pd, const float* rows, const uint8_t* term, const uint8_t* trunc, long long n_rows, float* out, hipStream_t stream);
 hipError_t launch_gae_scan(const GaeScan& g, hipStream_t stream);
 hipError_t launch_log_prob(const LogProbDesc& d, long long n_rows, hipStream_t stream);
+// the normaliser (hb_norm.hip): the chunk partials of a step or reset (and the per-env accumulators), then the merge and the normalisation
+hipError_t launch_norm_moments(const NormDesc& d, hipStream_t stream);
+hipError_t launch_norm_apply(const NormDesc& d, hipStream_t stream);
 // order: [2 * n_env] ints - the permutation, then the sort keys of the pass (read once from counts)
 hipError_t launch_order(const int* counts, int* order, int n_env, int e0, int n, hipStream_t stream, int slot = 3, int shift = 3);
 hipError_t launch_mlp_layer(const float* X, const float* W, const float* bias, float* Y, int Mrows, int K, int N, int act, hipStream_t stream);

@@ -159,6 +159,23 @@ class HbGaeOut(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("value", "terminal_value", "log_prob", "advantage", "returns")]
 
 
+class HbNormConfig(ctypes.Structure):
+    """hb_norm_config (include/hb.h): VecNormalize's switches and constants."""
+    _fields_ = [("norm_obs", ctypes.c_int), ("norm_reward", ctypes.c_int), ("training", ctypes.c_int), ("clip_obs", ctypes.c_float),
+                ("clip_reward", ctypes.c_float), ("gamma", ctypes.c_float), ("epsilon", ctypes.c_float)]
+
+
+class HbNormIo(ctypes.Structure):
+    """hb_norm_io (include/hb.h): device pointers of one normaliser step."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("obs_in", "obs_out", "reward_in", "reward_out", "terminated", "truncated", "terminal_obs_in",
+                                               "terminal_obs_out", "ep_return_out", "ep_length_out")]
+
+
+class HbNormTapes(ctypes.Structure):
+    """hb_norm_tapes (include/hb.h): the normaliser's own tapes of a collection, each nullable."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("raw_obs", "raw_reward", "ep_return", "ep_length")]
+
+
 class HbError(RuntimeError):
     pass
 
@@ -271,6 +288,16 @@ def lib():
     L.hb_env_collect_dev.argtypes = [vp, ci, ci, ctypes.POINTER(HbCollectOut)]
     L.hb_critic_set_mlp.argtypes = [vp, ci, vp, vp, vp]
     L.hb_collect_gae_dev.argtypes = [vp, ci, ctypes.POINTER(HbCollectOut), ctypes.POINTER(HbGaeConfig), ctypes.POINTER(HbGaeOut)]
+    L.hb_norm_default_config.argtypes = [ctypes.POINTER(HbNormConfig)]
+    L.hb_norm_configure.argtypes = [vp, ctypes.POINTER(HbNormConfig)]
+    L.hb_norm_get_stats.argtypes = [vp, vp]
+    L.hb_norm_set_stats.argtypes = [vp, vp]
+    L.hb_norm_get_env.argtypes = [vp, vp, vp, vp]
+    L.hb_norm_episode_totals.argtypes = [vp, vp]
+    L.hb_norm_step_dev.argtypes = [vp, ctypes.POINTER(HbNormIo)]
+    L.hb_norm_reset_dev.argtypes = [vp, vp, vp]
+    L.hb_norm_obs_dev.argtypes = [vp, vp, vp, ctypes.c_longlong]
+    L.hb_env_collect_norm_dev.argtypes = [vp, ci, ci, ctypes.POINTER(HbCollectOut), ctypes.POINTER(HbNormTapes)]
     L.hb_dev_alloc.restype = vp; L.hb_dev_alloc.argtypes = [vp, ctypes.c_uint64]
     L.hb_dev_free.restype = None; L.hb_dev_free.argtypes = [vp, vp]
     L.hb_host_alloc.restype = vp; L.hb_host_alloc.argtypes = [ctypes.c_uint64]
@@ -1211,6 +1238,67 @@ class Batch:
         rc = lib().hb_collect_gae_dev(self._h, int(T), ctypes.byref(tapes), ctypes.byref(cfg), ctypes.byref(out))
         _check(rc, "hb_collect_gae_dev", "needs T >= 1, gamma and lam in [0, 1], at least one output, the tapes each output reads, a critic "
                "(critic_set) for the value outputs and a sampling actor (actor_set, not the deterministic head) for log_prob" if rc == -1 else None)
+
+    # ---- running observation / reward normalisation and episode statistics (include/hb.h: hb_norm_*)
+    _NORM_WHY = "needs a normaliser (norm_configure) and the required device pointers"
+
+    def norm_configure(self, norm_obs=True, norm_reward=True, training=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8):
+        """Installs the normaliser (VecNormalize over a VecMonitor, stable-baselines3's defaults); a later call changes the switches and
+        constants and keeps the statistics (training=False: evaluation).  norm_configure(None) removes it."""
+        if norm_obs is None:
+            _check(lib().hb_norm_configure(self._h, None), "hb_norm_configure")
+            return
+        cfg = HbNormConfig(int(bool(norm_obs)), int(bool(norm_reward)), int(bool(training)), float(clip_obs), float(clip_reward), float(gamma), float(epsilon))
+        rc = lib().hb_norm_configure(self._h, ctypes.byref(cfg))
+        _check(rc, "hb_norm_configure", "clip_obs, clip_reward and epsilon must be finite and positive, gamma in [0, 1]" if rc == -1 else
+               "more than 240 observations" if rc == -4 else None)
+
+    def norm_stats(self):
+        """the flat fp64 record obs_mean[nobs] | obs_var[nobs] | obs_count | ret_mean | ret_var | ret_count (hb_norm_get_stats)"""
+        out = np.zeros(2 * self.model.nobs + 4, dtype=np.float64)
+        _check(lib().hb_norm_get_stats(self._h, _ptr(out)), "hb_norm_get_stats", "no normaliser configured")
+        return out
+
+    def norm_set_stats(self, record):
+        a = np.ascontiguousarray(record, dtype=np.float64)
+        if a.shape != (2 * self.model.nobs + 4,):
+            raise ValueError("norm_set_stats: the record holds 2 nobs + 4 values")
+        _check(lib().hb_norm_set_stats(self._h, _ptr(a)), "hb_norm_set_stats", "needs a normaliser, finite values, and no negative var or count")
+
+    def norm_env(self):
+        """(disc_return [n_env] f64, ep_return [n_env] f64, ep_length [n_env] i32): the per-env accumulators (hb_norm_get_env)"""
+        ret, er, el = np.zeros(self.n_env), np.zeros(self.n_env), np.zeros(self.n_env, dtype=np.int32)
+        _check(lib().hb_norm_get_env(self._h, _ptr(ret), _ptr(er), _ptr(el)), "hb_norm_get_env", "no normaliser configured")
+        return ret, er, el
+
+    def norm_episode_totals(self):
+        """[episodes finished, sum of returns, sum of squared returns, sum of lengths] since the normaliser was installed"""
+        out = np.zeros(4, dtype=np.float64)
+        _check(lib().hb_norm_episode_totals(self._h, _ptr(out)), "hb_norm_episode_totals", "no normaliser configured")
+        return out
+
+    def norm_step_dev(self, obs_in, obs_out, reward_in, terminated, truncated, reward_out=None, terminal_obs_in=None, terminal_obs_out=None,
+                      ep_return_out=None, ep_length_out=None):
+        """hb_norm_step_dev: one VecNormalize / VecMonitor step over the batch's rows on its stream; device pointers, in place allowed."""
+        io = HbNormIo(obs_in, obs_out, reward_in, reward_out, terminated, truncated, terminal_obs_in, terminal_obs_out, ep_return_out, ep_length_out)
+        _check(lib().hb_norm_step_dev(self._h, ctypes.byref(io)), "hb_norm_step_dev", self._NORM_WHY)
+
+    def norm_reset_dev(self, obs_in, obs_out):
+        """hb_norm_reset_dev: VecNormalize.reset on the observations hb_env_reset returned (device pointers)."""
+        _check(lib().hb_norm_reset_dev(self._h, ctypes.c_void_p(obs_in), ctypes.c_void_p(obs_out)), "hb_norm_reset_dev", self._NORM_WHY)
+
+    def norm_obs_dev(self, in_ptr, out_ptr, n_rows):
+        """hb_norm_obs_dev: normalize_obs on n_rows rows with the current statistics, no update."""
+        _check(lib().hb_norm_obs_dev(self._h, ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr), int(n_rows)), "hb_norm_obs_dev", self._NORM_WHY)
+
+    def env_collect_norm_dev(self, T, n_substeps=1, obs=None, action=None, mean=None, log_std=None, eps=None, reward=None, terminated=None,
+                             truncated=None, terminal_obs=None, raw_obs=None, raw_reward=None, ep_return=None, ep_length=None):
+        """hb_env_collect_norm_dev: env_collect_dev with the normaliser behind every env step; row 0 of obs is given normalised.  The aux
+        tapes raw_obs [T, n_env, nobs], raw_reward, ep_return (float32) and ep_length (int32) [T, n_env] are optional."""
+        out = HbCollectOut(obs, action, mean, log_std, eps, reward, terminated, truncated, terminal_obs)
+        aux = HbNormTapes(raw_obs, raw_reward, ep_return, ep_length)
+        rc = lib().hb_env_collect_norm_dev(self._h, int(T), int(n_substeps), ctypes.byref(out), ctypes.byref(aux))
+        _check(rc, "hb_env_collect_norm_dev", "needs what env_collect_dev needs and a normaliser (norm_configure)" if rc == -1 else None)
 
     # ---- device buffers / timing helpers (no HIP headers or torch needed on the caller's side)
     def dev_alloc(self, nbytes):

@@ -50,7 +50,7 @@ _NO_INFO = {}  # (shared by the envs that did not finish an episode this step: S
 
 class VecEnv:
     def __init__(self, model, n_envs, device=0, n_substeps=1, randomization_factor=1.0, realism=False, domain_randomization=False, seed=0, team=False,
-                 contact_forces=False, body_accelerations=False, height_scan=None, **reward_overrides):
+                 contact_forces=False, body_accelerations=False, height_scan=None, normalize=None, **reward_overrides):
         """realism=True adds CPUEnv's sensor/action noise, delay FIFOs and pushes (hb_env_randomization), scaled by
         randomization_factor exactly like the reset perturbation; domain_randomization=True draws per-env masses, floor
         friction, joint and actuator parameters at every reset (hb_domain_randomization).  team=True: the reference's own
@@ -59,7 +59,12 @@ class VecEnv:
         body_contact_forces(); such steps run the full step kernel.  body_accelerations=True: likewise every body's acceleration
         (hb_body_acc_readout), read with body_accelerations().  height_scan=dict(body=..., xs=..., ys=..., z0=1.0, cutoff=2 * z0): a grid
         of downward rays from z0 above `body` (id or name) at the offsets xs (forward) x ys (left) of its heading frame, at the geoms of the
-        world body only (hb_ray_configure: yaw frame, static), read with height_scan() / height_scan_torch(); the observation is unchanged."""
+        world body only (hb_ray_configure: yaw frame, static), read with height_scan() / height_scan_torch(); the observation is unchanged.
+        normalize=dict(norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8) (any subset; {} for the
+        defaults): stable-baselines3's VecNormalize over a VecMonitor on the device (hb_norm_*): reset, step*, step_torch and collect*
+        return normalised observations and rewards, finished envs' infos carry "episode": {"r", "l"} and a normalised
+        terminal_observation; `training`, normalize_obs, get_original_obs / get_original_reward, save_normalization / load_normalization as
+        in VecNormalize.  normalize=None: every path is unchanged."""
         self.model = model if isinstance(model, Model) else Model.load(model)
         self.batch = Batch(self.model, n_envs, device)
         self.num_envs = int(n_envs)
@@ -117,6 +122,117 @@ class VecEnv:
         self.seed_value = int(seed)
         self.render_mode = None
         self.batch.env_terminal_obs(fetch=False)  # the env kernel records the observation an episode ends in (hb_env_terminal_obs)
+        self._norm = None
+        if normalize is not None:
+            opts = dict(norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8)
+            unknown = set(normalize) - set(opts)
+            if unknown:
+                raise TypeError("normalize: unknown option(s) %s" % sorted(unknown))
+            opts.update(normalize)
+            self._norm = opts
+            self._training = True
+            self._orig_obs = self._orig_reward = None
+            self.batch.norm_configure(training=True, **opts)
+
+    # ---- VecNormalize's surface (normalize=...)
+    def _need_norm(self, what):
+        if self._norm is None:
+            raise RuntimeError("%s: create the VecEnv with normalize=dict(...)" % what)
+
+    @property
+    def training(self):
+        """VecNormalize.training: False freezes the running statistics (evaluation); the monitor keeps counting"""
+        self._need_norm("training")
+        return self._training
+
+    @training.setter
+    def training(self, on):
+        self._need_norm("training")
+        self._training = bool(on)
+        self.batch.norm_configure(training=self._training, **self._norm)
+
+    def _norm_host(self):
+        """the device block the host paths stage a step in: obs | reward | ep_return | ep_length | terminal_obs | terminated | truncated"""
+        h = getattr(self, "_norm_dev", None)
+        if h is None:
+            n, nobs = self.num_envs, self.model.nobs
+            ob, rb = n * nobs * 4, n * 4
+            base = self.batch.dev_alloc(2 * ob + 3 * rb + 2 * n)
+            h = self._norm_dev = dict(obs=base, reward=base + ob, ep_ret=base + ob + rb, ep_len=base + ob + 2 * rb, tobs=base + ob + 3 * rb,
+                                      term=base + 2 * ob + 3 * rb, trunc=base + 2 * ob + 3 * rb + n, ob=ob, rb=rb)
+        return h
+
+    def _norm_reset_host(self, obs):
+        h = self._norm_host()
+        self._orig_obs, self._orig_reward = obs, None
+        self.batch.to_dev(h["obs"], obs)
+        self.batch.norm_reset_dev(h["obs"], h["obs"])
+        return self.batch.from_dev(h["obs"], obs.shape)
+
+    def _norm_step_host(self, obs, rew, term, trunc):
+        """one normaliser step on host arrays: (obs, reward, ep_return, ep_length), and the normalised terminal observations kept for
+        _sb3 when an env finished"""
+        h, n, nobs = self._norm_host(), self.num_envs, self.model.nobs
+        self._orig_obs, self._orig_reward = obs, rew
+        done = term | trunc
+        self.batch.to_dev(h["obs"], np.concatenate([np.ascontiguousarray(obs, np.float32).reshape(-1), np.ascontiguousarray(rew, np.float32)]))
+        self.batch.to_dev(h["term"], np.concatenate([term.astype(np.uint8), trunc.astype(np.uint8)]))
+        tobs = None
+        if done.any():
+            self.batch.to_dev(h["tobs"], self.batch.env_terminal_obs())
+            tobs = h["tobs"]
+        self.batch.norm_step_dev(h["obs"], h["obs"], h["reward"], h["term"], h["trunc"], reward_out=h["reward"], terminal_obs_in=tobs,
+                                 terminal_obs_out=tobs, ep_return_out=h["ep_ret"], ep_length_out=h["ep_len"])
+        out = self.batch.from_dev(h["obs"], (n * nobs + 3 * n,))
+        self._norm_tobs = self.batch.from_dev(h["tobs"], (n, nobs)) if tobs else None
+        return out[:n * nobs].reshape(n, nobs), out[n * nobs:n * nobs + n], out[n * nobs + n:n * nobs + 2 * n], out[n * nobs + 2 * n:].view(np.int32)
+
+    def normalize_obs(self, x):
+        """VecNormalize.normalize_obs: x [..., nobs] (array or CUDA tensor) with the current statistics, no update (hb_norm_obs_dev)"""
+        self._need_norm("normalize_obs")
+        nobs = self.model.nobs
+        if isinstance(x, np.ndarray) or not hasattr(x, "data_ptr"):
+            a = np.ascontiguousarray(x, dtype=np.float32)
+            assert a.shape[-1] == nobs and a.size, a.shape
+            p = self.batch.dev_alloc(a.nbytes)
+            try:
+                self.batch.to_dev(p, a)
+                self.batch.norm_obs_dev(p, p, a.size // nobs)
+                return self.batch.from_dev(p, a.shape)
+            finally:
+                self.batch.dev_free(p)
+        import torch
+        a = x.contiguous()
+        assert a.dtype == torch.float32 and a.shape[-1] == nobs and a.numel(), tuple(a.shape)
+        out = torch.empty_like(a)
+        stream = torch.cuda.ExternalStream(self.batch.stream, device=a.device)
+        cur = torch.cuda.current_stream(a.device)
+        stream.wait_stream(cur)
+        self.batch.norm_obs_dev(a.data_ptr(), out.data_ptr(), a.numel() // nobs)
+        cur.wait_stream(stream)  # (whatever the caller's stream does with either tensor next is ordered behind the kernel)
+        return out
+
+    def get_original_obs(self):
+        """VecNormalize.get_original_obs: the raw observations of the last reset / step* / step_torch (array or CUDA tensor)"""
+        self._need_norm("get_original_obs")
+        return self._orig_obs
+
+    def get_original_reward(self):
+        """VecNormalize.get_original_reward: the raw rewards of the last step* / step_torch"""
+        self._need_norm("get_original_reward")
+        return self._orig_reward
+
+    def save_normalization(self, path):
+        """VecNormalize.save: the flat statistics record (hb_norm_get_stats) as an .npz"""
+        self._need_norm("save_normalization")
+        np.savez(path, record=self.batch.norm_stats(), nobs=self.model.nobs)
+
+    def load_normalization(self, path):
+        self._need_norm("load_normalization")
+        with np.load(path if str(path).endswith(".npz") else str(path) + ".npz") as z:
+            if int(z["nobs"]) != self.model.nobs:
+                raise ValueError("load_normalization: the record is for %d observations, this model has %d" % (int(z["nobs"]), self.model.nobs))
+            self.batch.norm_set_stats(z["record"])
 
     @property
     def randomization_factor(self):
@@ -178,6 +294,8 @@ class VecEnv:
 
     def reset(self):
         self._last_obs = self.batch.env_reset()  # (a reference only: what collect() starts from when it is given no obs0)
+        if self._norm is not None:
+            self._last_obs = self._norm_reset_host(self._last_obs)
         return self._last_obs
 
     def step_async(self, actions):
@@ -205,13 +323,17 @@ class VecEnv:
         done = arr["done"]
         infos = [_NO_INFO] * self.num_envs
         if done.any():
-            tobs = self.batch.env_terminal_obs()  # one more transfer, only on the steps an episode ends
+            tobs = self.batch.env_terminal_obs() if self._norm is None else self._norm_tobs  # one more transfer, only on the steps an episode ends
             for i in np.flatnonzero(done):
                 infos[i] = {"terminal_observation": tobs[i].copy(), "TimeLimit.truncated": bool(trunc[i] and not term[i]), "is_success": bool(trunc[i]),
                             "warnings": int(arr["warnings"][i])}
+                if self._norm is not None:
+                    infos[i]["episode"] = {"r": float(arr["ep_return"][i]), "l": int(arr["ep_length"][i])}  # (Monitor's)
         return obs, rew, done, infos
 
     def _finish(self, obs, rew, term, trunc):
+        if self._norm is not None:
+            obs, rew, ep_ret, ep_len = self._norm_step_host(obs, rew, term, trunc)
         self._last_obs = obs
         done = term | trunc
         # "warnings": the per-env HB_WARN_* bits (mjData.warning, mjdata.h:54-65): a contact or constraint-row overflow (rows were dropped for
@@ -225,6 +347,8 @@ class VecEnv:
         w = self._warn
         infos = {"is_success": trunc.copy(), "done": done, "warnings": w,  # cpu_env.py:688-689
                  "overflow": (w & (WARN_CONTACTFULL | WARN_CNSTRFULL)) != 0}
+        if self._norm is not None:
+            infos["ep_return"], infos["ep_length"] = ep_ret, ep_len  # (of the episodes that ended at this step, 0 elsewhere)
         return obs, rew, term, trunc, infos
 
     def body_contact_forces(self):
@@ -332,7 +456,14 @@ class VecEnv:
         cur = torch.cuda.current_stream(a.device)
         self._t_stream.wait_stream(cur)   # the policy's output is complete before the step reads it
         o, r, te, tr = self._t_out
-        self.batch.env_step_dev(a.data_ptr(), o.data_ptr(), r.data_ptr(), te.data_ptr(), tr.data_ptr(), self.n_substeps)
+        if self._norm is None:
+            self.batch.env_step_dev(a.data_ptr(), o.data_ptr(), r.data_ptr(), te.data_ptr(), tr.data_ptr(), self.n_substeps)
+        else:  # the step writes the raw tensors (get_original_*), the normaliser the returned ones, on the same stream
+            if getattr(self, "_t_raw", None) is None:
+                self._t_raw = (torch.empty_like(o), torch.empty_like(r))
+            self._orig_obs, self._orig_reward = self._t_raw
+            self.batch.env_step_dev(a.data_ptr(), self._orig_obs.data_ptr(), self._orig_reward.data_ptr(), te.data_ptr(), tr.data_ptr(), self.n_substeps)
+            self.batch.norm_step_dev(self._orig_obs.data_ptr(), o.data_ptr(), self._orig_reward.data_ptr(), te.data_ptr(), tr.data_ptr(), reward_out=r.data_ptr())
         cur.wait_stream(self._t_stream)   # and the caller's stream sees the results
         a.record_stream(self._t_stream)
         self._last_obs = o
@@ -349,7 +480,7 @@ class VecEnv:
         [in, out], the transpose of torch.nn.Linear.weight; tanh hidden layers, linear output)."""
         self.batch.critic_set(sizes, weights, biases)
 
-    def collect_torch(self, T, obs0=None, terminal_obs=False, gae=None):
+    def collect_torch(self, T, obs0=None, terminal_obs=False, gae=None, raw=False):
         """T steps of the installed actor in the env loop on the device (hb_env_collect_dev): no host transfer, no host synchronisation,
         one Python call.  Returns a dict of CUDA tensors: "obs" [T + 1, n, nobs] (row 0 is obs0; row t + 1 the observation after step t,
         for an env that finished there the first of its new episode), "action", "mean", "eps" [T, n, nu] (and "log_std" with the squashed
@@ -361,7 +492,11 @@ class VecEnv:
         gae=dict(gamma=..., lam=..., bootstrap_truncated=True): the PPO buffer behind the collection on the same stream (hb_collect_gae_dev,
         needs critic_set): adds "value" [T + 1, n], "advantage" and "returns" [T, n], and with the gaussian and squashed heads "log_prob"
         [T, n]; with bootstrap_truncated (the default) the terminal_obs tape is recorded whether asked for or not, and V of it is folded
-        into the reward of envs cut by truncation alone, as stable-baselines3's collect_rollouts does.  gae=None: exactly the call above."""
+        into the reward of envs cut by truncation alone, as stable-baselines3's collect_rollouts does.  gae=None: exactly the call above.
+        With normalize=... (hb_env_collect_norm_dev): "obs" and "reward" are normalised, so are the rows of "terminal_obs" whose env
+        finished; obs0 is a NORMALISED observation (what reset / step* / collect* returned); the dict gains "ep_return" float32 and
+        "ep_length" int32 [T, n] (the return and length of the episode that ended at (t, e), 0 elsewhere), and with raw=True "raw_obs"
+        [T, n, nobs] (row t: the raw form of obs[t + 1]) and "raw_reward" [T, n]; gae=... then works on the normalised tapes."""
         import torch
         T = int(T)
         if gae is not None:
@@ -398,8 +533,22 @@ class VecEnv:
         assert tuple(src.shape) == (n, nobs), tuple(src.shape)
         t["obs"][0].copy_(src)  # on the caller's stream, behind whatever produced src (a host array: uploaded here)
         stream.wait_stream(cur)   # obs[0] is complete, and whoever still reads the previous tapes is done, before they are rewritten
-        self.batch.env_collect_dev(T, self.n_substeps, **{k: v.data_ptr() for k, v in t.items()})
         out = dict(t)
+        if self._norm is None:
+            if raw:
+                raise RuntimeError("collect: raw=True needs normalize=dict(...)")
+            self.batch.env_collect_dev(T, self.n_substeps, **{k: v.data_ptr() for k, v in t.items()})
+        else:
+            akey = ("norm", T, bool(raw))
+            if akey not in cache:
+                aux = {"ep_return": torch.empty((T, n), dtype=torch.float32, device=dev), "ep_length": torch.empty((T, n), dtype=torch.int32, device=dev)}
+                if raw:
+                    aux["raw_obs"] = torch.empty((T, n, nobs), dtype=torch.float32, device=dev)
+                    aux["raw_reward"] = torch.empty((T, n), dtype=torch.float32, device=dev)
+                cache[akey] = aux
+            aux = cache[akey]
+            self.batch.env_collect_norm_dev(T, self.n_substeps, **{k: v.data_ptr() for k, v in t.items()}, **{k: v.data_ptr() for k, v in aux.items()})
+            out.update(aux)
         if gae:
             gkey = ("gae", T)
             if gkey not in cache:
@@ -414,9 +563,12 @@ class VecEnv:
         out["terminated"], out["truncated"] = t["terminated"].view(torch.bool), t["truncated"].view(torch.bool)
         return out
 
-    def collect(self, T, obs0=None, terminal_obs=False, gae=None):
+    def collect(self, T, obs0=None, terminal_obs=False, gae=None, raw=False):
         """collect_torch with numpy arrays: the same dict, copied to the host (one synchronisation at the end)."""
-        return {k: v.cpu().numpy() for k, v in self.collect_torch(T, obs0=obs0, terminal_obs=terminal_obs, gae=gae).items()}
+        return {k: v.cpu().numpy() for k, v in self.collect_torch(T, obs0=obs0, terminal_obs=terminal_obs, gae=gae, raw=raw).items()}
 
     def close(self):
+        if getattr(self, "_norm_dev", None) is not None:
+            self.batch.dev_free(self._norm_dev["obs"])
+            self._norm_dev = None
         self.batch.close()

@@ -910,6 +910,90 @@ typedef struct hb_gae_out {  /* device pointers, each nullable, not all NULL */
  * call writes nothing. */
 int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb_gae_config* cfg, const hb_gae_out* out);
 
+/* ---- running observation / reward normalisation and episode statistics on the device (VecNormalize over a VecMonitor) ---- */
+
+/* The semantics are those of stable-baselines3's VecNormalize wrapped around a VecMonitor, restated here [recall: neither package is a
+ * dependency of this library; tests/norm_ref.py is the fp64 restatement the kernels are held to].
+ * Statistics are fp64: obs_rms = mean[nobs], var[nobs], count; ret_rms = mean, var, count (scalars); all start at mean 0, var 1,
+ * count 1e-4.  An UPDATE with n rows of mean mb and biased variance vb does, with d = mb - mean, tot = count + n:
+ *   mean += d n / tot;   var = (var count + vb n + d d count n / tot) / tot;   count = tot.
+ * One STEP, given the raw obs[n_env][nobs], the raw reward[n_env] and done = terminated | truncated, in this order:
+ *   1. training && norm_obs: update obs_rms with the n_env rows of obs (terminal observations never enter an update);
+ *   2. obs_out = clip((obs - mean) / sqrt(var + epsilon), -clip_obs, clip_obs) with the statistics after 1 (norm_obs 0: obs_out = obs);
+ *   3. training: ret[e] = ret[e] gamma + reward[e] for every env, then update ret_rms with the n_env values of ret (whether or not
+ *      norm_reward is set, as SB3 does);
+ *   4. norm_reward: reward_out = clip(reward / sqrt(ret_var + epsilon), -clip_reward, clip_reward) with the statistics after 3, else
+ *      reward_out = reward;
+ *   5. where done, the terminal-observation row is normalised as in 2 with the statistics after 1;
+ *   6. the monitor: ep_ret[e] += reward[e] (raw), ep_len[e] += 1; where done, ep_return_out[e] = ep_ret[e], ep_length_out[e] = ep_len[e],
+ *      the episode totals advance and ep_ret[e] = ep_len[e] = 0; where not done both outputs are 0;
+ *   7. ret[e] = 0 where done.
+ * A RESET (VecNormalize.reset) sets ret, ep_ret and ep_len to 0, updates obs_rms with the reset observations when training && norm_obs,
+ * and normalises them.
+ * Arithmetic: sums, statistics and (x - mean) / sqrt(var + epsilon) in fp64, rounded to fp32 once and clipped in fp32.  The n_env rows
+ * are reduced in fixed chunks of 64 consecutive envs, merged in chunk order with the update formula: the same bits run after run, but
+ * statistics are PER BATCH - unlike the actor's draws, normalised values are not the same bits on any split of a batch.  Several ranks
+ * share statistics through hb_norm_get_stats / hb_norm_set_stats: each rank reads its record, the ranks merge the records with the
+ * update formula (n = the other record's count, mb its mean, vb its var), and each rank writes the result back.
+ * Non-finite inputs are not special-cased, as in SB3: a NaN or infinity in an observation or reward enters the statistics. */
+typedef struct hb_norm_config {
+  int norm_obs, norm_reward, training;            /* SB3's defaults: 1, 1, 1 */
+  float clip_obs, clip_reward, gamma, epsilon;    /* 10, 10, 0.99, 1e-8 */
+} hb_norm_config;
+int hb_norm_default_config(hb_norm_config* cfg);
+/* Installs the normaliser.  The first installation allocates and initialises the statistics and the per-env accumulators; a later call
+ * changes the flags and constants and keeps statistics and accumulators (training = 0: evaluation with frozen statistics).  cfg NULL
+ * removes the normaliser with its statistics.  HB_EINVAL: NULL b; clip_obs, clip_reward or epsilon not finite or not positive; gamma
+ * not finite or outside [0, 1].  HB_EUNSUPPORTED: nobs above 240 (a chunk of rows is held in LDS).  A refused call changes nothing. */
+int hb_norm_configure(hb_batch* b, const hb_norm_config* cfg);
+/* VecNormalize.save / load, and the multi-GPU merge above.  The record is 2 nobs + 4 doubles: obs_mean[nobs] | obs_var[nobs] |
+ * obs_count | ret_mean | ret_var | ret_count.  Host pointers; both calls run behind the work enqueued so far and end synchronised.
+ * HB_EINVAL: NULL argument, no normaliser; set: a non-finite value, a negative var or count (nothing is written then). */
+int hb_norm_get_stats(hb_batch* b, double* out);
+int hb_norm_set_stats(hb_batch* b, const double* in);
+/* The per-env accumulators, each [n_env], each pointer nullable: the discounted return ret, the running episode return and length. */
+int hb_norm_get_env(hb_batch* b, double* disc_return, double* ep_return, int32_t* ep_length);
+/* out[0..3]: episodes finished, the sum of their (raw) returns, the sum of the squared returns, the sum of their lengths - counted
+ * since the first hb_norm_configure (ep_rew_mean = out[1] / out[0], ep_len_mean = out[3] / out[0]). */
+int hb_norm_episode_totals(hb_batch* b, double out[4]);
+
+typedef struct hb_norm_io {   /* device pointers; an output may be its input (in place) */
+  const float* obs_in;           /* [n_env][nobs] raw */
+  float* obs_out;                /* [n_env][nobs] */
+  const float* reward_in;        /* [n_env] raw */
+  float* reward_out;             /* [n_env], nullable */
+  const uint8_t* terminated;     /* [n_env] */
+  const uint8_t* truncated;      /* [n_env] */
+  const float* terminal_obs_in;  /* [n_env][nobs], nullable (then terminal_obs_out too): only the rows of done envs are read */
+  float* terminal_obs_out;       /* [n_env][nobs]: only the rows of done envs are written */
+  float* ep_return_out;          /* [n_env], nullable */
+  int32_t* ep_length_out;        /* [n_env], nullable */
+} hb_norm_io;
+/* One step (1 - 7 above) for the batch's n_env rows in two launches on the batch's stream: no host synchronisation, no transfer.
+ * HB_EINVAL: NULL b or io, no normaliser, NULL obs_in, obs_out, reward_in, terminated or truncated, only one of terminal_obs_in /
+ * terminal_obs_out.  A refused call writes nothing and leaves the statistics as they were. */
+int hb_norm_step_dev(hb_batch* b, const hb_norm_io* io);
+/* The reset form, for the observations hb_env_reset returned (device pointers, [n_env][nobs], in place allowed). */
+int hb_norm_reset_dev(hb_batch* b, const float* obs_in, float* obs_out);
+/* VecNormalize.normalize_obs: point 2 with the current statistics on any number of rows, no update (evaluation data, a learner's own
+ * buffers).  HB_EINVAL: NULL argument, no normaliser, n_rows < 1. */
+int hb_norm_obs_dev(hb_batch* b, const float* in, float* out, long long n_rows);
+
+typedef struct hb_norm_tapes {   /* device pointers, each nullable */
+  float* raw_obs;       /* [T][n_env][nobs]  row t is the raw form of obs[t + 1] */
+  float* raw_reward;    /* [T][n_env] */
+  float* ep_return;     /* [T][n_env]        the return of the episode env e finished at step t, 0 elsewhere */
+  int32_t* ep_length;   /* [T][n_env] */
+} hb_norm_tapes;
+/* hb_env_collect_dev's loop with one hb_norm_step_dev behind every env step, all on the batch's stream (the pipes of a pipelined batch
+ * are joined where the actor's launch already joins them).  The actor reads obs[t]; the caller supplies row 0 ALREADY NORMALISED - what
+ * hb_norm_reset_dev, hb_norm_step_dev or row T of the previous collection gave.  The env step writes raw values; the normaliser writes
+ * obs[t + 1], reward[t] and the rows of terminal_obs[t] whose env finished at t in normalised form (the other rows of terminal_obs[t]
+ * keep what the table copy put there: they were never meaningful), and fills the tapes of aux that are given (aux may be NULL).  With
+ * norm_obs = norm_reward = 0 the tapes of out equal hb_env_collect_dev's bit for bit.
+ * HB_EINVAL: as hb_env_collect_dev, and no normaliser. */
+int hb_env_collect_norm_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out* out, const hb_norm_tapes* aux);
+
 /* ---- host-side helpers so a C/C++/ctypes caller needs no HIP headers ---------------------------- */
 
 /* Device buffer on the batch's GPU (hipMalloc / hipFree). */
