@@ -11,14 +11,14 @@ namespace hb {
 // 16-column output tiles of a layer, each sweeping K four columns per v_mfma_f32_16x16x4_f32 (exact f32) with the A operand from LDS and
 // the B operand from weights the host packed in operand order (wp[tile][k/4][lane] = W[4(k/4) + lane/16][16 tile + lane%16], one coalesced
 // 256-byte wave load per MFMA); a layer with fewer than eight tiles splits K across the idle waves and the partial tiles are summed in a
-// fixed order (deterministic, no atomics).  What differs:
+// fixed order (deterministic, no atomics).  That layer loop is hb_mlp_layers.inl, included in place by the three kernels that run it
+// (here, hb_policy_kernel, hb_value_kernel): "head 0 is the existing policy" holds because it is the same source.  What differs:
 //  - the input tile is read from an observation row [n_env][nobs] - the env adapter's noisy, delayed observation - in one coalesced pass;
 //  - the last layer leaves its pre-activations (bias added) in the LDS tile, and a head pass with one lane per (env, actuator) forms
 //    mean, log_std, the N(0, 1) draw and the action and stores them: the block's 16 rows are one contiguous stretch of every tape, so
 //    consecutive lanes write consecutive floats.
 // The draw of (env, actuator) depends on the env's GLOBAL index and the step counter only (rng_normal, hb_kcommon.hpp): the same on any
 // split of a batch, whatever block or lane computes it.
-typedef float f32x4a __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(512) void hb_actor_kernel(const ActorDesc ad, const float* obs, const ActorTapes tp, int n_env, unsigned env_global0, unsigned draw) {
   extern __shared__ __attribute__((aligned(16))) float sm_actor[];
   const PolicyDesc& pd = ad.net;
@@ -39,60 +39,9 @@ __global__ __launch_bounds__(512) void hb_actor_kernel(const ActorDesc ad, const
     if (tid < 48) cur[(tid / 3) * ldx + nobs + tid % 3] = 0.f;
   }
   __syncthreads();
-  const int col = lane & 15, quad = lane >> 4;  // A: row = col, k offset = quad;  B: k offset = quad, column = col;  D: rows 4 quad + r, column col
-  for (int l = 0; l < pd.nl; l++) {
-    const int K = pd.sizes[l], N = pd.sizes[l + 1], KK = (K + 3) / 4, ntile = (N + 15) / 16;
-    const bool last = l + 1 == pd.nl;
-    int S = 1;  // K slices per tile
-    while (S * 2 * ntile <= 8) S *= 2;
-    const float* wp = pd.w[l];
-    const float* bias = pd.b[l];
-    if (!last && tid < 48) nxt[(tid / 3) * ldx + N + tid % 3] = 0.f;  // pad columns of the next layer's input
-    for (int it = wave; it < ntile * S; it += 8) {
-      const int nt = it / S, sl = it - nt * S;
-      const int kb = KK * sl / S, ke = KK * (sl + 1) / S;
-      f32x4a D = {0.f, 0.f, 0.f, 0.f};
-      const float* ap = cur + col * ldx + quad;
-      const float* bp = wp + (size_t)nt * KK * 64 + lane;
-      int kk = kb;
-      for (; kk + 8 <= ke; kk += 8) {  // eight operand pairs in flight per batch of MFMAs
-        float a[8], w[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { a[u] = ap[4 * (kk + u)]; w[u] = bp[(size_t)(kk + u) * 64]; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) D = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u], D, 0, 0, 0);
-      }
-      for (; kk < ke; kk++) D = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[4 * kk], bp[(size_t)kk * 64], D, 0, 0, 0);
-      const int n = nt * 16 + col;
-      if (S == 1) {
-        if (n < N) {
-          const float bn = bias[n];
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const float v = D[r] + bn;
-            nxt[(4 * quad + r) * ldx + n] = last ? v : tanhf(v);  // (the last layer's activation belongs to the head)
-          }
-        }
-      } else {
-        float* pp = part + it * 256;
-#pragma unroll
-        for (int r = 0; r < 4; r++) pp[(4 * quad + r) * 16 + col] = D[r];
-      }
-    }
-    __syncthreads();
-    if (S > 1) {
-      for (int idx = tid; idx < ntile * 256; idx += 512) {
-        const int nt = idx >> 8, rc = idx & 255, row = rc >> 4, n = nt * 16 + (rc & 15);
-        if (n < N) {
-          float v = bias[n];
-          for (int sl = 0; sl < S; sl++) v += part[(nt * S + sl) * 256 + rc];
-          nxt[row * ldx + n] = last ? v : tanhf(v);
-        }
-      }
-      __syncthreads();
-    }
-    float* t = cur; cur = nxt; nxt = t;
-  }
+#define HB_MLP_EMIT(row, n, v) nxt[(row) * ldx + (n)] = last ? (v) : tanhf(v)  // (the last layer's activation belongs to the head)
+#include "hb_mlp_layers.inl"
+#undef HB_MLP_EMIT
   // the head: cur holds the last layer's pre-activations [16][nu] (head 2: [16][2 nu], mean | log_std)
   const int nu = ad.nu;
   for (int idx = tid; idx < live * nu; idx += 512) {

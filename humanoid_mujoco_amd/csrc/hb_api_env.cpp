@@ -1,6 +1,8 @@
 // hb_api_env.cpp — the C-ABI of libhb.so (include/hb.h), the env adapter: observations, rewards and resets, the realism layer and
 // domain randomisation, the policy MLP, the sampling actor with its rollout collection, the critic with the PPO buffer over the tapes, and
-// the running observation / reward normaliser with its episode statistics.
+// the running observation / reward normaliser with its episode statistics.  The policy, the actor and the critic are each a DevMlp
+// (hb_batch.hpp): one owner packs, uploads and describes an installed network, and one check (mlp_args_ok) covers the arrays of the three
+// hb_*_set_mlp entry points; their kernels share one layer loop (hb_mlp_layers.inl).
 #include "hb_batch.hpp"
 
 extern "C" {
@@ -370,76 +372,44 @@ int hb_env_step_async(hb_batch* b, const float* action, int n_substeps, float* o
   return env_step_host(b, action, n_substeps, obs, reward, terminated, truncated, false);
 }
 
-// A layer's weights W[K][N] (row-major) in the B-operand order of v_mfma_f32_16x16x4_f32, as the fused policy and actor kernels stream them:
-// wp[tile][k/4][lane] = W[4(k/4) + lane/16][16 tile + lane%16], zero padded
-static std::vector<float> pack_mfma_b(const float* W, int K, int N) {
-  const int KK = (K + 3) / 4, ntile = (N + 15) / 16;
-  std::vector<float> wp((size_t)ntile * KK * 64, 0.f);
-  for (int nt = 0; nt < ntile; nt++)
-    for (int kk = 0; kk < KK; kk++)
-      for (int ln = 0; ln < 64; ln++) {
-        const int k = 4 * kk + (ln >> 4), n = 16 * nt + (ln & 15);
-        if (k < K && n < N) wp[((size_t)nt * KK + kk) * 64 + ln] = W[(size_t)k * N + n];
-      }
-  return wp;
-}
-
 int hb_policy_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases) {
-  if (!b || !sizes || !weights || !biases || n_layers < 1 || n_layers > 4) return HB_EINVAL;
+  if (!b || !mlp_args_ok(n_layers, sizes, weights, biases)) return HB_EINVAL;
   if (sizes[0] != b->D.dm.nobs || sizes[n_layers] != b->D.dm.nu) return HB_EINVAL;
-  for (int l = 0; l <= n_layers; l++) if (sizes[l] < 1 || sizes[l] > 512) return HB_EINVAL;
+  bool fused = true;  // one-launch policy kernel: every width fits its LDS tiles
+  int maxh = 1;
+  for (int l = 0; l <= n_layers; l++) {
+    if (sizes[l] > 512) return HB_EINVAL;
+    fused = fused && sizes[l] <= 256;
+    if (l > 0 && l < n_layers) maxh = std::max(maxh, sizes[l]);
+  }
   int rc = env_alloc(b);
   if (rc != HB_OK) return rc;
   HB_HIP(hipSetDevice(b->device));
-  HB_HIP(hipStreamSynchronize(main_stream(b)));
-  int maxh = 1;
-  bool fused = true;  // one-launch policy kernel: every width fits its LDS tiles
-  for (int l = 0; l <= n_layers; l++) fused = fused && sizes[l] <= 256;
-  for (int l = 0; l < n_layers; l++) {
-    if (!weights[l] || !biases[l]) return HB_EINVAL;
-    b->d_mlp_wp[l].reset();
-    if (fused) {
-      const std::vector<float> wp = pack_mfma_b(weights[l], sizes[l], sizes[l + 1]);
-      if (b->d_mlp_wp[l].alloc(wp.size()) != HB_OK) return HB_ENOMEM;
-      HB_HIP(hipMemcpy(b->d_mlp_wp[l], wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    reset_all(b->d_mlp_w[l], b->d_mlp_b[l]);
-    size_t nw = (size_t)sizes[l] * sizes[l + 1];
-    if (b->d_mlp_w[l].alloc(nw) != HB_OK || b->d_mlp_b[l].alloc(sizes[l + 1]) != HB_OK) return HB_ENOMEM;
-    HB_HIP(hipMemcpy(b->d_mlp_w[l], weights[l], nw * sizeof(float), hipMemcpyHostToDevice));
-    HB_HIP(hipMemcpy(b->d_mlp_b[l], biases[l], sizes[l + 1] * sizeof(float), hipMemcpyHostToDevice));
-    if (l + 1 < n_layers) maxh = std::max(maxh, sizes[l + 1]);
+  HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a call still in flight reads the buffers that are replaced below)
+  // (every argument check is behind us: from here on only the device can fail, and then no policy is installed)
+  for (int l = 0; l < 4; l++) b->d_mlp_w[l].reset();
+  reset_all(b->d_mlp_h[0], b->d_mlp_h[1], b->d_mlp_act);
+  rc = b->policy.install(n_layers, sizes, weights, biases);
+  if (rc == HB_OK && fused) rc = b->d_mlp_act.alloc(((size_t)(b->n_env + 15) / 16 + hb_batch::kPipes) * 32 * b->policy.desc().ldx, /*zero=*/true);
+  for (int l = 0; l < n_layers && rc == HB_OK && !fused; l++) {  // the layer-by-layer path reads the weights as they are given
+    const size_t nw = (size_t)sizes[l] * sizes[l + 1];
+    rc = b->d_mlp_w[l].alloc(nw);
+    if (rc == HB_OK && hipMemcpy(b->d_mlp_w[l], weights[l], nw * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = HB_ENODEVICE;
   }
-  for (int i = 0; i < 2; i++) {
-    b->d_mlp_h[i].reset();
-    if (b->d_mlp_h[i].alloc((size_t)b->n_env * maxh) != HB_OK) return HB_ENOMEM;
-  }
-  b->d_mlp_act.reset();
-  if (fused) {
-    int widest = 1;
-    for (int l = 0; l <= n_layers; l++) widest = std::max(widest, sizes[l]);
-    const size_t floats = ((size_t)(b->n_env + 15) / 16 + hb_batch::kPipes) * 32 * (widest + 4);
-    if ((rc = b->d_mlp_act.alloc(floats, /*zero=*/true)) != HB_OK) return rc;
-  }
-  b->mlp_layers = n_layers;
+  for (int i = 0; i < 2 && rc == HB_OK && !fused; i++) rc = b->d_mlp_h[i].alloc((size_t)b->n_env * maxh);
+  if (rc != HB_OK) b->policy.clear();
   b->mlp_fused = fused;
-  for (int l = 0; l <= n_layers; l++) b->mlp_sizes[l] = sizes[l];
-  return HB_OK;
+  return rc;
 }
 
 // obs -> MLP -> ctrl for envs [lo, hi) on `st`
 // (seg >= 0: env segment `seg` of a pipelined closed loop: the LDS-free kernel, which the GPU places beside the running step kernels)
 static int policy_forward(hb_batch* b, int lo, int hi, hipStream_t st, int seg = -1) {
-  if (b->mlp_layers < 1) return HB_EINVAL;
+  const DevMlp& net = b->policy;
+  if (net.layers < 1) return HB_EINVAL;
   const DevModel& dm = b->D.dm;
   if (b->mlp_fused) {
-    PolicyDesc pd;
-    memset(&pd, 0, sizeof pd);
-    pd.nl = b->mlp_layers;
-    int widest = 1;
-    for (int l = 0; l <= b->mlp_layers; l++) { pd.sizes[l] = b->mlp_sizes[l]; widest = std::max(widest, b->mlp_sizes[l]); }
-    for (int l = 0; l < b->mlp_layers; l++) { pd.w[l] = b->d_mlp_wp[l]; pd.b[l] = b->d_mlp_b[l]; }
-    pd.ldx = widest + 4;  // + the K pad columns (K is swept four at a time); 16-row tiles
+    const PolicyDesc pd = net.desc();
     const bool lean_ok = b->tune[HB_TUNE_POLICY_LEAN] != 0;
     const bool lean_all = b->tune[HB_TUNE_POLICY_LEAN] == 2;
     if (lean_all && seg < 0) seg = 0;
@@ -451,11 +421,11 @@ static int policy_forward(hb_batch* b, int lo, int hi, hipStream_t st, int seg =
     return HB_OK;
   }
   // wide layers: one launch per layer, activations through HBM
-  HB_HIP(launch_obs(dm, b->d_state + (size_t)lo * dm.nstate, b->d_obs + (size_t)lo * b->mlp_sizes[0], hi - lo, st));
-  const float* x = b->d_obs + (size_t)lo * b->mlp_sizes[0];
-  for (int l = 0; l < b->mlp_layers; l++) {
-    float* y = ((l + 1 == b->mlp_layers) ? ctrl_for_write(b) : b->d_mlp_h[l & 1]) + (size_t)lo * b->mlp_sizes[l + 1];
-    HB_HIP(launch_mlp_layer(x, b->d_mlp_w[l], b->d_mlp_b[l], y, hi - lo, b->mlp_sizes[l], b->mlp_sizes[l + 1], 1, st));
+  HB_HIP(launch_obs(dm, b->d_state + (size_t)lo * dm.nstate, b->d_obs + (size_t)lo * net.sizes[0], hi - lo, st));
+  const float* x = b->d_obs + (size_t)lo * net.sizes[0];
+  for (int l = 0; l < net.layers; l++) {
+    float* y = ((l + 1 == net.layers) ? ctrl_for_write(b) : b->d_mlp_h[l & 1]) + (size_t)lo * net.sizes[l + 1];
+    HB_HIP(launch_mlp_layer(x, b->d_mlp_w[l], net.b[l], y, hi - lo, net.sizes[l], net.sizes[l + 1], 1, st));
     x = y;
   }
   return HB_OK;
@@ -498,13 +468,11 @@ int hb_rollout_policy(hb_batch* b, int T, float* qpos_out_dev) {
 // ---- actor and rollout collection
 
 int hb_actor_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases, const hb_actor_config* cfg) {
-  if (!b || !sizes || !weights || !biases || !cfg || n_layers < 1 || n_layers > 4) return HB_EINVAL;
+  if (!b || !cfg || !mlp_args_ok(n_layers, sizes, weights, biases)) return HB_EINVAL;
   const int nu = b->D.dm.nu;
   if (cfg->head != HB_ACTOR_DETERMINISTIC && cfg->head != HB_ACTOR_GAUSSIAN && cfg->head != HB_ACTOR_SQUASHED) return HB_EINVAL;
   if (nu < 1 || nu > kActorMaxNu) return HB_EINVAL;
   if (sizes[0] != b->D.dm.nobs || sizes[n_layers] != (cfg->head == HB_ACTOR_SQUASHED ? 2 * nu : nu)) return HB_EINVAL;
-  for (int l = 0; l <= n_layers; l++) if (sizes[l] < 1) return HB_EINVAL;
-  for (int l = 0; l < n_layers; l++) if (!weights[l] || !biases[l]) return HB_EINVAL;
   if (cfg->head == HB_ACTOR_GAUSSIAN) for (int i = 0; i < nu; i++) if (!std::isfinite(cfg->log_std[i])) return HB_EINVAL;
   for (int l = 0; l <= n_layers; l++) if (sizes[l] > 256) return HB_EUNSUPPORTED;  // (the fused kernel's LDS tiles; no layer-by-layer fallback)
   int rc = env_alloc(b);
@@ -512,16 +480,7 @@ int hb_actor_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* c
   HB_HIP(hipSetDevice(b->device));
   HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a collection still in flight reads the buffers that are replaced below)
   // (every argument check is behind us: from here on only the device can fail, and then no actor is installed)
-  b->actor_layers = 0;
-  for (int l = 0; l < 4; l++) reset_all(b->d_actor_wp[l], b->d_actor_b[l]);
-  for (int l = 0; l < n_layers; l++) {
-    const std::vector<float> packed = pack_mfma_b(weights[l], sizes[l], sizes[l + 1]);
-    if (b->d_actor_wp[l].alloc(packed.size()) != HB_OK || b->d_actor_b[l].alloc(sizes[l + 1]) != HB_OK) return HB_ENOMEM;
-    HB_HIP(hipMemcpy(b->d_actor_wp[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-    HB_HIP(hipMemcpy(b->d_actor_b[l], biases[l], sizes[l + 1] * sizeof(float), hipMemcpyHostToDevice));
-  }
-  b->actor_layers = n_layers;
-  for (int l = 0; l <= n_layers; l++) b->actor_sizes[l] = sizes[l];
+  if ((rc = b->actor.install(n_layers, sizes, weights, biases)) != HB_OK) return rc;
   b->actor_cfg = *cfg;
   b->actor_draw0 = 0;
   return HB_OK;
@@ -531,7 +490,7 @@ static int norm_step_impl(hb_batch* b, const hb_norm_io& io);
 
 // the loop of hb_env_collect_dev; norm: one normaliser step behind every env step (hb_env_collect_norm_dev), aux: its tapes or null
 static int collect_impl(hb_batch* b, int T, int n_substeps, const hb_collect_out* out, bool norm, const hb_norm_tapes* aux) {
-  if (!b || T < 1 || n_substeps < 1 || !out || !out->obs || !out->action || b->actor_layers < 1) return HB_EINVAL;
+  if (!b || T < 1 || n_substeps < 1 || !out || !out->obs || !out->action || b->actor.layers < 1) return HB_EINVAL;
   if (out->log_std && b->actor_cfg.head != HB_ACTOR_SQUASHED) return HB_EINVAL;
   if (norm && !b->norm_on) return HB_EINVAL;
   int rc = env_alloc(b);
@@ -542,11 +501,7 @@ static int collect_impl(hb_batch* b, int T, int n_substeps, const hb_collect_out
   if (out->terminal_obs && !b->d_term_obs && (rc = hb_env_terminal_obs(b, nullptr)) != HB_OK) return rc;
   ActorDesc ad;
   memset(&ad, 0, sizeof ad);
-  ad.net.nl = b->actor_layers;
-  int widest = 1;
-  for (int l = 0; l <= b->actor_layers; l++) { ad.net.sizes[l] = b->actor_sizes[l]; widest = std::max(widest, b->actor_sizes[l]); }
-  for (int l = 0; l < b->actor_layers; l++) { ad.net.w[l] = b->d_actor_wp[l]; ad.net.b[l] = b->d_actor_b[l]; }
-  ad.net.ldx = widest + 4;  // + the K pad columns (K is swept four at a time); 16-row tiles
+  ad.net = b->actor.desc();
   ad.head = b->actor_cfg.head; ad.deterministic = b->actor_cfg.deterministic != 0; ad.nu = dm.nu; ad.seed = b->actor_cfg.seed;
   memcpy(ad.log_std, b->actor_cfg.log_std, sizeof ad.log_std);
   for (int t = 0; t < T; t++) {
@@ -588,25 +543,13 @@ int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out*
 // ---- critic and the PPO buffer over a collection's tapes
 
 int hb_critic_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases) {
-  if (!b || !sizes || !weights || !biases || n_layers < 1 || n_layers > 4) return HB_EINVAL;
+  if (!b || !mlp_args_ok(n_layers, sizes, weights, biases)) return HB_EINVAL;
   if (sizes[0] != b->D.dm.nobs || sizes[n_layers] != 1) return HB_EINVAL;
-  for (int l = 0; l <= n_layers; l++) if (sizes[l] < 1) return HB_EINVAL;
-  for (int l = 0; l < n_layers; l++) if (!weights[l] || !biases[l]) return HB_EINVAL;
   for (int l = 0; l <= n_layers; l++) if (sizes[l] > 256) return HB_EUNSUPPORTED;  // (the fused kernel's LDS tiles; no layer-by-layer fallback)
   HB_HIP(hipSetDevice(b->device));
   HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a call still in flight reads the buffers that are replaced below)
   // (every argument check is behind us: from here on only the device can fail, and then no critic is installed)
-  b->critic_layers = 0;
-  for (int l = 0; l < 4; l++) reset_all(b->d_critic_wp[l], b->d_critic_b[l]);
-  for (int l = 0; l < n_layers; l++) {
-    const std::vector<float> packed = pack_mfma_b(weights[l], sizes[l], sizes[l + 1]);
-    if (b->d_critic_wp[l].alloc(packed.size()) != HB_OK || b->d_critic_b[l].alloc(sizes[l + 1]) != HB_OK) return HB_ENOMEM;
-    HB_HIP(hipMemcpy(b->d_critic_wp[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-    HB_HIP(hipMemcpy(b->d_critic_b[l], biases[l], sizes[l + 1] * sizeof(float), hipMemcpyHostToDevice));
-  }
-  b->critic_layers = n_layers;
-  for (int l = 0; l <= n_layers; l++) b->critic_sizes[l] = sizes[l];
-  return HB_OK;
+  return b->critic.install(n_layers, sizes, weights, biases);
 }
 
 int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb_gae_config* cfg, const hb_gae_out* out) {
@@ -615,13 +558,13 @@ int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb
   if (!std::isfinite(cfg->gamma) || !std::isfinite(cfg->lam) || cfg->gamma < 0.f || cfg->gamma > 1.f || cfg->lam < 0.f || cfg->lam > 1.f) return HB_EINVAL;
   const bool boot = cfg->bootstrap_truncated != 0, scan = out->advantage || out->returns;
   const bool want_value = out->value || scan, want_tv = out->terminal_value || (scan && boot);
-  if ((want_value || want_tv) && b->critic_layers < 1) return HB_EINVAL;
+  if ((want_value || want_tv) && b->critic.layers < 1) return HB_EINVAL;
   if (want_value && !tapes->obs) return HB_EINVAL;
   if (scan && (!tapes->reward || !tapes->terminated || !tapes->truncated)) return HB_EINVAL;
   if (want_tv && (!tapes->terminal_obs || !tapes->terminated || !tapes->truncated)) return HB_EINVAL;
   const int head = b->actor_cfg.head;
   if (out->log_prob) {
-    if (b->actor_layers < 1 || head == HB_ACTOR_DETERMINISTIC || !tapes->eps) return HB_EINVAL;
+    if (b->actor.layers < 1 || head == HB_ACTOR_DETERMINISTIC || !tapes->eps) return HB_EINVAL;
     if (head == HB_ACTOR_SQUASHED && (!tapes->mean || !tapes->log_std)) return HB_EINVAL;
   }
   HB_HIP(hipSetDevice(b->device));
@@ -640,15 +583,7 @@ int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb
     if (want_tv && !tv) tv = p;
   }
   hipStream_t st = main_stream(b);
-  PolicyDesc pd;
-  memset(&pd, 0, sizeof pd);
-  if (want_value || want_tv) {
-    pd.nl = b->critic_layers;
-    int widest = 1;
-    for (int l = 0; l <= b->critic_layers; l++) { pd.sizes[l] = b->critic_sizes[l]; widest = std::max(widest, b->critic_sizes[l]); }
-    for (int l = 0; l < b->critic_layers; l++) { pd.w[l] = b->d_critic_wp[l]; pd.b[l] = b->d_critic_b[l]; }
-    pd.ldx = widest + 4;  // + the K pad columns (K is swept four at a time); 16-row tiles
-  }
+  const PolicyDesc pd = b->critic.desc();  // (read only where there is a critic: checked above)
   if (want_value) HB_HIP(launch_value(pd, tapes->obs, nullptr, nullptr, rows + b->n_env, value, st));
   if (want_tv) {
     if (boot) HB_HIP(launch_value(pd, tapes->terminal_obs, tapes->terminated, tapes->truncated, rows, tv, st));

@@ -75,6 +75,62 @@ class DevBuf {
 template <class... B>
 void reset_all(B&... bufs) { (bufs.reset(), ...); }
 
+// The owner of one installed MLP as the 16-row fused kernels read it (hb_mlp_layers.inl): per layer the weights W[K][N] (row-major) in
+// the B-operand order of v_mfma_f32_16x16x4_f32 and the bias.  layers 0: none installed.
+struct DevMlp {
+  int layers = 0;
+  int sizes[5] = {0, 0, 0, 0, 0};
+  DevBuf<float> wp[4], b[4];
+
+  // wp[tile][k/4][lane] = W[4(k/4) + lane/16][16 tile + lane%16], zero padded: one coalesced 256-byte wave load per MFMA
+  static std::vector<float> pack_mfma_b(const float* W, int K, int N) {
+    const int KK = (K + 3) / 4, ntile = (N + 15) / 16;
+    std::vector<float> out((size_t)ntile * KK * 64, 0.f);
+    for (int nt = 0; nt < ntile; nt++)
+      for (int kk = 0; kk < KK; kk++)
+        for (int ln = 0; ln < 64; ln++) {
+          const int k = 4 * kk + (ln >> 4), n = 16 * nt + (ln & 15);
+          if (k < K && n < N) out[((size_t)nt * KK + kk) * 64 + ln] = W[(size_t)k * N + n];
+        }
+    return out;
+  }
+  void clear() {
+    layers = 0;
+    for (int l = 0; l < 4; l++) reset_all(wp[l], b[l]);
+  }
+  // Replaces the network (arguments checked by the caller: mlp_args_ok; nothing on the device still reads the old one).  Only the device
+  // can fail here, and then no network is installed.
+  int install(int n_layers, const int* sz, const float* const* weights, const float* const* biases) {
+    clear();
+    for (int l = 0; l < n_layers; l++) {
+      const std::vector<float> packed = pack_mfma_b(weights[l], sz[l], sz[l + 1]);
+      if (wp[l].alloc(packed.size()) != HB_OK || b[l].alloc(sz[l + 1]) != HB_OK) { clear(); return HB_ENOMEM; }
+      if (hipMemcpy(wp[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(b[l], biases[l], sz[l + 1] * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { clear(); return HB_ENODEVICE; }
+    }
+    for (int l = 0; l <= n_layers; l++) sizes[l] = sz[l];
+    layers = n_layers;
+    return HB_OK;
+  }
+  PolicyDesc desc() const {
+    PolicyDesc pd;
+    memset(&pd, 0, sizeof pd);
+    pd.nl = layers;
+    int widest = 1;
+    for (int l = 0; l <= layers; l++) { pd.sizes[l] = sizes[l]; widest = std::max(widest, sizes[l]); }
+    for (int l = 0; l < layers; l++) { pd.w[l] = wp[l]; pd.b[l] = b[l]; }
+    pd.ldx = widest + 4;  // + the K pad columns (K is swept four at a time); 16-row tiles
+    return pd;
+  }
+};
+// what every hb_*_set_mlp checks of its arrays before it touches the batch; the widths' upper limit and the end widths are the caller's
+inline bool mlp_args_ok(int n_layers, const int* sizes, const float* const* weights, const float* const* biases) {
+  if (!sizes || !weights || !biases || n_layers < 1 || n_layers > 4) return false;
+  for (int l = 0; l <= n_layers; l++) if (sizes[l] < 1) return false;
+  for (int l = 0; l < n_layers; l++) if (!weights[l] || !biases[l]) return false;
+  return true;
+}
+
 // One block of the device copies of a host call's arrays: count floats (none: the block is not there, and dev stays null), filled from
 // `up` before the launch where that is given and copied to `down` behind it where that is given.
 struct StageBlock {
@@ -190,27 +246,21 @@ struct hb_batch {
   int dr_stride = 0;
   DevBuf<uint8_t> d_rmask;     // hb_env_reset's pending-envs mask
   DevBuf<int> d_pending;
-  // policy MLP (hb_policy_*)
-  int mlp_layers = 0;
-  int mlp_sizes[5] = {0, 0, 0, 0, 0};
-  DevBuf<float> d_mlp_w[4];
-  DevBuf<float> d_mlp_wp[4];  // packed for hb_policy_kernel (all widths <= 256), else null
+  // policy MLP (hb_policy_*): the installed network; for a network with a width above 256, which takes one launch per layer instead of
+  // hb_policy_kernel, also the unpacked weights and the hidden activations (ping-pong), null otherwise
+  DevMlp policy;
   bool mlp_fused = false;
-  DevBuf<float> d_mlp_b[4];
-  DevBuf<float> d_mlp_h[2];  // hidden activations, ping-pong
+  DevBuf<float> d_mlp_w[4];
+  DevBuf<float> d_mlp_h[2];
   DevBuf<float> d_mlp_act;   // activation scratch of the LDS-free policy kernel: [n_env / 16 + kPipes][2][16][widest + 4]
-  // sampling actor (hb_actor_set_mlp, hb_env_collect_dev): packed weights and biases of hb_actor_kernel, the head, and the number of
-  // steps collected since the actor was installed (the step counter of its random draws)
-  int actor_layers = 0;  // 0: none installed
-  int actor_sizes[5] = {0, 0, 0, 0, 0};
-  DevBuf<float> d_actor_wp[4], d_actor_b[4];
+  // sampling actor (hb_actor_set_mlp, hb_env_collect_dev): the network of hb_actor_kernel, the head, and the number of steps collected
+  // since the actor was installed (the step counter of its random draws)
+  DevMlp actor;
   hb_actor_config actor_cfg = {};
   unsigned actor_draw0 = 0;
-  // critic (hb_critic_set_mlp, hb_collect_gae_dev): packed weights and biases of hb_value_kernel, and the scratch the value and terminal-value
-  // tapes go to when the caller gives none, [2 T + 1][n_env], grown on demand
-  int critic_layers = 0;  // 0: none installed
-  int critic_sizes[5] = {0, 0, 0, 0, 0};
-  DevBuf<float> d_critic_wp[4], d_critic_b[4];
+  // critic (hb_critic_set_mlp, hb_collect_gae_dev): the network of hb_value_kernel, and the scratch the value and terminal-value tapes go
+  // to when the caller gives none, [2 T + 1][n_env], grown on demand
+  DevMlp critic;
   DevBuf<float> d_gae;
   // normaliser (hb_norm_*): the double-buffered statistics record (slot norm_k is current; hb_device.hpp: NormDesc), the per-env
   // accumulators ret | ep_ret [2][n_env] and ep_len [n_env], and the chunk partials of a step; all null while none is configured

@@ -639,8 +639,7 @@ __global__ __launch_bounds__(kGroup) void hb_mlp_layer_kernel(const float* X, co
 // B operand from weights pre-packed on the host in operand order (one coalesced 256-byte wave load per MFMA:
 // wp[tile][k/4][lane] = W[4(k/4) + lane/16][16 tile + lane%16]).  A layer with fewer than eight tiles (the
 // nu-wide output layer) splits K across the idle waves instead; the partial tiles are summed in a fixed order
-// (deterministic, no atomics).
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+// (deterministic, no atomics).  The layer loop is hb_mlp_layers.inl, shared with hb_actor_kernel and hb_value_kernel.
 __global__ __launch_bounds__(512) void hb_policy_kernel(const DevModel M, const PolicyDesc pd, const float* state, float* ctrl, int n_env) {
   extern __shared__ float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -670,64 +669,15 @@ __global__ __launch_bounds__(512) void hb_policy_kernel(const DevModel M, const 
     }
   }
   __syncthreads();
-  const int col = lane & 15, quad = lane >> 4;  // A: row = col, k offset = quad;  B: k offset = quad, column = col;  D: rows 4 quad + r, column col
-  for (int l = 0; l < pd.nl; l++) {
-    const int K = pd.sizes[l], N = pd.sizes[l + 1], KK = (K + 3) / 4, ntile = (N + 15) / 16;
-    const bool last = l + 1 == pd.nl;
-    int S = 1;  // K slices per tile
-    while (S * 2 * ntile <= 8) S *= 2;
-    const float* wp = pd.w[l];
-    const float* bias = pd.b[l];
-    if (!last && tid < 48) nxt[(tid / 3) * ldx + N + tid % 3] = 0.f;  // pad columns of the next layer's input
-    for (int it = wave; it < ntile * S; it += 8) {
-      const int nt = it / S, sl = it - nt * S;
-      const int kb = KK * sl / S, ke = KK * (sl + 1) / S;
-      f32x4v D = {0.f, 0.f, 0.f, 0.f};
-      const float* ap = cur + col * ldx + quad;
-      const float* bp = wp + (size_t)nt * KK * 64 + lane;
-      int kk = kb;
-      for (; kk + 8 <= ke; kk += 8) {  // eight operand pairs in flight per batch of MFMAs
-        float a[8], w[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { a[u] = ap[4 * (kk + u)]; w[u] = bp[(size_t)(kk + u) * 64]; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) D = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u], D, 0, 0, 0);
-      }
-      for (; kk < ke; kk++) D = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[4 * kk], bp[(size_t)kk * 64], D, 0, 0, 0);
-      const int n = nt * 16 + col;
-      if (S == 1) {
-        const float bn = n < N ? bias[n] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int row = 4 * quad + r;
-          if (n < N) {
-            const float v = tanhf(D[r] + bn);
-            if (!last) nxt[row * ldx + n] = v;
-            else if (m0 + row < n_env) ctrl[(size_t)(m0 + row) * N + n] = v;
-          }
-        }
-      } else {
-        float* pp = part + it * 256;
-#pragma unroll
-        for (int r = 0; r < 4; r++) pp[(4 * quad + r) * 16 + col] = D[r];
-      }
-    }
-    __syncthreads();
-    if (S > 1) {
-      for (int idx = tid; idx < ntile * 256; idx += 512) {
-        const int nt = idx >> 8, rc = idx & 255, row = rc >> 4, n = nt * 16 + (rc & 15);
-        if (n < N) {
-          float v = bias[n];
-          for (int sl = 0; sl < S; sl++) v += part[(nt * S + sl) * 256 + rc];
-          v = tanhf(v);
-          if (!last) nxt[row * ldx + n] = v;
-          else if (m0 + row < n_env) ctrl[(size_t)(m0 + row) * N + n] = v;
-        }
-      }
-      __syncthreads();
-    }
-    float* t = cur; cur = nxt; nxt = t;
-  }
+  // tanh behind every layer; the last one's outputs are the controls of the rows that are envs
+#define HB_MLP_EMIT(row, n, v)                                                                     \
+  do {                                                                                             \
+    const float y_ = tanhf(v);                                                                     \
+    if (!last) nxt[(row) * ldx + (n)] = y_;                                                        \
+    else if (m0 + (row) < n_env) ctrl[(size_t)(m0 + (row)) * N + (n)] = y_;                        \
+  } while (0)
+#include "hb_mlp_layers.inl"
+#undef HB_MLP_EMIT
 }
 
 // The same policy without LDS and inside 64 VGPRs: four waves per block of sixteen envs, activations ping-pong through an L2-resident
@@ -775,7 +725,7 @@ __attribute__((amdgpu_num_vgpr(32))) __global__ __launch_bounds__(256) void hb_p
     // two output tiles per wave and pass: they share the A operand, and their accumulators are two independent MFMA chains
     for (int nt = 2 * wave; nt < ntile; nt += 8) {
       const bool two = nt + 1 < ntile;
-      f32x4v D0 = {0.f, 0.f, 0.f, 0.f}, D1 = {0.f, 0.f, 0.f, 0.f};
+      f32x4 D0 = {0.f, 0.f, 0.f, 0.f}, D1 = {0.f, 0.f, 0.f, 0.f};
       const float* ap = cur + lane;
       const float* bp0 = wp + (size_t)nt * KK * 64 + lane;
       const float* bp1 = bp0 + (two ? (size_t)KK * 64 : 0);

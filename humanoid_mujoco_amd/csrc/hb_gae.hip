@@ -10,8 +10,8 @@ namespace hb {
 // hb_actor_kernel's design (hb_actor.hip) on a row array [n_rows][nobs]: 16 rows per block, activations ping-pong between two LDS tiles,
 // eight waves share the 16-column output tiles of a layer, each sweeping K four columns per v_mfma_f32_16x16x4_f32 (exact f32), B operand
 // from the packed weights; a layer with fewer than eight tiles splits K across the idle waves and the partial tiles are summed in a fixed
-// order.  The layer loop is a COPY of hb_actor_kernel's, statement for statement (the same operations in the same order): moved into a
-// shared __device__ function, the actor compiled to 53 VGPRs instead of 50 (profiles/gae_kernel_resources.txt), so the actor keeps its own.
+// order.  The layer loop is hb_actor_kernel's: both include hb_mlp_layers.inl with the same hook (as text, not as a shared __device__
+// function, which cost the actor three registers: profiles/gae_kernel_resources.txt, profiles/mlp_shared_loop.txt).
 // What differs from the actor:
 //  - term / trunc null: every row is evaluated (the obs tape).  Both given: row i is evaluated where trunc[i] && !term[i] - the rows
 //    that are bootstrapped - and every other row is NOT READ (it holds stale or arbitrary data), loads as zeros and gets out[i] = 0; a
@@ -20,7 +20,6 @@ namespace hb {
 //    at the top).
 // A row's value does not depend on the other rows of its tile nor on where in the tile it stands (every D[i][j] of an MFMA is its own
 // chain over k), so V is the same bits however the rows are cut into batches.
-typedef float f32x4g __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(512) void hb_value_kernel(const PolicyDesc pd, const float* rows, const uint8_t* term, const uint8_t* trunc, long long n_rows, float* out) {
   extern __shared__ __attribute__((aligned(16))) float sm_value[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -47,60 +46,9 @@ __global__ __launch_bounds__(512) void hb_value_kernel(const PolicyDesc pd, cons
     if (tid < 48) cur[(tid / 3) * ldx + nobs + tid % 3] = 0.f;
   }
   __syncthreads();
-  const int col = lane & 15, quad = lane >> 4;  // A: row = col, k offset = quad;  B: k offset = quad, column = col;  D: rows 4 quad + r, column col
-  for (int l = 0; l < pd.nl; l++) {
-    const int K = pd.sizes[l], N = pd.sizes[l + 1], KK = (K + 3) / 4, ntile = (N + 15) / 16;
-    const bool last = l + 1 == pd.nl;
-    int S = 1;  // K slices per tile
-    while (S * 2 * ntile <= 8) S *= 2;
-    const float* wp = pd.w[l];
-    const float* bias = pd.b[l];
-    if (!last && tid < 48) nxt[(tid / 3) * ldx + N + tid % 3] = 0.f;  // pad columns of the next layer's input
-    for (int it = wave; it < ntile * S; it += 8) {
-      const int nt = it / S, sl = it - nt * S;
-      const int kb = KK * sl / S, ke = KK * (sl + 1) / S;
-      f32x4g D = {0.f, 0.f, 0.f, 0.f};
-      const float* ap = cur + col * ldx + quad;
-      const float* bp = wp + (size_t)nt * KK * 64 + lane;
-      int kk = kb;
-      for (; kk + 8 <= ke; kk += 8) {  // eight operand pairs in flight per batch of MFMAs
-        float a[8], w[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { a[u] = ap[4 * (kk + u)]; w[u] = bp[(size_t)(kk + u) * 64]; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) D = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u], D, 0, 0, 0);
-      }
-      for (; kk < ke; kk++) D = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[4 * kk], bp[(size_t)kk * 64], D, 0, 0, 0);
-      const int n = nt * 16 + col;
-      if (S == 1) {
-        if (n < N) {
-          const float bn = bias[n];
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const float v = D[r] + bn;
-            nxt[(4 * quad + r) * ldx + n] = last ? v : tanhf(v);
-          }
-        }
-      } else {
-        float* pp = part + it * 256;
-#pragma unroll
-        for (int r = 0; r < 4; r++) pp[(4 * quad + r) * 16 + col] = D[r];
-      }
-    }
-    __syncthreads();
-    if (S > 1) {
-      for (int idx = tid; idx < ntile * 256; idx += 512) {
-        const int nt = idx >> 8, rc = idx & 255, row = rc >> 4, n = nt * 16 + (rc & 15);
-        if (n < N) {
-          float v = bias[n];
-          for (int sl = 0; sl < S; sl++) v += part[(nt * S + sl) * 256 + rc];
-          nxt[row * ldx + n] = last ? v : tanhf(v);
-        }
-      }
-      __syncthreads();
-    }
-    float* t = cur; cur = nxt; nxt = t;
-  }
+#define HB_MLP_EMIT(row, n, v) nxt[(row) * ldx + (n)] = last ? (v) : tanhf(v)  // (the critic is linear at the top)
+#include "hb_mlp_layers.inl"
+#undef HB_MLP_EMIT
   // cur holds the last layer's output, column 0 of every row
   if (tid < live) out[m0 + tid] = (sel >> tid & 1u) ? cur[tid * ldx] : 0.f;
 }

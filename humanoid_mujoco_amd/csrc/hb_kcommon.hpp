@@ -59,6 +59,7 @@ __device__ __forceinline__ float uniformf(float v) { return __int_as_float(__bui
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));  // the accumulator of v_mfma_f32_16x16x4_f32 (hb_mlp_layers.inl, hb_policy_lean_kernel)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 

@@ -331,6 +331,24 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
+def _mlp_args(what, weights, biases, sizes=None):
+    """The arguments of hb_policy_set_mlp / hb_actor_set_mlp / hb_critic_set_mlp: (ws, bs, csizes, wp, bp) - the contiguous float32 arrays
+    (keep them alive across the call) and the ctypes arrays of the widths and of the weight and bias pointers.  sizes None: the widths
+    are the first weight's rows and every weight's columns.  Every layer's shape is checked, so the library never reads past an array."""
+    ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
+    bs = [np.ascontiguousarray(x, dtype=np.float32) for x in biases]
+    if sizes is None:  # (a weight that is no matrix leaves the list short, and fails the check below)
+        sizes = [w.shape[0] for w in ws[:1] if w.ndim == 2] + [w.shape[1] for w in ws if w.ndim == 2]
+    sizes = [int(s) for s in sizes]
+    if len(ws) != len(sizes) - 1 or len(bs) != len(ws) or any(w.shape != (a, c) for w, a, c in zip(ws, sizes[:-1], sizes[1:])) or \
+            any(x.shape != (c,) for x, c in zip(bs, sizes[1:])):
+        raise ValueError("%s: weights[l] must be [sizes[l], sizes[l+1]] and biases[l] [sizes[l+1]]" % what)
+    csz = (ctypes.c_int * len(sizes))(*sizes)
+    wp = (ctypes.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+    bp = (ctypes.c_void_p * len(bs))(*[x.ctypes.data for x in bs])
+    return ws, bs, csz, wp, bp
+
+
 class _Pinned:
     """numpy array over page-locked host memory (hb_host_alloc): copies to and from it are DMA transfers."""
 
@@ -1157,12 +1175,8 @@ class Batch:
     # ---- policy in the loop (BASELINE config 4)
     def set_policy_mlp(self, weights, biases):
         """weights[l]: [in, out] float32 (transpose of torch.nn.Linear.weight); tanh after every layer."""
-        ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
-        bs = [np.ascontiguousarray(x, dtype=np.float32) for x in biases]
-        sizes = (ctypes.c_int * (len(ws) + 1))(*([ws[0].shape[0]] + [w.shape[1] for w in ws]))
-        wp = (ctypes.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
-        bp = (ctypes.c_void_p * len(bs))(*[x.ctypes.data for x in bs])
-        _check(lib().hb_policy_set_mlp(self._h, len(ws), sizes, wp, bp), "hb_policy_set_mlp")
+        ws, bs, csz, wp, bp = _mlp_args("set_policy_mlp", weights, biases)
+        _check(lib().hb_policy_set_mlp(self._h, len(ws), csz, wp, bp), "hb_policy_set_mlp")
 
     def policy_eval(self):
         out = np.zeros((self.n_env, self.model.nu), dtype=np.float32)
@@ -1179,12 +1193,7 @@ class Batch:
         (tanh output, no sampling), "gaussian" (linear mean, state-independent log_std [nu]: SB3 PPO / A2C) or "squashed" (linear
         mean | log_std, clamped to [-20, 2], tanh of the sample: SB3 SAC), or the ACTOR_* value.  At most four layers of width <= 256."""
         head = ACTOR_HEADS[head] if isinstance(head, str) else int(head)
-        sizes = [int(s) for s in sizes]
-        ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
-        bs = [np.ascontiguousarray(x, dtype=np.float32) for x in biases]
-        if len(ws) != len(sizes) - 1 or len(bs) != len(ws) or any(w.shape != (a, c) for w, a, c in zip(ws, sizes[:-1], sizes[1:])) or \
-                any(x.shape != (c,) for x, c in zip(bs, sizes[1:])):
-            raise ValueError("actor_set: weights[l] must be [sizes[l], sizes[l+1]] and biases[l] [sizes[l+1]]")
+        ws, bs, csz, wp, bp = _mlp_args("actor_set", weights, biases, sizes)
         cfg = HbActorConfig()
         cfg.head, cfg.seed, cfg.deterministic = head, int(seed) & 0xFFFFFFFF, int(bool(deterministic))
         if log_std is not None:
@@ -1192,9 +1201,6 @@ class Batch:
             if len(ls) > 32:
                 raise ValueError("actor_set: log_std holds at most 32 actuators")
             cfg.log_std[:len(ls)] = [float(x) for x in ls]
-        csz = (ctypes.c_int * len(sizes))(*sizes)
-        wp = (ctypes.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
-        bp = (ctypes.c_void_p * len(bs))(*[x.ctypes.data for x in bs])
         rc = lib().hb_actor_set_mlp(self._h, len(ws), csz, wp, bp, ctypes.byref(cfg))
         _check(rc, "hb_actor_set_mlp", "a layer wider than 256: the actor is one fused kernel, there is no layer-by-layer path" if rc == -4 else
                "sizes must run from nobs to nu (squashed: 2 nu) over 1..4 layers, nu <= 32, log_std finite" if rc == -1 else None)
@@ -1214,15 +1220,7 @@ class Batch:
         """Installs the critic.  sizes: [nobs, hidden..., 1]; weights[l]: [sizes[l], sizes[l+1]] float32 - the TRANSPOSE of
         torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; tanh after every hidden layer, the last layer linear.  At most four layers of
         width <= 256.  Independent of the actor and of the policy MLP."""
-        sizes = [int(s) for s in sizes]
-        ws = [np.ascontiguousarray(w, dtype=np.float32) for w in weights]
-        bs = [np.ascontiguousarray(x, dtype=np.float32) for x in biases]
-        if len(ws) != len(sizes) - 1 or len(bs) != len(ws) or any(w.shape != (a, c) for w, a, c in zip(ws, sizes[:-1], sizes[1:])) or \
-                any(x.shape != (c,) for x, c in zip(bs, sizes[1:])):
-            raise ValueError("critic_set: weights[l] must be [sizes[l], sizes[l+1]] and biases[l] [sizes[l+1]]")
-        csz = (ctypes.c_int * len(sizes))(*sizes)
-        wp = (ctypes.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
-        bp = (ctypes.c_void_p * len(bs))(*[x.ctypes.data for x in bs])
+        ws, bs, csz, wp, bp = _mlp_args("critic_set", weights, biases, sizes)
         rc = lib().hb_critic_set_mlp(self._h, len(ws), csz, wp, bp)
         _check(rc, "hb_critic_set_mlp", "a layer wider than 256: the critic is one fused kernel, there is no layer-by-layer path" if rc == -4 else
                "sizes must run from nobs to 1 over 1..4 layers" if rc == -1 else None)

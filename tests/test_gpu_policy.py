@@ -123,6 +123,30 @@ def test_policy_argument_checks(hbmod, humanoid_model, gpu):
         b.set_policy_mlp([np.zeros((m.nobs + 1, m.nu), np.float32)], [np.zeros(m.nu, np.float32)])  # wrong input width
 
 
+def test_refused_install_leaves_policy_intact(hbmod, humanoid_model, gpu):
+    """hb_policy_set_mlp checks every argument before it touches the batch: a call refused for a null weights[1] - the same sizes, other
+    weights - leaves the installed policy as it was, bit for bit (37 envs: a partial 16-row tile)."""
+    import ctypes
+    m = humanoid_model
+    sizes = [m.nobs, 33, m.nu]
+
+    def net(seed):
+        rng = np.random.default_rng(seed)
+        return ([rng.uniform(-0.3, 0.3, size=(a, c)).astype(np.float32) for a, c in zip(sizes[:-1], sizes[1:])],
+                [rng.uniform(-0.3, 0.3, size=c).astype(np.float32) for c in sizes[1:]])
+    b = hbmod.Batch(m, 37, gpu)
+    b.reset(perturb=True)
+    b.set_policy_mlp(*net(1))
+    kept = b.policy_eval()
+    assert np.abs(kept).std() > 0.01
+    ws, bs = net(2)
+    csz = (ctypes.c_int * 3)(*sizes)
+    wp = (ctypes.c_void_p * 2)(ws[0].ctypes.data, None)
+    bp = (ctypes.c_void_p * 2)(*[x.ctypes.data for x in bs])
+    assert hbmod.lib().hb_policy_set_mlp(b._h, 2, csz, wp, bp) == -1  # HB_EINVAL
+    assert np.array_equal(b.policy_eval(), kept)
+
+
 def _fixture_policy():
     import os
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "policy_mlp_seed0.npz"))
