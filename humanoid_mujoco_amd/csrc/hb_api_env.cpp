@@ -467,6 +467,13 @@ int hb_rollout_policy(hb_batch* b, int T, float* qpos_out_dev) {
 
 // ---- actor and rollout collection
 
+// the sizes of an installed network are those of the arguments (a learner on the batch keeps its state then: learner_net_replaced)
+static bool mlp_same_shape(const DevMlp& n, int n_layers, const int* sizes) {
+  if (n.layers != n_layers) return false;
+  for (int l = 0; l <= n_layers; l++) if (n.sizes[l] != sizes[l]) return false;
+  return true;
+}
+
 int hb_actor_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases, const hb_actor_config* cfg) {
   if (!b || !cfg || !mlp_args_ok(n_layers, sizes, weights, biases)) return HB_EINVAL;
   const int nu = b->D.dm.nu;
@@ -480,10 +487,11 @@ int hb_actor_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* c
   HB_HIP(hipSetDevice(b->device));
   HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a collection still in flight reads the buffers that are replaced below)
   // (every argument check is behind us: from here on only the device can fail, and then no actor is installed)
-  if ((rc = b->actor.install(n_layers, sizes, weights, biases)) != HB_OK) return rc;
+  const bool same = mlp_same_shape(b->actor, n_layers, sizes);
+  if ((rc = b->actor.install(n_layers, sizes, weights, biases)) != HB_OK) { b->learner.clear(); return rc; }
   b->actor_cfg = *cfg;
   b->actor_draw0 = 0;
-  return HB_OK;
+  return learner_net_replaced(b, 0, same);
 }
 
 static int norm_step_impl(hb_batch* b, const hb_norm_io& io);
@@ -499,6 +507,7 @@ static int collect_impl(hb_batch* b, int T, int n_substeps, const hb_collect_out
   const DevModel& dm = b->D.dm;
   const size_t n = b->n_env, nu = dm.nu, nobs = dm.nobs;
   if (out->terminal_obs && !b->d_term_obs && (rc = hb_env_terminal_obs(b, nullptr)) != HB_OK) return rc;
+  if ((rc = learner_sync_log_std(b)) != HB_OK) return rc;  // (a learner's Adam steps moved log_std on the device: hb_ppo_adam_dev)
   ActorDesc ad;
   memset(&ad, 0, sizeof ad);
   ad.net = b->actor.desc();
@@ -549,7 +558,12 @@ int hb_critic_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* 
   HB_HIP(hipSetDevice(b->device));
   HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a call still in flight reads the buffers that are replaced below)
   // (every argument check is behind us: from here on only the device can fail, and then no critic is installed)
-  return b->critic.install(n_layers, sizes, weights, biases);
+  const bool same = mlp_same_shape(b->critic, n_layers, sizes);
+  int rc = learner_sync_log_std(b);  // (whatever becomes of a learner below, the actor keeps the log_std it trained)
+  if (rc != HB_OK) return rc;
+  rc = b->critic.install(n_layers, sizes, weights, biases);
+  if (rc != HB_OK) { b->learner.clear(); return rc; }
+  return learner_net_replaced(b, 1, same);
 }
 
 int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb_gae_config* cfg, const hb_gae_out* out) {
@@ -600,6 +614,8 @@ int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb
     HB_HIP(launch_gae_scan(g, st));
   }
   if (out->log_prob) {
+    const int rc = learner_sync_log_std(b);  // (as in the collection)
+    if (rc != HB_OK) return rc;
     LogProbDesc d;
     memset(&d, 0, sizeof d);
     d.head = head; d.nu = b->D.dm.nu;

@@ -131,6 +131,30 @@ inline bool mlp_args_ok(int n_layers, const int* sizes, const float* const* weig
   return true;
 }
 
+// The PPO learner of a batch (hb_learner_*, hb_api_ppo.cpp): the trainable parameters as ONE flat record (include/hb.h: the actor's layers
+// W | b, log_std, the critic's layers), the gradient and the Adam moments in the same layout, the packed transposes of the weights the
+// backward pass multiplies by (layer 0 needs none), and the scratch of a minibatch.  The forward operands stay where they are: in the
+// batch's actor and critic (DevMlp), which hb_ppo_adam_kernel refreshes entry by entry.
+struct Learner {
+  bool on = false;
+  hb_ppo_config cfg = {};
+  int P = 0, off_log_std = 0;
+  int off_w[2][4] = {}, off_b[2][4] = {};
+  long long calls = 0;         // Adam calls since t was last set; t = calls - the device's count of skipped steps
+  bool log_std_dirty = false;  // the device's log_std is newer than actor_cfg.log_std
+  DevBuf<float> d_param, d_grad, d_m, d_v, d_zero, d_wt[2][4];
+  DevBuf<float> d_scratch;     // activations, dZ, outputs and the by-row terms of a minibatch: grows with mb
+  DevBuf<float> d_part;        // [64][P] chunk partials of the gradient
+  DevBuf<double> d_dbl;        // advpart [64][2] | statpart [64][8] | normpart
+  DevBuf<int> d_nskip;
+  void clear() {
+    on = false; P = 0; calls = 0; log_std_dirty = false;
+    reset_all(d_param, d_grad, d_m, d_v, d_zero, d_scratch, d_part, d_dbl);
+    d_nskip.reset();
+    for (int k = 0; k < 2; k++) for (int l = 0; l < 4; l++) d_wt[k][l].reset();
+  }
+};
+
 // One block of the device copies of a host call's arrays: count floats (none: the block is not there, and dev stays null), filled from
 // `up` before the launch where that is given and copied to `down` behind it where that is given.
 struct StageBlock {
@@ -262,6 +286,8 @@ struct hb_batch {
   // to when the caller gives none, [2 T + 1][n_env], grown on demand
   DevMlp critic;
   DevBuf<float> d_gae;
+  // PPO learner (hb_learner_create): off until created
+  Learner learner;
   // normaliser (hb_norm_*): the double-buffered statistics record (slot norm_k is current; hb_device.hpp: NormDesc), the per-env
   // accumulators ret | ep_ret [2][n_env] and ep_len [n_env], and the chunk partials of a step; all null while none is configured
   bool norm_on = false;
@@ -327,5 +353,9 @@ int launch_segment(hb_batch* b, BatchPtrs P, int nsteps, const Segment& sg, int 
 void steps_enqueued(hb_batch* b, int nseg, bool reorder, bool refreshed = false);
 int launch_steps(hb_batch* b, BatchPtrs& P, int nsteps, bool foldable = false);
 int rollout_open(hb_batch* b, const float* ctrl, int T, bool want_qpos);
+// the learner's hooks in the calls that read or replace what it trains (hb_api_ppo.cpp): before a descriptor with log_std is built;
+// behind hb_actor_set_mlp / hb_critic_set_mlp (net 0 / 1) once the new network is installed, shapes_same telling whether the sizes stayed
+int learner_sync_log_std(hb_batch* b);
+int learner_net_replaced(hb_batch* b, int net, bool shapes_same);
 }  // namespace hb
 #pragma GCC visibility pop

@@ -306,6 +306,57 @@ struct NormDesc {
   int* ep_length_out;
 };
 
+// hb_ppo_* (hb_ppo.hip): the learner.  Every reduction over the minibatch rows - dW, db, dlog_std, the advantage moments, the loss
+// statistics - goes over chunks of ppo_row_chunk(mb) consecutive minibatch rows, chunk c = rows [c chunk, (c + 1) chunk), whose partials
+// are merged in chunk order: 64 rows up to 4096, beyond that mb / 64 rounded up to whole 16-row tiles (never more than 64 chunks, which
+// bounds the partial gradients at 64 P floats).  The gradient norm goes over chunks of kPpoNormChunk entries of the flat record.
+constexpr int kPpoNormChunk = 4096;
+constexpr int kPpoMaxSeg = 17;  // tensors of the flat record: 2 x 4 x (W, b) + log_std
+__host__ __device__ inline int ppo_row_chunk(int mb) { return mb <= 4096 ? 64 : ((mb + 63) / 64 + 15) / 16 * 16; }
+// LDS row stride of a 16-row operand tile of hb_ppo_wgrad_kernel: whole 16-column tiles, and 16 mod 32 so that the four rows a wave
+// reads in one MFMA operand fall on different banks
+__host__ __device__ inline int ppo_ld(int w) { const int p = (w + 15) / 16 * 16; return p % 32 == 0 ? p + 16 : p; }
+struct PpoNet {
+  PolicyDesc fwd;   // the packed operands the forward kernels read (DevMlp)
+  PolicyDesc bwd;   // dA = dZ W^T as the same layer loop: nl = L - 1, the widths in reverse, w[j] = the packed transpose of layer L - 1 - j, b = zeros
+  float* act[4];    // act[l] [mb][sizes[l]]: the input of layer l (act[0]: the gathered observations, shared by both networks)
+  float* dz[4];     // dz[l] [mb][sizes[l + 1]]: dloss / d(pre-activation of layer l)
+  float* out;       // [mb][sizes[L]]: the last layer's output (mean, value)
+  int off_w[4], off_b[4];  // where W_l and b_l stand in the flat record
+};
+struct PpoDesc {
+  PpoNet net[2];    // actor, critic
+  const float *obs, *action, *old_log_prob, *advantage, *returns;
+  const int* index; // null: rows first .. first + mb - 1
+  long long first;
+  int mb, nobs, nu, chunk, nchunk, P, off_log_std, normalize;
+  float clip_range, ent_coef, vf_coef;
+  const float* param;  // the flat record (log_std is read from it)
+  float* gls;          // [mb][nu] dloss / dlog_std by row
+  float* srow;         // [mb][5] by row: the terms of policy_loss, value_loss, approx_kl, clip_fraction, and the ratio
+  double* advpart;     // [nchunk][2] sum and sum of squares of the chunk's advantages
+  double* statpart;    // [nchunk][8] the chunk's sums of srow (the ratio: its maximum)
+  float* part;         // [nchunk][P] the chunk's gradients
+  float* grad;         // [P]
+  float* stats;        // [16] or null
+};
+struct PpoSeg {
+  int start, K, N;     // flat offset; W[K][N], or K = 0: a vector of N
+  float* dst;          // W: the packed B operand of the forward pass; vector: its copy (null: none)
+  float* dst_t;        // W: the packed B operand of W^T (null: layer 0, which needs none)
+};
+struct PpoAdamDesc {
+  int P, nseg, nnorm;
+  PpoSeg seg[kPpoMaxSeg];
+  float *param, *m, *v;
+  const float* grad;
+  double* normpart;    // [nnorm]
+  int* nskip;          // skipped steps since t was last set
+  long long calls;     // t = calls - *nskip (this step included)
+  float lr, beta1, beta2, eps, max_grad_norm;
+  float* stats;
+};
+
 // Buffers of the STAGED step of the general variants (launch_step): hb_pose_kernel writes every geom's world pose and the env's
 // narrowphase work items, hb_narrow_kernel evaluates the items (one per lane, at the occupancy of a small kernel: the MPR climbs are
 // chains of dependent loads), the step kernel appends the results in item order.  All null: the step kernel does all of it itself.

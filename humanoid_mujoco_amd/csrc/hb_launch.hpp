@@ -69,6 +69,11 @@ hipError_t launch_log_prob(const LogProbDesc& d, long long n_rows, hipStream_t s
 // the normaliser (hb_norm.hip): the chunk partials of a step or reset (and the per-env accumulators), then the merge and the normalisation
 hipError_t launch_norm_moments(const NormDesc& d, hipStream_t stream);
 hipError_t launch_norm_apply(const NormDesc& d, hipStream_t stream);
+// the learner (hb_ppo.hip): the five launches of hb_ppo_grad_dev - forward with kept activations (and the advantage partials), the head
+// (loss terms and the top gradients by row), the back-propagation of dZ through the layers, the chunk partials of dW / db / dlog_std
+// and the statistics - and their merge; then the two of hb_ppo_adam_dev - the norm partials, and clipping + Adam + operand refresh
+hipError_t launch_ppo_grad(const PpoDesc& d, hipStream_t stream);
+hipError_t launch_ppo_adam(const PpoAdamDesc& d, hipStream_t stream);
 // order: [2 * n_env] ints - the permutation, then the sort keys of the pass (read once from counts)
 hipError_t launch_order(const int* counts, int* order, int n_env, int e0, int n, hipStream_t stream, int slot = 3, int shift = 3);
 hipError_t launch_mlp_layer(const float* X, const float* W, const float* bias, float* Y, int Mrows, int K, int N, int act, hipStream_t stream);

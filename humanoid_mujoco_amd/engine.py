@@ -176,6 +176,66 @@ class HbNormTapes(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("raw_obs", "raw_reward", "ep_return", "ep_length")]
 
 
+class HbPpoConfig(ctypes.Structure):
+    """hb_ppo_config (include/hb.h): the hyper-parameters of the PPO learner, stable-baselines3's defaults."""
+    _fields_ = [("clip_range", ctypes.c_float), ("ent_coef", ctypes.c_float), ("vf_coef", ctypes.c_float), ("max_grad_norm", ctypes.c_float),
+                ("normalize_advantage", ctypes.c_int), ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("eps", ctypes.c_float)]
+
+
+class HbPpoRows(ctypes.Structure):
+    """hb_ppo_rows (include/hb.h): device pointers of the flattened tapes, and the minibatch (index, or first .. first + mb - 1)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("obs", "action", "old_log_prob", "advantage", "returns", "index")] + \
+               [("n_rows", ctypes.c_longlong), ("first", ctypes.c_longlong), ("mb", ctypes.c_int)]
+
+
+# the statistics hb_ppo_grad_dev / hb_ppo_adam_dev leave in their float[16] (include/hb.h), in order
+PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction", "grad_norm", "adv_mean", "adv_std", "ratio_max",
+             "skipped")
+
+
+def ppo_flat_shapes(actor_sizes, critic_sizes, nu):
+    """The tensors of the learner's flat record in order, as (name, shape): the actor's layers W [K, N] | b [N], log_std [nu], the critic's
+    layers (include/hb.h: hb_learner_get_params)."""
+    out = []
+    for tag, sizes in (("actor", actor_sizes), ("critic", critic_sizes)):
+        for l in range(len(sizes) - 1):
+            out += [("%s.w%d" % (tag, l), (int(sizes[l]), int(sizes[l + 1]))), ("%s.b%d" % (tag, l), (int(sizes[l + 1]),))]
+        if tag == "actor":
+            out.append(("log_std", (int(nu),)))
+    return out
+
+
+def ppo_split(flat, actor_sizes, critic_sizes, nu):
+    """The flat record as a dict of per-tensor arrays (copies): actor.w0, actor.b0, ..., log_std, critic.w0, ..."""
+    flat = np.asarray(flat)
+    shapes = ppo_flat_shapes(actor_sizes, critic_sizes, nu)
+    if flat.shape != (sum(int(np.prod(sh)) for _, sh in shapes),):
+        raise ValueError("ppo_split: the record of these networks holds %d values" % sum(int(np.prod(sh)) for _, sh in shapes))
+    out, o = {}, 0
+    for name, sh in shapes:
+        n = int(np.prod(sh))
+        out[name] = flat[o:o + n].reshape(sh).copy()
+        o += n
+    return out
+
+
+def ppo_join(tensors, actor_sizes, critic_sizes, nu, dtype=np.float32):
+    """The inverse of ppo_split."""
+    parts = []
+    for name, sh in ppo_flat_shapes(actor_sizes, critic_sizes, nu):
+        a = np.asarray(tensors[name], dtype=dtype)
+        if a.shape != sh:
+            raise ValueError("ppo_join: %s must be %s" % (name, sh))
+        parts.append(a.ravel())
+    return np.concatenate(parts)
+
+
+def ppo_row_chunk(mb):
+    """Rows per chunk of the learner's row reductions for a minibatch of mb rows (hb_ppo_row_chunk)."""
+    return int(lib().hb_ppo_row_chunk(int(mb)))
+
+
 class HbError(RuntimeError):
     pass
 
@@ -298,6 +358,20 @@ def lib():
     L.hb_norm_reset_dev.argtypes = [vp, vp, vp]
     L.hb_norm_obs_dev.argtypes = [vp, vp, vp, ctypes.c_longlong]
     L.hb_env_collect_norm_dev.argtypes = [vp, ci, ci, ctypes.POINTER(HbCollectOut), ctypes.POINTER(HbNormTapes)]
+    L.hb_ppo_default_config.argtypes = [ctypes.POINTER(HbPpoConfig)]
+    L.hb_ppo_row_chunk.argtypes = [ci]
+    L.hb_learner_create.argtypes = [vp, ctypes.POINTER(HbPpoConfig)]
+    L.hb_learner_configure.argtypes = [vp, ctypes.POINTER(HbPpoConfig)]
+    L.hb_learner_destroy.argtypes = [vp]
+    L.hb_learner_param_count.argtypes = [vp]; L.hb_learner_param_count.restype = ctypes.c_longlong
+    L.hb_learner_get_params.argtypes = [vp, vp, ctypes.c_longlong]; L.hb_learner_set_params.argtypes = [vp, vp, ctypes.c_longlong]
+    L.hb_learner_get_grads.argtypes = [vp, vp, ctypes.c_longlong]
+    L.hb_learner_get_state.argtypes = [vp, vp, vp, vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
+    L.hb_learner_set_state.argtypes = [vp, vp, vp, vp, ctypes.c_longlong, ctypes.c_longlong]
+    L.hb_learner_grad_dev.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_longlong)]
+    L.hb_ppo_grad_dev.argtypes = [vp, ctypes.POINTER(HbPpoRows), vp]
+    L.hb_ppo_adam_dev.argtypes = [vp, vp]
+    L.hb_ppo_minibatch_dev.argtypes = [vp, ctypes.POINTER(HbPpoRows), vp]
     L.hb_dev_alloc.restype = vp; L.hb_dev_alloc.argtypes = [vp, ctypes.c_uint64]
     L.hb_dev_free.restype = None; L.hb_dev_free.argtypes = [vp, vp]
     L.hb_host_alloc.restype = vp; L.hb_host_alloc.argtypes = [ctypes.c_uint64]
@@ -1236,6 +1310,99 @@ class Batch:
         rc = lib().hb_collect_gae_dev(self._h, int(T), ctypes.byref(tapes), ctypes.byref(cfg), ctypes.byref(out))
         _check(rc, "hb_collect_gae_dev", "needs T >= 1, gamma and lam in [0, 1], at least one output, the tapes each output reads, a critic "
                "(critic_set) for the value outputs and a sampling actor (actor_set, not the deterministic head) for log_prob" if rc == -1 else None)
+
+    # ---- the PPO learner (include/hb.h: hb_learner_*, hb_ppo_*)
+    _PPO_WHY = "needs a learner (learner_create), the five tapes, 1 <= mb, and first + mb <= n_rows without an index"
+
+    def _ppo_config(self, what, cfg, base=None):
+        c = HbPpoConfig()
+        if base is not None:
+            ctypes.memmove(ctypes.byref(c), ctypes.byref(base), ctypes.sizeof(c))
+        else:
+            _check(lib().hb_ppo_default_config(ctypes.byref(c)), "hb_ppo_default_config")
+        names = dict(HbPpoConfig._fields_)
+        for k, v in cfg.items():
+            if k not in names:
+                raise ValueError("%s: unknown hyper-parameter %r (one of %s)" % (what, k, ", ".join(names)))
+            setattr(c, k, int(bool(v)) if k == "normalize_advantage" else float(v))
+        return c
+
+    def learner_create(self, **cfg):
+        """Creates the PPO learner over the installed actor (Gaussian head) and critic: they become the trainable parameters, with Adam
+        moments of zero and t = 0.  cfg: clip_range, ent_coef, vf_coef, max_grad_norm, normalize_advantage, lr, beta1, beta2, eps
+        (stable-baselines3's defaults where not given)."""
+        c = self._ppo_config("learner_create", cfg)
+        rc = lib().hb_learner_create(self._h, ctypes.byref(c))
+        _check(rc, "hb_learner_create", "the learner trains the Gaussian head only: the deterministic head has no density, and the squashed head "
+               "(SAC's actor) belongs to an off-policy learner" if rc == -4 else
+               "needs an actor and a critic, clip_range > 0, betas in [0, 1), lr >= 0, eps > 0, all finite" if rc == -1 else None)
+        self._ppo_cfg = c
+
+    def learner_configure(self, **cfg):
+        """Changes hyper-parameters (schedules of lr or clip_range) and keeps parameters, moments and t; those not named stay."""
+        c = self._ppo_config("learner_configure", cfg, getattr(self, "_ppo_cfg", None))
+        _check(lib().hb_learner_configure(self._h, ctypes.byref(c)), "hb_learner_configure",
+               "needs a learner, clip_range > 0, betas in [0, 1), lr >= 0, eps > 0, all finite")
+        self._ppo_cfg = c
+
+    def learner_destroy(self):
+        _check(lib().hb_learner_destroy(self._h), "hb_learner_destroy", "no learner")
+
+    def learner_param_count(self):
+        n = lib().hb_learner_param_count(self._h)
+        _check(0 if n >= 0 else int(n), "hb_learner_param_count", "no learner")
+        return int(n)
+
+    def learner_params(self):
+        """the parameters as the flat float32 record (ppo_split gives the per-layer arrays)"""
+        out = np.zeros(self.learner_param_count(), dtype=np.float32)
+        _check(lib().hb_learner_get_params(self._h, _ptr(out), out.size), "hb_learner_get_params")
+        return out
+
+    def learner_set_params(self, flat):
+        a = np.ascontiguousarray(flat, dtype=np.float32)
+        _check(lib().hb_learner_set_params(self._h, _ptr(a), a.size if a.ndim == 1 else -1), "hb_learner_set_params",
+               "needs a learner and a flat record of learner_param_count() values")
+
+    def learner_grads(self):
+        out = np.zeros(self.learner_param_count(), dtype=np.float32)
+        _check(lib().hb_learner_get_grads(self._h, _ptr(out), out.size), "hb_learner_get_grads")
+        return out
+
+    def learner_state(self):
+        """{"params", "m", "v": flat float32 records, "t": Adam's step count}: checkpoint of the learner"""
+        n = self.learner_param_count()
+        p, m, v = (np.zeros(n, dtype=np.float32) for _ in range(3))
+        t = ctypes.c_longlong()
+        _check(lib().hb_learner_get_state(self._h, _ptr(p), _ptr(m), _ptr(v), n, ctypes.byref(t)), "hb_learner_get_state")
+        return {"params": p, "m": m, "v": v, "t": int(t.value)}
+
+    def learner_set_state(self, state):
+        p, m, v = (np.ascontiguousarray(state[k], dtype=np.float32) for k in ("params", "m", "v"))
+        n = p.size if p.ndim == 1 and p.shape == m.shape == v.shape else -1
+        _check(lib().hb_learner_set_state(self._h, _ptr(p), _ptr(m), _ptr(v), n, int(state["t"])), "hb_learner_set_state",
+               "needs a learner, three flat records of learner_param_count() values and t >= 0")
+
+    def learner_grad_dev(self):
+        """(device pointer, count) of the gradient buffer, flat layout: what a multi-GPU caller all-reduces between ppo_grad_dev and ppo_adam_dev"""
+        p, n = ctypes.c_void_p(), ctypes.c_longlong()
+        _check(lib().hb_learner_grad_dev(self._h, ctypes.byref(p), ctypes.byref(n)), "hb_learner_grad_dev", "no learner")
+        return p.value, int(n.value)
+
+    def ppo_grad_dev(self, obs, action, old_log_prob, advantage, returns, n_rows, mb, index=None, first=0, stats=None):
+        """hb_ppo_grad_dev: loss, statistics and gradients of one minibatch, enqueued on the batch's stream.  Device pointers of the
+        flattened tapes ([n_rows, ...]); index: device int32 [mb], or None for rows first .. first + mb - 1; stats: device float32 [16]."""
+        rows = HbPpoRows(obs, action, old_log_prob, advantage, returns, index, int(n_rows), int(first), int(mb))
+        _check(lib().hb_ppo_grad_dev(self._h, ctypes.byref(rows), ctypes.c_void_p(stats or 0)), "hb_ppo_grad_dev", self._PPO_WHY)
+
+    def ppo_adam_dev(self, stats=None):
+        """hb_ppo_adam_dev: global-norm clipping and the Adam step on the gradient buffer; the next collection runs the new parameters."""
+        _check(lib().hb_ppo_adam_dev(self._h, ctypes.c_void_p(stats or 0)), "hb_ppo_adam_dev", "no learner")
+
+    def ppo_minibatch_dev(self, obs, action, old_log_prob, advantage, returns, n_rows, mb, index=None, first=0, stats=None):
+        """hb_ppo_minibatch_dev: ppo_grad_dev, then ppo_adam_dev."""
+        rows = HbPpoRows(obs, action, old_log_prob, advantage, returns, index, int(n_rows), int(first), int(mb))
+        _check(lib().hb_ppo_minibatch_dev(self._h, ctypes.byref(rows), ctypes.c_void_p(stats or 0)), "hb_ppo_minibatch_dev", self._PPO_WHY)
 
     # ---- running observation / reward normalisation and episode statistics (include/hb.h: hb_norm_*)
     _NORM_WHY = "needs a normaliser (norm_configure) and the required device pointers"

@@ -567,6 +567,85 @@ class VecEnv:
         """collect_torch with numpy arrays: the same dict, copied to the host (one synchronisation at the end)."""
         return {k: v.cpu().numpy() for k, v in self.collect_torch(T, obs0=obs0, terminal_obs=terminal_obs, gae=gae, raw=raw).items()}
 
+    # ---- the PPO learner on the device (Batch.learner_create, ppo_minibatch_dev)
+    def learner(self, **cfg):
+        """Creates the PPO learner over the networks of actor_set (Gaussian head) and critic_set, which become the trainable parameters:
+        what collect_torch runs afterwards is whatever ppo_update left.  cfg: clip_range, ent_coef, vf_coef, max_grad_norm,
+        normalize_advantage, lr, beta1, beta2, eps - stable-baselines3's defaults where not given (Batch.learner_configure changes them
+        later, e.g. for a learning-rate schedule)."""
+        self.batch.learner_create(**cfg)
+        self._ppo_updates = self._ppo_epochs = 0
+
+    def ppo_minibatches(self, n_rows, batch_size, n_epochs, seed=None, update=None):
+        """The minibatches ppo_update visits: a list, one entry per epoch, of (perm, [(start, mb), ...]) - perm a CUDA int32 permutation of the
+        n_rows rows drawn with torch.randperm from a device generator seeded by (seed, update), one draw per epoch in order; minibatch k
+        of the epoch is perm[start:start + mb]: consecutive stretches of batch_size, the last one shorter."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        seed = self.seed_value if seed is None else int(seed)
+        update = getattr(self, "_ppo_updates", 0) if update is None else int(update)
+        g = torch.Generator(device=dev)
+        g.manual_seed((seed * 1000003 + update) % (1 << 62))
+        cuts = [(s0, min(int(batch_size), n_rows - s0)) for s0 in range(0, n_rows, int(batch_size))]
+        return [(torch.randperm(n_rows, generator=g, device=dev).to(torch.int32), cuts) for _ in range(int(n_epochs))]
+
+    def ppo_update(self, buf, n_epochs=10, batch_size=64, target_kl=None, seed=None):
+        """stable-baselines3's PPO.train over the dict collect_torch(T, gae=...) returned, on the device: the first T rows of its tapes are
+        flattened to T n rows (views, no copy), and every epoch visits them in the minibatches of ppo_minibatches, one
+        Batch.ppo_minibatch_dev (seven launches) each, all on the batch's stream.  Without target_kl nothing in the loop touches the host:
+        the statistics of every minibatch stay on the device and are read once at the end.  With target_kl the approx_kl of each minibatch
+        is read before its step, as SB3 does, and the update stops (without that step) when it exceeds 1.5 target_kl.  Returns the means
+        of the statistics (engine.PPO_STATS): the losses, approx_kl, clip_fraction, the advantage moments and ratio_max over every
+        minibatch EVALUATED - the one that stopped the update included, as in SB3's logs -, grad_norm and skipped over the minibatches
+        STEPPED (NaN when none was); "n_minibatches" (steps taken in this call), "early_stop", "n_updates" (epochs begun since the learner
+        was created, SB3's counter) and "explained_variance" of the buffer's value against its returns.  Streams are ordered as in
+        collect_torch."""
+        import torch
+        from .engine import PPO_STATS
+        if batch_size < 1 or n_epochs < 1:
+            raise ValueError("ppo_update: n_epochs and batch_size must be at least 1")
+        for k in ("obs", "action", "log_prob", "advantage", "returns", "value"):
+            if k not in buf:
+                raise ValueError("ppo_update: the buffer has no %r - collect with gae=dict(...) and the gaussian head" % k)
+        T, n = buf["advantage"].shape
+        R = T * n
+        dev = torch.device("cuda", self._device)
+        plan = self.ppo_minibatches(R, batch_size, n_epochs, seed=seed)
+        stats = torch.zeros((sum(len(c) for _, c in plan), 16), dtype=torch.float32, device=dev)
+        tapes = [buf["obs"][:T], buf["action"], buf["log_prob"], buf["advantage"], buf["returns"]]
+        assert all(x.is_contiguous() and x.dtype == torch.float32 for x in tapes)
+        ptrs = [x.data_ptr() for x in tapes]
+        stream = torch.cuda.ExternalStream(self.batch.stream, device=dev)  # (fetching the stream launches held step calls and joins the pipes)
+        cur = torch.cuda.current_stream(dev)
+        stream.wait_stream(cur)  # the buffer, the permutations and the zeroed statistics are complete
+        done, stopped = 0, False
+        for perm, cuts in plan:
+            self._ppo_epochs = getattr(self, "_ppo_epochs", 0) + 1
+            for s0, mb in cuts:
+                sp = stats[done].data_ptr()
+                if target_kl is None:
+                    self.batch.ppo_minibatch_dev(*ptrs, R, mb, index=perm.data_ptr() + 4 * s0, stats=sp)
+                else:
+                    self.batch.ppo_grad_dev(*ptrs, R, mb, index=perm.data_ptr() + 4 * s0, stats=sp)
+                    if float(self.batch.from_dev(sp + 4 * 4, (1,))[0]) > 1.5 * float(target_kl):
+                        stopped = True
+                        break
+                    self.batch.ppo_adam_dev(stats=sp)
+                done += 1
+            if stopped:
+                break
+        cur.wait_stream(stream)  # the caller's stream is behind the update: the tapes and permutations may be reused or freed on it
+        self._ppo_updates = getattr(self, "_ppo_updates", 0) + 1
+        ret, val = buf["returns"].reshape(-1), buf["value"][:T].reshape(-1)
+        var = ret.var()
+        log = {"explained_variance": float("nan") if float(var) == 0.0 else float(1.0 - (ret - val).var() / var)}
+        rows = stats[:done + (1 if stopped else 0)].double().cpu().numpy()
+        for i, k in enumerate(PPO_STATS):
+            part = rows[:done] if k in ("grad_norm", "skipped") else rows
+            log[k] = float(part[:, i].mean()) if len(part) else float("nan")
+        log.update(n_minibatches=done, n_updates=self._ppo_epochs, early_stop=stopped)
+        return log
+
     def close(self):
         if getattr(self, "_norm_dev", None) is not None:
             self.batch.dev_free(self._norm_dev["obs"])

@@ -994,6 +994,114 @@ typedef struct hb_norm_tapes {   /* device pointers, each nullable */
  * HB_EINVAL: as hb_env_collect_dev, and no normaliser. */
 int hb_env_collect_norm_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out* out, const hb_norm_tapes* aux);
 
+/* ---- the PPO learner on the device: clipped surrogate, backward pass, global-norm clipping, Adam ------------------------------ */
+
+/* The update rule is stable-baselines3's PPO.train with separate actor and critic networks and a state-independent log_std
+ * (HB_ACTOR_GAUSSIAN), clip_range_vf = None, restated here [neither package is a dependency; tests/ppo_ref.py is the fp64 restatement
+ * the kernels are held to].  The data are flattened tapes of n_rows rows (hb_ppo_rows); a minibatch is mb of those rows.  With the
+ * current parameters, c = clip_range, s_i = exp(log_std_i):
+ *   mu_r = actor(obs_r)   v_r = critic(obs_r)             (tanh after every hidden layer, linear at the top)
+ *   lp_r = sum_i ( -(a_ri - mu_ri)^2 / (2 s_i^2) - log_std_i - log(2 pi) / 2 )
+ *   A_r  = normalize_advantage && mb > 1 ? (adv_r - mean(adv)) / (std(adv) + 1e-8) : adv_r      (std unbiased, over the minibatch)
+ *   d_r  = lp_r - old_log_prob_r,  ratio_r = exp(d_r)
+ *   policy_loss  = -mean_r min(A_r ratio_r, A_r clamp(ratio_r, 1 - c, 1 + c))
+ *   value_loss   = mean_r (returns_r - v_r)^2
+ *   entropy_loss = -sum_i (1/2 + log(2 pi) / 2 + log_std_i)
+ *   loss         = policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ *   approx_kl    = mean_r ((ratio_r - 1) - d_r),  clip_fraction = mean_r [ |ratio_r - 1| > c ]
+ * Gradients are autograd's: dloss/dlp_r = -A_r ratio_r / mb where 1 - c <= ratio_r <= 1 + c (bounds included) or where
+ * A_r ratio_r < A_r clamp(ratio_r), else 0; dlp/dmu_ri = (a_ri - mu_ri) / s_i^2; dlp/dlog_std_i = (a_ri - mu_ri)^2 / s_i^2 - 1;
+ * dloss/dlog_std_i gains -ent_coef; dloss/dv_r = 2 vf_coef (v_r - returns_r) / mb; back-propagation through the tanh layers.
+ * The step (torch.nn.utils.clip_grad_norm_, then torch.optim.Adam without weight decay or amsgrad): g = the 2-norm of ALL gradient
+ * entries; max_grad_norm > 0: every entry is scaled by min(1, max_grad_norm / (g + 1e-6)); t += 1; m = b1 m + (1 - b1) grad;
+ * v = b2 v + (1 - b2) grad^2; p -= lr / (1 - b1^t) m / (sqrt(v) / sqrt(1 - b2^t) + eps).  A non-finite g leaves parameters, moments and
+ * t untouched and sets the `skipped` statistic.
+ * Arithmetic: every matrix product is v_mfma_f32_16x16x4_f32 (exact f32); A_r, the advantage moments, the statistics, the norm and
+ * the Adam step are formed in fp64 and rounded to fp32 once.  Every reduction over rows goes over chunks of hb_ppo_row_chunk(mb)
+ * consecutive minibatch rows merged in chunk order, the norm over chunks of 4096 entries: no atomics, the same bits run after run. */
+typedef struct hb_ppo_config {
+  float clip_range;          /* 0.2    > 0 */
+  float ent_coef;            /* 0 */
+  float vf_coef;             /* 0.5 */
+  float max_grad_norm;       /* 0.5    <= 0: no clipping */
+  int normalize_advantage;   /* 1 */
+  float lr;                  /* 3e-4   >= 0 */
+  float beta1, beta2;        /* 0.9, 0.999   in [0, 1) */
+  float eps;                 /* 1e-5   > 0 */
+} hb_ppo_config;
+int hb_ppo_default_config(hb_ppo_config* cfg);
+
+/* Creates the batch's learner: the installed actor (its head must be HB_ACTOR_GAUSSIAN) and critic become the trainable parameters -
+ * the networks hb_env_collect_dev and hb_collect_gae_dev run ARE the learner's, there is no second copy to keep in step.  Allocates
+ * the gradient, the Adam moments (zero) and the packed transposes; t = 0.  A learner that exists is replaced: moments and t start over,
+ * the parameters - log_std included - are the trained ones.
+ * hb_learner_configure changes the hyper-parameters (learning-rate and clip-range schedules) and touches no state.
+ * hb_actor_set_mlp / hb_critic_set_mlp on a batch with a learner: the new network becomes the trainable one; when its sizes (and the
+ * Gaussian head) are unchanged the learner stays, that network's moments (the actor's: log_std's too) are zeroed, t and the other
+ * network's moments stay; when they changed the learner is destroyed and has to be created again.  Either way the actor goes on with the
+ * trained log_std behind hb_critic_set_mlp, and with the log_std of its new config behind hb_actor_set_mlp.
+ * HB_EINVAL: NULL argument; no actor or no critic; a hyper-parameter that is not finite or out of range (clip_range <= 0, a beta
+ * outside [0, 1), lr < 0, eps <= 0); configure / destroy without a learner.  HB_EUNSUPPORTED: the deterministic head, and the squashed
+ * head (HB_ACTOR_SQUASHED, SAC's actor: an off-policy learner is not part of this library).  A refused call changes nothing. */
+int hb_learner_create(hb_batch* b, const hb_ppo_config* cfg);
+int hb_learner_configure(hb_batch* b, const hb_ppo_config* cfg);
+int hb_learner_destroy(hb_batch* b);
+
+/* The flat record, P = hb_learner_param_count(b) floats: the actor's layers in order, each W[sizes[l]][sizes[l+1]] row-major
+ * (hb_actor_set_mlp's convention: the transpose of torch.nn.Linear.weight) followed by b[sizes[l+1]]; then log_std[nu]; then the
+ * critic's layers the same way.  Parameters, gradients and both moments use it; how the device holds the operands of its kernels
+ * (packed B operands, a second packing of the transposes) is internal.  Host pointers; every call runs behind the work enqueued so
+ * far and ends synchronised.  get_state / set_state: params[P] | m[P] | v[P] and the step count t - checkpoint and resume; set_params
+ * and set_state also refresh what the forward kernels read and the actor's log_std.  count must equal P.
+ * HB_EINVAL: NULL argument, no learner, a wrong count, t < 0.  (hb_learner_param_count: the count, or HB_EINVAL.) */
+long long hb_learner_param_count(hb_batch* b);
+int hb_learner_get_params(hb_batch* b, float* out, long long count);
+int hb_learner_set_params(hb_batch* b, const float* in, long long count);
+int hb_learner_get_grads(hb_batch* b, float* out, long long count);
+int hb_learner_get_state(hb_batch* b, float* params, float* m, float* v, long long count, long long* t);
+int hb_learner_set_state(hb_batch* b, const float* params, const float* m, const float* v, long long count, long long t);
+/* The device gradient buffer and its length P, in the flat layout above: a multi-GPU caller all-reduces it (and divides by the number
+ * of ranks) between hb_ppo_grad_dev and hb_ppo_adam_dev.  The pointer stays valid until the learner is destroyed. */
+int hb_learner_grad_dev(hb_batch* b, float** ptr, long long* count);
+/* Rows per chunk of the row reductions of a minibatch of mb rows (64 up to 4096 rows; beyond that mb / 64 rounded up to a multiple of
+ * 16, so that there are never more than 64 chunks); 0 for mb < 1. */
+int hb_ppo_row_chunk(int mb);
+
+typedef struct hb_ppo_rows {     /* device pointers */
+  const float* obs;              /* [n_rows][nobs] */
+  const float* action;           /* [n_rows][nu] */
+  const float* old_log_prob;     /* [n_rows] */
+  const float* advantage;        /* [n_rows] */
+  const float* returns;          /* [n_rows] */
+  const int32_t* index;          /* [mb] row numbers in any order, repeats allowed; NULL: rows first .. first + mb - 1 */
+  long long n_rows, first;
+  int mb;
+} hb_ppo_rows;
+
+/* Loss, statistics and all gradients of one minibatch, into the learner's gradient buffer: FIVE launches on the batch's stream whatever
+ * mb is (forward with kept activations; the head by row; back-propagation of dZ; the chunk partials of dW, db, dlog_std and the
+ * statistics; their merge).  Asynchronous: no host synchronisation, no host transfer, no allocation beyond the learner's scratch, which
+ * grows on demand (every layer's activations and dZ as [mb][width], and [chunks][P] partial gradients; a call that has to grow it waits
+ * for the stream first).  A pure function of the rows, the parameters and the config: nothing else of the batch is written - state, draw
+ * counter, status words, hb_last_kernel and hb_batch_step_launches stay (held hb_step_dev calls are launched first and the pipes joined,
+ * as for every other call).  Rows outside the minibatch are not read.  The values of index[] are the caller's responsibility, like
+ * every device pointer of this API: they are not checked.
+ * stats_dev: NULL or a device float[16]: policy_loss, value_loss, entropy_loss, loss, approx_kl, clip_fraction, grad_norm (before
+ * clipping), adv_mean, adv_std (the minibatch's moments, whether or not they are applied), ratio_max, skipped, then zeros.
+ * hb_ppo_grad_dev writes all sixteen, grad_norm and skipped as 0; hb_ppo_adam_dev, given the same pointer, writes those two alone.
+ * HB_EINVAL: NULL b or rows, no learner, a NULL tape, mb < 1, n_rows < 1, first < 0 or first + mb > n_rows (index NULL). */
+int hb_ppo_grad_dev(hb_batch* b, const hb_ppo_rows* rows, float* stats_dev);
+/* Clipping and the Adam step on the gradient buffer, in TWO launches (the norm's chunk sums; the step), asynchronous like the above.
+ * The step kernel also rewrites every updated weight in the packed operands the forward kernels read, so the next
+ * hb_env_collect_dev / hb_collect_gae_dev / hb_ppo_grad_dev runs the new parameters with no host transfer; pad entries of the packed
+ * operands are never written and stay zero.  log_std reaches hb_actor_kernel and hb_log_prob_kernel by value in their descriptors:
+ * the call marks the learner dirty, and the first later hb_env_collect*_dev / hb_collect_gae_dev copies the nu floats back into the
+ * actor's config - ONE device-to-host copy of at most 128 bytes and one synchronisation per iteration, not per minibatch.
+ * HB_EINVAL: NULL b, no learner. */
+int hb_ppo_adam_dev(hb_batch* b, float* stats_dev);
+/* hb_ppo_grad_dev, then hb_ppo_adam_dev: seven launches. */
+int hb_ppo_minibatch_dev(hb_batch* b, const hb_ppo_rows* rows, float* stats_dev);
+
 /* ---- host-side helpers so a C/C++/ctypes caller needs no HIP headers ---------------------------- */
 
 /* Device buffer on the batch's GPU (hipMalloc / hipFree). */
