@@ -464,9 +464,23 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       Op[3] = {f0[2] + f2[2], f0[3] + f2[3], f0[4] + f2[4], f0[5] + f2[5]};
     }
     if (on && l < 16) s_if[l] = l < 10 ? s_cinert[l] : 0.f;  // world body
-    int pf_pk = 0;
-    float2 pf_ad = {0.f, 0.f};
-    if (on) { pf_pk = M.mrec[l]; pf_ad = M.mdiag[l]; }
+    // the table words of ALL the qM rounds (round r: entry l + H r; the last round is partial) - model constants at addresses the lane knows
+    // here - are requested now, under the crb sweep: no round waits for a table word.  Every lane loads, without a branch around the load: a
+    // lane beyond the last entry reads the last one and drops it.  (24 registers; both kernels stay at 0 B of scratch, two waves per SIMD)
+    constexpr int kMRounds = (NM + H - 1) / H;
+    int pf_pk[kMRounds];
+    float2 pf_ad[kMRounds];
+    const float m_hstep = M.timestep;
+    {
+      const int HB_CONST* const mrec = M.mrec;
+      const float2 HB_CONST* const mdiag = M.mdiag;
+#pragma unroll
+      for (int r = 0; r < kMRounds; r++) {
+        const int e = l + H * r < NM ? l + H * r : NM - 1;
+        pf_pk[r] = mrec[e];
+        pf_ad[r] = mdiag[e];
+      }
+    }
     gsync();
     // mj_crb and the mj_rne backward pass: one sweep up the tree, children into parents (pull form)
     for (int L = NLEVEL - 2; L >= 1; L--) {
@@ -490,6 +504,8 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     float4 pf_bA = {0.f, 0.f, 0.f, 0.f}, pf_bB = pf_bA, pf_bC = pf_bA, pf_a0 = pf_bA, pf_a1 = pf_bA, pf_a2 = pf_bA, pf_a3 = pf_bA;
     if (dofl) { pf_bA = M.drec[3 * l]; pf_bB = M.drec[3 * l + 1]; pf_bC = M.drec[3 * l + 2]; }
     if (on && l < NU) { const float4 HB_CONST* AR4 = M.arec + (size_t)l * 4; pf_a0 = AR4[0]; pf_a1 = AR4[1]; pf_a2 = AR4[2]; pf_a3 = AR4[3]; }
+    // the broadphase's first round of pair records: requested with the words above, not at the head of mj_collision
+    const float4 pf_n0 = M.crec[3 * (size_t)l], pf_n1 = M.crec[3 * (size_t)l + 1];
     // crb[body(i)] cdof_i is the same for every entry (i, j) of row i: once per dof (lane = dof), kept in the kinematics scratch
     // (xmat .. xaxis: last read by the cdof / geoms stage) for the entries' rounds below
     float* const s_mb = Dn + d_mbuf;
@@ -509,26 +525,32 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     }
     gsync();
     if (on) {
-      for (int e = l; e < NM; e += H) {
-        const int pk = pf_pk;
-        const float2 ad = pf_ad;
-        if (e + H < NM) { pf_pk = M.mrec[e + H]; pf_ad = M.mdiag[e + H]; }
-        const int i = pk & 255, j = (pk >> 8) & 255;
-        float buf[6];
-        {
-          const float4* Bp = reinterpret_cast<const float4*>(s_mb + kMbufStride * i);
-          const float4 b0 = Bp[0], b1 = Bp[1];
-          buf[0] = b0.x; buf[1] = b0.y; buf[2] = b0.z; buf[3] = b0.w; buf[4] = b1.x; buf[5] = b1.y;
+      // two stages: the rows of round r + 1 (crb cdof of dof i, cdof of dof j) are read from LDS before the sum of round r
+      float4 nb0, nb1, nc0, nc1;
+      auto ld_rows = [&](int pk) {
+        const float4* Bp = reinterpret_cast<const float4*>(s_mb + kMbufStride * (pk & 255));
+        const float4* Cp = reinterpret_cast<const float4*>(s_cdof + kCdofStride * ((pk >> 8) & 255));
+        nb0 = Bp[0]; nb1 = Bp[1]; nc0 = Cp[0]; nc1 = Cp[1];
+      };
+      ld_rows(pf_pk[0]);
+#pragma unroll
+      for (int r = 0; r < kMRounds; r++) {
+        const int e = l + H * r;
+        const int pk = pf_pk[r];
+        const float2 ad = pf_ad[r];
+        const float buf[6] = {nb0.x, nb0.y, nb0.z, nb0.w, nb1.x, nb1.y};
+        const float cj[6] = {nc0.x, nc0.y, nc0.z, nc1.x, nc1.y, nc1.z};
+        if (r + 1 < kMRounds) ld_rows(pf_pk[r + 1]);
+        if (e < NM) {
+          const int i = pk & 255, j = (pk >> 8) & 255;
+          float sacc = 0.f;
+          for (int t = 0; t < 6; t++) sacc += cj[t] * buf[t];
+          sacc += ad.x;
+          // H = M + h diag(damping) differs from M on the diagonal only: the one-env kernel's pair {M, H}, the H half kept for diagonal entries
+          const f32x2 mh = {sacc, sacc + (eulerdamp ? m_hstep * ad.y : 0.f)};
+          s_qM[e] = mh.x;
+          if (i == j) s_Hd[i] = mh.y;
         }
-        float sacc = 0.f;
-        float cj[6];
-        ld_cdof(s_cdof, j, cj);
-        for (int t = 0; t < 6; t++) sacc += cj[t] * buf[t];
-        sacc += ad.x;
-        // H = M + h diag(damping) differs from M on the diagonal only: the one-env kernel's pair {M, H}, the H half kept for diagonal entries
-        const f32x2 mh = {sacc, sacc + (eulerdamp ? M.timestep * ad.y : 0.f)};
-        s_qM[e] = mh.x;
-        if (i == j) s_Hd[i] = mh.y;
       }
     }
     gsync();
@@ -571,7 +593,7 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       int* s_list = reinterpret_cast<int*>(s_C) + h * 160;
       int nlist = 0;
       {
-        float4 n0 = M.crec[3 * (size_t)l], n1 = M.crec[3 * (size_t)l + 1];
+        float4 n0 = pf_n0, n1 = pf_n1;
         for (int p0 = 0; p0 < NPAIR; p0 += H) {
           const int p = p0 + l;
           const float4 c0 = n0, c1 = n1;
