@@ -488,6 +488,7 @@ int hb_actor_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* c
   HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a collection still in flight reads the buffers that are replaced below)
   // (every argument check is behind us: from here on only the device can fail, and then no actor is installed)
   const bool same = mlp_same_shape(b->actor, n_layers, sizes);
+  b->sac.clear();  // (a SAC learner does not outlive the actor it trained: hb_sac_create again)
   if ((rc = b->actor.install(n_layers, sizes, weights, biases)) != HB_OK) { b->learner.clear(); return rc; }
   b->actor_cfg = *cfg;
   b->actor_draw0 = 0;

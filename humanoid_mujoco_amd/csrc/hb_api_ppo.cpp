@@ -4,15 +4,6 @@
 
 namespace {
 
-// the inverse of DevMlp::pack_mfma_b
-std::vector<float> unpack_mfma_b(const std::vector<float>& packed, int K, int N) {
-  const int KK = (K + 3) / 4;
-  std::vector<float> W((size_t)K * N);
-  for (int k = 0; k < K; k++)
-    for (int n = 0; n < N; n++) W[(size_t)k * N + n] = packed[((size_t)(n >> 4) * KK + (k >> 2)) * 64 + (k & 3) * 16 + (n & 15)];
-  return W;
-}
-
 const DevMlp& net_of(const hb_batch* b, int k) { return k == 0 ? b->actor : b->critic; }
 
 bool cfg_ok(const hb_ppo_config* c) {
@@ -46,7 +37,7 @@ int read_installed(hb_batch* b, std::vector<float>& flat) {
       const int K = n.sizes[l], N = n.sizes[l + 1];
       std::vector<float> packed(n.wp[l].capacity());
       HB_HIP(hipMemcpy(packed.data(), n.wp[l], packed.size() * sizeof(float), hipMemcpyDeviceToHost));
-      const std::vector<float> W = unpack_mfma_b(packed, K, N);
+      const std::vector<float> W = DevMlp::unpack_mfma_b(packed, K, N);
       memcpy(&flat[L.off_w[k][l]], W.data(), W.size() * sizeof(float));
       HB_HIP(hipMemcpy(&flat[L.off_b[k][l]], n.b[l], N * sizeof(float), hipMemcpyDeviceToHost));
     }

@@ -94,6 +94,14 @@ struct DevMlp {
         }
     return out;
   }
+  // its inverse: W[K][N] from the packed operand (the learners read the installed networks back)
+  static std::vector<float> unpack_mfma_b(const std::vector<float>& packed, int K, int N) {
+    const int KK = (K + 3) / 4;
+    std::vector<float> W((size_t)K * N);
+    for (int k = 0; k < K; k++)
+      for (int n = 0; n < N; n++) W[(size_t)k * N + n] = packed[((size_t)(n >> 4) * KK + (k >> 2)) * 64 + (k & 3) * 16 + (n & 15)];
+    return W;
+  }
   void clear() {
     layers = 0;
     for (int l = 0; l < 4; l++) reset_all(wp[l], b[l]);
@@ -152,6 +160,31 @@ struct Learner {
     reset_all(d_param, d_grad, d_m, d_v, d_zero, d_scratch, d_part, d_dbl);
     d_nskip.reset();
     for (int k = 0; k < 2; k++) for (int l = 0; l < 4; l++) d_wt[k][l].reset();
+  }
+};
+
+// The SAC learner of a batch (hb_sac_*, hb_api_sac.cpp): the trainable parameters as ONE flat record (include/hb.h: the actor's layers
+// W | b, Q1's, Q2's, log_ent_coef), the gradient and the Adam moments in the same layout, the targets (their record, Q1' then Q2', and the
+// packed operands their forward pass reads), the packed transposes of the backward pass (wt[net][0] of a Q network: the transpose of
+// layer 0's action rows), and the scratch of a minibatch.  The forward operands of the live networks stay where they are: in the batch's
+// actor and q[0], q[1] (DevMlp), which hb_sac_adam_kernel refreshes entry by entry.
+struct SacLearner {
+  bool on = false;
+  hb_sac_config cfg = {};
+  int P = 0, PT = 0, off_q = 0;   // off_q: where Q1's stretch begins; the targets' record mirrors [off_q, P - 1)
+  int off_w[3][4] = {}, off_b[3][4] = {};
+  long long t = 0;
+  DevMlp tq[2];
+  DevBuf<float> d_param, d_grad, d_m, d_v, d_target, d_zero, d_alpha, d_wt[3][4];
+  DevBuf<float> d_scratch;     // activations, dZ, outputs and the by-row terms of a minibatch: grows with mb
+  DevBuf<float> d_part;        // [64][P] chunk partials of the gradient
+  DevBuf<double> d_dbl;        // statpart [64][kSacSrow]
+  void clear() {
+    on = false; P = PT = off_q = 0; t = 0;
+    tq[0].clear(); tq[1].clear();
+    reset_all(d_param, d_grad, d_m, d_v, d_target, d_zero, d_alpha, d_scratch, d_part);
+    d_dbl.reset();
+    for (int k = 0; k < 3; k++) for (int l = 0; l < 4; l++) d_wt[k][l].reset();
   }
 };
 
@@ -288,6 +321,9 @@ struct hb_batch {
   DevBuf<float> d_gae;
   // PPO learner (hb_learner_create): off until created
   Learner learner;
+  // Q networks (hb_q_set_mlp, hb_q_values_dev) over obs | action, and the SAC learner (hb_sac_create): off until created
+  DevMlp q[2];
+  SacLearner sac;
   // normaliser (hb_norm_*): the double-buffered statistics record (slot norm_k is current; hb_device.hpp: NormDesc), the per-env
   // accumulators ret | ep_ret [2][n_env] and ep_len [n_env], and the chunk partials of a step; all null while none is configured
   bool norm_on = false;

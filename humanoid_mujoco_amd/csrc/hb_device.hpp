@@ -357,6 +357,101 @@ struct PpoAdamDesc {
   float* stats;
 };
 
+// hb_sac_* (hb_sac.hip): the SAC learner.  The launches of one gradient step are described job by job: a forward pass, a reversed
+// (back-propagating) pass and a dW pass each run a list of jobs side by side (grid y), so the same three kernels serve the actor, the two
+// Q networks and the two targets.  Row reductions go over the PPO learner's chunks (ppo_row_chunk).
+constexpr unsigned RS_SAC_PI = 33, RS_SAC_NEXT = 34;  // random-number streams of eps_pi and eps_next (RS_ACTOR is 32)
+constexpr int kSacMaxSeg = 17;   // tensors one Adam or Polyak launch covers: 2 x 4 x (W, b) + log_ent_coef
+constexpr int kSacSrow = 8;      // by-row terms of a phase
+struct SacFwdJob {
+  PolicyDesc net;
+  const float *x0, *x1;  // the input row is x0's n0 columns | x1's n1 columns (n1 0: none)
+  int n0, n1;
+  int gather0, gather1;  // 1: minibatch row r is row index[r] (or first + r) of the array; 0: row r
+  float* in_store;       // [mb][n0 + n1] or null: the gathered input rows (act[0] of the dW pass)
+  float* act[4];         // act[l] [mb][sizes[l]], l = 1 .. L - 1: the tanh outputs; act[1] null: nothing is stored
+  float* out;            // [mb][sizes[L]] the last layer's (linear) output
+};
+struct SacFwdDesc {
+  SacFwdJob job[4];
+  const int* index;
+  long long first;
+  int mb;
+};
+struct SacBwdJob {
+  PolicyDesc net;        // the reversed network: the widths from the top down, w[j] = the packed transpose of layer L - 1 - j, b = zeros;
+                         // nl = L - 1 stops at dZ_0; nl = L goes one step further, into the Q network's action inputs
+  int L;                 // layers of the forward network
+  int unit_top;          // 1: the top gradient is 1 for every row (dQ / da); 0: read from top
+  const float* top;      // [mb][sizes[L]]
+  const float* act[4];   // the tanh outputs the forward pass kept
+  float* dz[4];          // dz[l] [mb][sizes[l + 1]], l = 0 .. L - 2, written; dz[0] null: not stored (no dW follows)
+  float* da;             // [mb][nu]: dloss / d(action inputs), the nl = L step
+};
+struct SacBwdDesc {
+  SacBwdJob job[2];
+  int mb;
+};
+struct SacWgJob {
+  const float *A, *Z;    // dW = A^T Z: A [mb][K], Z [mb][N]
+  int K, N, off_w, off_b;
+};
+struct SacWgDesc {
+  SacWgJob job[8];
+  int njob, mb, chunk, nchunk, P, ncol;
+  float* part;           // [nchunk][P]
+  const float* srow;     // [mb][kSacSrow] by-row terms, the first ncol of them summed by the block behind the jobs
+  double* statpart;      // [nchunk][kSacSrow]
+};
+struct SacHeadDesc {
+  int mb, nu, eps_given;
+  unsigned seed, t;
+  const int* index;
+  long long first;
+  float gamma, target_entropy;
+  const float* param;    // the flat record (log_ent_coef is its last entry)
+  int P;
+  float* alpha;          // [1] exp(log_ent_coef) at the start of the step
+  const float *reward;
+  const uint8_t* done;
+  float *eps_pi, *eps_next;        // the caller's [mb][nu], nullable
+  float *eps;                      // [mb][nu] scratch: the draws of the pi branch
+  const float *pi_out, *nx_out;    // [mb][2 nu] the actor on obs / next_obs
+  float *a_pi, *a_nx, *lp_pi, *lp_nx;
+  const float *q[2], *qt[2], *qpi[2];  // [mb] Q(obs, action), Q'(next_obs, a'), Q(obs, a_pi)
+  const float* da[2];              // [mb][nu] dQk / da at a_pi
+  float *dzq[2];                   // [mb] the Q networks' top dZ
+  float *dza;                      // [mb][2 nu] the actor's top dZ
+  float* srow;                     // [mb][kSacSrow]
+};
+struct SacReduceDesc {
+  int lo, hi, P, nchunk, mb, phase;  // entries [lo, hi) of the flat record; phase 0: critics and log_ent_coef, 1: actor
+  float target_entropy;
+  const float *part, *param, *alpha;
+  const double* statpart;
+  float *grad, *stats;
+};
+struct SacSeg {
+  int start, K, N, k0;   // flat offset; W[K][N], or K = 0: a vector of N; rows k >= k0 have an entry in dst_t, at row k - k0
+  float* dst;            // W: the packed B operand of the forward pass; vector: its copy (null: none)
+  float* dst_t;          // W: the packed B operand of the transpose (null: none)
+};
+struct SacAdamDesc {
+  int lo, hi, nseg, ent_index;   // entries [lo, hi); ent_index: log_ent_coef (its own learning rate), -1: not in this launch
+  SacSeg seg[kSacMaxSeg];
+  float *param, *m, *v;
+  const float* grad;
+  long long t;           // this step included
+  float lr, lr_ent, beta1, beta2, eps;
+};
+struct SacPolyakDesc {
+  int n, nseg;
+  SacSeg seg[kSacMaxSeg];  // starts relative to the targets' record
+  const float* src;      // the live Q networks' stretch of the flat record
+  float* target;
+  float tau;
+};
+
 // Buffers of the STAGED step of the general variants (launch_step): hb_pose_kernel writes every geom's world pose and the env's
 // narrowphase work items, hb_narrow_kernel evaluates the items (one per lane, at the occupancy of a small kernel: the MPR climbs are
 // chains of dependent loads), the step kernel appends the results in item order.  All null: the step kernel does all of it itself.

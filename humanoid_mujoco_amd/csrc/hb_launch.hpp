@@ -74,6 +74,16 @@ hipError_t launch_norm_apply(const NormDesc& d, hipStream_t stream);
 // and the statistics - and their merge; then the two of hb_ppo_adam_dev - the norm partials, and clipping + Adam + operand refresh
 hipError_t launch_ppo_grad(const PpoDesc& d, hipStream_t stream);
 hipError_t launch_ppo_adam(const PpoAdamDesc& d, hipStream_t stream);
+// the SAC learner (hb_sac.hip), one launch each: njob forward passes side by side; the head by row (what: 0 the two samples and their
+// log-probabilities, 1 the target and the critics' top dZ, 2 the actor's top dZ); njob reversed passes; the chunk partials of dW / db of
+// the jobs and of the by-row terms; their merge; Adam over a stretch of the flat record; the Polyak step of the targets
+hipError_t launch_sac_forward(const SacFwdDesc& d, int njob, hipStream_t stream);
+hipError_t launch_sac_head(const SacHeadDesc& d, int what, hipStream_t stream);
+hipError_t launch_sac_backprop(const SacBwdDesc& d, int njob, hipStream_t stream);
+hipError_t launch_sac_wgrad(const SacWgDesc& d, hipStream_t stream);
+hipError_t launch_sac_reduce(const SacReduceDesc& d, hipStream_t stream);
+hipError_t launch_sac_adam(const SacAdamDesc& d, hipStream_t stream);
+hipError_t launch_sac_polyak(const SacPolyakDesc& d, hipStream_t stream);
 // order: [2 * n_env] ints - the permutation, then the sort keys of the pass (read once from counts)
 hipError_t launch_order(const int* counts, int* order, int n_env, int e0, int n, hipStream_t stream, int slot = 3, int shift = 3);
 hipError_t launch_mlp_layer(const float* X, const float* W, const float* bias, float* Y, int Mrows, int K, int N, int act, hipStream_t stream);

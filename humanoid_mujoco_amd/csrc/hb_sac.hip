@@ -1,0 +1,438 @@
+// hb_sac.hip - the SAC learner of hb_sac_step_dev: stable-baselines3's SAC.train for the squashed Gaussian actor (HB_ACTOR_SQUASHED), twin
+// Q networks over obs | action, their Polyak-averaged targets and the entropy coefficient.  A translation unit of its own: no other
+// kernel compiles differently for it.  The design is hb_ppo.hip's - 16 gathered rows per block through hb_mlp_layers.inl, activations and
+// dZ in a learner-owned scratch [mb][width], the reversed network for dA = dZ W^T, 32 accumulator tiles per wave for dW = A^T dZ over a
+// chunk of rows, chunk partials merged in order - with the launches described job by job (hb_device.hpp: Sac*Desc), so that three
+// kernels serve five networks.
+//
+// hb_sac_step_dev is SIXTEEN launches whatever the minibatch size (fifteen on a step the target update interval skips):
+//   1. hb_sac_forward_kernel   grid (tiles, 4): the actor on obs (activations kept) and on next_obs (nothing kept), Q1 and Q2 on
+//      obs | action (input rows and activations kept)
+//   2. hb_sac_sample_kernel    one lane per row: eps_pi, eps_next (drawn or read), a_pi, a', lp_pi, lp'; alpha = exp(log_ent_coef)
+//   3. hb_sac_forward_kernel   grid (tiles, 2): Q1', Q2' on next_obs | a', nothing kept
+//   4. hb_sac_critic_head_kernel  one lane per row: y, the top dZ of Q1 and Q2, the by-row terms of the statistics
+//   5. hb_sac_backprop_kernel  grid (tiles, 2): dZ of Q1 and Q2 down to layer 0
+//   6. hb_sac_wgrad_kernel     grid (chunks, layers of Q1 and Q2 + 1): dW, db by chunk; the last y: the chunk sums of the by-row terms
+//   7. hb_sac_reduce_kernel    the chunk partials in chunk order; the statistics and dloss / dlog_ent_coef
+//   8. hb_sac_adam_kernel      Q1, Q2 (and log_ent_coef), with the refresh of every packed operand
+//   9. hb_sac_forward_kernel   grid (tiles, 2): the UPDATED Q1, Q2 on obs | a_pi, activations kept
+//  10. hb_sac_backprop_kernel  grid (tiles, 2): from a top gradient of 1 down INTO the action inputs: dQ1 / da, dQ2 / da (no dZ stored)
+//  11. hb_sac_actor_head_kernel  one lane per row: min Q, the actor's top dZ (mean | log_std), the by-row terms
+//  12. hb_sac_backprop_kernel  grid (tiles, 1): the actor's dZ
+//  13. hb_sac_wgrad_kernel     grid (chunks, layers of the actor + 1)
+//  14. hb_sac_reduce_kernel
+//  15. hb_sac_adam_kernel      the actor
+//  16. hb_sac_polyak_kernel    Q' = tau Q + (1 - tau) Q', one lane per entry, with the refresh of the targets' packed operands
+// All matrix products are v_mfma_f32_16x16x4_f32 (exact f32).  No atomics, no cross-block communication inside a launch: every reduction
+// has an order fixed by (mb, sizes) alone, so the same inputs give the same bits.
+#include <hip/hip_runtime.h>
+#include "hb_kcommon.hpp"
+#include "hb_launch.hpp"
+
+namespace hb {
+
+// minibatch row r of the tapes
+__device__ __forceinline__ long long sac_src_row(const int* index, long long first, int r) { return index ? (long long)index[r] : first + r; }
+
+__global__ __launch_bounds__(512) void hb_sac_forward_kernel(const SacFwdDesc d) {
+  extern __shared__ __attribute__((aligned(16))) float sm_sac[];
+  const SacFwdJob& jb = d.job[blockIdx.y];
+  const PolicyDesc& pd = jb.net;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m0 = blockIdx.x * 16, ldx = pd.ldx;
+  const int live = min(16, d.mb - m0);
+  float* cur = sm_sac;
+  float* nxt = sm_sac + 16 * ldx;
+  float* part = sm_sac + 32 * ldx;  // [8][16][16] partial tiles
+  {
+    // the input tile from its two sources; rows past mb and the K pad columns are zero
+    const int n0 = jb.n0, n1 = jb.n1, nin = n0 + n1;
+    for (int idx = tid; idx < 16 * nin; idx += 512) {
+      const int row = idx / nin, c = idx - row * nin;
+      float x = 0.f;
+      if (row < live) {
+        const int r = m0 + row;
+        if (c < n0) x = jb.x0[(size_t)(jb.gather0 ? sac_src_row(d.index, d.first, r) : (long long)r) * n0 + c];
+        else x = jb.x1[(size_t)(jb.gather1 ? sac_src_row(d.index, d.first, r) : (long long)r) * n1 + (c - n0)];
+        if (jb.in_store) jb.in_store[(size_t)r * nin + c] = x;
+      }
+      cur[row * ldx + c] = x;
+    }
+    if (tid < 48) cur[(tid / 3) * ldx + nin + tid % 3] = 0.f;
+  }
+  __syncthreads();
+  // (l: the layer index of the loop)
+#define HB_MLP_EMIT(row, n, v) do { \
+    const float a_ = last ? (v) : tanhf(v); \
+    nxt[(row) * ldx + (n)] = a_; \
+    if ((row) < live) { \
+      if (last) jb.out[(size_t)(m0 + (row)) * N + (n)] = a_; \
+      else if (jb.act[1]) jb.act[l + 1][(size_t)(m0 + (row)) * N + (n)] = a_; \
+    } \
+  } while (0)
+#include "hb_mlp_layers.inl"
+#undef HB_MLP_EMIT
+}
+
+// One lane per minibatch row, both branches (0: pi on obs, 1: next on next_obs).  Roundings are fp32 and follow hb_log_prob_kernel
+// (hb_gae.hip) term by term; the draw of (row r, element i) is rng_normal(seed, r, 0, t, stream, i).
+__global__ __launch_bounds__(256) void hb_sac_sample_kernel(const SacHeadDesc d) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r == 0) d.alpha[0] = (float)exp((double)d.param[d.P - 1]);
+  if (r >= d.mb) return;
+  const int nu = d.nu;
+  const float half_log_2pi = 0.91893853320467274178f, log2f_ = 0.69314718055994530942f;
+  for (int br = 0; br < 2; br++) {
+    const float* out = (br ? d.nx_out : d.pi_out) + (size_t)r * 2 * nu;
+    float* user = br ? d.eps_next : d.eps_pi;
+    float* act = (br ? d.a_nx : d.a_pi) + (size_t)r * nu;
+    float sum = 0.f;
+    for (int i = 0; i < nu; i++) {
+      const size_t o = (size_t)r * nu + i;
+      float eps;
+      if (d.eps_given) eps = user[o];
+      else {
+        eps = rng_normal(d.seed, (unsigned)r, 0u, d.t, br ? RS_SAC_NEXT : RS_SAC_PI, (unsigned)i);
+        if (user) user[o] = eps;
+      }
+      if (!br) d.eps[o] = eps;
+      const float ls = fminf(2.f, fmaxf(-20.f, out[nu + i]));
+      float term = __fsub_rn(__fmaf_rn(-0.5f * eps, eps, -ls), half_log_2pi);
+      const float x = __fmaf_rn(expf(ls), eps, out[i]);
+      const float a = fabsf(x);
+      const float corr = 2.f * __fsub_rn(__fsub_rn(log2f_, a), log1pf(expf(-2.f * a)));
+      term = __fsub_rn(term, corr);
+      sum = __fadd_rn(sum, term);
+      act[i] = tanhf(x);
+    }
+    (br ? d.lp_nx : d.lp_pi)[r] = sum;
+  }
+}
+
+// y = reward + (1 - done) gamma (min(Q1', Q2') - alpha lp'); dloss / dQk = (Qk - y) / mb
+__global__ __launch_bounds__(256) void hb_sac_critic_head_kernel(const SacHeadDesc d) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= d.mb) return;
+  const long long src = sac_src_row(d.index, d.first, r);
+  const float alpha = d.alpha[0];
+  const float tq = __fmaf_rn(-alpha, d.lp_nx[r], fminf(d.qt[0][r], d.qt[1][r]));
+  const float rew = d.reward[src];
+  const float y = d.done[src] ? rew : __fmaf_rn(d.gamma, tq, rew);
+  const float inv_mb = 1.f / (float)d.mb;
+  const float q1 = d.q[0][r], q2 = d.q[1][r];
+  const float e1 = q1 - y, e2 = q2 - y;
+  d.dzq[0][r] = e1 * inv_mb;
+  d.dzq[1][r] = e2 * inv_mb;
+  float* sr = d.srow + (size_t)r * kSacSrow;
+  sr[0] = e1 * e1; sr[1] = e2 * e2; sr[2] = d.lp_pi[r]; sr[3] = q1; sr[4] = q2; sr[5] = y;
+}
+
+// The actor's top dZ.  g = d min(Q1, Q2) / da: the smaller network's, and on a tie half of each (torch.min's backward).
+// mb dL/dmean_i = 2 alpha a_i - g_i (1 - a_i^2);  mb dL/dls_i = alpha (-1 + 2 a_i s_i eps_i) - g_i (1 - a_i^2) s_i eps_i where the clamp passes
+__global__ __launch_bounds__(256) void hb_sac_actor_head_kernel(const SacHeadDesc d) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= d.mb) return;
+  const int nu = d.nu;
+  const float alpha = d.alpha[0], inv_mb = 1.f / (float)d.mb;
+  const float q1 = d.qpi[0][r], q2 = d.qpi[1][r];
+  const float w1 = q1 < q2 ? 1.f : (q1 == q2 ? 0.5f : 0.f), w2 = 1.f - w1;
+  const float* out = d.pi_out + (size_t)r * 2 * nu;
+  float* dz = d.dza + (size_t)r * 2 * nu;
+  for (int i = 0; i < nu; i++) {
+    const size_t o = (size_t)r * nu + i;
+    const float g = w1 * d.da[0][o] + w2 * d.da[1][o];
+    const float a = d.a_pi[o], eps = d.eps[o];
+    const float raw = out[nu + i];
+    const float se = expf(fminf(2.f, fmaxf(-20.f, raw))) * eps;
+    const float gx = g * __fmaf_rn(-a, a, 1.f);  // through tanh
+    const float aa = 2.f * alpha * a;
+    dz[i] = (aa - gx) * inv_mb;
+    const bool pass = raw >= -20.f && raw <= 2.f;
+    dz[nu + i] = pass ? (__fmaf_rn(aa, se, -alpha) - gx * se) * inv_mb : 0.f;
+  }
+  const float mq = fminf(q1, q2);
+  float* sr = d.srow + (size_t)r * kSacSrow;
+  sr[0] = __fmaf_rn(alpha, d.lp_pi[r], -mq);
+  sr[1] = mq;
+}
+
+__global__ __launch_bounds__(512) void hb_sac_backprop_kernel(const SacBwdDesc d) {
+  extern __shared__ __attribute__((aligned(16))) float sm_sac[];
+  const SacBwdJob& jb = d.job[blockIdx.y];
+  const PolicyDesc& pd = jb.net;
+  if (pd.nl < 1) return;  // one layer and no input gradient: its dZ is the head's
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m0 = blockIdx.x * 16, ldx = pd.ldx, L = jb.L;
+  const int live = min(16, d.mb - m0);
+  float* cur = sm_sac;
+  float* nxt = sm_sac + 16 * ldx;
+  float* part = sm_sac + 32 * ldx;
+  {
+    const int n0 = pd.sizes[0];
+    for (int idx = tid; idx < 16 * n0; idx += 512) {
+      const int row = idx / n0;
+      cur[row * ldx + (idx - row * n0)] = row < live ? (jb.unit_top ? 1.f : jb.top[(size_t)m0 * n0 + idx]) : 0.f;
+    }
+    if (tid < 48) cur[(tid / 3) * ldx + n0 + tid % 3] = 0.f;
+  }
+  __syncthreads();
+  // step l of the loop multiplies by the transpose of layer L - 1 - l: v is dloss / dact[L - 1 - l] - a tanh output, or for
+  // L - 1 - l == 0 (a Q network's nl = L) the action inputs, which are no tanh output: no 1 - a^2
+#define HB_MLP_EMIT(row, n, v) do { \
+    float g_ = 0.f; \
+    if ((row) < live) { \
+      const size_t o_ = (size_t)(m0 + (row)) * N + (n); \
+      if (L - 1 - l == 0) { \
+        g_ = (v); \
+        jb.da[o_] = g_; \
+      } else { \
+        const float a_ = jb.act[L - 1 - l][o_]; \
+        g_ = (v) * __fmaf_rn(-a_, a_, 1.f); \
+        if (jb.dz[0]) jb.dz[L - 2 - l][o_] = g_; \
+      } \
+    } \
+    nxt[(row) * ldx + (n)] = g_; \
+  } while (0)
+#include "hb_mlp_layers.inl"
+#undef HB_MLP_EMIT
+}
+
+// hb_ppo_wgrad_kernel's design over a list of jobs: dW = A^T dZ over one chunk of rows, the A operand of the MFMA being A^T (row i =
+// input column, k = minibatch row), the B operand dZ, both from 16-row LDS tiles.  Wave w owns the output tiles (kt, nt), kt = w and
+// w + 8, nt = 0 .. 15: 32 accumulators, which cover the widest layer (256 x 256).  db: lane n adds column n of every dZ tile in row order.
+__global__ __launch_bounds__(512) void hb_sac_wgrad_kernel(const SacWgDesc d) {
+  __shared__ float sA[16 * 272], sZ[16 * 272];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = blockIdx.x;
+  const int r0 = c * d.chunk, r1 = min(d.mb, r0 + d.chunk);
+  float* out = d.part + (size_t)c * d.P;
+  if ((int)blockIdx.y == d.njob) {
+    // the chunk sums of the by-row terms, in row order (fp64)
+    if (tid < d.ncol) {
+      double s = 0.0;
+      for (int r = r0; r < r1; r++) s += (double)d.srow[(size_t)r * kSacSrow + tid];
+      d.statpart[kSacSrow * c + tid] = s;
+    }
+    return;
+  }
+  const SacWgJob& jb = d.job[blockIdx.y];
+  const int K = jb.K, N = jb.N;
+  const int Kp = (K + 15) / 16 * 16, Np = (N + 15) / 16 * 16, lda = ppo_ld(K), ldz = ppo_ld(N);
+  const int ktiles = Kp / 16, ntiles = Np / 16;
+  const float* A = jb.A;
+  const float* Z = jb.Z;
+  const int col = lane & 15, quad = lane >> 4;
+  f32x4 acc[2][16];
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int j = 0; j < 16; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float bsum = 0.f;
+  for (int t0 = r0; t0 < r1; t0 += 16) {
+    for (int idx = tid; idx < 16 * Kp; idx += 512) {
+      const int row = idx / Kp, k = idx - row * Kp;
+      sA[row * lda + k] = (t0 + row < r1 && k < K) ? A[(size_t)(t0 + row) * K + k] : 0.f;
+    }
+    for (int idx = tid; idx < 16 * Np; idx += 512) {
+      const int row = idx / Np, n = idx - row * Np;
+      sZ[row * ldz + n] = (t0 + row < r1 && n < N) ? Z[(size_t)(t0 + row) * N + n] : 0.f;
+    }
+    __syncthreads();
+    if (wave < ktiles) {
+      const bool two = wave + 8 < ktiles;
+      for (int s = 0; s < 4; s++) {
+        const float a0 = sA[(4 * s + quad) * lda + wave * 16 + col];
+        const float a1 = two ? sA[(4 * s + quad) * lda + (wave + 8) * 16 + col] : 0.f;
+        const float* zp = sZ + (4 * s + quad) * ldz + col;
+#pragma unroll
+        for (int nt = 0; nt < 16; nt++) {
+          if (nt < ntiles) {
+            const float z = zp[nt * 16];
+            acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, z, acc[0][nt], 0, 0, 0);
+            if (two) acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, z, acc[1][nt], 0, 0, 0);
+          }
+        }
+      }
+    }
+    if (tid < N) {
+      for (int row = 0; row < 16; row++) bsum += sZ[row * ldz + tid];
+    }
+    __syncthreads();
+  }
+  float* gw = out + jb.off_w;
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    const int kt = wave + 8 * i;
+    if (kt < ktiles) {
+#pragma unroll
+      for (int nt = 0; nt < 16; nt++) {
+        if (nt < ntiles) {
+          const int n = nt * 16 + col;
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const int k = kt * 16 + 4 * quad + r;
+            if (k < K && n < N) gw[(size_t)k * N + n] = acc[i][nt][r];
+          }
+        }
+      }
+    }
+  }
+  if (tid < N) out[jb.off_b + tid] = bsum;
+}
+
+// One lane per entry of [lo, hi): the chunk partials summed in chunk order.  One more block merges the by-row terms (fp64 sums in chunk
+// order, rounded once): phase 0 - critic_loss, ent_coef_loss, the alpha used, the means of lp_pi, Q1, Q2, y, and dloss / dlog_ent_coef =
+// -(mean lp_pi + target_entropy) into the record's last entry; phase 1 - actor_loss and the mean of min Q(obs, a_pi).
+__global__ __launch_bounds__(256) void hb_sac_reduce_kernel(const SacReduceDesc d) {
+  if (blockIdx.x == gridDim.x - 1) {
+    if (threadIdx.x != 0) return;
+    double s[6] = {0, 0, 0, 0, 0, 0};
+    const int ncol = d.phase == 0 ? 6 : 2;
+    for (int c = 0; c < d.nchunk; c++)
+      for (int j = 0; j < ncol; j++) s[j] += d.statpart[kSacSrow * c + j];
+    const double inv = 1.0 / d.mb;
+    if (d.phase == 0) {
+      const double mlp = s[2] * inv, te = (double)d.target_entropy;
+      d.grad[d.P - 1] = (float)(-(mlp + te));
+      if (d.stats) {
+        for (int j = 0; j < 16; j++) d.stats[j] = 0.f;
+        d.stats[1] = (float)(0.5 * (s[0] * inv + s[1] * inv));
+        d.stats[2] = (float)(-(double)d.param[d.P - 1] * (mlp + te));
+        d.stats[3] = d.alpha[0];
+        d.stats[4] = (float)mlp; d.stats[5] = (float)(s[3] * inv); d.stats[6] = (float)(s[4] * inv); d.stats[7] = (float)(s[5] * inv);
+      }
+    } else if (d.stats) {
+      d.stats[0] = (float)(s[0] * inv);
+      d.stats[8] = (float)(s[1] * inv);
+    }
+    return;
+  }
+  const int i = d.lo + blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.hi) return;
+  float g = 0.f;
+  for (int c = 0; c < d.nchunk; c++) g += d.part[(size_t)c * d.P + i];
+  d.grad[i] = g;
+}
+
+// where entry j of a segment stands in the packed operands (DevMlp::pack_mfma_b of W and of the transpose of its rows k0 ..)
+__device__ __forceinline__ void sac_refresh(const SacSeg& sg, int j, float pf) {
+  if (sg.K == 0) {
+    if (sg.dst) sg.dst[j] = pf;
+    return;
+  }
+  const int k = j / sg.N, n = j - k * sg.N;
+  if (sg.dst) sg.dst[((size_t)(n >> 4) * ((sg.K + 3) / 4) + (k >> 2)) * 64 + (k & 3) * 16 + (n & 15)] = pf;
+  if (sg.dst_t && k >= sg.k0) {
+    const int kt = k - sg.k0;
+    sg.dst_t[((size_t)(kt >> 4) * ((sg.N + 3) / 4) + (n >> 2)) * 64 + (n & 3) * 16 + (kt & 15)] = pf;
+  }
+}
+
+// torch.optim.Adam, one lane per entry of [lo, hi): fp64 on the fp32 gradient, moments and parameter, each result rounded to fp32 once.
+// Pad entries of the packed operands are never written, so they stay zero.
+__global__ __launch_bounds__(256) void hb_sac_adam_kernel(const SacAdamDesc d) {
+  const int i = d.lo + blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.hi) return;
+  const double t = (double)d.t;
+  const double g = (double)d.grad[i];
+  const double b1 = (double)d.beta1, b2 = (double)d.beta2;
+  const double m = b1 * (double)d.m[i] + (1.0 - b1) * g;
+  const double v = b2 * (double)d.v[i] + (1.0 - b2) * g * g;
+  const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+  const double lr = i == d.ent_index ? (double)d.lr_ent : (double)d.lr;
+  const double p = (double)d.param[i] - lr / bc1 * m / (sqrt(v) / sqrt(bc2) + (double)d.eps);
+  const float pf = (float)p;
+  d.m[i] = (float)m; d.v[i] = (float)v; d.param[i] = pf;
+  int sgi = 0;
+  while (sgi + 1 < d.nseg && i >= d.seg[sgi + 1].start) sgi++;
+  sac_refresh(d.seg[sgi], i - d.seg[sgi].start, pf);
+}
+
+// Q' = tau Q + (1 - tau) Q' in fp64, rounded once, one lane per entry of the targets' record
+__global__ __launch_bounds__(256) void hb_sac_polyak_kernel(const SacPolyakDesc d) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= d.n) return;
+  const double tau = (double)d.tau;
+  const float pf = (float)(tau * (double)d.src[i] + (1.0 - tau) * (double)d.target[i]);
+  d.target[i] = pf;
+  int sgi = 0;
+  while (sgi + 1 < d.nseg && i >= d.seg[sgi + 1].start) sgi++;
+  sac_refresh(d.seg[sgi], i - d.seg[sgi].start, pf);
+}
+
+static size_t sac_shmem(int ldx) { return ((size_t)32 * ldx + 8 * 256) * sizeof(float); }  // two activation tiles + the split-K partial tiles
+
+hipError_t launch_sac_forward(const SacFwdDesc& d, int njob, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (d.mb < 1 || njob < 1 || njob > 4) return hipErrorInvalidValue;
+  int ldx = 1;
+  for (int j = 0; j < njob; j++) {
+    const SacFwdJob& jb = d.job[j];
+    if (jb.net.nl < 1 || jb.net.nl > 4 || jb.n0 < 1 || jb.n1 < 0 || jb.n0 + jb.n1 != jb.net.sizes[0] || !jb.x0 || (jb.n1 && !jb.x1) || !jb.out) return hipErrorInvalidValue;
+    for (int l = 0; l <= jb.net.nl; l++) if (jb.net.sizes[l] < 1 || jb.net.sizes[l] + 4 > jb.net.ldx) return hipErrorInvalidValue;
+    ldx = max(ldx, jb.net.ldx);
+  }
+  if (sac_shmem(ldx) > 64 * 1024) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hb_sac_forward_kernel, dim3((d.mb + 15) / 16, njob), dim3(512), sac_shmem(ldx), stream, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_sac_head(const SacHeadDesc& d, int what, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (d.mb < 1 || d.nu < 1 || d.nu > kActorMaxNu || d.P < 1 || what < 0 || what > 2) return hipErrorInvalidValue;
+  if (d.eps_given && (!d.eps_pi || !d.eps_next)) return hipErrorInvalidValue;
+  const dim3 grid((d.mb + 255) / 256);
+  if (what == 0) hipLaunchKernelGGL(hb_sac_sample_kernel, grid, dim3(256), 0, stream, d);
+  else if (what == 1) hipLaunchKernelGGL(hb_sac_critic_head_kernel, grid, dim3(256), 0, stream, d);
+  else hipLaunchKernelGGL(hb_sac_actor_head_kernel, grid, dim3(256), 0, stream, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_sac_backprop(const SacBwdDesc& d, int njob, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (d.mb < 1 || njob < 1 || njob > 2) return hipErrorInvalidValue;
+  int ldx = 1;
+  for (int j = 0; j < njob; j++) {
+    const SacBwdJob& jb = d.job[j];
+    if (jb.net.nl < 0 || jb.net.nl > jb.L || jb.L < 1 || jb.L > 4 || (!jb.unit_top && !jb.top) || (jb.net.nl == jb.L && !jb.da)) return hipErrorInvalidValue;
+    for (int l = 0; l <= jb.net.nl; l++) if (jb.net.sizes[l] < 1 || jb.net.sizes[l] + 4 > jb.net.ldx) return hipErrorInvalidValue;
+    ldx = max(ldx, jb.net.ldx);
+  }
+  if (sac_shmem(ldx) > 64 * 1024) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hb_sac_backprop_kernel, dim3((d.mb + 15) / 16, njob), dim3(512), sac_shmem(ldx), stream, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_sac_wgrad(const SacWgDesc& d, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (d.mb < 1 || d.njob < 1 || d.njob > 8 || d.chunk < 1 || d.nchunk != (d.mb + d.chunk - 1) / d.chunk || d.nchunk > 64 || d.ncol < 1 || d.ncol > kSacSrow) return hipErrorInvalidValue;
+  for (int j = 0; j < d.njob; j++) {
+    const SacWgJob& jb = d.job[j];
+    if (jb.K < 1 || jb.K > 256 || jb.N < 1 || jb.N > 256 || jb.off_w < 0 || jb.off_b < 0 || jb.off_w + jb.K * jb.N > d.P || jb.off_b + jb.N > d.P) return hipErrorInvalidValue;
+  }
+  hipLaunchKernelGGL(hb_sac_wgrad_kernel, dim3(d.nchunk, d.njob + 1), dim3(512), 0, stream, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_sac_reduce(const SacReduceDesc& d, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (d.lo < 0 || d.hi <= d.lo || d.hi > d.P || d.nchunk < 1 || d.nchunk > 64 || d.mb < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hb_sac_reduce_kernel, dim3((d.hi - d.lo + 255) / 256 + 1), dim3(256), 0, stream, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_sac_adam(const SacAdamDesc& d, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (d.lo < 0 || d.hi <= d.lo || d.nseg < 1 || d.nseg > kSacMaxSeg || d.seg[0].start != d.lo || d.t < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hb_sac_adam_kernel, dim3((d.hi - d.lo + 255) / 256), dim3(256), 0, stream, d);
+  return hipGetLastError();
+}
+
+hipError_t launch_sac_polyak(const SacPolyakDesc& d, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (d.n < 1 || d.nseg < 1 || d.nseg > kSacMaxSeg || d.seg[0].start != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hb_sac_polyak_kernel, dim3((d.n + 255) / 256), dim3(256), 0, stream, d);
+  return hipGetLastError();
+}
+
+}  // namespace hb

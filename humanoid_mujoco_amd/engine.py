@@ -236,6 +236,60 @@ def ppo_row_chunk(mb):
     return int(lib().hb_ppo_row_chunk(int(mb)))
 
 
+class HbSacConfig(ctypes.Structure):
+    """hb_sac_config (include/hb.h): the hyper-parameters of the SAC learner, stable-baselines3's defaults."""
+    _fields_ = [(n, ctypes.c_float) for n in ("gamma", "tau", "lr_actor", "lr_critic", "lr_ent", "beta1", "beta2", "eps", "ent_coef_init")] + \
+               [("auto_ent", ctypes.c_int), ("target_entropy_auto", ctypes.c_int), ("target_entropy", ctypes.c_float),
+                ("target_update_interval", ctypes.c_int), ("seed", ctypes.c_uint)]
+
+
+class HbSacRows(ctypes.Structure):
+    """hb_sac_rows (include/hb.h): device pointers of the replay rows, the minibatch (index, or first .. first + mb - 1) and the draws."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("obs", "action", "reward", "next_obs", "done", "index")] + \
+               [("n_rows", ctypes.c_longlong), ("first", ctypes.c_longlong), ("mb", ctypes.c_int), ("eps_pi", ctypes.c_void_p),
+                ("eps_next", ctypes.c_void_p), ("eps_given", ctypes.c_int)]
+
+
+# the statistics hb_sac_step_dev leaves in its float[16] (include/hb.h), in order
+SAC_STATS = ("actor_loss", "critic_loss", "ent_coef_loss", "ent_coef", "lp_pi", "q1", "q2", "y", "min_q_pi")
+
+
+def sac_flat_shapes(actor_sizes, q_sizes):
+    """The tensors of the SAC learner's flat record in order, as (name, shape): the actor's layers W [K, N] | b [N], Q1's, Q2's,
+    log_ent_coef [1] (include/hb.h: hb_sac_get_params).  The targets' record mirrors the q1.*, q2.* stretch."""
+    out = []
+    for tag, sizes in (("actor", actor_sizes), ("q1", q_sizes), ("q2", q_sizes)):
+        for l in range(len(sizes) - 1):
+            out += [("%s.w%d" % (tag, l), (int(sizes[l]), int(sizes[l + 1]))), ("%s.b%d" % (tag, l), (int(sizes[l + 1]),))]
+    out.append(("log_ent_coef", (1,)))
+    return out
+
+
+def sac_split(flat, actor_sizes, q_sizes):
+    """The flat record as a dict of per-tensor arrays (copies): actor.w0, actor.b0, ..., q1.w0, ..., q2.w0, ..., log_ent_coef."""
+    flat = np.asarray(flat)
+    shapes = sac_flat_shapes(actor_sizes, q_sizes)
+    if flat.shape != (sum(int(np.prod(sh)) for _, sh in shapes),):
+        raise ValueError("sac_split: the record of these networks holds %d values" % sum(int(np.prod(sh)) for _, sh in shapes))
+    out, o = {}, 0
+    for name, sh in shapes:
+        n = int(np.prod(sh))
+        out[name] = flat[o:o + n].reshape(sh).copy()
+        o += n
+    return out
+
+
+def sac_join(tensors, actor_sizes, q_sizes, dtype=np.float32):
+    """The inverse of sac_split."""
+    parts = []
+    for name, sh in sac_flat_shapes(actor_sizes, q_sizes):
+        a = np.asarray(tensors[name], dtype=dtype)
+        if a.shape != sh:
+            raise ValueError("sac_join: %s must be %s" % (name, sh))
+        parts.append(a.ravel())
+    return np.concatenate(parts)
+
+
 class HbError(RuntimeError):
     pass
 
@@ -372,6 +426,19 @@ def lib():
     L.hb_ppo_grad_dev.argtypes = [vp, ctypes.POINTER(HbPpoRows), vp]
     L.hb_ppo_adam_dev.argtypes = [vp, vp]
     L.hb_ppo_minibatch_dev.argtypes = [vp, ctypes.POINTER(HbPpoRows), vp]
+    ll = ctypes.c_longlong
+    L.hb_q_set_mlp.argtypes = [vp, ci, ci, vp, vp, vp]
+    L.hb_q_values_dev.argtypes = [vp, vp, vp, ll, vp, vp]
+    L.hb_sac_default_config.argtypes = [ctypes.POINTER(HbSacConfig)]
+    L.hb_sac_create.argtypes = [vp, ctypes.POINTER(HbSacConfig)]
+    L.hb_sac_configure.argtypes = [vp, ctypes.POINTER(HbSacConfig)]
+    L.hb_sac_destroy.argtypes = [vp]
+    L.hb_sac_param_count.argtypes = [vp]; L.hb_sac_param_count.restype = ll
+    L.hb_sac_target_count.argtypes = [vp]; L.hb_sac_target_count.restype = ll
+    L.hb_sac_get_params.argtypes = [vp, vp, ll]; L.hb_sac_set_params.argtypes = [vp, vp, ll]; L.hb_sac_get_grads.argtypes = [vp, vp, ll]
+    L.hb_sac_get_state.argtypes = [vp, vp, vp, vp, ll, vp, ll, ctypes.POINTER(ll)]
+    L.hb_sac_set_state.argtypes = [vp, vp, vp, vp, ll, vp, ll, ll]
+    L.hb_sac_step_dev.argtypes = [vp, ctypes.POINTER(HbSacRows), vp]
     L.hb_dev_alloc.restype = vp; L.hb_dev_alloc.argtypes = [vp, ctypes.c_uint64]
     L.hb_dev_free.restype = None; L.hb_dev_free.argtypes = [vp, vp]
     L.hb_host_alloc.restype = vp; L.hb_host_alloc.argtypes = [ctypes.c_uint64]
@@ -1403,6 +1470,110 @@ class Batch:
         """hb_ppo_minibatch_dev: ppo_grad_dev, then ppo_adam_dev."""
         rows = HbPpoRows(obs, action, old_log_prob, advantage, returns, index, int(n_rows), int(first), int(mb))
         _check(lib().hb_ppo_minibatch_dev(self._h, ctypes.byref(rows), ctypes.c_void_p(stats or 0)), "hb_ppo_minibatch_dev", self._PPO_WHY)
+
+    # ---- the Q networks and the SAC learner (include/hb.h: hb_q_*, hb_sac_*)
+    def q_set(self, k, sizes, weights, biases):
+        """Installs Q network k (0 or 1).  sizes: [nobs + nu, hidden..., 1] - the input row is obs | action; weights[l]: [sizes[l],
+        sizes[l+1]] float32 - the TRANSPOSE of torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; tanh after every hidden layer, the last
+        layer linear.  At most four layers of width <= 256.  Destroys a SAC learner of this batch."""
+        ws, bs, csz, wp, bp = _mlp_args("q_set", weights, biases, sizes)
+        rc = lib().hb_q_set_mlp(self._h, int(k), len(ws), csz, wp, bp)
+        _check(rc, "hb_q_set_mlp", "a layer wider than 256: the Q network is one fused kernel, there is no layer-by-layer path" if rc == -4 else
+               "k is 0 or 1, sizes must run from nobs + nu to 1 over 1..4 layers" if rc == -1 else None)
+
+    def q_values_dev(self, obs, action, n_rows, q1=None, q2=None):
+        """hb_q_values_dev: Q1 and Q2 over n_rows rows obs [n_rows, nobs] | action [n_rows, nu] into q1, q2 [n_rows] (device pointers,
+        at least one), one launch on the batch's stream."""
+        rc = lib().hb_q_values_dev(self._h, ctypes.c_void_p(obs or 0), ctypes.c_void_p(action or 0), int(n_rows), ctypes.c_void_p(q1 or 0), ctypes.c_void_p(q2 or 0))
+        _check(rc, "hb_q_values_dev", "needs obs, action, n_rows >= 1 and an output whose Q network is installed (q_set)")
+
+    _SAC_WHY = "needs a SAC learner (sac_create), the five tapes, 1 <= mb, first + mb <= n_rows without an index, and both eps with eps_given"
+    _SAC_CFG_WHY = ("gamma and tau in [0, 1], learning rates >= 0, betas in [0, 1), eps > 0, ent_coef_init > 0, "
+                    "target_update_interval >= 1, all finite")
+
+    def _sac_config(self, what, cfg, base=None):
+        c = HbSacConfig()
+        if base is not None:
+            ctypes.memmove(ctypes.byref(c), ctypes.byref(base), ctypes.sizeof(c))
+        else:
+            _check(lib().hb_sac_default_config(ctypes.byref(c)), "hb_sac_default_config")
+        names = dict(HbSacConfig._fields_)
+        for k, v in cfg.items():
+            if k not in names:
+                raise ValueError("%s: unknown hyper-parameter %r (one of %s)" % (what, k, ", ".join(names)))
+            if k == "target_entropy" and "target_entropy_auto" not in cfg:
+                c.target_entropy_auto = 0
+            setattr(c, k, int(v) if names[k] in (ctypes.c_int, ctypes.c_uint) else float(v))
+        return c
+
+    def sac_create(self, **cfg):
+        """Creates the SAC learner over the installed actor (squashed head) and Q networks: they become the trainable parameters, the
+        targets are made as copies of Q1 and Q2, log_ent_coef = log(ent_coef_init), Adam moments of zero and t = 0.  cfg: the fields of
+        hb_sac_config (stable-baselines3's defaults where not given; a target_entropy switches target_entropy_auto off)."""
+        c = self._sac_config("sac_create", cfg)
+        rc = lib().hb_sac_create(self._h, ctypes.byref(c))
+        _check(rc, "hb_sac_create", "the SAC learner trains the squashed head only (actor_set(head=\"squashed\")); the Gaussian head is the "
+               "PPO learner's" if rc == -4 else "needs an actor and two Q networks of equal sizes (q_set); " + self._SAC_CFG_WHY if rc == -1 else None)
+        self._sac_cfg = c
+
+    def sac_configure(self, **cfg):
+        """Changes hyper-parameters and keeps parameters, moments, targets and t; those not named stay."""
+        c = self._sac_config("sac_configure", cfg, getattr(self, "_sac_cfg", None))
+        _check(lib().hb_sac_configure(self._h, ctypes.byref(c)), "hb_sac_configure", "needs a SAC learner; " + self._SAC_CFG_WHY)
+        self._sac_cfg = c
+
+    def sac_destroy(self):
+        _check(lib().hb_sac_destroy(self._h), "hb_sac_destroy", "no SAC learner")
+
+    def sac_param_count(self):
+        n = lib().hb_sac_param_count(self._h)
+        _check(0 if n >= 0 else int(n), "hb_sac_param_count", "no SAC learner")
+        return int(n)
+
+    def sac_target_count(self):
+        n = lib().hb_sac_target_count(self._h)
+        _check(0 if n >= 0 else int(n), "hb_sac_target_count", "no SAC learner")
+        return int(n)
+
+    def sac_params(self):
+        """the parameters as the flat float32 record (sac_split gives the per-layer arrays)"""
+        out = np.zeros(self.sac_param_count(), dtype=np.float32)
+        _check(lib().hb_sac_get_params(self._h, _ptr(out), out.size), "hb_sac_get_params")
+        return out
+
+    def sac_set_params(self, flat):
+        a = np.ascontiguousarray(flat, dtype=np.float32)
+        _check(lib().hb_sac_set_params(self._h, _ptr(a), a.size if a.ndim == 1 else -1), "hb_sac_set_params",
+               "needs a SAC learner and a flat record of sac_param_count() values")
+
+    def sac_grads(self):
+        """the gradients the last step used, flat layout"""
+        out = np.zeros(self.sac_param_count(), dtype=np.float32)
+        _check(lib().hb_sac_get_grads(self._h, _ptr(out), out.size), "hb_sac_get_grads")
+        return out
+
+    def sac_state(self):
+        """{"params", "m", "v": flat float32 records, "targets": the targets' record (Q1' then Q2'), "t": the step count}: checkpoint"""
+        n, nt = self.sac_param_count(), self.sac_target_count()
+        p, m, v = (np.zeros(n, dtype=np.float32) for _ in range(3))
+        tg = np.zeros(nt, dtype=np.float32)
+        t = ctypes.c_longlong()
+        _check(lib().hb_sac_get_state(self._h, _ptr(p), _ptr(m), _ptr(v), n, _ptr(tg), nt, ctypes.byref(t)), "hb_sac_get_state")
+        return {"params": p, "m": m, "v": v, "targets": tg, "t": int(t.value)}
+
+    def sac_set_state(self, state):
+        p, m, v, tg = (np.ascontiguousarray(state[k], dtype=np.float32) for k in ("params", "m", "v", "targets"))
+        n = p.size if p.ndim == 1 and p.shape == m.shape == v.shape else -1
+        _check(lib().hb_sac_set_state(self._h, _ptr(p), _ptr(m), _ptr(v), n, _ptr(tg), tg.size if tg.ndim == 1 else -1, int(state["t"])),
+               "hb_sac_set_state", "needs a SAC learner, three flat records of sac_param_count() values, sac_target_count() targets and t >= 0")
+
+    def sac_step_dev(self, obs, action, reward, next_obs, done, n_rows, mb, index=None, first=0, eps_pi=None, eps_next=None, eps_given=False,
+                     stats=None):
+        """hb_sac_step_dev: one SAC gradient step on a minibatch, enqueued on the batch's stream.  Device pointers of the replay rows
+        ([n_rows, ...]; done uint8); index: device int32 [mb], or None for rows first .. first + mb - 1; eps_pi, eps_next: device float32
+        [mb, nu], written with the draws (eps_given False) or read (True); stats: device float32 [16] (SAC_STATS)."""
+        rows = HbSacRows(obs, action, reward, next_obs, done, index, int(n_rows), int(first), int(mb), eps_pi, eps_next, int(bool(eps_given)))
+        _check(lib().hb_sac_step_dev(self._h, ctypes.byref(rows), ctypes.c_void_p(stats or 0)), "hb_sac_step_dev", self._SAC_WHY)
 
     # ---- running observation / reward normalisation and episode statistics (include/hb.h: hb_norm_*)
     _NORM_WHY = "needs a normaliser (norm_configure) and the required device pointers"

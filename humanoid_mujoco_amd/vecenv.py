@@ -646,6 +646,52 @@ class VecEnv:
         log.update(n_minibatches=done, n_updates=self._ppo_epochs, early_stop=stopped)
         return log
 
+    # ---- the SAC learner on the device (Batch.sac_create, sac_step_dev)
+    def q_set(self, k, sizes, weights, biases):
+        """Installs Q network k (0 or 1) of the SAC learner (Batch.q_set: sizes [nobs + nu, hidden..., 1] over the row obs | action,
+        weights[l] is [in, out], the transpose of torch.nn.Linear.weight; tanh hidden layers, linear output)."""
+        self.batch.q_set(k, sizes, weights, biases)
+
+    def sac_learner(self, **cfg):
+        """Creates the SAC learner over the networks of actor_set (squashed head) and q_set, which become the trainable parameters: what
+        collect_torch runs afterwards is whatever sac_update left, with no actor_set in between.  cfg: the fields of hb_sac_config -
+        stable-baselines3's defaults where not given; seed defaults to this VecEnv's seed."""
+        cfg.setdefault("seed", self.seed_value & 0xFFFFFFFF)
+        self.batch.sac_create(**cfg)
+        self._sac_updates = self._sac_steps = 0
+
+    def sac_update(self, replay, gradient_steps, batch_size=256, seed=None):
+        """stable-baselines3's SAC.train over a ReplayBuffer on this VecEnv's device: gradient_steps calls of Batch.sac_step_dev (sixteen
+        launches each), every one on batch_size rows drawn uniformly from the filled part of the ring (torch.randint from a device
+        generator seeded by (seed, the number of sac_update calls so far)), all on the batch's stream.  Nothing in the loop touches the
+        host: the statistics of every step stay on the device and are read once at the end.  Returns their means (engine.SAC_STATS) and
+        "n_updates" (gradient steps since the learner was created, SB3's counter).  Streams are ordered as in ppo_update."""
+        import torch
+        from .engine import SAC_STATS
+        if batch_size < 1 or gradient_steps < 1:
+            raise ValueError("sac_update: gradient_steps and batch_size must be at least 1")
+        dev = torch.device("cuda", self._device)
+        if replay.device != dev:
+            raise ValueError("sac_update: the replay buffer lives on %s, the learner on %s" % (replay.device, dev))
+        seed = self.seed_value if seed is None else int(seed)
+        g = torch.Generator(device=dev)
+        g.manual_seed((seed * 1000003 + getattr(self, "_sac_updates", 0)) % (1 << 62))
+        index = replay.sample_index(int(gradient_steps) * int(batch_size), g)
+        stats = torch.zeros((int(gradient_steps), 16), dtype=torch.float32, device=dev)
+        ptrs = [x.data_ptr() for x in (replay.obs, replay.action, replay.reward, replay.next_obs, replay.done)]
+        stream = torch.cuda.ExternalStream(self.batch.stream, device=dev)  # (fetching the stream launches held step calls and joins the pipes)
+        cur = torch.cuda.current_stream(dev)
+        stream.wait_stream(cur)  # the ring, the indices and the zeroed statistics are complete
+        for k in range(int(gradient_steps)):
+            self.batch.sac_step_dev(*ptrs, replay.capacity, int(batch_size), index=index.data_ptr() + 4 * k * int(batch_size), stats=stats[k].data_ptr())
+        cur.wait_stream(stream)  # the caller's stream is behind the update: the ring and the indices may be reused on it
+        self._sac_updates = getattr(self, "_sac_updates", 0) + 1
+        rows = stats.double().mean(dim=0).cpu().numpy()
+        log = {k: float(rows[i]) for i, k in enumerate(SAC_STATS)}
+        self._sac_steps = getattr(self, "_sac_steps", 0) + int(gradient_steps)
+        log["n_updates"] = self._sac_steps
+        return log
+
     def close(self):
         if getattr(self, "_norm_dev", None) is not None:
             self.batch.dev_free(self._norm_dev["obs"])

@@ -1042,7 +1042,7 @@ int hb_ppo_default_config(hb_ppo_config* cfg);
  * trained log_std behind hb_critic_set_mlp, and with the log_std of its new config behind hb_actor_set_mlp.
  * HB_EINVAL: NULL argument; no actor or no critic; a hyper-parameter that is not finite or out of range (clip_range <= 0, a beta
  * outside [0, 1), lr < 0, eps <= 0); configure / destroy without a learner.  HB_EUNSUPPORTED: the deterministic head, and the squashed
- * head (HB_ACTOR_SQUASHED, SAC's actor: an off-policy learner is not part of this library).  A refused call changes nothing. */
+ * head (HB_ACTOR_SQUASHED, SAC's actor: its learner is hb_sac_create, below).  A refused call changes nothing. */
 int hb_learner_create(hb_batch* b, const hb_ppo_config* cfg);
 int hb_learner_configure(hb_batch* b, const hb_ppo_config* cfg);
 int hb_learner_destroy(hb_batch* b);
@@ -1101,6 +1101,121 @@ int hb_ppo_grad_dev(hb_batch* b, const hb_ppo_rows* rows, float* stats_dev);
 int hb_ppo_adam_dev(hb_batch* b, float* stats_dev);
 /* hb_ppo_grad_dev, then hb_ppo_adam_dev: seven launches. */
 int hb_ppo_minibatch_dev(hb_batch* b, const hb_ppo_rows* rows, float* stats_dev);
+
+/* ---- the SAC learner on the device: twin Q critics, squashed Gaussian actor, entropy coefficient, Polyak targets, Adam -------- */
+
+/* The update rule is stable-baselines3's SAC.train, restated here [neither package is a dependency; tests/sac_ref.py is the fp64
+ * restatement the kernels are held to].  Networks (tanh after every hidden layer, linear at the top, at most four layers of width
+ * <= 256; SB3's SAC default is ReLU - a stated difference): the ACTOR, the installed HB_ACTOR_SQUASHED network obs[nobs] -> 2 nu
+ * (mean | raw log_std); Q1 and Q2, two networks of equal sizes [nobs + nu] -> 1 whose input row is obs | action; the TARGETS Q1', Q2',
+ * created as copies.  One gradient step on mb rows (obs, action, reward, next_obs, done), with alpha = exp(log_ent_coef) at the START of
+ * the step, ls = clamp(raw_ls, -20, 2), s = exp(ls):
+ *   pi:     x = mean(obs) + s(obs) eps_pi,  a_pi = tanh(x),
+ *           lp_pi = sum_i (-eps_i^2 / 2 - ls_i - log(2 pi) / 2) - sum_i 2 (log 2 - x_i - softplus(-2 x_i))   (hb_collect_gae_dev's head 2)
+ *   next:   the same on next_obs with eps_next: a', lp'
+ *   ent:    ent_coef_loss = -mean_r (log_ent_coef (lp_pi_r + target_entropy)), lp_pi a constant; auto_ent: Adam on log_ent_coef
+ *   target: y_r = reward_r + (1 - done_r) gamma (min(Q1'(next_obs, a'), Q2'(next_obs, a')) - alpha lp'_r), a constant
+ *   critic: critic_loss = (mean_r (Q1(obs, action) - y)^2 + mean_r (Q2(obs, action) - y)^2) / 2; dloss/dQk_r = (Qk_r - y_r) / mb; Adam on
+ *           Q1, Q2
+ *   actor:  with the UPDATED Q1, Q2: actor_loss = mean_r (alpha lp_pi_r - min(Q1(obs, a_pi), Q2(obs, a_pi))), the gradient through a_pi
+ *           and lp_pi into the actor only; Adam on the actor
+ *   polyak: when the step count t, this step included, is a multiple of target_update_interval: Q' = tau Q + (1 - tau) Q'.  (SB3 counts
+ *           the gradient steps of one train() call from 0; here the count is the learner's t, which a checkpoint carries.)
+ * Gradients are autograd's: torch.clamp passes the gradient where -20 <= raw_ls <= 2 (bounds included) and nothing outside; torch.min
+ * sends it to the smaller Q, and on an exact tie half to each; with g_i = d min Q / da_i:  dlp/dmean_i = 2 a_i,
+ * dlp/dls_i = -1 + 2 a_i s_i eps_i, da_i/dx_i = 1 - a_i^2, mb dL/dmean_i = 2 alpha a_i - g_i (1 - a_i^2),
+ * mb dL/dls_i = alpha (-1 + 2 a_i s_i eps_i) - g_i (1 - a_i^2) s_i eps_i.  [tests/test_sac_cpu.py holds all of it to torch autograd in
+ * float64: no disagreement was found.]  The log-probability is not SB3's log(1 - a^2 + 1e-6): the same stated difference as in
+ * hb_collect_gae_dev.
+ * Adam is torch.optim.Adam per group (actor, critics, log_ent_coef), each with its own learning rate; no gradient clipping and no skip
+ * logic, as SB3's SAC has none; ONE step count t serves all groups; with auto_ent = 0 log_ent_coef is never stepped.
+ * Arithmetic follows the PPO learner: matrix products are v_mfma_f32_16x16x4_f32 (exact f32); row reductions go over chunks of
+ * hb_ppo_row_chunk(mb) rows in row order, merged in chunk order; the statistics, alpha, the Adam and the Polyak step are formed in fp64
+ * and rounded to fp32 once.  No atomics: the same call gives the same bits.
+ * Draws: eps_pi[r][i] = rng_normal(seed, minibatch row r, 0, t, stream 33, element i), eps_next on stream 34 (RS_ACTOR is 32, the realism
+ * layer uses 1..8, domain randomisation 16..25), t being the step count BEFORE the step.
+ * NOT provided: a multi-GPU gradient all-reduce (the step would have to be split at two points), gSDE / use_sde, more than two critics. */
+
+/* Installs Q network k (0 or 1): an MLP [nobs + nu] -> sizes[1] -> ... -> 1 over the row obs | action, hb_critic_set_mlp's conventions
+ * and checks (HB_EINVAL: NULL argument, k outside 0..1, n_layers outside 1..4, a size < 1, sizes[0] != nobs + nu, sizes[n_layers] != 1;
+ * HB_EUNSUPPORTED: a width above 256).  Independent of the actor, the PPO critic and the MLP of hb_policy_set_mlp.  On a batch with a
+ * SAC learner the call destroys that learner (so does hb_actor_set_mlp): create it again.  A refused call changes nothing. */
+int hb_q_set_mlp(hb_batch* b, int k, int n_layers, const int* sizes, const float* const* weights, const float* const* biases);
+/* Q1 and Q2 over n_rows rows: obs [n_rows][nobs], action [n_rows][nu] -> q1_out, q2_out [n_rows] (device pointers, either output nullable,
+ * not both), ONE launch on the batch's stream, nothing kept.  HB_EINVAL: NULL b, obs or action, both outputs NULL, n_rows < 1 or above
+ * 2^31 - 1, an output whose network is not installed. */
+int hb_q_values_dev(hb_batch* b, const float* obs, const float* action, long long n_rows, float* q1_out, float* q2_out);
+
+typedef struct hb_sac_config {
+  float gamma;                  /* 0.99    in [0, 1] */
+  float tau;                    /* 0.005   in [0, 1] */
+  float lr_actor, lr_critic, lr_ent;  /* 3e-4 each   >= 0 */
+  float beta1, beta2;           /* 0.9, 0.999   in [0, 1) */
+  float eps;                    /* 1e-8    > 0 */
+  float ent_coef_init;          /* 1.0     > 0; read by hb_sac_create alone: log_ent_coef = log(ent_coef_init) */
+  int auto_ent;                 /* 1       0: log_ent_coef stays what it is */
+  int target_entropy_auto;      /* 1       target_entropy = -nu */
+  float target_entropy;         /* 0       read when target_entropy_auto is 0 */
+  int target_update_interval;   /* 1       >= 1 */
+  unsigned seed;                /* 0       of the draws */
+} hb_sac_config;
+int hb_sac_default_config(hb_sac_config* cfg);
+
+/* Creates the batch's SAC learner: the installed actor (its head must be HB_ACTOR_SQUASHED) and both Q networks become the trainable
+ * parameters - the actor hb_env_collect_dev runs IS the learner's.  Makes the targets as copies of Q1 and Q2, sets
+ * log_ent_coef = log(ent_coef_init), zeroes the moments, t = 0.  A SAC learner that exists is replaced.  hb_sac_configure changes the
+ * hyper-parameters and touches no state.  hb_actor_set_mlp or hb_q_set_mlp on a batch with a SAC learner destroys it.  A PPO learner
+ * (hb_learner_create) needs the Gaussian head, this one the squashed head: a batch never holds both.
+ * HB_EINVAL: NULL argument; no actor, a Q network missing, Q1 and Q2 of unequal sizes; a hyper-parameter that is not finite or out of
+ * range (above); configure / destroy without a learner.  HB_EUNSUPPORTED: any other actor head.  A refused call changes nothing. */
+int hb_sac_create(hb_batch* b, const hb_sac_config* cfg);
+int hb_sac_configure(hb_batch* b, const hb_sac_config* cfg);
+int hb_sac_destroy(hb_batch* b);
+
+/* The flat record, P = hb_sac_param_count(b) floats: the actor's layers in order, each W[sizes[l]][sizes[l+1]] row-major followed by
+ * b[sizes[l+1]]; then Q1's layers, then Q2's, then log_ent_coef.  Parameters, gradients and both moments use it.  The targets' record,
+ * PT = hb_sac_target_count(b) floats: Q1' then Q2' in the same layer layout.  Host pointers; every call runs behind the work enqueued so
+ * far and ends synchronised.  get_grads after a step returns the gradients that step USED: the critic and log_ent_coef entries come from
+ * its critic phase (the log_ent_coef entry is formed whether or not auto_ent steps it), the actor entries from its actor phase, which
+ * forms no dW of the Q networks.  set_params / set_state also refresh every operand the kernels read; set_params leaves the targets.
+ * HB_EINVAL: NULL argument, no learner, a wrong count, t < 0. */
+long long hb_sac_param_count(hb_batch* b);
+long long hb_sac_target_count(hb_batch* b);
+int hb_sac_get_params(hb_batch* b, float* out, long long count);
+int hb_sac_set_params(hb_batch* b, const float* in, long long count);
+int hb_sac_get_grads(hb_batch* b, float* out, long long count);
+int hb_sac_get_state(hb_batch* b, float* params, float* m, float* v, long long count, float* targets, long long target_count, long long* t);
+int hb_sac_set_state(hb_batch* b, const float* params, const float* m, const float* v, long long count, const float* targets, long long target_count, long long t);
+
+typedef struct hb_sac_rows {     /* device pointers */
+  const float* obs;              /* [n_rows][nobs] */
+  const float* action;           /* [n_rows][nu] */
+  const float* reward;           /* [n_rows] */
+  const float* next_obs;         /* [n_rows][nobs] */
+  const uint8_t* done;           /* [n_rows]  terminated (an env cut by truncation alone bootstraps) */
+  const int32_t* index;          /* [mb] row numbers in any order, repeats allowed; NULL: rows first .. first + mb - 1 */
+  long long n_rows, first;
+  int mb;
+  float* eps_pi;                 /* [mb][nu], nullable unless eps_given */
+  float* eps_next;               /* [mb][nu], nullable unless eps_given */
+  int eps_given;                 /* 0: the draws are made on the device and written to the pointers that are given; 1: they are read */
+} hb_sac_rows;
+
+/* One gradient step as above, asynchronous on the batch's stream: SIXTEEN launches whatever mb is (fifteen on a step whose count is no
+ * multiple of target_update_interval) - forward of the actor on obs and next_obs and of Q1, Q2; the samples by row; forward of the
+ * targets; the critic head by row; back-propagation, dW partials, their merge and Adam for Q1, Q2 (and log_ent_coef); forward of the
+ * updated Q1, Q2 at a_pi; their back-propagation into the action inputs; the actor head by row; back-propagation, dW partials, merge and
+ * Adam for the actor; the Polyak step.  No host synchronisation, no host transfer, no allocation beyond the learner's scratch, which
+ * grows with mb (a call that has to grow it waits for the stream first).  The Adam and Polyak kernels rewrite every updated weight in
+ * the packed operands the forward kernels read and in the packed transposes, so the next hb_env_collect_dev runs the new actor; pad
+ * entries are never written.  A pure function of the rows, the draws and the learner's state: nothing else of the batch is written -
+ * state, the collection's draw counter, status words, hb_last_kernel and hb_batch_step_launches stay.  Rows outside the minibatch are
+ * not read; the values of index[] are not checked.
+ * stats_dev: NULL or a device float[16]: actor_loss, critic_loss, ent_coef_loss, ent_coef (the alpha used), the means of lp_pi,
+ * Q1(obs, action), Q2(obs, action), y and min Q(obs, a_pi), then zeros.
+ * HB_EINVAL: NULL b or rows, no learner, a NULL tape, mb < 1, n_rows < 1, first < 0 or first + mb > n_rows (index NULL), eps_given with a
+ * NULL eps_pi or eps_next.  A refused call writes nothing. */
+int hb_sac_step_dev(hb_batch* b, const hb_sac_rows* rows, float* stats_dev);
 
 /* ---- host-side helpers so a C/C++/ctypes caller needs no HIP headers ---------------------------- */
 
