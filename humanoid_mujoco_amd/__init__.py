@@ -7,7 +7,7 @@ plus the VecEnv-shaped adapter in ``vecenv.py``.
 from .engine import (Batch, HbError, Model, lib, LIB_PATH, INT_EULER, INT_RK4, STATE_INTEGRATION, STATE_PHYSICS, STATE_QPOS, STATE_QVEL,  # noqa: F401
                      STATE_TIME, STATE_WARMSTART, STATE_XFRC_APPLIED, WARN_BADQACC, WARN_BADQPOS, WARN_BADQVEL,
                      WARN_CNSTRFULL, WARN_CONTACTFULL, quat_to_mat, height_scan_rays, RAY_STATIC, RAY_MOVING, HbJacSpec, MAX_JAC, JAC_POINT, JAC_SUBTREE_COM,
-                     ACTOR_DETERMINISTIC, ACTOR_GAUSSIAN, ACTOR_SQUASHED, RS_ACTOR, HbActorConfig, HbCollectOut, HbGaeConfig, HbGaeOut, HbNormConfig, HbNormIo, HbNormTapes, HbSacConfig, HbSacRows, SAC_STATS, sac_flat_shapes, sac_split, sac_join)
+                     ACTOR_DETERMINISTIC, ACTOR_GAUSSIAN, ACTOR_SQUASHED, ACT_TANH, ACT_RELU, ACT_ELU, NET_POLICY, NET_ACTOR, NET_CRITIC, NET_Q1, NET_Q2, RS_ACTOR, HbActorConfig, HbCollectOut, HbGaeConfig, HbGaeOut, HbNormConfig, HbNormIo, HbNormTapes, HbSacConfig, HbSacRows, SAC_STATS, sac_flat_shapes, sac_split, sac_join)
 
 from .vecenv import VecEnv  # noqa: E402,F401
 from .replay import ReplayBuffer  # noqa: E402,F401

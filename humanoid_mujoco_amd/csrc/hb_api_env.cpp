@@ -425,7 +425,7 @@ static int policy_forward(hb_batch* b, int lo, int hi, hipStream_t st, int seg =
   const float* x = b->d_obs + (size_t)lo * net.sizes[0];
   for (int l = 0; l < net.layers; l++) {
     float* y = ((l + 1 == net.layers) ? ctrl_for_write(b) : b->d_mlp_h[l & 1]) + (size_t)lo * net.sizes[l + 1];
-    HB_HIP(launch_mlp_layer(x, b->d_mlp_w[l], net.b[l], y, hi - lo, net.sizes[l], net.sizes[l + 1], 1, st));
+    HB_HIP(launch_mlp_layer(x, b->d_mlp_w[l], net.b[l], y, hi - lo, net.sizes[l], net.sizes[l + 1], 1 + (l + 1 == net.layers ? kActTanh : net.act), st));
     x = y;
   }
   return HB_OK;
@@ -565,6 +565,41 @@ int hb_critic_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* 
   rc = b->critic.install(n_layers, sizes, weights, biases);
   if (rc != HB_OK) { b->learner.clear(); return rc; }
   return learner_net_replaced(b, 1, same);
+}
+
+// ---- the hidden activation of an installed network
+
+static DevMlp* mlp_of(hb_batch* b, int net) {
+  switch (net) {
+    case HB_NET_POLICY: return &b->policy;
+    case HB_NET_ACTOR: return &b->actor;
+    case HB_NET_CRITIC: return &b->critic;
+    case HB_NET_Q1: return &b->q[0];
+    case HB_NET_Q2: return &b->q[1];
+    default: return nullptr;
+  }
+}
+
+int hb_mlp_get_activation(hb_batch* b, int net) {
+  const DevMlp* n = b ? mlp_of(b, net) : nullptr;
+  return n && n->layers >= 1 ? n->act : HB_EINVAL;
+}
+
+int hb_mlp_set_activation(hb_batch* b, int net, int activation) {
+  DevMlp* n = b ? mlp_of(b, net) : nullptr;
+  if (!n || n->layers < 1) return HB_EINVAL;
+  if (activation != HB_ACT_TANH && activation != HB_ACT_RELU && activation != HB_ACT_ELU) return HB_EINVAL;
+  if (n->act == activation) return HB_OK;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a learner step still in flight uses the buffers that are released below)
+  // a learner does not outlive the network it trained, as behind the network's set_mlp; the actor's draw counter goes on
+  if (net == HB_NET_ACTOR || net == HB_NET_CRITIC) {
+    const int rc = learner_activation_changed(b);
+    if (rc != HB_OK) return rc;
+  }
+  if (net == HB_NET_ACTOR || net == HB_NET_Q1 || net == HB_NET_Q2) b->sac.clear();
+  n->act = activation;
+  return HB_OK;
 }
 
 int hb_collect_gae_dev(hb_batch* b, int T, const hb_collect_out* tapes, const hb_gae_config* cfg, const hb_gae_out* out) {

@@ -121,6 +121,16 @@ int learner_net_replaced(hb_batch* b, int net, bool shapes_same) {
   return HB_OK;
 }
 
+int learner_activation_changed(hb_batch* b) {
+  Learner& L = b->learner;
+  if (!L.on) return HB_OK;
+  int rc = learner_sync_log_std(b);
+  if (rc == HB_OK) rc = idle(b);
+  if (rc != HB_OK) return rc;
+  L.clear();
+  return HB_OK;
+}
+
 }  // namespace hb
 
 extern "C" {

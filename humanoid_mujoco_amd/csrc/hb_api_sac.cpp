@@ -94,6 +94,7 @@ int write_targets(hb_batch* b, const float* rec) {
     for (int l = 0; l < n.layers; l++) { w[l] = rec + (L.off_w[k + 1][l] - L.off_q); bias[l] = rec + (L.off_b[k + 1][l] - L.off_q); }
     const int rc = L.tq[k].install(n.layers, n.sizes, w, bias);
     if (rc != HB_OK) return rc;
+    L.tq[k].act = n.act;  // (a target runs its Q network's activation; a change of that one destroys the learner)
   }
   return HB_OK;
 }
@@ -166,6 +167,7 @@ int hb_sac_create(hb_batch* b, const hb_sac_config* cfg) {
   if (!b || !cfg || !cfg_ok(cfg) || b->actor.layers < 1 || b->q[0].layers < 1 || b->q[1].layers < 1) return HB_EINVAL;
   if (b->q[0].layers != b->q[1].layers) return HB_EINVAL;
   for (int l = 0; l <= b->q[0].layers; l++) if (b->q[0].sizes[l] != b->q[1].sizes[l]) return HB_EINVAL;
+  if (b->q[0].act != b->q[1].act) return HB_EINVAL;  // (the actor's may differ)
   if (b->actor_cfg.head != HB_ACTOR_SQUASHED) return HB_EUNSUPPORTED;
   const int nu = b->D.dm.nu;
   if (nu < 1 || nu > kActorMaxNu) return HB_EINVAL;
@@ -375,7 +377,7 @@ int hb_sac_step_dev(hb_batch* b, const hb_sac_rows* rows, float* stats_dev) {
   bw.mb = rows->mb;
   for (int k = 0; k < 2; k++) {
     SacBwdJob& j = bw.job[k];
-    j.net = reversed(k + 1, false); j.L = Lq; j.top = q_dz[k][Lq - 1];
+    j.net = reversed(k + 1, false); j.L = Lq; j.activation = Q.act; j.top = q_dz[k][Lq - 1];
     for (int l = 1; l < Lq; l++) j.act[l] = q_act[k][l];
     for (int l = 0; l < Lq - 1; l++) j.dz[l] = q_dz[k][l];
   }
@@ -413,7 +415,7 @@ int hb_sac_step_dev(hb_batch* b, const hb_sac_rows* rows, float* stats_dev) {
   bw.mb = rows->mb;
   for (int k = 0; k < 2; k++) {
     SacBwdJob& j = bw.job[k];
-    j.net = reversed(k + 1, true); j.L = Lq; j.unit_top = 1; j.da = q_da[k];
+    j.net = reversed(k + 1, true); j.L = Lq; j.activation = Q.act; j.unit_top = 1; j.da = q_da[k];
     for (int l = 1; l < Lq; l++) j.act[l] = q_act[k][l];
   }
   HB_HIP(launch_sac_backprop(bw, 2, st));
@@ -424,7 +426,7 @@ int hb_sac_step_dev(hb_batch* b, const hb_sac_rows* rows, float* stats_dev) {
   bw.mb = rows->mb;
   {
     SacBwdJob& j = bw.job[0];
-    j.net = reversed(0, false); j.L = La; j.top = a_dz[La - 1];
+    j.net = reversed(0, false); j.L = La; j.activation = A.act; j.top = a_dz[La - 1];
     for (int l = 1; l < La; l++) j.act[l] = a_act[l];
     for (int l = 0; l < La - 1; l++) j.dz[l] = a_dz[l];
   }

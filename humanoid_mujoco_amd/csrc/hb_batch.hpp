@@ -76,9 +76,11 @@ template <class... B>
 void reset_all(B&... bufs) { (bufs.reset(), ...); }
 
 // The owner of one installed MLP as the 16-row fused kernels read it (hb_mlp_layers.inl): per layer the weights W[K][N] (row-major) in
-// the B-operand order of v_mfma_f32_16x16x4_f32 and the bias.  layers 0: none installed.
+// the B-operand order of v_mfma_f32_16x16x4_f32 and the bias, and the activation behind the hidden layers (HB_ACT_*: every installation
+// starts with tanh; hb_mlp_set_activation changes it).  layers 0: none installed.
 struct DevMlp {
-  int layers = 0;
+  short layers = 0;          // (two shorts in the place of the one int this held: the batch handle keeps its layout)
+  short act = HB_ACT_TANH;
   int sizes[5] = {0, 0, 0, 0, 0};
   DevBuf<float> wp[4], b[4];
 
@@ -104,6 +106,7 @@ struct DevMlp {
   }
   void clear() {
     layers = 0;
+    act = HB_ACT_TANH;
     for (int l = 0; l < 4; l++) reset_all(wp[l], b[l]);
   }
   // Replaces the network (arguments checked by the caller: mlp_args_ok; nothing on the device still reads the old one).  Only the device
@@ -117,7 +120,7 @@ struct DevMlp {
           hipMemcpy(b[l], biases[l], sz[l + 1] * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { clear(); return HB_ENODEVICE; }
     }
     for (int l = 0; l <= n_layers; l++) sizes[l] = sz[l];
-    layers = n_layers;
+    layers = (short)n_layers;
     return HB_OK;
   }
   PolicyDesc desc() const {
@@ -128,6 +131,7 @@ struct DevMlp {
     for (int l = 0; l <= layers; l++) { pd.sizes[l] = sizes[l]; widest = std::max(widest, sizes[l]); }
     for (int l = 0; l < layers; l++) { pd.w[l] = wp[l]; pd.b[l] = b[l]; }
     pd.ldx = widest + 4;  // + the K pad columns (K is swept four at a time); 16-row tiles
+    pd.act = act;
     return pd;
   }
 };
@@ -393,5 +397,7 @@ int rollout_open(hb_batch* b, const float* ctrl, int T, bool want_qpos);
 // behind hb_actor_set_mlp / hb_critic_set_mlp (net 0 / 1) once the new network is installed, shapes_same telling whether the sizes stayed
 int learner_sync_log_std(hb_batch* b);
 int learner_net_replaced(hb_batch* b, int net, bool shapes_same);
+// behind a change of the actor's or the critic's hidden activation: the learner is destroyed, the actor keeps the log_std it trained
+int learner_activation_changed(hb_batch* b);
 }  // namespace hb
 #pragma GCC visibility pop

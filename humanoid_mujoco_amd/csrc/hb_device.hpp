@@ -237,12 +237,14 @@ struct CostSpec {
   float weight[8], p[8], q[8], risk;
 };
 
+enum { kActTanh = 0, kActRelu = 1, kActElu = 2 };  // the activation behind the hidden layers = HB_ACT_* (include/hb.h)
 struct PolicyDesc {
   int nl;
   int sizes[5];
   const float* w[4];
   const float* b[4];
   int ldx;  // LDS row stride of an activation tile: widest layer + 4 (K is swept four columns at a time: zero pad columns)
+  int act;  // kAct*: behind every hidden layer (the last layer belongs to the kernel that runs the network)
 };
 
 // fused actor kernel (hb_actor_kernel, hb_actor.hip): the same network description, the sampling head (hb_actor_config, include/hb.h)
@@ -369,7 +371,7 @@ struct SacFwdJob {
   int n0, n1;
   int gather0, gather1;  // 1: minibatch row r is row index[r] (or first + r) of the array; 0: row r
   float* in_store;       // [mb][n0 + n1] or null: the gathered input rows (act[0] of the dW pass)
-  float* act[4];         // act[l] [mb][sizes[l]], l = 1 .. L - 1: the tanh outputs; act[1] null: nothing is stored
+  float* act[4];         // act[l] [mb][sizes[l]], l = 1 .. L - 1: the hidden activations' outputs; act[1] null: nothing is stored
   float* out;            // [mb][sizes[L]] the last layer's (linear) output
 };
 struct SacFwdDesc {
@@ -384,7 +386,8 @@ struct SacBwdJob {
   int L;                 // layers of the forward network
   int unit_top;          // 1: the top gradient is 1 for every row (dQ / da); 0: read from top
   const float* top;      // [mb][sizes[L]]
-  const float* act[4];   // the tanh outputs the forward pass kept
+  int activation;        // kAct* of the forward network: its derivative is formed from the kept outputs
+  const float* act[4];   // the hidden activations' outputs the forward pass kept
   float* dz[4];          // dz[l] [mb][sizes[l + 1]], l = 0 .. L - 2, written; dz[0] null: not stored (no dW follows)
   float* da;             // [mb][nu]: dloss / d(action inputs), the nl = L step
 };

@@ -20,38 +20,12 @@ namespace hb {
 //    at the top).
 // A row's value does not depend on the other rows of its tile nor on where in the tile it stands (every D[i][j] of an MFMA is its own
 // chain over k), so V is the same bits however the rows are cut into batches.
-__global__ __launch_bounds__(512) void hb_value_kernel(const PolicyDesc pd, const float* rows, const uint8_t* term, const uint8_t* trunc, long long n_rows, float* out) {
-  extern __shared__ __attribute__((aligned(16))) float sm_value[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long m0 = (long long)blockIdx.x * 16;
-  const int ldx = pd.ldx;
-  const int live = (int)min(16LL, n_rows - m0);  // rows of this block that exist
-  // bit r: row m0 + r is evaluated (every wave forms the same word)
-  unsigned sel = (1u << live) - 1u;
-  if (term) sel = (unsigned)__ballot(lane < live && trunc[m0 + min(lane, live - 1)] && !term[m0 + min(lane, live - 1)]) & 0xffffu;
-  if (!sel) {
-    if (tid < live) out[m0 + tid] = 0.f;
-    return;
-  }
-  float* cur = sm_value;
-  float* nxt = sm_value + 16 * ldx;
-  float* part = sm_value + 32 * ldx;  // [8][16][16] partial tiles
-  {
-    const int nobs = pd.sizes[0];
-    const float* src = rows + (size_t)m0 * nobs;
-    for (int idx = tid; idx < 16 * nobs; idx += 512) {
-      const int row = idx / nobs, c = idx - row * nobs;
-      cur[row * ldx + c] = (sel >> row & 1u) ? src[idx] : 0.f;
-    }
-    if (tid < 48) cur[(tid / 3) * ldx + nobs + tid % 3] = 0.f;
-  }
-  __syncthreads();
-#define HB_MLP_EMIT(row, n, v) nxt[(row) * ldx + (n)] = last ? (v) : tanhf(v)  // (the critic is linear at the top)
-#include "hb_mlp_layers.inl"
-#undef HB_MLP_EMIT
-  // cur holds the last layer's output, column 0 of every row
-  if (tid < live) out[m0 + tid] = (sel >> tid & 1u) ? cur[tid * ldx] : 0.f;
-}
+#define HB_ACT_ANY 0
+#include "hb_value_kernel.inl"
+#undef HB_ACT_ANY
+#define HB_ACT_ANY 1
+#include "hb_value_kernel.inl"
+#undef HB_ACT_ANY
 
 hipError_t launch_value(const PolicyDesc& pd, const float* rows, const uint8_t* term, const uint8_t* trunc, long long n_rows, float* out, hipStream_t stream) {
   (void)hipGetLastError();
@@ -59,7 +33,8 @@ hipError_t launch_value(const PolicyDesc& pd, const float* rows, const uint8_t* 
   const size_t shmem = ((size_t)32 * pd.ldx + 8 * 256) * sizeof(float);  // two activation tiles + the split-K partial tiles
   const long long nblk = (n_rows + 15) / 16;
   if (shmem > 64 * 1024 || nblk > 0x7fffffffLL) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hb_value_kernel, dim3((unsigned)nblk), dim3(512), shmem, stream, pd, rows, term, trunc, n_rows, out);
+  if (pd.act == kActTanh) hipLaunchKernelGGL(hb_value_kernel, dim3((unsigned)nblk), dim3(512), shmem, stream, pd, rows, term, trunc, n_rows, out);
+  else hipLaunchKernelGGL(hb_value_act_kernel, dim3((unsigned)nblk), dim3(512), shmem, stream, pd, rows, term, trunc, n_rows, out);
   return hipGetLastError();
 }
 

@@ -58,6 +58,20 @@ __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirs
 __device__ __forceinline__ float uniformf(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
+// The hidden activation of an installed MLP (PolicyDesc::act, kAct*) on the pre-activation v; act is the same in every lane of a block.
+// A non-finite v stays non-finite behind all three (ReLU as a select, not fmaxf, which would drop a NaN).
+__device__ __forceinline__ float mlp_act(int act, float v) {
+  if (act == kActTanh) return tanhf(v);
+  if (act == kActRelu) return v < 0.f ? 0.f : v;
+  return v > 0.f ? v : expm1f(v);
+}
+// its derivative from the stored OUTPUT a: tanh 1 - a^2; ReLU 0 at v <= 0 (torch's); ELU exp(v) = a + 1 at v <= 0
+__device__ __forceinline__ float mlp_act_slope(int act, float a) {
+  if (act == kActTanh) return __fmaf_rn(-a, a, 1.f);
+  if (act == kActRelu) return a > 0.f ? 1.f : 0.f;
+  return a > 0.f ? 1.f : a + 1.f;
+}
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));  // the accumulator of v_mfma_f32_16x16x4_f32 (hb_mlp_layers.inl, hb_policy_lean_kernel)
 typedef float f32x2 __attribute__((ext_vector_type(2)));

@@ -1,5 +1,6 @@
-// hb_mlp_layers.inl - the layer loop of the 16-row fused MLP kernels: hb_policy_kernel (hb_env.hip), hb_actor_kernel (hb_actor.hip) and
-// hb_value_kernel (hb_gae.hip) include it in place, once each, inside the kernel body.  Text, not a function: as a __device__ function
+// hb_mlp_layers.inl - the layer loop of the 16-row fused MLP kernels: hb_policy_kernel (hb_policy_kernels.inl), hb_actor_kernel
+// (hb_actor_kernel.inl), hb_value_kernel (hb_value_kernel.inl) and the learners' forward and backward kernels (hb_ppo_mlp.inl,
+// hb_sac_mlp.inl) include it in place, once each, inside the kernel body.  Text, not a function: as a __device__ function
 // with an epilogue functor the same loop costs the policy kernel its 64th register step and a wave per SIMD
 // (profiles/mlp_shared_loop.txt).  Its contract:
 //  - in scope: pd (PolicyDesc), tid, lane, wave, ldx = pd.ldx, and the LDS pointers cur (the input tile [16][ldx], its three pad
@@ -7,7 +8,7 @@
 //    behind a __syncthreads() that covers the input tile;
 //  - the hook HB_MLP_EMIT(row, n, v), which the kernel defines before the include and undefines behind it: called once per output
 //    (row 0..15, column n < N) of every layer with the pre-activation v = sum + bias, with last (this is the last layer), N (the
-//    layer's width) and nxt visible; on a layer that is not the last it has to store the activation to nxt[row * ldx + n];
+//    layer's width) and nxt visible; on a layer that is not the last it has to store the activation - the network's own, pd.act - to nxt[row * ldx + n];
 //  - behind it cur is the tile the last layer's hook wrote (where it wrote to nxt), and every thread is past the last barrier.
 // Eight waves share the 16-column output tiles of a layer, each sweeping K four columns per v_mfma_f32_16x16x4_f32 (exact f32) with the
 // A operand from LDS and the B operand from the packed weights (DevMlp, hb_batch.hpp); a layer with fewer than eight tiles splits K

@@ -36,63 +36,13 @@ __device__ __forceinline__ void ppo_adv_moments(const PpoDesc& d, double& mean, 
   sd = sqrt(var);
 }
 
-__global__ __launch_bounds__(512) void hb_ppo_forward_kernel(const PpoDesc d) {
-  extern __shared__ __attribute__((aligned(16))) float sm_ppo[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (blockIdx.y == 2) {
-    // chunk sums of the advantage: lane t takes rows t, t + 512, ... of the chunk, lane 0 adds the 512 sums in lane order
-    const int c = blockIdx.x;
-    if (c >= d.nchunk) return;
-    double* red = (double*)sm_ppo;
-    const int r1 = min(d.mb, (c + 1) * d.chunk);
-    double s = 0.0, q = 0.0;
-    for (int r = c * d.chunk + tid; r < r1; r += 512) {
-      const double a = (double)d.advantage[ppo_src_row(d, r)];
-      s += a; q += a * a;
-    }
-    red[tid] = s; red[512 + tid] = q;
-    __syncthreads();
-    if (tid == 0) {
-      double S = 0.0, Q = 0.0;
-      for (int t = 0; t < 512; t++) { S += red[t]; Q += red[512 + t]; }
-      d.advpart[2 * c] = S; d.advpart[2 * c + 1] = Q;
-    }
-    return;
-  }
-  const PpoNet& nw = d.net[blockIdx.y];
-  const PolicyDesc& pd = nw.fwd;
-  const int m0 = blockIdx.x * 16, ldx = pd.ldx;
-  const int live = min(16, d.mb - m0);
-  float* cur = sm_ppo;
-  float* nxt = sm_ppo + 16 * ldx;
-  float* part = sm_ppo + 32 * ldx;  // [8][16][16] partial tiles
-  {
-    // the gathered observation tile; rows past mb and the K pad columns are zero.  The actor's blocks keep it as act[0] for the dW pass.
-    const int nobs = pd.sizes[0];
-    for (int idx = tid; idx < 16 * nobs; idx += 512) {
-      const int row = idx / nobs, c = idx - row * nobs;
-      float x = 0.f;
-      if (row < live) {
-        x = d.obs[(size_t)ppo_src_row(d, m0 + row) * nobs + c];
-        if (blockIdx.y == 0) nw.act[0][(size_t)(m0 + row) * nobs + c] = x;
-      }
-      cur[row * ldx + c] = x;
-    }
-    if (tid < 48) cur[(tid / 3) * ldx + nobs + tid % 3] = 0.f;
-  }
-  __syncthreads();
-  // (l: the layer index of the loop)
-#define HB_MLP_EMIT(row, n, v) do { \
-    const float a_ = last ? (v) : tanhf(v); \
-    nxt[(row) * ldx + (n)] = a_; \
-    if ((row) < live) { \
-      if (last) nw.out[(size_t)(m0 + (row)) * N + (n)] = a_; \
-      else nw.act[l + 1][(size_t)(m0 + (row)) * N + (n)] = a_; \
-    } \
-  } while (0)
-#include "hb_mlp_layers.inl"
-#undef HB_MLP_EMIT
-}
+// hb_ppo_forward_kernel, hb_ppo_backprop_kernel and their twins for networks that are not tanh
+#define HB_ACT_ANY 0
+#include "hb_ppo_mlp.inl"
+#undef HB_ACT_ANY
+#define HB_ACT_ANY 1
+#include "hb_ppo_mlp.inl"
+#undef HB_ACT_ANY
 
 // One lane per minibatch row.  Roundings are fp32 unless said otherwise; A_r is formed in fp64 from the fp64 moments and rounded once.
 __global__ __launch_bounds__(256) void hb_ppo_head_kernel(const PpoDesc d) {
@@ -137,42 +87,6 @@ __global__ __launch_bounds__(256) void hb_ppo_head_kernel(const PpoDesc d) {
   sr[2] = (ratio - 1.f) - dl;
   sr[3] = fabsf(ratio - 1.f) > d.clip_range ? 1.f : 0.f;
   sr[4] = ratio;
-}
-
-__global__ __launch_bounds__(512) void hb_ppo_backprop_kernel(const PpoDesc d) {
-  extern __shared__ __attribute__((aligned(16))) float sm_ppo[];
-  const PpoNet& nw = d.net[blockIdx.y];
-  const PolicyDesc& pd = nw.bwd;
-  if (pd.nl < 1) return;  // one layer: its dZ is the head's
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = blockIdx.x * 16, ldx = pd.ldx, L = nw.fwd.nl;
-  const int live = min(16, d.mb - m0);
-  float* cur = sm_ppo;
-  float* nxt = sm_ppo + 16 * ldx;
-  float* part = sm_ppo + 32 * ldx;
-  {
-    const int n0 = pd.sizes[0];
-    const float* src = nw.dz[L - 1] + (size_t)m0 * n0;
-    for (int idx = tid; idx < 16 * n0; idx += 512) {
-      const int row = idx / n0, c = idx - row * n0;
-      cur[row * ldx + c] = row < live ? src[idx] : 0.f;
-    }
-    if (tid < 48) cur[(tid / 3) * ldx + n0 + tid % 3] = 0.f;
-  }
-  __syncthreads();
-  // step l of the loop multiplies by the transpose of layer L - 1 - l: v is dloss / dact[L - 1 - l], a tanh output
-#define HB_MLP_EMIT(row, n, v) do { \
-    float g_ = 0.f; \
-    if ((row) < live) { \
-      const size_t o_ = (size_t)(m0 + (row)) * N + (n); \
-      const float a_ = nw.act[L - 1 - l][o_]; \
-      g_ = (v) * __fmaf_rn(-a_, a_, 1.f); \
-      nw.dz[L - 2 - l][o_] = g_; \
-    } \
-    nxt[(row) * ldx + (n)] = g_; \
-  } while (0)
-#include "hb_mlp_layers.inl"
-#undef HB_MLP_EMIT
 }
 
 // dW = A^T dZ over one chunk of rows: the A operand of the MFMA is A^T (row i = input column, k = minibatch row), the B operand dZ
@@ -365,9 +279,12 @@ hipError_t launch_ppo_grad(const PpoDesc& d, hipStream_t stream) {
   const size_t shmem = ((size_t)32 * ldx + 8 * 256) * sizeof(float);  // two activation tiles + the split-K partial tiles (>= the 8 KB of the advantage blocks)
   if (shmem > 64 * 1024 || tiles < d.nchunk) return hipErrorInvalidValue;
   const int nlay = d.net[0].fwd.nl + d.net[1].fwd.nl;
-  hipLaunchKernelGGL(hb_ppo_forward_kernel, dim3(tiles, 3), dim3(512), shmem, stream, d);
+  const bool tanh_only = d.net[0].fwd.act == kActTanh && d.net[1].fwd.act == kActTanh;
+  if (tanh_only) hipLaunchKernelGGL(hb_ppo_forward_kernel, dim3(tiles, 3), dim3(512), shmem, stream, d);
+  else hipLaunchKernelGGL(hb_ppo_forward_act_kernel, dim3(tiles, 3), dim3(512), shmem, stream, d);
   hipLaunchKernelGGL(hb_ppo_head_kernel, dim3((d.mb + 255) / 256), dim3(256), 0, stream, d);
-  hipLaunchKernelGGL(hb_ppo_backprop_kernel, dim3(tiles, 2), dim3(512), shmem, stream, d);
+  if (tanh_only) hipLaunchKernelGGL(hb_ppo_backprop_kernel, dim3(tiles, 2), dim3(512), shmem, stream, d);
+  else hipLaunchKernelGGL(hb_ppo_backprop_act_kernel, dim3(tiles, 2), dim3(512), shmem, stream, d);
   hipLaunchKernelGGL(hb_ppo_wgrad_kernel, dim3(d.nchunk, nlay + 1), dim3(512), 0, stream, d);
   hipLaunchKernelGGL(hb_ppo_reduce_kernel, dim3((d.P + 255) / 256 + 1), dim3(256), 0, stream, d);
   return hipGetLastError();

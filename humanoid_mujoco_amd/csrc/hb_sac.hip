@@ -34,45 +34,13 @@ namespace hb {
 // minibatch row r of the tapes
 __device__ __forceinline__ long long sac_src_row(const int* index, long long first, int r) { return index ? (long long)index[r] : first + r; }
 
-__global__ __launch_bounds__(512) void hb_sac_forward_kernel(const SacFwdDesc d) {
-  extern __shared__ __attribute__((aligned(16))) float sm_sac[];
-  const SacFwdJob& jb = d.job[blockIdx.y];
-  const PolicyDesc& pd = jb.net;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = blockIdx.x * 16, ldx = pd.ldx;
-  const int live = min(16, d.mb - m0);
-  float* cur = sm_sac;
-  float* nxt = sm_sac + 16 * ldx;
-  float* part = sm_sac + 32 * ldx;  // [8][16][16] partial tiles
-  {
-    // the input tile from its two sources; rows past mb and the K pad columns are zero
-    const int n0 = jb.n0, n1 = jb.n1, nin = n0 + n1;
-    for (int idx = tid; idx < 16 * nin; idx += 512) {
-      const int row = idx / nin, c = idx - row * nin;
-      float x = 0.f;
-      if (row < live) {
-        const int r = m0 + row;
-        if (c < n0) x = jb.x0[(size_t)(jb.gather0 ? sac_src_row(d.index, d.first, r) : (long long)r) * n0 + c];
-        else x = jb.x1[(size_t)(jb.gather1 ? sac_src_row(d.index, d.first, r) : (long long)r) * n1 + (c - n0)];
-        if (jb.in_store) jb.in_store[(size_t)r * nin + c] = x;
-      }
-      cur[row * ldx + c] = x;
-    }
-    if (tid < 48) cur[(tid / 3) * ldx + nin + tid % 3] = 0.f;
-  }
-  __syncthreads();
-  // (l: the layer index of the loop)
-#define HB_MLP_EMIT(row, n, v) do { \
-    const float a_ = last ? (v) : tanhf(v); \
-    nxt[(row) * ldx + (n)] = a_; \
-    if ((row) < live) { \
-      if (last) jb.out[(size_t)(m0 + (row)) * N + (n)] = a_; \
-      else if (jb.act[1]) jb.act[l + 1][(size_t)(m0 + (row)) * N + (n)] = a_; \
-    } \
-  } while (0)
-#include "hb_mlp_layers.inl"
-#undef HB_MLP_EMIT
-}
+// hb_sac_forward_kernel, hb_sac_backprop_kernel and their twins for launches with a job whose network is not tanh
+#define HB_ACT_ANY 0
+#include "hb_sac_mlp.inl"
+#undef HB_ACT_ANY
+#define HB_ACT_ANY 1
+#include "hb_sac_mlp.inl"
+#undef HB_ACT_ANY
 
 // One lane per minibatch row, both branches (0: pi on obs, 1: next on next_obs).  Roundings are fp32 and follow hb_log_prob_kernel
 // (hb_gae.hip) term by term; the draw of (row r, element i) is rng_normal(seed, r, 0, t, stream, i).
@@ -154,47 +122,6 @@ __global__ __launch_bounds__(256) void hb_sac_actor_head_kernel(const SacHeadDes
   float* sr = d.srow + (size_t)r * kSacSrow;
   sr[0] = __fmaf_rn(alpha, d.lp_pi[r], -mq);
   sr[1] = mq;
-}
-
-__global__ __launch_bounds__(512) void hb_sac_backprop_kernel(const SacBwdDesc d) {
-  extern __shared__ __attribute__((aligned(16))) float sm_sac[];
-  const SacBwdJob& jb = d.job[blockIdx.y];
-  const PolicyDesc& pd = jb.net;
-  if (pd.nl < 1) return;  // one layer and no input gradient: its dZ is the head's
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = blockIdx.x * 16, ldx = pd.ldx, L = jb.L;
-  const int live = min(16, d.mb - m0);
-  float* cur = sm_sac;
-  float* nxt = sm_sac + 16 * ldx;
-  float* part = sm_sac + 32 * ldx;
-  {
-    const int n0 = pd.sizes[0];
-    for (int idx = tid; idx < 16 * n0; idx += 512) {
-      const int row = idx / n0;
-      cur[row * ldx + (idx - row * n0)] = row < live ? (jb.unit_top ? 1.f : jb.top[(size_t)m0 * n0 + idx]) : 0.f;
-    }
-    if (tid < 48) cur[(tid / 3) * ldx + n0 + tid % 3] = 0.f;
-  }
-  __syncthreads();
-  // step l of the loop multiplies by the transpose of layer L - 1 - l: v is dloss / dact[L - 1 - l] - a tanh output, or for
-  // L - 1 - l == 0 (a Q network's nl = L) the action inputs, which are no tanh output: no 1 - a^2
-#define HB_MLP_EMIT(row, n, v) do { \
-    float g_ = 0.f; \
-    if ((row) < live) { \
-      const size_t o_ = (size_t)(m0 + (row)) * N + (n); \
-      if (L - 1 - l == 0) { \
-        g_ = (v); \
-        jb.da[o_] = g_; \
-      } else { \
-        const float a_ = jb.act[L - 1 - l][o_]; \
-        g_ = (v) * __fmaf_rn(-a_, a_, 1.f); \
-        if (jb.dz[0]) jb.dz[L - 2 - l][o_] = g_; \
-      } \
-    } \
-    nxt[(row) * ldx + (n)] = g_; \
-  } while (0)
-#include "hb_mlp_layers.inl"
-#undef HB_MLP_EMIT
 }
 
 // hb_ppo_wgrad_kernel's design over a list of jobs: dW = A^T dZ over one chunk of rows, the A operand of the MFMA being A^T (row i =
@@ -373,7 +300,10 @@ hipError_t launch_sac_forward(const SacFwdDesc& d, int njob, hipStream_t stream)
     ldx = max(ldx, jb.net.ldx);
   }
   if (sac_shmem(ldx) > 64 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hb_sac_forward_kernel, dim3((d.mb + 15) / 16, njob), dim3(512), sac_shmem(ldx), stream, d);
+  bool tanh_only = true;
+  for (int j = 0; j < njob; j++) tanh_only = tanh_only && d.job[j].net.act == kActTanh;
+  if (tanh_only) hipLaunchKernelGGL(hb_sac_forward_kernel, dim3((d.mb + 15) / 16, njob), dim3(512), sac_shmem(ldx), stream, d);
+  else hipLaunchKernelGGL(hb_sac_forward_act_kernel, dim3((d.mb + 15) / 16, njob), dim3(512), sac_shmem(ldx), stream, d);
   return hipGetLastError();
 }
 
@@ -399,7 +329,10 @@ hipError_t launch_sac_backprop(const SacBwdDesc& d, int njob, hipStream_t stream
     ldx = max(ldx, jb.net.ldx);
   }
   if (sac_shmem(ldx) > 64 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hb_sac_backprop_kernel, dim3((d.mb + 15) / 16, njob), dim3(512), sac_shmem(ldx), stream, d);
+  bool tanh_only = true;
+  for (int j = 0; j < njob; j++) tanh_only = tanh_only && d.job[j].activation == kActTanh;
+  if (tanh_only) hipLaunchKernelGGL(hb_sac_backprop_kernel, dim3((d.mb + 15) / 16, njob), dim3(512), sac_shmem(ldx), stream, d);
+  else hipLaunchKernelGGL(hb_sac_backprop_act_kernel, dim3((d.mb + 15) / 16, njob), dim3(512), sac_shmem(ldx), stream, d);
   return hipGetLastError();
 }
 

@@ -136,6 +136,10 @@ class HbDomainRandomization(ctypes.Structure):
 
 ACTOR_DETERMINISTIC, ACTOR_GAUSSIAN, ACTOR_SQUASHED = 0, 1, 2  # hb_actor_config.head (HB_ACTOR_*)
 ACTOR_HEADS = {"deterministic": ACTOR_DETERMINISTIC, "gaussian": ACTOR_GAUSSIAN, "squashed": ACTOR_SQUASHED}
+ACT_TANH, ACT_RELU, ACT_ELU = 0, 1, 2  # the hidden activation of an installed MLP (HB_ACT_*)
+ACTIVATIONS = {"tanh": ACT_TANH, "relu": ACT_RELU, "elu": ACT_ELU}
+NET_POLICY, NET_ACTOR, NET_CRITIC, NET_Q1, NET_Q2 = 0, 1, 2, 3, 4  # which installed MLP (HB_NET_*)
+NETS = {"policy": NET_POLICY, "actor": NET_ACTOR, "critic": NET_CRITIC, "q1": NET_Q1, "q2": NET_Q2}
 RS_ACTOR = 32  # random-number stream of the actor's draws (include/hb.h: hb_env_collect_dev)
 
 
@@ -429,6 +433,8 @@ def lib():
     ll = ctypes.c_longlong
     L.hb_q_set_mlp.argtypes = [vp, ci, ci, vp, vp, vp]
     L.hb_q_values_dev.argtypes = [vp, vp, vp, ll, vp, vp]
+    L.hb_mlp_set_activation.argtypes = [vp, ci, ci]
+    L.hb_mlp_get_activation.argtypes = [vp, ci]
     L.hb_sac_default_config.argtypes = [ctypes.POINTER(HbSacConfig)]
     L.hb_sac_create.argtypes = [vp, ctypes.POINTER(HbSacConfig)]
     L.hb_sac_configure.argtypes = [vp, ctypes.POINTER(HbSacConfig)]
@@ -461,6 +467,22 @@ def quat_to_mat(q):
     m[..., 1, 0] = 2 * (x * y + w * z); m[..., 1, 1] = w * w - x * x + y * y - z * z; m[..., 1, 2] = 2 * (y * z - w * x)
     m[..., 2, 0] = 2 * (x * z - w * y); m[..., 2, 1] = 2 * (y * z + w * x); m[..., 2, 2] = w * w - x * x - y * y + z * z
     return m
+
+
+def _activation(a):
+    if isinstance(a, str):
+        if a not in ACTIVATIONS:
+            raise ValueError("activation must be one of %s, not %r" % (sorted(ACTIVATIONS), a))
+        return ACTIVATIONS[a]
+    return int(a)
+
+
+def _net(n):
+    if isinstance(n, str):
+        if n not in NETS:
+            raise ValueError("net must be one of %s, not %r" % (sorted(NETS), n))
+        return NETS[n]
+    return int(n)
 
 
 def _check(rc, what, why=None):
@@ -1314,10 +1336,28 @@ class Batch:
                                      ctypes.c_void_p(terminated_ptr), ctypes.c_void_p(truncated_ptr)), "hb_env_step_dev")
 
     # ---- policy in the loop (BASELINE config 4)
-    def set_policy_mlp(self, weights, biases):
-        """weights[l]: [in, out] float32 (transpose of torch.nn.Linear.weight); tanh after every layer."""
+    def set_policy_mlp(self, weights, biases, activation="tanh"):
+        """weights[l]: [in, out] float32 (transpose of torch.nn.Linear.weight); `activation` ("tanh", "relu", "elu") after every hidden
+        layer, tanh after the last."""
+        act = _activation(activation)
         ws, bs, csz, wp, bp = _mlp_args("set_policy_mlp", weights, biases)
         _check(lib().hb_policy_set_mlp(self._h, len(ws), csz, wp, bp), "hb_policy_set_mlp")
+        if act != ACT_TANH:  # (what hb_policy_set_mlp installs)
+            self.mlp_set_activation(NET_POLICY, act)
+
+    def mlp_set_activation(self, net, activation):
+        """hb_mlp_set_activation: the activation behind the hidden layers of the installed network `net` ("policy", "actor", "critic",
+        "q1", "q2" or the NET_* value): "tanh", "relu", "elu" or the ACT_* value.  Every installation starts with tanh; a change destroys
+        a learner that trains the network, as installing it again does."""
+        rc = lib().hb_mlp_set_activation(self._h, _net(net), _activation(activation))
+        _check(rc, "hb_mlp_set_activation", "needs an installed network of that kind")
+
+    def mlp_activation(self, net):
+        """The activation behind the hidden layers of the installed network `net` ("policy", "actor", "critic", "q1", "q2" or NET_*):
+        "tanh", "relu" or "elu"."""
+        rc = lib().hb_mlp_get_activation(self._h, _net(net))
+        _check(min(rc, 0), "hb_mlp_get_activation", "needs an installed network of that kind")
+        return {v: k for k, v in ACTIVATIONS.items()}[rc]
 
     def policy_eval(self):
         out = np.zeros((self.n_env, self.model.nu), dtype=np.float32)
@@ -1328,12 +1368,13 @@ class Batch:
         _check(lib().hb_rollout_policy(self._h, int(T), ctypes.c_void_p(qpos_out_ptr or 0)), "hb_rollout_policy")
 
     # ---- actor and rollout collection (include/hb.h: hb_actor_set_mlp, hb_env_collect_dev)
-    def actor_set(self, sizes, weights, biases, head="gaussian", log_std=None, seed=0, deterministic=False):
+    def actor_set(self, sizes, weights, biases, head="gaussian", log_std=None, seed=0, deterministic=False, activation="tanh"):
         """Installs the sampling actor.  sizes: [nobs, hidden..., nu] (head "squashed": ..., 2 nu); weights[l]: [sizes[l], sizes[l+1]]
-        float32 - the TRANSPOSE of torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; tanh after every hidden layer.  head: "deterministic"
+        float32 - the TRANSPOSE of torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; `activation` ("tanh", "relu", "elu") after every hidden layer.  head: "deterministic"
         (tanh output, no sampling), "gaussian" (linear mean, state-independent log_std [nu]: SB3 PPO / A2C) or "squashed" (linear
         mean | log_std, clamped to [-20, 2], tanh of the sample: SB3 SAC), or the ACTOR_* value.  At most four layers of width <= 256."""
         head = ACTOR_HEADS[head] if isinstance(head, str) else int(head)
+        act = _activation(activation)
         ws, bs, csz, wp, bp = _mlp_args("actor_set", weights, biases, sizes)
         cfg = HbActorConfig()
         cfg.head, cfg.seed, cfg.deterministic = head, int(seed) & 0xFFFFFFFF, int(bool(deterministic))
@@ -1346,6 +1387,8 @@ class Batch:
         _check(rc, "hb_actor_set_mlp", "a layer wider than 256: the actor is one fused kernel, there is no layer-by-layer path" if rc == -4 else
                "sizes must run from nobs to nu (squashed: 2 nu) over 1..4 layers, nu <= 32, log_std finite" if rc == -1 else None)
         self.actor_head = head
+        if act != ACT_TANH:  # (what hb_actor_set_mlp installs)
+            self.mlp_set_activation(NET_ACTOR, act)
 
     def env_collect_dev(self, T, n_substeps=1, obs=None, action=None, mean=None, log_std=None, eps=None, reward=None, terminated=None,
                         truncated=None, terminal_obs=None):
@@ -1357,14 +1400,17 @@ class Batch:
                "tape only with the squashed head" if rc == -1 else None)
 
     # ---- critic and the PPO buffer over a collection's tapes (include/hb.h: hb_critic_set_mlp, hb_collect_gae_dev)
-    def critic_set(self, sizes, weights, biases):
+    def critic_set(self, sizes, weights, biases, activation="tanh"):
         """Installs the critic.  sizes: [nobs, hidden..., 1]; weights[l]: [sizes[l], sizes[l+1]] float32 - the TRANSPOSE of
-        torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; tanh after every hidden layer, the last layer linear.  At most four layers of
-        width <= 256.  Independent of the actor and of the policy MLP."""
+        torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; `activation` ("tanh", "relu", "elu") after every hidden layer, the last layer linear.  At most
+        four layers of width <= 256.  Independent of the actor and of the policy MLP."""
+        act = _activation(activation)
         ws, bs, csz, wp, bp = _mlp_args("critic_set", weights, biases, sizes)
         rc = lib().hb_critic_set_mlp(self._h, len(ws), csz, wp, bp)
         _check(rc, "hb_critic_set_mlp", "a layer wider than 256: the critic is one fused kernel, there is no layer-by-layer path" if rc == -4 else
                "sizes must run from nobs to 1 over 1..4 layers" if rc == -1 else None)
+        if act != ACT_TANH:  # (what hb_critic_set_mlp installs)
+            self.mlp_set_activation(NET_CRITIC, act)
 
     def collect_gae_dev(self, T, gamma, lam, bootstrap_truncated=True, *, obs=None, action=None, mean=None, log_std=None, eps=None, reward=None,
                         terminated=None, truncated=None, terminal_obs=None, value=None, terminal_value=None, log_prob=None, advantage=None, returns=None):
@@ -1472,14 +1518,18 @@ class Batch:
         _check(lib().hb_ppo_minibatch_dev(self._h, ctypes.byref(rows), ctypes.c_void_p(stats or 0)), "hb_ppo_minibatch_dev", self._PPO_WHY)
 
     # ---- the Q networks and the SAC learner (include/hb.h: hb_q_*, hb_sac_*)
-    def q_set(self, k, sizes, weights, biases):
+    def q_set(self, k, sizes, weights, biases, activation="tanh"):
         """Installs Q network k (0 or 1).  sizes: [nobs + nu, hidden..., 1] - the input row is obs | action; weights[l]: [sizes[l],
-        sizes[l+1]] float32 - the TRANSPOSE of torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; tanh after every hidden layer, the last
-        layer linear.  At most four layers of width <= 256.  Destroys a SAC learner of this batch."""
+        sizes[l+1]] float32 - the TRANSPOSE of torch.nn.Linear.weight -, biases[l]: [sizes[l+1]]; `activation` ("tanh", "relu", "elu") after every hidden layer,
+        the last layer linear; Q1 and Q2 of a SAC learner share it.  At most four layers of width <= 256.  Destroys a SAC learner of this
+        batch."""
+        act = _activation(activation)
         ws, bs, csz, wp, bp = _mlp_args("q_set", weights, biases, sizes)
         rc = lib().hb_q_set_mlp(self._h, int(k), len(ws), csz, wp, bp)
         _check(rc, "hb_q_set_mlp", "a layer wider than 256: the Q network is one fused kernel, there is no layer-by-layer path" if rc == -4 else
                "k is 0 or 1, sizes must run from nobs + nu to 1 over 1..4 layers" if rc == -1 else None)
+        if act != ACT_TANH:  # (what hb_q_set_mlp installs)
+            self.mlp_set_activation(NET_Q1 + int(k), act)
 
     def q_values_dev(self, obs, action, n_rows, q1=None, q2=None):
         """hb_q_values_dev: Q1 and Q2 over n_rows rows obs [n_rows, nobs] | action [n_rows, nu] into q1, q2 [n_rows] (device pointers,

@@ -469,16 +469,19 @@ class VecEnv:
         self._last_obs = o
         return o, r, te.view(torch.bool), tr.view(torch.bool)  # (the kernel writes 0 / 1 bytes: a view, not two conversion kernels)
 
-    def actor_set(self, sizes, weights, biases, head="gaussian", log_std=None, seed=None, deterministic=False):
+    def actor_set(self, sizes, weights, biases, head="gaussian", log_std=None, seed=None, deterministic=False, activation="tanh"):
         """Installs the sampling actor collect() / collect_torch() run in the env loop (Batch.actor_set: weights[l] is [in, out], the
-        transpose of torch.nn.Linear.weight; heads "deterministic", "gaussian", "squashed").  seed defaults to this VecEnv's seed; its
+        transpose of torch.nn.Linear.weight; heads "deterministic", "gaussian", "squashed"; hidden activation
+        "tanh", "relu" or "elu").  seed defaults to this VecEnv's seed; its
         draws are a random stream of their own, independent of the realism layer's."""
-        self.batch.actor_set(sizes, weights, biases, head=head, log_std=log_std, seed=self.seed_value if seed is None else seed, deterministic=deterministic)
+        self.batch.actor_set(sizes, weights, biases, head=head, log_std=log_std, seed=self.seed_value if seed is None else seed, deterministic=deterministic,
+                             activation=activation)
 
-    def critic_set(self, sizes, weights, biases):
+    def critic_set(self, sizes, weights, biases, activation="tanh"):
         """Installs the critic collect() / collect_torch() evaluate with gae=... (Batch.critic_set: sizes [nobs, hidden..., 1], weights[l] is
-        [in, out], the transpose of torch.nn.Linear.weight; tanh hidden layers, linear output)."""
-        self.batch.critic_set(sizes, weights, biases)
+        [in, out], the transpose of torch.nn.Linear.weight; hidden layers with `activation` - "tanh", "relu" or "elu" -, linear
+        output)."""
+        self.batch.critic_set(sizes, weights, biases, activation=activation)
 
     def collect_torch(self, T, obs0=None, terminal_obs=False, gae=None, raw=False):
         """T steps of the installed actor in the env loop on the device (hb_env_collect_dev): no host transfer, no host synchronisation,
@@ -647,10 +650,11 @@ class VecEnv:
         return log
 
     # ---- the SAC learner on the device (Batch.sac_create, sac_step_dev)
-    def q_set(self, k, sizes, weights, biases):
+    def q_set(self, k, sizes, weights, biases, activation="tanh"):
         """Installs Q network k (0 or 1) of the SAC learner (Batch.q_set: sizes [nobs + nu, hidden..., 1] over the row obs | action,
-        weights[l] is [in, out], the transpose of torch.nn.Linear.weight; tanh hidden layers, linear output)."""
-        self.batch.q_set(k, sizes, weights, biases)
+        weights[l] is [in, out], the transpose of torch.nn.Linear.weight; hidden layers with `activation` - "tanh", "relu" or "elu" -, linear
+        output; both Q networks of a learner share it)."""
+        self.batch.q_set(k, sizes, weights, biases, activation=activation)
 
     def sac_learner(self, **cfg):
         """Creates the SAC learner over the networks of actor_set (squashed head) and q_set, which become the trainable parameters: what

@@ -792,7 +792,8 @@ int hb_env_step_dev(hb_batch* b, const float* action_dev, int n_substeps, float*
 
 /* ---- policy in the loop (BASELINE.json configs[3]: MLP policy inference fused into the rollout loop) ---------- */
 
-/* Installs an MLP policy obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] == nu with tanh after every layer
+/* Installs an MLP policy obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] == nu with tanh after every layer (hidden
+ * layers: or what hb_mlp_set_activation chooses)
  * (sizes and activation of simulation/hyperparam_config.py:21-27, rl/train.py:163-167).  weights[l] is row-major
  * [sizes[l]][sizes[l+1]] float32 (the transpose of torch.nn.Linear.weight), biases[l] is [sizes[l+1]].  Host pointers;
  * copied to the device.  n_layers <= 4, every size <= 512. */
@@ -816,7 +817,7 @@ typedef struct hb_actor_config {
   int deterministic;     /* 1: eps = 0 for every head (evaluation rollouts) */
 } hb_actor_config;
 
-/* Installs the actor of hb_env_collect_dev: an MLP obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] with tanh after every hidden layer; the
+/* Installs the actor of hb_env_collect_dev: an MLP obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] with tanh (or what hb_mlp_set_activation chooses) after every hidden layer; the
  * last layer has tanh for head 0 and is linear for heads 1 and 2.  sizes[0] == nobs; sizes[n_layers] == nu for heads 0 and 1 and 2 nu for
  * head 2.  weights[l] is row-major [sizes[l]][sizes[l+1]] float32 (the transpose of torch.nn.Linear.weight), biases[l] is [sizes[l+1]];
  * host pointers, copied to the device.  The actor is separate from the MLP of hb_policy_set_mlp: either may be installed or replaced
@@ -856,7 +857,7 @@ int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out*
 
 /* ---- PPO buffer over the tapes of a collection: critic values, log-probabilities, GAE(gamma, lambda) advantages and returns ---- */
 
-/* Installs the critic of hb_collect_gae_dev: an MLP obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] == 1 with tanh after every hidden layer
+/* Installs the critic of hb_collect_gae_dev: an MLP obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] == 1 with tanh (or what hb_mlp_set_activation chooses) after every hidden layer
  * and a linear last layer.  The weight conventions are hb_actor_set_mlp's: weights[l] is row-major [sizes[l]][sizes[l+1]] float32 (the
  * transpose of torch.nn.Linear.weight), biases[l] is [sizes[l+1]]; host pointers, copied to the device and packed.  The critic is
  * independent of the actor and of the MLP of hb_policy_set_mlp: any of them may be installed or replaced without touching the others.
@@ -1146,6 +1147,33 @@ int hb_q_set_mlp(hb_batch* b, int k, int n_layers, const int* sizes, const float
  * 2^31 - 1, an output whose network is not installed. */
 int hb_q_values_dev(hb_batch* b, const float* obs, const float* action, long long n_rows, float* q1_out, float* q2_out);
 
+/* ---- the hidden activation of an installed network ----------------------------------------------------------------------------- */
+
+#define HB_ACT_TANH 0
+#define HB_ACT_RELU 1   /* v < 0 ? 0 : v; derivative 0 at v <= 0, as torch */
+#define HB_ACT_ELU  2   /* v > 0 ? v : expm1(v)  (alpha = 1) */
+#define HB_NET_POLICY 0 /* hb_policy_set_mlp */
+#define HB_NET_ACTOR  1 /* hb_actor_set_mlp */
+#define HB_NET_CRITIC 2 /* hb_critic_set_mlp */
+#define HB_NET_Q1     3 /* hb_q_set_mlp, k = 0 */
+#define HB_NET_Q2     4 /* hb_q_set_mlp, k = 1 */
+/* The activation behind every HIDDEN layer of the installed network `net`, in every kernel that runs it - hb_policy_eval and
+ * hb_rollout_policy, the collection, hb_collect_gae_dev, hb_q_values_dev, both learners' forward and backward passes (which form the
+ * derivative from the kept output a: 1 - a^2; a > 0 ? 1 : 0; a > 0 ? 1 : a + 1).  The last layer stays what its installation made it:
+ * tanh for hb_policy_set_mlp and actor head 0, linear for the other heads, the critic and Q; the squashing tanh of HB_ACTOR_SQUASHED is
+ * part of the head.  A non-finite pre-activation stays non-finite behind all three.  Every hb_*_set_mlp installs its network with
+ * HB_ACT_TANH: a caller that never calls this function sees no difference, and one that replaces a network sets the activation again.
+ * Setting the value in force is a no-op.  Another value follows the rule of the network's set_mlp: on the actor or the critic it destroys
+ * a PPO learner (the actor keeps the log_std it trained), on the actor, Q1 or Q2 a SAC learner; the actor's draw counter is NOT reset.
+ * The SAC targets run their Q network's activation, and hb_sac_create refuses Q1 and Q2 with different ones (the actor's may differ).
+ * The activation belongs to the installation, not to a learner: the parameter, moment and checkpoint records (hb_learner_get_state,
+ * hb_sac_get_state) keep their layout and do not hold it, so a caller that resumes repeats set_mlp AND this call before it creates the
+ * learner and restores the state.
+ * HB_EINVAL: NULL batch, a net that is none of HB_NET_*, an activation that is none of HB_ACT_*, no network of that kind installed.  A
+ * refused call changes nothing. */
+int hb_mlp_set_activation(hb_batch* b, int net, int activation);
+int hb_mlp_get_activation(hb_batch* b, int net);   /* HB_ACT_*, or HB_EINVAL */
+
 typedef struct hb_sac_config {
   float gamma;                  /* 0.99    in [0, 1] */
   float tau;                    /* 0.005   in [0, 1] */
@@ -1166,7 +1194,7 @@ int hb_sac_default_config(hb_sac_config* cfg);
  * log_ent_coef = log(ent_coef_init), zeroes the moments, t = 0.  A SAC learner that exists is replaced.  hb_sac_configure changes the
  * hyper-parameters and touches no state.  hb_actor_set_mlp or hb_q_set_mlp on a batch with a SAC learner destroys it.  A PPO learner
  * (hb_learner_create) needs the Gaussian head, this one the squashed head: a batch never holds both.
- * HB_EINVAL: NULL argument; no actor, a Q network missing, Q1 and Q2 of unequal sizes; a hyper-parameter that is not finite or out of
+ * HB_EINVAL: NULL argument; no actor, a Q network missing, Q1 and Q2 of unequal sizes or with different activations; a hyper-parameter that is not finite or out of
  * range (above); configure / destroy without a learner.  HB_EUNSUPPORTED: any other actor head.  A refused call changes nothing. */
 int hb_sac_create(hb_batch* b, const hb_sac_config* cfg);
 int hb_sac_configure(hb_batch* b, const hb_sac_config* cfg);

@@ -25,6 +25,7 @@ import humanoid_mujoco_amd as hb  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=15)
 ap.add_argument("--out", default=None)
+ap.add_argument("--activation", choices=("tanh", "relu", "elu"), default="tanh", help="hidden activation of actor and critic, both sides")
 args = ap.parse_args()
 N, T, ACTOR, CRITIC = 4096, 32, [48, 256, 256, 21], [48, 256, 256, 1]
 GAMMA, LAM = 0.99, 0.95
@@ -60,14 +61,14 @@ for l, (w, b) in enumerate(zip(cw, cb)):
         lin.bias.copy_(torch.from_numpy(b))
     layers.append(lin)
     if l + 1 < len(cw):
-        layers.append(torch.nn.Tanh())
+        layers.append({"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU, "elu": torch.nn.ELU}[args.activation]())
 critic = torch.nn.Sequential(*layers).to(dev)
 std = torch.from_numpy(np.exp(log_std)).to(dev)
 
 env = hb.VecEnv(model, N, 0, seed=1, reward_kind=1, max_time=0.1)
-env.actor_set(ACTOR, aw, ab, head="gaussian", log_std=log_std, seed=1)
-env.critic_set(CRITIC, cw, cb)
-say("%s, %d envs, T = %d, actor %s (Gaussian head), critic %s, gamma %.2f lam %.2f, %d windows per variant after one warm-up round [%s]" % (
+env.actor_set(ACTOR, aw, ab, head="gaussian", log_std=log_std, seed=1, activation=args.activation)
+env.critic_set(CRITIC, cw, cb, activation=args.activation)
+say(("%s, %d envs, T = %d, actor %s (Gaussian head), critic %s, " + args.activation + " hidden layers, gamma %.2f lam %.2f, %d windows per variant after one warm-up round [%s]") % (
     env.batch.device_name(), N, T, "-".join(map(str, ACTOR)), "-".join(map(str, CRITIC)), GAMMA, LAM, args.reps, "device events"))
 
 

@@ -5,13 +5,13 @@ collected with collect_torch(T, gae=...) and trained on by both.  Minibatches of
 one epoch and ten (at 64 rows the torch loop of ten epochs is 20 480 steps: only one epoch is measured there unless --full).
   (dev)   env.ppo_update(buf, n_epochs, batch_size): seven launches per minibatch on the batch's stream, the statistics read once at the end;
           the next collection runs the trained networks as they are
-  (torch) torch.nn.Linear networks, autograd, clip_grad_norm_ and torch.optim.Adam over the same rows in the same minibatch scheme
+  (torch) torch.nn.Linear networks with the matching activation module, autograd, clip_grad_norm_ and torch.optim.Adam over the same rows in the same minibatch scheme
           (one randperm per epoch), then what the torch learner needs before the next collection: the parameters to the host and
           actor_set / critic_set - on a second VecEnv of the same size that has NO learner, which is what a torch-only user runs
 Both are timed on the host clock around a device synchronisation (launch overhead is part of what is compared), alternated in one process
 after a warm-up round; printed: medians with minimum and maximum and the spread of the per-round ratio.  Every configuration runs in a child
 process of its own under its own time limit, and the first one that fails ends the run.
-usage: gpu_ppo_bench.py [--reps N] [--full] [--out FILE]     (results: profiles/ppo_bench.txt)"""
+usage: gpu_ppo_bench.py [--reps N] [--full] [--activation tanh|relu|elu] [--out FILE]     (results: profiles/ppo_bench.txt)"""
 import argparse
 import os
 import subprocess
@@ -25,6 +25,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--full", action="store_true")
 ap.add_argument("--out", default=None)
+ap.add_argument("--activation", choices=("tanh", "relu", "elu"), default="tanh", help="hidden activation of actor and critic, both sides")
 ap.add_argument("--child", nargs=2, type=int, default=None, metavar=("BATCH", "EPOCHS"))
 args = ap.parse_args()
 N, T, ACTOR, CRITIC = 4096, 32, [48, 256, 256, 21], [48, 256, 256, 1]
@@ -35,7 +36,7 @@ if args.child is None:
     for mb, ep in configs:
         limit = 900 if mb == 64 else 300
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(mb), str(ep), "--reps", str(args.reps if mb > 64 else min(args.reps, 3))],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(mb), str(ep), "--reps", str(args.reps if mb > 64 else min(args.reps, 3)), "--activation", args.activation],
                                capture_output=True, text=True, timeout=limit)
         except subprocess.TimeoutExpired:
             sys.exit("gpu_ppo_bench: batch %d, %d epoch(s) ran into its time limit of %d s - nothing more is started" % (mb, ep, limit))
@@ -78,7 +79,7 @@ def torch_net(ws, bs):
             lin.bias.copy_(torch.from_numpy(b))
         layers.append(lin)
         if l + 1 < len(ws):
-            layers.append(torch.nn.Tanh())
+            layers.append({"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU, "elu": torch.nn.ELU}[args.activation]())
     return torch.nn.Sequential(*layers).to(dev)
 
 
@@ -86,13 +87,13 @@ aw, ab = mlp(ACTOR)
 cw, cb = mlp(CRITIC)
 log_std0 = np.full(ACTOR[-1], -1.0, np.float32)
 env = hb.VecEnv(model, N, 0, seed=1, reward_kind=1, max_time=0.1)
-env.actor_set(ACTOR, aw, ab, head="gaussian", log_std=log_std0, seed=1)
-env.critic_set(CRITIC, cw, cb)
+env.actor_set(ACTOR, aw, ab, head="gaussian", log_std=log_std0, seed=1, activation=args.activation)
+env.critic_set(CRITIC, cw, cb, activation=args.activation)
 env.learner()
 env.reset()
 plain = hb.VecEnv(model, N, 0, seed=1, reward_kind=1, max_time=0.1)   # the torch learner's env: no device learner behind actor_set / critic_set
-plain.actor_set(ACTOR, aw, ab, head="gaussian", log_std=log_std0, seed=1)
-plain.critic_set(CRITIC, cw, cb)
+plain.actor_set(ACTOR, aw, ab, head="gaussian", log_std=log_std0, seed=1, activation=args.activation)
+plain.critic_set(CRITIC, cw, cb, activation=args.activation)
 buf = env.collect_torch(T, gae=dict(gamma=0.99, lam=0.95))
 R = N * T
 obs, action = buf["obs"][:T].reshape(R, -1), buf["action"].reshape(R, -1)
@@ -125,9 +126,10 @@ def torch_update():
             opt.step()
     with torch.no_grad():
         lin = [m for m in actor if isinstance(m, torch.nn.Linear)]
-        plain.actor_set(ACTOR, [m.weight.T.cpu().numpy() for m in lin], [m.bias.cpu().numpy() for m in lin], head="gaussian", log_std=log_std.cpu().numpy(), seed=1)
+        plain.actor_set(ACTOR, [m.weight.T.cpu().numpy() for m in lin], [m.bias.cpu().numpy() for m in lin], head="gaussian", log_std=log_std.cpu().numpy(), seed=1,
+                        activation=args.activation)
         lin = [m for m in critic if isinstance(m, torch.nn.Linear)]
-        plain.critic_set(CRITIC, [m.weight.T.cpu().numpy() for m in lin], [m.bias.cpu().numpy() for m in lin])
+        plain.critic_set(CRITIC, [m.weight.T.cpu().numpy() for m in lin], [m.bias.cpu().numpy() for m in lin], activation=args.activation)
 
 
 def timed(fn):

@@ -4,13 +4,13 @@ same GPU: 1024 envs of the 27-dof model, the 48-256-256-42 squashed actor and tw
 collect_torch(16, terminal_obs=True) and trained on by both, 64 gradient steps at batch_size 256 (stable-baselines3's default) and at 4096.
   (dev)   env.sac_update(replay, 64, batch_size): sixteen launches per gradient step on the batch's stream, the statistics read once at
           the end; the next collection runs the trained actor as it is
-  (torch) tanh torch.nn.Linear networks, autograd, three torch.optim.Adam, the Polyak step, over minibatches drawn the same way, then the
+  (torch) torch.nn.Linear networks with the matching activation module, autograd, three torch.optim.Adam, the Polyak step, over minibatches drawn the same way, then the
           ONE thing the torch loop owes the next collection: the actor's parameters to the host and actor_set - on a second VecEnv of
           the same size that has NO learner, which is what a torch-only user runs
 Both are timed on the host clock around a device synchronisation (launch overhead is part of what is compared), alternated in one process,
 three rounds after a warm-up round; printed: medians with minimum and maximum, the time per gradient step and the spread of the per-round
 ratio.  Every configuration runs in a child process of its own under its own time limit, and the first one that fails ends the run.
-usage: gpu_sac_bench.py [--reps N] [--out FILE]     (results: profiles/sac_bench.txt)"""
+usage: gpu_sac_bench.py [--reps N] [--activation tanh|relu|elu] [--out FILE]     (results: profiles/sac_bench.txt)"""
 import argparse
 import os
 import subprocess
@@ -23,6 +23,7 @@ sys.path.insert(0, ROOT)
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--out", default=None)
+ap.add_argument("--activation", choices=("tanh", "relu", "elu"), default="tanh", help="hidden activation of every network, both sides")
 ap.add_argument("--child", type=int, default=None, metavar="BATCH")
 args = ap.parse_args()
 N, T, STEPS, ACTOR, QNET = 1024, 16, 64, [48, 256, 256, 42], [69, 256, 256, 1]
@@ -32,7 +33,7 @@ if args.child is None:
     for mb in (256, 4096):
         limit = 240
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(mb), "--reps", str(args.reps)], capture_output=True, text=True, timeout=limit)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(mb), "--reps", str(args.reps), "--activation", args.activation], capture_output=True, text=True, timeout=limit)
         except subprocess.TimeoutExpired:
             sys.exit("gpu_sac_bench: batch %d ran into its time limit of %d s - nothing more is started" % (mb, limit))
         sys.stdout.write(r.stdout)
@@ -75,20 +76,20 @@ def torch_net(ws, bs):
             lin.bias.copy_(torch.from_numpy(b))
         layers.append(lin)
         if l + 1 < len(ws):
-            layers.append(torch.nn.Tanh())
+            layers.append({"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU, "elu": torch.nn.ELU}[args.activation]())
     return torch.nn.Sequential(*layers).to(dev)
 
 
 aw, ab = mlp(ACTOR)
 qw, qb = zip(mlp(QNET), mlp(QNET))
 env = hb.VecEnv(model, N, 0, seed=1, reward_kind=1, max_time=0.1)
-env.actor_set(ACTOR, aw, ab, head="squashed", seed=1)
+env.actor_set(ACTOR, aw, ab, head="squashed", seed=1, activation=args.activation)
 for k in range(2):
-    env.q_set(k, QNET, qw[k], qb[k])
+    env.q_set(k, QNET, qw[k], qb[k], activation=args.activation)
 env.sac_learner()
 env.reset()
 plain = hb.VecEnv(model, N, 0, seed=1, reward_kind=1, max_time=0.1)   # the torch learner's env: no device learner behind actor_set
-plain.actor_set(ACTOR, aw, ab, head="squashed", seed=1)
+plain.actor_set(ACTOR, aw, ab, head="squashed", seed=1, activation=args.activation)
 replay = hb.ReplayBuffer(N * T, model.nobs, NU, dev)
 replay.add(env.collect_torch(T, terminal_obs=True))
 
@@ -142,7 +143,7 @@ def torch_update():
                     pt.mul_(1 - 0.005).add_(p, alpha=0.005)
     with torch.no_grad():
         lin = [m for m in actor if isinstance(m, torch.nn.Linear)]
-        plain.actor_set(ACTOR, [m.weight.T.cpu().numpy() for m in lin], [m.bias.cpu().numpy() for m in lin], head="squashed", seed=1)
+        plain.actor_set(ACTOR, [m.weight.T.cpu().numpy() for m in lin], [m.bias.cpu().numpy() for m in lin], head="squashed", seed=1, activation=args.activation)
 
 
 def timed(fn):
@@ -161,7 +162,7 @@ for rep in range(args.reps + 1):  # (the first round warms both up and is not co
         ms["dev"].append(td)
         ms["torch"].append(tt)
 ratio = np.array(ms["torch"]) / np.array(ms["dev"])
-print("%s, ring of %d rows, actor %s, Q networks %s, batch_size %d, %d gradient steps, %d rounds after a warm-up round [host clock around a device synchronisation]" % (
+print(("%s, ring of %d rows, actor %s, Q networks %s, " + args.activation + " hidden layers, batch_size %d, %d gradient steps, %d rounds after a warm-up round [host clock around a device synchronisation]") % (
     env.batch.device_name(), replay.size, "-".join(map(str, ACTOR)), "-".join(map(str, QNET)), MB, STEPS, args.reps))
 for k, name in (("dev", "sac_update (device learner)"), ("torch", "torch learner + actor_set")):
     print("  %-32s median %10.2f ms (min %10.2f max %10.2f), %8.1f us per gradient step" % (name, float(np.median(ms[k])), min(ms[k]), max(ms[k]),
