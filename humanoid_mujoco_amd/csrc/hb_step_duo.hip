@@ -682,17 +682,39 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       // more contacts in one of the envs than two envs to a wave hold: one env at a time (nothing of this pass has left the wave)
       if (__ballot(ncon > kNCh)) { serial = true; continue; }
     } else if (ncon > kNconMax) { status |= (1 << 1); ncon = kNconMax; }
+    // mj_makeConstraint's table words, requested ahead of their use.  The limit candidates' records depend on the lane alone: the first two
+    // quads of every round go out here, behind the narrowphase, in one go (they used to be fetched round by round, each behind a reload of
+    // the table's base pointer, and a second time by the limit-row pass, which now keeps them).  The pair words go out as soon as the
+    // contact's pair is known, below.
+    constexpr int kLimRounds = (NLIM + H - 1) / H;
+    float4 lr0[kLimRounds], lr1[kLimRounds];
+    {
+      const float4 HB_CONST* const lrec = M.lrec;
+#pragma unroll
+      for (int k = 0; k < kLimRounds; k++) {
+        const float4 HB_CONST* LR = lrec + (size_t)min(l + H * k, NLIM - 1) * 4;  // (no predicate: a lane beyond the last candidate reads the last one's, unused)
+        lr0[k] = LR[0]; lr1[k] = LR[1];
+      }
+    }
     gsync();
     // self collision (CPUEnv._check_self_collision, cpu_env.py:576-584)
     int pairid = 0;
     if (l < ncon) pairid = __float_as_int(con_rec(l)[C_PAIR]);
-    bool selfc = false;
-    if (l < ncon) selfc = M.pair_self[pairid] != 0;
+    bool selfc;
+    float pmargin, pgap, pfric;
+    int pdim;
+    float4 pr1, pr2, pr3, pr4;
+    {  // (no predicate, so that nothing waits here: a lane without a contact reads pair 0's words and uses none of them)
+      const int pself = M.pair_self[pairid];
+      pmargin = M.pair_margin[pairid]; pgap = M.pair_gap[pairid]; pdim = M.pair_dim[pairid]; pfric = M.pair_friction[3 * pairid];
+      const float4 HB_CONST* PR = M.prec + (size_t)pairid * 5;
+      pr1 = PR[1]; pr2 = PR[2]; pr3 = PR[3]; pr4 = PR[4];
+      selfc = l < ncon && pself != 0;
+    }
 
     HB_STAMP(7);
     // ---------------------------------------------------------------- mj_makeConstraint: count, place, write
     // (a) limit candidates: 2 per limited joint / tendon in constraint order, 32 per round
-    constexpr int kLimRounds = (NLIM + H - 1) / H;
     bool lact[kLimRounds];
     float ldist[kLimRounds], lmargin[kLimRounds];
     int lrow[kLimRounds];
@@ -702,8 +724,7 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       const int c = l + H * k;
       lact[k] = false; ldist[k] = 0.f; lmargin[k] = 0.f;
       if (on && c < NLIM) {
-        const float4 HB_CONST* LR = M.lrec + (size_t)c * 4;
-        const float4 r0 = LR[0], r1 = LR[1];
+        const float4 r0 = lr0[k], r1 = lr1[k];
         const int kind = __float_as_int(r0.x), id = __float_as_int(r0.y), side = __float_as_int(r0.z);
         lmargin[k] = r1.x;
         const float value = kind == 0 ? s_qpos[__float_as_int(r0.w)] : s_tenlen[id];
@@ -717,14 +738,11 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     // (b) contacts: 0, 1 or 4 rows each
     int myrows = 0;
     bool incl = false;
-    float4 pr1 = {0.f, 0.f, 0.f, 0.f}, pr2 = pr1, pr3 = pr1, pr4 = pr1;
     if (l < ncon) {
       const float* c = con_rec(l);
-      const float includemargin = M.pair_margin[pairid] - M.pair_gap[pairid];
+      const float includemargin = pmargin - pgap;
       incl = c[C_DIST] < includemargin;
-      myrows = incl ? (M.pair_dim[pairid] == 1 ? 1 : 4) : 0;
-      const float4 HB_CONST* PR = M.prec + (size_t)pairid * 5;
-      pr1 = PR[1]; pr2 = PR[2]; pr3 = PR[3]; pr4 = PR[4];
+      myrows = incl ? (pdim == 1 ? 1 : 4) : 0;
     }
     const unsigned lower = (1u << l) - 1u;
     const unsigned one_row = (unsigned)(__ballot(myrows == 1) >> (32 * h)), four_rows = (unsigned)(__ballot(myrows == 4) >> (32 * h));
@@ -768,13 +786,24 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       if (lact[k] && lrow[k] < kNefcMax) {
         const int c = l + H * k;
         const float4 HB_CONST* LR = M.lrec + (size_t)c * 4;
-        const float4 r0 = LR[0], r1 = LR[1], r2 = LR[2], r3 = LR[3];
+        const float4 r0 = lr0[k], r1 = lr1[k], r2 = LR[2], r3 = LR[3];
         const int kind = __float_as_int(r0.x), id = __float_as_int(r0.y), side = __float_as_int(r0.z);
+        // a tendon row's words in one go: the count and the tendon's record (trec: the coefficients and dof addresses of its first four
+        // wraps, the same numbers as wrap_prm / wrap_dofadr) - not tendon_num -> tendon_adr -> wrap_dofadr / wrap_prm per wrap
+        int tnum = 0;
+        float4 tcoef = {0.f, 0.f, 0.f, 0.f}, tdof = tcoef;
+        if (kind != 0) { tnum = M.tendon_num[id]; tcoef = M.trec[3 * id]; tdof = M.trec[3 * id + 2]; }
         const int prow = rbase + lrow[k];
         float* Jr = s_C + prow * kCsD;
         for (int kk = 0; kk < kCsD; kk++) Jr[kk] = 0.f;
         if (kind == 0) Jr[__float_as_int(r3.z)] = (float)(-side);
-        else for (int w = 0; w < M.tendon_num[id]; w++) Jr[M.wrap_dofadr[M.tendon_adr[id] + w]] = (float)(-side) * M.wrap_prm[M.tendon_adr[id] + w];
+        else {
+          if (tnum > 0) Jr[__float_as_int(tdof.x)] = (float)(-side) * tcoef.x;
+          if (tnum > 1) Jr[__float_as_int(tdof.y)] = (float)(-side) * tcoef.y;
+          if (tnum > 2) Jr[__float_as_int(tdof.z)] = (float)(-side) * tcoef.z;
+          if (tnum > 3) Jr[__float_as_int(tdof.w)] = (float)(-side) * tcoef.w;
+          for (int w = 4; w < tnum; w++) Jr[M.wrap_dofadr[M.tendon_adr[id] + w]] = (float)(-side) * M.wrap_prm[M.tendon_adr[id] + w];
+        }
         float* e = s_meta + prow;
         e[E_POS * 64] = ldist[k]; e[E_MARGIN * 64] = lmargin[k];
         e[E_SOLREF0 * 64] = r1.z; e[E_SOLREF1 * 64] = r1.w;
@@ -787,8 +816,8 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     const int rowv = placedl ? base : -1;
     if (l < ncon) {
       float* c = con_rec(l);
-      const int cdim = M.pair_dim[pairid] == 1 ? 1 : 3;
-      const float mu = fmaxf(1e-5f, M.pair_friction[3 * pairid]);
+      const int cdim = pdim == 1 ? 1 : 3;
+      const float mu = fmaxf(1e-5f, pfric);
       c[C_ROW] = __int_as_float(rowv);
       c[C_DIM] = __int_as_float(cdim);
       c[C_FRIC] = mu;
@@ -943,7 +972,7 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
             const float* Wp = lds + envLo * kEnvF + o_W;
             float a[14];
 #pragma unroll
-            for (int kk = 0; kk < 14; kk++) a[kk] = av ? Ap[2 * kk] : 0.f;
+            for (int kk = 0; kk < 14; kk++) { const float w = Ap[2 * kk]; a[kk] = av ? w : 0.f; }
 #pragma unroll
             for (int kk = 0; kk < 14; kk++) D = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], Wp[(2 * kk + half) * kWsD + col], D, 0, 0, 0);
           }
@@ -952,7 +981,7 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
             const float* Wp = lds + (1 - envLo) * kEnvF + o_W;
             float a[14];
 #pragma unroll
-            for (int kk = 0; kk < 14; kk++) a[kk] = av ? Ap[2 * kk] : 0.f;
+            for (int kk = 0; kk < 14; kk++) { const float w = Ap[2 * kk]; a[kk] = av ? w : 0.f; }
 #pragma unroll
             for (int kk = 0; kk < 14; kk++) D = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], Wp[(2 * kk + half) * kWsD + col], D, 0, 0, 0);
           }
@@ -980,7 +1009,8 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       float jas = 0.f, diag = 0.f;
 #pragma unroll
       for (int k = 0; k < 28; k++) {
-        const float c = rowact ? Cr[k] : 0.f;
+        const float w = Cr[k];
+        const float c = rowact ? w : 0.f;
         jas += c * yv[k];
         diag += c * c;
       }
@@ -1030,7 +1060,8 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       {
 #pragma unroll
         for (int kk = 0; kk < 14; kk++) {
-          const float a0 = lo0 ? A0p[2 * kk] : 0.f;
+          const float w0 = A0p[2 * kk];
+          const float a0 = lo0 ? w0 : 0.f;
           X0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, a0, X0, 0, 0, 0);
         }
         if (nLo > 32) {  // (never paired)
@@ -1049,13 +1080,15 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
         if (hiY0) {
 #pragma unroll
           for (int kk = 0; kk < 14; kk++) {
-            const float a1 = hi1 ? A1p[2 * kk] : 0.f;
+            const float w1 = A1p[2 * kk];
+            const float a1 = hi1 ? w1 : 0.f;
             Y0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, a1, Y0, 0, 0, 0);
           }
         } else {
 #pragma unroll
           for (int kk = 0; kk < 14; kk++) {
-            const float a1 = hi1 ? A1p[2 * kk] : 0.f;
+            const float w1 = A1p[2 * kk];
+            const float a1 = hi1 ? w1 : 0.f;
             Y1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, a1, Y1, 0, 0, 0);
           }
         }
@@ -1418,10 +1451,23 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
       const int mybase = (h == envLo) ? 0 : split, myn = (h == envLo) ? nLo : nHi;
       const int kc = l < kCsD ? l : 0;
       float sacc = 0.f;
-      for (int i = 0; i < nmax; i++) {
-        const float fa = rdlane(fz, i), fb = rdlane(fz, (split + i) & 63);
-        const float f = (h == envLo) ? fa : fb;
-        if (i < myn) sacc += f * s_C[(mybase + i) * kCsD + kc];
+      // Four rows' words of C are read together, ahead of the four dependent adds, each without a predicate: the row index is clamped into C
+      // (packed, the other env's i runs past this env's rows, and C is the last array of the LDS map), and the condition picks VALUES.  (The
+      // empty asm pins each word in front of the selects: left to itself the compiler moves the read back under the condition.)
+      for (int i0 = 0; i0 < nmax; i0 += 4) {
+        float cw[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) cw[r] = s_C[min(mybase + i0 + r, 63) * kCsD + kc];
+#pragma unroll
+        for (int r = 0; r < 4; r++) asm volatile("" : "+v"(cw[r]));
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int i = i0 + r;
+          const float fa = rdlane(fz, i & 63), fb = rdlane(fz, (split + i) & 63);
+          const float f = (h == envLo) ? fa : fb;
+          const float cz = i < myn ? cw[r] : 0.f;
+          sacc = i < myn ? sacc + f * cz : sacc;
+        }
       }
       const float* myy = s_C + (mybase + myn) * kCsD;
       if (dofl) s_v2[l] = myy[l] + sacc;  // y + s
