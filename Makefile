@@ -2,13 +2,13 @@
 HIPCC ?= hipcc
 ARCH ?= gfx950
 CSRC := humanoid_mujoco_amd/csrc
-HOST_SRCS := $(CSRC)/hb_api.cpp $(CSRC)/hb_api_rollout.cpp $(CSRC)/hb_api_env.cpp $(CSRC)/hb_api_dyn.cpp $(CSRC)/hb_api_ppo.cpp $(CSRC)/hb_api_sac.cpp $(CSRC)/hb_batch.cpp $(CSRC)/hb_tables.cpp $(CSRC)/mjcf.cpp $(CSRC)/setconst.cpp $(CSRC)/model_io.cpp $(CSRC)/mesh.cpp
+HOST_SRCS := $(CSRC)/hb_api.cpp $(CSRC)/hb_api_rollout.cpp $(CSRC)/hb_api_env.cpp $(CSRC)/hb_api_dyn.cpp $(CSRC)/hb_api_ppo.cpp $(CSRC)/hb_api_sac.cpp $(CSRC)/hb_learn_host.cpp $(CSRC)/hb_batch.cpp $(CSRC)/hb_tables.cpp $(CSRC)/mjcf.cpp $(CSRC)/setconst.cpp $(CSRC)/model_io.cpp $(CSRC)/mesh.cpp
 HIP_SRCS := $(CSRC)/hb_step.hip $(CSRC)/hb_step_duo.hip $(CSRC)/hb_narrow.hip $(CSRC)/hb_env.hip $(CSRC)/hb_actor.hip $(CSRC)/hb_gae.hip $(CSRC)/hb_norm.hip $(CSRC)/hb_ppo.hip $(CSRC)/hb_sac.hip $(CSRC)/hb_kin.hip $(CSRC)/hb_ray.hip $(CSRC)/hb_dyn.hip
 HDRS := $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inl) include/hb.h
 LIB := humanoid_mujoco_amd/libhb.so
 FLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result -ffp-contract=on -fno-slp-vectorize -fno-vectorize $(EXTRA)
 
-all: $(LIB) build/hb_compile build/hb_tables build/hb_testspeed oracle
+all: $(LIB) build/hb_compile build/hb_tables build/hb_learn_check build/hb_testspeed oracle
 
 # host sources are plain C++ (HIP runtime API only); only the kernels are compiled for the device
 HOSTFLAGS := -O2 -std=c++17 -fPIC -Wall -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
@@ -51,6 +51,14 @@ build/hb_tables: $(TABLES_SRCS) $(HDRS)
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -o $@ $(TABLES_SRCS)
 
+# the learners' host arithmetic and operand refresh checked on the host (header-only: nothing of HIP is linked); _san: under sanitizers
+build/hb_learn_check: tools/hb_learn_check.cpp $(HDRS)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -o $@ tools/hb_learn_check.cpp
+build/hb_learn_check_san: tools/hb_learn_check.cpp $(HDRS)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tools/hb_learn_check.cpp
+
 build/hb_testspeed: tools/hb_testspeed.cpp $(LIB) include/hb.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -Wall -Iinclude -o $@ tools/hb_testspeed.cpp -Lhumanoid_mujoco_amd -lhb -Wl,-rpath,'$$ORIGIN/../humanoid_mujoco_amd'
@@ -63,7 +71,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) build/hb_compile build/hb_tables build/hb_testspeed
+	rm -f $(LIB) build/hb_compile build/hb_tables build/hb_learn_check build/hb_learn_check_san build/hb_testspeed
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

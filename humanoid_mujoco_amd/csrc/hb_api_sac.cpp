@@ -4,8 +4,17 @@
 
 namespace {
 
-// network k of the flat record: the actor, Q1, Q2
-const DevMlp& net_of(const hb_batch* b, int k) { return k == 0 ? b->actor : b->q[k - 1]; }
+// the networks of the flat record: the actor, Q1, Q2; layer 0 of a Q network has the transpose of its action rows (dQ / da)
+LearnNets nets_of(const hb_batch* b) {
+  const int nobs = b->D.dm.nobs;
+  return LearnNets{3, {&b->actor, &b->q[0], &b->q[1]}, {-1, nobs, nobs}};
+}
+// the same with the targets in the Q networks' places (their tensors stand where their Q network's do)
+LearnNets target_nets_of(hb_batch* b) {
+  LearnNets ns = nets_of(b);
+  ns.net[1] = &b->sac.tq[0]; ns.net[2] = &b->sac.tq[1];
+  return ns;
+}
 
 bool cfg_ok(const hb_sac_config* c) {
   const float f[] = {c->gamma, c->tau, c->lr_actor, c->lr_critic, c->lr_ent, c->beta1, c->beta2, c->eps, c->ent_coef_init, c->target_entropy};
@@ -17,71 +26,11 @@ bool cfg_ok(const hb_sac_config* c) {
 // the flat layout (include/hb.h): the actor's layers W | b, Q1's, Q2's, log_ent_coef
 void layout(hb_batch* b) {
   SacLearner& L = b->sac;
-  int o = 0;
-  for (int k = 0; k < 3; k++) {
-    if (k == 1) L.off_q = o;
-    const DevMlp& n = net_of(b, k);
-    for (int l = 0; l < n.layers; l++) {
-      L.off_w[k][l] = o; o += n.sizes[l] * n.sizes[l + 1];
-      L.off_b[k][l] = o; o += n.sizes[l + 1];
-    }
-  }
-  L.PT = o - L.off_q;
-  L.P = o + 1;
-}
-
-// the flat record of what is installed (the packed operands read back from the device); the last entry is left 0
-int read_installed(hb_batch* b, std::vector<float>& flat) {
-  const SacLearner& L = b->sac;
-  flat.assign(L.P, 0.f);
-  for (int k = 0; k < 3; k++) {
-    const DevMlp& n = net_of(b, k);
-    for (int l = 0; l < n.layers; l++) {
-      const int K = n.sizes[l], N = n.sizes[l + 1];
-      std::vector<float> packed(n.wp[l].capacity());
-      HB_HIP(hipMemcpy(packed.data(), n.wp[l], packed.size() * sizeof(float), hipMemcpyDeviceToHost));
-      const std::vector<float> W = DevMlp::unpack_mfma_b(packed, K, N);
-      memcpy(&flat[L.off_w[k][l]], W.data(), W.size() * sizeof(float));
-      HB_HIP(hipMemcpy(&flat[L.off_b[k][l]], n.b[l], N * sizeof(float), hipMemcpyDeviceToHost));
-    }
-  }
-  return HB_OK;
-}
-
-// the packed transpose of rows k0 .. K - 1 of W[K][N]
-int write_transpose(DevBuf<float>& dst, const float* W, int K, int N, int k0) {
-  const int Ka = K - k0;
-  std::vector<float> Wt((size_t)N * Ka);
-  for (int kk = 0; kk < Ka; kk++) for (int nn = 0; nn < N; nn++) Wt[(size_t)nn * Ka + kk] = W[(size_t)(k0 + kk) * N + nn];
-  const std::vector<float> packed = DevMlp::pack_mfma_b(Wt.data(), N, Ka);
-  if (dst.reserve(packed.size()) != HB_OK) return HB_ENOMEM;
-  HB_HIP(hipMemcpy(dst, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-  return HB_OK;
-}
-
-// the flat record to the device: the master copy and every operand the kernels read (forward: only with `forward`; the packed
-// transposes always).  The stream is idle.
-int write_params(hb_batch* b, const float* flat, bool forward) {
-  SacLearner& L = b->sac;
-  const int nobs = b->D.dm.nobs;
-  HB_HIP(hipMemcpy(L.d_param, flat, (size_t)L.P * sizeof(float), hipMemcpyHostToDevice));
-  for (int k = 0; k < 3; k++) {
-    const DevMlp& n = net_of(b, k);
-    for (int l = 0; l < n.layers; l++) {
-      const int K = n.sizes[l], N = n.sizes[l + 1];
-      const float* W = flat + L.off_w[k][l];
-      if (forward) {
-        const std::vector<float> packed = DevMlp::pack_mfma_b(W, K, N);
-        HB_HIP(hipMemcpy(n.wp[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-        HB_HIP(hipMemcpy(n.b[l], flat + L.off_b[k][l], N * sizeof(float), hipMemcpyHostToDevice));
-      }
-      if (l > 0 || k > 0) {
-        const int rc = write_transpose(L.d_wt[k][l], W, K, N, l == 0 ? nobs : 0);
-        if (rc != HB_OK) return rc;
-      }
-    }
-  }
-  return HB_OK;
+  const LearnNets ns = nets_of(b);
+  L.off_q = L.layout(ns, 0, 0);
+  const int end = L.layout(ns, 2, L.layout(ns, 1, L.off_q));
+  L.PT = end - L.off_q;
+  L.P = end + 1;
 }
 
 // the targets' record to the device, and the operands of their forward pass
@@ -99,26 +48,7 @@ int write_targets(hb_batch* b, const float* rec) {
   return HB_OK;
 }
 
-int idle(hb_batch* b) {
-  HB_HIP(hipSetDevice(b->device));
-  HB_HIP(hipStreamSynchronize(main_stream(b)));
-  return HB_OK;
-}
-
 float target_entropy(const hb_batch* b) { return b->sac.cfg.target_entropy_auto ? -(float)b->D.dm.nu : b->sac.cfg.target_entropy; }
-
-// the tensors of network k as Adam / Polyak segments; base: what a start is relative to; targets: the operands of tq, no transposes
-int segments(hb_batch* b, int k, int base, bool targets, SacSeg* seg) {
-  SacLearner& L = b->sac;
-  const DevMlp& n = targets ? L.tq[k - 1] : net_of(b, k);
-  int ns = 0;
-  for (int l = 0; l < n.layers; l++) {
-    float* dst_t = targets || (l == 0 && k == 0) ? nullptr : L.d_wt[k][l].get();
-    seg[ns++] = SacSeg{L.off_w[k][l] - base, n.sizes[l], n.sizes[l + 1], l == 0 && k > 0 ? b->D.dm.nobs : 0, n.wp[l].get(), dst_t};
-    seg[ns++] = SacSeg{L.off_b[k][l] - base, 0, n.sizes[l + 1], 0, n.b[l].get(), nullptr};
-  }
-  return ns;
-}
 
 }  // namespace
 
@@ -128,7 +58,7 @@ int hb_q_set_mlp(hb_batch* b, int k, int n_layers, const int* sizes, const float
   if (!b || k < 0 || k > 1 || !mlp_args_ok(n_layers, sizes, weights, biases)) return HB_EINVAL;
   if (sizes[0] != b->D.dm.nobs + b->D.dm.nu || sizes[n_layers] != 1) return HB_EINVAL;
   for (int l = 0; l <= n_layers; l++) if (sizes[l] > 256) return HB_EUNSUPPORTED;  // (the fused kernel's LDS tiles; no layer-by-layer fallback)
-  const int rc = idle(b);  // (a call still in flight reads the buffers that are replaced below)
+  const int rc = learner_idle(b);  // (a call still in flight reads the buffers that are replaced below)
   if (rc != HB_OK) return rc;
   b->sac.clear();
   return b->q[k].install(n_layers, sizes, weights, biases);
@@ -171,25 +101,20 @@ int hb_sac_create(hb_batch* b, const hb_sac_config* cfg) {
   if (b->actor_cfg.head != HB_ACTOR_SQUASHED) return HB_EUNSUPPORTED;
   const int nu = b->D.dm.nu;
   if (nu < 1 || nu > kActorMaxNu) return HB_EINVAL;
-  int rc = idle(b);
+  int rc = learner_idle(b);
   if (rc != HB_OK) return rc;
   SacLearner& L = b->sac;
   L.clear();
   layout(b);
-  const size_t P = L.P;
-  rc = L.d_param.alloc(P);
-  if (rc == HB_OK) rc = L.d_grad.alloc(P, true);
-  if (rc == HB_OK) rc = L.d_m.alloc(P, true);
-  if (rc == HB_OK) rc = L.d_v.alloc(P, true);
+  const LearnNets ns = nets_of(b);
+  rc = L.alloc_record(64 * kSacSrow);
   if (rc == HB_OK) rc = L.d_target.alloc(L.PT);
-  if (rc == HB_OK) rc = L.d_zero.alloc(256, true);
   if (rc == HB_OK) rc = L.d_alpha.alloc(4, true);
-  if (rc == HB_OK) rc = L.d_dbl.alloc(64 * kSacSrow, true);
   std::vector<float> flat;
-  if (rc == HB_OK) rc = read_installed(b, flat);
+  if (rc == HB_OK) rc = L.read_installed(ns, flat);
   if (rc == HB_OK) {
-    flat[P - 1] = (float)std::log((double)cfg->ent_coef_init);
-    rc = write_params(b, flat.data(), false);
+    flat[L.P - 1] = (float)std::log((double)cfg->ent_coef_init);
+    rc = L.write_params(ns, flat.data(), false);
   }
   if (rc == HB_OK) rc = write_targets(b, flat.data() + L.off_q);
   if (rc != HB_OK) { L.clear(); return rc; }
@@ -206,7 +131,7 @@ int hb_sac_configure(hb_batch* b, const hb_sac_config* cfg) {
 
 int hb_sac_destroy(hb_batch* b) {
   if (!b || !b->sac.on) return HB_EINVAL;
-  const int rc = idle(b);
+  const int rc = learner_idle(b);
   if (rc != HB_OK) return rc;
   b->sac.clear();
   return HB_OK;
@@ -215,32 +140,21 @@ int hb_sac_destroy(hb_batch* b) {
 long long hb_sac_param_count(hb_batch* b) { return b && b->sac.on ? b->sac.P : HB_EINVAL; }
 long long hb_sac_target_count(hb_batch* b) { return b && b->sac.on ? b->sac.PT : HB_EINVAL; }
 
-static int get_flat(hb_batch* b, const float* dev, float* out, long long count) {
-  if (!b || !out || !b->sac.on || count != b->sac.P) return HB_EINVAL;
-  const int rc = idle(b);
-  if (rc != HB_OK) return rc;
-  HB_HIP(hipMemcpy(out, dev, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-  return HB_OK;
-}
-
-int hb_sac_get_params(hb_batch* b, float* out, long long count) { return get_flat(b, b ? b->sac.d_param.get() : nullptr, out, count); }
-int hb_sac_get_grads(hb_batch* b, float* out, long long count) { return get_flat(b, b ? b->sac.d_grad.get() : nullptr, out, count); }
+int hb_sac_get_params(hb_batch* b, float* out, long long count) { return b ? b->sac.download(b, b->sac.d_param, out, count) : HB_EINVAL; }
+int hb_sac_get_grads(hb_batch* b, float* out, long long count) { return b ? b->sac.download(b, b->sac.d_grad, out, count) : HB_EINVAL; }
 
 int hb_sac_set_params(hb_batch* b, const float* in, long long count) {
   if (!b || !in || !b->sac.on || count != b->sac.P) return HB_EINVAL;
-  const int rc = idle(b);
+  const int rc = learner_idle(b);
   if (rc != HB_OK) return rc;
-  return write_params(b, in, true);
+  return b->sac.write_params(nets_of(b), in, true);
 }
 
 int hb_sac_get_state(hb_batch* b, float* params, float* m, float* v, long long count, float* targets, long long target_count, long long* t) {
   if (!b || !params || !m || !v || !targets || !t || !b->sac.on || count != b->sac.P || target_count != b->sac.PT) return HB_EINVAL;
   SacLearner& L = b->sac;
-  const int rc = idle(b);
+  const int rc = L.get_record(b, params, m, v);
   if (rc != HB_OK) return rc;
-  HB_HIP(hipMemcpy(params, L.d_param, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-  HB_HIP(hipMemcpy(m, L.d_m, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-  HB_HIP(hipMemcpy(v, L.d_v, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
   HB_HIP(hipMemcpy(targets, L.d_target, (size_t)target_count * sizeof(float), hipMemcpyDeviceToHost));
   *t = L.t;
   return HB_OK;
@@ -249,12 +163,11 @@ int hb_sac_get_state(hb_batch* b, float* params, float* m, float* v, long long c
 int hb_sac_set_state(hb_batch* b, const float* params, const float* m, const float* v, long long count, const float* targets, long long target_count, long long t) {
   if (!b || !params || !m || !v || !targets || !b->sac.on || count != b->sac.P || target_count != b->sac.PT || t < 0) return HB_EINVAL;
   SacLearner& L = b->sac;
-  int rc = idle(b);
+  int rc = learner_idle(b);
   if (rc != HB_OK) return rc;
-  if ((rc = write_params(b, params, true)) != HB_OK) return rc;
+  if ((rc = L.write_params(nets_of(b), params, true)) != HB_OK) return rc;
   if ((rc = write_targets(b, targets)) != HB_OK) return rc;
-  HB_HIP(hipMemcpy(L.d_m, m, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
-  HB_HIP(hipMemcpy(L.d_v, v, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
+  if ((rc = L.set_moments(m, v)) != HB_OK) return rc;
   L.t = t;
   return HB_OK;
 }
@@ -272,59 +185,40 @@ int hb_sac_step_dev(hb_batch* b, const hb_sac_rows* rows, float* stats_dev) {
   const DevMlp& A = b->actor;
   const DevMlp& Q = b->q[0];
   const int La = A.layers, Lq = Q.layers;
-  auto r4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
   const int chunk = ppo_row_chunk(rows->mb), nchunk = (rows->mb + chunk - 1) / chunk;
-  // the scratch: the actor's input rows, activations, dZ and its two outputs | the samples | per Q network: activations, dZ, the three
-  // outputs and dQ / da | the Q networks' input rows | the by-row terms
-  size_t need = r4(mb * nobs) + 2 * r4(mb * 2 * nu) + 3 * r4(mb * nu) + 2 * r4(mb) + r4(mb * (nobs + nu)) + r4(mb * kSacSrow);
-  for (int l = 1; l < La; l++) need += r4(mb * A.sizes[l]);
-  for (int l = 0; l < La; l++) need += r4(mb * A.sizes[l + 1]);
-  for (int k = 0; k < 2; k++) {
-    for (int l = 1; l < Lq; l++) need += r4(mb * Q.sizes[l]);
-    for (int l = 0; l < Lq; l++) need += r4(mb * Q.sizes[l + 1]);
-    need += 3 * r4(mb) + r4(mb * nu);
-  }
-  if (need > L.d_scratch.capacity() || (size_t)nchunk * L.P > L.d_part.capacity()) {
-    HB_HIP(hipStreamSynchronize(st));  // (a call still in flight uses the buffers that are replaced)
-    if (L.d_scratch.reserve(need) != HB_OK || L.d_part.reserve((size_t)nchunk * L.P) != HB_OK) return HB_ENOMEM;
-  }
-  float* p = L.d_scratch;
-  auto take = [&](size_t n) { float* q = p; p += r4(n); return q; };
+  const LearnNets ns = nets_of(b), ts = target_nets_of(b);
+  // the scratch: the actor's input rows, activations, dZ and its two outputs | the samples | the Q networks' input rows | per Q network:
+  // activations, dZ, the three outputs and dQ / da | the by-row terms
   float *a_act[4] = {}, *a_dz[4] = {}, *q_act[2][4] = {}, *q_dz[2][4] = {};
-  a_act[0] = take(mb * nobs);
-  for (int l = 1; l < La; l++) a_act[l] = take(mb * A.sizes[l]);
-  for (int l = 0; l < La; l++) a_dz[l] = take(mb * A.sizes[l + 1]);
-  float* pi_out = take(mb * 2 * nu);
-  float* nx_out = take(mb * 2 * nu);
-  float* a_pi = take(mb * nu);
-  float* a_nx = take(mb * nu);
-  float* eps = take(mb * nu);
-  float* lp_pi = take(mb);
-  float* lp_nx = take(mb);
-  float* q_in = take(mb * (nobs + nu));
-  float *q_out[2], *qt_out[2], *qpi_out[2], *q_da[2];
-  for (int k = 0; k < 2; k++) {
-    q_act[k][0] = q_in;
-    for (int l = 1; l < Lq; l++) q_act[k][l] = take(mb * Q.sizes[l]);
-    for (int l = 0; l < Lq; l++) q_dz[k][l] = take(mb * Q.sizes[l + 1]);
-    q_out[k] = take(mb); qt_out[k] = take(mb); qpi_out[k] = take(mb);
-    q_da[k] = take(mb * nu);
-  }
-  float* srow = take(mb * kSacSrow);
-
-  // the reversed network of net k (0 actor, 1 Q1, 2 Q2): nl = L - 1 steps down to dZ_0, or L steps into the action inputs
-  auto reversed = [&](int k, bool to_input) {
-    const DevMlp& n = net_of(b, k);
-    const int nl = n.layers;
-    PolicyDesc r;
-    memset(&r, 0, sizeof r);
-    r.nl = to_input ? nl : nl - 1;
-    r.ldx = n.desc().ldx;
-    for (int j = 0; j <= nl - 1; j++) r.sizes[j] = n.sizes[nl - j];
-    if (to_input) r.sizes[nl] = (int)nu;
-    for (int j = 0; j < r.nl; j++) { r.w[j] = L.d_wt[k][nl - 1 - j]; r.b[j] = L.d_zero; }
-    return r;
+  float *pi_out, *nx_out, *a_pi, *a_nx, *eps, *lp_pi, *lp_nx, *q_in, *q_out[2], *qt_out[2], *qpi_out[2], *q_da[2], *srow;
+  auto carve = [&](ScratchCarve c) {
+    a_act[0] = c.take(mb * nobs);
+    for (int l = 1; l < La; l++) a_act[l] = c.take(mb * A.sizes[l]);
+    for (int l = 0; l < La; l++) a_dz[l] = c.take(mb * A.sizes[l + 1]);
+    pi_out = c.take(mb * 2 * nu);
+    nx_out = c.take(mb * 2 * nu);
+    a_pi = c.take(mb * nu);
+    a_nx = c.take(mb * nu);
+    eps = c.take(mb * nu);
+    lp_pi = c.take(mb);
+    lp_nx = c.take(mb);
+    q_in = c.take(mb * (nobs + nu));
+    for (int k = 0; k < 2; k++) {
+      q_act[k][0] = q_in;
+      for (int l = 1; l < Lq; l++) q_act[k][l] = c.take(mb * Q.sizes[l]);
+      for (int l = 0; l < Lq; l++) q_dz[k][l] = c.take(mb * Q.sizes[l + 1]);
+      q_out[k] = c.take(mb); qt_out[k] = c.take(mb); qpi_out[k] = c.take(mb);
+      q_da[k] = c.take(mb * nu);
+    }
+    srow = c.take(mb * kSacSrow);
+    return c.used;
   };
+  const int rc = L.reserve_scratch(carve(ScratchCarve{}), nchunk, st);
+  if (rc != HB_OK) return rc;
+  carve(ScratchCarve{L.d_scratch, 0});
+
+  // the reversed network of net k (0 actor, 1 Q1, 2 Q2): L - 1 steps down to dZ_0, or L steps into the action inputs
+  auto reversed = [&](int k, bool to_input) { return learn_reversed(L.view(ns, k), to_input ? (int)nu : 0, L.d_zero); };
   auto fwd_job = [&](SacFwdJob& j, const DevMlp& n, const float* x0, const float* x1, bool gather1, float* in_store, float* const* act, float* out) {
     j.net = n.desc();
     j.x0 = x0; j.n0 = (int)nobs; j.gather0 = 1;
@@ -334,7 +228,7 @@ int hb_sac_step_dev(hb_batch* b, const hb_sac_rows* rows, float* stats_dev) {
     j.out = out;
   };
   auto wg_jobs = [&](SacWgDesc& w, int k, float* const* act, float* const* dz) {
-    const DevMlp& n = net_of(b, k);
+    const DevMlp& n = *ns.net[k];
     for (int l = 0; l < n.layers; l++) w.job[w.njob++] = SacWgJob{act[l], dz[l], n.sizes[l], n.sizes[l + 1], L.off_w[k][l], L.off_b[k][l]};
   };
   const long long t1 = L.t + 1;
@@ -401,9 +295,9 @@ int hb_sac_step_dev(hb_batch* b, const hb_sac_rows* rows, float* stats_dev) {
   ad.param = L.d_param; ad.m = L.d_m; ad.v = L.d_v; ad.grad = L.d_grad; ad.t = t1;
   ad.beta1 = L.cfg.beta1; ad.beta2 = L.cfg.beta2; ad.eps = L.cfg.eps; ad.lr_ent = L.cfg.lr_ent;
   ad.lo = L.off_q; ad.hi = L.cfg.auto_ent ? L.P : L.P - 1; ad.ent_index = L.P - 1; ad.lr = L.cfg.lr_critic;
-  ad.nseg = segments(b, 1, 0, false, ad.seg);
-  ad.nseg += segments(b, 2, 0, false, ad.seg + ad.nseg);
-  ad.seg[ad.nseg++] = SacSeg{L.P - 1, 0, 1, 0, nullptr, nullptr};
+  ad.nseg = learn_segments(L.view(ns, 1), 0, ad.seg);
+  ad.nseg += learn_segments(L.view(ns, 2), 0, ad.seg + ad.nseg);
+  ad.seg[ad.nseg++] = ParamSeg{L.P - 1, 0, 1, 0, nullptr, nullptr};
   HB_HIP(launch_sac_adam(ad, st));
   // 9. the updated Q1, Q2 on obs | a_pi
   memset(f.job, 0, sizeof f.job);
@@ -441,15 +335,15 @@ int hb_sac_step_dev(hb_batch* b, const hb_sac_rows* rows, float* stats_dev) {
   HB_HIP(launch_sac_reduce(rd, st));
   ad.lo = 0; ad.hi = L.off_q; ad.ent_index = -1; ad.lr = L.cfg.lr_actor;
   memset(ad.seg, 0, sizeof ad.seg);
-  ad.nseg = segments(b, 0, 0, false, ad.seg);
+  ad.nseg = learn_segments(L.view(ns, 0), 0, ad.seg);
   HB_HIP(launch_sac_adam(ad, st));
   // 16. the targets
   if (t1 % L.cfg.target_update_interval == 0) {
     SacPolyakDesc pk;
     memset(&pk, 0, sizeof pk);
     pk.n = L.PT; pk.src = L.d_param + L.off_q; pk.target = L.d_target; pk.tau = L.cfg.tau;
-    pk.nseg = segments(b, 1, L.off_q, true, pk.seg);
-    pk.nseg += segments(b, 2, L.off_q, true, pk.seg + pk.nseg);
+    pk.nseg = learn_segments(L.view(ts, 1, false), L.off_q, pk.seg);
+    pk.nseg += learn_segments(L.view(ts, 2, false), L.off_q, pk.seg + pk.nseg);
     HB_HIP(launch_sac_polyak(pk, st));
   }
   L.t = t1;

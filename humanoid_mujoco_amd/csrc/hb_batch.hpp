@@ -4,6 +4,7 @@
 #include "../../include/hb.h"
 #include "hb_device.hpp"
 #include "hb_launch.hpp"
+#include "hb_learn_host.hpp"
 #include "hb_model.hpp"
 #include <algorithm>
 #include <cmath>
@@ -98,10 +99,9 @@ struct DevMlp {
   }
   // its inverse: W[K][N] from the packed operand (the learners read the installed networks back)
   static std::vector<float> unpack_mfma_b(const std::vector<float>& packed, int K, int N) {
-    const int KK = (K + 3) / 4;
     std::vector<float> W((size_t)K * N);
     for (int k = 0; k < K; k++)
-      for (int n = 0; n < N; n++) W[(size_t)k * N + n] = packed[((size_t)(n >> 4) * KK + (k >> 2)) * 64 + (k & 3) * 16 + (n & 15)];
+      for (int n = 0; n < N; n++) W[(size_t)k * N + n] = packed[packed_b_index(k, n, K)];
     return W;
   }
   void clear() {
@@ -143,52 +143,79 @@ inline bool mlp_args_ok(int n_layers, const int* sizes, const float* const* weig
   return true;
 }
 
-// The PPO learner of a batch (hb_learner_*, hb_api_ppo.cpp): the trainable parameters as ONE flat record (include/hb.h: the actor's layers
-// W | b, log_std, the critic's layers), the gradient and the Adam moments in the same layout, the packed transposes of the weights the
-// backward pass multiplies by (layer 0 needs none), and the scratch of a minibatch.  The forward operands stay where they are: in the
-// batch's actor and critic (DevMlp), which hb_ppo_adam_kernel refreshes entry by entry.
-struct Learner {
+// What the learners of a batch share (hb_learn_host.cpp): the trainable parameters of up to three networks as ONE flat record (per
+// network its layers W | b; what else the record holds is the learner's), the gradient and the Adam moments in the same layout, the
+// packed transposes of the weights the backward pass multiplies by (LearnNet: which layers have one), and the scratch of a minibatch.
+// The forward operands stay where they are: in the batch's networks (DevMlp), which the Adam kernels refresh entry by entry.
+struct LearnNets {
+  int n;
+  const DevMlp* net[3];  // in the order of the record
+  int k0[3];             // LearnNet::k0 of each
+};
+struct LearnerCore {
   bool on = false;
-  hb_ppo_config cfg = {};
-  int P = 0, off_log_std = 0;
-  int off_w[2][4] = {}, off_b[2][4] = {};
-  long long calls = 0;         // Adam calls since t was last set; t = calls - the device's count of skipped steps
-  bool log_std_dirty = false;  // the device's log_std is newer than actor_cfg.log_std
-  DevBuf<float> d_param, d_grad, d_m, d_v, d_zero, d_wt[2][4];
+  int P = 0;
+  int off_w[3][4] = {}, off_b[3][4] = {};
+  DevBuf<float> d_param, d_grad, d_m, d_v, d_zero, d_wt[3][4];
   DevBuf<float> d_scratch;     // activations, dZ, outputs and the by-row terms of a minibatch: grows with mb
   DevBuf<float> d_part;        // [64][P] chunk partials of the gradient
-  DevBuf<double> d_dbl;        // advpart [64][2] | statpart [64][8] | normpart
-  DevBuf<int> d_nskip;
+  DevBuf<double> d_dbl;        // the learner's fp64 partials
   void clear() {
-    on = false; P = 0; calls = 0; log_std_dirty = false;
-    reset_all(d_param, d_grad, d_m, d_v, d_zero, d_scratch, d_part, d_dbl);
+    on = false; P = 0;
+    reset_all(d_param, d_grad, d_m, d_v, d_zero, d_scratch, d_part);
+    d_dbl.reset();
+    for (int k = 0; k < 3; k++) for (int l = 0; l < 4; l++) d_wt[k][l].reset();
+  }
+  // network k as plain data (hb_learn_host.hpp); with_t false: without the transposes (a target network, which has none)
+  LearnNet view(const LearnNets& ns, int k, bool with_t = true) const;
+  // the layers of network k from entry o of the record on; returns the entry behind them
+  int layout(const LearnNets& ns, int k, int o) { return learn_layout(ns.net[k]->layers, ns.net[k]->sizes, o, off_w[k], off_b[k]); }
+  // the record of P entries, its gradient, moments (zero) and the zero bias of the reversed networks; d_dbl with ndbl zeros
+  int alloc_record(size_t ndbl);
+  // the flat record of what is installed: the networks' packed operands read back from the device; every other entry 0
+  int read_installed(const LearnNets& ns, std::vector<float>& flat) const;
+  // the flat record to the device: the master copy and every operand the kernels read (forward: only with `forward`; the packed
+  // transposes always).  The stream is idle.
+  int write_params(const LearnNets& ns, const float* flat, bool forward);
+  // room for `need` floats of scratch and nchunk chunk partials (a call still in flight uses the buffers that are replaced: the
+  // stream is synchronised before they grow)
+  int reserve_scratch(size_t need, int nchunk, hipStream_t st);
+  // count == P entries of a device record to the host, behind whatever is in flight on the batch's stream; HB_EINVAL: no learner, or another count
+  int download(hb_batch* b, const float* dev, float* out, long long count) const;
+  // the record and the moments, P entries each (get: behind whatever is in flight; set_moments: the stream is idle)
+  int get_record(hb_batch* b, float* params, float* m, float* v) const;
+  int set_moments(const float* m, const float* v);
+};
+
+// The PPO learner of a batch (hb_learner_*, hb_api_ppo.cpp): the record is the actor's layers, log_std, the critic's layers
+// (include/hb.h); layer 0 needs no transpose.
+struct Learner : LearnerCore {
+  hb_ppo_config cfg = {};
+  int off_log_std = 0;
+  long long calls = 0;         // Adam calls since t was last set; t = calls - the device's count of skipped steps
+  bool log_std_dirty = false;  // the device's log_std is newer than actor_cfg.log_std
+  DevBuf<int> d_nskip;         // (d_dbl: advpart [64][2] | statpart [64][8] | normpart)
+  void clear() {
+    LearnerCore::clear();
+    calls = 0; log_std_dirty = false;
     d_nskip.reset();
-    for (int k = 0; k < 2; k++) for (int l = 0; l < 4; l++) d_wt[k][l].reset();
   }
 };
 
-// The SAC learner of a batch (hb_sac_*, hb_api_sac.cpp): the trainable parameters as ONE flat record (include/hb.h: the actor's layers
-// W | b, Q1's, Q2's, log_ent_coef), the gradient and the Adam moments in the same layout, the targets (their record, Q1' then Q2', and the
-// packed operands their forward pass reads), the packed transposes of the backward pass (wt[net][0] of a Q network: the transpose of
-// layer 0's action rows), and the scratch of a minibatch.  The forward operands of the live networks stay where they are: in the batch's
-// actor and q[0], q[1] (DevMlp), which hb_sac_adam_kernel refreshes entry by entry.
-struct SacLearner {
-  bool on = false;
+// The SAC learner of a batch (hb_sac_*, hb_api_sac.cpp): the record is the actor's layers, Q1's, Q2's, log_ent_coef (include/hb.h);
+// the targets (their record, Q1' then Q2', and the packed operands their forward pass reads); wt[net][0] of a Q network is the
+// transpose of layer 0's action rows.
+struct SacLearner : LearnerCore {
   hb_sac_config cfg = {};
-  int P = 0, PT = 0, off_q = 0;   // off_q: where Q1's stretch begins; the targets' record mirrors [off_q, P - 1)
-  int off_w[3][4] = {}, off_b[3][4] = {};
+  int PT = 0, off_q = 0;       // off_q: where Q1's stretch begins; the targets' record mirrors [off_q, P - 1)
   long long t = 0;
   DevMlp tq[2];
-  DevBuf<float> d_param, d_grad, d_m, d_v, d_target, d_zero, d_alpha, d_wt[3][4];
-  DevBuf<float> d_scratch;     // activations, dZ, outputs and the by-row terms of a minibatch: grows with mb
-  DevBuf<float> d_part;        // [64][P] chunk partials of the gradient
-  DevBuf<double> d_dbl;        // statpart [64][kSacSrow]
+  DevBuf<float> d_target, d_alpha;  // (d_dbl: statpart [64][kSacSrow])
   void clear() {
-    on = false; P = PT = off_q = 0; t = 0;
+    LearnerCore::clear();
+    PT = off_q = 0; t = 0;
     tq[0].clear(); tq[1].clear();
-    reset_all(d_param, d_grad, d_m, d_v, d_target, d_zero, d_alpha, d_scratch, d_part);
-    d_dbl.reset();
-    for (int k = 0; k < 3; k++) for (int l = 0; l < 4; l++) d_wt[k][l].reset();
+    reset_all(d_target, d_alpha);
   }
 };
 
@@ -399,5 +426,7 @@ int learner_sync_log_std(hb_batch* b);
 int learner_net_replaced(hb_batch* b, int net, bool shapes_same);
 // behind a change of the actor's or the critic's hidden activation: the learner is destroyed, the actor keeps the log_std it trained
 int learner_activation_changed(hb_batch* b);
+// both learners (hb_learn_host.cpp): the batch's device current and nothing in flight on its stream
+int learner_idle(hb_batch* b);
 }  // namespace hb
 #pragma GCC visibility pop

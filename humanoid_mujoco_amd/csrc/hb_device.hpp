@@ -313,9 +313,8 @@ struct NormDesc {
 // are merged in chunk order: 64 rows up to 4096, beyond that mb / 64 rounded up to whole 16-row tiles (never more than 64 chunks, which
 // bounds the partial gradients at 64 P floats).  The gradient norm goes over chunks of kPpoNormChunk entries of the flat record.
 constexpr int kPpoNormChunk = 4096;
-constexpr int kPpoMaxSeg = 17;  // tensors of the flat record: 2 x 4 x (W, b) + log_std
 __host__ __device__ inline int ppo_row_chunk(int mb) { return mb <= 4096 ? 64 : ((mb + 63) / 64 + 15) / 16 * 16; }
-// LDS row stride of a 16-row operand tile of hb_ppo_wgrad_kernel: whole 16-column tiles, and 16 mod 32 so that the four rows a wave
+// LDS row stride of a 16-row operand tile of the wgrad kernels (learn_wgrad_chunk): whole 16-column tiles, and 16 mod 32 so that the four rows a wave
 // reads in one MFMA operand fall on different banks
 __host__ __device__ inline int ppo_ld(int w) { const int p = (w + 15) / 16 * 16; return p % 32 == 0 ? p + 16 : p; }
 struct PpoNet {
@@ -342,14 +341,34 @@ struct PpoDesc {
   float* grad;         // [P]
   float* stats;        // [16] or null
 };
-struct PpoSeg {
-  int start, K, N;     // flat offset; W[K][N], or K = 0: a vector of N
-  float* dst;          // W: the packed B operand of the forward pass; vector: its copy (null: none)
-  float* dst_t;        // W: the packed B operand of W^T (null: layer 0, which needs none)
+// Both learners (hb_ppo.hip, hb_sac.hip; their shared kernel bodies: hb_learn_core.hpp).  A tensor of a flat parameter record and the
+// packed operands that follow it: whoever writes entry i of the record - Adam, the Polyak step - passes the value to learn_refresh.
+constexpr int kLearnMaxSeg = 17;  // tensors one Adam or Polyak launch covers: 2 x 4 x (W, b) + log_std or log_ent_coef
+struct ParamSeg {
+  int start, K, N, k0;   // flat offset; W[K][N], or K = 0: a vector of N; rows k >= k0 have an entry in dst_t, at row k - k0
+  float* dst;            // W: the packed B operand of the forward pass; vector: its copy (null: none)
+  float* dst_t;          // W: the packed B operand of the transpose of rows k0 .. (null: none)
 };
+// where W[k][n] of W[K][N] stands in its packed B operand (DevMlp::pack_mfma_b)
+__host__ __device__ inline size_t packed_b_index(int k, int n, int K) { return ((size_t)(n >> 4) * ((K + 3) / 4) + (k >> 2)) * 64 + (k & 3) * 16 + (n & 15); }
+// entry i of the record took the value pf: the segment it belongs to (seg[0 .. nseg) by ascending start, seg[0].start <= i), and its
+// copy into the packed operands.  Pad entries of those are never written, so they stay zero.
+__host__ __device__ inline void learn_refresh(const ParamSeg* seg, int nseg, int i, float pf) {
+  int sgi = 0;
+  while (sgi + 1 < nseg && i >= seg[sgi + 1].start) sgi++;
+  const ParamSeg& sg = seg[sgi];
+  const int j = i - sg.start;
+  if (sg.K == 0) {
+    if (sg.dst) sg.dst[j] = pf;
+    return;
+  }
+  const int k = j / sg.N, n = j - k * sg.N;
+  if (sg.dst) sg.dst[packed_b_index(k, n, sg.K)] = pf;
+  if (sg.dst_t && k >= sg.k0) sg.dst_t[packed_b_index(n, k - sg.k0, sg.N)] = pf;
+}
 struct PpoAdamDesc {
   int P, nseg, nnorm;
-  PpoSeg seg[kPpoMaxSeg];
+  ParamSeg seg[kLearnMaxSeg];
   float *param, *m, *v;
   const float* grad;
   double* normpart;    // [nnorm]
@@ -361,9 +380,9 @@ struct PpoAdamDesc {
 
 // hb_sac_* (hb_sac.hip): the SAC learner.  The launches of one gradient step are described job by job: a forward pass, a reversed
 // (back-propagating) pass and a dW pass each run a list of jobs side by side (grid y), so the same three kernels serve the actor, the two
-// Q networks and the two targets.  Row reductions go over the PPO learner's chunks (ppo_row_chunk).
+// Q networks and the two targets.  Row reductions go over the PPO learner's chunks (ppo_row_chunk); the Adam and Polyak launches cover
+// ParamSeg segments (above), as the PPO learner's Adam launch does.
 constexpr unsigned RS_SAC_PI = 33, RS_SAC_NEXT = 34;  // random-number streams of eps_pi and eps_next (RS_ACTOR is 32)
-constexpr int kSacMaxSeg = 17;   // tensors one Adam or Polyak launch covers: 2 x 4 x (W, b) + log_ent_coef
 constexpr int kSacSrow = 8;      // by-row terms of a phase
 struct SacFwdJob {
   PolicyDesc net;
@@ -434,14 +453,9 @@ struct SacReduceDesc {
   const double* statpart;
   float *grad, *stats;
 };
-struct SacSeg {
-  int start, K, N, k0;   // flat offset; W[K][N], or K = 0: a vector of N; rows k >= k0 have an entry in dst_t, at row k - k0
-  float* dst;            // W: the packed B operand of the forward pass; vector: its copy (null: none)
-  float* dst_t;          // W: the packed B operand of the transpose (null: none)
-};
 struct SacAdamDesc {
   int lo, hi, nseg, ent_index;   // entries [lo, hi); ent_index: log_ent_coef (its own learning rate), -1: not in this launch
-  SacSeg seg[kSacMaxSeg];
+  ParamSeg seg[kLearnMaxSeg];
   float *param, *m, *v;
   const float* grad;
   long long t;           // this step included
@@ -449,7 +463,7 @@ struct SacAdamDesc {
 };
 struct SacPolyakDesc {
   int n, nseg;
-  SacSeg seg[kSacMaxSeg];  // starts relative to the targets' record
+  ParamSeg seg[kLearnMaxSeg];  // starts relative to the targets' record
   const float* src;      // the live Q networks' stretch of the flat record
   float* target;
   float tau;

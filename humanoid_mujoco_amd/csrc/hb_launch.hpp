@@ -71,7 +71,9 @@ hipError_t launch_norm_moments(const NormDesc& d, hipStream_t stream);
 hipError_t launch_norm_apply(const NormDesc& d, hipStream_t stream);
 // the learner (hb_ppo.hip): the five launches of hb_ppo_grad_dev - forward with kept activations (and the advantage partials), the head
 // (loss terms and the top gradients by row), the back-propagation of dZ through the layers, the chunk partials of dW / db / dlog_std
-// and the statistics - and their merge; then the two of hb_ppo_adam_dev - the norm partials, and clipping + Adam + operand refresh
+// and the statistics - and their merge; then the two of hb_ppo_adam_dev - the norm partials, and clipping + Adam + operand refresh.
+// (What this learner's kernels and the SAC learner's do alike - the dW / db sweep, the merge of the partials, Adam's step, the refresh
+// over ParamSeg segments, at most kLearnMaxSeg a launch - is hb_learn_core.hpp's and hb_device.hpp's learn_refresh.)
 hipError_t launch_ppo_grad(const PpoDesc& d, hipStream_t stream);
 hipError_t launch_ppo_adam(const PpoAdamDesc& d, hipStream_t stream);
 // the SAC learner (hb_sac.hip), one launch each: njob forward passes side by side; the head by row (what: 0 the two samples and their

@@ -18,14 +18,13 @@
 // them in order, then clipping, Adam and the refresh of the packed operands, one lane per entry).
 // All matrix products are v_mfma_f32_16x16x4_f32 (exact f32).  No atomics, no cross-block communication inside a launch: every
 // reduction has an order fixed by (mb, sizes) alone (hb_device.hpp: ppo_row_chunk), so the same inputs give the same bits.
+// What this learner's kernels and the SAC learner's (hb_sac.hip) do alike is one piece of code: the row gather, the dW / db sweep, the
+// merge of the partials and Adam's step in hb_learn_core.hpp, the refresh of the packed operands in hb_device.hpp (learn_refresh).
 #include <hip/hip_runtime.h>
-#include "hb_kcommon.hpp"
+#include "hb_learn_core.hpp"
 #include "hb_launch.hpp"
 
 namespace hb {
-
-// minibatch row r of the tapes
-__device__ __forceinline__ long long ppo_src_row(const PpoDesc& d, int r) { return d.index ? (long long)d.index[r] : d.first + r; }
 
 // the moments of the minibatch's advantages from the chunk partials, merged in chunk order (fp64): mean, unbiased std (0 for mb = 1)
 __device__ __forceinline__ void ppo_adv_moments(const PpoDesc& d, double& mean, double& sd) {
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(256) void hb_ppo_head_kernel(const PpoDesc d) {
   __syncthreads();
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= d.mb) return;
-  const long long src = ppo_src_row(d, r);
+  const long long src = learn_src_row(d.index, d.first, r);
   const int nu = d.nu;
   const float half_log_2pi = 0.91893853320467274178f;
   const float* ls = d.param + d.off_log_std;
@@ -89,12 +88,11 @@ __global__ __launch_bounds__(256) void hb_ppo_head_kernel(const PpoDesc d) {
   sr[4] = ratio;
 }
 
-// dW = A^T dZ over one chunk of rows: the A operand of the MFMA is A^T (row i = input column, k = minibatch row), the B operand dZ
-// (k = minibatch row, column = output column), both read from 16-row LDS tiles.  Wave w owns the output tiles (kt, nt), kt = w and w + 8,
-// nt = 0 .. 15: 32 accumulators, which cover the widest layer (256 x 256).  db: lane n adds column n of every dZ tile in row order.
+// dW = A^T dZ and db over one chunk of rows (learn_wgrad_chunk), one layer of one network per blockIdx.y; the block behind the layers
+// sums what only this learner has
 __global__ __launch_bounds__(512) void hb_ppo_wgrad_kernel(const PpoDesc d) {
   __shared__ float sA[16 * 272], sZ[16 * 272];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int c = blockIdx.x;
   const int r0 = c * d.chunk, r1 = min(d.mb, r0 + d.chunk);
   float* out = d.part + (size_t)c * d.P;
@@ -116,68 +114,7 @@ __global__ __launch_bounds__(512) void hb_ppo_wgrad_kernel(const PpoDesc d) {
   }
   const PpoNet& nw = d.net[y < La ? 0 : 1];
   const int l = y < La ? y : y - La;
-  const int K = nw.fwd.sizes[l], N = nw.fwd.sizes[l + 1];
-  const int Kp = (K + 15) / 16 * 16, Np = (N + 15) / 16 * 16, lda = ppo_ld(K), ldz = ppo_ld(N);
-  const int ktiles = Kp / 16, ntiles = Np / 16;
-  const float* A = nw.act[l];
-  const float* Z = nw.dz[l];
-  const int col = lane & 15, quad = lane >> 4;
-  f32x4 acc[2][16];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 16; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float bsum = 0.f;
-  for (int t0 = r0; t0 < r1; t0 += 16) {
-    for (int idx = tid; idx < 16 * Kp; idx += 512) {
-      const int row = idx / Kp, k = idx - row * Kp;
-      sA[row * lda + k] = (t0 + row < r1 && k < K) ? A[(size_t)(t0 + row) * K + k] : 0.f;
-    }
-    for (int idx = tid; idx < 16 * Np; idx += 512) {
-      const int row = idx / Np, n = idx - row * Np;
-      sZ[row * ldz + n] = (t0 + row < r1 && n < N) ? Z[(size_t)(t0 + row) * N + n] : 0.f;
-    }
-    __syncthreads();
-    if (wave < ktiles) {
-      const bool two = wave + 8 < ktiles;
-      for (int s = 0; s < 4; s++) {
-        const float a0 = sA[(4 * s + quad) * lda + wave * 16 + col];
-        const float a1 = two ? sA[(4 * s + quad) * lda + (wave + 8) * 16 + col] : 0.f;
-        const float* zp = sZ + (4 * s + quad) * ldz + col;
-#pragma unroll
-        for (int nt = 0; nt < 16; nt++) {
-          if (nt < ntiles) {
-            const float z = zp[nt * 16];
-            acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, z, acc[0][nt], 0, 0, 0);
-            if (two) acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, z, acc[1][nt], 0, 0, 0);
-          }
-        }
-      }
-    }
-    if (tid < N) {
-      for (int row = 0; row < 16; row++) bsum += sZ[row * ldz + tid];
-    }
-    __syncthreads();
-  }
-  float* gw = out + nw.off_w[l];
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const int kt = wave + 8 * i;
-    if (kt < ktiles) {
-#pragma unroll
-      for (int nt = 0; nt < 16; nt++) {
-        if (nt < ntiles) {
-          const int n = nt * 16 + col;
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const int k = kt * 16 + 4 * quad + r;
-            if (k < K && n < N) gw[(size_t)k * N + n] = acc[i][nt][r];
-          }
-        }
-      }
-    }
-  }
-  if (tid < N) out[nw.off_b[l] + tid] = bsum;
+  learn_wgrad_chunk(nw.act[l], nw.dz[l], nw.fwd.sizes[l], nw.fwd.sizes[l + 1], r0, r1, out + nw.off_w[l], out + nw.off_b[l], sA, sZ);
 }
 
 __global__ __launch_bounds__(256) void hb_ppo_reduce_kernel(const PpoDesc d) {
@@ -201,8 +138,7 @@ __global__ __launch_bounds__(256) void hb_ppo_reduce_kernel(const PpoDesc d) {
   }
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= d.P) return;
-  float g = 0.f;
-  for (int c = 0; c < d.nchunk; c++) g += d.part[(size_t)c * d.P + i];
+  float g = learn_partials_sum(d.part, d.P, d.nchunk, i);
   if (i >= d.off_log_std && i < d.off_log_std + d.nu) g -= d.ent_coef;  // the entropy bonus
   d.grad[i] = g;
 }
@@ -224,9 +160,9 @@ __global__ __launch_bounds__(256) void hb_ppo_norm_kernel(const PpoAdamDesc d) {
   }
 }
 
-// One lane per entry of the flat record.  Every block forms the same norm (the partials in order); the step itself is fp64 on the fp32
-// gradient, moments and parameter, each result rounded to fp32 once.  A W entry is also written to its place in the packed B operand of
-// the forward kernels and in the packed transpose; pad entries of either are never written, so they stay zero.
+// One lane per entry of the flat record.  Every block forms the same norm (the partials in order); the step on the clipped gradient is
+// learn_adam_entry's.  A W entry is also written to its place in the packed B operand of the forward kernels and in the packed
+// transpose (learn_refresh).
 __global__ __launch_bounds__(256) void hb_ppo_adam_kernel(const PpoAdamDesc d) {
   __shared__ double gsh;
   if (threadIdx.x == 0) {
@@ -250,24 +186,7 @@ __global__ __launch_bounds__(256) void hb_ppo_adam_kernel(const PpoAdamDesc d) {
   const double t = (double)(d.calls - (long long)d.nskip[0]);
   const double scale = d.max_grad_norm > 0.f ? fmin(1.0, (double)d.max_grad_norm / (gn + 1e-6)) : 1.0;
   const double g = (double)d.grad[i] * scale;
-  const double b1 = (double)d.beta1, b2 = (double)d.beta2;
-  const double m = b1 * (double)d.m[i] + (1.0 - b1) * g;
-  const double v = b2 * (double)d.v[i] + (1.0 - b2) * g * g;
-  const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
-  const double p = (double)d.param[i] - (double)d.lr / bc1 * m / (sqrt(v) / sqrt(bc2) + (double)d.eps);
-  const float pf = (float)p;
-  d.m[i] = (float)m; d.v[i] = (float)v; d.param[i] = pf;
-  int sgi = 0;
-  while (sgi + 1 < d.nseg && i >= d.seg[sgi + 1].start) sgi++;
-  const PpoSeg& sg = d.seg[sgi];
-  const int j = i - sg.start;
-  if (sg.K == 0) {
-    if (sg.dst) sg.dst[j] = pf;
-  } else {
-    const int k = j / sg.N, n = j - k * sg.N;
-    sg.dst[((size_t)(n >> 4) * ((sg.K + 3) / 4) + (k >> 2)) * 64 + (k & 3) * 16 + (n & 15)] = pf;
-    if (sg.dst_t) sg.dst_t[((size_t)(k >> 4) * ((sg.N + 3) / 4) + (n >> 2)) * 64 + (n & 3) * 16 + (k & 15)] = pf;
-  }
+  learn_refresh(d.seg, d.nseg, i, learn_adam_entry(g, d.lr, t, d.beta1, d.beta2, d.eps, d.m, d.v, d.param, i));
 }
 
 hipError_t launch_ppo_grad(const PpoDesc& d, hipStream_t stream) {
@@ -292,7 +211,7 @@ hipError_t launch_ppo_grad(const PpoDesc& d, hipStream_t stream) {
 
 hipError_t launch_ppo_adam(const PpoAdamDesc& d, hipStream_t stream) {
   (void)hipGetLastError();
-  if (d.P < 1 || d.nseg < 1 || d.nseg > kPpoMaxSeg || d.nnorm != (d.P + kPpoNormChunk - 1) / kPpoNormChunk) return hipErrorInvalidValue;
+  if (d.P < 1 || d.nseg < 1 || d.nseg > kLearnMaxSeg || d.nnorm != (d.P + kPpoNormChunk - 1) / kPpoNormChunk) return hipErrorInvalidValue;
   hipLaunchKernelGGL(hb_ppo_norm_kernel, dim3(d.nnorm), dim3(256), 0, stream, d);
   hipLaunchKernelGGL(hb_ppo_adam_kernel, dim3((d.P + 255) / 256), dim3(256), 0, stream, d);
   return hipGetLastError();

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(512) void HB_PPO_FORWARD_KERNEL(const PpoDesc d) {
     const int r1 = min(d.mb, (c + 1) * d.chunk);
     double s = 0.0, q = 0.0;
     for (int r = c * d.chunk + tid; r < r1; r += 512) {
-      const double a = (double)d.advantage[ppo_src_row(d, r)];
+      const double a = (double)d.advantage[learn_src_row(d.index, d.first, r)];
       s += a; q += a * a;
     }
     red[tid] = s; red[512 + tid] = q;
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(512) void HB_PPO_FORWARD_KERNEL(const PpoDesc d) {
       const int row = idx / nobs, c = idx - row * nobs;
       float x = 0.f;
       if (row < live) {
-        x = d.obs[(size_t)ppo_src_row(d, m0 + row) * nobs + c];
+        x = d.obs[(size_t)learn_src_row(d.index, d.first, m0 + row) * nobs + c];
         if (blockIdx.y == 0) nw.act[0][(size_t)(m0 + row) * nobs + c] = x;
       }
       cur[row * ldx + c] = x;

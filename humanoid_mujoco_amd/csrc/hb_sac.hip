@@ -3,7 +3,8 @@
 // kernel compiles differently for it.  The design is hb_ppo.hip's - 16 gathered rows per block through hb_mlp_layers.inl, activations and
 // dZ in a learner-owned scratch [mb][width], the reversed network for dA = dZ W^T, 32 accumulator tiles per wave for dW = A^T dZ over a
 // chunk of rows, chunk partials merged in order - with the launches described job by job (hb_device.hpp: Sac*Desc), so that three
-// kernels serve five networks.
+// kernels serve five networks.  What the two learners' kernels do alike is one piece of code: the row gather, the dW / db sweep, the
+// merge of the partials and Adam's step in hb_learn_core.hpp, the refresh of the packed operands in hb_device.hpp (learn_refresh).
 //
 // hb_sac_step_dev is SIXTEEN launches whatever the minibatch size (fifteen on a step the target update interval skips):
 //   1. hb_sac_forward_kernel   grid (tiles, 4): the actor on obs (activations kept) and on next_obs (nothing kept), Q1 and Q2 on
@@ -26,13 +27,10 @@
 // All matrix products are v_mfma_f32_16x16x4_f32 (exact f32).  No atomics, no cross-block communication inside a launch: every reduction
 // has an order fixed by (mb, sizes) alone, so the same inputs give the same bits.
 #include <hip/hip_runtime.h>
-#include "hb_kcommon.hpp"
+#include "hb_learn_core.hpp"
 #include "hb_launch.hpp"
 
 namespace hb {
-
-// minibatch row r of the tapes
-__device__ __forceinline__ long long sac_src_row(const int* index, long long first, int r) { return index ? (long long)index[r] : first + r; }
 
 // hb_sac_forward_kernel, hb_sac_backprop_kernel and their twins for launches with a job whose network is not tanh
 #define HB_ACT_ANY 0
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(256) void hb_sac_sample_kernel(const SacHeadDesc d)
 __global__ __launch_bounds__(256) void hb_sac_critic_head_kernel(const SacHeadDesc d) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= d.mb) return;
-  const long long src = sac_src_row(d.index, d.first, r);
+  const long long src = learn_src_row(d.index, d.first, r);
   const float alpha = d.alpha[0];
   const float tq = __fmaf_rn(-alpha, d.lp_nx[r], fminf(d.qt[0][r], d.qt[1][r]));
   const float rew = d.reward[src];
@@ -124,12 +122,10 @@ __global__ __launch_bounds__(256) void hb_sac_actor_head_kernel(const SacHeadDes
   sr[1] = mq;
 }
 
-// hb_ppo_wgrad_kernel's design over a list of jobs: dW = A^T dZ over one chunk of rows, the A operand of the MFMA being A^T (row i =
-// input column, k = minibatch row), the B operand dZ, both from 16-row LDS tiles.  Wave w owns the output tiles (kt, nt), kt = w and
-// w + 8, nt = 0 .. 15: 32 accumulators, which cover the widest layer (256 x 256).  db: lane n adds column n of every dZ tile in row order.
+// dW = A^T dZ and db over one chunk of rows (learn_wgrad_chunk), one job per blockIdx.y; the block behind the jobs sums the by-row terms
 __global__ __launch_bounds__(512) void hb_sac_wgrad_kernel(const SacWgDesc d) {
   __shared__ float sA[16 * 272], sZ[16 * 272];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int c = blockIdx.x;
   const int r0 = c * d.chunk, r1 = min(d.mb, r0 + d.chunk);
   float* out = d.part + (size_t)c * d.P;
@@ -143,68 +139,7 @@ __global__ __launch_bounds__(512) void hb_sac_wgrad_kernel(const SacWgDesc d) {
     return;
   }
   const SacWgJob& jb = d.job[blockIdx.y];
-  const int K = jb.K, N = jb.N;
-  const int Kp = (K + 15) / 16 * 16, Np = (N + 15) / 16 * 16, lda = ppo_ld(K), ldz = ppo_ld(N);
-  const int ktiles = Kp / 16, ntiles = Np / 16;
-  const float* A = jb.A;
-  const float* Z = jb.Z;
-  const int col = lane & 15, quad = lane >> 4;
-  f32x4 acc[2][16];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 16; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float bsum = 0.f;
-  for (int t0 = r0; t0 < r1; t0 += 16) {
-    for (int idx = tid; idx < 16 * Kp; idx += 512) {
-      const int row = idx / Kp, k = idx - row * Kp;
-      sA[row * lda + k] = (t0 + row < r1 && k < K) ? A[(size_t)(t0 + row) * K + k] : 0.f;
-    }
-    for (int idx = tid; idx < 16 * Np; idx += 512) {
-      const int row = idx / Np, n = idx - row * Np;
-      sZ[row * ldz + n] = (t0 + row < r1 && n < N) ? Z[(size_t)(t0 + row) * N + n] : 0.f;
-    }
-    __syncthreads();
-    if (wave < ktiles) {
-      const bool two = wave + 8 < ktiles;
-      for (int s = 0; s < 4; s++) {
-        const float a0 = sA[(4 * s + quad) * lda + wave * 16 + col];
-        const float a1 = two ? sA[(4 * s + quad) * lda + (wave + 8) * 16 + col] : 0.f;
-        const float* zp = sZ + (4 * s + quad) * ldz + col;
-#pragma unroll
-        for (int nt = 0; nt < 16; nt++) {
-          if (nt < ntiles) {
-            const float z = zp[nt * 16];
-            acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, z, acc[0][nt], 0, 0, 0);
-            if (two) acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, z, acc[1][nt], 0, 0, 0);
-          }
-        }
-      }
-    }
-    if (tid < N) {
-      for (int row = 0; row < 16; row++) bsum += sZ[row * ldz + tid];
-    }
-    __syncthreads();
-  }
-  float* gw = out + jb.off_w;
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const int kt = wave + 8 * i;
-    if (kt < ktiles) {
-#pragma unroll
-      for (int nt = 0; nt < 16; nt++) {
-        if (nt < ntiles) {
-          const int n = nt * 16 + col;
-#pragma unroll
-          for (int r = 0; r < 4; r++) {
-            const int k = kt * 16 + 4 * quad + r;
-            if (k < K && n < N) gw[(size_t)k * N + n] = acc[i][nt][r];
-          }
-        }
-      }
-    }
-  }
-  if (tid < N) out[jb.off_b + tid] = bsum;
+  learn_wgrad_chunk(jb.A, jb.Z, jb.K, jb.N, r0, r1, out + jb.off_w, out + jb.off_b, sA, sZ);
 }
 
 // One lane per entry of [lo, hi): the chunk partials summed in chunk order.  One more block merges the by-row terms (fp64 sums in chunk
@@ -236,43 +171,15 @@ __global__ __launch_bounds__(256) void hb_sac_reduce_kernel(const SacReduceDesc 
   }
   const int i = d.lo + blockIdx.x * 256 + threadIdx.x;
   if (i >= d.hi) return;
-  float g = 0.f;
-  for (int c = 0; c < d.nchunk; c++) g += d.part[(size_t)c * d.P + i];
-  d.grad[i] = g;
+  d.grad[i] = learn_partials_sum(d.part, d.P, d.nchunk, i);
 }
 
-// where entry j of a segment stands in the packed operands (DevMlp::pack_mfma_b of W and of the transpose of its rows k0 ..)
-__device__ __forceinline__ void sac_refresh(const SacSeg& sg, int j, float pf) {
-  if (sg.K == 0) {
-    if (sg.dst) sg.dst[j] = pf;
-    return;
-  }
-  const int k = j / sg.N, n = j - k * sg.N;
-  if (sg.dst) sg.dst[((size_t)(n >> 4) * ((sg.K + 3) / 4) + (k >> 2)) * 64 + (k & 3) * 16 + (n & 15)] = pf;
-  if (sg.dst_t && k >= sg.k0) {
-    const int kt = k - sg.k0;
-    sg.dst_t[((size_t)(kt >> 4) * ((sg.N + 3) / 4) + (n >> 2)) * 64 + (n & 3) * 16 + (kt & 15)] = pf;
-  }
-}
-
-// torch.optim.Adam, one lane per entry of [lo, hi): fp64 on the fp32 gradient, moments and parameter, each result rounded to fp32 once.
-// Pad entries of the packed operands are never written, so they stay zero.
+// torch.optim.Adam, one lane per entry of [lo, hi) (learn_adam_entry), with the refresh of the packed operands (learn_refresh)
 __global__ __launch_bounds__(256) void hb_sac_adam_kernel(const SacAdamDesc d) {
   const int i = d.lo + blockIdx.x * 256 + threadIdx.x;
   if (i >= d.hi) return;
-  const double t = (double)d.t;
-  const double g = (double)d.grad[i];
-  const double b1 = (double)d.beta1, b2 = (double)d.beta2;
-  const double m = b1 * (double)d.m[i] + (1.0 - b1) * g;
-  const double v = b2 * (double)d.v[i] + (1.0 - b2) * g * g;
-  const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
-  const double lr = i == d.ent_index ? (double)d.lr_ent : (double)d.lr;
-  const double p = (double)d.param[i] - lr / bc1 * m / (sqrt(v) / sqrt(bc2) + (double)d.eps);
-  const float pf = (float)p;
-  d.m[i] = (float)m; d.v[i] = (float)v; d.param[i] = pf;
-  int sgi = 0;
-  while (sgi + 1 < d.nseg && i >= d.seg[sgi + 1].start) sgi++;
-  sac_refresh(d.seg[sgi], i - d.seg[sgi].start, pf);
+  const float& lr = i == d.ent_index ? d.lr_ent : d.lr;
+  learn_refresh(d.seg, d.nseg, i, learn_adam_entry((double)d.grad[i], lr, (double)d.t, d.beta1, d.beta2, d.eps, d.m, d.v, d.param, i));
 }
 
 // Q' = tau Q + (1 - tau) Q' in fp64, rounded once, one lane per entry of the targets' record
@@ -282,9 +189,7 @@ __global__ __launch_bounds__(256) void hb_sac_polyak_kernel(const SacPolyakDesc 
   const double tau = (double)d.tau;
   const float pf = (float)(tau * (double)d.src[i] + (1.0 - tau) * (double)d.target[i]);
   d.target[i] = pf;
-  int sgi = 0;
-  while (sgi + 1 < d.nseg && i >= d.seg[sgi + 1].start) sgi++;
-  sac_refresh(d.seg[sgi], i - d.seg[sgi].start, pf);
+  learn_refresh(d.seg, d.nseg, i, pf);
 }
 
 static size_t sac_shmem(int ldx) { return ((size_t)32 * ldx + 8 * 256) * sizeof(float); }  // two activation tiles + the split-K partial tiles
@@ -356,14 +261,14 @@ hipError_t launch_sac_reduce(const SacReduceDesc& d, hipStream_t stream) {
 
 hipError_t launch_sac_adam(const SacAdamDesc& d, hipStream_t stream) {
   (void)hipGetLastError();
-  if (d.lo < 0 || d.hi <= d.lo || d.nseg < 1 || d.nseg > kSacMaxSeg || d.seg[0].start != d.lo || d.t < 1) return hipErrorInvalidValue;
+  if (d.lo < 0 || d.hi <= d.lo || d.nseg < 1 || d.nseg > kLearnMaxSeg || d.seg[0].start != d.lo || d.t < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(hb_sac_adam_kernel, dim3((d.hi - d.lo + 255) / 256), dim3(256), 0, stream, d);
   return hipGetLastError();
 }
 
 hipError_t launch_sac_polyak(const SacPolyakDesc& d, hipStream_t stream) {
   (void)hipGetLastError();
-  if (d.n < 1 || d.nseg < 1 || d.nseg > kSacMaxSeg || d.seg[0].start != 0) return hipErrorInvalidValue;
+  if (d.n < 1 || d.nseg < 1 || d.nseg > kLearnMaxSeg || d.seg[0].start != 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(hb_sac_polyak_kernel, dim3((d.n + 255) / 256), dim3(256), 0, stream, d);
   return hipGetLastError();
 }

@@ -32,8 +32,8 @@ __global__ __launch_bounds__(512) void HB_SAC_FORWARD_KERNEL(const SacFwdDesc d)
       float x = 0.f;
       if (row < live) {
         const int r = m0 + row;
-        if (c < n0) x = jb.x0[(size_t)(jb.gather0 ? sac_src_row(d.index, d.first, r) : (long long)r) * n0 + c];
-        else x = jb.x1[(size_t)(jb.gather1 ? sac_src_row(d.index, d.first, r) : (long long)r) * n1 + (c - n0)];
+        if (c < n0) x = jb.x0[(size_t)(jb.gather0 ? learn_src_row(d.index, d.first, r) : (long long)r) * n0 + c];
+        else x = jb.x1[(size_t)(jb.gather1 ? learn_src_row(d.index, d.first, r) : (long long)r) * n1 + (c - n0)];
         if (jb.in_store) jb.in_store[(size_t)r * nin + c] = x;
       }
       cur[row * ldx + c] = x;
