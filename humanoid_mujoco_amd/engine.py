@@ -198,24 +198,23 @@ PPO_STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "
              "skipped")
 
 
-def ppo_flat_shapes(actor_sizes, critic_sizes, nu):
-    """The tensors of the learner's flat record in order, as (name, shape): the actor's layers W [K, N] | b [N], log_std [nu], the critic's
-    layers (include/hb.h: hb_learner_get_params)."""
+def _flat_shapes(nets, tail):
+    """(name, shape) of a flat record's tensors in order: for every (tag, sizes) of nets the layers W [K, N] | b [N], and behind the
+    network it names the one tensor of tail = (tag, name, shape)."""
     out = []
-    for tag, sizes in (("actor", actor_sizes), ("critic", critic_sizes)):
+    for tag, sizes in nets:
         for l in range(len(sizes) - 1):
             out += [("%s.w%d" % (tag, l), (int(sizes[l]), int(sizes[l + 1]))), ("%s.b%d" % (tag, l), (int(sizes[l + 1]),))]
-        if tag == "actor":
-            out.append(("log_std", (int(nu),)))
+        if tag == tail[0]:
+            out.append(tail[1:])
     return out
 
 
-def ppo_split(flat, actor_sizes, critic_sizes, nu):
-    """The flat record as a dict of per-tensor arrays (copies): actor.w0, actor.b0, ..., log_std, critic.w0, ..."""
+def _split(what, flat, shapes):
     flat = np.asarray(flat)
-    shapes = ppo_flat_shapes(actor_sizes, critic_sizes, nu)
-    if flat.shape != (sum(int(np.prod(sh)) for _, sh in shapes),):
-        raise ValueError("ppo_split: the record of these networks holds %d values" % sum(int(np.prod(sh)) for _, sh in shapes))
+    total = sum(int(np.prod(sh)) for _, sh in shapes)
+    if flat.shape != (total,):
+        raise ValueError("%s: the record of these networks holds %d values" % (what, total))
     out, o = {}, 0
     for name, sh in shapes:
         n = int(np.prod(sh))
@@ -224,15 +223,30 @@ def ppo_split(flat, actor_sizes, critic_sizes, nu):
     return out
 
 
-def ppo_join(tensors, actor_sizes, critic_sizes, nu, dtype=np.float32):
-    """The inverse of ppo_split."""
+def _join(what, tensors, shapes, dtype):
     parts = []
-    for name, sh in ppo_flat_shapes(actor_sizes, critic_sizes, nu):
+    for name, sh in shapes:
         a = np.asarray(tensors[name], dtype=dtype)
         if a.shape != sh:
-            raise ValueError("ppo_join: %s must be %s" % (name, sh))
+            raise ValueError("%s: %s must be %s" % (what, name, sh))
         parts.append(a.ravel())
     return np.concatenate(parts)
+
+
+def ppo_flat_shapes(actor_sizes, critic_sizes, nu):
+    """The tensors of the learner's flat record in order, as (name, shape): the actor's layers W [K, N] | b [N], log_std [nu], the critic's
+    layers (include/hb.h: hb_learner_get_params)."""
+    return _flat_shapes((("actor", actor_sizes), ("critic", critic_sizes)), ("actor", "log_std", (int(nu),)))
+
+
+def ppo_split(flat, actor_sizes, critic_sizes, nu):
+    """The flat record as a dict of per-tensor arrays (copies): actor.w0, actor.b0, ..., log_std, critic.w0, ..."""
+    return _split("ppo_split", flat, ppo_flat_shapes(actor_sizes, critic_sizes, nu))
+
+
+def ppo_join(tensors, actor_sizes, critic_sizes, nu, dtype=np.float32):
+    """The inverse of ppo_split."""
+    return _join("ppo_join", tensors, ppo_flat_shapes(actor_sizes, critic_sizes, nu), dtype)
 
 
 def ppo_row_chunk(mb):
@@ -261,37 +275,17 @@ SAC_STATS = ("actor_loss", "critic_loss", "ent_coef_loss", "ent_coef", "lp_pi", 
 def sac_flat_shapes(actor_sizes, q_sizes):
     """The tensors of the SAC learner's flat record in order, as (name, shape): the actor's layers W [K, N] | b [N], Q1's, Q2's,
     log_ent_coef [1] (include/hb.h: hb_sac_get_params).  The targets' record mirrors the q1.*, q2.* stretch."""
-    out = []
-    for tag, sizes in (("actor", actor_sizes), ("q1", q_sizes), ("q2", q_sizes)):
-        for l in range(len(sizes) - 1):
-            out += [("%s.w%d" % (tag, l), (int(sizes[l]), int(sizes[l + 1]))), ("%s.b%d" % (tag, l), (int(sizes[l + 1]),))]
-    out.append(("log_ent_coef", (1,)))
-    return out
+    return _flat_shapes((("actor", actor_sizes), ("q1", q_sizes), ("q2", q_sizes)), ("q2", "log_ent_coef", (1,)))
 
 
 def sac_split(flat, actor_sizes, q_sizes):
     """The flat record as a dict of per-tensor arrays (copies): actor.w0, actor.b0, ..., q1.w0, ..., q2.w0, ..., log_ent_coef."""
-    flat = np.asarray(flat)
-    shapes = sac_flat_shapes(actor_sizes, q_sizes)
-    if flat.shape != (sum(int(np.prod(sh)) for _, sh in shapes),):
-        raise ValueError("sac_split: the record of these networks holds %d values" % sum(int(np.prod(sh)) for _, sh in shapes))
-    out, o = {}, 0
-    for name, sh in shapes:
-        n = int(np.prod(sh))
-        out[name] = flat[o:o + n].reshape(sh).copy()
-        o += n
-    return out
+    return _split("sac_split", flat, sac_flat_shapes(actor_sizes, q_sizes))
 
 
 def sac_join(tensors, actor_sizes, q_sizes, dtype=np.float32):
     """The inverse of sac_split."""
-    parts = []
-    for name, sh in sac_flat_shapes(actor_sizes, q_sizes):
-        a = np.asarray(tensors[name], dtype=dtype)
-        if a.shape != sh:
-            raise ValueError("sac_join: %s must be %s" % (name, sh))
-        parts.append(a.ravel())
-    return np.concatenate(parts)
+    return _join("sac_join", tensors, sac_flat_shapes(actor_sizes, q_sizes), dtype)
 
 
 class HbError(RuntimeError):
@@ -1427,18 +1421,55 @@ class Batch:
     # ---- the PPO learner (include/hb.h: hb_learner_*, hb_ppo_*)
     _PPO_WHY = "needs a learner (learner_create), the five tapes, 1 <= mb, and first + mb <= n_rows without an index"
 
-    def _ppo_config(self, what, cfg, base=None):
-        c = HbPpoConfig()
+    @staticmethod
+    def _learn_config(struct, default_fn, what, cfg, base, convert):
+        """A learner's config struct: base's values, or the library's defaults (default_fn: the C function's name), and on top of them
+        cfg's, each set by convert(c, k, v)."""
+        c = struct()
         if base is not None:
             ctypes.memmove(ctypes.byref(c), ctypes.byref(base), ctypes.sizeof(c))
         else:
-            _check(lib().hb_ppo_default_config(ctypes.byref(c)), "hb_ppo_default_config")
-        names = dict(HbPpoConfig._fields_)
+            _check(getattr(lib(), default_fn)(ctypes.byref(c)), default_fn)
+        names = dict(struct._fields_)
         for k, v in cfg.items():
             if k not in names:
                 raise ValueError("%s: unknown hyper-parameter %r (one of %s)" % (what, k, ", ".join(names)))
-            setattr(c, k, int(bool(v)) if k == "normalize_advantage" else float(v))
+            convert(c, k, v)
         return c
+
+    # a learner's records (both keep them in LearnerCore): fn is the C function, name what _check calls it, why its refusal's text
+    def _learn_count(self, fn, name, why):
+        n = fn(self._h)
+        _check(0 if n >= 0 else int(n), name, why)
+        return int(n)
+
+    def _learn_download(self, n, fn, name):
+        out = np.zeros(n, dtype=np.float32)
+        _check(fn(self._h, _ptr(out), out.size), name)
+        return out
+
+    def _learn_upload(self, flat, fn, name, why):
+        a = np.ascontiguousarray(flat, dtype=np.float32)
+        _check(fn(self._h, _ptr(a), a.size if a.ndim == 1 else -1), name, why)
+
+    def _learn_get_state(self, n, fn, name, *more):
+        """(params, m, v, t); more: the arrays the C function fills behind the three records, each passed with its size"""
+        p, m, v = (np.zeros(n, dtype=np.float32) for _ in range(3))
+        t = ctypes.c_longlong()
+        _check(fn(self._h, _ptr(p), _ptr(m), _ptr(v), n, *[x for a in more for x in (_ptr(a), a.size)], ctypes.byref(t)), name)
+        return p, m, v, int(t.value)
+
+    def _learn_set_state(self, state, fn, name, why, *more):
+        """more: the keys of state the C function reads behind the three records"""
+        p, m, v, *rest = (np.ascontiguousarray(state[k], dtype=np.float32) for k in ("params", "m", "v") + more)
+        n = p.size if p.ndim == 1 and p.shape == m.shape == v.shape else -1
+        _check(fn(self._h, _ptr(p), _ptr(m), _ptr(v), n, *[x for a in rest for x in (_ptr(a), a.size if a.ndim == 1 else -1)], int(state["t"])),
+               name, why)
+
+    def _ppo_config(self, what, cfg, base=None):
+        def convert(c, k, v):
+            setattr(c, k, int(bool(v)) if k == "normalize_advantage" else float(v))
+        return self._learn_config(HbPpoConfig, "hb_ppo_default_config", what, cfg, base, convert)
 
     def learner_create(self, **cfg):
         """Creates the PPO learner over the installed actor (Gaussian head) and critic: they become the trainable parameters, with Adam
@@ -1462,39 +1493,26 @@ class Batch:
         _check(lib().hb_learner_destroy(self._h), "hb_learner_destroy", "no learner")
 
     def learner_param_count(self):
-        n = lib().hb_learner_param_count(self._h)
-        _check(0 if n >= 0 else int(n), "hb_learner_param_count", "no learner")
-        return int(n)
+        return self._learn_count(lib().hb_learner_param_count, "hb_learner_param_count", "no learner")
 
     def learner_params(self):
         """the parameters as the flat float32 record (ppo_split gives the per-layer arrays)"""
-        out = np.zeros(self.learner_param_count(), dtype=np.float32)
-        _check(lib().hb_learner_get_params(self._h, _ptr(out), out.size), "hb_learner_get_params")
-        return out
+        return self._learn_download(self.learner_param_count(), lib().hb_learner_get_params, "hb_learner_get_params")
 
     def learner_set_params(self, flat):
-        a = np.ascontiguousarray(flat, dtype=np.float32)
-        _check(lib().hb_learner_set_params(self._h, _ptr(a), a.size if a.ndim == 1 else -1), "hb_learner_set_params",
-               "needs a learner and a flat record of learner_param_count() values")
+        self._learn_upload(flat, lib().hb_learner_set_params, "hb_learner_set_params", "needs a learner and a flat record of learner_param_count() values")
 
     def learner_grads(self):
-        out = np.zeros(self.learner_param_count(), dtype=np.float32)
-        _check(lib().hb_learner_get_grads(self._h, _ptr(out), out.size), "hb_learner_get_grads")
-        return out
+        return self._learn_download(self.learner_param_count(), lib().hb_learner_get_grads, "hb_learner_get_grads")
 
     def learner_state(self):
         """{"params", "m", "v": flat float32 records, "t": Adam's step count}: checkpoint of the learner"""
-        n = self.learner_param_count()
-        p, m, v = (np.zeros(n, dtype=np.float32) for _ in range(3))
-        t = ctypes.c_longlong()
-        _check(lib().hb_learner_get_state(self._h, _ptr(p), _ptr(m), _ptr(v), n, ctypes.byref(t)), "hb_learner_get_state")
-        return {"params": p, "m": m, "v": v, "t": int(t.value)}
+        p, m, v, t = self._learn_get_state(self.learner_param_count(), lib().hb_learner_get_state, "hb_learner_get_state")
+        return {"params": p, "m": m, "v": v, "t": t}
 
     def learner_set_state(self, state):
-        p, m, v = (np.ascontiguousarray(state[k], dtype=np.float32) for k in ("params", "m", "v"))
-        n = p.size if p.ndim == 1 and p.shape == m.shape == v.shape else -1
-        _check(lib().hb_learner_set_state(self._h, _ptr(p), _ptr(m), _ptr(v), n, int(state["t"])), "hb_learner_set_state",
-               "needs a learner, three flat records of learner_param_count() values and t >= 0")
+        self._learn_set_state(state, lib().hb_learner_set_state, "hb_learner_set_state",
+                              "needs a learner, three flat records of learner_param_count() values and t >= 0")
 
     def learner_grad_dev(self):
         """(device pointer, count) of the gradient buffer, flat layout: what a multi-GPU caller all-reduces between ppo_grad_dev and ppo_adam_dev"""
@@ -1542,19 +1560,13 @@ class Batch:
                     "target_update_interval >= 1, all finite")
 
     def _sac_config(self, what, cfg, base=None):
-        c = HbSacConfig()
-        if base is not None:
-            ctypes.memmove(ctypes.byref(c), ctypes.byref(base), ctypes.sizeof(c))
-        else:
-            _check(lib().hb_sac_default_config(ctypes.byref(c)), "hb_sac_default_config")
         names = dict(HbSacConfig._fields_)
-        for k, v in cfg.items():
-            if k not in names:
-                raise ValueError("%s: unknown hyper-parameter %r (one of %s)" % (what, k, ", ".join(names)))
+
+        def convert(c, k, v):
             if k == "target_entropy" and "target_entropy_auto" not in cfg:
                 c.target_entropy_auto = 0
             setattr(c, k, int(v) if names[k] in (ctypes.c_int, ctypes.c_uint) else float(v))
-        return c
+        return self._learn_config(HbSacConfig, "hb_sac_default_config", what, cfg, base, convert)
 
     def sac_create(self, **cfg):
         """Creates the SAC learner over the installed actor (squashed head) and Q networks: they become the trainable parameters, the
@@ -1576,46 +1588,31 @@ class Batch:
         _check(lib().hb_sac_destroy(self._h), "hb_sac_destroy", "no SAC learner")
 
     def sac_param_count(self):
-        n = lib().hb_sac_param_count(self._h)
-        _check(0 if n >= 0 else int(n), "hb_sac_param_count", "no SAC learner")
-        return int(n)
+        return self._learn_count(lib().hb_sac_param_count, "hb_sac_param_count", "no SAC learner")
 
     def sac_target_count(self):
-        n = lib().hb_sac_target_count(self._h)
-        _check(0 if n >= 0 else int(n), "hb_sac_target_count", "no SAC learner")
-        return int(n)
+        return self._learn_count(lib().hb_sac_target_count, "hb_sac_target_count", "no SAC learner")
 
     def sac_params(self):
         """the parameters as the flat float32 record (sac_split gives the per-layer arrays)"""
-        out = np.zeros(self.sac_param_count(), dtype=np.float32)
-        _check(lib().hb_sac_get_params(self._h, _ptr(out), out.size), "hb_sac_get_params")
-        return out
+        return self._learn_download(self.sac_param_count(), lib().hb_sac_get_params, "hb_sac_get_params")
 
     def sac_set_params(self, flat):
-        a = np.ascontiguousarray(flat, dtype=np.float32)
-        _check(lib().hb_sac_set_params(self._h, _ptr(a), a.size if a.ndim == 1 else -1), "hb_sac_set_params",
-               "needs a SAC learner and a flat record of sac_param_count() values")
+        self._learn_upload(flat, lib().hb_sac_set_params, "hb_sac_set_params", "needs a SAC learner and a flat record of sac_param_count() values")
 
     def sac_grads(self):
         """the gradients the last step used, flat layout"""
-        out = np.zeros(self.sac_param_count(), dtype=np.float32)
-        _check(lib().hb_sac_get_grads(self._h, _ptr(out), out.size), "hb_sac_get_grads")
-        return out
+        return self._learn_download(self.sac_param_count(), lib().hb_sac_get_grads, "hb_sac_get_grads")
 
     def sac_state(self):
         """{"params", "m", "v": flat float32 records, "targets": the targets' record (Q1' then Q2'), "t": the step count}: checkpoint"""
-        n, nt = self.sac_param_count(), self.sac_target_count()
-        p, m, v = (np.zeros(n, dtype=np.float32) for _ in range(3))
-        tg = np.zeros(nt, dtype=np.float32)
-        t = ctypes.c_longlong()
-        _check(lib().hb_sac_get_state(self._h, _ptr(p), _ptr(m), _ptr(v), n, _ptr(tg), nt, ctypes.byref(t)), "hb_sac_get_state")
-        return {"params": p, "m": m, "v": v, "targets": tg, "t": int(t.value)}
+        tg = np.zeros(self.sac_target_count(), dtype=np.float32)
+        p, m, v, t = self._learn_get_state(self.sac_param_count(), lib().hb_sac_get_state, "hb_sac_get_state", tg)
+        return {"params": p, "m": m, "v": v, "targets": tg, "t": t}
 
     def sac_set_state(self, state):
-        p, m, v, tg = (np.ascontiguousarray(state[k], dtype=np.float32) for k in ("params", "m", "v", "targets"))
-        n = p.size if p.ndim == 1 and p.shape == m.shape == v.shape else -1
-        _check(lib().hb_sac_set_state(self._h, _ptr(p), _ptr(m), _ptr(v), n, _ptr(tg), tg.size if tg.ndim == 1 else -1, int(state["t"])),
-               "hb_sac_set_state", "needs a SAC learner, three flat records of sac_param_count() values, sac_target_count() targets and t >= 0")
+        self._learn_set_state(state, lib().hb_sac_set_state, "hb_sac_set_state",
+                              "needs a SAC learner, three flat records of sac_param_count() values, sac_target_count() targets and t >= 0", "targets")
 
     def sac_step_dev(self, obs, action, reward, next_obs, done, n_rows, mb, index=None, first=0, eps_pi=None, eps_next=None, eps_given=False,
                      stats=None):

@@ -1,8 +1,10 @@
 """fp64 numpy restatement of the PPO learner (include/hb.h: hb_ppo_grad_dev, hb_ppo_adam_dev): stable-baselines3's PPO.train for separate
-actor and critic MLPs (tanh hidden layers, linear top) and a state-independent log_std - the forward pass with kept activations, the loss
+actor and critic MLPs (mlp_ref.py: the chosen hidden activation, tanh by default, linear top) and a state-independent log_std - the loss
 and its statistics, the analytic gradients, global-norm clipping, Adam, and the flat parameter record with its per-tensor split.
 test_ppo_cpu.py holds it against torch autograd and torch.optim.Adam in float64; test_gpu_ppo.py holds the kernels against it."""
 import numpy as np
+
+import mlp_ref as ml
 
 HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
 DEFAULTS = dict(clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, normalize_advantage=1, lr=3e-4, beta1=0.9, beta2=0.999, eps=1e-5)
@@ -19,50 +21,18 @@ def config(**kw):
 
 def flat_shapes(actor_sizes, critic_sizes, nu):
     """(name, shape) of the tensors of the flat record in order: the actor's layers W [K, N] | b [N], log_std [nu], the critic's layers"""
-    out = []
-    for tag, sizes in (("actor", actor_sizes), ("critic", critic_sizes)):
-        for l in range(len(sizes) - 1):
-            out += [("%s.w%d" % (tag, l), (sizes[l], sizes[l + 1])), ("%s.b%d" % (tag, l), (sizes[l + 1],))]
-        if tag == "actor":
-            out.append(("log_std", (nu,)))
-    return out
+    return ml.net_shapes("actor", actor_sizes) + [("log_std", (nu,))] + ml.net_shapes("critic", critic_sizes)
 
 
 def split(flat, actor_sizes, critic_sizes, nu):
-    flat = np.asarray(flat)
-    out, o = {}, 0
-    for name, sh in flat_shapes(actor_sizes, critic_sizes, nu):
-        n = int(np.prod(sh))
-        out[name] = flat[o:o + n].reshape(sh).copy()
-        o += n
-    assert o == flat.size, (o, flat.size)
-    return out
+    return ml.split(flat, flat_shapes(actor_sizes, critic_sizes, nu))
 
 
 def join(tensors, actor_sizes, critic_sizes, nu):
-    return np.concatenate([np.asarray(tensors[name], dtype=np.float64).reshape(sh).ravel() for name, sh in flat_shapes(actor_sizes, critic_sizes, nu)])
+    return ml.join(tensors, flat_shapes(actor_sizes, critic_sizes, nu))
 
 
-def forward(tensors, tag, n_layers, x):
-    """acts[l]: the input of layer l (acts[0] = x), and the last layer's (linear) output"""
-    acts, a = [], np.asarray(x, dtype=np.float64)
-    for l in range(n_layers):
-        acts.append(a)
-        z = a @ np.asarray(tensors["%s.w%d" % (tag, l)], dtype=np.float64) + np.asarray(tensors["%s.b%d" % (tag, l)], dtype=np.float64)
-        a = z if l == n_layers - 1 else np.tanh(z)
-    return acts, a
-
-
-def backward(tensors, tag, n_layers, acts, dz, grads):
-    """dz: dloss / d(the last layer's output); fills grads[tag.w*], grads[tag.b*]"""
-    for l in range(n_layers - 1, -1, -1):
-        grads["%s.w%d" % (tag, l)] = acts[l].T @ dz
-        grads["%s.b%d" % (tag, l)] = dz.sum(axis=0)
-        if l > 0:
-            dz = (dz @ np.asarray(tensors["%s.w%d" % (tag, l)], dtype=np.float64).T) * (1.0 - acts[l] ** 2)
-
-
-def loss_and_grads(flat, actor_sizes, critic_sizes, rows, cfg, index=None, first=0, mb=None):
+def loss_and_grads(flat, actor_sizes, critic_sizes, rows, cfg, index=None, first=0, mb=None, act_actor="tanh", act_critic="tanh"):
     """rows: dict obs [R, nobs], action [R, nu], old_log_prob, advantage, returns [R].  Returns (stats dict, flat fp64 gradient, extras)."""
     nu = actor_sizes[-1]
     t = split(np.asarray(flat, dtype=np.float64), actor_sizes, critic_sizes, nu)
@@ -72,8 +42,8 @@ def loss_and_grads(flat, actor_sizes, critic_sizes, rows, cfg, index=None, first
     old, adv, ret = (np.asarray(rows[k], dtype=np.float64)[sel] for k in ("old_log_prob", "advantage", "returns"))
     c = float(cfg["clip_range"])
     La, Lc = len(actor_sizes) - 1, len(critic_sizes) - 1
-    acts_a, mu = forward(t, "actor", La, obs)
-    acts_c, v = forward(t, "critic", Lc, obs)
+    acts_a, mu, _ = ml.forward(t, "actor", La, obs, act_actor)
+    acts_c, v, _ = ml.forward(t, "critic", Lc, obs, act_critic)
     v = v[:, 0]
     ls = t["log_std"]
     s2 = np.exp(2.0 * ls)
@@ -94,9 +64,9 @@ def loss_and_grads(flat, actor_sizes, critic_sizes, rows, cfg, index=None, first
     inside = (ratio >= 1.0 - c) & (ratio <= 1.0 + c)
     glp = np.where(inside | (s1 < s2c), -A * ratio / mb, 0.0)
     grads = {}
-    backward(t, "actor", La, acts_a, glp[:, None] * (act - mu) / s2, grads)
+    ml.backward(t, "actor", La, acts_a, glp[:, None] * (act - mu) / s2, act_actor, grads)
     grads["log_std"] = (glp[:, None] * ((act - mu) ** 2 / s2 - 1.0)).sum(axis=0) - cfg["ent_coef"]
-    backward(t, "critic", Lc, acts_c, (2.0 * cfg["vf_coef"] * (v - ret) / mb)[:, None], grads)
+    ml.backward(t, "critic", Lc, acts_c, (2.0 * cfg["vf_coef"] * (v - ret) / mb)[:, None], act_critic, grads)
     g = join(grads, actor_sizes, critic_sizes, nu)
     stats["grad_norm"] = float(np.sqrt((g ** 2).sum()))
     return stats, g, dict(mu=mu, v=v, lp=lp, ratio=ratio, A=A, glp=glp, acts_a=acts_a, acts_c=acts_c)
@@ -112,29 +82,18 @@ def adam_step(p, m, v, t, g, cfg):
     gn = float(np.sqrt((g ** 2).sum()))
     if not np.isfinite(gn):
         return p.copy(), m.copy(), v.copy(), t, gn, True
-    g = g * clip_scale(gn, float(cfg["max_grad_norm"]))
-    b1, b2 = float(cfg["beta1"]), float(cfg["beta2"])
-    t = t + 1
-    m = b1 * m + (1.0 - b1) * g
-    v = b2 * v + (1.0 - b2) * g * g
-    p = p - float(cfg["lr"]) / (1.0 - b1 ** t) * m / (np.sqrt(v) / np.sqrt(1.0 - b2 ** t) + float(cfg["eps"]))
-    return p, m, v, t, gn, False
+    p, m, v = ml.adam(p, m, v, t + 1, g * clip_scale(gn, float(cfg["max_grad_norm"])), cfg["lr"], cfg)
+    return p, m, v, t + 1, gn, False
 
 
-def torch_loss(torch, dtype, flat, asz, csz, rows, cfg, sel):
+def torch_loss(torch, dtype, flat, asz, csz, rows, cfg, sel, act_actor="tanh", act_critic="tanh"):
     """SB3's PPO.train loss written with torch ops on CPU leaves of `dtype` (one leaf per tensor of the flat record): autograd in float64
     is what the reference is held to, in float32 it is the noise floor of an independent single-precision evaluation"""
     nu = asz[-1]
     leaves = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in split(flat, asz, csz, nu).items()}
-
-    def mlp(tag, n, x):
-        for l in range(n):
-            x = x @ leaves["%s.w%d" % (tag, l)] + leaves["%s.b%d" % (tag, l)]
-            if l < n - 1:
-                x = torch.tanh(x)
-        return x
     obs, act, old, adv, ret = (torch.tensor(np.asarray(rows[k], dtype=np.float64)[sel], dtype=dtype) for k in ("obs", "action", "old_log_prob", "advantage", "returns"))
-    mu, v = mlp("actor", len(asz) - 1, obs), mlp("critic", len(csz) - 1, obs)[:, 0]
+    mu = ml.torch_mlp(torch, leaves, "actor", len(asz) - 1, obs, act_actor)
+    v = ml.torch_mlp(torch, leaves, "critic", len(csz) - 1, obs, act_critic)[:, 0]
     dist = torch.distributions.Normal(mu, torch.ones_like(mu) * leaves["log_std"].exp())
     lp = dist.log_prob(act).sum(dim=1)
     if cfg["normalize_advantage"] and len(sel) > 1:
@@ -163,7 +122,7 @@ def random_problem(actor_sizes, critic_sizes, n_rows, seed, stale=0.3):
             t[name] = rng.normal(0.0, 0.1, sh)
     flat = join(t, actor_sizes, critic_sizes, nu).astype(np.float32).astype(np.float64)
     obs = rng.normal(0.0, 1.0, (n_rows, actor_sizes[0])).astype(np.float32)
-    _, mu = forward(split(flat, actor_sizes, critic_sizes, nu), "actor", len(actor_sizes) - 1, obs)
+    mu = ml.forward(split(flat, actor_sizes, critic_sizes, nu), "actor", len(actor_sizes) - 1, obs)[1]
     ls = split(flat, actor_sizes, critic_sizes, nu)["log_std"]
     action = (mu + np.exp(ls) * rng.normal(0.0, 1.0, mu.shape)).astype(np.float32)
     lp = (-(action - mu) ** 2 / (2.0 * np.exp(2.0 * ls)) - ls - HALF_LOG_2PI).sum(axis=1)

@@ -1,12 +1,11 @@
-"""tests/act_ref.py without a device: the fp64 MLP with a chosen hidden activation against torch autograd in float64 (nn.Tanh / nn.ReLU /
-nn.ELU), for tanh against ppo_ref / sac_ref; the margin conditions of exactly the problems tests/test_gpu_act.py runs; and the refusals of
+"""tests/mlp_ref.py and act_ref.py without a device: the fp64 MLP with a chosen hidden activation against torch autograd in float64 (nn.Tanh /
+nn.ReLU / nn.ELU), tanh as the default the learner references run; the margin conditions of exactly the problems tests/test_gpu_act.py runs; and the refusals of
 hb_mlp_set_activation / hb_mlp_get_activation that need no device."""
 import numpy as np
 import pytest
 
 import act_ref as ac
-import ppo_ref as pr
-import sac_ref as sr
+import mlp_ref as ml
 
 
 def _net(sizes, seed, tag="n"):
@@ -18,7 +17,7 @@ def _net(sizes, seed, tag="n"):
     return t
 
 
-@pytest.mark.parametrize("activation", ac.ACTIVATIONS)
+@pytest.mark.parametrize("activation", ml.ACTIVATIONS)
 @pytest.mark.parametrize("sizes", [[48, 20, 72, 21], [69, 256, 1], [48, 21]])
 def test_forward_and_backward_equal_autograd(activation, sizes):
     torch = pytest.importorskip("torch")
@@ -26,46 +25,48 @@ def test_forward_and_backward_equal_autograd(activation, sizes):
     t = _net(sizes, 3)
     rng = np.random.default_rng(4)
     x, top = rng.normal(size=(40, sizes[0])), rng.normal(size=(40, sizes[-1]))
-    acts, out, zs = ac.forward(t, "n", n, x, activation)
+    acts, out, zs = ml.forward(t, "n", n, x, activation)
     grads = {}
-    dx = ac.backward(t, "n", n, acts, top, activation, grads)
+    dx = ml.backward(t, "n", n, acts, top, activation, grads)
     leaves = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in t.items()}
     xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
-    o = ac.torch_mlp(torch, leaves, "n", n, xt, activation)
+    o = ml.torch_mlp(torch, leaves, "n", n, xt, activation)
     assert np.abs(o.detach().numpy() - out).max() <= 1e-13 * max(1.0, np.abs(out).max())
     (o * torch.tensor(top)).sum().backward()
     assert np.abs(xt.grad.numpy() - dx).max() <= 1e-12 * max(1.0, np.abs(dx).max())
     for k in t:
         assert np.abs(leaves[k].grad.numpy() - grads[k]).max() <= 1e-12 * max(1.0, np.abs(grads[k]).max()), k
-    assert len(zs) == n - 1 and all(np.array_equal(ac.act(activation, z), a) for z, a in zip(zs, acts[1:]))
+    assert len(zs) == n - 1 and all(np.array_equal(ml.act(activation, z), a) for z, a in zip(zs, acts[1:]))
 
 
 def test_tanh_is_the_existing_references():
+    """ppo_ref and sac_ref run mlp_ref with the activation left out where their caller names none: that default is tanh, bit for bit,
+    and tanh is what those references stated themselves before - np.tanh behind a hidden layer, the derivative 1 - a^2 from its output"""
     t = _net([48, 20, 72, 21], 5, "actor")
     rng = np.random.default_rng(6)
     x, top = rng.normal(size=(40, 48)), rng.normal(size=(40, 21))
-    acts, out, _ = ac.forward(t, "actor", 3, x, "tanh")
-    for ref in (pr, sr):
-        racts, rout = ref.forward(t, "actor", 3, x)
-        assert np.array_equal(rout, out) and all(np.array_equal(a, b) for a, b in zip(racts, acts))
-    g, gp, gs = {}, {}, {}
-    dx = ac.backward(t, "actor", 3, acts, top, "tanh", g)
-    pr.backward(t, "actor", 3, acts, top, gp)
-    assert np.array_equal(sr.backward(t, "actor", 3, acts, top, gs), dx)
+    acts, out, zs = ml.forward(t, "actor", 3, x, "tanh")
+    racts, rout, _ = ml.forward(t, "actor", 3, x)
+    assert np.array_equal(rout, out) and all(np.array_equal(a, b) for a, b in zip(racts, acts))
+    assert all(np.array_equal(np.tanh(z), a) for z, a in zip(zs, acts[1:]))
+    assert all(np.array_equal(ml.slope("tanh", a), 1.0 - a ** 2) for a in acts[1:])
+    g, gd = {}, {}
+    dx = ml.backward(t, "actor", 3, acts, top, "tanh", g)
+    assert np.array_equal(ml.backward(t, "actor", 3, acts, top, grads=gd), dx)
     for k in g:
-        assert np.array_equal(g[k], gp[k]) and np.array_equal(g[k], gs[k]), k
-    e, _ = ac.fwd_err(t, "actor", 3, acts, "tanh")
-    assert np.array_equal(e, sr.fwd_err(t, "actor", 3, acts))
+        assert np.array_equal(g[k], gd[k]), k
+    e, _ = ml.fwd_err(t, "actor", 3, acts, "tanh")
+    assert np.array_equal(e, ml.fwd_err(t, "actor", 3, acts)[0])
 
 
 def test_activations_at_their_edges():
     z = np.array([-np.inf, -30.0, -1.0, -0.0, 0.0, 2.0, np.inf, np.nan])
     with np.errstate(invalid="ignore"):
-        r, e = ac.act("relu", z), ac.act("elu", z)
+        r, e = ml.act("relu", z), ml.act("elu", z)
     assert np.array_equal(r[:7], [0.0, 0.0, 0.0, 0.0, 0.0, 2.0, np.inf]) and np.isnan(r[7])   # (NaN stays NaN: a select, not a maximum)
     assert np.array_equal(e[[0, 3, 4, 5, 6]], [-1.0, 0.0, 0.0, 2.0, np.inf]) and e[2] == np.expm1(-1.0) and np.isnan(e[7])
-    assert np.array_equal(ac.slope("relu", r[:6]), [0, 0, 0, 0, 0, 1])                            # (0 at v <= 0, as torch)
-    assert np.allclose(ac.slope("elu", e[:6]), np.exp(np.minimum(z[:6], 0.0)), rtol=0, atol=1e-15)
+    assert np.array_equal(ml.slope("relu", r[:6]), [0, 0, 0, 0, 0, 1])                            # (0 at v <= 0, as torch)
+    assert np.allclose(ml.slope("elu", e[:6]), np.exp(np.minimum(z[:6], 0.0)), rtol=0, atol=1e-15)
 
 
 @pytest.mark.parametrize("key", sorted(ac.PPO_SEEDS))

@@ -1,10 +1,10 @@
 """The hidden activation of the installed MLPs (include/hb.h: hb_mlp_set_activation) on the device, ReLU and ELU: every forward kernel
-against the fp64 reference of tests/act_ref.py within the derived forward bound, both learners' gradients against torch float64 autograd
+against the fp64 MLP of tests/mlp_ref.py within the derived forward bound, both learners' gradients against torch float64 autograd
 on the same rows, an Adam step of each learner, the rules of the interface, and tanh set explicitly against tanh never set, bit for bit.
 27-dof humanoid, 24 envs, minibatches of 40 rows; hidden widths 20 | 72 (split-K merge hook | direct hook) and 256 (act_ref.HIDDEN).
 
 Bounds, u = 2^-24:
- - forward: act_ref.fwd_err, the layer recurrence e' = (K + 2) u (|a| |W| + |b|) + e |W| + c u with c = 4 (tanhf), 0 (ReLU), 2 (ELU: twice
+ - forward: mlp_ref.fwd_err, the layer recurrence e' = (K + 2) u (|a| |W| + |b|) + e |W| + c u with c = 4 (tanhf), 0 (ReLU), 2 (ELU: twice
    the measured worst error of expm1f, profiles/act_parity.txt); behind a tanh output (hb_policy_eval) one more 4 u, behind the clamp of
    log_std nothing (both have slopes of at most 1);
  - gradients, per tensor: max|g_gpu - g_64| <= k max|g_64|, k = 8 x the float32 noise floor - the largest max|g_32 - g_64| / max|g_64| over
@@ -19,13 +19,14 @@ import numpy as np
 import pytest
 
 import act_ref as ac
+import mlp_ref as ml
 import ppo_ref as pr
 import sac_ref as sr
 from oracle_lib import HUMANOID_HBM  # noqa: F401  (the model of the humanoid_model fixture)
 
 pytestmark = pytest.mark.gpu
 
-NOBS, NU, U = ac.NOBS, ac.NU, ac.U
+NOBS, NU, U = ac.NOBS, ac.NU, ml.U
 N, MB, SEL = ac.N_ENV, ac.MB, ac.SEL
 ACTS = ("relu", "elu")
 NETS = sorted(ac.HIDDEN)
@@ -114,8 +115,8 @@ def test_policy_eval(hbmod, humanoid_model, gpu, activation, net):
     b.set_policy_mlp(*ac.layers(t, "p", sizes), activation=activation)
     assert b.mlp_activation("policy") == activation
     obs, _, _, _ = b.obs(want_reward=False)
-    acts, out, _ = ac.forward(t, "p", len(sizes) - 1, obs, activation)
-    bound = ac.fwd_err(t, "p", len(sizes) - 1, acts, activation)[0] + 4 * U
+    acts, out, _ = ml.forward(t, "p", len(sizes) - 1, obs, activation)
+    bound = ml.fwd_err(t, "p", len(sizes) - 1, acts, activation)[0] + 4 * U
     worst = []
     for lean in (1, 2):
         b.tune(policy_lean=lean)
@@ -143,8 +144,8 @@ def test_collected_step_values_and_q(hbmod, humanoid_model, gpu, activation, net
     assert [b.mlp_activation(k) for k in ("actor", "critic", "q1", "q2")] == [activation] * 4
     tapes, ptr = _collect(b, mem, _obs0(41), log_std=True)
     La = len(asz) - 1
-    acts, out, _ = ac.forward(t, "actor", La, tapes["obs"][0], activation)
-    e = ac.fwd_err(t, "actor", La, acts, activation)[0]
+    acts, out, _ = ml.forward(t, "actor", La, tapes["obs"][0], activation)
+    e = ml.fwd_err(t, "actor", La, acts, activation)[0]
     r_mean = _ratio(np.abs(tapes["mean"][0] - out[:, :NU]), e[:, :NU])
     r_ls = _ratio(np.abs(tapes["log_std"][0] - np.clip(out[:, NU:], -20.0, 2.0)), e[:, NU:])
     assert r_mean <= 1.0 and r_ls <= 1.0, (r_mean, r_ls)
@@ -153,8 +154,8 @@ def test_collected_step_values_and_q(hbmod, humanoid_model, gpu, activation, net
     b.collect_gae_dev(1, 0.99, 0.95, True, obs=ptr["obs"], value=pv)
     rows = tapes["obs"].reshape(2 * N, NOBS)
     assert np.isfinite(rows).all()
-    acts, v, _ = ac.forward(t, "critic", len(csz) - 1, rows, activation)
-    r_v = _ratio(np.abs(b.from_dev(pv, (2 * N,)) - v[:, 0]), ac.fwd_err(t, "critic", len(csz) - 1, acts, activation)[0][:, 0])
+    acts, v, _ = ml.forward(t, "critic", len(csz) - 1, rows, activation)
+    r_v = _ratio(np.abs(b.from_dev(pv, (2 * N,)) - v[:, 0]), ml.fwd_err(t, "critic", len(csz) - 1, acts, activation)[0][:, 0])
     assert r_v <= 1.0, r_v
     rng = np.random.default_rng(42)
     obs, action = rng.normal(size=(MB, NOBS)).astype(np.float32), np.tanh(rng.normal(size=(MB, NU))).astype(np.float32)
@@ -163,8 +164,8 @@ def test_collected_step_values_and_q(hbmod, humanoid_model, gpu, activation, net
     xin = np.concatenate([obs, action], axis=1)
     r_q = 0.0
     for tag, p in (("q1", p1), ("q2", p2)):
-        acts, q, _ = ac.forward(t, tag, len(qsz) - 1, xin, activation)
-        r_q = max(r_q, _ratio(np.abs(b.from_dev(p, (MB,)) - q[:, 0]), ac.fwd_err(t, tag, len(qsz) - 1, acts, activation)[0][:, 0]))
+        acts, q, _ = ml.forward(t, tag, len(qsz) - 1, xin, activation)
+        r_q = max(r_q, _ratio(np.abs(b.from_dev(p, (MB,)) - q[:, 0]), ml.fwd_err(t, tag, len(qsz) - 1, acts, activation)[0][:, 0]))
     assert r_q <= 1.0, r_q
     mem.free()
     env.close()
@@ -186,7 +187,7 @@ def test_relu_gives_exact_zeros(hbmod, humanoid_model, gpu, hidden):
     b, mem = env.batch, Mem(env.batch)
     b.actor_set(sizes, *ac.layers(t, "actor", sizes), head="gaussian", log_std=np.zeros(NU, np.float32), seed=3, activation="relu")
     tapes, _ = _collect(b, mem, obs0)
-    z = ac.forward(t, "actor", 2, obs0, "relu")[2][0][:, :NU]
+    z = ml.forward(t, "actor", 2, obs0, "relu")[2][0][:, :NU]
     mean = tapes["mean"][0]
     assert (z < 0).sum() > 50 and (z > 0).sum() > 50
     assert (mean[z < 0] == 0.0).all() and (mean[z > 0] > 0.0).all()
@@ -219,7 +220,7 @@ def test_ppo_gradients_and_adam_step(hbmod, humanoid_model, gpu, activation, net
     got = pr.split(b.learner_grads().astype(np.float64), asz, csz, NU)
     assert all(np.isfinite(g).all() for g in got.values())
     tensors = list(got)
-    g64, g32 = ({k: v for k, v in ac.torch_grads(torch, *ac.torch_ppo_loss(torch, dt, flat, asz, csz, rows, cfg, SEL, activation, activation), tensors).items()}
+    g64, g32 = ({k: v for k, v in ac.torch_grads(torch, *pr.torch_loss(torch, dt, flat, asz, csz, rows, cfg, SEL, activation, activation)[:2], tensors).items()}
                 for dt in (torch.float64, torch.float32))
     worst = 0.0
     for group in ("actor", "critic"):   # (log_std goes with the actor)
@@ -235,9 +236,9 @@ def test_ppo_gradients_and_adam_step(hbmod, humanoid_model, gpu, activation, net
     assert np.abs(new - flat).max() > 1e-3
     tn = pr.split(new, asz, csz, NU)
     tapes, _ = _collect(b, mem, _obs0(61))
-    acts, mu, _ = ac.forward(tn, "actor", len(asz) - 1, tapes["obs"][0], activation)
-    r_mean = _ratio(np.abs(tapes["mean"][0] - mu), ac.fwd_err(tn, "actor", len(asz) - 1, acts, activation)[0])
-    _, mu_old, _ = ac.forward(t, "actor", len(asz) - 1, tapes["obs"][0], activation)
+    acts, mu, _ = ml.forward(tn, "actor", len(asz) - 1, tapes["obs"][0], activation)
+    r_mean = _ratio(np.abs(tapes["mean"][0] - mu), ml.fwd_err(tn, "actor", len(asz) - 1, acts, activation)[0])
+    _, mu_old, _ = ml.forward(t, "actor", len(asz) - 1, tapes["obs"][0], activation)
     assert r_mean <= 1.0 and np.abs(mu - mu_old).max() > 1e-3, r_mean
     mem.free()
     env.close()
@@ -301,9 +302,9 @@ def test_sac_step_gradients_and_targets(hbmod, humanoid_model, gpu, activation, 
     anames = [k for k in got if k.startswith("actor")]
     ref, floor = {}, {}
     for dt, dst in ((torch.float64, ref), (torch.float32, floor)):
-        lc = ac.torch_sac_losses(torch, dt, s0["params"], s0["targets"], asz, qsz, rows, SEL, ep, en, cfg, activation, activation)
+        lc = sr.torch_losses(torch, dt, s0["params"], s0["targets"], asz, qsz, rows, SEL, ep, en, cfg, act_actor=activation, act_q=activation)
         dst.update(ac.torch_grads(torch, lc[0] + lc[1], lc[3], cnames))
-        la = ac.torch_sac_losses(torch, dt, mid, s0["targets"], asz, qsz, rows, SEL, ep, en, cfg, activation, activation, alpha=alpha)
+        la = sr.torch_losses(torch, dt, mid, s0["targets"], asz, qsz, rows, SEL, ep, en, cfg, alpha=alpha, act_actor=activation, act_q=activation)
         dst.update(ac.torch_grads(torch, la[2], la[3], anames))
     worst = 0.0
     for ks in (cnames, anames):
@@ -317,8 +318,8 @@ def test_sac_step_gradients_and_targets(hbmod, humanoid_model, gpu, activation, 
     assert not np.array_equal(s1["targets"], s0["targets"])
     t1 = sr.split(s1["params"], asz, qsz)
     tapes, _ = _collect(b, mem, _obs0(71), log_std=True)
-    acts, out, _ = ac.forward(t1, "actor", len(asz) - 1, tapes["obs"][0], activation)
-    e = ac.fwd_err(t1, "actor", len(asz) - 1, acts, activation)[0]
+    acts, out, _ = ml.forward(t1, "actor", len(asz) - 1, tapes["obs"][0], activation)
+    e = ml.fwd_err(t1, "actor", len(asz) - 1, acts, activation)[0]
     r_act = max(_ratio(np.abs(tapes["mean"][0] - out[:, :NU]), e[:, :NU]), _ratio(np.abs(tapes["log_std"][0] - np.clip(out[:, NU:], -20.0, 2.0)), e[:, NU:]))
     assert r_act <= 1.0, r_act
     # a second step: its y comes from the targets the Polyak step left, on the Q networks' activation.  One row, so that y is not an

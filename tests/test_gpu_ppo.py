@@ -3,8 +3,8 @@ tests/ppo_ref.py, at the GPU's own downloaded parameters.  Batches of 16 envs, s
 
 Bounds, u = 2^-24:
  (a) derived from the arithmetic, by row and summed (_derived): the statistics, the top-layer bias gradients of both networks and the
-     log_std gradient.  The forward error of a network follows its layers, e' = (K + 2) u (|a| |W| + |b|) + e |W| (+ 4 u behind tanhf):
-     a K-term f32 MFMA chain and the bias, then the error carried in.  From the error of mean and value: log-probability, ratio (expf at
+     log_std gradient.  The forward error of a network follows its layers (mlp_ref.fwd_err: a K-term f32 MFMA chain and the bias, then
+     the error carried in, 4 u behind tanhf).  From the error of mean and value: log-probability, ratio (expf at
      1 ulp), the loss terms, dloss/dmean, dloss/dlog_std, dloss/dvalue, each a handful of f32 roundings; a row whose ratio stands within
      its error of a clip bound may take the other branch and counts with its whole term.  Row sums: n u sum|x| for n f32 additions.
  (b) the back-propagated gradients (every W, the hidden biases), per tensor: max|g_gpu - g_64| <= k max|g_64| with k = 8 x the float32
@@ -22,6 +22,7 @@ import os
 import numpy as np
 import pytest
 
+import mlp_ref as ml
 import ppo_ref as pr
 from oracle_lib import HUMANOID_HBM  # noqa: F401  (the model of the humanoid_model fixture)
 
@@ -97,16 +98,6 @@ class Dev:
             self.b.dev_free(p)
 
 
-def _fwd_err(t, tag, n_layers, acts):
-    e = np.zeros_like(acts[0])
-    for l in range(n_layers):
-        W, bias = np.abs(t["%s.w%d" % (tag, l)]), np.abs(t["%s.b%d" % (tag, l)])
-        e = (W.shape[0] + 2) * U * (np.abs(acts[l]) @ W + bias) + e @ W
-        if l < n_layers - 1:
-            e = e + 4 * U
-    return e
-
-
 def _derived(flat, asz, csz, rows, sel, cfg, ex, stats, chunk):
     """tier (a): bounds of the statistics and of the head gradients (dict name -> bound)"""
     t = pr.split(flat, asz, csz, NU)
@@ -118,7 +109,7 @@ def _derived(flat, asz, csz, rows, sel, cfg, ex, stats, chunk):
     c, vf = cfg["clip_range"], cfg["vf_coef"]
     ls = t["log_std"]
     s = np.exp(ls)
-    dmu_e, dv_e = _fwd_err(t, "actor", len(asz) - 1, ex["acts_a"]), _fwd_err(t, "critic", len(csz) - 1, ex["acts_c"])[:, 0]
+    dmu_e, dv_e = ml.fwd_err(t, "actor", len(asz) - 1, ex["acts_a"])[0], ml.fwd_err(t, "critic", len(csz) - 1, ex["acts_c"])[0][:, 0]
     z = (act - mu) / s
     dz = np.abs(z) * 3 * U + dmu_e / s
     M = 0.5 * z * z + np.abs(ls) + pr.HALF_LOG_2PI

@@ -3,8 +3,8 @@ downloaded state.  Batches of 16 envs, synthetic rows (no physics), the draws gi
 
 Bounds, u = 2^-24:
  (a) derived from the arithmetic, by row and summed (_derived_*): the statistics, the top-layer bias gradients of Q1 and Q2 and the
-     log_ent_coef gradient.  The forward error of a network follows its layers (sac_ref.fwd_err, the recurrence of test_gpu_ppo.py), the
-     error of a sampled action carried into the Q networks' input rows (sac_ref.action_err); from there the log-probabilities, the target,
+     log_ent_coef gradient.  The forward error of a network follows its layers (mlp_ref.fwd_err), the error of a sampled action carried
+     into the Q networks' input rows (sac_ref.action_err); from there the log-probabilities (sac_ref.lp_err), the target (sac_ref.target),
      the residuals Qk - y, each a handful of f32 roundings; means are formed in fp64 from the f32 terms.
  (b) the back-propagated gradients - every W and hidden bias of Q1, Q2, and EVERY tensor of the actor, whose top dZ already holds
      dQ / da, a back-propagated quantity -, per tensor: max|g_gpu - g_64| <= k max|g_64|, k = 8 x the float32 noise floor, the floor
@@ -20,6 +20,7 @@ import os
 import numpy as np
 import pytest
 
+import mlp_ref as ml
 import sac_ref as sr
 from oracle_lib import HUMANOID_HBM  # noqa: F401  (the model of the humanoid_model fixture)
 
@@ -119,30 +120,14 @@ class Dev:
             self.b.dev_free(p)
 
 
-def _lp_err(h, e_out):
-    """the error of a row's log-probability given the error of the actor's output, and the error of its action"""
-    nu = h["mean"].shape[1]
-    e_mean, e_ls = e_out[:, :nu], e_out[:, nu:]
-    dx = e_mean + h["s"] * np.abs(h["eps"]) * (np.expm1(e_ls) + 3 * U) + U * np.abs(h["x"])
-    M = 0.5 * h["eps"] ** 2 + np.abs(h["ls"]) + sr.HALF_LOG_2PI + 2.0 * (sr.LOG2 + np.abs(h["x"]) + sr.LOG2)
-    return (e_ls + 2.0 * dx).sum(axis=1) + (nu + 10) * U * M.sum(axis=1)
-
-
 def _derived_critic(flat, targets, asz, qsz, rows, sel, cfg, ex, stats):
     """tier (a), critic phase: bounds of its statistics, of the Q networks' top bias gradients and of dloss / dlog_ent_coef"""
     t = sr.split(flat, asz, qsz)
-    tt = sr.with_targets(t, targets, asz, qsz)
     La, Lq, mb = len(asz) - 1, len(qsz) - 1, len(sel)
     nsum = mb + 2
-    pi, nx = ex["pi"], ex["nx"]
-    e_pi, e_nx = sr.fwd_err(t, "actor", La, pi["acts"]), sr.fwd_err(t, "actor", La, nx["acts"])
-    dlp_pi, dlp_nx = _lp_err(pi, e_pi), _lp_err(nx, e_nx)
-    e_in = np.concatenate([np.zeros((mb, NOBS)), sr.action_err(nx, e_nx)], axis=1)
-    e_t = np.maximum(sr.fwd_err(tt, "q1", Lq, ex["acts_t1"], e_in)[:, 0], sr.fwd_err(tt, "q2", Lq, ex["acts_t2"], e_in)[:, 0])
-    alpha, gamma = ex["alpha"], cfg["gamma"]
-    done = np.asarray(rows["done"], dtype=np.float64)[sel]
-    mq = np.minimum(ex["qt1"], ex["qt2"])
-    dy = (1.0 - done) * gamma * (e_t + alpha * dlp_nx + 3 * U * (np.abs(mq) + np.abs(alpha * nx["lp"]))) + 2 * U * np.abs(ex["y"])
+    pi, alpha = ex["pi"], ex["alpha"]
+    dlp_pi = sr.lp_err(pi, ml.fwd_err(t, "actor", La, pi["acts"])[0])
+    dy = sr.target(flat, targets, asz, qsz, rows, sel, ex["nx"]["eps"], cfg)[1]
     lec = abs(float(t["log_ent_coef"][0]))
     B = {"ent_coef": 2 * U * alpha, "lp_pi": dlp_pi.mean() + U * abs(stats["lp_pi"]), "y": dy.mean() + U * abs(stats["y"])}
     B["ent_coef_loss"] = lec * dlp_pi.mean() + 2 * U * abs(stats["ent_coef_loss"]) + 1e-12
@@ -150,7 +135,7 @@ def _derived_critic(flat, targets, asz, qsz, rows, sel, cfg, ex, stats):
     B["critic_loss"] = U * abs(stats["critic_loss"]) + 1e-12
     for k, tag, acts in ((1, "q1", ex["acts1"]), (2, "q2", ex["acts2"])):
         q = ex["q%d" % k]
-        e_q = sr.fwd_err(t, tag, Lq, acts)[:, 0]
+        e_q = ml.fwd_err(t, tag, Lq, acts)[0][:, 0]
         e = q - ex["y"]
         de = e_q + dy + U * np.abs(e)
         B["q%d" % k] = e_q.mean() + U * abs(stats["q%d" % k])
@@ -164,10 +149,10 @@ def _derived_actor(flat, asz, qsz, sel, ex, alpha, stats):
     t = sr.split(flat, asz, qsz)
     La, Lq, mb = len(asz) - 1, len(qsz) - 1, len(sel)
     pi = ex["pi"]
-    e_pi = sr.fwd_err(t, "actor", La, pi["acts"])
-    dlp = _lp_err(pi, e_pi)
+    e_pi = ml.fwd_err(t, "actor", La, pi["acts"])[0]
+    dlp = sr.lp_err(pi, e_pi)
     e_in = np.concatenate([np.zeros((mb, NOBS)), sr.action_err(pi, e_pi)], axis=1)
-    e_q = np.maximum(sr.fwd_err(t, "q1", Lq, ex["acts1"], e_in)[:, 0], sr.fwd_err(t, "q2", Lq, ex["acts2"], e_in)[:, 0])
+    e_q = np.maximum(ml.fwd_err(t, "q1", Lq, ex["acts1"], e0=e_in)[0][:, 0], ml.fwd_err(t, "q2", Lq, ex["acts2"], e0=e_in)[0][:, 0])
     mq = np.minimum(ex["q1"], ex["q2"])
     return {"min_q_pi": e_q.mean() + U * abs(stats["min_q_pi"]),
             "actor_loss": (alpha * dlp + e_q + 3 * U * (np.abs(alpha * pi["lp"]) + np.abs(mq))).mean() + U * abs(stats["actor_loss"]) + 1e-12}
@@ -306,8 +291,8 @@ def test_q_values_against_fp64(hbmod, humanoid_model, gpu, net):
         assert np.array_equal(b.from_dev(p1, (n,)), got[1])
         xin = np.concatenate([obs, act], axis=1).astype(np.float64)
         for k, tag in enumerate(("q1", "q2")):
-            acts, q = sr.forward(t, tag, Lq, xin)
-            bound = sr.fwd_err(t, tag, Lq, acts)[:, 0]
+            acts, q, _ = ml.forward(t, tag, Lq, xin)
+            bound = ml.fwd_err(t, tag, Lq, acts)[0][:, 0]
             r = _worst_ratio(np.abs(got[k] - q[:, 0]), bound)
             worst = max(worst, r)
             assert r <= 1.0, (net, n, tag, r)
@@ -482,8 +467,8 @@ def test_the_loop(hbmod, humanoid_model, gpu):
     assert np.array_equal(out["eps"], ref["eps"]) and np.abs(out["eps"]).max() > 0       # the draw counter stayed
     La = len(asz) - 1
     for tt, differs in ((t, False), (sr.split(pb["flat"], asz, qsz), True)):
-        acts, o64 = sr.forward(tt, "actor", La, out["obs"][:4].reshape(64, NOBS).astype(np.float64))
-        e = sr.fwd_err(tt, "actor", La, acts)
+        acts, o64, _ = ml.forward(tt, "actor", La, out["obs"][:4].reshape(64, NOBS).astype(np.float64))
+        e = ml.fwd_err(tt, "actor", La, acts)[0]
         mean64, ls64 = o64[:, :NU].reshape(4, 16, NU), np.clip(o64[:, NU:], -20, 2).reshape(4, 16, NU)
         ok = (np.abs(out["mean"] - mean64) <= e[:, :NU].reshape(4, 16, NU)).all() and (np.abs(out["log_std"] - ls64) <= e[:, NU:].reshape(4, 16, NU)).all()
         assert ok != differs

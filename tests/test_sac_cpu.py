@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import mlp_ref as ml
 import sac_ref as sr
 from conftest import ROOT
 
@@ -86,7 +87,7 @@ def test_reference_adam_equals_torch_adam_per_group():
             g = rng.normal(size=200)
             leaf.grad = torch.tensor(g.copy())
             opt.step()
-            p, m, v = sr.adam(p, m, v, t, g, lr, cfg)
+            p, m, v = ml.adam(p, m, v, t, g, lr, cfg)
             assert np.abs(leaf.detach().numpy() - p).max() <= 1e-12 * np.abs(p).max()
 
 
@@ -141,13 +142,13 @@ def test_random_problem_meets_its_conditions(net):
         assert 0.07 <= lo_share <= 0.12 and 0.05 <= hi_share <= (0.25 if net == "one_layer" else 0.15), (lo_share, hi_share)
         assert np.minimum(np.abs(raw + 20), np.abs(raw - 2)).min() >= 1e-3
         xin = np.concatenate([rows["obs"].astype(np.float64), pi["a"]], axis=1)
-        q1, q2 = sr.forward(t, "q1", Lq, xin)[1], sr.forward(t, "q2", Lq, xin)[1]
+        q1, q2 = ml.forward(t, "q1", Lq, xin)[1], ml.forward(t, "q2", Lq, xin)[1]
         assert np.abs(q1 - q2).min() >= 1e-4 * max(np.abs(q1).max(), np.abs(q2).max())
 
 
 @pytest.mark.parametrize("net", sorted(NETS))
 def test_forward_error_bounds_leave_a_quarter_of_the_margins(net):
-    """Each net's derived float32 forward-error bound (the layer recurrence of tests/test_gpu_ppo.py, sac_ref.fwd_err, on exact input rows)
+    """Each net's derived float32 forward-error bound (the layer recurrence of mlp_ref.fwd_err on exact input rows)
     is below a quarter of the margin random_problem keeps on its output: 1e-3 on the actor's raw log_std, 1e-4 max|Q| on Q1 and on Q2 at
     (obs, a_pi).  The recurrence is a worst-case sum; what the kernels lose is 0.001 to 0.01 of it (profiles/sac_parity.txt)."""
     asz, qsz = NETS[net]
@@ -158,11 +159,11 @@ def test_forward_error_bounds_leave_a_quarter_of_the_margins(net):
         rows = pb["rows"]
         pi = sr.head(t, La, rows["obs"], pb["eps_pi"])
         xin = np.concatenate([rows["obs"].astype(np.float64), pi["a"]], axis=1)
-        acts1, q1 = sr.forward(t, "q1", Lq, xin)
-        acts2, q2 = sr.forward(t, "q2", Lq, xin)
+        acts1, q1, _ = ml.forward(t, "q1", Lq, xin)
+        acts2, q2, _ = ml.forward(t, "q2", Lq, xin)
         qmax = max(np.abs(q1).max(), np.abs(q2).max())
-        e_ls = sr.fwd_err(t, "actor", La, pi["acts"])[:, NU:].max()
-        e_q = max(sr.fwd_err(t, "q1", Lq, acts1).max(), sr.fwd_err(t, "q2", Lq, acts2).max())
+        e_ls = ml.fwd_err(t, "actor", La, pi["acts"])[0][:, NU:].max()
+        e_q = max(ml.fwd_err(t, "q1", Lq, acts1)[0].max(), ml.fwd_err(t, "q2", Lq, acts2)[0].max())
         print("\n  %s, %d rows: log_std bound %.2e of 2.5e-4, Q bound %.2e of %.2e" % (net, n_rows, e_ls, e_q, 0.25e-4 * qmax))
         assert e_ls < 0.25 * 1e-3, e_ls
         assert e_q < 0.25 * 1e-4 * qmax, (e_q, qmax)
