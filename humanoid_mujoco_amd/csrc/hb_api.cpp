@@ -149,6 +149,7 @@ hb_batch* hb_batch_create(const hb_model* m, int n_env, int device, char* err, i
   std::string e;
   if (!build_device_model(m->m, b->D, e)) { set_err(err, err_sz, e); delete b; return nullptr; }
   const DevModel& dm = b->D.dm;
+  b->env_nobs = dm.nobs;  // (until hb_env_obs_extend widens the adapter's rows)
   bool ok = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming) == hipSuccess;
   // (the pipes' streams are created when hb_batch_pipeline asks for them: the runtime maps streams
@@ -418,6 +419,8 @@ int hb_kinematics_states(hb_batch* b, const float* qpos, const float* qvel, int 
 int hb_ray_configure(hb_batch* b, const hb_ray_spec* spec, const float* pnt, const float* vec, int n_ray) {
   if (!b) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
+  // while the scan is part of the observation (hb_env_obs_extend) the rays may move, their number may not: every row is sized by it
+  if (b->obs_ext.height_scan && (!spec || n_ray != b->n_ray || !(spec->cutoff > 0.f))) return HB_EINVAL;
   if (!spec || n_ray == 0) {  // remove: rays in flight (hb_rays_dev) read the buffers until the stream has run dry
     HB_HIP(hipStreamSynchronize(main_stream(b)));
     b->n_ray = 0;
@@ -459,9 +462,8 @@ int hb_ray_configure(hb_batch* b, const hb_ray_spec* spec, const float* pnt, con
   b->n_ray = n_ray;
   return HB_OK;
 }
-int hb_rays_dev(hb_batch* b, float* dist_dev, int* geomid_dev) {
-  if (!b || (!dist_dev && !geomid_dev) || b->n_ray < 1) return HB_EINVAL;
-  HB_HIP(hipSetDevice(b->device));
+// the poses the installed rays need and the ray kernel, on the batch's stream: A's outputs (and mask, transform) are the caller's
+static int rays_launch(hb_batch* b, RayArgs A) {
   const hipStream_t stream = main_stream(b);  // (held step calls launched, pipes joined: the rays see the state they leave)
   const DevModel& dm = b->D.dm;
   const bool framed = b->ray_spec.frame != HB_RAY_FRAME_WORLD;
@@ -472,17 +474,38 @@ int hb_rays_dev(hb_batch* b, float* dist_dev, int* geomid_dev) {
                                      b->ray_moving ? d_geom : nullptr, stream);
     if (rc != HB_OK) return rc;
   }
-  RayArgs A;
-  memset(&A, 0, sizeof A);
   A.pnt = b->d_ray; A.vec = b->d_ray + 3 * (size_t)b->n_ray; A.geoms = b->d_ray_geoms;
   A.n_ray = b->n_ray; A.n_geom = b->ray_ngeom; A.n_env = b->n_env;
   A.frame = b->ray_spec.frame; A.frame_body = b->ray_spec.frame_body; A.cutoff = b->ray_spec.cutoff;
   A.body_pose = framed ? d_body : nullptr; A.geom_pose = b->ray_moving ? d_geom : nullptr;
   A.dr = b->d_dr; A.dr_stride = b->dr_stride; A.has_hfield = b->ray_hfield ? 1 : 0;
-  A.dist = dist_dev; A.geomid = geomid_dev;
   HB_HIP(launch_rays(b->D.d_dm, dm, A, stream, &b->last_kernel));
   return HB_OK;
 }
+int hb_rays_dev(hb_batch* b, float* dist_dev, int* geomid_dev) {
+  if (!b || (!dist_dev && !geomid_dev) || b->n_ray < 1) return HB_EINVAL;
+  HB_HIP(hipSetDevice(b->device));
+  RayArgs A;
+  memset(&A, 0, sizeof A);
+  A.dist = dist_dev; A.geomid = geomid_dev;
+  return rays_launch(b, A);
+}
+extern "C++" {
+namespace hb {
+int rays_scan_launch(hb_batch* b, const uint8_t* mask, float* out, int stride, int col) {
+  if (b->n_ray < 1 || !b->obs_ext.height_scan) return HB_EINVAL;
+  RayArgs A;
+  memset(&A, 0, sizeof A);
+  A.dist = out; A.env_mask = mask;
+  A.xform = 1; A.out_stride = stride; A.out_col = col;
+  A.x_offset = b->obs_ext.scan_offset; A.x_scale = b->obs_ext.scan_scale; A.x_lo = b->obs_ext.scan_lo; A.x_hi = b->obs_ext.scan_hi;
+  const char* name = b->last_kernel;  // (hb_last_kernel goes on naming the step kernel of the env step this is part of)
+  const int rc = rays_launch(b, A);
+  b->last_kernel = name;
+  return rc;
+}
+}  // namespace hb
+}  // extern "C++"
 int hb_rays(hb_batch* b, float* dist, int* geomid) {
   if (!b || (!dist && !geomid) || b->n_ray < 1) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));

@@ -15,7 +15,8 @@ static int env_alloc(hb_batch* b) {
   const size_t nu = std::max(1, dm.nu);
   // one record [obs n x nobs | reward n | terminated n | truncated n]: a host that keeps its four buffers in the same order and
   // back to back (engine.py does) gets them in one transfer instead of four
-  int rc = b->d_record.alloc(n * dm.nobs * sizeof(float) + n * sizeof(float) + 2 * n);
+  // (nobs: the adapter's row, the model's observation and what hb_env_obs_extend appends)
+  int rc = b->d_record.alloc(n * b->env_nobs * sizeof(float) + n * sizeof(float) + 2 * n);
   if (rc == HB_OK) rc = b->d_prev.alloc(n * nu, /*zero=*/true);
   if (rc == HB_OK) rc = b->d_latest.alloc(n * nu, /*zero=*/true);
   if (rc == HB_OK) rc = b->d_action.alloc(n * nu);
@@ -24,7 +25,7 @@ static int env_alloc(hb_batch* b) {
   if (rc == HB_OK) rc = b->d_seen.alloc(n, /*zero=*/true);
   if (rc != HB_OK) { reset_all(b->d_record, b->d_prev, b->d_latest, b->d_action, b->d_qfrc, b->d_episode, b->d_seen); return rc; }
   b->d_obs = reinterpret_cast<float*>(b->d_record.get());
-  b->d_reward = b->d_obs + n * dm.nobs;
+  b->d_reward = b->d_obs + n * b->env_nobs;
   b->d_term = reinterpret_cast<uint8_t*>(b->d_reward + n);
   b->d_trunc = b->d_term + n;
   hb_env_config def;
@@ -44,6 +45,22 @@ static int env_eval(hb_batch* b, bool allow_reset, bool observe, const uint8_t* 
   const float* src = b->D.d_qpos_src + (cfg.reset_keyframe < 0 || cfg.reset_keyframe >= m.nkey ? 0 : (size_t)(1 + cfg.reset_keyframe) * m.nq);
   EnvRandState S = b->rs;
   if (!b->rand_on) memset(&S, 0, sizeof S);
+  if (b->n_ext > 0) {
+    // the extended row: the scan is cast here, at the state the step left (an episode that ends below ends in it, over the elevations
+    // it was run on); the env kernel appends the last action and the scan to the rows it writes; the envs it resets get the scan of
+    // their new state, over their new elevations, from a second cast masked to them
+    const bool scan = b->obs_ext.height_scan != 0;
+    ObsExtArgs X;
+    memset(&X, 0, sizeof X);
+    X.stride = b->env_nobs; X.n_act = b->obs_ext.prev_action ? b->D.dm.nu : 0; X.n_scan = scan ? b->n_ray : 0;
+    X.scan = b->d_ext_scan; X.reset_flag = scan && cfg.auto_reset ? b->d_ext_reset.get() : nullptr;
+    int rc = scan ? rays_scan_launch(b, nullptr, b->d_ext_scan, b->n_ray, 0) : HB_OK;
+    if (rc != HB_OK) return rc;
+    HB_HIP(launch_env(b->D.dm, cfg, b->env_rand, S, b->d_state, b->d_qfrc, b->d_counts, b->d_prev, b->d_latest, src, b->d_episode, b->d_status, d_obs, d_reward,
+                      d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen, &X));
+    if (X.reset_flag) return rays_scan_launch(b, X.reset_flag, d_obs, b->env_nobs, b->D.dm.nobs + X.n_act);
+    return HB_OK;
+  }
   HB_HIP(launch_env(b->D.dm, cfg, b->env_rand, S, b->d_state, b->d_qfrc, b->d_counts, b->d_prev, b->d_latest, src, b->d_episode, b->d_status, d_obs, d_reward,
                     d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen));
   return HB_OK;
@@ -53,8 +70,8 @@ int hb_get_obs(hb_batch* b, float* obs, float* reward, uint8_t* terminated, uint
   if (!b || !obs) return HB_EINVAL;
   int rc = env_alloc(b);
   if (rc != HB_OK) return rc;
-  int n = b->n_env, nobs = b->D.dm.nobs;
-  if (reward || terminated || truncated) {
+  int n = b->n_env, nobs = b->env_nobs;
+  if (reward || terminated || truncated || b->n_ext > 0) {  // (an extended row is the env kernel's: hb_obs_kernel writes the base alone)
     rc = env_eval(b, false, false, nullptr, b->d_obs, b->d_reward, b->d_term, b->d_trunc);  // pure evaluation: no reset, no bookkeeping, true observation
     if (rc != HB_OK) return rc;
   } else {
@@ -258,6 +275,56 @@ int hb_env_get_domain_params(hb_batch* b, float* out) {
   return b->dr_stride;
 }
 
+// ---- observation extension: the last action and the configured height scan behind the model's observation
+
+int hb_env_nobs(hb_batch* b) { return b ? b->env_nobs : HB_EINVAL; }
+
+int hb_env_obs_extend(hb_batch* b, const hb_obs_ext* ext) {
+  if (!b) return HB_EINVAL;
+  // everything sized by the observation comes after this call
+  if (b->actor.layers >= 1 || b->critic.layers >= 1 || b->q[0].layers >= 1 || b->q[1].layers >= 1 || b->norm_on || b->learner.on || b->sac.on) return HB_EINVAL;
+  hb_obs_ext x;
+  memset(&x, 0, sizeof x);
+  if (ext) {
+    if (!std::isfinite(ext->scan_offset) || !std::isfinite(ext->scan_scale) || !std::isfinite(ext->scan_lo) || !std::isfinite(ext->scan_hi)) return HB_EINVAL;
+    x.prev_action = ext->prev_action != 0;
+    x.height_scan = ext->height_scan != 0;
+    if (x.height_scan) {
+      if (b->n_ray < 1 || !(b->ray_spec.cutoff > 0.f) || ext->scan_lo > ext->scan_hi) return HB_EINVAL;
+      x.scan_offset = ext->scan_offset; x.scan_scale = ext->scan_scale; x.scan_lo = ext->scan_lo; x.scan_hi = ext->scan_hi;
+    }
+  }
+  const int n_ext = (x.prev_action ? b->D.dm.nu : 0) + (x.height_scan ? b->n_ray : 0);
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a step still in flight writes the buffers that are replaced below)
+  // the scan's scratch first: a failure here leaves the batch as it was
+  DevBuf<float> scan;
+  DevBuf<uint8_t> flag;
+  if (x.height_scan && (scan.alloc((size_t)b->n_env * b->n_ray) != HB_OK || flag.alloc((size_t)b->n_env, /*zero=*/true) != HB_OK)) return HB_ENOMEM;
+  const int total = b->D.dm.nobs + n_ext;
+  if (total != b->env_nobs) {
+    // the record and the terminal-observation table have rows of the new width
+    const bool had_record = b->env_ready, had_term = (bool)b->d_term_obs;
+    DevBuf<uint8_t> record;
+    DevBuf<float> term;
+    const size_t n = b->n_env;
+    if (had_record && record.alloc(n * total * sizeof(float) + n * sizeof(float) + 2 * n) != HB_OK) return HB_ENOMEM;
+    if (had_term && term.alloc(n * total, /*zero=*/true) != HB_OK) return HB_ENOMEM;
+    if (had_record) {
+      b->d_record.swap(record);
+      b->d_obs = reinterpret_cast<float*>(b->d_record.get());
+      b->d_reward = b->d_obs + n * total;
+      b->d_term = reinterpret_cast<uint8_t*>(b->d_reward + n);
+      b->d_trunc = b->d_term + n;
+    }
+    if (had_term) b->d_term_obs.swap(term);
+  }
+  b->d_ext_scan.swap(scan);
+  b->d_ext_reset.swap(flag);
+  b->obs_ext = x; b->n_ext = n_ext; b->env_nobs = total;
+  return HB_OK;
+}
+
 // CPUEnv._apply_action (+ pushes) -> n_substeps x mj_step -> reward / termination / observation, for every env or those of `mask`
 static int env_step_impl(hb_batch* b, const float* action_dev, int n_substeps, const uint8_t* mask, bool allow_reset, float* obs_dev, float* reward_dev,
                          uint8_t* terminated_dev, uint8_t* truncated_dev) {
@@ -317,7 +384,7 @@ int hb_env_reset(hb_batch* b, float* obs) {
   // the observation the reference returns from reset(): one more pass through the noise and delay lines
   rc = env_eval(b, false, true, nullptr, b->d_obs, b->d_reward, b->d_term, b->d_trunc);
   if (rc != HB_OK) return rc;
-  HB_HIP(hipMemcpyAsync(obs, b->d_obs, n * b->D.dm.nobs * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  HB_HIP(hipMemcpyAsync(obs, b->d_obs, n * b->env_nobs * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   return HB_OK;
 }
@@ -333,7 +400,7 @@ static int env_step_host(hb_batch* b, const float* action, int n_substeps, float
   if (!b || !action || !obs || !reward || !terminated || !truncated) return HB_EINVAL;
   int rc = env_alloc(b);
   if (rc != HB_OK) return rc;
-  int n = b->n_env, nu = b->D.dm.nu, nobs = b->D.dm.nobs;
+  int n = b->n_env, nu = b->D.dm.nu, nobs = b->env_nobs;
   if (nu) HB_HIP(hipMemcpyAsync(b->d_action, action, (size_t)n * nu * sizeof(float), hipMemcpyHostToDevice, main_stream(b)));
   rc = hb_env_step_dev(b, b->d_action, n_substeps, b->d_obs, b->d_reward, b->d_term, b->d_trunc);
   if (rc != HB_OK) return rc;
@@ -354,9 +421,9 @@ int hb_env_terminal_obs(hb_batch* b, float* terminal_obs) {
   int rc = env_alloc(b);
   if (rc != HB_OK) return rc;
   HB_HIP(hipSetDevice(b->device));
-  const size_t bytes = (size_t)b->n_env * b->D.dm.nobs * sizeof(float);
+  const size_t bytes = (size_t)b->n_env * b->env_nobs * sizeof(float);
   if (!b->d_term_obs) {  // first call: from the next hb_env_step on the env kernel records them
-    if (b->d_term_obs.alloc((size_t)b->n_env * b->D.dm.nobs) != HB_OK) return HB_ENOMEM;
+    if (b->d_term_obs.alloc((size_t)b->n_env * b->env_nobs) != HB_OK) return HB_ENOMEM;
     HB_HIP(hipMemsetAsync(b->d_term_obs, 0, bytes, main_stream(b)));
   }
   if (terminal_obs) {
@@ -479,7 +546,7 @@ int hb_actor_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* c
   const int nu = b->D.dm.nu;
   if (cfg->head != HB_ACTOR_DETERMINISTIC && cfg->head != HB_ACTOR_GAUSSIAN && cfg->head != HB_ACTOR_SQUASHED) return HB_EINVAL;
   if (nu < 1 || nu > kActorMaxNu) return HB_EINVAL;
-  if (sizes[0] != b->D.dm.nobs || sizes[n_layers] != (cfg->head == HB_ACTOR_SQUASHED ? 2 * nu : nu)) return HB_EINVAL;
+  if (sizes[0] != b->env_nobs || sizes[n_layers] != (cfg->head == HB_ACTOR_SQUASHED ? 2 * nu : nu)) return HB_EINVAL;
   if (cfg->head == HB_ACTOR_GAUSSIAN) for (int i = 0; i < nu; i++) if (!std::isfinite(cfg->log_std[i])) return HB_EINVAL;
   for (int l = 0; l <= n_layers; l++) if (sizes[l] > 256) return HB_EUNSUPPORTED;  // (the fused kernel's LDS tiles; no layer-by-layer fallback)
   int rc = env_alloc(b);
@@ -506,7 +573,7 @@ static int collect_impl(hb_batch* b, int T, int n_substeps, const hb_collect_out
   if (rc != HB_OK) return rc;
   HB_HIP(hipSetDevice(b->device));
   const DevModel& dm = b->D.dm;
-  const size_t n = b->n_env, nu = dm.nu, nobs = dm.nobs;
+  const size_t n = b->n_env, nu = dm.nu, nobs = b->env_nobs;
   if (out->terminal_obs && !b->d_term_obs && (rc = hb_env_terminal_obs(b, nullptr)) != HB_OK) return rc;
   if ((rc = learner_sync_log_std(b)) != HB_OK) return rc;  // (a learner's Adam steps moved log_std on the device: hb_ppo_adam_dev)
   ActorDesc ad;
@@ -554,7 +621,7 @@ int hb_env_collect_dev(hb_batch* b, int T, int n_substeps, const hb_collect_out*
 
 int hb_critic_set_mlp(hb_batch* b, int n_layers, const int* sizes, const float* const* weights, const float* const* biases) {
   if (!b || !mlp_args_ok(n_layers, sizes, weights, biases)) return HB_EINVAL;
-  if (sizes[0] != b->D.dm.nobs || sizes[n_layers] != 1) return HB_EINVAL;
+  if (sizes[0] != b->env_nobs || sizes[n_layers] != 1) return HB_EINVAL;
   for (int l = 0; l <= n_layers; l++) if (sizes[l] > 256) return HB_EUNSUPPORTED;  // (the fused kernel's LDS tiles; no layer-by-layer fallback)
   HB_HIP(hipSetDevice(b->device));
   HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a call still in flight reads the buffers that are replaced below)
@@ -676,7 +743,7 @@ int hb_norm_configure(hb_batch* b, const hb_norm_config* cfg) {
   if (cfg && (!std::isfinite(cfg->clip_obs) || !(cfg->clip_obs > 0.f) || !std::isfinite(cfg->clip_reward) || !(cfg->clip_reward > 0.f) ||
               !std::isfinite(cfg->epsilon) || !(cfg->epsilon > 0.f) || !std::isfinite(cfg->gamma) || cfg->gamma < 0.f || cfg->gamma > 1.f))
     return HB_EINVAL;
-  const int nobs = b->D.dm.nobs;
+  const int nobs = b->env_nobs;
   if (cfg && (nobs < 1 || nobs > kNormMaxObs)) return HB_EUNSUPPORTED;
   HB_HIP(hipSetDevice(b->device));
   if (!cfg) {
@@ -706,7 +773,7 @@ int hb_norm_configure(hb_batch* b, const hb_norm_config* cfg) {
 int hb_norm_get_stats(hb_batch* b, double* out) {
   if (!b || !out || !b->norm_on) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
-  const int nobs = b->D.dm.nobs;
+  const int nobs = b->env_nobs;
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   HB_HIP(hipMemcpy(out, b->d_norm_rec + (size_t)b->norm_k * norm_rec_doubles(nobs), (size_t)(2 * nobs + 4) * sizeof(double), hipMemcpyDeviceToHost));
   return HB_OK;
@@ -714,7 +781,7 @@ int hb_norm_get_stats(hb_batch* b, double* out) {
 
 int hb_norm_set_stats(hb_batch* b, const double* in) {
   if (!b || !in || !b->norm_on) return HB_EINVAL;
-  const int nobs = b->D.dm.nobs;
+  const int nobs = b->env_nobs;
   for (int i = 0; i < 2 * nobs + 4; i++) if (!std::isfinite(in[i])) return HB_EINVAL;
   for (int c = 0; c < nobs; c++) if (in[nobs + c] < 0.0) return HB_EINVAL;
   if (in[2 * nobs] < 0.0 || in[2 * nobs + 2] < 0.0 || in[2 * nobs + 3] < 0.0) return HB_EINVAL;
@@ -738,7 +805,7 @@ int hb_norm_get_env(hb_batch* b, double* disc_return, double* ep_return, int32_t
 int hb_norm_episode_totals(hb_batch* b, double out[4]) {
   if (!b || !out || !b->norm_on) return HB_EINVAL;
   HB_HIP(hipSetDevice(b->device));
-  const int nobs = b->D.dm.nobs;
+  const int nobs = b->env_nobs;
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   HB_HIP(hipMemcpy(out, b->d_norm_rec + (size_t)b->norm_k * norm_rec_doubles(nobs) + 2 * nobs + 4, 4 * sizeof(double), hipMemcpyDeviceToHost));
   return HB_OK;
@@ -749,7 +816,7 @@ static NormDesc norm_desc(hb_batch* b) {
   const hb_norm_config& c = b->norm_cfg;
   NormDesc d;
   memset(&d, 0, sizeof d);
-  d.nobs = b->D.dm.nobs;
+  d.nobs = b->env_nobs;
   d.norm_obs = c.norm_obs != 0; d.norm_reward = c.norm_reward != 0;
   d.k = b->norm_k;
   d.clip_obs = c.clip_obs; d.clip_reward = c.clip_reward; d.gamma = (double)c.gamma; d.epsilon = (double)c.epsilon;

@@ -58,7 +58,11 @@ class DevBuf {
     if (p_) return HB_OK;
     if (hipMalloc((void**)&p_, n * sizeof(T)) != hipSuccess) { p_ = nullptr; return HB_ENOMEM; }
     cap_ = n;
-    if (zero) HB_HIP(hipMemset(p_, 0, n * sizeof(T)));
+    if (zero) {
+      // (the fill runs on the null stream, which a batch's non-blocking stream does not wait for: it is complete before anyone launches)
+      HB_HIP(hipMemset(p_, 0, n * sizeof(T)));
+      HB_HIP(hipStreamSynchronize(nullptr));
+    }
     return HB_OK;
   }
   // grow only: room for n elements; a buffer that has to grow loses its contents, and is empty when that fails
@@ -67,6 +71,8 @@ class DevBuf {
     reset();
     return alloc(n);
   }
+  // trades allocations with another owner: a replacement is built aside and swapped in once nothing can fail any more
+  void swap(DevBuf& o) { std::swap(p_, o.p_); std::swap(cap_, o.cap_); }
 
  private:
   T* p_ = nullptr;
@@ -321,6 +327,13 @@ struct hb_batch {
   hb_ray_spec ray_spec = {};
   int n_ray = 0, ray_ngeom = 0;                  // n_ray 0: nothing configured
   bool ray_moving = false, ray_hfield = false;   // a geom of a moving body / a height field is among the eligible geoms
+  // observation extension (hb_env_obs_extend): env_nobs is the width of every row the adapter produces and every consumer of them is
+  // sized by, D.dm.nobs (the base, which the policy kernels and compute_obs keep) + n_ext; the scan cast before the env kernel,
+  // [n_env][n_ray], and the envs the env kernel reset, [n_env], for the masked second cast; both null without a scan
+  hb_obs_ext obs_ext = {};
+  int env_nobs = 0, n_ext = 0;
+  DevBuf<float> d_ext_scan;
+  DevBuf<uint8_t> d_ext_reset;
   DevBuf<int> d_episode;
   int env_offset = 0;
   // realism layer (hb_env_randomize)
@@ -428,5 +441,8 @@ int learner_net_replaced(hb_batch* b, int net, bool shapes_same);
 int learner_activation_changed(hb_batch* b);
 // both learners (hb_learn_host.cpp): the batch's device current and nothing in flight on its stream
 int learner_idle(hb_batch* b);
+// the installed rays as the scan of the observation extension (hb_api.cpp): the poses they need, then the ray kernel with the extension's
+// transform, for every env or those of `mask`, into out[env * stride + col + ray]; hb_last_kernel stays what it was
+int rays_scan_launch(hb_batch* b, const uint8_t* mask, float* out, int stride, int col);
 }  // namespace hb
 #pragma GCC visibility pop

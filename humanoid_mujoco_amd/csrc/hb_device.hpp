@@ -719,6 +719,21 @@ struct RayArgs {
   int has_hfield;          // a height field is among the geoms
   float* dist;             // [n_env][n_ray], nullable
   int* geomid;             // [n_env][n_ray], nullable
+  // the scan of the env adapter's observation extension (hb_env_obs_extend); all zero for hb_rays*:
+  const uint8_t* env_mask; // nullable [n_env]: only the envs whose byte is set are cast (a block is one env: the others return at once)
+  int xform;               // 1: dist receives clamp(x_scale * (x_offset - d), x_lo, x_hi), d = the distance, or cutoff where nothing is hit,
+  int out_stride, out_col; //    at dist[env * out_stride + out_col + ray]: straight into a row of a wider table
+  float x_offset, x_scale, x_lo, x_hi;
+};
+// what the env kernel appends to the base observation (hb_env_obs_extend): rows of `stride` floats, [ base (M.nobs) | the env's last
+// action (n_act: nu or 0) | scan (n_scan) ].  scan: [n_env][n_scan], cast at the state the env kernel is handed (before any reset): it
+// goes into the terminal row of an env that resets and into the observation row of every other one; the scan columns of an env that
+// resets are left to a second, masked ray launch behind the env kernel, which reads reset_flag [n_env] (1: reset in this launch).
+// Without an extension: stride = M.nobs, everything else 0.
+struct ObsExtArgs {
+  int stride, n_act, n_scan;
+  const float* scan;
+  uint8_t* reset_flag;
 };
 constexpr int kAccPark = 24;  // floats per body in BatchPtrs::body_acc_park (six 16-byte moves)
 

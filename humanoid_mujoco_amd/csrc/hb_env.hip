@@ -465,7 +465,8 @@ __device__ __forceinline__ float env_lane_sum(float x) {
 }
 __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const EnvConfig cfg, const EnvRand R, const EnvRandState S, float* state, const float* qfrc, const int* counts,
                               float* prev, float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated,
-                              uint8_t* truncated, const uint8_t* mask, int observe, const DomainRand D, float* dr, int dr_stride, int n_env, int env_offset, float* term_obs, int* seen) {
+                              uint8_t* truncated, const uint8_t* mask, int observe, const DomainRand D, float* dr, int dr_stride, int n_env, int env_offset, float* term_obs, int* seen,
+                              const ObsExtArgs X) {
   extern __shared__ float sh_state[];
   const int grp = threadIdx.x / kEnvLanes, l = threadIdx.x % kEnvLanes;
   const int e = blockIdx.x * (256 / kEnvLanes) + grp;
@@ -557,9 +558,12 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
   // infos[i]["terminal_observation"] (DummyVecEnv.step_wait; SAC / PPO bootstrap from it when the episode was truncated) - the same sensor
   // model, noise and delays as any other observation of that episode (CPUEnv.step returns self._get_obs() before anything resets)
   if (reset && term_obs) {
-    float* to = term_obs + (size_t)e * M.nobs;
+    float* to = term_obs + (size_t)e * X.stride;
     if (rand_on && observe) envrand_observe(M, R, S, e, env_offset + e, ep, ls, to, l, kEnvLanes);
     else compute_obs(M, ls, to, l, kEnvLanes);
+    // the extension of the state the episode ends in: the action just applied, the scan before the reset (over the old elevations)
+    for (int i = l; i < X.n_act; i += kEnvLanes) to[M.nobs + i] = latest[(size_t)e * M.nu + i];
+    for (int i = l; i < X.n_scan; i += kEnvLanes) to[M.nobs + X.n_act + i] = X.scan[(size_t)e * X.n_scan + i];
   }
   __syncthreads();  // (every lane has read the old state and the old episode number)
   if (reset) {
@@ -580,10 +584,15 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
   __syncthreads();  // the new state (LDS) and the new episode's delays (global, written by lane 0) are visible to the env's lanes
   if (active) {
     if (reset) for (int i = l; i < M.nstate; i += kEnvLanes) s[i] = ls[i];
-    float* o = obs + (size_t)e * M.nobs;
+    float* o = obs + (size_t)e * X.stride;
     if (rand_on && observe) envrand_observe(M, R, S, e, env_offset + e, ep, ls, o, l, kEnvLanes);
     else compute_obs(M, ls, o, l, kEnvLanes);
+    // the extension (no noise, no delay): the last action - zero in a new episode: this lane cleared these very entries above -, and the
+    // scan of an env that goes on; an env that was reset gets its scan from the masked ray launch behind this kernel
+    for (int i = l; i < X.n_act; i += kEnvLanes) o[M.nobs + i] = latest[(size_t)e * M.nu + i];
+    if (!reset) for (int i = l; i < X.n_scan; i += kEnvLanes) o[M.nobs + X.n_act + i] = X.scan[(size_t)e * X.n_scan + i];
   }
+  if (X.reset_flag && e < n_env && l == 0) X.reset_flag[e] = reset ? 1 : 0;
 }
 
 // hb_env_reset's collision test (cpu_env.py:411-414): envs of the mask that collide (mode 1: any contact, mode 2:
@@ -736,11 +745,13 @@ hipError_t launch_action(const float* action, float* prev, float* latest, float*
 }
 hipError_t launch_env(const DevModel& M, const EnvConfig& cfg, const EnvRand& R, const EnvRandState& S, float* state, const float* qfrc, const int* counts, float* prev,
                       float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated,
-                      const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs, int* seen) {
+                      const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs, int* seen,
+                      const ObsExtArgs* ext) {
   (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
   const int per_block = 256 / kEnvLanes;
+  const ObsExtArgs X = ext ? *ext : ObsExtArgs{M.nobs, 0, 0, nullptr, nullptr};  // (none: rows of the base observation alone)
   hipLaunchKernelGGL(hb_env_kernel, dim3((n_env + per_block - 1) / per_block), dim3(256), (size_t)per_block * ((M.nstate + 3) & ~3) * sizeof(float), stream, M, cfg, R, S, state, qfrc, counts, prev, latest, qpos_src, episode, status, obs,
-                     reward, terminated, truncated, mask, observe, D, dr, dr_stride, n_env, env_offset, term_obs, seen);
+                     reward, terminated, truncated, mask, observe, D, dr, dr_stride, n_env, env_offset, term_obs, seen, X);
   return hipGetLastError();
 }
 hipError_t launch_domain_rand(const DevModel& M, const DomainRand& D, float* dr, int stride, const int* episode, const uint8_t* mask, int n_env, int env_offset,

@@ -35,7 +35,7 @@ inline hipError_t launch_packed(const PackedKernel<Args> (&triple)[3], const Dev
   *kernel = K.name;
   return hipGetLastError();
 }
-// the configured rays against every env's geoms (hb_ray.hip; hb_rays*)
+// the configured rays against every env's geoms (hb_ray.hip; hb_rays*, and the scan of hb_env_obs_extend: RayArgs::xform)
 hipError_t launch_rays(const DevModel* M_dev, const DevModel& M, const RayArgs& A, hipStream_t stream, const char** kernel);
 // two envs per wave: a lean launch of the 27-dof humanoid's PGS kernel (hb_step_duo.hip; chosen by launch_step)
 hipError_t launch_step_duo(const DevModel* M_dev, const BatchPtrs& P, int nsteps, hipStream_t stream, const char** kernel);
@@ -54,7 +54,8 @@ hipError_t launch_obs(const DevModel& M, const float* state, float* obs, int n_e
 hipError_t launch_action(const float* action, float* prev, float* latest, float* ctrl, int n, hipStream_t stream);
 hipError_t launch_env(const DevModel& M, const EnvConfig& cfg, const EnvRand& R, const EnvRandState& S, float* state, const float* qfrc, const int* counts, float* prev,
                       float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated,
-                      const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs = nullptr, int* seen = nullptr);
+                      const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs = nullptr, int* seen = nullptr,
+                      const ObsExtArgs* ext = nullptr);  // ext null: rows of M.nobs floats, the base observation alone
 hipError_t launch_domain_rand(const DevModel& M, const DomainRand& D, float* dr, int stride, const int* episode, const uint8_t* mask, int n_env, int env_offset,
                               hipStream_t stream);
 hipError_t launch_policy(const DevModel& M, const PolicyDesc& pd, const float* state, float* ctrl, int n_env, hipStream_t stream);

@@ -1,6 +1,8 @@
 // hb_ray.hip - the ray read-out (hb_rays*, include/hb.h): mj_ray of every configured ray against every env's geoms, a pure function of
 // the geoms' world poses (the model's own for the world body, hb_kin.hip's read-out for the rest), the model and the env's elevations.
-// A kernel of its own: nothing of the batch is written and no step kernel carries anything for it.
+// A kernel of its own: nothing of the batch is written and no step kernel carries anything for it.  The same kernels cast the scan of the
+// env adapter's observation extension (hb_env_obs_extend): RayArgs::xform turns the distance into the observation's entry and writes it
+// into a row of a wider table, RayArgs::env_mask leaves out the envs that are not asked for.
 #include <hip/hip_runtime.h>
 #include "hb_kcommon.hpp"
 #include "hb_launch.hpp"
@@ -125,9 +127,10 @@ __device__ __forceinline__ float ray_hfield(const float* data, int nrow, int nco
 // garbage and nothing else: the only data-dependent indices are the grid cell's, and those are clamped.
 template <int LDS>
 __device__ __forceinline__ void ray_body(const DevModel* Mp, const RayArgs& A) {
+  const int env = (int)blockIdx.x;
+  if (A.env_mask && !A.env_mask[env]) return;  // (the same for every lane of the block: nobody is left waiting at the barrier below)
   DevModelRef M = *(const DevModel HB_CONST*)(uintptr_t)Mp;
   extern __shared__ float lds[];
-  const int env = (int)blockIdx.x;
   const int i = (int)(blockIdx.y * blockDim.x + threadIdx.x);
   const DomainLayout DL = domain_layout(M.nbody, M.nv, M.nlimcand, M.nu, M.nhfielddata);
   const float* hglobal = A.dr ? A.dr + (size_t)env * A.dr_stride + DL.o_hfield : (const float*)M.hfield_data;
@@ -178,6 +181,13 @@ __device__ __forceinline__ void ray_body(const DevModel* Mp, const RayArgs& A) {
     if (t < best) { best = t; bestg = g; }
   }
   if (bestg < 0 || !(best <= tmax)) { best = -1.f; bestg = -1; }  // (nothing hit, or only beyond the cutoff; a NaN is no hit)
+  if (A.xform) {
+    // the observation's scan entry: a subtract, a multiply, a clamp - each rounded on its own (numpy float32 gives the same bits)
+    const float d = best < 0.f ? A.cutoff : best;
+    const float v = __fmul_rn(A.x_scale, __fsub_rn(A.x_offset, d));
+    A.dist[(size_t)env * A.out_stride + A.out_col + i] = fminf(fmaxf(v, A.x_lo), A.x_hi);
+    return;
+  }
   const size_t at = (size_t)env * A.n_ray + i;
   if (A.dist) A.dist[at] = best;
   if (A.geomid) A.geomid[at] = bestg;
@@ -188,6 +198,7 @@ __global__ __launch_bounds__(kRayBlock) void hb_ray_lds_kernel(const DevModel* M
 hipError_t launch_rays(const DevModel* M_dev, const DevModel& M, const RayArgs& A, hipStream_t stream, const char** kernel) {
   (void)hipGetLastError();
   if (A.n_env < 1 || A.n_ray < 1 || A.n_ray > kRayMax) return hipErrorInvalidValue;
+  if (A.xform && (!A.dist || A.out_stride < A.out_col + A.n_ray || A.out_col < 0)) return hipErrorInvalidValue;
   const int threads = min(kRayBlock, (A.n_ray + kGroup - 1) / kGroup * kGroup);
   const dim3 grid((unsigned)A.n_env, (unsigned)((A.n_ray + threads - 1) / threads));  // (y: at most kRayMax / 64 blocks)
   if (A.has_hfield && M.nhfielddata <= kRayLdsFloats) {

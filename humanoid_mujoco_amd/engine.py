@@ -42,6 +42,12 @@ class HbSizes(ctypes.Structure):
                                             "npair", "nobs", "ncon_max", "nefc_max")]
 
 
+class HbObsExt(ctypes.Structure):
+    """hb_obs_ext (include/hb.h): what the env adapter appends to the model's observation."""
+    _fields_ = [("prev_action", ctypes.c_int), ("height_scan", ctypes.c_int), ("scan_offset", ctypes.c_float), ("scan_scale", ctypes.c_float),
+                ("scan_lo", ctypes.c_float), ("scan_hi", ctypes.c_float)]
+
+
 class HbRaySpec(ctypes.Structure):
     """hb_ray_spec (include/hb.h): frame, eligible geoms and cutoff of the installed rays."""
     _fields_ = [("frame", ctypes.c_int), ("frame_body", ctypes.c_int), ("bodyexclude", ctypes.c_int), ("flags", ctypes.c_int), ("cutoff", ctypes.c_float)]
@@ -393,6 +399,8 @@ def lib():
     L.hb_env_step.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     L.hb_env_step_async.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     L.hb_env_step_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+    L.hb_env_obs_extend.argtypes = [vp, ctypes.POINTER(HbObsExt)]
+    L.hb_env_nobs.argtypes = [vp]
     L.hb_policy_set_mlp.argtypes = [vp, ci, vp, vp, vp]
     L.hb_policy_eval.argtypes = [vp, vp]
     L.hb_rollout_policy.argtypes = [vp, ci, vp]
@@ -912,7 +920,7 @@ class Batch:
         return self.get_state(STATE_TIME)[:, 0]
 
     def obs(self, want_reward=True):
-        o = np.zeros((self.n_env, self.model.nobs), dtype=np.float32)
+        o = np.zeros((self.n_env, self.env_nobs), dtype=np.float32)
         r = np.zeros(self.n_env, dtype=np.float32) if want_reward else None
         te = np.zeros(self.n_env, dtype=np.uint8)
         tr = np.zeros(self.n_env, dtype=np.uint8)
@@ -1258,8 +1266,32 @@ class Batch:
         _check(min(0, lib().hb_env_get_domain_params(self._h, _ptr(out))), "hb_env_get_domain_params")
         return out
 
+    @property
+    def env_nobs(self):
+        """the width of every observation row the env adapter produces: the model's nobs and what obs_extend appended (hb_env_nobs)"""
+        return int(lib().hb_env_nobs(self._h))
+
+    def obs_extend(self, prev_action=False, height_scan=None):
+        """Appends to every observation of the env adapter, on the device (hb_env_obs_extend): prev_action - the nu entries of the action
+        the env last applied (zero after a reset); height_scan=dict(offset=0.0, scale=1.0, clip=(lo, hi)) - one entry per installed ray
+        (ray_configure, with a cutoff > 0), clamp(scale * (offset - d), lo, hi) with d the ray's distance, or the cutoff where nothing is
+        hit.  Row layout [model nobs | prev_action | scan]; env_nobs is the new width.  Call it before anything sized by the observation
+        is installed (actor, critic, Q networks, normaliser, learners); obs_extend() with nothing on removes the extension.  A call that
+        is refused (HbError) changes nothing."""
+        x = HbObsExt(1 if prev_action else 0, 0, 0.0, 1.0, 0.0, 0.0)
+        if height_scan is not None:
+            hs = dict(height_scan)
+            lo, hi = hs.pop("clip", (-3.0e38, 3.0e38))
+            x.height_scan, x.scan_offset, x.scan_scale, x.scan_lo, x.scan_hi = 1, float(hs.pop("offset", 0.0)), float(hs.pop("scale", 1.0)), float(lo), float(hi)
+            if hs:
+                raise TypeError("obs_extend: unknown height_scan option(s) %s" % sorted(hs))
+        rc = lib().hb_env_obs_extend(self._h, ctypes.byref(x))
+        _check(rc, "hb_env_obs_extend", "call it before an actor, critic, Q network, normaliser or learner is installed; height_scan needs rays "
+               "installed with a cutoff > 0, finite parameters and clip lo <= hi" if rc == -1 else None)
+        self._env_pin = None  # (the transfer record of env_step has rows of the old width)
+
     def env_reset(self):
-        o = np.zeros((self.n_env, self.model.nobs), dtype=np.float32)
+        o = np.zeros((self.n_env, self.env_nobs), dtype=np.float32)
         _check(lib().hb_env_reset(self._h, _ptr(o)), "hb_env_reset")
         return o
 
@@ -1270,7 +1302,7 @@ class Batch:
         wait=False: enqueue only (hb_env_step_async) and return None; sync(), then env_step_result()."""
         pin = getattr(self, "_env_pin", None)
         if pin is None:
-            n, nobs = self.n_env, self.model.nobs
+            n, nobs = self.n_env, self.env_nobs
             ob, rb = n * nobs * 4, n * 4
             out = _Pinned((ob + rb + 2 * n,), np.uint8)
             pin = self._env_pin = dict(a=_Pinned((n, self.model.nu), np.float32), out=out,
@@ -1318,7 +1350,7 @@ class Batch:
         if not fetch:
             _check(lib().hb_env_terminal_obs(self._h, None), "hb_env_terminal_obs")
             return None
-        out = np.zeros((self.n_env, self.model.nobs), dtype=np.float32)
+        out = np.zeros((self.n_env, self.env_nobs), dtype=np.float32)
         _check(lib().hb_env_terminal_obs(self._h, _ptr(out)), "hb_env_terminal_obs")
         return out
 
@@ -1638,13 +1670,13 @@ class Batch:
 
     def norm_stats(self):
         """the flat fp64 record obs_mean[nobs] | obs_var[nobs] | obs_count | ret_mean | ret_var | ret_count (hb_norm_get_stats)"""
-        out = np.zeros(2 * self.model.nobs + 4, dtype=np.float64)
+        out = np.zeros(2 * self.env_nobs + 4, dtype=np.float64)
         _check(lib().hb_norm_get_stats(self._h, _ptr(out)), "hb_norm_get_stats", "no normaliser configured")
         return out
 
     def norm_set_stats(self, record):
         a = np.ascontiguousarray(record, dtype=np.float64)
-        if a.shape != (2 * self.model.nobs + 4,):
+        if a.shape != (2 * self.env_nobs + 4,):
             raise ValueError("norm_set_stats: the record holds 2 nobs + 4 values")
         _check(lib().hb_norm_set_stats(self._h, _ptr(a)), "hb_norm_set_stats", "needs a normaliser, finite values, and no negative var or count")
 

@@ -9,10 +9,16 @@ class ReplayBuffer:
     With VecEnv(normalize=...) the ring holds the normalised tapes as collected; stable-baselines3 stores raw values and normalises on
     sampling, which this buffer does not do."""
 
-    def __init__(self, capacity, nobs, nu, device="cpu"):
+    def __init__(self, capacity, nobs, nu=None, device="cpu"):
+        """nobs: the width of an observation row, or the VecEnv the transitions come from - the buffer then takes its widths from the
+        env (env.nobs, the model's observation and what obs_extend appends, and the model's nu)"""
         import torch
         if capacity < 1:
             raise ValueError("ReplayBuffer: capacity must be at least 1")
+        if hasattr(nobs, "nobs"):
+            nobs, nu = nobs.nobs, (nobs.model.nu if nu is None else nu)
+        if nu is None:
+            raise TypeError("ReplayBuffer: nu is required with a numeric nobs")
         self.capacity, self.nobs, self.nu = int(capacity), int(nobs), int(nu)
         self.device = torch.device(device)
         f32 = dict(dtype=torch.float32, device=self.device)

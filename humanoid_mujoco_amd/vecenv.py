@@ -50,7 +50,7 @@ _NO_INFO = {}  # (shared by the envs that did not finish an episode this step: S
 
 class VecEnv:
     def __init__(self, model, n_envs, device=0, n_substeps=1, randomization_factor=1.0, realism=False, domain_randomization=False, seed=0, team=False,
-                 contact_forces=False, body_accelerations=False, height_scan=None, normalize=None, **reward_overrides):
+                 contact_forces=False, body_accelerations=False, height_scan=None, normalize=None, obs_extend=None, **reward_overrides):
         """realism=True adds CPUEnv's sensor/action noise, delay FIFOs and pushes (hb_env_randomization), scaled by
         randomization_factor exactly like the reset perturbation; domain_randomization=True draws per-env masses, floor
         friction, joint and actuator parameters at every reset (hb_domain_randomization).  team=True: the reference's own
@@ -59,7 +59,14 @@ class VecEnv:
         body_contact_forces(); such steps run the full step kernel.  body_accelerations=True: likewise every body's acceleration
         (hb_body_acc_readout), read with body_accelerations().  height_scan=dict(body=..., xs=..., ys=..., z0=1.0, cutoff=2 * z0): a grid
         of downward rays from z0 above `body` (id or name) at the offsets xs (forward) x ys (left) of its heading frame, at the geoms of the
-        world body only (hb_ray_configure: yaw frame, static), read with height_scan() / height_scan_torch(); the observation is unchanged.
+        world body only (hb_ray_configure: yaw frame, static), read with height_scan() / height_scan_torch(); the observation is unchanged
+        unless obs_extend asks for the scan.
+        obs_extend=dict(prev_action=True, height_scan=dict(offset=z0, scale=1.0, clip=(lo, hi))) (any subset): every observation this
+        VecEnv produces - reset, step*, step_torch, the tapes of collect*, terminal observations - gains, behind the model's nobs entries,
+        the action the env last applied (zero after a reset) and one entry per ray of height_scan=..., clamp(scale * (offset - distance),
+        lo, hi) - with offset = z0 the terrain height relative to the body (hb_env_obs_extend); `nobs`, observation_shape and
+        obs_layout() describe the row, and actor, critic, Q networks, normaliser, learners and ReplayBuffer are sized by it.  Extension
+        entries carry no sensor noise and no delay.  obs_extend=None, or a dict with everything off: the observation is the model's.
         normalize=dict(norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8) (any subset; {} for the
         defaults): stable-baselines3's VecNormalize over a VecMonitor on the device (hb_norm_*): reset, step*, step_torch and collect*
         return normalised observations and rewards, finished envs' infos carry "episode": {"r", "l"} and a normalised
@@ -99,6 +106,21 @@ class VecEnv:
             pnt, vec = height_scan_rays(xs, ys, z0)
             self.batch.ray_configure(pnt, vec, frame="yaw", frame_body=body, static=True, moving=False, cutoff=cutoff)
             self._scan = (len(ys), len(xs), cutoff)
+        # the extension of the observation, ahead of everything that is sized by it (the terminal-observation table, the normaliser)
+        ext = dict(obs_extend or {})
+        ext_scan, ext_act = ext.pop("height_scan", None), bool(ext.pop("prev_action", False))
+        if ext:
+            raise TypeError("obs_extend: unknown option(s) %s" % sorted(ext))
+        if ext_scan is not None and self._scan is None:
+            raise ValueError("obs_extend: height_scan needs the VecEnv's height_scan=dict(body=..., xs=..., ys=...)")
+        if ext_act or ext_scan is not None:
+            self.batch.obs_extend(prev_action=ext_act, height_scan=ext_scan)
+        self.nobs = self.batch.env_nobs
+        self._layout = {"base": slice(0, self.model.nobs)}
+        if ext_act:
+            self._layout["prev_action"] = slice(self.model.nobs, self.model.nobs + self.model.nu)
+        if ext_scan is not None:
+            self._layout["height_scan"] = slice(self.nobs - self._scan[0] * self._scan[1], self.nobs)
         self.realism = None
         if realism:
             self.realism = self.batch.env_default_randomization()
@@ -115,7 +137,7 @@ class VecEnv:
             self._apply_domain()
         # gymnasium-style space descriptions (cpu_env.py:56-63: Box(-1,1,(nu,)), Box(-10,10,(nobs,)))
         self.action_shape = (self.model.nu,)
-        self.observation_shape = (self.model.nobs,)
+        self.observation_shape = (self.nobs,)
         self.action_low, self.action_high = -1.0, 1.0
         self.action_space = Box(-1.0, 1.0, self.action_shape, seed=seed)
         self.observation_space = Box(-10.0, 10.0, self.observation_shape, seed=seed)
@@ -133,6 +155,11 @@ class VecEnv:
             self._training = True
             self._orig_obs = self._orig_reward = None
             self.batch.norm_configure(training=True, **opts)
+
+    def obs_layout(self):
+        """the columns of an observation row as slices: "base" (the model's nobs entries), and with obs_extend "prev_action" (nu) and
+        "height_scan" (len(ys) * len(xs) entries, row-major over ys then xs like height_scan())"""
+        return dict(self._layout)
 
     # ---- VecNormalize's surface (normalize=...)
     def _need_norm(self, what):
@@ -155,7 +182,7 @@ class VecEnv:
         """the device block the host paths stage a step in: obs | reward | ep_return | ep_length | terminal_obs | terminated | truncated"""
         h = getattr(self, "_norm_dev", None)
         if h is None:
-            n, nobs = self.num_envs, self.model.nobs
+            n, nobs = self.num_envs, self.nobs
             ob, rb = n * nobs * 4, n * 4
             base = self.batch.dev_alloc(2 * ob + 3 * rb + 2 * n)
             h = self._norm_dev = dict(obs=base, reward=base + ob, ep_ret=base + ob + rb, ep_len=base + ob + 2 * rb, tobs=base + ob + 3 * rb,
@@ -172,7 +199,7 @@ class VecEnv:
     def _norm_step_host(self, obs, rew, term, trunc):
         """one normaliser step on host arrays: (obs, reward, ep_return, ep_length), and the normalised terminal observations kept for
         _sb3 when an env finished"""
-        h, n, nobs = self._norm_host(), self.num_envs, self.model.nobs
+        h, n, nobs = self._norm_host(), self.num_envs, self.nobs
         self._orig_obs, self._orig_reward = obs, rew
         done = term | trunc
         self.batch.to_dev(h["obs"], np.concatenate([np.ascontiguousarray(obs, np.float32).reshape(-1), np.ascontiguousarray(rew, np.float32)]))
@@ -190,7 +217,7 @@ class VecEnv:
     def normalize_obs(self, x):
         """VecNormalize.normalize_obs: x [..., nobs] (array or CUDA tensor) with the current statistics, no update (hb_norm_obs_dev)"""
         self._need_norm("normalize_obs")
-        nobs = self.model.nobs
+        nobs = self.nobs
         if isinstance(x, np.ndarray) or not hasattr(x, "data_ptr"):
             a = np.ascontiguousarray(x, dtype=np.float32)
             assert a.shape[-1] == nobs and a.size, a.shape
@@ -225,13 +252,13 @@ class VecEnv:
     def save_normalization(self, path):
         """VecNormalize.save: the flat statistics record (hb_norm_get_stats) as an .npz"""
         self._need_norm("save_normalization")
-        np.savez(path, record=self.batch.norm_stats(), nobs=self.model.nobs)
+        np.savez(path, record=self.batch.norm_stats(), nobs=self.nobs)
 
     def load_normalization(self, path):
         self._need_norm("load_normalization")
         with np.load(path if str(path).endswith(".npz") else str(path) + ".npz") as z:
-            if int(z["nobs"]) != self.model.nobs:
-                raise ValueError("load_normalization: the record is for %d observations, this model has %d" % (int(z["nobs"]), self.model.nobs))
+            if int(z["nobs"]) != self.nobs:
+                raise ValueError("load_normalization: the record is for %d observations, this env has %d" % (int(z["nobs"]), self.nobs))
             self.batch.norm_set_stats(z["record"])
 
     @property
@@ -449,7 +476,7 @@ class VecEnv:
         a = actions.contiguous()
         if getattr(self, "_t_out", None) is None:
             dev = a.device
-            self._t_out = (torch.empty((self.num_envs, self.model.nobs), dtype=torch.float32, device=dev), torch.empty(self.num_envs, dtype=torch.float32, device=dev),
+            self._t_out = (torch.empty((self.num_envs, self.nobs), dtype=torch.float32, device=dev), torch.empty(self.num_envs, dtype=torch.float32, device=dev),
                            torch.empty(self.num_envs, dtype=torch.uint8, device=dev), torch.empty(self.num_envs, dtype=torch.uint8, device=dev))
             self._t_stream = torch.cuda.ExternalStream(self.batch.stream, device=dev)  # the batch's own HIP stream, seen by torch
         assert a.dtype == torch.float32 and tuple(a.shape) == (self.num_envs, self.model.nu)
@@ -509,7 +536,7 @@ class VecEnv:
                 raise TypeError("collect: unknown gae option(s) %s" % sorted(gae))
             gae = True
             terminal_obs = terminal_obs or g_boot
-        n, nobs, nu = self.num_envs, self.model.nobs, self.model.nu
+        n, nobs, nu = self.num_envs, self.nobs, self.model.nu
         dev = torch.device("cuda", self._device)
         squashed = getattr(self.batch, "actor_head", None) == 2
         key = (T, bool(terminal_obs), squashed)

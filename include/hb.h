@@ -790,6 +790,42 @@ int hb_env_step_async(hb_batch* b, const float* action, int n_substeps, float* o
 /* Same with device pointers, asynchronous on the batch's stream (policy on the same GPU). */
 int hb_env_step_dev(hb_batch* b, const float* action_dev, int n_substeps, float* obs_dev, float* reward_dev, uint8_t* terminated_dev, uint8_t* truncated_dev);
 
+/* ---- observation extension: the last action and the height scan in every observation the adapter produces ------------------------ */
+
+/* Appends to the model's observation, on the device, what a perceptive policy needs beside it.  Every row the env adapter writes is then
+ *   [ base (the model's nobs) | prev_action (nu) | scan (n_ray) ]        hb_env_nobs floats; a part that is off is absent
+ *   prev_action  the action the env last applied - the adapter's `latest`, which the reward's control-change term reads: behind the
+ *                realism layer's action noise and delay where that is on; zero after a reset
+ *   scan         one entry per installed ray (hb_ray_configure), in ray order: clamp(scan_scale * (scan_offset - d), scan_lo, scan_hi),
+ *                d the ray's distance at the env's state, or the configuration's cutoff where nothing is hit.  With scan_offset = the
+ *                height the rays start above the body this is the terrain height relative to the body origin.  fp32: a subtract, a
+ *                multiply, a clamp, each rounded once (no fused multiply-add); d has the bits hb_rays gives at that state.
+ * The model's nobs does not change: hb_model queries, hb_policy_set_mlp, hb_policy_eval and hb_rollout_policy never go through the
+ * adapter and keep the base observation.  The base part keeps its realism layer (noise, delay lines) exactly; extension entries get
+ * NO noise and NO delay.
+ * Producers - all write rows of hb_env_nobs floats: hb_env_reset, hb_env_step, hb_env_step_async, hb_env_step_dev, hb_get_obs,
+ * hb_env_terminal_obs, hb_env_collect_dev and hb_env_collect_norm_dev with their obs, terminal_obs and raw_obs tapes.
+ * Consumers - all sized by hb_env_nobs: hb_actor_set_mlp and hb_critic_set_mlp (sizes[0]), hb_q_set_mlp (sizes[0] - nu), the
+ * normaliser's record with hb_norm_* (their existing limit applies: nobs <= 240), hb_collect_gae_dev, the PPO and SAC learners.
+ * An episode that ends with auto_reset on: the terminal observation carries the extension of the state the episode ended in - the
+ * action just applied and the scan at the pre-reset state, with terrain randomisation over the OLD elevations; the observation of the
+ * new episode carries a zero last action and the scan at the reset state over the NEW elevations.
+ * With a scan an evaluation of the envs is: the poses the rays need and the ray kernel at the post-step state, the env kernel, and - where
+ * envs may reset - the same two launches masked to the envs that did, writing straight into their observation rows.  Without an extension the
+ * adapter makes exactly the launches it made before and gives the same bits.  No atomics: a scan entry is a function of the env's
+ * state, its elevations and the ray alone.  hb_last_kernel goes on naming the step kernel.
+ * Order of calls: before anything sized by the observation is installed.  HB_EINVAL: an actor, critic, Q network, normaliser or learner
+ * exists; height_scan with no rays installed or with a ray configuration whose cutoff <= 0; scan_lo > scan_hi; a non-finite parameter.
+ * While the scan is part of the observation, hb_ray_configure with another n_ray, a cutoff <= 0 or a removal is refused with HB_EINVAL;
+ * the same n_ray with new rays is allowed.  A refused call changes nothing.  NULL or an all-zero struct removes the extension. */
+typedef struct hb_obs_ext {
+  int prev_action;        /* 1: append the nu entries of the action the env last applied (the adapter's `latest`; 0 after a reset) */
+  int height_scan;        /* 1: append one entry per installed ray (hb_ray_configure), in ray order */
+  float scan_offset, scan_scale, scan_lo, scan_hi;
+} hb_obs_ext;
+int hb_env_obs_extend(hb_batch* b, const hb_obs_ext* ext);   /* NULL or all-zero: remove */
+int hb_env_nobs(hb_batch* b);                                /* base nobs + extension */
+
 /* ---- policy in the loop (BASELINE.json configs[3]: MLP policy inference fused into the rollout loop) ---------- */
 
 /* Installs an MLP policy obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] == nu with tanh after every layer (hidden
