@@ -76,6 +76,19 @@ __device__ __forceinline__ void uv_copies(float x, float& u, float& v) {
   u = __uint_as_float(s.x);
   v = __uint_as_float(s.y);
 }
+// half_sums' two sums without the way through scalars: on EVERY lane the sum over the 32 lanes of the lane's own half.  After the four DPP
+// steps every lane of a DPP row holds its row's sum - each level adds the same two partial sums, in one order or the other, and the add is
+// commutative: the same bits on all 16 lanes.  The U / V copies of that then are the sums of the half's two rows, and U + V is
+// rdlane(v, base) + rdlane(v, base + 16).
+__device__ __forceinline__ float half_sums_all(float v) {
+  v += dpp_mov<0xB1>(v);
+  v += dpp_mov<0x4E>(v);
+  v += dpp_mov<0x141>(v);
+  v += dpp_mov<0x140>(v);
+  float u, w;
+  uv_copies(v, u, w);
+  return u + w;
+}
 // the half that starts at lane BASE (0 or 32) alone
 template <int BASE>
 __device__ __forceinline__ float half_sum(float v) {
@@ -1204,7 +1217,7 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
   "s_lshl_b64 %[m], %[m], 1\n\t"                                                     \
   HB_BCAST_FMAC(k)
 #define HB_PGS_CHUNKB(c, pre)                                                        \
-  if ((c) * 4 >= ne) break;                                                          \
+  if ((c) > 0 && (c) * 4 >= ne) break;                                               \
   {                                                                                  \
     float d_;                                                                        \
     asm volatile(pre HB_PGS_ROWB(0) HB_PGS_ROWB(1) HB_PGS_ROWB(2) HB_PGS_ROWB(3)     \
@@ -1250,43 +1263,54 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     HB_PGS_CHUNKWU(0, "s_nop 0\n\t") HB_PGS_CHUNKWU(1, "") HB_PGS_CHUNKWU(2, "") HB_PGS_CHUNKWU(3, "") \
     HB_PGS_CHUNKWV(4, HB_PGS_ROWSW_4) HB_PGS_CHUNKWV(5, HB_PGS_ROWSW_4) HB_PGS_CHUNKWV(6, HB_PGS_ROWSW_4) HB_PGS_CHUNKWV(7, HB_PGS_ROWSW_3) \
   } while (0)
-      // the end of a paired sweep, the same behind every form of the row step: the steps join the forces, then each env's convergence test
-      // (all in row layout: rres is the residual of the lane's own row)
-      auto paired_end = [&](float delta, float res0) {
+      // The end of a paired sweep, the same behind every form of the row step: the steps join the forces, then ONE convergence test for both
+      // envs (all in row layout: rres is the residual of the lane's own row).  Paired means split == 32, so each env's sum is that of its
+      // half (no test of `aligned`, no rotated sum), taken on every lane of the half (half_sums_all); the two multiplies and the compare run
+      // once for all lanes, and env A's verdict is the low word of the compare mask, env B's the high word.  Both envs have swept equally
+      // often (`niter`).  The common case, both envs go on, is one branch back to the first row step; what a stopping env needs is behind it.
+      int niter = 0;
+      unsigned long long stop = 0;
+      auto paired_end = [&](float delta, float res0) {  // true: both envs sweep on
         force += delta;
-        float iLo, iHi;
-        env_sums(delta * (res0 + rres), iLo, iHi);
-        niterLo++; niterHi++;
-        if (-0.5f * iLo * pgs_scale < pgs_tol || niterLo >= max_sweeps) {
+        const float improvement = half_sums_all(delta * (res0 + rres));
+        niter++;
+        stop = __builtin_amdgcn_ballot_w64(-0.5f * improvement * pgs_scale < pgs_tol);
+        return __builtin_expect(stop == 0 && niter < max_sweeps, 1);
+      };
+      // Loop-invariant and outside the loops: the row count, the test that there are rows (a live env has rows) and the zero of the steps -
+      // a sweep rewrites the step of exactly the lanes the sweep before it wrote.
+      if (liveLo && liveHi) {
+        int ne;
+        asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(nmax2));
+        float dl = 0.f, res0;
+        if (short16) {
+          do {
+            const float nforce = -force;
+            res0 = rres;
+            unsigned long long turn = 0x0000000100000001ull;  // the lanes whose turn it is: row 0 of both envs
+            HB_PGS_SWEEPB;
+            rres = res;
+          } while (paired_end(dl, res0));
+        } else {
+          do {
+            res0 = rres;
+            float nforce, nforceV;
+            uv_copies(-force, nforce, nforceV);
+            unsigned long long turn = 0x0000000100000001ull;
+            HB_PGS_SWEEPW;
+            rres = (lane & 16) ? resV : res;  // (the select at the end of a sweep is the next sweep's res0)
+          } while (paired_end(dl, res0));
+        }
+        niterLo = niterHi = niter;
+        const bool cap = niter >= max_sweeps;
+        if ((unsigned)stop != 0 || cap) {
           liveLo = false;
           if (!h) { force_out = force; res = 0.f; resV = 0.f; rres = 0.f; force = 0.f; }  // rows of a finished env are inert from here on
         }
-        if (-0.5f * iHi * pgs_scale < pgs_tol || niterHi >= max_sweeps) {
+        if ((unsigned)(stop >> 32) != 0 || cap) {
           liveHi = false;
           if (h) { force_out = force; res = 0.f; resV = 0.f; rres = 0.f; force = 0.f; }
         }
-      };
-      while (short16 && liveLo && liveHi) {
-        int ne;
-        asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(nmax2));
-        const float nforce = -force, res0 = rres;
-        float dl = 0.f;
-        unsigned long long turn = 0x0000000100000001ull;  // the lanes whose turn it is: row 0 of both envs
-        HB_PGS_SWEEPB;
-        rres = res;
-        paired_end(dl, res0);
-      }
-      while (wide && liveLo && liveHi) {
-        int ne;
-        asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(nmax2));
-        const float res0 = rres;
-        float nforce, nforceV;
-        uv_copies(-force, nforce, nforceV);
-        float dl = 0.f;
-        unsigned long long turn = 0x0000000100000001ull;
-        HB_PGS_SWEEPW;
-        rres = (lane & 16) ? resV : res;  // (the select at the end of a sweep is the next sweep's res0)
-        paired_end(dl, res0);
       }
       // ONE env still sweeps (the wave sweeps max(sA, sB) times, each env its own count).  The tail works in row layout: behind a wide paired
       // loop every lane takes its own row's column, nAinv and residual back (33 selects, once).  With at most 16 rows in the env that sweeps
@@ -1314,38 +1338,42 @@ __device__ __forceinline__ void step_duo(const DevModel* Mp, const BatchPtrs& P,
     res = __builtin_fmaf(arS[(i) < 31 ? (i) : 0], __int_as_float(di_), res);         \
     dl = hb_writelane(di_, (base) + (i), dl);                                        \
   }
-#define HB_PGS_CHUNK1(base, c) if ((c) * 4 >= ne) break; HB_PGS_ROW1(base, (c) * 4) HB_PGS_ROW1(base, (c) * 4 + 1) HB_PGS_ROW1(base, (c) * 4 + 2) HB_PGS_ROW1(base, (c) * 4 + 3)
-#define HB_PGS_TAIL(base, live, n_, niter_, mine)                                    \
-    {                                                                                \
-      /* the end of a sweep of the one env left, the same behind both forms of the row step */ \
-      auto tail_end_ = [&](float delta, float res0) {                                \
-        force += delta;                                                              \
-        const float improvement = half_sum<base>(delta * (res0 + res));              \
-        niter_++;                                                                    \
-        if (-0.5f * improvement * pgs_scale < pgs_tol || niter_ >= max_sweeps) {     \
-          live = false;                                                              \
-          if (mine) force_out = force;                                               \
-        }                                                                            \
-      };                                                                             \
-      while (n_ <= 16 && live) { /* the broadcast row step above, on this env's DPP row */ \
-        int ne;                                                                      \
-        asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(n_));                       \
-        const float nforce = -force, res0 = res;                                     \
-        float dl = 0.f;                                                              \
-        unsigned long long turn = 1ull << (base);                                    \
-        HB_PGS_SWEEPB;                                                               \
-        tail_end_(dl, res0);                                                         \
-      }                                                                              \
-      while (live) {                                                                 \
-        int ne;                                                                      \
-        asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(n_));                       \
-        const float nforce = -force, res0 = res;                                     \
-        int dl = 0;                                                                  \
-        do {                                                                         \
-          HB_PGS_CHUNK1(base, 0) HB_PGS_CHUNK1(base, 1) HB_PGS_CHUNK1(base, 2) HB_PGS_CHUNK1(base, 3) HB_PGS_CHUNK1(base, 4) HB_PGS_CHUNK1(base, 5) HB_PGS_CHUNK1(base, 6) HB_PGS_CHUNK1(base, 7) \
-        } while (0);                                                                 \
-        tail_end_(__int_as_float(dl), res0);                                         \
-      }                                                                              \
+// (the tall tail has more than 16 rows: its first four chunks run without a test)
+#define HB_PGS_CHUNK1(base, c) if ((c) > 3 && (c) * 4 >= ne) break; HB_PGS_ROW1(base, (c) * 4) HB_PGS_ROW1(base, (c) * 4 + 1) HB_PGS_ROW1(base, (c) * 4 + 2) HB_PGS_ROW1(base, (c) * 4 + 3)
+// the sweeps of the one env left: as in the paired loops the row count and the zero of the steps are set once, and a sweep ends in one
+// branch, back to the first row step or on to what the stop needs
+#define HB_PGS_TAIL(base, live, n_, niter_, mine)                                                                                    \
+    if (live) {                                                                                                                      \
+      int ne;                                                                                                                        \
+      asm volatile("s_mov_b32 %0, %1" : "=s"(ne) : "s"(n_));                                                                         \
+      /* the end of a sweep, the same behind both forms of the row step; true: the env sweeps on */                                  \
+      auto tail_end_ = [&](float delta, float res0) {                                                                                \
+        force += delta;                                                                                                              \
+        const float improvement = half_sum<base>(delta * (res0 + res));                                                              \
+        niter_++;                                                                                                                    \
+        return !(-0.5f * improvement * pgs_scale < pgs_tol) && niter_ < max_sweeps;                                                  \
+      };                                                                                                                             \
+      float res0;                                                                                                                    \
+      if (n_ <= 16) { /* the broadcast row step above, on this env's DPP row */                                                      \
+        float dl = 0.f;                                                                                                              \
+        do {                                                                                                                         \
+          const float nforce = -force;                                                                                               \
+          res0 = res;                                                                                                                \
+          unsigned long long turn = 1ull << (base);                                                                                  \
+          HB_PGS_SWEEPB;                                                                                                             \
+        } while (tail_end_(dl, res0));                                                                                               \
+      } else {                                                                                                                       \
+        int dl = 0;                                                                                                                  \
+        do {                                                                                                                         \
+          const float nforce = -force;                                                                                               \
+          res0 = res;                                                                                                                \
+          do {                                                                                                                       \
+            HB_PGS_CHUNK1(base, 0) HB_PGS_CHUNK1(base, 1) HB_PGS_CHUNK1(base, 2) HB_PGS_CHUNK1(base, 3) HB_PGS_CHUNK1(base, 4) HB_PGS_CHUNK1(base, 5) HB_PGS_CHUNK1(base, 6) HB_PGS_CHUNK1(base, 7)\
+          } while (0);                                                                                                               \
+        } while (tail_end_(__int_as_float(dl), res0));                                                                               \
+      }                                                                                                                              \
+      live = false;                                                                                                                  \
+      if (mine) force_out = force;                                                                                                   \
     }
       HB_PGS_TAIL(0, liveLo, nLo, niterLo, !h)
       HB_PGS_TAIL(32, liveHi, nHi, niterHi, h)
