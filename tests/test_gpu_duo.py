@@ -5,36 +5,12 @@ tests/test_gpu_timed_kernels.py puts the 128 golden states of the fp64 oracle th
 Here the duo kernel is held bit-identical to the one-env kernels on every path it has: two envs packed at lanes 0 / 32, a heavy env packed in front of a light one, one env at a time (more than 12
 contacts, rows beyond the packed capacity), an odd env count, the heavy-first order, pipelined segments, the reset paths of mj_check*.
 """
-import os
-
 import numpy as np
 import pytest
 
-from oracle_lib import GOLDEN, HUMANOID_HBM
+from duo_lib import DUO, collapsed, env_steps_both_ways, partners, reference_step
 
 pytestmark = pytest.mark.gpu
-DUO = "hb_step_duo_kernel"
-
-
-@pytest.fixture(scope="module")
-def golden():
-    return np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
-
-
-def pack_state(g, idx):
-    return np.concatenate([g["time"][idx, None], g["qpos"][idx], g["qvel"][idx], g["warm"][idx]], axis=1)
-
-
-def _reference_step(hbmod, m, gpu, state, ctrl):
-    """the same step through the full one-env kernel (a launch that asks for the diagnostics takes hb_step_kernel)"""
-    r = hbmod.Batch(m, len(state), gpu)
-    r.diag_enable(True)
-    r.set_state(hbmod.STATE_INTEGRATION, state)
-    r.step(ctrl)
-    assert r.last_kernel() == "hb_step_kernel"
-    out = r.get_state(hbmod.STATE_INTEGRATION), r.counts(), r.status()
-    r.close()
-    return out
 
 
 def test_duo_is_bit_identical_to_the_one_env_kernel(hbmod, humanoid_model, gpu):
@@ -55,7 +31,7 @@ def test_duo_is_bit_identical_to_the_one_env_kernel(hbmod, humanoid_model, gpu):
             ctrl = rng.uniform(-1, 1, size=(n, m.nu)).astype(np.float32)
             b.step(ctrl)
             assert b.last_kernel() == DUO
-            want, wcounts, wstatus = _reference_step(hbmod, m, gpu, st, ctrl)
+            want, wcounts, wstatus = reference_step(hbmod, m, gpu, st, ctrl)
             got = b.get_state(hbmod.STATE_INTEGRATION)
             assert np.array_equal(got, want), (n, t, np.abs(got - want).max())
             for x, y in zip(b.counts(), wcounts):
@@ -63,42 +39,13 @@ def test_duo_is_bit_identical_to_the_one_env_kernel(hbmod, humanoid_model, gpu):
         b.close()
 
 
-def partners(n, anti=16):
-    """env -> the env it shares its wave with (-1: none), as hb_step_duo_kernel pairs the dispatch slots of an n-env launch without a
-    heavy-first order: the first `anti` slots with the last ones, the others with their neighbour (csrc/hb_step_duo.hip: kDuoAnti)"""
-    k = min(anti, n >> 2)
-    p = np.full(n, -1)
-    for e in range(n):
-        if e < k or e >= n - k:
-            p[e] = n - 1 - e
-        else:
-            q = e + 1 if (e - k) % 2 == 0 else e - 1
-            p[e] = q if q < n - k else -1
-    return p
-
-
-def _collapsed_states(hbmod, m, gpu, n):
-    """the collapsed regime of profiles/r01_soak_1e10.txt: humanoids dropped from a crouch with their limbs driven into the floor - many
-    contacts and limit rows at once"""
-    b = hbmod.Batch(m, n, gpu)
-    b.reset(perturb=True)
-    rng = np.random.default_rng(11)
-    b.rollout_halton(150)
-    ctrl = np.sign(rng.uniform(-1, 1, size=(n, m.nu))).astype(np.float32)  # saturated actuators
-    for _ in range(60):
-        b.step(ctrl)
-    st = b.get_state(hbmod.STATE_INTEGRATION)
-    b.close()
-    return st, ctrl
-
-
 def test_heavy_env_steps_take_the_packed_and_the_one_at_a_time_paths(hbmod, humanoid_model, gpu):
     """env-steps above 31 rows: packed in front of their partner's rows when both fit the wave's 64 row lanes, else one env at a time -
     bit-identical to the one-env kernel either way.  The states are chosen so that both paths occur (asserted on the row counts)."""
     m = humanoid_model
     n = 2048
-    st, ctrl = _collapsed_states(hbmod, m, gpu, n)
-    want, (ncon, nefc, niter), wstatus = _reference_step(hbmod, m, gpu, st, ctrl)
+    st, ctrl = collapsed(hbmod, m, gpu, n, 60, np.random.default_rng(11))  # (the collapsed regime of profiles/r01_soak_1e10.txt)
+    want, (ncon, nefc, niter), wstatus = reference_step(hbmod, m, gpu, st, ctrl)
     heavy = nefc > 31
     pidx = partners(n)
     partner = np.where(pidx >= 0, nefc[pidx], 0)
@@ -121,7 +68,7 @@ def test_heavy_env_steps_take_the_packed_and_the_one_at_a_time_paths(hbmod, huma
     # a heavy env beside a heavy env: force the one-env-at-a-time path by pairing the heaviest envs with each other
     idx = np.argsort(-nefc)[:128]  # (whatever the pairing: every env's partner is one of the heaviest)
     pair_state, pair_ctrl = st[idx], ctrl[idx]
-    want2, counts2, _ = _reference_step(hbmod, m, gpu, pair_state, pair_ctrl)
+    want2, counts2, _ = reference_step(hbmod, m, gpu, pair_state, pair_ctrl)
     c = hbmod.Batch(m, len(pair_state), gpu)
     c.duo(2)
     c.set_state(hbmod.STATE_INTEGRATION, pair_state)
@@ -152,7 +99,7 @@ def test_bad_states_reset_inside_a_shared_wave(hbmod, humanoid_model, gpu):
     st[n - 1 - 17, 1 + nq + 4] = 3e9   # ... and its partner in the same wave as well
     st[40, 1 + nq:1 + nq + nv] = 2e9
     ctrl = np.random.default_rng(3).uniform(-1, 1, size=(n, m.nu)).astype(np.float32)
-    want, wcounts, wstatus = _reference_step(hbmod, m, gpu, st, ctrl)
+    want, wcounts, wstatus = reference_step(hbmod, m, gpu, st, ctrl)
     b.set_state(hbmod.STATE_INTEGRATION, st)
     b.step(ctrl)
     assert b.last_kernel() == DUO
@@ -215,32 +162,12 @@ def test_env_adapter_steps_through_the_duo_kernel_read_the_same_torques(hbmod, h
     n, T = 256, 60
     rng = np.random.default_rng(9)
     acts = rng.uniform(-1, 1, (T, n, humanoid_model.nu)).astype(np.float32)
-    got, names = [], []
-    for duo in (0, 2):
-        env = hbmod.VecEnv(humanoid_model, n, gpu, realism=True, domain_randomization=True)
-        env.batch.tune(duo=duo)
-        out = [env.reset().copy()]
-        for t in range(T):
-            obs, rew, term, trunc, info = env.step_arrays(acts[t])
-            out += [obs.copy(), rew.copy(), term.copy(), trunc.copy()]
-        names.append(env.batch.last_kernel())
-        got.append(out)
-        env.close()
+    got, names = env_steps_both_ways(hbmod, humanoid_model, gpu, acts, realism=True, domain_randomization=True)
     assert names == ["hb_step_kernel", "hb_step_kernel"] or names[1].startswith("hb_step_duo"), names
     assert all(np.array_equal(a, b) for a, b in zip(got[0], got[1]))
     # (domain randomisation hands the launch per-env model parameters: that launch is not a lean one and takes the full kernel in both runs;
     # without it the second run is the duo kernel's)
-    got, names = [], []
-    for duo in (0, 2):
-        env = hbmod.VecEnv(humanoid_model, n, gpu)
-        env.batch.tune(duo=duo)
-        out = [env.reset().copy()]
-        for t in range(T):
-            obs, rew, term, trunc, info = env.step_arrays(acts[t])
-            out += [obs.copy(), rew.copy(), term.copy(), trunc.copy()]
-        names.append(env.batch.last_kernel())
-        got.append(out)
-        env.close()
+    got, names = env_steps_both_ways(hbmod, humanoid_model, gpu, acts)
     assert names == ["hb_step_h27_q_kernel", "hb_step_duo_kernel"], names
     assert all(np.array_equal(a, b) for a, b in zip(got[0], got[1]))
     assert any(np.abs(x).max() > 0 for x in got[0][2::4])  # rewards are not all zero

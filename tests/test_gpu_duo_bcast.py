@@ -2,197 +2,35 @@
 Gauss-Seidel row step hands lane k's proposal to the row lanes of its env by v_fmac_f32_dpp row_newbcast:k; the one-env tail takes that form
 whenever the env that sweeps on has at most 16 rows.  Above 16 rows the sweeps keep their earlier form.
 
-hb_step_duo_kernel (one step) and hb_step_duo_q_kernel (two and three steps, the state on chip in between) are held byte for byte (time,
-qpos, qvel, warm start, ncon / nefc / sweeps, status) to hb_step_h27_kernel, the one-env kernel, on waves put together for the path they are to
-take.  The one-env kernel's result for an env does not depend on the batch around it, so it is computed ONCE for a pool of states (the 128
-golden states of the fp64 oracle, a collapsed regime, the benchmark's settled regime, fresh resets in the air) over three steps; every case is
-an index list into that pool, laid out so that the duo kernels' pairing of dispatch slots puts the chosen envs into one wave.  Which path a
-wave takes is asserted on the reference's own row and sweep counts, and a pool that lacks the envs a case needs fails the case.
+Method and helpers: tests/duo_lib.py.  The pool is its bcast_pool (the 128 golden states of the fp64 oracle, a collapsed regime, the benchmark's
+settled regime, fresh resets in the air) over three steps; which path a wave takes is asserted on the reference's own row and sweep counts.
 """
-import os
+import functools
 
-import numpy as np
 import pytest
 
-from oracle_lib import GOLDEN, HUMANOID_HBM
+import duo_lib
+from duo_lib import CAP, ROWS_DPP, STEPS, Picker, light
 
 pytestmark = pytest.mark.gpu
-ONE, DUO, DUO_Q = "hb_step_h27_kernel", "hb_step_duo_kernel", "hb_step_duo_q_kernel"
-STEPS = 3
-NCON_HALF = 12   # contacts per env while two envs share a wave (kNCh)
-ROWS_HALF = 31   # rows per env of the paired sweeps
-ROWS_DPP = 16    # rows per env of the broadcast forms: one DPP row of 16 lanes
-CAP = 50         # the model's sweep limit (opt.iterations)
-
-
-def partners(n, anti=16):
-    """env -> the env it shares its wave with (-1: none), as hb_step_duo_kernel pairs the dispatch slots of an n-env launch without a
-    heavy-first order: the first `anti` slots with the last ones, the others with their neighbour (csrc/hb_step_duo.hip: kDuoAnti)"""
-    k = min(anti, n >> 2)
-    p = np.full(n, -1)
-    for e in range(n):
-        if e < k or e >= n - k:
-            p[e] = n - 1 - e
-        else:
-            q = e + 1 if (e - k) % 2 == 0 else e - 1
-            p[e] = q if q < n - k else -1
-    return p
-
-
-def partners_q(n):
-    """the same for hb_step_duo_q_kernel: every slot with the one from the other end of the launch (the middle one of an odd count: none)"""
-    p = n - 1 - np.arange(n)
-    p[p == np.arange(n)] = -1
-    return p
-
-
-def place(pairs, pairing):
-    """pool indices per dispatch slot such that `pairing` puts every (a, b) of `pairs` into one wave, a in the lower slot (lanes 0..31)"""
-    n = 2 * len(pairs)
-    p = pairing(n)
-    assert (p >= 0).all(), (n, p)
-    idx = np.full(n, -1)
-    pairs = list(pairs)
-    for e in range(n):
-        if p[e] > e:
-            assert p[p[e]] == e
-            idx[e], idx[p[e]] = pairs.pop(0)
-    assert (idx >= 0).all() and not pairs
-    return idx
-
-
-def reference(hbmod, m, gpu, state, tape, steps):
-    """the one-env kernel's `steps` steps of the states: per step (state, ncon, nefc, niter, status)"""
-    r = hbmod.Batch(m, len(state), gpu)
-    r.tune(duo=0)
-    r.set_state(hbmod.STATE_INTEGRATION, state)
-    out = []
-    for t in range(steps):
-        r.step(tape[t])
-        assert r.last_kernel().startswith(ONE[:-7])
-        ncon, nefc, niter = r.counts()
-        out.append((r.get_state(hbmod.STATE_INTEGRATION), ncon, nefc, niter, r.status()))
-    r.close()
-    return out
+step_duo, roll_duo = (functools.partial(f, min_envs=16) for f in (duo_lib.step_duo, duo_lib.roll_duo))  # every case is at least 8 waves
 
 
 @pytest.fixture(scope="module")
 def pool(hbmod, humanoid_model, gpu):
     """(state [N, 1 + nq + 2 nv] float32, control tape [STEPS, N, nu]): golden states | collapsed regime | settled regime | fresh resets in the air"""
-    m = humanoid_model
-    g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
-    gstate = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1).astype(np.float32)
-    gctrl = g["ctrl"].astype(np.float32)
-    rng = np.random.default_rng(11)
-    n = 2048
-    b = hbmod.Batch(m, n, gpu)
-    b.reset(perturb=True)
-    b.rollout_halton(150)
-    cctrl = np.sign(rng.uniform(-1, 1, size=(n, m.nu))).astype(np.float32)  # saturated actuators: limbs driven into the floor
-    for _ in range(60):
-        b.step(cctrl)
-    cstate = b.get_state(hbmod.STATE_INTEGRATION)
-    b.close()
-    b = hbmod.Batch(m, n, gpu)  # the benchmark's regime: fallen and settled under its control sequence
-    b.reset(perturb=True)
-    b.rollout_halton(600)
-    sstate = b.get_state(hbmod.STATE_INTEGRATION)
-    b.close()
-    sctrl = rng.uniform(-1, 1, size=(n, m.nu)).astype(np.float32)
-    a = hbmod.Batch(m, 64, gpu)
-    a.reset(perturb=True)
-    astate = a.get_state(hbmod.STATE_INTEGRATION)
-    a.close()
-    astate[:, 1 + 2] += 1.0  # one metre up: no contact
-    actrl = np.zeros((64, m.nu), np.float32)
-    state = np.ascontiguousarray(np.concatenate([gstate, cstate, sstate, astate]), dtype=np.float32)
-    ctrl = np.concatenate([gctrl, cctrl, sctrl, actrl])
-    tape = np.stack([np.roll(ctrl, 7 * t, axis=0) for t in range(STEPS)])
-    tape[:, -64:] = 0.0  # (the envs in the air stay limp: no joint runs into its limit)
-    return state, np.ascontiguousarray(tape)
+    return duo_lib.bcast_pool(hbmod, humanoid_model, gpu)
 
 
 @pytest.fixture(scope="module")
 def ref(hbmod, humanoid_model, gpu, pool):
-    state, tape = pool
-    out = reference(hbmod, humanoid_model, gpu, state, tape, STEPS)
-    ncon, nefc, niter = out[0][1], out[0][2], out[0][3]
-    lt = (ncon <= NCON_HALF) & (nefc <= ROWS_HALF) & (out[0][4] == 0)
+    out = duo_lib.reference(hbmod, humanoid_model, gpu, *pool, STEPS, kernel=duo_lib.ONE_ANY)
+    nefc, niter, lt = out[0][2], out[0][3], light(out)
     print("\npool of %d envs, first step: rows 0..%d, %d envs that pair; of those %d at most 16 rows, %d / %d / %d / %d with 1 / 15 / 16 / 17 rows, "
-          "%d at the sweep cap, %d with one sweep" % (len(state), nefc.max(), lt.sum(), (lt & (nefc <= 16)).sum(), (lt & (nefc == 1)).sum(),
+          "%d at the sweep cap, %d with one sweep" % (len(pool[0]), nefc.max(), lt.sum(), (lt & (nefc <= 16)).sum(), (lt & (nefc == 1)).sum(),
                                                      (lt & (nefc == 15)).sum(), (lt & (nefc == 16)).sum(), (lt & (nefc == 17)).sum(),
                                                      (lt & (niter == CAP)).sum(), (lt & (niter == 1)).sum()))
     return out
-
-
-def same_bytes(b, hbmod, want, idx, what):
-    """state, counts [0..2] and status of batch b against the reference's of the pool envs idx, byte for byte"""
-    ws, wncon, wnefc, wniter, wstatus = want
-    got = b.get_state(hbmod.STATE_INTEGRATION)
-    assert got.dtype == np.float32 and ws.dtype == np.float32
-    bad = np.flatnonzero((got.view(np.uint32) != ws[idx].view(np.uint32)).any(axis=1))
-    assert bad.size == 0, (what, "state of slots", bad[:8], "rows", wnefc[idx][bad[:8]], "sweeps", wniter[idx][bad[:8]])
-    for name, x, y in zip(("ncon", "nefc", "niter"), b.counts(), (wncon, wnefc, wniter)):
-        assert np.array_equal(x, y[idx]), (what, name, np.flatnonzero(x != y[idx])[:8])
-    assert np.array_equal(b.status(), wstatus[idx]), (what, "status")
-
-
-def step_duo(hbmod, m, gpu, pool, ref, pairs, what=""):
-    """one step through hb_step_duo_kernel"""
-    state, tape = pool
-    idx = place(pairs, partners)
-    assert 16 <= len(idx) <= 64  # at least 8 waves
-    b = hbmod.Batch(m, len(idx), gpu)
-    b.tune(duo=2, schedule=0)  # (no heavy-first order: the pairing is that of the dispatch slots)
-    b.set_state(hbmod.STATE_INTEGRATION, state[idx])
-    b.step(tape[0][idx])
-    assert b.last_kernel() == DUO
-    same_bytes(b, hbmod, ref[0], idx, what + " [%s]" % DUO)
-    b.close()
-
-
-def roll_duo(hbmod, m, gpu, pool, ref, pairs, steps=2, what=""):
-    """`steps` steps through hb_step_duo_q_kernel (the state stays on chip in between)"""
-    state, tape = pool
-    idx = place(pairs, partners_q)
-    assert 16 <= len(idx) <= 64 and 2 <= steps <= STEPS
-    b = hbmod.Batch(m, len(idx), gpu)
-    b.tune(duo=2, schedule=0)
-    b.set_state(hbmod.STATE_INTEGRATION, state[idx])
-    b.rollout(np.ascontiguousarray(tape[:steps, idx]))
-    assert b.last_kernel() == DUO_Q
-    same_bytes(b, hbmod, ref[steps - 1], idx, what + " [%s, %d steps]" % (DUO_Q, steps))
-    b.close()
-
-
-def light(ref, t=0):
-    """envs that share a wave in the paired layout at step t: at most 12 contacts and 31 rows, no warning"""
-    return (ref[t][1] <= NCON_HALF) & (ref[t][2] <= ROWS_HALF) & (ref[t][4] == 0)
-
-
-class Picker:
-    """hands out pool envs that satisfy a mask, each at most once"""
-
-    def __init__(self, seed=0):
-        self.used = set()
-        self.rng = np.random.default_rng(seed)
-
-    def take(self, mask, what):
-        cand = [e for e in self.rng.permutation(np.flatnonzero(mask)) if e not in self.used]
-        assert cand, "the pool has no unused env for: " + what
-        self.used.add(cand[0])
-        return cand[0]
-
-    def pair(self, mask, cond, what, tries=20000):
-        """two unused envs (a, b) of the pool that satisfy the mask, with cond(a, b); a is for the lower slot"""
-        ok = np.array([e for e in np.flatnonzero(mask) if e not in self.used])
-        assert len(ok) >= 2, "the pool has no pair of envs for: " + what
-        for ia, ib in self.rng.integers(len(ok), size=(tries, 2)):
-            a, b = ok[ia], ok[ib]
-            if a != b and cond(a, b):
-                self.used.update((a, b))
-                return a, b
-        raise AssertionError("the pool has no pair of envs for: " + what)
 
 
 def test_both_envs_at_most_16_rows(hbmod, humanoid_model, gpu, pool, ref):
@@ -273,7 +111,6 @@ def test_sweep_counts_of_the_two_envs(hbmod, humanoid_model, gpu, pool, ref):
 @pytest.mark.parametrize("limit", [0, 1, 2])
 def test_iteration_limits(hbmod, gpu, pool, ref, limit):
     """opt.iterations 0, 1 and 2 against the one-env kernel with the same limit: waves of at most 16 rows, of 16 | 17 rows and with one env above 16"""
-    state, tape = pool
     nefc = ref[0][2]  # (the rows of a step do not depend on the sweeps of that step)
     ok = light(ref) & (nefc >= 1)
     pk = Picker(4)
@@ -281,16 +118,7 @@ def test_iteration_limits(hbmod, gpu, pool, ref, limit):
     pairs = [(pk.take(short, "at most 16 rows"), pk.take(short, "at most 16 rows")) for _ in range(8)]
     pairs += [(pk.take(ok & (nefc == 16), "16 rows"), pk.take(ok & (nefc == 17), "17 rows")), (pk.take(ok & (nefc == 17), "17 rows"), pk.take(ok & (nefc == 16), "16 rows"))]
     pairs += [(pk.take(short, "at most 16 rows"), pk.take(tall, "above 16 rows")) for _ in range(3)] + [(pk.take(tall, "above 16 rows"), pk.take(short, "at most 16 rows")) for _ in range(3)]
-    m = hbmod.Model.load(HUMANOID_HBM)
-    m.set_opt(iterations=limit)
-    sel = np.array(sorted(e for p in pairs for e in p))
-    where = {e: k for k, e in enumerate(sel)}
-    sub = (np.ascontiguousarray(state[sel]), np.ascontiguousarray(tape[:, sel]))
-    want = reference(hbmod, m, gpu, sub[0], sub[1], 2)
-    assert np.array_equal(want[0][2], nefc[sel]) and want[0][3].max() == limit and want[1][3].max() == limit
-    local = [(where[a], where[b]) for a, b in pairs]
-    step_duo(hbmod, m, gpu, sub, want, local, what="iterations=%d" % limit)
-    roll_duo(hbmod, m, gpu, sub, want, local, steps=2, what="iterations=%d" % limit)
+    duo_lib.iteration_limit_case(hbmod, gpu, pool, ref, pairs, limit, min_envs=16)
 
 
 def test_row_counts_that_cross_16_between_steps(hbmod, humanoid_model, gpu, pool, ref):
@@ -317,28 +145,10 @@ def test_the_torque_read_out(hbmod, humanoid_model, gpu, pool, ref):
     """a launch that asks for the joint torques (qfrc_smooth + qfrc_constraint = M qacc, which the dual finish feeds; the env adapter's reward
     reads them) on waves of at most 16 rows and of one env above 16: the torque array itself, and the observations, rewards and episode ends
     of the env step, equal the one-env kernel's byte for byte"""
-    state, tape = pool
     nefc = ref[0][2]
     ok = light(ref) & (nefc >= 1)
     pk = Picker(6)
     short, tall = ok & (nefc <= ROWS_DPP), ok & (nefc > ROWS_DPP)
     pairs = [(pk.take(short, "at most 16 rows"), pk.take(short, "at most 16 rows")) for _ in range(16)]
     pairs += [(pk.take(short, "at most 16 rows"), pk.take(tall, "above 16 rows")) for _ in range(8)] + [(pk.take(tall, "above 16 rows"), pk.take(short, "at most 16 rows")) for _ in range(8)]
-    idx = place(pairs, partners)
-    assert len(idx) == 64
-    got, names = [], []
-    for duo in (0, 2):
-        env = hbmod.VecEnv(humanoid_model, len(idx), gpu)
-        env.batch.tune(duo=duo, schedule=0)
-        env.reset()
-        env.batch.set_state(hbmod.STATE_INTEGRATION, state[idx])
-        obs, rew, term, trunc, info = env.step_arrays(tape[0][idx])
-        got.append([env.batch.env_joint_torques(), obs.copy(), rew.copy(), term.copy(), trunc.copy()])
-        names.append(env.batch.last_kernel())
-        if duo == 0:
-            assert np.array_equal(env.batch.counts()[1], nefc[idx])  # the waves are the ones chosen
-        env.close()
-    assert names[0].startswith("hb_step_h27") and names[1] == DUO, names
-    assert all(a.dtype == b.dtype and a.tobytes() == b.tobytes() for a, b in zip(got[0], got[1]))
-    assert got[0][0].shape == (64, humanoid_model.nv) and (np.abs(got[0][0]).max(axis=1) > 0).all()  # every env has torques to compare
-    assert np.abs(got[0][2]).max() > 0  # the rewards are not all zero
+    duo_lib.torque_readout_case(hbmod, humanoid_model, gpu, pool, ref, pairs)

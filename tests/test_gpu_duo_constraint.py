@@ -5,10 +5,9 @@ of the dual finish are read from LDS without a predicate and chosen by a select 
 rows of an earlier pass or step, non-finite rows of an env that takes the bad-qacc path) and must never reach a result.
 
 Same arithmetic, so the same bits: hb_step_duo_kernel and hb_step_duo_q_kernel are held byte for byte (time, qpos, qvel, qacc_warmstart,
-ncon / nefc / sweeps, status) to hb_step_h27_kernel, the one-env kernel.  The scheme is that of tests/test_gpu_duo_once.py, whose pool
-and layout helpers are used: the one-env kernel's three steps are computed ONCE for the pool, every case is an index list into it of at
-most 64 envs and one to three steps, and the path a case takes is asserted on the reference's own counts.  The pool is that file's (golden
-states, the collapsed regime, bodies laid flat, fresh resets in the air) and behind it a few states built here from qpos: the standing
+ncon / nefc / sweeps, status) to hb_step_h27_kernel, the one-env kernel.  Method and helpers: tests/duo_lib.py; the path a case takes is
+asserted on the reference's own counts.  The pool is tests/test_gpu_duo_once.py's (duo_lib.once_pool: golden states, the collapsed regime,
+bodies laid flat, fresh resets in the air) and behind it a few states built here from qpos: the standing
 reset (8 contacts, 32 rows), bodies in the air with joints or a hamstring tendon beyond their range (limit rows without contacts; the
 oracle says on the CPU which rows exist), the standing body with such joints (limits and contacts), and states whose step runs
 mj_forward twice (a bad qacc).  A case the pool has no state for fails; only "exactly 32 rows" may take the nearest count above.
@@ -16,12 +15,11 @@ mj_forward twice (a bad qacc).  A case the pool has no state for fails; only "ex
 import numpy as np
 import pytest
 
+import duo_lib
+from duo_lib import BADQACC, NCON_HALF, ROWS_HALF, STEPS, both_kernels, fits_packed, light, roll_duo, step_duo
 from oracle_lib import Oracle
-from test_gpu_duo_once import NCON_HALF, ONE, ROWS_HALF, STEPS, fits_packed, light, roll_duo, step_duo
-from test_gpu_duo_once import pool as once_pool  # noqa: F401  (the fixture, under a name of its own)
 
 pytestmark = pytest.mark.gpu
-BADQACC = 1 << 6
 LIMIT_JOINT, LIMIT_TENDON = 3, 4  # efc types of the oracle (mjCNSTR_LIMIT_JOINT, mjCNSTR_LIMIT_TENDON); contact rows are above
 # qpos addresses: knee_right 13 (range up to 0.035), abdomen_y 8 (up to 0.52), knee_left 19, hip_y_right 12 and hip_y_left 18 (down to -2.62;
 # the hamstring tendons 0.5 hip_y - 0.5 knee reach down to -0.3)
@@ -55,10 +53,10 @@ def made():
 
 
 @pytest.fixture(scope="module")
-def pool(once_pool, humanoid_model, made):
+def pool(hbmod, humanoid_model, gpu, made):
     """tests/test_gpu_duo_once.py's pool | the BUILT states | NBAD states with velocities that overflow the accelerations"""
-    state, tape = once_pool
     m = humanoid_model
+    state, tape = duo_lib.once_pool(hbmod, m, gpu)
     extra = np.stack([made[name][0] for name, _, _ in BUILT])
     bad = np.stack([state[0], state[1], made["standing"][0]]).copy()
     bad[0, 1 + m.nq + 4] = 3e9              # an angular velocity of the root (tests/test_gpu_duo.py's recipe)
@@ -73,19 +71,9 @@ def pool(once_pool, humanoid_model, made):
 @pytest.fixture(scope="module")
 def ref(hbmod, humanoid_model, gpu, pool):
     """the one-env kernel's STEPS steps of the pool: per step (state, ncon, nefc, niter, status)"""
-    state, tape = pool
-    r = hbmod.Batch(humanoid_model, len(state), gpu)
-    r.tune(duo=0)
-    r.set_state(hbmod.STATE_INTEGRATION, state)
-    out = []
-    for t in range(STEPS):
-        r.step(tape[t])
-        assert r.last_kernel() == ONE
-        ncon, nefc, niter = r.counts()
-        out.append((r.get_state(hbmod.STATE_INTEGRATION), ncon, nefc, niter, r.status()))
-    r.close()
+    out = duo_lib.reference(hbmod, humanoid_model, gpu, *pool, STEPS)
     nefc = out[0][2]
-    print("\npool of %d envs, first step: envs per row count 0..40: %s" % (len(state), np.bincount(nefc, minlength=41)[:41].tolist()))
+    print("\npool of %d envs, first step: envs per row count 0..40: %s" % (len(pool[0]), np.bincount(nefc, minlength=41)[:41].tolist()))
     return out
 
 
@@ -99,11 +87,6 @@ def pick(mask, k, what, taken=()):
     e = [i for i in np.flatnonzero(mask) if i not in set(taken)]
     assert len(e) >= k, "the pool has %d envs for '%s', the case needs %d" % (len(e), what, k)
     return e[:k]
-
-
-def both_kernels(hbmod, m, gpu, pool, ref, pairs, singles=(), steps=2, what=""):
-    step_duo(hbmod, m, gpu, pool, ref, pairs, singles, what=what)
-    roll_duo(hbmod, m, gpu, pool, ref, pairs, singles, steps=steps, what=what)
 
 
 def test_the_built_states_are_what_they_are_built_for(made, pool, ref):

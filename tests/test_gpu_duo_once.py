@@ -2,172 +2,33 @@
 per dof in the qM stage, the AR columns of a pair of envs at most 31 rows each handed over by one swap per register, and the tiles of
 C = J W stored whole.
 
-hb_step_duo_kernel and hb_step_duo_q_kernel are held byte for byte (time, qpos, qvel, warm start, ncon / nefc / sweeps, status) to
-hb_step_h27_kernel, the one-env kernel, on waves put together for the path they are to take.  Every case is at most 64 envs and one to three
-steps.  The one-env kernel's result for an env does not depend on the batch around it, so it is computed ONCE, for a pool of states (the
-128 golden states of the fp64 oracle, the collapsed regime of tests/test_gpu_duo.py, bodies laid flat into the floor, fresh resets lifted
-off it) over three steps, and every case is an index list into that pool, laid out so that the duo kernels' pairing of dispatch slots puts the chosen envs into
-one wave.  Which path a wave takes is asserted on the reference's own contact and row counts.
+Method and helpers: tests/duo_lib.py.  Every case is at most 64 envs and one to three steps of its once_pool: the 128 golden states of the
+fp64 oracle, the collapsed regime of tests/test_gpu_duo.py, bodies laid flat into the floor, fresh resets lifted off it.  Which path a wave
+takes is asserted on the reference's own contact and row counts.
 """
-import os
-
 import numpy as np
 import pytest
 
-from oracle_lib import GOLDEN
+import duo_lib
+from duo_lib import DUO, NCON_HALF, ROWS_HALF, STEPS, env_steps_both_ways, fits_packed, light, partners, partners_q, roll_duo, step_duo
 
 pytestmark = pytest.mark.gpu
-ONE, DUO, DUO_Q = "hb_step_h27_kernel", "hb_step_duo_kernel", "hb_step_duo_q_kernel"
-STEPS = 3
-NCON_HALF = 12   # contacts per env while two envs share a wave (kNCh)
-ROWS_HALF = 31   # rows per env of the paired sweeps
-
-
-def partners(n, anti=16):
-    """env -> the env it shares its wave with (-1: none), as hb_step_duo_kernel pairs the dispatch slots of an n-env launch without a
-    heavy-first order: the first `anti` slots with the last ones, the others with their neighbour (csrc/hb_step_duo.hip: kDuoAnti)"""
-    k = min(anti, n >> 2)
-    p = np.full(n, -1)
-    for e in range(n):
-        if e < k or e >= n - k:
-            p[e] = n - 1 - e
-        else:
-            q = e + 1 if (e - k) % 2 == 0 else e - 1
-            p[e] = q if q < n - k else -1
-    return p
-
-
-def partners_q(n):
-    """the same for hb_step_duo_q_kernel: every slot with the one from the other end of the launch (the middle one of an odd count: none)"""
-    p = n - 1 - np.arange(n)
-    p[p == np.arange(n)] = -1
-    return p
-
-
-def place(pairs, singles, pairing):
-    """pool indices per dispatch slot such that `pairing` puts every (a, b) of `pairs` into one wave, a in the lower slot (lanes 0..31)"""
-    n = 2 * len(pairs) + len(singles)
-    p = pairing(n)
-    assert (p < 0).sum() == len(singles), (n, p)
-    idx = np.full(n, -1)
-    pairs, singles = list(pairs), list(singles)
-    for e in range(n):
-        if p[e] < 0:
-            idx[e] = singles.pop(0)
-        elif p[e] > e:
-            assert p[p[e]] == e
-            idx[e], idx[p[e]] = pairs.pop(0)
-    assert (idx >= 0).all() and not pairs and not singles
-    return idx
-
-
-def fits_packed(nf, ns):
-    """rows of two envs, the larger above 31, that one wave's 64 row lanes hold (csrc/hb_step_duo.hip: split)"""
-    return max((nf + 1 + 3) & ~3, 32) + ns + 1 <= 64
 
 
 @pytest.fixture(scope="module")
 def pool(hbmod, humanoid_model, gpu):
     """(state [N, 1 + nq + 2 nv] float32, control tape [STEPS, N, nu]): golden states | collapsed regime | lying flat | fresh resets in the air"""
-    m = humanoid_model
-    g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
-    gstate = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1).astype(np.float32)
-    gctrl = g["ctrl"].astype(np.float32)
-    n = 1792
-    b = hbmod.Batch(m, n, gpu)
-    b.reset(perturb=True)
-    rng = np.random.default_rng(11)
-    b.rollout_halton(150)
-    cctrl = np.sign(rng.uniform(-1, 1, size=(n, m.nu))).astype(np.float32)  # saturated actuators: limbs driven into the floor
-    for _ in range(60):
-        b.step(cctrl)
-    cstate = b.get_state(hbmod.STATE_INTEGRATION)
-    b.close()
-    a = hbmod.Batch(m, 64, gpu)
-    a.reset(perturb=True)
-    astate = a.get_state(hbmod.STATE_INTEGRATION)
-    a.close()
-    # lying flat, pressed into the floor: on the back, the front and either side at eight heights, limbs a little bent - every capsule of
-    # the body against the plane, more contacts than the collapsed regime reaches
-    lstate = astate.copy()
-    lstate[:, 1 + m.nq:] = 0.0
-    r = np.sqrt(0.5)
-    for k in range(64):
-        lstate[k, 1 + 2] = 0.03 + 0.012 * (k % 8)
-        lstate[k, 1 + 3:1 + 7] = ((r, 0, -r, 0), (r, 0, r, 0), (0.5, 0.5, -0.5, 0.5), (0.5, -0.5, -0.5, -0.5))[(k // 8) % 4]
-    lstate[:, 1 + 7:1 + m.nq] = np.random.default_rng(5).uniform(-0.1, 0.1, size=(64, m.nq - 7))
-    astate[:, 1 + 2] += 1.0  # one metre up: no contact
-    actrl = np.zeros((64, m.nu), np.float32)
-    state = np.ascontiguousarray(np.concatenate([gstate, cstate, lstate, astate]), dtype=np.float32)
-    ctrl = np.concatenate([gctrl, cctrl, actrl, actrl])
-    tape = np.stack([np.roll(ctrl, 7 * t, axis=0) for t in range(STEPS)])
-    tape[:, -64:] = 0.0  # (the envs in the air stay limp: no joint runs into its limit)
-    return state, np.ascontiguousarray(tape)
+    return duo_lib.once_pool(hbmod, humanoid_model, gpu)
 
 
 @pytest.fixture(scope="module")
 def ref(hbmod, humanoid_model, gpu, pool):
     """the one-env kernel's STEPS steps of the pool: per step (state, ncon, nefc, niter, status)"""
-    state, tape = pool
-    r = hbmod.Batch(humanoid_model, len(state), gpu)
-    r.tune(duo=0)
-    r.set_state(hbmod.STATE_INTEGRATION, state)
-    out = []
-    for t in range(STEPS):
-        r.step(tape[t])
-        assert r.last_kernel() == ONE
-        ncon, nefc, niter = r.counts()
-        out.append((r.get_state(hbmod.STATE_INTEGRATION), ncon, nefc, niter, r.status()))
-    r.close()
+    out = duo_lib.reference(hbmod, humanoid_model, gpu, *pool, STEPS)
     ncon, nefc = out[0][1], out[0][2]
     print("\npool of %d envs, first step: rows 0..%d (%d envs above 31, %d without rows), contacts 0..%d (%d envs above 12)"
-          % (len(state), nefc.max(), (nefc > 31).sum(), (nefc == 0).sum(), ncon.max(), (ncon > 12).sum()))
+          % (len(pool[0]), nefc.max(), (nefc > 31).sum(), (nefc == 0).sum(), ncon.max(), (ncon > 12).sum()))
     return out
-
-
-def same_bytes(b, hbmod, want, idx, what):
-    """state, counts [0..2] and status of batch b against the reference's of the pool envs idx, byte for byte"""
-    ws, wncon, wnefc, wniter, wstatus = want
-    got = b.get_state(hbmod.STATE_INTEGRATION)
-    assert got.dtype == np.float32 and ws.dtype == np.float32
-    bad = np.flatnonzero((got.view(np.uint32) != ws[idx].view(np.uint32)).any(axis=1))
-    assert bad.size == 0, (what, "state of slots", bad[:8], "rows", wnefc[idx][bad[:8]], "contacts", wncon[idx][bad[:8]])
-    for name, x, y in zip(("ncon", "nefc", "niter"), b.counts(), (wncon, wnefc, wniter)):
-        assert np.array_equal(x, y[idx]), (what, name, np.flatnonzero(x != y[idx])[:8])
-    assert np.array_equal(b.status(), wstatus[idx]), (what, "status")
-
-
-def step_duo(hbmod, m, gpu, pool, ref, pairs, singles=(), what=""):
-    """one step through hb_step_duo_kernel"""
-    state, tape = pool
-    idx = place(pairs, singles, partners)
-    assert len(idx) <= 64
-    b = hbmod.Batch(m, len(idx), gpu)
-    b.tune(duo=2, schedule=0)  # (no heavy-first order: the pairing is that of the dispatch slots)
-    b.set_state(hbmod.STATE_INTEGRATION, state[idx])
-    b.step(tape[0][idx])
-    assert b.last_kernel() == DUO
-    same_bytes(b, hbmod, ref[0], idx, what + " [%s]" % DUO)
-    b.close()
-
-
-def roll_duo(hbmod, m, gpu, pool, ref, pairs, singles=(), steps=2, what=""):
-    """`steps` steps through hb_step_duo_q_kernel (the state stays on chip in between)"""
-    state, tape = pool
-    idx = place(pairs, singles, partners_q)
-    assert len(idx) <= 64 and 2 <= steps <= STEPS
-    b = hbmod.Batch(m, len(idx), gpu)
-    b.tune(duo=2, schedule=0)
-    b.set_state(hbmod.STATE_INTEGRATION, state[idx])
-    b.rollout(np.ascontiguousarray(tape[:steps, idx]))
-    assert b.last_kernel() == DUO_Q
-    same_bytes(b, hbmod, ref[steps - 1], idx, what + " [%s, %d steps]" % (DUO_Q, steps))
-    b.close()
-
-
-def light(ref, t=0):
-    """envs that share a wave in the paired layout at step t: at most 12 contacts and 31 rows, no warning"""
-    return (ref[t][1] <= NCON_HALF) & (ref[t][2] <= ROWS_HALF) & (ref[t][4] == 0)
 
 
 def test_every_residue_of_the_two_row_counts(hbmod, humanoid_model, gpu, pool, ref):
@@ -276,17 +137,7 @@ def test_the_torque_read_out_is_the_one_env_kernels(hbmod, humanoid_model, gpu):
     the qM stage left in LDS, so observations, rewards and episode ends equal the one-env kernel's"""
     n = 64
     acts = np.random.default_rng(9).uniform(-1, 1, (2, n, humanoid_model.nu)).astype(np.float32)
-    got, names = [], []
-    for duo in (0, 2):
-        env = hbmod.VecEnv(humanoid_model, n, gpu)
-        env.batch.tune(duo=duo)
-        out = [env.reset().copy()]
-        for t in range(2):
-            obs, rew, term, trunc, info = env.step_arrays(acts[t])
-            out += [obs.copy(), rew.copy(), term.copy(), trunc.copy()]
-        names.append(env.batch.last_kernel())
-        got.append(out)
-        env.close()
+    got, names = env_steps_both_ways(hbmod, humanoid_model, gpu, acts)
     assert names[0].startswith("hb_step_h27") and names[1] == DUO, names
     assert all(a.dtype == b.dtype and a.tobytes() == b.tobytes() for a, b in zip(got[0], got[1]))
     assert all(np.abs(x).max() > 0 for x in got[0][2::4])  # the rewards are not all zero

@@ -9,22 +9,18 @@ hb_get_qacc is a read-out of the FULL kernels (a launch that asks for it takes h
 held here cannot report it.  What they keep of the solver's qacc is the warm start of the state record (mj_step: qacc_warmstart = qacc), and
 that is held twice: to the one-env lean kernel's, and to what hb_get_qacc reports for the same step through hb_step_kernel.
 
-Every case is at most eight envs and three steps; the one-env kernel's result for an env does not depend on the batch around it, so it is
-computed once per model for a small pool of states and every case is an index list into that pool (tests/test_gpu_duo_once.py's layout
-helpers put the chosen envs into one wave).
+Method and helpers: tests/duo_lib.py.  Every case is at most eight envs and three steps of a small pool of its own, whose reference is computed
+once per model.
 """
-import os
-
 import numpy as np
 import pytest
 
-from oracle_lib import GOLDEN, HUMANOID_HBM
-from test_gpu_duo_once import DUO, DUO_Q, NCON_HALF, ONE, ROWS_HALF, partners, partners_q, place, same_bytes
+import duo_lib
+from duo_lib import BADQACC, DUO, NCON_HALF, ROWS_HALF, STEPS, partners, partners_q, place, roll_duo, step_duo
+from oracle_lib import HUMANOID_HBM
 
 pytestmark = pytest.mark.gpu
-STEPS = 3
 NGOLD, NFLAT, NBAD = 32, 16, 3
-BADQACC = 1 << 6
 
 
 def zero_damping_hbm(dst):
@@ -53,76 +49,23 @@ def pool(hbmod, humanoid_model, gpu):
     the floor (tests/test_gpu_duo_once.py: more than 12 contacts) | NBAD of these states with velocities that overflow the accelerations
     (tests/test_gpu_duo.py: BADQACC)"""
     m = humanoid_model
-    g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
-    gstate = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1).astype(np.float32)[:NGOLD]
-    gctrl = g["ctrl"].astype(np.float32)[:NGOLD]
-    a = hbmod.Batch(m, NFLAT, gpu)
-    a.reset(perturb=True)
-    lstate = a.get_state(hbmod.STATE_INTEGRATION)
-    a.close()
-    lstate[:, 1 + m.nq:] = 0.0
-    r = np.sqrt(0.5)
-    for k in range(NFLAT):
-        lstate[k, 1 + 2] = 0.03 + 0.012 * (k % 8)
-        lstate[k, 1 + 3:1 + 7] = ((r, 0, -r, 0), (r, 0, r, 0), (0.5, 0.5, -0.5, 0.5), (0.5, -0.5, -0.5, -0.5))[(k // 8) % 4]
-    lstate[:, 1 + 7:1 + m.nq] = np.random.default_rng(5).uniform(-0.1, 0.1, size=(NFLAT, m.nq - 7))
+    gstate, gctrl = (x[:NGOLD] for x in duo_lib.golden_states())
+    lstate, lctrl = duo_lib.flat(hbmod, m, gpu, NFLAT)
     bad = np.concatenate([gstate[:2], lstate[:1]])  # NBAD candidates
     bad[0, 1 + m.nq + 4] = 3e9              # an angular velocity of the root
     bad[1, 1 + m.nq:1 + m.nq + m.nv] = 2e9  # every velocity
     bad[2, 1 + m.nq + 2] = 3e9              # a linear velocity, in contact
     state = np.ascontiguousarray(np.concatenate([gstate, lstate, bad]), dtype=np.float32)
-    ctrl = np.concatenate([gctrl, np.zeros((NFLAT, m.nu), np.float32), gctrl[:2], np.zeros((1, m.nu), np.float32)])
-    tape = np.stack([np.roll(ctrl, 5 * t, axis=0) for t in range(STEPS)])
-    return state, np.ascontiguousarray(tape)
+    return state, duo_lib.make_tape(np.concatenate([gctrl, lctrl, gctrl[:2], lctrl[:1]]), 5, limp_last=0)
 
 
 @pytest.fixture(scope="module")
 def ref(hbmod, models, gpu, pool):
     """per model, the one-env kernel's STEPS steps of the pool: per step (state, ncon, nefc, niter, status)"""
-    state, tape = pool
-    out = {}
-    for name, m in models.items():
-        r = hbmod.Batch(m, len(state), gpu)
-        r.tune(duo=0)
-        r.set_state(hbmod.STATE_INTEGRATION, state)
-        steps = []
-        for t in range(STEPS):
-            r.step(tape[t])
-            assert r.last_kernel() == ONE
-            ncon, nefc, niter = r.counts()
-            steps.append((r.get_state(hbmod.STATE_INTEGRATION), ncon, nefc, niter, r.status()))
-        r.close()
-        out[name] = steps
+    out = {name: duo_lib.reference(hbmod, m, gpu, *pool, STEPS) for name, m in models.items()}
     a, b = out["humanoid"][0][0], out["undamped"][0][0]
     assert (a[:NGOLD] != b[:NGOLD]).any(axis=1).all()  # the damping is in every env's step: the two references differ
     return out
-
-
-def run_steps(hbmod, m, gpu, pool, want, pairs, singles=(), steps=1, what=""):
-    """`steps` launches of hb_step_duo_kernel, held after every one"""
-    state, tape = pool
-    idx = place(pairs, singles, partners)
-    b = hbmod.Batch(m, len(idx), gpu)
-    b.tune(duo=2, schedule=0)  # (no heavy-first order: the pairing is that of the dispatch slots)
-    b.set_state(hbmod.STATE_INTEGRATION, state[idx])
-    for t in range(steps):
-        b.step(tape[t][idx])
-        assert b.last_kernel() == DUO
-        same_bytes(b, hbmod, want[t], idx, what + " [%s, step %d]" % (DUO, t))
-    b.close()
-
-
-def run_roll(hbmod, m, gpu, pool, want, pairs, singles=(), steps=STEPS, what=""):
-    """`steps` steps in one launch of hb_step_duo_q_kernel (the state stays on chip in between: the rounds run again on it)"""
-    state, tape = pool
-    idx = place(pairs, singles, partners_q)
-    b = hbmod.Batch(m, len(idx), gpu)
-    b.tune(duo=2, schedule=0)
-    b.set_state(hbmod.STATE_INTEGRATION, state[idx])
-    b.rollout(np.ascontiguousarray(tape[:steps, idx]))
-    assert b.last_kernel() == DUO_Q
-    same_bytes(b, hbmod, want[steps - 1], idx, what + " [%s, %d steps]" % (DUO_Q, steps))
-    b.close()
 
 
 def calm(want):
@@ -141,10 +84,10 @@ def test_a_pair(hbmod, models, gpu, pool, ref, model):
     e = calm(want)
     assert len(e) >= 2, len(e)
     pairs = [(e[0], e[1])]
-    run_steps(hbmod, models[model], gpu, pool, want, pairs, steps=1, what="a pair, " + model)
-    run_steps(hbmod, models[model], gpu, pool, want, pairs, steps=3, what="a pair, " + model)
-    run_roll(hbmod, models[model], gpu, pool, want, pairs, steps=2, what="a pair, " + model)
-    run_roll(hbmod, models[model], gpu, pool, want, pairs, steps=3, what="a pair, " + model)
+    step_duo(hbmod, models[model], gpu, pool, want, pairs, steps=1, what="a pair, " + model)
+    step_duo(hbmod, models[model], gpu, pool, want, pairs, steps=3, what="a pair, " + model)
+    roll_duo(hbmod, models[model], gpu, pool, want, pairs, steps=2, what="a pair, " + model)
+    roll_duo(hbmod, models[model], gpu, pool, want, pairs, steps=3, what="a pair, " + model)
 
 
 @pytest.mark.parametrize("model", ["humanoid", "undamped"])
@@ -153,8 +96,8 @@ def test_a_lone_env(hbmod, models, gpu, pool, ref, model):
     want = ref[model]
     e = calm(want)
     assert len(e) >= 3 and (partners(3) < 0).sum() == 1 and (partners_q(3) < 0).sum() == 1
-    run_steps(hbmod, models[model], gpu, pool, want, [(e[0], e[1])], [e[2]], steps=3, what="a lone env, " + model)
-    run_roll(hbmod, models[model], gpu, pool, want, [(e[0], e[1])], [e[2]], steps=3, what="a lone env, " + model)
+    step_duo(hbmod, models[model], gpu, pool, want, [(e[0], e[1])], [e[2]], steps=3, what="a lone env, " + model)
+    roll_duo(hbmod, models[model], gpu, pool, want, [(e[0], e[1])], [e[2]], steps=3, what="a lone env, " + model)
 
 
 @pytest.mark.parametrize("model", ["humanoid", "undamped"])
@@ -168,8 +111,8 @@ def test_a_serial_restart(hbmod, models, gpu, pool, ref, model):
     assert len(many) >= 2 and len(e) >= 2, (len(many), len(e), ncon[NGOLD:NGOLD + NFLAT])
     pairs = [(many[0], e[0]), (e[1], many[1])]
     assert all(max(ncon[a], ncon[b]) > NCON_HALF and min(ncon[a], ncon[b]) <= NCON_HALF for a, b in pairs)
-    run_steps(hbmod, models[model], gpu, pool, want, pairs, steps=1, what="a serial restart, " + model)
-    run_roll(hbmod, models[model], gpu, pool, want, pairs, steps=2, what="a serial restart, " + model)
+    step_duo(hbmod, models[model], gpu, pool, want, pairs, steps=1, what="a serial restart, " + model)
+    roll_duo(hbmod, models[model], gpu, pool, want, pairs, steps=2, what="a serial restart, " + model)
 
 
 def test_a_bad_qacc(hbmod, models, gpu, pool, ref):
@@ -181,8 +124,8 @@ def test_a_bad_qacc(hbmod, models, gpu, pool, ref):
     assert len(bad) >= 1, status
     e = calm(want)
     pairs = [(bad[0], e[0]), (e[1], bad[-1])]
-    run_steps(hbmod, models["humanoid"], gpu, pool, want, pairs, steps=1, what="a bad qacc")
-    run_roll(hbmod, models["humanoid"], gpu, pool, want, pairs, steps=2, what="a bad qacc")
+    step_duo(hbmod, models["humanoid"], gpu, pool, want, pairs, steps=1, what="a bad qacc")
+    roll_duo(hbmod, models["humanoid"], gpu, pool, want, pairs, steps=2, what="a bad qacc")
 
 
 def test_the_warm_start_is_the_full_kernels_qacc(hbmod, humanoid_model, gpu, pool, ref):

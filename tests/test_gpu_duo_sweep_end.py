@@ -4,63 +4,35 @@ in the low word of the mask and env B's in the high word - and one branch back w
 for rows are set once per solve, in the paired loops and in the tails of the one env left (short: at most 16 rows, tall: above).  None of
 it changes a bit.
 
-Method and helpers are those of tests/test_gpu_duo_bcast.py (the pool's recipe and `path` those of tests/test_gpu_duo_wide.py): hb_step_duo_kernel
-(one step) and hb_step_duo_q_kernel (two and three steps) are held byte for byte (time, qpos, qvel, warm start, ncon / nefc / sweeps, status) to
-hb_step_h27_kernel, whose result for an env does not depend on the batch around it and is computed ONCE for the pool over three steps.  Every
-case is an index list into the pool, laid out so that the pairing of dispatch slots puts the chosen envs into one wave; the path that wave
-takes is asserted on the reference's own counts, and a pool that lacks the envs a case needs fails the case.
+Method and helpers: tests/duo_lib.py; the pool is its wide_pool, shared with tests/test_gpu_duo_wide.py.  The path a wave takes (its `path`) is
+asserted on the reference's own counts.
 """
-import os
+import functools
 
 import numpy as np
 import pytest
 
-from oracle_lib import GOLDEN, HUMANOID_HBM
-from test_gpu_duo_bcast import CAP, ROWS_DPP, ROWS_HALF, STEPS, Picker, light, reference, roll_duo, step_duo
-from test_gpu_duo_wide import both_kernels, collapsed, path
+import duo_lib
+from duo_lib import CAP, ROWS_DPP, ROWS_HALF, STEPS, Picker, light, path
 
 pytestmark = pytest.mark.gpu
+roll_duo, both_kernels = (functools.partial(f, min_envs=16) for f in (duo_lib.roll_duo, duo_lib.both_kernels))  # every case is at least 8 waves
 
 
 @pytest.fixture(scope="module")
 def pool(hbmod, humanoid_model, gpu):
-    """(state [N, 1 + nq + 2 nv] float32, control tape [STEPS, N, nu]): golden states | collapsed regimes after 60, 20, 40 and 90 steps | settled regime |
-    fresh resets in the air (the pool of tests/test_gpu_duo_wide.py)"""
-    m = humanoid_model
-    g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
-    gstate = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1).astype(np.float32)
-    gctrl = g["ctrl"].astype(np.float32)
-    rng = np.random.default_rng(11)
-    n = 2048
-    cstate, cctrl = collapsed(hbmod, m, gpu, n, 60, rng)
-    b = hbmod.Batch(m, n, gpu)  # the benchmark's regime: fallen and settled under its control sequence
-    b.reset(perturb=True)
-    b.rollout_halton(600)
-    sstate = b.get_state(hbmod.STATE_INTEGRATION)
-    b.close()
-    sctrl = rng.uniform(-1, 1, size=(n, m.nu)).astype(np.float32)
-    more = [collapsed(hbmod, m, gpu, n, steps, rng) for steps in (20, 40, 90)]
-    a = hbmod.Batch(m, 64, gpu)
-    a.reset(perturb=True)
-    astate = a.get_state(hbmod.STATE_INTEGRATION)
-    a.close()
-    astate[:, 1 + 2] += 1.0  # one metre up: no contact
-    actrl = np.zeros((64, m.nu), np.float32)
-    state = np.ascontiguousarray(np.concatenate([gstate, cstate, sstate] + [s for s, _ in more] + [astate]), dtype=np.float32)
-    ctrl = np.concatenate([gctrl, cctrl, sctrl] + [c for _, c in more] + [actrl])
-    tape = np.stack([np.roll(ctrl, 7 * t, axis=0) for t in range(STEPS)])
-    tape[:, -64:] = 0.0  # (the envs in the air stay limp: no joint runs into its limit)
-    return state, np.ascontiguousarray(tape)
+    """(state [N, 1 + nq + 2 nv] float32, control tape [STEPS, N, nu]): golden states | collapsed regime after 60 steps | settled regime | collapsed
+    regimes after 20, 40 and 90 steps | fresh resets in the air"""
+    return duo_lib.wide_pool(hbmod, humanoid_model, gpu)
 
 
 @pytest.fixture(scope="module")
 def ref(hbmod, humanoid_model, gpu, pool):
-    state, tape = pool
-    out = reference(hbmod, humanoid_model, gpu, state, tape, STEPS)
+    out = duo_lib.wide_reference(hbmod, humanoid_model, gpu)
     nefc, niter = out[0][2], out[0][3]
     lt = light(out) & (niter >= 1)
     print("\npool of %d envs, first step, envs that pair and sweep: with 1..16 rows %s; of those with one sweep %s" %
-          (len(state), np.bincount(nefc[lt], minlength=17)[1:17].tolist(), np.bincount(nefc[lt & (niter == 1)], minlength=17)[1:17].tolist()))
+          (len(pool[0]), np.bincount(nefc[lt], minlength=17)[1:17].tolist(), np.bincount(nefc[lt & (niter == 1)], minlength=17)[1:17].tolist()))
     return out
 
 
@@ -75,7 +47,7 @@ def test_every_row_count_of_the_short_paired_loop(hbmod, humanoid_model, gpu, po
         pairs.append((pk.take(ok & (nefc <= n), "at most %d rows" % n), pk.take(ok & (nefc == n), "%d rows" % n)))
     assert [max(nefc[a], nefc[b]) for a, b in pairs] == [n for n in range(1, 17) for _ in range(2)]
     assert all(path(ref, a, b)[:2] == ("paired", "short") for a, b in pairs)
-    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, "short paired loop of 1..16 rows", steps=(2, 3))
+    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, what="short paired loop of 1..16 rows", steps=(2, 3))
 
 
 def test_every_row_count_of_the_short_tail(hbmod, humanoid_model, gpu, pool, ref):
@@ -94,7 +66,7 @@ def test_every_row_count_of_the_short_tail(hbmod, humanoid_model, gpu, pool, ref
     assert [nefc[e] for e in last] == [n for n in range(1, 17) for _ in range(2)]
     assert all(path(ref, a, b)[0] == "paired" and path(ref, a, b)[2] == "short" for a, b in pairs)
     assert sum(path(ref, a, b)[1] is not None for a, b in pairs) >= 16  # most tails follow a paired loop
-    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, "short tail of 1..16 rows", steps=(2, 3))
+    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, what="short tail of 1..16 rows", steps=(2, 3))
 
 
 @pytest.mark.parametrize("form", ["short", "wide"])
@@ -120,14 +92,13 @@ def test_the_order_in_which_the_two_envs_stop(hbmod, humanoid_model, gpu, pool, 
     pairs += [(pk.take(empty, "no rows"), pk.take(rows, "more than 4 sweeps")), (pk.take(rows, "more than 4 sweeps"), pk.take(empty, "no rows"))]
     assert all(path(ref, a, b) == ("paired", None, "short" if form == "short" else "tall") for a, b in pairs[-2:])
     assert len(pairs) == 16
-    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, "stopping order, %s form" % form)
+    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, what="stopping order, %s form" % form)
 
 
 @pytest.mark.parametrize("limit", [0, 1, 2])
 def test_iteration_limits(hbmod, gpu, pool, ref, limit):
     """opt.iterations 0, 1 and 2 against the one-env kernel with the same limit: the cap ends the paired loop of both forms (limit 2: or the envs'
     own tests do), and no sweep runs at 0"""
-    state, tape = pool
     nefc = ref[0][2]  # (the rows of a step do not depend on the sweeps of that step)
     ok = light(ref) & (nefc >= 1)
     pk = Picker(3)
@@ -135,18 +106,11 @@ def test_iteration_limits(hbmod, gpu, pool, ref, limit):
     pairs = [(pk.take(short, "at most 16 rows"), pk.take(short, "at most 16 rows")) for _ in range(6)]
     pairs += [(pk.take(tall, "above 16 rows"), pk.take(tall, "above 16 rows")) for _ in range(4)]
     pairs += [(pk.take(short, "at most 16 rows"), pk.take(tall, "above 16 rows")) for _ in range(3)] + [(pk.take(tall, "above 16 rows"), pk.take(short, "at most 16 rows")) for _ in range(3)]
-    m = hbmod.Model.load(HUMANOID_HBM)
-    m.set_opt(iterations=limit)
-    sel = np.array(sorted(e for p in pairs for e in p))
-    where = {e: k for k, e in enumerate(sel)}
-    sub = (np.ascontiguousarray(state[sel]), np.ascontiguousarray(tape[:, sel]))
-    want = reference(hbmod, m, gpu, sub[0], sub[1], 2)
-    assert np.array_equal(want[0][2], nefc[sel]) and want[0][3].max() == limit and want[1][3].max() == limit
-    local = [(where[a], where[b]) for a, b in pairs]
-    forms = [path(want, a, b)[:2] for a, b in local]
-    assert forms == ([("paired", None)] * 16 if limit == 0 else [("paired", "short")] * 6 + [("paired", "wide")] * 10)
-    step_duo(hbmod, m, gpu, sub, want, local, what="iterations=%d" % limit)
-    roll_duo(hbmod, m, gpu, sub, want, local, steps=2, what="iterations=%d" % limit)
+
+    def check(want, local):
+        forms = [path(want, a, b)[:2] for a, b in local]
+        assert forms == ([("paired", None)] * 16 if limit == 0 else [("paired", "short")] * 6 + [("paired", "wide")] * 10)
+    duo_lib.iteration_limit_case(hbmod, gpu, pool, ref, pairs, limit, min_envs=16, check=check)
 
 
 def test_wide_pairs_tall_tails_and_a_packed_wave(hbmod, humanoid_model, gpu, pool, ref):
@@ -164,7 +128,7 @@ def test_wide_pairs_tall_tails_and_a_packed_wave(hbmod, humanoid_model, gpu, poo
     assert all(path(ref, a, b) == ("paired", "wide", "tall") for a, b in tails)
     packed = [(pk.take(big, "32..63 rows"), pk.take(ok, "an env that pairs")), (pk.take(ok, "an env that pairs"), pk.take(big, "32..63 rows"))]
     assert all(path(ref, a, b)[0] == "packed" for a, b in packed)
-    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs + tails + packed, "wide pairs, tall tails, a packed wave", steps=(2, 3))
+    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs + tails + packed, what="wide pairs, tall tails, a packed wave", steps=(2, 3))
 
 
 def test_row_counts_that_cross_16_inside_a_launch(hbmod, humanoid_model, gpu, pool, ref):

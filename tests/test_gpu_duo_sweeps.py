@@ -11,37 +11,11 @@ import os
 import numpy as np
 import pytest
 
+from duo_lib import DUO, DUO_Q, partners, reference_step
 from oracle_lib import GOLDEN, HUMANOID_HBM
 
 pytestmark = pytest.mark.gpu
-DUO, DUO_Q = "hb_step_duo_kernel", "hb_step_duo_q_kernel"
 SEEDS = (0, 1, 2, 3)
-
-
-def partners(n, anti=16):
-    """env -> the env it shares its wave with (-1: none), as hb_step_duo_kernel pairs the dispatch slots of an n-env launch without a
-    heavy-first order: the first `anti` slots with the last ones, the others with their neighbour (csrc/hb_step_duo.hip: kDuoAnti)"""
-    k = min(anti, n >> 2)
-    p = np.full(n, -1)
-    for e in range(n):
-        if e < k or e >= n - k:
-            p[e] = n - 1 - e
-        else:
-            q = e + 1 if (e - k) % 2 == 0 else e - 1
-            p[e] = q if q < n - k else -1
-    return p
-
-
-def _reference_step(hbmod, m, gpu, state, ctrl):
-    """one step through the full one-env kernel (a launch that asks for the diagnostics takes hb_step_kernel)"""
-    r = hbmod.Batch(m, len(state), gpu)
-    r.diag_enable(True)
-    r.set_state(hbmod.STATE_INTEGRATION, state)
-    r.step(ctrl)
-    assert r.last_kernel() == "hb_step_kernel"
-    out = r.get_state(hbmod.STATE_INTEGRATION), r.counts(), r.status()
-    r.close()
-    return out
 
 
 def _duo_step(hbmod, m, gpu, state, ctrl):
@@ -81,7 +55,7 @@ def batches():
 @pytest.fixture(scope="module")
 def references(hbmod, humanoid_model, gpu, batches):
     """the one-env kernel's step of every batch, computed once: (state, (ncon, nefc, niter), status) per seed"""
-    return [_reference_step(hbmod, humanoid_model, gpu, st, ct) for st, ct in batches]
+    return [reference_step(hbmod, humanoid_model, gpu, st, ct) for st, ct in batches]
 
 
 def test_pairs_cover_every_sweep_path(references):
@@ -123,7 +97,7 @@ def test_two_steps_in_the_multi_step_kernel_are_bit_identical(hbmod, humanoid_mo
     m = humanoid_model
     for s, (st, ct), (mid, _, _) in zip(SEEDS, batches, references):
         ct2 = np.ascontiguousarray(ct[::-1])  # the second step's controls: another env's
-        want = _reference_step(hbmod, m, gpu, mid, ct2)
+        want = reference_step(hbmod, m, gpu, mid, ct2)
         b = hbmod.Batch(m, len(st), gpu)
         b.duo(2)
         b.set_state(hbmod.STATE_INTEGRATION, st)
@@ -140,7 +114,7 @@ def test_iteration_limits(hbmod, gpu, batches, iterations):
     m = hbmod.Model.load(HUMANOID_HBM)
     m.set_opt(iterations=iterations)
     st, ct = batches[0]
-    want = _reference_step(hbmod, m, gpu, st, ct)
+    want = reference_step(hbmod, m, gpu, st, ct)
     nefc, niter = want[1][1], want[1][2]
     assert (niter <= iterations).all() and (niter[nefc > 0] == iterations).sum() >= (8 if iterations else 0)
     if iterations == 0:

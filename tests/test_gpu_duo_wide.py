@@ -4,101 +4,40 @@ its row step broadcasts lane k's proposal by v_fmac_f32_dpp row_newbcast inside 
 row layout: in the short broadcast form with at most 16 rows, in the one-env kernel's row step (v_readlane) above.  At most 16 rows in both
 envs keeps the short form throughout, an env above 31 rows the packed layout.
 
-Method and helpers are those of tests/test_gpu_duo_bcast.py: hb_step_duo_kernel (one step) and hb_step_duo_q_kernel (two and three steps) are
-held byte for byte (time, qpos, qvel, warm start, ncon / nefc / sweeps, status) to hb_step_h27_kernel, whose result for an env does not depend
-on the batch around it and is computed ONCE for a pool of states over three steps.  Every case is an index list into the pool, laid out so
-that the pairing of dispatch slots puts the chosen envs into one wave; the path that wave takes (`path` below) is asserted on the reference's
-own contact, row and sweep counts, and a pool that lacks the envs a case needs fails the case.  The pool is that file's recipe plus three
-more collapsed regimes, for the rarer counts (31 rows, rows that cross 31 between two steps).  No env of the pool above 16 rows stops after
-ONE sweep by its own test (none in 8 x 2048 fallen envs left alone for 100 to 3000 steps either): a paired loop of one sweep is held by a short
-env with one sweep beside a tall one, and tall envs with one sweep by the iteration limit of 1.
+Method and helpers: tests/duo_lib.py.  The path a wave takes (its `path`) is asserted on the reference's own contact, row and sweep counts.  The
+pool is its wide_pool: bcast_pool's recipe plus three more collapsed regimes, for the rarer counts (31 rows, rows that cross 31 between two
+steps).  No env of the pool above 16 rows stops after ONE sweep by its own test (none in 8 x 2048 fallen envs left alone for 100 to 3000 steps
+either): a paired loop of one sweep is held by a short env with one sweep beside a tall one, and tall envs with one sweep by the iteration limit of 1.
 """
-import os
+import functools
 
 import numpy as np
 import pytest
 
-from oracle_lib import GOLDEN, HUMANOID_HBM
-from test_gpu_duo_bcast import CAP, DUO, NCON_HALF, ROWS_DPP, ROWS_HALF, STEPS, Picker, light, partners, place, reference, roll_duo, step_duo
+import duo_lib
+from duo_lib import CAP, ROWS_DPP, STEPS, Picker, light, path
 
 pytestmark = pytest.mark.gpu
-
-
-def path(ref, a, b, t=0):
-    """(layout, form of the paired loop, form of the tail) of the wave that steps pool envs a (lanes 0..31) and b at step t, from the reference's counts:
-    'paired' needs both envs at most 12 contacts and 31 rows; the paired loop runs while both sweep, in the short form when both have at most 16
-    rows and in the wide form otherwise; the tail is the env with more sweeps alone, in the short form when IT has at most 16 rows and in the one-env
-    kernel's row step ("tall") above"""
-    ncon, nefc, niter = ref[t][1], ref[t][2], ref[t][3]
-    if max(ncon[a], ncon[b]) > NCON_HALF or max(nefc[a], nefc[b]) > ROWS_HALF:
-        return ("packed", None, None)
-    loop = None if min(niter[a], niter[b]) == 0 else ("short" if max(nefc[a], nefc[b]) <= ROWS_DPP else "wide")
-    last = a if niter[a] > niter[b] else b
-    tail = None if niter[a] == niter[b] else ("short" if nefc[last] <= ROWS_DPP else "tall")
-    return ("paired", loop, tail)
-
-
-def collapsed(hbmod, m, gpu, n, steps, rng):
-    """n envs fallen under the Halton control sequence, then `steps` steps with saturated actuators (limbs driven into the floor, joints into their limits)"""
-    b = hbmod.Batch(m, n, gpu)
-    b.reset(perturb=True)
-    b.rollout_halton(150)
-    ctrl = np.sign(rng.uniform(-1, 1, size=(n, m.nu))).astype(np.float32)
-    for _ in range(steps):
-        b.step(ctrl)
-    state = b.get_state(hbmod.STATE_INTEGRATION)
-    b.close()
-    return state, ctrl
+roll_duo, both_kernels = (functools.partial(f, min_envs=16) for f in (duo_lib.roll_duo, duo_lib.both_kernels))  # every case is at least 8 waves
 
 
 @pytest.fixture(scope="module")
 def pool(hbmod, humanoid_model, gpu):
-    """(state [N, 1 + nq + 2 nv] float32, control tape [STEPS, N, nu]): golden states | collapsed regimes after 60, 20, 40 and 90 steps | settled regime |
-    fresh resets in the air"""
-    m = humanoid_model
-    g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
-    gstate = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1).astype(np.float32)
-    gctrl = g["ctrl"].astype(np.float32)
-    rng = np.random.default_rng(11)
-    n = 2048
-    cstate, cctrl = collapsed(hbmod, m, gpu, n, 60, rng)
-    b = hbmod.Batch(m, n, gpu)  # the benchmark's regime: fallen and settled under its control sequence
-    b.reset(perturb=True)
-    b.rollout_halton(600)
-    sstate = b.get_state(hbmod.STATE_INTEGRATION)
-    b.close()
-    sctrl = rng.uniform(-1, 1, size=(n, m.nu)).astype(np.float32)
-    more = [collapsed(hbmod, m, gpu, n, steps, rng) for steps in (20, 40, 90)]
-    a = hbmod.Batch(m, 64, gpu)
-    a.reset(perturb=True)
-    astate = a.get_state(hbmod.STATE_INTEGRATION)
-    a.close()
-    astate[:, 1 + 2] += 1.0  # one metre up: no contact
-    actrl = np.zeros((64, m.nu), np.float32)
-    state = np.ascontiguousarray(np.concatenate([gstate, cstate, sstate] + [s for s, _ in more] + [astate]), dtype=np.float32)
-    ctrl = np.concatenate([gctrl, cctrl, sctrl] + [c for _, c in more] + [actrl])
-    tape = np.stack([np.roll(ctrl, 7 * t, axis=0) for t in range(STEPS)])
-    tape[:, -64:] = 0.0  # (the envs in the air stay limp: no joint runs into its limit)
-    return state, np.ascontiguousarray(tape)
+    """(state [N, 1 + nq + 2 nv] float32, control tape [STEPS, N, nu]): golden states | collapsed regime after 60 steps | settled regime | collapsed
+    regimes after 20, 40 and 90 steps | fresh resets in the air"""
+    return duo_lib.wide_pool(hbmod, humanoid_model, gpu)
 
 
 @pytest.fixture(scope="module")
 def ref(hbmod, humanoid_model, gpu, pool):
-    state, tape = pool
-    out = reference(hbmod, humanoid_model, gpu, state, tape, STEPS)
+    out = duo_lib.wide_reference(hbmod, humanoid_model, gpu)
     nefc, niter = out[0][2], out[0][3]
     lt = light(out)
     print("\npool of %d envs, first step: rows 0..%d, %d envs that pair; of those with 17..31 rows: %s; with 32..63 rows and no warning: %d; "
-          "tall and at the sweep cap %d, tall with one sweep %d" % (len(state), nefc.max(), lt.sum(), np.bincount(nefc[lt], minlength=32)[17:32].tolist(),
+          "tall and at the sweep cap %d, tall with one sweep %d" % (len(pool[0]), nefc.max(), lt.sum(), np.bincount(nefc[lt], minlength=32)[17:32].tolist(),
                                                                    ((nefc >= 32) & (nefc <= 63) & (out[0][4] == 0)).sum(),
                                                                    (lt & (nefc > 16) & (niter == CAP)).sum(), (lt & (nefc > 16) & (niter == 1)).sum()))
     return out
-
-
-def both_kernels(hbmod, m, gpu, pool, ref, pairs, what, steps=(2,)):
-    step_duo(hbmod, m, gpu, pool, ref, pairs, what=what)
-    for k in steps:
-        roll_duo(hbmod, m, gpu, pool, ref, pairs, steps=k, what=what)
 
 
 def test_row_counts_at_the_edges_of_the_wide_form(hbmod, humanoid_model, gpu, pool, ref):
@@ -118,7 +57,7 @@ def test_row_counts_at_the_edges_of_the_wide_form(hbmod, humanoid_model, gpu, po
     for a, b in pairs:
         p = path(ref, a, b)
         assert p[0] == "paired" and (p[1] == "wide" if min(nefc[a], nefc[b]) > 0 else (p[1] is None and p[2] == "tall")), (nefc[a], nefc[b], p)
-    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, "edges of the wide form", steps=(2, 3))
+    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, what="edges of the wide form", steps=(2, 3))
 
 
 def test_every_residue_mod_4_of_both_row_counts(hbmod, humanoid_model, gpu, pool, ref):
@@ -129,7 +68,7 @@ def test_every_residue_mod_4_of_both_row_counts(hbmod, humanoid_model, gpu, pool
     pairs = [(pk.take(ok & (nefc % 4 == ra), "17..31 rows, %d mod 4" % ra), pk.take(ok & (nefc % 4 == rb), "17..31 rows, %d mod 4" % rb)) for ra in range(4) for rb in range(4)]
     assert len({(nefc[a] % 4, nefc[b] % 4) for a, b in pairs}) == 16
     assert all(17 <= nefc[e] <= 31 for p in pairs for e in p) and all(path(ref, a, b)[:2] == ("paired", "wide") for a, b in pairs)
-    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, "17..31 rows mod 4")
+    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, what="17..31 rows mod 4")
 
 
 def test_the_boundaries_of_the_wide_form(hbmod, humanoid_model, gpu, pool, ref):
@@ -150,7 +89,7 @@ def test_the_boundaries_of_the_wide_form(hbmod, humanoid_model, gpu, pool, ref):
     assert [(nefc[a], nefc[b]) for a, b in pairs[:6]] == [(16, 17)] * 2 + [(17, 16)] * 2 + [(16, 16)] * 2
     assert nefc[pairs[6][0]] == 31 and nefc[pairs[6][1]] >= 32 and nefc[pairs[7][0]] >= 32 and nefc[pairs[7][1]] == 31
     assert [path(ref, a, b)[:2] for a, b in pairs] == want
-    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, "16 | 17 and 31 | 32 rows")
+    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, what="16 | 17 and 31 | 32 rows")
 
 
 def test_the_order_in_which_the_two_envs_stop(hbmod, humanoid_model, gpu, pool, ref):
@@ -181,14 +120,13 @@ def test_the_order_in_which_the_two_envs_stop(hbmod, humanoid_model, gpu, pool, 
         assert all(path(ref, a, b) == want for a, b in ps), (want, [path(ref, a, b) for a, b in ps])
         pairs += ps
     assert len(pairs) == 21
-    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, "stopping order")
+    both_kernels(hbmod, humanoid_model, gpu, pool, ref, pairs, what="stopping order")
 
 
 @pytest.mark.parametrize("limit", [0, 1, 2])
 def test_iteration_limits(hbmod, gpu, pool, ref, limit):
     """opt.iterations 0, 1 and 2 against the one-env kernel with the same limit: two envs above 16 rows, one above beside one at or below in both
     slots, (16, 17) and (17, 16), 31 rows"""
-    state, tape = pool
     nefc = ref[0][2]  # (the rows of a step do not depend on the sweeps of that step)
     ok = light(ref) & (nefc >= 1)
     pk = Picker(4)
@@ -197,18 +135,11 @@ def test_iteration_limits(hbmod, gpu, pool, ref, limit):
     pairs += [(pk.take(ok & (nefc == 16), "16 rows"), pk.take(ok & (nefc == 17), "17 rows")), (pk.take(ok & (nefc == 17), "17 rows"), pk.take(ok & (nefc == 16), "16 rows"))]
     pairs += [(pk.take(short, "at most 16 rows"), pk.take(tall, "above 16 rows")) for _ in range(3)] + [(pk.take(tall, "above 16 rows"), pk.take(short, "at most 16 rows")) for _ in range(3)]
     pairs += [(pk.take(ok & (nefc == 31), "31 rows"), pk.take(tall, "above 16 rows"))]
-    m = hbmod.Model.load(HUMANOID_HBM)
-    m.set_opt(iterations=limit)
-    sel = np.array(sorted(e for p in pairs for e in p))
-    where = {e: k for k, e in enumerate(sel)}
-    sub = (np.ascontiguousarray(state[sel]), np.ascontiguousarray(tape[:, sel]))
-    want = reference(hbmod, m, gpu, sub[0], sub[1], 2)
-    assert np.array_equal(want[0][2], nefc[sel]) and want[0][3].max() == limit and want[1][3].max() == limit
-    local = [(where[a], where[b]) for a, b in pairs]
-    assert all(path(want, a, b)[0] == "paired" and max(want[0][2][a], want[0][2][b]) > ROWS_DPP for a, b in local)
-    assert all(path(want, a, b)[1] == (None if limit == 0 else "wide") for a, b in local)
-    step_duo(hbmod, m, gpu, sub, want, local, what="iterations=%d" % limit)
-    roll_duo(hbmod, m, gpu, sub, want, local, steps=2, what="iterations=%d" % limit)
+
+    def check(want, local):
+        assert all(path(want, a, b)[0] == "paired" and max(want[0][2][a], want[0][2][b]) > ROWS_DPP for a, b in local)
+        assert all(path(want, a, b)[1] == (None if limit == 0 else "wide") for a, b in local)
+    duo_lib.iteration_limit_case(hbmod, gpu, pool, ref, pairs, limit, min_envs=16, check=check)
 
 
 def test_row_counts_that_change_inside_one_launch(hbmod, humanoid_model, gpu, pool, ref):
@@ -248,7 +179,6 @@ def test_the_torque_read_out_of_wide_pairs(hbmod, humanoid_model, gpu, pool, ref
     """a launch that asks for the joint torques (which the dual finish feeds from the forces the sweeps leave) on waves of two envs above 16 rows and of
     one above beside one at or below: the torque array, and the observations, rewards and episode ends of the env step, equal the one-env kernel's
     byte for byte"""
-    state, tape = pool
     nefc, niter = ref[0][2], ref[0][3]
     ok = light(ref) & (nefc >= 1) & (niter >= 1)
     pk = Picker(6)
@@ -256,21 +186,4 @@ def test_the_torque_read_out_of_wide_pairs(hbmod, humanoid_model, gpu, pool, ref
     pairs = [(pk.take(tall, "above 16 rows"), pk.take(tall, "above 16 rows")) for _ in range(16)]
     pairs += [(pk.take(short, "at most 16 rows"), pk.take(tall, "above 16 rows")) for _ in range(8)] + [(pk.take(tall, "above 16 rows"), pk.take(short, "at most 16 rows")) for _ in range(8)]
     assert all(path(ref, a, b)[:2] == ("paired", "wide") for a, b in pairs)
-    idx = place(pairs, partners)
-    assert len(idx) == 64
-    got, names = [], []
-    for duo in (0, 2):
-        env = hbmod.VecEnv(humanoid_model, len(idx), gpu)
-        env.batch.tune(duo=duo, schedule=0)
-        env.reset()
-        env.batch.set_state(hbmod.STATE_INTEGRATION, state[idx])
-        obs, rew, term, trunc, info = env.step_arrays(tape[0][idx])
-        got.append([env.batch.env_joint_torques(), obs.copy(), rew.copy(), term.copy(), trunc.copy()])
-        names.append(env.batch.last_kernel())
-        if duo == 0:
-            assert np.array_equal(env.batch.counts()[1], nefc[idx])  # the waves are the ones chosen
-        env.close()
-    assert names[0].startswith("hb_step_h27") and names[1] == DUO, names
-    assert all(a.dtype == b.dtype and a.tobytes() == b.tobytes() for a, b in zip(got[0], got[1]))
-    assert got[0][0].shape == (64, humanoid_model.nv) and (np.abs(got[0][0]).max(axis=1) > 0).all()  # every env has torques to compare
-    assert np.abs(got[0][2]).max() > 0  # the rewards are not all zero
+    duo_lib.torque_readout_case(hbmod, humanoid_model, gpu, pool, ref, pairs)
