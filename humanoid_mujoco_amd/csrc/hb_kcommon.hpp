@@ -202,8 +202,20 @@ __device__ __forceinline__ int capsule_capsule(ConOut& c0, ConOut& c1, float mar
   V3 dif = pos1 - pos2;
   float ma = dot(axis1, axis1), mb = -dot(axis1, axis2), mc = dot(axis2, axis2);
   float u = -dot(axis1, dif), v = dot(axis2, dif);
+  // det = ma mc - mb^2 = |axis1 x axis2|^2.  Left to the compiler the difference of products is fma(ma, mc, -(mb * mb)): for bitwise equal
+  // axes the rounding residue of ma^2, 1e-14 and not 0, whenever |axis|^2 is an ulp off 1; short of that it carries up to four roundings,
+  // 2.4e-7, in size and in SIGN ("Parallel capsules").  Above kDetCross, forty times that (axes more than 0.18 degrees apart),
+  // it is used as it always was: x1 and x2 then solve the 2 x 2 system of the SAME rounded ma, mb, mc as their numerators, whose errors
+  // largely cancel, and no bit of them moves.  Below, the decision and det come from the cross product, formed from separately rounded
+  // products (never contracted): exactly zero for bitwise equal or opposite axes, accurate to 2e-7 / angle otherwise, never negative.
+  constexpr float kDetCross = 1e-5f;
   float det = ma * mc - mb * mb;
-  if (fabsf(det) >= HB_MINVAL) {
+  if (det < kDetCross) {
+    const V3 cr = {__fsub_rn(__fmul_rn(axis1.y, axis2.z), __fmul_rn(axis1.z, axis2.y)), __fsub_rn(__fmul_rn(axis1.z, axis2.x), __fmul_rn(axis1.x, axis2.z)),
+                   __fsub_rn(__fmul_rn(axis1.x, axis2.y), __fmul_rn(axis1.y, axis2.x))};
+    det = dot(cr, cr);
+  }
+  if (det >= HB_MINVAL) {
     float x1 = (mc * u - mb * v) / det, x2 = (ma * v - mb * u) / det;
     if (x1 > len1) { x1 = len1; x2 = (v - mb * len1) / mc; }
     else if (x1 < -len1) { x1 = -len1; x2 = (v + mb * len1) / mc; }
