@@ -171,6 +171,7 @@ hb_batch* hb_batch_create(const hb_model* m, int n_env, int device, char* err, i
     sb.geom = b->d_stage_geom; sb.item = b->d_stage_item; sb.nwork = b->d_stage_nwork; sb.nsearch = b->d_stage_nsearch; sb.result = b->d_stage_result;
     sb.nq = dm.nq; sb.nv = dm.nv; sb.nu = dm.nu;
     sb.no_mesh = b->model->m.nmesh == 0 ? 1 : 0;
+    sb.has_box = dm.has_box;
     sb.pose_lds = pose_lds_floats(dm.nq, dm.nbody, dm.ngeom) * (int)sizeof(float);
     if (dm.variant == 1 || b->D.d_dm_fast) {
       ok = ok && b->d_stage_defer.alloc((size_t)n_env * 3, /*zero=*/true) == HB_OK;  // flags | list | counters (StageBufs)
@@ -444,7 +445,7 @@ int hb_ray_configure(hb_batch* b, const hb_ray_spec* spec, const float* pnt, con
   for (int g = 0; g < m.ngeom; g++) {
     const int body = m.geom_bodyid[g], type = m.geom_type[g];
     if (body == spec->bodyexclude || !(spec->flags & (body == 0 ? HB_RAY_STATIC : HB_RAY_MOVING))) continue;
-    if (type != GEOM_PLANE && type != GEOM_HFIELD && type != GEOM_SPHERE && type != GEOM_CAPSULE) {
+    if (type != GEOM_PLANE && type != GEOM_HFIELD && type != GEOM_SPHERE && type != GEOM_CAPSULE && type != GEOM_BOX) {
       if (!m.geom_contype[g] && !m.geom_conaffinity[g]) continue;  // (a visual marker: it collides with nothing, and no ray sees it)
       return HB_EUNSUPPORTED;
     }

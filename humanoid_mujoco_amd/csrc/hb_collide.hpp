@@ -54,12 +54,14 @@ __device__ __forceinline__ bool boxes_touch(DevModelRef M, int g1, int g2, V3 dp
 // lowest point (z, relative to the geom's position) of geom g with orientation q in the frame the query is made in: the support
 // function along -z.  Single precision: the value only decides whether a prism under the geom is searched (the prism's top is
 // compared with it), and a vertex within rounding of the lowest one gives the same answer to within that rounding.
+template <int BOX = 0>
 __device__ __forceinline__ float lowest_point(DevModelRef M, int g, int type, float r, float h, Q4 q) {
   float m[9];
   q2mat(m, q);
   const V3 ld = {-m[6], -m[7], -m[8]};  // mat' (0, 0, -1): the query direction in the geom's frame
   if (type == 2) return -r;
   if (type == 3) return -r - fabsf(ld.z) * h;  // mat (ld r + (0, 0, sign(ld.z) h)) . z = -r - |ld.z| h
+  if (BOX != 0 && type == 6) { const V3 hb = ld3(M.geom_half + 3 * g); return -(fabsf(ld.x) * hb.x + fabsf(ld.y) * hb.y + fabsf(ld.z) * hb.z); }  // the corner by the signs of ld
   if (type != 7 || M.geom_meshnum[g] <= 0) return -M.geom_rbound[g];
   const float4 HB_CONST* start = M.mesh_start + kMeshStart * M.geom_dataid[g];
   const float ax = fabsf(ld.x), ay = fabsf(ld.y), az = fabsf(ld.z);
@@ -100,6 +102,8 @@ __device__ __forceinline__ float lowest_point(DevModelRef M, int g, int type, fl
 // appends the results (collide_gather).
 //
 // passes (1) and (2): s_scratch receives the pair list, the sub-grids of height-field pairs and the work items; returns the number of work items
+// (BOX = 1, here and below: the instantiations for models with box geoms, which alone carry the box colliders)
+template <int BOX = 0>
 __device__ __forceinline__ int build_work_list(DevModelRef M, int lane, const float* s_gpos, const float* s_gaxis, const float* s_gquat, int* s_scratch, int& status) {
   int* s_list = s_scratch;                   // [kListMax]
   int* s_pinfo = s_scratch + kListMax;       // [kListMax][4]: rmin, cmin, ncols of a height-field pair's sub-grid, lowest point of the geom (float bits)
@@ -121,7 +125,7 @@ __device__ __forceinline__ int build_work_list(DevModelRef M, int lane, const fl
         // that a separating axis keeps apart hold hulls that do not touch: the search would say so too, after two hull climbs
         // per support query (the robot's limbs are long and thin: most pairs that pass the bounding spheres stop here)
         const int t2 = (__float_as_int(c0.z) >> 8) & 255;
-        if (pass && M.box_cull && (t1 == 7 || t2 == 7)) pass = boxes_touch(M, g1, g2, dp, ldq(s_gquat + 4 * g1), ldq(s_gquat + 4 * g2), 0.5f * c0.w);
+        if (pass && M.box_cull && (t1 == 7 || t2 == 7 || (BOX != 0 && (t1 == 6 || (t1 == 3 && t2 == 6))))) pass = boxes_touch(M, g1, g2, dp, ldq(s_gquat + 4 * g1), ldq(s_gquat + 4 * g2), 0.5f * c0.w);
       }
     }
     const unsigned long long bal = __ballot(pass);
@@ -141,7 +145,7 @@ __device__ __forceinline__ int build_work_list(DevModelRef M, int lane, const fl
       const float4 c0 = M.crec[3 * (size_t)p], c1 = M.crec[3 * (size_t)p + 1];
       const int g1 = __float_as_int(c0.x), g2 = __float_as_int(c0.y), t1 = __float_as_int(c0.z) & 255;
       cnt = 1;
-      if (t1 == 0 && ((__float_as_int(c0.z) >> 8) & 255) == 7) cnt = 2;  // mjc_PlaneConvex: up to four contacts, two per work item
+      if (t1 == 0 && (((__float_as_int(c0.z) >> 8) & 255) == 7 || (BOX != 0 && ((__float_as_int(c0.z) >> 8) & 255) == 6))) cnt = 2;  // mjc_PlaneConvex, mjc_PlaneBox: up to four contacts, two per work item
       if (t1 == 1) {
         // mjc_ConvexHField's culling.  The sub-grid comes from the geom's bounding sphere in place of its exact bounding box (a superset
         // of MuJoCo's prisms in x and y: the extra ones lie outside the geom's footprint and cannot touch it), the height test from the
@@ -163,7 +167,7 @@ __device__ __forceinline__ int build_work_list(DevModelRef M, int lane, const fl
           const int ncols = max(cmax - cmin, 0), nrows = max(rmax - rmin, 0);
           cnt = nrows * 2 * ncols;
           const float4 c2 = M.crec[3 * (size_t)p + 2];
-          const float loz = q.z + lowest_point(M, g2, (__float_as_int(c0.z) >> 8) & 255, c2.x, c2.y, qmul(qconj(ldq(M.geom_quat + 4 * g1)), ldq(s_gquat + 4 * g2)));
+          const float loz = q.z + lowest_point<BOX>(M, g2, (__float_as_int(c0.z) >> 8) & 255, c2.x, c2.y, qmul(qconj(ldq(M.geom_quat + 4 * g1)), ldq(s_gquat + 4 * g2)));
           s_pinfo[4 * idx] = rmin; s_pinfo[4 * idx + 1] = cmin; s_pinfo[4 * idx + 2] = ncols; s_pinfo[4 * idx + 3] = __float_as_int(loz);
         }
       }
@@ -182,7 +186,7 @@ __device__ __forceinline__ int build_work_list(DevModelRef M, int lane, const fl
 // pass (3) for one work item: pair p (sub-item `sub` of the sub-grid rmin, cmin, ncols for a height-field pair) -> n contacts (0..2).
 // MODE 0: all of it.  MODE 1 (hb_pose_kernel): everything but the portal search; returns whether the item needs one (then n = 0).
 // MODE 2 (hb_narrow_kernel): an item MODE 1 said needs the portal search.
-template <int MODE, int MESH = 1, int GROUP = 1>
+template <int MODE, int MESH = 1, int GROUP = 1, int BOX = 0>
 __device__ __forceinline__ int eval_work_item(DevModelRef M, const float* hdata_all, bool have, int p, int sub, int rmin, int cmin, int ncols, float loz,
                                               const float* s_gpos, const float* s_gaxis, const float* s_gquat, ConOut& co0, ConOut& co1, int& n, V3& hint) {
   float4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0, c2 = c0;
@@ -230,6 +234,7 @@ __device__ __forceinline__ int eval_work_item(DevModelRef M, const float* hdata_
           for (int b = 0; b < 3; b++) o2.mat[3 * a + b] = hm[a] * m2[b] + hm[3 + a] * m2[3 + b] + hm[6 + a] * m2[6 + b];  // hm' m2
         o2.type = t2; o2.r = r2; o2.h = l2; o2.margin = margin;
         if constexpr (MESH != 0) set_mesh(M, o2, g2);
+        if (BOX != 0 && t2 == 6) o2.p0 = ld3(M.geom_half + 3 * g2);
         o1.type = -1; o1.pos = {0.f, 0.f, 0.f}; o1.r = o1.h = o1.margin = 0.f; o1.vert = M.mesh_start; o1.nbr = M.mesh_nbr;
 #pragma unroll
         for (int a = 0; a < 9; a++) o1.mat[a] = 0.f;
@@ -249,13 +254,29 @@ __device__ __forceinline__ int eval_work_item(DevModelRef M, const float* hdata_
           n = min(max(total - 2 * sub, 0), 2);
         }
       }
-    } else if (MESH != 0 && (t1 == 7 || t2 == 7)) {
-      // mjc_Convex: both geoms in the world frame, each inflated by half the margin
+    } else if (BOX != 0 && t1 == 0 && t2 == 6) {
+      // mjc_PlaneBox: analytic (never reaches the narrowphase kernel); work item `sub` carries contacts 2 sub, 2 sub + 1, as a plane - hull pair's
+      if constexpr (MODE != 2) {
+        const V3 normal = ld3(s_gaxis + 3 * g1);
+        if (dot(pos2 - pos1, normal) <= margin + rb2) {
+          float bm[9];
+          q2mat(bm, ldq(s_gquat + 4 * g2));
+          const int total = plane_box(pos2, bm, ld3(M.geom_half + 3 * g2), pos1, normal, margin, 2 * sub, co0.dist, co0.pos, co1.dist, co1.pos);
+          co0.n = normal; co1.n = normal;
+          n = min(max(total - 2 * sub, 0), 2);
+        }
+      }
+    } else if ((MESH != 0 && (t1 == 7 || t2 == 7)) || (BOX != 0 && (t1 == 6 || (t1 == 3 && t2 == 6)))) {
+      // mjc_Convex: both geoms in the world frame, each inflated by half the margin (a mesh hull or a box against anything but a plane,
+      // a height field or - a box - a sphere)
       q2mat(o1.mat, ldq(s_gquat + 4 * g1));
       q2mat(o2.mat, ldq(s_gquat + 4 * g2));
-      o1.type = t1; o1.pos = pos1; o1.r = c1.z; o1.h = c1.w; o1.margin = 0.5f * margin; set_mesh(M, o1, g1);
-      o2.type = t2; o2.pos = pos2; o2.r = r2; o2.h = l2; o2.margin = 0.5f * margin; set_mesh(M, o2, g2);
+      o1.type = t1; o1.pos = pos1; o1.r = c1.z; o1.h = c1.w; o1.margin = 0.5f * margin;
+      o2.type = t2; o2.pos = pos2; o2.r = r2; o2.h = l2; o2.margin = 0.5f * margin;
+      if constexpr (MESH != 0) { set_mesh(M, o1, g1); set_mesh(M, o2, g2); }
       o1.p0 = o1.p1 = o1.p2 = o1.p3 = o1.p4 = o1.p5 = V3{0.f, 0.f, 0.f};
+      if (BOX != 0 && t1 == 6) o1.p0 = ld3(M.geom_half + 3 * g1);
+      if (BOX != 0 && t2 == 6) o2.p0 = ld3(M.geom_half + 3 * g2);
       mpr_kind = 2;
     } else if (MODE == 2) {  // (the analytic pairs never reach the narrowphase kernel)
     } else if (t1 == 0) {
@@ -275,7 +296,11 @@ __device__ __forceinline__ int eval_work_item(DevModelRef M, const float* hdata_
     } else {
       const float r1 = c1.z, l1 = c1.w;
       if (t1 == 2 && t2 == 2) n = sphere_sphere(co0, margin, pos1, r1, pos2, r2) ? 1 : 0;
-      else if (t1 == 2) {
+      else if (BOX != 0 && t1 == 2 && t2 == 6) {
+        float bm[9];
+        q2mat(bm, ldq(s_gquat + 4 * g2));
+        n = sphere_box(co0, margin, pos1, r1, pos2, bm, ld3(M.geom_half + 3 * g2)) ? 1 : 0;
+      } else if (t1 == 2) {
         const float x = clampf(dot(ax2, pos1 - pos2), -l2, l2);
         n = sphere_sphere(co0, margin, pos1, r1, pos2 + ax2 * x, r2) ? 1 : 0;
       } else n = capsule_capsule(co0, co1, margin, pos1, ld3(s_gaxis + 3 * g1), r1, l1, pos2, ax2, r2, l2);
@@ -285,7 +310,7 @@ __device__ __forceinline__ int eval_work_item(DevModelRef M, const float* hdata_
   if (mpr_kind) {
     float depth;
     V3 dir, vec;
-    const bool hit = mpr_penetration<MESH, GROUP>(o1, o2, M.mpr_iterations, (double)M.mpr_tolerance, depth, dir, vec);
+    const bool hit = mpr_penetration<MESH, GROUP, BOX>(o1, o2, M.mpr_iterations, (double)M.mpr_tolerance, depth, dir, vec);
     if (mpr_kind == 1) {
       if (hit && depth >= 2.220446e-16f) {
         co0.dist = -depth;
@@ -342,13 +367,13 @@ __device__ __forceinline__ void append_contacts(int lane, float* s_con, int& nco
 }
 
 // the fused form: all three passes in the step kernel
-template <int NC>
+template <int NC, int BOX = 0>
 __device__ __forceinline__ int collide_general(DevModelRef M, const float* hdata_all, int lane, const float* s_gpos, const float* s_gaxis, const float* s_gquat,
                                                float* s_con, int* s_scratch, int& status) {
   const int* s_list = s_scratch;
   const int* s_pinfo = s_scratch + kListMax;
   const int* s_work = s_pinfo + 4 * kListMax;
-  const int nwork = build_work_list(M, lane, s_gpos, s_gaxis, s_gquat, s_scratch, status);
+  const int nwork = build_work_list<BOX>(M, lane, s_gpos, s_gaxis, s_gquat, s_scratch, status);
   int ncon = 0;
   for (int w0 = 0; w0 < nwork; w0 += kGroup) {
     const bool have = w0 + lane < nwork;
@@ -358,7 +383,7 @@ __device__ __forceinline__ int collide_general(DevModelRef M, const float* hdata
     ConOut co0, co1;
     int n;
     V3 hint;
-    eval_work_item<0>(M, hdata_all, have, p, sub, s_pinfo[4 * idx], s_pinfo[4 * idx + 1], s_pinfo[4 * idx + 2], __int_as_float(s_pinfo[4 * idx + 3]), s_gpos, s_gaxis, s_gquat, co0, co1, n, hint);
+    eval_work_item<0, 1, 1, BOX>(M, hdata_all, have, p, sub, s_pinfo[4 * idx], s_pinfo[4 * idx + 1], s_pinfo[4 * idx + 2], __int_as_float(s_pinfo[4 * idx + 3]), s_gpos, s_gaxis, s_gquat, co0, co1, n, hint);
     append_contacts<NC>(lane, s_con, ncon, n, co0, co1, hint, p);
   }
   if (ncon > NC) { status |= (1 << 1); ncon = NC; }

@@ -86,6 +86,7 @@ struct DevModel {
   const float HB_CONST *geom_size, *geom_pos, *geom_quat, *geom_rbound;
   const float HB_CONST* geom_half;  // [ngeom][3] half extents of the geom's bounding box in its own frame
   int box_cull;                     // 1: oriented-box test behind the bounding spheres of a portal-search pair (HB_BOX_CULL=0 switches it off: tests)
+  int has_box;                      // 1: a candidate pair has a box geom - the model steps in the kernels that carry the box colliders (COLL 2)
   // meshes: hull vertices as 16-byte records (x, y, z, link) and per geom the first record / the count (0 for other geom types);
   // link = first neighbour record << 8 | number of kMeshChunk-record chunks; mesh_nbr: one record per (vertex, neighbour): (x, y, z
   // of the neighbour, the neighbour's own link): the hull's edge graph with the coordinates inlined, every vertex's list padded to
@@ -486,6 +487,7 @@ struct StageBufs {
   // raises defer[env] and leaves its state alone, and the four-group kernel then steps exactly those envs (rerun = 1).
   const DevModel* dm_fast;  // null: no fast pass (not variant 2, or diagnostics on: their buffers have the big kernel's strides)
   int fast_lds;             // its dynamic LDS bytes
+  int has_box;              // DevModel::has_box: the pose / narrowphase launches are the *_box_kernel ones
   int* defer;               // [n_env]
   // the deferred envs of a launch as a list, so that the second pass is a handful of waves that loop over it instead of one wave per env
   // that looks at its flag and leaves (4096 waves of the four-group kernel, one per SIMD: 18 us): defer_list[blk0 + k], k < defer_count[blk0]

@@ -241,6 +241,38 @@ __device__ __forceinline__ int capsule_capsule(ConOut& c0, ConOut& c1, float mar
   if (h3 && n < 2) { if (n == 0) c0 = t3; else c1 = t3; n++; }
   return n;
 }
+// mjc_SphereBox: sphere (geom 1) at spos, box (geom 2) at bpos with orientation bmat (row-major) and half extents half.  The centre is
+// clamped into the box in the box's frame.  Outside: the normal runs from the centre to the clamped point, dist = d - r, the position
+// lies midway between the two surfaces.  Inside (the clamp moves nothing): the face of least half[k] - |c[k]| gives the normal, faces
+// taken in the order -x, +x, -y, +y, -z, +z and the first of the least kept; the normal is the inward one of that face (from the sphere
+// into the box), dist = -least - r.
+__device__ __forceinline__ bool sphere_box(ConOut& c, float margin, V3 spos, float radius, V3 bpos, const float* bmat, V3 half) {
+  const V3 dif = spos - bpos;
+  const V3 ctr = {bmat[0] * dif.x + bmat[3] * dif.y + bmat[6] * dif.z, bmat[1] * dif.x + bmat[4] * dif.y + bmat[7] * dif.z, bmat[2] * dif.x + bmat[5] * dif.y + bmat[8] * dif.z};
+  const V3 cl = {clampf(ctr.x, -half.x, half.x), clampf(ctr.y, -half.y, half.y), clampf(ctr.z, -half.z, half.z)};
+  const V3 out = cl - ctr;
+  const float d = sqrtf(dot(out, out));
+  if (d - radius > margin) return false;
+  V3 nl, pl;
+  if (d < HB_MINVAL) {
+    float least = half.x + ctr.x;
+    nl = {1.f, 0.f, 0.f};
+    if (half.x - ctr.x < least) { least = half.x - ctr.x; nl = {-1.f, 0.f, 0.f}; }
+    if (half.y + ctr.y < least) { least = half.y + ctr.y; nl = {0.f, 1.f, 0.f}; }
+    if (half.y - ctr.y < least) { least = half.y - ctr.y; nl = {0.f, -1.f, 0.f}; }
+    if (half.z + ctr.z < least) { least = half.z + ctr.z; nl = {0.f, 0.f, 1.f}; }
+    if (half.z - ctr.z < least) { least = half.z - ctr.z; nl = {0.f, 0.f, -1.f}; }
+    c.dist = -least - radius;
+    pl = ctr + nl * (0.5f * (radius - least));
+  } else {
+    nl = out * (1.f / d);
+    c.dist = d - radius;
+    pl = ctr + nl * (radius + 0.5f * c.dist);
+  }
+  c.n = mrot(bmat, nl);
+  c.pos = bpos + mrot(bmat, pl);
+  return true;
+}
 
 
 // closest point of triangle abc to p (Ericson, Real-Time Collision Detection 5.1.5)

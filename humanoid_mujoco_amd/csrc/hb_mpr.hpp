@@ -58,7 +58,7 @@ __device__ __forceinline__ V3d closest_on_triangle(V3d p, V3d a, V3d b, V3d c) {
   return a + ab * (vb * denom) + ac * (vc * denom);
 }
 
-// a convex object in the frame the test runs in: a geom (sphere 2, capsule 3, mesh hull 7) or a height-field prism (-1)
+// a convex object in the frame the test runs in: a geom (sphere 2, capsule 3, box 6, mesh hull 7) or a height-field prism (-1)
 struct CObj {
   int type;
   V3 pos;
@@ -69,7 +69,7 @@ struct CObj {
   const float4 HB_CONST* vert;
   const float4 HB_CONST* nbr;
   float margin;
-  V3 p0, p1, p2, p3, p4, p5;  // prism: bottom triangle 0..2, top triangle 3..5
+  V3 p0, p1, p2, p3, p4, p5;  // prism: bottom triangle 0..2, top triangle 3..5; box: p0 = its half extents (geom_half)
 };
 
 __device__ __forceinline__ V3d ccd_center(const CObj& o) {
@@ -212,8 +212,9 @@ __device__ __forceinline__ void climb(const CObj& o, Climb& c) {
   }
 }
 // the point farthest along dir (unit)
-// (MESH = 0: an instantiation for models without mesh geoms - the hull climb, its loads and its registers are not in the kernel)
-template <int MESH = 1, int GROUP = 1>
+// (MESH = 0: an instantiation for models without mesh geoms - the hull climb, its loads and its registers are not in the kernel;
+// BOX = 1: the instantiations for models with box geoms - no other kernel has the box's branch)
+template <int MESH = 1, int GROUP = 1, int BOX = 0>
 __device__ __forceinline__ V3d ccd_support(const CObj& o, V3d dir) {
   if (o.type < 0) {
     V3d best = widen(o.p0), c;
@@ -229,7 +230,11 @@ __device__ __forceinline__ V3d ccd_support(const CObj& o, V3d dir) {
   V3d res;
   if (o.type == 2) res = ld * (double)o.r;
   else if (o.type == 3) { res = ld * (double)o.r; res.z += ld.z >= 0.0 ? (double)o.h : -(double)o.h; }
-  else if constexpr (MESH != 0) {
+  else if (BOX != 0 && o.type == 6) {
+    // a box (half extents in p0): the corner by the signs of the local direction.  A zero component takes the + side: among corners of
+    // equal value that is the one hull_tie ranks first (its three weights are positive), so a box and its eight-corner hull agree
+    res = {ld.x >= 0.0 ? (double)o.p0.x : -(double)o.p0.x, ld.y >= 0.0 ? (double)o.p0.y : -(double)o.p0.y, ld.z >= 0.0 ? (double)o.p0.z : -(double)o.p0.z};
+  } else if constexpr (MESH != 0) {
     Climb c;
     c.ld = ld;
     climb_start(o, c);
@@ -274,12 +279,35 @@ __device__ __forceinline__ int plane_hull(const CObj& o, V3 ppos, V3 normal, flo
   return n;
 }
 
+// mjc_PlaneBox: the eight corners in the order i = 0..7, corner i = (i & 1 ? +hx : -hx, i & 2 ? +hy : -hy, i & 4 ? +hz : -hz) in the box's
+// frame.  ldist = n . (corner - centre), dist = n . (centre - plane_pos) + ldist; a corner with ldist > 0 or dist > margin is skipped,
+// the others give a contact at corner - n dist / 2, four at most.  Returns the count (0..4) and the contacts `first_k`, `first_k + 1` of
+// that list, as plane_hull does: a plane - box pair is two work items.
+__device__ __forceinline__ int plane_box(V3 bpos, const float* bmat, V3 half, V3 ppos, V3 normal, float margin, int first_k, float& da, V3& pa, float& db, V3& pb) {
+  const V3d nrm = widen(normal), ctr = widen(bpos);
+  const double cdist = dot(ctr - widen(ppos), nrm);
+  int n = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const double x = (i & 1) ? (double)half.x : -(double)half.x, y = (i & 2) ? (double)half.y : -(double)half.y, z = (i & 4) ? (double)half.z : -(double)half.z;
+    const V3d off = {(double)bmat[0] * x + (double)bmat[1] * y + (double)bmat[2] * z, (double)bmat[3] * x + (double)bmat[4] * y + (double)bmat[5] * z,
+                     (double)bmat[6] * x + (double)bmat[7] * y + (double)bmat[8] * z};
+    const double ldist = dot(nrm, off), d = cdist + ldist;
+    if (ldist > 0.0 || d > (double)margin || n >= 4) continue;
+    const V3 pos = narrow(ctr + off - nrm * (0.5 * d));
+    if (n == first_k) { da = (float)d; pa = pos; }
+    if (n == first_k + 1) { db = (float)d; pb = pos; }
+    n++;
+  }
+  return n;
+}
+
 struct CSup { V3d v, v1; };  // a point of the Minkowski difference obj1 - obj2 and its witness on obj1 (the one on obj2 is v1 - v)
-template <int MESH = 1, int GROUP = 1>
+template <int MESH = 1, int GROUP = 1, int BOX = 0>
 __device__ __forceinline__ CSup mpr_support(const CObj& o1, const CObj& o2, V3d dir) {
   CSup s;
-  s.v1 = ccd_support<MESH, GROUP>(o1, dir);
-  const V3d w2 = ccd_support<MESH, GROUP>(o2, dir * -1.0);
+  s.v1 = ccd_support<MESH, GROUP, BOX>(o1, dir);
+  const V3d w2 = ccd_support<MESH, GROUP, BOX>(o2, dir * -1.0);
   s.v = s.v1 - w2;
   return s;
 }
@@ -307,7 +335,7 @@ __device__ __forceinline__ void mpr_expand_portal(const CSup& P0, CSup& P1, CSup
 // and lanes inside different loops of the original would execute those loops one after the other (the wave's time the sum over the
 // loops of the slowest lane in each); with one loop it is the number of support calls of the longest test.  Per lane the statements,
 // their order and their operands are the original's.
-template <int MESH = 1, int GROUP = 1>
+template <int MESH = 1, int GROUP = 1, int BOX = 0>
 __device__ __forceinline__ bool mpr_penetration(const CObj& o1, const CObj& o2, int max_iterations, double tolerance, float& depth_out, V3& pdir_out, V3& pos_out) {
   CSup P0, P1, P2, P3;
   const V3d origin = {0.0, 0.0, 0.0};
@@ -334,7 +362,7 @@ __device__ __forceinline__ bool mpr_penetration(const CObj& o1, const CObj& o2, 
 #ifdef HB_NARROW_DIAG
     if (diag_calls++ >= g_mpr_limit[0]) break;
 #endif
-    const CSup s = mpr_support<MESH, GROUP>(o1, o2, dir);
+    const CSup s = mpr_support<MESH, GROUP, BOX>(o1, o2, dir);
     if (state == S_P1) {
       P1 = s;
       const double dt = dot(P1.v, dir);

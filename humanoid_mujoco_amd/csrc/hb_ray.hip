@@ -59,6 +59,27 @@ __device__ __forceinline__ float ray_capsule(V3 o, V3 d, float r, float half) {
   }
   return best;
 }
+// A box of half extents h: the six faces (the slab test, face by face, as mj_rayGeom walks them).  A face is hit where the ray crosses its
+// plane inside the other two extents; the nearest non-negative crossing counts, so a ray from outside gets the face it enters by and one
+// that starts inside the face it leaves by, as for the sphere and the capsule.  A ray parallel to a pair of faces cannot cross them.  eps
+// widens a face by what the crossing point is known to: a ray through an edge is found from either face and never slips between two.
+__device__ __forceinline__ float ray_box(V3 o, V3 d, V3 h) {
+  float best = kRayNone;
+  const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z}, hh[3] = {h.x, h.y, h.z};
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    if (dd[a] == 0.f) continue;
+    const int b = (a + 1) % 3, c = (a + 2) % 3;
+    const float inv = 1.f / dd[a];
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+      const float t = ((s ? hh[a] : -hh[a]) - oo[a]) * inv;
+      const float eb = 1e-6f * (hh[b] + fabsf(oo[b])), ec = 1e-6f * (hh[c] + fabsf(oo[c]));
+      ray_take(best, t, fabsf(oo[b] + t * dd[b]) <= hh[b] + eb && fabsf(oo[c] + t * dd[c]) <= hh[c] + ec);
+    }
+  }
+  return best;
+}
 
 // One triangle of a grid cell, in the cell's coordinates (u along the columns, v along the rows, both 0..1): the surface is
 // z = z0 + a u + b v over v <= u (LOWER) or v >= u; the ray is (u0 + t du, v0 + t dv, oz + t dz).  Both faces are hit.  eps widens the
@@ -173,6 +194,7 @@ __device__ __forceinline__ void ray_body(const DevModel* Mp, const RayArgs& A) {
     if (type == 0) t = ray_plane(lo, ld, s0, s1);
     else if (type == 2) t = ray_sphere(lo, ld, s0);
     else if (type == 3) t = ray_capsule(lo, ld, s0, s1);
+    else if (type == 6) t = ray_box(lo, ld, {s0, s1, M.geom_size[3 * g + 2]});
     else if (type == 1) {
       const int hid = M.geom_dataid[g];
       const float* data = (LDS != 0 ? (const float*)lds : hglobal) + M.hfield_adr[hid];

@@ -26,7 +26,7 @@ namespace hb {
 // SOLVER: mjtSolver of the instantiation (0 = PGS, 2 = Newton); everything outside the constraint solve, the mass-matrix
 // factorisation and the integrator's damped solve is shared.
 // COLL: 0 = the classic narrowphase (plane / sphere / capsule pairs, condim 1 / 3, inline), 1 = the general one (adds mesh hulls and
-// height-field prisms through MPR, condim 4 / 6).  NG: constraint rows live in NG groups of 64 (lane l owns rows l + 64 g); NG > 1
+// height-field prisms through MPR, condim 4 / 6), 2 = the general one with the box colliders (HB_BOX_KERNELS: a model with box geoms).  NG: constraint rows live in NG groups of 64 (lane l owns rows l + 64 g); NG > 1
 // only with the Newton solver (kBigGroups: 256 rows, for the reference's own robot: ten pyramid rows per condim-6 contact).
 // DEFER: the fast pass of a staged step.  1 (variant 2, StageBufs::dm_fast): an env-step that overflows this instantiation's rows or
 // contacts is not stepped here but flagged for the four-group kernel.  2 (variant 1): same capacities as the full kernel, nothing to
@@ -90,7 +90,8 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   static_assert(ACC == 0 || (LEAN == 0 && SIZED == 0 && INV == 0), "the body-acceleration read-out: full kernels only");
   static_assert(FRIC == 0 || (COLL == 0 && NG == 1 && DEFER == 0 && LEAN == 0 && SIZED == 0 && INTEG == 0 && ACC == 0), "friction loss: the full Euler kernels of the classic variant");
   static_assert(INTEG == 0 || (COLL == 0 && NG == 1 && DEFER == 0 && LEAN == 0 && SIZED == 0 && INV == 0), "RK4: the full kernels of the classic variant");
-  static_assert(NG == 1 || SOLVER == 2 || (COLL == 1 && NG == kPgsGroups && DEFER == 0), "PGS on more than one row group: the general variant's kPgsGroups instantiation");
+  static_assert(COLL != 2 || (DEFER == 0 && INV == 0 && LEAN == 0 && SIZED == 0), "box colliders: the full kernels of the general variants (the others only append results)");
+  static_assert(NG == 1 || SOLVER == 2 || (COLL != 0 && NG == kPgsGroups && DEFER == 0), "PGS on more than one row group: the general variant's kPgsGroups instantiation");
   constexpr int kNR = NG == 1 ? kNefcMax : 64 * NG;  // row capacity of this instantiation
   constexpr int kNC = NG == 1 ? kNconMax : kBigNconMax;  // contact capacity
   // the model tables are read through a constant-address-space pointer (not by-value kernel
@@ -699,7 +700,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
         // staged step: the narrowphase ran in its own kernel on this step's poses (launch_step); the second forward pass of a step
         // whose first one was reset (mj_checkAcc) runs on other poses and does its own
         if (DEFER != 0 || (P.stage.result && !redo)) ncon = collide_gather<kNC>(M, lane, env, P.stage, s_gaxis, s_con, status);  // (DEFER: always staged, never a second pass)
-        else ncon = collide_general<kNC>(M, dr ? dr + DL.o_hfield : (const float*)M.hfield_data, lane, s_gpos, s_gaxis, s_gquat, s_con, reinterpret_cast<int*>(s_C), status);
+        else ncon = collide_general<kNC, COLL == 2 ? 1 : 0>(M, dr ? dr + DL.o_hfield : (const float*)M.hfield_data, lane, s_gpos, s_gaxis, s_gquat, s_con, reinterpret_cast<int*>(s_C), status);
       }
     } else if (contacts_on) {
       // Two passes.  (1) Broadphase over every candidate pair - bounding spheres, or distance to the plane - with the
@@ -2339,6 +2340,20 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   K(hb_eq_inverse_kernel,             2,      28,     0,    1,          0,     0,    0,     1,   0,     0,   2,    2,     0,     0)       \
   K(hb_eq_inverse32_kernel,           2,      32,     0,    1,          0,     0,    0,     1,   0,     0,   2,    2,     0,     0)
 
+// ---- The same for a model with box geoms (DevModel::has_box; COLL 2): the kernels above that collide inside the step - the full kernels of
+// the general variants and their body-acceleration twins - once more with the box colliders (hb_collide.hpp: BOX).  A table of its own, so
+// that no kernel of a model without boxes holds a line of box code or is chosen differently; the fast passes and the inverse kernels only
+// append the results of the pose / narrowphase launches (hb_narrow.hip: the *_box_kernel ones) and serve both.
+#define HB_BOX_KERNELS(K)                                                                                                                 \
+  K(hb_box_gen_kernel,                0,      28,     2,    1,          0,     0,    0,     0,   0,     0,   0,    2,     0,     1)       \
+  K(hb_box_gen_big_kernel,            0,      28,     2,    kPgsGroups, 0,     0,    0,     0,   0,     0,   0,    1,     0,     1)       \
+  K(hb_box_newton_big20_kernel,       2,      20,     2,    kBigGroups, 0,     0,    0,     0,   0,     0,   0,    1,     0,     1)       \
+  K(hb_box_newton_big28_kernel,       2,      28,     2,    kBigGroups, 0,     0,    0,     0,   0,     0,   0,    1,     0,     1)       \
+  K(hb_box_acc_gen_kernel,            0,      28,     2,    1,          0,     0,    0,     0,   0,     1,   0,    2,     0,     1)       \
+  K(hb_box_acc_gen_big_kernel,        0,      28,     2,    kPgsGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)       \
+  K(hb_box_acc_newton_big20_kernel,   2,      20,     2,    kBigGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)       \
+  K(hb_box_acc_newton_big28_kernel,   2,      28,     2,    kBigGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)
+
 // (the entry calls step_body directly: a forwarding function template in between changes register allocation and scheduling; every kernel
 // has the one signature - launch_pass hands all of them three arguments - and an INV row runs a single step whatever the count says)
 #define HB_STEP_BODY_0(S, ND, C, G, D, L, Z, I, N, A, F) step_body<S, ND, C, G, D, L, Z, I, N, A, F>(Mp, P, I ? 1 : nsteps)
@@ -2346,6 +2361,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
 #define HB_DEFINE(name, S, ND, C, G, D, L, Z, I, N, A, F, W, V, R) \
   __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_BODY_##R(S, ND, C, G, D, L, Z, I, N, A, F); }
 HB_KERNELS(HB_DEFINE)
+HB_BOX_KERNELS(HB_DEFINE)
 
 struct StepConfig {
   int solver, ndense, coll, ng, defer, lean, sized, inv, integ, acc, fric;
@@ -2354,8 +2370,10 @@ struct StepConfig {
 struct StepKernel { const char* name; const void* fn; StepConfig cfg; bool rerun; };
 #define HB_ROW(name, S, ND, C, G, D, L, Z, I, N, A, F, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, N, A, F}, R != 0},
 static const StepKernel kStepKernels[] = {HB_KERNELS(HB_ROW)};
+static const StepKernel kBoxKernels[] = {HB_BOX_KERNELS(HB_ROW)};
 static const StepKernel* find_step_kernel(const StepConfig& c) {
   for (const StepKernel& k : kStepKernels) if (k.cfg == c) return &k;
+  for (const StepKernel& k : kBoxKernels) if (k.cfg == c) return &k;
   return nullptr;
 }
 
@@ -2426,6 +2444,9 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, const DevMod
   c.lean = (nsteps == 1 && lean_launch(P)) ? 1 : lean_launch(P, true) ? 2 : 0;
   c.sized = c.lean && sized_ok;
   c.acc = P.body_acc ? 1 : 0;  // (never lean: lean_launch; the full kernel of the same row with the body-acceleration read-out)
+  // a model with box geoms: the kernels that collide inside the step are the COLL 2 ones (HB_BOX_KERNELS); a launch that cannot be
+  // lean takes the full kernel, so the lean and size-specialised forms (which only gather) are looked for first as they are
+  if (M.has_box && c.coll && c.defer == 0) { c.coll = 2; c.lean = 0; c.sized = 0; }
   const StepKernel* k = find_step_kernel(c);
   if (!k && c.sized) { c.sized = 0; k = find_step_kernel(c); }
   if (!k && c.lean) { c.lean = 0; k = find_step_kernel(c); }
@@ -2508,9 +2529,13 @@ hipError_t launch_inverse(const DevModel* M_dev, const DevModel& M, const BatchP
   }
   return launch_pass(StepPass::Inverse, M_dev, M, P, 1, stream, kernel);
 }
-// every step and inverse instantiation: a layout over 64 KB must launch whichever of them the dispatch picks
+// every step and inverse instantiation, of both tables: a layout over 64 KB must launch whichever of them the dispatch picks
 hipError_t set_step_lds_limit(int bytes) {
   for (const StepKernel& k : kStepKernels) {
+    const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return e;
+  }
+  for (const StepKernel& k : kBoxKernels) {
     const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) return e;
   }

@@ -254,6 +254,7 @@ std::vector<double> geom_half_extents(const Model& m) {
     h[0] = h[1] = h[2] = m.geom_rbound[g];
     if (m.geom_type[g] == GEOM_SPHERE) h[0] = h[1] = h[2] = m.geom_size[3 * g];
     else if (m.geom_type[g] == GEOM_CAPSULE) { h[0] = h[1] = m.geom_size[3 * g]; h[2] = m.geom_size[3 * g] + m.geom_size[3 * g + 1]; }
+    else if (m.geom_type[g] == GEOM_BOX) { for (int c = 0; c < 3; c++) h[c] = m.geom_size[3 * g + c]; }  // the box itself: its colliders read their three sizes here
     else if (m.geom_type[g] == GEOM_MESH && m.geom_dataid[g] >= 0) {
       const int k = m.geom_dataid[g];
       h[0] = h[1] = h[2] = 0.0;
@@ -518,7 +519,7 @@ bool model_variant(const Model& m, int& variant, int& ncon_max, int& nefc_max, s
   for (int p = 0; p < m.npair; p++) {
     const int g1 = m.pair_geom1[p], g2 = m.pair_geom2[p];
     const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
-    if (t1 == GEOM_MESH || t2 == GEOM_MESH || t1 == GEOM_HFIELD || t2 == GEOM_HFIELD) general = true;
+    if (t1 == GEOM_MESH || t2 == GEOM_MESH || t1 == GEOM_HFIELD || t2 == GEOM_HFIELD || t1 == GEOM_BOX || t2 == GEOM_BOX) general = true;
     const int dim = pair_condim(m, g1, g2);
     if (dim != 1 && dim != 3) { general = true; wide = true; }
   }
@@ -570,6 +571,8 @@ bool build_model_tables(const Model& m, HostTables& H, std::string& err) {
   TF(geom_size, m.geom_size); TF(geom_pos, m.geom_pos); TF(geom_quat, m.geom_quat); TF(geom_rbound, m.geom_rbound);
   TF(geom_half, geom_half_extents(m));
   dm.box_cull = !(getenv("HB_BOX_CULL") && atoi(getenv("HB_BOX_CULL")) == 0);
+  dm.has_box = 0;
+  for (int p = 0; p < m.npair; p++) if (m.geom_type[m.pair_geom1[p]] == GEOM_BOX || m.geom_type[m.pair_geom2[p]] == GEOM_BOX) dm.has_box = 1;
   TI(pair_geom1, m.pair_geom1); TI(pair_geom2, m.pair_geom2); TI(pair_dim, P.dim); TI(pair_self, P.self);
   TF(pair_fricab, P.fricab);
   TF(pair_friction, P.fr); TF(pair_solref, P.solref); TF(pair_solimp, P.solimp); TF(pair_margin, P.margin); TF(pair_gap, P.gap);

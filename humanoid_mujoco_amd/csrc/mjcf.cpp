@@ -190,6 +190,7 @@ void geom_inertia(GeomTmp& g, double density, double mass_attr) {
   if (g.type == GEOM_SPHERE) vol = 4.0 / 3.0 * PI * r * r * r;
   else if (g.type == GEOM_CAPSULE) vol = PI * r * r * (2 * h) + 4.0 / 3.0 * PI * r * r * r;
   else if (g.type == GEOM_CYLINDER) vol = PI * r * r * (2 * h);
+  else if (g.type == GEOM_BOX) vol = 8.0 * g.size[0] * g.size[1] * g.size[2];
   else vol = 0;
   // (a mesh geom: volume and principal moments of its hull, in whose centre-of-mass / principal frame the geom already sits: compile_geom)
   if (g.type == GEOM_MESH) vol = g.mesh_volume;
@@ -215,6 +216,11 @@ void geom_inertia(GeomTmp& g, double density, double mass_attr) {
     const double height = 2 * h;
     g.inertia[0] = g.inertia[1] = mass * (3 * r * r + height * height) / 12.0;
     g.inertia[2] = mass * r * r / 2.0;
+  } else if (g.type == GEOM_BOX) {  // the solid box: m / 3 (hy^2 + hz^2, hx^2 + hz^2, hx^2 + hy^2)
+    const double x2 = g.size[0] * g.size[0], y2 = g.size[1] * g.size[1], z2 = g.size[2] * g.size[2];
+    g.inertia[0] = mass * (y2 + z2) / 3.0;
+    g.inertia[1] = mass * (x2 + z2) / 3.0;
+    g.inertia[2] = mass * (x2 + y2) / 3.0;
   }
 }
 
@@ -244,12 +250,14 @@ bool add_geom(Ctx& c, const XmlNode& n, int body, const std::string& childclass,
   else if (ts == "capsule") type = GEOM_CAPSULE;
   else if (ts == "hfield") type = GEOM_HFIELD;
   else if (ts == "mesh") type = GEOM_MESH;
+  else if (ts == "box") type = GEOM_BOX;
   else if (ts == "cylinder") type = GEOM_CYLINDER;  // accepted as a non-colliding (visual) geom only: build_pairs refuses it in a collision pair
-  else return c.fail("mjcf: geom type '" + ts + "' is not supported (plane, sphere, capsule, hfield, mesh; cylinder when non-colliding) in " + a.where);
+  else return c.fail("mjcf: geom type '" + ts + "' is not supported (plane, sphere, capsule, box, hfield, mesh; cylinder when non-colliding) in " + a.where);
   GeomTmp g;
   g.type = type;
   g.size[0] = g.size[1] = g.size[2] = 0;
-  if (a.vec("size", g.size, 3) < 0) return false;
+  const int nsize = a.vec("size", g.size, 3);
+  if (nsize < 0) return false;
   g.pos[0] = g.pos[1] = g.pos[2] = 0;
   if (a.vec("pos", g.pos, 3, 3) < 0) return false;
   if (!read_orientation(c, a, g.quat)) return false;
@@ -267,6 +275,7 @@ bool add_geom(Ctx& c, const XmlNode& n, int body, const std::string& childclass,
   }
   if (type == GEOM_SPHERE && g.size[0] <= 0) return c.fail("mjcf: sphere needs size>0 in " + a.where);
   if (type == GEOM_CAPSULE && (g.size[0] <= 0 || g.size[1] <= 0)) return c.fail("mjcf: capsule needs radius and half-length in " + a.where);
+  if (type == GEOM_BOX && !(nsize == 3 && g.size[0] > 0 && g.size[1] > 0 && g.size[2] > 0)) return c.fail("mjcf: box needs three positive half extents in size in " + a.where);
   int dataid = -1;
   if (type == GEOM_MESH) {
     // MuJoCo collides a mesh geom through the convex hull of its mesh (mesh.cpp), and its compiler re-centres a mesh on its centre of mass
@@ -312,6 +321,7 @@ bool add_geom(Ctx& c, const XmlNode& n, int body, const std::string& childclass,
   if (type == GEOM_SPHERE) rb = g.size[0];
   else if (type == GEOM_CAPSULE) rb = g.size[0] + g.size[1];
   else if (type == GEOM_CYLINDER) rb = std::sqrt(g.size[0] * g.size[0] + g.size[1] * g.size[1]);
+  else if (type == GEOM_BOX) rb = std::sqrt(g.size[0] * g.size[0] + g.size[1] * g.size[1] + g.size[2] * g.size[2]);
   else if (type == GEOM_MESH) rb = c.mesh_rbound[dataid];
   else if (type == GEOM_HFIELD) {
     const double* hs = &m.hfield_size[4 * dataid];
@@ -899,8 +909,8 @@ void build_pairs(Model& m) {
       int a = g1, b = g2;
       if (t1 > t2) { std::swap(a, b); std::swap(t1, t2); }
       if (t2 == GEOM_PLANE || t2 == GEOM_HFIELD) continue;  // plane-plane, plane-hfield, hfield-hfield: no collider
-      if (t1 == GEOM_CYLINDER || t2 == GEOM_CYLINDER || t1 == GEOM_ELLIPSOID || t2 == GEOM_ELLIPSOID || t1 == GEOM_BOX || t2 == GEOM_BOX) {
-        m.pair_unsupported = "collision between geoms '" + m.geom_name[a] + "' and '" + m.geom_name[b] + "': cylinder / ellipsoid / box colliders are not implemented";
+      if (t1 == GEOM_CYLINDER || t2 == GEOM_CYLINDER || t1 == GEOM_ELLIPSOID || t2 == GEOM_ELLIPSOID) {
+        m.pair_unsupported = "collision between geoms '" + m.geom_name[a] + "' and '" + m.geom_name[b] + "': cylinder / ellipsoid colliders are not implemented";
         continue;
       }
       m.pair_geom1.push_back(a);

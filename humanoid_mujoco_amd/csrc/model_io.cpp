@@ -226,9 +226,10 @@ bool validate_model(const Model& m, std::string& err) {
   for (int g = 0; g < m.ngeom; g++) {
     if (!in(m.geom_bodyid[g], 0, m.nbody)) return bad("geom_bodyid out of range");
     const int t = m.geom_type[g];
-    if (t != GEOM_PLANE && t != GEOM_HFIELD && t != GEOM_SPHERE && t != GEOM_CAPSULE && t != GEOM_MESH && t != GEOM_CYLINDER) return bad("geom type not supported");
+    if (t != GEOM_PLANE && t != GEOM_HFIELD && t != GEOM_SPHERE && t != GEOM_CAPSULE && t != GEOM_MESH && t != GEOM_CYLINDER && t != GEOM_BOX) return bad("geom type not supported");
     if (t == GEOM_HFIELD && !in(m.geom_dataid[g], 0, m.nhfield)) return bad("height-field geom without a valid field");
     if (t == GEOM_MESH && !in(m.geom_dataid[g], 0, m.nmesh)) return bad("mesh geom without a valid mesh");
+    if (t == GEOM_BOX && !(m.geom_size[3 * g] > 0 && m.geom_size[3 * g + 1] > 0 && m.geom_size[3 * g + 2] > 0)) return bad("box geom without three positive half extents");
     const int cd = m.geom_condim[g];
     if (cd != 1 && cd != 3 && cd != 4 && cd != 6) return bad("geom condim must be 1, 3, 4 or 6");
   }

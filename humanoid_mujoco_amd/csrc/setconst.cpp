@@ -190,7 +190,7 @@ void jac_point(const Model& m, const Kin& k, double* jacp, double* jacr, const d
 
 bool set_const(Model& m, std::string& err) {
   int nv = m.nv, nb = m.nbody;
-  if (nv == 0) { err = "model has no degrees of freedom"; return false; }
+  if (nv == 0) { err = "model has no degrees of freedom: a model without joints is not supported"; return false; }
   Kin k;
   position_stage(m, m.qpos0.data(), k);
   // subtree mass

@@ -61,7 +61,7 @@ class HbJacSpec(ctypes.Structure):
 MAX_JAC, JAC_POINT, JAC_SUBTREE_COM = 16, 0, 1
 RAY_STATIC, RAY_MOVING = 1, 2
 RAY_FRAMES = {"world": 0, "body": 1, "yaw": 2}
-RAY_SURFACES = (0, 1, 2, 3)  # geom types a ray intersects: plane, height field, sphere, capsule
+RAY_SURFACES = (0, 1, 2, 3, 6)  # geom types a ray intersects: plane, height field, sphere, capsule, box
 
 
 def height_scan_rays(xs, ys, z0=1.0):
@@ -840,10 +840,10 @@ class Batch:
         m = self.model
         gtype, gbody = m.array("geom_type").astype(int), m.array("geom_bodyid").astype(int)
         marker = (m.array("geom_contype") == 0) & (m.array("geom_conaffinity") == 0)
-        names = {5: "cylinder", 7: "mesh", 6: "box", 4: "ellipsoid"}
+        names = {5: "cylinder", 7: "mesh", 4: "ellipsoid"}
         for g in range(m.ngeom):
             if gbody[g] != bodyexclude and (flags & (RAY_STATIC if gbody[g] == 0 else RAY_MOVING)) and gtype[g] not in RAY_SURFACES and not marker[g]:
-                return ("geom %d (%s, a %s geom of body %r) would be eligible and rays intersect planes, height fields, spheres and capsules only"
+                return ("geom %d (%s, a %s geom of body %r) would be eligible and rays intersect planes, height fields, spheres, capsules and boxes only"
                         % (g, m.id2name("geom", g) or "unnamed", names.get(int(gtype[g]), "type %d" % gtype[g]), m.id2name("body", int(gbody[g]))))
         return None
 

@@ -85,7 +85,13 @@ typedef struct hb_sizes {
 /* ---- model --------------------------------------------------------------------------------- */
 
 /* Replaces mj_loadXML (mujoco.h:103) / mj_loadModel (mujoco.h:163).  `path` ends in ".xml"
- * (MJCF subset, compiled on the host) or ".hbm" (this engine's compiled text model). */
+ * (MJCF subset, compiled on the host) or ".hbm" (this engine's compiled text model).
+ * Geoms that collide: plane, sphere, capsule, box (mjGEOM_BOX, size = three half extents), mesh (through its convex hull) and height
+ * field; a cylinder only as a non-colliding marker.  A model with a colliding box steps in the kernels of the general collision path
+ * (hb_last_kernel: hb_box_* / the staged step's fast pass), as a mesh model does: at most 28 dofs, Euler, no friction loss or equality
+ * rows.  plane - box (up to four corner contacts) and sphere - box are MuJoCo's analytic routines; capsule - box, box - box, box - mesh
+ * and height field - box go through the portal search.  DEVIATION from MuJoCo: capsule - box and box - box give ONE contact per pair
+ * where mjc_CapsuleBox / mjc_BoxBox give up to 2 and 8 (a clipped box - box manifold is the follow-up). */
 hb_model* hb_model_load(const char* path, char* err, int err_sz);
 /* Replaces mj_loadXML with an in-memory string (mjVFS use in the reference). */
 hb_model* hb_model_load_xml_string(const char* xml, char* err, int err_sz);
@@ -308,12 +314,14 @@ int hb_dynamics_states_dev(hb_batch* b, const float* qpos_dev, const float* qvel
  *   plane        the z = 0 plane of the geom frame, hit from either side, inside size[0..1] where those are > 0
  *   sphere       the smallest non-negative root; from inside that is the exit point
  *   capsule      likewise, on the cylinder wall between the caps and the outer halves of the two end spheres
+ *   box          the six faces in the geom's frame (the slab test): the nearest non-negative crossing of a face's plane inside the
+ *                other two half extents - from outside the face the ray enters by, from inside the one it leaves by
  *   height field the elevation surface, triangulated exactly as the collider triangulates it: cell (r, c) is cut along the diagonal
  *                (r, c) - (r + 1, c + 1).  Both faces are hit.  With per-env elevations installed (hb_env_domain_randomize with
  *                floor_bump_max > 0) the env's OWN elevations are used.  The field's side walls and base are NOT intersected - a
  *                departure from MuJoCo, which also tests the field's bounding box: a ray that passes under the surface from the side
  *                sees the surface from below, or nothing.
- * Mesh and cylinder geoms (and box and ellipsoid ones) are not intersected: a configuration under which a geom of such a type would be
+ * Mesh and cylinder geoms (and ellipsoid ones) are not intersected: a configuration under which a geom of such a type would be
  * eligible is refused with HB_EUNSUPPORTED (Batch.ray_configure names the geom), e.g. HB_RAY_MOVING on the reference's robot, whose
  * HB_RAY_STATIC configurations see its height-field floor.  The one exception: a geom of such a type that collides with nothing (contype
  * and conaffinity both 0 - a visual marker, like the axis cylinders of the reference's world) is skipped, not refused.  A refused configuration (HB_EUNSUPPORTED or HB_EINVAL) leaves the previous
