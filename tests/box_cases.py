@@ -1,6 +1,6 @@
-"""The box scene, its MESH TWIN and the case table (tests/test_box_cpu.py, tests/test_gpu_box.py).
+"""The box scene, its MESH TWIN, the case table and its references (tests/test_box_cpu.py, tests/test_gpu_box.py).
 
-TEST INFRASTRUCTURE, pure numpy.  scene_xml(variant, twin) is one MJCF text: a TILTED plane, a small flat height field 30 m away, a
+TEST INFRASTRUCTURE.  The scene and the table are pure numpy.  scene_xml(variant, twin) is one MJCF text: a TILTED plane, a small flat height field 30 m away, a
 static box W, and four free bodies in geom order P (box), S (sphere), Q (box of other proportions), X (a capsule; in the "mesh"
 variant a small mesh hull).  A model may have 28 dofs, so the capsule and the hull take turns on the fourth body.  twin=True writes the
 same scene with every box replaced by a mesh of its eight corners: the form the fp64 oracle can load.  Every body has an explicit
@@ -10,12 +10,16 @@ build_cases(info, variant): a case is a name, its kind, the two geoms under test
 Exactly one pair is in range per case; the other bodies are parked along the plane's normal, 6 m apart.  Portal-search pairs are built on
 a face of the first box: the second geom's deepest point (its support point along the face's inward normal) stands over the face's
 interior at a chosen gap, which then is the true distance of the two geoms.
+
+reference(hbmod, variant, directory) is what the device is held to: box_ref for the analytic kinds, the fp64 oracle on the mesh twin
+(class Twin) for the portal-search kinds, each with its conditioning envelope (pair_cases.evaluations).
 """
 import numpy as np
 
 import box_ref
 import pair_ref
-from pair_cases import _f32, _q_z_to, _qaxis, _qmul, _qrand
+from oracle_lib import Oracle, load_state, parse_hbm
+from pair_cases import _f32, _q_z_to, _qaxis, _qmul, _qrand, evaluations, state_of
 
 MARGIN = 0.01
 HALF = {"W": (0.30, 0.20, 0.10), "P": (0.10, 0.06, 0.04), "Q": (0.05, 0.12, 0.08)}
@@ -236,3 +240,148 @@ def stairs_xml(twin=False, solver="PGS", nsteps=NSTEPS):
             '<body name="brick" pos="-0.8 0.1 %g"><freejoint name="brick"/><inertial pos="0 0 0" mass="%g" diaginertia="0.006 0.012 0.014"/>%s</body>'
             '</worldbody><actuator>%s</actuator></mujoco>\n'
             % (opt, asset, steps, box("torso"), legs, BRICK_HALF[2] + 0.001, BRICK_MASS, box("brick"), motors))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the references
+ANALYTIC = ("plane-box", "sphere-box")
+ROWS_PER_CONTACT = {1: 1, 3: 4, 4: 6, 6: 10}
+_cache = {}
+
+
+def compiled(hbmod, variant, directory):
+    """[model, .hbm path, parsed .hbm] of a scene variant, then the same three of its mesh twin"""
+    out = []
+    for twin in (False, True):
+        m = hbmod.Model.from_xml_string(scene_xml(variant, twin))
+        p = str(directory / ("boxes_%s%s.hbm" % (variant, "_twin" if twin else "")))
+        m.save(p)
+        out += [m, p, parse_hbm(p)]
+    return out
+
+
+def analytic(info, qpos, geoms, labels=None, tests=None):
+    """box_ref on the pair under test of an analytic case, as Oracle.contacts() would list it"""
+    gpos, gmat = pair_ref.geom_poses(info, qpos)
+    g1, g2 = geoms
+    size = info["geom_size"].reshape(-1, 3)
+    margin = max(info["geom_margin"][g1], info["geom_margin"][g2])
+    dim = int(max(info["geom_condim"][g1], info["geom_condim"][g2]))
+    if info["geom_type"][g1] == box_ref.GEOM_PLANE:
+        con = box_ref.plane_box(margin, gpos[g1], gmat[g1][:, 2], gpos[g2], gmat[g2], size[g2], labels, tests)
+    else:
+        c = box_ref.sphere_box(margin, gpos[g1], size[g1][0], gpos[g2], gmat[g2], size[g2], labels, tests)
+        con = [c] if c else []
+    return [dict(dist=c["dist"], pos=c["pos"], frame=c["normal"][None, :], dim=dim, geom1=int(g1), geom2=int(g2)) for c in con]
+
+
+class Twin:
+    """The fp64 oracle on a scene's mesh twin, spoken to in the BOX model's terms: states in the box model's qpos / qvel order, contacts
+    with the box model's geom ids.  For most scenes the twin has the box model's bodies in the same order and nothing is permuted.  The
+    xfirst_mesh scene (hull X ahead of the boxes) cannot use its own twin: the device collides (box, hull) - geom type order - and a twin
+    made of meshes alone would collide (hull, box) - geom id order - and the portal search is not symmetric in its two objects (measured in
+    the oracle: depth apart by up to 1e-2 on deep random overlaps).  Its twin is the "mesh" scene's, X behind the boxes, where the order
+    is (box, hull) too; bodies and geoms are matched by name."""
+
+    def __init__(self, info, tpath):
+        self.o = Oracle(tpath)
+        ti = self.o.info
+        self.nv, self.nu = self.o.nv, self.o.nu
+        self.geom = {g: list(info["geom_name"]).index(n) for g, n in enumerate(ti["geom_name"])}  # twin geom id -> box model's
+        self.qmap, self.vmap = np.zeros(self.o.nq, dtype=int), np.zeros(self.o.nv, dtype=int)     # twin index -> box model's index
+        for b, name in enumerate(ti["body_name"]):
+            if b == 0:
+                continue
+            bb = list(info["body_name"]).index(name)
+            jt, jb = ti["body_jntadr"][b], info["body_jntadr"][bb]
+            self.qmap[ti["jnt_qposadr"][jt]:ti["jnt_qposadr"][jt] + 7] = np.arange(7) + info["jnt_qposadr"][jb]
+            self.vmap[ti["jnt_dofadr"][jt]:ti["jnt_dofadr"][jt] + 6] = np.arange(6) + info["jnt_dofadr"][jb]
+        self.same_order = bool((self.qmap == np.arange(self.o.nq)).all())
+
+    def load(self, qpos):
+        load_state(self.o, state_of(self.o, np.asarray(qpos)[self.qmap]), np.zeros(self.o.nu))
+
+    def forward(self):
+        self.o.forward()
+
+    def step(self):
+        self.o.step()
+
+    @property
+    def ncon(self):
+        return self.o.ncon
+
+    @property
+    def nefc(self):
+        return self.o.nefc
+
+    def contacts(self):
+        out = self.o.contacts()
+        for c in out:
+            c["geom1"], c["geom2"] = self.geom[c["geom1"]], self.geom[c["geom2"]]
+        return out
+
+    def _back(self, x, m):
+        out = np.zeros(len(x))
+        out[m] = x
+        return out
+
+    @property
+    def qpos(self):
+        return self._back(self.o.qpos, self.qmap)
+
+    @property
+    def qvel(self):
+        return self._back(self.o.qvel, self.vmap)
+
+
+def _evaluate(ref, case, qpos):
+    if case["kind"] in ANALYTIC:
+        con = analytic(ref["info"], qpos, case["geoms"])
+        return dict(qpos=qpos, ncon=len(con), nefc=len(con) * ROWS_PER_CONTACT[con[0]["dim"]] if con else 0, con=con)
+    o = ref["oracle"]
+    o.load(qpos)
+    o.forward()
+    return dict(qpos=qpos, ncon=o.ncon, nefc=o.nefc, con=o.contacts())
+
+
+def reference(hbmod, variant, directory):
+    """dict(model, info, twin_info, oracle (on the twin), cases, evals, ill): evals[i] lists case i's reference evaluations, the unperturbed
+    one first (an exact case has no other) - box_ref for the analytic kinds, the oracle on the mesh twin for the portal-search kinds"""
+    if variant in _cache:
+        return _cache[variant]
+    m, p, info, _, tp, tinfo = compiled(hbmod, variant, directory)
+    if variant == "xfirst_mesh":  # (class Twin: the twin with X behind the boxes)
+        _, _, _, _, tp, tinfo = compiled(hbmod, "mesh", directory)
+    ref = dict(model=m, path=p, info=info, twin_info=tinfo, oracle=Twin(info, tp), cases=build_cases(info, variant))
+    evals, ill = evaluations(ref["cases"], lambda c, qpos: _evaluate(ref, c, qpos))
+    ref.update(evals=evals, ill=ill)
+    _cache[variant] = ref
+    return ref
+
+
+def twin_agreement(ref):
+    """{case index: same order} of the plane - box cases whose box_ref contacts equal the oracle's plane - hull contacts on the twin to 1e-9
+    as SETS; same order: also in the same order (the hull lists its support vertex first, then that vertex's neighbours; the box its
+    corners in corner order - the PGS solver cut at 50 sweeps is sensitive to the order, DESIGN.md 2, the Newton solver is not)"""
+    o = ref["oracle"]
+    out = {}
+    for i, c in enumerate(ref["cases"]):
+        if c["kind"] != "plane-box":
+            continue
+        o.load(c["qpos"])
+        o.forward()
+        mine, theirs = ref["evals"][i][0]["con"], o.contacts()
+        if len(mine) != len(theirs) or any((t["geom1"], t["geom2"]) != c["geoms"] for t in theirs):
+            continue
+        left = list(range(len(theirs)))
+        order = []
+        for a in mine:
+            k = next((k for k in left if abs(a["dist"] - theirs[k]["dist"]) <= 1e-9 and np.abs(a["pos"] - theirs[k]["pos"]).max() <= 1e-9
+                      and np.abs(a["frame"][0] - theirs[k]["frame"][0]).max() <= 1e-9), None)
+            if k is None:
+                break
+            left.remove(k)
+            order.append(k)
+        else:
+            out[i] = order == sorted(order)
+    return out

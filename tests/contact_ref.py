@@ -165,7 +165,7 @@ CASES = ("humanoid27_pgs", "humanoid27_newton", "humanoid27_pgs_unsized", "chain
 def make_case(hb, name, tmp_path):
     import os
     from kernel_models import chain_xml, oracle_for, rollout_states
-    from oracle_lib import GOLDEN, HUMANOID_HBM, ROOT, Oracle
+    from oracle_lib import GOLDEN, HUMANOID_HBM, TEAM_HBM, Oracle
     if name.startswith("humanoid27"):
         g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
         st = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1).astype(np.float32).astype(np.float64)
@@ -175,7 +175,7 @@ def make_case(hb, name, tmp_path):
             o.set_opt(solver=2, iterations=100)
         return m, o, st, g["ctrl"].astype(np.float32), (dict(sized=0) if name.endswith("unsized") else None)
     if name == "team_robot":
-        p = os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "team_robot.hbm")
+        p = TEAM_HBM
         o = Oracle(p)
         st, ct = team_states(o)
         return hb.Model.load(p), o, st, ct, None

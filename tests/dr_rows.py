@@ -13,14 +13,13 @@ import dr_ref
 import eq_ref
 import fric_ref
 import rk4_ref
+from bounds import BOUNDS  # noqa: F401  (the golden bounds: tests/test_gpu_domain_params.py takes them from here)
 from eq_models import add_equality
+from fric_models import add_friction
 from kernel_models import chain_xml, rollout_states
-from oracle_lib import HUMANOID_HBM, ROOT, Oracle, load_state
-from test_gpu_fric import add_friction
-from test_gpu_kernel_matrix import BOUNDS, CHAINS  # noqa: F401  (the golden bounds and the chain specs are the kernel matrix's own)
+from oracle_lib import HUMANOID_HBM, TEAM_HBM, Oracle, load_state
+from step_lib import CHAINS
 
-ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
-TEAM_HBM = os.path.join(ASSETS, "team_robot.hbm")
 _TMP = None
 N, ROUNDS, T = 8, 4, 5
 FORCERANGE = 0.6   # of the chains' motors (gain 1, ctrl in [-1, 1]): the clamp bites whenever |ctrl| > 0.6 -+ the drawn change
@@ -162,7 +161,7 @@ COMPARED = {"diag": ("qpos", "qvel", "qacc", "force"), "state": ("qpos", "qvel")
 
 
 def deviation(x, r):
-    """the compared quantities of x against the reference step r, each in the normalisation of its bound (test_gpu_kernel_matrix)"""
+    """the compared quantities of x against the reference step r, each in the normalisation of its bound (bounds.BOUNDS)"""
     d = dict(qpos=(np.abs(x["qpos"] - r["qpos"]) / np.maximum(1.0, np.abs(r["qpos"]))).max(), qvel=np.abs(x["qvel"] - r["qvel"]).max() / max(1.0, np.abs(r["qvel"]).max()),
              qacc=np.abs(x["qacc"] - r["qacc"]).max() / max(1.0, np.abs(r["qacc"]).max()))
     if r["nefc"]:

@@ -18,6 +18,20 @@ def obs_from_state(qpos, qvel):
     return np.concatenate([qpos[7:], qvel[6:], qvel[3:6], g]), g
 
 
+# the reference's own robot (simulation_parameters.py:84-103): its observation lists the joints in this order
+JOINT_NAMES = ["right_shoulder_pitch", "right_shoulder_roll", "right_elbow", "left_shoulder_pitch", "left_shoulder_roll", "left_elbow",
+               "left_hip_roll", "left_hip_pitch", "left_knee", "right_hip_roll", "right_hip_pitch", "right_knee"]
+
+
+def team_obs(m, qpos, qvel):
+    """(obs[30] = [q_j(12), qd_j(12), qvel[3:6], R(q_root)' (0, 0, -1)] of the team robot's model m, the dof addresses of its joints)"""
+    jid = [m.name2id("joint", n) for n in JOINT_NAMES]
+    qadr = m.array("jnt_qposadr").astype(int)[jid]
+    dadr = m.array("jnt_dofadr").astype(int)[jid]
+    _, g = obs_from_state(qpos, qvel)
+    return np.concatenate([qpos[qadr], qvel[dadr], qvel[3:6], g]), dadr
+
+
 def standup_reward(cfg, time, qpos, qvel, joint_torques, prev_action, latest_action, self_collision):
     _, g = obs_from_state(qpos, qvel)
     r = cfg.w_hvel * scaled_exp(np.sum((qvel[0:2] - np.array(cfg.target_velocity[:])) ** 2))

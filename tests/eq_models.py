@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE: the product package never imports this module.
 
-The chains: kernel_models.chain_xml at the two dense orders (nv 28 and 32), PGS condim 3 and Newton condim 1, with test_gpu_fric's
+The chains: kernel_models.chain_xml at the two dense orders (nv 28 and 32), PGS condim 3 and Newton condim 1, with fric_models'
 friction loss on top and an <equality> section of nine rows: a linear joint coupling, one with quadratic and cubic terms, a joint1-only
 lock with a0 != 0, a connect between two links six bodies apart, a connect of a late link to the world, and one inactive element.
 The small models: a one-dof slider, a planar four-bar (three hinges, the loop closed by a connect to the world), a geared pendulum pair.
@@ -10,10 +10,12 @@ The small models: a one-dof slider, a planar four-bar (three hinges, the loop cl
 import functools
 import os
 
+import pytest
+
 import eq_ref
+from fric_models import add_friction
 from kernel_models import chain_xml
 from oracle_lib import Oracle
-from test_gpu_fric import add_friction
 
 MODELS = {  # name -> (nv, condim, solver, step kernel, inverse kernel)
     "eq28_cd3_pgs": (28, 3, "PGS", "hb_eq_kernel", "hb_eq_inverse_kernel"),
@@ -69,6 +71,12 @@ def reference(name, tmp):
     o = Oracle(p)
     st, ct = eq_ref.rollout_states(o)
     return p, o, st, ct, eq_ref.steps_ref(o, st, ct)
+
+
+@pytest.fixture(scope="session")
+def eq_tmp(tmp_path_factory):
+    """where reference() and the small models keep their files: imported by name into the test files that use it"""
+    return str(tmp_path_factory.mktemp("eq"))
 
 
 # ---- the small models

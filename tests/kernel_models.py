@@ -1,4 +1,5 @@
-"""Generated models at the sizes where the step kernels' dispatch and their dense, padded code change (tests/test_gpu_kernel_matrix.py).
+"""Generated models at the sizes where the step kernels' dispatch and their dense, padded code change (tests/test_gpu_kernel_matrix.py;
+the chain specs themselves are step_lib.CHAINS).
 
 chain_xml writes a capsule chain in MJCF: a free or a fixed base, two joints per link (hinges on alternating axes, one slide joint), a motor
 on every joint, ranges on every third joint, a plane or a height-field floor.  Only the base and every third link collide, and only with
@@ -14,7 +15,7 @@ import re
 
 import numpy as np
 
-from oracle_lib import ROOT, Oracle, load_state
+from oracle_lib import CSRC, Oracle, load_state
 
 # the columns of a row of HB_KERNELS behind the name: step_body's template arguments (the configuration the dispatch looks a kernel up
 # by), then the launch attributes
@@ -24,7 +25,7 @@ KERNEL_COLUMNS = CONFIG_COLUMNS + ("WAVES", "VGPRS", "RERUN")
 
 def kernel_table():
     """hb_step.hip's kernel table in row order: [(name, {column: the cell's text})]"""
-    lines = open(os.path.join(ROOT, "humanoid_mujoco_amd", "csrc", "hb_step.hip")).read().split("\n")
+    lines = open(os.path.join(CSRC, "hb_step.hip")).read().split("\n")
     first = lines.index(next(ln for ln in lines if ln.startswith("#define HB_KERNELS(K)")))
     last = next(k for k in range(first, len(lines)) if not lines[k].rstrip().endswith("\\"))  # the macro's last line has no continuation
     rows = []
@@ -49,7 +50,7 @@ AXES = ("0 1 0", "0 0 1", "1 0 0")
 
 def chain_xml(nv, free=True, floor="plane", condim=3, solver="PGS", timestep=0.004, forcerange=None):
     """A capsule chain of nv degrees of freedom (6 of them the free base's).  floor: "plane" or "hfield" (the height field of
-    test_oracle_convex._hfield_xml with condim and friction of its own).  PGS runs its 50 sweeps with tolerance 0, as the terrain
+    convex_models.hfield_xml with condim and friction of its own).  PGS runs its 50 sweeps with tolerance 0, as the terrain
     config does: whenever there are rows the sweep counts of device and oracle are the same number.  forcerange: None (no force limits, the XML of
     every caller that does not pass it) or r: every motor forcelimited to [-r, r]."""
     nj = nv - (6 if free else 0)
@@ -94,9 +95,10 @@ def chain_xml(nv, free=True, floor="plane", condim=3, solver="PGS", timestep=0.0
 
 
 def oracle_for(hbmod, xml, tmp_path, name="m.hbm"):
-    """the model, its .hbm path and the fp64 oracle on it (test_oracle_convex._oracle_from_xml)"""
+    """the model compiled from the MJCF text, the .hbm file it was saved to in the directory tmp_path (a path or its text), and the
+    fp64 oracle on that file"""
     m = hbmod.Model.from_xml_string(xml)
-    p = str(tmp_path / name)
+    p = os.path.join(str(tmp_path), name)
     m.save(p)
     return m, p, Oracle(p)
 

@@ -1,6 +1,11 @@
 """ctypes binding of oracle/liboracle.so for the tests, smoke() and bench.py's cpu_baseline leg.
 
 TEST INFRASTRUCTURE: the product package (humanoid_mujoco_amd/) never imports this module.
+
+It is the bottom of the helper modules beside the tests and holds the paths they all use.  The rule for everything under tests/: no
+module imports from a test_*.py file.  What more than one file needs lives in a helper module (a name that does not start with test_,
+a docstring that says test infrastructure); helper modules import each other downwards only - bounds and oracle_lib at the bottom, the
+*_ref restatements and *_models / *_cases above them, step_lib and the learners' *_lib on top - and never a test file.
 """
 import ctypes
 import os
@@ -12,7 +17,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.environ.get("HB_ORACLE_SO") or os.path.join(ORACLE_DIR, "liboracle.so")  # HB_ORACLE_SO: e.g. a sanitizer build (tools/asan_host.sh)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-HUMANOID_HBM = os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "humanoid27.hbm")
+MODELS_DIR = os.path.join(ROOT, "tests", "models")
+ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
+CSRC = os.path.join(ROOT, "humanoid_mujoco_amd", "csrc")
+HUMANOID_HBM = os.path.join(ASSETS, "humanoid27.hbm")
+HFIELD_HBM = os.path.join(ASSETS, "humanoid27_hfield.hbm")
+TEAM_HBM = os.path.join(ASSETS, "team_robot.hbm")
+TEAM_PLANE_HBM = os.path.join(ASSETS, "team_robot_plane.hbm")
+HB_TABLES = os.path.join(ROOT, "build", "hb_tables")            # the host tools (Makefile: build/...; tests/tables_lib.py runs the first)
+HB_LEARN_CHECK = os.path.join(ROOT, "build", "hb_learn_check")
 
 _lib = None
 
@@ -64,6 +77,13 @@ def lib():
         L.om_rollout_window.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, pd]
         _lib = L
     return _lib
+
+
+def golden_states():
+    """the 128 golden states of tests/golden/humanoid27_steps.npz: ([time, qpos, qvel, qacc_warmstart] records, controls, contact counts)"""
+    g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
+    st = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1)
+    return st, g["ctrl"], g["ncon"]
 
 
 def parse_hbm(path):

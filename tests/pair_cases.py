@@ -1,7 +1,7 @@
 """The pair scene and its case table: one plane, two capsules and two spheres on free bodies, every primitive pair placed in a
-chosen configuration (tests/test_pair_cases_cpu.py, tests/test_gpu_narrow_pairs.py).
+chosen configuration (tests/test_pair_cases_cpu.py, tests/test_gpu_narrow_pairs.py), and the oracle's side of it: reference().
 
-TEST INFRASTRUCTURE, pure numpy.  scene_xml(variant) is one MJCF text with a TILTED plane, capsules A and B and spheres S and T
+TEST INFRASTRUCTURE.  The scene and the table are pure numpy.  scene_xml(variant) is one MJCF text with a TILTED plane, capsules A and B and spheres S and T
 of different sizes and a positive geom margin, in four variants by text substitution (VARIANTS).  build_cases(info) returns the
 table for a compiled variant (info: oracle_lib.parse_hbm of its .hbm): a case is a name, the two geoms under test, a full qpos
 already rounded to fp32, the branch labels it is built to take (pair_ref's labels) and whether it is EXACT.  One env is one case.
@@ -12,10 +12,14 @@ random rotation and an offset of order 1 m, so that a capsule's world axis is a 
 not exactly 1).  EXACT cases are those whose decisive operands are bitwise identical on the device and in the oracle: capsules
 that carry the same fp32 quaternion bit pattern (exactly parallel axes), coincident sphere centres, a sphere centre exactly on a
 capsule's axis.  They get no conditioning envelope and no count allowance.
+
+reference(hbmod, variant, directory) is what the device is held to: the oracle on every case, and - the CONDITIONING ENVELOPE - on NPERT
+states whose qpos is perturbed by one fp32 rounding.  evaluations, envelope and state_of serve the box table (tests/box_cases.py) too.
 """
 import numpy as np
 
 import pair_ref
+from oracle_lib import Oracle, load_state, parse_hbm
 
 MARGIN = 0.01
 SIZE = {"A": (0.05, 0.20), "B": (0.04, 0.15), "S": (0.07, 0.0), "T": (0.09, 0.0)}  # radius, half-length
@@ -267,3 +271,117 @@ def build_cases(info):
             pB, qB = world(m[:, 2] * 0.03 + m[:, 0] * (lim - 0.02), _qmul(ql, _qaxis(ax, sgn * ang)))
             add("A-B near-parallel %.0e rad, %s" % (ang, tag), ("A", "B"), {"A": (pA, qA), "B": (pB, qB)})
     return cases
+
+
+# ---------------------------------------------------------------------------------------------------------------- the references
+GUARD = 1e-4  # no case sits on an activation boundary: every activation test the reference makes is further than this off its threshold
+NPERT = 32    # perturbed evaluations per case
+_cache = {}
+
+
+def state_of(o, qpos):
+    """the mjSTATE_INTEGRATION record of a case: at rest at qpos, time 0 (o: anything with nv - an oracle, a model)"""
+    return np.concatenate([[0.0], qpos, np.zeros(2 * o.nv)])
+
+
+def evaluations(cases, evaluate):
+    """(evals, ill) of a case table under evaluate(case, qpos) -> dict(qpos, ncon, nefc, con).  evals[i] lists case i's evaluations, the
+    unperturbed one first; an exact case has no other, every other case NPERT more at qpos + 2^-24 max(1, |qpos|) N(0, 1) - one
+    default_rng(7) per table, drawn in case order.  ill[i]: the evaluations of case i disagree on the contact count."""
+    rng = np.random.default_rng(7)
+    evals, ill = [], []
+    for c in cases:
+        ev = [evaluate(c, c["qpos"])]
+        if not c["exact"]:
+            for _ in range(NPERT):
+                ev.append(evaluate(c, c["qpos"] + 2.0 ** -24 * np.maximum(1.0, np.abs(c["qpos"])) * rng.standard_normal(len(c["qpos"]))))
+        evals.append(ev)
+        ill.append(len({e["ncon"] for e in ev}) > 1)
+    return evals, np.array(ill)
+
+
+def _spread(ref, others):
+    """largest deviation of dist, pos and normal of evaluations with ref's count from ref, per contact: [ncon, 3]"""
+    env = np.zeros((ref["ncon"], 3))
+    for ev in others:
+        if ev["ncon"] != ref["ncon"]:
+            continue
+        for i, (a, b) in enumerate(zip(ref["con"], ev["con"])):
+            env[i] = np.maximum(env[i], (abs(a["dist"] - b["dist"]), np.abs(a["pos"] - b["pos"]).max(), np.abs(a["frame"][0] - b["frame"][0]).max()))
+    return env
+
+
+def envelope(ref, i, ncon):
+    """(the evaluation of case i that a device reporting ncon contacts is held to, its [ncon, 3] envelope), or None when no evaluation
+    the rules allow has that count: the unperturbed reference, or for an ill-conditioned case any of its perturbed evaluations"""
+    ev = ref["evals"][i]
+    pick = next((e for e in ev if e["ncon"] == ncon), None)
+    if pick is None:
+        return None
+    return pick, _spread(pick, [e for e in ev if e is not pick])
+
+
+def compiled(hbmod, variant, directory):
+    """(model, .hbm path, parsed .hbm) of a scene variant"""
+    m = hbmod.Model.from_xml_string(scene_xml(variant))
+    p = str(directory / ("pairs_%s.hbm" % variant))
+    m.save(p)
+    return m, p, parse_hbm(p)
+
+
+def evaluate(o, qpos):
+    """the oracle's contacts at rest at qpos"""
+    load_state(o, state_of(o, qpos), np.zeros(o.nu))
+    o.forward()
+    return dict(qpos=qpos, ncon=o.ncon, nefc=o.nefc, con=o.contacts())
+
+
+def reference(hbmod, variant, directory):
+    """The oracle's side of a scene variant, computed once: dict(model, path, info, cases, evals, ill, oracle).  envelope(ref, i, n) gives
+    the evaluation a device count n is held to and the spread around it."""
+    if variant in _cache:
+        return _cache[variant]
+    m, p, info = compiled(hbmod, variant, directory)
+    o = Oracle(p)
+    cases = build_cases(info)
+    evals, ill = evaluations(cases, lambda c, qpos: evaluate(o, qpos))
+    ref = dict(model=m, path=p, info=info, cases=cases, evals=evals, ill=ill, oracle=o)
+    _cache[variant] = ref
+    return ref
+
+
+# ---------------------------------------------------------------------------------------------------------------- the device's side
+def launch(hbmod, gpu, ref, knobs, diag, tiles=1):
+    """one step of a batch from the cases' states (tiled `tiles` times), one env per case, no controls: what it left.  knobs: Batch.tune's,
+    and body_acc=1 for the body-acceleration read-out; diag: the diagnostic outputs, with the contact records"""
+    m, cases = ref["model"], ref["cases"]
+    st = np.tile(np.stack([state_of(m, c["qpos"]) for c in cases]), (tiles, 1))
+    knobs = dict(knobs)
+    acc = knobs.pop("body_acc", 0)
+    b = hbmod.Batch(m, len(st), gpu)
+    b.tune(**knobs)
+    b.diag_enable(diag)
+    if acc:
+        b.body_acc_readout(True)
+    if tiles > 1:
+        b.pipeline(False)  # one launch over the whole batch: the two-envs-per-wave narrowphase (hb_narrow.hip: launch_pose_narrow)
+    b.set_state(hbmod.STATE_INTEGRATION, st)
+    b.step(np.zeros((len(st), m.nu), dtype=np.float32))
+    out = dict(kernel=b.last_kernel(), counts=b.counts(), status=b.status(), state=b.get_state(hbmod.STATE_INTEGRATION), qpos=b.qpos.astype(np.float64), qvel=b.qvel.astype(np.float64),
+               con=b.contacts().astype(np.float64) if diag else None)
+    b.close()
+    return out
+
+
+def held_to(ref, i, ncon, nefc, bad, who):
+    """the evaluation case i's device counts are held to and its envelope; None, and an entry in bad that names the reference `who`, if
+    the counts match none"""
+    c = ref["cases"][i]
+    got = envelope(ref, i, ncon)
+    if got is None:
+        bad.append((c["name"], "contact count", ncon, who, sorted({e["ncon"] for e in ref["evals"][i]})))
+    elif nefc != got[0]["nefc"]:
+        bad.append((c["name"], "nefc", nefc, who, got[0]["nefc"]))
+    else:
+        return got
+    return None

@@ -14,11 +14,8 @@ import numpy as np
 
 import ray_ref
 from kernel_models import chain_xml, rollout_states
-from oracle_lib import HUMANOID_HBM, Oracle, load_state
+from oracle_lib import HFIELD_HBM, HUMANOID_HBM, TEAM_HBM, Oracle, load_state  # noqa: F401  (HFIELD_HBM: tests take it from here)
 
-ASSETS = os.path.dirname(HUMANOID_HBM)
-HFIELD_HBM = os.path.join(ASSETS, "humanoid27_hfield.hbm")
-TEAM_HBM = os.path.join(ASSETS, "team_robot.hbm")
 FRAMES = {"world": ray_ref.FRAME_WORLD, "body": ray_ref.FRAME_BODY, "yaw": ray_ref.FRAME_YAW}
 BASE = 1  # the chain's base body
 PHASE = {"world": 0.1, "body": 0.32, "yaw": 0.0}

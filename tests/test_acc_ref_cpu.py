@@ -15,18 +15,12 @@ import numpy as np
 import acc_ref
 import rk4_ref
 from kernel_models import KERNEL_COLUMNS, chain_xml, kernel_table, oracle_for, rollout_states
-from oracle_lib import GOLDEN, HUMANOID_HBM, ROOT, Oracle, load_state
+from oracle_lib import HUMANOID_HBM, Oracle, golden_states, load_state, MODELS_DIR as MODELS
+from step_lib import ACC_KERNELS, ACC_RK4_KERNELS
 
-MODELS = os.path.join(ROOT, "tests", "models")
 TOL = 1e-12
 FD_H = 5e-7
 FD_BOUND = 3 * 9.7e-11  # three times the worst deviation measured on the oracle: see test_readout_is_the_time_derivative_of_point_velocities
-
-
-def golden_states():
-    g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
-    st = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1)
-    return st, g["ctrl"], g["ncon"]
 
 
 def worst_bias_deviation(o, states, ctrls):
@@ -186,8 +180,6 @@ def test_every_full_kernel_has_a_twin_with_the_readout():
     """hb_step.hip's kernel table (HB_KERNELS): the read-out's instantiations (ACC = 1) repeat, parameter for parameter, exactly the
     rows that are full kernels (LEAN = 0, INV = 0, FRIC = 0) of the same INTEG - so that a launch with the read-out finds its kernel
     whatever the model - under names the step-kernel matrix does not collect; tests/test_gpu_body_acc.py names the ones it runs"""
-    import test_gpu_body_acc as tg
-
     def rows(integ, acc):  # (every column but ACC itself)
         return {n: tuple(c[k] for k in KERNEL_COLUMNS if k != "ACC") for n, c in kernel_table()
                 if c["INTEG"] == integ and c["ACC"] == acc and (acc == "1" or (c["LEAN"] == "0" and c["INV"] == "0" and c["FRIC"] == "0"))}
@@ -197,5 +189,5 @@ def test_every_full_kernel_has_a_twin_with_the_readout():
     assert {n.replace("hb_step", "hb_acc", 1): r for n, r in full.items()} == acc
     assert {n.replace("hb_rk4", "hb_acc_rk4", 1): r for n, r in rk4.items()} == acc_rk4
     assert not any(re.match(r"hb_step\w*_kernel$", n) for n in list(acc) + list(acc_rk4))
-    used = {k for v in tg.KERNELS.values() for k in v} | set(tg.RK4_KERNELS.values())
+    used = {k for v in ACC_KERNELS.values() for k in v} | set(ACC_RK4_KERNELS.values())
     assert used <= set(acc) | set(acc_rk4) and len(used) >= 10

@@ -11,12 +11,11 @@ restatements, and the case table of tests/box_cases.py proven on the references 
     oracle's plane - hull collider give the same contacts to 1e-9 are listed (at least 20); every branch label is taken at least twice;
   - conditioning: every case's envelope under one fp32 rounding of qpos (as tests/test_pair_cases_cpu.py), at most 5 % ill-conditioned.
 
-reference() is what tests/test_gpu_box.py holds the device to.
+box_cases.reference() is what tests/test_gpu_box.py holds the device to.
 """
 import collections
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,15 +24,10 @@ import box_cases
 import box_ref
 import pair_ref
 import ray_ref
-from oracle_lib import ROOT, Oracle, load_state, parse_hbm
-from test_pair_cases_cpu import NPERT, _spread, state_of
-
-GUARD = 1e-4
-ANALYTIC = ("plane-box", "sphere-box")
-ROWS_PER_CONTACT = {1: 1, 3: 4, 4: 6, 6: 10}
-TOOL = os.path.join(ROOT, "build", "hb_tables")
-ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
-_cache = {}
+from box_cases import ANALYTIC, analytic, reference, twin_agreement
+from oracle_lib import ASSETS, GOLDEN, MODELS_DIR, parse_hbm
+from pair_cases import GUARD, envelope
+from tables_lib import GENERAL_28, STAGED, fields, run as _tables
 
 
 def _xml(body, option="", tail=""):
@@ -86,7 +80,7 @@ def test_a_model_without_boxes_compiles_to_the_parents_bytes(hbmod, tmp_path):
     import pair_cases
     out = str(tmp_path / "pairs.hbm")
     hbmod.Model.from_xml_string(pair_cases.scene_xml("hfield")).save(out)
-    assert open(out, "rb").read() == open(os.path.join(ROOT, "tests", "golden", "pairs_hfield.hbm"), "rb").read()
+    assert open(out, "rb").read() == open(os.path.join(GOLDEN, "pairs_hfield.hbm"), "rb").read()
 
 
 @pytest.mark.parametrize("size", ["0.1 0.2", "0.1", "0.1 0.2 0", "0.1 -0.2 0.3", ""])
@@ -109,15 +103,7 @@ def test_cylinder_pair_is_still_refused(hbmod):
     assert "box" not in str(e.value)
 
 
-def _tables(path, *options):
-    if not os.path.exists(TOOL):
-        subprocess.check_call(["make", "-C", ROOT, "-s", "build/hb_tables"])
-    p = subprocess.run([TOOL, str(path)] + [str(o) for o in options], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    return p.returncode, p.stdout
-
-
 def test_variant_is_general_and_geom_half_is_the_box(hbmod, tmp_path):
-    from test_device_tables_cpu import fields
     for k, (option, variant) in enumerate((('solver="PGS"', 1), ('solver="Newton"', 2))):
         p = tmp_path / ("m%d.xml" % k)
         p.write_text(_xml(BOX_BODY % 'mass="1"', option))
@@ -139,7 +125,6 @@ def test_variant_is_general_and_geom_half_is_the_box(hbmod, tmp_path):
 
 
 def test_30_dof_box_model_gets_the_existing_message(tmp_path):
-    from test_device_tables_cpu import GENERAL_28
     bodies = "".join('<body pos="%d 0 1"><freejoint/><geom type="box" size="0.1 0.2 0.3" mass="1"/></body>' % k for k in range(5))
     p = tmp_path / "m.xml"
     p.write_text(_xml(bodies))
@@ -154,7 +139,6 @@ def test_variant_rules_refuse_a_box_model(tmp_path, what, options, message):
     """The existing refusals of a model that steps in stages, word for word (tests/test_device_tables_cpu.py pins the strings).  They name
     what made a model general before boxes - "mesh hulls, height fields or condim 4 / 6" - and not the box that this model has: DESIGN.md
     3.6a and INTEGRATION.md say that a colliding box belongs in that list."""
-    from test_device_tables_cpu import STAGED
     hinges = "".join('<body pos="%d 0 1"><joint name="j%d" type="hinge" axis="0 1 0" %s/><geom type="box" size="0.1 0.2 0.3" mass="1"/></body>'
                      % (k, k, 'frictionloss="0.1"' if what == "friction loss" else "") for k in range(2))
     tail = '<equality><joint joint1="j0" joint2="j1"/></equality>' if what == "equality" else ""
@@ -165,9 +149,9 @@ def test_variant_rules_refuse_a_box_model(tmp_path, what, options, message):
 
 def test_the_stairs_model_file_is_the_generators(hbmod):
     """tests/models/box_stairs.xml is box_cases.stairs_xml() written out: four box steps, a box-footed biped, a brick - 16 dofs"""
-    text = open(os.path.join(ROOT, "tests", "models", "box_stairs.xml")).read()
+    text = open(os.path.join(MODELS_DIR, "box_stairs.xml")).read()
     assert text == box_cases.stairs_xml()
-    m = hbmod.Model.load(os.path.join(ROOT, "tests", "models", "box_stairs.xml"))
+    m = hbmod.Model.load(os.path.join(MODELS_DIR, "box_stairs.xml"))
     assert (m.nv, m.nu) == (16, 4) and (np.asarray(m.array("geom_type")) == 6).sum() == 8 and m.nv <= 28
 
 
@@ -312,159 +296,7 @@ def test_support_and_lowest_point():
         assert abs(box_ref.lowest_point(h, R) - (c @ R.T)[:, 2].min()) <= 1e-15
 
 
-# ---- the case table on the references alone -----------------------------------------------------------------------------------------
-def compiled(hbmod, variant, directory):
-    out = []
-    for twin in (False, True):
-        m = hbmod.Model.from_xml_string(box_cases.scene_xml(variant, twin))
-        p = str(directory / ("boxes_%s%s.hbm" % (variant, "_twin" if twin else "")))
-        m.save(p)
-        out += [m, p, parse_hbm(p)]
-    return out
-
-
-def _analytic(info, qpos, geoms, labels=None, tests=None):
-    """box_ref on the pair under test of an analytic case, as Oracle.contacts() would list it"""
-    gpos, gmat = pair_ref.geom_poses(info, qpos)
-    g1, g2 = geoms
-    size = info["geom_size"].reshape(-1, 3)
-    margin = max(info["geom_margin"][g1], info["geom_margin"][g2])
-    dim = int(max(info["geom_condim"][g1], info["geom_condim"][g2]))
-    if info["geom_type"][g1] == box_ref.GEOM_PLANE:
-        con = box_ref.plane_box(margin, gpos[g1], gmat[g1][:, 2], gpos[g2], gmat[g2], size[g2], labels, tests)
-    else:
-        c = box_ref.sphere_box(margin, gpos[g1], size[g1][0], gpos[g2], gmat[g2], size[g2], labels, tests)
-        con = [c] if c else []
-    return [dict(dist=c["dist"], pos=c["pos"], frame=c["normal"][None, :], dim=dim, geom1=int(g1), geom2=int(g2)) for c in con]
-
-
-class Twin:
-    """The fp64 oracle on a scene's mesh twin, spoken to in the BOX model's terms: states in the box model's qpos / qvel order, contacts
-    with the box model's geom ids.  For most scenes the twin has the box model's bodies in the same order and nothing is permuted.  The
-    xfirst_mesh scene (hull X ahead of the boxes) cannot use its own twin: the device collides (box, hull) - geom type order - and a twin
-    made of meshes alone would collide (hull, box) - geom id order - and the portal search is not symmetric in its two objects (measured in
-    the oracle: depth apart by up to 1e-2 on deep random overlaps).  Its twin is the "mesh" scene's, X behind the boxes, where the order
-    is (box, hull) too; bodies and geoms are matched by name."""
-
-    def __init__(self, info, tpath):
-        self.o = Oracle(tpath)
-        ti = self.o.info
-        self.nv, self.nu = self.o.nv, self.o.nu
-        self.geom = {g: list(info["geom_name"]).index(n) for g, n in enumerate(ti["geom_name"])}  # twin geom id -> box model's
-        self.qmap, self.vmap = np.zeros(self.o.nq, dtype=int), np.zeros(self.o.nv, dtype=int)     # twin index -> box model's index
-        for b, name in enumerate(ti["body_name"]):
-            if b == 0:
-                continue
-            bb = list(info["body_name"]).index(name)
-            jt, jb = ti["body_jntadr"][b], info["body_jntadr"][bb]
-            self.qmap[ti["jnt_qposadr"][jt]:ti["jnt_qposadr"][jt] + 7] = np.arange(7) + info["jnt_qposadr"][jb]
-            self.vmap[ti["jnt_dofadr"][jt]:ti["jnt_dofadr"][jt] + 6] = np.arange(6) + info["jnt_dofadr"][jb]
-        self.same_order = bool((self.qmap == np.arange(self.o.nq)).all())
-
-    def load(self, qpos):
-        load_state(self.o, state_of(self.o, np.asarray(qpos)[self.qmap]), np.zeros(self.o.nu))
-
-    def forward(self):
-        self.o.forward()
-
-    def step(self):
-        self.o.step()
-
-    @property
-    def ncon(self):
-        return self.o.ncon
-
-    @property
-    def nefc(self):
-        return self.o.nefc
-
-    def contacts(self):
-        out = self.o.contacts()
-        for c in out:
-            c["geom1"], c["geom2"] = self.geom[c["geom1"]], self.geom[c["geom2"]]
-        return out
-
-    def _back(self, x, m):
-        out = np.zeros(len(x))
-        out[m] = x
-        return out
-
-    @property
-    def qpos(self):
-        return self._back(self.o.qpos, self.qmap)
-
-    @property
-    def qvel(self):
-        return self._back(self.o.qvel, self.vmap)
-
-
-def _evaluate(ref, case, qpos):
-    if case["kind"] in ANALYTIC:
-        con = _analytic(ref["info"], qpos, case["geoms"])
-        return dict(qpos=qpos, ncon=len(con), nefc=len(con) * ROWS_PER_CONTACT[con[0]["dim"]] if con else 0, con=con)
-    o = ref["oracle"]
-    o.load(qpos)
-    o.forward()
-    return dict(qpos=qpos, ncon=o.ncon, nefc=o.nefc, con=o.contacts())
-
-
-def reference(hbmod, variant, directory):
-    """dict(model, info, twin_info, oracle (on the twin), cases, evals, ill): evals[i] lists case i's reference evaluations, the unperturbed
-    one first (an exact case has no other) - box_ref for the analytic kinds, the oracle on the mesh twin for the portal-search kinds"""
-    if variant in _cache:
-        return _cache[variant]
-    m, p, info, _, tp, tinfo = compiled(hbmod, variant, directory)
-    if variant == "xfirst_mesh":  # (class Twin: the twin with X behind the boxes)
-        _, _, _, _, tp, tinfo = compiled(hbmod, "mesh", directory)
-    ref = dict(model=m, path=p, info=info, twin_info=tinfo, oracle=Twin(info, tp), cases=box_cases.build_cases(info, variant))
-    rng = np.random.default_rng(7)
-    evals, ill = [], []
-    for c in ref["cases"]:
-        ev = [_evaluate(ref, c, c["qpos"])]
-        if not c["exact"]:
-            for _ in range(NPERT):
-                ev.append(_evaluate(ref, c, c["qpos"] + 2.0 ** -24 * np.maximum(1.0, np.abs(c["qpos"])) * rng.standard_normal(len(c["qpos"]))))
-        evals.append(ev)
-        ill.append(len({e["ncon"] for e in ev}) > 1)
-    ref.update(evals=evals, ill=np.array(ill))
-    _cache[variant] = ref
-    return ref
-
-
-def envelope(ref, i, ncon):
-    ev = ref["evals"][i]
-    pick = next((e for e in ev if e["ncon"] == ncon), None)
-    return None if pick is None else (pick, _spread(pick, [e for e in ev if e is not pick]))
-
-
-def twin_agreement(ref):
-    """{case index: same order} of the plane - box cases whose box_ref contacts equal the oracle's plane - hull contacts on the twin to 1e-9
-    as SETS; same order: also in the same order (the hull lists its support vertex first, then that vertex's neighbours; the box its
-    corners in corner order - the PGS solver cut at 50 sweeps is sensitive to the order, DESIGN.md 2, the Newton solver is not)"""
-    o = ref["oracle"]
-    out = {}
-    for i, c in enumerate(ref["cases"]):
-        if c["kind"] != "plane-box":
-            continue
-        o.load(c["qpos"])
-        o.forward()
-        mine, theirs = ref["evals"][i][0]["con"], o.contacts()
-        if len(mine) != len(theirs) or any((t["geom1"], t["geom2"]) != c["geoms"] for t in theirs):
-            continue
-        left = list(range(len(theirs)))
-        order = []
-        for a in mine:
-            k = next((k for k in left if abs(a["dist"] - theirs[k]["dist"]) <= 1e-9 and np.abs(a["pos"] - theirs[k]["pos"]).max() <= 1e-9
-                      and np.abs(a["frame"][0] - theirs[k]["frame"][0]).max() <= 1e-9), None)
-            if k is None:
-                break
-            left.remove(k)
-            order.append(k)
-        else:
-            out[i] = order == sorted(order)
-    return out
-
-
+# ---- the case table on the references alone (box_cases.reference) ------------------------------------------------------------------
 @pytest.fixture(scope="module", params=("pgs", "mesh", "xfirst", "xfirst_mesh"))
 def ref(request, hbmod, tmp_path_factory):
     return reference(hbmod, request.param, tmp_path_factory.mktemp("boxes"))
@@ -532,7 +364,7 @@ def test_every_branch_is_taken_at_least_twice_and_off_its_boundary(ref):
         if c["kind"] not in ANALYTIC:
             continue
         labels, tests = [], []
-        _analytic(ref["info"], c["qpos"], c["geoms"], labels, tests)
+        analytic(ref["info"], c["qpos"], c["geoms"], labels, tests)
         hist.update(set(labels))
         for t in tests:
             if t[0] == "corner":  # a corner that is low enough to count is clear of the margin and of ldist = 0

@@ -16,17 +16,9 @@ import pytest
 
 import contact_ref
 from kernel_models import rollout_states
-from oracle_lib import GOLDEN, HUMANOID_HBM, ROOT, Oracle, load_state
+from oracle_lib import ASSETS, HUMANOID_HBM, TEAM_HBM, Oracle, golden_states, load_state, MODELS_DIR as MODELS
 
-ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
-MODELS = os.path.join(ROOT, "tests", "models")
 TOL = 1e-12
-
-
-def golden_states():
-    g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
-    st = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1)
-    return st, g["ctrl"], g["ncon"]
 
 
 def worst_identity(o, states, ctrls):
@@ -58,7 +50,7 @@ def test_decode_reproduces_root_forces_on_golden_states(solver, iterations):
 
 def test_decode_reproduces_root_forces_on_the_team_robot():
     """condim 6: torsional and rolling rows, mesh hulls on a height field"""
-    o = Oracle(os.path.join(ASSETS, "team_robot.hbm"))
+    o = Oracle(TEAM_HBM)
     states, ctrls = contact_ref.team_states(o)
     worst, with_rows, outs = worst_identity(o, states, ctrls)
     six = sum(any(k["dim"] == 6 and k["efc_address"] >= 0 for k in con) for _, con in outs)

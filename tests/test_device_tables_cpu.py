@@ -18,32 +18,15 @@ reached at all: an .hbm edited to jnt_type 1 fails the loader's "nq / nv do not 
 tables of a joint type nothing in this project writes.
 """
 import os
-import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from eq_models import add_equality
+from fric_models import add_friction
 from kernel_models import chain_xml
-from test_gpu_fric import add_friction
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOL = os.path.join(ROOT, "build", "hb_tables")
-ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def tools():
-    if not os.path.exists(TOOL):
-        subprocess.check_call(["make", "-C", ROOT, "-s", "build/hb_tables"])
-
-
-def run(model, *options):
-    """(exit code, stdout) of build/hb_tables on a model file"""
-    p = subprocess.run([TOOL, str(model)] + [str(o) for o in options], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    assert p.stderr == "", p.stderr
-    return p.returncode, p.stdout
+from oracle_lib import ASSETS, MODELS_DIR
+from tables_lib import GENERAL_28, STAGED, fields, read_dump, run
 
 
 def write(tmp_path, name, text):
@@ -71,11 +54,9 @@ def nested(n):
     return xml
 
 
-STAGED = "only models that step in one kernel (plane / sphere / capsule geoms, condim 1 / 3) are implemented; this model steps in stages (mesh hulls, height fields or condim 4 / 6): "
 EQ = '<equality><joint joint1="j1" joint2="j3"/></equality>'
 LOCKS = "<equality>" + "".join('<joint joint1="j%d"/>' % j for j in range(20)) + "</equality>"
 HFIELD_ASSET = '<asset><hfield name="h" nrow="2" ncol="2" size="1 1 0.1 0.1" elevation="0 0.1 0.2 0"/></asset>'
-GENERAL_28 = "models with mesh geoms, height fields or condim 4 / 6 support at most 28 degrees of freedom in this build"
 # name -> (the model's MJCF, tool options, the message)
 XML_REFUSALS = {
     "nv_33": (chain_xml(33), (), "this build supports nv <= 32 degrees of freedom"),
@@ -128,45 +109,10 @@ def test_rk4_on_a_staged_model_is_refused(name):
 
 
 def test_unknown_integrator():
-    assert run(os.path.join(ROOT, "tests", "models", "pendulum.xml"), "--integrator", 2) == (1, "refused: integrator 2 is not implemented (Euler = 0, RK4 = 1)\n")
+    assert run(os.path.join(MODELS_DIR, "pendulum.xml"), "--integrator", 2) == (1, "refused: integrator 2 is not implemented (Euler = 0, RK4 = 1)\n")
 
 
 # ---- (b)
-def fields(out):
-    """the tool's lines: scalars and flags by name; "array" -> {name: length}; "table" -> {name: (array, offset, count, hash)}"""
-    f = {"array": {}, "table": {}}
-    for ln in out.strip().split("\n"):
-        t = ln.split()
-        if t[0] == "array":
-            f["array"][t[1]] = int(t[2])
-        elif t[0] == "table":
-            f["table"][t[1]] = (t[2], int(t[3]), int(t[4]), t[5])
-        elif t[0] == "qpos_src":
-            f["qpos_src"] = int(t[1])
-        else:
-            f[t[0]] = float(t[1]) if "." in t[1] or "e" in t[1] else int(t[1])
-    return f
-
-
-def read_dump(path):
-    """the int array and the fix-ups [(field offset, array, element offset)] of a --dump file (tools/hb_tables.cpp)"""
-    raw = open(path, "rb").read()
-    assert raw[:8] == b"HBTABLE1"
-    pos = 8
-
-    def u64():
-        nonlocal pos
-        pos += 8
-        return struct.unpack_from("<Q", raw, pos - 8)[0]
-
-    n = u64(); pos += n  # the DevModel
-    n = u64(); iv = np.frombuffer(raw, "<i4", n, pos); pos += 4 * n
-    n = u64(); pos += 4 * n
-    n = u64(); pos += 8 * n
-    fix = [(u64(), u64(), u64()) for _ in range(u64())]
-    return iv, fix
-
-
 # the sizes of kSizedHumanoid27 and kSizedTeamV1 (hb_device.hpp), and what the reference models are besides
 EXPECT = {
     "humanoid27": dict(nq=28, nv=27, nu=21, nbody=17, njnt=22, ngeom=20, ntendon=2, nM=243, ntree=1, npair=159, nlevel=7, nlimcand=46, nstate=83,
@@ -177,7 +123,7 @@ EXPECT = {
     "equalities": dict(variant=0, sized_h27=0, sized_team=0, fast_lds_floats=0),
 }
 PATHS = {"humanoid27": os.path.join(ASSETS, "humanoid27.hbm"), "team_robot": os.path.join(ASSETS, "team_robot.hbm"),
-         "equalities": os.path.join(ROOT, "tests", "models", "equalities.xml")}
+         "equalities": os.path.join(MODELS_DIR, "equalities.xml")}
 ARRAY_CODE = {"int": 0, "float": 1, "u64": 2}
 
 

@@ -4,7 +4,6 @@ states, envs and blocks (dr_ref.draw), the reference's step with the env's block
 least 10 x the GPU bound of a compared quantity, on at least half of the (state, env) cases and on at least four.  Without that a kernel
 that ignored the family would pass the GPU test."""
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import pytest
 import dr_ref
 from oracle_lib import Oracle, load_state
 from dr_rows import BOUNDS, CASES, COMPARED, N, ROUNDS, ROWS, blocks, config, deviation, ref_step, round_states, setup_row
+from step_lib import report
 
 FACTOR = 10.0  # the reference's change over the GPU bound
 
@@ -140,11 +140,7 @@ def test_every_tested_family_is_observable_on_the_reference(hbmod, row):
             seen = int((r >= FACTOR).sum())
             line = "observability %-22s %-10s %-5s (%s) change / bound >= %g in %2d of %d cases, median %.3g, counts change in %d" % (
                 row, family, mode, ", ".join(COMPARED[mode]), FACTOR, seen, len(r), np.median(r), int(np.isinf(r).sum()))
-            print("  " + line)
-            out = os.environ.get("HB_DR_PARITY_OUT")
-            if out:
-                with open(out, "a") as f:
-                    f.write(line + "\n")
+            report(line, "HB_DR_PARITY_OUT", lead="  ")
             assert len(r) == N * ROUNDS and seen >= max(4, len(r) // 2), (row, family, mode, seen, np.sort(r)[:8])
 
 

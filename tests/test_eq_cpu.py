@@ -9,21 +9,14 @@ import pytest
 
 import eq_ref
 import fric_ref
-from eq_models import (EQUALITY, FOURBAR_BENT, MODELS, NE, SLIDER_A0, SLIDER_MASS, SLIDER_SOLIMP, SLIDER_SOLREF, add_equality, eq_chain_xml, fourbar_xml,
-                       geared_xml, plain_chain_xml, reference, slider_xml)
-from kernel_models import chain_xml, kernel_table, row_kinds
-from oracle_lib import ROOT, Oracle, load_state, parse_hbm
+from eq_models import (EQUALITY, FOURBAR_BENT, MODELS, NE, SLIDER_A0, SLIDER_MASS, SLIDER_SOLIMP, SLIDER_SOLREF, add_equality, eq_chain_xml, eq_tmp,  # noqa: F401  (eq_tmp: a fixture)
+                       fourbar_xml, geared_xml, plain_chain_xml, reference, slider_xml)
+from kernel_models import chain_xml, kernel_table, oracle_for, row_kinds
+from oracle_lib import ASSETS, CSRC, MODELS_DIR, Oracle, load_state, parse_hbm
 from rk4_ref import integrate_pos
-from test_gpu_kernel_matrix import _kernel_names_in_source
+from step_lib import kernel_names_in_source
 
-ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
-CSRC = os.path.join(ROOT, "humanoid_mujoco_amd", "csrc")
 EQ_KERNELS = ["hb_eq_kernel", "hb_eq32_kernel", "hb_eq_newton28_kernel", "hb_eq_newton32_kernel", "hb_eq_inverse_kernel", "hb_eq_inverse32_kernel"]
-
-
-@pytest.fixture(scope="module")
-def eq_tmp(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("eq"))
 
 
 def _xml(equality, default="", free=False):
@@ -136,7 +129,7 @@ def test_kernel_list():
     names = [n for n, c in kernel_table() if c["FRIC"] == "2"]
     assert names == EQ_KERNELS, names
     assert not any(re.fullmatch(r"hb_step\w*_kernel", n) for n in names)
-    assert not set(names) & _kernel_names_in_source()
+    assert not set(names) & kernel_names_in_source()
     cfg = {n: c for n, c in kernel_table()}
     for n in names:  # (the friction row of the same place in its list, but for the FRIC cell)
         twin = dict(cfg[n.replace("hb_eq", "hb_fric")], FRIC="2")
@@ -156,9 +149,7 @@ def _random_states(o, n, seed, scale=0.4):
 
 
 def _small(hbmod, xml, tmp_path, name):
-    p = str(tmp_path / name)
-    hbmod.Model.from_xml_string(xml).save(p)
-    return Oracle(p)
+    return oracle_for(hbmod, xml, tmp_path, name)[2]
 
 
 def test_jacobian_against_central_differences(hbmod, eq_tmp, tmp_path):
@@ -268,7 +259,7 @@ def test_gpu_state_sets_cover_the_rows(hbmod, eq_tmp):
 
 def test_the_sanitizer_pass_model(hbmod, tmp_path):
     """tests/models/equalities.xml (what tools/asan_host.sh takes through compile -> save -> load -> save): every accepted form, five rows"""
-    m = hbmod.Model.load(os.path.join(ROOT, "tests", "models", "equalities.xml"))
+    m = hbmod.Model.load(os.path.join(MODELS_DIR, "equalities.xml"))
     assert m.neq == 4 and m.equality_rows() == 3 + 1 + 1 and [e["name"] for e in m.equalities()] == ["close", "tether", "gear", "lock"]
     assert np.array_equal(m.array("eq_solref"), [0.03, 1, 0.01, 1, 0.03, 1, 0.01, 1])
     a, b = str(tmp_path / "a.hbm"), str(tmp_path / "b.hbm")
@@ -284,7 +275,7 @@ def test_id2name(hbmod):
     """hb_model_id2name, the inverse of hb_model_name2id that Model.equalities() reads its names through: every kind, an unnamed
     element, and the error returns (unknown kind, id out of range, a buffer without room for the terminator)"""
     import ctypes
-    m = hbmod.Model.load(os.path.join(ROOT, "tests", "models", "equalities.xml"))
+    m = hbmod.Model.load(os.path.join(MODELS_DIR, "equalities.xml"))
     for kind, names in (("body", ["frame", "crank", "rod"]), ("joint", ["root", "a", "s"]), ("geom", ["floor", "frame"]), ("equality", ["close", "lock"])):
         for n in names:
             i = m.name2id(kind, n)

@@ -7,23 +7,16 @@ import numpy as np
 import pytest
 
 import fric_ref
+from fric_models import MODELS, add_friction, fric_chain_xml, fric_tmp, pendulum_xml, reference  # noqa: F401  (fric_tmp: a fixture)
 from kernel_models import CNSTR_LIMIT_JOINT, chain_xml, kernel_table, oracle_for, oracle_steps, rollout_states, row_kinds
-from oracle_lib import ROOT, Oracle, load_state, parse_hbm
-from test_gpu_fric import MODELS, add_friction, fric_chain_xml, pendulum_xml, reference
-from test_gpu_kernel_matrix import _kernel_names_in_source
+from oracle_lib import ASSETS, CSRC, Oracle, load_state, parse_hbm
+from step_lib import kernel_names_in_source
 
-ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
-CSRC = os.path.join(ROOT, "humanoid_mujoco_amd", "csrc")
 FRIC_KERNELS = ["hb_fric_kernel", "hb_fric32_kernel", "hb_fric_newton28_kernel", "hb_fric_newton32_kernel", "hb_fric_inverse_kernel", "hb_fric_inverse32_kernel"]
 TWO_DOF = ('<mujoco><option timestep="0.002" solver="%s" iterations="%d" tolerance="0"/><worldbody><body pos="0 0 1">'
            '<joint name="h" type="hinge" axis="0 1 0" frictionloss="0.3" damping="0.1"/><geom type="capsule" fromto="0 0 0 0.4 0 0" size="0.02" mass="1"/>'
            '<body pos="0.2 0 0"><joint name="s" type="slide" axis="1 0 0" frictionloss="0.8" solreffriction="0.05 1"/><geom type="sphere" size="0.04" mass="0.5"/></body>'
            '</body></worldbody></mujoco>')
-
-
-@pytest.fixture(scope="module")
-def fric_tmp(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("fric"))
 
 
 def _xml(joint_attrs="", default="", tendon="", extra_joint=""):
@@ -177,6 +170,6 @@ def test_kernel_list():
     names = [n for n, c in kernel_table() if c["FRIC"] == "1"]
     assert names == FRIC_KERNELS, names
     assert not any(re.fullmatch(r"hb_step\w*_kernel", n) for n in names)
-    assert not set(names) & _kernel_names_in_source()
+    assert not set(names) & kernel_names_in_source()
     src = open(os.path.join(CSRC, "hb_step.hip")).read()
     assert re.search(r"kStepKernels\[\] = \{(.*?)\};", src, re.S).group(1) == "HB_KERNELS(HB_ROW)"  # (every row of the table)

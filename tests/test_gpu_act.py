@@ -23,6 +23,7 @@ import mlp_ref as ml
 import ppo_ref as pr
 import sac_ref as sr
 from oracle_lib import HUMANOID_HBM  # noqa: F401  (the model of the humanoid_model fixture)
+from sac_lib import state64 as _state64
 
 pytestmark = pytest.mark.gpu
 
@@ -260,11 +261,6 @@ def _sac_env(hbmod, m, gpu, net, pb, act_actor, act_q, **cfg):
     st["params"], st["targets"] = pb["flat"].astype(np.float32), pb["targets"].astype(np.float32)
     b.sac_set_state(st)
     return env
-
-
-def _state64(b):
-    s = b.sac_state()
-    return {k: (s[k].astype(np.float64) if k != "t" else s[k]) for k in s}
 
 
 @pytest.mark.parametrize("net", NETS)

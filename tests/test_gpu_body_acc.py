@@ -22,21 +22,17 @@ import pytest
 import acc_ref
 import contact_ref
 import rk4_ref
+from bounds import ACC_DECODE_BOUND as DECODE_BOUND, ACC_PARITY_BOUND as PARITY_BOUND
 from oracle_lib import HUMANOID_HBM, Oracle, load_state
+from step_lib import ACC_KERNELS as KERNELS, ACC_RK4_KERNELS as RK4_KERNELS
 
 pytestmark = pytest.mark.gpu
-DECODE_BOUND = 1.8e-6
-PARITY_BOUND = 2.7e-4
 RK4_STAGE_BOUND = 1.1e-5
 MAX_LEFT_OUT = 2
-KERNELS = {"humanoid27_pgs": ("hb_acc_kernel",), "humanoid27_newton": ("hb_acc_newton28_kernel",), "humanoid27_pgs_unsized": ("hb_acc_kernel",),
-           "chain12_cd4": ("hb_acc_gen_big_kernel", "hb_acc_gen_fast1_kernel"), "chain12_cd6": ("hb_acc_gen_big_kernel", "hb_acc_gen_fast1_kernel"),
-           "chain12_hfield": ("hb_acc_gen_kernel", "hb_acc_gen_fast_kernel"), "team_robot": ("hb_acc_newton_big20_kernel", "hb_acc_newton_gen20_kernel")}
-# (a launch that carries the read-out runs the full kernel's twin with the read-out: hb_acc_* for hb_step_*, hb_acc_rk4_* for hb_rk4_*)
+# (KERNELS and RK4_KERNELS, which kernels may write a model's read-out: step_lib.ACC_KERNELS, ACC_RK4_KERNELS)
 # the staged steps whose fast pass runs on a one-group layout: [kernel with the diagnostics, which switch that pass off; kernel without]
 FAST_PASS = {"chain12_cd4": ["hb_acc_gen_big_kernel", "hb_acc_gen_fast1_kernel"], "chain12_cd6": ["hb_acc_gen_big_kernel", "hb_acc_gen_fast1_kernel"],
              "team_robot": ["hb_acc_newton_big20_kernel", "hb_acc_newton_gen20_kernel"]}
-RK4_KERNELS = {"humanoid27_pgs": "hb_acc_rk4_kernel", "humanoid27_newton": "hb_acc_rk4_newton28_kernel"}
 TORSO, FOOT_R, FOOT_L = 1, 7, 10  # bodies of humanoid27.hbm
 IMUS = ((TORSO, (0.0, 0.0, 0.1)), (FOOT_R, (0.05, 0.02, -0.03)))  # the second: a non-zero offset on a limb body
 FRAMEACC = (TORSO, FOOT_L)

@@ -6,10 +6,10 @@ where the step kernel collides itself the hb_box_* rows of hb_step.hip.  One env
 kernel it ran.
 
 Rows with contact records (diagnostics on), per case against the reference from the same fp32-rounded state - box_ref for the analytic
-pairs, the fp64 oracle on the MESH TWIN for the portal-search pairs (tests/test_box_cpu.py: reference):
+pairs, the fp64 oracle on the MESH TWIN for the portal-search pairs (tests/box_cases.py: reference):
   - the count is identical, under the EXACT / ill-conditioned rule of tests/test_gpu_narrow_pairs.py; ncon and nefc;
   - geom ids and dim identical; the frame orthonormal to 1e-5, its first row the normal;
-  - dist, pos and normal within BASE + K * envelope, BASE = test_gpu_convex.TOL (dist 5e-7, pos 3e-6, normal 3e-5), the bounds that file
+  - dist, pos and normal within BASE + K * envelope, BASE = bounds.CONVEX_TOL (dist 5e-7, pos 3e-6, normal 3e-5), the bounds that file
     holds hull pairs to.  K = 6, from the roundings between qpos and a box CORNER, counted as tests/test_gpu_narrow_pairs.py counts them for
     a capsule's axis, in units of one rounding of a quaternion component (which moves a corner at |h| from the centre by 2 |h| 2^-24): the
     normalisation rounds each component once (1); hb_kcommon.hpp q2mat forms an entry of the rotation from at most four rounded products
@@ -26,21 +26,20 @@ pairs, the fp64 oracle on the MESH TWIN for the portal-search pairs (tests/test_
 Worst measured / bound per pair kind is printed and appended to the file HB_BOX_PARITY_OUT names (profiles/box_parity.txt).
 
 The rows without contact records (the staged step; narrow_prim 1 and 0 bit for bit equal): counts() under the same rule, and for the
-twin-agreement cases of plane - box and every portal-search case qpos / qvel after the step within test_gpu_kernel_matrix.BOUNDS of the
+twin-agreement cases of plane - box and every portal-search case qpos / qvel after the step within bounds.BOUNDS of the
 oracle's step on the twin.  Under Newton that is every twin-agreement case; under PGS, cut at 50 sweeps and therefore sensitive to the
 ORDER of the contacts, those the twin's plane - hull collider lists in the box's corner order.
 """
 import collections
-import os
 
 import numpy as np
 import pytest
 
 import box_cases
-from test_box_cpu import ANALYTIC, envelope, reference, twin_agreement
-from test_gpu_convex import TOL
-from test_gpu_kernel_matrix import BOUNDS
-from test_pair_cases_cpu import state_of
+from bounds import BOUNDS, CONVEX_TOL as TOL
+from box_cases import ANALYTIC, reference, twin_agreement
+from pair_cases import held_to, launch
+from step_lib import report
 
 pytestmark = pytest.mark.gpu
 
@@ -66,45 +65,9 @@ ROWS = [("fused",       "pgs",        {"staged": 0},  True,  "hb_box_gen_kernel"
         ("xfirst_mesh-lean", "xfirst_mesh", {},       False, "hb_step_gen_fast_lean_kernel")]
 
 
-def _launch(hbmod, gpu, ref, knobs, diag, tiles=1):
-    m, cases = ref["model"], ref["cases"]
-    st = np.tile(np.stack([state_of(m, c["qpos"]) for c in cases]), (tiles, 1))
-    knobs = dict(knobs)
-    acc = knobs.pop("body_acc", 0)
-    b = hbmod.Batch(m, len(st), gpu)
-    b.tune(**knobs)
-    b.diag_enable(diag)
-    if acc:
-        b.body_acc_readout(True)
-    if tiles > 1:
-        b.pipeline(False)  # one launch over the whole batch: the two-envs-per-wave narrowphase (hb_narrow.hip: launch_pose_narrow)
-    b.set_state(hbmod.STATE_INTEGRATION, st)
-    b.step(np.zeros((len(st), m.nu), dtype=np.float32))
-    out = dict(kernel=b.last_kernel(), counts=b.counts(), status=b.status(), state=b.get_state(hbmod.STATE_INTEGRATION), qpos=b.qpos.astype(np.float64), qvel=b.qvel.astype(np.float64),
-               con=b.contacts().astype(np.float64) if diag else None)
-    b.close()
-    return out
-
-
-def _held_to(ref, i, ncon, nefc, bad):
-    c = ref["cases"][i]
-    got = envelope(ref, i, ncon)
-    if got is None:
-        bad.append((c["name"], "contact count", ncon, "reference", sorted({e["ncon"] for e in ref["evals"][i]})))
-    elif nefc != got[0]["nefc"]:
-        bad.append((c["name"], "nefc", nefc, "reference", got[0]["nefc"]))
-    else:
-        return got
-    return None
-
-
 def _report(label, worst):
     lines = ["%-12s %-12s worst measured / bound: dist %.3f pos %.3f normal %.3f   (%d contacts)" % ((label, k) + tuple(w[:3]) + (int(w[3]),)) for k, w in sorted(worst.items())]
-    print("\n" + "\n".join(lines))
-    out = os.environ.get("HB_BOX_PARITY_OUT")
-    if out:
-        with open(out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    report(lines, "HB_BOX_PARITY_OUT", lead="\n")
 
 
 def _check_exact_box_box(ref, c, d, want, bad):
@@ -132,7 +95,7 @@ def _check_contacts(ref, got, label):
     worst = collections.defaultdict(lambda: np.zeros(4))
     bad = []
     for i, c in enumerate(ref["cases"]):
-        held = _held_to(ref, i, int(nc[i]), int(ne[i]), bad)
+        held = held_to(ref, i, int(nc[i]), int(ne[i]), bad, "reference")
         if held is None:
             continue
         ev, env = held
@@ -167,7 +130,7 @@ def _check_state(ref, got, label):
     n = n_agree = 0
     bad = []
     for i, c in enumerate(ref["cases"]):
-        held = _held_to(ref, i, int(nc[i]), int(ne[i]), bad)
+        held = held_to(ref, i, int(nc[i]), int(ne[i]), bad, "reference")
         if held is None or (c["kind"] in ANALYTIC and i not in agree):
             continue
         n_agree += c["kind"] in ANALYTIC
@@ -182,10 +145,7 @@ def _check_state(ref, got, label):
             bad.append((c["name"], "qpos %.2e qvel %.2e" % (dq, dv)))
         wq, wv, n = max(wq, dq), max(wv, dv), n + 1
     line = "%-12s state after the step, %d cases against the oracle on the twin: worst qpos %.2e (bound %.0e) qvel %.2e (bound %.0e)" % (label, n, wq, BOUNDS["qpos"], wv, BOUNDS["qvel"])
-    print("\n" + line)
-    if os.environ.get("HB_BOX_PARITY_OUT"):
-        with open(os.environ["HB_BOX_PARITY_OUT"], "a") as f:
-            f.write(line + "\n")
+    report(line, "HB_BOX_PARITY_OUT", lead="\n")
     print("".join("\n  %s: %s" % (label, x) for x in bad))
     assert n_agree >= 20 and n - n_agree >= 70 and not bad, (label, n_agree, n, len(bad), bad[:3])
 
@@ -195,14 +155,14 @@ def test_box_pairs(hbmod, gpu, tmp_path_factory, row):
     label, scene, knobs, diag, kernel = row
     ref = reference(hbmod, scene, tmp_path_factory.mktemp("boxes"))
     if knobs == "narrow_prim":
-        got = [_launch(hbmod, gpu, ref, {"narrow_prim": prim}, False) for prim in (1, 0)]
+        got = [launch(hbmod, gpu, ref, {"narrow_prim": prim}, False) for prim in (1, 0)]
         for g in got:
             assert g["kernel"] == kernel, (label, g["kernel"], kernel)
         assert np.array_equal(got[0]["state"], got[1]["state"]) and np.array_equal(got[0]["status"], got[1]["status"]), label
         assert all(np.array_equal(a, b) for a, b in zip(got[0]["counts"], got[1]["counts"])), label
         got = got[0]
     else:
-        got = _launch(hbmod, gpu, ref, knobs, diag)
+        got = launch(hbmod, gpu, ref, knobs, diag)
         assert got["kernel"] == kernel, (label, got["kernel"], kernel)
     assert not got["status"].any(), (label, got["status"])
     assert got["counts"][0].max() == 4 and (got["counts"][0] == 0).sum() >= 10
@@ -218,7 +178,7 @@ def test_two_envs_per_wave_narrowphase(hbmod, gpu, tmp_path_factory, scene):
     meshes, hb_narrow2_box_kernel with): the case table three times over in one unpipelined launch, every copy bit for bit the table's own
     own launch (one env per wave), which the rows above hold to the reference"""
     ref = reference(hbmod, scene, tmp_path_factory.mktemp("boxes"))
-    one, three = _launch(hbmod, gpu, ref, {}, False), _launch(hbmod, gpu, ref, {}, False, tiles=3)
+    one, three = launch(hbmod, gpu, ref, {}, False), launch(hbmod, gpu, ref, {}, False, tiles=3)
     n = len(ref["cases"])
     assert 3 * n >= 512 and not three["status"].any() and three["kernel"] == one["kernel"]
     for t in range(3):
@@ -288,17 +248,11 @@ def test_standing_on_the_stairs_model(hbmod, gpu, tmp_path, solver):
     drift, drift_o = np.abs(z - z[0]).max(), np.abs(z_o - z_o[0]).max()
     line = ("standing %-6s the brick's normal forces - m g (%.3f N): oracle on the twin %.3e, device %.3e (bound 2 x the oracle's); "
             "height drift over %d steps: oracle %.3e, device %.3e" % (solver, weight, bound_o, worst, steps, drift_o, drift))
-    print("\n" + line)
-    if os.environ.get("HB_BOX_PARITY_OUT"):
-        with open(os.environ["HB_BOX_PARITY_OUT"], "a") as f:
-            f.write(line + "\n")
+    report(line, "HB_BOX_PARITY_OUT", lead="\n")
     line = "standing %-6s the same over the last 100 steps (at rest): oracle %.3e, device %.3e (bound 2 x the oracle's + %.0e x m g)" % (solver, rest_o, rest, TOL["force"])
-    print(line)
-    if os.environ.get("HB_BOX_PARITY_OUT"):
-        with open(os.environ["HB_BOX_PARITY_OUT"], "a") as f:
-            f.write(line + "\n")
+    report(line, "HB_BOX_PARITY_OUT", lead="")
     assert worst <= 2 * bound_o
     # The bound above is set by the landing transient of a brick released 1 mm up.  At rest: twice the oracle's own residual, plus the
-    # project's bound on a constraint force in fp32, test_gpu_convex.TOL["force"] = 3e-4 of its scale (here the weight)
+    # project's bound on a constraint force in fp32, bounds.CONVEX_TOL["force"] = 3e-4 of its scale (here the weight)
     assert rest <= 2 * rest_o + TOL["force"] * weight
     assert (np.abs(z - z[0]).max(axis=1) <= drift_o + TOL["pos"] * steps).all()

@@ -3,7 +3,7 @@ tests/ray_ref.py for every other surface of the scene, the nearest hit winning (
 
 The scene is tests/box_cases.py's: a tilted plane, a height field, the static box W and the moving boxes P and Q beside a sphere and a
 capsule.  64 rays x 8 envs, in the world frame (half of them aimed at W and what lies on it, half at the height field and what hovers over
-it), in the sphere S's body frame and in its yaw frame (S itself excluded, half of the rays aimed at the box P beside it).  BOUND is tests/test_gpu_ray.py's (profiles/ray_parity.txt): 1e-5 relative to max(1, dist).
+it), in the sphere S's body frame and in its yaw frame (S itself excluded, half of the rays aimed at the box P beside it).  BOUND is tests/test_gpu_ray.py's, bounds.RAY_BOUND (profiles/ray_parity.txt): 1e-5 relative to max(1, dist).
 A ray is FRAGILE as in ray_ref (second candidate within 1e-4, grazing below |cos| 0.05, a miss that clears a surface by less than 1e-4
 - for a box: a miss that hits the box grown by 1e-4) and then may give either candidate.
 
@@ -19,7 +19,7 @@ import obs_ext_ref
 import pair_ref
 import ray_ref
 from oracle_lib import parse_hbm
-from test_gpu_ray import BOUND
+from bounds import RAY_BOUND as BOUND
 
 pytestmark = pytest.mark.gpu
 N_ENV, N_RAY = 8, 64

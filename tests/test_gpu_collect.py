@@ -15,27 +15,22 @@ Bounds:
                  head (one expf, one product, one sum in fp32; |eps| <= 5.9 for a 24-bit uniform), 2e-6 absolute for the squashed head (tanhf
                  on top, slope <= 1), and equality with mean for the deterministic one.
 HB_COLLECT_PARITY_OUT=<file> collects the worst values (profiles/collect_parity.txt)."""
-import os
-
 import numpy as np
 import pytest
 
 import actor_ref as ar
-from oracle_lib import HUMANOID_HBM  # noqa: F401  (the model of the humanoid_model fixture)
+from bounds import MEAN_TOL
+from oracle_lib import HUMANOID_HBM, TEAM_HBM  # noqa: F401  (the model of the humanoid_model fixture)
+from step_lib import report
 
 pytestmark = pytest.mark.gpu
 
 SEED, T, NOBS, NU = 2024, 8, 48, 21  # (tests/test_actor_cpu.py checks the draws of this seed)
-MEAN_TOL, EPS_TOL, ACT_TOL = 5e-5, 2e-5, 2e-6
-TEAM_HBM = os.path.join(os.path.dirname(HUMANOID_HBM), "team_robot.hbm")
+EPS_TOL, ACT_TOL = 2e-5, 2e-6
 
 
 def _report(line):
-    print("\n  " + line)
-    out = os.environ.get("HB_COLLECT_PARITY_OUT")
-    if out:
-        with open(out, "a") as f:
-            f.write(line + "\n")
+    report(line, "HB_COLLECT_PARITY_OUT")
 
 
 class Tapes:

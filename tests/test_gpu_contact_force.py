@@ -18,12 +18,10 @@ import pytest
 
 import contact_ref
 import rk4_ref
-from oracle_lib import HUMANOID_HBM, ROOT, Oracle, load_state
+from bounds import CONTACT_DECODE_BOUND as DECODE_BOUND, CONTACT_PARITY_BOUND as PARITY_BOUND
+from oracle_lib import HUMANOID_HBM, MODELS_DIR, Oracle, load_state
 
 pytestmark = pytest.mark.gpu
-MODELS = os.path.join(ROOT, "tests", "models")
-DECODE_BOUND = 1.5e-6
-PARITY_BOUND = 5e-4
 # which kernels may write a model's read-out (Batch.last_kernel after the step; a staged step is named after its fast pass)
 KERNELS = {"humanoid27_pgs": ("hb_step_kernel",), "humanoid27_newton": ("hb_step_newton28_kernel",), "humanoid27_pgs_unsized": ("hb_step_kernel",),
            "chain12_cd4": ("hb_step_gen_big_kernel", "hb_step_gen_fast1_kernel"), "chain12_cd6": ("hb_step_gen_big_kernel", "hb_step_gen_fast1_kernel"),
@@ -267,7 +265,7 @@ def test_edges(hbmod, gpu, humanoid_model):
 def test_dropped_rows_read_zero(hbmod, gpu):
     """tests/models/overflow.xml: 30 resting spheres, 24 contacts kept, 15 of them get their four rows (60 of 63), the other nine are
     dropped with HB_WARN_CNSTRFULL and read zero; the warning bits and the states are those of a batch without the read-out"""
-    m = hbmod.Model.load(os.path.join(MODELS, "overflow.xml"))
+    m = hbmod.Model.load(os.path.join(MODELS_DIR, "overflow.xml"))
     got = []
     for readout in (False, True):
         b = hbmod.Batch(m, 4, gpu)

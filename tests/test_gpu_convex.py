@@ -2,7 +2,7 @@
 world.xml + humanoid.xml: mesh hulls, condim 6, height-field floor, Newton): the HIP kernels through the C-ABI against the
 fp64 oracle, teacher-forced one step from states along oracle trajectories.
 
-Tolerances (at most 3x the maxima measured on the MI355X, gpurun_out/r02f/pytest.log): contact distance 5e-7 m, position
+Tolerances (bounds.CONVEX_TOL; at most 3x the maxima measured on the MI355X in round 2): contact distance 5e-7 m, position
 3e-6 m, normal 3e-5; qacc 2e-4 and forces 3e-4 relative to their scale, qvel 1.5e-5, qpos 1e-6.  Counts (ncon, nefc)
 identical.  The portal search (MPR) runs in double precision on the device as in the oracle (an fp32 search proved
 unstable against metre-sized prisms, hb_mpr.hpp), from fp32 poses: a state whose search still ends on another portal (hull against
@@ -14,11 +14,11 @@ import os
 import numpy as np
 import pytest
 
-from oracle_lib import ROOT, Oracle
-from test_oracle_convex import BALL_MESH, CUBE_MESH, _hfield_xml
+from bounds import CONVEX_TOL as TOL
+from convex_models import BALL_MESH, CUBE_MESH, hfield_xml
+from oracle_lib import MODELS_DIR, TEAM_HBM, TEAM_PLANE_HBM, Oracle
 
 pytestmark = pytest.mark.gpu
-TEAM_HBM = os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "team_robot.hbm")
 
 
 def _contacts_match(o, dev, nc_dev, ne_dev, tol):
@@ -107,9 +107,6 @@ def _teacher_forced(hbmod, gpu, path, states, ctrls, tol, min_contacts=1, max_di
         assert x <= tol[k], (k, x, tol[k])
     worst["max_nefc"] = max_nefc
     return worst
-
-
-TOL = dict(qpos=1e-6, qvel=1.5e-5, qacc=2e-4, force=3e-4, dist=5e-7, pos=3e-6, nrm=3e-5)
 
 
 def _oracle_states(path, envs, T, every, seed=0, ctrl_scale=1.0, init=None):
@@ -251,7 +248,7 @@ def test_primitives_and_hulls_on_a_bumpy_field(hbmod, gpu, tmp_path):
             '<body pos="0.4 -0.4 0.5" euler="20 40 0"><freejoint/><geom type="capsule" size="0.05 0.12" condim="3"/></body>'
             '<body pos="0.1 0.5 0.5" euler="10 20 30"><freejoint/><inertial pos="0 0 0" mass="0.5" diaginertia="0.001 0.001 0.001"/><geom type="mesh" mesh="cube" condim="4"/></body>'
             '<body pos="0.12 0.52 0.62"><freejoint/><inertial pos="0 0 0" mass="0.3" diaginertia="0.0005 0.0005 0.0005"/><geom type="mesh" mesh="ball" condim="6" friction="0.7 0.02 0.01"/></body>')
-    xml = _hfield_xml(elev, body, nrow=6, ncol=6, size="1 1 0.3 0.2", extra=CUBE_MESH + BALL_MESH)
+    xml = hfield_xml(elev, body, nrow=6, ncol=6, size="1 1 0.3 0.2", extra=CUBE_MESH + BALL_MESH)
     for solver, name in ((2, "bumpy_newton.hbm"), (0, "bumpy_pgs.hbm")):
         if solver == 0:  # the one-group PGS instantiation holds 63 rows: friction cones of dimension 3 keep four bodies inside that
             xml = xml.replace('condim="6"', 'condim="3"').replace('condim="4"', 'condim="3"')
@@ -276,8 +273,7 @@ def test_mesh_mesh_stack(hbmod, gpu, tmp_path):
 
 def test_ball_and_capsules_on_a_sloped_field(hbmod, gpu, tmp_path):
     """tests/models/ball_hfield.xml (a ball and capsules on a sloped field, default solver): the prism scheme for primitives."""
-    from test_gpu_parity import MODELS
-    m = hbmod.Model.load(os.path.join(MODELS, "ball_hfield.xml"))
+    m = hbmod.Model.load(os.path.join(MODELS_DIR, "ball_hfield.xml"))
     p = str(tmp_path / "ball_hfield.hbm")
     m.save(p)
     states, ctrls = _oracle_states(p, envs=1, T=900, every=10)
@@ -288,7 +284,6 @@ def test_plane_mesh_hulls_on_a_plane(hbmod, gpu, tmp_path):
     """mjc_PlaneConvex on the device against the oracle, teacher-forced: a cube hull and a 300-vertex ball dropped, tilted, on a PLANE
     (up to four contacts per hull: the support vertex and its graph neighbours), Newton with condim 6 and PGS with condim 3; through the
     fused kernel (diagnostics on) and - the robot test below - the staged step."""
-    from test_oracle_convex import PLANE_CUBE_XML  # noqa: F401
     body = ('<body pos="0.0 0.0 0.12" euler="20 30 10"><freejoint/><inertial pos="0 0 0" mass="0.5" diaginertia="0.001 0.001 0.001"/><geom type="mesh" mesh="cube" condim="%d"/></body>'
             '<body pos="0.3 0.1 0.15"><freejoint/><inertial pos="0 0 0" mass="0.3" diaginertia="0.0005 0.0005 0.0005"/><geom type="mesh" mesh="ball" condim="%d" friction="0.7 0.02 0.01"/></body>')
     for solver, dim, name in ((2, 6, "plane_newton.hbm"), (0, 3, "plane_pgs.hbm")):
@@ -303,12 +298,12 @@ def test_plane_mesh_hulls_on_a_plane(hbmod, gpu, tmp_path):
         assert w["max_nefc"] >= (40 if solver == 2 else 16)  # a hull flat on the plane: four contacts
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(TEAM_HBM), "team_robot_plane.hbm")), reason="assets/team_robot_plane.hbm not built")
+@pytest.mark.skipif(not os.path.exists(TEAM_PLANE_HBM), reason="assets/team_robot_plane.hbm not built")
 def test_team_robot_on_the_reference_plane_floor(hbmod, gpu):
     """The reference's robot on its type="plane" floor (simulation/assets/green_screen_world.xml, compiled to assets/team_robot_plane.hbm):
     the staged step (pose kernel evaluates the plane - hull items, no portal search for them) against the oracle, teacher-forced along the
     robot's fall and rest on the plane."""
-    path = os.path.join(os.path.dirname(TEAM_HBM), "team_robot_plane.hbm")
+    path = TEAM_PLANE_HBM
 
     def init(o, e, rng):
         o.qpos[7:] += rng.uniform(-0.2, 0.2, o.nq - 7)
@@ -362,7 +357,7 @@ def test_exact_ties_on_flat_facets_terminate_and_match(hbmod, gpu, tmp_path):
     worlds = {
         "tie_plane.hbm": '<mujoco><option timestep="0.002"/><asset>%s</asset><worldbody><geom type="plane" size="0 0 .05" condim="3"/>%s%s</worldbody></mujoco>'
                          % (CUBE_MESH, cube % "0 0 0.0495", cube % "0 0 0.149"),
-        "tie_hfield.hbm": _hfield_xml(np.zeros((4, 4)), cube % "0.125 0.125 0.0495" + cube % "0.125 0.125 0.149", extra=CUBE_MESH),
+        "tie_hfield.hbm": hfield_xml(np.zeros((4, 4)), cube % "0.125 0.125 0.0495" + cube % "0.125 0.125 0.149", extra=CUBE_MESH),
     }
     for name, xml in worlds.items():
         p = _save(hbmod, xml, tmp_path, name)
@@ -382,7 +377,7 @@ def test_pgs_beyond_63_rows(hbmod, gpu, tmp_path):
             '<body pos="0.4 -0.4 0.5" euler="20 40 0"><freejoint/><geom type="capsule" size="0.05 0.12" condim="6"/></body>'
             '<body pos="0.1 0.5 0.5" euler="10 20 30"><freejoint/><inertial pos="0 0 0" mass="0.5" diaginertia="0.001 0.001 0.001"/><geom type="mesh" mesh="cube" condim="4"/></body>'
             '<body pos="0.12 0.52 0.62"><freejoint/><inertial pos="0 0 0" mass="0.3" diaginertia="0.0005 0.0005 0.0005"/><geom type="mesh" mesh="ball" condim="6" friction="0.7 0.02 0.01"/></body>')
-    xml = _hfield_xml(elev, body, nrow=6, ncol=6, size="1 1 0.3 0.2", extra=CUBE_MESH + BALL_MESH)
+    xml = hfield_xml(elev, body, nrow=6, ncol=6, size="1 1 0.3 0.2", extra=CUBE_MESH + BALL_MESH)
     m = hbmod.Model.from_xml_string(xml)
     m.set_opt(solver=0, iterations=50)
     assert (m.ncon_max, m.nefc_max) == (48, 128)

@@ -8,7 +8,7 @@ A batch of N = 8 envs draws its blocks at once (env_domain_randomize on the plai
 (env_domain_params) and each env's diag step from teacher-forced states of the nominal rollout (kernel_models.rollout_states; ROUNDS
 rounds, state (8 r + e) mod 30 on env e; row d "all": of the env's OWN rollout on its own block, so that it touches its own height
 map - at least half of the cases must be in contact) is held to the oracle whose model arrays carry that env's block (dr_ref.apply): counts and PGS
-sweep counts identical, status zero, qpos / qvel / qacc / efc_force / contact dist, pos, frame within test_gpu_kernel_matrix.BOUNDS.
+sweep counts identical, status zero, qpos / qvel / qacc / efc_force / contact dist, pos, frame within bounds.BOUNDS.
 The blocks are fp32 values handed to the oracle exactly: they add no error.  tests/test_dr_ref_cpu.py proves on the reference alone that
 every (row, family) pair listed here is OBSERVABLE in every run mode the row has: the oracle's step with the env's block differs from its
 step with the nominal block by at least 10 x the bound of a quantity THAT MODE COMPARES (a launch without diagnostic outputs: qpos, qvel
@@ -41,19 +41,17 @@ switching the block off; the subtree sensors with per-env masses over the model'
 restatement (dr_ref.draw) table by table; the masked redraw at an auto-reset; the friction scale on a model without a plane floor.
 The worst deviations are printed (pytest -s); profiles/domain_params_parity.txt holds the numbers measured on MI355X.
 """
-import os
-
 import numpy as np
 import pytest
 
 import dr_ref
 from dr_rows import BOUNDS, CASES, N, ROUNDS, ROWS, T, config, deviation, ref_step, round_states, setup_row
 from oracle_lib import load_state
-from test_gpu_kernel_matrix import _result, _same, _state_vs_oracle, _vs_oracle
+from step_lib import report, result, same, state_vs_oracle, vs_oracle
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
 def _vs_ref(hbmod, b, S, st, ct, label, before):
-    """_vs_oracle for the rows whose reference is a restatement on top of the oracle (fric_ref, eq_ref, rk4_ref)"""
+    """step_lib.vs_oracle for the rows whose reference is a restatement on top of the oracle (fric_ref, eq_ref, rk4_ref)"""
     b.diag_enable(True)
     b.set_state(hbmod.STATE_INTEGRATION, st)
     b.step(ct)
@@ -84,11 +82,7 @@ def _vs_ref(hbmod, b, S, st, ct, label, before):
 
 
 def _profile(line):
-    print("  " + line)
-    out = os.environ.get("HB_DR_PARITY_OUT")  # (set to collect the lines of profiles/domain_params_parity.txt)
-    if out:
-        with open(out, "a") as f:
-            f.write(line + "\n")
+    report(line, "HB_DR_PARITY_OUT", lead="  ")  # (set to collect the lines of profiles/domain_params_parity.txt)
 
 
 def _batch(hbmod, gpu, S, D, knobs=None, n=N):
@@ -122,11 +116,11 @@ def test_step_kernels_use_the_envs_parameters(hbmod, gpu, row, cfg, run):
                 assert mode == "diag"
                 w = _vs_ref(hbmod, b, S, st, ct, label, before)
             elif mode == "diag":
-                w = _vs_oracle(hbmod, b, o, st, ct, S["fences_ok"], label, before)
+                w = vs_oracle(hbmod, b, o, st, ct, S["fences_ok"], label, before)
             else:
                 b.set_state(hbmod.STATE_INTEGRATION, st)
                 b.step(ct)
-                w = _state_vs_oracle(hbmod, b, o, st, ct, S["fences_ok"], label, before)
+                w = state_vs_oracle(hbmod, b, o, st, ct, S["fences_ok"], label, before)
             assert b.last_kernel() == kernel, (label, b.last_kernel(), kernel)
             touching += int((b.counts()[0] > 0).sum())
             for key, x in w.items():
@@ -162,7 +156,7 @@ def test_launch_forms_under_a_block_are_bit_identical(hbmod, gpu, row):
         b.step(ctrl)
         b.sync()
         assert b.last_kernel() == full, b.last_kernel()
-    ref = _result(hbmod, b)
+    ref = result(hbmod, b)
     assert ref[1][1].max() > 0 and not ref[2].any()
     b.close()
     for form in ("rollout", "steps", "vecenv"):
@@ -181,7 +175,7 @@ def test_launch_forms_under_a_block_are_bit_identical(hbmod, gpu, row):
                 b.step(ctrl)
         else:
             env.step_arrays(ctrl)
-        _same(_result(hbmod, b), ref, "%s %s" % (row, form))
+        same(result(hbmod, b), ref, "%s %s" % (row, form))
         assert b.last_kernel() == full, (row, form, b.last_kernel())
         b.close()
 
@@ -202,7 +196,7 @@ def test_switching_the_block_off(hbmod, gpu, row, lean):
             b.env_domain_randomize(config(S, "all"))
             b.set_state(hbmod.STATE_INTEGRATION, st)
             b.step(ct)
-            with_block = _result(hbmod, b)
+            with_block = result(hbmod, b)
             b.env_domain_randomize(None)
             assert b.env_domain_params() is None
         b.set_state(hbmod.STATE_INTEGRATION, st)
@@ -211,14 +205,14 @@ def test_switching_the_block_off(hbmod, gpu, row, lean):
         assert b.last_kernel() == (lean[-1] if had_block else lean[0]), (row, had_block, b.last_kernel())
         for t in range(T - 1):
             b.step(ct)
-        res.append(_result(hbmod, b))
+        res.append(result(hbmod, b))
         assert b.last_kernel() in lean, (row, had_block, b.last_kernel())
         if not had_block:
             b.set_state(hbmod.STATE_INTEGRATION, st)
             b.step(ct)
-            assert not np.array_equal(_result(hbmod, b)[0], with_block[0])  # (and the block did matter)
+            assert not np.array_equal(result(hbmod, b)[0], with_block[0])  # (and the block did matter)
         b.close()
-    _same(res[0], res[1], row + " after env_domain_randomize(None)")
+    same(res[0], res[1], row + " after env_domain_randomize(None)")
 
 
 # ---- sensors: per-env masses over the model's (stale) subtree mass
@@ -374,8 +368,8 @@ def test_friction_scale_without_a_plane_floor_is_ignored(hbmod, gpu):
         for t in range(T):
             b.step(ct)
         assert b.last_kernel() == "hb_step_gen_fast_kernel"
-        res.append(_result(hbmod, b))
+        res.append(result(hbmod, b))
         b.close()
     assert res[0][1][0].max() > 0  # (there are contacts)
-    _same(res[1], res[0], "friction scale 0.3 .. 0.6")
-    _same(res[2], res[0], "friction scale 1.5 .. 3")
+    same(res[1], res[0], "friction scale 0.3 .. 0.6")
+    same(res[2], res[0], "friction scale 1.5 .. 3")

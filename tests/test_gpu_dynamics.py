@@ -2,7 +2,7 @@
 forces and the Jacobians built from its kinematics (tests/dyn_ref.py), and its contract as a pure function of the state: the same bits
 whatever the packing, the batch size, a state's place in a wave or the form of the call, nothing of the batch written.
 
-Bounds (errors relative to max(1, max |reference|) of the quantity in the state): the project's convention, 3 x the maxima of
+Bounds (bounds.DYN_BOUND; errors relative to max(1, max |reference|) of the quantity in the state): the project's convention, 3 x the maxima of
 profiles/dynamics_parity.txt (tools/gpu_dynamics_report.py, the same cases and the same sixteen points), rounded down.  All maxima are
 far below the 4e-4 qacc bound of tests/test_gpu_parity.py.
     M             measured maximum 2.814e-7 (chain32),    3 x = 8.442e-7  -> 8.44e-7
@@ -22,15 +22,14 @@ import pytest
 import dr_ref
 import dyn_ref
 import kin_ref
-from oracle_lib import HUMANOID_HBM, load_state
+from bounds import DYN_BOUND as BOUND
+from bounds import VEL_BOUND  # the velocities of Batch.kinematics against the same oracle
+from oracle_lib import ASSETS, HUMANOID_HBM, load_state
+from step_lib import same_dict, snapshot
 
 pytestmark = pytest.mark.gpu
 
-BOUND = {"M": 8.44e-7, "bias": 5.02e-6, "passive": 2.04e-7, "jac": 1.66e-6}
-assert max(BOUND.values()) < 4e-4
-VEL_BOUND = 1.8e-6  # tests/test_gpu_kinematics.py: the velocities of Batch.kinematics against the same oracle
 QUANT = ("M", "bias", "passive", "jac")
-ASSETS = os.path.dirname(HUMANOID_HBM)
 
 _cache = {}
 
@@ -59,12 +58,6 @@ def _readout(hbmod, m, states, spec, gpu, **tune):
     return out, kernel
 
 
-def _same(a, b, label):
-    assert a.keys() == b.keys(), label
-    for k in a:
-        assert a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), (label, k)
-
-
 @pytest.mark.parametrize("name", kin_ref.CASES)
 def test_parity(hbmod, gpu, tmp_path_factory, name):
     """every state of every case inside the four bounds, on the kernel the model's size asks for; M symmetric bit for bit"""
@@ -88,10 +81,10 @@ def test_packing_and_place_are_bit_identical(hbmod, gpu, tmp_path_factory, name)
     packed, k1 = _readout(hbmod, m, states, spec, gpu)
     plain, k0 = _readout(hbmod, m, states, spec, gpu, kin_pack=0)
     assert (k1, k0) == (kernel, "hb_dyn64_kernel")
-    _same(packed, plain, "kin_pack")
+    same_dict(packed, plain, "kin_pack")
     for n in (1, per + 1):
         out, _ = _readout(hbmod, m, states[:n], spec, gpu)
-        _same(out, {k: a[:n] for k, a in packed.items()}, "n %d" % n)
+        same_dict(out, {k: a[:n] for k, a in packed.items()}, "n %d" % n)
     qpos, qvel = kin_ref.split_state(o, states)
     b = hbmod.Batch(m, 2, gpu)
     for k in (0, 7):
@@ -110,36 +103,32 @@ def test_forms_agree(hbmod, gpu, tmp_path_factory):
     full = b.dynamics(jac=spec)
     st = b.get_state(hbmod.STATE_INTEGRATION)
     qpos, qvel = st[:, 1:1 + m.nq].copy(), st[:, 1 + m.nq:1 + m.nq + m.nv].copy()
-    _same(b.dynamics_states(qpos, qvel, jac=spec), full, "dynamics_states on get_state")
+    same_dict(b.dynamics_states(qpos, qvel, jac=spec), full, "dynamics_states on get_state")
     tape = b.dynamics_states(np.stack([qpos, qpos[::-1]]), np.stack([qvel, qvel[::-1]]), jac=spec)
     assert tape["M"].shape == (2, n, m.nv, m.nv) and tape["jac"].shape == (2, n, 16, 6, m.nv)
-    _same({k: a[1, ::-1] for k, a in tape.items()}, full, "leading shape")
+    same_dict({k: a[1, ::-1] for k, a in tape.items()}, full, "leading shape")
     nov = b.dynamics_states(qpos, None, bias=False, passive=False, jac=spec)
-    _same(nov, {k: full[k] for k in ("M", "jac")}, "qvel=None")
+    same_dict(nov, {k: full[k] for k in ("M", "jac")}, "qvel=None")
     for r in range(1, 4):
         for keep in itertools.combinations(QUANT, r):
             kw = dict(M="M" in keep, bias="bias" in keep, passive="passive" in keep, jac=spec if "jac" in keep else None)
-            _same(b.dynamics(**kw), {k: full[k] for k in QUANT if k in keep}, "subset %s" % (keep,))
-            _same(b.dynamics_states(qpos, qvel, **kw), {k: full[k] for k in QUANT if k in keep}, "states subset %s" % (keep,))
+            same_dict(b.dynamics(**kw), {k: full[k] for k in QUANT if k in keep}, "subset %s" % (keep,))
+            same_dict(b.dynamics_states(qpos, qvel, **kw), {k: full[k] for k in QUANT if k in keep}, "states subset %s" % (keep,))
     # device forms
     ptr = {k: b.dev_alloc(full[k].nbytes) for k in QUANT}
     b.dynamics_dev(ptr["M"], ptr["bias"], ptr["passive"], spec, ptr["jac"])
     b.sync()
-    _same({k: b.from_dev(ptr[k], full[k].shape) for k in QUANT}, full, "dynamics_dev")
+    same_dict({k: b.from_dev(ptr[k], full[k].shape) for k in QUANT}, full, "dynamics_dev")
     dq, dv = b.dev_alloc(qpos.nbytes), b.dev_alloc(qvel.nbytes)
     b.to_dev(dq, qpos); b.to_dev(dv, qvel)
     for k in QUANT:
         b.to_dev(ptr[k], np.zeros_like(full[k]))
     b.dynamics_states_dev(dq, dv, n, ptr["M"], ptr["bias"], ptr["passive"], spec, ptr["jac"])
     b.sync()
-    _same({k: b.from_dev(ptr[k], full[k].shape) for k in QUANT}, full, "dynamics_states_dev")
+    same_dict({k: b.from_dev(ptr[k], full[k].shape) for k in QUANT}, full, "dynamics_states_dev")
     for p in list(ptr.values()) + [dq, dv]:
         b.dev_free(p)
     b.close()
-
-
-def _snapshot(hbmod, b):
-    return [b.get_state(hbmod.STATE_INTEGRATION), b.status()] + list(b.counts()) + [np.array(b.step_launches()), b.qpos.copy(), b.qvel.copy()]
 
 
 def test_pure_function(hbmod, gpu, tmp_path_factory):
@@ -153,9 +142,9 @@ def test_pure_function(hbmod, gpu, tmp_path_factory):
         b.diag_enable(True)
         b.set_state(hbmod.STATE_INTEGRATION, np.asarray(states[:n]))
         b.step(ctrl)
-    before = _snapshot(hbmod, a) + [a.qacc(), a.efc_force()]
+    before = snapshot(hbmod, a, extra=[a.qpos.copy(), a.qvel.copy(), a.qacc(), a.efc_force()])
     a.dynamics(jac=spec)
-    for x, y in zip(before, _snapshot(hbmod, a) + [a.qacc(), a.efc_force()]):
+    for x, y in zip(before, snapshot(hbmod, a, extra=[a.qpos.copy(), a.qvel.copy(), a.qacc(), a.efc_force()])):
         assert np.array_equal(x, y)
     for b in (a, twin):
         b.step(ctrl)
@@ -192,7 +181,7 @@ def test_held_steps_come_first(hbmod, gpu, tmp_path_factory):
     st = b.get_state(hbmod.STATE_INTEGRATION)
     assert launches >= 1 and b.step_launches() - n0 == launches  # (the read-out is not counted)
     assert not np.array_equal(st[:, 1:1 + m.nq], big[:, 1:1 + m.nq].astype(np.float32))
-    _same(b.dynamics_states(st[:, 1:1 + m.nq].copy(), st[:, 1 + m.nq:1 + m.nq + m.nv].copy(), jac=spec), out, "held step calls")
+    same_dict(b.dynamics_states(st[:, 1:1 + m.nq].copy(), st[:, 1 + m.nq:1 + m.nq + m.nv].copy(), jac=spec), out, "held step calls")
     b.dev_free(d)
     b.close()
 
@@ -376,7 +365,7 @@ def test_bad_row_stays_alone(hbmod, gpu, tmp_path_factory):
     bad_q[2, 10] = np.nan
     bad = b.dynamics_states(bad_q, qvel, jac=spec)
     keep = [0, 1, 3, 4]
-    _same({k: a[keep] for k, a in bad.items()}, {k: a[keep] for k, a in good.items()}, "rows beside the bad one")
+    same_dict({k: a[keep] for k, a in bad.items()}, {k: a[keep] for k, a in good.items()}, "rows beside the bad one")
     assert np.array_equal(b.status(), status)
     b.close()
 
@@ -392,9 +381,9 @@ def test_vecenv(hbmod, gpu, humanoid_model):
     spec = env.batch.jac_spec(bodies=["torso"], subtree_coms=[0, "torso"])
     want = env.batch.dynamics(jac=spec)
     assert want["M"].shape == (32, 27, 27) and want["jac"].shape == (32, 3, 6, 27)
-    _same(env.dynamics(jac=spec), want, "VecEnv.dynamics")
+    same_dict(env.dynamics(jac=spec), want, "VecEnv.dynamics")
     t = env.dynamics_torch(jac=spec)
-    _same({k: a.cpu().numpy() for k, a in t.items()}, want, "VecEnv.dynamics_torch")
+    same_dict({k: a.cpu().numpy() for k, a in t.items()}, want, "VecEnv.dynamics_torch")
     t = env.dynamics_torch(M=True, bias=False, passive=False)
     assert set(t) == {"M"} and np.array_equal(t["M"].cpu().numpy(), want["M"])
     env.close()

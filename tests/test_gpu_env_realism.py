@@ -295,9 +295,7 @@ def test_floor_heightmap_randomization(hbmod, gpu):
     """CPUEnv._randomize_floor_heightmap (cpu_env.py:267-280) on the device: every env gets its own 8 x 8 elevation map,
     smooth noise shifted and scaled to [0, MIN + factor (MAX - MIN)], redrawn per episode; the collision kernel reads the
     env's own map (one step from identical states matches the oracle whose hfield_data was set to that env's map)."""
-    import os
-    from oracle_lib import ROOT
-    path = os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "humanoid27_hfield.hbm")
+    from oracle_lib import HFIELD_HBM as path
     m = hbmod.Model.load(path)
     n = 6
     env = hbmod.VecEnv(m, n, gpu, auto_reset=0, max_time=0.0, target_z=10.0)

@@ -2,50 +2,36 @@
 reference of tests/eq_ref.py: the oracle's forward pass with the equality and friction rows stacked in front.
 
 Models: tests/eq_models.py.  States of the chains: every 10th of a 300-step reference rollout, rounded to fp32; tests/test_eq_cpu.py
-holds the reference to things it does not define and checks what these state sets cover.  The bounds are test_gpu_kernel_matrix.BOUNDS,
-test_gpu_inverse.py's, test_gpu_contact_force.py's and test_gpu_parity.py's: imported or restated, never wider.
+holds the reference to things it does not define and checks what these state sets cover.  The bounds are bounds.BOUNDS,
+test_gpu_inverse.py's, the contact-force read-out's and the free-running bound (tests/bounds.py): imported, never wider.
 """
-import os
-
 import numpy as np
 import pytest
 
 import eq_ref
+from bounds import BOUNDS, FREE_RUNNING_BOUND, CONTACT_DECODE_BOUND as DECODE_BOUND, CONTACT_PARITY_BOUND as PARITY_BOUND
 from contact_ref import body_wrenches, contact_forces
-from eq_models import (DISABLED_KERNEL, FOURBAR_BENT, MODELS, NE, SLIDER_A0, SLIDER_SOLIMP, SLIDER_SOLREF, add_equality, eq_chain_xml, fourbar_xml, geared_xml,
-                       plain_chain_xml, reference, scissors_xml, slider_xml)
+from eq_models import (DISABLED_KERNEL, FOURBAR_BENT, MODELS, NE, SLIDER_A0, SLIDER_SOLIMP, SLIDER_SOLREF, add_equality, eq_chain_xml, eq_tmp,  # noqa: F401  (eq_tmp: a fixture)
+                       fourbar_xml, geared_xml, plain_chain_xml, reference, scissors_xml, slider_xml)
+from fric_models import add_friction
 from inverse_ref import force_scale, forward_at
-from kernel_models import chain_xml
-from oracle_lib import Oracle
-from test_gpu_contact_force import DECODE_BOUND, PARITY_BOUND
-from test_gpu_fric import _diag_step, _same, add_friction
-from test_gpu_kernel_matrix import BOUNDS, T
-
-FREE_RUNNING_BOUND = 1e-4  # (test_gpu_parity.py: relative qpos drift of its contact-free free-running window)
+from kernel_models import chain_xml, oracle_for
+from step_lib import T, diag_step, report, result, same
 
 
-@pytest.fixture(scope="session")
-def eq_tmp(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("eq"))
-
-
-def _report(line, env="HB_EQ_PARITY_OUT"):
-    print("\n  " + line)
-    out = os.environ.get(env)  # (set to collect the lines of profiles/eq_parity.txt)
-    if out:
-        with open(out, "a") as f:
-            f.write(line + "\n")
+def _report(line):
+    report(line, "HB_EQ_PARITY_OUT")  # (set to collect the lines of profiles/eq_parity.txt)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(MODELS))
 def test_one_step_against_the_reference(hbmod, gpu, eq_tmp, name):
     """Teacher-forced, diagnostics on: the expected kernel, counts and PGS sweep counts identical, qacc / efc_force / state / contacts
-    within test_gpu_kernel_matrix.BOUNDS, status zero.  Worst deviations: profiles/eq_parity.txt."""
+    within bounds.BOUNDS, status zero.  Worst deviations: profiles/eq_parity.txt."""
     p, o, st, ct, ref = reference(name, eq_tmp)
     m = hbmod.Model.load(p)
     assert m.equality_rows() == NE
-    d = _diag_step(hbmod, m, st, ct, gpu)
+    d = diag_step(hbmod, m, st, ct, gpu)
     assert d["kernel"] == MODELS[name][3], d["kernel"]
     assert not d["status"].any(), d["status"]
     worst = dict(qpos=0.0, qvel=0.0, qacc=0.0, force=0.0, dist=0.0, pos=0.0, frame=0.0)
@@ -143,7 +129,7 @@ def test_contact_force_readout(hbmod, gpu, eq_tmp):
     name = "eq28_cd3_pgs"
     p, o, st, ct, ref = reference(name, eq_tmp)
     m = hbmod.Model.load(p)
-    d = _diag_step(hbmod, m, st, ct, gpu, readout=True)
+    d = diag_step(hbmod, m, st, ct, gpu, readout=True)
     assert d["kernel"] == "hb_eq_kernel"
     gb = o.info["geom_bodyid"]
     seen = 0
@@ -176,25 +162,25 @@ def test_launch_shapes_are_bit_identical(hbmod, gpu, eq_tmp, name):
     m = hbmod.Model.load(p)
     kernel = MODELS[name][3]
     n = len(st)
-    ref1 = _diag_step(hbmod, m, st, ct, gpu)["result"]
+    ref1 = diag_step(hbmod, m, st, ct, gpu)["result"]
     ctrlT = np.random.default_rng(5).uniform(-1, 1, (T, n, m.nu)).astype(np.float32)
     ctrlT[0] = ct
     b = hbmod.Batch(m, n, gpu)
     b.set_state(hbmod.STATE_INTEGRATION, st); b.step(ct)
-    _same((b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status()), ref1, name + " step")
+    same(result(hbmod, b), ref1, name + " step")
     assert b.last_kernel() == kernel
     b.set_state(hbmod.STATE_INTEGRATION, st)
     b.rollout(ctrlT)
-    refT = (b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status())
+    refT = result(hbmod, b)
     assert b.last_kernel() == kernel and not refT[2].any()
     b.set_state(hbmod.STATE_INTEGRATION, st)
     for t in range(T):
         b.step(ctrlT[t])
-    _same((b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status()), refT, name + " steps")
+    same(result(hbmod, b), refT, name + " steps")
     assert b.last_kernel() == kernel
     b.set_state(hbmod.STATE_INTEGRATION, st)
     sens = b.rollout_sensors(ctrlT, hbmod.Batch.sensor_spec(framepos_bodies=(1, m.nbody - 1), linvel_bodies=(2,)))
-    _same((b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status()), refT, name + " rollout with sensors")
+    same(result(hbmod, b), refT, name + " rollout with sensors")
     assert b.last_kernel() == kernel and np.isfinite(np.asarray(sens[0] if isinstance(sens, tuple) else sens)).all()
     b.close()
     # two segments: the library cuts a batch into segments of at least 64 envs, so the states are tiled to 128 (the only batch here above 64)
@@ -209,10 +195,10 @@ def test_launch_shapes_are_bit_identical(hbmod, gpu, eq_tmp, name):
             b.step(ctrlT[t][idx])
         b.join()
         assert b.segments == (pipe or 1), b.segments
-        res.append((b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status()))
+        res.append(result(hbmod, b))
         assert b.last_kernel() == kernel
         b.close()
-    _same(res[1], res[0], name + " pipelined")
+    same(res[1], res[0], name + " pipelined")
     assert np.array_equal(res[0][0][:n], refT[0])
 
 
@@ -256,9 +242,9 @@ def test_disabled_means_absent(hbmod, gpu, eq_tmp, name, how):
     off = hbmod.Model.from_xml_string(eq_chain_xml(name, flag="disable") if how == "flag" else eq_chain_xml(name, inactive=True))
     plain = hbmod.Model.from_xml_string(plain_chain_xml(name))
     assert off.neq == 6 and off.equality_rows() == 0 and plain.neq == 0
-    a, b = _diag_step(hbmod, off, st, ct, gpu), _diag_step(hbmod, plain, st, ct, gpu)
+    a, b = diag_step(hbmod, off, st, ct, gpu), diag_step(hbmod, plain, st, ct, gpu)
     assert a["kernel"] == b["kernel"] == DISABLED_KERNEL[name], (a["kernel"], b["kernel"])
-    _same(a["result"], b["result"], name + " " + how)
+    same(a["result"], b["result"], name + " " + how)
     assert np.array_equal(a["qacc"], b["qacc"]) and np.array_equal(a["force"], b["force"]) and np.array_equal(a["con"], b["con"])
     # (and with nothing always active at all: the kernel of a plain chain)
     nv, condim, solver = MODELS[name][:3]
@@ -271,10 +257,8 @@ def test_disabled_means_absent(hbmod, gpu, eq_tmp, name, how):
 
 
 def _small(hbmod, xml, tmp, name):
-    p = os.path.join(tmp, name)
-    m = hbmod.Model.from_xml_string(xml)
-    m.save(p)
-    return m, Oracle(p)
+    m, _, o = oracle_for(hbmod, xml, tmp, name)
+    return m, o
 
 
 def _free_run(hbmod, gpu, m, o, q0, steps):

@@ -7,6 +7,8 @@ launch per call, for every pattern of calls that folds or has to stop folding.""
 import numpy as np
 import pytest
 
+from step_lib import everything
+
 pytestmark = pytest.mark.gpu
 N = 512  # (three segments of a pipelined batch: 170 / 171 envs, an odd number for the two-envs-per-wave kernel)
 T = 150
@@ -23,10 +25,6 @@ def _policy(m):
     sizes = [m.nobs, 32, m.nu]
     return ([(0.2 * rng.standard_normal((sizes[i], sizes[i + 1]))).astype(np.float32) for i in range(2)],
             [(0.1 * rng.standard_normal(sizes[i + 1])).astype(np.float32) for i in range(2)])
-
-
-def _everything(hbmod, b):
-    return (b.get_state(hbmod.STATE_INTEGRATION),) + tuple(b.counts()) + (b.status(),)
 
 
 def _same(x, y):
@@ -49,7 +47,7 @@ def test_folded_step_calls_are_bit_identical(hbmod, humanoid_model, gpu, duo, pi
             b.step_dev(ctrl + t * stride)
         b.sync()
         assert b.last_kernel() == (kernel if folds else kernel.replace("_q_kernel", "_kernel"))
-        got.append(_everything(hbmod, b))
+        got.append(everything(hbmod, b))
         b.dev_free(ctrl)
         b.close()
     assert _same(got[0], got[1])
@@ -79,7 +77,7 @@ def test_folded_calls_of_other_models_and_solvers(hbmod, gpu):
             b.sync()
             launches.append(b.step_launches() - n0)
             names.append(b.last_kernel())
-            got.append(_everything(hbmod, b))
+            got.append(everything(hbmod, b))
             b.dev_free(p)
             b.close()
         assert _same(got[0], got[1])
@@ -125,7 +123,7 @@ def test_fold_stops_where_it_has_to(hbmod, humanoid_model, gpu):
         for t in range(100, 110):
             b.step_dev(ctrl + t * stride)
         b.sync()
-        got.append(tuple(mid) + _everything(hbmod, b))
+        got.append(tuple(mid) + everything(hbmod, b))
         b.dev_free(ctrl); b.dev_free(one)
         b.close()
     assert _same(got[0], got[1]) and _same(got[0], got[2])

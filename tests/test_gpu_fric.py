@@ -5,121 +5,30 @@ Models: the capsule chains of tests/kernel_models.py at the two dense orders (nv
 frictionloss on every other joint in mixed magnitudes - some far above what a motor (gear 2) can push, so that the joint sticks, some far
 below, so that it slips - and solreffriction / solimpfriction of their own on some.  States: every 10th of a 300-step reference
 rollout, rounded to fp32.  tests/test_fric_cpu.py holds the reference to the oracle and checks what these state sets cover.
-The bounds are test_gpu_kernel_matrix.BOUNDS, test_gpu_inverse.py's and test_gpu_contact_force.py's: imported or restated, never wider.
+The bounds are bounds.BOUNDS, test_gpu_inverse.py's and the contact-force read-out's (tests/bounds.py): imported, never wider.
 """
-import functools
-import os
-import re
-
 import numpy as np
 import pytest
 
 import fric_ref
+from bounds import BOUNDS, CONTACT_DECODE_BOUND as DECODE_BOUND, CONTACT_PARITY_BOUND as PARITY_BOUND
 from contact_ref import body_wrenches, contact_forces
+from fric_models import MODELS, PLAIN_KERNEL, add_friction, fric_chain_xml, fric_tmp, pendulum_xml, reference  # noqa: F401  (fric_tmp: a fixture)
 from inverse_ref import force_scale, forward_at
 from kernel_models import chain_xml
-from oracle_lib import ROOT, Oracle, load_state
-from test_gpu_contact_force import DECODE_BOUND, PARITY_BOUND
-from test_gpu_kernel_matrix import BOUNDS, T
-
-FL = (4.0, 0.05, 0.6, 0.02, 3.0)  # frictionloss of the chain's joints 0, 2, 4, ...: above the motors' 2 N m (sticks) and below (slips)
-MODELS = {  # name -> (nv, condim, solver, step kernel, inverse kernel)
-    "fric28_cd3_pgs": (28, 3, "PGS", "hb_fric_kernel", "hb_fric_inverse_kernel"),
-    "fric32_cd3_pgs": (32, 3, "PGS", "hb_fric32_kernel", "hb_fric_inverse32_kernel"),
-    "fric28_cd1_newton": (28, 1, "Newton", "hb_fric_newton28_kernel", "hb_fric_inverse_kernel"),
-    "fric32_cd1_newton": (32, 1, "Newton", "hb_fric_newton32_kernel", "hb_fric_inverse32_kernel"),
-}
-PLAIN_KERNEL = {"fric28_cd3_pgs": "hb_step_kernel", "fric32_cd3_pgs": "hb_step32_kernel", "fric28_cd1_newton": "hb_step_newton28_kernel",
-                "fric32_cd1_newton": "hb_step_newton32_kernel"}
-
-
-def add_friction(xml, value=None, flag=None, solimp=None):
-    """chain_xml's MJCF with frictionloss on joints j0, j2, j4, ... (FL in turn, or `value` on EVERY joint, with the impedance `solimp`
-    if given), solreffriction on every fourth and solimpfriction on every sixth of them; flag: a <flag frictionloss=.../> value"""
-    def joint(mo):
-        j = int(mo.group(1))
-        if value is not None:
-            return '<joint name="j%d" frictionloss="%g"%s' % (j, value, ' solimpfriction="%g %g 0.001 0.5 2"' % (solimp, solimp) if solimp else "")
-        if j % 2:
-            return mo.group(0)
-        extra = ' frictionloss="%g"' % FL[(j // 2) % len(FL)]
-        if j % 4 == 0:
-            extra += ' solreffriction="0.03 1.2"'
-        if j % 6 == 0:
-            extra += ' solimpfriction="0.8 0.9 0.002 0.5 2"'
-        return '<joint name="j%d"%s' % (j, extra)
-    xml = re.sub(r'<joint name="j(\d+)"', joint, xml)
-    if flag:
-        xml = re.sub(r"(<option [^>]*?)/>", r'\1><flag frictionloss="%s"/></option>' % flag, xml, count=1)
-    return xml
-
-
-def fric_chain_xml(name, **kw):
-    nv, condim, solver = MODELS[name][:3]
-    return add_friction(chain_xml(nv, condim=condim, solver=solver), **kw)
-
-
-@functools.lru_cache(maxsize=None)
-def reference(name, tmp):
-    """(model .hbm path, oracle, states, ctrls, reference steps) of a model: computed once per session and shared, never changed"""
-    import humanoid_mujoco_amd as hb
-    p = os.path.join(tmp, name + ".hbm")
-    hb.Model.from_xml_string(fric_chain_xml(name)).save(p)
-    o = Oracle(p)
-    st, ct = fric_ref.rollout_states(o)
-    return p, o, st, ct, fric_ref.steps_ref(o, st, ct)
-
-
-@pytest.fixture(scope="session")
-def fric_tmp(tmp_path_factory):
-    return str(tmp_path_factory.mktemp("fric"))
-
-
-# (armature 1 and a friction impedance of 0.99: R = 0.0101 / 1.0533 = 0.0096, B = 2 / (0.99 * 0.02) = 101 - a held joint creeps at
-# tau R / B = 1.9e-4 rad / s, a fifth of test_stick_and_slip's 1e-3 rad in the 1 s it runs)
-PENDULUM = ('<mujoco><option timestep="0.002" solver="Newton" tolerance="1e-10"/><worldbody><body pos="0 0 1">'
-            '<joint name="h" type="hinge" axis="0 1 0" armature="1" frictionloss="%g" solimpfriction="0.99 0.99 0.001 0.5 2"/><geom type="capsule" fromto="0 0 0 %g 0 0" size="0.02" mass="1"/>'
-            '</body></worldbody></mujoco>')
-
-
-def pendulum_xml(fl, sign=1):
-    """a horizontal hinge pendulum at rest (a 0.4 m capsule of 1 kg along +-x about the y axis): gravity torque m g l / 2 = 1.962 N m"""
-    return PENDULUM % (fl, 0.4 * sign)
+from oracle_lib import Oracle
+from step_lib import T, diag_step, report, result, same
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
-def _diag_step(hb, m, st, ct, gpu, readout=False):
-    b = hb.Batch(m, len(st), gpu)
-    b.diag_enable(True)
-    if readout:
-        b.contact_readout(True)
-    b.set_state(hb.STATE_INTEGRATION, st)
-    b.step(ct)
-    nc, ne, ni = b.counts()
-    out = dict(qpos=b.qpos.astype(np.float64), qvel=b.qvel.astype(np.float64), qacc=b.qacc().astype(np.float64), force=b.efc_force().astype(np.float64),
-               con=b.contacts().astype(np.float64), ncon=nc, nefc=ne, niter=ni, status=b.status(), kernel=b.last_kernel(),
-               result=(b.get_state(hb.STATE_INTEGRATION), b.counts(), b.status()))
-    if readout:
-        out["cf"], out["bc"] = b.contact_force().astype(np.float64), b.body_contact().astype(np.float64)
-    b.close()
-    return out
-
-
-def _same(x, y, label):
-    assert np.array_equal(x[0], y[0]), (label, "state", np.abs(x[0] - y[0]).max())
-    for u, w in zip(x[1], y[1]):
-        assert np.array_equal(u, w), (label, "counts")
-    assert np.array_equal(x[2], y[2]), (label, "status")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(MODELS))
 def test_one_step_against_the_reference(hbmod, gpu, fric_tmp, name):
     """Teacher-forced, diagnostics on: the expected kernel, counts and PGS sweep counts identical, qacc / efc_force / state / contacts
-    within test_gpu_kernel_matrix.BOUNDS, friction-row forces inside their bound, status zero.  Worst deviations: profiles/fric_parity.txt."""
+    within bounds.BOUNDS, friction-row forces inside their bound, status zero.  Worst deviations: profiles/fric_parity.txt."""
     p, o, st, ct, ref = reference(name, fric_tmp)
     m = hbmod.Model.load(p)
-    d = _diag_step(hbmod, m, st, ct, gpu)
+    d = diag_step(hbmod, m, st, ct, gpu)
     assert d["kernel"] == MODELS[name][3], d["kernel"]
     assert not d["status"].any(), d["status"]
     fr = fric_ref.friction_rows(o)
@@ -144,11 +53,7 @@ def test_one_step_against_the_reference(hbmod, gpu, fric_tmp, name):
         worst["bound"] = max(worst["bound"], (np.abs(d["force"][k, :nf]) / fr["fl"]).max())
         assert not d["force"][k, ne:].any()
     line = "%-20s %-26s nf %2d, rows <= %2d: %s" % (name, d["kernel"], nf, max(ref["nefc"]), " ".join("%s %.2e" % kv for kv in worst.items()))
-    print("\n  " + line)
-    out = os.environ.get("HB_FRIC_PARITY_OUT")  # (set to collect the lines of profiles/fric_parity.txt)
-    if out:
-        with open(out, "a") as f:
-            f.write(line + "\n")
+    report(line, "HB_FRIC_PARITY_OUT")  # (set to collect the lines of profiles/fric_parity.txt)
     assert worst.pop("bound") <= 1.0 + 1e-6
     for key, x in worst.items():
         assert x <= BOUNDS[key], (name, key, x, BOUNDS[key])
@@ -163,21 +68,21 @@ def test_launch_shapes_are_bit_identical(hbmod, gpu, fric_tmp, name):
     m = hbmod.Model.load(p)
     kernel = MODELS[name][3]
     n = len(st)
-    ref1 = _diag_step(hbmod, m, st, ct, gpu)["result"]
+    ref1 = diag_step(hbmod, m, st, ct, gpu)["result"]
     ctrlT = np.random.default_rng(5).uniform(-1, 1, (T, n, m.nu)).astype(np.float32)
     ctrlT[0] = ct
     b = hbmod.Batch(m, n, gpu)
     b.set_state(hbmod.STATE_INTEGRATION, st); b.step(ct)
-    _same((b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status()), ref1, name + " step")
+    same(result(hbmod, b), ref1, name + " step")
     assert b.last_kernel() == kernel
     b.set_state(hbmod.STATE_INTEGRATION, st)
     b.rollout(ctrlT)
-    refT = (b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status())
+    refT = result(hbmod, b)
     assert b.last_kernel() == kernel and not refT[2].any()
     b.set_state(hbmod.STATE_INTEGRATION, st)
     for t in range(T):
         b.step(ctrlT[t])
-    _same((b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status()), refT, name + " steps")
+    same(result(hbmod, b), refT, name + " steps")
     assert b.last_kernel() == kernel
     b.close()
     # two segments: the library cuts a batch into segments of at least 64 envs, so the states are tiled to 128 (the only batch here above 64)
@@ -192,10 +97,10 @@ def test_launch_shapes_are_bit_identical(hbmod, gpu, fric_tmp, name):
             b.step(ctrlT[t][idx])
         b.join()
         assert b.segments == (pipe or 1), b.segments
-        res.append((b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status()))
+        res.append(result(hbmod, b))
         assert b.last_kernel() == kernel
         b.close()
-    _same(res[1], res[0], name + " pipelined")
+    same(res[1], res[0], name + " pipelined")
     assert np.array_equal(res[0][0][:n], refT[0])
 
 
@@ -212,7 +117,7 @@ def test_disabled_or_zero_friction_is_an_ordinary_model(hbmod, gpu, tmp_path, na
     o = Oracle(p)
     st, ct = rollout_states(o, steps=100)
     ref = oracle_steps(o, st, ct)
-    d = _diag_step(hbmod, m, st, ct, gpu)
+    d = diag_step(hbmod, m, st, ct, gpu)
     assert d["kernel"] == PLAIN_KERNEL[name], d["kernel"]
     assert not d["status"].any()
     for k in range(len(st)):
@@ -315,7 +220,7 @@ def test_contact_force_readout(hbmod, gpu, fric_tmp):
     name = "fric28_cd3_pgs"
     p, o, st, ct, ref = reference(name, fric_tmp)
     m = hbmod.Model.load(p)
-    d = _diag_step(hbmod, m, st, ct, gpu, readout=True)
+    d = diag_step(hbmod, m, st, ct, gpu, readout=True)
     assert d["kernel"] == "hb_fric_kernel"
     gb = o.info["geom_bodyid"]
     seen = 0

@@ -23,44 +23,25 @@ Two tiers, u = 2^-24:
      gamma V_terminal), so advantage by (1 + 2 gamma) eps_V / (1 - gamma lam) plus tier (a)'s bound, and returns by eps_V more.
 HB_GAE_PARITY_OUT=<file> collects the worst values (profiles/gae_parity.txt)."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import actor_ref as ar
 import gae_ref as gr
+from gae_lib import C_SCAN, CRITICS, GAMMA, LAM, NOBS, NU, OUTS, TAPES, VALUE_TOL, U, critic as _critic, log_std as _log_std  # noqa: F401
+from gae_lib import run as _run, scan_bounds as _scan_bounds
 from oracle_lib import HUMANOID_HBM  # noqa: F401  (the model of the humanoid_model fixture)
+from step_lib import report
 
 pytestmark = pytest.mark.gpu
 
-NOBS, NU, SEED = 48, 21, 2024
-U = 2.0 ** -24
-VALUE_TOL = 5e-5
-C_SCAN = 5
+SEED = 2024
 C_LOGP = {ar.GAUSSIAN: 3, ar.SQUASHED: 12}
-GAMMA, LAM = float(np.float32(0.99)), float(np.float32(0.95))  # (what the C struct holds: the reference gets the same numbers)
-CRITICS = {"linear": [NOBS, 1], "small": [NOBS, 40, 24, 1], "wide": [NOBS, 256, 256, 1]}
-TAPES = ("obs", "action", "mean", "log_std", "eps", "reward", "terminated", "truncated", "terminal_obs")
-OUTS = ("value", "terminal_value", "log_prob", "advantage", "returns")
 
 
 def _report(line):
-    print("\n  " + line)
-    out = os.environ.get("HB_GAE_PARITY_OUT")
-    if out:
-        with open(out, "a") as f:
-            f.write(line + "\n")
-
-
-def _critic(kind):
-    sizes = CRITICS[kind]
-    ws, bs = ar.make_actor(sizes, seed=21, scale=0.35 if len(sizes) > 2 else 0.5)
-    return sizes, ws, bs
-
-
-def _log_std():
-    return np.linspace(-1.5, 0.3, NU).astype(np.float32)
+    report(line, "HB_GAE_PARITY_OUT")
 
 
 def _blocks(T, n):
@@ -122,32 +103,6 @@ def _cut(tp, lo, hi):
     return {k: np.ascontiguousarray(v[:, lo:hi]) for k, v in tp.items()}
 
 
-def _run(b, T, tp, gamma=GAMMA, lam=LAM, boot=True, outs=OUTS, tapes=TAPES, raw=False):
-    """uploads the tapes, calls hb_collect_gae_dev with the outputs in `outs` (prefilled with NaN), returns them as numpy (raw: the return
-    code and the outputs, no exception)"""
-    n = b.n_env
-    tptr = {k: b.dev_alloc(max(4, tp[k].nbytes)) for k in tapes}
-    for k in tapes:
-        b.to_dev(tptr[k], tp[k])
-    shape = {k: (T + 1, n) if k == "value" else (T, n) for k in outs}
-    optr = {k: b.dev_alloc(max(4, int(np.prod(s)) * 4)) for k, s in shape.items()}
-    for k, s in shape.items():
-        if np.prod(s):
-            b.to_dev(optr[k], np.full(s, np.nan, np.float32))
-    try:
-        if raw:
-            import humanoid_mujoco_amd as hbm
-            rc = hbm.lib().hb_collect_gae_dev(b._h, T, ctypes.byref(hbm.HbCollectOut(**tptr)), ctypes.byref(hbm.HbGaeConfig(gamma, lam, int(boot))),
-                                              ctypes.byref(hbm.HbGaeOut(**optr)))
-        else:
-            b.collect_gae_dev(T, gamma, lam, boot, **tptr, **optr)
-        got = {k: b.from_dev(optr[k], s) for k, s in shape.items()}
-    finally:
-        for p in list(tptr.values()) + list(optr.values()):
-            b.dev_free(p)
-    return (rc, got) if raw else got
-
-
 def _batch(hbmod, m, n, gpu, critic="small", head=ar.GAUSSIAN):
     b = hbmod.Batch(m, n, gpu)
     sizes, ws, bs = _critic(critic)
@@ -157,16 +112,6 @@ def _batch(hbmod, m, n, gpu, critic="small", head=ar.GAUSSIAN):
         aw, ab = ar.make_actor(asz, seed=5)
         b.actor_set(asz, aw, ab, head=head, log_std=_log_std() if head == ar.GAUSSIAN else None, seed=SEED)
     return b, ws, bs
-
-
-def _scan_bounds(tp, value, tv, gamma, lam, boot=True):
-    """(reference advantage, returns, tier (a) bound of advantage, of returns) for the given value tapes"""
-    adv, ret = gr.gae(tp["reward"], value, tv, tp["terminated"], tp["truncated"], gamma, lam, boot)
-    rp = gr.shaped_reward(tp["reward"], tv, tp["terminated"], tp["truncated"], gamma, boot)
-    v = np.asarray(value, dtype=np.float64)
-    S = float((np.abs(rp) + 2.0 * np.maximum(np.abs(v[:-1]), np.abs(v[1:])) + np.abs(adv)).max())
-    b_adv = C_SCAN * U * S / (1.0 - gamma * lam)
-    return adv, ret, b_adv, b_adv + U * S
 
 
 def _logp_bound(head, tp, ls):

@@ -10,12 +10,9 @@ import numpy as np
 import pytest
 
 from inverse_ref import force_scale, forward_at, inverse_ref, inverse_terms
-from oracle_lib import GOLDEN, HUMANOID_HBM, Oracle
+from oracle_lib import ASSETS, GOLDEN, HUMANOID_HBM, Oracle, MODELS_DIR as MODELS
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODELS = os.path.join(ROOT, "tests", "models")
-ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
 SOL_NEWTON = 2
 
 

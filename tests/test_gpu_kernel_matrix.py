@@ -7,7 +7,7 @@ TABLE has one row per (model, launch, knobs) and the kernel that launch must run
   - the full one-step kernel with the diagnostic outputs ("diag") against the oracle, teacher-forced from states every 10 steps along a
     300-step oracle rollout (rounded to fp32 first, then stepped by both): counts identical, PGS sweep counts identical, qacc and
     efc_force within 4e-4 * max(1, max|.|), qpos within 4e-5 relative, qvel within 4e-4 * max(1, max|qvel|), contact dist / pos
-    within 1e-5 and frame within 1e-3, status zero (the golden bounds of tests/test_gpu_parity.py);
+    within 1e-5 and frame within 1e-3, status zero (bounds.BOUNDS, the golden bounds of tests/test_gpu_parity.py);
   - every other launch of the row set bit for bit against it: one-step launches ("step") against the diag step, multi-step launches
     ("rollout", "steps": T single step calls) against the full kernel's T-step rollout ("rollout_qpos"), in state, counts and status;
   - rows whose knob selects another algorithm (staged=0, fastpass=0: the fused general step) are diag launches held to the oracle;
@@ -18,38 +18,16 @@ must be PROVED to sit within fp32 rounding of one where the oracle gives the dev
 The worst deviation of every model is printed (pytest -s); profiles/kernel_matrix_parity.txt holds the numbers measured on MI355X.
 """
 import os
-import re
 
 import numpy as np
 import pytest
 
 from inverse_ref import force_scale, forward_at, inverse_terms
 from kernel_models import CONFIG_COLUMNS, chain_xml, kernel_table, oracle_for, oracle_steps, perturbed_hbm, rollout_states, row_kinds
-from oracle_lib import HUMANOID_HBM, ROOT, Oracle, load_state, prove_rounding_fence
+from oracle_lib import HFIELD_HBM, HUMANOID_HBM, MODELS_DIR, TEAM_HBM, Oracle
+from step_lib import CHAINS, T, kernel_names_in_source, result, same, state_vs_oracle, vs_oracle
 
-ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
-CSRC = os.path.join(ROOT, "humanoid_mujoco_amd", "csrc")
-HFIELD_HBM = os.path.join(ASSETS, "humanoid27_hfield.hbm")
-TEAM_HBM = os.path.join(ASSETS, "team_robot.hbm")
-T = 5  # steps of the multi-step launches
-BOUNDS = dict(qpos=4e-5, qvel=4e-4, qacc=4e-4, force=4e-4, dist=1e-5, pos=1e-5, frame=1e-3)
-
-# ---- models: generated chains (nv, base, floor, condim, solver) and the assets / their same-size copies
-CHAINS = {}
-for _nv in (20, 21, 28, 29, 31, 32):
-    CHAINS["chain%d_cd3_pgs" % _nv] = (_nv, True, "plane", 3, "PGS")
-    CHAINS["chain%d_cd1_newton" % _nv] = (_nv, True, "plane", 1, "Newton")
-for _nv in (28, 32):
-    CHAINS["chain%d_cd1_pgs" % _nv] = (_nv, True, "plane", 1, "PGS")
-    CHAINS["chain%d_cd3_newton" % _nv] = (_nv, True, "plane", 3, "Newton")
-CHAINS["chain28_fixed_cd3_pgs"] = (28, False, "plane", 3, "PGS")
-CHAINS["chain28_fixed_cd1_newton"] = (28, False, "plane", 1, "Newton")
-for _nv in (20, 21, 28):
-    CHAINS["chain%d_cd6_newton" % _nv] = (_nv, True, "plane", 6, "Newton")
-for _nv in (21, 28):
-    CHAINS["chain%d_cd4_pgs" % _nv] = (_nv, True, "plane", 4, "PGS")
-    CHAINS["chain%d_cd6_pgs" % _nv] = (_nv, True, "plane", 6, "PGS")
-    CHAINS["chain%d_hfield_pgs" % _nv] = (_nv, True, "hfield", 3, "PGS")
+# ---- models: the generated chains (step_lib.CHAINS) and the assets / their same-size copies
 # the assets: (path, solver override, keyframe, perturbed)
 ASSET_MODELS = {
     "humanoid27_pgs": (HUMANOID_HBM, None, -1, False),
@@ -128,19 +106,11 @@ DUO_KERNELS = {"hb_step_duo_kernel", "hb_step_duo_q_kernel"}  # (also held to th
 NOT_BIT_IDENTICAL = ("staged", "fastpass")  # knobs that select another algorithm: those rows are held to the oracle instead
 
 
-def _kernel_names_in_source():
-    names = {n for n, _ in kernel_table() if re.fullmatch(r"hb_step\w*_kernel", n)}  # rows of hb_step.hip's kernel table
-    for f in ("hb_step.hip", "hb_step_duo.hip"):
-        src = open(os.path.join(CSRC, f)).read()
-        names |= set(re.findall(r"__global__[^;{]*?\bvoid\s+(hb_step\w*_kernel)\s*\(", src))  # defined by hand (the duo kernels)
-    return names
-
-
 def test_table_names_every_step_kernel():
     """(CPU) the table must name every step-kernel instantiation of hb_step.hip / hb_step_duo.hip: a new one fails here until it has a
     row, and a row cannot name a kernel that does not exist"""
     table = {k for rows in TABLE.values() for _, _, k in rows}
-    src = _kernel_names_in_source()
+    src = kernel_names_in_source()
     assert len(src) >= 25
     assert src == table | DUO_KERNELS, (sorted(src - table - DUO_KERNELS), sorted(table - src))
 
@@ -192,116 +162,6 @@ def _setup(hbmod, name, tmp_path):
     return m, path, o, st, ct, path.endswith(("hfield.hbm", "team_robot.hbm"))
 
 
-def _contacts_ok(o, con, nc, ne):
-    """the oracle's contacts (after forward) against one env's device records: None if counts, geoms or dims differ, else the worst
-    (dist, pos, frame) deviations"""
-    if (o.ncon, o.nefc) != (nc, ne):
-        return None
-    w = np.zeros(3)
-    for i, c in enumerate(o.contacts()):
-        if (int(con[i, 14]), int(con[i, 15])) != (c["geom1"], c["geom2"]):
-            return None
-        w = np.maximum(w, (abs(con[i, 0] - c["dist"]), np.abs(con[i, 1:4] - c["pos"]).max(), np.abs(con[i, 4:13] - c["frame"].reshape(-1)).max()))
-    return w
-
-
-def _vs_oracle(hbmod, b, o, st, ct, fences_ok, label, before=None):
-    """one diag step of batch b from the states against the oracle from the same states; returns the worst deviations.  before(k), if
-    given, is called ahead of env k's oracle step (tests/test_gpu_domain_params.py: it writes env k's model parameters into the oracle)"""
-    b.diag_enable(True)
-    b.set_state(hbmod.STATE_INTEGRATION, st)
-    b.step(ct)
-    q, v, a = b.qpos.astype(np.float64), b.qvel.astype(np.float64), b.qacc().astype(np.float64)
-    f, con = b.efc_force().astype(np.float64), b.contacts().astype(np.float64)
-    nc, ne, ni = b.counts()
-    b.diag_enable(False)
-    assert not b.status().any(), (label, b.status())
-    worst = dict(qpos=0.0, qvel=0.0, qacc=0.0, force=0.0, dist=0.0, pos=0.0, frame=0.0)
-    fences = 0
-    pgs = o.opt("solver") != 2
-    for k in range(len(st)):
-        if before is not None:
-            before(k)
-        load_state(o, st[k], ct[k].astype(np.float64))
-        o.forward()
-        w = _contacts_ok(o, con[k], nc[k], ne[k])
-        on_fence = w is None and fences_ok
-        if on_fence:
-            got = {}
-
-            def accept(oo):
-                oo.forward()
-                got["w"] = _contacts_ok(oo, con[k], nc[k], ne[k])
-                return got["w"] is not None
-            assert prove_rounding_fence(o, st[k], ct[k].astype(np.float64), accept, seed=k) is not None, (label, k, "contacts differ, no fence proof")
-            w = got["w"]
-            fences += 1
-        assert w is not None, (label, k, "counts / contacts differ", (nc[k], ne[k]), (o.ncon, o.nefc))
-        if pgs and ne[k]:
-            assert ni[k] == o.dint("solver_niter"), (label, k, ni[k], o.dint("solver_niter"))
-        worst["dist"], worst["pos"], worst["frame"] = max(worst["dist"], w[0]), max(worst["pos"], w[1]), max(worst["frame"], w[2])
-        worst["qacc"] = max(worst["qacc"], np.abs(a[k] - o.qacc).max() / max(1.0, np.abs(o.qacc).max()))
-        if o.nefc:
-            fo = o.efc_force[:o.nefc]
-            worst["force"] = max(worst["force"], np.abs(f[k, :o.nefc] - fo).max() / max(1.0, np.abs(fo).max()))
-        o.step()
-        if not on_fence:  # (the neighbouring state differs from the device's in qpos by construction)
-            worst["qpos"] = max(worst["qpos"], (np.abs(q[k] - o.qpos) / np.maximum(1.0, np.abs(o.qpos))).max())
-        worst["qvel"] = max(worst["qvel"], np.abs(v[k] - o.qvel).max() / max(1.0, np.abs(o.qvel).max()))
-    print("  %-48s worst %s, %d states on a proved rounding fence" % (label, " ".join("%s %.2e" % kv for kv in worst.items()), fences))
-    assert fences <= max(1, 0.05 * len(st)), (label, fences)
-    for key, x in worst.items():
-        assert x <= BOUNDS[key], (label, key, x, BOUNDS[key])
-    return worst
-
-
-def _state_vs_oracle(hbmod, b, o, st, ct, fences_ok, label, before=None):
-    """the state a one-step launch of batch b left (no diagnostic outputs) against the oracle's step from the same states: counts and
-    PGS sweep counts identical, qpos and qvel within the golden bounds"""
-    q, v = b.qpos.astype(np.float64), b.qvel.astype(np.float64)
-    nc, ne, ni = b.counts()
-    assert not b.status().any(), (label, b.status())
-    worst = dict(qpos=0.0, qvel=0.0)
-    fences = 0
-    pgs = o.opt("solver") != 2
-    for k in range(len(st)):
-        if before is not None:
-            before(k)
-        load_state(o, st[k], ct[k].astype(np.float64))
-        o.forward()
-        on_fence = (o.ncon, o.nefc) != (nc[k], ne[k])
-        if on_fence:
-            assert fences_ok, (label, k, "counts differ", (nc[k], ne[k]), (o.ncon, o.nefc))
-
-            def accept(oo):
-                oo.forward()
-                return (oo.ncon, oo.nefc) == (nc[k], ne[k])
-            assert prove_rounding_fence(o, st[k], ct[k].astype(np.float64), accept, seed=k) is not None, (label, k, "counts differ, no fence proof")
-            fences += 1
-        if pgs and ne[k]:
-            assert ni[k] == o.dint("solver_niter"), (label, k, ni[k], o.dint("solver_niter"))
-        o.step()
-        if not on_fence:
-            worst["qpos"] = max(worst["qpos"], (np.abs(q[k] - o.qpos) / np.maximum(1.0, np.abs(o.qpos))).max())
-        worst["qvel"] = max(worst["qvel"], np.abs(v[k] - o.qvel).max() / max(1.0, np.abs(o.qvel).max()))
-    print("  %-48s worst %s, %d states on a proved rounding fence" % (label, " ".join("%s %.2e" % kv for kv in worst.items()), fences))
-    assert fences <= max(1, 0.05 * len(st)), (label, fences)
-    for key, x in worst.items():
-        assert x <= BOUNDS[key], (label, key, x, BOUNDS[key])
-    return worst
-
-
-def _result(hbmod, b):
-    return b.get_state(hbmod.STATE_INTEGRATION), b.counts(), b.status()
-
-
-def _same(x, y, label):
-    assert np.array_equal(x[0], y[0]), (label, "state", np.abs(x[0] - y[0]).max())
-    for u, w in zip(x[1], y[1]):
-        assert np.array_equal(u, w), (label, "counts")
-    assert np.array_equal(x[2], y[2]), (label, "status")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(TABLE))
 def test_kernel_matrix(hbmod, gpu, tmp_path, name):
@@ -318,19 +178,19 @@ def test_kernel_matrix(hbmod, gpu, tmp_path, name):
     print("\n%s (nv %d):" % (name, m.nv))
     # the references: the diag step (against the oracle) and the full kernel's T-step rollout
     b = batch({})
-    _vs_oracle(hbmod, b, o, st, ct, fences_ok, name + " diag")
-    ref1 = _result(hbmod, b)
+    vs_oracle(hbmod, b, o, st, ct, fences_ok, name + " diag")
+    ref1 = result(hbmod, b)
     fast = rows[0][2] in BIG_KERNELS
     if fast:
         f = batch({"lean": 0})
         f.set_state(hbmod.STATE_INTEGRATION, st)
         f.step(ct)
-        _state_vs_oracle(hbmod, f, o, st, ct, fences_ok, "%s fast kernel [%s]" % (name, f.last_kernel()))
-        ref1 = _result(hbmod, f)
+        state_vs_oracle(hbmod, f, o, st, ct, fences_ok, "%s fast kernel [%s]" % (name, f.last_kernel()))
+        ref1 = result(hbmod, f)
         f.close()
     b.set_state(hbmod.STATE_INTEGRATION, st)
     qT = b.rollout(ctrlT, want_qpos=True)
-    refT = _result(hbmod, b)
+    refT = result(hbmod, b)
     assert np.array_equal(qT[-1], refT[0][:, 1:1 + m.nq])
     assert ref1[1][1].max() > 0 and not refT[2].any()
     b.close()
@@ -339,23 +199,23 @@ def test_kernel_matrix(hbmod, gpu, tmp_path, name):
         b = batch(knobs)
         if launch == "diag" and knobs:
             assert set(knobs) <= set(NOT_BIT_IDENTICAL), label
-            _vs_oracle(hbmod, b, o, st, ct, fences_ok, label)
+            vs_oracle(hbmod, b, o, st, ct, fences_ok, label)
         elif launch == "diag":
             b.diag_enable(True); b.set_state(hbmod.STATE_INTEGRATION, st); b.step(ct)
             if not fast:
-                _same(_result(hbmod, b), ref1, label)
+                same(result(hbmod, b), ref1, label)
         elif launch == "step":
             b.set_state(hbmod.STATE_INTEGRATION, st); b.step(ct)
-            _same(_result(hbmod, b), ref1, label)
+            same(result(hbmod, b), ref1, label)
         elif launch == "steps":
             b.set_state(hbmod.STATE_INTEGRATION, st)
             for t in range(T):
                 b.step(ctrlT[t])
-            _same(_result(hbmod, b), refT, label)
+            same(result(hbmod, b), refT, label)
         else:
             b.set_state(hbmod.STATE_INTEGRATION, st)
             q = b.rollout(ctrlT, want_qpos=launch == "rollout_qpos")
-            _same(_result(hbmod, b), refT, label)
+            same(result(hbmod, b), refT, label)
             if q is not None:
                 assert np.array_equal(q, qT), label
         assert b.last_kernel() == kernel, (label, b.last_kernel(), kernel)
@@ -398,10 +258,10 @@ def test_schedule_knob_is_bit_identical_on_a_pipelined_batch(hbmod, humanoid_mod
         for t in range(10):
             b.step(ctrl[t])
         b.join()
-        res.append(_result(hbmod, b))
+        res.append(result(hbmod, b))
         assert b.segments > 1
         b.close()
-    _same(res[0], res[1], "schedule=0")
+    same(res[0], res[1], "schedule=0")
     assert res[0][1][1].max() > 0
 
 
@@ -413,7 +273,7 @@ def test_narrow_prim_knob_is_bit_identical(hbmod, gpu, tmp_path, model):
         m, p, o = oracle_for(hbmod, chain_xml(*CHAINS[model]), tmp_path)
         st, ct = rollout_states(o)
     else:
-        m = hbmod.Model.load(os.path.join(ROOT, "tests", "models", model + ".xml"))
+        m = hbmod.Model.load(os.path.join(MODELS_DIR, model + ".xml"))
         p = str(tmp_path / "m.hbm"); m.save(p)
         st, ct = rollout_states(Oracle(p))
     n = len(st)
@@ -424,9 +284,9 @@ def test_narrow_prim_knob_is_bit_identical(hbmod, gpu, tmp_path, model):
         b.set_state(hbmod.STATE_INTEGRATION, st)
         for _ in range(T):
             b.step(ct)
-        res.append(_result(hbmod, b))
+        res.append(result(hbmod, b))
         b.close()
-    _same(res[0], res[1], model + " narrow_prim=0")
+    same(res[0], res[1], model + " narrow_prim=0")
     assert res[0][1][0].max() > 0
 
 

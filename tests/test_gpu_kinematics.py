@@ -2,7 +2,7 @@
 mj_comVel products (tests/kin_ref.py), and its contract as a pure function of the state: the same bits whatever the packing, the batch
 size, a state's place in a wave or the form of the call, nothing of the batch written.
 
-Bounds (errors relative to max(1, max |reference|) of the state): the project's convention is 3 x the maxima of
+Bounds (bounds.POSE_BOUND, VEL_BOUND; errors relative to max(1, max |reference|) of the state): the project's convention is 3 x the maxima of
 profiles/kinematics_parity.txt (tools/gpu_kinematics_report.py, the same cases), capped at the 1.8e-6 DECODE_BOUND of
 tests/test_gpu_body_acc.py, which covers the same fp32 kinematics plus a longer sum.
     poses       measured maximum 5.146e-7 (chain32), 3 x = 1.5438e-6          -> 1.54e-6 (rounded down)
@@ -14,12 +14,10 @@ import numpy as np
 import pytest
 
 import kin_ref
+from bounds import POSE_BOUND, VEL_BOUND
+from step_lib import same_dict, snapshot
 
 pytestmark = pytest.mark.gpu
-
-POSE_BOUND = 1.54e-6
-VEL_BOUND = 1.8e-6
-assert POSE_BOUND <= 1.8e-6 and VEL_BOUND <= 1.8e-6
 
 _cache = {}
 
@@ -47,12 +45,6 @@ def _readout(hbmod, m, states, gpu, **tune):
     return out, kernel
 
 
-def _same(a, b, label):
-    assert a.keys() == b.keys(), label
-    for k in a:
-        assert a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), (label, k)
-
-
 @pytest.mark.parametrize("name", kin_ref.CASES)
 def test_parity(hbmod, gpu, tmp_path_factory, name):
     """1: every state of every case inside both bounds, on the kernel the model's size asks for"""
@@ -73,17 +65,17 @@ def test_packing_is_bit_identical(hbmod, gpu, tmp_path_factory, name):
     packed, k1 = _readout(hbmod, m, states, gpu)
     plain, k0 = _readout(hbmod, m, states, gpu, kin_pack=0)
     assert (k1, k0) == (kernel, "hb_kin64_kernel")
-    _same(packed, plain, "kin_pack")
+    same_dict(packed, plain, "kin_pack")
     for n in (1, 3, 5):
         out, _ = _readout(hbmod, m, states[:n], gpu)
-        _same(out, {k: a[:n] for k, a in packed.items()}, "n_env %d" % n)
+        same_dict(out, {k: a[:n] for k, a in packed.items()}, "n_env %d" % n)
     big = np.tile(states, (137, 1))[:4097]
     out, _ = _readout(hbmod, m, big, gpu)
     for pack in (1, 0):
         for e in (0, 1, 4095, 4096):
             one, _ = _readout(hbmod, m, big[e:e + 1], gpu, kin_pack=pack)
-            _same(one, {k: a[e:e + 1] for k, a in out.items()}, "row %d of 4097, kin_pack %d" % (e, pack))
-    _same({k: a[:len(states)] for k, a in out.items()}, packed, "4097")
+            same_dict(one, {k: a[e:e + 1] for k, a in out.items()}, "row %d of 4097, kin_pack %d" % (e, pack))
+    same_dict({k: a[:len(states)] for k, a in out.items()}, packed, "4097")
 
 
 def test_states_permuted(hbmod, gpu, tmp_path_factory):
@@ -94,7 +86,7 @@ def test_states_permuted(hbmod, gpu, tmp_path_factory):
     a = b.kinematics_states(qpos, qvel, geoms=True)
     perm = np.random.default_rng(0).permutation(len(qpos))
     p = b.kinematics_states(qpos[perm], qvel[perm], geoms=True)
-    _same({k: v[perm] for k, v in a.items()}, p, "permuted")
+    same_dict({k: v[perm] for k, v in a.items()}, p, "permuted")
     b.close()
 
 
@@ -112,17 +104,17 @@ def test_states_form(hbmod, gpu, tmp_path_factory):
     for t in range(T):
         rec[:, 1:1 + m.nq], rec[:, 1 + m.nq:1 + m.nq + m.nv] = q[t], v[t]
         b.set_state(hbmod.STATE_INTEGRATION, rec)
-        _same(b.kinematics(geoms=True), {k: a[t] for k, a in tape.items()}, "step %d" % t)
+        same_dict(b.kinematics(geoms=True), {k: a[t] for k, a in tape.items()}, "step %d" % t)
     b.close()
     b = hbmod.Batch(m, 4, gpu)
     qpos, qvel = kin_ref.split_state(o, states[:7])
     seven = b.kinematics_states(qpos, qvel, geoms=True)
     assert seven["pose"].shape == (7, m.nbody, 10)
     full, _ = _readout(hbmod, m, states[:7], gpu)
-    _same(seven, full, "n = 7 on 4 envs")
+    same_dict(seven, full, "n = 7 on 4 envs")
     nov = b.kinematics_states(qpos, None, vel=False, geoms=True)
     assert set(nov) == {"pose", "geoms"}
-    _same(nov, {k: seven[k] for k in nov}, "qvel=None")
+    same_dict(nov, {k: seven[k] for k in nov}, "qvel=None")
     # device forms
     sizes = {"pose": m.nbody * 10, "vel": m.nbody * 6, "geoms": m.ngeom * 7}
     ptr = {k: b.dev_alloc(4 * 7 * s) for k, s in sizes.items()}
@@ -130,19 +122,15 @@ def test_states_form(hbmod, gpu, tmp_path_factory):
     b.to_dev(dq, qpos); b.to_dev(dv, qvel)
     b.kinematics_states_dev(dq, dv, 7, ptr["pose"], ptr["vel"], ptr["geoms"])
     b.sync()
-    _same({k: b.from_dev(ptr[k], seven[k].shape) for k in sizes}, seven, "kinematics_states_dev")
+    same_dict({k: b.from_dev(ptr[k], seven[k].shape) for k in sizes}, seven, "kinematics_states_dev")
     b.set_state(hbmod.STATE_INTEGRATION, np.asarray(states[:4]))
     host = b.kinematics(geoms=True)
     b.kinematics_dev(ptr["pose"], ptr["vel"], ptr["geoms"])
     b.sync()
-    _same({k: b.from_dev(ptr[k], host[k].shape) for k in sizes}, host, "kinematics_dev")
+    same_dict({k: b.from_dev(ptr[k], host[k].shape) for k in sizes}, host, "kinematics_dev")
     for p in list(ptr.values()) + [dq, dv]:
         b.dev_free(p)
     b.close()
-
-
-def _snapshot(hbmod, b):
-    return [b.get_state(hbmod.STATE_INTEGRATION), b.status()] + list(b.counts()) + [np.array(b.step_launches())]
 
 
 def test_pure_function(hbmod, gpu, tmp_path_factory):
@@ -154,9 +142,9 @@ def test_pure_function(hbmod, gpu, tmp_path_factory):
     for b in (a, twin):
         b.set_state(hbmod.STATE_INTEGRATION, np.asarray(states[:n]))
         b.step(ctrl)
-    before = _snapshot(hbmod, a)
+    before = snapshot(hbmod, a)
     a.kinematics(geoms=True)
-    for x, y in zip(before, _snapshot(hbmod, a)):
+    for x, y in zip(before, snapshot(hbmod, a)):
         assert np.array_equal(x, y)
     for b in (a, twin):
         b.step(ctrl)
@@ -182,8 +170,8 @@ def test_pure_function(hbmod, gpu, tmp_path_factory):
         outs.append({"state": b.get_state(hbmod.STATE_INTEGRATION)})
         b.dev_free(d)
         b.close()
-    _same(outs[0], outs[2], "held step calls")
-    _same(outs[1], outs[3], "state after")
+    same_dict(outs[0], outs[2], "held step calls")
+    same_dict(outs[1], outs[3], "state after")
     assert not np.array_equal(outs[1]["state"][:, 1:1 + m.nq], big[:, 1:1 + m.nq].astype(np.float32))
     # a free joint's quaternion of norm 1.3
     b = hbmod.Batch(m, 1, gpu)
@@ -275,7 +263,7 @@ def test_bad_row_stays_alone(hbmod, gpu, tmp_path_factory):
     bad_q[2, 10] = np.nan
     bad = b.kinematics_states(bad_q, qvel, geoms=True)
     keep = [0, 1, 3, 4]
-    _same({k: a[keep] for k, a in bad.items()}, {k: a[keep] for k, a in good.items()}, "rows beside the bad one")
+    same_dict({k: a[keep] for k, a in bad.items()}, {k: a[keep] for k, a in good.items()}, "rows beside the bad one")
     assert np.array_equal(b.status(), status)
     b.close()
 

@@ -11,10 +11,11 @@ import os
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden", "mjpc_expectations.npz")
-TWO_MOTORS = os.path.join(ROOT, "tests", "models", "two_motors.xml")
-PARTICLE = os.path.join(ROOT, "tests", "golden", "particle_task.hbm")
+from oracle_lib import GOLDEN, MODELS_DIR, ROOT
+
+GOLD = os.path.join(GOLDEN, "mjpc_expectations.npz")
+TWO_MOTORS = os.path.join(MODELS_DIR, "two_motors.xml")
+PARTICLE = os.path.join(GOLDEN, "particle_task.hbm")
 TOL = 2e-6  # fp32 evaluation of values that are exact binary fractions or one rounding away from them; the reference compares with == (ElementsAre)
 
 

@@ -9,7 +9,7 @@ Rows with contact records (diagnostics on), per case against the oracle from the
     a centre on an axis) must match the unperturbed oracle; an ill-conditioned case (tests/test_pair_cases_cpu.py: its perturbed oracle
     evaluations disagree on the count) may match the count of any of them; ncon and nefc;
   - geom ids and dim identical; the frame orthonormal to 1e-5, its first row the normal;
-  - dist, pos and normal within BASE + K * envelope.  BASE is the project's measured contact bounds (test_gpu_convex.TOL: dist 5e-7, pos
+  - dist, pos and normal within BASE + K * envelope.  BASE is the project's measured contact bounds (bounds.CONVEX_TOL: dist 5e-7, pos
     3e-6, normal 3e-5).  The envelope is the oracle's own spread under one fp32 rounding of qpos (32 draws of 2^-24 max(1, |qpos|) N(0, 1)).
     K = 4, from the roundings between qpos and a geom's world axis (hb_kinematics.hpp geom_world_pose / quat_zaxis, hb_kcommon.hpp
     qnormalize): a body's position is copied and the geoms sit at the body's origin, so only the quaternion rounds.  Each component is
@@ -23,19 +23,18 @@ The worst measured / bound per pair type is printed, and appended to the file HB
 holds the MI355X figures).  A ratio above 1 is a failure.
 
 Rows without contact records (the lean launch of the classic families; the staged step, narrow_prim 1 and 0): counts() under the same
-rule, the state after the step within test_gpu_kernel_matrix.BOUNDS of the oracle's step, the two narrow_prim settings bit for bit.
+rule, the state after the step within bounds.BOUNDS of the oracle's step, the two narrow_prim settings bit for bit.
 """
 import collections
-import os
 
 import numpy as np
 import pytest
 
+from bounds import BOUNDS, CONVEX_TOL as TOL
 from kernel_models import kernel_table
 from oracle_lib import load_state
-from test_gpu_convex import TOL
-from test_gpu_kernel_matrix import BOUNDS
-from test_pair_cases_cpu import envelope, reference, state_of
+from pair_cases import held_to, launch, reference, state_of
+from step_lib import report
 
 pytestmark = pytest.mark.gpu
 
@@ -62,41 +61,9 @@ ROWS = [("pgs",             "pgs",        {},              True,  "hb_step_kerne
         ("newton_cd6-staged", "newton_cd6", "narrow_prim", False, "hb_step_newton_gen28_kernel")]
 
 
-def _launch(hbmod, gpu, ref, knobs, diag):
-    m, cases = ref["model"], ref["cases"]
-    o = ref["oracle"]
-    st = np.stack([state_of(o, c["qpos"]) for c in cases])
-    b = hbmod.Batch(m, len(cases), gpu)
-    b.tune(**knobs)
-    b.diag_enable(diag)
-    b.set_state(hbmod.STATE_INTEGRATION, st)
-    b.step(np.zeros((len(cases), m.nu), dtype=np.float32))
-    out = dict(kernel=b.last_kernel(), counts=b.counts(), status=b.status(), state=b.get_state(hbmod.STATE_INTEGRATION), qpos=b.qpos.astype(np.float64), qvel=b.qvel.astype(np.float64),
-               con=b.contacts().astype(np.float64) if diag else None)
-    b.close()
-    return out
-
-
-def _held_to(ref, i, ncon, nefc, bad):
-    """the oracle evaluation case i's device counts are held to and its envelope; None, and an entry in bad, if the counts match none"""
-    c = ref["cases"][i]
-    got = envelope(ref, i, ncon)
-    if got is None:
-        bad.append((c["name"], "contact count", ncon, "oracle", sorted({e["ncon"] for e in ref["evals"][i]})))
-    elif nefc != got[0]["nefc"]:
-        bad.append((c["name"], "nefc", nefc, "oracle", got[0]["nefc"]))
-    else:
-        return got
-    return None
-
-
 def _report(label, worst):
     lines = ["%-18s %-4s worst measured / bound: dist %.3f pos %.3f normal %.3f   (%d contacts)" % ((label, k) + tuple(w[:3]) + (int(w[3]),)) for k, w in sorted(worst.items())]
-    print("\n" + "\n".join(lines))
-    out = os.environ.get("HB_PAIR_PARITY_OUT")
-    if out:
-        with open(out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    report(lines, "HB_PAIR_PARITY_OUT", lead="\n")
 
 
 def _check_contacts(ref, got, label):
@@ -104,7 +71,7 @@ def _check_contacts(ref, got, label):
     worst = collections.defaultdict(lambda: np.zeros(4))
     bad = []
     for i, c in enumerate(ref["cases"]):
-        held = _held_to(ref, i, int(nc[i]), int(ne[i]), bad)
+        held = held_to(ref, i, int(nc[i]), int(ne[i]), bad, "oracle")
         if held is None:
             continue
         ev, env = held
@@ -132,7 +99,7 @@ def _check_state(ref, got, label):
     wq = wv = 0.0
     bad = []
     for i, c in enumerate(ref["cases"]):
-        held = _held_to(ref, i, int(nc[i]), int(ne[i]), bad)
+        held = held_to(ref, i, int(nc[i]), int(ne[i]), bad, "oracle")
         if held is None:
             continue
         load_state(o, state_of(o, held[0]["qpos"]), np.zeros(o.nu))
@@ -153,14 +120,14 @@ def test_narrow_pairs(hbmod, gpu, tmp_path_factory, row):
     ref = reference(hbmod, scene, tmp_path_factory.mktemp("pairs"))
     kernel = kernel or _big_newton_kernel(ref["model"].nv)
     if knobs == "narrow_prim":
-        got = [_launch(hbmod, gpu, ref, {"narrow_prim": prim}, False) for prim in (1, 0)]
+        got = [launch(hbmod, gpu, ref, {"narrow_prim": prim}, False) for prim in (1, 0)]
         for g in got:
             assert g["kernel"] == kernel, (label, g["kernel"], kernel)
         assert np.array_equal(got[0]["state"], got[1]["state"]) and np.array_equal(got[0]["status"], got[1]["status"]), label
         assert all(np.array_equal(a, b) for a, b in zip(got[0]["counts"], got[1]["counts"])), label
         got = got[0]
     else:
-        got = _launch(hbmod, gpu, ref, knobs, diag)
+        got = launch(hbmod, gpu, ref, knobs, diag)
         assert got["kernel"] == kernel, (label, got["kernel"], kernel)
     assert not got["status"].any(), (label, got["status"])
     assert got["counts"][0].max() == 2 and (got["counts"][0] == 0).sum() >= 10

@@ -14,7 +14,7 @@ import os
 import numpy as np
 import pytest
 
-from oracle_lib import GOLDEN, HUMANOID_HBM, Oracle
+from oracle_lib import GOLDEN, HUMANOID_HBM, Oracle, MODELS_DIR as MODELS
 
 pytestmark = pytest.mark.gpu
 SOL_NEWTON = 2
@@ -104,7 +104,6 @@ def test_free_running_tracks_oracle_through_contacts(hbmod, newton_model, gpu):
     assert worst <= 5e-4, worst
 
 
-MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models")
 
 
 @pytest.mark.parametrize("name,steps", [("ball_plane", 400), ("capsules", 300), ("chain", 300), ("pendulum_limit", 500), ("maxsize", 600)])

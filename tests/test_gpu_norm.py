@@ -19,31 +19,27 @@ Bounds (nothing here is tuned; u = 2^-53, v = 2^-24):
    steps here): 2 (n + 8) u times the sum of the magnitudes.
 HB_NORM_PARITY_OUT=<file> collects the worst values (profiles/norm_parity.txt)."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import actor_ref as ar
+import gae_lib as tg
 import gae_ref as gr
 import norm_ref as nr
-from oracle_lib import HUMANOID_HBM  # noqa: F401  (the model of the humanoid_model fixture)
+from norm_lib import Tracker, ratio as _ratio
+from oracle_lib import HUMANOID_HBM, TEAM_PLANE_HBM  # noqa: F401  (the model of the humanoid_model fixture)
+from step_lib import report
 
 pytestmark = pytest.mark.gpu
 
 SEED, T = 2024, 8
-V32 = 2.0 ** -24
-TEAM_PLANE_HBM = os.path.join(os.path.dirname(HUMANOID_HBM), "team_robot_plane.hbm")
 CFG = dict(norm_obs=True, norm_reward=True, training=True, clip_obs=1.25, clip_reward=2.0, gamma=0.99, epsilon=1e-8)
 K_STEPS = 5
 
 
 def _report(line):
-    print("\n  " + line)
-    out = os.environ.get("HB_NORM_PARITY_OUT")
-    if out:
-        with open(out, "a") as f:
-            f.write(line + "\n")
+    report(line, "HB_NORM_PARITY_OUT")
 
 
 class Dev:
@@ -107,85 +103,6 @@ def _synthetic(n, nobs):
     d = dict(obs=obs, rew=rew, term=term.astype(np.uint8), trunc=trunc.astype(np.uint8), tobs=tobs, done=done)
     _data[(n, nobs)] = d
     return d
-
-
-class Tracker:
-    """the reference and the bounds of the module docstring, advanced together"""
-
-    def __init__(self, n, nobs, **cfg):
-        self.ref = nr.NormRef(n, nobs, **cfg)
-        self.eo, self.er = nr.ErrorBound((nobs,)), nr.ErrorBound()
-        self.k, self.ret_max, self.tot_mag, self.count_adds = 0, 0.0, np.zeros(4), 0
-
-    def _obs_update(self, obs):
-        before = nr.RunningMeanStd((self.ref.nobs,))
-        before.mean, before.var, before.count = self.ref.obs_rms.mean.copy(), self.ref.obs_rms.var.copy(), self.ref.obs_rms.count
-        return before
-
-    def reset(self, obs):
-        upd = self.ref.training and self.ref.norm_obs
-        before = self._obs_update(obs)
-        out = self.ref.reset(obs)
-        if upd:
-            self.eo.update(before, self.ref.obs_rms, obs)
-            self.count_adds += (self.ref.n_env + 63) // 64 + 1
-        return out
-
-    def step(self, obs, rew, term, trunc, tobs=None):
-        ref = self.ref
-        before = self._obs_update(obs)
-        rb = nr.RunningMeanStd()
-        rb.mean, rb.var, rb.count = ref.ret_rms.mean, ref.ret_rms.var, ref.ret_rms.count
-        ret_new = ref.ret * ref.gamma + np.asarray(rew, np.float64)
-        out = ref.step(obs, rew, term, trunc, tobs)
-        self.k += 1
-        if ref.training:
-            self.count_adds += (ref.n_env + 63) // 64 + 1
-            if ref.norm_obs:
-                self.eo.update(before, ref.obs_rms, obs)
-            self.ret_max = max(self.ret_max, float(np.abs(ret_new).max()))
-            self.er.update(rb, ref.ret_rms, ret_new, x_err=2 * self.k * nr.U64 * self.ret_max)
-        done = np.asarray(term, bool) | np.asarray(trunc, bool)
-        er = out["ep_return"].astype(np.float64)[done]
-        self.tot_mag += [0.0, np.abs(er).sum(), (er * er).sum(), 0.0]
-        return out
-
-    def dz_obs(self, x):
-        """the bound on |out_dev - out_ref| for rows x [.., nobs] normalised with the CURRENT statistics"""
-        ref = self.ref
-        if not ref.norm_obs:
-            return np.zeros(np.shape(x))
-        x = np.asarray(x, np.float64)
-        inv = 1.0 / np.sqrt(ref.obs_rms.var + ref.epsilon)
-        z = (x - ref.obs_rms.mean) * inv
-        dz = np.abs(z) * (2 * self.eo.var) / (2 * (ref.obs_rms.var + ref.epsilon)) + 2 * self.eo.mean * inv + 6 * nr.U64 * np.abs(z)
-        return 2 * V32 * np.minimum(np.abs(z), ref.clip_obs) + dz
-
-    def dz_rew(self, r):
-        ref = self.ref
-        if not ref.norm_reward:
-            return np.zeros(np.shape(r))
-        z = np.asarray(r, np.float64) / np.sqrt(ref.ret_rms.var + ref.epsilon)
-        dz = np.abs(z) * (2 * self.er.var) / (2 * (ref.ret_rms.var + ref.epsilon)) + 6 * nr.U64 * np.abs(z)
-        return 2 * V32 * np.minimum(np.abs(z), ref.clip_reward) + dz
-
-    def stats_ratio(self, rec):
-        """largest |device - reference| / bound over the record's means and variances (counts must be equal)"""
-        n, ref = self.ref.nobs, self.ref.record()
-        for i in (2 * n, 2 * n + 3):
-            assert abs(rec[i] - ref[i]) <= self.count_adds * nr.U64 * ref[i], "counts"
-        tiny = 1e-300
-        r = [np.abs(rec[:n] - ref[:n]) / (2 * self.eo.mean + tiny), np.abs(rec[n:2 * n] - ref[n:2 * n]) / (2 * self.eo.var + tiny),
-             [abs(rec[2 * n + 1] - ref[2 * n + 1]) / (2 * self.er.mean + tiny)], [abs(rec[2 * n + 2] - ref[2 * n + 2]) / (2 * self.er.var + tiny)]]
-        return float(max(np.max(x) for x in r))
-
-
-def _ratio(got, want, bound):
-    """largest |got - want| / bound; where the bound is 0 the values must be equal"""
-    got, want, bound = np.asarray(got, np.float64), np.asarray(want, np.float64), np.asarray(bound, np.float64)
-    err = np.abs(got - want)
-    assert np.all(err[bound == 0] == 0)
-    return float((err[bound > 0] / bound[bound > 0]).max()) if (bound > 0).any() else 0.0
 
 
 def _primitive(hbmod, model, gpu, n, inplace):
@@ -533,13 +450,12 @@ def test_composition_with_the_ppo_buffer(hbmod, humanoid_model, gpu):
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("torch sees no GPU")
-    import test_gpu_gae as tg
     m, n = humanoid_model, 37
     env = hbmod.VecEnv(m, n, gpu, realism=True, domain_randomization=True, seed=7, reward_kind=1, max_time=0.02, normalize={})
     asz = [tg.NOBS, 40, 24, tg.NU]
     aw, ab = ar.make_actor(asz, seed=11, scale=0.35)
-    env.actor_set(asz, aw, ab, head="gaussian", log_std=tg._log_std(), seed=SEED)
-    sizes, ws, bs = tg._critic("small")
+    env.actor_set(asz, aw, ab, head="gaussian", log_std=tg.log_std(), seed=SEED)
+    sizes, ws, bs = tg.critic("small")
     env.critic_set(sizes, ws, bs)
     o0 = env.reset()
     tk = Tracker(n, m.nobs)
@@ -559,9 +475,9 @@ def test_composition_with_the_ppo_buffer(hbmod, humanoid_model, gpu):
     tv64 = np.zeros((T, n))
     tv64[boot] = gr.values(out["terminal_obs"][boot], ws, bs)
     e_v = float((np.abs(out["value"] - v64) / np.maximum(1.0, np.abs(v64))).max())
-    hand = tg._run(env.batch, T, tp, tapes=tuple(tp))
-    _, _, b_adv, b_ret = tg._scan_bounds(tp, hand["value"], hand["terminal_value"], tg.GAMMA, tg.LAM)
-    adv64, ret64, _, _ = tg._scan_bounds(tp, v64, tv64, tg.GAMMA, tg.LAM)
+    hand = tg.run(env.batch, T, tp, tapes=tuple(tp))
+    _, _, b_adv, b_ret = tg.scan_bounds(tp, hand["value"], hand["terminal_value"], tg.GAMMA, tg.LAM)
+    adv64, ret64, _, _ = tg.scan_bounds(tp, v64, tv64, tg.GAMMA, tg.LAM)
     eps_v = tg.VALUE_TOL * max(1.0, float(np.abs(v64).max()), float(np.abs(tv64).max()))
     b_adv64 = (1.0 + 2.0 * tg.GAMMA) * eps_v / (1.0 - tg.GAMMA * tg.LAM) + b_adv
     e_adv, e_ret = float(np.abs(out["advantage"] - adv64).max()), float(np.abs(out["returns"] - ret64).max())

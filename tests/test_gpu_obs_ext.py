@@ -12,8 +12,9 @@ Bounds - none of them new:
   fp64     the scan against obs_ext_ref over tests/ray_ref.py's cast: tests/test_gpu_ray.py's BOUND = 1e-5 max(1, dist) times scan_scale,
            on the rays the reference calls robust;
   mean     tests/test_gpu_collect.py's MEAN_TOL = 5e-5 max(1, |ref|) against mlp_ref in fp64;
-  norm     tests/test_gpu_norm.py's Tracker (its derived bounds, ratio <= 1);
-  learners tests/test_gpu_ppo.py's _check_case and tests/test_gpu_sac.py's _check_step with their own bounds, on the extended tapes.
+  norm     tests/test_gpu_norm.py's Tracker (norm_lib: its derived bounds, ratio <= 1);
+  learners tests/test_gpu_ppo.py's check_case and tests/test_gpu_sac.py's check_step (ppo_lib, sac_lib) with their own bounds, on the
+           extended tapes.
 """
 import ctypes
 
@@ -24,12 +25,12 @@ import mlp_ref as ml
 import obs_ext_ref
 import ray_cases
 import ray_ref
+from bounds import MEAN_TOL  # tests/test_gpu_collect.py's
+from bounds import RAY_BOUND as BOUND  # tests/test_gpu_ray.py's
 from oracle_lib import Oracle
 
 pytestmark = pytest.mark.gpu
 
-BOUND = 1e-5     # tests/test_gpu_ray.py
-MEAN_TOL = 5e-5  # tests/test_gpu_collect.py
 NOBS, NU = 48, 21
 Z0, CUTOFF = 1.0, 4.0
 HS = dict(offset=1.0, scale=2.0, clip=(-4.0, 5.0))
@@ -230,7 +231,7 @@ def test_collection(hbmod, gpu):
 
 def test_normaliser(hbmod, gpu, tmp_path):
     pytest.importorskip("torch")
-    import test_gpu_norm as tn
+    import norm_lib as tn
     n = 24
     a = _env(hbmod, gpu, n, "3x2", domain_randomization=True, max_time=0.02, normalize={})
     t = _ext_actor(a.nobs)
@@ -239,13 +240,13 @@ def test_normaliser(hbmod, gpu, tmp_path):
     raw0 = a.get_original_obs()
     assert o0.shape == raw0.shape == (n, a.nobs)
     tk = tn.Tracker(n, a.nobs)
-    worst = dict(obs=tn._ratio(o0, tk.reset(raw0), tk.dz_obs(raw0)), rew=0.0)
+    worst = dict(obs=tn.ratio(o0, tk.reset(raw0), tk.dz_obs(raw0)), rew=0.0)
     out = a.collect(T, terminal_obs=True, raw=True)
     assert out["raw_obs"].shape == (T, n, a.nobs) and (out["terminated"] | out["truncated"]).any()
     for k in range(T):
         want = tk.step(out["raw_obs"][k], out["raw_reward"][k], out["terminated"][k], out["truncated"][k])
-        worst["obs"] = max(worst["obs"], tn._ratio(out["obs"][k + 1], want["obs"], tk.dz_obs(out["raw_obs"][k])))
-        worst["rew"] = max(worst["rew"], tn._ratio(out["reward"][k], want["reward"], tk.dz_rew(out["raw_reward"][k])))
+        worst["obs"] = max(worst["obs"], tn.ratio(out["obs"][k + 1], want["obs"], tk.dz_obs(out["raw_obs"][k])))
+        worst["rew"] = max(worst["rew"], tn.ratio(out["reward"][k], want["reward"], tk.dz_rew(out["raw_reward"][k])))
     rec = a.batch.norm_stats()
     stats = tk.stats_ratio(rec)
     print("\n  normaliser over %d columns: statistics / bound %.3g, obs / bound %.3g, reward / bound %.3g" % (a.nobs, stats, worst["obs"], worst["rew"]))
@@ -271,7 +272,7 @@ def test_normaliser(hbmod, gpu, tmp_path):
 def test_ppo_learner(hbmod, gpu, monkeypatch):
     torch = pytest.importorskip("torch")
     import ppo_ref as pr
-    import test_gpu_ppo as tp
+    import ppo_lib as tp
     n = 16
     env = _env(hbmod, gpu, n, "3x2", domain_randomization=True, max_time=0.02)
     asz, csz = [env.nobs, 16, NU], [env.nobs, 16, 1]
@@ -280,7 +281,7 @@ def test_ppo_learner(hbmod, gpu, monkeypatch):
     t = pr.split(flat.astype(np.float32), asz, csz, NU)
     env.actor_set(asz, [t["actor.w0"], t["actor.w1"]], [t["actor.b0"], t["actor.b1"]], head="gaussian", log_std=t["log_std"])
     env.critic_set(csz, [t["critic.w0"], t["critic.w1"]], [t["critic.b0"], t["critic.b1"]])
-    cfg = tp._cfg(ent_coef=0.01)
+    cfg = tp.cfg(ent_coef=0.01)
     env.learner(**cfg)
     env.reset()
     buf = env.collect_torch(T, gae=dict(gamma=0.99, lam=0.95))
@@ -293,8 +294,8 @@ def test_ppo_learner(hbmod, gpu, monkeypatch):
     flat64 = b.learner_params().astype(np.float64)
     assert np.array_equal(flat64, flat.astype(np.float32).astype(np.float64))
     worst = dict(stat=0.0, head=0.0, floor=0.0, k=0.0, ratio=0.0, rel=0.0)
-    tp._check_case(b, "obs_ext", flat64, rows, "mb50_index", np.random.default_rng(2).permutation(R)[:50], 0, 50, cfg, worst)
-    tp._check_case(b, "obs_ext", flat64, rows, "all_rows", None, 0, R, cfg, worst)
+    tp.check_case(b, "obs_ext", flat64, rows, "mb50_index", np.random.default_rng(2).permutation(R)[:50], 0, 50, cfg, worst)
+    tp.check_case(b, "obs_ext", flat64, rows, "all_rows", None, 0, R, cfg, worst)
     print("\n  ppo on %d-wide rows: statistics %.3f, head gradients %.3f of their bounds; back-propagated: measured / k %.3f" % (env.nobs, worst["stat"], worst["head"], worst["rel"]))
     log = env.ppo_update(buf, n_epochs=1, batch_size=48)
     after = b.learner_params()
@@ -306,7 +307,7 @@ def test_ppo_learner(hbmod, gpu, monkeypatch):
 def test_sac_learner(hbmod, gpu, monkeypatch):
     torch = pytest.importorskip("torch")
     import sac_ref as sr
-    import test_gpu_sac as ts
+    import sac_lib as ts
     n = 16
     env = _env(hbmod, gpu, n, "3x2", domain_randomization=True, max_time=0.02)
     asz, qsz = [env.nobs, 16, 2 * NU], [env.nobs + NU, 16, 1]
@@ -316,8 +317,8 @@ def test_sac_learner(hbmod, gpu, monkeypatch):
     b = env.batch
     with pytest.raises(hbmod.HbError):  # (sized by the env's row, not the model's)
         b.q_set(0, [NOBS + NU, 16, 1], [np.zeros((NOBS + NU, 16), np.float32), np.zeros((16, 1), np.float32)], [np.zeros(16, np.float32), np.zeros(1, np.float32)])
-    ts._install(b, "obs_ext", pb["flat"])
-    cfg = ts._cfg(lr_actor=1e-3, lr_critic=1e-3, lr_ent=1e-3, ent_coef_init=0.3)
+    ts.install(b, "obs_ext", pb["flat"])
+    cfg = ts.cfg(lr_actor=1e-3, lr_critic=1e-3, lr_ent=1e-3, ent_coef_init=0.3)
     env.sac_learner(**cfg)
     st = b.sac_state()
     st["params"], st["targets"] = pb["flat"].astype(np.float32), pb["targets"].astype(np.float32)
@@ -335,9 +336,9 @@ def test_sac_learner(hbmod, gpu, monkeypatch):
     assert done.any() and np.array_equal(rows["next_obs"][done], tobs[done]) and rows["next_obs"][done][:, NOBS:NOBS + NU].any()
     rng = np.random.default_rng(6)
     pb2 = dict(rows=rows, eps_pi=rng.normal(size=(R, NU)).astype(np.float32), eps_next=rng.normal(size=(R, NU)).astype(np.float32))
-    worst = ts._new_worst()
-    ts._check_step(b, "obs_ext", pb2, rng.permutation(R)[:40], cfg, worst, "mb40_index")
-    print("\n  " + ts._line("sac step on %d-wide rows" % env.nobs, worst))
+    worst = ts.new_worst()
+    ts.check_step(b, "obs_ext", pb2, rng.permutation(R)[:40], cfg, worst, "mb40_index")
+    print("\n  " + ts.line("sac step on %d-wide rows" % env.nobs, worst))
     before = b.sac_state()["params"].copy()
     log = env.sac_update(replay, 1, batch_size=32)
     after = b.sac_state()["params"]

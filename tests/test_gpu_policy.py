@@ -149,7 +149,8 @@ def test_refused_install_leaves_policy_intact(hbmod, humanoid_model, gpu):
 
 def _fixture_policy():
     import os
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "policy_mlp_seed0.npz"))
+    from oracle_lib import GOLDEN
+    g = np.load(os.path.join(GOLDEN, "policy_mlp_seed0.npz"))
     return [g["w0"], g["w1"], g["w2"]], [g["b0"], g["b1"], g["b2"]], g
 
 

@@ -4,7 +4,7 @@ The ray sets are tests/ray_cases.py's; tests/test_ray_cpu.py holds, from the ref
 lines, vertices and cuts none of them is fragile.  For every robust ray the device must name the reference's geom and give its distance
 within BOUND; for a planted ray one of the reference's two candidates.
 
-BOUND is the project's contact-geometry bound, test_gpu_kernel_matrix.BOUNDS["pos"] = 1e-5 relative to max(1, dist_ref).  Measured on MI355X
+BOUND (bounds.RAY_BOUND) is the project's contact-geometry bound, bounds.BOUNDS["pos"] = 1e-5 relative to max(1, dist_ref).  Measured on MI355X
 by tools/gpu_ray_report.py (profiles/ray_parity.txt; these sets at 30 states of the chain's rollout, 8 of the robot's, 8 envs' own terrain):
 worst 2.141e-06 (a floor-plane hit 5 m away from a tumbled base frame), medians below 7e-08 - under the target, so the target is the bound
 (it would have become four times the measured worst case otherwise).
@@ -16,11 +16,12 @@ import pytest
 
 import ray_cases
 import ray_ref
+from bounds import RAY_BOUND as BOUND
 from oracle_lib import Oracle
+from step_lib import snapshot
 
 pytestmark = pytest.mark.gpu
 
-BOUND = 1e-5  # = test_gpu_kernel_matrix.BOUNDS["pos"]; profiles/ray_parity.txt: worst measured 2.141e-06, below it
 KERNELS = ("hb_ray_kernel", "hb_ray_lds_kernel")
 
 
@@ -133,10 +134,6 @@ def test_team_robot(hbmod, gpu):
     b.close()
 
 
-def _snapshot(hbmod, b):
-    return [b.get_state(hbmod.STATE_INTEGRATION), b.status()] + list(b.counts()) + [np.array(b.step_launches())]
-
-
 def test_nothing_is_written(hbmod, gpu):
     """state, status, counts, launch count and the next step are those of a twin that never cast a ray; the device form is the host form"""
     c = ray_cases.case("prim_body")
@@ -148,10 +145,10 @@ def test_nothing_is_written(hbmod, gpu):
         b.set_state(hbmod.STATE_INTEGRATION, states)
         b.step(ctrl)
     a.ray_configure(c["pnt"], c["vec"], **_spec(c))
-    before = _snapshot(hbmod, a)
+    before = snapshot(hbmod, a)
     dist, gid = a.rays()
     assert a.last_kernel() in KERNELS
-    for x, y in zip(before, _snapshot(hbmod, a)):
+    for x, y in zip(before, snapshot(hbmod, a)):
         assert np.array_equal(x, y)
     dd, dg = a.dev_alloc(dist.nbytes), a.dev_alloc(gid.nbytes)
     a.rays_dev(dd, dg)
@@ -161,7 +158,7 @@ def test_nothing_is_written(hbmod, gpu):
     a.rays_dev(None, dg)
     a.sync()
     assert np.array_equal(a.from_dev(dd, dist.shape), dist) and np.array_equal(a.from_dev(dg, gid.shape, np.int32), gid)
-    for x, y in zip(before, _snapshot(hbmod, a)):
+    for x, y in zip(before, snapshot(hbmod, a)):
         assert np.array_equal(x, y)
     a.dev_free(dd); a.dev_free(dg)
     for b in (a, twin):

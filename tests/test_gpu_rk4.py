@@ -1,12 +1,12 @@
 """The RK4 integrator (mjINT_RK4; hb_step.hip: step_body's INTEG, the INTEG rows of HB_KERNELS) on the GPU, against the fp64 reference of
 tests/rk4_ref.py (the RK4 recurrence restated over the oracle's mj_forward).
 
-KERNELS names every RK4 kernel and the model that must run it (Batch.last_kernel): the benchmark humanoid under PGS/50 and Newton/100,
+KERNELS (step_lib.RK4_KERNELS) names every RK4 kernel and the model that must run it (Batch.last_kernel): the benchmark humanoid under PGS/50 and Newton/100,
 and the capsule chains of tests/kernel_models.py at 28 and 32 dofs with `integrator="RK4"` in their <option>.
 
 One-step bounds (BOUNDS): the project's rule is at most 3 x the measured maximum, against the fp64 reference, and for these kernels no
 more than twice the Euler step's bound of the same quantity (tests/test_gpu_parity.py: qpos 4e-5 relative, qvel / qacc / force
-4e-4 * max(1, max|.|)).  The measurement is quoted at BOUNDS (profiles/rk4_parity_report.txt, from tools/gpu_rk4_parity_report.py).
+4e-4 * max(1, max|.|)).  The measurement is quoted at bounds.RK4_BOUNDS (profiles/rk4_parity_report.txt, from tools/gpu_rk4_parity_report.py).
 """
 import os
 
@@ -14,22 +14,15 @@ import numpy as np
 import pytest
 
 import rk4_ref
+import step_lib
+from bounds import RK4_BOUNDS as BOUNDS
 from kernel_models import CNSTR_CONTACT_FRICTIONLESS, CNSTR_CONTACT_PYRAMIDAL, CNSTR_LIMIT_JOINT, chain_xml, oracle_for, rollout_states
-from oracle_lib import GOLDEN, HUMANOID_HBM, ROOT, Oracle
+from oracle_lib import ASSETS, HUMANOID_HBM, Oracle, golden_states
+from step_lib import RK4_KERNELS as KERNELS, T, everything
 
 pytestmark = pytest.mark.gpu
 
-ASSETS = os.path.join(ROOT, "humanoid_mujoco_amd", "assets")
-KERNELS = {"humanoid27_pgs": "hb_rk4_kernel", "humanoid27_newton": "hb_rk4_newton28_kernel",
-           "chain28_cd3_pgs": "hb_rk4_kernel", "chain32_cd3_pgs": "hb_rk4_32_kernel",
-           "chain28_cd1_newton": "hb_rk4_newton28_kernel", "chain32_cd1_newton": "hb_rk4_newton32_kernel"}
-CHAINS = {"chain28_cd3_pgs": (28, True, "plane", 3, "PGS"), "chain32_cd3_pgs": (32, True, "plane", 3, "PGS"),
-          "chain28_cd1_newton": (28, True, "plane", 1, "Newton"), "chain32_cd1_newton": (32, True, "plane", 1, "Newton")}
-# Measured on MI355X against the fp64 reference, maximum over the six models (median of the worst model in brackets):
-#   qpos 2.27e-6 (4.96e-8)   qvel 5.07e-5 (5.24e-7)   qacc = qacc_warmstart' 8.09e-5 (4.39e-6)   efc_force 9.63e-5 (3.48e-6)   time 1.14e-7
-# - every one below the Euler step's bound itself (4e-5 / 4e-4), none near twice it.  Each bound is at most 3 x its measured maximum.
-BOUNDS = dict(qpos=6e-6, qvel=1.5e-4, qacc=2.4e-4, warm=2.4e-4, force=2.8e-4, time=3e-7)
-T = 5
+CHAINS = {name: step_lib.CHAINS[name] for name in ("chain28_cd3_pgs", "chain32_cd3_pgs", "chain28_cd1_newton", "chain32_cd1_newton")}
 
 
 def _humanoid(hbmod, solver, iterations, integrator=1, **opt):
@@ -41,9 +34,8 @@ def _humanoid(hbmod, solver, iterations, integrator=1, **opt):
 
 
 def _golden_states():
-    g = np.load(os.path.join(GOLDEN, "humanoid27_steps.npz"))
-    st = np.concatenate([g["time"][:, None], g["qpos"], g["qvel"], g["warm"]], axis=1)
-    return st.astype(np.float32).astype(np.float64), g["ctrl"].astype(np.float32)
+    st, ctrl, _ = golden_states()
+    return st.astype(np.float32).astype(np.float64), ctrl.astype(np.float32)
 
 
 def _rk4_chain(hbmod, name, tmp_path):
@@ -95,10 +87,6 @@ def test_one_step_parity_of_the_other_kernels_and_sizes(hbmod, gpu, tmp_path, na
     assert con >= 10 and lim >= 10, (name, con, lim)
 
 
-def _everything(hbmod, b):
-    return (b.get_state(hbmod.STATE_INTEGRATION),) + tuple(b.counts()) + (b.status(),)
-
-
 def test_launch_shapes_are_the_same_arithmetic(hbmod, gpu):
     """T steps as one rollout, as T step calls, as T folded step_dev calls on a pipelined batch, each with the diagnostic outputs on
     and off: one instantiation serves them all, so state, counts and status are bit-identical"""
@@ -127,7 +115,7 @@ def test_launch_shapes_are_the_same_arithmetic(hbmod, gpu):
                 b.sync()
                 b.dev_free(p)
             assert b.last_kernel() == "hb_rk4_kernel", (shape, diag, b.last_kernel())
-            got[shape, diag] = _everything(hbmod, b)
+            got[shape, diag] = everything(hbmod, b)
             b.close()
     ref = got["rollout", False]
     assert ref[2].max() > 0 and not ref[4].any()

@@ -5,23 +5,19 @@ env and returns the new episode's first observation; "TimeLimit.truncated" = tru
 
 Reference for the terminal observation: a second VecEnv with auto_reset = 0 stepped with the same actions - its observation of the
 same step IS the un-reset one (bit for bit), and tests/env_ref.py restates it from the state in numpy fp64."""
-import os
-
 import numpy as np
 import pytest
 
-from env_ref import obs_from_state
-from oracle_lib import HUMANOID_HBM, ROOT
+from env_ref import obs_from_state, team_obs
+from oracle_lib import HUMANOID_HBM, TEAM_HBM
 
 pytestmark = pytest.mark.gpu
-TEAM_HBM = os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "team_robot.hbm")
 
 
 def _ref_obs(m, team, qpos, qvel):
     if not team:
         return obs_from_state(qpos, qvel)[0]
-    from test_gpu_team_env import _team_obs
-    return _team_obs(m, qpos, qvel)[0]
+    return team_obs(m, qpos, qvel)[0]
 
 
 @pytest.mark.parametrize("team", [False, True])

@@ -6,12 +6,10 @@ import os
 import numpy as np
 import pytest
 
-from oracle_lib import ROOT
-from test_oracle_convex import BALL_MESH, CUBE_MESH, _hfield_xml
+from convex_models import BALL_MESH, CUBE_MESH, hfield_xml
+from oracle_lib import HFIELD_HBM as TERRAIN_HBM, TEAM_HBM
 
 pytestmark = pytest.mark.gpu
-TEAM_HBM = os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "team_robot.hbm")
-TERRAIN_HBM = os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "humanoid27_hfield.hbm")
 
 
 TUNE = {"HB_STAGED": "staged", "HB_FASTPASS": "fastpass"}
@@ -119,7 +117,7 @@ def test_fast_pass_defers_what_it_cannot_hold(hbmod, gpu, tmp_path):
             '<body pos="0.4 -0.4 0.5" euler="20 40 0"><freejoint/><geom type="capsule" size="0.05 0.12" condim="3"/></body>'
             '<body pos="0.1 0.5 0.5" euler="10 20 30"><freejoint/><inertial pos="0 0 0" mass="0.5" diaginertia="0.001 0.001 0.001"/><geom type="mesh" mesh="cube" condim="4"/></body>'
             '<body pos="0.12 0.52 0.62"><freejoint/><inertial pos="0 0 0" mass="0.3" diaginertia="0.0005 0.0005 0.0005"/><geom type="mesh" mesh="ball" condim="6" friction="0.7 0.02 0.01"/></body>')
-    m = hbmod.Model.from_xml_string(_hfield_xml(elev, body, nrow=6, ncol=6, size="1 1 0.3 0.2", extra=CUBE_MESH + BALL_MESH))
+    m = hbmod.Model.from_xml_string(hfield_xml(elev, body, nrow=6, ncol=6, size="1 1 0.3 0.2", extra=CUBE_MESH + BALL_MESH))
     m.set_opt(solver=2, iterations=100)
     n = 256
     # states along the fall and the landing: env e has run 3 e steps

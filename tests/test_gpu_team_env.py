@@ -2,28 +2,16 @@
 world.xml): obs[30] = [q_j(12), qd_j(12), qvel[3:6], R(q_root)' (0, 0, -1)] with the joints in JOINT_NAMES order
 (simulation_parameters.py:84-103), action[12] in the same order, standupReward with the reference's constants, the
 standup reset (lying on the floor) with its perturbations, kp / force-range randomisation on the twelve motors."""
-import os
-
 import numpy as np
 import pytest
 
 import dr_ref
-from env_ref import obs_from_state, standup_reward
-from oracle_lib import ROOT, Oracle, load_state
-from test_gpu_kernel_matrix import BOUNDS, _state_vs_oracle
+from bounds import BOUNDS
+from env_ref import JOINT_NAMES, standup_reward, team_obs
+from oracle_lib import TEAM_HBM, Oracle, load_state
+from step_lib import state_vs_oracle
 
 pytestmark = pytest.mark.gpu
-TEAM_HBM = os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "team_robot.hbm")
-JOINT_NAMES = ["right_shoulder_pitch", "right_shoulder_roll", "right_elbow", "left_shoulder_pitch", "left_shoulder_roll", "left_elbow",
-               "left_hip_roll", "left_hip_pitch", "left_knee", "right_hip_roll", "right_hip_pitch", "right_knee"]
-
-
-def _team_obs(m, qpos, qvel):
-    jid = [m.name2id("joint", n) for n in JOINT_NAMES]
-    qadr = m.array("jnt_qposadr").astype(int)[jid]
-    dadr = m.array("jnt_dofadr").astype(int)[jid]
-    _, g = obs_from_state(qpos, qvel)
-    return np.concatenate([qpos[qadr], qvel[dadr], qvel[3:6], g]), dadr
 
 
 def test_team_config_is_the_references(hbmod, gpu):
@@ -58,7 +46,7 @@ def test_team_reset_is_the_standup_reset_with_its_perturbations(hbmod, gpu):
     nc, _, _ = env.batch.counts()
     assert not nc.any()  # CPUEnv.reset starts over while anything is in contact (cpu_env.py:411-414)
     for e in range(0, n, 7):
-        want, _ = _team_obs(m, q[e], st[e, 1 + m.nq:1 + m.nq + m.nv])
+        want, _ = team_obs(m, q[e], st[e, 1 + m.nq:1 + m.nq + m.nv])
         assert np.allclose(obs[e], want, atol=1e-5)
     env.close()
 
@@ -86,7 +74,7 @@ def test_team_step_reward_and_observation_match_the_reference_formula(hbmod, gpu
             o.ctrl[:] = act[e]
             o.forward()
             q1, v1 = st1[e, 1:1 + m.nq], st1[e, 1 + m.nq:1 + m.nq + m.nv]
-            want, dadr = _team_obs(m, q1, v1)
+            want, dadr = team_obs(m, q1, v1)
             assert np.allclose(obs[e], want, atol=1e-5)
             torques = (o.qfrc_smooth + o.qfrc_constraint)[dadr]
             selfcol = any(c["geom1"] > 3 for c in o.contacts())  # geoms 0..3 are the world's (three markers and the floor)
@@ -130,7 +118,7 @@ def test_team_domain_randomisation_sets_the_motor_gains(hbmod, gpu):
         assert np.isfinite(obs).all() and np.isfinite(rew).all() and not (term | trunc).any()
         v1 = b.qvel.astype(np.float64)
         # (counts identical - or, for this mesh-on-height-field model, proved to sit on a rounding fence -, qpos and qvel within BOUNDS)
-        _state_vs_oracle(hbmod, b, o, st, act, True, "team domain randomisation, command %.1f" % level, before=lambda k: dr_ref.apply(o, prm[k], L, base))
+        state_vs_oracle(hbmod, b, o, st, act, True, "team domain randomisation, command %.1f" % level, before=lambda k: dr_ref.apply(o, prm[k], L, base))
         dr_ref.restore(o, base)
         moved = 0
         for e in range(0, n, 8):

@@ -6,9 +6,8 @@ import os
 import numpy as np
 
 from inverse_ref import forward_at, inverse_ref
-from oracle_lib import GOLDEN, Oracle
+from oracle_lib import GOLDEN, Oracle, MODELS_DIR as MODELS
 
-MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models")
 SOL_NEWTON = 2
 HB_EINVAL = -1  # include/hb.h
 

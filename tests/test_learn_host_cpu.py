@@ -5,8 +5,7 @@ that every packed index stays inside its operand and that rows below k0 reach no
 import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOL = os.path.join(ROOT, "build", "hb_learn_check")
+from oracle_lib import HB_LEARN_CHECK as TOOL, ROOT
 
 
 def test_layout_segments_refresh_and_carve():

@@ -10,9 +10,8 @@ import numpy as np
 import pytest
 
 from conftest import REF_HUMANOID_XML
-from oracle_lib import HUMANOID_HBM, Oracle, parse_hbm
+from oracle_lib import HFIELD_HBM, HUMANOID_HBM, Oracle, parse_hbm, MODELS_DIR as MODELS
 
-MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models")
 
 
 def test_humanoid_sizes_and_layout(humanoid_model):
@@ -271,8 +270,7 @@ def test_heightfield_asset_and_config5_model(hbmod, tmp_path):
     assert info["geom_type"][0] == 1 and info["geom_dataid"][0] == 0
     assert set(zip(info["pair_geom1"], info["pair_geom2"])) == {(0, 1), (0, 2), (1, 2)}
     # config-5 model: same humanoid, plane replaced by the 8x8 field of SURVEY.md 8(d), PGS exactly 50 sweeps
-    from oracle_lib import ROOT
-    h = parse_hbm(os.path.join(ROOT, "humanoid_mujoco_amd", "assets", "humanoid27_hfield.hbm"))
+    h = parse_hbm(HFIELD_HBM)
     base = parse_hbm(HUMANOID_HBM)
     assert h["geom_type"][0] == 1 and list(h["hfield_size"]) == [10, 10, 1, 1] and h["tolerance"] == 0 and h["iterations"] == 50
     assert np.array_equal(h["body_mass"], base["body_mass"]) and np.array_equal(h["pair_geom1"], base["pair_geom1"])

@@ -8,9 +8,7 @@ import numpy as np
 
 import obs_ext_ref
 import ray_cases
-from oracle_lib import Oracle
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from oracle_lib import ROOT, Oracle
 
 
 def test_library_exports_the_entry_points(hbmod):

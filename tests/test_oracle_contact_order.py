@@ -6,7 +6,8 @@ profiles/r03_contact_order.txt and DESIGN.md §2)."""
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from oracle_lib import ROOT
+
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 

@@ -11,10 +11,11 @@ import numpy as np
 import pytest
 
 from conftest import REFERENCE
+from convex_models import BALL_MESH, CUBE, CUBE_MESH, PLANE_CUBE_XML, hfield_xml
+from kernel_models import oracle_for
 from oracle_lib import Oracle, mpr
 
 TEAM_XML = os.path.join(REFERENCE, "simulation/assets/world.xml")
-CUBE = np.array([[x, y, z] for x in (-.5, .5) for y in (-.5, .5) for z in (-.5, .5)])
 
 
 def rot(axis, ang):
@@ -192,17 +193,9 @@ def test_team_robot_compiles_with_its_hulls(hbmod):
         assert vnum[k] < 400
 
 
-def _hfield_xml(elev, body, nrow=4, ncol=4, size="2 2 1 0.5", extra=""):
-    return ('<mujoco><option timestep="0.002"/><asset><hfield name="h" nrow="%d" ncol="%d" size="%s" elevation="%s"/>%s</asset>'
-            '<worldbody><geom name="floor" type="hfield" hfield="h" condim="6" friction="1.5"/>%s</worldbody></mujoco>'
-            % (nrow, ncol, size, " ".join("%.17g" % v for v in np.asarray(elev).reshape(-1)), extra, body))
-
-
 def _oracle_from_xml(hbmod, xml, tmp_path, name="m.hbm"):
-    m = hbmod.Model.from_xml_string(xml)
-    p = str(tmp_path / name)
-    m.save(p)
-    return m, Oracle(p)
+    m, _, o = oracle_for(hbmod, xml, tmp_path, name)
+    return m, o
 
 
 def test_sphere_on_tilted_planar_field_equals_sphere_on_plane(hbmod, tmp_path):
@@ -218,7 +211,7 @@ def test_sphere_on_tilted_planar_field_equals_sphere_on_plane(hbmod, tmp_path):
         surf = np.array([x, y, (x + 2) * slope])
         centre = surf + nrm * (radius - pen)
         body = '<body pos="%.17g %.17g %.17g"><freejoint/><geom type="sphere" size="%g" condim="6"/></body>' % (*centre, radius)
-        m, o = _oracle_from_xml(hbmod, _hfield_xml(elev, body), tmp_path)
+        m, o = _oracle_from_xml(hbmod, hfield_xml(elev, body), tmp_path)
         o.reset(); o.forward()
         cons = o.contacts()
         assert len(cons) >= 1
@@ -235,22 +228,9 @@ def test_sphere_on_tilted_planar_field_equals_sphere_on_plane(hbmod, tmp_path):
         assert all(k["dist"] >= c["dist"] - 1e-9 for k in cons)
     # well above the surface: nothing
     body = '<body pos="0.35 0.9 %.17g"><freejoint/><geom type="sphere" size="0.1"/></body>' % ((0.35 + 2) * slope + 0.2)
-    _, o = _oracle_from_xml(hbmod, _hfield_xml(elev, body), tmp_path)
+    _, o = _oracle_from_xml(hbmod, hfield_xml(elev, body), tmp_path)
     o.reset(); o.forward()
     assert o.ncon == 0
-
-
-CUBE_MESH = '<mesh name="cube" vertex="%s"/>' % " ".join("%g" % (0.1 * v) for v in CUBE.reshape(-1))
-
-
-def _ball_points(n=300, r=0.05):
-    k = np.arange(n) + 0.5
-    phi = np.arccos(1 - 2 * k / n)
-    th = np.pi * (1 + 5 ** 0.5) * k
-    return r * np.stack([np.cos(th) * np.sin(phi), np.sin(th) * np.sin(phi), np.cos(phi)], axis=1)
-
-
-BALL_MESH = '<mesh name="ball" vertex="%s"/>' % " ".join("%.9g" % v for v in _ball_points().reshape(-1))
 
 
 def test_resting_hull_carries_its_weight_and_condim6_rows(hbmod, tmp_path):
@@ -259,7 +239,7 @@ def test_resting_hull_carries_its_weight_and_condim6_rows(hbmod, tmp_path):
     the normal components of its contact forces adding up to m g; every condim-6 contact is ten pyramid rows."""
     body = ('<body pos="0.3 0.2 0.06"><freejoint/><inertial pos="0 0 0" mass="0.5" diaginertia="0.001 0.001 0.001"/>'
             '<geom type="mesh" mesh="ball" condim="6" friction="0.6 0.02 0.01"/></body>')
-    m, o = _oracle_from_xml(hbmod, _hfield_xml(np.zeros((4, 4)), body, extra=BALL_MESH), tmp_path)
+    m, o = _oracle_from_xml(hbmod, hfield_xml(np.zeros((4, 4)), body, extra=BALL_MESH), tmp_path)
     o.reset()
     for t in range(1500):
         o.step()
@@ -289,7 +269,7 @@ def test_resting_hull_carries_its_weight_and_condim6_rows(hbmod, tmp_path):
 def test_condim4_has_six_rows(hbmod, tmp_path):
     body = ('<body pos="0 0 0.049"><freejoint/><inertial pos="0 0 0" mass="0.5" diaginertia="0.001 0.001 0.001"/>'
             '<geom type="mesh" mesh="cube" condim="4"/></body>')
-    xml = _hfield_xml(np.zeros((4, 4)), body, extra=CUBE_MESH).replace('condim="6" friction="1.5"', 'condim="3"')
+    xml = hfield_xml(np.zeros((4, 4)), body, extra=CUBE_MESH).replace('condim="6" friction="1.5"', 'condim="3"')
     _, o = _oracle_from_xml(hbmod, xml, tmp_path)
     o.reset(); o.forward()
     assert o.ncon >= 1 and o.nefc == 6 * o.ncon
@@ -308,13 +288,7 @@ def test_mesh_mesh_contact_between_two_bodies(hbmod, tmp_path):
     assert c["dim"] == 3 and o.nefc == 4
 
 
-# ---- mjc_PlaneConvex: mesh hulls on a PLANE floor (the reference's green_screen_world.xml:30 and empty_world.xml:24 put the robot's
-# meshes on one; rl/generate_policy_videos.py builds CPUEnv on it)
-PLANE_CUBE_XML = ('<mujoco><option timestep="0.002"/><asset>%s</asset><worldbody><geom name="floor" type="plane" pos="0 0 0" size="0 0 .05" condim="3"/>'
-                  '<body pos="%s" %s><freejoint/><inertial pos="0 0 0" mass="0.5" diaginertia="0.001 0.001 0.001"/><geom type="mesh" mesh="cube" condim="%d"/></body>'
-                  '</worldbody></mujoco>')
-
-
+# ---- mjc_PlaneConvex: mesh hulls on a PLANE floor (convex_models.PLANE_CUBE_XML)
 def test_plane_mesh_contacts_at_the_lowest_corners(hbmod, tmp_path):
     """A cube hull (edge 0.1) lying flat, 1 mm into the plane: the support vertex and its graph neighbours in the bottom face, never a top
     vertex (outside the margin); contact i at its vertex moved half the penetration up, distance = the vertex's height, normal = the

@@ -10,9 +10,8 @@ import os
 import numpy as np
 import pytest
 
-from oracle_lib import HUMANOID_HBM, Oracle, halton
+from oracle_lib import HUMANOID_HBM, Oracle, halton, MODELS_DIR as MODELS
 
-MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models")
 CONTACT, LIMIT, PASSIVE, ACT, EULERDAMP, GRAVITY, WARMSTART = 16, 8, 32, 1024, 16384, 64, 256
 
 

@@ -5,7 +5,7 @@
 """
 import numpy as np
 
-from oracle_lib import Oracle
+from oracle_lib import MODELS_DIR, Oracle
 
 SOL_PGS, SOL_NEWTON = 0, 2
 
@@ -90,7 +90,7 @@ def test_newton_agrees_with_converged_pgs_on_other_models(tmp_path):
     """Same cross-check on the small test models: condim-1 pairs, multi-tree contact, slide joints, joint limits."""
     import os
     import humanoid_mujoco_amd as hb
-    models = os.path.join(os.path.dirname(os.path.abspath(__file__)), "models")
+    models = MODELS_DIR
     for name, steps in (("ball_plane", 300), ("capsules", 300), ("chain", 200)):
         p = str(tmp_path / (name + ".hbm"))
         hb.Model.load(os.path.join(models, name + ".xml")).save(p)

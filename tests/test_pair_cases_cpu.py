@@ -10,7 +10,7 @@
     disagree on the contact COUNT is ill-conditioned; at most 5 % of the table may be.  The exact cases (bitwise equal operands) get
     neither an envelope nor a count allowance: reference() gives them a zero envelope and only the unperturbed evaluation.
 
-reference() is what tests/test_gpu_narrow_pairs.py holds the device to.
+pair_cases.reference() computes all of this once; it is what tests/test_gpu_narrow_pairs.py holds the device to.
 """
 import collections
 
@@ -19,73 +19,8 @@ import pytest
 
 import pair_cases
 import pair_ref
-from oracle_lib import Oracle, load_state, parse_hbm
-
-GUARD = 1e-4
-NPERT = 32
-_cache = {}
-
-
-def compiled(hbmod, variant, directory):
-    """(model, .hbm path, parsed .hbm) of a scene variant"""
-    m = hbmod.Model.from_xml_string(pair_cases.scene_xml(variant))
-    p = str(directory / ("pairs_%s.hbm" % variant))
-    m.save(p)
-    return m, p, parse_hbm(p)
-
-
-def state_of(o, qpos):
-    return np.concatenate([[0.0], qpos, np.zeros(2 * o.nv)])
-
-
-def _evaluate(o, qpos):
-    load_state(o, state_of(o, qpos), np.zeros(o.nu))
-    o.forward()
-    return dict(qpos=qpos, ncon=o.ncon, nefc=o.nefc, con=o.contacts())
-
-
-def _spread(ref, others):
-    """largest deviation of dist, pos and normal of evaluations with ref's count from ref, per contact: [ncon, 3]"""
-    env = np.zeros((ref["ncon"], 3))
-    for ev in others:
-        if ev["ncon"] != ref["ncon"]:
-            continue
-        for i, (a, b) in enumerate(zip(ref["con"], ev["con"])):
-            env[i] = np.maximum(env[i], (abs(a["dist"] - b["dist"]), np.abs(a["pos"] - b["pos"]).max(), np.abs(a["frame"][0] - b["frame"][0]).max()))
-    return env
-
-
-def reference(hbmod, variant, directory):
-    """The oracle's side of a scene variant, computed once: dict(model, path, info, cases, evals, ill).  evals[i] lists case i's
-    evaluations, the unperturbed one first (an exact case has no other); envelope(i, n) gives the evaluation a device count n is held
-    to and the spread around it."""
-    if variant in _cache:
-        return _cache[variant]
-    m, p, info = compiled(hbmod, variant, directory)
-    o = Oracle(p)
-    cases = pair_cases.build_cases(info)
-    rng = np.random.default_rng(7)
-    evals, ill = [], []
-    for c in cases:
-        ev = [_evaluate(o, c["qpos"])]
-        if not c["exact"]:
-            for _ in range(NPERT):
-                ev.append(_evaluate(o, c["qpos"] + 2.0 ** -24 * np.maximum(1.0, np.abs(c["qpos"])) * rng.standard_normal(len(c["qpos"]))))
-        evals.append(ev)
-        ill.append(len({e["ncon"] for e in ev}) > 1)
-    ref = dict(model=m, path=p, info=info, cases=cases, evals=evals, ill=np.array(ill), oracle=o)
-    _cache[variant] = ref
-    return ref
-
-
-def envelope(ref, i, ncon):
-    """(the evaluation of case i that a device reporting ncon contacts is held to, its [ncon, 3] envelope), or None when no evaluation
-    the rules allow has that count: the unperturbed oracle, or for an ill-conditioned case any of its perturbed evaluations"""
-    ev = ref["evals"][i]
-    pick = next((e for e in ev if e["ncon"] == ncon), None)
-    if pick is None:
-        return None
-    return pick, _spread(pick, [e for e in ev if e is not pick])
+from oracle_lib import Oracle
+from pair_cases import GUARD, compiled, envelope, evaluate, reference
 
 
 @pytest.fixture(scope="module")
@@ -184,7 +119,7 @@ def test_scene_variants_share_the_table(hbmod, tmp_path):
         o = Oracle(p)
         got = []
         for c in pair_cases.build_cases(info)[::7]:
-            ev = _evaluate(o, c["qpos"])
+            ev = evaluate(o, c["qpos"])
             got.append((ev["ncon"], [x["dist"] for x in ev["con"]]))
         base = base or got
         assert got == base, v

@@ -13,11 +13,12 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from oracle_lib import GOLDEN, ROOT
+
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from make_particle_golden import GOAL, HBM, HORIZON, REF_XML, closed_form, oracle_rollout, policy  # noqa: E402
 
-GOLD = os.path.join(ROOT, "tests", "golden", "particle_rollout.npz")
+GOLD = os.path.join(GOLDEN, "particle_rollout.npz")
 
 
 def reference_bounds(states):

@@ -8,9 +8,8 @@ import pytest
 
 import rk4_ref
 from kernel_models import chain_xml, kernel_table
-from oracle_lib import HUMANOID_HBM, ROOT, Oracle, parse_hbm
-
-CSRC = os.path.join(ROOT, "humanoid_mujoco_amd", "csrc")
+from oracle_lib import CSRC, HUMANOID_HBM, Oracle, parse_hbm
+from step_lib import RK4_KERNELS, kernel_names_in_source
 
 
 def _hbm_with_integrator(tmp_path, value):
@@ -103,13 +102,11 @@ def test_reference_is_exact_on_a_constant_acceleration(hbmod, tmp_path):
 
 def test_rk4_kernels_are_named_outside_the_step_kernel_pattern_and_all_tested():
     """the RK4 kernels - the rows of the kernel table with INTEG = 1 and no read-out - have names that the step-kernel matrix
-    (test_gpu_kernel_matrix.py) does not collect; each is in the table of test_gpu_rk4.py"""
-    import test_gpu_kernel_matrix as tkm
-    import test_gpu_rk4
+    (test_gpu_kernel_matrix.py) does not collect; each is in the table test_gpu_rk4.py runs (step_lib.RK4_KERNELS)"""
     names = [n for n, c in kernel_table() if c["INTEG"] == "1" and c["ACC"] == "0"]
     assert sorted(names) == ["hb_rk4_32_kernel", "hb_rk4_kernel", "hb_rk4_newton28_kernel", "hb_rk4_newton32_kernel"]
-    assert not set(names) & tkm._kernel_names_in_source()
+    assert not set(names) & kernel_names_in_source()
     assert not any(re.match(r"hb_step\w*_kernel$", n) for n in names)
-    assert set(names) == set(test_gpu_rk4.KERNELS.values())
+    assert set(names) == set(RK4_KERNELS.values())
     src = open(os.path.join(CSRC, "hb_step.hip")).read()
     assert "kStepKernels[] = {HB_KERNELS(HB_ROW)};" in src  # (every row of the table is in the dispatch's array)

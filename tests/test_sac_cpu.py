@@ -11,18 +11,9 @@ import pytest
 import mlp_ref as ml
 import sac_ref as sr
 from conftest import ROOT
+from sac_lib import NETS, problem as _problem
 
 NOBS, NU = 48, 21
-NETS = {"small": ([48, 20, 33, 42], [69, 20, 33, 1]), "one_layer": ([48, 42], [69, 1]), "mixed": ([48, 64, 42], [69, 16, 1])}
-
-_problems = {}
-
-
-def _problem(net, n_rows, seed=1):
-    key = (net, n_rows, seed)
-    if key not in _problems:
-        _problems[key] = sr.random_problem(*NETS[net], n_rows, seed=seed)
-    return _problems[key]
 
 
 @pytest.mark.parametrize("net", sorted(NETS))
