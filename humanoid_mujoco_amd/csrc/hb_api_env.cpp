@@ -45,7 +45,12 @@ static int env_eval(hb_batch* b, bool allow_reset, bool observe, const uint8_t* 
   const float* src = b->D.d_qpos_src + (cfg.reset_keyframe < 0 || cfg.reset_keyframe >= m.nkey ? 0 : (size_t)(1 + cfg.reset_keyframe) * m.nq);
   EnvRandState S = b->rs;
   if (!b->rand_on) memset(&S, 0, sizeof S);
-  if (b->n_ext > 0) {
+  // velocity commands: the env kernel is handed the envs' records; only a step may redraw inside an episode (allow_reset: hb_env_step*,
+  // hb_env_collect*; not hb_get_obs, not the settle step or the final observation of hb_env_reset)
+  CmdArgs K;
+  memset(&K, 0, sizeof K);
+  if (b->d_cmd) { K.cmd = b->d_cmd; K.C = b->cmd_cfg; K.resample = allow_reset ? 1 : 0; K.obs_col = b->cmd_cfg.observe ? b->env_nobs - 3 : -1; }
+  if (b->env_nobs != b->D.dm.nobs) {
     // the extended row: the scan is cast here, at the state the step left (an episode that ends below ends in it, over the elevations
     // it was run on); the env kernel appends the last action and the scan to the rows it writes; the envs it resets get the scan of
     // their new state, over their new elevations, from a second cast masked to them
@@ -57,12 +62,12 @@ static int env_eval(hb_batch* b, bool allow_reset, bool observe, const uint8_t* 
     int rc = scan ? rays_scan_launch(b, nullptr, b->d_ext_scan, b->n_ray, 0) : HB_OK;
     if (rc != HB_OK) return rc;
     HB_HIP(launch_env(b->D.dm, cfg, b->env_rand, S, b->d_state, b->d_qfrc, b->d_counts, b->d_prev, b->d_latest, src, b->d_episode, b->d_status, d_obs, d_reward,
-                      d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen, &X));
+                      d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen, &X, &K));
     if (X.reset_flag) return rays_scan_launch(b, X.reset_flag, d_obs, b->env_nobs, b->D.dm.nobs + X.n_act);
     return HB_OK;
   }
   HB_HIP(launch_env(b->D.dm, cfg, b->env_rand, S, b->d_state, b->d_qfrc, b->d_counts, b->d_prev, b->d_latest, src, b->d_episode, b->d_status, d_obs, d_reward,
-                    d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen));
+                    d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen, nullptr, &K));
   return HB_OK;
 }
 
@@ -71,7 +76,7 @@ int hb_get_obs(hb_batch* b, float* obs, float* reward, uint8_t* terminated, uint
   int rc = env_alloc(b);
   if (rc != HB_OK) return rc;
   int n = b->n_env, nobs = b->env_nobs;
-  if (reward || terminated || truncated || b->n_ext > 0) {  // (an extended row is the env kernel's: hb_obs_kernel writes the base alone)
+  if (reward || terminated || truncated || nobs != b->D.dm.nobs) {  // (an extended row is the env kernel's: hb_obs_kernel writes the base alone)
     rc = env_eval(b, false, false, nullptr, b->d_obs, b->d_reward, b->d_term, b->d_trunc);  // pure evaluation: no reset, no bookkeeping, true observation
     if (rc != HB_OK) return rc;
   } else {
@@ -279,10 +284,34 @@ int hb_env_get_domain_params(hb_batch* b, float* out) {
 
 int hb_env_nobs(hb_batch* b) { return b ? b->env_nobs : HB_EINVAL; }
 
+// the record and the terminal-observation table with rows of `total` floats (the stream is idle); a failure leaves the batch as it was
+static int env_rows_resize(hb_batch* b, int total) {
+  if (total == b->env_nobs) return HB_OK;
+  const bool had_record = b->env_ready, had_term = (bool)b->d_term_obs;
+  DevBuf<uint8_t> record;
+  DevBuf<float> term;
+  const size_t n = b->n_env;
+  if (had_record && record.alloc(n * total * sizeof(float) + n * sizeof(float) + 2 * n) != HB_OK) return HB_ENOMEM;
+  if (had_term && term.alloc(n * total, /*zero=*/true) != HB_OK) return HB_ENOMEM;
+  if (had_record) {
+    b->d_record.swap(record);
+    b->d_obs = reinterpret_cast<float*>(b->d_record.get());
+    b->d_reward = b->d_obs + n * total;
+    b->d_term = reinterpret_cast<uint8_t*>(b->d_reward + n);
+    b->d_trunc = b->d_term + n;
+  }
+  if (had_term) b->d_term_obs.swap(term);
+  b->env_nobs = total;
+  return HB_OK;
+}
+static bool obs_consumers_exist(const hb_batch* b) {
+  return b->actor.layers >= 1 || b->critic.layers >= 1 || b->q[0].layers >= 1 || b->q[1].layers >= 1 || b->norm_on || b->learner.on || b->sac.on;
+}
+
 int hb_env_obs_extend(hb_batch* b, const hb_obs_ext* ext) {
   if (!b) return HB_EINVAL;
   // everything sized by the observation comes after this call
-  if (b->actor.layers >= 1 || b->critic.layers >= 1 || b->q[0].layers >= 1 || b->q[1].layers >= 1 || b->norm_on || b->learner.on || b->sac.on) return HB_EINVAL;
+  if (obs_consumers_exist(b)) return HB_EINVAL;
   hb_obs_ext x;
   memset(&x, 0, sizeof x);
   if (ext) {
@@ -301,27 +330,105 @@ int hb_env_obs_extend(hb_batch* b, const hb_obs_ext* ext) {
   DevBuf<float> scan;
   DevBuf<uint8_t> flag;
   if (x.height_scan && (scan.alloc((size_t)b->n_env * b->n_ray) != HB_OK || flag.alloc((size_t)b->n_env, /*zero=*/true) != HB_OK)) return HB_ENOMEM;
-  const int total = b->D.dm.nobs + n_ext;
-  if (total != b->env_nobs) {
-    // the record and the terminal-observation table have rows of the new width
-    const bool had_record = b->env_ready, had_term = (bool)b->d_term_obs;
-    DevBuf<uint8_t> record;
-    DevBuf<float> term;
-    const size_t n = b->n_env;
-    if (had_record && record.alloc(n * total * sizeof(float) + n * sizeof(float) + 2 * n) != HB_OK) return HB_ENOMEM;
-    if (had_term && term.alloc(n * total, /*zero=*/true) != HB_OK) return HB_ENOMEM;
-    if (had_record) {
-      b->d_record.swap(record);
-      b->d_obs = reinterpret_cast<float*>(b->d_record.get());
-      b->d_reward = b->d_obs + n * total;
-      b->d_term = reinterpret_cast<uint8_t*>(b->d_reward + n);
-      b->d_trunc = b->d_term + n;
-    }
-    if (had_term) b->d_term_obs.swap(term);
-  }
+  // the record and the terminal-observation table have rows of the new width (observed commands stay the last three columns)
+  const int rc = env_rows_resize(b, b->D.dm.nobs + n_ext + (b->d_cmd && b->cmd_cfg.observe ? 3 : 0));
+  if (rc != HB_OK) return rc;
   b->d_ext_scan.swap(scan);
   b->d_ext_reset.swap(flag);
-  b->obs_ext = x; b->n_ext = n_ext; b->env_nobs = total;
+  b->obs_ext = x; b->n_ext = n_ext;
+  return HB_OK;
+}
+
+// ---- velocity commands (include/hb.h: hb_env_commands)
+
+static thread_local const char* g_cmd_error = "";
+static int cmd_refuse(const char* why) { g_cmd_error = why; return HB_EINVAL; }
+const char* hb_error(void) { return g_cmd_error; }
+
+int hb_env_default_commands(const hb_model* m, hb_env_commands* out) {
+  g_cmd_error = "";
+  if (!m || !out) return cmd_refuse("hb_env_default_commands: NULL argument");
+  memset(out, 0, sizeof *out);
+  out->seed = 0;
+  out->vx_min = -1.f; out->vx_max = 1.f; out->vy_min = -0.5f; out->vy_max = 0.5f; out->yaw_min = -1.f; out->yaw_max = 1.f;
+  out->resample_time = 5.f; out->zero_fraction = 0.1f;
+  out->w_yaw = 2.5f;  // half of hb_env_default_config's w_hvel
+  out->frame = 1; out->observe = 1;
+  return HB_OK;
+}
+
+int hb_env_commands_check(const hb_model* m, const hb_env_commands* c) {
+  g_cmd_error = "";
+  if (!m || !c) return cmd_refuse("commands: NULL argument");
+  const float f[] = {c->vx_min, c->vx_max, c->vy_min, c->vy_max, c->yaw_min, c->yaw_max, c->resample_time, c->zero_fraction, c->w_yaw};
+  for (float x : f) if (!std::isfinite(x)) return cmd_refuse("commands: a field is not finite");
+  if (c->vx_min > c->vx_max || c->vy_min > c->vy_max || c->yaw_min > c->yaw_max) return cmd_refuse("commands: a range has min > max");
+  if (c->zero_fraction < 0.f || c->zero_fraction > 1.f) return cmd_refuse("commands: zero_fraction is outside [0, 1]");
+  if (c->frame != 0 && c->frame != 1) return cmd_refuse("commands: frame is neither 0 (world) nor 1 (heading)");
+  if (c->observe != 0 && c->observe != 1) return cmd_refuse("commands: observe is neither 0 nor 1");
+  bool free_root = false;  // (what the device model's obs_root_dofadr >= 0 says: hb_tables.cpp)
+  for (int j = 0; j < m->m.njnt; j++) free_root = free_root || m->m.jnt_type[j] == JNT_FREE;
+  if (!free_root) return cmd_refuse("commands: the model's observation has no free root");
+  return HB_OK;
+}
+
+int hb_env_commands_configure(hb_batch* b, const hb_env_commands* cfg) {
+  g_cmd_error = "";
+  if (!b) return cmd_refuse("hb_env_commands_configure: NULL batch");
+  if (cfg && hb_env_commands_check(b->model, cfg) != HB_OK) return HB_EINVAL;
+  static_assert(sizeof(hb_env_commands) == sizeof(EnvCommands), "hb_env_commands and EnvCommands must have the same layout");
+  const bool was = b->d_cmd && b->cmd_cfg.observe, now = cfg && cfg->observe;
+  if (was != now && obs_consumers_exist(b))
+    return cmd_refuse("commands: the observation width would change while an actor, critic, Q network, normaliser or learner exists");
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a step still in flight reads the buffers that are replaced below)
+  DevBuf<float4> rec;
+  const bool fresh = cfg && !b->d_cmd;
+  if (fresh && rec.alloc((size_t)b->n_env, /*zero=*/true) != HB_OK) return HB_ENOMEM;
+  if ((rc = env_rows_resize(b, b->D.dm.nobs + b->n_ext + (now ? 3 : 0))) != HB_OK) return rc;
+  if (!cfg) {
+    b->d_cmd.reset();
+    memset(&b->cmd_cfg, 0, sizeof b->cmd_cfg);
+    return HB_OK;
+  }
+  memcpy(&b->cmd_cfg, cfg, sizeof *cfg);
+  if (fresh) {
+    // valid commands at once: draw 0 of every env's current episode; hb_env_reset draws again for the episode numbers it assigns
+    b->d_cmd.swap(rec);
+    HB_HIP(launch_command_reset(b->cmd_cfg, b->d_cmd, b->d_episode, nullptr, b->n_env, b->env_offset, main_stream(b)));
+    HB_HIP(hipStreamSynchronize(main_stream(b)));
+  }
+  return HB_OK;
+}
+
+int hb_env_get_commands(hb_batch* b, float* out) {
+  g_cmd_error = "";
+  if (!b || !out) return cmd_refuse("hb_env_get_commands: NULL argument");
+  if (!b->d_cmd) return cmd_refuse("hb_env_get_commands: no command configuration is installed");
+  HB_HIP(hipSetDevice(b->device));
+  std::vector<float> rec((size_t)b->n_env * 4);
+  HB_HIP(hipMemcpyAsync(rec.data(), b->d_cmd, rec.size() * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  for (int e = 0; e < b->n_env; e++) for (int c = 0; c < 3; c++) out[3 * (size_t)e + c] = rec[4 * (size_t)e + c];
+  return HB_OK;
+}
+
+int hb_env_set_commands(hb_batch* b, const float* cmd, const uint8_t* mask) {
+  g_cmd_error = "";
+  if (!b || !cmd) return cmd_refuse("hb_env_set_commands: NULL argument");
+  if (!b->d_cmd) return cmd_refuse("hb_env_set_commands: no command configuration is installed");
+  for (int e = 0; e < b->n_env; e++)
+    if (!mask || mask[e]) for (int c = 0; c < 3; c++) if (!std::isfinite(cmd[3 * (size_t)e + c])) return cmd_refuse("hb_env_set_commands: a command is not finite");
+  HB_HIP(hipSetDevice(b->device));
+  // the records through the host, behind the enqueued work: the chosen envs' commands change, every draw count stays
+  std::vector<float> rec((size_t)b->n_env * 4);
+  HB_HIP(hipMemcpyAsync(rec.data(), b->d_cmd, rec.size() * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  for (int e = 0; e < b->n_env; e++)
+    if (!mask || mask[e]) for (int c = 0; c < 3; c++) rec[4 * (size_t)e + c] = cmd[3 * (size_t)e + c];
+  HB_HIP(hipMemcpy(b->d_cmd, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
   return HB_OK;
 }
 
@@ -381,6 +488,8 @@ int hb_env_reset(hb_batch* b, float* obs) {
       if (pending == 0) break;
     }
   }
+  // draw 0 of every env's command, with the episode numbers the envs ended up with
+  if (b->d_cmd) HB_HIP(launch_command_reset(b->cmd_cfg, b->d_cmd, b->d_episode, nullptr, b->n_env, b->env_offset, main_stream(b)));
   // the observation the reference returns from reset(): one more pass through the noise and delay lines
   rc = env_eval(b, false, true, nullptr, b->d_obs, b->d_reward, b->d_term, b->d_trunc);
   if (rc != HB_OK) return rc;

@@ -334,6 +334,10 @@ struct hb_batch {
   int env_nobs = 0, n_ext = 0;
   DevBuf<float> d_ext_scan;
   DevBuf<uint8_t> d_ext_reset;
+  // velocity commands (hb_env_commands_configure): the configuration and every env's record (cx, cy, cyaw, draw count), null while
+  // none is installed; with cmd_cfg.observe the three entries are the last columns of a row: env_nobs = D.dm.nobs + n_ext + 3
+  EnvCommands cmd_cfg = {};
+  DevBuf<float4> d_cmd;
   DevBuf<int> d_episode;
   int env_offset = 0;
   // realism layer (hb_env_randomize)

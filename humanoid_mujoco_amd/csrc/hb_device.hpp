@@ -737,6 +737,22 @@ struct ObsExtArgs {
   const float* scan;
   uint8_t* reset_flag;
 };
+// velocity commands (hb_env_commands_configure): the configuration (the layout of hb_env_commands) and what the env kernel is handed.
+// cmd: [n_env] (cx, cy, cyaw, the bits of the draw count k of the episode) - one 16-byte read per env; null: the feature is off and
+// nothing else is read.  resample: this launch may redraw inside an episode (a step; not a pure evaluation or a settle step).
+// obs_col: the column of the three command entries in an observation row, or -1 when the command is not observed.
+constexpr unsigned RS_COMMAND = 40;  // random-number stream of the command draws (1..8, 16..25 and 32..34 are taken)
+struct EnvCommands {
+  unsigned seed;
+  float vx_min, vx_max, vy_min, vy_max, yaw_min, yaw_max;
+  float resample_time, zero_fraction, w_yaw;
+  int frame, observe;
+};
+struct CmdArgs {
+  float4* cmd;
+  EnvCommands C;
+  int resample, obs_col;
+};
 constexpr int kAccPark = 24;  // floats per body in BatchPtrs::body_acc_park (six 16-byte moves)
 
 }  // namespace hb

@@ -452,6 +452,34 @@ __global__ void hb_action_kernel(const float* action, float* prev, float* latest
 
 __device__ __forceinline__ float scaled_exp(float x) { return expf(-x / 0.5f); }  // reward_functions.py:17-19
 
+// ---- velocity commands (hb_env_commands_configure; include/hb.h has the definitions, tests/cmd_ref.py restates them) ----------------
+// Draw k of episode ep of global env g, by NL >= 4 cooperating lanes of which l is this one: lane c < 3 returns component c of the
+// command, lo_c + u_{c+1} (hi_c - lo_c) as a subtract, a multiply and an add, each rounded once, or 0 where u_0 < zero_fraction (lane 3
+// draws u_0 and hands it round); the other lanes return nothing of use.  One hash per lane and one shuffle: no serial loop.
+template <int NL>
+__device__ __forceinline__ float command_draw(const EnvCommands& C, int env_global, int ep, int k, int l) {
+  static_assert(NL >= 4 && (NL & (NL - 1)) == 0, "command_draw: four lanes or more");
+  const float u = rng_uniform(C.seed, env_global, ep, k, RS_COMMAND, (l + 1) & 3);
+  const float u0 = __shfl(u, 3, NL);
+  // (the three ranges applied to this lane's u and the lane's own picked from the results: a pick among the configuration's fields
+  // themselves becomes an indexed read of the kernel argument, which costs the env kernel a stack frame)
+  const float vx = __fadd_rn(C.vx_min, __fmul_rn(u, __fsub_rn(C.vx_max, C.vx_min)));
+  const float vy = __fadd_rn(C.vy_min, __fmul_rn(u, __fsub_rn(C.vy_max, C.vy_min)));
+  const float vw = __fadd_rn(C.yaw_min, __fmul_rn(u, __fsub_rn(C.yaw_max, C.yaw_min)));
+  return u0 < C.zero_fraction ? 0.f : l == 0 ? vx : l == 1 ? vy : vw;
+}
+// ... and into the env's record: lanes 0..2 their component, lane 3 the new draw count (four neighbouring words: one transaction)
+__device__ __forceinline__ void command_store(float4* rec, int l, float v, int k_next) {
+  if (l < 3) reinterpret_cast<float*>(rec)[l] = v;
+  else if (l == 3) reinterpret_cast<int*>(rec)[3] = k_next;
+}
+constexpr int kCmdLanes = 4;
+__global__ void hb_command_reset_kernel(const EnvCommands C, float4* cmd, const int* episode, const uint8_t* mask, int n_env, int env_offset) {
+  const int e = (blockIdx.x * blockDim.x + threadIdx.x) / kCmdLanes, l = threadIdx.x % kCmdLanes;
+  if (e >= n_env || (mask && !mask[e])) return;
+  command_store(cmd + e, l, command_draw<kCmdLanes>(C, env_offset + e, episode[e], 0, l), 1);
+}
+
 // standupReward (reward_functions.py:247-374) + observation + termination + auto-reset.  kEnvLanes lanes per env, 256 / kEnvLanes
 // envs per block (it was one thread per env: 37 us of serial work on 32 CUs for 4096 envs, a fifth of VecEnv.step_torch's GPU time).
 // The env's state record is staged in LDS (one coalesced pass instead of a strided read per thread); sums over joints, actuators
@@ -466,7 +494,7 @@ __device__ __forceinline__ float env_lane_sum(float x) {
 __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const EnvConfig cfg, const EnvRand R, const EnvRandState S, float* state, const float* qfrc, const int* counts,
                               float* prev, float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated,
                               uint8_t* truncated, const uint8_t* mask, int observe, const DomainRand D, float* dr, int dr_stride, int n_env, int env_offset, float* term_obs, int* seen,
-                              const ObsExtArgs X) {
+                              const ObsExtArgs X, const CmdArgs K) {
   extern __shared__ float sh_state[];
   const int grp = threadIdx.x / kEnvLanes, l = threadIdx.x % kEnvLanes;
   const int e = blockIdx.x * (256 / kEnvLanes) + grp;
@@ -477,6 +505,8 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
   if (active) for (int i = l; i < M.nstate; i += kEnvLanes) ls[i] = s[i];
   __syncthreads();
   bool reset = false;
+  float cmd_l = 0.f;  // (commands: this lane's word of the env's record - lanes 0..2: a component of the command in force during the
+                      // step that is rewarded here, lane 3: the draws made so far in the episode)
   if (active) {
     const float* qpos = ls + 1;
     const float* qvel = ls + 1 + M.nq;
@@ -491,8 +521,25 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     float r = 0.f;
     // horizontal velocity
     float vx = da >= 0 ? qvel[da] : 0.f, vy = da >= 0 ? qvel[da + 1] : 0.f;
-    float dvx = vx - cfg.target_velocity[0], dvy = vy - cfg.target_velocity[1];
+    float tvx = cfg.target_velocity[0], tvy = cfg.target_velocity[1];
+    float4 cmd = {0.f, 0.f, 0.f, 0.f};
+    if (K.cmd) {
+      cmd = K.cmd[e];
+      tvx = cmd.x; tvy = cmd.y;
+      cmd_l = l == 0 ? cmd.x : l == 1 ? cmd.y : l == 2 ? cmd.z : cmd.w;
+      if (K.C.frame == 1) {  // the planar velocity in the root's heading frame (m[0], m[3]: the root's x axis in the world)
+        float hc, hs;
+        heading_cs(m[0], m[3], hc, hs);
+        const float wx = vx, wy = vy;
+        vx = hc * wx + hs * wy; vy = hc * wy - hs * wx;
+      }
+    }
+    float dvx = vx - tvx, dvy = vy - tvy;
     r += cfg.w_hvel * scaled_exp(dvx * dvx + dvy * dvy);
+    if (K.cmd) {  // the yaw rate: the world z component of the root's (body-frame) angular velocity
+      const float dw = (da >= 0 ? m[6] * qvel[da + 3] + m[7] * qvel[da + 4] + m[8] * qvel[da + 5] : 0.f) - cmd.z;
+      r += K.C.w_yaw * scaled_exp(dw * dw);
+    }
     // upright: |g_local - (0,0,-1)|^2
     r += cfg.w_upright * scaled_exp(g[0] * g[0] + g[1] * g[1] + (g[2] + 1.f) * (g[2] + 1.f));
     // torso height: linear ramp min_z -> target_z, clamped (numpy.interp)
@@ -564,6 +611,7 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     // the extension of the state the episode ends in: the action just applied, the scan before the reset (over the old elevations)
     for (int i = l; i < X.n_act; i += kEnvLanes) to[M.nobs + i] = latest[(size_t)e * M.nu + i];
     for (int i = l; i < X.n_scan; i += kEnvLanes) to[M.nobs + X.n_act + i] = X.scan[(size_t)e * X.n_scan + i];
+    if (K.cmd && K.obs_col >= 0) for (int i = l; i < 3; i += kEnvLanes) to[K.obs_col + i] = cmd_l;  // (the old command)
   }
   __syncthreads();  // (every lane has read the old state and the old episode number)
   if (reset) {
@@ -580,6 +628,14 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     static_assert(kEnvLanes == kDrawLanes, "the env kernel draws an episode's model parameters with all lanes of the env");
     if (dr) domain_draw<kDrawLanes>(M, D, dr + (size_t)e * dr_stride, env_offset + e, ep, l);
   }
+  if (K.cmd && active) {
+    // draw 0 of the episode that begins here, or - in a step - draw k of the one that goes on once its time has come: at most one draw
+    const int k = reset ? 0 : __float_as_int(__shfl(cmd_l, 3, kEnvLanes));
+    if (reset || (K.resample && K.C.resample_time > 0.f && ls[0] >= __fmul_rn((float)k, K.C.resample_time))) {
+      cmd_l = command_draw<kEnvLanes>(K.C, env_offset + e, ep, k, l);
+      command_store(K.cmd + e, l, cmd_l, k + 1);
+    }
+  }
   __threadfence_block();
   __syncthreads();  // the new state (LDS) and the new episode's delays (global, written by lane 0) are visible to the env's lanes
   if (active) {
@@ -591,6 +647,7 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     // scan of an env that goes on; an env that was reset gets its scan from the masked ray launch behind this kernel
     for (int i = l; i < X.n_act; i += kEnvLanes) o[M.nobs + i] = latest[(size_t)e * M.nu + i];
     if (!reset) for (int i = l; i < X.n_scan; i += kEnvLanes) o[M.nobs + X.n_act + i] = X.scan[(size_t)e * X.n_scan + i];
+    if (K.cmd && K.obs_col >= 0) for (int i = l; i < 3; i += kEnvLanes) o[K.obs_col + i] = cmd_l;  // (no noise, no delay)
   }
   if (X.reset_flag && e < n_env && l == 0) X.reset_flag[e] = reset ? 1 : 0;
 }
@@ -746,12 +803,19 @@ hipError_t launch_action(const float* action, float* prev, float* latest, float*
 hipError_t launch_env(const DevModel& M, const EnvConfig& cfg, const EnvRand& R, const EnvRandState& S, float* state, const float* qfrc, const int* counts, float* prev,
                       float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated,
                       const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs, int* seen,
-                      const ObsExtArgs* ext) {
+                      const ObsExtArgs* ext, const CmdArgs* cmd) {
   (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
   const int per_block = 256 / kEnvLanes;
+  const CmdArgs K = cmd ? *cmd : CmdArgs{};  // (none: a null record, and nothing else is read)
   const ObsExtArgs X = ext ? *ext : ObsExtArgs{M.nobs, 0, 0, nullptr, nullptr};  // (none: rows of the base observation alone)
   hipLaunchKernelGGL(hb_env_kernel, dim3((n_env + per_block - 1) / per_block), dim3(256), (size_t)per_block * ((M.nstate + 3) & ~3) * sizeof(float), stream, M, cfg, R, S, state, qfrc, counts, prev, latest, qpos_src, episode, status, obs,
-                     reward, terminated, truncated, mask, observe, D, dr, dr_stride, n_env, env_offset, term_obs, seen, X);
+                     reward, terminated, truncated, mask, observe, D, dr, dr_stride, n_env, env_offset, term_obs, seen, X, K);
+  return hipGetLastError();
+}
+hipError_t launch_command_reset(const EnvCommands& C, float4* cmd, const int* episode, const uint8_t* mask, int n_env, int env_offset, hipStream_t stream) {
+  (void)hipGetLastError();
+  const int per_block = 256 / kCmdLanes;
+  hipLaunchKernelGGL(hb_command_reset_kernel, dim3((n_env + per_block - 1) / per_block), dim3(256), 0, stream, C, cmd, episode, mask, n_env, env_offset);
   return hipGetLastError();
 }
 hipError_t launch_domain_rand(const DevModel& M, const DomainRand& D, float* dr, int stride, const int* episode, const uint8_t* mask, int n_env, int env_offset,

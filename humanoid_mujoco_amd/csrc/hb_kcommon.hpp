@@ -368,6 +368,14 @@ __device__ __forceinline__ float dot32(const float* row, const float* v) {
 
 // ------------------------------------------------------------------------------------------
 
+// the heading frame of a body (HB_RAY_FRAME_YAW, and frame 1 of hb_env_commands): its x axis (ax, ay, .) flattened onto the world xy
+// plane, as the unit vector (c, s); (1, 0) below a flattened length of 1e-6
+__device__ __forceinline__ void heading_cs(float ax, float ay, float& c, float& s) {
+  const float n = sqrtf(ax * ax + ay * ay);
+  c = 1.f; s = 0.f;
+  if (n >= 1e-6f) { c = ax / n; s = ay / n; }
+}
+
 // ---- counter-based random numbers (env realism, rollout noise): one 32-bit word per (seed, global env, episode, step,
 // stream, element): reproducible, order-free, the same on any split of the batch.  tests/env_ref.py restates them in numpy.
 __device__ __forceinline__ unsigned rng_mix(unsigned h, unsigned v) {

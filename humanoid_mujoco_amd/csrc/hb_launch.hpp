@@ -55,7 +55,10 @@ hipError_t launch_action(const float* action, float* prev, float* latest, float*
 hipError_t launch_env(const DevModel& M, const EnvConfig& cfg, const EnvRand& R, const EnvRandState& S, float* state, const float* qfrc, const int* counts, float* prev,
                       float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated,
                       const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs = nullptr, int* seen = nullptr,
-                      const ObsExtArgs* ext = nullptr);  // ext null: rows of M.nobs floats, the base observation alone
+                      const ObsExtArgs* ext = nullptr,   // ext null: rows of M.nobs floats, the base observation alone
+                      const CmdArgs* cmd = nullptr);     // cmd null: no velocity commands
+// draw 0 of the episodes in `episode` for every env (or those of `mask`): the command state at an episode start outside the env kernel
+hipError_t launch_command_reset(const EnvCommands& C, float4* cmd, const int* episode, const uint8_t* mask, int n_env, int env_offset, hipStream_t stream);
 hipError_t launch_domain_rand(const DevModel& M, const DomainRand& D, float* dr, int stride, const int* episode, const uint8_t* mask, int n_env, int env_offset,
                               hipStream_t stream);
 hipError_t launch_policy(const DevModel& M, const PolicyDesc& pd, const float* state, float* ctrl, int n_env, hipStream_t stream);

@@ -170,9 +170,8 @@ __device__ __forceinline__ void ray_body(const DevModel* Mp, const RayArgs& A) {
     else {
       // the heading frame: the body's x axis flattened onto the world xy plane, z up
       const V3 ax = qrot(xq, {1.f, 0.f, 0.f});
-      const float n = sqrtf(ax.x * ax.x + ax.y * ax.y);
-      float cx = 1.f, cy = 0.f;
-      if (n >= 1e-6f) { cx = ax.x / n; cy = ax.y / n; }
+      float cx, cy;
+      heading_cs(ax.x, ax.y, cx, cy);
       o = {xp.x + cx * o.x - cy * o.y, xp.y + cy * o.x + cx * o.y, xp.z + o.z};
       d = {cx * d.x - cy * d.y, cy * d.x + cx * d.y, d.z};
     }

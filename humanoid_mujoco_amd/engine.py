@@ -48,6 +48,12 @@ class HbObsExt(ctypes.Structure):
                 ("scan_lo", ctypes.c_float), ("scan_hi", ctypes.c_float)]
 
 
+class HbEnvCommands(ctypes.Structure):
+    """hb_env_commands (include/hb.h): per-env velocity commands - ranges, schedule, reward weight, frame, observation."""
+    _fields_ = [("seed", ctypes.c_uint)] + [(n, ctypes.c_float) for n in ("vx_min", "vx_max", "vy_min", "vy_max", "yaw_min", "yaw_max", "resample_time",
+                                                                           "zero_fraction", "w_yaw")] + [("frame", ctypes.c_int), ("observe", ctypes.c_int)]
+
+
 class HbRaySpec(ctypes.Structure):
     """hb_ray_spec (include/hb.h): frame, eligible geoms and cutoff of the installed rays."""
     _fields_ = [("frame", ctypes.c_int), ("frame_body", ctypes.c_int), ("bodyexclude", ctypes.c_int), ("flags", ctypes.c_int), ("cutoff", ctypes.c_float)]
@@ -401,6 +407,13 @@ def lib():
     L.hb_env_step_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     L.hb_env_obs_extend.argtypes = [vp, ctypes.POINTER(HbObsExt)]
     L.hb_env_nobs.argtypes = [vp]
+    L.hb_env_default_commands.argtypes = [vp, ctypes.POINTER(HbEnvCommands)]
+    L.hb_env_commands_check.argtypes = [vp, ctypes.POINTER(HbEnvCommands)]
+    L.hb_env_commands_configure.argtypes = [vp, ctypes.POINTER(HbEnvCommands)]
+    L.hb_env_get_commands.argtypes = [vp, vp]
+    L.hb_env_set_commands.argtypes = [vp, vp, vp]
+    L.hb_error.argtypes = []
+    L.hb_error.restype = ctypes.c_char_p
     L.hb_policy_set_mlp.argtypes = [vp, ci, vp, vp, vp]
     L.hb_policy_eval.argtypes = [vp, vp]
     L.hb_rollout_policy.argtypes = [vp, ci, vp]
@@ -1289,6 +1302,46 @@ class Batch:
         _check(rc, "hb_env_obs_extend", "call it before an actor, critic, Q network, normaliser or learner is installed; height_scan needs rays "
                "installed with a cutoff > 0, finite parameters and clip lo <= hi" if rc == -1 else None)
         self._env_pin = None  # (the transfer record of env_step has rows of the old width)
+
+    def default_commands(self):
+        """hb_env_default_commands: an HbEnvCommands to edit and hand to commands_configure"""
+        c = HbEnvCommands()
+        _check(lib().hb_env_default_commands(self.model._h, ctypes.byref(c)), "hb_env_default_commands")
+        return c
+
+    def commands_configure(self, cfg=None, **kw):
+        """Per-env velocity commands on the device (hb_env_commands_configure): commands_configure(vx_min=..., resample_time=..., frame=1,
+        observe=1, ...) installs the defaults of hb_env_default_commands with the given fields replaced (or an HbEnvCommands as it is);
+        commands_configure(None) with no fields removes them.  Every env then follows its own (vx, vy, yaw rate), drawn at every episode
+        start and every resample_time seconds, rewarded by the linear and the yaw term (target_velocity is ignored), and - with observe -
+        seen as the last three entries of every observation row (env_nobs grows by 3: call it before anything sized by the observation
+        is installed).  A call that is refused (HbError, with the library's reason) changes nothing."""
+        if cfg is None and kw:
+            cfg = self.default_commands()
+        for k, v in kw.items():
+            if not hasattr(cfg, k):
+                raise TypeError("commands_configure: unknown field %r" % k)
+            setattr(cfg, k, v)
+        rc = lib().hb_env_commands_configure(self._h, ctypes.byref(cfg) if cfg is not None else None)
+        _check(rc, "hb_env_commands_configure", lib().hb_error().decode() if rc == -1 else None)
+        self._env_pin = None  # (the transfer record of env_step has rows of the old width)
+
+    def commands(self):
+        """[n_env, 3] float32: every env's current (vx, vy, yaw rate) command, behind the enqueued work (hb_env_get_commands)"""
+        out = np.zeros((self.n_env, 3), dtype=np.float32)
+        rc = lib().hb_env_get_commands(self._h, _ptr(out))
+        _check(rc, "hb_env_get_commands", lib().hb_error().decode() if rc == -1 else None)
+        return out
+
+    def set_commands(self, cmd, mask=None):
+        """Overwrites the current command of the envs of `mask` ([n_env] bool; None: all) with cmd [n_env, 3] (or [3] for all of them) -
+        evaluation and teleoperation (hb_env_set_commands).  The draw counters do not move: the next scheduled draw replaces it."""
+        c = np.ascontiguousarray(np.broadcast_to(np.asarray(cmd, dtype=np.float32), (self.n_env, 3)))
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+        if m is not None and m.shape != (self.n_env,):
+            raise ValueError("set_commands: mask must be [n_env]")
+        rc = lib().hb_env_set_commands(self._h, _ptr(c), _ptr(m))
+        _check(rc, "hb_env_set_commands", lib().hb_error().decode() if rc == -1 else None)
 
     def env_reset(self):
         o = np.zeros((self.n_env, self.env_nobs), dtype=np.float32)

@@ -50,7 +50,7 @@ _NO_INFO = {}  # (shared by the envs that did not finish an episode this step: S
 
 class VecEnv:
     def __init__(self, model, n_envs, device=0, n_substeps=1, randomization_factor=1.0, realism=False, domain_randomization=False, seed=0, team=False,
-                 contact_forces=False, body_accelerations=False, height_scan=None, normalize=None, obs_extend=None, **reward_overrides):
+                 contact_forces=False, body_accelerations=False, height_scan=None, normalize=None, obs_extend=None, commands=None, **reward_overrides):
         """realism=True adds CPUEnv's sensor/action noise, delay FIFOs and pushes (hb_env_randomization), scaled by
         randomization_factor exactly like the reset perturbation; domain_randomization=True draws per-env masses, floor
         friction, joint and actuator parameters at every reset (hb_domain_randomization).  team=True: the reference's own
@@ -67,6 +67,12 @@ class VecEnv:
         lo, hi) - with offset = z0 the terrain height relative to the body (hb_env_obs_extend); `nobs`, observation_shape and
         obs_layout() describe the row, and actor, critic, Q networks, normaliser, learners and ReplayBuffer are sized by it.  Extension
         entries carry no sensor noise and no delay.  obs_extend=None, or a dict with everything off: the observation is the model's.
+        commands=dict(vx_min=..., vx_max=..., vy_min=..., vy_max=..., yaw_min=..., yaw_max=..., resample_time=..., zero_fraction=...,
+        w_yaw=..., frame=1, observe=1, seed=...) (any subset; {} for the defaults of hb_env_default_commands, seed defaulting to this
+        VecEnv's): every env follows its own commanded planar velocity and yaw rate, drawn on the device at every episode start and every
+        resample_time seconds, rewarded by the linear and the yaw term (target_velocity is ignored) and - with observe - seen as the
+        last three entries of every row, behind the extension: obs_layout()["command"]; commands() and set_commands() read and override
+        them.  set_attr("randomization_factor", ...) does NOT scale the command ranges: they are the task, not a disturbance.
         normalize=dict(norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8) (any subset; {} for the
         defaults): stable-baselines3's VecNormalize over a VecMonitor on the device (hb_norm_*): reset, step*, step_torch and collect*
         return normalised observations and rewards, finished envs' infos carry "episode": {"r", "l"} and a normalised
@@ -115,12 +121,26 @@ class VecEnv:
             raise ValueError("obs_extend: height_scan needs the VecEnv's height_scan=dict(body=..., xs=..., ys=...)")
         if ext_act or ext_scan is not None:
             self.batch.obs_extend(prev_action=ext_act, height_scan=ext_scan)
+        # velocity commands: with observe they widen the row too, so they also come before everything sized by it
+        self.commands_cfg = None
+        if commands is not None:
+            self.commands_cfg = self.batch.default_commands()
+            self.commands_cfg.seed = int(seed)
+            for k, v in dict(commands).items():
+                if not hasattr(self.commands_cfg, k):
+                    raise TypeError("commands: unknown option %r" % k)
+                setattr(self.commands_cfg, k, v)
+            self.batch.commands_configure(self.commands_cfg)
         self.nobs = self.batch.env_nobs
         self._layout = {"base": slice(0, self.model.nobs)}
         if ext_act:
             self._layout["prev_action"] = slice(self.model.nobs, self.model.nobs + self.model.nu)
         if ext_scan is not None:
-            self._layout["height_scan"] = slice(self.nobs - self._scan[0] * self._scan[1], self.nobs)
+            n_scan = self._scan[0] * self._scan[1]
+            at = self.model.nobs + (self.model.nu if ext_act else 0)
+            self._layout["height_scan"] = slice(at, at + n_scan)
+        if self.commands_cfg is not None and self.commands_cfg.observe:
+            self._layout["command"] = slice(self.nobs - 3, self.nobs)
         self.realism = None
         if realism:
             self.realism = self.batch.env_default_randomization()
@@ -158,8 +178,17 @@ class VecEnv:
 
     def obs_layout(self):
         """the columns of an observation row as slices: "base" (the model's nobs entries), and with obs_extend "prev_action" (nu) and
-        "height_scan" (len(ys) * len(xs) entries, row-major over ys then xs like height_scan())"""
+        "height_scan" (len(ys) * len(xs) entries, row-major over ys then xs like height_scan()), and with observed commands "command"
+        (vx, vy, yaw rate: the last three entries)"""
         return dict(self._layout)
+
+    def commands(self):
+        """[num_envs, 3] float32: every env's current (vx, vy, yaw rate) command (Batch.commands)"""
+        return self.batch.commands()
+
+    def set_commands(self, cmd, mask=None):
+        """overrides the current command of the envs of `mask` (None: all) until their next scheduled draw (Batch.set_commands)"""
+        self.batch.set_commands(cmd, mask)
 
     # ---- VecNormalize's surface (normalize=...)
     def _need_norm(self, what):

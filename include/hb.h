@@ -802,6 +802,8 @@ int hb_env_step_dev(hb_batch* b, const float* action_dev, int n_substeps, float*
 
 /* Appends to the model's observation, on the device, what a perceptive policy needs beside it.  Every row the env adapter writes is then
  *   [ base (the model's nobs) | prev_action (nu) | scan (n_ray) ]        hb_env_nobs floats; a part that is off is absent
+ *                                                                        (observed velocity commands add three entries behind these:
+ *                                                                        hb_env_commands, below)
  *   prev_action  the action the env last applied - the adapter's `latest`, which the reward's control-change term reads: behind the
  *                realism layer's action noise and delay where that is on; zero after a reset
  *   scan         one entry per installed ray (hb_ray_configure), in ray order: clamp(scan_scale * (scan_offset - d), scan_lo, scan_hi),
@@ -832,7 +834,67 @@ typedef struct hb_obs_ext {
   float scan_offset, scan_scale, scan_lo, scan_hi;
 } hb_obs_ext;
 int hb_env_obs_extend(hb_batch* b, const hb_obs_ext* ext);   /* NULL or all-zero: remove */
-int hb_env_nobs(hb_batch* b);                                /* base nobs + extension */
+int hb_env_nobs(hb_batch* b);                                /* base nobs + extension (+ 3 with observed commands, below) */
+
+/* ---- velocity commands: every env follows its own commanded planar velocity and yaw rate, drawn, tracked and observed on the device -- */
+
+/* With a configuration installed every env owns a current command (cx, cy, cyaw) - m/s, m/s, rad/s - and the number k of draws made
+ * so far in its episode, in a device buffer of the batch (16 bytes per env).
+ *   draw     Draw k of episode ep of global env g (the batch's env offset + e) comes from the counter-based generator of
+ *            hb_env_randomization: u_i = uniform(seed, g, ep, k, stream 40, i), i = 0..3.  u_0 < zero_fraction: the command is (0, 0, 0).
+ *            Otherwise component c is lo_c + u_{c+1} * (hi_c - lo_c) in fp32: a subtract, a multiply, an add, each rounded once (no fused
+ *            multiply-add).  A draw depends on (seed, g, ep, k) alone: the same bits on any split of a batch and in any order of envs.
+ *   when     Draw 0 at every episode start: in hb_env_reset (with the episode number the env ends up with after the collision
+ *            re-draws of reset_collision_mode) and at an auto-reset inside the env kernel.  Inside an episode, with resample_time > 0,
+ *            the env kernel of hb_env_step* / hb_env_collect* redraws after the step's reward and termination are formed: an env that did
+ *            not reset and whose state time (fp32) >= (float)k * resample_time (an fp32 product) makes draw k and sets k += 1.  At most
+ *            one draw per env step.  hb_get_obs and the settle step of hb_env_reset never draw.
+ *   reward   A step is rewarded against the command that was in force during it - the one the policy saw in obs[t]; the terminal
+ *            observation of an episode carries that command, obs[t+1] the new one (or draw 0 of the new episode).
+ *            The linear term of hb_env_config becomes w_hvel * scaled_exp(|v - (cx, cy)|^2): frame 0, v = the root's world-frame
+ *            (vx, vy) as before; frame 1, the same vector in the root body's heading frame - the definition of HB_RAY_FRAME_YAW: the
+ *            root's x axis flattened onto the world xy plane, unit (c, s), (1, 0) below a flattened length of 1e-6; v = (c vx + s vy,
+ *            -s vx + c vy).  A term w_yaw * scaled_exp((wz - cyaw)^2) is added, wz = the world z component of the root's angular
+ *            velocity (the free joint's angular velocity is in the body frame: wz = R[2][0] w0 + R[2][1] w1 + R[2][2] w2).  Every other
+ *            term, termination, truncation, terminal_reward and auto-reset stay as they are.  hb_env_config.target_velocity is IGNORED
+ *            while commands are installed.
+ *   observe  1: every row the adapter writes becomes [ base | prev_action | scan | command(3) ] - the command last, so the offsets of
+ *            hb_env_obs_extend do not move - and hb_env_nobs grows by 3.  Command entries get NO noise and NO delay.  Producers and
+ *            consumers are those hb_env_obs_extend lists (hb_get_obs, the terminal-observation table and the collection tapes among the
+ *            producers; the normaliser's limit of 240 entries still applies).  hb_policy_set_mlp, hb_policy_eval and hb_rollout_policy
+ *            keep the base observation.
+ * Without a configuration the adapter makes exactly the launches it made before and gives the same bits; with one it makes the same
+ * number of launches per step, and hb_env_reset one small launch more (the draws).  No atomics.
+ * Refusals, all HB_EINVAL, each leaving everything as it was and its reason in hb_error(): a NULL batch; a non-finite field; a min above
+ * its max; zero_fraction outside [0, 1]; frame or observe other than 0 or 1; a model whose observation has no free root; a call that
+ * would change the observation width (observe 0 -> 1, 1 -> 0, or a removal with observe on) while an actor, critic, Q network,
+ * normaliser or learner exists - the rule of hb_env_obs_extend; hb_env_get_commands / hb_env_set_commands with nothing installed (or a
+ * NULL array).  Changing ranges, weights, frame or resample_time of an installed configuration is always allowed: the current commands
+ * and counters stay, ranges and resample_time act from the next draw, weights and frame from the next step.  Installing draws draw 0
+ * of every env's current episode at once. */
+typedef struct hb_env_commands {
+  unsigned seed;
+  float vx_min, vx_max, vy_min, vy_max;   /* m/s   */
+  float yaw_min, yaw_max;                 /* rad/s */
+  float resample_time;    /* s of env time between draws inside an episode; <= 0: one draw per episode */
+  float zero_fraction;    /* in [0,1]: probability that a draw is the zero command (stand still) */
+  float w_yaw;            /* weight of the yaw-rate term; w_hvel of hb_env_config keeps weighting the linear term */
+  int   frame;            /* 0: world axes (the frame the reward uses without commands); 1: the root body's heading frame */
+  int   observe;          /* 1: append (vx, vy, yaw) to every observation row the adapter writes */
+} hb_env_commands;
+/* seed 0, vx in [-1, 1], vy in [-0.5, 0.5], yaw in [-1, 1], a draw every 5 s, a tenth of the draws zero, w_yaw = half of the default
+ * w_hvel, heading frame, observed.  HB_EINVAL: NULL argument. */
+int hb_env_default_commands(const hb_model* m, hb_env_commands* out);
+/* The checks of hb_env_commands_configure that need no batch: the fields, and the model's free root.  HB_OK or HB_EINVAL with hb_error(). */
+int hb_env_commands_check(const hb_model* m, const hb_env_commands* cfg);
+int hb_env_commands_configure(hb_batch* b, const hb_env_commands* cfg);   /* NULL: remove */
+int hb_env_get_commands(hb_batch* b, float* out);                         /* host [n_env][3], behind the enqueued work */
+/* For evaluation and teleoperation: overwrites the current command of the chosen envs (mask NULL: all; else [n_env], non-zero = chosen).
+ * The draw counters do not move, so the next scheduled draw replaces the command as usual. */
+int hb_env_set_commands(hb_batch* b, const float* cmd, const uint8_t* mask); /* host [n_env][3]; mask NULL = all */
+/* Why the calling thread's last hb_env_*commands* call was refused ("" when it was not): a static string, valid until that thread's
+ * next such call. */
+const char* hb_error(void);
 
 /* ---- policy in the loop (BASELINE.json configs[3]: MLP policy inference fused into the rollout loop) ---------- */
 
