@@ -101,6 +101,13 @@ int hb_model_pair_order(hb_model* h, int order) {
   return h->m.pair_order;
 }
 
+int hb_model_box_manifold(hb_model* h, int mode) {
+  if (!h) return refuse_with("hb_model_box_manifold: NULL model");
+  if (mode == 0 || mode == 1) h->m.box_manifold = mode;
+  else if (mode != -1) return refuse_with("hb_model_box_manifold: mode must be 1 (on), 0 (off) or -1 (query)");
+  return h->m.box_manifold;
+}
+
 int hb_model_name2id(const hb_model* h, const char* kind, const char* name) {
   if (!h || !kind || !name) return -1;
   const std::vector<std::string>* v = names_of(h->m, kind);
@@ -171,7 +178,7 @@ hb_batch* hb_batch_create(const hb_model* m, int n_env, int device, char* err, i
     sb.geom = b->d_stage_geom; sb.item = b->d_stage_item; sb.nwork = b->d_stage_nwork; sb.nsearch = b->d_stage_nsearch; sb.result = b->d_stage_result;
     sb.nq = dm.nq; sb.nv = dm.nv; sb.nu = dm.nu;
     sb.no_mesh = b->model->m.nmesh == 0 ? 1 : 0;
-    sb.has_box = dm.has_box;
+    sb.has_box = dm.box_manifold ? 2 : dm.has_box;
     sb.pose_lds = pose_lds_floats(dm.nq, dm.nbody, dm.ngeom) * (int)sizeof(float);
     if (dm.variant == 1 || b->D.d_dm_fast) {
       ok = ok && b->d_stage_defer.alloc((size_t)n_env * 3, /*zero=*/true) == HB_OK;  // flags | list | counters (StageBufs)

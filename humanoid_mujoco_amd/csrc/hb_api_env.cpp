@@ -344,6 +344,7 @@ int hb_env_obs_extend(hb_batch* b, const hb_obs_ext* ext) {
 static thread_local const char* g_cmd_error = "";
 static int cmd_refuse(const char* why) { g_cmd_error = why; return HB_EINVAL; }
 const char* hb_error(void) { return g_cmd_error; }
+extern "C++" int hb::refuse_with(const char* why) { return cmd_refuse(why); }
 
 int hb_env_default_commands(const hb_model* m, hb_env_commands* out) {
   g_cmd_error = "";

@@ -22,6 +22,7 @@ struct hb_model {
 
 namespace hb {
 
+int refuse_with(const char* why);  // HB_EINVAL, with `why` (a string literal) left for hb_error() (hb_api_env.cpp)
 inline void set_err(char* err, int err_sz, const std::string& s) {
   if (err && err_sz > 0) { snprintf(err, err_sz, "%s", s.c_str()); }
 }

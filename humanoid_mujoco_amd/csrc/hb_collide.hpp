@@ -102,7 +102,8 @@ __device__ __forceinline__ float lowest_point(DevModelRef M, int g, int type, fl
 // appends the results (collide_gather).
 //
 // passes (1) and (2): s_scratch receives the pair list, the sub-grids of height-field pairs and the work items; returns the number of work items
-// (BOX = 1, here and below: the instantiations for models with box geoms, which alone carry the box colliders)
+// (BOX = 1, here and below: the instantiations for models with box geoms, which alone carry the box colliders; BOX = 2: those of a model
+// with the box - box manifold on, DevModel::box_manifold, which alone carry box_box - BOX = 1 is the text it was before the manifold)
 template <int BOX = 0>
 __device__ __forceinline__ int build_work_list(DevModelRef M, int lane, const float* s_gpos, const float* s_gaxis, const float* s_gquat, int* s_scratch, int& status) {
   int* s_list = s_scratch;                   // [kListMax]
@@ -146,6 +147,7 @@ __device__ __forceinline__ int build_work_list(DevModelRef M, int lane, const fl
       const int g1 = __float_as_int(c0.x), g2 = __float_as_int(c0.y), t1 = __float_as_int(c0.z) & 255;
       cnt = 1;
       if (t1 == 0 && (((__float_as_int(c0.z) >> 8) & 255) == 7 || (BOX != 0 && ((__float_as_int(c0.z) >> 8) & 255) == 6))) cnt = 2;  // mjc_PlaneConvex, mjc_PlaneBox: up to four contacts, two per work item
+      if (BOX == 2 && t1 == 6 && ((__float_as_int(c0.z) >> 8) & 255) == 6) cnt = 4;  // the box - box manifold: up to eight contacts, two per work item
       if (t1 == 1) {
         // mjc_ConvexHField's culling.  The sub-grid comes from the geom's bounding sphere in place of its exact bounding box (a superset
         // of MuJoCo's prisms in x and y: the extra ones lie outside the geom's footprint and cannot touch it), the height test from the
@@ -265,6 +267,18 @@ __device__ __forceinline__ int eval_work_item(DevModelRef M, const float* hdata_
           co0.n = normal; co1.n = normal;
           n = min(max(total - 2 * sub, 0), 2);
         }
+      }
+    } else if (MODE != 2 && BOX == 2 && t1 == 6 && t2 == 6) {
+      // the box - box manifold (BOX = 2: the kernels of a model with DevModel::box_manifold): analytic (never reaches the narrowphase kernel); work item `sub` carries contacts
+      // 2 sub, 2 sub + 1 of up to eight
+      if constexpr (MODE != 2) {
+        float am[9], bm[9];
+        q2mat(am, ldq(s_gquat + 4 * g1));
+        q2mat(bm, ldq(s_gquat + 4 * g2));
+        V3 normal;
+        const int total = box_box(pos1, am, ld3(M.geom_half + 3 * g1), pos2, bm, ld3(M.geom_half + 3 * g2), margin, 2 * sub, normal, co0.dist, co0.pos, co1.dist, co1.pos);
+        n = min(max(total - 2 * sub, 0), 2);
+        if (n) { co0.n = normal; co1.n = normal; }
       }
     } else if ((MESH != 0 && (t1 == 7 || t2 == 7)) || (BOX != 0 && (t1 == 6 || (t1 == 3 && t2 == 6)))) {
       // mjc_Convex: both geoms in the world frame, each inflated by half the margin (a mesh hull or a box against anything but a plane,

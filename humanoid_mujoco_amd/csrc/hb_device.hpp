@@ -145,8 +145,14 @@ struct DevModel {
   // equality constraints: the rows in front of the friction rows, one per active joint coupling and three per active connect (0: a model
   // without them, or disabled by the options), and per row a kErecQuads record (hb_tables.cpp).  Read by step_body's FRIC == 2 instantiations only.
   int neq_rows;
+  // the box - box manifold (Model::box_manifold and a box - box candidate pair): box - box pairs are four analytic work items of two contacts
+  // (hb_mpr.hpp: box_box) in place of one portal search.  Read by the host only: it selects the BOX = 2 kernels (hb_pose_boxm_kernel, hb_boxm_*).  It sits in the four bytes of padding
+  // between neq_rows and the pointer behind it: no field moves and the structure keeps its size (some kernels take it by value, and
+  // a longer one would move their other arguments).
+  int box_manifold;
   const float4 HB_CONST* erec;
 };
+static_assert(sizeof(DevModel) % 8 == 0 && offsetof(DevModel, erec) == offsetof(DevModel, neq_rows) + 8, "box_manifold fills the padding behind neq_rows");
 constexpr int kErecQuads = 7;
 
 typedef const DevModel HB_CONST& DevModelRef;
@@ -487,7 +493,7 @@ struct StageBufs {
   // raises defer[env] and leaves its state alone, and the four-group kernel then steps exactly those envs (rerun = 1).
   const DevModel* dm_fast;  // null: no fast pass (not variant 2, or diagnostics on: their buffers have the big kernel's strides)
   int fast_lds;             // its dynamic LDS bytes
-  int has_box;              // DevModel::has_box: the pose / narrowphase launches are the *_box_kernel ones
+  int has_box;              // DevModel::has_box: the pose / narrowphase launches are the *_box_kernel ones; 2 (DevModel::box_manifold): the pose launch is hb_pose_boxm_kernel
   int* defer;               // [n_env]
   // the deferred envs of a launch as a list, so that the second pass is a handful of waves that loop over it instead of one wave per env
   // that looks at its flag and leaves (4096 waves of the four-group kernel, one per SIMD: 18 us): defer_list[blk0 + k], k < defer_count[blk0]

@@ -104,6 +104,9 @@ struct Model {
   // the first body, then those of the second - the structure of MuJoCo's collision driver, which runs its broadphase over BODIES and then
   // walks the geoms of every body pair.  0: geom pairs ascending (rounds 1-3 of this engine; .hbm files without the field).
   int pair_order = 0;
+  // The box - box manifold: 1: every box - box candidate pair is collided by the analytic clipping routine, up to eight
+  // contacts; 0 (the default, and every .hbm without the record): one contact through the portal search.  An optional record.
+  int box_manifold = 0;
   std::string pair_unsupported;  // compile time only: why a colliding geom pair cannot be simulated (empty: all pairs have colliders)
 
   // ---- field visitor used by serialisation (model_io.cpp): f(name, member) for every field
@@ -128,6 +131,7 @@ struct Model {
     if (f.optional(neq() > 0)) {
       HB_F(eq_type); HB_F(eq_obj1id); HB_F(eq_obj2id); HB_F(eq_active0); HB_F(eq_data); HB_F(eq_solref); HB_F(eq_solimp); HB_F(eq_name);
     }
+    if (f.optional(box_manifold != 0)) HB_F(box_manifold);
     HB_F(geom_type); HB_F(geom_bodyid); HB_F(geom_contype); HB_F(geom_conaffinity); HB_F(geom_condim);
     HB_F(geom_priority); HB_F(geom_dataid);
     HB_F(geom_size); HB_F(geom_pos); HB_F(geom_quat); HB_F(geom_rbound); HB_F(geom_friction);

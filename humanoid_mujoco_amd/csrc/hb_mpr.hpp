@@ -302,6 +302,153 @@ __device__ __forceinline__ int plane_box(V3 bpos, const float* bmat, V3 half, V3
   return n;
 }
 
+// The box - box manifold (DevModel::box_manifold): this engine's own definition, not mjc_BoxBox.  A is geom 1, B geom 2,
+// the normal points from A to B; fp64 on the fp32 poses, as plane_box.  Fifteen separating axes (faces A0 A1 A2 B0 B1 B2, then the
+// normalised edge axes A_i x B_j with i major, skipped below |A_i x B_j|^2 = 1e-10; the largest separation of each group, the first of
+// equals); any separation over the margin: no contact.  The edge case (s_edge > s_face + 0.05 |s_face| + 1e-4 of the smallest half
+// extent) gives one contact between the closest points of the two supporting edges.  The face case clips the incident face against
+// the reference face in the reference face's frame: (a) incident corners inside the rectangle R, in corner order, (b) corners of R
+// strictly inside the projected incident face Q, lifted onto the incident plane, (c) the 16 edge crossings, lifted likewise; the first
+// eight with dist <= margin.  Nothing is indexed by a run-time count: every candidate is a predicate and a counter, as plane_box's.
+// Returns the count (0..8), the normal, and the contacts `first_k`, `first_k + 1` of the list: a box - box pair is four work items.
+struct BoxD { V3d p, ax[3]; double h[3]; };
+__device__ __forceinline__ V3d pick(bool c, V3d a, V3d b);
+__device__ __forceinline__ BoxD box_widen(V3 pos, const float* m, V3 half) {
+  BoxD b;
+  b.p = widen(pos);
+  b.ax[0] = {(double)m[0], (double)m[3], (double)m[6]}; b.ax[1] = {(double)m[1], (double)m[4], (double)m[7]}; b.ax[2] = {(double)m[2], (double)m[5], (double)m[8]};
+  b.h[0] = (double)half.x; b.h[1] = (double)half.y; b.h[2] = (double)half.z;
+  return b;
+}
+__device__ __forceinline__ double box_sep(V3d L, V3d t, const BoxD& A, const BoxD& B) {
+  return fabs(dot(t, L)) - (fabs(dot(L, A.ax[0])) * A.h[0] + fabs(dot(L, A.ax[1])) * A.h[1] + fabs(dot(L, A.ax[2])) * A.h[2])
+                         - (fabs(dot(L, B.ax[0])) * B.h[0] + fabs(dot(L, B.ax[1])) * B.h[1] + fabs(dot(L, B.ax[2])) * B.h[2]);
+}
+__device__ __forceinline__ int box_box(V3 apos, const float* amat, V3 ahalf, V3 bpos, const float* bmat, V3 bhalf, float margin_f, int first_k,
+                                       V3& nrm_out, float& da, V3& pa, float& db, V3& pb) {
+  const BoxD A = box_widen(apos, amat, ahalf), B = box_widen(bpos, bmat, bhalf);
+  const double margin = (double)margin_f;
+  const V3d t = B.p - A.p;
+  double sf = -1e300, se = -1e300, smax = -1e300;
+  int kf = 0, ke = -1;
+  V3d Le = {0.0, 0.0, 1.0};
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const double s = box_sep(k < 3 ? A.ax[k] : B.ax[k - 3], t, A, B);
+    if (s > sf) { sf = s; kf = k; }
+  }
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const V3d c = cross(A.ax[i], B.ax[j]);
+      const double l2 = dot(c, c);
+      if (l2 < 1e-10) continue;
+      const V3d L = c * (1.0 / sqrt(l2));
+      const double s = box_sep(L, t, A, B);
+      if (s > se) { se = s; ke = 3 * i + j; Le = L; }
+    }
+  smax = sf > se ? sf : se;
+  if (smax > margin) return 0;
+  const double hmin = fmin(fmin(fmin(A.h[0], A.h[1]), fmin(A.h[2], B.h[0])), fmin(B.h[1], B.h[2]));
+  if (ke >= 0 && se > sf + 0.05 * fabs(sf) + 1e-4 * hmin) {
+    // the edge case: A's edge along axis i, B's along axis j, through the corners that support L and -L (a zero takes +)
+    const int i = ke / 3, j = ke - 3 * i;
+    const V3d L = dot(t, Le) >= 0.0 ? Le : Le * -1.0;
+    V3d cA = A.p, cB = B.p, u = A.ax[0], v = B.ax[0];
+    double hu = A.h[0], hv = B.h[0];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      if (a != i) cA = cA + A.ax[a] * (dot(L, A.ax[a]) >= 0.0 ? A.h[a] : -A.h[a]); else { u = A.ax[a]; hu = A.h[a]; }
+      if (a != j) cB = cB + B.ax[a] * (-dot(L, B.ax[a]) >= 0.0 ? B.h[a] : -B.h[a]); else { v = B.ax[a]; hv = B.h[a]; }
+    }
+    const V3d w = cA - cB;
+    const double b = dot(u, v), d = dot(u, w), e = dot(v, w), den = 1.0 - b * b;
+    const double xa = fmin(fmax((b * e - d) / den, -hu), hu), xb = fmin(fmax((e - b * d) / den, -hv), hv);
+    nrm_out = narrow(L);
+    if (first_k == 0) { da = (float)se; pa = narrow(((cA + u * xa) + (cB + v * xb)) * 0.5); }
+    return 1;
+  }
+  // the face case.  r: the reference box (owner of face axis kf), c: the other, whose face most anti-parallel to n_r is the incident face
+  const bool ref_a = kf < 3;
+  const int a = ref_a ? kf : kf - 3;
+  const V3d rp = ref_a ? A.p : B.p, cp = ref_a ? B.p : A.p;
+  V3d rax[3], cax[3];
+  double rh[3], ch[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) { rax[k] = pick(ref_a, A.ax[k], B.ax[k]); cax[k] = pick(ref_a, B.ax[k], A.ax[k]); rh[k] = ref_a ? A.h[k] : B.h[k]; ch[k] = ref_a ? B.h[k] : A.h[k]; }
+  // (cyclic picks by selects: a run-time index into rax / cax would put them in scratch)
+  const V3d ra = pick(a == 0, rax[0], pick(a == 1, rax[1], rax[2])), u1 = pick(a == 0, rax[1], pick(a == 1, rax[2], rax[0])), u2 = pick(a == 0, rax[2], pick(a == 1, rax[0], rax[1]));
+  const double ha = a == 0 ? rh[0] : a == 1 ? rh[1] : rh[2], h1 = a == 0 ? rh[1] : a == 1 ? rh[2] : rh[0], h2 = a == 0 ? rh[2] : a == 1 ? rh[0] : rh[1];
+  const V3d nr = dot(cp - rp, ra) >= 0.0 ? ra : ra * -1.0;
+  const V3d cr = rp + nr * ha;
+  const double d0 = fabs(dot(nr, cax[0])), d1 = fabs(dot(nr, cax[1])), d2 = fabs(dot(nr, cax[2]));
+  const int j = (d0 >= d1 && d0 >= d2) ? 0 : (d1 >= d2 ? 1 : 2);  // (the first of the largest)
+  const V3d ja = pick(j == 0, cax[0], pick(j == 1, cax[1], cax[2])), e1 = pick(j == 0, cax[1], pick(j == 1, cax[2], cax[0])), e2 = pick(j == 0, cax[2], pick(j == 1, cax[0], cax[1]));
+  const double hj = j == 0 ? ch[0] : j == 1 ? ch[1] : ch[2], g1 = j == 0 ? ch[1] : j == 1 ? ch[2] : ch[0], g2 = j == 0 ? ch[2] : j == 1 ? ch[0] : ch[1];
+  const V3d ni = dot(nr, ja) >= 0.0 ? ja * -1.0 : ja;
+  const V3d ci = cp + ni * hj;
+  const double nn = dot(nr, ni);
+  nrm_out = narrow(ref_a ? nr : nr * -1.0);
+  int n = 0;
+  auto emit = [&](V3d pnt, double dist) {
+    if (dist > margin || n >= 8) return;
+    const V3 pos = narrow(pnt - nr * (0.5 * dist));
+    if (n == first_k) { da = (float)dist; pa = pos; }
+    if (n == first_k + 1) { db = (float)dist; pb = pos; }
+    n++;
+  };
+  auto lift = [&](double x, double y) {
+    const V3d p0 = cr + u1 * x + u2 * y;
+    const double lam = dot(ci - p0, ni) / nn;
+    emit(p0 + nr * lam, lam);
+  };
+  // the incident face's corners, cyclic over (e1, e2): (-,-), (+,-), (+,+), (-,+), in 3-D and in the reference face's frame
+  V3d C[4];
+  double qx[4], qy[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    C[k] = ci + e1 * ((k == 1 || k == 2) ? g1 : -g1) + e2 * (k >= 2 ? g2 : -g2);
+    qx[k] = dot(C[k] - cr, u1); qy[k] = dot(C[k] - cr, u2);
+  }
+  // (a) in ascending corner index: cyclic 0, 1, 3, 2 - for the incident axis y (the other two are z, x) 0, 3, 1, 2
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    const int k0 = s == 0 ? 0 : s == 1 ? 1 : s == 2 ? 3 : 2, k1 = s == 0 ? 0 : s == 1 ? 3 : s == 2 ? 1 : 2;
+    const V3d c = pick(j == 1, C[k1], C[k0]);
+    const double x = j == 1 ? qx[k1] : qx[k0], y = j == 1 ? qy[k1] : qy[k0];
+    if (fabs(x) <= h1 && fabs(y) <= h2) emit(c, dot(c - cr, nr));
+  }
+  // (b) R's corners strictly inside the parallelogram Q
+  const double e1x = qx[1] - qx[0], e1y = qy[1] - qy[0], e2x = qx[3] - qx[0], e2y = qy[3] - qy[0], det = e1x * e2y - e1y * e2x;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const double x = (k == 1 || k == 2) ? h1 : -h1, y = k >= 2 ? h2 : -h2;
+    const double dx = x - qx[0], dy = y - qy[0];
+    const double al = (dx * e2y - dy * e2x) / det, be = (e1x * dy - e1y * dx) / det;
+    if (al > 0.0 && al < 1.0 && be > 0.0 && be < 1.0) lift(x, y);
+  }
+  // (c) Q's edges (cyclic) against R's edges (y = -h2, x = +h1, y = +h2, x = -h1)
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    const int e_next = (e + 1) & 3;
+    const double dx = qx[e_next] - qx[e], dy = qy[e_next] - qy[e];
+#pragma unroll
+    for (int f = 0; f < 4; f++) {
+      const bool horiz = (f & 1) == 0;
+      const double dp = horiz ? dy : dx;
+      if (fabs(dp) < 1e-12) continue;
+      const double line = f == 0 ? -h2 : f == 1 ? h1 : f == 2 ? h2 : -h1;
+      const double tq = (line - (horiz ? qy[e] : qx[e])) / dp;
+      const double along = horiz ? qx[e] + tq * dx : qy[e] + tq * dy;
+      const double hl = horiz ? h1 : h2;
+      const double tr = (f == 0 || f == 1) ? (along + hl) / (2.0 * hl) : (hl - along) / (2.0 * hl);
+      if (tq > 0.0 && tq < 1.0 && tr > 0.0 && tr < 1.0) { if (horiz) lift(along, line); else lift(line, along); }
+    }
+  }
+  return n;
+}
+
 struct CSup { V3d v, v1; };  // a point of the Minkowski difference obj1 - obj2 and its witness on obj1 (the one on obj2 is v1 - v)
 template <int MESH = 1, int GROUP = 1, int BOX = 0>
 __device__ __forceinline__ CSup mpr_support(const CObj& o1, const CObj& o2, V3d dir) {

@@ -24,6 +24,9 @@ namespace hb {
 #define HB_POSE_BOX 1
 #include "hb_pose_kernel.inl"
 #undef HB_POSE_BOX
+#define HB_POSE_BOX 2
+#include "hb_pose_kernel.inl"
+#undef HB_POSE_BOX
 
 // hb_narrow_kernel: the portal searches, one wave per env (and per 64 of its searches): lane l runs the env's l-th search, prisms
 // first, exactly as the fused step kernel would (eval_work_item).  The waves are mostly empty (an env has about nine searches), but
@@ -117,7 +120,8 @@ hipError_t launch_pose_narrow(const DevModel* M_dev, const BatchPtrs& Q, hipStre
   (void)limits_set;
 #endif
   const bool box = Q.stage.has_box != 0;
-  hipLaunchKernelGGL(box ? hb_pose_box_kernel : hb_pose_kernel, dim3(Q.nblk), dim3(kGroup), (size_t)Q.stage.pose_lds, stream, M_dev, Q);
+  // (has_box 2: the box - box manifold - its pairs are evaluated in the pose kernel and never searched: the narrowphase kernels are the box ones)
+  hipLaunchKernelGGL(Q.stage.has_box == 2 ? hb_pose_boxm_kernel : box ? hb_pose_box_kernel : hb_pose_kernel, dim3(Q.nblk), dim3(kGroup), (size_t)Q.stage.pose_lds, stream, M_dev, Q);
   const bool pairs = Q.nblk == Q.n_env && Q.n_env >= 512;  // a launch that covers its whole batch: nothing overlaps its tail anyway
   if (pairs) {
     // (waves per pair of envs: a wave without searches left ends at once.  Meshes: four lanes per search, two waves hold sixteen searches per env -

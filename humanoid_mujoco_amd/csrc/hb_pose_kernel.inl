@@ -1,9 +1,11 @@
-// hb_pose_kernel.inl - included twice by hb_narrow.hip (HB_POSE_BOX 0, then 1): hb_pose_kernel with the text, registers and instructions it had
-// before box geoms, and hb_pose_box_kernel, its twin for a model with box geoms (StageBufs::has_box), which alone carries the analytic box
-// colliders and the box cases of the work lists.  Twice the text and not a function template called from two entries: the entry then
+// hb_pose_kernel.inl - included three times by hb_narrow.hip (HB_POSE_BOX 0, 1, 2): hb_pose_kernel with the text, registers and instructions it had
+// before box geoms, hb_pose_box_kernel, its twin for a model with box geoms (StageBufs::has_box), which alone carries the analytic box
+// colliders and the box cases of the work lists, and hb_pose_boxm_kernel (has_box 2: the box - box manifold on), which adds box_box.  Twice the text and not a function template called from two entries: the entry then
 // takes its arguments through a reference, and the compiler schedules the kernel's argument loads differently (133 instructions of
 // hb_pose_kernel moved when that was tried).
-#if HB_POSE_BOX
+#if HB_POSE_BOX == 2
+#define HB_POSE_KERNEL hb_pose_boxm_kernel
+#elif HB_POSE_BOX
 #define HB_POSE_KERNEL hb_pose_box_kernel
 #else
 #define HB_POSE_KERNEL hb_pose_kernel

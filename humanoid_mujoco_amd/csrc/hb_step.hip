@@ -26,7 +26,7 @@ namespace hb {
 // SOLVER: mjtSolver of the instantiation (0 = PGS, 2 = Newton); everything outside the constraint solve, the mass-matrix
 // factorisation and the integrator's damped solve is shared.
 // COLL: 0 = the classic narrowphase (plane / sphere / capsule pairs, condim 1 / 3, inline), 1 = the general one (adds mesh hulls and
-// height-field prisms through MPR, condim 4 / 6), 2 = the general one with the box colliders (HB_BOX_KERNELS: a model with box geoms).  NG: constraint rows live in NG groups of 64 (lane l owns rows l + 64 g); NG > 1
+// height-field prisms through MPR, condim 4 / 6), 2 = the general one with the box colliders (HB_BOX_KERNELS: a model with box geoms), 3 = 2 with the box - box manifold (HB_BOXM_KERNELS).  NG: constraint rows live in NG groups of 64 (lane l owns rows l + 64 g); NG > 1
 // only with the Newton solver (kBigGroups: 256 rows, for the reference's own robot: ten pyramid rows per condim-6 contact).
 // DEFER: the fast pass of a staged step.  1 (variant 2, StageBufs::dm_fast): an env-step that overflows this instantiation's rows or
 // contacts is not stepped here but flagged for the four-group kernel.  2 (variant 1): same capacities as the full kernel, nothing to
@@ -90,7 +90,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   static_assert(ACC == 0 || (LEAN == 0 && SIZED == 0 && INV == 0), "the body-acceleration read-out: full kernels only");
   static_assert(FRIC == 0 || (COLL == 0 && NG == 1 && DEFER == 0 && LEAN == 0 && SIZED == 0 && INTEG == 0 && ACC == 0), "friction loss: the full Euler kernels of the classic variant");
   static_assert(INTEG == 0 || (COLL == 0 && NG == 1 && DEFER == 0 && LEAN == 0 && SIZED == 0 && INV == 0), "RK4: the full kernels of the classic variant");
-  static_assert(COLL != 2 || (DEFER == 0 && INV == 0 && LEAN == 0 && SIZED == 0), "box colliders: the full kernels of the general variants (the others only append results)");
+  static_assert(COLL < 2 || (DEFER == 0 && INV == 0 && LEAN == 0 && SIZED == 0), "box colliders: the full kernels of the general variants (the others only append results)");
   static_assert(NG == 1 || SOLVER == 2 || (COLL != 0 && NG == kPgsGroups && DEFER == 0), "PGS on more than one row group: the general variant's kPgsGroups instantiation");
   constexpr int kNR = NG == 1 ? kNefcMax : 64 * NG;  // row capacity of this instantiation
   constexpr int kNC = NG == 1 ? kNconMax : kBigNconMax;  // contact capacity
@@ -700,7 +700,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
         // staged step: the narrowphase ran in its own kernel on this step's poses (launch_step); the second forward pass of a step
         // whose first one was reset (mj_checkAcc) runs on other poses and does its own
         if (DEFER != 0 || (P.stage.result && !redo)) ncon = collide_gather<kNC>(M, lane, env, P.stage, s_gaxis, s_con, status);  // (DEFER: always staged, never a second pass)
-        else ncon = collide_general<kNC, COLL == 2 ? 1 : 0>(M, dr ? dr + DL.o_hfield : (const float*)M.hfield_data, lane, s_gpos, s_gaxis, s_gquat, s_con, reinterpret_cast<int*>(s_C), status);
+        else ncon = collide_general<kNC, COLL == 3 ? 2 : COLL == 2 ? 1 : 0>(M, dr ? dr + DL.o_hfield : (const float*)M.hfield_data, lane, s_gpos, s_gaxis, s_gquat, s_con, reinterpret_cast<int*>(s_C), status);
       }
     } else if (contacts_on) {
       // Two passes.  (1) Broadphase over every candidate pair - bounding spheres, or distance to the plane - with the
@@ -2354,6 +2354,18 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   K(hb_box_acc_newton_big20_kernel,   2,      20,     2,    kBigGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)       \
   K(hb_box_acc_newton_big28_kernel,   2,      28,     2,    kBigGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)
 
+// ---- and once more with the box - box manifold (DevModel::box_manifold; COLL 3 = BOX 2 of hb_collide.hpp): a family of its own, so that the
+// kernels of a box model with the mode off are the text, registers and instructions they were (profiles/boxbox_kernel_resources.txt)
+#define HB_BOXM_KERNELS(K)                                                                                                                 \
+  K(hb_boxm_gen_kernel,               0,      28,     3,    1,          0,     0,    0,     0,   0,     0,   0,    2,     0,     1)       \
+  K(hb_boxm_gen_big_kernel,           0,      28,     3,    kPgsGroups, 0,     0,    0,     0,   0,     0,   0,    1,     0,     1)       \
+  K(hb_boxm_newton_big20_kernel,      2,      20,     3,    kBigGroups, 0,     0,    0,     0,   0,     0,   0,    1,     0,     1)       \
+  K(hb_boxm_newton_big28_kernel,      2,      28,     3,    kBigGroups, 0,     0,    0,     0,   0,     0,   0,    1,     0,     1)       \
+  K(hb_boxm_acc_gen_kernel,           0,      28,     3,    1,          0,     0,    0,     0,   0,     1,   0,    2,     0,     1)       \
+  K(hb_boxm_acc_gen_big_kernel,       0,      28,     3,    kPgsGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)       \
+  K(hb_boxm_acc_newton_big20_kernel,  2,      20,     3,    kBigGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)       \
+  K(hb_boxm_acc_newton_big28_kernel,  2,      28,     3,    kBigGroups, 0,     0,    0,     0,   0,     1,   0,    1,     0,     1)
+
 // (the entry calls step_body directly: a forwarding function template in between changes register allocation and scheduling; every kernel
 // has the one signature - launch_pass hands all of them three arguments - and an INV row runs a single step whatever the count says)
 #define HB_STEP_BODY_0(S, ND, C, G, D, L, Z, I, N, A, F) step_body<S, ND, C, G, D, L, Z, I, N, A, F>(Mp, P, I ? 1 : nsteps)
@@ -2362,6 +2374,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   __attribute__((amdgpu_num_vgpr(V))) __global__ __launch_bounds__(kGroup, W) void name(const DevModel* Mp, const BatchPtrs P, int nsteps) { HB_STEP_BODY_##R(S, ND, C, G, D, L, Z, I, N, A, F); }
 HB_KERNELS(HB_DEFINE)
 HB_BOX_KERNELS(HB_DEFINE)
+HB_BOXM_KERNELS(HB_DEFINE)
 
 struct StepConfig {
   int solver, ndense, coll, ng, defer, lean, sized, inv, integ, acc, fric;
@@ -2370,7 +2383,7 @@ struct StepConfig {
 struct StepKernel { const char* name; const void* fn; StepConfig cfg; bool rerun; };
 #define HB_ROW(name, S, ND, C, G, D, L, Z, I, N, A, F, W, V, R) {#name, reinterpret_cast<const void*>(name), {S, ND, C, G, D, L, Z, I, N, A, F}, R != 0},
 static const StepKernel kStepKernels[] = {HB_KERNELS(HB_ROW)};
-static const StepKernel kBoxKernels[] = {HB_BOX_KERNELS(HB_ROW)};
+static const StepKernel kBoxKernels[] = {HB_BOX_KERNELS(HB_ROW) HB_BOXM_KERNELS(HB_ROW)};
 static const StepKernel* find_step_kernel(const StepConfig& c) {
   for (const StepKernel& k : kStepKernels) if (k.cfg == c) return &k;
   for (const StepKernel& k : kBoxKernels) if (k.cfg == c) return &k;
@@ -2446,7 +2459,7 @@ static StepChoice select_step(StepPass pass, const DevModel* M_dev, const DevMod
   c.acc = P.body_acc ? 1 : 0;  // (never lean: lean_launch; the full kernel of the same row with the body-acceleration read-out)
   // a model with box geoms: the kernels that collide inside the step are the COLL 2 ones (HB_BOX_KERNELS); a launch that cannot be
   // lean takes the full kernel, so the lean and size-specialised forms (which only gather) are looked for first as they are
-  if (M.has_box && c.coll && c.defer == 0) { c.coll = 2; c.lean = 0; c.sized = 0; }
+  if (M.has_box && c.coll && c.defer == 0) { c.coll = M.box_manifold ? 3 : 2; c.lean = 0; c.sized = 0; }
   const StepKernel* k = find_step_kernel(c);
   if (!k && c.sized) { c.sized = 0; k = find_step_kernel(c); }
   if (!k && c.lean) { c.lean = 0; k = find_step_kernel(c); }

@@ -573,6 +573,9 @@ bool build_model_tables(const Model& m, HostTables& H, std::string& err) {
   dm.box_cull = !(getenv("HB_BOX_CULL") && atoi(getenv("HB_BOX_CULL")) == 0);
   dm.has_box = 0;
   for (int p = 0; p < m.npair; p++) if (m.geom_type[m.pair_geom1[p]] == GEOM_BOX || m.geom_type[m.pair_geom2[p]] == GEOM_BOX) dm.has_box = 1;
+  // (the mode counts only where it changes something: a model without a box - box candidate pair builds the tables it built before)
+  dm.box_manifold = 0;
+  if (m.box_manifold) for (int p = 0; p < m.npair; p++) if (m.geom_type[m.pair_geom1[p]] == GEOM_BOX && m.geom_type[m.pair_geom2[p]] == GEOM_BOX) dm.box_manifold = 1;
   TI(pair_geom1, m.pair_geom1); TI(pair_geom2, m.pair_geom2); TI(pair_dim, P.dim); TI(pair_self, P.self);
   TF(pair_fricab, P.fricab);
   TF(pair_friction, P.fr); TF(pair_solref, P.solref); TF(pair_solimp, P.solimp); TF(pair_margin, P.margin); TF(pair_gap, P.gap);

@@ -146,6 +146,7 @@ bool validate_model(const Model& m, std::string& err) {
     return bad("negative size");
   // (unsupported options are errors, never silently dropped: an integrator or cone this engine does not have would otherwise be stepped as Euler / pyramidal)
   if (m.integrator != INT_EULER && m.integrator != INT_RK4) return bad("integrator " + std::to_string(m.integrator) + " is not implemented (Euler = 0, RK4 = 1)");
+  if (m.box_manifold != 0 && m.box_manifold != 1) return bad("box_manifold must be 0 or 1");
   if (m.cone != 0) return bad("cone " + std::to_string(m.cone) + " is not implemented (pyramidal = 0)");
   if (m.nq > 4096 || m.nv > 4096 || m.nu > 4096 || m.njnt > 4096 || m.ngeom > 4096 || m.nwrap > 65536 || m.npair > (1 << 20)) return bad("size out of range");
   struct { const char* name; size_t have, want; } lens[] = {

@@ -361,6 +361,7 @@ def lib():
     L.hb_batch_step_launches.argtypes = [vp]; L.hb_batch_step_launches.restype = ctypes.c_longlong
     L.hb_batch_tune.argtypes = [vp, ci, ci]
     L.hb_model_pair_order.argtypes = [vp, ci]
+    L.hb_model_box_manifold.argtypes = [vp, ci]
     L.hb_env_terminal_obs.argtypes = [vp, vp]
     L.hb_env_warnings.argtypes = [vp, vp]
     L.hb_env_joint_torques.argtypes = [vp, vp]
@@ -610,6 +611,15 @@ class Model:
         rc = lib().hb_model_pair_order(self._h, int(order))
         if rc < 0:
             _check(rc, "hb_model_pair_order")
+        return rc
+
+    def box_manifold(self, mode=-1):
+        """the box - box manifold (include/hb.h: hb_model_box_manifold): 1 every box - box pair is collided by the analytic clipping
+        routine, up to eight contacts; 0 (the default) one contact through the portal search; -1: query.  Returns the mode in force.
+        Call before a Batch is made of the model."""
+        rc = lib().hb_model_box_manifold(self._h, int(mode))
+        if rc < 0:
+            _check(rc, "hb_model_box_manifold", lib().hb_error().decode() if rc == -1 else None)
         return rc
 
     def name2id(self, kind, name):

@@ -50,7 +50,7 @@ _NO_INFO = {}  # (shared by the envs that did not finish an episode this step: S
 
 class VecEnv:
     def __init__(self, model, n_envs, device=0, n_substeps=1, randomization_factor=1.0, realism=False, domain_randomization=False, seed=0, team=False,
-                 contact_forces=False, body_accelerations=False, height_scan=None, normalize=None, obs_extend=None, commands=None, **reward_overrides):
+                 contact_forces=False, body_accelerations=False, height_scan=None, normalize=None, obs_extend=None, commands=None, box_manifold=False, **reward_overrides):
         """realism=True adds CPUEnv's sensor/action noise, delay FIFOs and pushes (hb_env_randomization), scaled by
         randomization_factor exactly like the reset perturbation; domain_randomization=True draws per-env masses, floor
         friction, joint and actuator parameters at every reset (hb_domain_randomization).  team=True: the reference's own
@@ -77,8 +77,12 @@ class VecEnv:
         defaults): stable-baselines3's VecNormalize over a VecMonitor on the device (hb_norm_*): reset, step*, step_torch and collect*
         return normalised observations and rewards, finished envs' infos carry "episode": {"r", "l"} and a normalised
         terminal_observation; `training`, normalize_obs, get_original_obs / get_original_reward, save_normalization / load_normalization as
-        in VecNormalize.  normalize=None: every path is unchanged."""
+        in VecNormalize.  normalize=None: every path is unchanged.
+        box_manifold=True: box - box pairs give a clipped face manifold of up to eight contacts (Model.box_manifold) in place of the
+        portal search's one; set on the model before the batch is built.  False leaves the model as it came."""
         self.model = model if isinstance(model, Model) else Model.load(model)
+        if box_manifold:
+            self.model.box_manifold(1)
         self.batch = Batch(self.model, n_envs, device)
         self.num_envs = int(n_envs)
         self.n_substeps = int(n_substeps)

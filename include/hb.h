@@ -90,8 +90,9 @@ typedef struct hb_sizes {
  * field; a cylinder only as a non-colliding marker.  A model with a colliding box steps in the kernels of the general collision path
  * (hb_last_kernel: hb_box_* / the staged step's fast pass), as a mesh model does: at most 28 dofs, Euler, no friction loss or equality
  * rows.  plane - box (up to four corner contacts) and sphere - box are MuJoCo's analytic routines; capsule - box, box - box, box - mesh
- * and height field - box go through the portal search.  DEVIATION from MuJoCo: capsule - box and box - box give ONE contact per pair
- * where mjc_CapsuleBox / mjc_BoxBox give up to 2 and 8 (a clipped box - box manifold is the follow-up). */
+ * and height field - box go through the portal search, and so does box - box unless hb_model_box_manifold(m, 1) selects this engine's
+ * clipped manifold of up to eight contacts.  DEVIATION from MuJoCo: capsule - box gives ONE contact per pair where mjc_CapsuleBox gives
+ * up to 2, and so does box - box in mode 0 where mjc_BoxBox gives up to 8. */
 hb_model* hb_model_load(const char* path, char* err, int err_sz);
 /* Replaces mj_loadXML with an in-memory string (mjVFS use in the reference). */
 hb_model* hb_model_load_xml_string(const char* xml, char* err, int err_sz);
@@ -112,6 +113,15 @@ int hb_options_set(hb_model* m, const hb_options* in);
  * ascending (this engine's rounds 1-3, and .hbm files written then).  -1: query.  Returns the order in force.  Call before
  * hb_batch_create. */
 int hb_model_pair_order(hb_model* m, int order);
+/* The box - box manifold.  mode 1: every box - box candidate pair is collided by an analytic routine of THIS ENGINE'S OWN DEFINITION (not a
+ * restatement of mjc_BoxBox; DESIGN.md 3.6a gives it in full): fifteen separating axes, then either one edge - edge contact or the
+ * incident face clipped against the reference face - 0 to 8 contacts per pair in a fixed order (incident corners inside the reference
+ * face, reference corners inside the incident face, edge crossings), normal from geom 1 to geom 2, each an ordinary contact of the pair;
+ * no portal search.  mode 0 (the default, and every .hbm without the optional record box_manifold): one contact through the portal
+ * search, bit for bit what the engine did before the mode existed.  -1: query.  Returns the mode in force; any other mode is
+ * HB_EINVAL with its reason in hb_error().  The mode is saved in the .hbm only when it is 1.  A model without a box - box candidate pair
+ * accepts the mode and steps exactly as without it.  Capsule - box stays one contact.  Call before hb_batch_create. */
+int hb_model_box_manifold(hb_model* m, int mode);
 /* mj_name2id (mujoco.h:516) for kind in {"body","joint","geom","actuator","tendon","key","equality"}; -1 if absent. */
 int hb_model_name2id(const hb_model* m, const char* kind, const char* name);
 /* mj_id2name for the same kinds: copies the name (empty for an unnamed element) into out[cap], zero-terminated; returns its length,

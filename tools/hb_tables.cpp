@@ -70,7 +70,7 @@ int main(int argc, char** argv) {
   I(iterations) I(disableflags) I(solver) I(ls_iterations) F(ls_tolerance) I(box_cull) I(has_box) I(obs_root_body) I(obs_root_dofadr) I(obs_root_qadr)
   I(o_gquat) I(o_meta) I(o_AR) I(o_qpos) I(o_qvel) I(o_warm) I(o_ctrl) I(o_gpos) I(o_gaxis) I(o_scom) I(o_cdof) I(o_qLD) I(o_smooth) I(o_vec0) I(o_vec1) I(o_vec2) I(o_tenlen)
   I(o_xpos) I(o_xmat) I(o_xipos) I(o_xanchor) I(o_xaxis) I(o_cinert) I(o_crb) I(o_cvel) I(o_con) I(o_C) I(o_efc) I(o_force)
-  I(lds_floats) I(cstride) I(integrator) I(o_rk) I(nfric) I(neq_rows)
+  I(lds_floats) I(cstride) I(integrator) I(o_rk) I(nfric) I(neq_rows) I(box_manifold)
 #undef I
 #undef F
   printf("array int %zu\narray float %zu\narray u64 %zu\n", H.iv.size(), H.fv.size(), H.uv.size());
