@@ -610,8 +610,10 @@ int hb_diag_enable(hb_batch* b, int on) {
 }
 
 int hb_contact_readout(hb_batch* b, int on) {
-  if (!b) return HB_EINVAL;
+  refuse_clear();
+  if (!b) return refuse_with("hb_contact_readout: NULL batch");
   HB_HIP(hipSetDevice(b->device));
+  if (!on && b->d_feet) return refuse_with("hb_contact_readout: the installed foot-contact terms (hb_env_feet_configure) read it");
   (void)main_stream(b);  // from the next launch on: step calls held back are launched as they were made
   if (on && alloc_contact_readout(b) != HB_OK) return HB_ENOMEM;
   b->contact_readout = on != 0;

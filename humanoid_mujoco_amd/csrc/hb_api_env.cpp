@@ -50,6 +50,13 @@ static int env_eval(hb_batch* b, bool allow_reset, bool observe, const uint8_t* 
   CmdArgs K;
   memset(&K, 0, sizeof K);
   if (b->d_cmd) { K.cmd = b->d_cmd; K.C = b->cmd_cfg; K.resample = allow_reset ? 1 : 0; K.obs_col = b->cmd_cfg.observe ? b->env_nobs - 3 : -1; }
+  // foot-contact terms: the read-out of the last substep and the envs' records; only a step writes the records (the same switch)
+  FeetArgs A;
+  memset(&A, 0, sizeof A);
+  if (b->d_feet) {
+    A.body_contact = b->d_body_contact; A.rec = b->d_feet; A.F = b->feet_cfg; A.update = allow_reset ? 1 : 0;
+    A.obs_col = b->feet_cfg.observe ? b->env_nobs - (b->d_cmd && b->cmd_cfg.observe ? 3 : 0) - b->feet_cfg.n_feet : -1;
+  }
   if (b->env_nobs != b->D.dm.nobs) {
     // the extended row: the scan is cast here, at the state the step left (an episode that ends below ends in it, over the elevations
     // it was run on); the env kernel appends the last action and the scan to the rows it writes; the envs it resets get the scan of
@@ -62,12 +69,12 @@ static int env_eval(hb_batch* b, bool allow_reset, bool observe, const uint8_t* 
     int rc = scan ? rays_scan_launch(b, nullptr, b->d_ext_scan, b->n_ray, 0) : HB_OK;
     if (rc != HB_OK) return rc;
     HB_HIP(launch_env(b->D.dm, cfg, b->env_rand, S, b->d_state, b->d_qfrc, b->d_counts, b->d_prev, b->d_latest, src, b->d_episode, b->d_status, d_obs, d_reward,
-                      d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen, &X, &K));
+                      d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen, &X, &K, &A));
     if (X.reset_flag) return rays_scan_launch(b, X.reset_flag, d_obs, b->env_nobs, b->D.dm.nobs + X.n_act);
     return HB_OK;
   }
   HB_HIP(launch_env(b->D.dm, cfg, b->env_rand, S, b->d_state, b->d_qfrc, b->d_counts, b->d_prev, b->d_latest, src, b->d_episode, b->d_status, d_obs, d_reward,
-                    d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen, nullptr, &K));
+                    d_term, d_trunc, mask, observe ? 1 : 0, b->dom_rand, b->d_dr, b->dr_stride, b->n_env, b->env_offset, main_stream(b), observe ? b->d_term_obs.get() : nullptr, b->d_seen, nullptr, &K, &A));
   return HB_OK;
 }
 
@@ -304,6 +311,11 @@ static int env_rows_resize(hb_batch* b, int total) {
   b->env_nobs = total;
   return HB_OK;
 }
+// the width of a row: [ base | extension (n_ext) | foot-contact flags | command ]
+static int env_row_width(const hb_batch* b, int n_ext, bool cmd_observed, int n_feet_observed) {
+  return b->D.dm.nobs + n_ext + n_feet_observed + (cmd_observed ? 3 : 0);
+}
+static int feet_observed(const hb_batch* b) { return b->d_feet && b->feet_cfg.observe ? b->feet_cfg.n_feet : 0; }
 static bool obs_consumers_exist(const hb_batch* b) {
   return b->actor.layers >= 1 || b->critic.layers >= 1 || b->q[0].layers >= 1 || b->q[1].layers >= 1 || b->norm_on || b->learner.on || b->sac.on;
 }
@@ -331,7 +343,7 @@ int hb_env_obs_extend(hb_batch* b, const hb_obs_ext* ext) {
   DevBuf<uint8_t> flag;
   if (x.height_scan && (scan.alloc((size_t)b->n_env * b->n_ray) != HB_OK || flag.alloc((size_t)b->n_env, /*zero=*/true) != HB_OK)) return HB_ENOMEM;
   // the record and the terminal-observation table have rows of the new width (observed commands stay the last three columns)
-  const int rc = env_rows_resize(b, b->D.dm.nobs + n_ext + (b->d_cmd && b->cmd_cfg.observe ? 3 : 0));
+  const int rc = env_rows_resize(b, env_row_width(b, n_ext, b->d_cmd && b->cmd_cfg.observe, feet_observed(b)));
   if (rc != HB_OK) return rc;
   b->d_ext_scan.swap(scan);
   b->d_ext_reset.swap(flag);
@@ -345,6 +357,7 @@ static thread_local const char* g_cmd_error = "";
 static int cmd_refuse(const char* why) { g_cmd_error = why; return HB_EINVAL; }
 const char* hb_error(void) { return g_cmd_error; }
 extern "C++" int hb::refuse_with(const char* why) { return cmd_refuse(why); }
+extern "C++" void hb::refuse_clear() { g_cmd_error = ""; }
 
 int hb_env_default_commands(const hb_model* m, hb_env_commands* out) {
   g_cmd_error = "";
@@ -388,7 +401,7 @@ int hb_env_commands_configure(hb_batch* b, const hb_env_commands* cfg) {
   DevBuf<float4> rec;
   const bool fresh = cfg && !b->d_cmd;
   if (fresh && rec.alloc((size_t)b->n_env, /*zero=*/true) != HB_OK) return HB_ENOMEM;
-  if ((rc = env_rows_resize(b, b->D.dm.nobs + b->n_ext + (now ? 3 : 0))) != HB_OK) return rc;
+  if ((rc = env_rows_resize(b, env_row_width(b, b->n_ext, now, feet_observed(b)))) != HB_OK) return rc;
   if (!cfg) {
     b->d_cmd.reset();
     memset(&b->cmd_cfg, 0, sizeof b->cmd_cfg);
@@ -430,6 +443,103 @@ int hb_env_set_commands(hb_batch* b, const float* cmd, const uint8_t* mask) {
   for (int e = 0; e < b->n_env; e++)
     if (!mask || mask[e]) for (int c = 0; c < 3; c++) rec[4 * (size_t)e + c] = cmd[3 * (size_t)e + c];
   HB_HIP(hipMemcpy(b->d_cmd, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
+  return HB_OK;
+}
+
+// ---- foot-contact terms (include/hb.h: hb_env_feet)
+
+int hb_env_default_feet(const hb_model* m, hb_env_feet* out) {
+  g_cmd_error = "";
+  if (!m || !out) return cmd_refuse("hb_env_default_feet: NULL argument");
+  memset(out, 0, sizeof *out);
+  out->contact_threshold = 1.f;
+  out->w_air_time = 1.f; out->air_time_target = 0.5f;
+  out->air_gate = 1; out->air_cmd_min = 0.1f;
+  double mass = 0.0;
+  for (int i = 0; i < m->m.nbody; i++) mass += m->m.body_mass[i];
+  const double* g = m->m.gravity;
+  out->w_force = -0.01f; out->force_max = (float)(2.0 * mass * std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]));
+  out->w_stumble = -1.f; out->stumble_ratio = 5.f;
+  out->w_collision = -1.f;
+  return HB_OK;
+}
+
+int hb_env_feet_check(const hb_model* m, const hb_env_feet* c) {
+  g_cmd_error = "";
+  if (!m || !c) return cmd_refuse("feet: NULL argument");
+  if (c->n_feet < 1 || c->n_feet > HB_ENV_MAX_FEET) return cmd_refuse("feet: n_feet is outside 1..4");
+  if (c->n_penalised < 0 || c->n_penalised > HB_ENV_MAX_CONTACT_BODIES) return cmd_refuse("feet: n_penalised is outside 0..8");
+  if (c->n_terminal < 0 || c->n_terminal > HB_ENV_MAX_CONTACT_BODIES) return cmd_refuse("feet: n_terminal is outside 0..8");
+  const int nbody = m->m.nbody;
+  auto body_ok = [&](int id) { return id >= 1 && id < nbody; };
+  for (int i = 0; i < c->n_feet; i++) if (!body_ok(c->foot_body[i])) return cmd_refuse("feet: a foot body id is outside 1..nbody-1");
+  for (int i = 0; i < c->n_penalised; i++) if (!body_ok(c->penalised_body[i])) return cmd_refuse("feet: a penalised body id is outside 1..nbody-1");
+  for (int i = 0; i < c->n_terminal; i++) if (!body_ok(c->terminal_body[i])) return cmd_refuse("feet: a terminal body id is outside 1..nbody-1");
+  for (int i = 0; i < c->n_feet; i++)
+    for (int j = 0; j < i; j++) if (c->foot_body[i] == c->foot_body[j]) return cmd_refuse("feet: a body is named twice in foot_body");
+  const float f[] = {c->contact_threshold, c->w_air_time, c->air_time_target, c->air_cmd_min, c->w_force, c->force_max, c->w_stumble, c->stumble_ratio, c->w_collision};
+  for (float x : f) if (!std::isfinite(x)) return cmd_refuse("feet: a field is not finite");
+  if (c->contact_threshold <= 0.f) return cmd_refuse("feet: contact_threshold is not above 0");
+  if (c->air_cmd_min < 0.f) return cmd_refuse("feet: air_cmd_min is below 0");
+  if (c->stumble_ratio < 0.f) return cmd_refuse("feet: stumble_ratio is below 0");
+  if (c->air_gate != 0 && c->air_gate != 1) return cmd_refuse("feet: air_gate is neither 0 nor 1");
+  if (c->observe != 0 && c->observe != 1) return cmd_refuse("feet: observe is neither 0 nor 1");
+  return HB_OK;
+}
+
+int hb_env_feet_configure(hb_batch* b, const hb_env_feet* cfg) {
+  g_cmd_error = "";
+  if (!b) return cmd_refuse("hb_env_feet_configure: NULL batch");
+  if (cfg && hb_env_feet_check(b->model, cfg) != HB_OK) return HB_EINVAL;
+  static_assert(sizeof(hb_env_feet) == sizeof(EnvFeet), "hb_env_feet and EnvFeet must have the same layout");
+  static_assert(HB_ENV_MAX_FEET == kMaxFeet && HB_ENV_MAX_CONTACT_BODIES == kMaxContactBodies, "hb.h and hb_device.hpp must agree on the list lengths");
+  const int was = feet_observed(b), now = cfg && cfg->observe ? cfg->n_feet : 0;
+  if (was != now && obs_consumers_exist(b))
+    return cmd_refuse("feet: the observation width would change while an actor, critic, Q network, normaliser or learner exists");
+  int rc = env_alloc(b);
+  if (rc != HB_OK) return rc;
+  HB_HIP(hipSetDevice(b->device));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));  // (a step still in flight reads the buffers that are replaced below)
+  if (!cfg) {
+    if ((rc = env_rows_resize(b, env_row_width(b, b->n_ext, b->d_cmd && b->cmd_cfg.observe, 0))) != HB_OK) return rc;
+    b->d_feet.reset();
+    memset(&b->feet_cfg, 0, sizeof b->feet_cfg);
+    return HB_OK;
+  }
+  DevBuf<FeetRec> rec;
+  const bool fresh = !b->d_feet;
+  if (fresh && rec.alloc((size_t)b->n_env, /*zero=*/true) != HB_OK) return HB_ENOMEM;
+  // the terms read the per-body read-out: switched on here, and its error passed on with nothing changed
+  const bool readout_was = b->contact_readout;
+  if (!readout_was && (rc = hb_contact_readout(b, 1)) != HB_OK) return rc;
+  if ((rc = env_rows_resize(b, env_row_width(b, b->n_ext, b->d_cmd && b->cmd_cfg.observe, now))) != HB_OK) {
+    if (!readout_was) hb_contact_readout(b, 0);
+    return rc;
+  }
+  memcpy(&b->feet_cfg, cfg, sizeof *cfg);
+  if (fresh) b->d_feet.swap(rec);
+  // an episode start for every env at once: the feet down at the time each env has now
+  HB_HIP(launch_feet_reset(b->d_feet, b->d_state, b->D.dm.nstate, b->feet_cfg.n_feet, nullptr, b->n_env, main_stream(b)));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  return HB_OK;
+}
+
+int hb_env_feet_count(hb_batch* b) { return b && b->d_feet ? b->feet_cfg.n_feet : 0; }
+
+int hb_env_get_feet(hb_batch* b, float* t_last, uint8_t* contact) {
+  g_cmd_error = "";
+  if (!b) return cmd_refuse("hb_env_get_feet: NULL batch");
+  if (!b->d_feet) return cmd_refuse("hb_env_get_feet: no feet configuration is installed");
+  HB_HIP(hipSetDevice(b->device));
+  std::vector<FeetRec> rec((size_t)b->n_env);
+  HB_HIP(hipMemcpyAsync(rec.data(), b->d_feet, rec.size() * sizeof(FeetRec), hipMemcpyDeviceToHost, main_stream(b)));
+  HB_HIP(hipStreamSynchronize(main_stream(b)));
+  const int nf = b->feet_cfg.n_feet;
+  for (int e = 0; e < b->n_env; e++)
+    for (int f = 0; f < nf; f++) {
+      if (t_last) t_last[(size_t)e * nf + f] = rec[e].t_last[f];
+      if (contact) contact[(size_t)e * nf + f] = (rec[e].mask >> f) & 1u;
+    }
   return HB_OK;
 }
 
@@ -491,6 +601,8 @@ int hb_env_reset(hb_batch* b, float* obs) {
   }
   // draw 0 of every env's command, with the episode numbers the envs ended up with
   if (b->d_cmd) HB_HIP(launch_command_reset(b->cmd_cfg, b->d_cmd, b->d_episode, nullptr, b->n_env, b->env_offset, main_stream(b)));
+  // the feet records of the episodes that begin: after the last settle step, with the time each env has then
+  if (b->d_feet) HB_HIP(launch_feet_reset(b->d_feet, b->d_state, b->D.dm.nstate, b->feet_cfg.n_feet, nullptr, b->n_env, main_stream(b)));
   // the observation the reference returns from reset(): one more pass through the noise and delay lines
   rc = env_eval(b, false, true, nullptr, b->d_obs, b->d_reward, b->d_term, b->d_trunc);
   if (rc != HB_OK) return rc;

@@ -23,6 +23,7 @@ struct hb_model {
 namespace hb {
 
 int refuse_with(const char* why);  // HB_EINVAL, with `why` (a string literal) left for hb_error() (hb_api_env.cpp)
+void refuse_clear();               // hb_error() reads "" again: at the entry of every function that may call refuse_with
 inline void set_err(char* err, int err_sz, const std::string& s) {
   if (err && err_sz > 0) { snprintf(err, err_sz, "%s", s.c_str()); }
 }
@@ -339,6 +340,10 @@ struct hb_batch {
   // none is installed; with cmd_cfg.observe the three entries are the last columns of a row: env_nobs = D.dm.nobs + n_ext + 3
   EnvCommands cmd_cfg = {};
   DevBuf<float4> d_cmd;
+  // foot-contact terms (hb_env_feet_configure): the configuration and every env's record, null while none is installed; with
+  // feet_cfg.observe the n_feet contact flags sit directly in front of the command: env_nobs = D.dm.nobs + n_ext + n_feet (+ 3)
+  EnvFeet feet_cfg = {};
+  DevBuf<FeetRec> d_feet;
   DevBuf<int> d_episode;
   int env_offset = 0;
   // realism layer (hb_env_randomize)

@@ -759,6 +759,36 @@ struct CmdArgs {
   EnvCommands C;
   int resample, obs_col;
 };
+// foot-contact terms (hb_env_feet_configure): the configuration (the layout of hb_env_feet), every env's record, and what the env kernel
+// is handed.  rec: [n_env] FeetRec - null: the feature is off and nothing else is read.  body_contact: the read-out [n_env][nbody][6]
+// of the last physics substep.  update: this launch is a step evaluation and writes the records (the switch of CmdArgs::resample).
+// obs_col: the column of the n_feet contact flags in an observation row, or -1 when they are not observed.
+constexpr int kMaxFeet = 4, kMaxContactBodies = 8;
+struct EnvFeet {
+  int n_feet, foot_body[kMaxFeet];
+  int n_penalised, penalised_body[kMaxContactBodies];
+  int n_terminal, terminal_body[kMaxContactBodies];
+  float contact_threshold;
+  float w_air_time, air_time_target;
+  int air_gate;
+  float air_cmd_min;
+  float w_force, force_max;
+  float w_stumble, stumble_ratio;
+  float w_collision;
+  int observe;
+};
+struct FeetRec {
+  float t_last[kMaxFeet];  // the env time at which foot f was last evaluated in contact
+  unsigned mask;           // bit f: foot f was in contact at the last step evaluation
+  unsigned pad[3];
+};
+static_assert(sizeof(FeetRec) == 32, "one 32-byte record per env");
+struct FeetArgs {
+  const float* body_contact;
+  FeetRec* rec;
+  EnvFeet F;
+  int update, obs_col;
+};
 constexpr int kAccPark = 24;  // floats per body in BatchPtrs::body_acc_park (six 16-byte moves)
 
 }  // namespace hb

@@ -480,6 +480,36 @@ __global__ void hb_command_reset_kernel(const EnvCommands C, float4* cmd, const 
   command_store(cmd + e, l, command_draw<kCmdLanes>(C, env_offset + e, episode[e], 0, l), 1);
 }
 
+// ---- foot-contact terms (hb_env_feet_configure; include/hb.h has the definitions, tests/feet_ref.py restates them) -------------------
+// |F|^2 of a body's read-out row, and the planar and the normal part it is made of: every product and sum rounded once, in the order
+// (Fx Fx + Fy Fy) + Fz Fz, so that the contact and stumble decisions are reproducible bit for bit
+__device__ __forceinline__ float contact_n2(const float* bc, int body, float& pl, float& zz) {
+  const float fx = bc[6 * body], fy = bc[6 * body + 1], fz = bc[6 * body + 2];
+  pl = __fadd_rn(__fmul_rn(fx, fx), __fmul_rn(fy, fy));
+  zz = __fmul_rn(fz, fz);
+  return __fadd_rn(pl, zz);
+}
+// The body lane l owns in a list of the configuration (-1: none).  The list's entries are compared and selected one by one: an
+// indexed read of the kernel argument would cost the env kernel a stack frame (see command_draw).
+template <int N>
+__device__ __forceinline__ int feet_pick(const int (&list)[N], int n, int l) {
+  int b = -1;
+#pragma unroll
+  for (int i = 0; i < N; i++) b = l == i ? list[i] : b;
+  return l < n ? b : -1;
+}
+// episode start outside the env kernel (hb_env_reset, hb_env_feet_configure): t_last = the env's state time, every foot's bit set
+__global__ void hb_feet_reset_kernel(FeetRec* rec, const float* state, int nstate, int n_feet, const uint8_t* mask, int n_env) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_env || (mask && !mask[e])) return;
+  const float t = state[(size_t)e * nstate];
+  FeetRec r;
+  for (int f = 0; f < kMaxFeet; f++) r.t_last[f] = t;
+  r.mask = (1u << n_feet) - 1u;
+  r.pad[0] = r.pad[1] = r.pad[2] = 0u;
+  rec[e] = r;
+}
+
 // standupReward (reward_functions.py:247-374) + observation + termination + auto-reset.  kEnvLanes lanes per env, 256 / kEnvLanes
 // envs per block (it was one thread per env: 37 us of serial work on 32 CUs for 4096 envs, a fifth of VecEnv.step_torch's GPU time).
 // The env's state record is staged in LDS (one coalesced pass instead of a strided read per thread); sums over joints, actuators
@@ -494,7 +524,7 @@ __device__ __forceinline__ float env_lane_sum(float x) {
 __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const EnvConfig cfg, const EnvRand R, const EnvRandState S, float* state, const float* qfrc, const int* counts,
                               float* prev, float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated,
                               uint8_t* truncated, const uint8_t* mask, int observe, const DomainRand D, float* dr, int dr_stride, int n_env, int env_offset, float* term_obs, int* seen,
-                              const ObsExtArgs X, const CmdArgs K) {
+                              const ObsExtArgs X, const CmdArgs K, const FeetArgs A) {
   extern __shared__ float sh_state[];
   const int grp = threadIdx.x / kEnvLanes, l = threadIdx.x % kEnvLanes;
   const int e = blockIdx.x * (256 / kEnvLanes) + grp;
@@ -505,6 +535,8 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
   if (active) for (int i = l; i < M.nstate; i += kEnvLanes) ls[i] = s[i];
   __syncthreads();
   bool reset = false;
+  float feet_t = 0.f;      // (feet, lane f < n_feet: the time foot f was last in contact, as this evaluation leaves it)
+  unsigned feet_mask = 0;  // (feet: the contact bits of this evaluation where it updates the record, else the record's)
   float cmd_l = 0.f;  // (commands: this lane's word of the env's record - lanes 0..2: a component of the command in force during the
                       // step that is rewarded here, lane 3: the draws made so far in the episode)
   if (active) {
@@ -585,6 +617,41 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     }
     if (cfg.w_vvel != 0.f) { const float vz = da >= 0 ? qvel[da + 2] : 0.f; r += cfg.w_vvel * scaled_exp(vz * vz); }  // vertical_velocity_penalty
     if (counts[kCountStride * e + 4]) r += cfg.self_collision_penalty;
+    bool feet_term = false;
+    if (A.rec) {
+      // lane f < n_feet owns foot f; lanes 0..7 a penalised body each, lanes 8..15 a terminal body each.  The flags travel as one
+      // small integer per lane - stumbles, collisions and terminal contacts counted in fields of four bits, the feet's contact bits
+      // above them -, exact in fp32, so that three lane sums serve every term.
+      const float* bc = A.body_contact + (size_t)e * M.nbody * 6;
+      const float thr2 = __fmul_rn(A.F.contact_threshold, A.F.contact_threshold);
+      const int fb = feet_pick(A.F.foot_body, A.F.n_feet, l);
+      const int pb = feet_pick(A.F.penalised_body, A.F.n_penalised, l);
+      const int tb = feet_pick(A.F.terminal_body, A.F.n_terminal, l - kMaxContactBodies);
+      const unsigned old_mask = A.rec[e].mask;
+      float air = 0.f, force = 0.f, pl, zz;
+      int flags = 0;
+      if (fb >= 0) {
+        const float tl = A.rec[e].t_last[l];
+        const float n2 = contact_n2(bc, fb, pl, zz);
+        const bool c = n2 > thr2;
+        if (c && !((old_mask >> l) & 1u)) air = __fsub_rn(ls[0], tl) - A.F.air_time_target;
+        force = fmaxf(sqrtf(n2) - A.F.force_max, 0.f);
+        if (c && pl > __fmul_rn(__fmul_rn(A.F.stumble_ratio, A.F.stumble_ratio), zz)) flags += 1;
+        if (c) flags += 4096 << l;
+        feet_t = c ? ls[0] : tl;
+      }
+      if (pb >= 0 && contact_n2(bc, pb, pl, zz) > thr2) flags += 16;
+      if (tb >= 0 && contact_n2(bc, tb, pl, zz) > thr2) flags += 256;
+      air = env_lane_sum(air); force = env_lane_sum(force);
+      flags = (int)env_lane_sum((float)flags);
+      const bool gate = !A.F.air_gate || __fadd_rn(__fmul_rn(tvx, tvx), __fmul_rn(tvy, tvy)) > __fmul_rn(A.F.air_cmd_min, A.F.air_cmd_min);
+      if (gate) r += A.F.w_air_time * air;
+      r += A.F.w_force * force;
+      if (flags & 15) r += A.F.w_stumble;
+      r += A.F.w_collision * (float)((flags >> 4) & 15);
+      feet_term = ((flags >> 8) & 15) != 0;
+      feet_mask = A.update ? (unsigned)flags >> 12 : old_mask;
+    }
     const bool upright = fmaxf(fabsf(g[0]), fabsf(g[1])) < cfg.upright_tol;
     const bool timeup = cfg.max_time > 0.f && ls[0] >= cfg.max_time;
     bool term, trunc;
@@ -595,6 +662,7 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
       term = timeup;
       trunc = z >= cfg.target_z && upright;
     }
+    term = term || feet_term;
     if (term) r = cfg.terminal_reward;
     if (l == 0) { reward[e] = r; terminated[e] = term ? 1 : 0; truncated[e] = trunc ? 1 : 0; }
     reset = (term || trunc) && cfg.auto_reset;
@@ -612,6 +680,7 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     for (int i = l; i < X.n_act; i += kEnvLanes) to[M.nobs + i] = latest[(size_t)e * M.nu + i];
     for (int i = l; i < X.n_scan; i += kEnvLanes) to[M.nobs + X.n_act + i] = X.scan[(size_t)e * X.n_scan + i];
     if (K.cmd && K.obs_col >= 0) for (int i = l; i < 3; i += kEnvLanes) to[K.obs_col + i] = cmd_l;  // (the old command)
+    if (A.rec && A.obs_col >= 0 && l < A.F.n_feet) to[A.obs_col + l] = (feet_mask >> l) & 1u ? 1.f : 0.f;  // (the ending state's flags)
   }
   __syncthreads();  // (every lane has read the old state and the old episode number)
   if (reset) {
@@ -648,6 +717,15 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     for (int i = l; i < X.n_act; i += kEnvLanes) o[M.nobs + i] = latest[(size_t)e * M.nu + i];
     if (!reset) for (int i = l; i < X.n_scan; i += kEnvLanes) o[M.nobs + X.n_act + i] = X.scan[(size_t)e * X.n_scan + i];
     if (K.cmd && K.obs_col >= 0) for (int i = l; i < 3; i += kEnvLanes) o[K.obs_col + i] = cmd_l;  // (no noise, no delay)
+    if (A.rec) {
+      // an episode that begins here starts with its feet down at the new state's time: a standing start pays nothing
+      if (reset) { feet_t = ls[0]; feet_mask = (1u << A.F.n_feet) - 1u; }
+      if (A.update) {
+        if (l < A.F.n_feet) A.rec[e].t_last[l] = feet_t;
+        if (l == 0) A.rec[e].mask = feet_mask;
+      }
+      if (A.obs_col >= 0 && l < A.F.n_feet) o[A.obs_col + l] = (feet_mask >> l) & 1u ? 1.f : 0.f;  // (no noise, no delay)
+    }
   }
   if (X.reset_flag && e < n_env && l == 0) X.reset_flag[e] = reset ? 1 : 0;
 }
@@ -803,13 +881,19 @@ hipError_t launch_action(const float* action, float* prev, float* latest, float*
 hipError_t launch_env(const DevModel& M, const EnvConfig& cfg, const EnvRand& R, const EnvRandState& S, float* state, const float* qfrc, const int* counts, float* prev,
                       float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated,
                       const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs, int* seen,
-                      const ObsExtArgs* ext, const CmdArgs* cmd) {
+                      const ObsExtArgs* ext, const CmdArgs* cmd, const FeetArgs* feet) {
   (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
   const int per_block = 256 / kEnvLanes;
   const CmdArgs K = cmd ? *cmd : CmdArgs{};  // (none: a null record, and nothing else is read)
+  const FeetArgs A = feet ? *feet : FeetArgs{};  // (the same)
   const ObsExtArgs X = ext ? *ext : ObsExtArgs{M.nobs, 0, 0, nullptr, nullptr};  // (none: rows of the base observation alone)
   hipLaunchKernelGGL(hb_env_kernel, dim3((n_env + per_block - 1) / per_block), dim3(256), (size_t)per_block * ((M.nstate + 3) & ~3) * sizeof(float), stream, M, cfg, R, S, state, qfrc, counts, prev, latest, qpos_src, episode, status, obs,
-                     reward, terminated, truncated, mask, observe, D, dr, dr_stride, n_env, env_offset, term_obs, seen, X, K);
+                     reward, terminated, truncated, mask, observe, D, dr, dr_stride, n_env, env_offset, term_obs, seen, X, K, A);
+  return hipGetLastError();
+}
+hipError_t launch_feet_reset(FeetRec* rec, const float* state, int nstate, int n_feet, const uint8_t* mask, int n_env, hipStream_t stream) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(hb_feet_reset_kernel, dim3((n_env + 255) / 256), dim3(256), 0, stream, rec, state, nstate, n_feet, mask, n_env);
   return hipGetLastError();
 }
 hipError_t launch_command_reset(const EnvCommands& C, float4* cmd, const int* episode, const uint8_t* mask, int n_env, int env_offset, hipStream_t stream) {

@@ -56,7 +56,10 @@ hipError_t launch_env(const DevModel& M, const EnvConfig& cfg, const EnvRand& R,
                       float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated,
                       const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs = nullptr, int* seen = nullptr,
                       const ObsExtArgs* ext = nullptr,   // ext null: rows of M.nobs floats, the base observation alone
-                      const CmdArgs* cmd = nullptr);     // cmd null: no velocity commands
+                      const CmdArgs* cmd = nullptr,      // cmd null: no velocity commands
+                      const FeetArgs* feet = nullptr);   // feet null: no foot-contact terms
+// the feet records at an episode start outside the env kernel: t_last = the env's state time, every foot's bit set
+hipError_t launch_feet_reset(FeetRec* rec, const float* state, int nstate, int n_feet, const uint8_t* mask, int n_env, hipStream_t stream);
 // draw 0 of the episodes in `episode` for every env (or those of `mask`): the command state at an episode start outside the env kernel
 hipError_t launch_command_reset(const EnvCommands& C, float4* cmd, const int* episode, const uint8_t* mask, int n_env, int env_offset, hipStream_t stream);
 hipError_t launch_domain_rand(const DevModel& M, const DomainRand& D, float* dr, int stride, const int* episode, const uint8_t* mask, int n_env, int env_offset,

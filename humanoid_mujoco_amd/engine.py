@@ -54,6 +54,29 @@ class HbEnvCommands(ctypes.Structure):
                                                                            "zero_fraction", "w_yaw")] + [("frame", ctypes.c_int), ("observe", ctypes.c_int)]
 
 
+class HbEnvFeet(ctypes.Structure):
+    """hb_env_feet (include/hb.h): foot-contact terms of the env adapter - the bodies, the contact threshold, the weights, observation."""
+    _fields_ = [("n_feet", ctypes.c_int), ("foot_body", ctypes.c_int * 4), ("n_penalised", ctypes.c_int), ("penalised_body", ctypes.c_int * 8),
+                ("n_terminal", ctypes.c_int), ("terminal_body", ctypes.c_int * 8), ("contact_threshold", ctypes.c_float),
+                ("w_air_time", ctypes.c_float), ("air_time_target", ctypes.c_float), ("air_gate", ctypes.c_int), ("air_cmd_min", ctypes.c_float),
+                ("w_force", ctypes.c_float), ("force_max", ctypes.c_float), ("w_stumble", ctypes.c_float), ("stumble_ratio", ctypes.c_float),
+                ("w_collision", ctypes.c_float), ("observe", ctypes.c_int)]
+
+    def set_bodies(self, bodies=None, penalised=None, terminal=None):
+        """fills the three body lists (ids; None leaves a list as it is) and their counts"""
+        for ids, count, field, cap in ((bodies, "n_feet", "foot_body", 4), (penalised, "n_penalised", "penalised_body", 8), (terminal, "n_terminal", "terminal_body", 8)):
+            if ids is None:
+                continue
+            ids = [int(i) for i in ids]
+            if len(ids) > cap:
+                raise ValueError("feet: %s holds at most %d bodies" % (field, cap))
+            setattr(self, count, len(ids))
+            arr = getattr(self, field)
+            for i in range(cap):
+                arr[i] = ids[i] if i < len(ids) else 0
+        return self
+
+
 class HbRaySpec(ctypes.Structure):
     """hb_ray_spec (include/hb.h): frame, eligible geoms and cutoff of the installed rays."""
     _fields_ = [("frame", ctypes.c_int), ("frame_body", ctypes.c_int), ("bodyexclude", ctypes.c_int), ("flags", ctypes.c_int), ("cutoff", ctypes.c_float)]
@@ -413,6 +436,11 @@ def lib():
     L.hb_env_commands_configure.argtypes = [vp, ctypes.POINTER(HbEnvCommands)]
     L.hb_env_get_commands.argtypes = [vp, vp]
     L.hb_env_set_commands.argtypes = [vp, vp, vp]
+    L.hb_env_default_feet.argtypes = [vp, ctypes.POINTER(HbEnvFeet)]
+    L.hb_env_feet_check.argtypes = [vp, ctypes.POINTER(HbEnvFeet)]
+    L.hb_env_feet_configure.argtypes = [vp, ctypes.POINTER(HbEnvFeet)]
+    L.hb_env_get_feet.argtypes = [vp, vp, vp]
+    L.hb_env_feet_count.argtypes = [vp]
     L.hb_error.argtypes = []
     L.hb_error.restype = ctypes.c_char_p
     L.hb_policy_set_mlp.argtypes = [vp, ci, vp, vp, vp]
@@ -1014,7 +1042,8 @@ class Batch:
     # ---- contact forces (mj_contactForce, cfrc_ext without xfrc_applied; include/hb.h)
     def contact_readout(self, on=True):
         """From the next launch on, steps write every contact's force and every body's contact wrench (full step kernels only)."""
-        _check(lib().hb_contact_readout(self._h, int(on)), "hb_contact_readout")
+        rc = lib().hb_contact_readout(self._h, int(on))
+        _check(rc, "hb_contact_readout", lib().hb_error().decode() if rc == -1 else None)
 
     def contact_force(self):
         """[n_env, ncon_max, 6]: contact-frame force and torque of contact k of contacts(); zeros beyond the env's ncon."""
@@ -1352,6 +1381,43 @@ class Batch:
             raise ValueError("set_commands: mask must be [n_env]")
         rc = lib().hb_env_set_commands(self._h, _ptr(c), _ptr(m))
         _check(rc, "hb_env_set_commands", lib().hb_error().decode() if rc == -1 else None)
+
+    def default_feet(self):
+        """hb_env_default_feet: an HbEnvFeet to edit (set_bodies names the bodies) and hand to feet_configure"""
+        c = HbEnvFeet()
+        _check(lib().hb_env_default_feet(self.model._h, ctypes.byref(c)), "hb_env_default_feet")
+        return c
+
+    def feet_configure(self, cfg=None, **kw):
+        """Foot-contact terms in the env kernel (hb_env_feet_configure): feet_configure(bodies=(7, 10), penalised=(...), terminal=(...),
+        w_air_time=..., observe=1, ...) installs the defaults of hb_env_default_feet with the given fields replaced (or an HbEnvFeet as
+        it is); feet_configure(None) with no fields removes them.  Bodies are ids.  Every env then earns the air-time term at a touchdown,
+        pays for impacts, stumbles and contacts of the penalised bodies, and its episode ends when a terminal body touches anything; with
+        observe the n_feet contact flags sit in front of the command in every row (env_nobs grows by n_feet: call it before anything
+        sized by the observation is installed).  The contact read-out is switched on.  A call that is refused (HbError, with the
+        library's reason) changes nothing."""
+        if cfg is None and kw:
+            cfg = self.default_feet()
+        lists = {k: kw.pop(k) for k in ("bodies", "penalised", "terminal") if k in kw}
+        if lists:
+            cfg.set_bodies(**lists)
+        for k, v in kw.items():
+            if not hasattr(cfg, k) or k.endswith("_body"):
+                raise TypeError("feet_configure: unknown field %r" % k)
+            setattr(cfg, k, v)
+        rc = lib().hb_env_feet_configure(self._h, ctypes.byref(cfg) if cfg is not None else None)
+        _check(rc, "hb_env_feet_configure", lib().hb_error().decode() if rc == -1 else None)
+        self._env_pin = None  # (the transfer record of env_step has rows of the old width)
+
+    def feet(self):
+        """(t_last [n_env, n_feet] float32, contact [n_env, n_feet] uint8): the env time each foot was last evaluated in contact and the
+        contact bits of the last step evaluation, behind the enqueued work (hb_env_get_feet)"""
+        nf = int(lib().hb_env_feet_count(self._h))  # (the library's own count: the arrays below are never smaller than what it writes)
+        t = np.zeros((self.n_env, nf), dtype=np.float32)
+        c = np.zeros((self.n_env, nf), dtype=np.uint8)
+        rc = lib().hb_env_get_feet(self._h, _ptr(t), _ptr(c))
+        _check(rc, "hb_env_get_feet", lib().hb_error().decode() if rc == -1 else None)
+        return t, c
 
     def env_reset(self):
         o = np.zeros((self.n_env, self.env_nobs), dtype=np.float32)

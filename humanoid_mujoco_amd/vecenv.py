@@ -17,7 +17,7 @@ arrays) for callers that do not want N dicts per step; ``step_torch`` keeps ever
 """
 import numpy as np
 
-from .engine import WARN_BADQACC, WARN_BADQPOS, WARN_BADQVEL, WARN_CNSTRFULL, WARN_CONTACTFULL, Batch, Model, height_scan_rays
+from .engine import STATE_TIME, WARN_BADQACC, WARN_BADQPOS, WARN_BADQVEL, WARN_CNSTRFULL, WARN_CONTACTFULL, Batch, Model, height_scan_rays
 
 
 class Box:
@@ -50,7 +50,7 @@ _NO_INFO = {}  # (shared by the envs that did not finish an episode this step: S
 
 class VecEnv:
     def __init__(self, model, n_envs, device=0, n_substeps=1, randomization_factor=1.0, realism=False, domain_randomization=False, seed=0, team=False,
-                 contact_forces=False, body_accelerations=False, height_scan=None, normalize=None, obs_extend=None, commands=None, box_manifold=False, **reward_overrides):
+                 contact_forces=False, body_accelerations=False, height_scan=None, normalize=None, obs_extend=None, commands=None, box_manifold=False, feet=None, **reward_overrides):
         """realism=True adds CPUEnv's sensor/action noise, delay FIFOs and pushes (hb_env_randomization), scaled by
         randomization_factor exactly like the reset perturbation; domain_randomization=True draws per-env masses, floor
         friction, joint and actuator parameters at every reset (hb_domain_randomization).  team=True: the reference's own
@@ -73,6 +73,13 @@ class VecEnv:
         resample_time seconds, rewarded by the linear and the yaw term (target_velocity is ignored) and - with observe - seen as the
         last three entries of every row, behind the extension: obs_layout()["command"]; commands() and set_commands() read and override
         them.  set_attr("randomization_factor", ...) does NOT scale the command ranges: they are the task, not a disturbance.
+        feet=dict(bodies=("foot_right", "foot_left"), penalised=(...), terminal=(...), contact_threshold=..., w_air_time=...,
+        air_time_target=..., air_gate=1, air_cmd_min=..., w_force=..., force_max=..., w_stumble=..., stumble_ratio=..., w_collision=...,
+        observe=1) (bodies by name or id; the rest any subset of hb_env_feet, defaults of hb_env_default_feet): the foot-contact terms of
+        the env kernel (hb_env_feet_configure) - an air-time reward paid at touchdown, penalties on hard impacts, on stumbling and on
+        contacts of the penalised bodies, the end of the episode when a terminal body touches anything - read from the contact read-out on
+        the device (contact_forces is switched on); with observe the n_feet contact flags sit directly in front of the command:
+        obs_layout()["foot_contact"]; foot_contacts() and foot_air_time() read the state.
         normalize=dict(norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0, gamma=0.99, epsilon=1e-8) (any subset; {} for the
         defaults): stable-baselines3's VecNormalize over a VecMonitor on the device (hb_norm_*): reset, step*, step_torch and collect*
         return normalised observations and rewards, finished envs' infos carry "episode": {"r", "l"} and a normalised
@@ -135,6 +142,22 @@ class VecEnv:
                     raise TypeError("commands: unknown option %r" % k)
                 setattr(self.commands_cfg, k, v)
             self.batch.commands_configure(self.commands_cfg)
+        # foot-contact terms: with observe they widen the row as well
+        self.feet_cfg = None
+        if feet is not None:
+            opts = dict(feet)
+            self.feet_cfg = self.batch.default_feet()
+            ids = {k: [self.model.name2id("body", b) if isinstance(b, str) else int(b) for b in opts.pop(k)]
+                   for k in ("bodies", "penalised", "terminal") if k in opts}
+            if any(i < 0 for v in ids.values() for i in v):
+                raise ValueError("feet: a body name is not in the model")
+            self.feet_cfg.set_bodies(**ids)
+            for k, v in opts.items():
+                if not hasattr(self.feet_cfg, k) or k.endswith("_body"):
+                    raise TypeError("feet: unknown option %r" % k)
+                setattr(self.feet_cfg, k, v)
+            self.batch.feet_configure(self.feet_cfg)
+            self.contact_forces = True  # (the terms read the contact read-out, so body_contact_forces() is there too)
         self.nobs = self.batch.env_nobs
         self._layout = {"base": slice(0, self.model.nobs)}
         if ext_act:
@@ -143,7 +166,10 @@ class VecEnv:
             n_scan = self._scan[0] * self._scan[1]
             at = self.model.nobs + (self.model.nu if ext_act else 0)
             self._layout["height_scan"] = slice(at, at + n_scan)
-        if self.commands_cfg is not None and self.commands_cfg.observe:
+        n_cmd = 3 if self.commands_cfg is not None and self.commands_cfg.observe else 0
+        if self.feet_cfg is not None and self.feet_cfg.observe:
+            self._layout["foot_contact"] = slice(self.nobs - n_cmd - self.feet_cfg.n_feet, self.nobs - n_cmd)
+        if n_cmd:
             self._layout["command"] = slice(self.nobs - 3, self.nobs)
         self.realism = None
         if realism:
@@ -182,9 +208,23 @@ class VecEnv:
 
     def obs_layout(self):
         """the columns of an observation row as slices: "base" (the model's nobs entries), and with obs_extend "prev_action" (nu) and
-        "height_scan" (len(ys) * len(xs) entries, row-major over ys then xs like height_scan()), and with observed commands "command"
-        (vx, vy, yaw rate: the last three entries)"""
+        "height_scan" (len(ys) * len(xs) entries, row-major over ys then xs like height_scan()), with observed feet "foot_contact" (n_feet
+        flags, 0 or 1, directly in front of the command) and with observed commands "command" (vx, vy, yaw rate: the last three entries)"""
         return dict(self._layout)
+
+    def _need_feet(self, what):
+        if self.feet_cfg is None:
+            raise RuntimeError("%s: create the VecEnv with feet=dict(bodies=...)" % what)
+
+    def foot_contacts(self):
+        """[num_envs, n_feet] bool: the feet in contact at the last step evaluation (ones at an episode start; Batch.feet)"""
+        self._need_feet("foot_contacts")
+        return self.batch.feet()[1].astype(bool)
+
+    def foot_air_time(self):
+        """[num_envs, n_feet] float32: the state time minus the time each foot was last evaluated in contact (0 while it stands)"""
+        self._need_feet("foot_air_time")
+        return self.batch.get_state(STATE_TIME).reshape(-1, 1) - self.batch.feet()[0]
 
     def commands(self):
         """[num_envs, 3] float32: every env's current (vx, vy, yaw rate) command (Batch.commands)"""

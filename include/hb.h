@@ -906,6 +906,81 @@ int hb_env_set_commands(hb_batch* b, const float* cmd, const uint8_t* mask); /* 
  * next such call. */
 const char* hb_error(void);
 
+/* ---- foot-contact terms: air time, impacts, stumbles, collisions and contact resets, computed in the env kernel ------------------ */
+
+/* With a configuration installed the env kernel reads the per-body contact read-out (hb_contact_readout, which the configure call
+ * switches on; hb_contact_readout(b, 0) is then refused with HB_EINVAL and a reason in hb_error()) and every env owns one 32-byte
+ * record in a device buffer of the batch: t_last[4] (fp32, the env time at which foot f was last evaluated in contact), a mask word
+ * (bit f: foot f was in contact at the last step evaluation) and padding.
+ * Below, "one rounding" means a single fp32 multiply, add or subtract with no fused multiply-add, so that every discrete decision is
+ * reproducible bit for bit in numpy float32 (tests/feet_ref.py restates all of this).  F = the first three entries of the body's
+ * hb_get_body_contact row, the read-out of the last physics substep; t = the env's fp32 state time at the evaluation, before any reset.
+ *   in contact   n2 = (Fx*Fx + Fy*Fy) + Fz*Fz, each operation one rounding, in that order; c = n2 > thr*thr (thr = contact_threshold, the
+ *                product one rounding).  The same test serves feet, penalised bodies and terminal bodies.
+ *   air time     air_f = t - t_last[f] (one rounding); touchdown_f = c_f && !(mask bit f).  The term is
+ *                w_air_time * gate * sum_f (touchdown_f ? air_f - air_time_target : 0).  gate = 1 when air_gate == 0; otherwise
+ *                gate = (cx*cx + cy*cy > air_cmd_min*air_cmd_min), each operation one rounding, on the command in force during the step
+ *                (hb_env_commands), or on hb_env_config.target_velocity when no commands are installed.
+ *   impact       w_force * sum_f max(sqrt(n2_f) - force_max, 0), over all feet.
+ *   stumble      s_f = c_f && (Fx*Fx + Fy*Fy) > (ratio*ratio) * (Fz*Fz), each product and sum one rounding (ratio = stumble_ratio).
+ *                The term is w_stumble, once, if any s_f.
+ *   collision    w_collision * the number of penalised bodies in contact.
+ *   termination  any terminal body in contact: terminated = 1 under both reward_kinds.  It is OR-ed into the termination of
+ *                hb_env_config before the terminal reward replaces the step's reward, so terminal_reward and auto_reset act as for
+ *                any other termination.
+ *   The four terms are ADDED to the reward: penalties carry negative weights.
+ *   update       Step evaluations only - the env kernel of hb_env_step* / hb_env_collect*, the evaluations that may reset and that may
+ *                redraw a command: t_last[f] = c_f ? t : t_last[f]; the mask becomes the c_f bits.  hb_get_obs, the settle steps and
+ *                the final observation of hb_env_reset compute the terms but never write the record.  They do compute them: with
+ *                reset_collision_mode != 0 a settle step that ends with a terminal body in contact counts as ending in a terminal
+ *                state, and hb_env_reset draws that env again - with a foot among the terminal bodies every standing start is
+ *                redrawn for all eight attempts, so keep the feet out of terminal_body when that mode is on.  The final observation
+ *                of hb_env_reset evaluates the terms on the read-out of whatever physics step ran last (a settle step, or the last
+ *                step before the reset when there is none); its reward and flags are not returned.
+ *   episode      At an episode start t_last[f] = the new state's time and all n_feet mask bits are set, so a standing start pays
+ *   start        nothing for the first touchdown: at an auto-reset inside the env kernel; in hb_env_reset by one small launch after the
+ *                last settle step, with the time each env has then; in hb_env_feet_configure for every env at once.
+ *   observe      1: every row the adapter writes becomes [ base | prev_action | scan | foot_contact(n_feet) | command(3) ] - the
+ *                command stays last - and hb_env_nobs grows by n_feet.  The entries are the record's mask after the evaluation's update
+ *                (a looking evaluation: the record's mask as it is), as 0.f / 1.f, with NO noise and NO delay.  The terminal observation
+ *                carries the flags of the state the episode ended in, the first row of the new episode carries ones.  Producers and
+ *                consumers are those hb_env_obs_extend lists, and its rule holds: a call that would change the width (observe 0 <-> 1,
+ *                another n_feet while observed, a removal with observe on) while an actor, critic, Q network, normaliser or learner
+ *                exists is refused.
+ * Envs outside a launch's mask keep record, reward and rows.  Without a configuration the adapter makes exactly the launches it made
+ * before and gives the same bits; with one a step makes the same number of launches, and hb_env_reset one small launch more.  No atomics.
+ * A batch with feet steps in the full step kernel, as any batch with the contact read-out does (profiles/contact_readout_bench.txt).
+ * Not provided: foot slip (it needs body velocities: a kinematics launch per step), contact filtering over several steps, per-foot
+ * weights.
+ * Refusals, all HB_EINVAL, each leaving everything as it was and its reason in hb_error(): a NULL batch; n_feet outside 1..4,
+ * n_penalised or n_terminal outside 0..8; a body id outside 1..nbody-1; a body named twice in foot_body; a non-finite field;
+ * contact_threshold <= 0; air_cmd_min < 0; stumble_ratio < 0; air_gate or observe other than 0 or 1; the width rule above;
+ * hb_env_get_feet with nothing installed.  If the read-out cannot be had for the batch, that error is passed on and nothing changes. */
+#define HB_ENV_MAX_FEET 4
+#define HB_ENV_MAX_CONTACT_BODIES 8
+typedef struct hb_env_feet {
+  int   n_feet;       int foot_body[HB_ENV_MAX_FEET];                      /* body ids, 1 <= n_feet <= 4 */
+  int   n_penalised;  int penalised_body[HB_ENV_MAX_CONTACT_BODIES];       /* a contact costs w_collision each */
+  int   n_terminal;   int terminal_body[HB_ENV_MAX_CONTACT_BODIES];        /* a contact ends the episode */
+  float contact_threshold;   /* N: a body is "in contact" when |F| of its hb_get_body_contact row exceeds it (> 0) */
+  float w_air_time, air_time_target;  /* s */
+  int   air_gate;  float air_cmd_min;   /* 1: the air-time term counts only while the commanded planar speed > air_cmd_min (>= 0) */
+  float w_force, force_max;  /* N */
+  float w_stumble, stumble_ratio;
+  float w_collision;
+  int   observe;             /* 1: append n_feet contact flags (0.f / 1.f) to every row the adapter writes */
+} hb_env_feet;
+/* n_feet 0 and empty lists - the caller names the bodies -, threshold 1 N, w_air_time 1 with a target of 0.5 s, the gate on at 0.1 m/s,
+ * w_force -0.01 per N above force_max = 2 x the model's weight (total mass x |gravity|), w_stumble -1 at a ratio of 5, w_collision -1,
+ * observe 0.  HB_EINVAL: NULL argument. */
+int hb_env_default_feet(const hb_model* m, hb_env_feet* out);
+/* The checks of hb_env_feet_configure that need no batch: counts, body ids and fields.  HB_OK or HB_EINVAL with hb_error(). */
+int hb_env_feet_check(const hb_model* m, const hb_env_feet* cfg);
+int hb_env_feet_configure(hb_batch* b, const hb_env_feet* cfg);    /* NULL: remove (the read-out stays on) */
+int hb_env_feet_count(hb_batch* b);                                /* n_feet of the installed configuration; 0: none (or a NULL batch) */
+/* host [n_env][n_feet] each (n_feet: hb_env_feet_count), either nullable, behind the enqueued work: the records' t_last and contact bits (0 / 1) */
+int hb_env_get_feet(hb_batch* b, float* t_last, uint8_t* contact);
+
 /* ---- policy in the loop (BASELINE.json configs[3]: MLP policy inference fused into the rollout loop) ---------- */
 
 /* Installs an MLP policy obs[nobs] -> sizes[1] -> ... -> sizes[n_layers] == nu with tanh after every layer (hidden
