@@ -2,8 +2,8 @@
 HIPCC ?= hipcc
 ARCH ?= gfx950
 CSRC := humanoid_mujoco_amd/csrc
-HOST_SRCS := $(CSRC)/hb_api.cpp $(CSRC)/hb_api_rollout.cpp $(CSRC)/hb_api_env.cpp $(CSRC)/hb_api_dyn.cpp $(CSRC)/hb_api_ppo.cpp $(CSRC)/hb_api_sac.cpp $(CSRC)/hb_learn_host.cpp $(CSRC)/hb_batch.cpp $(CSRC)/hb_tables.cpp $(CSRC)/mjcf.cpp $(CSRC)/setconst.cpp $(CSRC)/model_io.cpp $(CSRC)/mesh.cpp
-HIP_SRCS := $(CSRC)/hb_step.hip $(CSRC)/hb_step_duo.hip $(CSRC)/hb_narrow.hip $(CSRC)/hb_env.hip $(CSRC)/hb_actor.hip $(CSRC)/hb_gae.hip $(CSRC)/hb_norm.hip $(CSRC)/hb_ppo.hip $(CSRC)/hb_sac.hip $(CSRC)/hb_kin.hip $(CSRC)/hb_ray.hip $(CSRC)/hb_dyn.hip
+HOST_SRCS := $(CSRC)/hb_api.cpp $(CSRC)/hb_api_rollout.cpp $(CSRC)/hb_api_env.cpp $(CSRC)/hb_api_policy.cpp $(CSRC)/hb_api_collect.cpp $(CSRC)/hb_api_dyn.cpp $(CSRC)/hb_api_ppo.cpp $(CSRC)/hb_api_sac.cpp $(CSRC)/hb_learn_host.cpp $(CSRC)/hb_batch.cpp $(CSRC)/hb_tables.cpp $(CSRC)/mjcf.cpp $(CSRC)/setconst.cpp $(CSRC)/model_io.cpp $(CSRC)/mesh.cpp
+HIP_SRCS := $(CSRC)/hb_step.hip $(CSRC)/hb_step_duo.hip $(CSRC)/hb_narrow.hip $(CSRC)/hb_env.hip $(CSRC)/hb_rollout.hip $(CSRC)/hb_policy.hip $(CSRC)/hb_actor.hip $(CSRC)/hb_gae.hip $(CSRC)/hb_norm.hip $(CSRC)/hb_ppo.hip $(CSRC)/hb_sac.hip $(CSRC)/hb_kin.hip $(CSRC)/hb_ray.hip $(CSRC)/hb_dyn.hip
 HDRS := $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inl) include/hb.h
 LIB := humanoid_mujoco_amd/libhb.so
 FLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result -ffp-contract=on -fno-slp-vectorize -fno-vectorize $(EXTRA)

@@ -1,5 +1,5 @@
 // hb_actor.hip - the sampling actor of hb_env_collect_dev: observation rows -> MLP -> head (deterministic / Gaussian / squashed Gaussian)
-// -> action and the tapes of what was drawn, one launch per env step.  A translation unit of its own: the kernels of hb_env.hip compile
+// -> action and the tapes of what was drawn, one launch per env step.  A translation unit of its own: the kernels of hb_env.hip and hb_policy.hip compile
 // exactly as they did without it.
 #include <hip/hip_runtime.h>
 #include "hb_kcommon.hpp"
@@ -7,7 +7,7 @@
 
 namespace hb {
 
-// hb_policy_kernel's design (hb_env.hip): 16 envs per block, activations ping-pong between two LDS tiles of 16 rows, eight waves share the
+// hb_policy_kernel's design (hb_policy.hip): 16 envs per block, activations ping-pong between two LDS tiles of 16 rows, eight waves share the
 // 16-column output tiles of a layer, each sweeping K four columns per v_mfma_f32_16x16x4_f32 (exact f32) with the A operand from LDS and
 // the B operand from weights the host packed in operand order (wp[tile][k/4][lane] = W[4(k/4) + lane/16][16 tile + lane%16], one coalesced
 // 256-byte wave load per MFMA); a layer with fewer than eight tiles splits K across the idle waves and the partial tiles are summed in a

@@ -1,7 +1,8 @@
 // hb_api.cpp — the C-ABI of libhb.so (include/hb.h), first part: model handles, the batch lifecycle and pipeline, reset / step / forward /
 // inverse / kinematics, status, counts and read-outs, memory helpers and timing.  Rollouts and tasks are in hb_api_rollout.cpp, the env
-// adapter and the policy in hb_api_env.cpp; the device model tables in hb_tables.cpp and the launch plumbing around the kernel
-// translation units (hb_step.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip) in hb_batch.cpp.
+// adapter in hb_api_env.cpp, the policy in hb_api_policy.cpp, the collection loop in hb_api_collect.cpp; the device model tables in
+// hb_tables.cpp and the launch plumbing around the kernel translation units (hb_step.hip, hb_narrow.hip, hb_env.hip, hb_rollout.hip, hb_kin.hip) in
+// hb_batch.cpp.
 //
 // Host C++ only; no PyTorch.  One hb_batch owns one HIP stream and all device memory of its
 // envs; the model is immutable and shareable (reference ownership rules: SURVEY.md §8b).
@@ -156,7 +157,7 @@ hb_batch* hb_batch_create(const hb_model* m, int n_env, int device, char* err, i
   std::string e;
   if (!build_device_model(m->m, b->D, e)) { set_err(err, err_sz, e); delete b; return nullptr; }
   const DevModel& dm = b->D.dm;
-  b->env_nobs = dm.nobs;  // (until hb_env_obs_extend widens the adapter's rows)
+  b->row = env_row(dm.nobs, 0, 0, 0, false);  // (until hb_env_obs_extend and the observed features widen the adapter's rows)
   bool ok = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming) == hipSuccess;
   // (the pipes' streams are created when hb_batch_pipeline asks for them: the runtime maps streams
@@ -500,12 +501,12 @@ int hb_rays_dev(hb_batch* b, float* dist_dev, int* geomid_dev) {
 }
 extern "C++" {
 namespace hb {
-int rays_scan_launch(hb_batch* b, const uint8_t* mask, float* out, int stride, int col) {
+int rays_scan_launch(hb_batch* b, const uint8_t* mask, float* rows) {
   if (b->n_ray < 1 || !b->obs_ext.height_scan) return HB_EINVAL;
   RayArgs A;
   memset(&A, 0, sizeof A);
-  A.dist = out; A.env_mask = mask;
-  A.xform = 1; A.out_stride = stride; A.out_col = col;
+  A.dist = rows ? rows : b->d_ext_scan.get(); A.env_mask = mask;
+  A.xform = 1; A.out_stride = rows ? b->row.width : b->n_ray; A.out_col = rows ? b->row.scan : 0;
   A.x_offset = b->obs_ext.scan_offset; A.x_scale = b->obs_ext.scan_scale; A.x_lo = b->obs_ext.scan_lo; A.x_hi = b->obs_ext.scan_hi;
   const char* name = b->last_kernel;  // (hb_last_kernel goes on naming the step kernel of the env step this is part of)
   const int rc = rays_launch(b, A);

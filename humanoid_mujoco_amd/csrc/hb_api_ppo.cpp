@@ -185,7 +185,7 @@ int hb_ppo_grad_dev(hb_batch* b, const hb_ppo_rows* rows, float* stats_dev) {
   Learner& L = b->learner;
   HB_HIP(hipSetDevice(b->device));
   hipStream_t st = main_stream(b);
-  const size_t mb = rows->mb, nu = b->D.dm.nu, nobs = b->env_nobs;
+  const size_t mb = rows->mb, nu = b->D.dm.nu, nobs = b->row.width;
   const int chunk = ppo_row_chunk(rows->mb), nchunk = (rows->mb + chunk - 1) / chunk;
   const LearnNets ns = nets_of(b);
   PpoDesc d;

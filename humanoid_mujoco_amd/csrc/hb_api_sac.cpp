@@ -6,7 +6,7 @@ namespace {
 
 // the networks of the flat record: the actor, Q1, Q2; layer 0 of a Q network has the transpose of its action rows (dQ / da)
 LearnNets nets_of(const hb_batch* b) {
-  const int nobs = b->env_nobs;
+  const int nobs = b->row.width;
   return LearnNets{3, {&b->actor, &b->q[0], &b->q[1]}, {-1, nobs, nobs}};
 }
 // the same with the targets in the Q networks' places (their tensors stand where their Q network's do)
@@ -56,7 +56,7 @@ extern "C" {
 
 int hb_q_set_mlp(hb_batch* b, int k, int n_layers, const int* sizes, const float* const* weights, const float* const* biases) {
   if (!b || k < 0 || k > 1 || !mlp_args_ok(n_layers, sizes, weights, biases)) return HB_EINVAL;
-  if (sizes[0] != b->env_nobs + b->D.dm.nu || sizes[n_layers] != 1) return HB_EINVAL;
+  if (sizes[0] != b->row.width + b->D.dm.nu || sizes[n_layers] != 1) return HB_EINVAL;
   for (int l = 0; l <= n_layers; l++) if (sizes[l] > 256) return HB_EUNSUPPORTED;  // (the fused kernel's LDS tiles; no layer-by-layer fallback)
   const int rc = learner_idle(b);  // (a call still in flight reads the buffers that are replaced below)
   if (rc != HB_OK) return rc;
@@ -78,7 +78,7 @@ int hb_q_values_dev(hb_batch* b, const float* obs, const float* action, long lon
     if (!outs[k]) continue;
     SacFwdJob& j = d.job[nj++];
     j.net = b->q[k].desc();
-    j.x0 = obs; j.n0 = b->env_nobs; j.x1 = action; j.n1 = b->D.dm.nu;
+    j.x0 = obs; j.n0 = b->row.width; j.x1 = action; j.n1 = b->D.dm.nu;
     j.out = outs[k];
   }
   HB_HIP(launch_sac_forward(d, nj, st));
@@ -181,7 +181,7 @@ int hb_sac_step_dev(hb_batch* b, const hb_sac_rows* rows, float* stats_dev) {
   SacLearner& L = b->sac;
   HB_HIP(hipSetDevice(b->device));
   hipStream_t st = main_stream(b);
-  const size_t mb = rows->mb, nu = b->D.dm.nu, nobs = b->env_nobs;
+  const size_t mb = rows->mb, nu = b->D.dm.nu, nobs = b->row.width;
   const DevMlp& A = b->actor;
   const DevMlp& Q = b->q[0];
   const int La = A.layers, Lq = Q.layers;

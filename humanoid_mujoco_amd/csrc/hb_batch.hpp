@@ -1,5 +1,6 @@
 // hb_batch.hpp — internal to libhb.so: the model and batch handles behind include/hb.h, the owner of their device memory, and the
-// launch plumbing (hb_batch.cpp) the C-ABI translation units (hb_api.cpp, hb_api_rollout.cpp, hb_api_env.cpp, hb_api_dyn.cpp) share.
+// launch plumbing (hb_batch.cpp) the C-ABI translation units (hb_api.cpp, hb_api_rollout.cpp, hb_api_env.cpp, hb_api_policy.cpp,
+// hb_api_collect.cpp, hb_api_dyn.cpp, hb_api_ppo.cpp, hb_api_sac.cpp) share.
 #pragma once
 #include "../../include/hb.h"
 #include "hb_device.hpp"
@@ -329,19 +330,19 @@ struct hb_batch {
   hb_ray_spec ray_spec = {};
   int n_ray = 0, ray_ngeom = 0;                  // n_ray 0: nothing configured
   bool ray_moving = false, ray_hfield = false;   // a geom of a moving body / a height field is among the eligible geoms
-  // observation extension (hb_env_obs_extend): env_nobs is the width of every row the adapter produces and every consumer of them is
-  // sized by, D.dm.nobs (the base, which the policy kernels and compute_obs keep) + n_ext; the scan cast before the env kernel,
-  // [n_env][n_ray], and the envs the env kernel reset, [n_env], for the masked second cast; both null without a scan
+  // the layout of every row the adapter produces (hb_device.hpp: EnvRow): every consumer of them is sized by row.width (hb_env_nobs);
+  // row.base is D.dm.nobs, which the policy kernels and compute_obs keep
+  EnvRow row = {};
+  // observation extension (hb_env_obs_extend): the scan cast before the env kernel, [n_env][n_ray], and the envs the env kernel reset,
+  // [n_env], for the masked second cast; both null without a scan
   hb_obs_ext obs_ext = {};
-  int env_nobs = 0, n_ext = 0;
   DevBuf<float> d_ext_scan;
   DevBuf<uint8_t> d_ext_reset;
   // velocity commands (hb_env_commands_configure): the configuration and every env's record (cx, cy, cyaw, draw count), null while
-  // none is installed; with cmd_cfg.observe the three entries are the last columns of a row: env_nobs = D.dm.nobs + n_ext + 3
+  // none is installed
   EnvCommands cmd_cfg = {};
   DevBuf<float4> d_cmd;
-  // foot-contact terms (hb_env_feet_configure): the configuration and every env's record, null while none is installed; with
-  // feet_cfg.observe the n_feet contact flags sit directly in front of the command: env_nobs = D.dm.nobs + n_ext + n_feet (+ 3)
+  // foot-contact terms (hb_env_feet_configure): the configuration and every env's record, null while none is installed
   EnvFeet feet_cfg = {};
   DevBuf<FeetRec> d_feet;
   DevBuf<int> d_episode;
@@ -452,7 +453,15 @@ int learner_activation_changed(hb_batch* b);
 // both learners (hb_learn_host.cpp): the batch's device current and nothing in flight on its stream
 int learner_idle(hb_batch* b);
 // the installed rays as the scan of the observation extension (hb_api.cpp): the poses they need, then the ray kernel with the extension's
-// transform, for every env or those of `mask`, into out[env * stride + col + ray]; hb_last_kernel stays what it was
-int rays_scan_launch(hb_batch* b, const uint8_t* mask, float* out, int stride, int col);
+// transform, for every env or those of `mask`, into the scan columns of `rows` (rows of the batch's layout), or with rows null into
+// d_ext_scan [n_env][n_ray]; hb_last_kernel stays what it was
+int rays_scan_launch(hb_batch* b, const uint8_t* mask, float* rows);
+// the env adapter (hb_api_env.cpp) as the policy and the collection loop use it: the adapter's buffers on first use; reward / termination /
+// observation of every env (or those of `mask`); one env step; whether anything sized by the observation exists
+int env_alloc(hb_batch* b);
+int env_eval(hb_batch* b, bool step, bool observe, const uint8_t* mask, float* d_obs, float* d_reward, uint8_t* d_term, uint8_t* d_trunc);
+int env_step_impl(hb_batch* b, const float* action_dev, int n_substeps, const uint8_t* mask, bool step, float* obs_dev, float* reward_dev,
+                  uint8_t* terminated_dev, uint8_t* truncated_dev);
+bool obs_consumers_exist(const hb_batch* b);
 }  // namespace hb
 #pragma GCC visibility pop

@@ -1,5 +1,5 @@
 // hb_device.hpp — device-side model tables and batch buffers (fp32), shared by the host
-// runtime (hb_tables.cpp, hb_batch.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip, hb_ray.hip, hb_dyn.hip).
+// runtime (hb_tables.cpp, hb_batch.cpp) and the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_rollout.hip, hb_policy.hip, hb_kin.hip, hb_ray.hip, hb_dyn.hip).
 //
 // The model is replicated read-only per device as two flat arrays (int, float); DevModel holds
 // typed pointers into them plus the per-env LDS layout.  All tables are small (a few KB) and
@@ -733,20 +733,29 @@ struct RayArgs {
   int out_stride, out_col; //    at dist[env * out_stride + out_col + ray]: straight into a row of a wider table
   float x_offset, x_scale, x_lo, x_hi;
 };
-// what the env kernel appends to the base observation (hb_env_obs_extend): rows of `stride` floats, [ base (M.nobs) | the env's last
-// action (n_act: nu or 0) | scan (n_scan) ].  scan: [n_env][n_scan], cast at the state the env kernel is handed (before any reset): it
-// goes into the terminal row of an env that resets and into the observation row of every other one; the scan columns of an env that
-// resets are left to a second, masked ray launch behind the env kernel, which reads reset_flag [n_env] (1: reset in this launch).
-// Without an extension: stride = M.nobs, everything else 0.
-struct ObsExtArgs {
-  int stride, n_act, n_scan;
-  const float* scan;
-  uint8_t* reset_flag;
+// The layout of an observation row of the env adapter, stated once:
+//   [ base (the model's nobs) | last action (nu) | scan (n_ray) | foot-contact flags (n_feet) | command (3) ]
+// A part that is off has count 0 (its offset is then where it would begin).  env_row() computes it from the few facts that determine it;
+// the env kernel, the host (hb_batch::row), hb_env_row and VecEnv read it.  The layout of hb_env_row (include/hb.h).
+struct EnvRow {
+  int base;                          // the count of the base part, at offset 0
+  int prev_action, n_prev_action;    // offset, count
+  int scan, n_scan;
+  int foot_contact, n_foot_contact;
+  int command, n_command;
+  int width;
 };
-// velocity commands (hb_env_commands_configure): the configuration (the layout of hb_env_commands) and what the env kernel is handed.
-// cmd: [n_env] (cx, cy, cyaw, the bits of the draw count k of the episode) - one 16-byte read per env; null: the feature is off and
-// nothing else is read.  resample: this launch may redraw inside an episode (a step; not a pure evaluation or a settle step).
-// obs_col: the column of the three command entries in an observation row, or -1 when the command is not observed.
+__host__ __device__ inline EnvRow env_row(int nobs, int n_prev_action, int n_scan, int n_feet_observed, bool cmd_observed) {
+  EnvRow r;
+  r.base = nobs;
+  r.prev_action = nobs; r.n_prev_action = n_prev_action;
+  r.scan = r.prev_action + r.n_prev_action; r.n_scan = n_scan;
+  r.foot_contact = r.scan + r.n_scan; r.n_foot_contact = n_feet_observed;
+  r.command = r.foot_contact + r.n_foot_contact; r.n_command = cmd_observed ? 3 : 0;
+  r.width = r.command + r.n_command;
+  return r;
+}
+// velocity commands (hb_env_commands_configure): the configuration (the layout of hb_env_commands); EnvArgs::cmd holds every env's record
 constexpr unsigned RS_COMMAND = 40;  // random-number stream of the command draws (1..8, 16..25 and 32..34 are taken)
 struct EnvCommands {
   unsigned seed;
@@ -754,15 +763,7 @@ struct EnvCommands {
   float resample_time, zero_fraction, w_yaw;
   int frame, observe;
 };
-struct CmdArgs {
-  float4* cmd;
-  EnvCommands C;
-  int resample, obs_col;
-};
-// foot-contact terms (hb_env_feet_configure): the configuration (the layout of hb_env_feet), every env's record, and what the env kernel
-// is handed.  rec: [n_env] FeetRec - null: the feature is off and nothing else is read.  body_contact: the read-out [n_env][nbody][6]
-// of the last physics substep.  update: this launch is a step evaluation and writes the records (the switch of CmdArgs::resample).
-// obs_col: the column of the n_feet contact flags in an observation row, or -1 when they are not observed.
+// foot-contact terms (hb_env_feet_configure): the configuration (the layout of hb_env_feet) and every env's record (EnvArgs::feet)
 constexpr int kMaxFeet = 4, kMaxContactBodies = 8;
 struct EnvFeet {
   int n_feet, foot_body[kMaxFeet];
@@ -783,11 +784,38 @@ struct FeetRec {
   unsigned pad[3];
 };
 static_assert(sizeof(FeetRec) == 32, "one 32-byte record per env");
-struct FeetArgs {
+// Everything hb_env_kernel takes besides the model, by value (launch_env; filled by env_eval in hb_api_env.cpp).  A feature that is off is
+// a null pointer - S.k_obs: the realism layer, dr: domain randomisation, term_obs, scan, cmd, feet - and nothing else of it is read.
+struct EnvArgs {
+  EnvConfig cfg;
+  EnvRand R;
+  EnvRandState S;
+  DomainRand D;
+  float* state; const float* qfrc; const int* counts;  // the batch's state records, the step's joint forces and counts
+  float* prev; float* latest;                          // the adapter's action bookkeeping
+  const float* qpos_src; int* episode; int* status;    // the reset pose, the episode numbers, the warning bits
+  float* obs; float* reward; uint8_t* terminated; uint8_t* truncated;  // the outputs
+  const uint8_t* mask;  // nullable [n_env]: only the envs whose byte is set are evaluated
+  int observe;          // the observation goes through the realism layer's noise and delay lines instead of being the true one
+  int step;             // this launch is a step of the episode: it may redraw a command inside an episode and it writes the feet records
+                        // (not a pure evaluation, a settle step or the final observation of hb_env_reset)
+  float* dr;            // [n_env][dr_stride] per-env model parameters
+  int dr_stride, n_env, env_offset;
+  float* term_obs;      // [n_env][row.width]: the observation of the state an episode ends in
+  int* seen;            // nullable [n_env]: the warning bits of the episodes that ended
+  EnvRow row;           // the rows of obs and term_obs
+  // the scan, [n_env][row.n_scan], cast at the state the env kernel is handed (before any reset): it goes into the terminal row of an env
+  // that resets and into the observation row of every other one; the scan columns of an env that resets are left to a second, masked ray
+  // launch behind the env kernel, which reads reset_flag [n_env] (1: reset in this launch; nullable)
+  const float* scan;
+  uint8_t* reset_flag;
+  // velocity commands: [n_env] (cx, cy, cyaw, the bits of the draw count k of the episode) - one 16-byte read per env
+  float4* cmd;
+  EnvCommands C;
+  // foot-contact terms: every env's record, and the read-out [n_env][nbody][6] of the last physics substep
+  FeetRec* feet;
   const float* body_contact;
-  FeetRec* rec;
   EnvFeet F;
-  int update, obs_col;
 };
 constexpr int kAccPark = 24;  // floats per body in BatchPtrs::body_acc_park (six 16-byte moves)
 

@@ -1,181 +1,10 @@
-// hb_env.hip - everything around the step kernels: MJPC task costs and spline tapes, reset, the env adapter (observations, rewards,
-// realism layer, domain randomisation), the policy MLP kernels, the heavy-first order, benchmark controls - and their launchers.
+// hb_env.hip - the env adapter: reset, the realism layer, domain randomisation, the observation, the action bookkeeping, velocity
+// commands, foot-contact terms, the env kernel (rewards, termination, auto-reset, the observation row) - and their launchers.
 #include <hip/hip_runtime.h>
 #include "hb_kcommon.hpp"
 #include "hb_launch.hpp"
 
 namespace hb {
-
-// ---- MJPC task cost on the recorded read-out rows --------------------------------------------------------------
-// mjpc::Norm (mujoco_mpc/mjpc/norm.cc:50-208), value only
-__device__ __forceinline__ float mjpc_norm(int type, const float* x, int n, float p, float q) {
-  float y = 0.f;
-  switch (type) {
-    case 0: for (int i = 0; i < n; i++) y += x[i] * x[i]; return 0.5f * y;                                   // kQuadratic
-    case 1: { float c = 0.f; for (int i = 0; i < n; i++) c += x[i] * x[i]; return powf(powf(c, 0.5f * q) + powf(p, q), 1.f / q) - p; }  // kL22
-    case 2: { float c = 0.f; for (int i = 0; i < n; i++) c += x[i] * x[i]; return sqrtf(c + p * p) - p; }  // kL2
-    case 3: for (int i = 0; i < n; i++) y += p * p * (coshf(x[i] / p) - 1.f); return y;                      // kCosh
-    case 5: for (int i = 0; i < n; i++) y += powf(fabsf(x[i]), p); return y;                                   // kPowerLoss
-    case 6: for (int i = 0; i < n; i++) y += sqrtf(x[i] * x[i] + p * p) - p; return y;                         // kSmoothAbsLoss
-    case 7: for (int i = 0; i < n; i++) y += powf(powf(fabsf(x[i]), q) + powf(p, q), 1.f / q) - p; return y;  // kSmoothAbs2Loss
-    case 8: for (int i = 0; i < n; i++) y += p > 0.f ? p * logf(1.f + expf(x[i] / p)) : fmaxf(x[i], 0.f); return y;  // kRectifyLoss
-    default: return x[0];                                                                                       // kNull
-  }
-}
-
-// BaseResidualFn::CostTerms + CostValue (mujoco_mpc/mjpc/task.cc:71-110): term k = weight[k] * Norm(norm[k]) of the next dim[k] residual
-// entries; the sum goes through the risk transformation (risk-neutral below kRiskNeutralTolerance = 1e-6).  `terms` nullable.
-__device__ __forceinline__ float mjpc_risk(float risk, float c) { return fabsf(risk) >= 1e-6f ? (expf(risk * c) - 1.f) / risk : c; }
-__device__ __forceinline__ float mjpc_cost_value(int nterm, const int* dim, const int* norm, const float* weight, const float* p, const float* q, float risk,
-                                                 const float* res, float* terms) {
-  float cost = 0.f;
-  int sh = 0;
-  for (int k = 0; k < nterm; k++) {
-    const float tk = weight[k] * mjpc_norm(norm[k], res + sh, dim[k], p[k], q[k]);
-    if (terms) terms[k] = tk;
-    cost += tk;
-    sh += dim[k];
-  }
-  return mjpc_risk(risk, cost);
-}
-
-// hb_task_cost: the same cost evaluation for n caller-supplied residual vectors (one thread each)
-__global__ void hb_cost_terms_kernel(const float* residual, int n, int nres, const CostSpec K, float* terms, float* cost) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  cost[e] = mjpc_cost_value(K.nterm, K.dim, K.norm, K.weight, K.p, K.q, K.risk, residual + (size_t)e * nres, terms ? terms + (size_t)e * K.nterm : nullptr);
-}
-
-// One thread per candidate: Stand::ResidualFn::Residual (tasks/humanoid/stand/stand.cc:41-104) on each of the H rows,
-// BaseResidualFn::CostValue (task.cc:71-110), Trajectory::UpdateReturn (trajectory.cc:312-326); a candidate that raised
-// a bad-state warning returns kMaxReturnValue (trajectory.cc:29,169-173)
-__global__ void hb_stand_cost_kernel(const float* rows, int H, int n_env, const StandTask K, const int* status, float* total, float* costs) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n_env) return;
-  float sum = 0.f;
-  for (int t = 0; t < H; t++) {
-    const float* r = rows + ((size_t)t * n_env + e) * K.stride;
-    float fz = 0.f, fx = 0.f, fy = 0.f;
-    for (int k = 0; k < K.n_feet; k++) { fx += r[K.o_feet + 3 * k]; fy += r[K.o_feet + 3 * k + 1]; fz += r[K.o_feet + 3 * k + 2]; }
-    const float inv = 1.f / (float)K.n_feet;
-    const float height = r[K.o_head + 2] - fz * inv - K.height_goal;
-    const float kFallTime = 0.2f;
-    const float dx = fx * inv - (r[K.o_com] + kFallTime * r[K.o_vel]), dy = fy * inv - (r[K.o_com + 1] + kFallTime * r[K.o_vel + 1]);
-    const float balance = sqrtf(dx * dx + dy * dy);
-    float c = K.weight[0] * mjpc_norm(K.norm[0], &height, 1, K.p[0], K.q[0]);
-    c += K.weight[1] * mjpc_norm(K.norm[1], &balance, 1, K.p[1], K.q[1]);
-    c += K.weight[2] * mjpc_norm(K.norm[2], r + K.o_vel, 2, K.p[2], K.q[2]);
-    c += K.weight[3] * mjpc_norm(K.norm[3], r + K.o_qvel + 6, K.nv - 6, K.p[3], K.q[3]);
-    c += K.weight[4] * mjpc_norm(K.norm[4], r + K.o_ctrl, K.nu, K.p[4], K.q[4]);
-    c = mjpc_risk(K.risk, c);
-    if (costs) costs[(size_t)t * n_env + e] = c;
-    sum += c;
-  }
-  const bool failed = status[e] & ((1 << 4) | (1 << 5) | (1 << 6));
-  total[e] = failed ? 1.0e6f : sum / (float)max(H, 1);
-}
-
-// Walk::ResidualFn::Residual (tasks/humanoid/walk/walk.cc:44-163) on each of the H rows, then the cost terms in the
-// order and with the dimensions the task's user sensors declare (task.cc:71-89), return as in hb_stand_cost_kernel
-__global__ void hb_walk_cost_kernel(const float* rows, int H, int n_env, const WalkTask K, const int* status, float* total, float* costs) {
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n_env) return;
-  float sum = 0.f;
-  for (int t = 0; t < H; t++) {
-    const float* r = rows + ((size_t)t * n_env + e) * K.stride;
-    float res[96];
-    int c = 0;
-    const float torso_height = r[K.o_torso + 2];
-    res[c++] = torso_height - K.height_goal;
-    const float* fr = r + K.o_foot_r;
-    const float* fl = r + K.o_foot_l;
-    res[c++] = 0.5f * (fl[2] + fr[2]) - r[K.o_pelvis + 2] - 0.2f;
-    // balance: capture point against its projection onto the segment between the feet
-    float cp[3] = {r[K.o_com] + 0.3f * r[K.o_vel], r[K.o_com + 1] + 0.3f * r[K.o_vel + 1], 1.0e-3f};
-    float axis[3] = {fr[0] - fl[0], fr[1] - fl[1], 1.0e-3f};
-    float an = sqrtf(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
-    if (an < 1e-15f) { axis[0] = 1.f; axis[1] = 0.f; axis[2] = 0.f; } else { axis[0] /= an; axis[1] /= an; axis[2] /= an; }  // mju_normalize3
-    const float length = 0.5f * an - 0.05f;
-    const float center[3] = {0.5f * (fr[0] + fl[0]), 0.5f * (fr[1] + fl[1]), 0.5f * (fr[2] + fl[2])};
-    const float vec[3] = {cp[0] - center[0], cp[1] - center[1], cp[2] - center[2]};
-    float tt = vec[0] * axis[0] + vec[1] * axis[1] + vec[2] * axis[2];
-    tt = fmaxf(-length, fminf(length, tt));
-    const float pcp[2] = {axis[0] * tt + center[0], axis[1] * tt + center[1]};
-    const float standing = torso_height / sqrtf(torso_height * torso_height + 0.45f * 0.45f) - 0.4f;
-    res[c++] = standing * (cp[0] - pcp[0]);
-    res[c++] = standing * (cp[1] - pcp[1]);
-    // upright: axes are [torso_up, pelvis_up, foot_right_up, foot_left_up, torso_forward, pelvis_forward, foot_right_forward, foot_left_forward]
-    const float* ax = r + K.o_axes;
-    res[c++] = ax[2] - 1.f;
-    res[c++] = 0.3f * (ax[3 + 2] - 1.f);
-    for (int f = 0; f < 2; f++) {
-      const float* up = ax + 3 * (2 + f);
-      res[c++] = 0.1f * standing * up[0]; res[c++] = 0.1f * standing * up[1]; res[c++] = 0.1f * standing * (up[2] - 1.f);
-    }
-    // posture
-    for (int i = 7; i < K.nq; i++) res[c++] = r[K.o_qpos + i];
-    // walk
-    float fw[2] = {0.f, 0.f};
-    for (int k = 4; k < 8; k++) { fw[0] += ax[3 * k]; fw[1] += ax[3 * k + 1]; }
-    const float fn = sqrtf(fw[0] * fw[0] + fw[1] * fw[1]);
-    if (fn < 1e-15f) { fw[0] = 1.f; fw[1] = 0.f; } else { fw[0] /= fn; fw[1] /= fn; }  // mju_normalize
-    const float* tv = r + K.o_linvel;  // torso, foot_right, foot_left
-    const float cv[2] = {0.5f * (r[K.o_sub] + tv[0]), 0.5f * (r[K.o_sub + 1] + tv[1])};
-    res[c++] = standing * (cv[0] * fw[0] + cv[1] * fw[1] - K.speed_goal);
-    // move feet
-    res[c++] = standing * (cv[0] - 0.5f * tv[3] - 0.5f * tv[6]);
-    res[c++] = standing * (cv[1] - 0.5f * tv[4] - 0.5f * tv[7]);
-    // control
-    for (int i = 0; i < K.nu; i++) res[c++] = r[K.o_ctrl + i];
-    const float cost = mjpc_cost_value(K.nterm, K.dim, K.norm, K.weight, K.p, K.q, K.risk, res, nullptr);
-    if (costs) costs[(size_t)t * n_env + e] = cost;
-    sum += cost;
-  }
-  const bool failed = status[e] & ((1 << 4) | (1 << 5) | (1 << 6));
-  total[e] = failed ? 1.0e6f : sum / (float)max(H, 1);
-}
-
-// ---- SamplingPolicy::Action on the device (mujoco_mpc/mjpc/planners/sampling/policy.cc:50-58): every candidate's
-// time spline (mjpc/spline/spline.cc:103-156,240-277: zero-order / linear / cubic Hermite with finite-difference slopes)
-// sampled at time0 + t * dt and clamped to ctrlrange, written as the action tape [T][n_env][nu] the rollouts read.
-// knots: [n_env][P][nu]; times: [P], increasing, shared by the candidates.
-__global__ void hb_spline_tape_kernel(const DevModel M, const float* knots, const float* times, int P, int interp, float time0, float dt, int T, int n_env, float* tape) {
-  const int nu = M.nu;
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)T * n_env * nu;
-  if (idx >= total) return;
-  const int i = (int)(idx % nu), e = (int)((idx / nu) % n_env), t = (int)(idx / ((size_t)nu * n_env));
-  const float time = time0 + (float)t * dt;
-  const float* y = knots + (size_t)e * P * nu + i;  // y[k * nu]: node k
-  float v;
-  int up = 0;
-  while (up < P && times[up] <= time) up++;  // std::upper_bound
-  if (P == 0) v = 0.f;
-  else if (up == P) v = y[(size_t)(P - 1) * nu];
-  else if (up == 0) v = y[0];
-  else {
-    const int lo = up - 1;
-    const float t0 = times[lo], t1 = times[up], x = (time - t0) / (t1 - t0);
-    const float p0 = y[(size_t)lo * nu], p1 = y[(size_t)up * nu];
-    if (interp == 0) v = p0;
-    else if (interp == 1) v = p0 * (1.f - x) + p1 * x;
-    else {
-      // TimeSpline::Slope: one-sided at the ends, mean of the two one-sided differences inside
-      auto slope = [&](int k) {
-        if (k == 0) return (y[(size_t)1 * nu] - y[0]) / (times[1] - times[0]);
-        const float back = (y[(size_t)k * nu] - y[(size_t)(k - 1) * nu]) / (times[k] - times[k - 1]);
-        if (k == P - 1) return back;
-        return 0.5f * (y[(size_t)(k + 1) * nu] - y[(size_t)k * nu]) / (times[k + 1] - times[k]) + 0.5f * back;
-      };
-      const float h = t1 - t0, x2 = x * x, x3 = x2 * x;
-      v = (2.f * x3 - 3.f * x2 + 1.f) * p0 + (x3 - 2.f * x2 + x) * h * slope(lo) + (-2.f * x3 + 3.f * x2) * p1 + (x3 - x2) * h * slope(up);
-    }
-  }
-  // Clamp(action, actuator_ctrlrange, nu) (utilities.cc:94-98); an actuator without a control range is left alone
-  const float lo_r = M.act_ctrlrange[2 * i], hi_r = M.act_ctrlrange[2 * i + 1];
-  if (M.act_ctrllimited[i] || lo_r < hi_r) v = fminf(fmaxf(v, lo_r), hi_r);
-  tape[idx] = v;
-}
 
 // ------------------------------------------------------------------------------------------
 // reset: qpos0/keyframe (+ Halton perturbation), zero velocity/warmstart/time/status
@@ -521,17 +350,29 @@ __device__ __forceinline__ float env_lane_sum(float x) {
   for (int m = kEnvLanes / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, kEnvLanes);
   return x;
 }
-__global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const EnvConfig cfg, const EnvRand R, const EnvRandState S, float* state, const float* qfrc, const int* counts,
-                              float* prev, float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated,
-                              uint8_t* truncated, const uint8_t* mask, int observe, const DomainRand D, float* dr, int dr_stride, int n_env, int env_offset, float* term_obs, int* seen,
-                              const ObsExtArgs X, const CmdArgs K, const FeetArgs A) {
+// What a row holds behind the base observation (EnvRow; no noise, no delay), written by the env's lanes: the env's last action, the scan
+// cast before this kernel (with_scan) or nothing in its columns, the feet's contact flags of `feet_mask`, the command of which `cmd_l` is
+// this lane's component.  A part that is off has count 0.
+__device__ __forceinline__ void env_row_tail(const EnvArgs& G, float* o, int e, int l, int nu, bool with_scan, unsigned feet_mask, float cmd_l) {
+  const EnvRow& W = G.row;
+  for (int i = l; i < W.n_prev_action; i += kEnvLanes) o[W.prev_action + i] = G.latest[(size_t)e * nu + i];
+  if (with_scan) for (int i = l; i < W.n_scan; i += kEnvLanes) o[W.scan + i] = G.scan[(size_t)e * W.n_scan + i];
+  if (l < W.n_foot_contact) o[W.foot_contact + l] = (feet_mask >> l) & 1u ? 1.f : 0.f;
+  for (int i = l; i < W.n_command; i += kEnvLanes) o[W.command + i] = cmd_l;
+}
+__global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const EnvArgs G) {
+  const EnvConfig& cfg = G.cfg;
+  const EnvRand& R = G.R;
+  const EnvRandState& S = G.S;
+  const EnvCommands& C = G.C;
+  const EnvFeet& F = G.F;
   extern __shared__ float sh_state[];
   const int grp = threadIdx.x / kEnvLanes, l = threadIdx.x % kEnvLanes;
   const int e = blockIdx.x * (256 / kEnvLanes) + grp;
-  const bool active = e < n_env && (!mask || mask[e]);
+  const bool active = e < G.n_env && (!G.mask || G.mask[e]);
   const int nsp = (M.nstate + 3) & ~3;
   float* ls = sh_state + grp * nsp;
-  float* s = state + (size_t)(active ? e : 0) * M.nstate;
+  float* s = G.state + (size_t)(active ? e : 0) * M.nstate;
   if (active) for (int i = l; i < M.nstate; i += kEnvLanes) ls[i] = s[i];
   __syncthreads();
   bool reset = false;
@@ -555,11 +396,11 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     float vx = da >= 0 ? qvel[da] : 0.f, vy = da >= 0 ? qvel[da + 1] : 0.f;
     float tvx = cfg.target_velocity[0], tvy = cfg.target_velocity[1];
     float4 cmd = {0.f, 0.f, 0.f, 0.f};
-    if (K.cmd) {
-      cmd = K.cmd[e];
+    if (G.cmd) {
+      cmd = G.cmd[e];
       tvx = cmd.x; tvy = cmd.y;
       cmd_l = l == 0 ? cmd.x : l == 1 ? cmd.y : l == 2 ? cmd.z : cmd.w;
-      if (K.C.frame == 1) {  // the planar velocity in the root's heading frame (m[0], m[3]: the root's x axis in the world)
+      if (C.frame == 1) {  // the planar velocity in the root's heading frame (m[0], m[3]: the root's x axis in the world)
         float hc, hs;
         heading_cs(m[0], m[3], hc, hs);
         const float wx = vx, wy = vy;
@@ -568,9 +409,9 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     }
     float dvx = vx - tvx, dvy = vy - tvy;
     r += cfg.w_hvel * scaled_exp(dvx * dvx + dvy * dvy);
-    if (K.cmd) {  // the yaw rate: the world z component of the root's (body-frame) angular velocity
+    if (G.cmd) {  // the yaw rate: the world z component of the root's (body-frame) angular velocity
       const float dw = (da >= 0 ? m[6] * qvel[da + 3] + m[7] * qvel[da + 4] + m[8] * qvel[da + 5] : 0.f) - cmd.z;
-      r += K.C.w_yaw * scaled_exp(dw * dw);
+      r += C.w_yaw * scaled_exp(dw * dw);
     }
     // upright: |g_local - (0,0,-1)|^2
     r += cfg.w_upright * scaled_exp(g[0] * g[0] + g[1] * g[1] + (g[2] + 1.f) * (g[2] + 1.f));
@@ -582,7 +423,7 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
       float acc = 0.f, n = 0.f;
       for (int j = l; j < M.njnt; j += kEnvLanes)
         if (M.jnt_type[j] >= 2) {
-          float x = fmaxf(fabsf(qfrc[(size_t)e * M.nv + M.jnt_dofadr[j]]) - cfg.safe_torque, 0.f);
+          float x = fmaxf(fabsf(G.qfrc[(size_t)e * M.nv + M.jnt_dofadr[j]]) - cfg.safe_torque, 0.f);
           acc += scaled_exp(x * x);
           n += 1.f;
         }
@@ -590,8 +431,8 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
       if (n > 0.f) r += cfg.w_torque * acc / n;
     }
     // control change / regularisation / symmetry on the (scaled) actions
-    const float* pa = prev + (size_t)e * M.nu;
-    const float* la = latest + (size_t)e * M.nu;
+    const float* pa = G.prev + (size_t)e * M.nu;
+    const float* la = G.latest + (size_t)e * M.nu;
     const float inv = 1.f / cfg.action_scale;
     if (M.nu > 0) {
       float chg = 0.f, reg = 0.f;
@@ -616,27 +457,27 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
       r += cfg.w_symmetry * sym / (float)(cfg.n_equal + cfg.n_opposite);
     }
     if (cfg.w_vvel != 0.f) { const float vz = da >= 0 ? qvel[da + 2] : 0.f; r += cfg.w_vvel * scaled_exp(vz * vz); }  // vertical_velocity_penalty
-    if (counts[kCountStride * e + 4]) r += cfg.self_collision_penalty;
+    if (G.counts[kCountStride * e + 4]) r += cfg.self_collision_penalty;
     bool feet_term = false;
-    if (A.rec) {
+    if (G.feet) {
       // lane f < n_feet owns foot f; lanes 0..7 a penalised body each, lanes 8..15 a terminal body each.  The flags travel as one
       // small integer per lane - stumbles, collisions and terminal contacts counted in fields of four bits, the feet's contact bits
       // above them -, exact in fp32, so that three lane sums serve every term.
-      const float* bc = A.body_contact + (size_t)e * M.nbody * 6;
-      const float thr2 = __fmul_rn(A.F.contact_threshold, A.F.contact_threshold);
-      const int fb = feet_pick(A.F.foot_body, A.F.n_feet, l);
-      const int pb = feet_pick(A.F.penalised_body, A.F.n_penalised, l);
-      const int tb = feet_pick(A.F.terminal_body, A.F.n_terminal, l - kMaxContactBodies);
-      const unsigned old_mask = A.rec[e].mask;
+      const float* bc = G.body_contact + (size_t)e * M.nbody * 6;
+      const float thr2 = __fmul_rn(F.contact_threshold, F.contact_threshold);
+      const int fb = feet_pick(F.foot_body, F.n_feet, l);
+      const int pb = feet_pick(F.penalised_body, F.n_penalised, l);
+      const int tb = feet_pick(F.terminal_body, F.n_terminal, l - kMaxContactBodies);
+      const unsigned old_mask = G.feet[e].mask;
       float air = 0.f, force = 0.f, pl, zz;
       int flags = 0;
       if (fb >= 0) {
-        const float tl = A.rec[e].t_last[l];
+        const float tl = G.feet[e].t_last[l];
         const float n2 = contact_n2(bc, fb, pl, zz);
         const bool c = n2 > thr2;
-        if (c && !((old_mask >> l) & 1u)) air = __fsub_rn(ls[0], tl) - A.F.air_time_target;
-        force = fmaxf(sqrtf(n2) - A.F.force_max, 0.f);
-        if (c && pl > __fmul_rn(__fmul_rn(A.F.stumble_ratio, A.F.stumble_ratio), zz)) flags += 1;
+        if (c && !((old_mask >> l) & 1u)) air = __fsub_rn(ls[0], tl) - F.air_time_target;
+        force = fmaxf(sqrtf(n2) - F.force_max, 0.f);
+        if (c && pl > __fmul_rn(__fmul_rn(F.stumble_ratio, F.stumble_ratio), zz)) flags += 1;
         if (c) flags += 4096 << l;
         feet_t = c ? ls[0] : tl;
       }
@@ -644,13 +485,13 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
       if (tb >= 0 && contact_n2(bc, tb, pl, zz) > thr2) flags += 256;
       air = env_lane_sum(air); force = env_lane_sum(force);
       flags = (int)env_lane_sum((float)flags);
-      const bool gate = !A.F.air_gate || __fadd_rn(__fmul_rn(tvx, tvx), __fmul_rn(tvy, tvy)) > __fmul_rn(A.F.air_cmd_min, A.F.air_cmd_min);
-      if (gate) r += A.F.w_air_time * air;
-      r += A.F.w_force * force;
-      if (flags & 15) r += A.F.w_stumble;
-      r += A.F.w_collision * (float)((flags >> 4) & 15);
+      const bool gate = !F.air_gate || __fadd_rn(__fmul_rn(tvx, tvx), __fmul_rn(tvy, tvy)) > __fmul_rn(F.air_cmd_min, F.air_cmd_min);
+      if (gate) r += F.w_air_time * air;
+      r += F.w_force * force;
+      if (flags & 15) r += F.w_stumble;
+      r += F.w_collision * (float)((flags >> 4) & 15);
       feet_term = ((flags >> 8) & 15) != 0;
-      feet_mask = A.update ? (unsigned)flags >> 12 : old_mask;
+      feet_mask = G.step ? (unsigned)flags >> 12 : old_mask;
     }
     const bool upright = fmaxf(fabsf(g[0]), fabsf(g[1])) < cfg.upright_tol;
     const bool timeup = cfg.max_time > 0.f && ls[0] >= cfg.max_time;
@@ -664,70 +505,65 @@ __global__ __launch_bounds__(256) void hb_env_kernel(const DevModel M, const Env
     }
     term = term || feet_term;
     if (term) r = cfg.terminal_reward;
-    if (l == 0) { reward[e] = r; terminated[e] = term ? 1 : 0; truncated[e] = trunc ? 1 : 0; }
+    if (l == 0) { G.reward[e] = r; G.terminated[e] = term ? 1 : 0; G.truncated[e] = trunc ? 1 : 0; }
     reset = (term || trunc) && cfg.auto_reset;
   }
   const bool rand_on = S.k_obs != nullptr;
-  int ep = active ? episode[e] : 0;
+  int ep = active ? G.episode[e] : 0;
   // the observation of the state an episode ENDS in, before the env is reset in place: what stable-baselines3's VecEnv hands the learner as
   // infos[i]["terminal_observation"] (DummyVecEnv.step_wait; SAC / PPO bootstrap from it when the episode was truncated) - the same sensor
   // model, noise and delays as any other observation of that episode (CPUEnv.step returns self._get_obs() before anything resets)
-  if (reset && term_obs) {
-    float* to = term_obs + (size_t)e * X.stride;
-    if (rand_on && observe) envrand_observe(M, R, S, e, env_offset + e, ep, ls, to, l, kEnvLanes);
+  if (reset && G.term_obs) {
+    float* to = G.term_obs + (size_t)e * G.row.width;
+    if (rand_on && G.observe) envrand_observe(M, R, S, e, G.env_offset + e, ep, ls, to, l, kEnvLanes);
     else compute_obs(M, ls, to, l, kEnvLanes);
-    // the extension of the state the episode ends in: the action just applied, the scan before the reset (over the old elevations)
-    for (int i = l; i < X.n_act; i += kEnvLanes) to[M.nobs + i] = latest[(size_t)e * M.nu + i];
-    for (int i = l; i < X.n_scan; i += kEnvLanes) to[M.nobs + X.n_act + i] = X.scan[(size_t)e * X.n_scan + i];
-    if (K.cmd && K.obs_col >= 0) for (int i = l; i < 3; i += kEnvLanes) to[K.obs_col + i] = cmd_l;  // (the old command)
-    if (A.rec && A.obs_col >= 0 && l < A.F.n_feet) to[A.obs_col + l] = (feet_mask >> l) & 1u ? 1.f : 0.f;  // (the ending state's flags)
+    // of the state the episode ends in: the action just applied, the scan before the reset (over the old elevations), the ending state's
+    // flags, the old command
+    env_row_tail(G, to, e, l, M.nu, true, feet_mask, cmd_l);
   }
   __syncthreads();  // (every lane has read the old state and the old episode number)
   if (reset) {
     // CPUEnv.reset for this env; the perturbation index advances with the episode count
     ep += 1;
-    reset_state(M, ls, qpos_src, cfg.reset_perturb, env_offset + e, ep, cfg.reset_quat_perturb, l, kEnvLanes);
-    for (int i = l; i < M.nu; i += kEnvLanes) { prev[(size_t)e * M.nu + i] = 0.f; latest[(size_t)e * M.nu + i] = 0.f; }
+    reset_state(M, ls, G.qpos_src, cfg.reset_perturb, G.env_offset + e, ep, cfg.reset_quat_perturb, l, kEnvLanes);
+    for (int i = l; i < M.nu; i += kEnvLanes) { G.prev[(size_t)e * M.nu + i] = 0.f; G.latest[(size_t)e * M.nu + i] = 0.f; }
     if (l == 0) {
-      episode[e] = ep;
-      if (seen) seen[e] |= status[e];  // (the warning bits of the episode that ends here stay readable: hb_env_warnings)
-      status[e] = 0;
-      if (rand_on) envrand_begin_episode(M, R, S, e, env_offset + e, ep);
+      G.episode[e] = ep;
+      if (G.seen) G.seen[e] |= G.status[e];  // (the warning bits of the episode that ends here stay readable: hb_env_warnings)
+      G.status[e] = 0;
+      if (rand_on) envrand_begin_episode(M, R, S, e, G.env_offset + e, ep);
     }
     static_assert(kEnvLanes == kDrawLanes, "the env kernel draws an episode's model parameters with all lanes of the env");
-    if (dr) domain_draw<kDrawLanes>(M, D, dr + (size_t)e * dr_stride, env_offset + e, ep, l);
+    if (G.dr) domain_draw<kDrawLanes>(M, G.D, G.dr + (size_t)e * G.dr_stride, G.env_offset + e, ep, l);
   }
-  if (K.cmd && active) {
+  if (G.cmd && active) {
     // draw 0 of the episode that begins here, or - in a step - draw k of the one that goes on once its time has come: at most one draw
     const int k = reset ? 0 : __float_as_int(__shfl(cmd_l, 3, kEnvLanes));
-    if (reset || (K.resample && K.C.resample_time > 0.f && ls[0] >= __fmul_rn((float)k, K.C.resample_time))) {
-      cmd_l = command_draw<kEnvLanes>(K.C, env_offset + e, ep, k, l);
-      command_store(K.cmd + e, l, cmd_l, k + 1);
+    if (reset || (G.step && C.resample_time > 0.f && ls[0] >= __fmul_rn((float)k, C.resample_time))) {
+      cmd_l = command_draw<kEnvLanes>(C, G.env_offset + e, ep, k, l);
+      command_store(G.cmd + e, l, cmd_l, k + 1);
     }
   }
   __threadfence_block();
   __syncthreads();  // the new state (LDS) and the new episode's delays (global, written by lane 0) are visible to the env's lanes
   if (active) {
     if (reset) for (int i = l; i < M.nstate; i += kEnvLanes) s[i] = ls[i];
-    float* o = obs + (size_t)e * X.stride;
-    if (rand_on && observe) envrand_observe(M, R, S, e, env_offset + e, ep, ls, o, l, kEnvLanes);
+    float* o = G.obs + (size_t)e * G.row.width;
+    if (rand_on && G.observe) envrand_observe(M, R, S, e, G.env_offset + e, ep, ls, o, l, kEnvLanes);
     else compute_obs(M, ls, o, l, kEnvLanes);
-    // the extension (no noise, no delay): the last action - zero in a new episode: this lane cleared these very entries above -, and the
-    // scan of an env that goes on; an env that was reset gets its scan from the masked ray launch behind this kernel
-    for (int i = l; i < X.n_act; i += kEnvLanes) o[M.nobs + i] = latest[(size_t)e * M.nu + i];
-    if (!reset) for (int i = l; i < X.n_scan; i += kEnvLanes) o[M.nobs + X.n_act + i] = X.scan[(size_t)e * X.n_scan + i];
-    if (K.cmd && K.obs_col >= 0) for (int i = l; i < 3; i += kEnvLanes) o[K.obs_col + i] = cmd_l;  // (no noise, no delay)
-    if (A.rec) {
+    if (G.feet) {
       // an episode that begins here starts with its feet down at the new state's time: a standing start pays nothing
-      if (reset) { feet_t = ls[0]; feet_mask = (1u << A.F.n_feet) - 1u; }
-      if (A.update) {
-        if (l < A.F.n_feet) A.rec[e].t_last[l] = feet_t;
-        if (l == 0) A.rec[e].mask = feet_mask;
+      if (reset) { feet_t = ls[0]; feet_mask = (1u << F.n_feet) - 1u; }
+      if (G.step) {
+        if (l < F.n_feet) G.feet[e].t_last[l] = feet_t;
+        if (l == 0) G.feet[e].mask = feet_mask;
       }
-      if (A.obs_col >= 0 && l < A.F.n_feet) o[A.obs_col + l] = (feet_mask >> l) & 1u ? 1.f : 0.f;  // (no noise, no delay)
     }
+    // the last action - zero in a new episode: this lane cleared these very entries above -, and the scan of an env that goes on; an env
+    // that was reset gets its scan from the masked ray launch behind this kernel
+    env_row_tail(G, o, e, l, M.nu, !reset, feet_mask, cmd_l);
   }
-  if (X.reset_flag && e < n_env && l == 0) X.reset_flag[e] = reset ? 1 : 0;
+  if (G.reset_flag && e < G.n_env && l == 0) G.reset_flag[e] = reset ? 1 : 0;
 }
 
 // hb_env_reset's collision test (cpu_env.py:411-414): envs of the mask that collide (mode 1: any contact, mode 2:
@@ -739,108 +575,6 @@ __global__ void hb_reset_check_kernel(const int* counts, const uint8_t* terminat
   const bool hit = mode == 1 ? counts[kCountStride * e] > 0 : counts[kCountStride * e + 4] != 0;
   if (hit || terminated[e] || truncated[e]) { episode[e]++; atomicAdd(pending, 1); }
   else mask[e] = 0;
-}
-
-
-// One dense layer of the policy MLP on the matrix cores: Y[M][N] = act(X[M][K] W[K][N] + b[N]); act 0: none, else 1 + kAct*.
-// One wave per 32x32 output tile, K swept two columns per v_mfma_f32_32x32x2_f32 (exact f32); the X tile
-// is staged through LDS (row stride K+1: conflict-free A-operand reads), W streams from L2 coalesced.
-__global__ __launch_bounds__(kGroup) void hb_mlp_layer_kernel(const float* X, const float* W, const float* bias, float* Y, int Mrows, int K, int N, int act) {
-  extern __shared__ float xs[];
-  const int lane = threadIdx.x, m0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
-  const int ks = K + 1;
-  for (int idx = lane; idx < 32 * K; idx += kGroup) {
-    const int r = idx / K, c = idx - r * K;
-    xs[r * ks + c] = (m0 + r < Mrows) ? X[(size_t)(m0 + r) * K + c] : 0.f;
-  }
-  __syncthreads();
-  const int col = lane & 31, half = lane >> 5;
-  const bool nvld = n0 + col < N;
-  f32x16 D;
-#pragma unroll
-  for (int r = 0; r < 16; r++) D[r] = 0.f;
-  for (int k0 = 0; k0 < K; k0 += 2) {
-    const int k = k0 + half;
-    const float a = k < K ? xs[col * ks + k] : 0.f;
-    const float bv = (nvld && k < K) ? W[(size_t)k * N + n0 + col] : 0.f;
-    D = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, D, 0, 0, 0);
-  }
-  const float bn = nvld ? bias[n0 + col] : 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; r++) {
-    const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-    if (row < Mrows && nvld) {
-      float v = D[r] + bn;
-      Y[(size_t)row * N + n0 + col] = act ? mlp_act(act - 1, v) : v;
-    }
-  }
-}
-
-// hb_policy_kernel, hb_policy_lean_kernel and their twins for networks that are not tanh
-#define HB_ACT_ANY 0
-#include "hb_policy_kernels.inl"
-#undef HB_ACT_ANY
-#define HB_ACT_ANY 1
-#include "hb_policy_kernels.inl"
-#undef HB_ACT_ANY
-
-// Probe for hb_batch_pipeline: one wave that idles for `ticks` of the 100 MHz wall clock (bounded by the sleep count as well) and
-// records when it began and ended.  Two of these on two streams overlap in time exactly when the streams own different hardware queues.
-__global__ __launch_bounds__(64) void hb_probe_spin_kernel(unsigned long long* out, unsigned ticks) {
-  const unsigned long long t0 = wall_clock64();
-  unsigned long long t = t0;
-  for (int guard = 0; guard < 2048 && t - t0 < ticks; guard++) {
-    __builtin_amdgcn_s_sleep(64);
-    t = wall_clock64();
-  }
-  if (threadIdx.x == 0) { out[0] = t0; out[1] = t; }
-}
-// Heavy-first dispatch order for the next launch: counting sort of the envs by the cost proxy of their
-// last step (constraint rows x solver sweeps, counts[4e+3]), most expensive first (LPT scheduling of
-// the 4096 blocks over the resident slots).  One block; the order inside a cost bin is arbitrary,
-// which cannot change results (envs are independent).
-__global__ __launch_bounds__(1024) void hb_order_kernel(const int* counts, int* order, int* keys, int e0, int n, int slot, int shift) {
-  // sorts envs e0 .. e0+n-1 into order[e0 .. e0+n-1], most expensive first; cost = counts[env][slot] >> shift, 256 bins
-  __shared__ int hist[256];
-  __shared__ int base[256];
-  const int tid = threadIdx.x;
-  if (tid < 256) hist[tid] = 0;
-  __syncthreads();
-  for (int e = e0 + tid; e < e0 + n; e += blockDim.x) {
-    int key = min(255, counts[kCountStride * e + slot] >> shift);
-    keys[e] = key;  // read ONCE: the slow lane of two-lane stepping may be writing counts beside this kernel, and a key that changed
-                    // between the two passes would leave an env out of the permutation
-    atomicAdd(&hist[255 - key], 1);  // bin 0 = most expensive
-  }
-  __syncthreads();
-  // exclusive prefix sum of the 256 bins (Hillis-Steele on 256 threads: 8 rounds instead of a 256-step serial loop
-  // on one thread, which was most of this kernel's 9 us on the critical path of every fourth step)
-  if (tid < 256) base[tid] = hist[tid];
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    int v = 0;
-    if (tid < 256 && tid >= o) v = base[tid - o];
-    __syncthreads();
-    if (tid < 256) base[tid] += v;
-    __syncthreads();
-  }
-  if (tid < 256) base[tid] += e0 - hist[tid];  // inclusive -> exclusive, offset by the segment start
-  __syncthreads();
-  for (int e = e0 + tid; e < e0 + n; e += blockDim.x) {
-    const int key = keys[e];
-    order[atomicAdd(&base[255 - key], 1)] = e;
-  }
-}
-
-// benchmark controls: ctrl[t][e][i] = 2*H(1+t0+t+1000*(env_offset+e), i+2) - 1  (testspeed.cc:64-80)
-__global__ void hb_halton_ctrl_kernel(float* out, int T, int n_env, int nu, int t0, int env_offset) {
-  size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)T * n_env * nu;
-  if (idx >= total) return;
-  int i = (int)(idx % nu);
-  size_t r = idx / nu;
-  int e = (int)(r % n_env), t = (int)(r / n_env);
-  out[idx] = 2.f * halton(1 + t0 + t + 1000 * (env_offset + e), i + 2) - 1.f;
 }
 
 hipError_t launch_reset(const DevModel& M, float* state, int* status, const uint8_t* mask, const float* qpos_src, const int* episode, int n_env, float perturb,
@@ -878,17 +612,10 @@ hipError_t launch_action(const float* action, float* prev, float* latest, float*
   hipLaunchKernelGGL(hb_action_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, action, prev, latest, ctrl, n);
   return hipGetLastError();
 }
-hipError_t launch_env(const DevModel& M, const EnvConfig& cfg, const EnvRand& R, const EnvRandState& S, float* state, const float* qfrc, const int* counts, float* prev,
-                      float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated,
-                      const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs, int* seen,
-                      const ObsExtArgs* ext, const CmdArgs* cmd, const FeetArgs* feet) {
+hipError_t launch_env(const DevModel& M, const EnvArgs& G, hipStream_t stream) {
   (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
   const int per_block = 256 / kEnvLanes;
-  const CmdArgs K = cmd ? *cmd : CmdArgs{};  // (none: a null record, and nothing else is read)
-  const FeetArgs A = feet ? *feet : FeetArgs{};  // (the same)
-  const ObsExtArgs X = ext ? *ext : ObsExtArgs{M.nobs, 0, 0, nullptr, nullptr};  // (none: rows of the base observation alone)
-  hipLaunchKernelGGL(hb_env_kernel, dim3((n_env + per_block - 1) / per_block), dim3(256), (size_t)per_block * ((M.nstate + 3) & ~3) * sizeof(float), stream, M, cfg, R, S, state, qfrc, counts, prev, latest, qpos_src, episode, status, obs,
-                     reward, terminated, truncated, mask, observe, D, dr, dr_stride, n_env, env_offset, term_obs, seen, X, K, A);
+  hipLaunchKernelGGL(hb_env_kernel, dim3((G.n_env + per_block - 1) / per_block), dim3(256), (size_t)per_block * ((M.nstate + 3) & ~3) * sizeof(float), stream, M, G);
   return hipGetLastError();
 }
 hipError_t launch_feet_reset(FeetRec* rec, const float* state, int nstate, int n_feet, const uint8_t* mask, int n_env, hipStream_t stream) {
@@ -906,60 +633,6 @@ hipError_t launch_domain_rand(const DevModel& M, const DomainRand& D, float* dr,
                               hipStream_t stream) {
   (void)hipGetLastError();
   hipLaunchKernelGGL(hb_domain_rand_kernel, dim3((n_env + 256 / kDrawLanes - 1) / (256 / kDrawLanes)), dim3(256), 0, stream, M, D, dr, stride, episode, mask, n_env, env_offset);
-  return hipGetLastError();
-}
-hipError_t launch_probe_spin(unsigned long long* out, unsigned ticks, hipStream_t stream) {
-  hipLaunchKernelGGL(hb_probe_spin_kernel, dim3(1), dim3(64), 0, stream, out, ticks);
-  return hipGetLastError();
-}
-hipError_t launch_order(const int* counts, int* order, int n_env, int e0, int n, hipStream_t stream, int slot, int shift) {
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(hb_order_kernel, dim3(1), dim3(1024), 0, stream, counts, order, order + n_env, e0, n, slot, shift);
-  return hipGetLastError();
-}
-hipError_t launch_mlp_layer(const float* X, const float* W, const float* bias, float* Y, int Mrows, int K, int N, int act, hipStream_t stream) {
-  (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
-  hipLaunchKernelGGL(hb_mlp_layer_kernel, dim3((Mrows + 31) / 32, (N + 31) / 32), dim3(kGroup), (size_t)32 * (K + 1) * sizeof(float), stream, X, W, bias, Y, Mrows, K, N, act);
-  return hipGetLastError();
-}
-hipError_t launch_policy_lean(const DevModel& M, const PolicyDesc& pd, const float* state, float* ctrl, float* act, int n_env, hipStream_t stream) {
-  (void)hipGetLastError();
-  if (pd.act == kActTanh) hipLaunchKernelGGL(hb_policy_lean_kernel, dim3((n_env + 15) / 16), dim3(256), 0, stream, M, pd, state, ctrl, act, n_env);
-  else hipLaunchKernelGGL(hb_policy_lean_act_kernel, dim3((n_env + 15) / 16), dim3(256), 0, stream, M, pd, state, ctrl, act, n_env);
-  return hipGetLastError();
-}
-hipError_t launch_policy(const DevModel& M, const PolicyDesc& pd, const float* state, float* ctrl, int n_env, hipStream_t stream) {
-  const size_t shmem = ((size_t)32 * pd.ldx + 8 * 256) * sizeof(float);
-  (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
-  if (pd.act == kActTanh) hipLaunchKernelGGL(hb_policy_kernel, dim3((n_env + 15) / 16), dim3(512), shmem, stream, M, pd, state, ctrl, n_env);
-  else hipLaunchKernelGGL(hb_policy_act_kernel, dim3((n_env + 15) / 16), dim3(512), shmem, stream, M, pd, state, ctrl, n_env);
-  return hipGetLastError();
-}
-hipError_t launch_halton_ctrl(float* out, int T, int n_env, int nu, int t0, int env_offset, hipStream_t stream) {
-  size_t total = (size_t)T * n_env * nu;
-  (void)hipGetLastError();  // the result below must be this launch's, not an older call's sticky error
-  hipLaunchKernelGGL(hb_halton_ctrl_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, out, T, n_env, nu, t0, env_offset);
-  return hipGetLastError();
-}
-hipError_t launch_stand_cost(const float* rows, int H, int n_env, const StandTask& K, const int* status, float* total, float* costs, hipStream_t stream) {
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(hb_stand_cost_kernel, dim3((n_env + 127) / 128), dim3(128), 0, stream, rows, H, n_env, K, status, total, costs);
-  return hipGetLastError();
-}
-hipError_t launch_walk_cost(const float* rows, int H, int n_env, const WalkTask& K, const int* status, float* total, float* costs, hipStream_t stream) {
-  (void)hipGetLastError();
-  hipLaunchKernelGGL(hb_walk_cost_kernel, dim3((n_env + 63) / 64), dim3(64), 0, stream, rows, H, n_env, K, status, total, costs);
-  return hipGetLastError();
-}
-hipError_t launch_cost_terms(const float* residual, int n, int nres, const CostSpec& K, float* terms, float* cost, hipStream_t stream) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(hb_cost_terms_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, residual, n, nres, K, terms, cost);
-  return hipGetLastError();
-}
-hipError_t launch_spline_tape(const DevModel& M, const float* knots, const float* times, int P, int interp, float time0, float dt, int T, int n_env, float* tape, hipStream_t stream) {
-  (void)hipGetLastError();
-  const size_t total = (size_t)T * n_env * M.nu;
-  hipLaunchKernelGGL(hb_spline_tape_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, M, knots, times, P, interp, time0, dt, T, n_env, tape);
   return hipGetLastError();
 }
 }  // namespace hb

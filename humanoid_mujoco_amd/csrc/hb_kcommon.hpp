@@ -1,4 +1,4 @@
-// hb_kcommon.hpp - device helpers shared by the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip):
+// hb_kcommon.hpp - device helpers shared by the kernel translation units (hb_step.hip, hb_step_duo.hip, hb_narrow.hip, hb_env.hip, hb_rollout.hip, hb_policy.hip, hb_kin.hip):
 // wave idioms, 3-vector / quaternion / spatial algebra, the primitive colliders, constraint impedance, counter-based random numbers and
 // the dense eliminations on the matrix cores.  Everything is __forceinline__: no device function crosses a translation unit.
 #pragma once

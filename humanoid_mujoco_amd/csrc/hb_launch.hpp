@@ -1,4 +1,4 @@
-// hb_launch.hpp — host-callable launchers implemented in the kernel translation units (hb_step.hip, hb_narrow.hip, hb_env.hip, hb_kin.hip, hb_ray.hip, hb_dyn.hip)
+// hb_launch.hpp — host-callable launchers implemented in the kernel translation units (hb_step.hip, hb_narrow.hip, hb_env.hip, hb_rollout.hip, hb_policy.hip, hb_kin.hip, hb_ray.hip, hb_dyn.hip, ...)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "hb_device.hpp"
@@ -52,12 +52,8 @@ hipError_t launch_reset_check(const int* counts, const uint8_t* terminated, cons
                               hipStream_t stream);
 hipError_t launch_obs(const DevModel& M, const float* state, float* obs, int n_env, hipStream_t stream);
 hipError_t launch_action(const float* action, float* prev, float* latest, float* ctrl, int n, hipStream_t stream);
-hipError_t launch_env(const DevModel& M, const EnvConfig& cfg, const EnvRand& R, const EnvRandState& S, float* state, const float* qfrc, const int* counts, float* prev,
-                      float* latest, const float* qpos_src, int* episode, int* status, float* obs, float* reward, uint8_t* terminated, uint8_t* truncated,
-                      const uint8_t* mask, int observe, const DomainRand& D, float* dr, int dr_stride, int n_env, int env_offset, hipStream_t stream, float* term_obs = nullptr, int* seen = nullptr,
-                      const ObsExtArgs* ext = nullptr,   // ext null: rows of M.nobs floats, the base observation alone
-                      const CmdArgs* cmd = nullptr,      // cmd null: no velocity commands
-                      const FeetArgs* feet = nullptr);   // feet null: no foot-contact terms
+// reward / termination / auto-reset / observation row of G.n_env envs (hb_env.hip: hb_env_kernel)
+hipError_t launch_env(const DevModel& M, const EnvArgs& G, hipStream_t stream);
 // the feet records at an episode start outside the env kernel: t_last = the env's state time, every foot's bit set
 hipError_t launch_feet_reset(FeetRec* rec, const float* state, int nstate, int n_feet, const uint8_t* mask, int n_env, hipStream_t stream);
 // draw 0 of the episodes in `episode` for every env (or those of `mask`): the command state at an episode start outside the env kernel

@@ -1,4 +1,4 @@
-// hb_policy_kernels.inl - included twice by hb_env.hip (HB_ACT_ANY 0, then 1): the kernels as they were for tanh networks - tanhf written into the hooks, the
+// hb_policy_kernels.inl - included twice by hb_policy.hip (HB_ACT_ANY 0, then 1): the kernels as they were for tanh networks - tanhf written into the hooks, the
 // text, registers and bits they had before a network could choose its hidden activation - and their *_act_kernel twins with the
 // block-uniform run-time choice of mlp_act / mlp_act_slope (hb_kcommon.hpp), which costs a hook two to four registers and some scalar
 // work (profiles/act_kernel_resources.txt, profiles/act_bench.txt).  The launchers pick the twin when a network is not tanh.

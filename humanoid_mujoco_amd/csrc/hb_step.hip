@@ -1,6 +1,7 @@
 // hb_step.hip — the fused physics-step kernel for gfx950 (MI355X).
-// (one of four kernel translation units: hb_step.hip - this file, the fused step kernels; hb_narrow.hip - the staged step's pose and
-// narrowphase kernels; hb_env.hip - env adapter, policy, task costs, reset; hb_step_duo.hip - two envs per wave)
+// (one of the kernel translation units: hb_step.hip - this file, the fused step kernels; hb_narrow.hip - the staged step's pose and
+// narrowphase kernels; hb_step_duo.hip - two envs per wave; hb_env.hip - env adapter, reset; hb_rollout.hip - task costs, spline tape,
+// dispatch order; hb_policy.hip - the policy MLP)
 //
 // One 64-lane wavefront advances ONE environment through the whole mj_step pipeline
 // (reference API: simulation/mujoco/include/mujoco/mujoco.h:120 mj_step; stage list

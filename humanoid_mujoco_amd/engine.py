@@ -48,6 +48,11 @@ class HbObsExt(ctypes.Structure):
                 ("scan_lo", ctypes.c_float), ("scan_hi", ctypes.c_float)]
 
 
+class HbEnvRow(ctypes.Structure):
+    """struct hb_env_row (include/hb.h): offset and count of every part of an observation row of the env adapter, and its width."""
+    _fields_ = [(n, ctypes.c_int) for n in ("base", "prev_action", "n_prev_action", "scan", "n_scan", "foot_contact", "n_foot_contact", "command", "n_command", "width")]
+
+
 class HbEnvCommands(ctypes.Structure):
     """hb_env_commands (include/hb.h): per-env velocity commands - ranges, schedule, reward weight, frame, observation."""
     _fields_ = [("seed", ctypes.c_uint)] + [(n, ctypes.c_float) for n in ("vx_min", "vx_max", "vy_min", "vy_max", "yaw_min", "yaw_max", "resample_time",
@@ -431,6 +436,7 @@ def lib():
     L.hb_env_step_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     L.hb_env_obs_extend.argtypes = [vp, ctypes.POINTER(HbObsExt)]
     L.hb_env_nobs.argtypes = [vp]
+    L.hb_env_row.argtypes = [vp, ctypes.POINTER(HbEnvRow)]
     L.hb_env_default_commands.argtypes = [vp, ctypes.POINTER(HbEnvCommands)]
     L.hb_env_commands_check.argtypes = [vp, ctypes.POINTER(HbEnvCommands)]
     L.hb_env_commands_configure.argtypes = [vp, ctypes.POINTER(HbEnvCommands)]
@@ -1322,6 +1328,13 @@ class Batch:
     def env_nobs(self):
         """the width of every observation row the env adapter produces: the model's nobs and what obs_extend appended (hb_env_nobs)"""
         return int(lib().hb_env_nobs(self._h))
+
+    def env_row(self):
+        """the layout of those rows, [base | prev_action | scan | foot_contact | command]: an HbEnvRow with the offset and the count of
+        every part (count 0: the part is off) and the width (hb_env_row)"""
+        r = HbEnvRow()
+        _check(lib().hb_env_row(self._h, ctypes.byref(r)), "hb_env_row")
+        return r
 
     def obs_extend(self, prev_action=False, height_scan=None):
         """Appends to every observation of the env adapter, on the device (hb_env_obs_extend): prev_action - the nu entries of the action

@@ -159,18 +159,12 @@ class VecEnv:
             self.batch.feet_configure(self.feet_cfg)
             self.contact_forces = True  # (the terms read the contact read-out, so body_contact_forces() is there too)
         self.nobs = self.batch.env_nobs
-        self._layout = {"base": slice(0, self.model.nobs)}
-        if ext_act:
-            self._layout["prev_action"] = slice(self.model.nobs, self.model.nobs + self.model.nu)
-        if ext_scan is not None:
-            n_scan = self._scan[0] * self._scan[1]
-            at = self.model.nobs + (self.model.nu if ext_act else 0)
-            self._layout["height_scan"] = slice(at, at + n_scan)
-        n_cmd = 3 if self.commands_cfg is not None and self.commands_cfg.observe else 0
-        if self.feet_cfg is not None and self.feet_cfg.observe:
-            self._layout["foot_contact"] = slice(self.nobs - n_cmd - self.feet_cfg.n_feet, self.nobs - n_cmd)
-        if n_cmd:
-            self._layout["command"] = slice(self.nobs - 3, self.nobs)
+        row = self.batch.env_row()
+        self._layout = {"base": slice(0, row.base)}
+        for key, part in (("prev_action", "prev_action"), ("height_scan", "scan"), ("foot_contact", "foot_contact"), ("command", "command")):
+            at, count = getattr(row, part), getattr(row, "n_" + part)
+            if count:
+                self._layout[key] = slice(at, at + count)
         self.realism = None
         if realism:
             self.realism = self.batch.env_default_randomization()

@@ -844,7 +844,19 @@ typedef struct hb_obs_ext {
   float scan_offset, scan_scale, scan_lo, scan_hi;
 } hb_obs_ext;
 int hb_env_obs_extend(hb_batch* b, const hb_obs_ext* ext);   /* NULL or all-zero: remove */
-int hb_env_nobs(hb_batch* b);                                /* base nobs + extension (+ 3 with observed commands, below) */
+int hb_env_nobs(hb_batch* b);                                /* the width of a row: hb_env_row's `width` */
+/* The layout of every row the adapter writes, [ base | prev_action | scan | foot_contact | command ]: the offset and the count of each
+ * part (a part that is off has count 0; base begins at 0) and the width.  Read-only; HB_EINVAL for a NULL argument.  (The struct has
+ * no typedef: the function bears the name, so the type is written `struct hb_env_row`.) */
+struct hb_env_row {
+  int base;
+  int prev_action, n_prev_action;
+  int scan, n_scan;
+  int foot_contact, n_foot_contact;
+  int command, n_command;
+  int width;
+};
+int hb_env_row(hb_batch* b, struct hb_env_row* out);
 
 /* ---- velocity commands: every env follows its own commanded planar velocity and yaw rate, drawn, tracked and observed on the device -- */
 

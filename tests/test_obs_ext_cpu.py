@@ -32,6 +32,23 @@ def test_ctypes_struct_matches_the_header(hbmod, tmp_path):
         assert int(out[f]) == getattr(cls, f).offset, f
 
 
+def test_env_row_export_and_mirror(hbmod, tmp_path):
+    """hb_env_row is exported and refuses NULL; engine.HbEnvRow has the size and the field offsets of the header's struct hb_env_row"""
+    import humanoid_mujoco_amd.engine as eng
+    assert hasattr(ctypes.CDLL(hbmod.LIB_PATH), "hb_env_row") and hbmod.lib().hb_env_row(None, None) == -1
+    cls = eng.HbEnvRow
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "hb.h"', 'int main(void) {', 'printf("size %zu\\n", sizeof(struct hb_env_row));']
+    lines += ['printf("%s %%zu\\n", offsetof(struct hb_env_row, %s));' % (f, f) for f, _ in cls._fields_]
+    src = tmp_path / "row.c"
+    src.write_text("\n".join(lines + ["return 0; }"]))
+    exe = tmp_path / "row"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    out = dict(l.split() for l in subprocess.check_output([str(exe)], text=True).splitlines())
+    assert int(out["size"]) == ctypes.sizeof(cls) == 40
+    for f, _ in cls._fields_:
+        assert int(out[f]) == getattr(cls, f).offset, f
+
+
 def _terrain_case(points, cutoff):
     """world-frame downward rays from `points` at the terrain model's static geoms"""
     c = ray_cases.case("terrain")

@@ -6,6 +6,7 @@ collect_torch window.  Microseconds per collected step for:
   (feet)            every term on, both feet, five penalised and two terminal bodies, the flags observed (the row grows by 2)
   (readout)         contact_forces=True and no feet: the price of the read-out alone, which forces the full step kernel
   (neither)         neither
+  (parent-feet)     (feet),
   (parent-readout)  (readout) and
   (parent-neither)  (neither) in another build of the package, given with --parent DIR: a checkout of the parent commit, built
 Every figure comes from a process of its own, started here one at a time under its own time limit, that builds the env, runs one warm-up
@@ -35,7 +36,7 @@ def child(case, root):
     xs, ys = np.linspace(-0.8, 0.8, 16), np.linspace(-0.5, 0.5, 11)
     kw = dict(domain_randomization=True, seed=1, height_scan=dict(body=1, xs=xs, ys=ys, z0=1.0, cutoff=4.0),
               obs_extend=dict(prev_action=True, height_scan=dict(offset=1.0, scale=1.0, clip=(-1.0, 1.0))), commands=dict(resample_time=0.05))
-    if case == "feet":
+    if case.endswith("feet"):
         kw["feet"] = dict(bodies=("foot_right", "foot_left"), penalised=("shin_right", "shin_left", "lower_arm_right", "lower_arm_left", "pelvis"),
                           terminal=("torso", "head"), observe=1)
     elif case.endswith("readout"):
@@ -59,7 +60,7 @@ def child(case, root):
 
 
 NAMES = {"feet": "(feet)           every term on, flags observed", "readout": "(readout)        contact_forces=True, no feet", "neither": "(neither)        no read-out, no feet",
-         "parent-readout": "(parent-readout) the parent commit's build", "parent-neither": "(parent-neither) the parent commit's build"}
+         "parent-feet": "(parent-feet)    the parent commit's build", "parent-readout": "(parent-readout) the parent commit's build", "parent-neither": "(parent-neither) the parent commit's build"}
 
 
 def main():
@@ -75,7 +76,7 @@ def main():
     import numpy as np
     cases = [("feet", ROOT), ("readout", ROOT), ("neither", ROOT)]
     if args.parent:
-        cases += [("parent-readout", os.path.abspath(args.parent)), ("parent-neither", os.path.abspath(args.parent))]
+        cases += [("parent-" + case, os.path.abspath(args.parent)) for case in ("feet", "readout", "neither")]
     us, info, rounds = {c: [] for c, _ in cases}, {}, []
     for rnd in range(args.rounds):
         for case, root in cases:
@@ -101,7 +102,7 @@ def main():
     lines.append("  the read-out itself (it forces the full step kernel; profiles/contact_readout_bench.txt): %+.1f us per step (%+.2f %%) over (neither); the whole bill of the feet: %+.1f us (%+.2f %%)"
                  % (med["readout"] - med["neither"], 100.0 * (med["readout"] - med["neither"]) / med["neither"], med["feet"] - med["neither"],
                     100.0 * (med["feet"] - med["neither"]) / med["neither"]))
-    for case in ("readout", "neither"):
+    for case in ("feet", "readout", "neither"):
         p = "parent-" + case
         if p in med:
             s = max(spread[case], spread[p])
