@@ -59,6 +59,16 @@ build/hb_learn_check_san: tools/hb_learn_check.cpp $(HDRS)
 	@mkdir -p build
 	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -o $@ tools/hb_learn_check.cpp
 
+# sensor_args (hb_api_rollout.cpp) checked on the host: the unit's other functions need the GPU runtime and the kernels, are not
+# referenced, and are dropped at link time (nothing of HIP is linked); _san: under sanitizers
+SENSOR_CHECK_SRCS := tools/hb_sensor_check.cpp $(CSRC)/hb_api_rollout.cpp $(CSRC)/hb_tables.cpp $(CSRC)/mjcf.cpp $(CSRC)/setconst.cpp $(CSRC)/model_io.cpp $(CSRC)/mesh.cpp
+build/hb_sensor_check: $(SENSOR_CHECK_SRCS) $(HDRS)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -ffunction-sections -Wl,--gc-sections -o $@ $(SENSOR_CHECK_SRCS)
+build/hb_sensor_check_san: $(SENSOR_CHECK_SRCS) $(HDRS)
+	@mkdir -p build
+	g++ $(HOSTFLAGS) -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffunction-sections -Wl,--gc-sections -o $@ $(SENSOR_CHECK_SRCS)
+
 build/hb_testspeed: tools/hb_testspeed.cpp $(LIB) include/hb.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -Wall -Iinclude -o $@ tools/hb_testspeed.cpp -Lhumanoid_mujoco_amd -lhb -Wl,-rpath,'$$ORIGIN/../humanoid_mujoco_amd'
@@ -71,7 +81,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) build/hb_compile build/hb_tables build/hb_learn_check build/hb_learn_check_san build/hb_testspeed
+	rm -f $(LIB) build/hb_compile build/hb_tables build/hb_learn_check build/hb_learn_check_san build/hb_sensor_check build/hb_sensor_check_san build/hb_testspeed
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

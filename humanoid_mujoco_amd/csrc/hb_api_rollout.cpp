@@ -344,84 +344,84 @@ int hb_state_from_proto(hb_batch* b, int env, const unsigned char* buf, int len)
   return HB_OK;
 }
 
+// the row of a spec (with tail parts: of a model with these sizes)
+static SensorRow spec_row(const hb_sensor_spec& s, int tail = 0, int nq = 0, int nv = 0, int nu = 0) {
+  return sensor_row(s.n_framepos, s.subtree_body >= 0, s.n_frameaxis, s.n_framelinvel, s.n_subtreelinvel, s.n_touch, s.n_contactforce, s.n_imu, s.n_frameacc, tail, nq, nv, nu);
+}
 int hb_sensor_size(const hb_sensor_spec* spec) {
   if (!spec || spec->n_framepos < 0 || spec->n_framepos > HB_MAX_FRAMEPOS) return HB_EINVAL;
   if (spec->n_frameaxis < 0 || spec->n_frameaxis > 8 || spec->n_framelinvel < 0 || spec->n_framelinvel > 8 || spec->n_subtreelinvel < 0 || spec->n_subtreelinvel > 4) return HB_EINVAL;
   if (spec->n_touch < 0 || spec->n_touch > 8 || spec->n_contactforce < 0 || spec->n_contactforce > 4) return HB_EINVAL;
   if (spec->n_imu < 0 || spec->n_imu > 4 || spec->n_frameacc < 0 || spec->n_frameacc > 4) return HB_EINVAL;
-  return 3 * spec->n_framepos + (spec->subtree_body >= 0 ? 6 : 0) + 3 * (spec->n_frameaxis + spec->n_framelinvel + spec->n_subtreelinvel) + spec->n_touch +
-         3 * spec->n_contactforce + 6 * (spec->n_imu + spec->n_frameacc);
+  return spec_row(*spec).width;
+}
+int hb_sensor_row(const hb_sensor_spec* spec, struct hb_sensor_row* out) {
+  static_assert(sizeof(struct hb_sensor_row) == offsetof(SensorRow, width) + sizeof(int), "hb_sensor_row is SensorRow up to its width");
+  if (!out || hb_sensor_size(spec) <= 0) return HB_EINVAL;
+  const SensorRow row = spec_row(*spec);
+  memcpy(out, &row, sizeof *out);
+  return HB_OK;
 }
 
-// fills the sensor fields of P and sizes the device read-out buffer for T steps
-static int sensor_setup(hb_batch* b, const hb_sensor_spec* spec, int T, BatchPtrs& P) {
-  const Model& m = b->model->m;
-  const int ns = hb_sensor_size(spec);
-  if (ns <= 0) return HB_EINVAL;
-  if (spec->n_imu + spec->n_frameacc > 0 && (b->D.dm.nfric || b->D.dm.neq_rows)) return HB_EUNSUPPORTED;  // (friction loss, equality rows: no kernel with the body-acceleration read-out)
-  for (int k = 0; k < spec->n_framepos; k++) if (spec->framepos_body[k] < 0 || spec->framepos_body[k] >= m.nbody) return HB_EINVAL;
-  int tree = -1;
-  if (spec->subtree_body >= 0) {
+extern "C++" {
+namespace hb {
+// The sensor read-out of `spec` on this model with the tail parts `tail` (kSensor*): the spec checked, the row laid out and every part's
+// table filled (S.out stays null).  Needs no batch: tools/hb_sensor_check.cpp runs it on the host.
+int sensor_args(const Model& m, const DevModel& dm, const hb_sensor_spec* spec, int tail, SensorArgs& S) {
+  memset(&S, 0, sizeof S);  // (BatchPtrs is compared byte for byte)
+  if (hb_sensor_size(spec) <= 0) return HB_EINVAL;
+  if (spec->n_imu + spec->n_frameacc > 0 && (dm.nfric || dm.neq_rows)) return HB_EUNSUPPORTED;  // (friction loss, equality rows: no kernel with the body-acceleration read-out)
+  S.row = spec_row(*spec, tail, dm.nq, dm.nv, dm.nu);
+  const SensorRow& R = S.row;
+  // a part's bodies, each in [first, nbody)
+  auto bodies = [&](const int* body, int n, int first, auto&& put) {
+    for (int k = 0; k < n; k++) { if (body[k] < first || body[k] >= m.nbody) return false; put(k, body[k]); }
+    return true;
+  };
+  const auto into = [](int* t) { return [t](int k, int id) { t[k] = id; }; };
+  const auto packed = [](auto& t) { return [&t](int k, int id) { t.set(k, id); }; };
+  if (!bodies(spec->framepos_body, R.n_framepos, 0, into(S.body)) || !bodies(spec->frameaxis_body, R.n_axis, 0, into(S.axis_body)) ||
+      !bodies(spec->framelinvel_body, R.n_linvel, 1, into(S.linvel_body)) || !bodies(spec->touch_body, R.n_touch, 0, packed(S.touch_body)) ||
+      !bodies(spec->contactforce_body, R.n_cfrc, 0, packed(S.cfrc_body)) || !bodies(spec->imu_body, R.n_imu, 0, packed(S.imu_body)) ||
+      !bodies(spec->frameacc_body, R.n_facc, 0, packed(S.facc_body)))
+    return HB_EINVAL;
+  for (int k = 0; k < R.n_framepos; k++) for (int i = 0; i < 3; i++) S.off[k][i] = spec->framepos_offset[k][i];
+  for (int k = 0; k < R.n_imu; k++) for (int i = 0; i < 3; i++) S.imu_off[k][i] = spec->imu_offset[k][i];
+  if (R.n_subtree) {
     if (spec->subtree_body < 1 || spec->subtree_body >= m.nbody || m.body_parentid[spec->subtree_body] != 0) return HB_EINVAL;  // a tree root
-    for (int bd = 1, t = 0; bd <= spec->subtree_body; bd++)
-      if (m.body_parentid[bd] == 0) { if (bd == spec->subtree_body) tree = t; t++; }
-    if (tree < 0) return HB_EINVAL;
+    for (int bd = 1; bd < spec->subtree_body; bd++) if (m.body_parentid[bd] == 0) S.tree++;
   }
-  const int rc = b->d_sensor_out.reserve((size_t)T * b->n_env * ns);
-  if (rc != HB_OK) return rc;
-  P.sensor_out = b->d_sensor_out; P.sensor_stride = ns; P.sensor_nframe = spec->n_framepos; P.sensor_tree = tree;
-  for (int k = 0; k < spec->n_framepos; k++) {
-    P.sensor_body[k] = spec->framepos_body[k];
-    for (int i = 0; i < 3; i++) P.sensor_off[k][i] = spec->framepos_offset[k][i];
+  for (int k = 0; k < R.n_axis; k++) {
+    if (spec->frameaxis_which[k] != 0 && spec->frameaxis_which[k] != 2) return HB_EINVAL;
+    S.axis_which |= (unsigned)spec->frameaxis_which[k] << (2 * k);
   }
-  P.sensor_naxis = spec->n_frameaxis; P.sensor_nlinvel = spec->n_framelinvel; P.sensor_nsub = spec->n_subtreelinvel;
-  for (int k = 0; k < spec->n_frameaxis; k++) {
-    if (spec->frameaxis_body[k] < 0 || spec->frameaxis_body[k] >= m.nbody || (spec->frameaxis_which[k] != 0 && spec->frameaxis_which[k] != 2)) return HB_EINVAL;
-    P.sensor_axis_body[k] = spec->frameaxis_body[k]; P.sensor_axis_which[k] = spec->frameaxis_which[k];
-  }
-  for (int k = 0; k < spec->n_framelinvel; k++) {
-    if (spec->framelinvel_body[k] < 1 || spec->framelinvel_body[k] >= m.nbody) return HB_EINVAL;
-    P.sensor_linvel_body[k] = spec->framelinvel_body[k];
-  }
-  for (int k = 0; k < spec->n_subtreelinvel; k++) {
+  for (int k = 0; k < R.n_sub; k++) {
     const int root = spec->subtreelinvel_body[k];
     if (root < 1 || root >= m.nbody) return HB_EINVAL;
-    unsigned long long mask = 0;
     double mass = 0;
     for (int bd = 1; bd < m.nbody; bd++)
       for (int a = bd; a > 0; a = m.body_parentid[a])
-        if (a == root) { mask |= 1ull << bd; mass += m.body_mass[bd]; break; }
-    P.sensor_submask[k] = mask;
-    P.sensor_subinv[k] = mass > 1e-15 ? (float)(1.0 / mass) : 0.f;
+        if (a == root) { S.submask[k] |= 1ull << bd; mass += m.body_mass[bd]; break; }
+    S.subinv[k] = mass > 1e-15 ? (float)(1.0 / mass) : 0.f;
   }
-  // touch / contact-force entries: written by the step kernel's contact-force epilogue, so the launch carries the read-out buffers
-  P.sensor_ntouch = spec->n_touch; P.sensor_ncfrc = spec->n_contactforce;
-  for (int k = 0; k < spec->n_touch; k++) {
-    if (spec->touch_body[k] < 0 || spec->touch_body[k] >= m.nbody) return HB_EINVAL;
-    P.sensor_touch_body[k] = spec->touch_body[k];
-  }
-  for (int k = 0; k < spec->n_contactforce; k++) {
-    if (spec->contactforce_body[k] < 0 || spec->contactforce_body[k] >= m.nbody) return HB_EINVAL;
-    P.sensor_cfrc_body[k] = spec->contactforce_body[k];
-  }
-  if (spec->n_touch + spec->n_contactforce > 0) {
+  return HB_OK;
+}
+}  // namespace hb
+}  // extern "C++"
+
+// the sensor read-out of `spec` with the tail parts `tail` in P, the device buffer sized for T rows per env, and the read-outs the
+// contact and acceleration parts are written by
+static int sensor_setup(hb_batch* b, const hb_sensor_spec* spec, int tail, int T, BatchPtrs& P) {
+  int rc = sensor_args(b->model->m, b->D.dm, spec, tail, P.sensor);
+  if (rc != HB_OK) return rc;
+  const SensorRow& R = P.sensor.row;
+  if ((rc = b->d_sensor_out.reserve((size_t)T * b->n_env * R.stride)) != HB_OK) return rc;
+  P.sensor.out = b->d_sensor_out;
+  if (R.n_touch + R.n_cfrc > 0) {  // written by the step kernel's contact-force epilogue, so the launch carries the read-out buffers
     if (alloc_contact_readout(b) != HB_OK) return HB_ENOMEM;
     P.contact_force = b->d_contact_force; P.body_contact = b->d_body_contact;
   }
-  // accelerometer / gyro and frame-acceleration entries: written by the body-acceleration epilogue, likewise
-  P.sensor_nimu = spec->n_imu; P.sensor_nfacc = spec->n_frameacc;
-  P.sensor_acc_off = ns - 6 * (spec->n_imu + spec->n_frameacc);  // (they are the last entries hb_sensor_size counts)
-  P.sensor_behind = spec->n_touch + 3 * spec->n_contactforce + 6 * (spec->n_imu + spec->n_frameacc);
-  for (int k = 0; k < spec->n_imu; k++) {
-    if (spec->imu_body[k] < 0 || spec->imu_body[k] >= m.nbody) return HB_EINVAL;
-    P.sensor_imu_body[k] = spec->imu_body[k];
-    for (int i = 0; i < 3; i++) P.sensor_imu_off[k][i] = spec->imu_offset[k][i];
-  }
-  for (int k = 0; k < spec->n_frameacc; k++) {
-    if (spec->frameacc_body[k] < 0 || spec->frameacc_body[k] >= m.nbody) return HB_EINVAL;
-    P.sensor_facc_body[k] = spec->frameacc_body[k];
-  }
-  if (spec->n_imu + spec->n_frameacc > 0) {
+  if (R.n_imu + R.n_facc > 0) {  // written by the body-acceleration epilogue, likewise
     if (alloc_body_acc_readout(b) != HB_OK) return HB_ENOMEM;
     P.body_acc = b->d_body_acc; P.body_acc_park = b->d_body_acc_park;
   }
@@ -436,21 +436,21 @@ int hb_rollout_sensors(hb_batch* b, const float* ctrl, int T, const hb_sensor_sp
   const size_t nq_out = (size_t)T * b->n_env * b->D.dm.nq;
   BatchPtrs P = make_ptrs(b);
   P.ctrl = b->d_ctrl; P.ctrl_mode = 1; P.qpos_out = qpos_out ? b->d_qpos_out.get() : nullptr;
-  rc = sensor_setup(b, spec, T, P);
+  rc = sensor_setup(b, spec, 0, T, P);
   if (rc != HB_OK) return rc;
   rc = launch_steps(b, P, T);
   if (rc != HB_OK) return rc;
-  HB_HIP(hipMemcpyAsync(sensor_out, b->d_sensor_out, (size_t)T * b->n_env * P.sensor_stride * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  HB_HIP(hipMemcpyAsync(sensor_out, b->d_sensor_out, (size_t)T * b->n_env * P.sensor.row.stride * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
   if (qpos_out) HB_HIP(hipMemcpyAsync(qpos_out, b->d_qpos_out, nq_out * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   return HB_OK;
 }
 
 // Trajectory::Rollout's data flow for a task cost on the device: `horizon - 1` steps from the current state with the
-// read-out row of every step (sensors of `spec`, then the state / control parts in `flags`), then one mj_forward with the
-// last action repeated (zero when horizon = 1) for the terminal row.  Leaves `horizon` rows of `*stride` floats in
+// read-out row of every step (sensors of `spec`, then the state / control parts in `tail`), then one mj_forward with the
+// last action repeated (zero when horizon = 1) for the terminal row.  Leaves `horizon` rows laid out as `*row` in
 // b->d_sensor_out and room for horizon + 1 floats per env in b->d_task_out; the status words are cleared first.
-static int rollout_rows(hb_batch* b, const float* ctrl, int H, const hb_sensor_spec* spec, int flags, int* stride) {
+static int rollout_rows(hb_batch* b, const float* ctrl, int H, const hb_sensor_spec* spec, int tail, SensorRow* row) {
   const DevModel& dm = b->D.dm;
   const int N = b->n_env, nu = dm.nu;
   const size_t n = (size_t)(H - 1) * N * nu;
@@ -467,12 +467,10 @@ static int rollout_rows(hb_batch* b, const float* ctrl, int H, const hb_sensor_s
   // failure is a property of THIS rollout (CheckWarnings looks at the warnings of the rollout's own mjData)
   HB_HIP(hipMemsetAsync(b->d_status, 0, (size_t)N * sizeof(int), main_stream(b)));
   BatchPtrs P = make_ptrs(b);
-  rc = sensor_setup(b, spec, H, P);
+  rc = sensor_setup(b, spec, tail, H, P);
   if (rc != HB_OK) return rc;
-  *stride = P.sensor_stride + ((flags & 4) ? dm.nq : 0) + ((flags & 1) ? dm.nv : 0) + ((flags & 2) ? nu : 0);
-  if ((rc = b->d_sensor_out.reserve((size_t)H * N * *stride)) != HB_OK) return rc;
+  *row = P.sensor.row;
   if ((rc = b->d_task_out.reserve((size_t)(H + 1) * N)) != HB_OK) return rc;
-  P.sensor_out = b->d_sensor_out; P.sensor_stride = *stride; P.sensor_flags = flags;
   if (H > 1) {
     P.ctrl = b->d_ctrl; P.ctrl_mode = 1;
     rc = launch_steps(b, P, H - 1);
@@ -481,7 +479,7 @@ static int rollout_rows(hb_batch* b, const float* ctrl, int H, const hb_sensor_s
   // final mj_forward with the last action repeated (trajectory.cc:188-202)
   BatchPtrs F = P;
   F.ctrl = b->d_ctrl + (H > 1 ? (size_t)(H - 2) * N * nu : 0); F.ctrl_mode = 0; F.integrate = 0;
-  F.sensor_out = b->d_sensor_out + (size_t)(H - 1) * N * *stride;
+  F.sensor.out = b->d_sensor_out + (size_t)(H - 1) * N * row->stride;
   F.blk0 = 0; F.nblk = N;
   HB_HIP(launch_batch_step(b, F, 1, main_stream(b)));
   return HB_OK;
@@ -550,14 +548,13 @@ int hb_rollout_task_walk(hb_batch* b, const float* ctrl, int H, const hb_task_wa
   spec.framelinvel_body[0] = task->torso_body; spec.framelinvel_body[1] = task->foot_right_body; spec.framelinvel_body[2] = task->foot_left_body;
   spec.n_subtreelinvel = 1;
   spec.subtreelinvel_body[0] = task->waist_lower_body;
-  int stride = 0;
-  int rc = rollout_rows(b, ctrl, H, &spec, /*qpos | ctrl*/ 4 | 2, &stride);
+  SensorRow R;
+  int rc = rollout_rows(b, ctrl, H, &spec, kSensorQpos | kSensorCtrl, &R);
   if (rc != HB_OK) return rc;
   WalkTask K;
   memset(&K, 0, sizeof K);
-  K.o_torso = 0; K.o_foot_r = 3; K.o_foot_l = 6; K.o_pelvis = 9; K.o_com = 12; K.o_vel = 15; K.o_axes = 18; K.o_linvel = K.o_axes + 24; K.o_sub = K.o_linvel + 9;
-  K.o_qpos = K.o_sub + 3; K.o_ctrl = K.o_qpos + dm.nq; K.nq = dm.nq; K.nu = dm.nu; K.stride = stride;
-  if (K.o_ctrl + dm.nu != stride) return HB_EINVAL;
+  K.o_torso = R.framepos; K.o_foot_r = R.framepos + 3; K.o_foot_l = R.framepos + 6; K.o_pelvis = R.framepos + 9; K.o_com = R.subtree; K.o_vel = R.subtree + 3;
+  K.o_axes = R.axis; K.o_linvel = R.linvel; K.o_sub = R.sub; K.o_qpos = R.qpos; K.o_ctrl = R.ctrl; K.nq = dm.nq; K.nu = dm.nu; K.stride = R.stride;
   K.height_goal = task->height_goal; K.speed_goal = task->speed_goal; K.risk = task->risk; K.nterm = task->n_term;
   for (int k = 0; k < task->n_term; k++) { K.dim[k] = task->dim[k]; K.norm[k] = task->norm[k]; K.weight[k] = task->weight[k]; K.p[k] = task->norm_p[k][0]; K.q[k] = task->norm_p[k][1]; }
   HB_HIP(launch_walk_cost(b->d_sensor_out, H, b->n_env, K, b->d_status, b->d_task_out, costs ? b->d_task_out + b->n_env : nullptr, main_stream(b)));
@@ -602,15 +599,13 @@ int hb_rollout_task_stand(hb_batch* b, const float* ctrl, int H, const hb_task_s
   }
   spec.subtree_body = task->subtree_body;
   if (spec.subtree_body < 0) return HB_EINVAL;
-  const int nu = dm.nu, nv = dm.nv;
-  int stride = 0;
-  int rc = rollout_rows(b, ctrl, H, &spec, /*qvel | ctrl*/ 1 | 2, &stride);
+  SensorRow R;
+  int rc = rollout_rows(b, ctrl, H, &spec, kSensorQvel | kSensorCtrl, &R);
   if (rc != HB_OK) return rc;
   StandTask K;
   memset(&K, 0, sizeof K);
-  K.n_feet = task->n_feet; K.o_head = 0; K.o_feet = 3; K.o_com = 3 * spec.n_framepos; K.o_vel = K.o_com + 3; K.o_qvel = K.o_com + 6; K.o_ctrl = K.o_qvel + nv;
-  K.nv = nv; K.nu = nu; K.stride = stride;
-  if (K.o_ctrl + nu != stride) return HB_EINVAL;
+  K.n_feet = task->n_feet; K.o_head = R.framepos; K.o_feet = R.framepos + 3; K.o_com = R.subtree; K.o_vel = R.subtree + 3; K.o_qvel = R.qvel; K.o_ctrl = R.ctrl;
+  K.nv = dm.nv; K.nu = dm.nu; K.stride = R.stride;
   K.height_goal = task->height_goal; K.risk = task->risk;
   for (int k = 0; k < 5; k++) { K.norm[k] = task->norm[k]; K.weight[k] = task->weight[k]; K.p[k] = task->norm_p[k][0]; K.q[k] = task->norm_p[k][1]; }
   HB_HIP(launch_stand_cost(b->d_sensor_out, H, b->n_env, K, b->d_status, b->d_task_out, costs ? b->d_task_out + b->n_env : nullptr, main_stream(b)));
@@ -625,10 +620,10 @@ int hb_sensors(hb_batch* b, const float* ctrl, const hb_sensor_spec* spec, float
   else if (n) HB_HIP(hipMemsetAsync(ctrl_for_write(b), 0, n * sizeof(float), main_stream(b)));
   BatchPtrs P = make_ptrs(b);
   P.ctrl = b->d_ctrl; P.ctrl_mode = 0; P.integrate = 0;
-  int rc = sensor_setup(b, spec, 1, P);
+  int rc = sensor_setup(b, spec, 0, 1, P);
   if (rc != HB_OK) return rc;
   HB_HIP(launch_batch_step(b, P, 1, main_stream(b)));
-  HB_HIP(hipMemcpyAsync(sensor_out, b->d_sensor_out, (size_t)b->n_env * P.sensor_stride * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
+  HB_HIP(hipMemcpyAsync(sensor_out, b->d_sensor_out, (size_t)b->n_env * P.sensor.row.stride * sizeof(float), hipMemcpyDeviceToHost, main_stream(b)));
   HB_HIP(hipStreamSynchronize(main_stream(b)));
   return HB_OK;
 }

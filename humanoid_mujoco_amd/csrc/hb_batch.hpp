@@ -431,6 +431,7 @@ int alloc_body_acc_readout(hb_batch* b);
 int reset_impl(hb_batch* b, const uint8_t* mask, int keyframe, float perturb_scale, int env_offset);
 bool staged_on(const hb_batch* b);
 BatchPtrs make_ptrs(hb_batch* b);
+int sensor_args(const Model& m, const DevModel& dm, const hb_sensor_spec* spec, int tail, SensorArgs& S);  // (hb_api_rollout.cpp)
 void join_pipes(hb_batch* b);
 int flush_steps(hb_batch* b);
 hipStream_t main_stream(hb_batch* b);

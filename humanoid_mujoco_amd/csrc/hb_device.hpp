@@ -601,6 +601,75 @@ __host__ __device__ inline int pose_lds_floats(int nq, int nb, int ngeom) {
   return ((nq + 3) & ~3) + 12 * nb + 2 * ((3 * ngeom + 3) & ~3) + 4 * ngeom + kListMax * 5 + kWorkMax;
 }
 
+// The layout of a row of the step kernel's sensor read-out, stated once:
+//   [ framepos (3 each) | subtreecom, subtreelinvel of one tree (6) | frame axes (3 each) | framelinvel (3 each) | subtreelinvel (3 each)
+//     | touch (1 each) | contact force (3 each) | accelerometer, gyro (6 each) | frameangacc, framelinacc (6 each) | qpos? | qvel? | ctrl? ]
+// Offsets in floats; n_*: a sensor part's entries (hb_sensor_spec's counts; n_subtree 1 or 0), a tail part's floats (nq, nv, nu or 0).
+// A part that is off has count 0 (its offset is then where it would begin).  `width` is what hb_sensor_size returns, `stride` the distance
+// between two rows.  sensor_row() computes it from the few facts that determine it; the step kernel, the host, the task rollouts,
+// hb_sensor_row (include/hb.h: the same layout up to `width`) and Batch.sensor_layout read it.
+struct SensorRow {
+  int framepos, n_framepos, subtree, n_subtree, axis, n_axis, linvel, n_linvel, sub, n_sub;  // offset, count of each part; framepos at 0
+  int touch, n_touch, cfrc, n_cfrc, imu, n_imu, facc, n_facc;
+  int width;
+  int qpos, n_qpos, qvel, n_qvel, ctrl, n_ctrl;
+  int stride;
+};
+constexpr int kSensorQvel = 1, kSensorCtrl = 2, kSensorQpos = 4;  // the tail parts a caller asks for
+__host__ __device__ inline SensorRow sensor_row(int n_framepos, bool tree, int n_axis, int n_linvel, int n_sub, int n_touch, int n_cfrc, int n_imu, int n_facc,
+                                                int tail, int nq, int nv, int nu) {
+  SensorRow r;
+  r.framepos = 0; r.n_framepos = n_framepos;
+  r.subtree = r.framepos + 3 * r.n_framepos; r.n_subtree = tree ? 1 : 0;
+  r.axis = r.subtree + 6 * r.n_subtree; r.n_axis = n_axis;
+  r.linvel = r.axis + 3 * r.n_axis; r.n_linvel = n_linvel;
+  r.sub = r.linvel + 3 * r.n_linvel; r.n_sub = n_sub;
+  r.touch = r.sub + 3 * r.n_sub; r.n_touch = n_touch;
+  r.cfrc = r.touch + r.n_touch; r.n_cfrc = n_cfrc;
+  r.imu = r.cfrc + 3 * r.n_cfrc; r.n_imu = n_imu;
+  r.facc = r.imu + 6 * r.n_imu; r.n_facc = n_facc;
+  r.width = r.facc + 6 * r.n_facc;
+  r.qpos = r.width; r.n_qpos = (tail & kSensorQpos) ? nq : 0;
+  r.qvel = r.qpos + r.n_qpos; r.n_qvel = (tail & kSensorQvel) ? nv : 0;
+  r.ctrl = r.qvel + r.n_qvel; r.n_ctrl = (tail & kSensorCtrl) ? nu : 0;
+  r.stride = r.ctrl + r.n_ctrl;
+  return r;
+}
+// The same row from its counts alone.  The step kernel addresses a row this way: it reads every second word of the record, one scalar
+// register each, where neighbouring words would be fetched as 8- and 16-register tuples that leave spill slots in the kernel's frame.
+__host__ __device__ inline SensorRow sensor_row(const SensorRow& c) {
+  return sensor_row(c.n_framepos, c.n_subtree != 0, c.n_axis, c.n_linvel, c.n_sub, c.n_touch, c.n_cfrc, c.n_imu, c.n_facc,
+                    (c.n_qpos ? kSensorQpos : 0) | (c.n_qvel ? kSensorQvel : 0) | (c.n_ctrl ? kSensorCtrl : 0), c.n_qpos, c.n_qvel, c.n_ctrl);
+}
+// N body ids, four to a word: a body is a lane of the step kernel, so an id fits a byte (whole words: the kernel reads an entry of a
+// table in its arguments with one scalar load)
+template <int N> struct BodyIds {
+  unsigned w[(N + 3) / 4];
+  __host__ __device__ int operator[](int k) const { return (w[k >> 2] >> (8 * (k & 3))) & 0xff; }
+  void set(int k, int id) { w[k >> 2] |= (unsigned)id << (8 * (k & 3)); }  // (of a zeroed table)
+};
+// The sensor read-out of a launch (hb_rollout_sensors, hb_sensors, the task rollouts), by value in BatchPtrs: where the rows go, their
+// layout and the table of every part (filled by sensor_args, hb_api_rollout.cpp).  out null: no read-out, and nothing else of it is
+// read.  (BatchPtrs is compared byte for byte: filled in zeroed memory, as the rest of it.)
+struct SensorArgs {
+  float* out;                     // [T][n_env][row.stride]
+  unsigned long long submask[4];  // subtreelinvel entry k: bit b = body b belongs to that subtree ...
+  SensorRow row;
+  int tree;                       // the tree whose subtreecom / subtreelinvel are read (when row.n_subtree)
+  float subinv[4];                // ... and 1 / the subtree's mass
+  float off[16][3];               // framepos of a site: offset in the body frame (zero: the body frame itself)
+  float imu_off[4][3];            // accelerometer / gyro: the site's offset in the body frame
+  int body[16];                   // framepos
+  int axis_body[8];               // framexaxis / framezaxis of a body frame (objtype xbody) ...
+  unsigned axis_which;            // ... two bits per entry: 0 the x axis, 2 the z axis
+  int linvel_body[8];             // framelinvel, objtype body: velocity of the inertial frame origin, world axes
+  BodyIds<8> touch_body;            // the normal-force sum of a body's contacts
+  BodyIds<4> cfrc_body;             // the force part of a body's contact wrench
+  BodyIds<4> imu_body;              // accelerometer[3] | gyro[3] at body frame + offset, in the body's axes
+  BodyIds<4> facc_body;             // frameangacc[3] | framelinacc[3] of a body: its row of body_acc
+};
+static_assert(__is_trivially_copyable(SensorArgs), "BatchPtrs is copied and compared byte for byte");
+
 // most step calls one launch executes (the calls the host enqueued back to back, hb_batch.cpp fold_steps)
 constexpr int kFoldMax = 256;
 struct BatchPtrs {
@@ -628,18 +697,7 @@ struct BatchPtrs {
   const int* order2;   // [n_env] nullable: the same for the narrowphase launch of a staged step, by the cost of its waves (counts[..][7])
   const float* dr;     // nullable [n_env][dr_stride]: per-env model parameters (DomainLayout)
   int dr_stride;
-  // sensor read-out (hb_rollout_sensors), nullable: [T][n_env][sensor_stride] = framepos of sensor_body[0..n) | subtreecom | subtreelinvel of tree sensor_tree
-  float* sensor_out;
-  int sensor_stride, sensor_nframe, sensor_tree;  // sensor_tree < 0: no subtree sensors
-  int sensor_body[16];
-  float sensor_off[16][3];  // framepos of a site: offset in the body frame (zero: the body frame itself)
-  int sensor_flags;         // bit 0: append qvel[nv], bit 1: append ctrl[nu], bit 2: append qpos[nq] (the inputs MJPC residuals read beside sensors)
-  // further read-outs, appended in this order behind framepos / subtreecom / subtreelinvel:
-  int sensor_naxis, sensor_axis_body[8], sensor_axis_which[8];  // framexaxis (0) / framezaxis (2) of a body frame (objtype xbody)
-  int sensor_nlinvel, sensor_linvel_body[8];                     // framelinvel, objtype body: velocity of the inertial frame origin, world axes
-  int sensor_nsub;                                               // subtreelinvel of further bodies (any body, not only a tree root)
-  unsigned long long sensor_submask[4];                          //   bit b: body b belongs to that subtree
-  float sensor_subinv[4];                                        //   1 / subtree mass
+  SensorArgs sensor;  // the sensor read-out (sensor.out nullable)
   const unsigned char* env_mask;  // nullable [n_env]: envs with a zero byte are skipped by this launch
   unsigned long long* stamps;  // diagnostic builds (-DHB_STAMPS) only: [n_env][16] s_memtime stamps of the last step
   int lean_ok;                // bit 0: the model's options allow the lean instantiations (mjOption.disableflags == 0); bit 1: its sizes and LDS
@@ -660,23 +718,12 @@ struct BatchPtrs {
   float* contact_force;
   float* body_contact;
   int cfrc_ncon;
-  // ... and their sensor entries, behind every other read-out of a sensor row: the normal-force sum of a body's contacts (one float
-  // each), then the force part of a body's contact wrench (three floats each)
-  int sensor_ntouch, sensor_touch_body[8];
-  int sensor_ncfrc, sensor_cfrc_body[4];
   // body-acceleration read-out (hb_body_acc_readout), both null or both set: [n_env][nbody][6] = angular | linear acceleration of the
   // body's xipos, world axes, gravity pseudo-acceleration included; and the scratch the step kernel parks what the read-out needs of the
   // kinematics in, [n_env][nbody][kAccPark]: bias cacc[6] | cvel[6] | xipos - subtree_com[3] | xpos - subtree_com[3] | xquat[4] | -.
   // A launch that carries them takes the full kernel's instantiation with the read-out (step_body's ACC, hb_step.hip: the ACC rows of HB_KERNELS).
   float* body_acc;
   float* body_acc_park;
-  // ... and their sensor entries, behind the contact-force entries: accelerometer[3] | gyro[3] at body frame + offset in the body's
-  // axes (six floats each), then frameangacc[3] | framelinacc[3] of a body (six floats each: its row of body_acc)
-  int sensor_nimu, sensor_imu_body[4];
-  float sensor_imu_off[4][3];
-  int sensor_nfacc, sensor_facc_body[4];
-  int sensor_acc_off;  // where these entries begin in a sensor row (floats)
-  int sensor_behind;   // floats of a sensor row written behind the solver: the contact-force read-out's entries and these
 };
 // arguments of the kinematics read-out (hb_kin.hip; hb_kinematics*): n states, state k's qpos at qpos + k qpos_stride (the batch's state
 // records, or packed rows), qvel likewise (read only when body_vel is asked for); the outputs are nullable, layouts in include/hb.h

@@ -75,7 +75,7 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
   const float P_xfrc_scale = LEAN ? 0.f : P.xfrc_scale, P_xfrc_rate = LEAN ? 0.f : P.xfrc_rate;
   const auto P_xfrc_seed = P.xfrc_seed; const auto P_xfrc_call = P.xfrc_call;
   float* const P_qfrc_out = (LEAN == 1 || INV) ? nullptr : P.qfrc_out;  // (LEAN == 2: the lean kernel of the env adapter, whose reward reads the constraint forces)
-  float* const P_sensor_out = (LEAN || INV) ? nullptr : P.sensor_out;
+  float* const P_sensor_out = (LEAN || INV) ? nullptr : P.sensor.out;
   float* const P_qpos_out = (LEAN || INV) ? nullptr : P.qpos_out;
   float* const P_qvel_out = (LEAN || INV) ? nullptr : P.qvel_out;
   float* const P_diag_qacc = (LEAN || INV) ? nullptr : P.diag_qacc;
@@ -509,44 +509,44 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
       w[4] = {rx.y, rx.z, xq.x, xq.y};
       w[5] = {xq.z, xq.w, 0.f, 0.f};
     }
-    // sensor read-out for planner residuals (mj_sensorPos/Vel of framepos, subtreecom, subtreelinvel)
+    // sensor read-out (mj_sensorPos/Vel): the parts of a row that are known before the solver (SensorRow, hb_device.hpp), and its tail
     if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // (RK4: the sensors of mj_step are those of the first stage)
-      float* so = P_sensor_out + ((size_t)step * P.n_env + env) * P.sensor_stride;
-      for (int k = 0; k < P.sensor_nframe; k++) {
-        const int sb = P.sensor_body[k];
-        const V3 w = ld3(s_xpq + kXpqStride * sb) + qrot(ldq(s_xpq + kXpqStride * sb + 4), {P.sensor_off[k][0], P.sensor_off[k][1], P.sensor_off[k][2]});  // site = body frame + offset
-        if (lane < 3) so[3 * k + lane] = lane == 0 ? w.x : (lane == 1 ? w.y : w.z);
+      const SensorArgs& S = P.sensor;
+      const SensorRow R = sensor_row(S.row);
+      float* so = P_sensor_out + ((size_t)step * P.n_env + env) * R.stride;
+      for (int k = 0; k < R.n_framepos; k++) {
+        const int sb = S.body[k];
+        const V3 w = ld3(s_xpq + kXpqStride * sb) + qrot(ldq(s_xpq + kXpqStride * sb + 4), {S.off[k][0], S.off[k][1], S.off[k][2]});  // site = body frame + offset
+        if (lane < 3) so[R.framepos + 3 * k + lane] = lane == 0 ? w.x : (lane == 1 ? w.y : w.z);
       }
-      {
-        int o = 3 * P.sensor_nframe + (P.sensor_tree >= 0 ? 6 : 0);
-        for (int k = 0; k < P.sensor_naxis; k++, o += 3) {  // framexaxis / framezaxis: a column of the body's rotation
-          const V3 e = P.sensor_axis_which[k] == 0 ? V3{1.f, 0.f, 0.f} : V3{0.f, 0.f, 1.f};
-          const V3 a = qrot(ldq(s_xpq + kXpqStride * P.sensor_axis_body[k] + 4), e);
-          if (lane < 3) so[o + lane] = lane == 0 ? a.x : (lane == 1 ? a.y : a.z);
-        }
-        for (int k = 0; k < P.sensor_nlinvel; k++, o += 3) {  // mj_objectVelocity at the inertial frame origin, world axes
-          const int sb = P.sensor_linvel_body[k];
-          const float* cv = s_va + 12 * sb;
-          const V3 v = V3{cv[3], cv[4], cv[5]} + cross(V3{cv[0], cv[1], cv[2]}, ld3(s_xipos + 3 * sb) - ld3(s_scom + 3 * M.body_treeid[sb]));
-          if (lane < 3) so[o + lane] = lane == 0 ? v.x : (lane == 1 ? v.y : v.z);
-        }
-        for (int k = 0; k < P.sensor_nsub; k++, o += 3) {  // mj_subtreeVel of a body's subtree: its linear momentum over its mass
-          V3 mom = {0.f, 0.f, 0.f};
-          if (bl && ((P.sensor_submask[k] >> myb) & 1ull)) {
-            const V3 ang = {mycvel[0], mycvel[1], mycvel[2]}, lin = {mycvel[3], mycvel[4], mycvel[5]};
-            mom = (lin + cross(ang, ld3(s_xipos + 3 * myb) - ld3(s_scom + 3 * __float_as_int(q1.y)))) * mymass;
-          }
-          const float im = P.sensor_subinv[k];
-          const float vx = wave_sum(mom.x) * im, vy = wave_sum(mom.y) * im, vz = wave_sum(mom.z) * im;
-          if (lane < 3) so[o + lane] = lane == 0 ? vx : (lane == 1 ? vy : vz);
-        }
-        o += P.sensor_behind;  // (touch / contact-force and accelerometer / gyro / frame-acceleration entries: written behind the solver, by the two epilogues)
-        if (P.sensor_flags & 4) { for (int i = lane; i < nq; i += kGroup) so[o + i] = s_qpos[i]; o += nq; }
-        if (P.sensor_flags & 1) { for (int i = lane; i < nv; i += kGroup) so[o + i] = s_qvel[i]; o += nv; }
-        if (P.sensor_flags & 2) for (int i = lane; i < HB_SZ(nu); i += kGroup) so[o + i] = s_ctrl[i];
+      int o = R.axis;  // (axes, framelinvel and subtreelinvel follow one another in a row: one running offset for the three loops)
+      for (int k = 0; k < R.n_axis; k++, o += 3) {  // framexaxis / framezaxis: a column of the body's rotation
+        const V3 e = ((S.axis_which >> (2 * k)) & 3) == 0 ? V3{1.f, 0.f, 0.f} : V3{0.f, 0.f, 1.f};
+        const V3 a = qrot(ldq(s_xpq + kXpqStride * S.axis_body[k] + 4), e);
+        if (lane < 3) so[o + lane] = lane == 0 ? a.x : (lane == 1 ? a.y : a.z);
       }
-      if (P.sensor_tree >= 0) {
-        const int t = P.sensor_tree;
+      for (int k = 0; k < R.n_linvel; k++, o += 3) {  // mj_objectVelocity at the inertial frame origin, world axes
+        const int sb = S.linvel_body[k];
+        const float* cv = s_va + 12 * sb;
+        const V3 v = V3{cv[3], cv[4], cv[5]} + cross(V3{cv[0], cv[1], cv[2]}, ld3(s_xipos + 3 * sb) - ld3(s_scom + 3 * M.body_treeid[sb]));
+        if (lane < 3) so[o + lane] = lane == 0 ? v.x : (lane == 1 ? v.y : v.z);
+      }
+      for (int k = 0; k < R.n_sub; k++, o += 3) {  // mj_subtreeVel of a body's subtree: its linear momentum over its mass
+        V3 mom = {0.f, 0.f, 0.f};
+        if (bl && ((S.submask[k] >> myb) & 1ull)) {
+          const V3 ang = {mycvel[0], mycvel[1], mycvel[2]}, lin = {mycvel[3], mycvel[4], mycvel[5]};
+          mom = (lin + cross(ang, ld3(s_xipos + 3 * myb) - ld3(s_scom + 3 * __float_as_int(q1.y)))) * mymass;
+        }
+        const float im = S.subinv[k];
+        const float vx = wave_sum(mom.x) * im, vy = wave_sum(mom.y) * im, vz = wave_sum(mom.z) * im;
+        if (lane < 3) so[o + lane] = lane == 0 ? vx : (lane == 1 ? vy : vz);
+      }
+      // (the touch / contact-force and accelerometer / gyro / frame-acceleration parts are written behind the solver, by the two epilogues)
+      if (R.n_qpos) for (int i = lane; i < nq; i += kGroup) so[R.qpos + i] = s_qpos[i];
+      if (R.n_qvel) for (int i = lane; i < nv; i += kGroup) so[R.qvel + i] = s_qvel[i];
+      if (R.n_ctrl) for (int i = lane; i < HB_SZ(nu); i += kGroup) so[R.ctrl + i] = s_ctrl[i];
+      if (R.n_subtree) {
+        const int t = S.tree;
         const V3 com = ld3(s_scom + 3 * t);
         // mj_subtreeVel for a whole tree: linear momentum over mass; a body's com moves with lin + ang x (xipos - com)
         V3 mom = {0.f, 0.f, 0.f};
@@ -557,8 +557,8 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
         const float im = M.tree_invmass[t];
         const float vx = wave_sum(mom.x) * im, vy = wave_sum(mom.y) * im, vz = wave_sum(mom.z) * im;
         if (lane < 3) {
-          so[3 * P.sensor_nframe + lane] = lane == 0 ? com.x : (lane == 1 ? com.y : com.z);
-          so[3 * P.sensor_nframe + 3 + lane] = lane == 0 ? vx : (lane == 1 ? vy : vz);
+          so[R.subtree + lane] = lane == 0 ? com.x : (lane == 1 ? com.y : com.z);
+          so[R.subtree + 3 + lane] = lane == 0 ? vx : (lane == 1 ? vy : vz);
         }
       }
     }
@@ -2016,11 +2016,13 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
           }
         }
         w[0] = Fs.x; w[1] = Fs.y; w[2] = Fs.z; w[3] = Ts.x; w[4] = Ts.y; w[5] = Ts.z;
-        if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // touch / contact-force entries, behind every other read-out of the row
-          float* so = P_sensor_out + ((size_t)step * P.n_env + env) * P.sensor_stride + 3 * (P.sensor_nframe + P.sensor_naxis + P.sensor_nlinvel + P.sensor_nsub) + (P.sensor_tree >= 0 ? 6 : 0);
-          for (int k = 0; k < P.sensor_ntouch; k++) if (P.sensor_touch_body[k] == lane) so[k] = touch;
-          so += P.sensor_ntouch;
-          for (int k = 0; k < P.sensor_ncfrc; k++) if (P.sensor_cfrc_body[k] == lane) { so[3 * k] = Fs.x; so[3 * k + 1] = Fs.y; so[3 * k + 2] = Fs.z; }
+        if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // the touch / contact-force parts of the sensor row
+          const SensorArgs& S = P.sensor;
+          const SensorRow R = sensor_row(S.row);
+          float* so = P_sensor_out + ((size_t)step * P.n_env + env) * R.stride;
+          for (int k = 0; k < R.n_touch; k++) if (S.touch_body[k] == lane) so[R.touch + k] = touch;
+          so += R.cfrc;
+          for (int k = 0; k < R.n_cfrc; k++) if (S.cfrc_body[k] == lane) { so[3 * k] = Fs.x; so[3 * k + 1] = Fs.y; so[3 * k + 2] = Fs.z; }
         }
       }
       gsync();
@@ -2051,20 +2053,22 @@ __device__ __forceinline__ void step_body(const DevModel* Mp, const BatchPtrs& P
         const V3 li = ac + cross(al, ri) + cross(om, vc + cross(om, ri));
         float* w = P_bacc + ((size_t)env * nb + lane) * 6;
         w[0] = al.x; w[1] = al.y; w[2] = al.z; w[3] = li.x; w[4] = li.y; w[5] = li.z;
-        if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // behind the contact-force entries of the row
-          float* so = P_sensor_out + ((size_t)step * P.n_env + env) * P.sensor_stride + P.sensor_acc_off;
-          const int nimu = P.sensor_nimu, nfacc = P.sensor_nfacc;
-          for (int k = 0; k < nimu; k++)
-            if (P.sensor_imu_body[k] == lane) {  // a site with the body's orientation: the point's acceleration and the angular velocity in its axes
+        if (P_sensor_out && (INTEG == 0 || stage == 0)) {  // the accelerometer / gyro and frame-acceleration parts of the sensor row
+          const SensorArgs& S = P.sensor;
+          const SensorRow R = sensor_row(S.row);
+          float* const row = P_sensor_out + ((size_t)step * P.n_env + env) * R.stride;
+          float* so = row + R.imu;
+          for (int k = 0; k < R.n_imu; k++)
+            if (S.imu_body[k] == lane) {  // a site with the body's orientation: the point's acceleration and the angular velocity in its axes
               const Q4 q = {k4.z, k4.w, k5.x, k5.y};
               const Q4 qc = {q.w, -q.x, -q.y, -q.z};
-              const V3 r = rx + qrot(q, {P.sensor_imu_off[k][0], P.sensor_imu_off[k][1], P.sensor_imu_off[k][2]});
+              const V3 r = rx + qrot(q, {S.imu_off[k][0], S.imu_off[k][1], S.imu_off[k][2]});
               const V3 acc = qrot(qc, ac + cross(al, r) + cross(om, vc + cross(om, r))), gy = qrot(qc, om);
               so[6 * k] = acc.x; so[6 * k + 1] = acc.y; so[6 * k + 2] = acc.z; so[6 * k + 3] = gy.x; so[6 * k + 4] = gy.y; so[6 * k + 5] = gy.z;
             }
-          so += 6 * nimu;
-          for (int k = 0; k < nfacc; k++)
-            if (P.sensor_facc_body[k] == lane) { so[6 * k] = al.x; so[6 * k + 1] = al.y; so[6 * k + 2] = al.z; so[6 * k + 3] = li.x; so[6 * k + 4] = li.y; so[6 * k + 5] = li.z; }
+          so = row + R.facc;
+          for (int k = 0; k < R.n_facc; k++)
+            if (S.facc_body[k] == lane) { so[6 * k] = al.x; so[6 * k + 1] = al.y; so[6 * k + 2] = al.z; so[6 * k + 3] = li.x; so[6 * k + 4] = li.y; so[6 * k + 5] = li.z; }
         }
       }
     }
@@ -2415,7 +2419,7 @@ static bool duo_pays(const BatchPtrs& P, int nsteps) {
 
 // the lean instantiations apply when the launch has none of the optional inputs / outputs (BatchPtrs::lean_ok bit 0, HB_TUNE_LEAN)
 static bool lean_launch(const BatchPtrs& P, bool with_qfrc = false) {
-  return (P.lean_ok & 1) && !P.xfrc && (with_qfrc || !P.qfrc_out) && !P.sensor_out && !P.qpos_out && !P.qvel_out && !P.diag_qacc && !P.diag_force && !P.diag_contact && !P.contact_force && !P.body_acc && !P.dr && !P.env_mask &&
+  return (P.lean_ok & 1) && !P.xfrc && (with_qfrc || !P.qfrc_out) && !P.sensor.out && !P.qpos_out && !P.qvel_out && !P.diag_qacc && !P.diag_force && !P.diag_contact && !P.contact_force && !P.body_acc && !P.dr && !P.env_mask &&
          P.integrate;
 }
 
@@ -2508,7 +2512,7 @@ hipError_t launch_step(const DevModel* M_dev, const DevModel& M, const BatchPtrs
     if (P.ctrl_mode == 1) Q.ctrl = P.ctrl + (size_t)t * P.n_env * P.stage.nu;
     if (P.qpos_out) Q.qpos_out = P.qpos_out + (size_t)t * P.n_env * P.stage.nq;
     if (P.qvel_out) Q.qvel_out = P.qvel_out + (size_t)t * P.n_env * P.stage.nv;
-    if (P.sensor_out) Q.sensor_out = P.sensor_out + (size_t)t * P.n_env * P.sensor_stride;
+    if (P.sensor.out) Q.sensor.out = P.sensor.out + (size_t)t * P.n_env * P.sensor.row.stride;
     hipError_t e = launch_pose_narrow(M_dev, Q, stream);  // (hb_narrow.hip)
     if (e != hipSuccess) return e;
     // The fast pass, then the variant's own kernel for what it deferred.  Variant 1: the step kernel without the portal-search code; the

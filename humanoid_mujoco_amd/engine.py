@@ -153,7 +153,8 @@ class HbCostSpec(ctypes.Structure):
 
 
 class HbSensorSpec(ctypes.Structure):
-    """hb_sensor_spec (include/hb.h): framepos bodies and the tree whose subtreecom / subtreelinvel are read out."""
+    """hb_sensor_spec (include/hb.h): the entries of every part of a sensor row - framepos, one tree's subtreecom / subtreelinvel, frame axes,
+    framelinvel, subtreelinvel, touch, contact force, accelerometer / gyro, frame acceleration (Batch.sensor_spec fills it)."""
     _fields_ = [("n_framepos", ctypes.c_int), ("framepos_body", ctypes.c_int * 16), ("subtree_body", ctypes.c_int),
                 ("framepos_offset", (ctypes.c_float * 3) * 16),
                 ("n_frameaxis", ctypes.c_int), ("frameaxis_body", ctypes.c_int * 8), ("frameaxis_which", ctypes.c_int * 8),
@@ -163,6 +164,14 @@ class HbSensorSpec(ctypes.Structure):
                 ("n_contactforce", ctypes.c_int), ("contactforce_body", ctypes.c_int * 4),
                 ("n_imu", ctypes.c_int), ("imu_body", ctypes.c_int * 4), ("imu_offset", (ctypes.c_float * 3) * 4),
                 ("n_frameacc", ctypes.c_int), ("frameacc_body", ctypes.c_int * 4)]
+
+
+SENSOR_PARTS = ("framepos", "subtree", "axis", "linvel", "sub", "touch", "cfrc", "imu", "facc")  # the parts of a sensor row, in its order
+
+
+class HbSensorRow(ctypes.Structure):
+    """struct hb_sensor_row (include/hb.h): offset (floats) and count (entries) of every part of a sensor row, and its width."""
+    _fields_ = [(f, ctypes.c_int) for n in SENSOR_PARTS for f in (n, "n_" + n)] + [("width", ctypes.c_int)]
 
 
 class HbDomainRandomization(ctypes.Structure):
@@ -415,6 +424,7 @@ def lib():
     L.hb_state_to_proto.argtypes = [vp, ci, vp, ci]
     L.hb_state_from_proto.argtypes = [vp, ci, cp, ci]
     L.hb_sensor_size.argtypes = [ctypes.POINTER(HbSensorSpec)]
+    L.hb_sensor_row.argtypes = [ctypes.POINTER(HbSensorSpec), ctypes.POINTER(HbSensorRow)]
     L.hb_set_state_broadcast.argtypes = [vp, cu, vp]
     L.hb_set_state_broadcast_f64.argtypes = [vp, cu, vp]
     L.hb_rollout_sensors.argtypes = [vp, vp, ci, ctypes.POINTER(HbSensorSpec), vp, vp]
@@ -1150,6 +1160,24 @@ class Batch:
             sp.frameacc_body[k] = int(bd)
         return sp
 
+    @staticmethod
+    def _sensor_size(spec):
+        ns = lib().hb_sensor_size(ctypes.byref(spec))
+        if ns <= 0:
+            raise HbError("hb_sensor_size: invalid sensor spec")
+        return ns
+
+    @staticmethod
+    def sensor_layout(spec):
+        """where each part of a row of `spec` is: {part: (offset, floats)} for SENSOR_PARTS (a part that is off: 0 floats), and "width"
+        (hb_sensor_row; the floats of a part end where the next part begins)"""
+        r = HbSensorRow()
+        _check(lib().hb_sensor_row(ctypes.byref(spec), ctypes.byref(r)), "hb_sensor_row")
+        ends = [getattr(r, n) for n in SENSOR_PARTS[1:]] + [r.width]
+        out = {n: (getattr(r, n), end - getattr(r, n)) for n, end in zip(SENSOR_PARTS, ends)}
+        out["width"] = r.width
+        return out
+
     def set_state_broadcast(self, spec, state):
         """One state record on every env (the common start of a sampling planner's candidates)."""
         s = np.ascontiguousarray(state)
@@ -1164,9 +1192,7 @@ class Batch:
         c = np.ascontiguousarray(ctrl, dtype=np.float32)
         T = c.shape[0]
         assert c.shape == (T, self.n_env, self.model.nu), c.shape
-        ns = lib().hb_sensor_size(ctypes.byref(spec))
-        if ns <= 0:
-            raise HbError("hb_sensor_size: invalid sensor spec")
+        ns = self._sensor_size(spec)
         out = np.zeros((T, self.n_env, ns), dtype=np.float32)
         q = np.zeros((T, self.n_env, self.model.nq), dtype=np.float32) if want_qpos else None
         _check(lib().hb_rollout_sensors(self._h, _ptr(c), T, ctypes.byref(spec), _ptr(out), _ptr(q)), "hb_rollout_sensors")
@@ -1183,7 +1209,7 @@ class Batch:
         if sensor_spec is None:
             _check(lib().hb_transition_fd(self._h, _ptr(xs), _ptr(us), _ptr(w), T, float(eps), int(bool(centered)), _ptr(A), _ptr(B)), "hb_transition_fd")
             return A, B
-        ns = lib().hb_sensor_size(ctypes.byref(sensor_spec))
+        ns = lib().hb_sensor_size(ctypes.byref(sensor_spec))  # (not _sensor_size: a spec it refuses has always ended in np.zeros' ValueError here)
         C = np.zeros((T, ns, 2 * nv)); D = np.zeros((T, ns, nu))
         _check(lib().hb_transition_fd_sensors(self._h, _ptr(xs), _ptr(us), _ptr(w), T, float(eps), int(bool(centered)), ctypes.byref(sensor_spec),
                                               _ptr(A), _ptr(B), _ptr(C), _ptr(D)), "hb_transition_fd_sensors")
@@ -1271,9 +1297,7 @@ class Batch:
         return q, v, f.astype(bool)
 
     def sensors(self, spec, ctrl=None):
-        ns = lib().hb_sensor_size(ctypes.byref(spec))
-        if ns <= 0:
-            raise HbError("hb_sensor_size: invalid sensor spec")
+        ns = self._sensor_size(spec)
         out = np.zeros((self.n_env, ns), dtype=np.float32)
         c = None if ctrl is None else np.ascontiguousarray(ctrl, dtype=np.float32)
         rc = lib().hb_sensors(self._h, _ptr(c), ctypes.byref(spec), _ptr(out))

@@ -376,10 +376,13 @@ int hb_state_from_proto(hb_batch* b, int env, const unsigned char* buf, int len)
 
 /* ---- planner rollouts (MJPC's Trajectory::Rollout, mujoco_mpc/mjpc/trajectory.cc:100-210) -------------------- */
 
-/* The sensors MJPC's humanoid tasks build their residuals from (tasks/humanoid_cap/stand/task.xml:22-40): framepos of
- * up to 16 bodies or sites (a site is a body plus an offset in the body frame), and subtreecom / subtreelinvel (mj_subtreeVel, mujoco.h:346) of one kinematic tree, named by its root
- * body (a direct child of the world; < 0: none).  Per env and step the read-out is
- * [framepos 0 (3) | ... | subtreecom (3) | subtreelinvel (3) | further read-outs, in the order of the fields below], hb_sensor_size() floats. */
+/* The sensors MJPC's humanoid tasks build their residuals from (tasks/humanoid_cap/stand/task.xml:22-40), and the contact and
+ * acceleration sensors of a legged robot.  Per env and step the read-out is a row of hb_sensor_size() floats, its parts in the order of
+ * the fields below (hb_sensor_row names where each begins):
+ *   [ framepos (3 each) | subtreecom (3), subtreelinvel (3) | frame axes (3 each) | framelinvel (3 each) | subtreelinvel (3 each)
+ *     | touch (1 each) | contact force (3 each) | accelerometer, gyro (6 each) | frameangacc, framelinacc (6 each) ]
+ * framepos: up to 16 bodies or sites (a site is a body plus an offset in the body frame); subtreecom / subtreelinvel (mj_subtreeVel,
+ * mujoco.h:346): of one kinematic tree, named by its root body (a direct child of the world; < 0: none). */
 #define HB_MAX_FRAMEPOS 16
 typedef struct hb_sensor_spec {
   int n_framepos;
@@ -412,7 +415,23 @@ typedef struct hb_sensor_spec {
   int n_frameacc;             /* six floats each: frameangacc[3] | framelinacc[3], objtype body: row b of hb_get_body_acc */
   int frameacc_body[4];
 } hb_sensor_spec;
-int hb_sensor_size(const hb_sensor_spec* spec);
+int hb_sensor_size(const hb_sensor_spec* spec);  /* the width of a row; HB_EINVAL for NULL or a count outside [0, its array's length] */
+/* The layout of that row: the offset (floats) and the count (entries, as in the spec; subtree: 1 or 0) of each part, and the width.  A
+ * part that is off has count 0 and the offset at which it would begin.  Needs no batch; HB_EINVAL for NULL, for a spec hb_sensor_size
+ * refuses and for an empty one.  (The struct has no typedef: the function bears the name.) */
+struct hb_sensor_row {
+  int framepos, n_framepos;
+  int subtree, n_subtree;
+  int axis, n_axis;
+  int linvel, n_linvel;
+  int sub, n_sub;
+  int touch, n_touch;
+  int cfrc, n_cfrc;
+  int imu, n_imu;
+  int facc, n_facc;
+  int width;
+};
+int hb_sensor_row(const hb_sensor_spec* spec, struct hb_sensor_row* out);
 /* mj_setState of ONE state on every env: the N candidate action sequences of a sampling planner all start from the
  * current state (sampling/planner.cc:342-380).  `state` is one record of hb_state_size(b, spec) floats. */
 int hb_set_state_broadcast(hb_batch* b, unsigned spec, const float* state);

@@ -128,6 +128,9 @@ def test_sensor_rows_are_the_single_steps_getter(hbmod, gpu):
     m, o, st, _, _ = contact_ref.make_case(hbmod, "humanoid27_pgs", None)
     n, T = len(st), 3
     spec = hbmod.Batch.sensor_spec(framepos_bodies=(TORSO,), contactforce_bodies=(FOOT_R,), imu=IMUS, frameacc_bodies=FRAMEACC)
+    lay = hbmod.Batch.sensor_layout(spec)
+    CFRC, IMU, FACC = (slice(o, o + c) for o, c in (lay["cfrc"], lay["imu"], lay["facc"]))
+    assert (CFRC, IMU, FACC, lay["width"]) == (slice(3, 6), slice(6, 18), slice(18, 30), 30)
     ctrl = np.random.default_rng(3).uniform(-1, 1, (T, n, m.nu)).astype(np.float32)
     b = hbmod.Batch(m, n, gpu)
     b.set_state(hbmod.STATE_INTEGRATION, st)
@@ -147,19 +150,19 @@ def test_sensor_rows_are_the_single_steps_getter(hbmod, gpu):
         before = s.get_state(hbmod.STATE_INTEGRATION).astype(np.float64)
         s.step(ctrl[t])
         acc, qacc = s.body_acc(), s.qacc().astype(np.float64)
-        assert np.array_equal(rows[t, :, 18:30], acc[:, FRAMEACC].reshape(n, 12)), t
-        assert np.array_equal(rows[t, :, 3:6], s.body_contact()[:, FOOT_R, 0:3]), t
+        assert np.array_equal(rows[t, :, FACC], acc[:, FRAMEACC].reshape(n, 12)), t
+        assert np.array_equal(rows[t, :, CFRC], s.body_contact()[:, FOOT_R, 0:3]), t
         for k in range(n):
             load_state(o, before[k], ctrl[t, k].astype(np.float64))
             o.forward()
             a = acc_ref.cacc(o, qacc[k])
             ref = np.concatenate([acc_ref.imu(o, bd, off, a=a) for bd, off in IMUS])
-            worst = max(worst, float(np.abs(rows[t, k, 6:18] - ref).max()) / acc_ref.scale(acc_ref.body_acc(o, a=a)))
+            worst = max(worst, float(np.abs(rows[t, k, IMU] - ref).max()) / acc_ref.scale(acc_ref.body_acc(o, a=a)))
     print("\n  accelerometer / gyro entries against R' of the reference: %.2e" % worst)
     assert worst <= DECODE_BOUND, worst
     assert np.array_equal(s.get_state(hbmod.STATE_INTEGRATION), end)
     r = s.sensors(spec, ctrl[0])
-    assert np.array_equal(r[:, 18:30], s.body_acc()[:, FRAMEACC].reshape(n, 12)) and np.abs(r[:, 6:18]).max() > 0
+    assert np.array_equal(r[:, FACC], s.body_acc()[:, FRAMEACC].reshape(n, 12)) and np.abs(r[:, IMU]).max() > 0
     x = np.concatenate([s.qpos[:1], s.qvel[:1]], axis=1).astype(np.float64)
     eps, j = 1e-3, 6 + int(np.argmin(np.abs(x[0, m.nq + 6:])))  # the joint that moves slowest in this state
     C = s.transition_fd(x, ctrl[0, :1].astype(np.float64), eps=eps, centered=False, sensor_spec=spec)[2]  # (1 + 2 nv + nu = 76 envs of the 128)
@@ -176,7 +179,7 @@ def test_sensor_rows_are_the_single_steps_getter(hbmod, gpu):
     r = s.sensors(spec, np.repeat(ctrl[0, :1], n, axis=0)).astype(np.float64)
     fd = (r[1] - r[0]) / eps
     print("  transition_fd column of qvel[%d] against two hb_sensors rows: %.2e of max |column| %.3g" % (j, np.abs(C[0, :, m.nv + j] - fd).max() / max(1.0, np.abs(fd).max()), np.abs(fd).max()))
-    assert np.abs(fd[6:18]).max() > 0 and np.abs(fd[18:30]).max() > 0
+    assert np.abs(fd[IMU]).max() > 0 and np.abs(fd[FACC]).max() > 0
     assert np.abs(C[0, :, m.nv + j] - fd).max() <= 1e-3 * max(1.0, np.abs(fd).max())
     s.close()
 

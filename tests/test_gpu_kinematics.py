@@ -202,8 +202,9 @@ def test_agrees_with_the_sensors(hbmod, gpu, tmp_path_factory):
     kin = b.kinematics()
     b.close()
     pose, vel = kin["pose"].astype(np.float64), kin["vel"].astype(np.float64)
-    ns = sens.shape[1]
-    fpos, axes, linvel = sens[:, :48].reshape(-1, 16, 3), sens[:, ns - 48:ns - 24].reshape(-1, 8, 3), sens[:, ns - 24:].reshape(-1, 8, 3)
+    lay = hbmod.Batch.sensor_layout(spec)
+    fpos, axes, linvel = (sens[:, o:o + c].reshape(len(states), -1, 3) for o, c in (lay["framepos"], lay["axis"], lay["linvel"]))
+    assert (fpos.shape[1], axes.shape[1], linvel.shape[1], lay["width"]) == (16, 8, 8, sens.shape[1])
     zcol = hbmod.quat_to_mat(pose[:, :, 3:7])[:, :, :, 2]
     for k in range(len(states)):
         ps = max(1.0, np.abs(pose[k]).max())
